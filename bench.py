@@ -17,6 +17,11 @@ ranks timing, the one JSON line) on the gloo backend without touching a GPU: tes
 Besides the decode metric the default line carries `prefill` (TTFT as TFLOP/s against the MFMA peak) and `sft` (one warm + two timed
 NVILA-8B SFT steps, BASELINE configs[2] per-GPU workload) so that the MFMA-bound halves of the north star are driver-observed too,
 and `sustained` (a >= 2 s decode replay after the timed region, so that a 5-s GPU-busy sampler has something to see).
+
+`--dump-outputs DIR` writes what the last timed step computed, as a caller of that path would receive it, to DIR/<name>.npy (float32, or float64
+for ids; 64 MB at most): decode `last_logits` + `token_ids` (the prefill's token and every generated one), sft `loss` + `params_sample` (a fixed
+sample of the updated weights), video `last_logits` + `token_ids`.  Weights, pixels and prompts are seeded, so two builds run with the same
+arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -44,8 +49,8 @@ SFT_TFLOP_PER_SAMPLE = 35.8   # fwd+bwd of one 769-token sample (1 
 def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=128)
-    ap.add_argument("--warmup", type=int, default=16)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default: 128 in decode mode, 3 in sft and video mode)")
+    ap.add_argument("--warmup", type=int, default=None, help="untimed steps before them (default: 16 in decode mode, 1 in sft mode)")
     ap.add_argument("--prompt-tokens", type=int, default=512)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-sft", action="store_true", help="decode mode: skip the bounded SFT sub-measurement (1 warm + 2 timed steps)")
@@ -63,7 +68,43 @@ def parse(argv=None):
     ap.add_argument("--dynamic-s2", action="store_true", help="full NVILA-8B recipe: 14 tiles (448/896/1344) -> 2304 image tokens (SURVEY 8f row 1)")
     ap.add_argument("--batch", type=int, default=1, help="decode mode: sequences per weight pass (2..16 = the batched decode step, value = aggregate tokens/s)")
     ap.add_argument("--selftest", action="store_true", help="harness only (gloo, no GPU): rendezvous + barrier + max-over-ranks + JSON line")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32/float64, <= 64 MB in all)")
+    a = ap.parse_args(argv)
+    if a.steps is None:
+        a.steps = 3 if a.mode in ("sft", "video") else 128
+    if a.warmup is None:
+        a.warmup = 1 if a.mode == "sft" else 16
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """`--dump-outputs`: one DIR/<name>.npy per array, float32 (float64 for integer data, exact up to 2^53), 64 MB at most in all."""
+    import numpy as np
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach().cpu()
+        host[name] = (t.double() if not t.is_floating_point() or t.dtype == torch.float64 else t.float()).numpy()
+    total = sum(v.nbytes for v in host.values())
+    if total > DUMP_MAX_BYTES:
+        raise ValueError(f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte budget")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in host.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+
+
+def seeded_sample(flat: torch.Tensor, n: int, seed: int = 0) -> torch.Tensor:
+    """A fixed sample of `n` elements of a 1-D tensor: the same indices on every run with the same size (sorted, drawn on the CPU)."""
+    if flat.numel() <= n:
+        return flat
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    idx = torch.randint(0, flat.numel(), (n,), generator=g).sort().values
+    return flat[idx.to(flat.device)]
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -558,6 +599,8 @@ def sft_main(a, rank, world, dev, dist):
         cfg.name += "-dynamic-s2"
     model = build_model(cfg, seed=0, device=dev)
     elapsed, loss, S, tr = sft_measure(model, cfg, a, rank, dev, dist, a.steps, a.warmup)
+    if a.dump_outputs and rank == 0:           # the loss and a fixed 4M-element sample of the updated bf16 weights
+        dump_outputs(a.dump_outputs, {"loss": torch.tensor([loss], dtype=torch.float64), "params_sample": seeded_sample(tr.flat.params, 4 << 20)})
     if rank == 0:
         blk = sft_block(elapsed, a.steps, a.micro_batch, S, world, loss,
                         sft_flops_per_sample(cfg, S) / 1e12 if a.dynamic_s2 else SFT_TFLOP_PER_SAMPLE)
@@ -614,13 +657,18 @@ def video_main(a, rank, dev):
                                      last_rows=torch.tensor([S - 1], device=dev, dtype=torch.int32))
         first = int(ops.argmax(r.last_logits[0]))
         t2 = time.perf_counter()
+        last["logits"] = r.last_logits[0]
         return t1 - t0, t2 - t1, first
+    last = {}
     once()
-    ts = [once() for _ in range(max(a.steps if a.steps != 128 else 3, 1))]
+    ts = [once() for _ in range(a.steps)]
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, {"last_logits": last["logits"], "token_ids": torch.tensor([ts[-1][2]])})
     enc = statistics.median(t[0] for t in ts)
     pre = statistics.median(t[1] for t in ts)
     flops = vit_flops(cfg, F_) + projector_flops(cfg, F_) + llm_prefill_flops(cfg, S)
     print(json.dumps({"metric": "TTFT, NVILA-Video-8B-style prefill", "value": round((enc + pre) * 1e3, 2), "unit": "ms", "n_gpus": 1,
+                      "steps": a.steps, "ms_per_step": round(sum(t[0] + t[1] for t in ts) / len(ts) * 1e3, 4),
                       "higher_is_better": False, "dtype": "bf16", "data": "synthetic",
                       "config": {"workload": f"{F_} frames x 448^2 -> {S} tokens ({'TSPVideoEncoder pool [[8,1,1]]' if a.tsp else 'per-frame <image> tokens'}), batch 1"},
                       "encode_ms": round(enc * 1e3, 2), "llm_prefill_ms": round(pre * 1e3, 2),
@@ -663,6 +711,8 @@ def batch_decode_main(a, rank, world, dev, dist):
         for _ in range(a.warmup):
             one()
         elapsed = timed_region(dist, dev, a.steps, one, torch.cuda.synchronize)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"last_logits": st.logits, "token_ids": st.out_ids[:, :a.warmup + a.steps]})   # [B, V] fp32, [B, n]
     if rank == 0:
         step_s = elapsed / a.steps
         byt = decode_bytes_per_token(cfg, S + a.warmup + a.steps // 2) + (Bn - 1) * 2 * cfg.llm.kv_size * 2 * cfg.llm.num_hidden_layers * (S + a.warmup + a.steps // 2)
@@ -785,6 +835,9 @@ def decode_main(a, rank, world, dev, dist):
     assert n_generated == a.warmup + a.steps, (n_generated, a.warmup, a.steps)
     chain_err = int(lib.vila_llm_decode_chain_error(st.ws.data_ptr(), stream.cuda_stream))
     assert chain_err == 0, "chained decode step: a bounded wait gave up — the timed tokens are invalid"
+    if a.dump_outputs and rank == 0:           # before the sustained replay below overwrites the session
+        dump_outputs(a.dump_outputs, {"last_logits": st.logits,                                          # [V] fp32, the last timed step's
+                                      "token_ids": torch.cat([torch.tensor([first]), st.out_ids[:n_generated].cpu()])})   # prefill's + every step's
     chained = os.environ.get("VILA_DECODE_CHAIN", "0") == "1" and not a.w4 and cache.max_ctx <= 2048
     ctx_mid = S + a.warmup + a.steps // 2
     step_bytes = decode_bytes_per_token(cfg, ctx_mid, a.w4)
@@ -940,8 +993,6 @@ def main(argv=None):
     if a.mode == "video":
         return video_main(a, rank, dev)
     if a.mode == "sft":
-        if a.steps == 128 and a.warmup == 16:
-            a.steps, a.warmup = 3, 1
         return sft_main(a, rank, world, dev, dist)
     return decode_main(a, rank, world, dev, dist)
 

@@ -95,3 +95,42 @@ def test_deadline_guard_prints_the_decode_line_and_exits_when_the_side_measureme
     g = bench.Deadline(0.05, None, _exit=codes.append)              # a rank other than 0: exits quietly
     time.sleep(0.4)
     assert codes == [0, 0] and capsys.readouterr().out == ""
+
+
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+def test_steps_and_warmup_are_taken_as_given_in_every_mode():
+    """--steps sets the number of timed steps: an explicit value is never replaced by a mode's own default."""
+    bench = _bench_module()
+    for mode in ("decode", "sft", "video"):
+        a = bench.parse(["--mode", mode, "--steps", "128", "--warmup", "16"])
+        assert (a.steps, a.warmup) == (128, 16), mode
+    assert (bench.parse([]).steps, bench.parse([]).warmup) == (128, 16)
+    assert (bench.parse(["--mode", "sft"]).steps, bench.parse(["--mode", "sft"]).warmup) == (3, 1)
+    assert bench.parse(["--mode", "video"]).steps == 3
+
+
+def test_dump_outputs_writes_float_arrays_within_the_budget(tmp_path):
+    import numpy as np
+    import pytest
+    import torch
+    bench = _bench_module()
+    logits = torch.randn(1000, dtype=torch.float32)
+    ids = torch.tensor([3, 2 ** 40 + 1, 7], dtype=torch.int64)
+    bench.dump_outputs(str(tmp_path / "out"), {"last_logits": logits, "token_ids": ids, "h": logits.to(torch.bfloat16)})
+    got = {n: np.load(tmp_path / "out" / f"{n}.npy") for n in ("last_logits", "token_ids", "h")}
+    assert got["last_logits"].dtype == np.float32 and np.array_equal(got["last_logits"], logits.numpy())
+    assert got["token_ids"].dtype == np.float64 and got["token_ids"].tolist() == [3.0, float(2 ** 40 + 1), 7.0]
+    assert got["h"].dtype == np.float32
+    with pytest.raises(ValueError):
+        bench.dump_outputs(str(tmp_path / "big"), {"x": torch.zeros((64 << 20) // 4 + 1)})
+    assert not (tmp_path / "big").exists()
+    flat = torch.arange(10 ** 6, dtype=torch.float32)
+    a, b = bench.seeded_sample(flat, 1000), bench.seeded_sample(flat, 1000)
+    assert a.shape == (1000,) and torch.equal(a, b) and bool((a[1:] >= a[:-1]).all())
