@@ -1,7 +1,7 @@
 /* vila_hip_tuning.h — tuning and test switches of libvila_hip.so.  NOT part of the drop-in boundary (include/vila_hip.h):
  * these are PROCESS-GLOBAL, not thread-safe, and exist for the A/B measurements under tools/ and for the parity tests that pin one
  * kernel variant (tests/test_gpu_ops.py).  A product binding never calls them; every switch defaults to the measured-best policy.
- * Environment equivalents read once at first use: VILA_GEMM_EX, VILA_ATTN_FWD=v1, VILA_ATTN_BWD=v1, VILA_DECODE_ATTN, VILA_DECODE_CHAIN, VILA_DECODE_PERSIST. */
+ * Environment equivalents read once at first use: VILA_GEMM_EX, VILA_ATTN_FWD=v1, VILA_ATTN_KS, VILA_ATTN_BWD=v1, VILA_DECODE_ATTN, VILA_DECODE_CHAIN, VILA_DECODE_PERSIST. */
 #ifndef VILA_HIP_TUNING_H
 #define VILA_HIP_TUNING_H
 #ifdef __cplusplus
@@ -50,6 +50,15 @@ void vila_norm_force_lat(int on);
  * K-sliced with the post-attention RMSNorm in its reduce (instead of ring GEMM + norm launch); both only where the grid is K-sliced at all
  * (>= 512 rows).  -1 = the environment's choice (VILA_PREFILL_QKV_SPLITK / VILA_PREFILL_OPROJ_SPLITK, default on), 0 = off, 1 = on */
 void vila_prefill_force_fusions(int qkv_rope, int oproj_norm);
+/* test hook of the attention forward (attn.hip): 0 = automatic (the policy below plus VILA_ATTN_FWD / VILA_ATTN_KS), or one form whatever the grid:
+ * 1 = A (256-row blocks, 32 rows per wave), 2 = B (64-row blocks, keys split two ways inside the block), 3 = C (128-row blocks, keys split two ways),
+ * 4 = D (128-row blocks, 16 rows per wave), 5 = the round-2 kernel (VILA_ATTN_FWD=v1).  Every form serves head dims 64, 72 and 128 */
+void vila_attn_force_fwd(int form);
+/* the form (1..5 as above) the automatic policy launches for this grid on the current device; host only, launches nothing */
+int vila_attn_fwd_form(int n_seq, int max_seqlen, int n_q_heads);
+/* test hook of the attention backward's dQ and dK / dV passes: 0 = VILA_ATTN_BWD from the environment (default: DMA), 1 = the round-1/2 kernels
+ * of attn_bwd.hip (VILA_ATTN_BWD=v1), 2 = the DMA-ring kernels of attn_bwd_dma.hip */
+void vila_attn_force_bwd(int impl);
 #ifdef __cplusplus
 }
 #endif

@@ -54,3 +54,54 @@ def margin_aware_ids(lg, lg_o, ids_o, free_ids=None):
         k = int(nd[0]) if nd.numel() else len(ids_o)
         assert torch.equal(free_ids[:k], ids_o[:k]), f"free-running ids {free_ids.tolist()} vs oracle {ids_o.tolist()} (first {k} must match)"
     return decisive
+
+
+def attn_ref(q, k, v, causal, cu=None, scale=None, return_lse=False):
+    """fp32 attention reference: softmax(scale * Q K^T + mask) V per sequence (`cu` = cu_seqlens, None = one sequence), GQA: q head h reads
+    kv head h // (Hq / Hkv); scale defaults to D^-0.5.  Computed per sequence and kv head so that the fp32 score matrices of long shapes stay
+    a few GB.  -> o [T, Hq, D] fp32 (+ lse [Hq, T] fp32, the natural-log sum of exp(scale * s) over the visible keys)."""
+    T, Hq, D = q.shape
+    Hkv = k.shape[1]
+    G = Hq // Hkv
+    scale = D ** -0.5 if scale is None else scale
+    out = torch.zeros((T, Hq, D), device=q.device, dtype=torch.float32)
+    lse = torch.zeros((Hq, T), device=q.device, dtype=torch.float32)
+    bounds = [0, T] if cu is None else cu.tolist()
+    for a, b in zip(bounds[:-1], bounds[1:]):
+        if b == a:
+            continue
+        future = torch.triu(torch.ones(b - a, b - a, dtype=torch.bool, device=q.device), 1) if causal else None
+        for g in range(Hkv):
+            hs = slice(g * G, (g + 1) * G)
+            s = torch.einsum("qhd,kd->hqk", q[a:b, hs].float(), k[a:b, g].float()) * scale
+            if causal:
+                s = s.masked_fill(future, float("-inf"))
+            lse[hs, a:b] = torch.logsumexp(s, -1)
+            out[a:b, hs] = torch.einsum("hqk,kd->qhd", torch.softmax(s, -1), v[a:b, g].float())
+    return (out, lse) if return_lse else out
+
+
+def attn_ref_grads(q, k, v, do, causal, cu=None, scale=None):
+    """fp32 autograd through attn_ref's formula, one kv head (and its q-head group) at a time.  -> o, dq, dk, dv (fp32)."""
+    T, Hq, D = q.shape
+    Hkv = k.shape[1]
+    G = Hq // Hkv
+    scale = D ** -0.5 if scale is None else scale
+    bounds = [0, T] if cu is None else cu.tolist()
+    o = torch.zeros((T, Hq, D), device=q.device, dtype=torch.float32)
+    dq, dk, dv = torch.zeros_like(o), torch.zeros((T, Hkv, D), device=q.device, dtype=torch.float32), torch.zeros((T, Hkv, D), device=q.device, dtype=torch.float32)
+    for g in range(Hkv):
+        hs = slice(g * G, (g + 1) * G)
+        qf = q[:, hs].float().detach().requires_grad_(True)
+        kf = k[:, g].float().detach().requires_grad_(True)
+        vf = v[:, g].float().detach().requires_grad_(True)
+        outs = []
+        for a, b in zip(bounds[:-1], bounds[1:]):
+            s = torch.einsum("qhd,kd->hqk", qf[a:b], kf[a:b]) * scale
+            if causal:
+                s = s.masked_fill(torch.triu(torch.ones(b - a, b - a, dtype=torch.bool, device=q.device), 1), float("-inf"))
+            outs.append(torch.einsum("hqk,kd->qhd", torch.softmax(s, -1), vf[a:b]))
+        og = torch.cat(outs, 0)
+        og.backward(do[:, hs].float())
+        o[:, hs], dq[:, hs], dk[:, g], dv[:, g] = og.detach(), qf.grad, kf.grad, vf.grad
+    return o, dq, dk, dv

@@ -1,0 +1,251 @@
+"""GPU parity tests of every form of the attention forward (vila_attn_force_fwd: A / B / C / D / v1) and both backward implementations
+(vila_attn_force_bwd: v1 / DMA) against the fp32 reference (tests/gpu_util.attn_ref / attn_ref_grads), at the edges where flash-attention
+kernels go wrong: sequence lengths straddling every block height, the causal diagonal, GQA 7:1, head dims 64 / 72 / 128, the key-split merge,
+large and uniform logits.  Which form the automatic policy picks is asserted at the model's shapes (vila_attn_fwd_form).
+
+Tolerances: the suite's operator bounds, o rel-L2 < 8e-3 (P is rounded to bf16 before PV, o to bf16; measured at most 2.2e-3 here, every
+form alike) and dq / dk / dv rel-L2 < 1.5e-2; lse max-abs < LSE_MAX_ABS = 1e-4 (measured, see there)."""
+import contextlib
+
+import pytest
+import torch
+
+from tests.gpu_util import attn_ref, attn_ref_grads, max_abs, randn_bf16, rel_l2
+
+pytestmark = pytest.mark.gpu
+
+FORMS = {1: "A", 2: "B", 3: "C", 4: "D", 5: "v1"}
+# one varlen batch whose sequences straddle every block height (16 / 32 rows per wave, 64 / 128 / 256-row blocks, 64-key tiles)
+VARLEN = [1, 15, 16, 17, 31, 32, 33, 63, 64, 65, 127, 128, 129, 255, 256, 257, 300]
+# lse max-abs against the fp32 logsumexp.  The kernel's scores are fp32 MFMA sums of the same bf16 products the reference uses, so lse agrees
+# to fp32 precision: measured on MI355X over every case of this file, all five forms alike, 3.8e-6 at |lse| < 16 and 3.1e-5 (4 fp32 ulps at
+# |lse| ~ 80) in the large-logit case.  The suite's earlier bound was 2e-2; this one keeps a 3x margin over the worst case measured.
+LSE_MAX_ABS = 1e-4
+O_REL = 8e-3
+GRAD_REL = 1.5e-2
+
+
+@pytest.fixture(scope="module")
+def lib():
+    assert torch.cuda.is_available(), "GPU tests need a GPU"
+    from vila_amd import _lib
+    return _lib.load()
+
+
+@contextlib.contextmanager
+def _forced(lib, fwd=0, bwd=0):
+    lib.vila_attn_force_fwd(fwd)
+    lib.vila_attn_force_bwd(bwd)
+    try:
+        yield
+    finally:
+        lib.vila_attn_force_fwd(0)
+        lib.vila_attn_force_bwd(0)
+
+
+def _qkv(T, Hq, Hkv, D, seed, q_scale=1.0):
+    """q / k / v as strided views of one fused [T, (Hq + 2 Hkv) D] buffer, as the model passes them."""
+    qkv = randn_bf16(T, (Hq + 2 * Hkv) * D, seed=seed)
+    q = qkv[:, : Hq * D].view(T, Hq, D)
+    if q_scale != 1.0:
+        q.copy_((q.float() * q_scale).to(torch.bfloat16))
+    return q, qkv[:, Hq * D:(Hq + Hkv) * D].view(T, Hkv, D), qkv[:, (Hq + Hkv) * D:].view(T, Hkv, D)
+
+
+def _fwd(q, k, v, causal, scale=None, cu=None, max_seqlen=None, n_seq=1):
+    """vila_attn_fwd_bf16 into o / lse buffers pre-filled with NaN, so that a row the kernel never writes fails the comparison."""
+    from vila_amd import _lib
+    from vila_amd.ops import _p, _stream
+    T, Hq, D = q.shape
+    Hkv = k.shape[1]
+    if cu is None:
+        max_seqlen = T // n_seq
+    else:
+        n_seq = cu.numel() - 1
+    o = torch.full((T, Hq, D), float("nan"), device=q.device, dtype=torch.bfloat16)
+    lse = torch.full((Hq, T), float("nan"), device=q.device, dtype=torch.float32)
+    _lib.check(_lib.load().vila_attn_fwd_bf16(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), q.stride(0), k.stride(0), v.stride(0),
+                                              o.stride(0), q.stride(1), k.stride(1), v.stride(1), o.stride(1), _p(cu), n_seq, T, int(max_seqlen),
+                                              Hq, Hkv, D, int(causal), float(scale if scale is not None else D ** -0.5), lse.data_ptr(), _stream()),
+               "attn_fwd")
+    return o, lse
+
+
+def _check_fwd(tag, o, lse, q, k, v, causal, scale=None, cu=None):
+    """o (overall and per sequence) and lse at every real row against the fp32 reference."""
+    ref, lse_ref = attn_ref(q, k, v, causal, cu, scale=scale, return_lse=True)
+    assert torch.isfinite(o.float()).all() and torch.isfinite(lse).all(), f"{tag}: non-finite rows in o / lse"
+    assert rel_l2(o, ref) < O_REL, f"{tag}: o rel-L2 {rel_l2(o, ref):.3e}"
+    bounds = [0, q.shape[0]] if cu is None else cu.tolist()
+    for a, b in zip(bounds[:-1], bounds[1:]):
+        assert rel_l2(o[a:b], ref[a:b]) < O_REL, f"{tag}: o rel-L2 {rel_l2(o[a:b], ref[a:b]):.3e} in the sequence of rows [{a}, {b})"
+    err = max_abs(lse, lse_ref)
+    assert err < LSE_MAX_ABS, f"{tag}: lse max-abs {err:.3e}"
+    return err
+
+
+@pytest.mark.parametrize("Hq,Hkv", [(4, 4), (14, 2)])
+@pytest.mark.parametrize("causal", [False, True])
+@pytest.mark.parametrize("D", [64, 72, 128])
+@pytest.mark.parametrize("form", sorted(FORMS))
+def test_every_form_matches_the_reference(lib, form, D, causal, Hq, Hkv):
+    """Each forced form: a varlen batch straddling every block height, a uniform batch without cu_seqlens (the ViT call), a non-default scale."""
+    cu = torch.tensor([0] + torch.tensor(VARLEN).cumsum(0).tolist(), dtype=torch.int32, device="cuda")
+    T = int(cu[-1])
+    q, k, v = _qkv(T, Hq, Hkv, D, seed=100 + D)
+    q2, k2, v2 = _qkv(3 * 200, Hq, Hkv, D, seed=200 + D)
+    q3, k3, v3 = _qkv(257, Hq, Hkv, D, seed=300 + D)
+    with _forced(lib, fwd=form):
+        o, lse = _fwd(q, k, v, causal, cu=cu, max_seqlen=max(VARLEN))
+        o2, lse2 = _fwd(q2, k2, v2, causal, n_seq=3)
+        o3, lse3 = _fwd(q3, k3, v3, causal, scale=0.25)
+    tag = f"form {FORMS[form]}"
+    _check_fwd(f"{tag} varlen", o, lse, q, k, v, causal, cu=cu)
+    _check_fwd(f"{tag} uniform", o2, lse2, q2, k2, v2, causal, cu=torch.arange(0, 601, 200, dtype=torch.int32, device="cuda"))
+    _check_fwd(f"{tag} scale 0.25", o3, lse3, q3, k3, v3, causal, scale=0.25)
+
+
+@pytest.mark.parametrize("form", sorted(FORMS))
+def test_every_form_survives_softmax_stress(lib, form):
+    """Running-max jumps inside both key groups of a key-split block (dominant keys in odd 64-key tiles, read by the second key group, and
+    late in an even one), causal rows whose second key group lies wholly in the future (the first rows of every sequence), scores spanning
+    about +-80 after scaling, and uniform scores (q = 0: o is the mean of the visible v rows, lse = log(#visible keys))."""
+    Hq, Hkv, D = 4, 2, 128
+    T = 300
+    q, k, v = _qkv(T, Hq, Hkv, D, seed=400)
+    for qi, kj, f in ((120, 100, 1.5), (250, 200, 1.5), (290, 280, 2.0), (299, 193, 1.5), (70, 66, -2.0)):
+        k[kj] = (q[qi, :: Hq // Hkv].float() * f).to(torch.bfloat16)    # kv head g spikes against q head 2g (the first head of its group)
+    cu = torch.tensor([0, 65, 165, 300], dtype=torch.int32, device="cuda")
+    qb, kb, vb = _qkv(T, Hq, Hkv, D, seed=401, q_scale=27.0)            # s * D^-0.5 ~ N(0, 27^2): the extreme keys near +-80
+    qz, kz, vz = _qkv(T, Hq, Hkv, D, seed=402)
+    qz.zero_()
+    for causal in (False, True):
+        with _forced(lib, fwd=form):
+            runs = [_fwd(q, k, v, causal), _fwd(q, k, v, causal, cu=cu, max_seqlen=135), _fwd(qb, kb, vb, causal), _fwd(qz, kz, vz, causal)]
+        tag = f"form {FORMS[form]} causal={causal}"
+        _check_fwd(f"{tag} max jump", *runs[0], q, k, v, causal)
+        _check_fwd(f"{tag} varlen max jump", *runs[1], q, k, v, causal, cu=cu)
+        s = torch.einsum("qhd,kd->hqk", qb[:, :2].float(), kb[:, 0].float()) * D ** -0.5
+        assert s.abs().max() > 60, "the large-logit case lost its range"
+        _check_fwd(f"{tag} large logits", *runs[2], qb, kb, vb, causal)
+        oz, lz = runs[3]
+        n = torch.arange(1, T + 1, device="cuda", dtype=torch.float64) if causal else torch.full((T,), float(T), device="cuda", dtype=torch.float64)
+        csum = vz.double().cumsum(0) if causal else vz.double().sum(0, keepdim=True).expand(T, -1, -1)
+        mean = (csum / n[:, None, None]).repeat_interleave(Hq // Hkv, 1)
+        assert torch.isfinite(oz.float()).all()
+        assert rel_l2(oz, mean) < 4e-3, f"{tag} uniform scores: o rel-L2 {rel_l2(oz, mean):.3e} vs the mean of v"
+        assert max_abs(lz, n.log()[None].expand(Hq, -1)) < 1e-5, f"{tag} uniform scores: lse vs log(n) {max_abs(lz, n.log()[None].expand(Hq, -1)):.3e}"
+
+
+@pytest.mark.parametrize("form", sorted(FORMS))
+def test_every_form_is_deterministic(lib, form):
+    """Two calls on the same inputs give bit-identical o and lse (the bit-exact resume test relies on it)."""
+    cu = torch.tensor([0] + torch.tensor(VARLEN).cumsum(0).tolist(), dtype=torch.int32, device="cuda")
+    T = int(cu[-1])
+    for D, causal, Hq, Hkv in ((128, True, 14, 2), (72, False, 4, 4)):
+        q, k, v = _qkv(T, Hq, Hkv, D, seed=500)
+        with _forced(lib, fwd=form):
+            o1, l1 = _fwd(q, k, v, causal, cu=cu, max_seqlen=max(VARLEN))
+            o2, l2 = _fwd(q, k, v, causal, cu=cu, max_seqlen=max(VARLEN))
+        assert torch.equal(o1, o2) and torch.equal(l1, l2), f"form {FORMS[form]} D={D}: two calls differ"
+
+
+# (name, n_seq, seqlen, Hq, Hkv, D, causal, cu_seqlens?, the form the policy picks on 256 CUs)
+MODEL_SHAPES = [
+    ("ViT, one 448^2 tile", 1, 1024, 16, 16, 72, False, False, 2),
+    ("ViT, 4 tiles", 4, 1024, 16, 16, 72, False, False, 3),
+    ("ViT, dynamic_s2 tower (14 tiles)", 14, 1024, 16, 16, 72, False, False, 1),
+    ("LLM prefill S = 769", 1, 769, 28, 4, 128, True, True, 3),
+    ("LLM long video prefill S = 4700", 1, 4700, 28, 4, 128, True, True, 1),
+    ("packed SFT batch 4 x 769", 4, 769, 28, 4, 128, True, True, 3),
+]
+
+
+@pytest.mark.parametrize("name,n_seq,S,Hq,Hkv,D,causal,varlen,form", MODEL_SHAPES, ids=[m[0] for m in MODEL_SHAPES])
+def test_automatic_policy_at_model_shapes(lib, name, n_seq, S, Hq, Hkv, D, causal, varlen, form):
+    """The automatic policy reaches forms A, B and C at the model's shapes; each is compared with the reference, forward and backward."""
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    if cus != 256:
+        pytest.skip(f"the form table is for 256 CUs; this device reports {cus}")
+    assert {m[-1] for m in MODEL_SHAPES} == {1, 2, 3}
+    got = lib.vila_attn_fwd_form(n_seq, S, Hq)
+    assert got == form, f"{name}: the policy picks form {FORMS.get(got, got)}, the table says {FORMS[form]}"
+    T = n_seq * S
+    q, k, v = _qkv(T, Hq, Hkv, D, seed=600 + n_seq)
+    cu = torch.arange(0, T + 1, S, dtype=torch.int32, device="cuda")
+    kw = dict(cu=cu, max_seqlen=S) if varlen else dict(n_seq=n_seq)
+    o, lse = _fwd(q, k, v, causal, **kw)
+    _check_fwd(name, o, lse, q, k, v, causal, cu=cu)
+    do = randn_bf16(T, Hq, D, seed=601)
+    _, dq_ref, dk_ref, dv_ref = attn_ref_grads(q, k, v, do, causal, cu)
+    dq, dk, dv = torch.zeros_like(q), torch.zeros_like(k), torch.zeros_like(v)
+    from vila_amd import ops
+    bkw = dict(cu_seqlens=cu, max_seqlen=S) if varlen else dict(n_seq=n_seq)
+    ops.attn_bwd(q, k, v, o, do, lse, causal, dq, dk, dv, **bkw)
+    for g, got_, ref in (("dq", dq, dq_ref), ("dk", dk, dk_ref), ("dv", dv, dv_ref)):
+        assert rel_l2(got_, ref) < GRAD_REL, f"{name}: {g} rel-L2 {rel_l2(got_, ref):.3e}"
+
+
+def _dqkv_views(T, Hq, Hkv, D):
+    buf = torch.zeros((T, (Hq + 2 * Hkv) * D), device="cuda", dtype=torch.bfloat16)
+    return buf[:, : Hq * D].view(T, Hq, D), buf[:, Hq * D:(Hq + Hkv) * D].view(T, Hkv, D), buf[:, (Hq + Hkv) * D:].view(T, Hkv, D)
+
+
+@pytest.mark.parametrize("Hq,Hkv", [(4, 4), (14, 2)])
+@pytest.mark.parametrize("causal", [False, True])
+@pytest.mark.parametrize("D", [64, 72, 128])
+@pytest.mark.parametrize("impl", [1, 2], ids=["v1", "dma"])
+def test_backward_both_implementations(lib, impl, D, causal, Hq, Hkv):
+    """dq / dk / dv of the v1 and DMA backward over the varlen batch, lse from the default forward, gradients into one fused dqkv buffer."""
+    from vila_amd import ops
+    cu = torch.tensor([0] + torch.tensor(VARLEN).cumsum(0).tolist(), dtype=torch.int32, device="cuda")
+    T = int(cu[-1])
+    q, k, v = _qkv(T, Hq, Hkv, D, seed=700 + D)
+    do = randn_bf16(T, Hq, D, seed=701)
+    _, dq_ref, dk_ref, dv_ref = attn_ref_grads(q, k, v, do, causal, cu)
+    o, lse = _fwd(q, k, v, causal, cu=cu, max_seqlen=max(VARLEN))
+    dq, dk, dv = _dqkv_views(T, Hq, Hkv, D)
+    with _forced(lib, bwd=impl):
+        ops.attn_bwd(q, k, v, o, do, lse, causal, dq, dk, dv, cu_seqlens=cu, max_seqlen=max(VARLEN))
+    for g, got, ref in (("dq", dq, dq_ref), ("dk", dk, dk_ref), ("dv", dv, dv_ref)):
+        assert rel_l2(got, ref) < GRAD_REL, f"impl {impl}: {g} rel-L2 {rel_l2(got, ref):.3e}"
+
+
+def test_dma_backward_consumes_every_forms_lse(lib):
+    """The lse each forced forward form writes drives the DMA backward to the reference gradients (hd 128, causal, GQA 7:1)."""
+    from vila_amd import ops
+    Hq, Hkv, D = 14, 2, 128
+    cu = torch.tensor([0] + torch.tensor(VARLEN).cumsum(0).tolist(), dtype=torch.int32, device="cuda")
+    T = int(cu[-1])
+    q, k, v = _qkv(T, Hq, Hkv, D, seed=800)
+    do = randn_bf16(T, Hq, D, seed=801)
+    _, dq_ref, dk_ref, dv_ref = attn_ref_grads(q, k, v, do, True, cu)
+    for form in sorted(FORMS):
+        with _forced(lib, fwd=form, bwd=2):
+            o, lse = _fwd(q, k, v, True, cu=cu, max_seqlen=max(VARLEN))
+            dq, dk, dv = _dqkv_views(T, Hq, Hkv, D)
+            ops.attn_bwd(q, k, v, o, do, lse, True, dq, dk, dv, cu_seqlens=cu, max_seqlen=max(VARLEN))
+        for g, got, ref in (("dq", dq, dq_ref), ("dk", dk, dk_ref), ("dv", dv, dv_ref)):
+            assert rel_l2(got, ref) < GRAD_REL, f"lse of form {FORMS[form]}: {g} rel-L2 {rel_l2(got, ref):.3e}"
+
+
+@pytest.mark.parametrize("impl", [1, 2], ids=["v1", "dma"])
+def test_backward_parts_split_is_bit_identical(lib, impl):
+    """SFTTrainer._attn_bwd's two-stream split: parts 1 (delta), then 4 (dK / dV) and 2 (dQ) with the delta passed back in == parts 7."""
+    from vila_amd import ops
+    Hq, Hkv, D = 28, 4, 128
+    cu = torch.tensor([0, 300, 769, 1000], dtype=torch.int32, device="cuda")
+    T = 1000
+    q, k, v = _qkv(T, Hq, Hkv, D, seed=900)
+    do = randn_bf16(T, Hq, D, seed=901)
+    o, lse = _fwd(q, k, v, True, cu=cu, max_seqlen=469)
+    with _forced(lib, bwd=impl):
+        whole = _dqkv_views(T, Hq, Hkv, D)
+        delta7 = ops.attn_bwd(q, k, v, o, do, lse, True, *whole, cu_seqlens=cu, max_seqlen=469)
+        split = _dqkv_views(T, Hq, Hkv, D)
+        delta = ops.attn_bwd(q, k, v, o, do, lse, True, *split, cu_seqlens=cu, max_seqlen=469, parts=1)
+        ops.attn_bwd(q, k, v, o, do, lse, True, *split, cu_seqlens=cu, max_seqlen=469, parts=4, delta=delta)
+        ops.attn_bwd(q, k, v, o, do, lse, True, *split, cu_seqlens=cu, max_seqlen=469, parts=2, delta=delta)
+    assert torch.equal(delta, delta7)
+    for g, a, b in zip(("dq", "dk", "dv"), split, whole):
+        assert torch.equal(a, b), f"impl {impl}: {g} of the split launch differs from parts = 7"

@@ -4,7 +4,7 @@ reference of the same op on the same seeded bf16 inputs.  Tolerances are stated 
 import pytest
 import torch
 
-from tests.gpu_util import max_abs, randn_bf16, rel_l2
+from tests.gpu_util import attn_ref as _attn_ref, max_abs, randn_bf16, rel_l2
 
 pytestmark = pytest.mark.gpu
 
@@ -174,22 +174,6 @@ def test_space_to_depth_bit_exact(ops, g, k):
     ref = O.downsample_block(x, k)
     out = ops.space_to_depth(x.to("cuda", torch.bfloat16), k)
     assert torch.equal(out.float().cpu(), ref)
-
-
-def _attn_ref(q, k, v, causal, cu=None):
-    """fp32 reference: softmax(QK^T/sqrt(d) + mask) V per sequence, GQA by repeat."""
-    T, Hq, D = q.shape
-    Hkv = k.shape[1]
-    qf, kf, vf = q.float(), k.float().repeat_interleave(Hq // Hkv, 1), v.float().repeat_interleave(Hq // Hkv, 1)
-    out = torch.zeros_like(qf)
-    bounds = [0, T] if cu is None else cu.tolist()
-    for a, b in zip(bounds[:-1], bounds[1:]):
-        s = torch.einsum("qhd,khd->hqk", qf[a:b], kf[a:b]) * D ** -0.5
-        if causal:
-            n = b - a
-            s = s.masked_fill(torch.triu(torch.ones(n, n, dtype=torch.bool, device=q.device), 1), float("-inf"))
-        out[a:b] = torch.einsum("hqk,khd->qhd", torch.softmax(s, -1), vf[a:b])
-    return out
 
 
 @pytest.mark.parametrize("T,Hq,Hkv,D,causal", [

@@ -7,7 +7,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from tests.gpu_util import GRAD_COS_MIN, grad_cos, max_abs, randn_bf16, rel_l2
+from tests.gpu_util import GRAD_COS_MIN, attn_ref_grads as _attn_ref_grads, grad_cos, max_abs, randn_bf16, rel_l2
 
 # Per-tensor exceptions to the stated cosine bound: (test tag, tensor-name suffix) -> (bound, measured, why).  Everything else: >= 0.999.
 GRAD_COS_EXCEPTIONS = {}
@@ -51,27 +51,11 @@ def test_linear_backward_via_transposed_gemm(ops):
     assert rel_l2(gb, dy.float().sum(0)) < 5e-3
 
 
-def _attn_ref_grads(q, k, v, do, causal, cu):
-    qf, kf, vf = [t.float().detach().requires_grad_(True) for t in (q, k, v)]
-    T, Hq, D = q.shape
-    G = Hq // k.shape[1]
-    outs = []
-    bounds = cu.tolist()
-    for a, b in zip(bounds[:-1], bounds[1:]):
-        s = torch.einsum("qhd,khd->hqk", qf[a:b], kf[a:b].repeat_interleave(G, 1)) * D ** -0.5
-        if causal:
-            n = b - a
-            s = s.masked_fill(torch.triu(torch.ones(n, n, dtype=torch.bool, device=q.device), 1), float("-inf"))
-        outs.append(torch.einsum("hqk,khd->qhd", torch.softmax(s, -1), vf[a:b].repeat_interleave(G, 1)))
-    o = torch.cat(outs, 0)
-    o.backward(do.float())
-    return o.detach(), qf.grad, kf.grad, vf.grad
-
-
 @pytest.mark.parametrize("bounds,Hq,Hkv,D,causal", [
     ([0, 1024], 16, 16, 72, False), ([0, 196, 392], 2, 2, 72, False), ([0, 50], 2, 2, 72, False),
     ([0, 769], 28, 4, 128, True), ([0, 100, 357, 400, 401], 4, 2, 128, True), ([0, 130], 4, 4, 64, True), ([0, 97], 2, 1, 128, False),
-    # grids above one block per CU take the 4-wave dK/dV kernel (the cases above the 8-wave two-group one)
+    # the largest dK / dV grids: 512 and 336 blocks of the DMA kernel, more than one per CU.  (The v1 kernels, VILA_ATTN_BWD=v1, switch from
+    # their 8-wave two-group dK / dV kernel to the 4-wave one above 320 blocks; they are tested in tests/test_gpu_attention_forms.py.)
     ([0, 1024, 2048], 16, 16, 72, False), ([0, 1300, 2600], 8, 8, 128, True),
 ])
 def test_attention_backward(ops, bounds, Hq, Hkv, D, causal):

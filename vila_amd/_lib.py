@@ -133,6 +133,9 @@ PROTOTYPES = {
     "vila_gemm_force_fuse_norm": (None, [c_int]),
     "vila_prefill_force_fusions": (None, [c_int, c_int]),
     "vila_norm_force_lat": (None, [c_int]),
+    "vila_attn_force_fwd": (None, [c_int]),
+    "vila_attn_fwd_form": (c_int, [c_int, c_int, c_int]),
+    "vila_attn_force_bwd": (None, [c_int]),
     "vila_decode_force_attn": (None, [c_int]),
     "vila_decode_force_chain": (None, [c_int]),
     "vila_decode_force_persist": (None, [c_int]),

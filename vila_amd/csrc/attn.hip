@@ -690,26 +690,43 @@ static int attn_ks_env() {
     if (v < 0) { const char* e = getenv("VILA_ATTN_KS"); v = (e && e[0] >= '0' && e[0] <= '3') ? e[0] - '0' : 1; }
     return v;
 }
-template <int HD, bool CAUSAL>
-static int launch_attn_t(const AttnArgs& a, hipStream_t s) {
-    const int64_t blocks2 = (int64_t)cdiv(a.max_seqlen, 256) * a.n_q_heads * a.n_seq;
-    if (blocks2 < 512) {
-        const int ks = attn_ks_env();
-        if (ks == 0) return launch_attn_q<HD, CAUSAL, 1>(a, s);
-        // 64-row blocks (16 rows per wave, 4 query groups x 2 key groups: half the dependent steps at the old per-step cost) while they all fit the
-        // chip at once — one 448^2 tile: 256 blocks, 20.7 -> 16.3 us; S = 769 would be 364 blocks = two rounds, 21.1 -> 22.0 us, and keeps 128 rows
-        // (profiles/r06_attn_keysplit_scan.txt).  VILA_ATTN_KS=2 / 3 force the 64- / 128-row form
-        const int64_t blocks64 = (int64_t)cdiv(a.max_seqlen, 64) * a.n_q_heads * a.n_seq;
-        if (ks == 2 || (ks == 1 && blocks64 <= attn_cu_count())) return launch_attn_q<HD, CAUSAL, 1, 2>(a, s);
-        return launch_attn_q<HD, CAUSAL, 2, 2>(a, s);
-    }
-    return launch_attn_q<HD, CAUSAL, 2>(a, s);
-}
-
 static int attn_fwd_impl() {          // VILA_ATTN_FWD=v1 selects the round-2 kernel (A/B measurements); default: the DMA-ring kernel
     static int impl = -1;
     if (impl < 0) { const char* e = getenv("VILA_ATTN_FWD"); impl = (e && e[0] == 'v' && e[1] == '1') ? 1 : 2; }
     return impl;
+}
+
+// The forms of the forward (vila_hip_tuning.h vila_attn_force_fwd): A = 256-row blocks (QF 2, KS 1), B = 64-row key-split blocks (QF 1, KS 2),
+// C = 128-row key-split blocks (QF 2, KS 2), D = 128-row blocks (QF 1, KS 1), V1 = the round-2 kernel (its own 128 / 256-row choice)
+enum { ATTN_FORM_AUTO = 0, ATTN_FORM_A = 1, ATTN_FORM_B = 2, ATTN_FORM_C = 3, ATTN_FORM_D = 4, ATTN_FORM_V1 = 5 };
+static int g_attn_force_fwd = ATTN_FORM_AUTO;          // test hook: 0 = the automatic policy, 1..5 = that form whatever the grid
+extern "C" void vila_attn_force_fwd(int form) { g_attn_force_fwd = form; }
+
+// the automatic policy: 256-row blocks while they give the chip at least two rounds, else 64-row key-split blocks while they all fit at once
+// (one 448^2 tile: 256 blocks, 20.7 -> 16.3 us; S = 769 would be 364 blocks = two rounds, 21.1 -> 22.0 us, and keeps 128 rows,
+// profiles/r06_attn_keysplit_scan.txt), else 128-row key-split blocks.  VILA_ATTN_KS=0 / 2 / 3 take D / B / C for the grids below A's.
+static int attn_auto_form(int n_seq, int max_seqlen, int n_q_heads) {
+    if (attn_fwd_impl() == 1) return ATTN_FORM_V1;
+    const int64_t blocks2 = (int64_t)cdiv(max_seqlen, 256) * n_q_heads * n_seq;
+    if (blocks2 >= 512) return ATTN_FORM_A;
+    const int ks = attn_ks_env();
+    if (ks == 0) return ATTN_FORM_D;
+    const int64_t blocks64 = (int64_t)cdiv(max_seqlen, 64) * n_q_heads * n_seq;
+    if (ks == 2 || (ks == 1 && blocks64 <= attn_cu_count())) return ATTN_FORM_B;
+    return ATTN_FORM_C;
+}
+// host only: the form the automatic policy launches for this grid on the current device (tests assert which form a model shape gets)
+extern "C" int vila_attn_fwd_form(int n_seq, int max_seqlen, int n_q_heads) { return attn_auto_form(n_seq, max_seqlen, n_q_heads); }
+
+template <int HD, bool CAUSAL>
+static int launch_attn_t(const AttnArgs& a, int form, hipStream_t s) {
+    switch (form) {
+        case ATTN_FORM_A: return launch_attn_q<HD, CAUSAL, 2>(a, s);
+        case ATTN_FORM_B: return launch_attn_q<HD, CAUSAL, 1, 2>(a, s);
+        case ATTN_FORM_C: return launch_attn_q<HD, CAUSAL, 2, 2>(a, s);
+        case ATTN_FORM_D: return launch_attn_q<HD, CAUSAL, 1>(a, s);
+        default: return launch_attn_v1_t<HD, CAUSAL>(a, s);
+    }
 }
 
 int launch_attn_fwd(const AttnArgs& a, hipStream_t s) {
@@ -721,13 +738,10 @@ int launch_attn_fwd(const AttnArgs& a, hipStream_t s) {
                  a.q_head_stride % 8 == 0 && a.k_head_stride % 8 == 0 && a.v_head_stride % 8 == 0 && a.o_head_stride % 4 == 0,
                  "attn: strides must keep 16-B (q,k,v) / 8-B (o) alignment");
     VILA_REQUIRE((uintptr_t)a.q % 16 == 0 && (uintptr_t)a.k % 16 == 0 && (uintptr_t)a.v % 16 == 0 && (uintptr_t)a.o % 8 == 0, "attn: pointer alignment");
-    if (attn_fwd_impl() == 1) {
-        if (a.head_dim == 128) return a.causal ? launch_attn_v1_t<128, true>(a, s) : launch_attn_v1_t<128, false>(a, s);
-        if (a.head_dim == 72) return a.causal ? launch_attn_v1_t<72, true>(a, s) : launch_attn_v1_t<72, false>(a, s);
-        if (a.head_dim == 64) return a.causal ? launch_attn_v1_t<64, true>(a, s) : launch_attn_v1_t<64, false>(a, s);
-    }
-    if (a.head_dim == 128) return a.causal ? launch_attn_t<128, true>(a, s) : launch_attn_t<128, false>(a, s);
-    if (a.head_dim == 72) return a.causal ? launch_attn_t<72, true>(a, s) : launch_attn_t<72, false>(a, s);
-    if (a.head_dim == 64) return a.causal ? launch_attn_t<64, true>(a, s) : launch_attn_t<64, false>(a, s);
+    VILA_REQUIRE(g_attn_force_fwd >= ATTN_FORM_AUTO && g_attn_force_fwd <= ATTN_FORM_V1, "attn: forced form %d (0 = automatic, 1..5)", g_attn_force_fwd);
+    const int form = g_attn_force_fwd != ATTN_FORM_AUTO ? g_attn_force_fwd : attn_auto_form(a.n_seq, a.max_seqlen, a.n_q_heads);
+    if (a.head_dim == 128) return a.causal ? launch_attn_t<128, true>(a, form, s) : launch_attn_t<128, false>(a, form, s);
+    if (a.head_dim == 72) return a.causal ? launch_attn_t<72, true>(a, form, s) : launch_attn_t<72, false>(a, form, s);
+    if (a.head_dim == 64) return a.causal ? launch_attn_t<64, true>(a, form, s) : launch_attn_t<64, false>(a, form, s);
     VILA_FAIL(-1, "attn: unsupported head_dim %d (supported: 64, 72, 128)", a.head_dim);
 }

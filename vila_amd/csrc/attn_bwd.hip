@@ -465,6 +465,9 @@ static int launch_bwd_t(const AttnBwdArgs& a, hipStream_t s, int parts) {
     return 0;
 }
 
+static int g_attn_force_bwd = 0;       // test hook (vila_hip_tuning.h): 0 = VILA_ATTN_BWD / default, 1 = the kernels of this file, 2 = DMA
+extern "C" void vila_attn_force_bwd(int impl) { g_attn_force_bwd = impl; }
+
 int launch_attn_bwd(const AttnBwdArgs& a, hipStream_t s, int parts) {
     VILA_REQUIRE(parts >= 1 && parts <= 7, "attn_bwd: parts must be a combination of 1 (delta), 2 (dQ), 4 (dK/dV)");
     VILA_REQUIRE(a.n_seq >= 1 && a.total_tokens >= 1 && a.max_seqlen >= 1, "attn_bwd: empty input");
@@ -473,8 +476,10 @@ int launch_attn_bwd(const AttnBwdArgs& a, hipStream_t s, int parts) {
     VILA_REQUIRE(a.lse != nullptr && a.delta != nullptr, "attn_bwd: lse / delta workspace missing");
     // VILA_ATTN_BWD=v1 keeps the round-1/2 dQ and dK / dV kernels of this file (A/B measurements); default: the DMA-ring kernels of
     // attn_bwd_dma.hip for those two passes, delta from here
-    static int impl = -1;
-    if (impl < 0) { const char* e = getenv("VILA_ATTN_BWD"); impl = (e && e[0] == 'v' && e[1] == '1') ? 1 : 2; }
+    VILA_REQUIRE(g_attn_force_bwd >= 0 && g_attn_force_bwd <= 2, "attn_bwd: forced implementation %d (0 = default, 1 = v1, 2 = DMA)", g_attn_force_bwd);
+    static int env_impl = -1;
+    if (env_impl < 0) { const char* e = getenv("VILA_ATTN_BWD"); env_impl = (e && e[0] == 'v' && e[1] == '1') ? 1 : 2; }
+    const int impl = g_attn_force_bwd != 0 ? g_attn_force_bwd : env_impl;
     if (impl == 2 && (parts & 6)) {
         if (parts & 1) {
             hipLaunchKernelGGL(attn_delta_kernel, dim3(cdiv(a.total_tokens * a.n_q_heads, 16)), dim3(256), 0, s, a);
