@@ -412,6 +412,26 @@ int vila_llm_decode_step_w4(const VilaLlmWeights* w, const VilaLlmLayerW4* qlaye
 int vila_llm_decode_step_w4_sample(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers /*[host]*/, const VilaKvCache* cache,
                             const VilaDecodeState* st, void* workspace, size_t workspace_bytes, const VilaSampling* sampling, vila_stream_t stream);
 
+/* W4A16 prefill GEMM (vila_amd/csrc/gemm_w4.hip) on the same packed buffers: y[M][N] = x[M][K] . W^T, x bf16 row stride K, y row stride N,
+ * any M >= 1.  mode 0: (+bias)(+residual, row stride N; y may alias it); mode 1: W holds 2N interleaved gate/up rows, y = silu(Wg x) * (Wu x),
+ * bias and residual must be NULL.  Deterministic (K-sliced grids add their fp32 slices in a fixed order).  K % 128 != 0, N % 16 != 0, another
+ * mode or a bias / residual the mode does not take -> -1.
+ * workspace: vila_gemm_w4_workspace_bytes(M, N, K, mode) bytes (0: none needed, NULL accepted). */
+size_t vila_gemm_w4_workspace_bytes(int M, int N, int K, int mode);
+int vila_gemm_w4_bf16(const void* x, const void* Wq, const void* Wsz, const void* bias, const void* residual, void* y,
+                      int M, int N, int K, int mode, void* workspace, size_t workspace_bytes, vila_stream_t stream);
+/* the fused q|k|v projection of a W4 layer (rows of the first q_heads + kv_heads heads RoPE-interleaved, VilaLlmLayerW4.qkv_q): y [M][(q_heads
+ * + 2 kv_heads) head_dim] in natural column order with the bias added, as the bf16 q|k|v GEMM leaves it for RoPE.  Workspace: mode 2 above. */
+int vila_gemm_w4_qkv_bf16(const void* x, const void* Wq, const void* Wsz, const void* bias, void* y, int M, int q_heads, int kv_heads,
+                          int head_dim, int K, void* workspace, size_t workspace_bytes, vila_stream_t stream);
+/* vila_llm_prefill with the five decoder projections read from the int4 layers (`w` still supplies embed, norms, q/k/v biases, lm_head;
+ * its projection pointers are not read).  Same arguments and contract, `qlayers` [host] added; the pruned last layer runs the W4 GEMVs. */
+size_t vila_llm_prefill_w4_workspace_bytes(const VilaLlmShape* s, int total_tokens);
+int vila_llm_prefill_w4(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers /*[host]*/, const void* embeds, const int32_t* positions,
+                        const int32_t* cu_seqlens, int n_seq, int total_tokens, int max_seqlen, const int32_t* seq_of_tok, const VilaKvCache* cache,
+                        const int32_t* last_rows, int n_last, float* last_logits, float* all_logits, void* final_hidden,
+                        void* layer_hidden, void* workspace, size_t workspace_bytes, vila_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

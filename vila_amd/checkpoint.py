@@ -69,6 +69,9 @@ def _folder_tensors(folder: str):
 
 def save_pretrained(model, output_dir: str, max_shard_bytes: int = 5 << 30) -> None:
     """Write the model in the reference's layout (llava_arch.py:158-204)."""
+    if getattr(model.llm, "_bf16_released", False):
+        raise RuntimeError("save_pretrained: the LLM's bf16 projection weights were freed by quantize_w4(release_bf16=True); "
+                           "a checkpoint of the reference's layout cannot be written from the int4 copies")
     cfg: VilaConfig = model.cfg
     c, v = cfg.llm, cfg.vision
     llm_cfg = {"model_type": "qwen2", "architectures": ["Qwen2ForCausalLM"], "hidden_size": c.hidden_size, "intermediate_size": c.intermediate_size,

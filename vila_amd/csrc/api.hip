@@ -1013,3 +1013,149 @@ static int decode_step_w4_impl(const VilaLlmWeights* w, const VilaLlmLayerW4* ql
     VILA_TRY(launch_decode_advance(st->pos, st->token, st->out_ids, st->n_out, st->max_out, s));
     return 0;
 }
+
+// =================================================================================================
+// W4A16 prefill: the LLM prefill of vila_llm_prefill with the five decoder projections read from the int4 layers (gemm_w4.hip), so a
+// quantised model runs from its int4 weights alone.  The loop mirrors vila_llm_prefill; where the bf16 path folds the norms and RoPE into
+// split-K reduces this one runs the standalone rmsnorm / rope_kv kernels.
+// =================================================================================================
+extern "C" size_t vila_gemm_w4_workspace_bytes(int M, int N, int K, int mode) { return gemm_w4_workspace_bytes(M, N, K, mode); }
+extern "C" int vila_gemm_w4_bf16(const void* x, const void* Wq, const void* Wsz, const void* bias, const void* residual, void* y,
+                                 int M, int N, int K, int mode, void* workspace, size_t workspace_bytes, vila_stream_t stream) {
+    VILA_REQUIRE(mode == 0 || mode == 1, "vila_gemm_w4_bf16: mode must be 0 or 1 (the q|k|v form is vila_gemm_w4_qkv_bf16)");
+    GemmW4Args g{};
+    g.x = B(x); g.Wq = (const uint32_t*)Wq; g.Wsz = (const uint32_t*)Wsz; g.bias = B(bias); g.residual = B(residual); g.y = B(y);
+    g.M = M; g.N = N; g.K = K; g.mode = mode;
+    return launch_gemm_w4(g, workspace, workspace_bytes, S(stream));
+}
+extern "C" int vila_gemm_w4_qkv_bf16(const void* x, const void* Wq, const void* Wsz, const void* bias, void* y, int M, int q_heads, int kv_heads,
+                                     int head_dim, int K, void* workspace, size_t workspace_bytes, vila_stream_t stream) {
+    VILA_REQUIRE(q_heads > 0 && kv_heads > 0, "vila_gemm_w4_qkv_bf16: q_heads=%d, kv_heads=%d", q_heads, kv_heads);
+    GemmW4Args g{};
+    g.x = B(x); g.Wq = (const uint32_t*)Wq; g.Wsz = (const uint32_t*)Wsz; g.bias = B(bias); g.y = B(y);
+    g.M = M; g.N = (q_heads + 2 * kv_heads) * head_dim; g.K = K; g.mode = 2; g.n_rope_heads = q_heads + kv_heads; g.hd = head_dim;
+    return launch_gemm_w4(g, workspace, workspace_bytes, S(stream));
+}
+
+static size_t prefill_w4_gemm_ws(const VilaLlmShape& sh, int T) {
+    const int H = sh.hidden, F = sh.inter, QS = sh.q_heads * sh.head_dim, QKV = (sh.q_heads + 2 * sh.kv_heads) * sh.head_dim;
+    size_t b = gemm_w4_workspace_bytes(T, QKV, H, 2);
+    const size_t o = gemm_w4_workspace_bytes(T, H, QS, 0), gu = gemm_w4_workspace_bytes(T, F, H, 1), dn = gemm_w4_workspace_bytes(T, H, F, 0);
+    if (o > b) b = o;
+    if (gu > b) b = gu;
+    if (dn > b) b = dn;
+    return b;
+}
+extern "C" size_t vila_llm_prefill_w4_workspace_bytes(const VilaLlmShape* s, int T) {
+    return vila_llm_prefill_workspace_bytes(s, T) + prefill_w4_gemm_ws(*s, T) + 256;
+}
+
+extern "C" int vila_llm_prefill_w4(const VilaLlmWeights* w, const VilaLlmLayerW4* ql, const void* embeds, const int32_t* positions,
+                                   const int32_t* cu_seqlens, int n_seq, int T, int max_seqlen, const int32_t* seq_of_tok, const VilaKvCache* cache,
+                                   const int32_t* last_rows, int n_last, float* last_logits, float* all_logits, void* final_hidden,
+                                   void* layer_hidden, void* workspace, size_t workspace_bytes, vila_stream_t stream) {
+    const VilaLlmShape& sh = w->shape;
+    hipStream_t s = S(stream);
+    VILA_REQUIRE(ql != nullptr, "llm_prefill_w4: the int4 layers are NULL");
+    VILA_REQUIRE(T > 0 && n_seq > 0, "llm_prefill_w4: empty input");
+    VILA_REQUIRE(sh.q_heads % sh.kv_heads == 0, "llm: q heads must be a multiple of kv heads");
+    VILA_REQUIRE(cu_seqlens != nullptr || n_seq == 1, "llm_prefill_w4: n_seq > 1 needs cu_seqlens");
+    VILA_REQUIRE(workspace_bytes >= vila_llm_prefill_w4_workspace_bytes(&sh, T), "llm_prefill_w4: workspace too small");
+    const int H = sh.hidden, F = sh.inter, hd = sh.head_dim, QS = sh.q_heads * hd, KS = sh.kv_heads * hd, QKV = QS + 2 * KS;
+    VILA_REQUIRE(QS == H, "llm: q_heads*head_dim (%d) must equal hidden (%d) for the in-place attention buffer", QS, H);
+    Arena a(workspace, workspace_bytes);
+    bf16_t* x = a.take<bf16_t>((size_t)T * H);
+    bf16_t* h = a.take<bf16_t>((size_t)T * H);
+    bf16_t* qkv = a.take<bf16_t>((size_t)T * QKV);
+    bf16_t* act = a.take<bf16_t>((size_t)T * F);
+    float* cs = a.take<float>((size_t)T * hd / 2);
+    float* sn = a.take<float>((size_t)T * hd / 2);
+    bf16_t* lastbuf = a.take<bf16_t>((size_t)(T > 8 ? T : 8) * H);
+    const size_t gws_bytes = prefill_w4_gemm_ws(sh, T);
+    char* gws = a.take<char>(gws_bytes);
+    VILA_REQUIRE(a.ok(), "llm_prefill_w4: workspace arena overflow");
+    if (cache != nullptr) VILA_REQUIRE(max_seqlen <= cache->max_ctx, "llm_prefill_w4: sequence (%d) longer than the KV cache (%d)", max_seqlen, cache->max_ctx);
+
+    VILA_HIP(hipMemcpyAsync(x, embeds, (size_t)T * H * 2, hipMemcpyDeviceToDevice, s));
+    VILA_TRY(launch_rope_table(positions, cs, sn, T, hd, sh.rope_theta, s));
+    bf16_t* taps = B(layer_hidden);
+    if (taps) VILA_HIP(hipMemcpyAsync(taps, x, (size_t)T * H * 2, hipMemcpyDeviceToDevice, s));
+    // only last-row logits wanted (generation): the last layer is finished for those rows alone, as in vila_llm_prefill, here by the W4 GEMVs
+    const bool prune_last = final_hidden == nullptr && all_logits == nullptr && taps == nullptr && cache != nullptr && last_logits != nullptr &&
+                            last_rows != nullptr && n_last >= 1 && n_last <= 4;
+    auto gemm4 = [&](const bf16_t* xin, const void* q, const void* sz, const void* bias, const bf16_t* res, bf16_t* y, int N, int K, int mode) {
+        GemmW4Args g{};
+        g.x = xin; g.Wq = (const uint32_t*)q; g.Wsz = (const uint32_t*)sz; g.bias = B(bias); g.residual = res; g.y = y;
+        g.M = T; g.N = N; g.K = K; g.mode = mode; g.n_rope_heads = sh.q_heads + sh.kv_heads; g.hd = hd;
+        return launch_gemm_w4(g, gws, gws_bytes, s);
+    };
+    for (int l = 0; l < sh.n_layers; ++l) {
+        const VilaLlmLayer& L = w->layers[l];
+        const VilaLlmLayerW4& Q = ql[l];
+        VILA_REQUIRE(L.bq != nullptr && B(L.bk) == B(L.bq) + QS && B(L.bv) == B(L.bk) + KS,
+                     "llm_prefill_w4: the q/k/v biases must be one contiguous q|k|v vector (layer %d)", l);
+        bf16_t* kc = nullptr; bf16_t* vc = nullptr; int max_ctx = 0;
+        if (cache != nullptr) {
+            const size_t per_layer = (size_t)cache->n_slots * sh.kv_heads * cache->max_ctx * hd;
+            kc = B(cache->k) + l * per_layer; vc = B(cache->v) + l * per_layer; max_ctx = cache->max_ctx;
+        }
+        VILA_TRY(launch_rmsnorm(x, B(L.ln1_w), h, T, H, sh.rms_eps, s));
+        VILA_TRY(gemm4(h, Q.qkv_q, Q.qkv_sz, L.bq, nullptr, qkv, QKV, H, 2));              // q | k | v + bias, natural column order
+        VILA_TRY(launch_rope_kv(qkv, cs, sn, positions, seq_of_tok, kc, vc, T, sh.q_heads, sh.kv_heads, hd, max_ctx, s));
+        AttnArgs at{};
+        at.q = qkv; at.k = qkv + QS; at.v = qkv + QS + KS; at.o = h;
+        at.q_tok_stride = at.k_tok_stride = at.v_tok_stride = QKV; at.o_tok_stride = QS;
+        at.q_head_stride = at.k_head_stride = at.v_head_stride = at.o_head_stride = hd;
+        at.cu_seqlens = cu_seqlens; at.n_seq = n_seq; at.total_tokens = T; at.max_seqlen = (cu_seqlens ? max_seqlen : T);
+        at.n_q_heads = sh.q_heads; at.n_kv_heads = sh.kv_heads; at.head_dim = hd; at.causal = 1;
+        at.scale = 1.0f / sqrtf((float)hd); at.lse = nullptr;
+        VILA_TRY(launch_attn_fwd(at, s));
+        if (l == sh.n_layers - 1 && prune_last) {
+            // generation prefill: after the last layer's K / V are in the cache, o_proj, the post-attention norm and the MLP of the asked-for
+            // rows run as the W4 decode GEMVs (modes 0 and 1), the same kernels and arithmetic order as the W4 decode step
+            VILA_TRY(launch_copy_rows(h, lastbuf, last_rows, nullptr, n_last, QS, s));
+            VILA_TRY(launch_copy_rows(x, lastbuf + (size_t)n_last * H, last_rows, nullptr, n_last, H, s));
+            for (int r = 0; r < n_last; ++r) {
+                bf16_t* ar = lastbuf + (size_t)r * H;
+                bf16_t* xr = lastbuf + (size_t)(n_last + r) * H;
+                bf16_t* fr = act + (size_t)r * F;
+                GemvW4Args o{};
+                o.x = ar; o.Wq = (const uint32_t*)Q.o_q; o.Wsz = (const uint32_t*)Q.o_sz; o.residual = xr; o.y = xr; o.N = H; o.K = QS; o.mode = 0;
+                VILA_TRY(launch_gemv_w4(o, s));
+                GemvW4Args gu{};
+                gu.x = xr; gu.norm_w = B(L.ln2_w); gu.eps = sh.rms_eps; gu.Wq = (const uint32_t*)Q.gateup_q; gu.Wsz = (const uint32_t*)Q.gateup_sz;
+                gu.y = fr; gu.N = F; gu.K = H; gu.mode = 1;
+                VILA_TRY(launch_gemv_w4(gu, s));
+                GemvW4Args dn{};
+                dn.x = fr; dn.Wq = (const uint32_t*)Q.down_q; dn.Wsz = (const uint32_t*)Q.down_sz; dn.residual = xr; dn.y = ar; dn.N = H; dn.K = F; dn.mode = 0;
+                VILA_TRY(launch_gemv_w4(dn, s));
+            }
+            break;
+        }
+        VILA_TRY(gemm4(h, Q.o_q, Q.o_sz, nullptr, x, x, H, QS, 0));                      // x += o_proj(attn)
+        VILA_TRY(launch_rmsnorm(x, B(L.ln2_w), h, T, H, sh.rms_eps, s));
+        VILA_TRY(gemm4(h, Q.gateup_q, Q.gateup_sz, nullptr, nullptr, act, F, H, 1));      // silu(gate) * up
+        VILA_TRY(gemm4(act, Q.down_q, Q.down_sz, nullptr, x, x, H, F, 0));                // x += down(...)
+        if (taps) VILA_HIP(hipMemcpyAsync(taps + (size_t)(l + 1) * T * H, x, (size_t)T * H * 2, hipMemcpyDeviceToDevice, s));
+    }
+
+    if (final_hidden != nullptr || all_logits != nullptr) {
+        bf16_t* fh = final_hidden ? B(final_hidden) : h;
+        VILA_TRY(launch_rmsnorm(x, B(w->norm_w), fh, T, H, sh.rms_eps, s));
+        if (all_logits) VILA_TRY(gemm(fh, H, w->lm_head, H, nullptr, nullptr, 0, all_logits, sh.vocab, T, sh.vocab, H, EPI_NONE, s, nullptr, 1));
+    }
+    if (n_last > 0 && last_logits != nullptr) {
+        VILA_REQUIRE(last_rows != nullptr, "llm_prefill_w4: last_rows is NULL");
+        if (!prune_last) VILA_TRY(launch_copy_rows(x, lastbuf, last_rows, nullptr, n_last, H, s));
+        if (n_last == 1) {
+            GemvArgs g{};
+            g.x = lastbuf; g.norm_w = B(w->norm_w); g.eps = sh.rms_eps; g.W = B(w->lm_head); g.y_f32 = last_logits;
+            g.N = sh.vocab; g.K = H; g.mode = 0;
+            VILA_TRY(launch_gemv(g, s));
+        } else {
+            VILA_TRY(launch_rmsnorm(lastbuf, B(w->norm_w), lastbuf, n_last, H, sh.rms_eps, s));
+            VILA_TRY(gemm(lastbuf, H, w->lm_head, H, nullptr, nullptr, 0, last_logits, sh.vocab, n_last, sh.vocab, H, EPI_NONE, s, nullptr, 1));
+        }
+    }
+    return 0;
+}

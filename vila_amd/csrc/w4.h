@@ -1,4 +1,4 @@
-// W4A16 decode GEMV arguments (gemv_w4.hip).
+// W4A16 decode GEMV (gemv_w4.hip) and prefill GEMM (gemm_w4.hip) arguments.
 #pragma once
 #include "common.h"
 
@@ -12,3 +12,14 @@ struct GemvW4Args {
     const float* part_o; const float* part_ml; int n_splits, split_keys;     // mode 4: [n_splits][K] un-normalised partial O, [n_splits][K/128][2] (m, l)
 };
 int launch_gemv_w4(const GemvW4Args& a, hipStream_t s);
+
+// Y[M][N] = X[M][K] . W^T on the same packed buffer; mode 0 plain (+bias)(+residual), 1 gate/up (2N interleaved rows -> silu(g) * u),
+// 2 qkv (first n_rope_heads heads of width hd RoPE-interleaved -> written in natural column order, + bias).  Row strides: X K, Y and residual N.
+struct GemmW4Args {
+    const bf16_t* x; const uint32_t* Wq; const uint32_t* Wsz;
+    const bf16_t* bias; const bf16_t* residual; bf16_t* y;
+    int M, N, K, mode;
+    int n_rope_heads, hd;
+};
+size_t gemm_w4_workspace_bytes(int M, int N, int K, int mode);     // fp32 K-slice slabs of an under-filled grid (0: none)
+int launch_gemm_w4(const GemmW4Args& a, void* ws, size_t ws_bytes, hipStream_t s);

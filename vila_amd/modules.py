@@ -103,6 +103,8 @@ class _HipModule(nn.Module):
 
     def refuse(self) -> None:
         """Re-establish the fused q/k/v storage after an op that re-allocated parameters (.to(), .half(), ...)."""
+        if getattr(self, "_bf16_released", False):
+            raise RuntimeError("refuse: the bf16 projection weights were freed by quantize_w4(release_bf16=True); there is no q/k/v buffer to re-fuse")
         for g in self._fused_groups:
             ts = [_get(self, m) for m in g]
             buf = torch.cat([t.data for t in ts], 0)
@@ -113,6 +115,15 @@ class _HipModule(nn.Module):
         self._invalidate()
 
     def _apply(self, fn, *a, **k):
+        if getattr(self, "_bf16_released", False):
+            # .cuda() / .to() / .half() on a model whose bf16 projections were released: the int4 copies stay where they are, so only a
+            # conversion that changes nothing is allowed (it leaves the model as it was); any other would split the model across devices / dtypes
+            probe = torch.empty(0, device=self.device, dtype=self.dtype)
+            t = fn(probe)
+            if t.device == probe.device and t.dtype == probe.dtype:
+                return self
+            raise RuntimeError(f"cannot move or convert the model to {t.device} / {t.dtype}: its bf16 projection weights were freed by "
+                               "quantize_w4(release_bf16=True) and its int4 copies stay on " + str(probe.device))
         r = super()._apply(fn, *a, **k)
         if getattr(self, "_fused_groups", None):
             self.refuse()
@@ -121,6 +132,8 @@ class _HipModule(nn.Module):
         return r
 
     def load_weights(self, w: Dict[str, torch.Tensor], prefix: str) -> None:
+        if getattr(self, "_bf16_released", False):
+            raise RuntimeError("load_weights: the bf16 projection weights were freed by quantize_w4(release_bf16=True); build a new model")
         with torch.no_grad():
             for n, p in self.named_parameters():
                 p.copy_(w[prefix + n])
@@ -347,17 +360,24 @@ class HipQwen2ForCausalLM(_HipModule):
         dev = embeds.device
         lib = _lib.load()
         w = self._struct()
-        ws = self._workspace(lib.vila_llm_prefill_workspace_bytes(C.byref(w.shape), T), dev)
+        w4 = getattr(self, "_w4", None) if getattr(self, "_w4_prefill", False) else None
+        if w4 is None:
+            self._require_bf16("the bf16 prefill")
+        ws_bytes = (lib.vila_llm_prefill_w4_workspace_bytes if w4 is not None else lib.vila_llm_prefill_workspace_bytes)(C.byref(w.shape), T)
+        ws = self._workspace(ws_bytes, dev)
         n_seq = 1 if cu_seqlens is None else cu_seqlens.numel() - 1
         n_last = 0 if last_rows is None else last_rows.numel()
         last_logits = torch.empty((n_last, c.vocab_size), device=dev, dtype=torch.float32) if n_last else None
         all_logits = torch.empty((T, c.vocab_size), device=dev, dtype=torch.float32) if want_all_logits else None
         final_hidden = torch.empty((T, c.hidden_size), device=dev, dtype=self.dtype) if want_final_hidden else None
         layer_hidden = torch.empty((c.num_hidden_layers + 1, T, c.hidden_size), device=dev, dtype=self.dtype) if want_layer_hidden else None
-        check(lib.vila_llm_prefill(C.byref(w), embeds.contiguous().data_ptr(), positions.data_ptr(), ops._p(cu_seqlens), n_seq, T,
-                                   int(max_seqlen), ops._p(seq_of_tok), C.byref(cache.c) if cache is not None else None,
-                                   ops._p(last_rows), n_last, ops._p(last_logits), ops._p(all_logits), ops._p(final_hidden),
-                                   ops._p(layer_hidden), ws.data_ptr(), ws.numel(), ops._stream()), "vila_llm_prefill")
+        args = (embeds.contiguous().data_ptr(), positions.data_ptr(), ops._p(cu_seqlens), n_seq, T, int(max_seqlen), ops._p(seq_of_tok),
+                C.byref(cache.c) if cache is not None else None, ops._p(last_rows), n_last, ops._p(last_logits), ops._p(all_logits),
+                ops._p(final_hidden), ops._p(layer_hidden), ws.data_ptr(), ws.numel(), ops._stream())
+        if w4 is not None:
+            check(lib.vila_llm_prefill_w4(C.byref(w), w4.ptr, *args), "vila_llm_prefill_w4")
+        else:
+            check(lib.vila_llm_prefill(C.byref(w), *args), "vila_llm_prefill")
         return SimpleNamespace(last_logits=last_logits, all_logits=all_logits, final_hidden=final_hidden, layer_hidden=layer_hidden)
 
     # ---- HF-style forward (inference logits / loss; no autograd here: training goes through vila_amd.train) ----
@@ -466,13 +486,55 @@ class HipQwen2ForCausalLM(_HipModule):
         self._decode = st
         return st
 
-    def quantize_w4(self, keep_logical: bool = True):
-        """Build int4 (group-128) copies of the five decoder projections: decode then runs the W4A16 GEMVs
-        (vila_llm_decode_step_w4); prefill keeps using the bf16 weights."""
+    _W4_PROJ = ("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj", "self_attn.o_proj", "mlp.gate_proj", "mlp.up_proj", "mlp.down_proj")
+
+    def quantize_w4(self, keep_logical: bool = True, prefill: bool = False, release_bf16: bool = False):
+        """Build int4 (group-128) copies of the five decoder projections: decode then runs the W4A16 GEMVs (vila_llm_decode_step_w4).
+        prefill=False (default): the prefill keeps using the bf16 weights.  prefill=True: every prefill (prefill_packed, generate, forward)
+        runs the W4A16 GEMMs as well (vila_llm_prefill_w4), so the model computes from its int4 weights alone.  release_bf16=True (needs
+        prefill=True) then frees the bf16 projection weights (`release_bf16_projections`)."""
+        if release_bf16 and not prefill:
+            raise ValueError("quantize_w4: release_bf16=True needs prefill=True (the bf16 prefill reads the bf16 projections)")
+        self._require_bf16("quantize_w4")
         from .quant import W4Weights
         self._w4 = W4Weights(self, keep_logical)
+        self._w4_prefill = bool(prefill)
         self._invalidate()
+        if release_bf16:
+            self.release_bf16_projections()
         return self._w4
+
+    def release_bf16_projections(self) -> int:
+        """Drop the bf16 q/k/v (one fused buffer), o, gate, up and down weights of every layer once the int4 copies serve both prefill and
+        decode (quantize_w4(prefill=True)).  Each projection parameter is re-pointed at a zero-element tensor [0, in_features] of its device
+        and dtype, so its storage is freed and nothing can read stale memory through it: torch ops see an empty tensor, and every path of
+        this package that would use the weights raises a RuntimeError naming release_bf16.  Returns the bytes of bf16 weights dropped."""
+        if getattr(self, "_w4", None) is None or not getattr(self, "_w4_prefill", False):
+            raise RuntimeError("release_bf16 needs quantize_w4(prefill=True) first: the bf16 prefill reads these weights")
+        proj = [_get(self, f"model.layers.{i}.{n}.weight") for i in range(self.lcfg.num_hidden_layers) for n in self._W4_PROJ]
+        proj_bytes = {}
+        for p in proj:
+            proj_bytes[p.untyped_storage().data_ptr()] = proj_bytes.get(p.untyped_storage().data_ptr(), 0) + p.numel() * p.element_size()
+        others = {p.untyped_storage().data_ptr() for n, p in self.named_parameters() if not any(f".{k}.weight" in "." + n for k in self._W4_PROJ)}
+        for p in proj:
+            st = p.untyped_storage()
+            if st.data_ptr() in others or proj_bytes[st.data_ptr()] != st.nbytes():
+                raise RuntimeError("release_bf16: the projection weights share their storage with other tensors (FlatParams?); nothing was freed")
+        freed = sum(proj_bytes.values())
+        self._invalidate()
+        self._bf16_released = True
+        for p in proj:
+            p.data = torch.empty((0,) + tuple(p.shape[1:]), device=p.device, dtype=p.dtype)
+        return freed
+
+    def _load_from_state_dict(self, *a, **k):
+        self._require_bf16("load_state_dict")
+        return super()._load_from_state_dict(*a, **k)
+
+    def _require_bf16(self, what: str) -> None:
+        if getattr(self, "_bf16_released", False):
+            raise RuntimeError(f"{what}: the bf16 projection weights were freed by quantize_w4(release_bf16=True); only the W4A16 "
+                               "prefill and decode can run on this model")
 
     def decode_step(self, cache, st) -> None:
         lib = _lib.load()
@@ -486,6 +548,7 @@ class HipQwen2ForCausalLM(_HipModule):
             check(lib.vila_llm_decode_step_w4(C.byref(self._struct()), w4.ptr, C.byref(cache.c), C.byref(st.c), st.ws.data_ptr(),
                                               st.ws.numel(), ops._stream()), "vila_llm_decode_step_w4")
             return
+        self._require_bf16("the bf16 decode step")
         if sp is not None:
             check(lib.vila_llm_decode_step_sample(C.byref(self._struct()), C.byref(cache.c), C.byref(st.c), st.ws.data_ptr(), st.ws.numel(),
                                                   C.byref(sp), ops._stream()), "vila_llm_decode_step_sample")
@@ -513,6 +576,7 @@ class HipQwen2ForCausalLM(_HipModule):
         return True
 
     def _batch_session(self, n: int, max_ctx: int, max_new_tokens: int):
+        self._require_bf16("the batched decode")
         key = (n, max_ctx, max_new_tokens, self.model.embed_tokens.weight.data_ptr(), _get(self, "model.layers.0.mlp.down_proj.weight").data_ptr())
         st = getattr(self, "_bdecode", None)
         if st is not None and st.key == key:
@@ -545,6 +609,7 @@ class HipQwen2ForCausalLM(_HipModule):
     # (re-wound after every chunk), which costs nothing extra: the step streams the weights once whatever the number of live rows.
     def batch_open(self, n_slots: int, max_ctx: int = 2048, max_new_tokens: int = 1024):
         c = self.lcfg
+        self._require_bf16("batch_open")
         if not (1 <= n_slots <= 16 and c.head_dim == 128 and max_ctx <= 2048 and getattr(self, "_w4", None) is None and self._qkv_fused()):
             raise ValueError("batch_open: the batched decode step serves 1..16 rows of a bf16 head-dim-128 model with caches <= 2048 positions")
         st = self._batch_session(max(n_slots, 2), max_ctx, max_new_tokens)

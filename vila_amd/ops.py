@@ -151,6 +151,38 @@ def gemv_w4(x: torch.Tensor, mat, norm_w: Optional[torch.Tensor] = None, eps: fl
     return y
 
 
+def gemm_w4(x: torch.Tensor, mat, bias: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
+            out: Optional[torch.Tensor] = None, heads: Optional[tuple] = None) -> torch.Tensor:
+    """W4A16 GEMM (prefill shapes) on a vila_amd.quant.W4Matrix: x [M, K] bf16 -> [M, N] bf16 = x . W^T (+bias)(+residual); gate/up
+    matrices give silu(x Wg^T) * (x Wu^T).  heads = (q_heads, kv_heads, head_dim) marks the fused q|k|v matrix of a W4 layer (rows of the
+    q and k heads RoPE-interleaved): the result comes back in natural q | k | v column order with the bias added."""
+    _need(x, name="x"); _need(mat.q, dtype=torch.int32, name="mat.q"); _need(mat.sz, dtype=torch.int32, name="mat.sz")
+    assert x.dim() == 2 and x.is_contiguous()
+    if x.shape[1] != mat.K:
+        raise ValueError(f"gemm_w4: x has {x.shape[1]} columns, the matrix {mat.K}")
+    M = x.shape[0]
+    lib = _lib.load()
+    mode = 2 if heads is not None else mat.mode
+    if out is None:
+        out = torch.empty((M, mat.N), device=x.device, dtype=torch.bfloat16)
+    if residual is not None:
+        _need(residual, name="residual"); assert residual.shape == (M, mat.N) and residual.is_contiguous()
+    nb = lib.vila_gemm_w4_workspace_bytes(M, mat.N, mat.K, mode)
+    ws = torch.empty((max(nb, 1),), device=x.device, dtype=torch.uint8)
+    if heads is not None:
+        nq, nkv, hd = (int(v) for v in heads)
+        if (nq + 2 * nkv) * hd != mat.N or mat.mode != 0:
+            raise ValueError(f"gemm_w4: heads {tuple(heads)} describe {(nq + 2 * nkv) * hd} q|k|v rows, the matrix has {mat.N} (mode {mat.mode})")
+        if residual is not None:
+            raise ValueError("gemm_w4: the q|k|v form takes no residual")
+        check(lib.vila_gemm_w4_qkv_bf16(x.data_ptr(), mat.q.data_ptr(), mat.sz.data_ptr(), _p(bias), out.data_ptr(), M, nq, nkv, hd, mat.K,
+                                        ws.data_ptr(), nb, _stream()), "gemm_w4_qkv")
+        return out
+    check(lib.vila_gemm_w4_bf16(x.data_ptr(), mat.q.data_ptr(), mat.sz.data_ptr(), _p(bias), _p(residual), out.data_ptr(), M, mat.N, mat.K,
+                                mat.mode, ws.data_ptr(), nb, _stream()), "gemm_w4")
+    return out
+
+
 def argmax(logits: torch.Tensor) -> torch.Tensor:
     _need(logits, dtype=torch.float32, name="logits")
     out = torch.empty((1,), device=logits.device, dtype=torch.int64)

@@ -36,6 +36,9 @@ class FlatParams:
     """Re-points every parameter of (llm, vision_tower, mm_projector) into one flat bf16 buffer; same layout for grads."""
 
     def __init__(self, model, with_optimizer_state: bool = True):
+        if getattr(model.llm, "_bf16_released", False):
+            raise RuntimeError("FlatParams: the LLM's bf16 projection weights were freed by quantize_w4(release_bf16=True); "
+                               "an SFT step cannot be built on the int4 copies")
         self.model = model
         entries: List[Tuple[str, torch.nn.Parameter]] = []
         for prefix, mod in (("llm.", model.llm), ("vision_tower.", model.vision_tower), ("mm_projector.", model.mm_projector)):
