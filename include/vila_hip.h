@@ -412,6 +412,20 @@ int vila_llm_decode_step_w4(const VilaLlmWeights* w, const VilaLlmLayerW4* qlaye
 int vila_llm_decode_step_w4_sample(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers /*[host]*/, const VilaKvCache* cache,
                             const VilaDecodeState* st, void* workspace, size_t workspace_bytes, const VilaSampling* sampling, vila_stream_t stream);
 
+/* W4A16 batched decode GEMV (vila_amd/csrc/gemv_w4_batch.hip) on the same packed buffers: y[m][N] = x[m][K] . W^T for the 1 <= n <= 16 rows of
+ * x (row stride ldx, a multiple of 8 elements); y and residual have row stride N.  mode 0: (+bias)(+residual; y may alias it); mode 1: W holds
+ * 2N interleaved gate/up rows, y = silu(Wg x) * (Wu x), bias and residual must be NULL.  Deterministic (fixed reduction order, no atomics);
+ * rows >= n and columns >= N of y are not written.  n outside 1..16, K % 128 != 0 or another mode -> -1. */
+int vila_gemv_w4_batch_bf16(const void* x, int64_t ldx, int n, const void* Wq, const void* Wsz, const void* bias, const void* residual,
+                            void* y, int N, int K, int mode, vila_stream_t stream);
+/* vila_llm_decode_step_batch with the q|k|v, o, gate/up and down projections of every layer read from `qlayers` [host] (W4A16 batched GEMVs).
+ * `w` still supplies embed, norms, the q/k/v biases (one contiguous q|k|v vector) and the bf16 lm_head; its projection pointers are not read.
+ * Same contract and limits as vila_llm_decode_step_batch (head_dim 128, max_ctx <= 2048, 1 <= n <= min(16, n_slots), q_heads * head_dim ==
+ * hidden), plus hidden % 128 == 0 and intermediate % 128 == 0; each is checked before anything is launched (-1). */
+size_t vila_llm_decode_batch_w4_workspace_bytes(const VilaLlmShape* s, int n);
+int vila_llm_decode_step_batch_w4(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers /*[host]*/, const VilaKvCache* cache,
+                                  const VilaDecodeBatch* st, void* workspace, size_t workspace_bytes, vila_stream_t stream);
+
 /* W4A16 prefill GEMM (vila_amd/csrc/gemm_w4.hip) on the same packed buffers: y[M][N] = x[M][K] . W^T, x bf16 row stride K, y row stride N,
  * any M >= 1.  mode 0: (+bias)(+residual, row stride N; y may alias it); mode 1: W holds 2N interleaved gate/up rows, y = silu(Wg x) * (Wu x),
  * bias and residual must be NULL.  Deterministic (K-sliced grids add their fp32 slices in a fixed order).  K % 128 != 0, N % 16 != 0, another

@@ -186,6 +186,10 @@ PROTOTYPES = {
                                         C.POINTER(VilaDecodeState), c_void_p, c_size_t, c_void_p]),
     "vila_llm_decode_step_w4_sample": (c_int, [C.POINTER(VilaLlmWeights), C.POINTER(VilaLlmLayerW4), C.POINTER(VilaKvCache),
                                                C.POINTER(VilaDecodeState), c_void_p, c_size_t, C.POINTER(VilaSampling), c_void_p]),
+    "vila_gemv_w4_batch_bf16": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "vila_llm_decode_batch_w4_workspace_bytes": (c_size_t, [C.POINTER(VilaLlmShape), c_int]),
+    "vila_llm_decode_step_batch_w4": (c_int, [C.POINTER(VilaLlmWeights), C.POINTER(VilaLlmLayerW4), C.POINTER(VilaKvCache),
+                                              C.POINTER(VilaDecodeBatch), c_void_p, c_size_t, c_void_p]),
     "vila_gemm_w4_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "vila_gemm_w4_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                   c_void_p, c_size_t, c_void_p]),

@@ -734,6 +734,34 @@ extern "C" int vila_llm_decode_step_batch(const VilaLlmWeights* w, const VilaKvC
                         st->max_out, st->logits, workspace, workspace_bytes, s);
 }
 
+// the batched step with the four projections of every layer read from the int4 layers (gemv_w4_batch.hip); embed, norms, the fused q|k|v
+// biases and the bf16 lm_head come from `w`, whose projection pointers are not read (empty after quantize_w4(release_bf16=True))
+extern "C" size_t vila_llm_decode_batch_w4_workspace_bytes(const VilaLlmShape* s, int n) {
+    return bdecode_workspace_bytes(s->hidden, s->inter, s->q_heads * s->head_dim, s->head_dim, n);
+}
+extern "C" int vila_llm_decode_step_batch_w4(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers, const VilaKvCache* cache, const VilaDecodeBatch* st,
+                                             void* workspace, size_t workspace_bytes, vila_stream_t stream) {
+    VILA_REQUIRE(w != nullptr && qlayers != nullptr && cache != nullptr && st != nullptr && workspace != nullptr, "llm_decode_batch_w4: NULL argument");
+    const VilaLlmShape& sh = w->shape;
+    hipStream_t s = S(stream);
+    const int QS = sh.q_heads * sh.head_dim, KS = sh.kv_heads * sh.head_dim;
+    std::vector<BLayer> layers(sh.n_layers);
+    std::vector<BLayerW4> ql(sh.n_layers);
+    for (int l = 0; l < sh.n_layers; ++l) {
+        const VilaLlmLayer& L = w->layers[l];
+        const VilaLlmLayerW4& Q = qlayers[l];
+        VILA_REQUIRE(L.bq != nullptr && B(L.bk) == B(L.bq) + QS && B(L.bv) == B(L.bk) + KS,
+                     "llm_decode_batch_w4: the q/k/v biases must be one contiguous q|k|v vector (layer %d)", l);
+        VILA_REQUIRE(Q.qkv_q && Q.qkv_sz && Q.o_q && Q.o_sz && Q.gateup_q && Q.gateup_sz && Q.down_q && Q.down_sz,
+                     "llm_decode_batch_w4: int4 layer %d has a NULL buffer", l);
+        layers[l] = BLayer{L.ln1_w, nullptr, L.bq, nullptr, L.ln2_w, nullptr, nullptr, nullptr};
+        ql[l] = BLayerW4{Q.qkv_q, Q.qkv_sz, Q.o_q, Q.o_sz, Q.gateup_q, Q.gateup_sz, Q.down_q, Q.down_sz};
+    }
+    BDecodeArgs m{w->embed, w->norm_w, w->lm_head, sh.hidden, sh.inter, sh.n_layers, sh.q_heads, sh.kv_heads, sh.head_dim, sh.vocab, sh.rms_eps, sh.rope_theta};
+    return bdecode_step(m, layers.data(), B(cache->k), B(cache->v), cache->max_ctx, cache->n_slots, st->n, st->pos, st->token, st->out_ids, st->n_out,
+                        st->max_out, st->logits, workspace, workspace_bytes, s, ql.data());
+}
+
 // =================================================================================================
 // hipGraph helpers
 // =================================================================================================
@@ -939,6 +967,16 @@ extern "C" int vila_gemv_w4_bf16(const void* x, const void* norm_w, float eps, c
     VILA_REQUIRE(mode == 0 || mode == 1, "vila_gemv_w4_bf16: mode must be 0 or 1");
     VILA_REQUIRE(x != nullptr && Wq != nullptr && Wsz != nullptr && y != nullptr, "vila_gemv_w4_bf16: NULL pointer");
     return launch_gemv_w4(g, S(stream));
+}
+
+extern "C" int vila_gemv_w4_batch_bf16(const void* x, int64_t ldx, int n, const void* Wq, const void* Wsz, const void* bias, const void* residual,
+                                       void* y, int N, int K, int mode, vila_stream_t stream) {
+    VILA_REQUIRE(mode == 0 || mode == 1, "vila_gemv_w4_batch_bf16: mode must be 0 or 1");
+    VILA_REQUIRE(x != nullptr && Wq != nullptr && Wsz != nullptr && y != nullptr, "vila_gemv_w4_batch_bf16: NULL pointer");
+    GemvW4BatchArgs g{};
+    g.x = B(x); g.ldx = ldx; g.Wq = (const uint32_t*)Wq; g.Wsz = (const uint32_t*)Wsz; g.bias = B(bias); g.residual = B(residual); g.ldr = N;
+    g.y = B(y); g.ldy = N; g.n = n; g.N = N; g.K = K; g.mode = mode;
+    return launch_gemv_w4_batch(g, S(stream));
 }
 
 static int decode_step_w4_impl(const VilaLlmWeights* w, const VilaLlmLayerW4* ql, const VilaKvCache* cache, const VilaDecodeState* st,

@@ -17,6 +17,7 @@
 #include "kernels.h"
 #include "gemv_common.h"
 #include "attn_common.h"
+#include "w4.h"
 #include <cstdlib>
 #include <cstring>
 
@@ -498,11 +499,14 @@ size_t bdecode_workspace_bytes(int H, int F, int QS, int hd, int n) {
 }
 
 int bdecode_step(const BDecodeArgs& m, const BLayer* layers, bf16_t* kcache, bf16_t* vcache, int max_ctx, int n_slots, int n, int32_t* pos, int64_t* token,
-                 int64_t* out_ids, int32_t* n_out, int max_out, float* logits, void* workspace, size_t workspace_bytes, hipStream_t s) {
+                 int64_t* out_ids, int32_t* n_out, int max_out, float* logits, void* workspace, size_t workspace_bytes, hipStream_t s,
+                 const BLayerW4* qlayers) {
     const int H = m.hidden, F = m.inter, hd = m.head_dim, QS = m.q_heads * hd, KS = m.kv_heads * hd;
     VILA_REQUIRE(n >= 1 && n <= 16 && n <= n_slots, "batched decode: %d sequences need 1..16 KV-cache slots (cache has %d)", n, n_slots);
     VILA_REQUIRE(QS == H, "batched decode: q_heads*head_dim (%d) must equal hidden (%d)", QS, H);
     VILA_REQUIRE(hd == 128 && max_ctx <= 2048, "batched decode: head_dim 128 and caches up to 2048 positions (got %d, %d)", hd, max_ctx);
+    VILA_REQUIRE(qlayers == nullptr || (H % 128 == 0 && F % 128 == 0),
+                 "batched W4 decode: hidden (%d) and intermediate (%d) must be multiples of the 128-wide quantisation group", H, F);
     VILA_REQUIRE(workspace_bytes >= bdecode_workspace_bytes(H, F, QS, hd, n), "batched decode: workspace too small");
     char* wp = (char*)workspace; size_t off = 0;
     auto take = [&](size_t bytes) { off = align_up(off, 256); void* r = wp + off; off += bytes; return r; };
@@ -524,19 +528,30 @@ int bdecode_step(const BDecodeArgs& m, const BLayer* layers, bf16_t* kcache, bf1
     float* pick_v = (float*)take((size_t)n * PICK_SLICES * 4);
     int* pick_i = (int*)take((size_t)n * PICK_SLICES * 4);
     VILA_REQUIRE(off <= workspace_bytes, "batched decode: workspace layout");
+    // the four projections: bf16 skinny GEMMs, or with int4 layers the W4A16 batched GEMV on the same operands and epilogue
+    auto proj = [&](const BGemmArgs& g, const void* wq, const void* wsz) -> int {
+        if (qlayers == nullptr) return launch_bgemm(g, s);
+        GemvW4BatchArgs a{};
+        a.x = g.x; a.ldx = g.ldx; a.Wq = (const uint32_t*)wq; a.Wsz = (const uint32_t*)wsz; a.bias = g.bias; a.residual = g.residual; a.ldr = g.ldr;
+        a.y = g.y; a.ldy = g.ldy; a.n = g.n; a.N = g.N; a.K = g.K; a.mode = g.mode;
+        a.q_out = g.q_out; a.ldq = g.ldq; a.kcache = g.kcache; a.vcache = g.vcache; a.slot_stride = g.slot_stride; a.pos = g.pos; a.rope_cs = g.rope_cs;
+        a.nq = g.nq; a.nkv = g.nkv; a.hd = g.hd; a.max_ctx = g.max_ctx;
+        return launch_gemv_w4_batch(a, s);
+    };
     hipLaunchKernelGGL(bdec_prologue_kernel, dim3(cdiv(H / 8, 256), n), dim3(256), 0, s, (const bf16_t*)m.embed, token, x, H, (int64_t)m.vocab, pos, rope_cs, hd, m.rope_theta);
     VILA_LAUNCH_CHECK();
     const int64_t per_layer = (int64_t)n_slots * m.kv_heads * max_ctx * hd, slot_stride = (int64_t)m.kv_heads * max_ctx * hd;
     bf16_t* cur = x; bf16_t* nxt = x2;
     for (int l = 0; l < m.n_layers; ++l) {
         const BLayer& L = layers[l];
+        const BLayerW4 Q = qlayers != nullptr ? qlayers[l] : BLayerW4{};
         bf16_t* kc = kcache + l * per_layer; bf16_t* vc = vcache + l * per_layer;
         BGemmArgs qa{};
         VILA_TRY(normed(qa, cur, L.ln1_w));
         qa.ldx = H; qa.W = (const bf16_t*)L.wqkv; qa.bias = (const bf16_t*)L.bqkv;
         qa.n = n; qa.N = QS + 2 * KS; qa.K = H; qa.mode = 2; qa.q_out = q; qa.ldq = QS; qa.kcache = kc; qa.vcache = vc; qa.slot_stride = slot_stride;
         qa.pos = pos; qa.rope_cs = rope_cs; qa.nq = m.q_heads; qa.nkv = m.kv_heads; qa.hd = hd; qa.max_ctx = max_ctx;
-        VILA_TRY(launch_bgemm(qa, s));
+        VILA_TRY(proj(qa, Q.qkv_q, Q.qkv_sz));
         AttnDecodeArgs ad{};
         ad.q = q; ad.kcache = kc; ad.vcache = vc; ad.o = ao; ad.pos_ptr = pos; ad.nq = m.q_heads; ad.nkv = m.kv_heads; ad.hd = hd; ad.max_ctx = max_ctx;
         ad.n_splits = cdiv(max_ctx, 64); ad.scale = 1.0f / sqrtf((float)hd);
@@ -548,15 +563,15 @@ int bdecode_step(const BDecodeArgs& m, const BLayer* layers, bf16_t* kcache, bf1
         if (rc == 1) VILA_TRY(launch_attn_decode_rows(ad, n, QS, QS, slot_stride, s));       // group size without an instantiation: one block per query head
         BGemmArgs o{};
         o.x = ao; o.ldx = QS; o.W = (const bf16_t*)L.wo; o.residual = cur; o.ldr = H; o.y = nxt; o.ldy = H; o.n = n; o.N = H; o.K = QS; o.mode = 0;
-        VILA_TRY(launch_bgemm(o, s));
+        VILA_TRY(proj(o, Q.o_q, Q.o_sz));
         BGemmArgs gu{};
         VILA_TRY(normed(gu, nxt, L.ln2_w));
         gu.ldx = H; gu.W = (const bf16_t*)L.w_gate; gu.W2 = (const bf16_t*)L.w_up;
         gu.y = act; gu.ldy = F; gu.n = n; gu.N = F; gu.K = H; gu.mode = 1;
-        VILA_TRY(launch_bgemm(gu, s));
+        VILA_TRY(proj(gu, Q.gateup_q, Q.gateup_sz));
         BGemmArgs dn{};
         dn.x = act; dn.ldx = F; dn.W = (const bf16_t*)L.w_down; dn.residual = nxt; dn.ldr = H; dn.y = cur; dn.ldy = H; dn.n = n; dn.N = H; dn.K = F; dn.mode = 0;
-        VILA_TRY(launch_bgemm(dn, s));
+        VILA_TRY(proj(dn, Q.down_q, Q.down_sz));
     }
     BGemmArgs lm{};
     VILA_TRY(normed(lm, cur, m.norm_w));

@@ -155,9 +155,13 @@ struct BDecodeArgs {
     int hidden, inter, n_layers, q_heads, kv_heads, head_dim, vocab; float rms_eps, rope_theta;
 };
 struct BLayer { const void *ln1_w, *wqkv, *bqkv, *wo, *ln2_w, *w_gate, *w_up, *w_down; };
+// the int4 projections of a layer (quant.py W4Weights, layout gemv_w4.hip); with them the step runs the four projections as W4A16 batched
+// GEMVs (gemv_w4_batch.hip) and reads no bf16 projection pointer of BLayer (bqkv, the fused q|k|v bias, is still read)
+struct BLayerW4 { const void *qkv_q, *qkv_sz, *o_q, *o_sz, *gateup_q, *gateup_sz, *down_q, *down_sz; };
 size_t bdecode_workspace_bytes(int H, int F, int QS, int hd, int n);
 int bdecode_step(const BDecodeArgs& m, const BLayer* layers, bf16_t* kcache, bf16_t* vcache, int max_ctx, int n_slots, int n, int32_t* pos, int64_t* token,
-                 int64_t* out_ids, int32_t* n_out, int max_out, float* logits, void* workspace, size_t workspace_bytes, hipStream_t s);
+                 int64_t* out_ids, int32_t* n_out, int max_out, float* logits, void* workspace, size_t workspace_bytes, hipStream_t s,
+                 const BLayerW4* qlayers = nullptr);
 int launch_decode_prologue(const bf16_t* table, const int64_t* tok, bf16_t* out, int H, int64_t vocab, const int32_t* pos, float* rope_cs,
                            int hd, float theta, hipStream_t s, uint32_t* chain_ctr = nullptr, int n_chain = 0);
 int launch_decode_advance(int32_t* pos, const int64_t* tok, int64_t* out_ids, int32_t* n_out, int max_out, hipStream_t s);

@@ -23,3 +23,20 @@ struct GemmW4Args {
 };
 size_t gemm_w4_workspace_bytes(int M, int N, int K, int mode);     // fp32 K-slice slabs of an under-filled grid (0: none)
 int launch_gemm_w4(const GemmW4Args& a, void* ws, size_t ws_bytes, hipStream_t s);
+
+// Y[m][N] = X[m][K] . W^T for 1 <= n <= 16 activation rows (gemv_w4_batch.hip), the batched decode's projections on the same packed
+// buffer.  mode 0 plain (+bias)(+residual, y may alias it), 1 gate/up (2N interleaved rows -> silu(g) * u), 2 q|k|v + bias + RoPE at each
+// row's position + K/V append into row m's cache slot (N = (nq + 2 nkv) hd, q/k heads RoPE-interleaved; rope_cs [n][hd] = cos | sin).
+struct GemvW4BatchArgs {
+    const bf16_t* x; int64_t ldx;                  // [n][K] activations
+    const uint32_t* Wq; const uint32_t* Wsz;
+    const bf16_t* bias;                            // [N] optional (modes 0, 2)
+    const bf16_t* residual; int64_t ldr;           // [n][N] optional (mode 0)
+    bf16_t* y; int64_t ldy;                        // [n][N] (modes 0, 1)
+    int n, N, K, mode;
+    bf16_t* q_out; int64_t ldq;                    // mode 2: [n][nq*hd]
+    bf16_t* kcache; bf16_t* vcache; int64_t slot_stride;     // this layer's [slots][nkv][max_ctx][hd]; row m uses slot m
+    const int32_t* pos; const float* rope_cs;      // [n], [n][hd]
+    int nq, nkv, hd, max_ctx;
+};
+int launch_gemv_w4_batch(const GemvW4BatchArgs& a, hipStream_t s);

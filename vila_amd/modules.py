@@ -488,17 +488,22 @@ class HipQwen2ForCausalLM(_HipModule):
 
     _W4_PROJ = ("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj", "self_attn.o_proj", "mlp.gate_proj", "mlp.up_proj", "mlp.down_proj")
 
-    def quantize_w4(self, keep_logical: bool = True, prefill: bool = False, release_bf16: bool = False):
+    def quantize_w4(self, keep_logical: bool = True, prefill: bool = False, release_bf16: bool = False, batch_decode: bool = False):
         """Build int4 (group-128) copies of the five decoder projections: decode then runs the W4A16 GEMVs (vila_llm_decode_step_w4).
         prefill=False (default): the prefill keeps using the bf16 weights.  prefill=True: every prefill (prefill_packed, generate, forward)
         runs the W4A16 GEMMs as well (vila_llm_prefill_w4), so the model computes from its int4 weights alone.  release_bf16=True (needs
-        prefill=True) then frees the bf16 projection weights (`release_bf16_projections`)."""
+        prefill=True) then frees the bf16 projection weights (`release_bf16_projections`).
+        batch_decode=False (default): generate() on a batch decodes its rows one after another with the solo W4 step, and batch_open refuses
+        the model.  batch_decode=True: generate(batch), batch_open / batch_admit / batch_run and a serving ContinuousBatcher run the W4A16
+        batched step (vila_llm_decode_step_batch_w4: one pass over the int4 weights for up to 16 rows), also after release_bf16.  Its sums
+        run in another order than the solo step's, so ids can differ from the row-by-row ones where the top-2 margin is not decisive."""
         if release_bf16 and not prefill:
             raise ValueError("quantize_w4: release_bf16=True needs prefill=True (the bf16 prefill reads the bf16 projections)")
         self._require_bf16("quantize_w4")
         from .quant import W4Weights
         self._w4 = W4Weights(self, keep_logical)
         self._w4_prefill = bool(prefill)
+        self._w4_batch = bool(batch_decode)
         self._invalidate()
         if release_bf16:
             self.release_bf16_projections()
@@ -560,9 +565,18 @@ class HipQwen2ForCausalLM(_HipModule):
     def _can_batch_decode(self, inputs_embeds, attention_mask, max_new_tokens, do_sample, forced_ids, return_logits, cache) -> bool:
         c = self.lcfg
         Bn, S = inputs_embeds.shape[0], inputs_embeds.shape[1]
-        return (not do_sample and forced_ids is None and not return_logits and cache is None and getattr(self, "_w4", None) is None and
-                max_new_tokens >= 1 and self._qkv_fused() and 2 <= Bn <= 16 and c.head_dim == 128 and c.hidden_size % 64 == 0 and c.intermediate_size % 64 == 0 and
-                ((S + max_new_tokens + 255) // 256) * 256 <= 2048)
+        return (not do_sample and forced_ids is None and not return_logits and cache is None and self.can_batch_decode_step() and
+                max_new_tokens >= 1 and (self._w4_batched() or self._qkv_fused()) and 2 <= Bn <= 16 and c.hidden_size % 64 == 0 and
+                c.intermediate_size % 64 == 0 and ((S + max_new_tokens + 255) // 256) * 256 <= 2048)
+
+    def _w4_batched(self) -> bool:
+        """The batched step reads the int4 layers (quantize_w4(batch_decode=True))."""
+        return getattr(self, "_w4", None) is not None and getattr(self, "_w4_batch", False)
+
+    def can_batch_decode_step(self) -> bool:
+        """Whether this model has a batched decode step (batch_open / continuous batching): a head-dim-128 decoder that is bf16, or
+        quantised with quantize_w4(batch_decode=True).  A model quantised without it decodes its rows one at a time."""
+        return self.lcfg.head_dim == 128 and (getattr(self, "_w4", None) is None or self._w4_batched())
 
     def _qkv_fused(self) -> bool:
         """q/k/v of every layer are views of one buffer (the batched step reads them as ONE [q + 2kv, hidden] matrix); `refuse()` re-establishes
@@ -576,8 +590,12 @@ class HipQwen2ForCausalLM(_HipModule):
         return True
 
     def _batch_session(self, n: int, max_ctx: int, max_new_tokens: int):
-        self._require_bf16("the batched decode")
-        key = (n, max_ctx, max_new_tokens, self.model.embed_tokens.weight.data_ptr(), _get(self, "model.layers.0.mlp.down_proj.weight").data_ptr())
+        w4 = self._w4_batched()
+        if not w4:
+            self._require_bf16("the batched decode")
+        # a W4 session's graph bakes the int4 buffers' pointers: a re-quantise must not replay it
+        q4 = self._w4.mats[0]["down"].q.data_ptr() if w4 else None
+        key = (n, max_ctx, max_new_tokens, self.model.embed_tokens.weight.data_ptr(), _get(self, "model.layers.0.mlp.down_proj.weight").data_ptr(), q4)
         st = getattr(self, "_bdecode", None)
         if st is not None and st.key == key:
             return st
@@ -592,7 +610,8 @@ class HipQwen2ForCausalLM(_HipModule):
             st.out_ids = torch.zeros((n, max(max_new_tokens, 1)), device=dev, dtype=torch.int64)
             st.n_out = torch.zeros(n, device=dev, dtype=torch.int32)
             st.logits = torch.zeros((n, self.lcfg.vocab_size), device=dev, dtype=torch.float32)
-            st.ws = torch.empty((lib.vila_llm_decode_batch_workspace_bytes(C.byref(w.shape), n),), device=dev, dtype=torch.uint8)
+            ws_bytes = lib.vila_llm_decode_batch_w4_workspace_bytes if w4 else lib.vila_llm_decode_batch_workspace_bytes
+            st.ws = torch.empty((ws_bytes(C.byref(w.shape), n),), device=dev, dtype=torch.uint8)
         st.c = _lib.VilaDecodeBatch(n, st.pos.data_ptr(), st.token.data_ptr(), st.out_ids.data_ptr(), st.n_out.data_ptr(), max(max_new_tokens, 1),
                                     st.logits.data_ptr())
         st.stream = torch.cuda.Stream(device=dev)
@@ -600,6 +619,10 @@ class HipQwen2ForCausalLM(_HipModule):
         return st
 
     def _batch_step(self, st) -> None:
+        if self._w4_batched():
+            check(_lib.load().vila_llm_decode_step_batch_w4(C.byref(self._struct()), self._w4.ptr, C.byref(st.cache.c), C.byref(st.c), st.ws.data_ptr(),
+                                                            st.ws.numel(), ops._stream()), "vila_llm_decode_step_batch_w4")
+            return
         check(_lib.load().vila_llm_decode_step_batch(C.byref(self._struct()), C.byref(st.cache.c), C.byref(st.c), st.ws.data_ptr(), st.ws.numel(),
                                                      ops._stream()), "vila_llm_decode_step_batch")
 
@@ -608,10 +631,11 @@ class HipQwen2ForCausalLM(_HipModule):
     # KV slot, set the row's position and first token, replay the same captured graph.  A free row idles at positions 0..15 of its own slot
     # (re-wound after every chunk), which costs nothing extra: the step streams the weights once whatever the number of live rows.
     def batch_open(self, n_slots: int, max_ctx: int = 2048, max_new_tokens: int = 1024):
-        c = self.lcfg
-        self._require_bf16("batch_open")
-        if not (1 <= n_slots <= 16 and c.head_dim == 128 and max_ctx <= 2048 and getattr(self, "_w4", None) is None and self._qkv_fused()):
-            raise ValueError("batch_open: the batched decode step serves 1..16 rows of a bf16 head-dim-128 model with caches <= 2048 positions")
+        if not self._w4_batched():
+            self._require_bf16("batch_open")
+        if not (1 <= n_slots <= 16 and max_ctx <= 2048 and self.can_batch_decode_step() and (self._w4_batched() or self._qkv_fused())):
+            raise ValueError("batch_open: the batched decode step serves 1..16 rows of a head-dim-128 model (bf16, or quantize_w4(batch_decode=True)) "
+                             "with caches <= 2048 positions")
         st = self._batch_session(max(n_slots, 2), max_ctx, max_new_tokens)
         st.pos.zero_(); st.n_out.zero_(); st.token.zero_()
         if st.graph is None:

@@ -151,6 +151,25 @@ def gemv_w4(x: torch.Tensor, mat, norm_w: Optional[torch.Tensor] = None, eps: fl
     return y
 
 
+def gemv_w4_batch(x: torch.Tensor, mat, bias: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """W4A16 batched decode GEMV on a vila_amd.quant.W4Matrix: x [n, K] bf16 (1 <= n <= 16 rows) -> [n, N] bf16 = x . W^T (+bias)(+residual
+    [n, N]); gate/up matrices give silu(x Wg^T) * (x Wu^T) and take no bias or residual.  Rows of `out` beyond n are not written."""
+    _need(x, name="x"); _need(mat.q, dtype=torch.int32, name="mat.q"); _need(mat.sz, dtype=torch.int32, name="mat.sz")
+    assert x.dim() == 2 and x.stride(1) == 1
+    if x.shape[1] != mat.K:
+        raise ValueError(f"gemv_w4_batch: x has {x.shape[1]} columns, the matrix {mat.K}")
+    n = x.shape[0]
+    if out is None:
+        out = torch.empty((n, mat.N), device=x.device, dtype=torch.bfloat16)
+    assert out.is_contiguous() and out.shape[1] == mat.N and out.shape[0] >= n
+    if residual is not None:
+        _need(residual, name="residual"); assert residual.shape == (n, mat.N) and residual.is_contiguous()
+    check(_lib.load().vila_gemv_w4_batch_bf16(x.data_ptr(), x.stride(0), n, mat.q.data_ptr(), mat.sz.data_ptr(), _p(bias), _p(residual),
+                                              out.data_ptr(), mat.N, mat.K, mat.mode, _stream()), "gemv_w4_batch")
+    return out
+
+
 def gemm_w4(x: torch.Tensor, mat, bias: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
             out: Optional[torch.Tensor] = None, heads: Optional[tuple] = None) -> torch.Tensor:
     """W4A16 GEMM (prefill shapes) on a vila_amd.quant.W4Matrix: x [M, K] bf16 -> [M, N] bf16 = x . W^T (+bias)(+residual); gate/up

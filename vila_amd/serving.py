@@ -804,6 +804,13 @@ def _request_models():
     return _MODELS
 
 
+def continuous_batching(model) -> bool:
+    """`create_app`'s choice of batcher: `ContinuousBatcher` when the model's LLM has the batched decode step (its `can_batch_decode_step()`:
+    a bf16 head-dim-128 decoder, or one quantised with quantize_w4(batch_decode=True)), else the static-window `RequestBatcher`."""
+    pred = getattr(getattr(model, "llm", None), "can_batch_decode_step", None)
+    return bool(pred()) if callable(pred) else False
+
+
 def create_app(model, tokenizer, model_name: str = "NVILA-8B", batch_window_s: Optional[float] = None, max_batch: int = 8,
                stream_timeout_s: Optional[float] = 600.0):
     """FastAPI app with the reference's POST /chat/completions (server.py:171-290).  Import-time optional: needs fastapi + pydantic.
@@ -817,12 +824,7 @@ def create_app(model, tokenizer, model_name: str = "NVILA-8B", batch_window_s: O
     app = FastAPI()
     batcher = None
     if batch_window_s is not None:
-        # continuous batching when the model has the batched decode step (a bf16 head-dim-128 decoder); else the static-window batcher
-        try:
-            ok = hasattr(model.llm, "batch_open") and model.llm.lcfg.head_dim == 128 and getattr(model.llm, "_w4", None) is None
-        except AttributeError:
-            ok = False
-        batcher = ContinuousBatcher(HipBatchEngine(model, tokenizer, n_slots=max_batch), max_batch=max_batch) if ok else \
+        batcher = ContinuousBatcher(HipBatchEngine(model, tokenizer, n_slots=max_batch), max_batch=max_batch) if continuous_batching(model) else \
             RequestBatcher(model, tokenizer, window_s=batch_window_s)
     app.state.batcher = batcher
 
