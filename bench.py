@@ -14,9 +14,12 @@ environment) it re-executes itself under torch.distributed.run on 127.0.0.1 — 
 (`torchrun --nproc_per_node`, scripts/NVILA-Lite/sft.sh:15-17).  `--selftest` runs only the harness (rendezvous, barrier, max-over-
 ranks timing, the one JSON line) on the gloo backend without touching a GPU: tests/test_bench_launcher_cpu.py drives it with 2 ranks.
 
-Besides the decode metric the default line carries `prefill` (TTFT as TFLOP/s against the MFMA peak) and `sft` (one warm + two timed
-NVILA-8B SFT steps, BASELINE configs[2] per-GPU workload) so that the MFMA-bound halves of the north star are driver-observed too,
-and `sustained` (a >= 2 s decode replay after the timed region, so that a 5-s GPU-busy sampler has something to see).
+A plain run does what its headline figure needs and nothing else: it builds the model, runs the prefill the decode starts from, warms up,
+times the steps, writes `--dump-outputs` and prints the line.  `--full` adds everything else the benchmark measures, on top of the same
+timed steps: `ttft_ms` (median of 5) and `prefill` (TTFT as TFLOP/s against the MFMA peak), `roofline` (the dominant decode kernel timed on
+its own), `sft` (one warm + two timed NVILA-8B SFT steps, BASELINE configs[2] per-GPU workload; with N > 1 the gradient exchange on every
+rank), `sustained` (a >= 6 s decode replay after the timed region, so that a 5-s GPU-busy sampler has something to see) and `cpu_baseline`.
+`--no-sft`, `--no-sustain` and `--no-cpu-baseline` leave single blocks of a `--full` line out.
 
 `--dump-outputs DIR` writes what the last timed step computed, as a caller of that path would receive it, to DIR/<name>.npy (float32, or float64
 for ids; 64 MB at most): decode `last_logits` + `token_ids` (the prefill's token and every generated one), sft `loss` + `params_sample` (a fixed
@@ -52,9 +55,12 @@ def parse(argv=None):
     ap.add_argument("--steps", type=int, default=None, help="timed steps (default: 128 in decode mode, 3 in sft and video mode)")
     ap.add_argument("--warmup", type=int, default=None, help="untimed steps before them (default: 16 in decode mode, 1 in sft mode)")
     ap.add_argument("--prompt-tokens", type=int, default=512)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-sft", action="store_true", help="decode mode: skip the bounded SFT sub-measurement (1 warm + 2 timed steps)")
-    ap.add_argument("--no-sustain", action="store_true", help="decode mode: skip the >= 2 s sustained replay after the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="decode mode: also measure TTFT + prefill roofline, the dominant kernel's roofline, the SFT step, the sustained replay and "
+                         "the CPU baseline (the default line carries the timed decode only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-sft", action="store_true", help="--full: skip the bounded SFT sub-measurement (1 warm + 2 timed steps)")
+    ap.add_argument("--no-sustain", action="store_true", help="--full: skip the >= 6 s sustained replay after the timed region")
     ap.add_argument("--eager-decode", action="store_true", help="experiment: launch the kernels of a token eagerly instead of replaying a hipGraph")
     ap.add_argument("--config", default="nvila_8b", choices=["nvila_8b", "reduced", "nvila_lite_3b"],
                     help="nvila_lite_3b = BASELINE configs[0] on the GPU (3x3 projector, 2048-wide 36-layer tied-head LLM; use --prompt-tokens 32)")
@@ -231,7 +237,8 @@ def selftest_main(a, rank, world):
     step = lambda: time.sleep(0.002)
     # dry run of the SFT data-parallel plumbing (no kernels): the trainer's flat buffers over a tiny CPU model, the global token count, the
     # media agreement and every gradient bucket's exchange over the process group, in the backward order the real step announces them.
-    # `--mode sft` times it; the default mode runs it once — the GPU default mode runs the real SFT side measurement on every rank.
+    # `--mode sft` times it; the default mode runs it once, with or without --full (it costs no GPU time) — the GPU default mode runs the
+    # real SFT side measurement on every rank under --full.
     from vila_amd import configs
     from vila_amd.train import SFTTrainer
     from vila_amd.vlm import HipLlavaLlamaModel
@@ -750,7 +757,7 @@ def decode_main(a, rank, world, dev, dist):
     max_new = a.steps + a.warmup + 2
     cache = llm.new_cache(((S + max_new + 255) // 256) * 256)
 
-    # ---- TTFT: pixels + ids resident on the device -> first token id on the host ----
+    # ---- prefill: pixels + ids resident on the device -> first token id on the host (the KV cache and token the decode starts from) ----
     def ttft_once():
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -760,32 +767,35 @@ def decode_main(a, rank, world, dev, dist):
         first = int(ops.argmax(r.last_logits[0]))
         return time.perf_counter() - t0, first, e
 
-    ttft_once()
-    tt = []
-    for _ in range(5):
-        t, first, e = ttft_once()
-        tt.append(t)
-    ttft = statistics.median(tt)
-    # the encoder part alone (ViT + projector), HIP-event timed on the current stream
-    ev_a, ev_b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    bs = media_cfg.get("image", {}).get("block_sizes")
-    torch.cuda.synchronize()
-    ev_a.record()
-    for _ in range(3):
-        model.encode_images(pixels, block_sizes=bs)
-    ev_b.record()
-    torch.cuda.synchronize()
-    encode_ms = ev_a.elapsed_time(ev_b) / 3
-    prefill_flops = vit_flops(cfg, n_tiles) + projector_flops(cfg, n_tiles) + llm_prefill_flops(cfg, S)
-    pre_traffic = None          # L2-fill bytes of the prefill's dominant kernel (fused gate/up GEMM) from the committed --pmc passes of THIS command
-    tj = next((p_ for p_ in (os.path.join(ROOT, "profiles", n_) for n_ in ("r06_pmc_traffic.json", "r05_pmc_traffic.json", "r04_pmc_traffic.json", "r03_pmc_traffic.json")) if os.path.exists(p_)), None)
-    if a.config == "nvila_8b" and not a.dynamic_s2 and tj is not None:
-        with open(tj) as f:
-            pre_traffic = json.load(f).get("prefill_gateup")
-    prefill = {"ttft_ms": round(ttft * 1e3, 3), "encode_images_ms": round(encode_ms, 3), "tflop": round(prefill_flops / 1e12, 3),
-               "roofline": {"bound": "mfma", "achieved": round(prefill_flops / ttft / 1e12, 1), "peak": MFMA_PEAK_TF, "unit": "TFLOP/s",
-                            "frac": round(prefill_flops / ttft / (MFMA_PEAK_TF * 1e12), 4), "traffic": pre_traffic,
-                            "note": "algorithmic FLOPs of ViT (26 layers) + projector + LLM prefill + last-row lm_head (SURVEY §8d) / host-observed TTFT"}}
+    _, first, _ = ttft_once()
+    ttft, prefill = None, None
+    if a.full:
+        # ---- TTFT: median of 5 after the run above (the warm one) ----
+        tt = []
+        for _ in range(5):
+            t, first, e = ttft_once()
+            tt.append(t)
+        ttft = statistics.median(tt)
+        # the encoder part alone (ViT + projector), HIP-event timed on the current stream
+        ev_a, ev_b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        bs = media_cfg.get("image", {}).get("block_sizes")
+        torch.cuda.synchronize()
+        ev_a.record()
+        for _ in range(3):
+            model.encode_images(pixels, block_sizes=bs)
+        ev_b.record()
+        torch.cuda.synchronize()
+        encode_ms = ev_a.elapsed_time(ev_b) / 3
+        prefill_flops = vit_flops(cfg, n_tiles) + projector_flops(cfg, n_tiles) + llm_prefill_flops(cfg, S)
+        pre_traffic = None          # L2-fill bytes of the prefill's dominant kernel (fused gate/up GEMM) from the committed --pmc passes of THIS command
+        tj = next((p_ for p_ in (os.path.join(ROOT, "profiles", n_) for n_ in ("r06_pmc_traffic.json", "r05_pmc_traffic.json", "r04_pmc_traffic.json", "r03_pmc_traffic.json")) if os.path.exists(p_)), None)
+        if a.config == "nvila_8b" and not a.dynamic_s2 and tj is not None:
+            with open(tj) as f:
+                pre_traffic = json.load(f).get("prefill_gateup")
+        prefill = {"ttft_ms": round(ttft * 1e3, 3), "encode_images_ms": round(encode_ms, 3), "tflop": round(prefill_flops / 1e12, 3),
+                   "roofline": {"bound": "mfma", "achieved": round(prefill_flops / ttft / 1e12, 1), "peak": MFMA_PEAK_TF, "unit": "TFLOP/s",
+                                "frac": round(prefill_flops / ttft / (MFMA_PEAK_TF * 1e12), 4), "traffic": pre_traffic,
+                                "note": "algorithmic FLOPs of ViT (26 layers) + projector + LLM prefill + last-row lm_head (SURVEY §8d) / host-observed TTFT"}}
 
     if a.w4:
         w4 = llm.quantize_w4(keep_logical=False)     # decode now streams int4 weights; the prefill above used bf16
@@ -843,6 +853,38 @@ def decode_main(a, rank, world, dev, dist):
     step_bytes = decode_bytes_per_token(cfg, ctx_mid, a.w4)
     step_s = elapsed / a.steps
     launches = int(lib.vila_llm_decode_launches(C.byref(llm._struct().shape), cache.max_ctx))
+
+    def line(sft, cpu):
+        value = world * a.steps / elapsed
+        out = {
+            "metric": "decode tokens/sec + TTFT, NVILA-Lite-3B-shaped 1-image prompt (BASELINE configs[0] on the GPU)" if a.config == "nvila_lite_3b" else
+                      "decode tokens/sec + TTFT, NVILA-8B 1-image prompt",
+            "value": round(value, 2), "unit": "tokens/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+            "ms_per_step": round(step_s * 1e3, 4), "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": round(value / A100_DECODE_TOKS, 3) if a.config == "nvila_8b" else None,
+            "vs_baseline_note": "value / 82.1 tok/s (NVILA-8B FP16 on ONE A100, TinyChat backend, README.md:65) — other hardware and fp16; no MI355X number is published",
+            "dtype": "w4a16 (int4 group-128 weights, bf16 activations, fp32 accumulate)" if a.w4 else "bf16",
+            "data": f"synthetic (seeded random weights at {cfg.name} shapes; U(-1,1) pixels; random prompt ids)",
+        }
+        if a.full:
+            out.update({"ttft_ms": round(ttft * 1e3, 3),
+                        "ttft_note": "median of 5: pixels+ids on device -> ViT(26 layers) + mm_projector + splice + 769-token prefill + argmax -> id on host"})
+        out["config"] = {
+            "workload": f"{cfg.name} {'W4A16 decode / bf16 prefill' if a.w4 else 'bf16'}{' + W8A8 vision tower' if a.w8_vit else ''}, 1x448^2 image + {a.prompt_tokens}-token prompt (S={S}), batch 1, greedy decode, "
+                        f"context {S + a.warmup}..{S + a.warmup + a.steps}", "parallelism": f"replicas x{world}" if world > 1 else "single GPU",
+            "decode": f"hipGraph replay of {launches} launches/token" + (", kernels chained over two streams (each streams its weights under its predecessor's tail)" if chained else ""),
+            **({"parity": "unpinned against the reference (its quantised backend, TinyChat / llm-awq, is external: no reference-held vectors); "
+                          "pinned against the dequantise-then-fp32 oracle of the same quantised weights"} if (a.w4 or a.w8_vit) else {})}
+        if a.full:
+            out.update({"roofline": roofline, "prefill": prefill, "sft": sft, "sustained": sustained, "cpu_baseline": cpu})
+        return out
+
+    if not a.full:                     # a plain run: the timed decode is all its line needs
+        if rank == 0:
+            print(json.dumps(line(None, None)))
+        if dist is not None:
+            dist.destroy_process_group()
+        return
 
     # ---- sustained replay (>= 6 s of back-to-back tokens; context rewound whenever the cache fills) ----
     sustained = None
@@ -917,35 +959,10 @@ def decode_main(a, rank, world, dev, dist):
                                "frac": round(step_bytes / step_s / 1e9 / HBM_PEAK_GBS, 4),
                                "gpu_ms_per_step_hip_events": round(ev0.elapsed_time(ev1) / a.steps, 4)}}
 
-    def line(sft, cpu):
-        value = world * a.steps / elapsed
-        return {
-            "metric": "decode tokens/sec + TTFT, NVILA-Lite-3B-shaped 1-image prompt (BASELINE configs[0] on the GPU)" if a.config == "nvila_lite_3b" else
-                      "decode tokens/sec + TTFT, NVILA-8B 1-image prompt",
-            "value": round(value, 2), "unit": "tokens/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-            "ms_per_step": round(step_s * 1e3, 4), "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": round(value / A100_DECODE_TOKS, 3) if a.config == "nvila_8b" else None,
-            "vs_baseline_note": "value / 82.1 tok/s (NVILA-8B FP16 on ONE A100, TinyChat backend, README.md:65) — other hardware and fp16; no MI355X number is published",
-            "dtype": "w4a16 (int4 group-128 weights, bf16 activations, fp32 accumulate)" if a.w4 else "bf16",
-            "data": f"synthetic (seeded random weights at {cfg.name} shapes; U(-1,1) pixels; random prompt ids)",
-            "ttft_ms": round(ttft * 1e3, 3),
-            "ttft_note": "median of 5: pixels+ids on device -> ViT(26 layers) + mm_projector + splice + 769-token prefill + argmax -> id on host",
-            "config": {"workload": f"{cfg.name} {'W4A16 decode / bf16 prefill' if a.w4 else 'bf16'}{' + W8A8 vision tower' if a.w8_vit else ''}, 1x448^2 image + {a.prompt_tokens}-token prompt (S={S}), batch 1, greedy decode, "
-                                   f"context {S + a.warmup}..{S + a.warmup + a.steps}", "parallelism": f"replicas x{world}" if world > 1 else "single GPU",
-                       "decode": f"hipGraph replay of {launches} launches/token" + (", kernels chained over two streams (each streams its weights under its predecessor's tail)" if chained else ""),
-                       **({"parity": "unpinned against the reference (its quantised backend, TinyChat / llm-awq, is external: no reference-held vectors); "
-                                     "pinned against the dequantise-then-fp32 oracle of the same quantised weights"} if (a.w4 or a.w8_vit) else {})},
-            "roofline": roofline,
-            "prefill": prefill,
-            "sft": sft,
-            "sustained": sustained,
-            "cpu_baseline": cpu,
-        }
-
     # ---- bounded SFT sub-measurement: 1 warm + 2 timed steps of the configs[2] per-GPU workload (needs ~150 GB of the 288 GB).  With
-    # world > 1 (the driver's `bench.py --gpus N`) EVERY rank runs it with the process group: the per-layer gradient buckets go through RCCL's
+    # world > 1 (`bench.py --gpus N --full`) EVERY rank runs it with the process group: the per-layer gradient buckets go through RCCL's
     # SUM all-reduce under the backward (replaces scripts/zero3.json + transformer_normalize_monkey_patch.py:242-263), so the
-    # scaling runs exercise the 16.1 GB exchange without any extra flag.  The decode line above is complete at this point: with world > 1 a
+    # scaling runs under --full exercise the 16.1 GB exchange.  The decode line above is complete at this point: with world > 1 a
     # deadline guards it, so a rank that dies inside a step (the others would sit in its all-reduce until RCCL's watchdog ends the job
     # without any output) costs the `sft` block, not the measurement. ----
     sft = None

@@ -33,6 +33,15 @@ def test_gpus_2_spawns_two_ranks_and_prints_one_line():
     assert sft["exchange_bytes"] > 0 and sft["buckets"] >= 8
 
 
+def test_full_is_an_opt_in_that_leaves_the_selftest_line_whole():
+    """`--full` (the decode mode's side measurements) is off by default; the selftest's line and its SFT dry run do not depend on it."""
+    bench = _bench_module()
+    assert bench.parse([]).full is False and bench.parse(["--full"]).full is True
+    plain = _run(["--gpus", "1", "--selftest", "--steps", "2", "--warmup", "0"])
+    full = _run(["--gpus", "1", "--selftest", "--full", "--steps", "2", "--warmup", "0"])
+    assert sorted(plain) == sorted(full) and plain["sft"]["exchange_ok"] is True and full["sft"]["exchange_ok"] is True
+
+
 def test_single_rank_needs_no_launcher():
     out = _run(["--gpus", "1", "--selftest", "--steps", "3", "--warmup", "0"])
     assert out["n_gpus"] == 1 and out["config"]["group_world_size"] == 1

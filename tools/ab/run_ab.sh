@@ -12,7 +12,7 @@ for rep in 1 2; do for v in old new; do
 done; done
 for v in old new old new; do
   use $v
-  timeout 300 python bench.py --no-sft --no-sustain --no-cpu-baseline --steps 32 --warmup 8 2>/dev/null | tail -1 > $O/bench_$v.json
+  timeout 300 python bench.py --full --no-sft --no-sustain --no-cpu-baseline --steps 32 --warmup 8 2>/dev/null | tail -1 > $O/bench_$v.json
   python -c "import json; d=json.loads(open('$O/bench_$v.json').read()); print('$v: decode', d['value'], 'ttft', d['ttft_ms'])"
 done
 use new

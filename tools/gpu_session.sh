@@ -17,7 +17,7 @@ case $step in
 import json; d=json.loads(open('$O/warm_$mb.json').read().strip().splitlines()[-1]); print('warm MB $mb: value', d['value'], 'ms/step', d['ms_per_step'])" || tail -3 "$O/warm_$mb.err"; done ;;
   seam)      timeout 600 python -m pytest tests/test_gpu_train.py -m gpu -q -k "seam or per_bucket" 2>&1 | tail -8 ;;
   ex)        timeout 900 python -m pytest tests/test_gpu_ops.py tests/test_gpu_model.py -m gpu -q -k "leftover or tail_rows or gateup or splitk or gemm_plain" 2>&1 | tail -8
-             for e in 0 1; do VILA_GEMM_EX=$e timeout 300 python bench.py --no-sft --no-sustain --no-cpu-baseline --steps 32 --warmup 8 > "$O/ex_$e.json" 2> "$O/ex_$e.err"; python -c "
+             for e in 0 1; do VILA_GEMM_EX=$e timeout 300 python bench.py --full --no-sft --no-sustain --no-cpu-baseline --steps 32 --warmup 8 > "$O/ex_$e.json" 2> "$O/ex_$e.err"; python -c "
 import json; d=json.loads(open('$O/ex_$e.json').read().strip().splitlines()[-1]); print('EX=$e: ttft', d['ttft_ms'], 'value', d['value'])" || tail -3 "$O/ex_$e.err"; done
              for e in 0 1; do VILA_GEMM_EX=$e timeout 300 tools/gemm_bench fwd > "$O/gemm_fwd_ex$e.log" 2>&1; grep -E "sched=0 " "$O/gemm_fwd_ex$e.log" | head -24; done ;;
   batch)     timeout 900 python -m pytest tests/test_gpu_batch_decode.py -m gpu -q 2>&1 | tail -25
@@ -34,7 +34,7 @@ import json; d=json.loads(open('$O/batch_$b.json').read().strip().splitlines()[-
              paste -d'\n' "$O/attn_v1.log" "$O/attn_new.log" ;;
   sft)       for i in 1 2; do timeout 400 python bench.py --mode sft --steps 4 --warmup 2 2>"$O/sft_$i.err" | tee "$O/sft_$i.json" | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('sft ->', d['ms_per_step'], 'ms  loss', d.get('loss'))"; done ;;
   sft_s2)    timeout 600 python bench.py --mode sft --dynamic-s2 --micro-batch 1 --steps 3 --warmup 1 2>"$O/sft_s2.err" | tee "$O/sft_s2.json" | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('sft dynamic_s2 ->', d['ms_per_step'], 'ms  frac', d['roofline']['frac'])" ;;
-  bench)     timeout 600 python bench.py > "$O/bench.json" 2> "$O/bench.err"; python - "$O/bench.json" <<'P'
+  bench)     timeout 600 python bench.py --full > "$O/bench.json" 2> "$O/bench.err"; python - "$O/bench.json" <<'P'
 import json,sys
 try:
     d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
@@ -43,20 +43,20 @@ except Exception as e:
     print("bench parse failed", e)
 P
              ;;
-  bench_fast) timeout 400 python bench.py --no-sft --no-sustain --no-cpu-baseline > "$O/bench_fast.json" 2> "$O/bench_fast.err"; python -c "
+  bench_fast) timeout 400 python bench.py --full --no-sft --no-sustain --no-cpu-baseline > "$O/bench_fast.json" 2> "$O/bench_fast.err"; python -c "
 import json; d=json.loads(open('$O/bench_fast.json').read().strip().splitlines()[-1]); print('value', d['value'], 'ttft', d['ttft_ms'], 'prefill frac', d['prefill']['roofline']['frac'])" ;;
   video)     for args in "--mode video" "--mode video --tsp"; do timeout 400 python bench.py $args 2>>"$O/video.err" | tail -1 | tee -a "$O/video.jsonl" | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['config']['workload'][:60], d['value'], 'ms encode', d['encode_ms'], 'prefill', d['llm_prefill_ms'])"; done ;;
   chain_tests) timeout 1200 python -m pytest tests/test_gpu_model.py tests/test_gpu_batch_decode.py tests/test_gpu_serving.py tests/test_gpu_sampling.py -m gpu -q -x 2>&1 | tail -25 > "$O/pytest_chain.log"; tail -25 "$O/pytest_chain.log" ;;
   full_depth) timeout 1200 python -m pytest tests/test_gpu_full_depth.py -m gpu -q -s -k "${FD_K:-full_depth}" 2>&1 | grep -v "^$" > "$O/pytest_full_depth.log"; grep -n "full depth\|forward loss\|Error\|passed\|failed" "$O/pytest_full_depth.log" | cut -c1-600 | tail -30 ;;
-  chain_ab)  for cv in "0 95" "1 95" "1 80" "1 110"; do set -- $cv; VILA_DECODE_CHAIN=$1 VILA_DECODE_CHAIN_PRED=$2 timeout 300 python bench.py --no-sft --no-sustain --no-cpu-baseline --steps 64 --warmup 8 > "$O/chain_$1_$2.json" 2> "$O/chain_$1_$2.err"; python -c "
+  chain_ab)  for cv in "0 95" "1 95" "1 80" "1 110"; do set -- $cv; VILA_DECODE_CHAIN=$1 VILA_DECODE_CHAIN_PRED=$2 timeout 300 python bench.py --full --no-sft --no-sustain --no-cpu-baseline --steps 64 --warmup 8 > "$O/chain_$1_$2.json" 2> "$O/chain_$1_$2.err"; python -c "
 import json; d=json.loads(open('$O/chain_$1_$2.json').read().strip().splitlines()[-1]); print('chain=$1 pred=$2: value', d['value'], 'ms/step', d['ms_per_step'], 'ttft', d['ttft_ms'], 'gateup us', d['roofline']['avg_launch_us'])" || tail -5 "$O/chain_$1_$2.err"; done ;;
   chain_prof) timeout 600 bash tools/profile.sh chain --no-sft --no-sustain --no-cpu-baseline --steps 32 --warmup 8 2>&1 | tail -2
              python tools/rocpd_summary.py "$GRAFT_REPO_ROOT/gpurun_out/prof_chain/trace_results.db" "$O/chain_kernel_stats.csv"; head -8 "$O/chain_kernel_stats.csv"
              python tools/rocpd_rows.py "$GRAFT_REPO_ROOT/gpurun_out/prof_chain/trace_results.db" decode_prologue_kernel decode_advance_kernel -3 "$O/chain_token_rows.txt"; head -34 "$O/chain_token_rows.txt"
              rm -f "$GRAFT_REPO_ROOT/gpurun_out/prof_chain/trace_results.db" ;;
-  bpc2)      VILA_DECODE_CHAIN=0 VILA_GEMV_BPC=2 timeout 300 python bench.py --no-sft --no-sustain --no-cpu-baseline --steps 64 --warmup 8 > "$O/bpc2.json" 2> "$O/bpc2.err"; python -c "
+  bpc2)      VILA_DECODE_CHAIN=0 VILA_GEMV_BPC=2 timeout 300 python bench.py --full --no-sft --no-sustain --no-cpu-baseline --steps 64 --warmup 8 > "$O/bpc2.json" 2> "$O/bpc2.err"; python -c "
 import json; d=json.loads(open('$O/bpc2.json').read().strip().splitlines()[-1]); print('chain=0 bpc=2: value', d['value'], 'ms/step', d['ms_per_step'], 'gateup us', d['roofline']['avg_launch_us'])" || tail -5 "$O/bpc2.err" ;;
-  fuse_ab)   for c in 0 1 0 1; do VILA_FUSE_NORM=$c timeout 300 python bench.py --no-sft --no-sustain --no-cpu-baseline --steps 32 --warmup 8 > "$O/fuse_$c.json" 2> "$O/fuse_$c.err"; python -c "
+  fuse_ab)   for c in 0 1 0 1; do VILA_FUSE_NORM=$c timeout 300 python bench.py --full --no-sft --no-sustain --no-cpu-baseline --steps 32 --warmup 8 > "$O/fuse_$c.json" 2> "$O/fuse_$c.err"; python -c "
 import json; d=json.loads(open('$O/fuse_$c.json').read().strip().splitlines()[-1]); print('fuse_norm=$c: ttft', d['ttft_ms'], 'encode', d['prefill']['encode_images_ms'], 'value', d['value'])" || tail -5 "$O/fuse_$c.err"; done ;;
   fuse_tests) timeout 1200 python -m pytest tests/test_gpu_model.py tests/test_gpu_full_size.py tests/test_gpu_baseline_configs.py tests/test_video_encoders.py tests/test_dynamic_s2.py -m gpu -q -x 2>&1 | tail -8 ;;
   smoke)     python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1 ;;

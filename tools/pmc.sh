@@ -8,6 +8,6 @@ cd /tmp && export TMPDIR=/tmp
 for CTR in FETCH_SIZE WRITE_SIZE; do
   OUT=$REPO/gpurun_out/pmc_${TAG}_$CTR
   mkdir -p "$OUT"
-  rocprofv3 --pmc $CTR --kernel-trace -d "$OUT" -o pmc -- python "$REPO/bench.py" --no-cpu-baseline "$@" > "$OUT/stdout.log" 2> "$OUT/stderr.log"
+  rocprofv3 --pmc $CTR --kernel-trace -d "$OUT" -o pmc -- python "$REPO/bench.py" --full --no-cpu-baseline "$@" > "$OUT/stdout.log" 2> "$OUT/stderr.log"
   echo "$CTR rc=$?"
 done

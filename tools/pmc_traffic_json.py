@@ -25,7 +25,7 @@ H, F, S = 3584, 18944, 769
 dec_alg = 2 * F * H * 2 + H * 2 * 2 + F * 2
 f, w = pick("void gemv_kernel<1, 4>")
 doc = {"kernel": "gemv_kernel<1,4>",
-       "source": f"rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) --kernel-trace -- python bench.py --no-cpu-baseline --no-sft --no-sustain --steps 8 --warmup 2 "
+       "source": f"rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) --kernel-trace -- python bench.py --full --no-cpu-baseline --no-sft --no-sustain --steps 8 --warmup 2 "
                  f"(round {tag}, tools/pmc.sh via tools/validate_gpu.sh; per-kernel averages in profiles/{tag}_pmc_hbm_counters.txt)",
        "correction": "gfx950: FETCH_SIZE counts 128-B requests as 64 B for wide coalesced 16-B/lane streams -> x2 (MI355X_MICROARCH.md HBM section); WRITE_SIZE uncalibrated, taken as reported"}
 if f and w:

@@ -7,6 +7,6 @@ REPO=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$REPO/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats -d "$OUT" -o trace -- python "$REPO/bench.py" --no-cpu-baseline "$@" > "$OUT/bench_stdout.log" 2> "$OUT/bench_stderr.log"
+rocprofv3 --kernel-trace --stats -d "$OUT" -o trace -- python "$REPO/bench.py" --full --no-cpu-baseline "$@" > "$OUT/bench_stdout.log" 2> "$OUT/bench_stderr.log"
 echo "rocprofv3 rc=$?"
 find "$OUT" -name "*kernel_stats*" | head

@@ -15,7 +15,7 @@ for n in ("sft_base_1","sft_optdefer_1","sft_base_2","sft_optdefer_2"):
         d=json.loads(open(f"gpurun_out/r06_{n}.json").read()); print(n, d["ms_per_step"], "ms")
     except Exception as e: print(n, "failed", e)
 P
-timeout 600 python bench.py > $O/r06_bench_base.json 2>> $O/r06_call1.err
+timeout 600 python bench.py --full > $O/r06_bench_base.json 2>> $O/r06_call1.err
 python -c "
 import json
 d=json.loads(open('gpurun_out/r06_bench_base.json').read().strip().splitlines()[-1]); print('value', d['value'], 'ttft', d.get('ttft_ms'), 'sft', (d.get('sft') or {}).get('ms_per_step'))"

@@ -6,7 +6,7 @@ timeout 900 python -m pytest tests/test_gpu_model.py -m gpu -q -k "persistent or
 tail -12 $O/r06_call2_tests.log
 for i in 1 2; do
   for m in 0 1; do
-    VILA_DECODE_PERSIST=$m timeout 300 python bench.py --no-sft --no-cpu-baseline --no-sustain 2>>$O/r06_call2.err | tail -1 > $O/r06_decode_persist${m}_$i.json
+    VILA_DECODE_PERSIST=$m timeout 300 python bench.py --full --no-sft --no-cpu-baseline --no-sustain 2>>$O/r06_call2.err | tail -1 > $O/r06_decode_persist${m}_$i.json
     python -c "
 import json
 d=json.loads(open('$O/r06_decode_persist${m}_$i.json').read()); print('persist=$m run $i: value', d['value'], 'ms/step', d['ms_per_step'], 'ttft', d.get('ttft_ms'), 'launches', d.get('config',{}).get('launches_per_token'))"

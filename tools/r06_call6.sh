@@ -2,7 +2,7 @@
 cd "$GRAFT_REPO_ROOT" || exit 1
 O=gpurun_out; mkdir -p $O
 timeout 1500 python -m pytest tests/test_gpu_train.py tests/test_gpu_full_depth.py -m gpu -q -k "nccl or backward_probe or identical_bits" 2>&1 | tail -8
-timeout 900 python bench.py > $O/r06_bench_mid.json 2> $O/r06_bench_mid.err
+timeout 900 python bench.py --full > $O/r06_bench_mid.json 2> $O/r06_bench_mid.err
 python - <<'P'
 import json
 d=json.loads(open("gpurun_out/r06_bench_mid.json").read().strip().splitlines()[-1])

@@ -4,7 +4,7 @@ VAR=$1; R=${2:-2}; A=${3:-0}; Bv=${4:-1}
 O=gpurun_out; mkdir -p $O
 for i in $(seq 1 $R); do
   for v in $A $Bv; do
-    env $VAR=$v python bench.py --no-cpu-baseline --no-sft --no-sustain --steps 32 --warmup 8 2>/dev/null | tail -1 > $O/ab_tmp.json
+    env $VAR=$v python bench.py --full --no-cpu-baseline --no-sft --no-sustain --steps 32 --warmup 8 2>/dev/null | tail -1 > $O/ab_tmp.json
     python - "$VAR=$v" <<'PY'
 import json, sys
 d = json.loads(open("gpurun_out/ab_tmp.json").read())

@@ -3,7 +3,7 @@
 REPO=${GRAFT_REPO_ROOT:-/root/repo}; O=$REPO/gpurun_out; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 rm -rf $O/prof_rows_s
-timeout 400 rocprofv3 --kernel-trace -d $O/prof_rows_s -o trace -- python $REPO/bench.py --prompt-tokens 32 --no-cpu-baseline --no-sft --no-sustain --steps 8 --warmup 2 > $O/prof_rows_s.log 2>&1
+timeout 400 rocprofv3 --kernel-trace -d $O/prof_rows_s -o trace -- python $REPO/bench.py --prompt-tokens 32 --full --no-cpu-baseline --no-sft --no-sustain --steps 8 --warmup 2 > $O/prof_rows_s.log 2>&1
 DB=$(find $O/prof_rows_s -name "*.db" | head -1)
 cd $REPO && python tools/rocpd_rows.py "$DB" im2col_kernel argmax_stage2 -2 $O/r06_ttft_rows_s289.txt "attn_fwd_kernel<128"
 find $O/prof_rows_s -name "*.db" -delete

@@ -14,14 +14,14 @@ if [ -z "$VAL_LIGHT" ]; then
 VILA_SFT_C_ABI=1 timeout 300 python bench.py --mode sft --steps 4 --warmup 2 2>"$O/val_sft_c.err" | tee "$O/val_sft_c.json" | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('sft c-abi ->', d['ms_per_step'], 'ms  loss', d.get('loss'))"
 VILA_BENCH_FORCE_DIST=1 timeout 300 python bench.py --mode sft --steps 3 --warmup 1 2>"$O/val_sft_forcedist.err" | tee "$O/val_sft_forcedist.json" | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[0]); print('sft force-dist (nccl, world 1) ->', d['ms_per_step'], 'ms')"
 # the default line with the process group forced up in a world of one: the SFT side measurement takes the RCCL path the driver's --gpus N takes
-VILA_BENCH_FORCE_DIST=1 timeout 400 python bench.py --no-sustain --no-cpu-baseline --steps 16 --warmup 4 2>"$O/val_bench_forcedist.err" | tail -1 > "$O/val_bench_forcedist.json"
+VILA_BENCH_FORCE_DIST=1 timeout 400 python bench.py --full --no-sustain --no-cpu-baseline --steps 16 --warmup 4 2>"$O/val_bench_forcedist.err" | tail -1 > "$O/val_bench_forcedist.json"
 python -c "
 import json
 d = json.loads(open('gpurun_out/val_bench_forcedist.json').read()); s = d.get('sft') or {}
 print('bench (forced nccl group, world 1): value', d['value'], '| sft', s.get('ms_per_step'), 'ms, exchange_active', s.get('exchange_active'), 'bytes', s.get('exchange_bytes'), s.get('error'))
 "
 fi
-timeout 600 python bench.py > "$O/val_bench.json" 2> "$O/val_bench.err"
+timeout 600 python bench.py --full > "$O/val_bench.json" 2> "$O/val_bench.err"
 python - <<'P'
 import json
 try:
@@ -38,7 +38,7 @@ import sys, json
 d = json.loads(sys.stdin.read()); print('VILA_DECODE_PERSIST=$m: value', d['value'], 'tok/s, ms/step', d['ms_per_step'], '|', d.get('config', {}).get('decode'))" | tee -a "$O/val_persist_ab.log"
 done
 for args in "--w4" "--w8-vit" "--dynamic-s2" "--mode video" "--mode video --tsp" "--prompt-tokens 32"; do
-  timeout 400 python bench.py $args --no-sft --no-sustain --no-cpu-baseline 2>>"$O/val_other_modes.err" | tail -1 >> "$O/val_other_modes.jsonl"
+  timeout 400 python bench.py $args --full --no-sft --no-sustain --no-cpu-baseline 2>>"$O/val_other_modes.err" | tail -1 >> "$O/val_other_modes.jsonl"
 done
 python - <<'P'
 import json
@@ -59,7 +59,7 @@ for line in open('gpurun_out/val_batch_decode.jsonl'):
     d = json.loads(line); print('batch decode', d['config']['workload'][:40], '|', d['value'], d['unit'], '| ms/step', d['ms_per_step'])
 "
 timeout 400 python bench.py --mode sft --dynamic-s2 --micro-batch 1 --steps 3 --warmup 1 2>"$O/val_sft_s2.err" | tee "$O/val_sft_s2.json" | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('sft dynamic_s2 ->', d['ms_per_step'], 'ms')"
-timeout 400 python bench.py --config nvila_lite_3b --no-sft --no-sustain --no-cpu-baseline 2>"$O/val_bench_lite3b.err" | tail -1 > "$O/val_bench_lite3b.json"
+timeout 400 python bench.py --config nvila_lite_3b --full --no-sft --no-sustain --no-cpu-baseline 2>"$O/val_bench_lite3b.err" | tail -1 > "$O/val_bench_lite3b.json"
 python -c "
 import json
 d = json.loads(open('gpurun_out/val_bench_lite3b.json').read().strip().splitlines()[-1]); print('lite-3b', d['value'], d['unit'], 'ttft', d.get('ttft_ms'))
