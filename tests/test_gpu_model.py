@@ -226,37 +226,6 @@ def test_rope_and_kv_scatter_fused_into_the_qkv_reduce_equal_the_separate_launch
     assert rel_l2(out["fused"][2], out["ring"][2]) < 2e-2
 
 
-def test_chained_decode_step_equals_the_plain_step():
-    """The opt-in chained decode step (vila_decode_force_chain(1): kernels alternate over two streams, stream their weights while the predecessor
-    finishes and wait on device-side arrival counts; api.hip — measured slower than the plain step and OFF by default, profiles/
-    r04_decode_chain_ab.log) must produce the plain step's logits BIT FOR BIT (same kernels, same summation order; only the hand-off differs) at
-    NVILA-8B widths, eager and through the captured graph, and must not report a given-up wait."""
-    from vila_amd import _lib
-    from vila_amd.vlm import build_model
-    lib = _lib.load()
-    cfg = configs.reduced_8b(layers_v=2, layers_l=3, vocab=32000)
-    cfg.image_token_id, cfg.llm.eos_token_id = 31999, 31998
-    model = build_model(cfg, seed=11)
-    g = torch.Generator().manual_seed(11)
-    e = (torch.randn(1, 300, cfg.llm.hidden_size, generator=g) * 0.5).to(torch.bfloat16).cuda()
-    n = 12
-    lib.vila_decode_force_chain(0)
-    model.llm._invalidate()
-    ids0, lg0 = model.llm.generate(inputs_embeds=e, max_new_tokens=n, return_logits=True, use_graph=False, eos_token_id=-1)
-    free0 = model.llm.generate(inputs_embeds=e, max_new_tokens=n, use_graph=True, eos_token_id=-1)
-    try:
-        lib.vila_decode_force_chain(1)
-        model.llm._invalidate()
-        ids1, lg1 = model.llm.generate(inputs_embeds=e, max_new_tokens=n, return_logits=True, use_graph=False, eos_token_id=-1)
-        free1 = model.llm.generate(inputs_embeds=e, max_new_tokens=n, use_graph=True, eos_token_id=-1)      # raises if a wait gave up
-        again = model.llm.generate(inputs_embeds=e, max_new_tokens=n, use_graph=True, eos_token_id=-1)      # replay: counters re-zeroed per token
-    finally:
-        lib.vila_decode_force_chain(0)
-        model.llm._invalidate()
-    assert torch.equal(lg1, lg0), f"chained vs plain decode logits differ: max {float((lg1 - lg0).abs().max()):.3e}"
-    assert torch.equal(ids1, ids0) and torch.equal(free1, free0) and torch.equal(again, free0)
-
-
 @pytest.mark.parametrize("shape", ["8b_width", "tiny", "lite3b_width"])
 def test_persistent_decode_step_equals_the_launch_path(shape):
     """Round 6: the batch-1 decode token as ONE persistent launch (decode_persist.hip: 5 phases per layer behind fence-free grid barriers, the
@@ -378,8 +347,8 @@ def test_wide_llm_prefill_and_decode(wide):
 
 @pytest.mark.parametrize("S", [257, 260, 272])
 def test_wide_llm_prefill_tail_rows_via_gemv(wide, S):
-    """S = k * 256 + (1..16): the leftover rows of the MLP GEMMs ride in the last 256-row tile as an extra fragment (round 3; rounds 1 / 2:
-    through the decode GEMV kernels, still the path under VILA_GEMM_EX=0) — every row must match the oracle, the leftover rows included."""
+    """S = k * 256 + (1..16): the leftover rows of the MLP GEMMs ride in the last 256-row tile as an extra fragment (round 3; rounds 1 / 2
+    ran them through the decode GEMV kernels) — every row must match the oracle, the leftover rows included."""
     cfg, w, model = wide
     g = torch.Generator().manual_seed(S)
     e = (torch.randn(1, S, cfg.llm.hidden_size, generator=g) * 0.5).to(torch.bfloat16)

@@ -48,14 +48,6 @@ import json; d=json.loads(open('$O/bench_fast.json').read().strip().splitlines()
   video)     for args in "--mode video" "--mode video --tsp"; do timeout 400 python bench.py $args 2>>"$O/video.err" | tail -1 | tee -a "$O/video.jsonl" | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['config']['workload'][:60], d['value'], 'ms encode', d['encode_ms'], 'prefill', d['llm_prefill_ms'])"; done ;;
   chain_tests) timeout 1200 python -m pytest tests/test_gpu_model.py tests/test_gpu_batch_decode.py tests/test_gpu_serving.py tests/test_gpu_sampling.py -m gpu -q -x 2>&1 | tail -25 > "$O/pytest_chain.log"; tail -25 "$O/pytest_chain.log" ;;
   full_depth) timeout 1200 python -m pytest tests/test_gpu_full_depth.py -m gpu -q -s -k "${FD_K:-full_depth}" 2>&1 | grep -v "^$" > "$O/pytest_full_depth.log"; grep -n "full depth\|forward loss\|Error\|passed\|failed" "$O/pytest_full_depth.log" | cut -c1-600 | tail -30 ;;
-  chain_ab)  for cv in "0 95" "1 95" "1 80" "1 110"; do set -- $cv; VILA_DECODE_CHAIN=$1 VILA_DECODE_CHAIN_PRED=$2 timeout 300 python bench.py --full --no-sft --no-sustain --no-cpu-baseline --steps 64 --warmup 8 > "$O/chain_$1_$2.json" 2> "$O/chain_$1_$2.err"; python -c "
-import json; d=json.loads(open('$O/chain_$1_$2.json').read().strip().splitlines()[-1]); print('chain=$1 pred=$2: value', d['value'], 'ms/step', d['ms_per_step'], 'ttft', d['ttft_ms'], 'gateup us', d['roofline']['avg_launch_us'])" || tail -5 "$O/chain_$1_$2.err"; done ;;
-  chain_prof) timeout 600 bash tools/profile.sh chain --no-sft --no-sustain --no-cpu-baseline --steps 32 --warmup 8 2>&1 | tail -2
-             python tools/rocpd_summary.py "$GRAFT_REPO_ROOT/gpurun_out/prof_chain/trace_results.db" "$O/chain_kernel_stats.csv"; head -8 "$O/chain_kernel_stats.csv"
-             python tools/rocpd_rows.py "$GRAFT_REPO_ROOT/gpurun_out/prof_chain/trace_results.db" decode_prologue_kernel decode_advance_kernel -3 "$O/chain_token_rows.txt"; head -34 "$O/chain_token_rows.txt"
-             rm -f "$GRAFT_REPO_ROOT/gpurun_out/prof_chain/trace_results.db" ;;
-  bpc2)      VILA_DECODE_CHAIN=0 VILA_GEMV_BPC=2 timeout 300 python bench.py --full --no-sft --no-sustain --no-cpu-baseline --steps 64 --warmup 8 > "$O/bpc2.json" 2> "$O/bpc2.err"; python -c "
-import json; d=json.loads(open('$O/bpc2.json').read().strip().splitlines()[-1]); print('chain=0 bpc=2: value', d['value'], 'ms/step', d['ms_per_step'], 'gateup us', d['roofline']['avg_launch_us'])" || tail -5 "$O/bpc2.err" ;;
   fuse_ab)   for c in 0 1 0 1; do VILA_FUSE_NORM=$c timeout 300 python bench.py --full --no-sft --no-sustain --no-cpu-baseline --steps 32 --warmup 8 > "$O/fuse_$c.json" 2> "$O/fuse_$c.err"; python -c "
 import json; d=json.loads(open('$O/fuse_$c.json').read().strip().splitlines()[-1]); print('fuse_norm=$c: ttft', d['ttft_ms'], 'encode', d['prefill']['encode_images_ms'], 'value', d['value'])" || tail -5 "$O/fuse_$c.err"; done ;;
   fuse_tests) timeout 1200 python -m pytest tests/test_gpu_model.py tests/test_gpu_full_size.py tests/test_gpu_baseline_configs.py tests/test_video_encoders.py tests/test_dynamic_s2.py -m gpu -q -x 2>&1 | tail -8 ;;

@@ -19,8 +19,6 @@ void vila_set_error(const char* fmt, ...) {
 extern "C" const char* vila_last_error(void) { return g_err; }
 extern "C" int vila_abi_version(void) { return 1; }
 
-int gemm256_tiles_m_of(int M);      // gemm256.hip
-
 namespace {
 struct Arena {
     char* base; size_t size, off;
@@ -311,18 +309,51 @@ extern "C" size_t vila_llm_prefill_workspace_bytes(const VilaLlmShape* s, int T)
     b += align_up((size_t)8 * T * H * 4, 256);                 // split-K fp32 slabs (down_proj: up to 8 slices; tail round of gate/up) at small T
     return b + 8192;
 }
+// the W4A16 GEMMs' K-slice slabs (gemm_w4.hip): the largest of the four projections' (the W4 prefill has them in place of the bf16 slabs)
+static size_t prefill_w4_gemm_ws(const VilaLlmShape& sh, int T) {
+    const int H = sh.hidden, F = sh.inter, QS = sh.q_heads * sh.head_dim, QKV = (sh.q_heads + 2 * sh.kv_heads) * sh.head_dim;
+    size_t b = gemm_w4_workspace_bytes(T, QKV, H, 2);
+    const size_t o = gemm_w4_workspace_bytes(T, H, QS, 0), gu = gemm_w4_workspace_bytes(T, F, H, 1), dn = gemm_w4_workspace_bytes(T, H, F, 0);
+    if (o > b) b = o;
+    if (gu > b) b = gu;
+    if (dn > b) b = dn;
+    return b;
+}
+extern "C" size_t vila_llm_prefill_w4_workspace_bytes(const VilaLlmShape* s, int T) {
+    return vila_llm_prefill_workspace_bytes(s, T) + prefill_w4_gemm_ws(*s, T) + 256;
+}
 
-extern "C" int vila_llm_prefill(const VilaLlmWeights* w, const void* embeds, const int32_t* positions, const int32_t* cu_seqlens,
-                                int n_seq, int T, int max_seqlen, const int32_t* seq_of_tok, const VilaKvCache* cache,
-                                const int32_t* last_rows, int n_last, float* last_logits, float* all_logits, void* final_hidden,
-                                void* layer_hidden, void* workspace, size_t workspace_bytes, vila_stream_t stream) {
+// One projection of a decoder layer for ONE row as a decode GEMV (the batch-1 decode step, the pruned last layer of the prefill): the bf16
+// kernel on g (gemv.hip), or with int4 weights (w4) the W4A16 GEMV (gemv_w4.hip) on the same operands and epilogue.  bf16 mode 2 (x = the
+// merge of the decode attention's 256-key partials) is W4 mode 4; grid_cap is the bf16 kernel's alone.
+static int proj_gemv(const GemvArgs& g, bool w4, const void* wq, const void* wsz, hipStream_t s) {
+    if (!w4) return launch_gemv(g, s);
+    GemvW4Args a{};
+    a.x = g.x; a.norm_w = g.norm_w; a.eps = g.eps; a.Wq = (const uint32_t*)wq; a.Wsz = (const uint32_t*)wsz; a.bias = g.bias; a.residual = g.residual;
+    a.y = g.y; a.N = g.N; a.K = g.K; a.mode = g.mode == 2 ? 4 : g.mode;
+    a.part_o = g.part_o; a.part_ml = g.part_ml; a.pos_ptr = g.pos_ptr; a.n_splits = g.n_splits; a.split_keys = g.split_keys;
+    return launch_gemv_w4(a, s);
+}
+
+// The LLM prefill.  ql == nullptr: the bf16 projections, whose GEMMs may take the follow-up (RoPE + KV-cache scatter, the next RMSNorm) along
+// in their split-K reduce and say so through rope_done / ln2_done / ln1_done.  ql != nullptr (vila_llm_prefill_w4): the five decoder
+// projections read from the int4 layers (gemm_w4.hip), so a quantised model runs from its int4 weights alone; those GEMMs take no follow-up,
+// so the standalone rmsnorm / rope_kv kernels run instead.
+static int llm_prefill_impl(const VilaLlmWeights* w, const VilaLlmLayerW4* ql, const void* embeds, const int32_t* positions,
+                            const int32_t* cu_seqlens, int n_seq, int T, int max_seqlen, const int32_t* seq_of_tok, const VilaKvCache* cache,
+                            const int32_t* last_rows, int n_last, float* last_logits, float* all_logits, void* final_hidden,
+                            void* layer_hidden, void* workspace, size_t workspace_bytes, vila_stream_t stream) {
     const VilaLlmShape& sh = w->shape;
     hipStream_t s = S(stream);
-    VILA_REQUIRE(T > 0 && n_seq > 0, "llm_prefill: empty input");
+    const bool w4 = ql != nullptr;
+    const char* fn = w4 ? "llm_prefill_w4" : "llm_prefill";
+    VILA_REQUIRE(T > 0 && n_seq > 0, "%s: empty input", fn);
     VILA_REQUIRE(sh.q_heads % sh.kv_heads == 0, "llm: q heads must be a multiple of kv heads");
-    VILA_REQUIRE(cu_seqlens != nullptr || n_seq == 1, "llm_prefill: n_seq > 1 needs cu_seqlens");
-    VILA_REQUIRE(workspace_bytes >= vila_llm_prefill_workspace_bytes(&sh, T), "llm_prefill: workspace too small");
+    VILA_REQUIRE(cu_seqlens != nullptr || n_seq == 1, "%s: n_seq > 1 needs cu_seqlens", fn);
+    VILA_REQUIRE(workspace_bytes >= (w4 ? vila_llm_prefill_w4_workspace_bytes(&sh, T) : vila_llm_prefill_workspace_bytes(&sh, T)),
+                 "%s: workspace too small", fn);
     const int H = sh.hidden, F = sh.inter, hd = sh.head_dim, QS = sh.q_heads * hd, KS = sh.kv_heads * hd, QKV = QS + 2 * KS;
+    VILA_REQUIRE(QS == H, "llm: q_heads*head_dim (%d) must equal hidden (%d) for the in-place attention buffer", QS, H);
     Arena a(workspace, workspace_bytes);
     bf16_t* x = a.take<bf16_t>((size_t)T * H);
     bf16_t* h = a.take<bf16_t>((size_t)T * H);
@@ -331,10 +362,12 @@ extern "C" int vila_llm_prefill(const VilaLlmWeights* w, const void* embeds, con
     float* cs = a.take<float>((size_t)T * hd / 2);
     float* sn = a.take<float>((size_t)T * hd / 2);
     bf16_t* lastbuf = a.take<bf16_t>((size_t)(T > 8 ? T : 8) * H);
-    float* skws = a.take<float>((size_t)8 * T * H);
-    const size_t skws_bytes = (size_t)8 * T * H * 4;
-    VILA_REQUIRE(a.ok(), "llm_prefill: workspace arena overflow");
-    if (cache != nullptr) VILA_REQUIRE(max_seqlen <= cache->max_ctx, "llm_prefill: sequence (%d) longer than the KV cache (%d)", max_seqlen, cache->max_ctx);
+    const size_t skws_bytes = w4 ? 0 : (size_t)8 * T * H * 4;       // the bf16 GEMMs' split-K fp32 slabs
+    float* skws = w4 ? nullptr : a.take<float>(skws_bytes / 4);
+    const size_t gws_bytes = w4 ? prefill_w4_gemm_ws(sh, T) : 0;     // the W4A16 GEMMs' slabs
+    char* gws = w4 ? a.take<char>(gws_bytes) : nullptr;
+    VILA_REQUIRE(a.ok(), "%s: workspace arena overflow", fn);
+    if (cache != nullptr) VILA_REQUIRE(max_seqlen <= cache->max_ctx, "%s: sequence (%d) longer than the KV cache (%d)", fn, max_seqlen, cache->max_ctx);
 
     VILA_HIP(hipMemcpyAsync(x, embeds, (size_t)T * H * 2, hipMemcpyDeviceToDevice, s));
     VILA_TRY(launch_rope_table(positions, cs, sn, T, hd, sh.rope_theta, s));
@@ -343,26 +376,32 @@ extern "C" int vila_llm_prefill(const VilaLlmWeights* w, const void* embeds, con
 
     // only last-row logits wanted (generation): the last layer is finished for those rows alone (see below)
     const bool prune_last = final_hidden == nullptr && all_logits == nullptr && taps == nullptr && cache != nullptr && last_logits != nullptr &&
-                            last_rows != nullptr && n_last >= 1 && n_last <= 4 && H % 8 == 0 && F % 8 == 0 && QS == H;
-    // 1..16 leftover rows (T = 256 k + r) ride in the last row tile of the 256^2 GEMMs as an extra fragment (gemm256_kernel.h, EX); only when
-    // that policy is switched off (VILA_GEMM_EX=0) do 1..4 leftover rows of the MLP go through the decode GEMVs as in rounds 1 / 2
-    const bool ex_rows = gemm256_tiles_m_of(T) < cdiv(T, 256);
-    const int tail_rows = (!ex_rows && T > 256 && T % 256 >= 1 && T % 256 <= 4 && H % 8 == 0 && F % 8 == 0) ? T % 256 : 0;
-    const int Tg = T - tail_rows;     // rows of the gate/up and down GEMMs; the rest via GEMV
+                            last_rows != nullptr && n_last >= 1 && n_last <= 4 && H % 8 == 0 && F % 8 == 0;
+    auto gemm4 = [&](const bf16_t* xin, const void* q, const void* sz, const void* bias, const bf16_t* res, bf16_t* y, int N, int K, int mode) {
+        GemmW4Args g{};
+        g.x = xin; g.Wq = (const uint32_t*)q; g.Wsz = (const uint32_t*)sz; g.bias = B(bias); g.residual = res; g.y = y;
+        g.M = T; g.N = N; g.K = K; g.mode = mode; g.n_rope_heads = sh.q_heads + sh.kv_heads; g.hd = hd;
+        return launch_gemm_w4(g, gws, gws_bytes, s);
+    };
     int ln1_done = 0;                                           // the previous layer's down-proj reduce already wrote input_layernorm(x) into h
     for (int l = 0; l < sh.n_layers; ++l) {
         const VilaLlmLayer& L = w->layers[l];
+        const VilaLlmLayerW4 Q = w4 ? ql[l] : VilaLlmLayerW4{};
+        if (w4) VILA_REQUIRE(L.bq != nullptr && B(L.bk) == B(L.bq) + QS && B(L.bv) == B(L.bk) + KS,
+                             "llm_prefill_w4: the q/k/v biases must be one contiguous q|k|v vector (layer %d)", l);
         if (!ln1_done) VILA_TRY(launch_rmsnorm(x, B(L.ln1_w), h, T, H, sh.rms_eps, s));
         ln1_done = 0;
-        const bool fused = (B(L.wk) == B(L.wq) + (size_t)QS * H) && (B(L.wv) == B(L.wk) + (size_t)KS * H) &&
-                           (B(L.bk) == B(L.bq) + QS) && (B(L.bv) == B(L.bk) + KS);
         bf16_t* kc = nullptr; bf16_t* vc = nullptr; int max_ctx = 0;
         if (cache != nullptr) {
             const size_t per_layer = (size_t)cache->n_slots * sh.kv_heads * cache->max_ctx * hd;
             kc = B(cache->k) + l * per_layer; vc = B(cache->v) + l * per_layer; max_ctx = cache->max_ctx;
         }
         int rope_done = 0;
-        if (fused) {
+        const bool fused = !w4 && (B(L.wk) == B(L.wq) + (size_t)QS * H) && (B(L.wv) == B(L.wk) + (size_t)KS * H) &&
+                           (B(L.bk) == B(L.bq) + QS) && (B(L.bv) == B(L.bk) + KS);
+        if (w4) {
+            VILA_TRY(gemm4(h, Q.qkv_q, Q.qkv_sz, L.bq, nullptr, qkv, QKV, H, 2));                 // q | k | v + bias, natural column order
+        } else if (fused) {
             // one GEMM for q | k | v; where its grid is K-sliced (S = 769: 54 tiles x 4 slices) the reduce adds the bias, rotates q and k and
             // writes K / V into the cache (VILA_PREFILL_QKV_SPLITK=0: ring GEMM + rope_kv_kernel as in rounds 1-5)
             NextRope nr;
@@ -382,12 +421,11 @@ extern "C" int vila_llm_prefill(const VilaLlmWeights* w, const void* embeds, con
         at.cu_seqlens = cu_seqlens; at.n_seq = n_seq; at.total_tokens = T; at.max_seqlen = (cu_seqlens ? max_seqlen : T);
         at.n_q_heads = sh.q_heads; at.n_kv_heads = sh.kv_heads; at.head_dim = hd; at.causal = 1;
         at.scale = 1.0f / sqrtf((float)hd); at.lse = nullptr;
-        VILA_REQUIRE(QS == H, "llm: q_heads*head_dim (%d) must equal hidden (%d) for the in-place attention buffer", QS, H);
         VILA_TRY(launch_attn_fwd(at, s));
         if (l == sh.n_layers - 1 && prune_last) {
             // Generation prefill: after the last layer's K / V are in the cache only the rows whose logits are asked for feed anything.
             // Their o_proj, post-attention norm and MLP run as three decode GEMVs per row (weights stream once at HBM rate) instead of
-            // four GEMMs over all T rows: same arithmetic order per row as the decode step, which is parity-tested against this path.
+            // four GEMMs over all T rows: the same kernels and arithmetic order per row as the decode step, which is parity-tested against this path.
             VILA_TRY(launch_copy_rows(h, lastbuf, last_rows, nullptr, n_last, QS, s));             // attention output rows
             VILA_TRY(launch_copy_rows(x, lastbuf + (size_t)n_last * H, last_rows, nullptr, n_last, H, s));   // residual rows
             for (int r = 0; r < n_last; ++r) {
@@ -396,42 +434,38 @@ extern "C" int vila_llm_prefill(const VilaLlmWeights* w, const void* embeds, con
                 bf16_t* fr = act + (size_t)r * F;                           // silu(gate) * up of the row
                 GemvArgs g0{};
                 g0.x = ar; g0.W = B(L.wo); g0.residual = xr; g0.y = xr; g0.N = H; g0.K = QS; g0.mode = 0;
-                VILA_TRY(launch_gemv(g0, s));
+                VILA_TRY(proj_gemv(g0, w4, Q.o_q, Q.o_sz, s));
                 GemvArgs g1{};
                 g1.x = xr; g1.norm_w = B(L.ln2_w); g1.eps = sh.rms_eps; g1.W = B(L.w_gate); g1.W2 = B(L.w_up); g1.y = fr; g1.N = F; g1.K = H; g1.mode = 1;
-                VILA_TRY(launch_gemv(g1, s));
+                VILA_TRY(proj_gemv(g1, w4, Q.gateup_q, Q.gateup_sz, s));
                 GemvArgs g2{};
                 g2.x = fr; g2.W = B(L.w_down); g2.residual = xr; g2.y = ar; g2.N = H; g2.K = F; g2.mode = 0;
-                VILA_TRY(launch_gemv(g2, s));
+                VILA_TRY(proj_gemv(g2, w4, Q.down_q, Q.down_sz, s));
             }
             break;
         }
-        // x += o_proj(attn).  The post-attention RMSNorm is offered to the GEMM: where its grid is K-sliced (S = 769: 42 tiles x 6 slices) the
-        // reduce holds whole rows and writes h = norm(x) as well (h is free: the GEMM kernel that read it has finished when the reduce runs)
+        // x += o_proj(attn).  The post-attention RMSNorm is offered to the bf16 GEMM: where its grid is K-sliced (S = 769: 42 tiles x 6 slices)
+        // the reduce holds whole rows and writes h = norm(x) as well (h is free: the GEMM kernel that read it has finished when the reduce runs)
         int ln2_done = 0;
-        NextNorm n2;
-        n2.w = L.ln2_w; n2.eps = sh.rms_eps; n2.rms = 1; n2.out = h; n2.done = &ln2_done;
-        VILA_TRY(gemm(h, QS, L.wo, QS, nullptr, x, H, x, H, T, H, QS, EPI_NONE, s, nullptr, 0, skws, skws_bytes, 0, prefill_oproj_norm() ? &n2 : nullptr));
-        if (!ln2_done) VILA_TRY(launch_rmsnorm(x, B(L.ln2_w), h, T, H, sh.rms_eps, s));
-        // MLP.  A prompt of 3 x 256 + 1 tokens (the benchmark's 769) would spend a whole extra row-tile round on ONE row in the two
-        // big GEMMs; those 1-4 leftover rows go through the decode GEMV kernels instead (the weights stream once more at HBM rate:
-        // 44 + 25 us per row against 94 + 40 us for the extra tile round)
-        VILA_TRY(gemm(h, H, L.w_gate, H, nullptr, nullptr, 0, act, F, Tg, F, H, EPI_GATEUP, s, L.w_up, 0, skws, skws_bytes));  // silu(gate)*up
-        for (int r = Tg; r < T; ++r) {
-            GemvArgs g{};
-            g.x = h + (size_t)r * H; g.W = B(L.w_gate); g.W2 = B(L.w_up); g.y = act + (size_t)r * F; g.N = F; g.K = H; g.mode = 1;
-            VILA_TRY(launch_gemv(g, s));
+        if (w4) {
+            VILA_TRY(gemm4(h, Q.o_q, Q.o_sz, nullptr, x, x, H, QS, 0));
+        } else {
+            NextNorm n2;
+            n2.w = L.ln2_w; n2.eps = sh.rms_eps; n2.rms = 1; n2.out = h; n2.done = &ln2_done;
+            VILA_TRY(gemm(h, QS, L.wo, QS, nullptr, x, H, x, H, T, H, QS, EPI_NONE, s, nullptr, 0, skws, skws_bytes, 0, prefill_oproj_norm() ? &n2 : nullptr));
         }
-        // x += down(...); where the GEMM is K-sliced (S = 769: 56 tiles cannot fill the chip) its reduce takes the NEXT layer's input_layernorm
-        // along (h is free: gate/up has consumed it).  Only when every row goes through the GEMM (no GEMV tail rows).
-        NextNorm nn;
-        const bool offer = l + 1 < sh.n_layers && Tg == T;
-        if (offer) { nn.w = w->layers[l + 1].ln1_w; nn.eps = sh.rms_eps; nn.rms = 1; nn.out = h; nn.done = &ln1_done; }
-        VILA_TRY(gemm(act, F, L.w_down, F, nullptr, x, H, x, H, Tg, H, F, EPI_NONE, s, nullptr, 0, skws, skws_bytes, 0, offer ? &nn : nullptr));  // x += down(...)
-        for (int r = Tg; r < T; ++r) {
-            GemvArgs g{};
-            g.x = act + (size_t)r * F; g.W = B(L.w_down); g.residual = x + (size_t)r * H; g.y = x + (size_t)r * H; g.N = H; g.K = F; g.mode = 0;
-            VILA_TRY(launch_gemv(g, s));
+        if (!ln2_done) VILA_TRY(launch_rmsnorm(x, B(L.ln2_w), h, T, H, sh.rms_eps, s));
+        // MLP: silu(gate) * up, then x += down(...); where the bf16 down GEMM is K-sliced (S = 769: 56 tiles cannot fill the chip) its reduce takes
+        // the NEXT layer's input_layernorm along (h is free: gate/up has consumed it)
+        if (w4) {
+            VILA_TRY(gemm4(h, Q.gateup_q, Q.gateup_sz, nullptr, nullptr, act, F, H, 1));
+            VILA_TRY(gemm4(act, Q.down_q, Q.down_sz, nullptr, x, x, H, F, 0));
+        } else {
+            VILA_TRY(gemm(h, H, L.w_gate, H, nullptr, nullptr, 0, act, F, T, F, H, EPI_GATEUP, s, L.w_up, 0, skws, skws_bytes));
+            NextNorm nn;
+            const bool offer = l + 1 < sh.n_layers;
+            if (offer) { nn.w = w->layers[l + 1].ln1_w; nn.eps = sh.rms_eps; nn.rms = 1; nn.out = h; nn.done = &ln1_done; }
+            VILA_TRY(gemm(act, F, L.w_down, F, nullptr, x, H, x, H, T, H, F, EPI_NONE, s, nullptr, 0, skws, skws_bytes, 0, offer ? &nn : nullptr));
         }
         if (taps) VILA_HIP(hipMemcpyAsync(taps + (size_t)(l + 1) * T * H, x, (size_t)T * H * 2, hipMemcpyDeviceToDevice, s));
     }
@@ -442,7 +476,7 @@ extern "C" int vila_llm_prefill(const VilaLlmWeights* w, const void* embeds, con
         if (all_logits) VILA_TRY(gemm(fh, H, w->lm_head, H, nullptr, nullptr, 0, all_logits, sh.vocab, T, sh.vocab, H, EPI_NONE, s, nullptr, 1));
     }
     if (n_last > 0 && last_logits != nullptr) {
-        VILA_REQUIRE(last_rows != nullptr, "llm_prefill: last_rows is NULL");
+        VILA_REQUIRE(last_rows != nullptr, "%s: last_rows is NULL", fn);
         if (!prune_last) VILA_TRY(launch_copy_rows(x, lastbuf, last_rows, nullptr, n_last, H, s));     // (pruned: lastbuf already holds the rows)
         if (n_last == 1) {
             GemvArgs g{};
@@ -456,9 +490,25 @@ extern "C" int vila_llm_prefill(const VilaLlmWeights* w, const void* embeds, con
     }
     return 0;
 }
+extern "C" int vila_llm_prefill(const VilaLlmWeights* w, const void* embeds, const int32_t* positions, const int32_t* cu_seqlens,
+                                int n_seq, int T, int max_seqlen, const int32_t* seq_of_tok, const VilaKvCache* cache,
+                                const int32_t* last_rows, int n_last, float* last_logits, float* all_logits, void* final_hidden,
+                                void* layer_hidden, void* workspace, size_t workspace_bytes, vila_stream_t stream) {
+    return llm_prefill_impl(w, nullptr, embeds, positions, cu_seqlens, n_seq, T, max_seqlen, seq_of_tok, cache, last_rows, n_last, last_logits,
+                            all_logits, final_hidden, layer_hidden, workspace, workspace_bytes, stream);
+}
+// the prefill with the five decoder projections read from the int4 layers; embed, norms, the fused q|k|v biases and the bf16 lm_head come from `w`
+extern "C" int vila_llm_prefill_w4(const VilaLlmWeights* w, const VilaLlmLayerW4* ql, const void* embeds, const int32_t* positions,
+                                   const int32_t* cu_seqlens, int n_seq, int T, int max_seqlen, const int32_t* seq_of_tok, const VilaKvCache* cache,
+                                   const int32_t* last_rows, int n_last, float* last_logits, float* all_logits, void* final_hidden,
+                                   void* layer_hidden, void* workspace, size_t workspace_bytes, vila_stream_t stream) {
+    VILA_REQUIRE(ql != nullptr, "llm_prefill_w4: the int4 layers are NULL");
+    return llm_prefill_impl(w, ql, embeds, positions, cu_seqlens, n_seq, T, max_seqlen, seq_of_tok, cache, last_rows, n_last, last_logits,
+                            all_logits, final_hidden, layer_hidden, workspace, workspace_bytes, stream);
+}
 
 // =================================================================================================
-// LLM decode step (batch 1, greedy)
+// LLM decode step (batch 1)
 // =================================================================================================
 static inline int dec_splits(int max_ctx) { return cdiv(max_ctx, 64); }
 // kernel launches of one vila_llm_decode_step: prologue + per layer {qkv, attention (1 launch up to 2048 cached positions, else
@@ -471,6 +521,8 @@ extern "C" int vila_llm_decode_launches(const VilaLlmShape* s, int max_ctx) {
     if (decode_persist_ok(*s, max_ctx)) return 6;                 // prologue, the persistent layers kernel, lm_head, argmax x2, advance
     return 1 + s->n_layers * (max_ctx <= 2048 ? 5 : 6) + 4;      // a sampled step: + 1 (three selection launches instead of two argmax stages)
 }
+// first in the arena: word 0 = the error flag (vila_llm_decode_chain_error), then the persistent kernel's barrier words (DpArgs::sync)
+static const size_t DEC_SYNC_WORDS = 64 + (size_t)DP_SYNC_COUNT * DP_SYNC_STRIDE;
 extern "C" size_t vila_llm_decode_workspace_bytes(const VilaLlmShape* s, int max_ctx) {
     const size_t H = s->hidden, F = s->inter, QS = (size_t)s->q_heads * s->head_dim;
     const size_t ns = dec_splits(max_ctx);
@@ -480,7 +532,7 @@ extern "C" size_t vila_llm_decode_workspace_bytes(const VilaLlmShape* s, int max
     b += 2 * align_up(256 * 4, 256) + align_up((size_t)s->head_dim * 4, 256);
     b += align_up(QS * 2, 256);
     b += align_up(sample_workspace_bytes(), 256);
-    b += align_up((64 + (4 * (size_t)s->n_layers + 2) * CHAIN_WORDS) * 4, 256);      // chained step: error word + per-kernel count / flag words (first in the arena)
+    b += align_up(DEC_SYNC_WORDS * 4, 256);
     return b + 4096;
 }
 
@@ -504,17 +556,30 @@ static int decode_persist_mode() {
     if (g_decode_persist < 0) { const char* e = getenv("VILA_DECODE_PERSIST"); g_decode_persist = (e && e[0] == '1') ? 1 : 0; }
     return g_decode_persist;
 }
-static int decode_step_impl(const VilaLlmWeights* w, const VilaKvCache* cache, const VilaDecodeState* st, void* workspace, size_t workspace_bytes,
-                            const VilaSampling* sp, vila_stream_t stream);
+static int decode_step_impl(const VilaLlmWeights* w, const VilaLlmLayerW4* ql, const VilaKvCache* cache, const VilaDecodeState* st,
+                            void* workspace, size_t workspace_bytes, const VilaSampling* sp, vila_stream_t stream);
 extern "C" int vila_llm_decode_step(const VilaLlmWeights* w, const VilaKvCache* cache, const VilaDecodeState* st,
                                     void* workspace, size_t workspace_bytes, vila_stream_t stream) {
-    return decode_step_impl(w, cache, st, workspace, workspace_bytes, nullptr, stream);
+    return decode_step_impl(w, nullptr, cache, st, workspace, workspace_bytes, nullptr, stream);
 }
 // the same step with a stochastic pick (temperature / top-k / top-p) instead of argmax: generate(do_sample=True)
 extern "C" int vila_llm_decode_step_sample(const VilaLlmWeights* w, const VilaKvCache* cache, const VilaDecodeState* st,
                                            void* workspace, size_t workspace_bytes, const VilaSampling* sp, vila_stream_t stream) {
     VILA_REQUIRE(sp != nullptr, "llm_decode_sample: sampling parameters are NULL");
-    return decode_step_impl(w, cache, st, workspace, workspace_bytes, sp, stream);
+    return decode_step_impl(w, nullptr, cache, st, workspace, workspace_bytes, sp, stream);
+}
+// W4A16 decode: the step with the five decoder-layer projections read from int4 group-128 weights, bf16 everything else
+extern "C" int vila_llm_decode_step_w4(const VilaLlmWeights* w, const VilaLlmLayerW4* ql, const VilaKvCache* cache, const VilaDecodeState* st,
+                                       void* workspace, size_t workspace_bytes, vila_stream_t stream) {
+    VILA_REQUIRE(ql != nullptr, "llm_decode_w4: the int4 layers are NULL");
+    return decode_step_impl(w, ql, cache, st, workspace, workspace_bytes, nullptr, stream);
+}
+// the W4A16 step with a stochastic pick (generate(do_sample=True) on a quantised decoder)
+extern "C" int vila_llm_decode_step_w4_sample(const VilaLlmWeights* w, const VilaLlmLayerW4* ql, const VilaKvCache* cache, const VilaDecodeState* st,
+                                              void* workspace, size_t workspace_bytes, const VilaSampling* sp, vila_stream_t stream) {
+    VILA_REQUIRE(sp != nullptr, "llm_decode_w4_sample: sampling parameters are NULL");
+    VILA_REQUIRE(ql != nullptr, "llm_decode_w4: the int4 layers are NULL");
+    return decode_step_impl(w, ql, cache, st, workspace, workspace_bytes, sp, stream);
 }
 extern "C" size_t vila_sample_workspace_bytes(void) { return sample_workspace_bytes(); }
 extern "C" int vila_sample_f32(const float* logits, int n, const VilaSampling* sp, const int32_t* counter, int64_t* out, void* workspace,
@@ -522,48 +587,8 @@ extern "C" int vila_sample_f32(const float* logits, int n, const VilaSampling* s
     VILA_REQUIRE(sp != nullptr && logits != nullptr && out != nullptr && workspace != nullptr, "sample: NULL argument");
     return launch_sample(logits, n, sp->temperature, sp->top_k, sp->top_p, sp->seed, sp->seed_dev, counter, out, workspace, dist_out, S(stream));
 }
-// ---- chained decode step (round 4) ------------------------------------------------------------------------------------------------------
-// Three of a layer's five kernel boundaries are CHAINED: the successor is launched while its predecessor still runs, requests the weights it can
-// (they do not depend on activations), and waits on the predecessor's device-side done counter before it touches an activation
-// (gemv_common.h chain_wait / chain_done).  What a plain boundary costs — the predecessor's tail with the HBM pipe running dry, the launch gap,
-// the successor's first memory round trip — is spent streaming the successor's weights instead.
-//   layer l:   A qkv  ->  B attention  ->  C o_proj  =>  D gate/up  =>  E down  =>  A' qkv of layer l+1          ( => chained, -> plain )
-// Two streams X / Y swap roles every layer:  X: A B C . E        Y: (event: B done) D . A' B' C' . E'      X: (event: B' done) D' ...
-// so a chained kernel is launched when the kernel TWO before it has finished (stream order) and at most two kernels are in flight.
-// Why it cannot deadlock (a waiting kernel must never keep the kernel it waits for off the chip): every chained kernel and the kernel it
-// waits for are launched with <= 2 blocks per CU and <= 136 VGPRs — about half a CU each — so both are entirely resident whatever the dispatch order;
-// the attention kernel (16-wave blocks that need a whole CU) is never beside a waiting kernel: D is held back by an event until B has finished.
-// The waits are bounded all the same: a give-up is reported in workspace word 0 (vila_llm_decode_chain_error) instead of hanging the device.
-// MEASURED (profiles/r04_decode_chain_ab.log, five sessions): 3.28 ms per token chained against 2.99 plain — the device-side hand-off costs what a
-// kernel boundary costs on this chip, so the prefetched weights buy nothing.  The chain is therefore OFF by default; VILA_DECODE_CHAIN=1 /
-// vila_decode_force_chain(1) selects it (parity-tested: tests/test_gpu_model.py::test_chained_decode_step_equals_the_plain_step).
-static int g_decode_chain = -1;
-extern "C" void vila_decode_force_chain(int on) { g_decode_chain = on ? 1 : 0; }
-static int decode_chain_mode() {
-    if (g_decode_chain < 0) { const char* e = getenv("VILA_DECODE_CHAIN"); g_decode_chain = (e && e[0] == '1') ? 1 : 0; }
-    return g_decode_chain;
-}
-// VILA_DECODE_CHAIN_PRED (percent, default 95): how much of the predecessor's predicted run time (its bytes at 6.2 TB/s) a waiting kernel
-// treats as the point around which its polls concentrate (gemv_common.h chain_wait)
-static double chain_pred_scale() {
-    static double v = -1.0;
-    if (v < 0) { const char* e = getenv("VILA_DECODE_CHAIN_PRED"); v = (e && atoi(e) > 0) ? atoi(e) / 100.0 : 0.95; }
-    return v;
-}
-struct ChainStreams { hipStream_t s2 = nullptr; hipEvent_t fork = nullptr, join = nullptr; };
-static ChainStreams& chain_streams() {
-    static thread_local ChainStreams per_dev[16];
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    ChainStreams& c = per_dev[dev & 15];
-    if (c.s2 == nullptr) {
-        if (hipStreamCreateWithFlags(&c.s2, hipStreamNonBlocking) != hipSuccess) c.s2 = nullptr;
-        (void)hipEventCreateWithFlags(&c.fork, hipEventDisableTiming);
-        (void)hipEventCreateWithFlags(&c.join, hipEventDisableTiming);
-    }
-    return c;
-}
-// word 0 of the decode workspace: 1 if a chained kernel's bounded wait gave up since the last call of this function (then results are invalid)
+// word 0 of the decode workspace: 1 if a bounded grid-barrier wait of the persistent kernel gave up since the last call of this function
+// (then results are invalid)
 extern "C" int vila_llm_decode_chain_error(void* workspace, vila_stream_t stream) {
     hipStream_t s = S(stream);
     uint32_t h = 0;
@@ -573,17 +598,20 @@ extern "C" int vila_llm_decode_chain_error(void* workspace, vila_stream_t stream
     return (int)h;
 }
 
-static int decode_step_impl(const VilaLlmWeights* w, const VilaKvCache* cache, const VilaDecodeState* st, void* workspace, size_t workspace_bytes,
-                            const VilaSampling* sp, vila_stream_t stream) {
+// The batch-1 step: ql == nullptr runs the bf16 projections, otherwise the int4 layers' W4A16 GEMVs (the lm_head stays bf16 either way, as
+// AWQ / TinyChat keep it fp16).  Only the four projection launches of a layer differ between the two.
+static int decode_step_impl(const VilaLlmWeights* w, const VilaLlmLayerW4* ql, const VilaKvCache* cache, const VilaDecodeState* st,
+                            void* workspace, size_t workspace_bytes, const VilaSampling* sp, vila_stream_t stream) {
     const VilaLlmShape& sh = w->shape;
     hipStream_t s = S(stream);
-    VILA_REQUIRE(cache != nullptr && st != nullptr, "llm_decode: cache/state is NULL");
-    VILA_REQUIRE(workspace_bytes >= vila_llm_decode_workspace_bytes(&sh, cache->max_ctx), "llm_decode: workspace too small");
+    const bool w4 = ql != nullptr;
+    const char* fn = w4 ? "llm_decode_w4" : "llm_decode";
+    VILA_REQUIRE(cache != nullptr && st != nullptr, "%s: cache/state is NULL", fn);
+    VILA_REQUIRE(workspace_bytes >= vila_llm_decode_workspace_bytes(&sh, cache->max_ctx), "%s: workspace too small", fn);
     const int H = sh.hidden, F = sh.inter, hd = sh.head_dim, QS = sh.q_heads * hd, KS = sh.kv_heads * hd;
     const int ns = dec_splits(cache->max_ctx);
     Arena a(workspace, workspace_bytes);
-    const int n_chain = 4 * sh.n_layers + 2;                    // chained kernels of a token: A, C, D, E per layer + lm_head (+ 1 spare)
-    uint32_t* chain_mem = a.take<uint32_t>(64 + (size_t)n_chain * CHAIN_WORDS);    // [0] error word, [64..] per kernel: arrival count + CHAIN_FLAGS go-flags
+    uint32_t* sync = a.take<uint32_t>(DEC_SYNC_WORDS);          // [0] error word, [64..] the persistent kernel's barrier words
     bf16_t* x = a.take<bf16_t>(H);
     bf16_t* x2 = a.take<bf16_t>(H);
     bf16_t* q = a.take<bf16_t>(QS);
@@ -595,12 +623,12 @@ static int decode_step_impl(const VilaLlmWeights* w, const VilaKvCache* cache, c
     float* rope_cs = a.take<float>(hd);
     bf16_t* ao = a.take<bf16_t>(QS);
     void* smp_ws = a.take<char>(sample_workspace_bytes());
-    VILA_REQUIRE(a.ok(), "llm_decode: workspace arena overflow");
+    VILA_REQUIRE(a.ok(), "%s: workspace arena overflow", fn);
+    const size_t per_layer = (size_t)cache->n_slots * sh.kv_heads * cache->max_ctx * hd;
 
-    if (decode_persist_ok(sh, cache->max_ctx) && !decode_chain_mode() && cache->n_slots >= 1) {
+    if (!w4 && decode_persist_ok(sh, cache->max_ctx) && cache->n_slots >= 1) {
         // ---- the persistent token: prologue (embedding row, RoPE row, barrier words) + ONE launch for 28 layers and the head ----
         DpArgs d{};
-        const size_t per_layer = (size_t)cache->n_slots * sh.kv_heads * cache->max_ctx * hd;
         for (int l = 0; l < sh.n_layers; ++l) {
             const VilaLlmLayer& L = w->layers[l];
             const bool fused = (B(L.wk) == B(L.wq) + (size_t)QS * H) && (B(L.wv) == B(L.wk) + (size_t)KS * H) &&
@@ -611,98 +639,58 @@ static int decode_step_impl(const VilaLlmWeights* w, const VilaKvCache* cache, c
         d.norm_w = B(w->norm_w); d.lm_head = B(w->lm_head); d.logits = st->logits;
         d.kcache = B(cache->k); d.vcache = B(cache->v); d.kv_layer_stride = (int64_t)per_layer;
         d.pos_ptr = st->pos; d.rope_cs = rope_cs; d.x0 = x; d.x1 = x2; d.q = q; d.act = act; d.part_o = part_o; d.part_ml = part_ml;
-        d.sync = chain_mem;
+        d.sync = sync;
         d.n_layers = sh.n_layers; d.H = H; d.F = F; d.nq = sh.q_heads; d.nkv = sh.kv_heads; d.hd = hd; d.vocab = sh.vocab; d.max_ctx = cache->max_ctx;
         d.eps = sh.rms_eps; d.scale = 1.0f / sqrtf((float)hd);
-        VILA_TRY(launch_decode_prologue(B(w->embed), st->token, x, H, sh.vocab, st->pos, rope_cs, hd, sh.rope_theta, s, chain_mem + 64, 1));
+        VILA_TRY(launch_decode_prologue(B(w->embed), st->token, x, H, sh.vocab, st->pos, rope_cs, hd, sh.rope_theta, s, sync + 64));
         VILA_TRY(launch_decode_persist(d, s));
-        // the head as its own launch: final RMSNorm + lm_head rows -> fp32 logits (152 064 x 3584: 1.09 GB, 7 TB/s in gemv_kernel<0,7>).  The
-        // last layer's residual stream is in `x` (an even number of buffer swaps per layer).
-        GemvArgs lm{};
-        lm.x = x; lm.norm_w = B(w->norm_w); lm.eps = sh.rms_eps; lm.W = B(w->lm_head); lm.y_f32 = st->logits; lm.N = sh.vocab; lm.K = H; lm.mode = 0;
-        VILA_TRY(launch_gemv(lm, s));
-        if (sp != nullptr) VILA_TRY(launch_sample(st->logits, sh.vocab, sp->temperature, sp->top_k, sp->top_p, sp->seed, sp->seed_dev, st->pos, st->token, smp_ws, nullptr, s));
-        else VILA_TRY(launch_argmax(st->logits, sh.vocab, st->token, tv, ti, s));
-        VILA_TRY(launch_decode_advance(st->pos, st->token, st->out_ids, st->n_out, st->max_out, s));
-        return 0;
-    }
-    const bool split256 = decode_attn_mode() >= 1 && cache->max_ctx <= 2048 && hd == 128;
-    ChainStreams* cs = nullptr;
-    if (decode_chain_mode() && split256) {                      // (the long-context split-KV + merge pair stays unchained)
-        cs = &chain_streams();
-        if (cs->s2 == nullptr || cs->fork == nullptr || cs->join == nullptr) cs = nullptr;
-    }
-    const bool chained = cs != nullptr;
-    uint32_t* ctr = chained ? chain_mem + 64 : nullptr;
-    int k_idx = 0;                                              // index of the next kernel's done counter
-    int prev_grid = 0;                                          // grid of the kernel launched last (what a chained successor waits for)
-    // link of the next kernel: counts itself under its own index; `wait` = it is launched early and waits for the previous kernel's whole grid
-    // `pred_bytes`: what the kernel waited for streams — its predicted run time (at 6 TB/s) is slept through before the first poll
-    auto link = [&](ChainLink& c, bool wait, size_t pred_bytes) {
-        if (!chained) return;
-        c.ctr = ctr; c.err = chain_mem; c.done_idx = k_idx;
-        c.wait_idx = (wait && k_idx > 0) ? k_idx - 1 : -1; c.wait_target = (uint32_t)prev_grid;
-        const int us = (int)((double)pred_bytes / 6.2e6 * chain_pred_scale());
-        c.pre_sleep_us = (wait && us > 0) ? us : 0;
-        ++k_idx;
-    };
-    const size_t bytes_o = (size_t)H * QS * 2, bytes_gu = (size_t)2 * F * H * 2, bytes_dn = (size_t)H * F * 2;
-    const int bpc = chained ? 2 : 0;                            // half a CU per chained kernel (0 = the launcher's default of 4)
-
-    VILA_TRY(launch_decode_prologue(B(w->embed), st->token, x, H, sh.vocab, st->pos, rope_cs, hd, sh.rope_theta, s, ctr, chained ? n_chain : 0));
-    hipStream_t X = s, Y = chained ? cs->s2 : s;                // X runs A B C E of this layer, Y its D
-    if (chained) {
-        VILA_HIP(hipEventRecord(cs->fork, s));
-        VILA_HIP(hipStreamWaitEvent(cs->s2, cs->fork, 0));
-    }
-    bf16_t* cur = x; bf16_t* nxt = x2;
-    for (int l = 0; l < sh.n_layers; ++l) {
-        const VilaLlmLayer& L = w->layers[l];
-        const size_t per_layer = (size_t)cache->n_slots * sh.kv_heads * cache->max_ctx * hd;
-        bf16_t* kc = B(cache->k) + l * per_layer; bf16_t* vc = B(cache->v) + l * per_layer;
-        const bool fused = (B(L.wk) == B(L.wq) + (size_t)QS * H) && (B(L.wv) == B(L.wk) + (size_t)KS * H) &&
-                           (B(L.bk) == B(L.bq) + QS) && (B(L.bv) == B(L.bk) + KS);
-        VILA_REQUIRE(fused, "llm_decode: q/k/v projection weights and biases must be views of one fused [q+2kv, hidden] buffer");
-        QkvDecodeArgs qa{};
-        qa.x = cur; qa.norm_w = B(L.ln1_w); qa.eps = sh.rms_eps; qa.Wqkv = B(L.wq); qa.bqkv = B(L.bq); qa.q_out = q;
-        qa.kcache = kc; qa.vcache = vc; qa.pos_ptr = st->pos; qa.K = H; qa.nq = sh.q_heads; qa.nkv = sh.kv_heads; qa.hd = hd;
-        qa.max_ctx = cache->max_ctx; qa.rope_cs = rope_cs; qa.max_bpc = bpc;
-        link(qa.chain, l > 0, bytes_dn);                                  // A: chained behind the previous layer's E (layer 0: behind the prologue, stream order)
-        VILA_TRY(launch_qkv_decode(qa, X, &prev_grid));
-        AttnDecodeArgs ad{};
-        ad.q = q; ad.kcache = kc; ad.vcache = vc; ad.o = ao; ad.part_o = part_o; ad.part_ml = part_ml; ad.pos_ptr = st->pos;
-        ad.nq = sh.q_heads; ad.nkv = sh.kv_heads; ad.hd = hd; ad.max_ctx = cache->max_ctx; ad.n_splits = ns; ad.scale = 1.0f / sqrtf((float)hd);
-        ad.split256 = split256 ? 1 : 0;
-        VILA_TRY(launch_attn_decode(ad, X, nullptr));           // B: plain, behind A on the same stream
-        if (chained) {
-            VILA_HIP(hipEventRecord(cs->join, X));              // (event reuse: every record is consumed by the wait right below)
-            VILA_HIP(hipStreamWaitEvent(Y, cs->join, 0));       // D may not sit on the CUs while B needs whole ones
+    } else {
+        // per-head blocks over 256-key slices whose partials meet in the o_proj GEMV's prologue (§4.3; the W4 GEMV's merge holds up to 7 x 16 heads)
+        const bool split256 = decode_attn_mode() >= 1 && cache->max_ctx <= 2048 && hd == 128 && (!w4 || QS <= 7 * 16 * 128);
+        VILA_TRY(launch_decode_prologue(B(w->embed), st->token, x, H, sh.vocab, st->pos, rope_cs, hd, sh.rope_theta, s));
+        bf16_t* cur = x; bf16_t* nxt = x2;
+        for (int l = 0; l < sh.n_layers; ++l) {
+            const VilaLlmLayer& L = w->layers[l];
+            const VilaLlmLayerW4 Q = w4 ? ql[l] : VilaLlmLayerW4{};
+            bf16_t* kc = B(cache->k) + l * per_layer; bf16_t* vc = B(cache->v) + l * per_layer;
+            if (w4) {
+                GemvW4Args qa{};
+                qa.x = cur; qa.norm_w = B(L.ln1_w); qa.eps = sh.rms_eps; qa.Wq = (const uint32_t*)Q.qkv_q; qa.Wsz = (const uint32_t*)Q.qkv_sz;
+                qa.bias = B(L.bq); qa.K = H; qa.N = QS + 2 * KS; qa.mode = 3; qa.q_out = q; qa.kcache = kc; qa.vcache = vc; qa.pos_ptr = st->pos;
+                qa.rope_cs = rope_cs; qa.nq = sh.q_heads; qa.nkv = sh.kv_heads; qa.hd = hd; qa.max_ctx = cache->max_ctx;
+                VILA_TRY(launch_gemv_w4(qa, s));
+            } else {
+                const bool fused = (B(L.wk) == B(L.wq) + (size_t)QS * H) && (B(L.wv) == B(L.wk) + (size_t)KS * H) &&
+                                   (B(L.bk) == B(L.bq) + QS) && (B(L.bv) == B(L.bk) + KS);
+                VILA_REQUIRE(fused, "llm_decode: q/k/v projection weights and biases must be views of one fused [q+2kv, hidden] buffer");
+                QkvDecodeArgs qa{};
+                qa.x = cur; qa.norm_w = B(L.ln1_w); qa.eps = sh.rms_eps; qa.Wqkv = B(L.wq); qa.bqkv = B(L.bq); qa.q_out = q;
+                qa.kcache = kc; qa.vcache = vc; qa.pos_ptr = st->pos; qa.K = H; qa.nq = sh.q_heads; qa.nkv = sh.kv_heads; qa.hd = hd;
+                qa.max_ctx = cache->max_ctx; qa.rope_cs = rope_cs;
+                VILA_TRY(launch_qkv_decode(qa, s));
+            }
+            AttnDecodeArgs ad{};
+            ad.q = q; ad.kcache = kc; ad.vcache = vc; ad.o = ao; ad.part_o = part_o; ad.part_ml = part_ml; ad.pos_ptr = st->pos;
+            ad.nq = sh.q_heads; ad.nkv = sh.kv_heads; ad.hd = hd; ad.max_ctx = cache->max_ctx; ad.n_splits = ns; ad.scale = 1.0f / sqrtf((float)hd);
+            ad.split256 = split256 ? 1 : 0;
+            VILA_TRY(launch_attn_decode(ad, s));
+            GemvArgs o{};
+            o.x = ao; o.W = B(L.wo); o.residual = cur; o.y = nxt; o.N = H; o.K = QS; o.mode = 0;
+            if (split256) { o.mode = 2; o.part_o = part_o; o.part_ml = part_ml; o.pos_ptr = st->pos; o.n_splits = cdiv(cache->max_ctx, 256); o.split_keys = 256; o.grid_cap = decode_attn_mode() == 2 ? 512 : 256; }
+            VILA_TRY(proj_gemv(o, w4, Q.o_q, Q.o_sz, s));
+            GemvArgs gu{};
+            gu.x = nxt; gu.norm_w = B(L.ln2_w); gu.eps = sh.rms_eps; gu.W = B(L.w_gate); gu.W2 = B(L.w_up); gu.y = act; gu.N = F; gu.K = H; gu.mode = 1;
+            VILA_TRY(proj_gemv(gu, w4, Q.gateup_q, Q.gateup_sz, s));
+            GemvArgs dn{};
+            dn.x = act; dn.W = B(L.w_down); dn.residual = nxt; dn.y = cur; dn.N = H; dn.K = F; dn.mode = 0;
+            VILA_TRY(proj_gemv(dn, w4, Q.down_q, Q.down_sz, s));
         }
-        GemvArgs o{};
-        o.x = ao; o.W = B(L.wo); o.residual = cur; o.y = nxt; o.N = H; o.K = QS; o.mode = 0;
-        if (split256) { o.mode = 2; o.part_o = part_o; o.part_ml = part_ml; o.pos_ptr = st->pos; o.n_splits = cdiv(cache->max_ctx, 256); o.split_keys = 256; o.grid_cap = decode_attn_mode() == 2 ? 512 : 256; }
-        link(o.chain, false, 0);                                   // C: plain behind B, but it counts itself done for D
-        VILA_TRY(launch_gemv(o, X, &prev_grid));
-        GemvArgs gu{};
-        gu.x = nxt; gu.norm_w = B(L.ln2_w); gu.eps = sh.rms_eps; gu.W = B(L.w_gate); gu.W2 = B(L.w_up); gu.y = act; gu.N = F; gu.K = H; gu.mode = 1;
-        gu.max_bpc = bpc;
-        link(gu.chain, true, bytes_o);                                   // D: launched when B is done, waits for C
-        VILA_TRY(launch_gemv(gu, Y, &prev_grid));
-        GemvArgs dn{};
-        dn.x = act; dn.W = B(L.w_down); dn.residual = nxt; dn.y = cur; dn.N = H; dn.K = F; dn.mode = 0; dn.max_bpc = bpc;
-        link(dn.chain, true, bytes_gu);                                   // E: launched when C is done (stream order on X), waits for D
-        VILA_TRY(launch_gemv(dn, X, &prev_grid));
-        if (chained) { hipStream_t t = X; X = Y; Y = t; }       // the next layer's A goes behind D (done before E can be) and waits for E
     }
+    // the head: final RMSNorm + lm_head rows -> fp32 logits (152 064 x 3584: 1.09 GB, 7 TB/s in gemv_kernel<0,7>).  Both paths leave the last
+    // layer's residual stream in `x` (the persistent kernel swaps its buffers an even number of times per layer).
     GemvArgs lm{};
-    lm.x = cur; lm.norm_w = B(w->norm_w); lm.eps = sh.rms_eps; lm.W = B(w->lm_head); lm.y_f32 = st->logits; lm.N = sh.vocab; lm.K = H; lm.mode = 0;
-    lm.max_bpc = bpc;
-    link(lm.chain, true, bytes_dn);                                       // lm_head: like an A — behind the last D, waits for the last E
-    VILA_TRY(launch_gemv(lm, X, &prev_grid));
-    if (chained) {                                              // the token choice runs on the caller's stream behind BOTH streams
-        VILA_HIP(hipEventRecord(cs->fork, cs->s2));
-        VILA_HIP(hipStreamWaitEvent(s, cs->fork, 0));
-    }
+    lm.x = x; lm.norm_w = B(w->norm_w); lm.eps = sh.rms_eps; lm.W = B(w->lm_head); lm.y_f32 = st->logits; lm.N = sh.vocab; lm.K = H; lm.mode = 0;
+    VILA_TRY(launch_gemv(lm, s));
     if (sp != nullptr) VILA_TRY(launch_sample(st->logits, sh.vocab, sp->temperature, sp->top_k, sp->top_p, sp->seed, sp->seed_dev, st->pos, st->token, smp_ws, nullptr, s));
     else VILA_TRY(launch_argmax(st->logits, sh.vocab, st->token, tv, ti, s));
     VILA_TRY(launch_decode_advance(st->pos, st->token, st->out_ids, st->n_out, st->max_out, s));
@@ -957,7 +945,7 @@ extern "C" int vila_video_pool_bwd_bf16(const void* dpooled, void* dfeats, int n
 }
 
 // =================================================================================================
-// W4A16 decode: int4 group-128 weights for the five decoder-layer projections, bf16 everything else
+// W4A16 operators: int4 group-128 weights of the decoder-layer projections, as decode GEMVs and prefill GEMMs
 // =================================================================================================
 extern "C" int vila_gemv_w4_bf16(const void* x, const void* norm_w, float eps, const void* Wq, const void* Wsz,
                                  const void* bias, const void* residual, void* y, int N, int K, int mode, vila_stream_t stream) {
@@ -978,85 +966,6 @@ extern "C" int vila_gemv_w4_batch_bf16(const void* x, int64_t ldx, int n, const 
     g.y = B(y); g.ldy = N; g.n = n; g.N = N; g.K = K; g.mode = mode;
     return launch_gemv_w4_batch(g, S(stream));
 }
-
-static int decode_step_w4_impl(const VilaLlmWeights* w, const VilaLlmLayerW4* ql, const VilaKvCache* cache, const VilaDecodeState* st,
-                               void* workspace, size_t workspace_bytes, const VilaSampling* sp, vila_stream_t stream);
-extern "C" int vila_llm_decode_step_w4(const VilaLlmWeights* w, const VilaLlmLayerW4* ql, const VilaKvCache* cache, const VilaDecodeState* st,
-                                       void* workspace, size_t workspace_bytes, vila_stream_t stream) {
-    return decode_step_w4_impl(w, ql, cache, st, workspace, workspace_bytes, nullptr, stream);
-}
-// the W4A16 step with a stochastic pick (generate(do_sample=True) on a quantised decoder)
-extern "C" int vila_llm_decode_step_w4_sample(const VilaLlmWeights* w, const VilaLlmLayerW4* ql, const VilaKvCache* cache, const VilaDecodeState* st,
-                                              void* workspace, size_t workspace_bytes, const VilaSampling* sp, vila_stream_t stream) {
-    VILA_REQUIRE(sp != nullptr, "llm_decode_w4_sample: sampling parameters are NULL");
-    return decode_step_w4_impl(w, ql, cache, st, workspace, workspace_bytes, sp, stream);
-}
-static int decode_step_w4_impl(const VilaLlmWeights* w, const VilaLlmLayerW4* ql, const VilaKvCache* cache, const VilaDecodeState* st,
-                               void* workspace, size_t workspace_bytes, const VilaSampling* sp, vila_stream_t stream) {
-    const VilaLlmShape& sh = w->shape;
-    hipStream_t s = S(stream);
-    VILA_REQUIRE(cache != nullptr && st != nullptr && ql != nullptr, "llm_decode_w4: cache/state/weights is NULL");
-    VILA_REQUIRE(workspace_bytes >= vila_llm_decode_workspace_bytes(&sh, cache->max_ctx), "llm_decode_w4: workspace too small");
-    const int H = sh.hidden, F = sh.inter, hd = sh.head_dim, QS = sh.q_heads * hd;
-    const int ns = dec_splits(cache->max_ctx);
-    Arena a(workspace, workspace_bytes);
-    (void)a.take<uint32_t>(64 + (4 * (size_t)sh.n_layers + 2) * CHAIN_WORDS);      // same layout as the bf16 step: word 0 = the chain error flag (unused here, stays 0)
-    bf16_t* x = a.take<bf16_t>(H);
-    bf16_t* x2 = a.take<bf16_t>(H);
-    bf16_t* q = a.take<bf16_t>(QS);
-    bf16_t* act = a.take<bf16_t>(F);
-    float* part_o = a.take<float>((size_t)ns * QS);
-    float* part_ml = a.take<float>((size_t)ns * sh.q_heads * 2);
-    float* tv = a.take<float>(256);
-    int* ti = a.take<int>(256);
-    float* rope_cs = a.take<float>(hd);
-    bf16_t* ao = a.take<bf16_t>(QS);
-    void* smp_ws = a.take<char>(sample_workspace_bytes());
-    VILA_REQUIRE(a.ok(), "llm_decode_w4: workspace arena overflow");
-    const bool split256 = decode_attn_mode() >= 1 && cache->max_ctx <= 2048 && hd == 128 && QS <= 7 * 16 * 128;   // as the bf16 step (§4.3)
-    VILA_TRY(launch_decode_prologue(B(w->embed), st->token, x, H, sh.vocab, st->pos, rope_cs, hd, sh.rope_theta, s));
-    bf16_t* cur = x; bf16_t* nxt = x2;
-    for (int l = 0; l < sh.n_layers; ++l) {
-        const VilaLlmLayer& L = w->layers[l];
-        const VilaLlmLayerW4& Q = ql[l];
-        const size_t per_layer = (size_t)cache->n_slots * sh.kv_heads * cache->max_ctx * hd;
-        bf16_t* kc = B(cache->k) + l * per_layer; bf16_t* vc = B(cache->v) + l * per_layer;
-        GemvW4Args qa{};
-        qa.x = cur; qa.norm_w = B(L.ln1_w); qa.eps = sh.rms_eps; qa.Wq = (const uint32_t*)Q.qkv_q; qa.Wsz = (const uint32_t*)Q.qkv_sz;
-        qa.bias = B(L.bq); qa.K = H; qa.N = QS + 2 * sh.kv_heads * hd; qa.mode = 3; qa.q_out = q; qa.kcache = kc; qa.vcache = vc; qa.pos_ptr = st->pos;
-        qa.rope_cs = rope_cs; qa.nq = sh.q_heads; qa.nkv = sh.kv_heads; qa.hd = hd; qa.max_ctx = cache->max_ctx;
-        VILA_TRY(launch_gemv_w4(qa, s));
-        AttnDecodeArgs ad{};
-        ad.q = q; ad.kcache = kc; ad.vcache = vc; ad.o = ao; ad.part_o = part_o; ad.part_ml = part_ml; ad.pos_ptr = st->pos;
-        ad.nq = sh.q_heads; ad.nkv = sh.kv_heads; ad.hd = hd; ad.max_ctx = cache->max_ctx; ad.n_splits = ns; ad.scale = 1.0f / sqrtf((float)hd);
-        ad.split256 = split256 ? 1 : 0;                        // per-head blocks over 256-key slices; the slices meet in the o_proj kernel's prologue
-        VILA_TRY(launch_attn_decode(ad, s));
-        GemvW4Args o{};
-        o.x = ao; o.Wq = (const uint32_t*)Q.o_q; o.Wsz = (const uint32_t*)Q.o_sz; o.residual = cur; o.y = nxt; o.N = H; o.K = QS; o.mode = 0;
-        if (split256) { o.mode = 4; o.part_o = part_o; o.part_ml = part_ml; o.pos_ptr = st->pos; o.n_splits = cdiv(cache->max_ctx, 256); o.split_keys = 256; }
-        VILA_TRY(launch_gemv_w4(o, s));
-        GemvW4Args gu{};
-        gu.x = nxt; gu.norm_w = B(L.ln2_w); gu.eps = sh.rms_eps; gu.Wq = (const uint32_t*)Q.gateup_q; gu.Wsz = (const uint32_t*)Q.gateup_sz;
-        gu.y = act; gu.N = F; gu.K = H; gu.mode = 1;
-        VILA_TRY(launch_gemv_w4(gu, s));
-        GemvW4Args dn{};
-        dn.x = act; dn.Wq = (const uint32_t*)Q.down_q; dn.Wsz = (const uint32_t*)Q.down_sz; dn.residual = nxt; dn.y = cur; dn.N = H; dn.K = F; dn.mode = 0;
-        VILA_TRY(launch_gemv_w4(dn, s));
-    }
-    GemvArgs lm{};
-    lm.x = cur; lm.norm_w = B(w->norm_w); lm.eps = sh.rms_eps; lm.W = B(w->lm_head); lm.y_f32 = st->logits; lm.N = sh.vocab; lm.K = H; lm.mode = 0;
-    VILA_TRY(launch_gemv(lm, s));       // lm_head stays bf16 (as AWQ / TinyChat keep it fp16)
-    if (sp != nullptr) VILA_TRY(launch_sample(st->logits, sh.vocab, sp->temperature, sp->top_k, sp->top_p, sp->seed, sp->seed_dev, st->pos, st->token, smp_ws, nullptr, s));
-    else VILA_TRY(launch_argmax(st->logits, sh.vocab, st->token, tv, ti, s));
-    VILA_TRY(launch_decode_advance(st->pos, st->token, st->out_ids, st->n_out, st->max_out, s));
-    return 0;
-}
-
-// =================================================================================================
-// W4A16 prefill: the LLM prefill of vila_llm_prefill with the five decoder projections read from the int4 layers (gemm_w4.hip), so a
-// quantised model runs from its int4 weights alone.  The loop mirrors vila_llm_prefill; where the bf16 path folds the norms and RoPE into
-// split-K reduces this one runs the standalone rmsnorm / rope_kv kernels.
-// =================================================================================================
 extern "C" size_t vila_gemm_w4_workspace_bytes(int M, int N, int K, int mode) { return gemm_w4_workspace_bytes(M, N, K, mode); }
 extern "C" int vila_gemm_w4_bf16(const void* x, const void* Wq, const void* Wsz, const void* bias, const void* residual, void* y,
                                  int M, int N, int K, int mode, void* workspace, size_t workspace_bytes, vila_stream_t stream) {
@@ -1073,127 +982,4 @@ extern "C" int vila_gemm_w4_qkv_bf16(const void* x, const void* Wq, const void* 
     g.x = B(x); g.Wq = (const uint32_t*)Wq; g.Wsz = (const uint32_t*)Wsz; g.bias = B(bias); g.y = B(y);
     g.M = M; g.N = (q_heads + 2 * kv_heads) * head_dim; g.K = K; g.mode = 2; g.n_rope_heads = q_heads + kv_heads; g.hd = head_dim;
     return launch_gemm_w4(g, workspace, workspace_bytes, S(stream));
-}
-
-static size_t prefill_w4_gemm_ws(const VilaLlmShape& sh, int T) {
-    const int H = sh.hidden, F = sh.inter, QS = sh.q_heads * sh.head_dim, QKV = (sh.q_heads + 2 * sh.kv_heads) * sh.head_dim;
-    size_t b = gemm_w4_workspace_bytes(T, QKV, H, 2);
-    const size_t o = gemm_w4_workspace_bytes(T, H, QS, 0), gu = gemm_w4_workspace_bytes(T, F, H, 1), dn = gemm_w4_workspace_bytes(T, H, F, 0);
-    if (o > b) b = o;
-    if (gu > b) b = gu;
-    if (dn > b) b = dn;
-    return b;
-}
-extern "C" size_t vila_llm_prefill_w4_workspace_bytes(const VilaLlmShape* s, int T) {
-    return vila_llm_prefill_workspace_bytes(s, T) + prefill_w4_gemm_ws(*s, T) + 256;
-}
-
-extern "C" int vila_llm_prefill_w4(const VilaLlmWeights* w, const VilaLlmLayerW4* ql, const void* embeds, const int32_t* positions,
-                                   const int32_t* cu_seqlens, int n_seq, int T, int max_seqlen, const int32_t* seq_of_tok, const VilaKvCache* cache,
-                                   const int32_t* last_rows, int n_last, float* last_logits, float* all_logits, void* final_hidden,
-                                   void* layer_hidden, void* workspace, size_t workspace_bytes, vila_stream_t stream) {
-    const VilaLlmShape& sh = w->shape;
-    hipStream_t s = S(stream);
-    VILA_REQUIRE(ql != nullptr, "llm_prefill_w4: the int4 layers are NULL");
-    VILA_REQUIRE(T > 0 && n_seq > 0, "llm_prefill_w4: empty input");
-    VILA_REQUIRE(sh.q_heads % sh.kv_heads == 0, "llm: q heads must be a multiple of kv heads");
-    VILA_REQUIRE(cu_seqlens != nullptr || n_seq == 1, "llm_prefill_w4: n_seq > 1 needs cu_seqlens");
-    VILA_REQUIRE(workspace_bytes >= vila_llm_prefill_w4_workspace_bytes(&sh, T), "llm_prefill_w4: workspace too small");
-    const int H = sh.hidden, F = sh.inter, hd = sh.head_dim, QS = sh.q_heads * hd, KS = sh.kv_heads * hd, QKV = QS + 2 * KS;
-    VILA_REQUIRE(QS == H, "llm: q_heads*head_dim (%d) must equal hidden (%d) for the in-place attention buffer", QS, H);
-    Arena a(workspace, workspace_bytes);
-    bf16_t* x = a.take<bf16_t>((size_t)T * H);
-    bf16_t* h = a.take<bf16_t>((size_t)T * H);
-    bf16_t* qkv = a.take<bf16_t>((size_t)T * QKV);
-    bf16_t* act = a.take<bf16_t>((size_t)T * F);
-    float* cs = a.take<float>((size_t)T * hd / 2);
-    float* sn = a.take<float>((size_t)T * hd / 2);
-    bf16_t* lastbuf = a.take<bf16_t>((size_t)(T > 8 ? T : 8) * H);
-    const size_t gws_bytes = prefill_w4_gemm_ws(sh, T);
-    char* gws = a.take<char>(gws_bytes);
-    VILA_REQUIRE(a.ok(), "llm_prefill_w4: workspace arena overflow");
-    if (cache != nullptr) VILA_REQUIRE(max_seqlen <= cache->max_ctx, "llm_prefill_w4: sequence (%d) longer than the KV cache (%d)", max_seqlen, cache->max_ctx);
-
-    VILA_HIP(hipMemcpyAsync(x, embeds, (size_t)T * H * 2, hipMemcpyDeviceToDevice, s));
-    VILA_TRY(launch_rope_table(positions, cs, sn, T, hd, sh.rope_theta, s));
-    bf16_t* taps = B(layer_hidden);
-    if (taps) VILA_HIP(hipMemcpyAsync(taps, x, (size_t)T * H * 2, hipMemcpyDeviceToDevice, s));
-    // only last-row logits wanted (generation): the last layer is finished for those rows alone, as in vila_llm_prefill, here by the W4 GEMVs
-    const bool prune_last = final_hidden == nullptr && all_logits == nullptr && taps == nullptr && cache != nullptr && last_logits != nullptr &&
-                            last_rows != nullptr && n_last >= 1 && n_last <= 4;
-    auto gemm4 = [&](const bf16_t* xin, const void* q, const void* sz, const void* bias, const bf16_t* res, bf16_t* y, int N, int K, int mode) {
-        GemmW4Args g{};
-        g.x = xin; g.Wq = (const uint32_t*)q; g.Wsz = (const uint32_t*)sz; g.bias = B(bias); g.residual = res; g.y = y;
-        g.M = T; g.N = N; g.K = K; g.mode = mode; g.n_rope_heads = sh.q_heads + sh.kv_heads; g.hd = hd;
-        return launch_gemm_w4(g, gws, gws_bytes, s);
-    };
-    for (int l = 0; l < sh.n_layers; ++l) {
-        const VilaLlmLayer& L = w->layers[l];
-        const VilaLlmLayerW4& Q = ql[l];
-        VILA_REQUIRE(L.bq != nullptr && B(L.bk) == B(L.bq) + QS && B(L.bv) == B(L.bk) + KS,
-                     "llm_prefill_w4: the q/k/v biases must be one contiguous q|k|v vector (layer %d)", l);
-        bf16_t* kc = nullptr; bf16_t* vc = nullptr; int max_ctx = 0;
-        if (cache != nullptr) {
-            const size_t per_layer = (size_t)cache->n_slots * sh.kv_heads * cache->max_ctx * hd;
-            kc = B(cache->k) + l * per_layer; vc = B(cache->v) + l * per_layer; max_ctx = cache->max_ctx;
-        }
-        VILA_TRY(launch_rmsnorm(x, B(L.ln1_w), h, T, H, sh.rms_eps, s));
-        VILA_TRY(gemm4(h, Q.qkv_q, Q.qkv_sz, L.bq, nullptr, qkv, QKV, H, 2));              // q | k | v + bias, natural column order
-        VILA_TRY(launch_rope_kv(qkv, cs, sn, positions, seq_of_tok, kc, vc, T, sh.q_heads, sh.kv_heads, hd, max_ctx, s));
-        AttnArgs at{};
-        at.q = qkv; at.k = qkv + QS; at.v = qkv + QS + KS; at.o = h;
-        at.q_tok_stride = at.k_tok_stride = at.v_tok_stride = QKV; at.o_tok_stride = QS;
-        at.q_head_stride = at.k_head_stride = at.v_head_stride = at.o_head_stride = hd;
-        at.cu_seqlens = cu_seqlens; at.n_seq = n_seq; at.total_tokens = T; at.max_seqlen = (cu_seqlens ? max_seqlen : T);
-        at.n_q_heads = sh.q_heads; at.n_kv_heads = sh.kv_heads; at.head_dim = hd; at.causal = 1;
-        at.scale = 1.0f / sqrtf((float)hd); at.lse = nullptr;
-        VILA_TRY(launch_attn_fwd(at, s));
-        if (l == sh.n_layers - 1 && prune_last) {
-            // generation prefill: after the last layer's K / V are in the cache, o_proj, the post-attention norm and the MLP of the asked-for
-            // rows run as the W4 decode GEMVs (modes 0 and 1), the same kernels and arithmetic order as the W4 decode step
-            VILA_TRY(launch_copy_rows(h, lastbuf, last_rows, nullptr, n_last, QS, s));
-            VILA_TRY(launch_copy_rows(x, lastbuf + (size_t)n_last * H, last_rows, nullptr, n_last, H, s));
-            for (int r = 0; r < n_last; ++r) {
-                bf16_t* ar = lastbuf + (size_t)r * H;
-                bf16_t* xr = lastbuf + (size_t)(n_last + r) * H;
-                bf16_t* fr = act + (size_t)r * F;
-                GemvW4Args o{};
-                o.x = ar; o.Wq = (const uint32_t*)Q.o_q; o.Wsz = (const uint32_t*)Q.o_sz; o.residual = xr; o.y = xr; o.N = H; o.K = QS; o.mode = 0;
-                VILA_TRY(launch_gemv_w4(o, s));
-                GemvW4Args gu{};
-                gu.x = xr; gu.norm_w = B(L.ln2_w); gu.eps = sh.rms_eps; gu.Wq = (const uint32_t*)Q.gateup_q; gu.Wsz = (const uint32_t*)Q.gateup_sz;
-                gu.y = fr; gu.N = F; gu.K = H; gu.mode = 1;
-                VILA_TRY(launch_gemv_w4(gu, s));
-                GemvW4Args dn{};
-                dn.x = fr; dn.Wq = (const uint32_t*)Q.down_q; dn.Wsz = (const uint32_t*)Q.down_sz; dn.residual = xr; dn.y = ar; dn.N = H; dn.K = F; dn.mode = 0;
-                VILA_TRY(launch_gemv_w4(dn, s));
-            }
-            break;
-        }
-        VILA_TRY(gemm4(h, Q.o_q, Q.o_sz, nullptr, x, x, H, QS, 0));                      // x += o_proj(attn)
-        VILA_TRY(launch_rmsnorm(x, B(L.ln2_w), h, T, H, sh.rms_eps, s));
-        VILA_TRY(gemm4(h, Q.gateup_q, Q.gateup_sz, nullptr, nullptr, act, F, H, 1));      // silu(gate) * up
-        VILA_TRY(gemm4(act, Q.down_q, Q.down_sz, nullptr, x, x, H, F, 0));                // x += down(...)
-        if (taps) VILA_HIP(hipMemcpyAsync(taps + (size_t)(l + 1) * T * H, x, (size_t)T * H * 2, hipMemcpyDeviceToDevice, s));
-    }
-
-    if (final_hidden != nullptr || all_logits != nullptr) {
-        bf16_t* fh = final_hidden ? B(final_hidden) : h;
-        VILA_TRY(launch_rmsnorm(x, B(w->norm_w), fh, T, H, sh.rms_eps, s));
-        if (all_logits) VILA_TRY(gemm(fh, H, w->lm_head, H, nullptr, nullptr, 0, all_logits, sh.vocab, T, sh.vocab, H, EPI_NONE, s, nullptr, 1));
-    }
-    if (n_last > 0 && last_logits != nullptr) {
-        VILA_REQUIRE(last_rows != nullptr, "llm_prefill_w4: last_rows is NULL");
-        if (!prune_last) VILA_TRY(launch_copy_rows(x, lastbuf, last_rows, nullptr, n_last, H, s));
-        if (n_last == 1) {
-            GemvArgs g{};
-            g.x = lastbuf; g.norm_w = B(w->norm_w); g.eps = sh.rms_eps; g.W = B(w->lm_head); g.y_f32 = last_logits;
-            g.N = sh.vocab; g.K = H; g.mode = 0;
-            VILA_TRY(launch_gemv(g, s));
-        } else {
-            VILA_TRY(launch_rmsnorm(lastbuf, B(w->norm_w), lastbuf, n_last, H, sh.rms_eps, s));
-            VILA_TRY(gemm(lastbuf, H, w->lm_head, H, nullptr, nullptr, 0, last_logits, sh.vocab, n_last, sh.vocab, H, EPI_NONE, s, nullptr, 1));
-        }
-    }
-    return 0;
 }

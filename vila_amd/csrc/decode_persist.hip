@@ -35,6 +35,9 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t dp_rsrc(const void* p, int byt
 __device__ __forceinline__ float dp_ld_bf16(__amdgpu_buffer_rsrc_t rs, int idx) {
     return bf2f((bf16_t)__builtin_amdgcn_raw_buffer_load_b16(rs, (unsigned)idx * 2u, 0, 16));
 }
+__device__ __forceinline__ u32x4 dp_ldx16(__amdgpu_buffer_rsrc_t rs, int c) {      // 16-byte chunk c
+    return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (unsigned)c * 16u, 0, 16));
+}
 __device__ __forceinline__ void dp_st_u32(uint32_t* p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void dp_st_u16(bf16_t* p, bf16_t v) { __hip_atomic_store((unsigned short*)p, (unsigned short)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void dp_st_f2(float* p, float a, float b) {
@@ -173,9 +176,7 @@ __device__ __forceinline__ void dp_gemv_phase(DpBuf<R, U>& b, const bf16_t* sx, 
 }
 
 // ---- activation staging (all 8 waves call; workers act) -----------------------------------------------------------------------
-// RMSNorm form: the launch path's stage_x<true> with its 256 threads = worker waves 0..3 (same chunk -> thread map, same partial
-// sums, same order of the four wave sums): bit-identical rstd.
-// RMSNorm form: the launch path's stage_x<true> with its 256 threads = worker waves 0..3 (same chunk -> thread map, same partial sums, same
+// RMSNorm form: the launch path's stage_x with its 256 threads = worker waves 0..3 (same chunk -> thread map, same partial sums, same
 // order of the four wave sums): bit-identical rstd.  The gain is requested together with x (the launch path reads it behind the reduction: one
 // more dependent round trip).  (Requesting it ahead of the grid barrier, with the weight prefetch, was tried: the allocator spills it across
 // the barrier and reloads it element by element.)
@@ -189,7 +190,7 @@ __device__ __forceinline__ void dp_stage_x_norm(const bf16_t* x, const bf16_t* _
 #pragma unroll
         for (int i = 0; i < MAXC; ++i) {
             const int c = tid + 256 * i;
-            v[i] = (c < nch) ? ldx16<true>(x, rs, c) : (u32x4){0u, 0u, 0u, 0u};
+            v[i] = (c < nch) ? dp_ldx16(rs, c) : (u32x4){0u, 0u, 0u, 0u};
         }
 #pragma unroll
         for (int i = 0; i < MAXC; ++i) { int c = tid + 256 * i; c = c < nch ? c : nch - 1; g[i] = *(const u32x4*)(norm_w + c * 8); }
@@ -224,7 +225,7 @@ __device__ __forceinline__ void dp_stage_x_copy(const bf16_t* x, int K, bf16_t* 
         for (int c0 = tid; c0 < nch; c0 += 4 * DPW * 64) {
             u32x4 t[4];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) { const int c = c0 + DPW * 64 * i; t[i] = (c < nch) ? ldx16<true>(x, rs, c) : (u32x4){0u, 0u, 0u, 0u}; }
+            for (int i = 0; i < 4; ++i) { const int c = c0 + DPW * 64 * i; t[i] = (c < nch) ? dp_ldx16(rs, c) : (u32x4){0u, 0u, 0u, 0u}; }
 #pragma unroll
             for (int i = 0; i < 4; ++i) { const int c = c0 + DPW * 64 * i; if (c < nch) *(u32x4*)(sx + c * 8) = t[i]; }
         }

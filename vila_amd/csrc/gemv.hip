@@ -5,6 +5,7 @@
 // (bias, RoPE, KV-cache write, SiLU*up, residual add) are fused so a decoder layer is 6 launches.
 #include "kernels.h"
 #include "gemv_common.h"
+#include "decode_persist.h"
 
 #define DEC_KS 64      // keys per split of the decode attention
 #define DEC_MAXG 8     // max query heads per kv head
@@ -129,10 +130,8 @@ __global__ __launch_bounds__(256) void gemv_kernel(GemvArgs p, int n_groups, int
             rows[0] = p.W + (int64_t)n * p.K; rows[1] = p.W + (int64_t)n1 * p.K;
         }
     };
-    // Epilogue: after the wave reduction every lane holds the sums; lanes 0 and 1 each produce one of the wave's two adjacent outputs (rows n, n + 1).
-    // Plain launch: each stores its own bf16.  Chained launch (a successor reads the output while this kernel's neighbours still run): lane 0
-    // stores both as ONE write-through 4-byte word (gemv_common.h store_bf16_pair).
-    const bool coh_out = p.chain.ctr != nullptr && p.chain.done_idx >= 0;
+    // Epilogue: after the wave reduction every lane holds the sums; lanes 0 and 1 each produce and store one of the wave's two adjacent
+    // outputs (rows n, n + 1).
     float e_bias = 0.f, e_res = 0.f;
     auto finish = [&](int gg, float (&acc)[R]) {
         const int n = gg * 2;
@@ -148,13 +147,7 @@ __global__ __launch_bounds__(256) void gemv_kernel(GemvArgs p, int n_groups, int
             if (p.residual != nullptr) v = bfround(v) + e_res;
             o = f2bf(v);
         }
-        if (p.y == nullptr) return;
-        if (coh_out) {
-            const bf16_t o1 = (bf16_t)__shfl((int)o, 1, 64);
-            if (lane == 0 && n < p.N) store_bf16_pair(p.y, n, n + 1 < p.N, o, o1, true);
-        } else if (lane < 2 && n + lane < p.N) {
-            p.y[n + lane] = o;
-        }
+        if (p.y != nullptr && lane < 2 && n + lane < p.N) p.y[n + lane] = o;
     };
     // the epilogue's operands are requested BEFORE the dot product: fetched after the reduction they add a dependent memory round
     // trip (~1 us) to the tail of every wave, i.e. to the kernel
@@ -174,19 +167,15 @@ __global__ __launch_bounds__(256) void gemv_kernel(GemvArgs p, int n_groups, int
     const bool has = g < n_groups;
     // issue the first weight batch before staging x only for short rows (K <= 4096: the staging latency is comparable to the
     // stream); for K = 18944 the x staging is long and queuing the weight loads in front of it measured 13 % slower
-    // (a chained kernel always prefetches: what it loads before the wait streams in under its predecessor's tail)
-    const bool early = has && (p.K <= 4096 || p.chain.ctr != nullptr);
+    const bool early = has && p.K <= 4096;
     if (early) { rows_of(g, rows); load_batch<R, U>(rows, 0, lane, nch, b0); }
     if (has) epi_fetch(g);
-    chain_wait(p.chain);                        // everything above reads weights / operands of kernels <= i-2 only
     if constexpr (MODE == 2) {
         const int ks = p.split_keys > 0 ? p.split_keys : DEC_KS;
         const int n_active = (*p.pos_ptr + ks) / ks;             // ceil((pos+1)/ks)
         stage_x_attn(p.part_o, p.part_ml, n_active, p.K >> 7, sx, scratch);
-    } else if (p.chain.ctr != nullptr && p.chain.wait_idx >= 0) {
-        stage_x<true>(p.x, p.norm_w, p.eps, p.K, sx, scratch);   // x comes from the kernel just waited for: sc1 loads
     } else {
-        stage_x<false>(p.x, p.norm_w, p.eps, p.K, sx, scratch);
+        stage_x(p.x, p.norm_w, p.eps, p.K, sx, scratch);
     }
     if (early) {
         float acc[R];
@@ -206,19 +195,12 @@ __global__ __launch_bounds__(256) void gemv_kernel(GemvArgs p, int n_groups, int
         wave_rows_dot<R, U>(rows, sx, p.K, lane, acc, 0);
         finish(g, acc);
     }
-    chain_done(p.chain);
 }
 
 // Grid sizing for the HBM-bound GEMVs: a multiple of the 256 CUs (the dispatcher deals blocks round-robin, so 448 blocks
-// would leave 64 CUs with half the work of the others) and at most 4 blocks (16 waves) per CU = everything resident at once;
+// would leave 64 CUs with half the work of the others) and at most GEMV_BPC blocks per CU (4 = 16 waves = everything resident at once);
 // waves then walk the row groups with a grid stride.
-// bpc = blocks per CU cap: a chained kernel that leaves half of every CU's registers to its neighbour lets that neighbour's blocks be
-// resident (and prefetching) while it runs (api.hip "chained decode step").
-static int gemv_default_bpc() {           // VILA_GEMV_BPC (1..4): tuning / A-B switch for the unchained launches
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("VILA_GEMV_BPC"); v = (e && e[0] >= '1' && e[0] <= '4') ? e[0] - '0' : 4; }
-    return v;
-}
+#define GEMV_BPC 4
 static int gemv_cu_count() {
     static thread_local int per_dev[16] = {0};
     int dev = 0;
@@ -243,50 +225,44 @@ static int gemv_skew() {
 }
 // grid of an HBM-bound GEMV: (CUs) x (blocks per CU, 1..4) so that blocks b, b + CUs, ... share a CU and deal that CU's row groups among their
 // waves (*ncu_out = CUs); small problems (fewer groups than one block per CU would hold) keep one block per 4 groups and the plain walk (*ncu_out = 0)
-static inline int balanced_grid(int n_groups, int bpc, int* ncu_out) {
+static inline int balanced_grid(int n_groups, int* ncu_out) {
     const int ncu = gemv_cu_count();
     int want = cdiv(n_groups, 4);
-    const int b = (bpc >= 1 && bpc <= 4) ? bpc : gemv_default_bpc();
     if (want <= ncu || !gemv_cu_map_on()) {
         if (ncu_out) *ncu_out = 0;
-        const int cap = ncu * b;
+        const int cap = ncu * GEMV_BPC;
         if (want > cap) want = cap;
         return want <= ncu ? want : cdiv(want, ncu) * ncu;
     }
-    int per = cdiv(want, ncu); if (per > b) per = b;
+    int per = cdiv(want, ncu); if (per > GEMV_BPC) per = GEMV_BPC;
     if (ncu_out) *ncu_out = ncu;
     return ncu * per;
 }
 
-int launch_gemv(const GemvArgs& a, hipStream_t s, int* grid_out) {
+int launch_gemv(const GemvArgs& a, hipStream_t s) {
     VILA_REQUIRE(a.K % 8 == 0 && a.K > 0 && a.N > 0, "gemv: K=%d must be a positive multiple of 8", a.K);
     VILA_REQUIRE((uintptr_t)a.W % 16 == 0, "gemv: weight pointer alignment");
     const int n_groups = cdiv(a.N, 2);
     int ncu = 0;
-    int grid = balanced_grid(n_groups, a.max_bpc, &ncu);
+    int grid = balanced_grid(n_groups, &ncu);
     size_t lds = ((size_t)a.K * 2 + 15) / 16 * 16 + 16;
     const bool short_k = a.K <= 3584;
-    GemvArgs b = a;                                              // (the chain link learns the grid it is launched with)
     if (a.mode == 1) {
         VILA_REQUIRE(a.W2 != nullptr && a.y != nullptr && (uintptr_t)a.x % 16 == 0, "gemv: gate/up mode needs W2, bf16 y, aligned x");
-        b.chain.done_blocks = (uint32_t)grid;
-        hipLaunchKernelGGL((gemv_kernel<1, 4>), dim3(grid), dim3(256), lds, s, b, n_groups, ncu, gemv_skew());
+        hipLaunchKernelGGL((gemv_kernel<1, 4>), dim3(grid), dim3(256), lds, s, a, n_groups, ncu, gemv_skew());
     } else if (a.mode == 2) {
         VILA_REQUIRE(a.part_o != nullptr && a.part_ml != nullptr && a.pos_ptr != nullptr && a.K % 128 == 0, "gemv: attention-merge mode needs partials");
         lds += (size_t)a.n_splits * (a.K / 128) * 4;
         const int cap = a.grid_cap > 0 ? a.grid_cap : 256;           // the merge prologue is paid per block: default ~1 block per CU
         if (grid > cap) grid = ncu > 0 ? (cap / ncu >= 1 ? (cap / ncu) * ncu : ncu) : cap;
-        b.chain.done_blocks = (uint32_t)grid;
-        if (short_k) hipLaunchKernelGGL((gemv_kernel<2, 7>), dim3(grid), dim3(256), lds, s, b, n_groups, ncu, 0);
-        else hipLaunchKernelGGL((gemv_kernel<2, 4>), dim3(grid), dim3(256), lds, s, b, n_groups, ncu, 0);
+        if (short_k) hipLaunchKernelGGL((gemv_kernel<2, 7>), dim3(grid), dim3(256), lds, s, a, n_groups, ncu, 0);
+        else hipLaunchKernelGGL((gemv_kernel<2, 4>), dim3(grid), dim3(256), lds, s, a, n_groups, ncu, 0);
     } else {
         VILA_REQUIRE((uintptr_t)a.x % 16 == 0, "gemv: x alignment");
-        b.chain.done_blocks = (uint32_t)grid;
-        if (short_k) hipLaunchKernelGGL((gemv_kernel<0, 7>), dim3(grid), dim3(256), lds, s, b, n_groups, ncu, 0);
-        else hipLaunchKernelGGL((gemv_kernel<0, 4>), dim3(grid), dim3(256), lds, s, b, n_groups, ncu, 0);
+        if (short_k) hipLaunchKernelGGL((gemv_kernel<0, 7>), dim3(grid), dim3(256), lds, s, a, n_groups, ncu, 0);
+        else hipLaunchKernelGGL((gemv_kernel<0, 4>), dim3(grid), dim3(256), lds, s, a, n_groups, ncu, 0);
     }
     VILA_LAUNCH_CHECK();
-    if (grid_out != nullptr) *grid_out = grid;
     return 0;
 }
 
@@ -359,9 +335,7 @@ __global__ __launch_bounds__(256) void qkv_decode_kernel(QkvDecodeArgs p, int nc
     Batch<2, U> b0;
     const bool has = g < n_groups;
     if (has) { rows_of(g); load_batch<2, U>(rows, 0, lane, nch, b0); epi_fetch(g); }
-    chain_wait(p.chain);
-    if (p.chain.ctr != nullptr && p.chain.wait_idx >= 0) stage_x<true>(p.x, p.norm_w, p.eps, p.K, sx, scratch);
-    else stage_x<false>(p.x, p.norm_w, p.eps, p.K, sx, scratch);
+    stage_x(p.x, p.norm_w, p.eps, p.K, sx, scratch);
     if (has) {
         float acc[2] = {0.f, 0.f};
         fma_batch<2, U>(b0, sx, 0, lane, nch, acc);
@@ -376,22 +350,18 @@ __global__ __launch_bounds__(256) void qkv_decode_kernel(QkvDecodeArgs p, int nc
         wave_rows_dot<2, U>(rows, sx, p.K, lane, acc, 0);
         finish(g, acc);
     }
-    chain_done(p.chain);
 }
 
-int launch_qkv_decode(const QkvDecodeArgs& a, hipStream_t s, int* grid_out) {
+int launch_qkv_decode(const QkvDecodeArgs& a, hipStream_t s) {
     VILA_REQUIRE(a.K % 8 == 0 && a.hd % 4 == 0 && a.rope_cs != nullptr, "qkv_decode: K=%d hd=%d", a.K, a.hd);
     const int n_groups = (a.nq + 2 * a.nkv) * (a.hd / 2);
     const size_t lds = ((size_t)a.K * 2 + 15) / 16 * 16 + 16;
     // one rotate-half pair per wave; K <= 3584: the whole row pair (14 x 16 B per lane) is in flight in ONE round trip
     int ncu = 0;
-    const int grid = balanced_grid(n_groups, a.max_bpc, &ncu);
-    QkvDecodeArgs b = a;
-    b.chain.done_blocks = (uint32_t)grid;
-    if (a.K <= 3584) hipLaunchKernelGGL(qkv_decode_kernel<7>, dim3(grid), dim3(256), lds, s, b, ncu);
-    else hipLaunchKernelGGL(qkv_decode_kernel<4>, dim3(grid), dim3(256), lds, s, b, ncu);
+    const int grid = balanced_grid(n_groups, &ncu);
+    if (a.K <= 3584) hipLaunchKernelGGL(qkv_decode_kernel<7>, dim3(grid), dim3(256), lds, s, a, ncu);
+    else hipLaunchKernelGGL(qkv_decode_kernel<4>, dim3(grid), dim3(256), lds, s, a, ncu);
     VILA_LAUNCH_CHECK();
-    if (grid_out != nullptr) *grid_out = grid;
     return 0;
 }
 
@@ -636,7 +606,7 @@ int launch_attn_decode_rows(const AttnDecodeArgs& a0, int n_rows, int64_t q_row_
     return 0;
 }
 
-int launch_attn_decode(const AttnDecodeArgs& a, hipStream_t s, int* grid_out) {
+int launch_attn_decode(const AttnDecodeArgs& a, hipStream_t s) {
     VILA_REQUIRE(a.hd == 128, "attn_decode: head_dim must be 128 (got %d)", a.hd);
     VILA_REQUIRE(a.nq % a.nkv == 0 && a.nq / a.nkv <= DEC_MAXG, "attn_decode: GQA group %d/%d unsupported (max %d)", a.nq, a.nkv, DEC_MAXG);
     VILA_REQUIRE(a.n_splits * DEC_KS >= a.max_ctx, "attn_decode: n_splits too small for max_ctx");
@@ -644,7 +614,6 @@ int launch_attn_decode(const AttnDecodeArgs& a, hipStream_t s, int* grid_out) {
         VILA_REQUIRE(a.max_ctx <= 2048 && a.n_splits * DEC_KS >= a.max_ctx, "attn_decode: 256-key slices need max_ctx <= 2048");
         hipLaunchKernelGGL(attn_decode_head<true>, dim3(a.nq, cdiv(a.max_ctx, 256)), dim3(1024), 0, s, a);
         VILA_LAUNCH_CHECK();
-        if (grid_out != nullptr) *grid_out = a.nq * cdiv(a.max_ctx, 256);
         return 0;
     }
     if (a.o != nullptr && a.max_ctx <= 2048 && !a.force_split) {
@@ -672,12 +641,10 @@ int launch_attn_decode(const AttnDecodeArgs& a, hipStream_t s, int* grid_out) {
 // both rounded to bf16 (HF casts cos/sin to the activation dtype before use)
 __global__ void decode_prologue_kernel(const bf16_t* __restrict__ table, const int64_t* __restrict__ tok, bf16_t* __restrict__ out, int H,
                                        int64_t vocab, const int32_t* __restrict__ pos, float* __restrict__ rope_cs, int hd, float theta,
-                                       uint32_t* __restrict__ chain_ctr, int n_chain) {
-    // chained step: this token's done counters start at zero (every chained kernel is launched behind this one)
-    // (n_chain kernels x (1 count + CHAIN_FLAGS flag) words, CHAIN_STRIDE words apart)
-    if (chain_ctr != nullptr)
-        for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n_chain * (CHAIN_FLAGS + 1); i += gridDim.x * blockDim.x)
-            chain_ctr[(size_t)i * CHAIN_STRIDE] = 0u;
+                                       uint32_t* __restrict__ dp_sync) {
+    // the persistent token's grid-barrier words start at zero (decode_persist.hip is launched behind this kernel)
+    if (dp_sync != nullptr)
+        for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < DP_SYNC_COUNT; i += gridDim.x * blockDim.x) dp_sync[(size_t)i * DP_SYNC_STRIDE] = 0u;
     int64_t id = *tok;
     id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
     for (int c = blockIdx.x * blockDim.x + threadIdx.x; c < (H >> 3); c += gridDim.x * blockDim.x)
@@ -691,10 +658,10 @@ __global__ void decode_prologue_kernel(const bf16_t* __restrict__ table, const i
     }
 }
 int launch_decode_prologue(const bf16_t* table, const int64_t* tok, bf16_t* out, int H, int64_t vocab, const int32_t* pos, float* rope_cs,
-                           int hd, float theta, hipStream_t s, uint32_t* chain_ctr, int n_chain) {
+                           int hd, float theta, hipStream_t s, uint32_t* dp_sync) {
     VILA_REQUIRE(hd / 2 <= 256, "decode_prologue: head_dim too large");
     hipLaunchKernelGGL(decode_prologue_kernel, dim3(cdiv(H / 8, 256)), dim3(256), 0, s, table, tok, out, H, vocab, pos, rope_cs, hd, theta,
-                       chain_ctr, n_chain);
+                       dp_sync);
     VILA_LAUNCH_CHECK();
     return 0;
 }
