@@ -158,9 +158,8 @@ size_t vila_llm_decode_workspace_bytes(const VilaLlmShape* s, int max_ctx);
 int vila_llm_decode_launches(const VilaLlmShape* s, int max_ctx);
 int vila_llm_decode_step(const VilaLlmWeights* w, const VilaKvCache* cache, const VilaDecodeState* st,
                          void* workspace, size_t workspace_bytes, vila_stream_t stream);
-/* Word 0 of the decode workspace is an error flag: the caller zeroes the first 256 bytes of a new workspace once.  Only the opt-in PERSISTENT
- * step writes it (vila_hip_tuning.h vila_decode_force_persist / VILA_DECODE_PERSIST=1: its grid-barrier waits are bounded and a give-up sets
- * the word).  This call synchronises `stream`, returns the word and clears it: 0 = every token so far is valid. */
+/* Always returns 0: no decode step reports a device-side error.  Kept, with its signature, so that existing bindings still link; it neither
+ * reads the workspace nor touches the stream. */
 int vila_llm_decode_chain_error(void* workspace, vila_stream_t stream);
 
 /* generate(do_sample=True): what HF GenerationMixin.sample does after the forward — logits / temperature -> TopK -> TopP -> softmax ->

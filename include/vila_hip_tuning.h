@@ -1,7 +1,7 @@
 /* vila_hip_tuning.h — tuning and test switches of libvila_hip.so.  NOT part of the drop-in boundary (include/vila_hip.h):
  * these are PROCESS-GLOBAL, not thread-safe, and exist for the A/B measurements under tools/ and for the parity tests that pin one
  * kernel variant (tests/test_gpu_ops.py).  A product binding never calls them; every switch defaults to the measured-best policy.
- * Environment equivalents read once at first use: VILA_GEMM_EX, VILA_ATTN_FWD=v1, VILA_ATTN_KS, VILA_ATTN_BWD=v1, VILA_DECODE_ATTN, VILA_DECODE_PERSIST. */
+ * Environment equivalents read once at first use: VILA_GEMM_EX, VILA_ATTN_FWD=v1, VILA_ATTN_KS, VILA_ATTN_BWD=v1, VILA_DECODE_ATTN. */
 #ifndef VILA_HIP_TUNING_H
 #define VILA_HIP_TUNING_H
 #ifdef __cplusplus
@@ -15,14 +15,6 @@ void vila_gemm_force_hybrid(int on);
 /* tuning hook for the decode step's attention (caches up to 2048 positions): 2 (default) / 1 = per-head blocks over 256-key slices with the
  * merge in the o_proj GEMV's prologue (512 / 256 o_proj blocks), 0 = one block per query head over the whole context + plain o_proj */
 void vila_decode_force_attn(int mode);
-/* the batch-1 decode token as ONE persistent launch (decode_persist.hip: 28 layers x 5 phases + lm_head behind fence-free grid barriers, the
- * next phase's weights streaming across every barrier) + lm_head: 1 = on where the shape is supported, 0 = the per-kernel step (prologue +
- * 5 launches per layer + lm_head; the default: the two measure within 1.5 % of each other); environment: VILA_DECODE_PERSIST=1.  Logits are
- * bit-identical either way (tests/test_gpu_model.py::test_persistent_decode_step_equals_the_launch_path). */
-void vila_decode_force_persist(int on);
-/* measurement hook of the persistent token kernel: `buf` = device memory for [n_blocks][n_layers * 5 + 1][12] 64-bit s_memrealtime stamps (100 MHz)
- * written by blocks < n_blocks of every following launch (tools/decode_persist_trace.py); NULL = off (default) */
-void vila_decode_persist_trace(void* buf, int n_blocks);
 /* tuning hook: output rows per tile of the 256-wide kernel: 0 = automatic (192 when it saves tile-times), 192, 256 */
 void vila_gemm_force_bm(int bm);
 /* tuning / test hook: 0 = automatic tile choice, 1 = 128x128, 2 = 128x64, 3 = 256x128, 4 = 256x256 LDS-DMA, 5 = split-K if possible,

@@ -31,12 +31,6 @@ except Exception as e:
     print("bench parse failed", e)
 P
 : > "$O/val_other_modes.jsonl"
-# the persistent decode layers kernel (opt-in) beside the default per-kernel step, same box
-for m in 0 1 0 1; do
-  VILA_DECODE_PERSIST=$m timeout 300 python bench.py --no-sft --no-sustain --no-cpu-baseline 2>>"$O/val_persist.err" | tail -1 | python -c "
-import sys, json
-d = json.loads(sys.stdin.read()); print('VILA_DECODE_PERSIST=$m: value', d['value'], 'tok/s, ms/step', d['ms_per_step'], '|', d.get('config', {}).get('decode'))" | tee -a "$O/val_persist_ab.log"
-done
 for args in "--w4" "--w8-vit" "--dynamic-s2" "--mode video" "--mode video --tsp" "--prompt-tokens 32"; do
   timeout 400 python bench.py $args --full --no-sft --no-sustain --no-cpu-baseline 2>>"$O/val_other_modes.err" | tail -1 >> "$O/val_other_modes.jsonl"
 done

@@ -5,7 +5,6 @@
 #include "../../include/vila_hip.h"
 #include "../../include/vila_hip_tuning.h"
 #include "kernels.h"
-#include "decode_persist.h"
 #include "train.h"
 #include "w4.h"
 
@@ -513,16 +512,9 @@ extern "C" int vila_llm_prefill_w4(const VilaLlmWeights* w, const VilaLlmLayerW4
 static inline int dec_splits(int max_ctx) { return cdiv(max_ctx, 64); }
 // kernel launches of one vila_llm_decode_step: prologue + per layer {qkv, attention (1 launch up to 2048 cached positions, else
 // split-KV + merge), o_proj, gate/up, down} + lm_head + argmax x2 + advance
-static int decode_persist_mode();
-static bool decode_persist_ok(const VilaLlmShape& sh, int max_ctx) {
-    return decode_persist_mode() != 0 && decode_persist_supported(sh.hidden, sh.inter, sh.q_heads, sh.kv_heads, sh.head_dim, sh.n_layers, max_ctx, sh.vocab);
-}
 extern "C" int vila_llm_decode_launches(const VilaLlmShape* s, int max_ctx) {
-    if (decode_persist_ok(*s, max_ctx)) return 6;                 // prologue, the persistent layers kernel, lm_head, argmax x2, advance
     return 1 + s->n_layers * (max_ctx <= 2048 ? 5 : 6) + 4;      // a sampled step: + 1 (three selection launches instead of two argmax stages)
 }
-// first in the arena: word 0 = the error flag (vila_llm_decode_chain_error), then the persistent kernel's barrier words (DpArgs::sync)
-static const size_t DEC_SYNC_WORDS = 64 + (size_t)DP_SYNC_COUNT * DP_SYNC_STRIDE;
 extern "C" size_t vila_llm_decode_workspace_bytes(const VilaLlmShape* s, int max_ctx) {
     const size_t H = s->hidden, F = s->inter, QS = (size_t)s->q_heads * s->head_dim;
     const size_t ns = dec_splits(max_ctx);
@@ -532,7 +524,6 @@ extern "C" size_t vila_llm_decode_workspace_bytes(const VilaLlmShape* s, int max
     b += 2 * align_up(256 * 4, 256) + align_up((size_t)s->head_dim * 4, 256);
     b += align_up(QS * 2, 256);
     b += align_up(sample_workspace_bytes(), 256);
-    b += align_up(DEC_SYNC_WORDS * 4, 256);
     return b + 4096;
 }
 
@@ -544,17 +535,6 @@ extern "C" void vila_decode_force_attn(int mode) { g_decode_attn = mode; }
 static int decode_attn_mode() {
     if (g_decode_attn < 0) { const char* e = getenv("VILA_DECODE_ATTN"); g_decode_attn = (e && e[0] >= '0' && e[0] <= '2') ? e[0] - '0' : 2; }
     return g_decode_attn;
-}
-// The 28 layers of a token as ONE persistent launch (decode_persist.hip): VILA_DECODE_PERSIST=1 / vila_decode_force_persist(1).  OFF by default:
-// bit-identical logits, and measured AT PARITY with the per-kernel step (336.7 vs 341.9 tok/s, profiles/r06_decode_persist_ab.log) — both spend
-// ~7 us per all-to-all edge around phases that stream at 7.1-7.3 TB/s (profiles/r06_persist_trace.txt has the per-phase anatomy).
-static int g_decode_persist = -1;
-extern "C" void vila_decode_force_persist(int on) { g_decode_persist = on ? 1 : 0; }
-// measurement hook: device buffer [n_blocks][n_layers * 5 + 1][12] of s_memrealtime stamps written by the next persistent launches (null: off)
-extern "C" void vila_decode_persist_trace(void* buf, int n_blocks) { decode_persist_set_trace((unsigned long long*)buf, n_blocks); }
-static int decode_persist_mode() {
-    if (g_decode_persist < 0) { const char* e = getenv("VILA_DECODE_PERSIST"); g_decode_persist = (e && e[0] == '1') ? 1 : 0; }
-    return g_decode_persist;
 }
 static int decode_step_impl(const VilaLlmWeights* w, const VilaLlmLayerW4* ql, const VilaKvCache* cache, const VilaDecodeState* st,
                             void* workspace, size_t workspace_bytes, const VilaSampling* sp, vila_stream_t stream);
@@ -587,16 +567,8 @@ extern "C" int vila_sample_f32(const float* logits, int n, const VilaSampling* s
     VILA_REQUIRE(sp != nullptr && logits != nullptr && out != nullptr && workspace != nullptr, "sample: NULL argument");
     return launch_sample(logits, n, sp->temperature, sp->top_k, sp->top_p, sp->seed, sp->seed_dev, counter, out, workspace, dist_out, S(stream));
 }
-// word 0 of the decode workspace: 1 if a bounded grid-barrier wait of the persistent kernel gave up since the last call of this function
-// (then results are invalid)
-extern "C" int vila_llm_decode_chain_error(void* workspace, vila_stream_t stream) {
-    hipStream_t s = S(stream);
-    uint32_t h = 0;
-    VILA_HIP(hipMemcpyAsync(&h, workspace, 4, hipMemcpyDeviceToHost, s));
-    VILA_HIP(hipStreamSynchronize(s));
-    if (h != 0) VILA_HIP(hipMemsetAsync(workspace, 0, 4, s));
-    return (int)h;
-}
+// no decode step sets an error any more: always 0, kept so that existing bindings still link (vila_hip.h)
+extern "C" int vila_llm_decode_chain_error(void*, vila_stream_t) { return 0; }
 
 // The batch-1 step: ql == nullptr runs the bf16 projections, otherwise the int4 layers' W4A16 GEMVs (the lm_head stays bf16 either way, as
 // AWQ / TinyChat keep it fp16).  Only the four projection launches of a layer differ between the two.
@@ -611,7 +583,6 @@ static int decode_step_impl(const VilaLlmWeights* w, const VilaLlmLayerW4* ql, c
     const int H = sh.hidden, F = sh.inter, hd = sh.head_dim, QS = sh.q_heads * hd, KS = sh.kv_heads * hd;
     const int ns = dec_splits(cache->max_ctx);
     Arena a(workspace, workspace_bytes);
-    uint32_t* sync = a.take<uint32_t>(DEC_SYNC_WORDS);          // [0] error word, [64..] the persistent kernel's barrier words
     bf16_t* x = a.take<bf16_t>(H);
     bf16_t* x2 = a.take<bf16_t>(H);
     bf16_t* q = a.take<bf16_t>(QS);
@@ -626,68 +597,48 @@ static int decode_step_impl(const VilaLlmWeights* w, const VilaLlmLayerW4* ql, c
     VILA_REQUIRE(a.ok(), "%s: workspace arena overflow", fn);
     const size_t per_layer = (size_t)cache->n_slots * sh.kv_heads * cache->max_ctx * hd;
 
-    if (!w4 && decode_persist_ok(sh, cache->max_ctx) && cache->n_slots >= 1) {
-        // ---- the persistent token: prologue (embedding row, RoPE row, barrier words) + ONE launch for 28 layers and the head ----
-        DpArgs d{};
-        for (int l = 0; l < sh.n_layers; ++l) {
-            const VilaLlmLayer& L = w->layers[l];
+    // per-head blocks over 256-key slices whose partials meet in the o_proj GEMV's prologue (§4.3; the W4 GEMV's merge holds up to 7 x 16 heads)
+    const bool split256 = decode_attn_mode() >= 1 && cache->max_ctx <= 2048 && hd == 128 && (!w4 || QS <= 7 * 16 * 128);
+    VILA_TRY(launch_decode_prologue(B(w->embed), st->token, x, H, sh.vocab, st->pos, rope_cs, hd, sh.rope_theta, s));
+    bf16_t* cur = x; bf16_t* nxt = x2;
+    for (int l = 0; l < sh.n_layers; ++l) {
+        const VilaLlmLayer& L = w->layers[l];
+        const VilaLlmLayerW4 Q = w4 ? ql[l] : VilaLlmLayerW4{};
+        bf16_t* kc = B(cache->k) + l * per_layer; bf16_t* vc = B(cache->v) + l * per_layer;
+        if (w4) {
+            GemvW4Args qa{};
+            qa.x = cur; qa.norm_w = B(L.ln1_w); qa.eps = sh.rms_eps; qa.Wq = (const uint32_t*)Q.qkv_q; qa.Wsz = (const uint32_t*)Q.qkv_sz;
+            qa.bias = B(L.bq); qa.K = H; qa.N = QS + 2 * KS; qa.mode = 3; qa.q_out = q; qa.kcache = kc; qa.vcache = vc; qa.pos_ptr = st->pos;
+            qa.rope_cs = rope_cs; qa.nq = sh.q_heads; qa.nkv = sh.kv_heads; qa.hd = hd; qa.max_ctx = cache->max_ctx;
+            VILA_TRY(launch_gemv_w4(qa, s));
+        } else {
             const bool fused = (B(L.wk) == B(L.wq) + (size_t)QS * H) && (B(L.wv) == B(L.wk) + (size_t)KS * H) &&
                                (B(L.bk) == B(L.bq) + QS) && (B(L.bv) == B(L.bk) + KS);
             VILA_REQUIRE(fused, "llm_decode: q/k/v projection weights and biases must be views of one fused [q+2kv, hidden] buffer");
-            d.layer[l] = DpLayer{B(L.ln1_w), B(L.wq), B(L.bq), B(L.wo), B(L.ln2_w), B(L.w_gate), B(L.w_up), B(L.w_down)};
+            QkvDecodeArgs qa{};
+            qa.x = cur; qa.norm_w = B(L.ln1_w); qa.eps = sh.rms_eps; qa.Wqkv = B(L.wq); qa.bqkv = B(L.bq); qa.q_out = q;
+            qa.kcache = kc; qa.vcache = vc; qa.pos_ptr = st->pos; qa.K = H; qa.nq = sh.q_heads; qa.nkv = sh.kv_heads; qa.hd = hd;
+            qa.max_ctx = cache->max_ctx; qa.rope_cs = rope_cs;
+            VILA_TRY(launch_qkv_decode(qa, s));
         }
-        d.norm_w = B(w->norm_w); d.lm_head = B(w->lm_head); d.logits = st->logits;
-        d.kcache = B(cache->k); d.vcache = B(cache->v); d.kv_layer_stride = (int64_t)per_layer;
-        d.pos_ptr = st->pos; d.rope_cs = rope_cs; d.x0 = x; d.x1 = x2; d.q = q; d.act = act; d.part_o = part_o; d.part_ml = part_ml;
-        d.sync = sync;
-        d.n_layers = sh.n_layers; d.H = H; d.F = F; d.nq = sh.q_heads; d.nkv = sh.kv_heads; d.hd = hd; d.vocab = sh.vocab; d.max_ctx = cache->max_ctx;
-        d.eps = sh.rms_eps; d.scale = 1.0f / sqrtf((float)hd);
-        VILA_TRY(launch_decode_prologue(B(w->embed), st->token, x, H, sh.vocab, st->pos, rope_cs, hd, sh.rope_theta, s, sync + 64));
-        VILA_TRY(launch_decode_persist(d, s));
-    } else {
-        // per-head blocks over 256-key slices whose partials meet in the o_proj GEMV's prologue (§4.3; the W4 GEMV's merge holds up to 7 x 16 heads)
-        const bool split256 = decode_attn_mode() >= 1 && cache->max_ctx <= 2048 && hd == 128 && (!w4 || QS <= 7 * 16 * 128);
-        VILA_TRY(launch_decode_prologue(B(w->embed), st->token, x, H, sh.vocab, st->pos, rope_cs, hd, sh.rope_theta, s));
-        bf16_t* cur = x; bf16_t* nxt = x2;
-        for (int l = 0; l < sh.n_layers; ++l) {
-            const VilaLlmLayer& L = w->layers[l];
-            const VilaLlmLayerW4 Q = w4 ? ql[l] : VilaLlmLayerW4{};
-            bf16_t* kc = B(cache->k) + l * per_layer; bf16_t* vc = B(cache->v) + l * per_layer;
-            if (w4) {
-                GemvW4Args qa{};
-                qa.x = cur; qa.norm_w = B(L.ln1_w); qa.eps = sh.rms_eps; qa.Wq = (const uint32_t*)Q.qkv_q; qa.Wsz = (const uint32_t*)Q.qkv_sz;
-                qa.bias = B(L.bq); qa.K = H; qa.N = QS + 2 * KS; qa.mode = 3; qa.q_out = q; qa.kcache = kc; qa.vcache = vc; qa.pos_ptr = st->pos;
-                qa.rope_cs = rope_cs; qa.nq = sh.q_heads; qa.nkv = sh.kv_heads; qa.hd = hd; qa.max_ctx = cache->max_ctx;
-                VILA_TRY(launch_gemv_w4(qa, s));
-            } else {
-                const bool fused = (B(L.wk) == B(L.wq) + (size_t)QS * H) && (B(L.wv) == B(L.wk) + (size_t)KS * H) &&
-                                   (B(L.bk) == B(L.bq) + QS) && (B(L.bv) == B(L.bk) + KS);
-                VILA_REQUIRE(fused, "llm_decode: q/k/v projection weights and biases must be views of one fused [q+2kv, hidden] buffer");
-                QkvDecodeArgs qa{};
-                qa.x = cur; qa.norm_w = B(L.ln1_w); qa.eps = sh.rms_eps; qa.Wqkv = B(L.wq); qa.bqkv = B(L.bq); qa.q_out = q;
-                qa.kcache = kc; qa.vcache = vc; qa.pos_ptr = st->pos; qa.K = H; qa.nq = sh.q_heads; qa.nkv = sh.kv_heads; qa.hd = hd;
-                qa.max_ctx = cache->max_ctx; qa.rope_cs = rope_cs;
-                VILA_TRY(launch_qkv_decode(qa, s));
-            }
-            AttnDecodeArgs ad{};
-            ad.q = q; ad.kcache = kc; ad.vcache = vc; ad.o = ao; ad.part_o = part_o; ad.part_ml = part_ml; ad.pos_ptr = st->pos;
-            ad.nq = sh.q_heads; ad.nkv = sh.kv_heads; ad.hd = hd; ad.max_ctx = cache->max_ctx; ad.n_splits = ns; ad.scale = 1.0f / sqrtf((float)hd);
-            ad.split256 = split256 ? 1 : 0;
-            VILA_TRY(launch_attn_decode(ad, s));
-            GemvArgs o{};
-            o.x = ao; o.W = B(L.wo); o.residual = cur; o.y = nxt; o.N = H; o.K = QS; o.mode = 0;
-            if (split256) { o.mode = 2; o.part_o = part_o; o.part_ml = part_ml; o.pos_ptr = st->pos; o.n_splits = cdiv(cache->max_ctx, 256); o.split_keys = 256; o.grid_cap = decode_attn_mode() == 2 ? 512 : 256; }
-            VILA_TRY(proj_gemv(o, w4, Q.o_q, Q.o_sz, s));
-            GemvArgs gu{};
-            gu.x = nxt; gu.norm_w = B(L.ln2_w); gu.eps = sh.rms_eps; gu.W = B(L.w_gate); gu.W2 = B(L.w_up); gu.y = act; gu.N = F; gu.K = H; gu.mode = 1;
-            VILA_TRY(proj_gemv(gu, w4, Q.gateup_q, Q.gateup_sz, s));
-            GemvArgs dn{};
-            dn.x = act; dn.W = B(L.w_down); dn.residual = nxt; dn.y = cur; dn.N = H; dn.K = F; dn.mode = 0;
-            VILA_TRY(proj_gemv(dn, w4, Q.down_q, Q.down_sz, s));
-        }
+        AttnDecodeArgs ad{};
+        ad.q = q; ad.kcache = kc; ad.vcache = vc; ad.o = ao; ad.part_o = part_o; ad.part_ml = part_ml; ad.pos_ptr = st->pos;
+        ad.nq = sh.q_heads; ad.nkv = sh.kv_heads; ad.hd = hd; ad.max_ctx = cache->max_ctx; ad.n_splits = ns; ad.scale = 1.0f / sqrtf((float)hd);
+        ad.split256 = split256 ? 1 : 0;
+        VILA_TRY(launch_attn_decode(ad, s));
+        GemvArgs o{};
+        o.x = ao; o.W = B(L.wo); o.residual = cur; o.y = nxt; o.N = H; o.K = QS; o.mode = 0;
+        if (split256) { o.mode = 2; o.part_o = part_o; o.part_ml = part_ml; o.pos_ptr = st->pos; o.n_splits = cdiv(cache->max_ctx, 256); o.split_keys = 256; o.grid_cap = decode_attn_mode() == 2 ? 512 : 256; }
+        VILA_TRY(proj_gemv(o, w4, Q.o_q, Q.o_sz, s));
+        GemvArgs gu{};
+        gu.x = nxt; gu.norm_w = B(L.ln2_w); gu.eps = sh.rms_eps; gu.W = B(L.w_gate); gu.W2 = B(L.w_up); gu.y = act; gu.N = F; gu.K = H; gu.mode = 1;
+        VILA_TRY(proj_gemv(gu, w4, Q.gateup_q, Q.gateup_sz, s));
+        GemvArgs dn{};
+        dn.x = act; dn.W = B(L.w_down); dn.residual = nxt; dn.y = cur; dn.N = H; dn.K = F; dn.mode = 0;
+        VILA_TRY(proj_gemv(dn, w4, Q.down_q, Q.down_sz, s));
     }
-    // the head: final RMSNorm + lm_head rows -> fp32 logits (152 064 x 3584: 1.09 GB, 7 TB/s in gemv_kernel<0,7>).  Both paths leave the last
-    // layer's residual stream in `x` (the persistent kernel swaps its buffers an even number of times per layer).
+    // the head: final RMSNorm + lm_head rows -> fp32 logits (152 064 x 3584: 1.09 GB, 7 TB/s in gemv_kernel<0,7>).  The last layer's residual
+    // stream is in `x`: o_proj writes x2 and down_proj writes x back, so every layer ends where it began.
     GemvArgs lm{};
     lm.x = x; lm.norm_w = B(w->norm_w); lm.eps = sh.rms_eps; lm.W = B(w->lm_head); lm.y_f32 = st->logits; lm.N = sh.vocab; lm.K = H; lm.mode = 0;
     VILA_TRY(launch_gemv(lm, s));

@@ -5,7 +5,6 @@
 // (bias, RoPE, KV-cache write, SiLU*up, residual add) are fused so a decoder layer is 6 launches.
 #include "kernels.h"
 #include "gemv_common.h"
-#include "decode_persist.h"
 
 #define DEC_KS 64      // keys per split of the decode attention
 #define DEC_MAXG 8     // max query heads per kv head
@@ -199,7 +198,7 @@ __global__ __launch_bounds__(256) void gemv_kernel(GemvArgs p, int n_groups, int
 
 // Grid sizing for the HBM-bound GEMVs: a multiple of the 256 CUs (the dispatcher deals blocks round-robin, so 448 blocks
 // would leave 64 CUs with half the work of the others) and at most GEMV_BPC blocks per CU (4 = 16 waves = everything resident at once);
-// waves then walk the row groups with a grid stride.
+// the blocks of a CU then deal that CU's row groups (CuMap, gemv_common.h).
 #define GEMV_BPC 4
 static int gemv_cu_count() {
     static thread_local int per_dev[16] = {0};
@@ -212,27 +211,14 @@ static int gemv_cu_count() {
     }
     return n;
 }
-// VILA_GEMV_CU_MAP=0: the grid-stride walk of rounds 1-5 (A/B switch); VILA_GEMV_SKEW=n: row groups per CU moved from odd to even XCDs (gate/up)
-static int gemv_cu_map_on() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("VILA_GEMV_CU_MAP"); v = (e && e[0] == '0') ? 0 : 1; }
-    return v;
-}
-static int gemv_skew() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("VILA_GEMV_SKEW"); v = (e && e[0] >= '0' && e[0] <= '9') ? atoi(e) : 1; }
-    return v;
-}
 // grid of an HBM-bound GEMV: (CUs) x (blocks per CU, 1..4) so that blocks b, b + CUs, ... share a CU and deal that CU's row groups among their
 // waves (*ncu_out = CUs); small problems (fewer groups than one block per CU would hold) keep one block per 4 groups and the plain walk (*ncu_out = 0)
 static inline int balanced_grid(int n_groups, int* ncu_out) {
     const int ncu = gemv_cu_count();
     int want = cdiv(n_groups, 4);
-    if (want <= ncu || !gemv_cu_map_on()) {
+    if (want <= ncu) {
         if (ncu_out) *ncu_out = 0;
-        const int cap = ncu * GEMV_BPC;
-        if (want > cap) want = cap;
-        return want <= ncu ? want : cdiv(want, ncu) * ncu;
+        return want;
     }
     int per = cdiv(want, ncu); if (per > GEMV_BPC) per = GEMV_BPC;
     if (ncu_out) *ncu_out = ncu;
@@ -249,7 +235,8 @@ int launch_gemv(const GemvArgs& a, hipStream_t s) {
     const bool short_k = a.K <= 3584;
     if (a.mode == 1) {
         VILA_REQUIRE(a.W2 != nullptr && a.y != nullptr && (uintptr_t)a.x % 16 == 0, "gemv: gate/up mode needs W2, bf16 y, aligned x");
-        hipLaunchKernelGGL((gemv_kernel<1, 4>), dim3(grid), dim3(256), lds, s, a, n_groups, ncu, gemv_skew());
+        // skew 1: one gate/up group per CU moves from the odd XCDs to the even ones (profiles/r06_gemv_cu_map_ab.log: 337.8 -> 339.3 tok/s)
+        hipLaunchKernelGGL((gemv_kernel<1, 4>), dim3(grid), dim3(256), lds, s, a, n_groups, ncu, 1);
     } else if (a.mode == 2) {
         VILA_REQUIRE(a.part_o != nullptr && a.part_ml != nullptr && a.pos_ptr != nullptr && a.K % 128 == 0, "gemv: attention-merge mode needs partials");
         lds += (size_t)a.n_splits * (a.K / 128) * 4;
@@ -640,11 +627,7 @@ int launch_attn_decode(const AttnDecodeArgs& a, hipStream_t s) {
 // per-token prologue: x = embed[token]; rope table for the token's position: cs[0:hd/2] = cos, cs[hd/2:hd] = sin,
 // both rounded to bf16 (HF casts cos/sin to the activation dtype before use)
 __global__ void decode_prologue_kernel(const bf16_t* __restrict__ table, const int64_t* __restrict__ tok, bf16_t* __restrict__ out, int H,
-                                       int64_t vocab, const int32_t* __restrict__ pos, float* __restrict__ rope_cs, int hd, float theta,
-                                       uint32_t* __restrict__ dp_sync) {
-    // the persistent token's grid-barrier words start at zero (decode_persist.hip is launched behind this kernel)
-    if (dp_sync != nullptr)
-        for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < DP_SYNC_COUNT; i += gridDim.x * blockDim.x) dp_sync[(size_t)i * DP_SYNC_STRIDE] = 0u;
+                                       int64_t vocab, const int32_t* __restrict__ pos, float* __restrict__ rope_cs, int hd, float theta) {
     int64_t id = *tok;
     id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
     for (int c = blockIdx.x * blockDim.x + threadIdx.x; c < (H >> 3); c += gridDim.x * blockDim.x)
@@ -658,10 +641,9 @@ __global__ void decode_prologue_kernel(const bf16_t* __restrict__ table, const i
     }
 }
 int launch_decode_prologue(const bf16_t* table, const int64_t* tok, bf16_t* out, int H, int64_t vocab, const int32_t* pos, float* rope_cs,
-                           int hd, float theta, hipStream_t s, uint32_t* dp_sync) {
+                           int hd, float theta, hipStream_t s) {
     VILA_REQUIRE(hd / 2 <= 256, "decode_prologue: head_dim too large");
-    hipLaunchKernelGGL(decode_prologue_kernel, dim3(cdiv(H / 8, 256)), dim3(256), 0, s, table, tok, out, H, vocab, pos, rope_cs, hd, theta,
-                       dp_sync);
+    hipLaunchKernelGGL(decode_prologue_kernel, dim3(cdiv(H / 8, 256)), dim3(256), 0, s, table, tok, out, H, vocab, pos, rope_cs, hd, theta);
     VILA_LAUNCH_CHECK();
     return 0;
 }

@@ -143,7 +143,6 @@ size_t bdecode_workspace_bytes(int H, int F, int QS, int hd, int n);
 int bdecode_step(const BDecodeArgs& m, const BLayer* layers, bf16_t* kcache, bf16_t* vcache, int max_ctx, int n_slots, int n, int32_t* pos, int64_t* token,
                  int64_t* out_ids, int32_t* n_out, int max_out, float* logits, void* workspace, size_t workspace_bytes, hipStream_t s,
                  const BLayerW4* qlayers = nullptr);
-// dp_sync != nullptr: the persistent token's barrier words (decode_persist.h DpArgs::sync + 64) are zeroed as well
 int launch_decode_prologue(const bf16_t* table, const int64_t* tok, bf16_t* out, int H, int64_t vocab, const int32_t* pos, float* rope_cs,
-                           int hd, float theta, hipStream_t s, uint32_t* dp_sync = nullptr);
+                           int hd, float theta, hipStream_t s);
 int launch_decode_advance(int32_t* pos, const int64_t* tok, int64_t* out_ids, int32_t* n_out, int max_out, hipStream_t s);
