@@ -231,7 +231,8 @@ def test_dma_backward_consumes_every_forms_lse(lib):
 
 @pytest.mark.parametrize("impl", [1, 2], ids=["v1", "dma"])
 def test_backward_parts_split_is_bit_identical(lib, impl):
-    """SFTTrainer._attn_bwd's two-stream split: parts 1 (delta), then 4 (dK / dV) and 2 (dQ) with the delta passed back in == parts 7."""
+    """The separately launchable parts of the backward (a caller may run dQ and dK / dV on two streams): parts 1 (delta), then 4 (dK / dV)
+    and 2 (dQ) with the delta passed back in == parts 7."""
     from vila_amd import ops
     Hq, Hkv, D = 28, 4, 128
     cu = torch.tensor([0, 300, 769, 1000], dtype=torch.int32, device="cuda")

@@ -355,6 +355,81 @@ def test_reference_collated_batch_is_what_the_step_plans_on():
     assert n_targets == want > 0
 
 
+def _plan_case(case):
+    """-> (cfg, video tokens of the encoder, model_max_length, ids, labels, mask, n image tiles, block_sizes, frames per video)."""
+    import numpy as np
+    if case == "collated":                         # the reference collator's batch: dynamic_s2, two images and one video (frames as images)
+        fx = np.load(os.path.join(os.path.dirname(__file__), "golden", "collate_batch_ref.npz"))
+        cfg = configs.tiny_s2()
+        ids, labels, mask = (torch.from_numpy(fx[k]) for k in ("input_ids", "labels", "attention_mask"))
+        blocks = [None if b[0] < 0 else (int(b[0]), int(b[1])) for b in fx["block_sizes"]]
+        vtok = (((1, 1, 1),), [], [cfg.newline_token_id], [])
+        return cfg, vtok, None, ids, labels, mask, len(fx["image_pool_index"]), blocks, [int(n) for n in fx["video_frames"]]
+    cfg = configs.tiny("mlp_downsample")           # 4 x 4 patches, 2 x 2 down-sampled: 4 tokens per tile
+    I, V, pad = cfg.image_token_id, cfg.video_token_id, 0
+    if case == "tsp_video":                        # one image and one 4-frame video, frame by frame and pooled (2, 2, 2), behind each other
+        rows = [[1, 20, I, 21, 22, 23], [1, V, 30, 31]]
+        vtok = (((1, 1, 1), (2, 2, 2)), [5], [cfg.newline_token_id], [7])
+        n_tiles, frames, max_len = 1, [4], None
+    else:                                          # "truncated": 15 rows after expansion, cut to 10 = inside the second image's block
+        rows = [[1, 20, I, 21, 22, I, 23], [1, 40, I, 41]]
+        vtok = (((1, 1, 1),), [], [cfg.newline_token_id], [])
+        n_tiles, frames, max_len = 3, [], 10
+    L = max(len(r) for r in rows)
+    ids = torch.tensor([r + [pad] * (L - len(r)) for r in rows], dtype=torch.int64)
+    mask = torch.tensor([[1] * len(r) + [0] * (L - len(r)) for r in rows], dtype=torch.bool)
+    labels = torch.where(mask, ids, torch.full_like(ids, -100))
+    labels[:, :2] = -100                           # the prompt
+    if case == "truncated":
+        labels[0, 5:] = -100                       # `count_targets` counts before the cut: the rows the cut drops carry no target here
+    return cfg, vtok, max_len, ids, labels, mask, n_tiles, None, frames
+
+
+@pytest.mark.parametrize("case", ["collated", "tsp_video", "truncated"])
+def test_plan_batch_row_maps_partition_the_packed_rows(case):
+    """`SFTTrainer._plan_batch`, the host plan both step drivers run on: what follows from its definition, on the reference collator's batch
+    (images + a video under dynamic_s2), on a video that a TSP encoder also pools, and on a batch whose truncation cuts media rows."""
+    from types import SimpleNamespace
+    from vila_amd.train import SFTTrainer, count_targets
+    cfg, vtok, max_len, ids, labels, mask, n_tiles, blocks, frames = _plan_case(case)
+    tr = SFTTrainer.__new__(SFTTrainer)            # the plan reads the config, the tokenizer's limit and the video encoder's tokens only
+    tr.cfg, tr.model, tr._video_tokens = cfg, SimpleNamespace(tokenizer=SimpleNamespace(model_max_length=max_len)), lambda: vtok
+    images = [torch.zeros(1)] * n_tiles
+    videos = [torch.zeros(nf, 1) for nf in frames]
+    for n_given in (None, 1234):
+        p = tr._plan_batch(ids, images, labels, mask, n_given, blocks, videos)
+        assert p.n_items == (p.n_valid if n_given is None else n_given)
+    T, V = p.T, cfg.llm.vocab_size
+    assert p.n_img == len(p.images) == n_tiles + sum(frames)
+    assert p.n_prow == p.n_pin * cfg.tokens_per_tile and p.n_buf >= p.n_prow and (p.n_buf > p.n_prow) == bool(p.pools)
+    for name in ("txt_src", "txt_dst", "feat_src", "feat_dst", "nl_src", "nl_dst", "positions", "cu_seqlens"):
+        t = getattr(p, name)
+        assert t.dtype == torch.int32 and t.device.type == "cpu" and t.is_contiguous(), name
+    # the three destination maps are disjoint and together every packed row
+    dst = torch.cat([p.txt_dst, p.feat_dst, p.nl_dst]).long()
+    assert dst.numel() == T and torch.equal(torch.sort(dst).values, torch.arange(T))
+    assert p.txt_src.numel() == p.txt_dst.numel() and p.feat_src.numel() == p.feat_dst.numel() and p.nl_src.numel() == p.nl_dst.numel()
+    assert p.feat_src.numel() > 0 and bool(((p.feat_src >= 0) & (p.feat_src < p.n_buf)).all())
+    for src in (p.txt_src, p.nl_src):
+        assert bool(((src >= 0) & (src < V)).all())
+    assert not bool(((p.txt_src == cfg.image_token_id) | (p.txt_src == cfg.video_token_id)).any())
+    # positions restart at every sequence boundary and count up by one
+    cu = p.cu_seqlens.long()
+    assert int(cu[0]) == 0 and int(cu[-1]) == T and cu.numel() == ids.shape[0] + 1
+    for a, b in zip(cu[:-1].tolist(), cu[1:].tolist()):
+        assert torch.equal(p.positions[a:b].long(), torch.arange(b - a))
+    assert p.max_seqlen == int((cu[1:] - cu[:-1]).max())
+    # targets: as many as the step counts for the loss; a row and the row its target comes from lie in the same packed sequence
+    assert p.n_valid == p.target_rows.numel() == p.targets.numel() == count_targets(ids, labels, mask, (cfg.image_token_id, cfg.video_token_id)) > 0
+    seq_of = lambda r: torch.searchsorted(cu, r, right=True)
+    assert torch.equal(seq_of(p.target_rows), seq_of(p.target_rows + 1)) and int(p.target_rows.max()) + 1 < T
+    assert bool(((p.targets >= 0) & (p.targets < V)).all())
+    if case == "tsp_video":                        # 4 frames of 4 rows, then (4 / 2) pooled frames of one row behind the projector's rows
+        assert p.n_prow == 5 * 4 and p.n_buf == p.n_prow + 2 and int(p.feat_src.max()) == p.n_buf - 1
+    if case == "truncated":                        # sample 0 keeps 10 of its 15 rows: one row of its second image; sample 1 all 8
+        assert cu.tolist() == [0, 10, 18] and p.feat_src.numel() == 4 + 1 + 4 < p.n_buf
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # gradient accumulation: one update from several micro-batches (SFTTrainer.step_accumulated)
 # ---------------------------------------------------------------------------------------------------------------------

@@ -18,6 +18,7 @@ Backward is explicit (no autograd graph): every op is a C-ABI call on the curren
 """
 from __future__ import annotations
 
+import os
 from types import SimpleNamespace
 from typing import Dict, List, Optional, Tuple
 
@@ -271,34 +272,34 @@ def _cm_ok(T: int, N: int, K: int) -> bool:
 
 
 def linear_bwd(x2: torch.Tensor, w: torch.Tensor, dy2: torch.Tensor, gw: torch.Tensor, gb: Optional[torch.Tensor] = None,
-               need_dx: bool = True, dx_residual: Optional[torch.Tensor] = None, dy_t: Optional[torch.Tensor] = None,
+               need_dx: bool = True, dx_residual: Optional[torch.Tensor] = None,
                cm: bool = False, side: Optional["torch.cuda.Stream"] = None, ws: Optional[torch.Tensor] = None,
                ws_side: Optional[torch.Tensor] = None):
     """x2 [M,K], w [N,K], dy2 [M,N]  ->  writes gw [N,K] (and gb [N]); returns dx [M,K] (+ dx_residual).
-    cm: read W, dY and X as they lie (vila_gemm_bf16_t: contraction-major operands through the LDS transpose reads) instead of making
-    transposed copies.  side: stream for the weight-gradient GEMM — dgrad and wgrad only share inputs, so the two run concurrently
-    and the partial last round of one kernel's 256x256 tiles is filled by the other's."""
+    cm: read W, dY and X as they lie (vila_gemm_bf16_t: contraction-major operands through the LDS transpose reads) where `_cm_ok` takes
+    the shape, instead of making transposed copies.  side: stream for the weight-gradient GEMM — dgrad and wgrad only share inputs, so
+    the two run concurrently and the partial last round of one kernel's 256x256 tiles is filled by the other's.  Split-K slabs are per
+    stream: `ws` is the compute stream's, `ws_side` the side stream's own."""
     w2 = w.view(w.shape[0], -1)
     gw2 = gw.view(w.shape[0], -1) if gw.dim() != 2 else gw
     M, K = x2.shape
     N = w2.shape[0]
     if cm and _cm_ok(M, N, K):
-        def wgrad():
-            ops.gemm_t(dy2, x2, a_cm=True, b_cm=True, out=gw2, ws=ws_side if (side is not None and ws_side is not None) else ws)   # dW = dY^T X
+        def wgrad(slab):
+            ops.gemm_t(dy2, x2, a_cm=True, b_cm=True, out=gw2, ws=slab)             # dW = dY^T X
             if gb is not None:
                 ops.colsum(dy2, gb)
         if side is not None:
             side.wait_event(torch.cuda.current_stream().record_event())             # dY and X are final on the compute stream
             with torch.cuda.stream(side):
-                wgrad()
+                wgrad(ws_side)
             dy2.record_stream(side); x2.record_stream(side)
         else:
-            wgrad()
+            wgrad(ws)
         if not need_dx:
             return None
-        # split-K slabs are per stream: with a side stream the dgrad may slice K only when the wgrad has a workspace of its own
-        return ops.gemm_t(dy2, w2, b_cm=True, residual=dx_residual, ws=ws if (side is None or ws_side is not None) else None)   # dX = dY W (+ residual)
-    dyt = dy_t if dy_t is not None else ops.transpose(dy2)           # [N, Mp]
+        return ops.gemm_t(dy2, w2, b_cm=True, residual=dx_residual, ws=ws)          # dX = dY W (+ residual)
+    dyt = ops.transpose(dy2)                                         # [N, Mp]
     xt = ops.transpose(x2)                                           # [K, Mp]
     ops.gemm(dyt, xt, out=gw2)                                       # dW = dY^T X
     if gb is not None:
@@ -329,42 +330,19 @@ class SFTTrainer:
         # side: weight-gradient GEMMs of the decoder layers (concurrent with the dgrad chain on the compute stream)
         # opt : per-bucket gradient exchange + AdamW, as soon as a layer's gradients are final — the optimizer streams 28 B per
         #       parameter at HBM rate and the exchange runs on xGMI while the matrix cores work on the layers below
-        import os
-        flag = lambda name, default: os.environ.get(name, default) not in ("0", "", "false")
-        self.side = torch.cuda.Stream(device=dev) if (on_gpu and flag("VILA_SFT_SIDE", "1")) else None
-        self.opt = torch.cuda.Stream(device=dev) if (on_gpu and flag("VILA_SFT_OPT_STREAM", "1")) else None
-        # dK / dV on its own stream beside dQ: measured 211.3 / 209.7 -> 210.3 / 209.7 ms, i.e. nothing (the chip already runs ~2 kernels at a
-        # time and the step is throughput-bound): off by default, kept as a switch
-        self.attn_s = torch.cuda.Stream(device=dev) if (on_gpu and flag("VILA_SFT_ATTN_STREAM", "0")) else None
-        self.use_c_abi = flag("VILA_SFT_C_ABI", "0")            # step(): forward+backward as ONE vila_sft_fwd_bwd call (else Python-orchestrated ops)
-        self.lean_adamw = flag("VILA_SFT_LEAN_ADAMW", "1")      # <= 32-VGPR optimizer kernel: co-resident with the GEMM blocks
-        self.cm = flag("VILA_SFT_CM", "1")  # dgrad / wgrad on the tensors as they lie (no transposed copies) where the shapes allow
-        # fp32 slabs for the K-sliced launches (lm_head dgrad, tower shapes, tail tiles behind whole rounds)
+        self.side = torch.cuda.Stream(device=dev) if on_gpu else None
+        self.opt = torch.cuda.Stream(device=dev) if on_gpu else None
+        # step(): forward + backward as ONE vila_sft_fwd_bwd call (else Python-orchestrated ops)
+        self.use_c_abi = os.environ.get("VILA_SFT_C_ABI", "0") not in ("0", "", "false")
+        # fp32 slabs for the K-sliced launches (lm_head dgrad, tower shapes, tail tiles behind whole rounds); the side stream has its own
         self.ws = torch.empty(128 << 20, device=dev, dtype=torch.uint8) if on_gpu else None
-        # the tower / projector GEMMs (M = 1024 per image, N = 1152): contraction-major too, K-sliced where their 256^2 tiles under-fill
-        self.cm_vit = self.cm and flag("VILA_SFT_CM_VIT", "1")
-        self.ws_side = torch.empty(128 << 20, device=dev, dtype=torch.uint8) if (on_gpu and self.side is not None) else None   # the side stream's own slabs
+        self.ws_side = torch.empty(128 << 20, device=dev, dtype=torch.uint8) if on_gpu else None
         self._bucket_step = False          # set per step: apply AdamW bucket by bucket (no global clipping)
         self._touched: List[str] = []      # bucket prefixes whose gradients this step produced, in the order they became final
         # gradient accumulation (`step_accumulated`): the sum of the earlier micro-batches' gradients and what `_ready` does with a bucket —
         # None: a plain step; "hold": not the last micro-batch (no exchange, no update); "add": the last one (bucket += held sum, then as usual)
         self._acc: Optional[torch.Tensor] = None
         self._acc_mode: Optional[str] = None
-
-    def _attn_bwd(self, *a, **kw) -> None:
-        """Flash-attention backward.  dQ and dK / dV share no output and both under-fill the chip (208 blocks at 4 x 769 tokens, 4-13 % of the
-        MFMA rate), so once delta is done dK / dV runs on its own stream beside dQ and the two meet again in front of the QKV dgrad."""
-        if self.attn_s is None:
-            ops.attn_bwd(*a, **kw)
-            return
-        main = torch.cuda.current_stream()
-        delta = ops.attn_bwd(*a, parts=1, **kw)
-        self.attn_s.wait_event(main.record_event())                     # delta, dO and the saved q / k / v are final
-        with torch.cuda.stream(self.attn_s):
-            ops.attn_bwd(*a, parts=4, delta=delta, **kw)
-            done = self.attn_s.record_event()
-        ops.attn_bwd(*a, parts=2, delta=delta, **kw)
-        main.wait_event(done)                                            # (every later use or free of these tensors is ordered behind this)
 
     def _ready(self, prefix: str) -> None:
         """Gradients under `prefix` are final once the compute stream and the wgrad stream reach this point: hand the bucket to the
@@ -412,7 +390,7 @@ class SFTTrainer:
         f.bucket_steps[prefix] = step
         if self.wd == 0.0 or not self.decay_groups:          # every NVILA script trains with --weight_decay 0.: one launch per bucket
             ops.adamw_step(f.master[a:b], f.m[a:b], f.v[a:b], f.grads[a:b], f.params[a:b], self.lr, self.betas[0], self.betas[1],
-                           self.eps, self.wd, step, grad_scale, lean=self.lean_adamw)
+                           self.eps, self.wd, step, grad_scale, lean=True)
             return
         # weight decay > 0: the reference's two parameter groups (biases and LayerNorm weights do not decay) = one launch per run of
         # adjacent tensors with the same flag
@@ -420,7 +398,7 @@ class SFTTrainer:
             self._decay_runs[prefix] = f.decay_runs(prefix)
         for ra, rb, dec in self._decay_runs[prefix]:
             ops.adamw_step(f.master[ra:rb], f.m[ra:rb], f.v[ra:rb], f.grads[ra:rb], f.params[ra:rb], self.lr, self.betas[0], self.betas[1],
-                           self.eps, self.wd if dec else 0.0, step, grad_scale, lean=self.lean_adamw)
+                           self.eps, self.wd if dec else 0.0, step, grad_scale, lean=True)
 
     # ------------------------------------------------------------------ ViT ------------------------------------------------
     def _vit_fwd(self, pixels: torch.Tensor):
@@ -476,7 +454,7 @@ class SFTTrainer:
         P, G = self.flat.param, self.flat.grad
         pre = "vision_tower.vision_tower.vision_model."
         B, N, D, hd, H = saved.B, v.num_patches, v.hidden_size, v.head_dim, v.num_attention_heads
-        kw = dict(cm=self.cm_vit, side=self.side, ws=self.ws, ws_side=self.ws_side) if self.cm_vit else {}
+        kw = dict(cm=True, side=self.side, ws=self.ws, ws_side=self.ws_side)
         for i in reversed(range(v.num_used_layers)):
             l = f"{pre}encoder.layers.{i}."
             s = saved.layers[i]
@@ -488,8 +466,8 @@ class SFTTrainer:
             da = linear_bwd(s.a.view(B * N, D), P(l + "self_attn.out_proj.weight"), dx_mid, G(l + "self_attn.out_proj.weight"), G(l + "self_attn.out_proj.bias"), **kw)
             dqkv = torch.empty_like(s.qkv)
             q3, d3 = s.qkv.view(B * N, 3 * H, hd), dqkv.view(B * N, 3 * H, hd)
-            self._attn_bwd(q3[:, :H], q3[:, H:2 * H], q3[:, 2 * H:], s.a, da.view(B * N, H, hd), s.lse, False,
-                           d3[:, :H], d3[:, H:2 * H], d3[:, 2 * H:], n_seq=B)
+            ops.attn_bwd(q3[:, :H], q3[:, H:2 * H], q3[:, 2 * H:], s.a, da.view(B * N, H, hd), s.lse, False,
+                         d3[:, :H], d3[:, H:2 * H], d3[:, 2 * H:], n_seq=B)
             dh1 = linear_bwd(s.h1, self._fused(l + "self_attn.", "weight"), dqkv, self._fused_grad(l + "self_attn.", "weight"), self._fused_grad(l + "self_attn.", "bias"), **kw)
             dxi = ops.norm_bwd(s.x_in, P(l + "layer_norm1.weight"), dh1, G(l + "layer_norm1.weight"), G(l + "layer_norm1.bias"), v.layer_norm_eps, False)
             dx = ops.add(dx_mid, dxi)
@@ -531,7 +509,7 @@ class SFTTrainer:
         pre = "mm_projector.layers."
         B, T, _ = s.y.shape
         d = dout.reshape(B * T, -1)
-        kw = dict(cm=self.cm_vit, side=self.side, ws=self.ws, ws_side=self.ws_side) if self.cm_vit else {}
+        kw = dict(cm=True, side=self.side, ws=self.ws, ws_side=self.ws_side)
         if self.cfg.mm_projector_type == "mlp_downsample_3x3_fix":
             dh2 = linear_bwd(s.h2, P(pre + "7.weight"), d, G(pre + "7.weight"), G(pre + "7.bias"), **kw)
             dz2 = ops.act_bwd(s.z2, dh2, 2)
@@ -580,7 +558,7 @@ class SFTTrainer:
         for i in reversed(range(c.num_hidden_layers)):
             l = f"llm.model.layers.{i}."
             s = saved.layers[i]
-            kw = dict(cm=self.cm, side=self.side, ws=self.ws, ws_side=self.ws_side)
+            kw = dict(cm=True, side=self.side, ws=self.ws, ws_side=self.ws_side)
             dact = linear_bwd(s.act, P(l + "mlp.down_proj.weight"), dx, G(l + "mlp.down_proj.weight"), **kw)
             dg, du = ops.silu_mul_bwd(s.g, s.u, dact)
             dh2 = linear_bwd(s.h2, P(l + "mlp.gate_proj.weight"), dg, G(l + "mlp.gate_proj.weight"), **kw)
@@ -590,8 +568,8 @@ class SFTTrainer:
             da = linear_bwd(s.a.view(T, nq * hd), P(l + "self_attn.o_proj.weight"), dx_mid, G(l + "self_attn.o_proj.weight"), **kw)
             dqkv = torch.empty_like(s.qkv)
             q3, d3 = s.qkv.view(T, nq + 2 * nkv, hd), dqkv.view(T, nq + 2 * nkv, hd)
-            self._attn_bwd(q3[:, :nq], q3[:, nq:nq + nkv], q3[:, nq + nkv:], s.a, da.view(T, nq, hd), s.lse, True,
-                           d3[:, :nq], d3[:, nq:nq + nkv], d3[:, nq + nkv:], cu_seqlens=saved.cu, max_seqlen=saved.max_seqlen)
+            ops.attn_bwd(q3[:, :nq], q3[:, nq:nq + nkv], q3[:, nq + nkv:], s.a, da.view(T, nq, hd), s.lse, True,
+                         d3[:, :nq], d3[:, nq:nq + nkv], d3[:, nq + nkv:], cu_seqlens=saved.cu, max_seqlen=saved.max_seqlen)
             ops.rope_bwd_(dqkv, saved.cs, saved.sn, nq, nkv, hd)
             dh1 = linear_bwd(s.h1, self._fused(l + "self_attn.", "weight"), dqkv, self._fused_grad(l + "self_attn.", "weight"), self._fused_grad(l + "self_attn.", "bias"), **kw)
             dxi = ops.norm_bwd(s.x_in, P(l + "input_layernorm.weight"), dh1, G(l + "input_layernorm.weight"), None, c.rms_norm_eps, True)
@@ -704,6 +682,57 @@ class SFTTrainer:
             return torch.empty((0,), dtype=torch.int64)
         return torch.cat(list(blocks)).to(plan_img_src.device)[plan_img_src.long()]
 
+    def _plan_batch(self, input_ids, images, labels, attention_mask=None, num_items_in_batch=None, block_sizes=None, videos=None):
+        """The host plan of one step, shared by both drivers: integers and index tensors only (they live where `input_ids` lives: the
+        host for host-side ids, where nothing is launched and the step has no nonzero() + device sync in its middle — VERDICT round 2).
+        Splice + pack as llava_arch.py:412-490, 744-800; training truncates every sample to tokenizer.model_max_length AFTER media
+        expansion (llava_arch.py:519-526), and rows cut off by it are absent from the feat / nl maps.
+          images, n_img                    tiles in tower order (dynamic_s2: of every scale of every image; videos: their frames behind)
+          s2, n_pin, n_prow, pools, n_buf  `_media_plan` / `_media_blocks`: projector inputs and output rows, media feature buffer rows
+          T, txt / feat / nl _src, _dst    packed rows; int32 row maps into them from the embedding table (txt, nl) and the media buffer (feat)
+          positions, cu_seqlens, max_seqlen
+          target_rows, targets             packed rows that have a target (HF ForCausalLMLoss: shift by one inside each packed row)
+          n_valid, n_items                 their number; the count the loss is divided by"""
+        cfg = self.cfg
+        images, frames = self._with_videos(images, videos)
+        n_img = len(images)
+        s2, rows, n_pin = self._media_plan(n_img, self._block_sizes_with_frames(block_sizes, frames))
+        n_prow = n_pin * cfg.tokens_per_tile
+        img_blocks, vid_blocks, pools, n_buf = self._media_blocks(rows, frames, n_prow)
+        plan = self._splice(input_ids, attention_mask, labels, img_blocks, vid_blocks)
+        rp = repack(plan.mask, plan.labels)
+        T = int(rp.rows.numel())
+        hd = rp.rows.device
+        inv = torch.full((plan.B * plan.S,), -1, dtype=torch.int64, device=hd)        # packed row index of every padded-grid position
+        inv[rp.rows] = torch.arange(T, device=hd)
+        i32 = lambda t: t.to(torch.int32).contiguous()
+        # every spliced media row is a row of the media feature buffer or a token's embedding ("\n", the video encoder's start / end /
+        # separator tokens): `_media_blocks`
+        mrow = self._media_rows(plan.img_src, img_blocks + vid_blocks).to(hd)
+        dst_p = inv[plan.img_dst.long()]
+        is_nl = mrow < 0
+        tgt = torch.full((T,), IGNORE_INDEX, dtype=torch.int64, device=hd)
+        tgt[:-1] = rp.labels[1:]
+        valid = torch.nonzero(tgt != IGNORE_INDEX, as_tuple=False).flatten()
+        n_valid = int(valid.numel())
+        return SimpleNamespace(
+            images=images, n_img=n_img, s2=s2, n_pin=n_pin, n_prow=n_prow, pools=pools, n_buf=n_buf, T=T,
+            txt_src=i32(plan.txt_src), txt_dst=i32(inv[plan.txt_dst.long()]),
+            feat_src=i32(mrow[~is_nl]), feat_dst=i32(dst_p[~is_nl]), nl_src=i32(-1 - mrow[is_nl]), nl_dst=i32(dst_p[is_nl]),
+            positions=i32(rp.position_ids), cu_seqlens=i32(rp.cu_seqlens), max_seqlen=int(rp.max_seqlen),
+            target_rows=valid, targets=tgt[valid].contiguous(), n_valid=n_valid,
+            n_items=n_valid if num_items_in_batch is None else int(num_items_in_batch))
+
+    def _begin_step(self) -> None:
+        """The previous step's optimizer / exchange / wgrad work reads grads and writes params: order this step behind it, then start
+        from zero gradients and an empty bucket record."""
+        for st in (self.opt, self.side):
+            if st is not None:
+                torch.cuda.current_stream().wait_stream(st)
+        self.flat.grads.zero_()
+        self.reducer.log.clear()
+        self._touched = []
+
     # ------------------------------------------------------------------ one C-ABI call ------------------------------------
     def _c_structs(self, ptr):
         """(VilaVitWeights, VilaProjWeights, VilaLlmWeights) whose pointers come from `ptr(name)`: flat.param for the weights, flat.grad for
@@ -762,47 +791,22 @@ class SFTTrainer:
         import ctypes as C
         from . import _lib
         from ._lib import check
-        model, cfg, flat = self.model, self.cfg, self.flat
-        dev = model.device
-        for st in (self.opt, self.side):
-            if st is not None:
-                torch.cuda.current_stream().wait_stream(st)
-        flat.grads.zero_()
-        self.reducer.log.clear()
-        self._touched = []
-        c = cfg.llm
-        images, frames = self._with_videos(images, videos)
-        n_img = len(images)                             # tiles (dynamic_s2: the tiles of every scale of every image; videos: their frames)
-        pixels = torch.stack(list(images), 0).to(device=dev, dtype=torch.bfloat16).contiguous() if n_img else None
-        s2, rows, n_pin = self._media_plan(n_img, self._block_sizes_with_frames(block_sizes, frames))
-        img_blocks, vid_blocks, pools, n_buf = self._media_blocks(rows, frames, n_pin * cfg.tokens_per_tile)
-        plan = self._splice(input_ids, attention_mask, labels, img_blocks, vid_blocks)
-        rp = repack(plan.mask, plan.labels)
-        T = int(rp.rows.numel())
-        inv = torch.full((plan.B * plan.S,), -1, dtype=torch.int64)
-        inv[rp.rows] = torch.arange(T)
-        i32 = lambda t: t.to(torch.int32).contiguous().to(dev)
-        txt_src, txt_dst = i32(plan.txt_src), i32(inv[plan.txt_dst.long()])
-        mrow = self._media_rows(plan.img_src, img_blocks + vid_blocks)
-        dst_p = inv[plan.img_dst.long()]
-        is_nl = mrow < 0                                  # token rows: "\n" and the video encoder's start / end / separator tokens
-        feat_src, feat_dst, nl_dst = i32(mrow[~is_nl]), i32(dst_p[~is_nl]), i32(dst_p[is_nl])
-        nl_src = i32(-1 - mrow[is_nl])
-        tgt = torch.full((T,), IGNORE_INDEX, dtype=torch.int64)
-        tgt[:-1] = rp.labels[1:]
-        valid = torch.nonzero(tgt != IGNORE_INDEX, as_tuple=False).flatten()
-        n_valid = int(valid.numel())
-        n_items = n_valid if num_items_in_batch is None else int(num_items_in_batch)
-        rows32, tg = i32(valid), tgt[valid].contiguous().to(dev)
-        pos, cu = i32(rp.position_ids), i32(rp.cu_seqlens)
+        cfg, flat = self.cfg, self.flat
+        dev = self.model.device
+        self._begin_step()
+        p = self._plan_batch(input_ids, images, labels, attention_mask, num_items_in_batch, block_sizes, videos)
+        n_img, s2, n_pin, pools, n_buf = p.n_img, p.s2, p.n_pin, p.pools, p.n_buf
+        pixels = torch.stack(p.images, 0).to(device=dev, dtype=torch.bfloat16).contiguous() if n_img else None
+        txt_src, txt_dst, feat_src, feat_dst, nl_src, nl_dst, pos, cu, rows32, tg = (t.to(dev) for t in (
+            p.txt_src, p.txt_dst, p.feat_src, p.feat_dst, p.nl_src, p.nl_dst, p.positions, p.cu_seqlens, p.target_rows.to(torch.int32), p.targets))
         b = _lib.VilaSftBatch()
         P = lambda t: t.data_ptr() if t is not None and t.numel() else None
-        b.pixels, b.n_images, b.total_tokens = P(pixels), n_img, T
+        b.pixels, b.n_images, b.total_tokens = P(pixels), n_img, p.T
         b.txt_src, b.txt_dst, b.n_txt = P(txt_src), P(txt_dst), int(txt_src.numel())
         b.feat_src, b.feat_dst, b.n_feat = P(feat_src), P(feat_dst), int(feat_dst.numel())
         b.nl_src, b.nl_dst, b.n_nl = P(nl_src), P(nl_dst), int(nl_dst.numel())
-        b.positions, b.cu_seqlens, b.n_seq, b.max_seqlen = P(pos), P(cu), int(cu.numel()) - 1, int(rp.max_seqlen)
-        b.target_rows, b.targets, b.n_targets, b.loss_scale = P(rows32), P(tg), n_valid, 1.0 / max(n_items, 1)
+        b.positions, b.cu_seqlens, b.n_seq, b.max_seqlen = P(pos), P(cu), int(cu.numel()) - 1, p.max_seqlen
+        b.target_rows, b.targets, b.n_targets, b.loss_scale = P(rows32), P(tg), p.n_valid, 1.0 / max(p.n_items, 1)
         if s2 is not None:
             s2_desc, s2_tdesc = s2.desc.contiguous().to(dev), s2.tile_desc.contiguous().to(dev)
             b.s2_desc, b.s2_tile_desc, b.s2_n_blocks, b.s2_n_scales = P(s2_desc), P(s2_tdesc), n_pin, len(cfg.s2_scales)
@@ -853,52 +857,30 @@ class SFTTrainer:
         dynamic_s2 (the NVILA-8B recipe, scripts/NVILA/stage1_9tile.sh:19-22): `images` = the tiles of every scale of every image in
         tower order, `block_sizes` = media_config["image"]["block_sizes"] (one (h, w) or None per image); between tower and projector
         run the merge kernel forward and its adjoint backward (llava_arch.py:298-390)."""
-        model, cfg, flat = self.model, self.cfg, self.flat
-        dev = model.device
+        cfg, flat = self.cfg, self.flat
+        dev = self.model.device
         P, G = flat.param, flat.grad
-        for st in (self.opt, self.side):             # the previous step's optimizer / exchange / wgrad work reads grads, writes params
-            if st is not None:
-                torch.cuda.current_stream().wait_stream(st)
-        flat.grads.zero_()
-        self.reducer.log.clear()
-        self._touched = []
+        self._begin_step()
         c = cfg.llm
         H = c.hidden_size
-        # ---- vision + projector (+ "\n" end token) ----
-        images, frames = self._with_videos(images, videos)
-        pixels = torch.stack(list(images), 0).to(device=dev, dtype=torch.bfloat16) if len(images) else None
-        n_img = 0 if pixels is None else pixels.shape[0]          # tiles (dynamic_s2: of every scale of every image)
-        s2, rows, n_pin = self._media_plan(n_img, self._block_sizes_with_frames(block_sizes, frames))
+        p = self._plan_batch(input_ids, images, labels, attention_mask, num_items_in_batch, block_sizes, videos)
+        n_img, s2, pools, n_buf, n_prow, T = p.n_img, p.s2, p.pools, p.n_buf, p.n_prow, p.T
+        # ---- vision + projector ----
         if n_img:
+            pixels = torch.stack(p.images, 0).to(device=dev, dtype=torch.bfloat16)
             feats, vit_saved = self._vit_fwd(pixels)
             if s2 is not None:
                 s2_desc, s2_tdesc = s2.desc.to(dev), s2.tile_desc.to(dev)
                 feats = ops.s2_merge(feats, s2_desc, len(cfg.s2_scales), s2.splits)   # [n_blocks, N, n_scales*C]
             proj, proj_saved = self._proj_fwd(feats)                                   # [n_pin, T', H]
+            assert proj.shape[0] * proj.shape[1] == n_prow, f"the projector wrote {proj.shape[0]} x {proj.shape[1]} rows, the plan has {n_prow}"
         table = P("llm.model.embed_tokens.weight")
-        # ---- splice + pack (llava_arch.py:412-490, 744-800) ----
-        # training truncates every sample to tokenizer.model_max_length AFTER media expansion (llava_arch.py:519-526)
-        n_prow = proj.shape[0] * proj.shape[1] if n_img else 0                         # projector output rows
-        img_blocks, vid_blocks, pools, n_buf = self._media_blocks(rows, frames, n_prow)
-        plan = self._splice(input_ids, attention_mask, labels, img_blocks, vid_blocks)
-        rp = repack(plan.mask, plan.labels)
-        T = int(rp.rows.numel())
-        # packed row index of every padded-grid position
-        inv = torch.full((plan.B * plan.S,), -1, dtype=torch.int64, device=rp.rows.device)
-        inv[rp.rows] = torch.arange(T, device=rp.rows.device)
-        txt_dst = inv[plan.txt_dst.long()].to(torch.int32).to(dev)
+        # ---- splice + pack: text rows, media rows, the media tokens' rows ----
+        txt_src, txt_dst = p.txt_src.to(dev), p.txt_dst.to(dev)
         x0 = torch.empty((T, H), device=dev, dtype=torch.bfloat16)
-        ops.copy_rows(table, x0, plan.txt_src.to(dev), txt_dst, int(txt_dst.numel()))
+        ops.copy_rows(table, x0, txt_src, txt_dst, int(txt_dst.numel()))
         if n_img:
-            # every spliced media row is a row of the media feature buffer or a token's embedding (`_media_blocks`); rows cut off by the
-            # truncation are absent from plan.img_src / img_dst
-            mrow = self._media_rows(plan.img_src, img_blocks + vid_blocks).to(inv.device)
-            dst_p = inv[plan.img_dst.long()]
-            is_nl = mrow < 0
-            feat_src = mrow[~is_nl].to(torch.int32).to(dev)
-            feat_dst = dst_p[~is_nl].to(torch.int32).to(dev)
-            nl_dst = dst_p[is_nl].to(torch.int32).to(dev)
-            nl_src = (-1 - mrow[is_nl]).to(torch.int32).to(dev)
+            feat_src, feat_dst, nl_src, nl_dst = p.feat_src.to(dev), p.feat_dst.to(dev), p.nl_src.to(dev), p.nl_dst.to(dev)
             n_feat, n_nl = int(feat_dst.numel()), int(nl_dst.numel())
             media = proj.reshape(n_prow, H)
             if pools:                                                                  # TSPVideoEncoder: mean over (t, h, w) windows (tsp.py:28-52)
@@ -908,20 +890,12 @@ class SFTTrainer:
             ops.copy_rows(media, x0, feat_src, feat_dst, n_feat)
             if n_nl:
                 ops.copy_rows(table, x0, nl_src, nl_dst, n_nl)
-        pos = rp.position_ids.to(dev)
-        cu = rp.cu_seqlens.to(dev)
-        # rows that have a target (HF ForCausalLMLoss: shift by one inside each packed row): integer work on the plan's device — the
-        # host for host-side ids — so the step has no nonzero() launch + device sync in its middle
-        lab_h = rp.labels
-        tgt_h = torch.full((T,), IGNORE_INDEX, dtype=torch.int64, device=lab_h.device)
-        tgt_h[:-1] = lab_h[1:]
-        valid_h = torch.nonzero(tgt_h != IGNORE_INDEX, as_tuple=False).flatten()
-        n_valid = int(valid_h.numel())
-        valid, tgt_valid = valid_h.to(dev), tgt_h[valid_h].contiguous().to(dev)
+        pos, cu = p.positions.to(dev), p.cu_seqlens.to(dev)
+        n_valid, n_items = p.n_valid, p.n_items
+        valid, tgt_valid = p.target_rows.to(dev), p.targets.to(dev)
         # ---- LLM ----
-        saved = self._llm_fwd(x0, pos, cu, rp.max_seqlen)
+        saved = self._llm_fwd(x0, pos, cu, p.max_seqlen)
         # ---- loss on the rows that have a target ----
-        n_items = n_valid if num_items_in_batch is None else int(num_items_in_batch)
         loss = torch.zeros((1,), device=dev, dtype=torch.float32)
         dhn = torch.zeros((T, H), device=dev, dtype=torch.bfloat16)
         head_name = "llm.model.embed_tokens.weight" if c.tie_word_embeddings else "llm.lm_head.weight"
@@ -940,7 +914,7 @@ class SFTTrainer:
                 logits = ops.gemm(hv[r0:r1], head, out_f32=True)                         # [<= LOGIT_CHUNK, V] fp32
                 ops.ce_loss(logits, tgt_valid[r0:r1], loss, 1.0 / max(n_items, 1), out=dlog[r0:r1])
             del logits
-            dhv = linear_bwd(hv, head, dlog, G(head_name), cm=self.cm, ws=self.ws)
+            dhv = linear_bwd(hv, head, dlog, G(head_name), cm=True, ws=self.ws)
             ops.copy_rows(dhv, dhn, None, rows32, n_valid)
         if not c.tie_word_embeddings:
             self._ready("llm.lm_head.")
@@ -951,7 +925,10 @@ class SFTTrainer:
         ge = G("llm.model.embed_tokens.weight")
         dtxt = torch.empty((int(txt_dst.numel()), H), device=dev, dtype=torch.bfloat16)
         ops.copy_rows(dx0, dtxt, txt_dst, None, int(txt_dst.numel()))
-        ops.scatter_add_rows(dtxt, ge, plan.txt_src.to(dev))
+        # the token ids are uploaded a second time on purpose: the pageable copy holds the host back until the decoder's backward has drained.
+        # With the projector / tower backward enqueued further ahead instead, the step measured 180.9-181.2 against 179.3-180.5 ms on one
+        # box, five alternating runs each (the chip is power-bound: DESIGN §4.4)
+        ops.scatter_add_rows(dtxt, ge, p.txt_src.to(dev))
         if n_img and n_nl:
             dnl = torch.empty((n_nl, H), device=dev, dtype=torch.bfloat16)
             ops.copy_rows(dx0, dnl, nl_dst, None, n_nl)
@@ -1012,7 +989,7 @@ class SFTTrainer:
         if self.max_grad_norm is not None:
             norm = float(ops.sumsq(f.grads).sqrt())                  # untouched buckets hold zeros
             scale = min(1.0, self.max_grad_norm / (norm + 1e-6))
-        # the same buckets, the same per-bucket step counts as the per-bucket path: results do not depend on VILA_SFT_OPT_STREAM
+        # the same buckets, the same per-bucket step counts as the per-bucket path: results do not depend on where AdamW ran
         for prefix in self._touched:
             self._adamw_bucket(prefix, scale)
 
