@@ -201,6 +201,30 @@ size_t vila_llm_decode_batch_workspace_bytes(const VilaLlmShape* s, int n);
 int vila_llm_decode_step_batch(const VilaLlmWeights* w, const VilaKvCache* cache, const VilaDecodeBatch* st,
                                void* workspace, size_t workspace_bytes, vila_stream_t stream);
 
+/* Per-row sampling for the batched step: the choice of VilaSampling (top_k in 1..64), made for every row at once.  All four members are DEVICE
+ * arrays of n entries that the kernels read at run time, so ONE captured hipGraph of the step serves any mix of rows: the host rewrites a row's
+ * entries when a request joins or leaves.  A row whose temperature is <= 0 is a greedy row (largest logit, ties to the lower index, as the greedy
+ * batched step picks).  A sampled row's token is bit for bit what vila_sample_f32 returns for the same logits row, parameters, seed and counter.
+ * Values out of range are clamped on the device (top_k to 1..64, top_p to (0, 1]); checking them is the host's business. */
+typedef struct {
+    const float* temperature;   /* [n]; <= 0: greedy row */
+    const int32_t* top_k;       /* [n]; 1..64 */
+    const float* top_p;         /* [n]; (0, 1] */
+    const uint64_t* seed;       /* [n] */
+} VilaBatchSampling;
+size_t vila_sample_batch_workspace_bytes(int n);
+/* logits [n][vocab] fp32, rows ld_logits floats apart, n <= 16 -> out[n]; counter: device [n] mixed into each row's RNG (nullable = 0);
+ * dist_out (nullable) [n][128]: per row 64 probabilities followed by 64 int32 token ids (descending probability, -1 = unused slot; a greedy
+ * row: probability 1 on its token).  Three launches whatever n.  No state is advanced. */
+int vila_sample_batch_f32(const float* logits, int64_t ld_logits, int n, int vocab, const VilaBatchSampling* sp, const int32_t* counter,
+                          int64_t* out, void* workspace, float* dist_out, vila_stream_t stream);
+/* vila_llm_decode_step_batch with that pick in place of the greedy one: row i draws with counter pos[i] (the position of the token it consumes,
+ * read before it advances), then token / out_ids / n_out / pos move as in the greedy step.  The launches before the pick are the greedy step's,
+ * so the logits are the same bits. */
+size_t vila_llm_decode_batch_sample_workspace_bytes(const VilaLlmShape* s, int n);
+int vila_llm_decode_step_batch_sample(const VilaLlmWeights* w, const VilaKvCache* cache, const VilaDecodeBatch* st,
+                                      void* workspace, size_t workspace_bytes, const VilaBatchSampling* sp, vila_stream_t stream);
+
 /* hipGraph helpers: capture whatever is enqueued on `stream` between begin/end, replay it later. */
 int vila_graph_begin(vila_stream_t stream);
 int vila_graph_end(vila_stream_t stream, void** graph_exec_out);
@@ -423,6 +447,11 @@ int vila_gemv_w4_batch_bf16(const void* x, int64_t ldx, int n, const void* Wq, c
 size_t vila_llm_decode_batch_w4_workspace_bytes(const VilaLlmShape* s, int n);
 int vila_llm_decode_step_batch_w4(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers /*[host]*/, const VilaKvCache* cache,
                                   const VilaDecodeBatch* st, void* workspace, size_t workspace_bytes, vila_stream_t stream);
+/* the W4 batched step with the per-row pick of vila_llm_decode_step_batch_sample */
+size_t vila_llm_decode_batch_w4_sample_workspace_bytes(const VilaLlmShape* s, int n);
+int vila_llm_decode_step_batch_w4_sample(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers /*[host]*/, const VilaKvCache* cache,
+                                         const VilaDecodeBatch* st, void* workspace, size_t workspace_bytes, const VilaBatchSampling* sp,
+                                         vila_stream_t stream);
 
 /* W4A16 prefill GEMM (vila_amd/csrc/gemm_w4.hip) on the same packed buffers: y[M][N] = x[M][K] . W^T, x bf16 row stride K, y row stride N,
  * any M >= 1.  mode 0: (+bias)(+residual, row stride N; y may alias it); mode 1: W holds 2N interleaved gate/up rows, y = silu(Wg x) * (Wu x),

@@ -67,6 +67,10 @@ class VilaSampling(C.Structure):
     _fields_ = [("temperature", c_float), ("top_k", c_int), ("top_p", c_float), ("seed", C.c_uint64), ("seed_dev", c_void_p)]
 
 
+class VilaBatchSampling(C.Structure):
+    _fields_ = [("temperature", c_void_p), ("top_k", c_void_p), ("top_p", c_void_p), ("seed", c_void_p)]
+
+
 class VilaDecodeState(C.Structure):
     _fields_ = [("pos", c_void_p), ("token", c_void_p), ("out_ids", c_void_p), ("n_out", c_void_p),
                 ("max_out", c_int), ("logits", c_void_p)]
@@ -116,6 +120,11 @@ PROTOTYPES = {
                                             c_void_p, c_size_t, C.POINTER(VilaSampling), c_void_p]),
     "vila_llm_decode_batch_workspace_bytes": (c_size_t, [C.POINTER(VilaLlmShape), c_int]),
     "vila_llm_decode_step_batch": (c_int, [C.POINTER(VilaLlmWeights), C.POINTER(VilaKvCache), C.POINTER(VilaDecodeBatch), c_void_p, c_size_t, c_void_p]),
+    "vila_sample_batch_workspace_bytes": (c_size_t, [c_int]),
+    "vila_sample_batch_f32": (c_int, [c_void_p, c_int64, c_int, c_int, C.POINTER(VilaBatchSampling), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vila_llm_decode_batch_sample_workspace_bytes": (c_size_t, [C.POINTER(VilaLlmShape), c_int]),
+    "vila_llm_decode_step_batch_sample": (c_int, [C.POINTER(VilaLlmWeights), C.POINTER(VilaKvCache), C.POINTER(VilaDecodeBatch), c_void_p, c_size_t,
+                                                  C.POINTER(VilaBatchSampling), c_void_p]),
     "vila_graph_begin": (c_int, [c_void_p]),
     "vila_graph_end": (c_int, [c_void_p, C.POINTER(c_void_p)]),
     "vila_graph_launch": (c_int, [c_void_p, c_void_p]),
@@ -187,6 +196,9 @@ PROTOTYPES = {
     "vila_llm_decode_batch_w4_workspace_bytes": (c_size_t, [C.POINTER(VilaLlmShape), c_int]),
     "vila_llm_decode_step_batch_w4": (c_int, [C.POINTER(VilaLlmWeights), C.POINTER(VilaLlmLayerW4), C.POINTER(VilaKvCache),
                                               C.POINTER(VilaDecodeBatch), c_void_p, c_size_t, c_void_p]),
+    "vila_llm_decode_batch_w4_sample_workspace_bytes": (c_size_t, [C.POINTER(VilaLlmShape), c_int]),
+    "vila_llm_decode_step_batch_w4_sample": (c_int, [C.POINTER(VilaLlmWeights), C.POINTER(VilaLlmLayerW4), C.POINTER(VilaKvCache),
+                                                     C.POINTER(VilaDecodeBatch), c_void_p, c_size_t, C.POINTER(VilaBatchSampling), c_void_p]),
     "vila_gemm_w4_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "vila_gemm_w4_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                   c_void_p, c_size_t, c_void_p]),

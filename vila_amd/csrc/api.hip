@@ -651,11 +651,28 @@ static int decode_step_impl(const VilaLlmWeights* w, const VilaLlmLayerW4* ql, c
 // =================================================================================================
 // Batched decode step (decode_batch.hip)
 // =================================================================================================
+// A sampled batched step keeps the greedy step's workspace layout and puts the sampler's candidates behind it: with `sp` set, the step's share of
+// *workspace_bytes shrinks to the greedy size and `out` points at the tail.
+struct BatchSamplingWs { const BatchSampling* sp; void* ws; };
+static int batch_sampling_of(const VilaBatchSampling* sp, const VilaLlmShape* sh, int n, void* workspace, size_t* workspace_bytes, BatchSampling* bs,
+                             BatchSamplingWs* out) {
+    out->sp = nullptr; out->ws = nullptr;
+    if (sp == nullptr) return 0;
+    VILA_REQUIRE(sp->temperature != nullptr && sp->top_k != nullptr && sp->top_p != nullptr && sp->seed != nullptr,
+                 "llm_decode_batch_sample: a per-row parameter array is NULL");
+    VILA_REQUIRE(n >= 1 && n <= 16, "llm_decode_batch_sample: 1..16 sequences (got %d)", n);
+    const size_t head = align_up(bdecode_workspace_bytes(sh->hidden, sh->inter, sh->q_heads * sh->head_dim, sh->head_dim, n), 256);
+    VILA_REQUIRE(*workspace_bytes >= head + sample_batch_workspace_bytes(n), "llm_decode_batch_sample: workspace too small");
+    *bs = BatchSampling{sp->temperature, sp->top_k, sp->top_p, sp->seed};
+    out->sp = bs; out->ws = (char*)workspace + head;
+    *workspace_bytes = head;
+    return 0;
+}
 extern "C" size_t vila_llm_decode_batch_workspace_bytes(const VilaLlmShape* s, int n) {
     return bdecode_workspace_bytes(s->hidden, s->inter, s->q_heads * s->head_dim, s->head_dim, n);
 }
-extern "C" int vila_llm_decode_step_batch(const VilaLlmWeights* w, const VilaKvCache* cache, const VilaDecodeBatch* st,
-                                          void* workspace, size_t workspace_bytes, vila_stream_t stream) {
+static int decode_step_batch_impl(const VilaLlmWeights* w, const VilaKvCache* cache, const VilaDecodeBatch* st, void* workspace, size_t workspace_bytes,
+                                  const VilaBatchSampling* sp, vila_stream_t stream) {
     VILA_REQUIRE(w != nullptr && cache != nullptr && st != nullptr && workspace != nullptr, "llm_decode_batch: NULL argument");
     const VilaLlmShape& sh = w->shape;
     hipStream_t s = S(stream);
@@ -669,8 +686,24 @@ extern "C" int vila_llm_decode_step_batch(const VilaLlmWeights* w, const VilaKvC
         layers[l] = BLayer{L.ln1_w, L.wq, L.bq, L.wo, L.ln2_w, L.w_gate, L.w_up, L.w_down};
     }
     BDecodeArgs m{w->embed, w->norm_w, w->lm_head, sh.hidden, sh.inter, sh.n_layers, sh.q_heads, sh.kv_heads, sh.head_dim, sh.vocab, sh.rms_eps, sh.rope_theta};
+    BatchSampling bs{};
+    BatchSamplingWs sw{};
+    VILA_TRY(batch_sampling_of(sp, &sh, st->n, workspace, &workspace_bytes, &bs, &sw));
     return bdecode_step(m, layers.data(), B(cache->k), B(cache->v), cache->max_ctx, cache->n_slots, st->n, st->pos, st->token, st->out_ids, st->n_out,
-                        st->max_out, st->logits, workspace, workspace_bytes, s);
+                        st->max_out, st->logits, workspace, workspace_bytes, s, nullptr, sw.sp, sw.ws);
+}
+extern "C" int vila_llm_decode_step_batch(const VilaLlmWeights* w, const VilaKvCache* cache, const VilaDecodeBatch* st,
+                                          void* workspace, size_t workspace_bytes, vila_stream_t stream) {
+    return decode_step_batch_impl(w, cache, st, workspace, workspace_bytes, nullptr, stream);
+}
+// the batched step with a per-row pick (sample.hip's batched sampler) instead of the greedy pair; everything before the pick is the same launches
+extern "C" size_t vila_llm_decode_batch_sample_workspace_bytes(const VilaLlmShape* s, int n) {
+    return align_up(vila_llm_decode_batch_workspace_bytes(s, n), 256) + sample_batch_workspace_bytes(n);
+}
+extern "C" int vila_llm_decode_step_batch_sample(const VilaLlmWeights* w, const VilaKvCache* cache, const VilaDecodeBatch* st,
+                                                 void* workspace, size_t workspace_bytes, const VilaBatchSampling* sp, vila_stream_t stream) {
+    VILA_REQUIRE(sp != nullptr, "llm_decode_batch_sample: sampling parameters are NULL");
+    return decode_step_batch_impl(w, cache, st, workspace, workspace_bytes, sp, stream);
 }
 
 // the batched step with the four projections of every layer read from the int4 layers (gemv_w4_batch.hip); embed, norms, the fused q|k|v
@@ -678,8 +711,8 @@ extern "C" int vila_llm_decode_step_batch(const VilaLlmWeights* w, const VilaKvC
 extern "C" size_t vila_llm_decode_batch_w4_workspace_bytes(const VilaLlmShape* s, int n) {
     return bdecode_workspace_bytes(s->hidden, s->inter, s->q_heads * s->head_dim, s->head_dim, n);
 }
-extern "C" int vila_llm_decode_step_batch_w4(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers, const VilaKvCache* cache, const VilaDecodeBatch* st,
-                                             void* workspace, size_t workspace_bytes, vila_stream_t stream) {
+static int decode_step_batch_w4_impl(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers, const VilaKvCache* cache, const VilaDecodeBatch* st,
+                                     void* workspace, size_t workspace_bytes, const VilaBatchSampling* sp, vila_stream_t stream) {
     VILA_REQUIRE(w != nullptr && qlayers != nullptr && cache != nullptr && st != nullptr && workspace != nullptr, "llm_decode_batch_w4: NULL argument");
     const VilaLlmShape& sh = w->shape;
     hipStream_t s = S(stream);
@@ -697,8 +730,32 @@ extern "C" int vila_llm_decode_step_batch_w4(const VilaLlmWeights* w, const Vila
         ql[l] = BLayerW4{Q.qkv_q, Q.qkv_sz, Q.o_q, Q.o_sz, Q.gateup_q, Q.gateup_sz, Q.down_q, Q.down_sz};
     }
     BDecodeArgs m{w->embed, w->norm_w, w->lm_head, sh.hidden, sh.inter, sh.n_layers, sh.q_heads, sh.kv_heads, sh.head_dim, sh.vocab, sh.rms_eps, sh.rope_theta};
+    BatchSampling bs{};
+    BatchSamplingWs sw{};
+    VILA_TRY(batch_sampling_of(sp, &sh, st->n, workspace, &workspace_bytes, &bs, &sw));
     return bdecode_step(m, layers.data(), B(cache->k), B(cache->v), cache->max_ctx, cache->n_slots, st->n, st->pos, st->token, st->out_ids, st->n_out,
-                        st->max_out, st->logits, workspace, workspace_bytes, s, ql.data());
+                        st->max_out, st->logits, workspace, workspace_bytes, s, ql.data(), sw.sp, sw.ws);
+}
+extern "C" int vila_llm_decode_step_batch_w4(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers, const VilaKvCache* cache, const VilaDecodeBatch* st,
+                                             void* workspace, size_t workspace_bytes, vila_stream_t stream) {
+    return decode_step_batch_w4_impl(w, qlayers, cache, st, workspace, workspace_bytes, nullptr, stream);
+}
+extern "C" size_t vila_llm_decode_batch_w4_sample_workspace_bytes(const VilaLlmShape* s, int n) {
+    return align_up(vila_llm_decode_batch_w4_workspace_bytes(s, n), 256) + sample_batch_workspace_bytes(n);
+}
+extern "C" int vila_llm_decode_step_batch_w4_sample(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers, const VilaKvCache* cache, const VilaDecodeBatch* st,
+                                                    void* workspace, size_t workspace_bytes, const VilaBatchSampling* sp, vila_stream_t stream) {
+    VILA_REQUIRE(sp != nullptr, "llm_decode_batch_w4_sample: sampling parameters are NULL");
+    return decode_step_batch_w4_impl(w, qlayers, cache, st, workspace, workspace_bytes, sp, stream);
+}
+
+// the batched sampler on its own (operator level: no state advance)
+extern "C" size_t vila_sample_batch_workspace_bytes(int n) { return sample_batch_workspace_bytes(n); }
+extern "C" int vila_sample_batch_f32(const float* logits, int64_t ld_logits, int n, int vocab, const VilaBatchSampling* sp, const int32_t* counter, int64_t* out,
+                                     void* workspace, float* dist_out, vila_stream_t stream) {
+    VILA_REQUIRE(sp != nullptr && logits != nullptr && out != nullptr && workspace != nullptr, "sample_batch: NULL argument");
+    const BatchSampling bs{sp->temperature, sp->top_k, sp->top_p, sp->seed};
+    return launch_sample_batch(logits, ld_logits, n, vocab, bs, counter, out, workspace, dist_out, nullptr, nullptr, nullptr, 0, S(stream));
 }
 
 // =================================================================================================

@@ -500,7 +500,7 @@ size_t bdecode_workspace_bytes(int H, int F, int QS, int hd, int n) {
 
 int bdecode_step(const BDecodeArgs& m, const BLayer* layers, bf16_t* kcache, bf16_t* vcache, int max_ctx, int n_slots, int n, int32_t* pos, int64_t* token,
                  int64_t* out_ids, int32_t* n_out, int max_out, float* logits, void* workspace, size_t workspace_bytes, hipStream_t s,
-                 const BLayerW4* qlayers) {
+                 const BLayerW4* qlayers, const BatchSampling* sampling, void* sampling_ws) {
     const int H = m.hidden, F = m.inter, hd = m.head_dim, QS = m.q_heads * hd, KS = m.kv_heads * hd;
     VILA_REQUIRE(n >= 1 && n <= 16 && n <= n_slots, "batched decode: %d sequences need 1..16 KV-cache slots (cache has %d)", n, n_slots);
     VILA_REQUIRE(QS == H, "batched decode: q_heads*head_dim (%d) must equal hidden (%d)", QS, H);
@@ -508,6 +508,7 @@ int bdecode_step(const BDecodeArgs& m, const BLayer* layers, bf16_t* kcache, bf1
     VILA_REQUIRE(qlayers == nullptr || (H % 128 == 0 && F % 128 == 0),
                  "batched W4 decode: hidden (%d) and intermediate (%d) must be multiples of the 128-wide quantisation group", H, F);
     VILA_REQUIRE(workspace_bytes >= bdecode_workspace_bytes(H, F, QS, hd, n), "batched decode: workspace too small");
+    VILA_REQUIRE(sampling == nullptr || sampling_ws != nullptr, "batched decode: the sampled pick needs its workspace");
     char* wp = (char*)workspace; size_t off = 0;
     auto take = [&](size_t bytes) { off = align_up(off, 256); void* r = wp + off; off += bytes; return r; };
     bf16_t* x = (bf16_t*)take((size_t)n * H * 2);
@@ -578,6 +579,9 @@ int bdecode_step(const BDecodeArgs& m, const BLayer* layers, bf16_t* kcache, bf1
     lm.ldx = H; lm.W = (const bf16_t*)m.lm_head; lm.y_f32 = logits; lm.ldf = m.vocab;
     lm.n = n; lm.N = m.vocab; lm.K = H; lm.mode = 0;
     VILA_TRY(launch_bgemm(lm, s));
+    // the pick: per-row sampling (sample.hip; greedy rows included, position = the draw's counter, read before it advances) or the greedy pair
+    if (sampling != nullptr)
+        return launch_sample_batch(logits, m.vocab, n, m.vocab, *sampling, pos, token, sampling_ws, nullptr, pos, out_ids, n_out, max_out, s);
     hipLaunchKernelGGL(bdec_pick1_kernel, dim3(PICK_SLICES, n), dim3(256), 0, s, logits, m.vocab, pick_v, pick_i);
     VILA_LAUNCH_CHECK();
     hipLaunchKernelGGL(bdec_pick2_kernel, dim3(n), dim3(64), 0, s, pick_v, pick_i, token, pos, out_ids, n_out, max_out);

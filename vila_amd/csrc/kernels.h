@@ -59,6 +59,13 @@ int launch_argmax(const float* logits, int V, int64_t* out, float* tmpv, int* tm
 size_t sample_workspace_bytes();
 int launch_sample(const float* logits, int n, float temperature, int top_k, float top_p, uint64_t seed, const uint64_t* seed_dev, const int32_t* counter, int64_t* out,
                   void* workspace, float* prob_out, hipStream_t s);
+// the batched sampler: one choice per row of logits [n][vocab] (n <= 16, top_k 1..64), every per-row parameter a device array [n]; temperature <= 0 =
+// greedy row.  out[row] = the token; dist_out (nullable) [n][128]; adv_pos != nullptr: also the batched decode step's state advance
+// (out_ids[row][n_out[row]++] = token, pos[row] = counter[row] + 1)
+struct BatchSampling { const float* temperature; const int32_t* top_k; const float* top_p; const uint64_t* seed; };
+size_t sample_batch_workspace_bytes(int n);
+int launch_sample_batch(const float* logits, int64_t ld_logits, int n, int vocab, const BatchSampling& sp, const int32_t* counter, int64_t* out, void* workspace,
+                        float* dist_out, int32_t* adv_pos, int64_t* adv_out_ids, int32_t* adv_n_out, int max_out, hipStream_t s);
 // dynamic_s2 merge (s2.hip): tower output -> projector input, desc = device [n_blocks][6] {tile_base, bh, bw, i, j, single}
 int launch_s2_merge(const bf16_t* feats, bf16_t* out, const int32_t* desc, int n_blocks, int g, int C, int n_scales, const int* splits,
                     hipStream_t s);
@@ -142,7 +149,7 @@ struct BLayerW4 { const void *qkv_q, *qkv_sz, *o_q, *o_sz, *gateup_q, *gateup_sz
 size_t bdecode_workspace_bytes(int H, int F, int QS, int hd, int n);
 int bdecode_step(const BDecodeArgs& m, const BLayer* layers, bf16_t* kcache, bf16_t* vcache, int max_ctx, int n_slots, int n, int32_t* pos, int64_t* token,
                  int64_t* out_ids, int32_t* n_out, int max_out, float* logits, void* workspace, size_t workspace_bytes, hipStream_t s,
-                 const BLayerW4* qlayers = nullptr);
+                 const BLayerW4* qlayers = nullptr, const BatchSampling* sampling = nullptr, void* sampling_ws = nullptr);
 int launch_decode_prologue(const bf16_t* table, const int64_t* tok, bf16_t* out, int H, int64_t vocab, const int32_t* pos, float* rope_cs,
                            int hd, float theta, hipStream_t s);
 int launch_decode_advance(int32_t* pos, const int64_t* tok, int64_t* out_ids, int32_t* n_out, int max_out, hipStream_t s);

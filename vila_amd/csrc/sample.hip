@@ -12,6 +12,8 @@
 // the vocabulary — goes through smp_large_kernel below: ONE 1024-thread block, radix selection over the 64-bit (value, index) keys for the k-th
 // largest, a mass-weighted radix descent for the nucleus threshold, a draw by prefix sums in index order.  The draw cannot match
 // torch.multinomial's generator bit for bit — parity for this op is distributional (tests/test_gpu_sampling.py).
+// The batched sampler at the end of the file makes the same choice for up to 16 rows at once (rows on blockIdx.y, per-row parameters in device
+// arrays, greedy rows beside sampled ones): the pick of a batched decode step whose ONE captured graph serves any mix of requests.
 #include "kernels.h"
 
 #define SMP_CAND 64
@@ -46,20 +48,43 @@ __device__ void smp_sort1024(uint64_t* keys) {
     __syncthreads();
 }
 
-// stage 1 / 2: candidates in, SMP_CAND best per block out.  in_vals == nullptr: read raw logits [n] (index = position);
-// otherwise read (key) candidates produced by the previous stage.
+// a greedy row needs the largest key only: keys[0] = max of the 1024, keys[1..63] = 0 (256 threads)
+__device__ void smp_max1024(uint64_t* keys) {
+    __shared__ uint64_t wm[4];
+    __syncthreads();
+    uint64_t m = 0;
+    for (int i = threadIdx.x; i < 1024; i += 256) { const uint64_t k = keys[i]; m = k > m ? k : m; }
+    for (int o = 32; o > 0; o >>= 1) { const uint64_t t = __shfl_xor((unsigned long long)m, o, 64); m = t > m ? t : m; }
+    if ((threadIdx.x & 63) == 0) wm[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x < SMP_CAND) {
+        uint64_t b = 0;
+        for (int w = 0; w < 4; ++w) b = wm[w] > b ? wm[w] : b;
+        keys[threadIdx.x] = threadIdx.x == 0 ? b : 0;
+    }
+    __syncthreads();
+}
+
+// stage 1 / 2: candidates in, SMP_CAND best per block out.  in_keys == nullptr: read raw logits [n] (index = position);
+// otherwise read (key) candidates produced by the previous stage.  Rows of a batch lie on blockIdx.y (in_stride / out_stride elements apart);
+// row_temperature (nullable, [rows], device): a row whose temperature is not positive is a greedy row and keeps its largest key only.
 __global__ __launch_bounds__(256) void smp_select_kernel(const float* __restrict__ logits, const uint64_t* __restrict__ in_keys, int n, int per_block,
-                                                         uint64_t* __restrict__ out_keys) {
+                                                         uint64_t* __restrict__ out_keys, int64_t in_stride, int64_t out_stride,
+                                                         const float* __restrict__ row_temperature) {
     __shared__ uint64_t keys[1024];
+    const int row = blockIdx.y;
+    const float* lr = logits != nullptr ? logits + row * in_stride : nullptr;
+    const uint64_t* kr = in_keys != nullptr ? in_keys + row * in_stride : nullptr;
     const int base = blockIdx.x * per_block;
     for (int i = threadIdx.x; i < 1024; i += 256) {
         const int g = base + i;
         uint64_t k = 0;                                             // below every real key
-        if (i < per_block && g < n) k = (in_keys != nullptr) ? in_keys[g] : smp_key(logits[g], g);
+        if (i < per_block && g < n) k = (kr != nullptr) ? kr[g] : smp_key(lr[g], g);
         keys[i] = k;
     }
-    smp_sort1024(keys);
-    if (threadIdx.x < SMP_CAND) out_keys[blockIdx.x * SMP_CAND + threadIdx.x] = keys[threadIdx.x];
+    if (row_temperature != nullptr && !(row_temperature[row] > 0.f)) smp_max1024(keys);       // block-uniform
+    else smp_sort1024(keys);
+    if (threadIdx.x < SMP_CAND) out_keys[row * out_stride + blockIdx.x * SMP_CAND + threadIdx.x] = keys[threadIdx.x];
 }
 
 __device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
@@ -69,14 +94,10 @@ __device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
     return x ^ (x >> 31);
 }
 
-// stage 3: global top-64, then temperature / top-k / top-p / draw by wave 0
-__global__ __launch_bounds__(256) void smp_final_kernel(const uint64_t* __restrict__ in_keys, int n_in, float inv_temperature, int top_k, float top_p,
-                                                        uint64_t seed_imm, const uint64_t* __restrict__ seed_dev, const int32_t* __restrict__ counter, int64_t* __restrict__ out, float* __restrict__ prob_out) {
-    __shared__ uint64_t keys[1024];
-    for (int i = threadIdx.x; i < 1024; i += 256) keys[i] = i < n_in ? in_keys[i] : 0;
-    smp_sort1024(keys);
-    if (threadIdx.x >= 64) return;
-    const int lane = threadIdx.x;
+// The draw, by ONE wave over the sorted candidates keys[0..63] (descending): temperature / top-k / top-p, then a counter-based uniform.  Shared by
+// the solo and the batched final stage, so that both make the same choice bit for bit.  Returns the token in every lane.
+__device__ __forceinline__ int smp_draw_wave(const uint64_t* keys, int lane, float inv_temperature, int top_k, float top_p, uint64_t seed, uint32_t counter,
+                                             float* __restrict__ prob_out) {
     const uint64_t k = keys[lane];
     const bool real = k != 0 && lane < top_k;                      // TopK: the k most likely survive
     const float z = smp_val(k) * inv_temperature, zmax = smp_val(keys[0]) * inv_temperature;
@@ -100,14 +121,65 @@ __global__ __launch_bounds__(256) void smp_final_kernel(const uint64_t* __restri
         const float t = __shfl_up(cum, o, 64);
         if (lane >= o) cum += t;
     }
-    const uint64_t seed = seed_dev != nullptr ? *seed_dev : seed_imm;
-    const uint64_t r = splitmix64(seed ^ splitmix64((uint64_t)(uint32_t)(counter != nullptr ? *counter : 0)));
+    const uint64_t r = splitmix64(seed ^ splitmix64((uint64_t)counter));
     const float u = (float)(r >> 40) * (1.0f / 16777216.0f) * kept_total;      // uniform in [0, kept_total)
     const unsigned long long hit = __ballot(keep && cum > u);
     const int pick = hit ? __ffsll((long long)hit) - 1 : 0;
-    if (lane == pick) *out = (int64_t)smp_idx(k);
     if (prob_out != nullptr) prob_out[lane] = pk / kept_total;     // optional: the distribution that was sampled (tests)
     if (prob_out != nullptr) ((int*)(prob_out + 64))[lane] = real ? smp_idx(k) : -1;
+    return __shfl(smp_idx(k), pick, 64);
+}
+
+// stage 3: global top-64, then temperature / top-k / top-p / draw by wave 0
+__global__ __launch_bounds__(256) void smp_final_kernel(const uint64_t* __restrict__ in_keys, int n_in, float inv_temperature, int top_k, float top_p,
+                                                        uint64_t seed_imm, const uint64_t* __restrict__ seed_dev, const int32_t* __restrict__ counter, int64_t* __restrict__ out, float* __restrict__ prob_out) {
+    __shared__ uint64_t keys[1024];
+    for (int i = threadIdx.x; i < 1024; i += 256) keys[i] = i < n_in ? in_keys[i] : 0;
+    smp_sort1024(keys);
+    if (threadIdx.x >= 64) return;
+    const int lane = threadIdx.x;
+    const uint64_t seed = seed_dev != nullptr ? *seed_dev : seed_imm;
+    const int tok = smp_draw_wave(keys, lane, inv_temperature, top_k, top_p, seed, (uint32_t)(counter != nullptr ? *counter : 0), prob_out);
+    if (lane == 0) *out = (int64_t)tok;
+}
+
+// stage 3 of the batched sampler: one block per row.  Every per-row parameter is read from device arrays, so ONE captured launch serves any mix
+// of rows: temperature <= 0 = greedy row (the largest key: highest value, ties to the lower index).  top_k / top_p are clamped to 1..64 / (0, 1]
+// (the host validates; a bad device value must not index out of range).  adv_pos != nullptr: the state advance of the batched decode step
+// (bdec_pick2_kernel's), with `counter` read BEFORE the position moves (counter and adv_pos are the same array there: no __restrict__).
+__global__ __launch_bounds__(256) void smp_batch_final_kernel(const uint64_t* __restrict__ in_keys, int n_in, int64_t in_stride, const float* __restrict__ temperature,
+                                                              const int32_t* __restrict__ top_k, const float* __restrict__ top_p, const uint64_t* __restrict__ seed,
+                                                              const int32_t* counter, int64_t* __restrict__ out, float* __restrict__ prob_out,
+                                                              int32_t* adv_pos, int64_t* __restrict__ adv_out_ids, int32_t* __restrict__ adv_n_out, int max_out) {
+    __shared__ uint64_t keys[1024];
+    const int row = blockIdx.x;
+    const float t = temperature[row];
+    const bool sampled = t > 0.f;                                   // block-uniform
+    for (int i = threadIdx.x; i < 1024; i += 256) keys[i] = i < n_in ? in_keys[row * in_stride + i] : 0;
+    if (sampled) smp_sort1024(keys); else smp_max1024(keys);
+    if (threadIdx.x >= 64) return;
+    const int lane = threadIdx.x;
+    const uint32_t ctr = counter != nullptr ? (uint32_t)counter[row] : 0u;
+    float* pr = prob_out != nullptr ? prob_out + (int64_t)row * 2 * SMP_CAND : nullptr;
+    int tok;
+    if (sampled) {
+        int k = top_k[row];
+        k = k < 1 ? 1 : (k > SMP_CAND ? SMP_CAND : k);
+        const float p = fminf(fmaxf(top_p[row], 1.17549435e-38f), 1.0f);
+        tok = smp_draw_wave(keys, lane, 1.0f / t, k, p, seed[row], ctr, pr);
+    } else {
+        tok = smp_idx(keys[0]);
+        if (pr != nullptr) { pr[lane] = lane == 0 ? 1.f : 0.f; ((int*)(pr + 64))[lane] = lane == 0 ? tok : -1; }
+    }
+    if (lane == 0) {
+        out[row] = (int64_t)tok;
+        if (adv_pos != nullptr) {
+            const int n = adv_n_out[row];
+            if (n < max_out) adv_out_ids[(int64_t)row * max_out + n] = (int64_t)tok;
+            adv_n_out[row] = n + 1;
+            adv_pos[row] = (int32_t)ctr + 1;
+        }
+    }
 }
 
 // ---- any top_k (round 4): exact selection without a candidate cut ----------------------------------------------------------------------------
@@ -267,11 +339,40 @@ int launch_sample(const float* logits, int n, float temperature, int top_k, floa
     VILA_REQUIRE(per1 <= 1024, "sample: vocabulary of %d exceeds %d x 1024 entries", n, SMP_S1_BLOCKS);
     uint64_t* c1 = (uint64_t*)workspace;
     uint64_t* c2 = c1 + SMP_S1_BLOCKS * SMP_CAND;
-    hipLaunchKernelGGL(smp_select_kernel, dim3(SMP_S1_BLOCKS), dim3(256), 0, s, logits, (const uint64_t*)nullptr, n, per1, c1);
+    hipLaunchKernelGGL(smp_select_kernel, dim3(SMP_S1_BLOCKS), dim3(256), 0, s, logits, (const uint64_t*)nullptr, n, per1, c1, (int64_t)0, (int64_t)0, (const float*)nullptr);
     VILA_LAUNCH_CHECK();
-    hipLaunchKernelGGL(smp_select_kernel, dim3(SMP_S2_BLOCKS), dim3(256), 0, s, (const float*)nullptr, (const uint64_t*)c1, SMP_S1_BLOCKS * SMP_CAND, 1024, c2);
+    hipLaunchKernelGGL(smp_select_kernel, dim3(SMP_S2_BLOCKS), dim3(256), 0, s, (const float*)nullptr, (const uint64_t*)c1, SMP_S1_BLOCKS * SMP_CAND, 1024, c2, (int64_t)0, (int64_t)0, (const float*)nullptr);
     VILA_LAUNCH_CHECK();
     hipLaunchKernelGGL(smp_final_kernel, dim3(1), dim3(256), 0, s, (const uint64_t*)c2, SMP_S2_BLOCKS * SMP_CAND, 1.0f / temperature, top_k, top_p, seed, seed_dev, counter, out, prob_out);
+    VILA_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- the batched sampler: one choice per row of logits [n][vocab] in three launches whatever n ------------------------------------------------
+// Rows lie on blockIdx.y.  Stage 1 cuts a row into cdiv(vocab, 1024) slices of (almost) 1024 logits — full sorts, where the solo path's fixed
+// 256 slices sort 594 logits and 430 pads each — stage 2 sorts 1024 candidates per block, stage 3 is one block per row.  The top-64 set under the
+// strict key order does not depend on the cut, and stage 3 draws with the solo sampler's own arithmetic (smp_draw_wave).
+static inline int smpb_s1(int vocab) { return cdiv(vocab, 1024); }
+static inline int smpb_s2(int vocab) { return cdiv(smpb_s1(vocab) * SMP_CAND, 1024); }
+size_t sample_batch_workspace_bytes(int n) { return (size_t)(n > 0 ? n : 0) * (SMP_S1_BLOCKS + SMP_S2_BLOCKS) * SMP_CAND * sizeof(uint64_t) + 256; }
+
+int launch_sample_batch(const float* logits, int64_t ld_logits, int n, int vocab, const BatchSampling& sp, const int32_t* counter, int64_t* out, void* workspace,
+                        float* dist_out, int32_t* adv_pos, int64_t* adv_out_ids, int32_t* adv_n_out, int max_out, hipStream_t s) {
+    VILA_REQUIRE(n >= 1 && n <= 16, "sample_batch: 1..16 rows (got %d)", n);
+    VILA_REQUIRE(vocab > 0 && ld_logits >= vocab, "sample_batch: row stride %lld is below the vocabulary %d", (long long)ld_logits, vocab);
+    VILA_REQUIRE(smpb_s1(vocab) <= SMP_S1_BLOCKS, "sample_batch: vocabulary of %d exceeds %d x 1024 entries", vocab, SMP_S1_BLOCKS);
+    VILA_REQUIRE(sp.temperature != nullptr && sp.top_k != nullptr && sp.top_p != nullptr && sp.seed != nullptr, "sample_batch: a per-row parameter array is NULL");
+    VILA_REQUIRE(adv_pos == nullptr || (adv_out_ids != nullptr && adv_n_out != nullptr && max_out >= 1), "sample_batch: the state advance needs out_ids and n_out");
+    const int s1 = smpb_s1(vocab), s2 = smpb_s2(vocab), per1 = cdiv(vocab, s1);
+    uint64_t* c1 = (uint64_t*)workspace;
+    uint64_t* c2 = c1 + (size_t)n * SMP_S1_BLOCKS * SMP_CAND;
+    hipLaunchKernelGGL(smp_select_kernel, dim3(s1, n), dim3(256), 0, s, logits, (const uint64_t*)nullptr, vocab, per1, c1, ld_logits, (int64_t)s1 * SMP_CAND, sp.temperature);
+    VILA_LAUNCH_CHECK();
+    hipLaunchKernelGGL(smp_select_kernel, dim3(s2, n), dim3(256), 0, s, (const float*)nullptr, (const uint64_t*)c1, s1 * SMP_CAND, 1024, c2, (int64_t)s1 * SMP_CAND,
+                       (int64_t)s2 * SMP_CAND, sp.temperature);
+    VILA_LAUNCH_CHECK();
+    hipLaunchKernelGGL(smp_batch_final_kernel, dim3(n), dim3(256), 0, s, (const uint64_t*)c2, s2 * SMP_CAND, (int64_t)s2 * SMP_CAND, sp.temperature, sp.top_k, sp.top_p, sp.seed,
+                       counter, out, dist_out, adv_pos, adv_out_ids, adv_n_out, max_out);
     VILA_LAUNCH_CHECK();
     return 0;
 }

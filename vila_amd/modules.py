@@ -561,10 +561,17 @@ class HipQwen2ForCausalLM(_HipModule):
                                        ops._stream()), "vila_llm_decode_step")
 
     # ---- batched greedy generate: one weight pass per step for up to 16 sequences (vila_llm_decode_step_batch) -----------------------
-    def _can_batch_decode(self, inputs_embeds, attention_mask, max_new_tokens, do_sample, forced_ids, return_logits, cache) -> bool:
+    def _can_batch_decode(self, inputs_embeds, attention_mask, max_new_tokens, do_sample, forced_ids, return_logits, cache,
+                          batch_sample: bool = False, top_k: int = 50) -> bool:
+        """The greedy batched step serves a padded batch; with batch_sample (opt-in) the same holds for a sampled batch whose top_k the
+        batched sampler serves (1..64), teacher forcing included."""
         c = self.lcfg
         Bn, S = inputs_embeds.shape[0], inputs_embeds.shape[1]
-        return (not do_sample and forced_ids is None and not return_logits and cache is None and self.can_batch_decode_step() and
+        if do_sample:
+            ok = batch_sample and 1 <= top_k <= 64
+        else:
+            ok = forced_ids is None and not return_logits
+        return (ok and cache is None and self.can_batch_decode_step() and
                 max_new_tokens >= 1 and (self._w4_batched() or self._qkv_fused()) and 2 <= Bn <= 16 and c.hidden_size % 64 == 0 and
                 c.intermediate_size % 64 == 0 and ((S + max_new_tokens + 255) // 256) * 256 <= 2048)
 
@@ -588,20 +595,23 @@ class HipQwen2ForCausalLM(_HipModule):
                 return False
         return True
 
-    def _batch_session(self, n: int, max_ctx: int, max_new_tokens: int):
+    def _batch_session(self, n: int, max_ctx: int, max_new_tokens: int, sampling: bool = False):
+        """sampling=True: the session owns per-row sampling parameters on the device (temperature / top_k / top_p / seed, every row greedy
+        until `_batch_set_sampling` says otherwise) and steps through the `_sample` entry points: one captured graph for any mix of rows."""
         w4 = self._w4_batched()
         if not w4:
             self._require_bf16("the batched decode")
         # a W4 session's graph bakes the int4 buffers' pointers: a re-quantise must not replay it
         q4 = self._w4.mats[0]["down"].q.data_ptr() if w4 else None
-        key = (n, max_ctx, max_new_tokens, self.model.embed_tokens.weight.data_ptr(), _get(self, "model.layers.0.mlp.down_proj.weight").data_ptr(), q4)
+        key = (n, max_ctx, max_new_tokens, bool(sampling), self.model.embed_tokens.weight.data_ptr(),
+               _get(self, "model.layers.0.mlp.down_proj.weight").data_ptr(), q4)
         st = getattr(self, "_bdecode", None)
         if st is not None and st.key == key:
             return st
         if st is not None and st.graph is not None:
             _lib.load().vila_graph_destroy(st.graph)
         dev, lib, w = self.device, _lib.load(), self._struct()
-        st = SimpleNamespace(key=key, graph=None)
+        st = SimpleNamespace(key=key, graph=None, sampling=bool(sampling), sp=None)
         with torch.inference_mode(False):
             st.cache = self.new_cache(max_ctx, n_slots=n)
             st.pos = torch.zeros(n, device=dev, dtype=torch.int32)
@@ -610,6 +620,13 @@ class HipQwen2ForCausalLM(_HipModule):
             st.n_out = torch.zeros(n, device=dev, dtype=torch.int32)
             st.logits = torch.zeros((n, self.lcfg.vocab_size), device=dev, dtype=torch.float32)
             ws_bytes = lib.vila_llm_decode_batch_w4_workspace_bytes if w4 else lib.vila_llm_decode_batch_workspace_bytes
+            if sampling:
+                ws_bytes = lib.vila_llm_decode_batch_w4_sample_workspace_bytes if w4 else lib.vila_llm_decode_batch_sample_workspace_bytes
+                st.s_temperature = torch.zeros(n, device=dev, dtype=torch.float32)          # 0 = greedy row
+                st.s_top_k = torch.full((n,), 50, device=dev, dtype=torch.int32)
+                st.s_top_p = torch.ones(n, device=dev, dtype=torch.float32)
+                st.s_seed = torch.zeros(n, device=dev, dtype=torch.int64)                   # bit patterns of uint64 seeds
+                st.sp = _lib.VilaBatchSampling(st.s_temperature.data_ptr(), st.s_top_k.data_ptr(), st.s_top_p.data_ptr(), st.s_seed.data_ptr())
             st.ws = torch.empty((ws_bytes(C.byref(w.shape), n),), device=dev, dtype=torch.uint8)
         st.c = _lib.VilaDecodeBatch(n, st.pos.data_ptr(), st.token.data_ptr(), st.out_ids.data_ptr(), st.n_out.data_ptr(), max(max_new_tokens, 1),
                                     st.logits.data_ptr())
@@ -618,6 +635,15 @@ class HipQwen2ForCausalLM(_HipModule):
         return st
 
     def _batch_step(self, st) -> None:
+        if st.sampling:
+            if self._w4_batched():
+                check(_lib.load().vila_llm_decode_step_batch_w4_sample(C.byref(self._struct()), self._w4.ptr, C.byref(st.cache.c), C.byref(st.c),
+                                                                       st.ws.data_ptr(), st.ws.numel(), C.byref(st.sp), ops._stream()),
+                      "vila_llm_decode_step_batch_w4_sample")
+                return
+            check(_lib.load().vila_llm_decode_step_batch_sample(C.byref(self._struct()), C.byref(st.cache.c), C.byref(st.c), st.ws.data_ptr(),
+                                                                st.ws.numel(), C.byref(st.sp), ops._stream()), "vila_llm_decode_step_batch_sample")
+            return
         if self._w4_batched():
             check(_lib.load().vila_llm_decode_step_batch_w4(C.byref(self._struct()), self._w4.ptr, C.byref(st.cache.c), C.byref(st.c), st.ws.data_ptr(),
                                                             st.ws.numel(), ops._stream()), "vila_llm_decode_step_batch_w4")
@@ -629,14 +655,43 @@ class HipQwen2ForCausalLM(_HipModule):
     # `vila_llm_decode_step_batch` takes per-row positions / output counters, so admission is host work: prefill the newcomer alone into its
     # KV slot, set the row's position and first token, replay the same captured graph.  A free row idles at positions 0..15 of its own slot
     # (re-wound after every chunk), which costs nothing extra: the step streams the weights once whatever the number of live rows.
-    def batch_open(self, n_slots: int, max_ctx: int = 2048, max_new_tokens: int = 1024):
+    @staticmethod
+    def _check_batch_sampling(sampling, what: str):
+        """(temperature, top_k, top_p, seed) of ONE row of a sampling batch session, validated where the values are known (the kernel only
+        clamps).  The batched sampler serves top_k in 1..64."""
+        temperature, top_k, top_p, seed = float(sampling[0]), int(sampling[1]), float(sampling[2]), int(sampling[3])
+        if temperature <= 0:
+            raise ValueError(f"`temperature` (={temperature}) has to be a strictly positive float, otherwise your next token scores will be invalid.")
+        if top_k < 0:
+            raise ValueError(f"`top_k` has to be a non-negative integer, but is {top_k}")
+        if not 1 <= top_k <= 64:
+            raise ValueError(f"{what}: the batched sampler serves top_k in 1..64 (got {top_k}); such a request runs solo")
+        if not 0.0 < top_p <= 1.0:
+            raise ValueError(f"`top_p` has to be a float > 0 and <= 1, but is {top_p}")
+        return temperature, top_k, top_p, seed
+
+    @staticmethod
+    def _batch_set_sampling(st, slot: int, sampling) -> None:
+        """Write one row's sampling parameters (None = greedy row) into the session's device arrays: the next replay reads them."""
+        t, k, p, seed = (0.0, 50, 1.0, 0) if sampling is None else sampling
+        st.s_temperature[slot:slot + 1].fill_(float(t))
+        st.s_top_k[slot:slot + 1].fill_(int(k))
+        st.s_top_p[slot:slot + 1].fill_(float(p))
+        st.s_seed[slot:slot + 1].fill_(_as_i64(seed))
+
+    def batch_open(self, n_slots: int, max_ctx: int = 2048, max_new_tokens: int = 1024, sampling: bool = False):
+        """Open (or re-use) the batched-decode session of `n_slots` rows with its captured step.  sampling=False: the greedy step.  sampling=True:
+        the step picks per row from device-resident parameters, so the ONE captured graph serves any mix of greedy and sampled rows
+        (`batch_admit(..., sampling=)`); the flag is part of the session key."""
         if not self._w4_batched():
             self._require_bf16("batch_open")
         if not (1 <= n_slots <= 16 and max_ctx <= 2048 and self.can_batch_decode_step() and (self._w4_batched() or self._qkv_fused())):
             raise ValueError("batch_open: the batched decode step serves 1..16 rows of a head-dim-128 model (bf16, or quantize_w4(batch_decode=True)) "
                              "with caches <= 2048 positions")
-        st = self._batch_session(max(n_slots, 2), max_ctx, max_new_tokens)
+        st = self._batch_session(max(n_slots, 2), max_ctx, max_new_tokens, sampling)
         st.pos.zero_(); st.n_out.zero_(); st.token.zero_()
+        if st.sampling:
+            st.s_temperature.zero_()                                   # every row starts greedy (idle)
         if st.graph is None:
             lib = _lib.load()
             torch.cuda.current_stream().synchronize()
@@ -653,9 +708,15 @@ class HipQwen2ForCausalLM(_HipModule):
                 st.pos.zero_(); st.n_out.zero_(); st.token.zero_()
         return st
 
-    def batch_admit(self, st, slot: int, embeds: torch.Tensor) -> int:
+    def batch_admit(self, st, slot: int, embeds: torch.Tensor, sampling=None) -> int:
         """Prefill ONE sequence [S, H] into KV slot `slot` of the open batch and make the row live: position S, first token = argmax of the
-        prefill's last row (returned), output counter 0."""
+        prefill's last row (returned), output counter 0.  sampling = (temperature, top_k in 1..64, top_p, seed), sampling sessions only: the
+        row samples — its parameters go to the device arrays, its first token is drawn from the prefill's last row with counter S - 1 (as the
+        solo generate draws it), the steps draw with the position of the token they consume.  None = greedy row."""
+        if sampling is not None:
+            if not st.sampling:
+                raise ValueError("batch_admit: a sampled row needs a session opened with batch_open(sampling=True)")
+            sampling = self._check_batch_sampling(sampling, "batch_admit")
         S = int(embeds.shape[0])
         if S + 1 > st.cache.max_ctx:
             raise ValueError(f"KV cache too small: {st.cache.max_ctx} < {S} + 1")
@@ -666,7 +727,10 @@ class HipQwen2ForCausalLM(_HipModule):
         cu = torch.tensor([0, S], device=dev, dtype=torch.int32)
         last = torch.full((1,), S - 1, device=dev, dtype=torch.int32)
         r = self.prefill_packed(embeds.to(self.dtype), pos, cu, S, cache=st.cache, seq_of_tok=seq, last_rows=last)
-        first = ops.argmax(r.last_logits[0])
+        first = (ops.argmax(r.last_logits[0]) if sampling is None else
+                 ops.sample(r.last_logits[0], sampling[0], sampling[1], sampling[2], sampling[3], counter=last))
+        if st.sampling:
+            self._batch_set_sampling(st, slot, sampling)
         st.pos[slot:slot + 1].fill_(S)
         st.n_out[slot:slot + 1].zero_()
         st.token[slot:slot + 1].copy_(first)
@@ -688,14 +752,21 @@ class HipQwen2ForCausalLM(_HipModule):
             idx = torch.tensor(slots, device=st.pos.device, dtype=torch.int64)
             st.pos.index_fill_(0, idx, 0)
             st.n_out.index_fill_(0, idx, 0)
+            if st.sampling:
+                st.s_temperature.index_fill_(0, idx, 0.0)              # an idle row is a greedy row
 
     def _generate_batch(self, inputs_embeds, attention_mask, max_new_tokens, eos_token_id, pad_token_id, use_graph: bool = True,
-                        forced_ids: Optional[torch.Tensor] = None, return_logits: bool = False):
+                        forced_ids: Optional[torch.Tensor] = None, return_logits: bool = False, sampling=None):
         """The padded batch as ONE packed prefill (every row into its own KV-cache slot) + batched decode steps: the weights are streamed
         once per step for all rows.  Returns [B, n_new] right-padded with pad_token_id behind each row's EOS, like HF.
         forced_ids [B, n_new] / return_logits: teacher forcing for the parity tests (eager launches; the ids fed after step t are
-        forced_ids[:, t]); returns (argmax ids [B, n_new], logits [n_new, B, V] fp32)."""
+        forced_ids[:, t]); returns (argmax ids [B, n_new], logits [n_new, B, V] fp32).
+        sampling: None (greedy session) or one entry per row, (temperature, top_k in 1..64, top_p, seed) or None for a greedy row: the batch
+        runs in a sampling session (`_batch_session(sampling=True)`), row b draws its first token with counter len_b - 1 and every step with
+        the position of the token it consumes; under teacher forcing the returned ids are the ones each step CHOSE."""
         ops._need(inputs_embeds, dtype=None, name="inputs_embeds")
+        if sampling is not None:
+            sampling = [None if sp is None else self._check_batch_sampling(sp, "generate(batch_sample=True)") for sp in sampling]
         Bn, S, H = inputs_embeds.shape
         dev = inputs_embeds.device
         mask = attention_mask.bool() if attention_mask is not None else torch.ones((Bn, S), dtype=torch.bool, device=dev)
@@ -709,9 +780,16 @@ class HipQwen2ForCausalLM(_HipModule):
         seq = torch.cat([torch.full((n,), b, dtype=torch.int32) for b, n in enumerate(lens)]).to(dev)
         last = torch.tensor([c - 1 for c in cu_h[1:]], device=dev, dtype=torch.int32)
         max_ctx = ((max(lens) + max_new_tokens + 255) // 256) * 256
-        st = self._batch_session(Bn, max_ctx, max_new_tokens)
+        st = self._batch_session(Bn, max_ctx, max_new_tokens, sampling is not None)
         r = self.prefill_packed(packed, pos, cu, max(lens), cache=st.cache, seq_of_tok=seq, last_rows=last)
-        first = torch.cat([ops.argmax(r.last_logits[b]) for b in range(Bn)])
+        if sampling is None:
+            first = torch.cat([ops.argmax(r.last_logits[b]) for b in range(Bn)])
+        else:
+            ctr = torch.tensor([n - 1 for n in lens], device=dev, dtype=torch.int32)
+            first = torch.cat([ops.argmax(r.last_logits[b]) if sp is None else
+                               ops.sample(r.last_logits[b], sp[0], sp[1], sp[2], sp[3], counter=ctr[b:b + 1]) for b, sp in enumerate(sampling)])
+            for b, sp in enumerate(sampling):
+                self._batch_set_sampling(st, b, sp)
         st.pos.copy_(torch.tensor(lens, dtype=torch.int32))
         st.n_out.zero_()
         st.token.copy_(first)
@@ -728,7 +806,7 @@ class HipQwen2ForCausalLM(_HipModule):
                 for t in range(n_steps):
                     self._batch_step(st)
                     step_logits.append(st.logits[:Bn].float().clone())
-                    ids.append(torch.cat([ops.argmax(st.logits[b]) for b in range(Bn)]))
+                    ids.append(torch.cat([ops.argmax(st.logits[b]) for b in range(Bn)]) if sampling is None else st.token[:Bn].clone())
                     if forced_ids is not None and t + 1 < forced_ids.shape[1]:
                         st.token.copy_(forced_ids[:, t + 1].to(dev))
             st.stream.synchronize()
@@ -774,18 +852,26 @@ class HipQwen2ForCausalLM(_HipModule):
             out[b, :len(r_)] = torch.tensor(r_, dtype=torch.int64, device=dev)
         return out
 
+    def _fresh_seed(self) -> int:
+        """The seed of a sampled request that names none: torch's initial seed stepped once per request."""
+        self._sample_calls = getattr(self, "_sample_calls", 0) + 1
+        return (torch.initial_seed() + 0x9E3779B97F4A7C15 * self._sample_calls) & 0xFFFFFFFFFFFFFFFF
+
     @torch.no_grad()
     def generate(self, inputs_embeds: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, max_new_tokens: Optional[int] = None,
                  eos_token_id=None, do_sample: Optional[bool] = None, temperature: Optional[float] = None, top_k: Optional[int] = None,
                  top_p: Optional[float] = None, seed: Optional[int] = None, pad_token_id: Optional[int] = None, generation_config=None,
                  use_graph: bool = True, return_logits: bool = False, forced_ids: Optional[torch.Tensor] = None, cache=None,
-                 max_length: Optional[int] = None, streamer=None, **kw):
+                 max_length: Optional[int] = None, streamer=None, batch_sample: Optional[bool] = None, **kw):
         """`llm.generate(inputs_embeds=, attention_mask=, **generation_kwargs)` as called at llava_arch.py:833 (HF semantics: returns ONLY the
         new tokens, [B, n_new]).  Greedy search or sampling (do_sample: temperature / top_k / top_p, HF order, on the device); explicit
         keyword arguments override `generation_config` (HF GenerationConfig-like: do_sample, temperature, top_k, top_p, max_new_tokens,
         eos_token_id, pad_token_id).  The whole step (28 layers + lm_head + token choice + position advance) is one hipGraph replay; the host
         polls for EOS every 16 tokens.  A padded batch (B > 1) is served one sequence at a time through the same cache and graph (each row
         costs a batch-1 decode: weights are streamed once per row and token) and right-padded with pad_token_id like HF.
+        batch_sample (opt-in, also read from generation_config; default False): a padded batch of 2..16 rows with do_sample and top_k in 1..64
+        runs the batched step with its per-row sampler — one weight pass per step for all rows, row b seeded `seed + b` as the row-by-row loop
+        seeds it.  The batched step sums in another order than the solo step, so the ids are no longer those of the rows' solo runs.
         forced_ids = teacher forcing for margin-aware parity tests.
         streamer = HF's `generate(streamer=...)` contract (what server.py:243 streams from): `put(LongTensor[1])` once per new token — the EOS
         included, nothing for a prompt given as embeddings — as the host learns of them (every 16 graph replays), then `end()`; batch size 1."""
@@ -798,12 +884,20 @@ class HipQwen2ForCausalLM(_HipModule):
         max_new_tokens = int(pick(max_new_tokens, "max_new_tokens", 32))
         eos_token_id = pick(eos_token_id, "eos_token_id", None)
         pad_token_id = pick(pad_token_id, "pad_token_id", None)
+        batch_sample = bool(pick(batch_sample, "batch_sample", False))
         if do_sample and temperature <= 0:
             raise ValueError(f"`temperature` (={temperature}) has to be a strictly positive float, otherwise your next token scores will be invalid.")
         if do_sample and top_k < 0:
             raise ValueError(f"`top_k` has to be a non-negative integer, but is {top_k}")       # (0 = no top-k filter, like HF)
-        if inputs_embeds.shape[0] > 1 and self._can_batch_decode(inputs_embeds, attention_mask, max_new_tokens, do_sample, forced_ids, return_logits, cache):
-            return self._generate_batch(inputs_embeds, attention_mask, max_new_tokens, eos_token_id, pad_token_id, use_graph)
+        if inputs_embeds.shape[0] > 1 and self._can_batch_decode(inputs_embeds, attention_mask, max_new_tokens, do_sample, forced_ids, return_logits, cache,
+                                                                 batch_sample, top_k):
+            if not do_sample:
+                return self._generate_batch(inputs_embeds, attention_mask, max_new_tokens, eos_token_id, pad_token_id, use_graph)
+            if seed is None:
+                seed = self._fresh_seed()
+            rows = [(temperature, top_k, top_p, (int(seed) + b) & 0xFFFFFFFFFFFFFFFF) for b in range(inputs_embeds.shape[0])]
+            return self._generate_batch(inputs_embeds, attention_mask, max_new_tokens, eos_token_id, pad_token_id, use_graph, forced_ids,
+                                        return_logits, sampling=rows)
         if inputs_embeds.shape[0] > 1:
             rows = []
             for b in range(inputs_embeds.shape[0]):
@@ -820,8 +914,7 @@ class HipQwen2ForCausalLM(_HipModule):
         sampling = None
         if do_sample:
             if seed is None:
-                self._sample_calls = getattr(self, "_sample_calls", 0) + 1
-                seed = (torch.initial_seed() + 0x9E3779B97F4A7C15 * self._sample_calls) & 0xFFFFFFFFFFFFFFFF
+                seed = self._fresh_seed()
             sampling = (temperature, top_k, top_p, int(seed))
         ops._need(inputs_embeds, dtype=None, name="inputs_embeds")
         x = inputs_embeds[0]

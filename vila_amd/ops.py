@@ -231,6 +231,34 @@ def sample(logits: torch.Tensor, temperature: float = 1.0, top_k: int = 50, top_
     return out
 
 
+def sample_batch(logits: torch.Tensor, temperature: torch.Tensor, top_k: torch.Tensor, top_p: torch.Tensor, seed: torch.Tensor,
+                 counter: Optional[torch.Tensor] = None, return_dist: bool = False):
+    """`sample` for up to 16 rows at once (the pick of the batched decode step): logits [n, V] fp32 (rows may be strided), every parameter a
+    DEVICE tensor [n] — temperature f32 (<= 0: greedy row = argmax, ties to the lower index), top_k i32 in 1..64, top_p f32 in (0, 1], seed i64
+    (the bit pattern of a uint64), counter i32 (optional).  A sampled row gets bit for bit the token `sample` returns for that row.
+    -> token ids [n] i64 (and, on request, (probabilities [n, 64], token ids [n, 64] i32))."""
+    _need(logits, dtype=torch.float32, name="logits")
+    if logits.dim() != 2 or logits.stride(1) != 1:
+        raise ValueError("sample_batch: logits must be [n, vocab] with contiguous rows")
+    n, V = logits.shape
+    for name, t, dt in (("temperature", temperature, torch.float32), ("top_k", top_k, torch.int32), ("top_p", top_p, torch.float32),
+                        ("seed", seed, torch.int64)) + ((("counter", counter, torch.int32),) if counter is not None else ()):
+        _need(t, dtype=dt, name=name)
+        if t.numel() != n or not t.is_contiguous():
+            raise ValueError(f"sample_batch: {name} must be a contiguous tensor of {n} entries")
+    import ctypes as C
+    lib = _lib.load()
+    out = torch.empty((n,), device=logits.device, dtype=torch.int64)
+    ws = torch.empty((lib.vila_sample_batch_workspace_bytes(n),), device=logits.device, dtype=torch.uint8)
+    dist = torch.zeros((n, 128), device=logits.device, dtype=torch.float32) if return_dist else None
+    sp = _lib.VilaBatchSampling(temperature.data_ptr(), top_k.data_ptr(), top_p.data_ptr(), seed.data_ptr())
+    check(lib.vila_sample_batch_f32(logits.data_ptr(), logits.stride(0), n, V, C.byref(sp), _p(counter), out.data_ptr(), ws.data_ptr(), _p(dist),
+                                    _stream()), "sample_batch")
+    if return_dist:
+        return out, dist[:, :64].clone(), dist[:, 64:].contiguous().view(torch.int32)
+    return out
+
+
 def embed_tokens(table: torch.Tensor, ids: torch.Tensor) -> torch.Tensor:
     _need(table, name="embed table")
     ids = ids.to(device=table.device, dtype=torch.int64).contiguous()

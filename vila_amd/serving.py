@@ -515,10 +515,13 @@ class RequestBatcher:
 
 class HipBatchEngine:
     """The model side of `ContinuousBatcher`: KV slots of ONE open batched-decode session (`HipQwen2ForCausalLM.batch_open`), driven by
-    the batcher's worker thread only."""
+    the batcher's worker thread only.  sampling=True opens the session with per-row sampling (`batch_open(sampling=True)`): `admit` then takes
+    a row's (temperature, top_k, top_p, seed) and a `ContinuousBatcher(batch_sampled=True)` puts sampled requests into rows."""
 
-    def __init__(self, model, tokenizer, n_slots: int = 8, max_ctx: int = 2048, max_new_tokens: int = 1024, eos_token_id=None):
+    def __init__(self, model, tokenizer, n_slots: int = 8, max_ctx: int = 2048, max_new_tokens: int = 1024, eos_token_id=None,
+                 sampling: bool = False):
         self.model, self.tokenizer = model, tokenizer
+        self.sampling = bool(sampling)
         self.n_slots, self.max_ctx, self.max_new_tokens = int(n_slots), int(max_ctx), int(max_new_tokens)
         eos = _eos_of(tokenizer, eos_token_id)
         self.eos = set(eos) if isinstance(eos, (list, tuple)) else {eos}
@@ -527,8 +530,18 @@ class HipBatchEngine:
     def _session(self):
         llm = self.model.llm
         if self.st is None or getattr(llm, "_bdecode", None) is not self.st:       # first use, or the weights moved and the session was dropped
-            self.st = llm.batch_open(self.n_slots, self.max_ctx, self.max_new_tokens)
+            self.st = llm.batch_open(self.n_slots, self.max_ctx, self.max_new_tokens, sampling=True) if self.sampling else \
+                llm.batch_open(self.n_slots, self.max_ctx, self.max_new_tokens)
         return self.st
+
+    @property
+    def batches_sampled(self) -> bool:
+        """Whether a sampled request (top_k in 1..64) can take a row of this engine's batch."""
+        return self.sampling
+
+    def fresh_seed(self) -> int:
+        """The seed of a sampled request that names none, derived as `generate` derives it."""
+        return self.model.llm._fresh_seed()
 
     def fits(self, n_prompt_tokens: int, max_new_tokens: int) -> bool:
         return max_new_tokens <= self.max_new_tokens and n_prompt_tokens + max_new_tokens <= self.max_ctx
@@ -543,8 +556,10 @@ class HipBatchEngine:
         e, _, _ = self.model._embed(ids, media, media_config)
         return e[0]
 
-    def admit(self, slot: int, embeds) -> int:
-        return self.model.llm.batch_admit(self._session(), slot, embeds)
+    def admit(self, slot: int, embeds, sampling=None) -> int:
+        if sampling is None:
+            return self.model.llm.batch_admit(self._session(), slot, embeds)
+        return self.model.llm.batch_admit(self._session(), slot, embeds, sampling=sampling)
 
     def run(self, k: int) -> None:
         self.model.llm.batch_run(self._session(), k)
@@ -572,12 +587,19 @@ class ContinuousBatcher:
     worker admits waiting greedy requests into free rows (each newcomer is prefilled alone into its KV slot and joins the next step), retires
     rows at EOS / max_new_tokens and hands their slot to the next request — a request that arrives one step after a batch started waits for at
     most one chunk, not for the whole batch.  Requests the batched step cannot serve (sampling, replies or prompts beyond the slots' cache) run
-    solo on the same thread once the live rows have drained; arrival order is kept (a solo request at the head blocks later admissions)."""
+    solo on the same thread once the live rows have drained; arrival order is kept (a solo request at the head blocks later admissions).
+    batch_sampled=True (opt-in; needs an engine whose `batches_sampled` is true, i.e. `HipBatchEngine(sampling=True)`): a request with
+    temperature > 0 and top_k (default 50) in 1..64 takes a free row like a greedy one — the reference's default request (0.2 / 0.9) then
+    batches instead of stalling the line.  The trade: the batched step sums in another order than the solo step, so the ids of a sampled
+    request are no longer those of its solo run (same distribution, same seed -> same reply within the batched path).  A request without a
+    seed gets one derived as `generate` derives it.  top_k = 0 or > 64 stays solo."""
 
-    def __init__(self, engine, max_batch: int = 8, chunk: int = 8):
+    def __init__(self, engine, max_batch: int = 8, chunk: int = 8, batch_sampled: bool = False):
         import queue
         import threading
         self.engine = engine
+        self.batch_sampled = bool(batch_sampled) and bool(getattr(engine, "batches_sampled", False))
+        self._seedless = 0
         self.max_batch = int(max(1, min(16, max_batch, getattr(engine, "n_slots", max_batch))))
         self.chunk = int(max(1, chunk))
         self._q: "queue.Queue" = queue.Queue()
@@ -589,7 +611,8 @@ class ContinuousBatcher:
         self._thread.start()
 
     def submit(self, prompt, max_new_tokens: int = 128, system: Optional[str] = None, stream: Optional["TextStream"] = None, **gen):
-        """-> Future of the decoded reply.  gen: temperature / top_p / top_k / seed — a request with temperature > 0 is a solo one.
+        """-> Future of the decoded reply.  gen: temperature / top_p / top_k / seed — a request with temperature > 0 is a solo one, unless the
+        batcher was built with batch_sampled=True and the request's top_k lies in 1..64 (then it takes a row).
         stream: a `TextStream` that receives the request's tokens while the row is still decoding — its first token at admission, then
         the new ones after every chunk of steps (server.py:241-270 streams a reply as it is generated); `end()` when the row retires,
         `fail()` with the exception the future gets."""
@@ -616,6 +639,28 @@ class ContinuousBatcher:
     def _greedy(req) -> bool:
         t = req.gen.get("temperature")
         return not t or t <= 0
+
+    def _row_sampling(self, req):
+        """(temperature, top_k, top_p, seed) when the request samples AND the batched sampler serves it, else None."""
+        if not self.batch_sampled or self._greedy(req):
+            return None
+        g = req.gen
+        top_k = 50 if g.get("top_k") is None else int(g["top_k"])
+        if not 1 <= top_k <= 64:
+            return None
+        seed = g.get("seed")
+        if seed is None:                                               # once per request: kept in `gen`, so a retry of the admission re-uses it
+            fresh = getattr(self.engine, "fresh_seed", None)
+            if callable(fresh):
+                seed = int(fresh())
+            else:
+                self._seedless += 1
+                seed = (torch.initial_seed() + 0x9E3779B97F4A7C15 * self._seedless) & 0xFFFFFFFFFFFFFFFF
+            req.gen = dict(g, seed=seed)
+        return (float(g["temperature"]), top_k, 1.0 if g.get("top_p") is None else float(g["top_p"]), int(seed))
+
+    def _batchable(self, req) -> bool:
+        return self._greedy(req) or self._row_sampling(req) is not None
 
     @staticmethod
     def _fail(req, ex) -> None:
@@ -705,7 +750,7 @@ class ContinuousBatcher:
                     req = pending[0]
                     slot = None                                        # the KV slot this admission took, if it got that far
                     try:
-                        if not self._greedy(req) or req.gen.get("_solo"):
+                        if not self._batchable(req) or req.gen.get("_solo"):
                             break
                         e = eng.embed(req.prompt, req.system)
                         if not eng.fits(int(e.shape[0]), req.max_new) or req.max_new < 1:
@@ -713,7 +758,8 @@ class ContinuousBatcher:
                             break
                         pending.popleft()
                         slot = free.pop(0)
-                        first = eng.admit(slot, e)
+                        sampling = self._row_sampling(req)
+                        first = eng.admit(slot, e) if sampling is None else eng.admit(slot, e, sampling)
                         row = SimpleNamespace(req=req, toks=[first], read=0, sent=0, closed=False)
                         self.events.append(("admit", slot, steps, len(rows)))
                         self._emit(row, [first])
@@ -740,7 +786,7 @@ class ContinuousBatcher:
                             self.events.append(("admit_failed", slot, steps))
                         self._fail(req, ex)
                 if not rows:
-                    if pending and (not self._greedy(pending[0]) or pending[0].gen.get("_solo")):
+                    if pending and (not self._batchable(pending[0]) or pending[0].gen.get("_solo")):
                         req = pending.popleft()
                         gen = {k: v for k, v in req.gen.items() if k != "_solo" and v is not None}
                         self.events.append(("solo", steps))
@@ -812,11 +858,14 @@ def continuous_batching(model) -> bool:
 
 
 def create_app(model, tokenizer, model_name: str = "NVILA-8B", batch_window_s: Optional[float] = None, max_batch: int = 8,
-               stream_timeout_s: Optional[float] = 600.0):
+               stream_timeout_s: Optional[float] = 600.0, batch_sampled: bool = False):
     """FastAPI app with the reference's POST /chat/completions (server.py:171-290).  Import-time optional: needs fastapi + pydantic.
     batch_window_s: when set (any value), requests go through a batcher whose ONE worker thread owns the model: `ContinuousBatcher` (greedy
     requests join / leave the batched decode step between steps; sampled ones run solo on the same thread) where the model has the batched
-    step, else `RequestBatcher` (greedy requests that arrive within the window share a batch; the rest run under the batcher's lock)."""
+    step, else `RequestBatcher` (greedy requests that arrive within the window share a batch; the rest run under the batcher's lock).
+    batch_sampled=True (with a ContinuousBatcher only): sampled requests — the default request, temperature 0.2 / top_p 0.9 / top_k 50 — join
+    the batched step as rows instead of running solo.  The trade: the ids of a sampled request are no longer those of its solo run (the
+    batched step sums in another order); greedy requests are served exactly as before."""
     from fastapi import FastAPI
     from fastapi.responses import JSONResponse, StreamingResponse
 
@@ -824,8 +873,11 @@ def create_app(model, tokenizer, model_name: str = "NVILA-8B", batch_window_s: O
     app = FastAPI()
     batcher = None
     if batch_window_s is not None:
-        batcher = ContinuousBatcher(HipBatchEngine(model, tokenizer, n_slots=max_batch), max_batch=max_batch) if continuous_batching(model) else \
-            RequestBatcher(model, tokenizer, window_s=batch_window_s)
+        if continuous_batching(model):
+            engine = HipBatchEngine(model, tokenizer, n_slots=max_batch, sampling=True) if batch_sampled else HipBatchEngine(model, tokenizer, n_slots=max_batch)
+            batcher = ContinuousBatcher(engine, max_batch=max_batch, batch_sampled=batch_sampled)
+        else:
+            batcher = RequestBatcher(model, tokenizer, window_s=batch_window_s)
     app.state.batcher = batcher
 
     def _prompt_of(messages):
