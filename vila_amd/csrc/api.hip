@@ -324,7 +324,7 @@ extern "C" size_t vila_llm_prefill_w4_workspace_bytes(const VilaLlmShape* s, int
 
 // One projection of a decoder layer for ONE row as a decode GEMV (the batch-1 decode step, the pruned last layer of the prefill): the bf16
 // kernel on g (gemv.hip), or with int4 weights (w4) the W4A16 GEMV (gemv_w4.hip) on the same operands and epilogue.  bf16 mode 2 (x = the
-// merge of the decode attention's 256-key partials) is W4 mode 4; grid_cap is the bf16 kernel's alone.
+// merge of the decode attention's 256-key partials) is W4 mode 4.
 static int proj_gemv(const GemvArgs& g, bool w4, const void* wq, const void* wsz, hipStream_t s) {
     if (!w4) return launch_gemv(g, s);
     GemvW4Args a{};
@@ -511,9 +511,10 @@ extern "C" int vila_llm_prefill_w4(const VilaLlmWeights* w, const VilaLlmLayerW4
 // =================================================================================================
 static inline int dec_splits(int max_ctx) { return cdiv(max_ctx, 64); }
 // kernel launches of one vila_llm_decode_step: prologue + per layer {qkv, attention (1 launch up to 2048 cached positions, else
-// split-KV + merge), o_proj, gate/up, down} + lm_head + argmax x2 + advance
+// split-KV + merge), o_proj, gate/up, down} + lm_head (which also reduces each block's logits to one (max, index) pair) + the final pick, which
+// advances the state as well
 extern "C" int vila_llm_decode_launches(const VilaLlmShape* s, int max_ctx) {
-    return 1 + s->n_layers * (max_ctx <= 2048 ? 5 : 6) + 4;      // a sampled step: + 1 (three selection launches instead of two argmax stages)
+    return 1 + s->n_layers * (max_ctx <= 2048 ? 5 : 6) + 2;      // a sampled step: + 3 (three selection launches and the advance after lm_head)
 }
 extern "C" size_t vila_llm_decode_workspace_bytes(const VilaLlmShape* s, int max_ctx) {
     const size_t H = s->hidden, F = s->inter, QS = (size_t)s->q_heads * s->head_dim;
@@ -521,15 +522,15 @@ extern "C" size_t vila_llm_decode_workspace_bytes(const VilaLlmShape* s, int max
     size_t b = 0;
     b += 2 * align_up(H * 2, 256) + 2 * align_up(QS * 2, 256) + align_up(F * 2, 256);
     b += align_up(ns * QS * 4, 256) + align_up(ns * s->q_heads * 2 * 4, 256);
-    b += 2 * align_up(256 * 4, 256) + align_up((size_t)s->head_dim * 4, 256);
+    b += 2 * align_up((size_t)gemv_grid_blocks(s->vocab) * 4, 256) + align_up((size_t)s->head_dim * 4, 256);
     b += align_up(QS * 2, 256);
     b += align_up(sample_workspace_bytes(), 256);
     return b + 4096;
 }
 
-// decode attention variant (vila_decode_force_attn): 2 (default) = per-head blocks over 256-key slices, merged in the prologue of the o_proj GEMV
-// (512 blocks); 1 = the same with 256 o_proj blocks; 0 = one block per query head over the whole context + plain o_proj (round 1).
-// Measured at context 785..913 (bench.py): 328.7 / 335.7 / 342.0 tok/s for 0 / 1 / 2.
+// decode attention variant (vila_decode_force_attn): 1 or 2 (default) = per-head blocks over 256-key slices, merged in the prologue of the o_proj GEMV
+// (8 waves per CU; until the GEMVs went to one block per CU, 1 meant 256 o_proj blocks and 2 meant 512); 0 = one block per query head over the whole
+// context + plain o_proj (round 1).  Measured at context 785..913 (bench.py): 328.7 / 335.7 / 342.0 tok/s for 0 / 256 blocks / 512 blocks.
 static int g_decode_attn = -1;     // -1: not set yet -> environment VILA_DECODE_ATTN, else 2
 extern "C" void vila_decode_force_attn(int mode) { g_decode_attn = mode; }
 static int decode_attn_mode() {
@@ -589,8 +590,9 @@ static int decode_step_impl(const VilaLlmWeights* w, const VilaLlmLayerW4* ql, c
     bf16_t* act = a.take<bf16_t>(F);
     float* part_o = a.take<float>((size_t)ns * QS);
     float* part_ml = a.take<float>((size_t)ns * sh.q_heads * 2);
-    float* tv = a.take<float>(256);
-    int* ti = a.take<int>(256);
+    const int n_pick = gemv_grid_blocks(sh.vocab);               // one (max, index) pair per lm_head block
+    float* tv = a.take<float>(n_pick);
+    int* ti = a.take<int>(n_pick);
     float* rope_cs = a.take<float>(hd);
     bf16_t* ao = a.take<bf16_t>(QS);
     void* smp_ws = a.take<char>(sample_workspace_bytes());
@@ -628,7 +630,7 @@ static int decode_step_impl(const VilaLlmWeights* w, const VilaLlmLayerW4* ql, c
         VILA_TRY(launch_attn_decode(ad, s));
         GemvArgs o{};
         o.x = ao; o.W = B(L.wo); o.residual = cur; o.y = nxt; o.N = H; o.K = QS; o.mode = 0;
-        if (split256) { o.mode = 2; o.part_o = part_o; o.part_ml = part_ml; o.pos_ptr = st->pos; o.n_splits = cdiv(cache->max_ctx, 256); o.split_keys = 256; o.grid_cap = decode_attn_mode() == 2 ? 512 : 256; }
+        if (split256) { o.mode = 2; o.part_o = part_o; o.part_ml = part_ml; o.pos_ptr = st->pos; o.n_splits = cdiv(cache->max_ctx, 256); o.split_keys = 256; }
         VILA_TRY(proj_gemv(o, w4, Q.o_q, Q.o_sz, s));
         GemvArgs gu{};
         gu.x = nxt; gu.norm_w = B(L.ln2_w); gu.eps = sh.rms_eps; gu.W = B(L.w_gate); gu.W2 = B(L.w_up); gu.y = act; gu.N = F; gu.K = H; gu.mode = 1;
@@ -641,10 +643,16 @@ static int decode_step_impl(const VilaLlmWeights* w, const VilaLlmLayerW4* ql, c
     // stream is in `x`: o_proj writes x2 and down_proj writes x back, so every layer ends where it began.
     GemvArgs lm{};
     lm.x = x; lm.norm_w = B(w->norm_w); lm.eps = sh.rms_eps; lm.W = B(w->lm_head); lm.y_f32 = st->logits; lm.N = sh.vocab; lm.K = H; lm.mode = 0;
+    // greedy: every lm_head block also reduces its rows to one (max, index) pair, and one small launch merges the pairs, writes the token and
+    // advances the state; sampled: the sampler reads the logits, then the advance
+    if (sp == nullptr) { lm.amax_v = tv; lm.amax_i = ti; }
     VILA_TRY(launch_gemv(lm, s));
-    if (sp != nullptr) VILA_TRY(launch_sample(st->logits, sh.vocab, sp->temperature, sp->top_k, sp->top_p, sp->seed, sp->seed_dev, st->pos, st->token, smp_ws, nullptr, s));
-    else VILA_TRY(launch_argmax(st->logits, sh.vocab, st->token, tv, ti, s));
-    VILA_TRY(launch_decode_advance(st->pos, st->token, st->out_ids, st->n_out, st->max_out, s));
+    if (sp != nullptr) {
+        VILA_TRY(launch_sample(st->logits, sh.vocab, sp->temperature, sp->top_k, sp->top_p, sp->seed, sp->seed_dev, st->pos, st->token, smp_ws, nullptr, s));
+        VILA_TRY(launch_decode_advance(st->pos, st->token, st->out_ids, st->n_out, st->max_out, s));
+    } else {
+        VILA_TRY(launch_argmax_pick_advance(tv, ti, n_pick, st->token, st->pos, st->out_ids, st->n_out, st->max_out, s));
+    }
     return 0;
 }
 

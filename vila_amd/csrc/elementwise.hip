@@ -2,6 +2,7 @@
 // All are vectorised 16 B per lane (guide G13) and keep statistics in fp32.
 #include <stdlib.h>
 #include "kernels.h"
+#include "gemv_common.h"
 
 // ------------------------------------------------------------------------------------------------
 // LayerNorm (SigLIP layer_norm1/2 eps 1e-6, modeling_siglip.py:723-725; projector nn.LayerNorm eps 1e-5,
@@ -499,19 +500,12 @@ int launch_embed_gather(const bf16_t* table, const int64_t* ids, bf16_t* out, in
 // greedy argmax over fp32 logits (HF GenerationMixin greedy, do_sample=False): first index of the maximum.
 // ------------------------------------------------------------------------------------------------
 #define ARGMAX_BLOCKS 256
-__device__ __forceinline__ void amax_merge(float& v, int& i, float v2, int i2) {
-    if (v2 > v || (v2 == v && i2 < i)) { v = v2; i = i2; }
-}
 __global__ __launch_bounds__(256) void argmax_stage1(const float* __restrict__ logits, int V, float* __restrict__ tv, int* __restrict__ ti) {
     __shared__ float sv[4];
     __shared__ int si[4];
     float best = -INFINITY; int bi = 0x7fffffff;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < V; i += ARGMAX_BLOCKS * 256) amax_merge(best, bi, logits[i], i);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float v2 = __shfl_xor(best, o, 64); const int i2 = __shfl_xor(bi, o, 64);
-        amax_merge(best, bi, v2, i2);
-    }
+    wave_amax(best, bi);
     if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = best; si[threadIdx.x >> 6] = bi; }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -523,17 +517,39 @@ __global__ __launch_bounds__(256) void argmax_stage2(const float* __restrict__ t
     __shared__ float sv[4];
     __shared__ int si[4];
     float best = tv[threadIdx.x]; int bi = ti[threadIdx.x];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float v2 = __shfl_xor(best, o, 64); const int i2 = __shfl_xor(bi, o, 64);
-        amax_merge(best, bi, v2, i2);
-    }
+    wave_amax(best, bi);
     if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = best; si[threadIdx.x >> 6] = bi; }
     __syncthreads();
     if (threadIdx.x == 0) {
         for (int w = 1; w < 4; ++w) amax_merge(best, bi, sv[w], si[w]);
         out[0] = (int64_t)bi;
     }
+}
+// The batch-1 greedy step's final pick: the lm_head GEMV has left one (max, index) pair per block (gemv_kernel, p.amax_v); merge the n pairs
+// with the same rule, write the token and advance the state (decode_advance_kernel's work): one launch for argmax_stage2 + the advance.
+__global__ __launch_bounds__(256) void argmax_pick_advance(const float* __restrict__ tv, const int* __restrict__ ti, int n, int64_t* __restrict__ token,
+                                                           int32_t* pos, int64_t* out_ids, int32_t* n_out, int max_out) {
+    __shared__ float sv[4];
+    __shared__ int si[4];
+    float best = -INFINITY; int bi = 0x7fffffff;
+    for (int i = threadIdx.x; i < n; i += 256) amax_merge(best, bi, tv[i], ti[i]);
+    wave_amax(best, bi);
+    if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = best; si[threadIdx.x >> 6] = bi; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < 4; ++w) amax_merge(best, bi, sv[w], si[w]);
+        token[0] = (int64_t)bi;
+        const int k = *n_out;
+        if (k < max_out) out_ids[k] = (int64_t)bi;
+        *n_out = k + 1;
+        *pos = *pos + 1;
+    }
+}
+int launch_argmax_pick_advance(const float* tv, const int* ti, int n, int64_t* token, int32_t* pos, int64_t* out_ids, int32_t* n_out, int max_out,
+                               hipStream_t s) {
+    hipLaunchKernelGGL(argmax_pick_advance, dim3(1), dim3(256), 0, s, tv, ti, n, token, pos, out_ids, n_out, max_out);
+    VILA_LAUNCH_CHECK();
+    return 0;
 }
 int launch_argmax(const float* logits, int V, int64_t* out, float* tmpv, int* tmpi, hipStream_t s) {
     hipLaunchKernelGGL(argmax_stage1, dim3(ARGMAX_BLOCKS), dim3(256), 0, s, logits, V, tmpv, tmpi);

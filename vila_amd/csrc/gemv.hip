@@ -29,10 +29,11 @@ __device__ __forceinline__ float dot8(const u32x4 w, const u32x4 x, float acc) {
 
 // stage x = merged split-KV attention output (flash-decoding combine fused into the o_proj GEMV):
 //   o[h][d] = sum_s exp(m_s - M) part_o[s][h][d] / sum_s exp(m_s - M) l_s ,  rounded to bf16 like the reference's attn output
+template <int NT>
 __device__ __forceinline__ void stage_x_attn(const float* __restrict__ part_o, const float* __restrict__ part_ml, int n_active,
                                              int nq, bf16_t* sx, float* wsm /* [n_active*nq] */) {
     const int tid = threadIdx.x;
-    for (int h = tid; h < nq; h += 256) {
+    for (int h = tid; h < nq; h += NT) {
         float M = -INFINITY;
         for (int s = 0; s < n_active; ++s) M = fmaxf(M, part_ml[((int64_t)s * nq + h) * 2]);
         float L = 0.f;
@@ -45,7 +46,7 @@ __device__ __forceinline__ void stage_x_attn(const float* __restrict__ part_o, c
     }
     __syncthreads();
     const int n4 = nq * 32;   // float4 chunks
-    for (int i = tid; i < n4; i += 256) {
+    for (int i = tid; i < n4; i += NT) {
         const int h = i >> 5;
         f32x4 o = (f32x4){0.f, 0.f, 0.f, 0.f};
         for (int s = 0; s < n_active; ++s) {
@@ -101,23 +102,25 @@ __device__ __forceinline__ void wave_rows_dot(const bf16_t* const (&wrow)[R], co
 // ------------------------------------------------------------------------------------------------
 // U = 16-B loads in flight per row and lane: 7 covers a whole K = 3584 row in ONE round trip (the short K=hidden GEMVs are
 // latency-bound), 4 is enough for the long rows (K = 18944) where many iterations pipeline anyway.
-template <int MODE, int U>   // MODE 0 plain, 1 gate/up, 2 plain with x = merged attention partials
-__global__ __launch_bounds__(256) void gemv_kernel(GemvArgs p, int n_groups, int ncu, int skew) {
+// NT = threads per block.  On the CU map ONE block of 256 x (blocks per CU of the balanced grid) threads runs per CU, so the activation is
+// loaded, normalised and written to LDS once per CU; its NT / 64 waves deal the CU's row groups (j = wave, stride NT / 64).
+template <int MODE, int U, int NT>   // MODE 0 plain, 1 gate/up, 2 plain with x = merged attention partials
+__global__ __launch_bounds__(NT) void gemv_kernel(GemvArgs p, int n_groups, int ncu, int skew) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     bf16_t* sx = (bf16_t*)smem;
     float* scratch = (float*)(smem + ((p.K * 2 + 15) & ~15));
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int nch = p.K >> 3;
     constexpr int R = (MODE == 1) ? 4 : 2;
-    // ncu > 0: the CU-balanced map (gemv_common.h CuMap; the grid is ncu x blocks-per-CU); ncu == 0: small grids, the plain grid-stride walk
+    // ncu > 0: the CU-balanced map (gemv_common.h CuMap; block = CU); ncu == 0: small grids, the plain grid-stride walk
+    constexpr int WPB = NT / 64;
     const CuMap cm(n_groups, ncu > 0 ? ncu : 8, ncu > 0 ? skew : 0);
-    const int cu = ncu > 0 ? (int)(blockIdx.x % ncu) : 0;
-    const int wpc = ncu > 0 ? (int)(gridDim.x / ncu) * 4 : 0;                 // waves dealing the CU's groups
+    const int cu = ncu > 0 ? (int)blockIdx.x : 0;
     const int cnt = ncu > 0 ? cm.count(cu) : 0;
-    int j = ncu > 0 ? (int)(blockIdx.x / ncu) * 4 + wave : 0;
-    const int stride = gridDim.x * 4;
-    int g = ncu > 0 ? (j < cnt ? cm.gid(cu, j) : n_groups) : blockIdx.x * 4 + wave;
-    auto next_group = [&]() { if (ncu > 0) { j += wpc; g = j < cnt ? cm.gid(cu, j) : n_groups; } else g += stride; };
+    int j = wave;                                                             // the block's WPB waves deal the CU's groups
+    const int stride = gridDim.x * WPB;
+    int g = ncu > 0 ? (j < cnt ? cm.gid(cu, j) : n_groups) : blockIdx.x * WPB + wave;
+    auto next_group = [&]() { if (ncu > 0) { j += WPB; g = j < cnt ? cm.gid(cu, j) : n_groups; } else g += stride; };
 
     auto rows_of = [&](int gg, const bf16_t* (&rows)[R]) {
         const int n = gg * 2;
@@ -132,6 +135,7 @@ __global__ __launch_bounds__(256) void gemv_kernel(GemvArgs p, int n_groups, int
     // Epilogue: after the wave reduction every lane holds the sums; lanes 0 and 1 each produce and store one of the wave's two adjacent
     // outputs (rows n, n + 1).
     float e_bias = 0.f, e_res = 0.f;
+    float best = -INFINITY; int bi = 0x7fffffff;     // p.amax_v: the largest fp32 output of this lane's rows so far (lanes 0 and 1)
     auto finish = [&](int gg, float (&acc)[R]) {
         const int n = gg * 2;
         bf16_t o = 0;
@@ -143,6 +147,7 @@ __global__ __launch_bounds__(256) void gemv_kernel(GemvArgs p, int n_groups, int
             float v = lane == 0 ? acc[0] : acc[1];
             v += e_bias;
             if (lane < 2 && n + lane < p.N && p.y_f32 != nullptr) p.y_f32[n + lane] = v;
+            if (p.amax_v != nullptr && lane < 2 && n + lane < p.N) amax_merge(best, bi, v, n + lane);
             if (p.residual != nullptr) v = bfround(v) + e_res;
             o = f2bf(v);
         }
@@ -172,9 +177,9 @@ __global__ __launch_bounds__(256) void gemv_kernel(GemvArgs p, int n_groups, int
     if constexpr (MODE == 2) {
         const int ks = p.split_keys > 0 ? p.split_keys : DEC_KS;
         const int n_active = (*p.pos_ptr + ks) / ks;             // ceil((pos+1)/ks)
-        stage_x_attn(p.part_o, p.part_ml, n_active, p.K >> 7, sx, scratch);
+        stage_x_attn<NT>(p.part_o, p.part_ml, n_active, p.K >> 7, sx, scratch);
     } else {
-        stage_x(p.x, p.norm_w, p.eps, p.K, sx, scratch);
+        stage_x<NT>(p.x, p.norm_w, p.eps, p.K, sx, scratch);
     }
     if (early) {
         float acc[R];
@@ -194,11 +199,25 @@ __global__ __launch_bounds__(256) void gemv_kernel(GemvArgs p, int n_groups, int
         wave_rows_dot<R, U>(rows, sx, p.K, lane, acc, 0);
         finish(g, acc);
     }
+    // the greedy pick's first stage (lm_head of the batch-1 step): this block's rows reduced to one (max, index) pair with argmax's tie rule
+    if constexpr (MODE == 0) {
+        if (p.amax_v != nullptr) {
+            __shared__ float sv[WPB];
+            __shared__ int si[WPB];
+            wave_amax(best, bi);
+            if (lane == 0) { sv[wave] = best; si[wave] = bi; }
+            __syncthreads();
+            if (threadIdx.x == 0) {
+                for (int w = 1; w < WPB; ++w) amax_merge(best, bi, sv[w], si[w]);
+                p.amax_v[blockIdx.x] = best; p.amax_i[blockIdx.x] = bi;
+            }
+        }
+    }
 }
 
-// Grid sizing for the HBM-bound GEMVs: a multiple of the 256 CUs (the dispatcher deals blocks round-robin, so 448 blocks
-// would leave 64 CUs with half the work of the others) and at most GEMV_BPC blocks per CU (4 = 16 waves = everything resident at once);
-// the blocks of a CU then deal that CU's row groups (CuMap, gemv_common.h).
+// Grid sizing for the HBM-bound GEMVs: one block per CU (the dispatcher deals blocks round-robin, so 448 blocks of 256 threads would leave
+// 64 CUs with half the work of the others) of up to GEMV_BPC x 256 threads (4 = 16 waves = everything resident at once); the waves of a
+// block deal that CU's row groups (CuMap, gemv_common.h).
 #define GEMV_BPC 4
 static int gemv_cu_count() {
     static thread_local int per_dev[16] = {0};
@@ -211,43 +230,57 @@ static int gemv_cu_count() {
     }
     return n;
 }
-// grid of an HBM-bound GEMV: (CUs) x (blocks per CU, 1..4) so that blocks b, b + CUs, ... share a CU and deal that CU's row groups among their
-// waves (*ncu_out = CUs); small problems (fewer groups than one block per CU would hold) keep one block per 4 groups and the plain walk (*ncu_out = 0)
-static inline int balanced_grid(int n_groups, int* ncu_out) {
+// grid of an HBM-bound GEMV: one block of 256 x *per_out (1..4) threads per CU (*ncu_out = CUs) whose waves deal that CU's row groups; small
+// problems (fewer groups than one 256-thread block per CU would hold) keep one 256-thread block per 4 groups and the plain walk (*ncu_out = 0)
+static inline int balanced_grid(int n_groups, int* ncu_out, int* per_out, int max_per = GEMV_BPC) {
     const int ncu = gemv_cu_count();
     int want = cdiv(n_groups, 4);
     if (want <= ncu) {
-        if (ncu_out) *ncu_out = 0;
+        *ncu_out = 0; *per_out = 1;
         return want;
     }
-    int per = cdiv(want, ncu); if (per > GEMV_BPC) per = GEMV_BPC;
-    if (ncu_out) *ncu_out = ncu;
-    return ncu * per;
+    int per = cdiv(want, ncu); if (per > max_per) per = max_per;
+    *ncu_out = ncu; *per_out = per;
+    return ncu;
+}
+int gemv_grid_blocks(int N) {
+    int ncu = 0, per = 1;
+    return balanced_grid(cdiv(N, 2), &ncu, &per);
+}
+
+template <int MODE, int U>
+static void gemv_launch(int per, int grid, size_t lds, hipStream_t s, const GemvArgs& a, int n_groups, int ncu, int skew) {
+    switch (per) {
+        case 1: hipLaunchKernelGGL((gemv_kernel<MODE, U, 256>), dim3(grid), dim3(256), lds, s, a, n_groups, ncu, skew); break;
+        case 2: hipLaunchKernelGGL((gemv_kernel<MODE, U, 512>), dim3(grid), dim3(512), lds, s, a, n_groups, ncu, skew); break;
+        case 3: hipLaunchKernelGGL((gemv_kernel<MODE, U, 768>), dim3(grid), dim3(768), lds, s, a, n_groups, ncu, skew); break;
+        default: hipLaunchKernelGGL((gemv_kernel<MODE, U, 1024>), dim3(grid), dim3(1024), lds, s, a, n_groups, ncu, skew); break;
+    }
 }
 
 int launch_gemv(const GemvArgs& a, hipStream_t s) {
     VILA_REQUIRE(a.K % 8 == 0 && a.K > 0 && a.N > 0, "gemv: K=%d must be a positive multiple of 8", a.K);
     VILA_REQUIRE((uintptr_t)a.W % 16 == 0, "gemv: weight pointer alignment");
+    VILA_REQUIRE(a.amax_v == nullptr || (a.mode == 0 && a.y_f32 != nullptr && a.amax_i != nullptr), "gemv: the fused pick needs mode 0 with fp32 output");
     const int n_groups = cdiv(a.N, 2);
-    int ncu = 0;
-    int grid = balanced_grid(n_groups, &ncu);
+    int ncu = 0, per = 1;
+    // mode 2: 8 waves per CU at most (the merge prologue; measured best)
+    const int grid = balanced_grid(n_groups, &ncu, &per, a.mode == 2 ? 2 : GEMV_BPC);
     size_t lds = ((size_t)a.K * 2 + 15) / 16 * 16 + 16;
     const bool short_k = a.K <= 3584;
     if (a.mode == 1) {
         VILA_REQUIRE(a.W2 != nullptr && a.y != nullptr && (uintptr_t)a.x % 16 == 0, "gemv: gate/up mode needs W2, bf16 y, aligned x");
         // skew 1: one gate/up group per CU moves from the odd XCDs to the even ones (profiles/r06_gemv_cu_map_ab.log: 337.8 -> 339.3 tok/s)
-        hipLaunchKernelGGL((gemv_kernel<1, 4>), dim3(grid), dim3(256), lds, s, a, n_groups, ncu, 1);
+        gemv_launch<1, 4>(per, grid, lds, s, a, n_groups, ncu, 1);
     } else if (a.mode == 2) {
         VILA_REQUIRE(a.part_o != nullptr && a.part_ml != nullptr && a.pos_ptr != nullptr && a.K % 128 == 0, "gemv: attention-merge mode needs partials");
         lds += (size_t)a.n_splits * (a.K / 128) * 4;
-        const int cap = a.grid_cap > 0 ? a.grid_cap : 256;           // the merge prologue is paid per block: default ~1 block per CU
-        if (grid > cap) grid = ncu > 0 ? (cap / ncu >= 1 ? (cap / ncu) * ncu : ncu) : cap;
-        if (short_k) hipLaunchKernelGGL((gemv_kernel<2, 7>), dim3(grid), dim3(256), lds, s, a, n_groups, ncu, 0);
-        else hipLaunchKernelGGL((gemv_kernel<2, 4>), dim3(grid), dim3(256), lds, s, a, n_groups, ncu, 0);
+        if (short_k) gemv_launch<2, 7>(per, grid, lds, s, a, n_groups, ncu, 0);
+        else gemv_launch<2, 4>(per, grid, lds, s, a, n_groups, ncu, 0);
     } else {
         VILA_REQUIRE((uintptr_t)a.x % 16 == 0, "gemv: x alignment");
-        if (short_k) hipLaunchKernelGGL((gemv_kernel<0, 7>), dim3(grid), dim3(256), lds, s, a, n_groups, ncu, 0);
-        else hipLaunchKernelGGL((gemv_kernel<0, 4>), dim3(grid), dim3(256), lds, s, a, n_groups, ncu, 0);
+        if (short_k) gemv_launch<0, 7>(per, grid, lds, s, a, n_groups, ncu, 0);
+        else gemv_launch<0, 4>(per, grid, lds, s, a, n_groups, ncu, 0);
     }
     VILA_LAUNCH_CHECK();
     return 0;
@@ -258,8 +291,8 @@ int launch_gemv(const GemvArgs& a, hipStream_t s) {
 // Group = 2 rows per wave: q/k heads -> the rotate-half pair {d, d+hd/2} of one head, v heads -> 2 consecutive rows.  cos/sin of the token's position come from the per-token table written by
 // decode_prologue_kernel (already rounded to bf16 like HF's cast of cos/sin to the activation dtype).
 // ------------------------------------------------------------------------------------------------
-template <int U>
-__global__ __launch_bounds__(256) void qkv_decode_kernel(QkvDecodeArgs p, int ncu) {
+template <int U, int NT>
+__global__ __launch_bounds__(NT) void qkv_decode_kernel(QkvDecodeArgs p, int ncu) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     bf16_t* sx = (bf16_t*)smem;
     float* scratch = (float*)(smem + ((p.K * 2 + 15) & ~15));
@@ -268,14 +301,14 @@ __global__ __launch_bounds__(256) void qkv_decode_kernel(QkvDecodeArgs p, int nc
     const int gph = half;                                      // groups (row pairs) per head
     const int n_groups = (p.nq + 2 * p.nkv) * gph;
     const int nch = p.K >> 3;
+    constexpr int WPB = NT / 64;
     const CuMap cm(n_groups, ncu > 0 ? ncu : 8, 0);
-    const int cu = ncu > 0 ? (int)(blockIdx.x % ncu) : 0;
-    const int wpc = ncu > 0 ? (int)(gridDim.x / ncu) * 4 : 0;
+    const int cu = ncu > 0 ? (int)blockIdx.x : 0;
     const int cnt = ncu > 0 ? cm.count(cu) : 0;
-    int j = ncu > 0 ? (int)(blockIdx.x / ncu) * 4 + wave : 0;
-    const int stride = gridDim.x * 4;
-    int g = ncu > 0 ? (j < cnt ? cm.gid(cu, j) : n_groups) : blockIdx.x * 4 + wave;
-    auto next_group = [&]() { if (ncu > 0) { j += wpc; g = j < cnt ? cm.gid(cu, j) : n_groups; } else g += stride; };
+    int j = wave;
+    const int stride = gridDim.x * WPB;
+    int g = ncu > 0 ? (j < cnt ? cm.gid(cu, j) : n_groups) : blockIdx.x * WPB + wave;
+    auto next_group = [&]() { if (ncu > 0) { j += WPB; g = j < cnt ? cm.gid(cu, j) : n_groups; } else g += stride; };
 
     int rows_i[2];
     const bf16_t* rows[2];
@@ -322,7 +355,7 @@ __global__ __launch_bounds__(256) void qkv_decode_kernel(QkvDecodeArgs p, int nc
     Batch<2, U> b0;
     const bool has = g < n_groups;
     if (has) { rows_of(g); load_batch<2, U>(rows, 0, lane, nch, b0); epi_fetch(g); }
-    stage_x(p.x, p.norm_w, p.eps, p.K, sx, scratch);
+    stage_x<NT>(p.x, p.norm_w, p.eps, p.K, sx, scratch);
     if (has) {
         float acc[2] = {0.f, 0.f};
         fma_batch<2, U>(b0, sx, 0, lane, nch, acc);
@@ -339,15 +372,24 @@ __global__ __launch_bounds__(256) void qkv_decode_kernel(QkvDecodeArgs p, int nc
     }
 }
 
+template <int U>
+static void qkv_launch(int per, int grid, size_t lds, hipStream_t s, const QkvDecodeArgs& a, int ncu) {
+    switch (per) {
+        case 1: hipLaunchKernelGGL((qkv_decode_kernel<U, 256>), dim3(grid), dim3(256), lds, s, a, ncu); break;
+        case 2: hipLaunchKernelGGL((qkv_decode_kernel<U, 512>), dim3(grid), dim3(512), lds, s, a, ncu); break;
+        case 3: hipLaunchKernelGGL((qkv_decode_kernel<U, 768>), dim3(grid), dim3(768), lds, s, a, ncu); break;
+        default: hipLaunchKernelGGL((qkv_decode_kernel<U, 1024>), dim3(grid), dim3(1024), lds, s, a, ncu); break;
+    }
+}
 int launch_qkv_decode(const QkvDecodeArgs& a, hipStream_t s) {
     VILA_REQUIRE(a.K % 8 == 0 && a.hd % 4 == 0 && a.rope_cs != nullptr, "qkv_decode: K=%d hd=%d", a.K, a.hd);
     const int n_groups = (a.nq + 2 * a.nkv) * (a.hd / 2);
     const size_t lds = ((size_t)a.K * 2 + 15) / 16 * 16 + 16;
     // one rotate-half pair per wave; K <= 3584: the whole row pair (14 x 16 B per lane) is in flight in ONE round trip
-    int ncu = 0;
-    const int grid = balanced_grid(n_groups, &ncu);
-    if (a.K <= 3584) hipLaunchKernelGGL(qkv_decode_kernel<7>, dim3(grid), dim3(256), lds, s, a, ncu);
-    else hipLaunchKernelGGL(qkv_decode_kernel<4>, dim3(grid), dim3(256), lds, s, a, ncu);
+    int ncu = 0, per = 1;
+    const int grid = balanced_grid(n_groups, &ncu, &per);
+    if (a.K <= 3584) qkv_launch<7>(per, grid, lds, s, a, ncu);
+    else qkv_launch<4>(per, grid, lds, s, a, ncu);
     VILA_LAUNCH_CHECK();
     return 0;
 }

@@ -55,6 +55,10 @@ int launch_rope_kv(bf16_t* qkv, const float* cs, const float* sn, const int32_t*
 int launch_embed_gather(const bf16_t* table, const int64_t* ids, bf16_t* out, int n, int H, int64_t vocab, hipStream_t s);
 int launch_copy_rows(const bf16_t* src, bf16_t* dst, const int32_t* src_row, const int32_t* dst_row, int n, int H, hipStream_t s);
 int launch_argmax(const float* logits, int V, int64_t* out, float* tmpv, int* tmpi, hipStream_t s);
+// final pick of the batch-1 greedy step: merges the n (max, index) pairs left by the lm_head GEMV (GemvArgs::amax_v), writes *token and advances
+// the state like launch_decode_advance
+int launch_argmax_pick_advance(const float* tv, const int* ti, int n, int64_t* token, int32_t* pos, int64_t* out_ids, int32_t* n_out, int max_out,
+                               hipStream_t s);
 // stochastic token choice (sample.hip): temperature -> top-k (1..64) -> top-p -> draw; counter = device scalar mixed into the RNG
 size_t sample_workspace_bytes();
 int launch_sample(const float* logits, int n, float temperature, int top_k, float top_p, uint64_t seed, const uint64_t* seed_dev, const int32_t* counter, int64_t* out,
@@ -111,9 +115,10 @@ struct GemvArgs {
     int N, K; int mode;       // 0 plain, 1 gate/up silu-mul, 2 plain with x = merge of the decode-attention partials
     const float* part_o; const float* part_ml; const int32_t* pos_ptr; int n_splits;   // mode 2
     int split_keys;           // mode 2: keys per partial slice (0 = the 64-key slices of attn_decode_partial)
-    int grid_cap;             // mode 2: upper bound of the grid (0 = 256 blocks)
+    float* amax_v; int* amax_i;   // mode 0 with y_f32, optional: one (max, index) pair of the fp32 outputs per block, [gemv_grid_blocks(N)]
 };
 int launch_gemv(const GemvArgs& a, hipStream_t s);
+int gemv_grid_blocks(int N);  // blocks of launch_gemv's grid for N rows in modes 0 and 1
 struct QkvDecodeArgs {
     const bf16_t* x; const bf16_t* norm_w; float eps;
     const bf16_t* Wqkv; const bf16_t* bqkv;   // fused [q+2kv][K], [q+2kv]
