@@ -32,6 +32,11 @@ void vila_gemm_force_group(int grp);
 /* the K-sliced GEMMs' reduce takes the next block's LayerNorm / RMSNorm along (prefill down_proj -> next input_layernorm, tower fc2 -> next
  * layer_norm1): 1 = on (default), 0 = separate norm launches (A/B and the parity test of the fused kernel); environment: VILA_FUSE_NORM */
 void vila_gemm_force_fuse_norm(int on);
+/* the launch plan of a bf16 GEMM under the current hooks, as one line of text ("family=... splits=... per=... full=... tail=... ex=... bm=... group=...
+ * sched=... ring=... pipe=... reduce=..."; csrc/gemm_plan.h has the fields).  Host only: launches nothing and asks the runtime for no device, so it works
+ * without a GPU.  ws_bytes = size of the fp32 workspace (0 = none given); offers: bit 0 = the next block's normalisation, bit 1 = the q/k/v RoPE + KV
+ * follow-up (what the prefill offers).  Returns the length written, -1 when buf_len is too small */
+int vila_gemm_plan_describe(int M, int N, int K, int epi, int out_f32, int a_cm, int b_cm, size_t ws_bytes, int offers, char* buf, int buf_len);
 /* LayerNorm / RMSNorm over rows wider than 1536 columns: every load (x, w, b) requested up front instead of x -> reduce -> w (elementwise.hip
  * norm_block_lat_kernel; bit-identical outputs; on by default since round 5): -1 = VILA_NORM_LAT from the environment (default 1), 0 = off, 1 = on */
 void vila_norm_force_lat(int on);

@@ -494,3 +494,79 @@ def test_gemm256_leftover_rows_ride_in_the_last_row_tile(ops, M):
         want = a2.float() @ wd.float().t() + res.float()
         out = ops.gemm(a2, wd, residual=res, ws=ws)                # under-filled grid + workspace -> K-sliced slabs + reduce
         assert rel_l2(out, want) < 4e-3 and rel_l2(out[lo:], want[lo:]) < 4e-3, f"split-K: {rel_l2(out, want):.3e} / {rel_l2(out[lo:], want[lo:]):.3e}"
+
+
+# rows of tests/golden/gemm_plan.json launched for real: one per kernel family of the launch plan (both hybrid forms, a fused gate/up row on the 256-wide
+# and on the register-staged kernel, the SFT dgrad / wgrad forms), and two rows with an offer, which only the prefill / the tower can launch: described only
+GEMM_PLAN_ROWS = [
+    "force_tile/4+ws", "nvila-lite-3b/M64/down+ws", "tower/14img/o_proj+ws", "nvila-lite-3b/M769/gateup+ws", "sft/nvila-lite-3b/dgrad_o_proj",
+    "sft/nvila-lite-3b/dgrad_o_proj+ws", "sft/nvila-lite-3b/wgrad_gate+ws", "nvila-lite-3b/M64/o_proj", "nvila-lite-3b/M64/o_proj+ws", "force_tile/1+ws",
+    "force_tile/2+ws", "force_tile/3+ws", "nvila-lite-3b/M64/gateup", "model/prefill_S769/l0_qkv", "model/tower_1img/l0_fc2",
+]
+GEMM_PLAN_FAMILIES = {"256", "256_sliced", "256_hybrid", "cm", "cm_sliced", "cm_hybrid", "ring", "ring_splitk", "reg128x128", "reg128x64", "reg256x128"}
+GEMM_KNOB_DEFAULTS = {"tile": 0, "sched": 0, "hybrid": 1, "bm": 0, "ex": -1, "group": -1, "fuse_norm": 1}
+
+
+def _gemm_plan_rows():
+    import json
+    import os
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "gemm_plan.json")) as f:
+        rows = {r["tag"]: r for r in json.load(f)["rows"]}
+    return [rows[t] for t in GEMM_PLAN_ROWS]
+
+
+def test_gemm_plan_rows_cover_every_family():
+    rows = _gemm_plan_rows()
+    assert {r["plan"]["family"] for r in rows} == GEMM_PLAN_FAMILIES
+    assert {r["plan"]["reduce"] for r in rows} == {"none", "plain", "norm", "rope", "tail", "gateup"}
+
+
+@pytest.mark.parametrize("tag", GEMM_PLAN_ROWS)
+def test_gemm_plan_describe_matches_the_recorded_launch_and_the_result_is_right(ops, tag):
+    """`vila_gemm_plan_describe` must state the launch written down for the row (tests/golden/gemm_plan.json; tests/test_gemm_plan_cpu.py pins the
+    whole file on the CPU), and the GEMM launched from that plan must meet this file's bound for a bf16 output: rel-L2 < 4e-3 against the fp32 product
+    (gate/up rows: against silu(a w^T) * (a w2^T) formed in fp32)."""
+    import ctypes
+    from vila_amd import _lib
+    lib = _lib.load()
+    r = _gemm_plan_rows()[GEMM_PLAN_ROWS.index(tag)]
+    M, N, K, a_cm, b_cm = r["M"], r["N"], r["K"], bool(r["a_cm"]), bool(r["b_cm"])
+    buf = ctypes.create_string_buffer(256)
+    out = ref = None
+    for k, v in r["knobs"].items():
+        getattr(lib, "vila_gemm_force_" + k)(v)
+    try:
+        n = lib.vila_gemm_plan_describe(M, N, K, r["epi"], r["out_f32"], int(a_cm), int(b_cm), r["ws_bytes"], r["offers"], buf, len(buf))
+        if not r["offers"]:
+            a = randn_bf16(*((K, M) if a_cm else (M, K)), seed=91)
+            w = randn_bf16(*((K, N) if b_cm else (N, K)), seed=92, scale=K ** -0.5)
+            ws = torch.empty(r["ws_bytes"] // 4, device="cuda", dtype=torch.float32) if r["ws_bytes"] else None
+            ref = (a.float().t() if a_cm else a.float()) @ (w.float() if b_cm else w.float().t())
+            if r["epi"] == 3:
+                w2 = randn_bf16(N, K, seed=93, scale=K ** -0.5)
+                ref = torch.nn.functional.silu(ref) * (a.float() @ w2.float().t())
+                out = ops.gemm(a, w, w2=w2, epi=3, ws=ws)
+            else:
+                out = ops.gemm_t(a, w, a_cm=a_cm, b_cm=b_cm, ws=ws) if (a_cm or b_cm) else ops.gemm(a, w, ws=ws)
+    finally:
+        for k in r["knobs"]:
+            getattr(lib, "vila_gemm_force_" + k)(GEMM_KNOB_DEFAULTS[k])
+    assert n > 0
+    got = dict(kv.split("=") for kv in buf.value.decode().split())
+    want = r["plan"]
+    said = {"family": got["family"], "grid": int(got["full"]), "slices": int(got["splits"]), "tail": int(got["tail"]), "ex": int(got["ex"]), "bm": int(got["bm"]),
+            "sched": int(got["sched"]), "ring": int(got["ring"]), "pipe": int(got["pipe"]), "reduce": got["reduce"]}
+    assert said == want, f"describe says {said}, the golden row says {want}"
+    if out is not None:
+        assert rel_l2(out, ref) < 4e-3, f"{tag}: rel={rel_l2(out, ref):.3e}"
+
+
+def test_gemm_plan_describe_refuses_what_launch_gemm_refuses():
+    """host only: a shape the launcher's argument checks reject (K % 8, N % 4, contraction-major rows % 8 or K < 128) has no plan to describe"""
+    import ctypes
+    from vila_amd import _lib
+    lib = _lib.load()
+    buf = ctypes.create_string_buffer(256)
+    for M, N, K, a_cm, b_cm in ((64, 64, 12, 0, 0), (64, 62, 64, 0, 0), (64, 68, 256, 0, 1), (64, 64, 64, 0, 1), (0, 64, 64, 0, 0)):
+        assert lib.vila_gemm_plan_describe(M, N, K, 0, 0, a_cm, b_cm, 0, 0, buf, len(buf)) > 0
+        assert buf.value.decode() == "family=unsupported", (M, N, K, a_cm, b_cm, buf.value)

@@ -140,6 +140,7 @@ PROTOTYPES = {
     "vila_gemm_force_ex": (None, [c_int]),
     "vila_gemm_force_group": (None, [c_int]),
     "vila_gemm_force_fuse_norm": (None, [c_int]),
+    "vila_gemm_plan_describe": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_size_t, c_int, C.c_char_p, c_int]),
     "vila_prefill_force_fusions": (None, [c_int, c_int]),
     "vila_norm_force_lat": (None, [c_int]),
     "vila_attn_force_fwd": (None, [c_int]),

@@ -14,7 +14,11 @@
 // issued before the MFMAs of tile t and written to LDS after them).  The epilogue goes through LDS so that the
 // residual read and the C write are full-row coalesced (8 / 16 B per lane).
 // Roofline: MFMA (2*M*N*K flop vs (M+N)*K*2 + M*N*2 bytes).
+#include <stdio.h>
+#include <stdlib.h>
 #include "kernels.h"
+#include "gemm_plan.h"
+#include "../../include/vila_hip_tuning.h"
 
 #define BK 64
 #define STG 68  // fp32 staging row stride (floats)
@@ -205,136 +209,98 @@ static int launch_cfg(const GemmArgs& a, hipStream_t s) {
     return 0;
 }
 
-bool gemm256_supported(const GemmArgs& a);
-int gemm256_tiles_m_of(int M);        // 256-row tiles under the extra-row-fragment policy (gemm256_kernel.h: M = 256 k + r, r <= 16 -> k tiles)
-int launch_gemm256(const GemmArgs& a, hipStream_t s);
-int launch_gemm256_splitk(const GemmArgs& a, int splits, float* slab, hipStream_t s);
-bool gemm_ring_supported(const GemmArgs& a);
-int launch_gemm_ring(const GemmArgs& a, int stages, hipStream_t s);
-int gemm_ring_splitk_slices(const GemmArgs& a);      // gemm_ring_splitk.hip: K-sliced 128x64 ring for short prompts (measured in round 5: the default for M < 512; VILA_RING_SPLITK=0 turns it off)
-int launch_gemm_ring_splitk(const GemmArgs& a, int splits, hipStream_t s);
-static int g_force_tile = 0;   // test / tuning hook: 0 auto, 1 = 128x128, 2 = 128x64, 3 = 256x128, 4 = 256x256 LDS-DMA kernel, 5 = split-K, 6 / 7 = 128x64 DMA ring with 4 / 3 stages, 8 = 128x128 DMA ring (2 stages), 11 = K-sliced 128x64 ring (needs a workspace), 12 / 13 / 14 = rings 7 / 8 / 6 with the PIPE 2 fragment schedule whatever VILA_RING_PIPE says, 15 / 16 / 17 = the same three with the plain schedule
-extern "C" void vila_gemm_force_tile(int t) { g_force_tile = t; }
-static int ring_splitk_env() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("VILA_RING_SPLITK"); v = (e && e[0] == '0') ? 0 : 1; }
-    return v;
+int launch_gemm256(const GemmArgs& a, const GemmPlan& p, hipStream_t s);              // gemm256.hip
+int launch_gemm256_splitk(const GemmArgs& a, const GemmPlan& p, hipStream_t s);
+int launch_gemm_ring(const GemmArgs& a, int ring, int pipe, hipStream_t s);           // gemm_ring.hip
+int launch_gemm_ring_splitk(const GemmArgs& a, int splits, hipStream_t s);            // gemm_ring_splitk.hip
+
+// ---- the tuning knobs (gemm_plan.h GemmKnobs): one struct, written by the hooks of vila_hip_tuning.h, its "ask the environment" values filled once ----
+static GemmKnobs g_gemm_knobs;
+extern "C" void vila_gemm_force_tile(int t) { g_gemm_knobs.force_tile = t; }
+extern "C" void vila_gemm_force_sched(int sched) { g_gemm_knobs.sched = sched; }
+extern "C" void vila_gemm_force_group(int grp) { g_gemm_knobs.group = grp; }
+extern "C" void vila_gemm_force_ex(int mode) { g_gemm_knobs.ex = mode; }
+extern "C" void vila_gemm_force_bm(int bm) { g_gemm_knobs.bm = bm; }
+extern "C" void vila_gemm_force_hybrid(int on) { g_gemm_knobs.hybrid = on; }
+extern "C" void vila_gemm_force_fuse_norm(int on) { g_gemm_knobs.fuse_norm = on ? 1 : 0; }
+static const GemmKnobs& gemm_knobs() {
+    GemmKnobs& k = g_gemm_knobs;
+    if (k.ex < 0) { const char* e = getenv("VILA_GEMM_EX"); k.ex = (e && e[0] >= '0' && e[0] <= '2') ? e[0] - '0' : 1; }
+    if (k.ring_splitk < 0) { const char* e = getenv("VILA_RING_SPLITK"); k.ring_splitk = (e && e[0] == '0') ? 0 : 1; }
+    if (k.ring_pipe < 0) { const char* e = getenv("VILA_RING_PIPE"); k.ring_pipe = (e && e[0] == '0') ? 0 : 2; }
+    if (k.fuse_norm < 0) { const char* e = getenv("VILA_FUSE_NORM"); k.fuse_norm = (e && e[0] == '0') ? 0 : 1; }
+    return k;
 }
-// Measured and rejected (tools/gemm_bench pol, profiles/r02_gemm_bench_policies.log): slicing K four ways for ONE under-filled round with a
-// long contraction (SFT down_proj forward / dgrad of gate and up: 182 tiles, 296 K-tiles -> 728 blocks = 2.84 rounds of a quarter of the
-// work).  The slabs (4 x 44 MB written and read) eat the gain: 488 -> 481, 522 -> 545, 559 -> 544 us.
+
+static GemmShape shape_of(const GemmArgs& a) {
+    return GemmShape{a.M, a.N, a.K, a.lda, a.ldw, a.epi, a.out_f32, a.a_cm, a.b_cm, a.ws != nullptr, a.ws_bytes,
+                     a.norm_out != nullptr && a.norm_w != nullptr, gemm_rope_offer(a)};
+}
+static bool gemm256_supported(const GemmArgs& a) { return gemm256_supported(shape_of(a)); }
+
+// One line of text for the plan of a problem under the current knobs: host only, launches nothing and asks the runtime for no device (packed
+// operands are assumed: lda / ldw = K, or the row count for a contraction-major operand).  offers: bit 0 = the next block's normalisation,
+// bit 1 = the q/k/v RoPE + KV follow-up.  Returns the length written, -1 when the buffer is too small.
+extern "C" int vila_gemm_plan_describe(int M, int N, int K, int epi, int out_f32, int a_cm, int b_cm, size_t ws_bytes, int offers, char* buf, int buf_len) {
+    const GemmShape h{M, N, K, a_cm ? M : K, b_cm ? N : K, epi, out_f32, a_cm, b_cm, ws_bytes > 0, ws_bytes, (offers & 1) != 0, (offers & 2) != 0};
+    if (!gemm_shape_ok(h)) {                        // launch_gemm would refuse it: never describe a launch that cannot happen
+        const int n = snprintf(buf, buf_len, "family=unsupported");
+        return (n >= 0 && n < buf_len) ? n : -1;
+    }
+    const GemmPlan p = gemm_plan(h, gemm_knobs());
+    const int n = snprintf(buf, buf_len, "family=%s splits=%d per=%d full=%d tail=%d ex=%d bm=%d group=%d sched=%d ring=%d pipe=%d reduce=%s",
+                           gemm_family_name(p.family), p.splits, p.per, p.n_full, p.n_tail, p.ex, p.bm, p.group, p.sched, p.ring, p.pipe, gemm_reduce_name(p.reduce));
+    return (n >= 0 && n < buf_len) ? n : -1;
+}
+
+// the register-staged kernels of this file
 template <int EPI, bool OUT_F32>
-static int launch_t(const GemmArgs& a, hipStream_t s) {
-    int sel = g_force_tile;
-    const int64_t tiles256 = (int64_t)gemm256_tiles_m_of(a.M) * cdiv(a.N, (EPI == EPI_GATEUP) ? 128 : 256);
-    if (sel == 4 || (sel == 0 && tiles256 >= 150)) {
-        if (gemm256_supported(a)) return launch_gemm256(a, s);
-        if (sel == 4) sel = 0;
-    }
-    // under-filled grid of 256^2 tiles (S = 769 prefill: 56 tiles for N = 3584): slice K over grid.y when a workspace is given
-    // (M >= 512 for the short contractions; a LONG contraction — down_proj, K = 18944 — is sliced at ANY M: at S = 289 (one image + a 32-token
-    // prompt, BASELINE configs[1]'s short prompt) the ring kernel walked 296 K-tiles per block, 149 us per layer, where 2 x 14 tiles x 8 slices
-    // take 57 + 11 us incl. the reduce: TTFT 13.2 -> 12.0 ms, profiles/r04_ttft_s289_ab.log; text-only prompts of 64 / 160 rows:
-    // profiles/r04_gemm_bench_presmall.log)
-    const int kt_all_ = cdiv(a.K, 64);
-    if ((sel == 0 || sel == 5) && EPI == EPI_NONE && !OUT_F32 && a.ws != nullptr && (a.M >= 512 || kt_all_ >= 128) && gemm256_supported(a)) {
-        const int kt = kt_all_;
-        // as many K-slices as keep every block resident at once (one 512-thread block per CU), at most 8, at least 8 K-tiles each;
-        // slices need not be equal (the last one takes the remainder): 42 tiles x 6 slices fills 252 CUs where 4 would fill 168
-        int splits = (int)(256 / tiles256);
-        if (splits > 8) splits = 8;
-        while (splits >= 2 && (cdiv(kt, splits) < 8 || (size_t)splits * a.M * a.N * 4 > a.ws_bytes)) --splits;
-        if (splits >= 2) splits = cdiv(kt, cdiv(kt, splits));      // drop empty trailing slices
-        if (splits < 2) splits = 0;
-        // K < 8192 (o_proj at S = 769): the DMA ring below does it in one launch at 557 TF/s vs 482 incl. the reduce
-        // ... unless the slices are many and still long (ViT fc2 of one image, K = 4304: 20 tiles x 8 slices; with COLD weights — what a
-        // forward pass sees — 45.6 -> 33.7 us, tools/gemm_bench precold; the warm numbers above hide that a lone tile's K loop runs at
-        // HBM latency)
-        // ... or the caller offers the next block's normalisation (o_proj of the prefill -> post-attention RMSNorm): the reduce then replaces
-        // the norm launch as well (ring 44.4 + norm 7.7 us against slices + fused reduce, round 6)
-        const bool norm_offer = a.norm_out != nullptr && a.norm_w != nullptr && a.N % 8 == 0 && a.N <= 16384 && splits >= 4;
-        // ... or the q/k/v projection's RoPE + KV scatter (72 tiles -> 54 with the extra row fragment, 4 slices: the reduce replaces rope_kv_kernel)
-        const bool rope_offer = gemm_rope_offer(a) && splits >= 4;
-        if (kt < 128 && sel == 0 && !(kt >= 64 && splits >= 6) && !norm_offer && !rope_offer) splits = 0;
-        // measured at M = 769 (tools/microbench.py prefill): N=3584,K=18944 233 -> 122 us; N=3584,K=3584 51 -> 41 us;
-        // N=4608 (72 tiles) only breaks even, so require at least 4 slices
-        if (splits >= 4 || (splits && sel == 5)) return launch_gemm256_splitk(a, splits, a.ws, s);
-    }
-    if (sel == 5) sel = 0;
-    if constexpr (EPI == EPI_NONE && !OUT_F32) {
-        if ((sel == 11 || (sel == 0 && ring_splitk_env() && a.M < 512)) && gemm_ring_supported(a)) {
-            const int sp = gemm_ring_splitk_slices(a);
-            if (sp >= 2) return launch_gemm_ring_splitk(a, sp, s);
-        }
-    }
-    // everything below the gemm256 threshold: the LDS-DMA ring kernels (gemm_ring.hip) instead of the one-tile-ahead register staging
-    if (EPI != EPI_GATEUP && !OUT_F32 && gemm_ring_supported(a)) {
-        const int64_t tiles_ring = (int64_t)cdiv(a.M, 128) * cdiv(a.N, 64);
-        // measured (tools/microbench.py tiles): the 128x64 3-stage ring wins while its grid fits about one round of the 512
-        // resident blocks (S=769 q/k/v 473 -> 675 TF/s, o_proj 397 -> 557, ViT fc2 168 -> 297); beyond that the 128x128 2-stage
-        // ring takes over from the register-staged 128x128 kernel (SFT ViT shapes 376-590 -> 459-697, 4096^3 810 -> 1015)
-        const int64_t tiles128r = (int64_t)cdiv(a.M, 128) * cdiv(a.N, 128);
-        if (sel >= 12 && sel <= 14) return launch_gemm_ring(a, sel == 12 ? 203 : sel == 13 ? 208 : 204, s);   // PIPE = 2 explicitly
-        if (sel >= 15 && sel <= 17) return launch_gemm_ring(a, sel == 15 ? 303 : sel == 16 ? 308 : 304, s);   // plain schedule explicitly
-        if (sel == 7 || (sel == 0 && tiles_ring <= 560 && tiles128r < 270)) return launch_gemm_ring(a, 3, s);
-        if (sel == 6) return launch_gemm_ring(a, 4, s);
-        if (sel == 8 || sel == 0) return launch_gemm_ring(a, 8, s);
-    }
-    if (sel >= 6 && sel <= 17) sel = 0;
-    if (sel == 0) {
-        const int64_t tiles128 = (int64_t)cdiv(a.M, 128) * cdiv(a.N, (EPI == EPI_GATEUP) ? 64 : 128);
-        if (tiles128 < 320 && EPI != EPI_GATEUP) sel = 2;
-        else sel = 1;
-    }
-    if (sel == 2 && EPI == EPI_GATEUP) sel = 1;
-    if (sel == 3) return launch_cfg<EPI, OUT_F32, 4, 4>(a, s);
+static int launch_reg_t(const GemmArgs& a, int family, hipStream_t s) {
+    if (family == GF_REG_256x128) return launch_cfg<EPI, OUT_F32, 4, 4>(a, s);
     if constexpr (EPI != EPI_GATEUP) {
-        if (sel == 2) return launch_cfg<EPI, OUT_F32, 2, 2>(a, s);
+        if (family == GF_REG_128x64) return launch_cfg<EPI, OUT_F32, 2, 2>(a, s);
     }
     return launch_cfg<EPI, OUT_F32, 2, 4>(a, s);
 }
-
-// dgrad / wgrad on the tensors as they lie (contraction-major operands, gemm256_kernel.h): always the 256x256 kernel, sliced over K
-// when its tiles cannot fill the chip and the caller lent a workspace
-static int launch_gemm_cm(const GemmArgs& a, hipStream_t s) {
-    VILA_REQUIRE(a.epi == EPI_NONE && !a.out_f32 && a.W2 == nullptr, "gemm: contraction-major operands take the plain bf16 epilogue only");
-    VILA_REQUIRE(((uintptr_t)a.A % 16 == 0) && ((uintptr_t)a.W % 16 == 0) && ((uintptr_t)a.C % 16 == 0) && a.lda % 8 == 0 && a.ldw % 8 == 0 &&
-                 a.ldc % 4 == 0 && a.N % 4 == 0, "gemm: pointers / leading dims must keep 16-B row alignment");
-    VILA_REQUIRE(a.residual == nullptr || (a.ldr % 4 == 0 && (uintptr_t)a.residual % 8 == 0), "gemm: residual alignment");
-    VILA_REQUIRE(gemm256_supported(a), "gemm: contraction-major operand needs rows %% 8 == 0, K >= 128 (M=%d N=%d K=%d a_cm=%d b_cm=%d)",
-                 a.M, a.N, a.K, a.a_cm, a.b_cm);
-    const int64_t tiles256 = (int64_t)cdiv(a.M, 256) * cdiv(a.N, 256);
-    if (a.ws != nullptr && tiles256 < 150) {
-        const int kt = cdiv(a.K, 64);
-        int splits = (int)(256 / tiles256);
-        if (splits > 8) splits = 8;
-        while (splits >= 2 && (cdiv(kt, splits) < 8 || (size_t)splits * a.M * a.N * 4 > a.ws_bytes)) --splits;
-        if (splits >= 2) splits = cdiv(kt, cdiv(kt, splits));
-        if (splits >= 2) return launch_gemm256_splitk(a, splits, a.ws, s);
+static int launch_reg(const GemmArgs& a, int family, hipStream_t s) {
+    if (a.epi == EPI_GATEUP) return launch_reg_t<EPI_GATEUP, false>(a, family, s);
+    if (a.out_f32) return launch_reg_t<EPI_NONE, true>(a, family, s);
+    switch (a.epi) {
+        case EPI_NONE: return launch_reg_t<EPI_NONE, false>(a, family, s);
+        case EPI_GELU_TANH: return launch_reg_t<EPI_GELU_TANH, false>(a, family, s);
+        case EPI_GELU_ERF: return launch_reg_t<EPI_GELU_ERF, false>(a, family, s);
     }
-    return launch_gemm256(a, s);
+    VILA_FAIL(-1, "gemm: unknown epilogue %d", a.epi);
 }
 
 int launch_gemm(const GemmArgs& a, hipStream_t s) {
     VILA_REQUIRE(a.M > 0 && a.N > 0 && a.K > 0, "gemm: empty problem M=%d N=%d K=%d", a.M, a.N, a.K);
-    if (a.a_cm || a.b_cm) return launch_gemm_cm(a, s);
-    VILA_REQUIRE(a.K % 8 == 0 && a.N % 4 == 0, "gemm: K (%d) must be a multiple of 8 and N (%d) of 4", a.K, a.N);
-    VILA_REQUIRE(a.lda % 8 == 0 && a.ldw % 8 == 0 && a.ldc % 4 == 0, "gemm: leading dims must keep 16-B row alignment");
-    VILA_REQUIRE(((uintptr_t)a.A % 16 == 0) && ((uintptr_t)a.W % 16 == 0) && ((uintptr_t)a.C % 16 == 0), "gemm: pointers must be 16-B aligned");
-    VILA_REQUIRE(a.residual == nullptr || (a.ldr % 4 == 0 && (uintptr_t)a.residual % 8 == 0), "gemm: residual alignment");
-    if (a.epi == EPI_GATEUP) {
-        VILA_REQUIRE(a.W2 != nullptr && !a.out_f32 && a.bias == nullptr, "gemm: gate/up mode needs W2, bf16 out, no bias");
-        VILA_REQUIRE((uintptr_t)a.W2 % 16 == 0, "gemm: W2 alignment");
-        return launch_t<EPI_GATEUP, false>(a, s);
+    if (a.a_cm || a.b_cm) {
+        VILA_REQUIRE(a.epi == EPI_NONE && !a.out_f32 && a.W2 == nullptr, "gemm: contraction-major operands take the plain bf16 epilogue only");
+        VILA_REQUIRE(((uintptr_t)a.A % 16 == 0) && ((uintptr_t)a.W % 16 == 0) && ((uintptr_t)a.C % 16 == 0) && a.lda % 8 == 0 && a.ldw % 8 == 0 &&
+                     a.ldc % 4 == 0 && a.N % 4 == 0, "gemm: pointers / leading dims must keep 16-B row alignment");
+        VILA_REQUIRE(a.residual == nullptr || (a.ldr % 4 == 0 && (uintptr_t)a.residual % 8 == 0), "gemm: residual alignment");
+        VILA_REQUIRE(gemm256_supported(a), "gemm: contraction-major operand needs rows %% 8 == 0, K >= 128 (M=%d N=%d K=%d a_cm=%d b_cm=%d)",
+                     a.M, a.N, a.K, a.a_cm, a.b_cm);
+    } else {
+        VILA_REQUIRE(a.K % 8 == 0 && a.N % 4 == 0, "gemm: K (%d) must be a multiple of 8 and N (%d) of 4", a.K, a.N);
+        VILA_REQUIRE(a.lda % 8 == 0 && a.ldw % 8 == 0 && a.ldc % 4 == 0, "gemm: leading dims must keep 16-B row alignment");
+        VILA_REQUIRE(((uintptr_t)a.A % 16 == 0) && ((uintptr_t)a.W % 16 == 0) && ((uintptr_t)a.C % 16 == 0), "gemm: pointers must be 16-B aligned");
+        VILA_REQUIRE(a.residual == nullptr || (a.ldr % 4 == 0 && (uintptr_t)a.residual % 8 == 0), "gemm: residual alignment");
+        if (a.epi == EPI_GATEUP) {
+            VILA_REQUIRE(a.W2 != nullptr && !a.out_f32 && a.bias == nullptr, "gemm: gate/up mode needs W2, bf16 out, no bias");
+            VILA_REQUIRE((uintptr_t)a.W2 % 16 == 0, "gemm: W2 alignment");
+        } else if (a.out_f32) {
+            VILA_REQUIRE(a.epi == EPI_NONE, "gemm: fp32 output only with EPI_NONE");
+        }
+        if (a.epi < EPI_NONE || a.epi > EPI_GATEUP) VILA_FAIL(-1, "gemm: unknown epilogue %d", a.epi);
     }
-    if (a.out_f32) {
-        VILA_REQUIRE(a.epi == EPI_NONE, "gemm: fp32 output only with EPI_NONE");
-        return launch_t<EPI_NONE, true>(a, s);
+    const GemmPlan p = gemm_plan(shape_of(a), gemm_knobs());
+    switch (p.family) {
+        case GF_256: case GF_256_HYBRID: case GF_CM: case GF_CM_HYBRID: return launch_gemm256(a, p, s);
+        case GF_256_SLICED: case GF_CM_SLICED: return launch_gemm256_splitk(a, p, s);
+        case GF_RING: return launch_gemm_ring(a, p.ring, p.pipe, s);
+        case GF_RING_SPLITK: return launch_gemm_ring_splitk(a, p.splits, s);
+        default: return launch_reg(a, p.family, s);
     }
-    switch (a.epi) {
-        case EPI_NONE: return launch_t<EPI_NONE, false>(a, s);
-        case EPI_GELU_TANH: return launch_t<EPI_GELU_TANH, false>(a, s);
-        case EPI_GELU_ERF: return launch_t<EPI_GELU_ERF, false>(a, s);
-    }
-    VILA_FAIL(-1, "gemm: unknown epilogue %d", a.epi);
 }

@@ -232,132 +232,71 @@ __global__ __launch_bounds__(256) void splitk_tail_reduce_kernel(const float* __
     }
 }
 
-int g_gemm256_sched = 0;      // tuning hook (vila_gemm_force_sched): 0 = default schedule of each layout; 1 / 2 / 9 = gemm256_kernel.h SCHED, 10 = SCHED 0
-extern "C" void vila_gemm_force_sched(int sched) { g_gemm256_sched = sched; }
-int launch_gemm256_cm(const GemmArgs& a, hipStream_t s);                       // gemm256_cm.hip
-int launch_gemm256_cm_splitk(const GemmArgs& a, int splits, float* slab, int per, hipStream_t s);
-int launch_gemm256_sched(const GemmArgs& a, int sched, hipStream_t s);
-int launch_gemm256_cm_range(const GemmArgs& a, int mode, int splits, int tile0, int n_tiles, int per, hipStream_t s);
-int g_gemm256_group = -1;           // tuning hook (vila_gemm_force_group): tile order, see gemm256_kernel.h
-extern "C" void vila_gemm_force_group(int grp) { g_gemm256_group = grp; }
-int g_gemm256_ex = -1;             // tuning hook (vila_gemm_force_ex): see gemm256_kernel.h
-extern "C" void vila_gemm_force_ex(int mode) { g_gemm256_ex = mode; }
-int g_gemm256_bm = 0;              // tuning hook (vila_gemm_force_bm): 0 = prefer_bm192's rule, 192 / 256 = force that tile height
-extern "C" void vila_gemm_force_bm(int bm) { g_gemm256_bm = bm; }
-static int g_gemm256_hybrid = 1;   // tuning hook: 0 = never cut a GEMM into whole rounds + K-sliced tail
-extern "C" void vila_gemm_force_hybrid(int on) { g_gemm256_hybrid = on; }
+int launch_gemm256_cm(const GemmArgs& a, const GemmPlan& p, hipStream_t s);                       // gemm256_cm.hip
+int launch_gemm256_cm_splitk(const GemmArgs& a, const GemmPlan& p, hipStream_t s);
+int launch_gemm256_sched(const GemmArgs& a, const GemmPlan& p, hipStream_t s);
+int launch_gemm256_cm_range(const GemmArgs& a, int mode, const GemmPlan& p, hipStream_t s);
 
-// Tile quantisation: T tiles on 256 CUs cost ceil(T / 256) rounds.  When the last round is short (wgrad of gate/up/down: 1036 tiles =
-// 4 rounds + 12 tiles, i.e. a fifth round for 1 % of the work) the whole rounds run as usual and the tail tiles are sliced over K so that
-// they fill the chip for a fraction of a tile time; their raw sums go to compact per-tile fp32 slabs and meet in a small reduce kernel
-// (bias / residual applied there).  Returns 1 when the GEMM was issued this way, 0 when the caller should launch it whole.
-static int try_hybrid(const GemmArgs& a, hipStream_t s) {
-    if (!g_gemm256_hybrid || a.ws == nullptr || a.epi != EPI_NONE || a.out_f32 || a.N % 4 != 0) return 0;
-    const int tiles_m = cdiv(a.M, 256), tiles = tiles_m * cdiv(a.N, 256), kt = cdiv(a.K, T256_BK);
-    const int full = (tiles / 256) * 256, tail = tiles - full;
-    if (full == 0 || tail == 0 || tail > 96 || kt < 16) return 0;      // a tail above ~1/3 of a round is cheaper left alone
-    int splits = 256 / tail;
-    if (splits > 8) splits = 8;
-    while (splits >= 2 && (cdiv(kt, splits) < 6 || (size_t)splits * tail * 65536 * 4 > a.ws_bytes)) --splits;
-    if (splits < 2) return 0;
-    const int per = cdiv(kt, splits);
-    splits = cdiv(kt, per);
-    const bool cm = a.a_cm || a.b_cm;
+// whole rounds + K-sliced tail (gemm_plan.h GF_256_HYBRID / GF_CM_HYBRID with the tail reduce)
+static int launch_hybrid(const GemmArgs& a, const GemmPlan& p, hipStream_t s) {
     GemmArgs b = a;
     b.C = a.ws; b.bias = nullptr; b.residual = nullptr;
-    if (cm) {
-        VILA_TRY(launch_gemm256_cm_range(a, 0, 1, 0, full, 0, s));
-        VILA_TRY(launch_gemm256_cm_range(b, 5, splits, full, tail, per, s));
+    if (a.a_cm || a.b_cm) {
+        VILA_TRY(launch_gemm256_cm_range(a, 0, p, s));
+        VILA_TRY(launch_gemm256_cm_range(b, 5, p, s));
     } else {
-        VILA_TRY((launch256_t<0, EPI_NONE, false, false, T256_CC_SCHED>(a, s, 1, 0, full)));
-        VILA_TRY((launch256_t<5, EPI_NONE, false, false, T256_CC_SCHED>(b, s, splits, full, tail, 0, per)));
+        VILA_TRY((launch256_t<0, EPI_NONE, false, false, T256_CC_SCHED>(a, s, p.group, 1, 0, p.n_full)));
+        VILA_TRY((launch256_t<5, EPI_NONE, false, false, T256_CC_SCHED>(b, s, p.group, p.splits, p.n_full, p.n_tail, 0, p.per)));
     }
-    hipLaunchKernelGGL(splitk_tail_reduce_kernel, dim3(tail * 16), dim3(256), 0, s, a.ws, splits, tail, full, tiles_m, cdiv(a.N, 256),
-                       gemm256_group(tiles_m, cdiv(a.N, 256), false), a.bias, a.residual, a.ldr,
-                       (bf16_t*)a.C, a.ldc, a.M, a.N, a.res_mod);
+    hipLaunchKernelGGL(splitk_tail_reduce_kernel, dim3(p.n_tail * 16), dim3(256), 0, s, a.ws, p.splits, p.n_tail, p.n_full, cdiv(a.M, 256), cdiv(a.N, 256),
+                       p.group, a.bias, a.residual, a.ldr, (bf16_t*)a.C, a.ldc, a.M, a.N, a.res_mod);
     VILA_LAUNCH_CHECK();
-    return 1;
+    return 0;
 }
 
-int gemm256_tiles_m_of(int M) { return gemm256_tiles_m(M); }       // for the dispatcher in gemm.hip
-
-bool gemm256_supported(const GemmArgs& a) {
-    if (a.a_cm && (a.M % 8 != 0 || a.lda % 8 != 0)) return false;
-    if (a.b_cm && (a.N % 8 != 0 || a.ldw % 8 != 0)) return false;
-    const int64_t ea = a.a_cm ? (int64_t)64 * a.lda + a.M : (int64_t)a.M * a.lda;      // largest 32-bit element offset the DMA lanes form
-    const int64_t eb = a.b_cm ? (int64_t)64 * a.ldw + a.N : (int64_t)a.N * a.ldw;
-    // a CC operand is read in 16-B chunks along K (K % 8 == 0); a CM operand in whole k-rows (any K)
-    if ((!a.a_cm || !a.b_cm) && a.K % 8 != 0) return false;
-    return a.K >= 2 * T256_BK && ea < (1ll << 31) && eb < (1ll << 31);
+// fused gate/up: whole, or whole rounds fused + the tail's tile columns K-sliced into raw gate / up planes that meet in a small reduce
+static int launch_gateup(const GemmArgs& a, const GemmPlan& p, hipStream_t s) {
+    if (p.reduce != GR_GATEUP) return launch256_fwd<2, EPI_NONE>(a, s, p);
+    VILA_TRY((launch256_fwd<2, EPI_NONE>(a, s, p, 1, 0, p.n_full)));
+    GemmArgs b = a;
+    b.C = a.ws; b.ldc = p.tail_cols;
+    VILA_TRY((launch256_fwd<4, EPI_NONE>(b, s, p, p.splits, p.n_full, p.n_tail, p.col0, p.per)));
+    const int64_t total = (int64_t)a.M * (p.tail_cols / 4);
+    const int grid = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
+    hipLaunchKernelGGL(splitk_gu_reduce_kernel, dim3(grid), dim3(256), 0, s, a.ws, p.splits, (bf16_t*)a.C, a.ldc, a.M, p.tail_cols, p.col0);
+    VILA_LAUNCH_CHECK();
+    return 0;
 }
 
-// Gate/up with an under-filled LAST round (S = 769: 592 tiles = 2 full rounds of 256 + 80): the full rounds run fused as usual, the
-// tail tiles are sliced over K so the last round costs 1/splits of a tile time; raw gate / up sums meet in a small reduce kernel.
-static int launch_gateup(const GemmArgs& a, hipStream_t s) {
-    const int tiles_n = cdiv(a.N, 128), kt = cdiv(a.K, T256_BK);
-    const bool ex = gemm256_ex_saves_round(a.M, tiles_n);   // 1..16 leftover rows ride in the last row tile (EX kernels)
-    const int tiles_m = ex ? a.M / 256 : cdiv(a.M, 256);
-    const int slots = 256;                                   // one 512-thread block per CU
-    const int full_tn = ((tiles_m * tiles_n) / slots) * slots / tiles_m;     // tile columns covered by whole rounds
-    const int tail_tn = tiles_n - full_tn, tail_tiles = tail_tn * tiles_m;
-    if (a.ws != nullptr && full_tn > 0 && tail_tiles > 0 && tail_tiles <= slots / 2 && kt >= 16) {
-        int splits = slots / tail_tiles;
-        if (splits > 4) splits = 4;
-        const int per = cdiv(kt, splits);
-        splits = cdiv(kt, per);
-        const int tc = tail_tn * 128 < a.N - full_tn * 128 ? tail_tn * 128 : a.N - full_tn * 128;      // output columns of the tail
-        if (splits >= 2 && (size_t)splits * 2 * a.M * tc * 4 <= a.ws_bytes && tc % 4 == 0) {
-            VILA_TRY((launch256_fwd<2, EPI_NONE>(a, s, ex, 1, 0, full_tn * tiles_m)));
-            GemmArgs b = a;
-            b.C = a.ws; b.ldc = tc;
-            VILA_TRY((launch256_fwd<4, EPI_NONE>(b, s, ex, splits, full_tn * tiles_m, tail_tiles, full_tn * 128, per)));
-            const int64_t total = (int64_t)a.M * (tc / 4);
-            const int grid = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
-            hipLaunchKernelGGL(splitk_gu_reduce_kernel, dim3(grid), dim3(256), 0, s, a.ws, splits, (bf16_t*)a.C, a.ldc, a.M, tc, full_tn * 128);
-            VILA_LAUNCH_CHECK();
-            return 0;
-        }
-    }
-    return launch256_fwd<2, EPI_NONE>(a, s, ex);
-}
-
-int launch_gemm256(const GemmArgs& a, hipStream_t s) {
-    if (g_gemm256_sched == 0 && a.epi == EPI_NONE && !a.out_f32) {
-        const int h = try_hybrid(a, s);
-        if (h != 0) return h < 0 ? h : 0;
-    }
-    if (a.a_cm || a.b_cm) return launch_gemm256_cm(a, s);
-    if (g_gemm256_sched != 0 && a.epi == EPI_NONE && !a.out_f32) return launch_gemm256_sched(a, g_gemm256_sched, s);
-    if (a.epi == EPI_GATEUP) return launch_gateup(a, s);
-    const bool ex = gemm256_ex_saves_round(a.M, cdiv(a.N, 256));
-    if (a.out_f32) return launch256_fwd<1, EPI_NONE>(a, s, ex);
+// the 256x256 kernel over the whole output: GF_256 / GF_256_HYBRID / GF_CM / GF_CM_HYBRID
+int launch_gemm256(const GemmArgs& a, const GemmPlan& p, hipStream_t s) {
+    if (p.reduce == GR_TAIL) return launch_hybrid(a, p, s);
+    if (a.a_cm || a.b_cm) return launch_gemm256_cm(a, p, s);
+    if (p.sched != 0) return launch_gemm256_sched(a, p, s);
+    if (a.epi == EPI_GATEUP) return launch_gateup(a, p, s);
+    if (a.out_f32) return launch256_fwd<1, EPI_NONE>(a, s, p);
     switch (a.epi) {
         case EPI_NONE:
-            if (prefer_bm192(a.M, a.N, g_gemm256_bm)) return launch256_t<0, EPI_NONE, false, false, T256_CC_SCHED, 192>(a, s);
-            return launch256_fwd<0, EPI_NONE>(a, s, ex);
-        case EPI_GELU_TANH: return launch256_fwd<0, EPI_GELU_TANH>(a, s, ex);
-        case EPI_GELU_ERF: return launch256_fwd<0, EPI_GELU_ERF>(a, s, ex);
+            if (p.bm == 192) return launch256_t<0, EPI_NONE, false, false, T256_CC_SCHED, 192>(a, s, p.group);
+            return launch256_fwd<0, EPI_NONE>(a, s, p);
+        case EPI_GELU_TANH: return launch256_fwd<0, EPI_GELU_TANH>(a, s, p);
+        case EPI_GELU_ERF: return launch256_fwd<0, EPI_GELU_ERF>(a, s, p);
     }
     VILA_FAIL(-1, "gemm256: unsupported epilogue %d", a.epi);
 }
 
-// VILA_FUSE_NORM=0: the reduce never takes the next block's normalisation along (A/B switch)
-static int g_fuse_norm = -1;
-extern "C" void vila_gemm_force_fuse_norm(int on) { g_fuse_norm = on ? 1 : 0; }
-static bool fused_norm_enabled() {
-    if (g_fuse_norm < 0) { const char* e = getenv("VILA_FUSE_NORM"); g_fuse_norm = (e && e[0] == '0') ? 0 : 1; }
-    return g_fuse_norm != 0;
-}
-// split-K: C = sum over `splits` K-slices; `slab` = splits * M * N fp32 workspace owned by the caller
-int launch_gemm256_splitk(const GemmArgs& a, int splits, float* slab, hipStream_t s) {
-    const int kt = cdiv(a.K, T256_BK), per = cdiv(kt, splits);
+// split-K (GF_256_SLICED / GF_CM_SLICED): C = sum over p.splits K-slices of p.per K-tiles; the slabs (splits * M * N fp32) live in the caller's
+// workspace a.ws; p.reduce names the reduce that finishes the output
+int launch_gemm256_splitk(const GemmArgs& a, const GemmPlan& p, hipStream_t s) {
+    const int kt = cdiv(a.K, T256_BK), per = p.per, splits = p.splits;
+    float* slab = a.ws;
     VILA_REQUIRE(a.epi == EPI_NONE && !a.out_f32 && a.N % 4 == 0 && splits >= 1 && (splits - 1) * per < kt,
                  "gemm256 split-K: %d K tiles cannot be cut into %d non-empty slices", kt, splits);
     GemmArgs b = a;
     b.C = slab; b.ldc = a.N; b.bias = nullptr; b.residual = nullptr;
-    if (a.a_cm || a.b_cm) VILA_TRY(launch_gemm256_cm_splitk(b, splits, slab, per, s));
-    else VILA_TRY((launch256_fwd<3, EPI_NONE>(b, s, gemm256_ex_rows(a.M) != 0, splits, 0, -1, 0, per)));      // the last slice takes the remainder
-    if (gemm_rope_offer(a)) {
+    if (a.a_cm || a.b_cm) VILA_TRY(launch_gemm256_cm_splitk(b, p, s));
+    else VILA_TRY((launch256_fwd<3, EPI_NONE>(b, s, p, splits, 0, -1, 0, per)));      // the last slice takes the remainder
+    if (p.reduce == GR_ROPE) {
         const int64_t total = (int64_t)a.M * (a.rope_nq + 2 * a.rope_nkv) * (a.rope_hd / 16);
         const int grid = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
         hipLaunchKernelGGL(splitk_reduce_rope_kernel, dim3(grid), dim3(256), 0, s, slab, splits, (int64_t)a.M * a.N, a.bias, (bf16_t*)a.C, a.ldc, a.M, a.N,
@@ -366,7 +305,7 @@ int launch_gemm256_splitk(const GemmArgs& a, int splits, float* slab, hipStream_
         *a.rope_done = 1;
         return 0;
     }
-    if (a.norm_out != nullptr && a.norm_w != nullptr && a.N % 8 == 0 && a.N <= 16384 && fused_norm_enabled()) {
+    if (p.reduce == GR_NORM) {
         // the reduce holds whole rows: the next block's LayerNorm / RMSNorm rides along (one launch and one read of the row less)
         if (a.norm_rms) hipLaunchKernelGGL(splitk_reduce_norm_kernel<true>, dim3(a.M), dim3(256), 0, s, slab, splits, (int64_t)a.M * a.N, a.bias, a.residual, a.ldr,
                                       (bf16_t*)a.C, a.ldc, a.N, a.res_mod, a.norm_w, a.norm_b, a.norm_eps, a.norm_out);

@@ -24,9 +24,11 @@
 //   7  role split with TWO phases of 32 MFMAs per K-tile (4 barriers): the default
 //   9  ablation: schedule 0 without any DMA inside the loop (wrong results; bounds what hiding the loads completely would buy)
 #pragma once
-#include <stdlib.h>
 #include "kernels.h"
+#include "gemm_plan.h"
 
+static_assert(GEMM_EPI_NONE == EPI_NONE && GEMM_EPI_GELU_TANH == EPI_GELU_TANH && GEMM_EPI_GELU_ERF == EPI_GELU_ERF && GEMM_EPI_GATEUP == EPI_GATEUP,
+              "gemm_plan.h names the epilogues of kernels.h");
 #define T256_BK 64
 #define T256_STG 68
 
@@ -69,13 +71,7 @@ __host__ __device__ inline void gemm256_tile_of(int id, int tiles_m, int tiles_n
         tm = id % tiles_m; tn = id / tiles_m;
     }
 }
-extern int g_gemm256_group;        // tuning hook (vila_gemm_force_group): -1 = the rule below, 0 = tm-fastest everywhere, n = groups of n
-// grouped order where a strip would be long (tiles_m > 16); `gateup` = a fused gate/up launch over part of the grid (tail policy): never
-static inline int gemm256_group(int tiles_m, int tiles_n, bool gateup) {
-    if (gateup || tiles_n < 2) return 0;
-    if (g_gemm256_group >= 0) return g_gemm256_group;
-    return tiles_m > 16 ? 4 : 0;
-}
+// (the grouped order is used where a strip would be long: gemm_plan.h gemm256_group)
 
 // (Measured and removed in round 5: an "epilogue prefetch" variant that requested a store pass's residual words ahead of the pass — the ISA shows
 // `global_load_dwordx2 -> s_waitcnt vmcnt(0) -> add -> global_store` 32 times per wave and tile with a residual.  Bit-identical results, and no
@@ -827,40 +823,10 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(GemmArgs p, int tiles_m
     }
 }
 
-// 192-row tiles (BM) when they need fewer tile-times than 256-row tiles: rounds(tiles) x work per tile, a 192-row tile priced at 0.78 of a
-// 256-row one (3/4 of the MFMAs on the same B traffic).  force: 0 = this rule, 192 / 256 = that tile height (vila_gemm_force_bm)
-static inline bool prefer_bm192(int M, int N, int force) {
-    if (force == 192) return true;
-    if (force == 256) return false;
-    const int t256 = cdiv(M, 256) * cdiv(N, 256), t192 = cdiv(M, 192) * cdiv(N, 256);
-    return 0.78 * cdiv(t192, 256) < 0.97 * cdiv(t256, 256);
-}
-
-// rows the LAST 256-row tile carries as an extra 16-row fragment (EX kernels): M = 256 k + r, k >= 1, 1 <= r <= 16; else 0.
-// VILA_GEMM_EX=0 switches the policy off (A/B measurements: the callers then see cdiv(M, 256) row tiles again)
-extern int g_gemm256_ex;      // gemm256.hip: -1 = VILA_GEMM_EX from the environment (default 1), 0 = off, 1 = the policy below, 2 = whenever the rows fit (tests)
-static inline int gemm256_ex_mode() {
-    if (g_gemm256_ex < 0) { const char* e = getenv("VILA_GEMM_EX"); g_gemm256_ex = (e && e[0] >= '0' && e[0] <= '2') ? e[0] - '0' : 1; }
-    return g_gemm256_ex;
-}
-static inline int gemm256_ex_rows(int M) {
-    const int r = M % 256;
-    return (gemm256_ex_mode() != 0 && M > 256 && r >= 1 && r <= 16) ? r : 0;
-}
-// 256-row tiles of an M-row output under that policy (what every launch policy must count with when it hands tile ranges to EX launches)
-static inline int gemm256_tiles_m(int M) { return gemm256_ex_rows(M) ? M / 256 : cdiv(M, 256); }
-// Whole-grid launches take the EX kernel only when dropping the extra row tile saves a ROUND of 256 blocks: its last-row blocks do 12.5 %
-// more MFMAs and the kernel carries 16-28 more registers, measured 5-10 % slower than the plain kernel on grids with the same number of
-// rounds (M = 3076 x N = 4608: 92 -> 101 us, profiles/r03_gemm_bench_fwd_ex.log); K-sliced launches always take it (fewer tiles = more slices)
-static inline bool gemm256_ex_saves_round(int M, int tiles_n) {
-    if (gemm256_ex_rows(M) == 0) return false;
-    if (gemm256_ex_mode() == 2) return true;
-    return cdiv((M / 256) * tiles_n, 256) < cdiv(cdiv(M, 256) * tiles_n, 256);
-}
-
-// tile range [tile0, tile0 + n_tiles) of the tile order (gemm256_tile_of; n_tiles < 0: all); per = K-tiles per slice for the split modes
+// tile range [tile0, tile0 + n_tiles) of the tile order (gemm256_tile_of with the plan's `grp`; n_tiles < 0: all); per = K-tiles per slice for
+// the split modes.  Every number comes from the launch plan (gemm_plan.h): EX, BM and grp must be the ones its tile counts were made with.
 template <int MODE, int EPI, bool ACM = false, bool BCM = false, int SCHED = 0, int BM = 256, bool EX = false>
-static int launch256_t(const GemmArgs& a, hipStream_t s, int splits = 1, int tile0 = 0, int n_tiles = -1, int col0 = 0, int per = 0) {
+static int launch256_t(const GemmArgs& a, hipStream_t s, int grp, int splits = 1, int tile0 = 0, int n_tiles = -1, int col0 = 0, int per = 0) {
     const int bn = (MODE == 2 || MODE == 4) ? 128 : 256;
     const int tiles_m = EX ? a.M / 256 : cdiv(a.M, BM), tiles_n = cdiv(a.N, bn);
     if (n_tiles < 0) n_tiles = tiles_m * tiles_n;
@@ -872,17 +838,13 @@ static int launch256_t(const GemmArgs& a, hipStream_t s, int splits = 1, int til
     }
     const int kt = cdiv(a.K, T256_BK);
     if (per <= 0) per = kt / splits;
-    // fused gate/up: grouped only when this launch covers the whole grid (its whole-rounds + sliced-tail policy cuts whole tile COLUMNS)
-    const bool gu_partial = (MODE == 4) || (MODE == 2 && (tile0 != 0 || n_tiles != tiles_m * tiles_n));
-    const int grp = gemm256_group(tiles_m, tiles_n, gu_partial);
     hipLaunchKernelGGL((gemm256_kernel<MODE, EPI, ACM, BCM, SCHED, BM, EX>), dim3(n_tiles, splits), dim3(512), lds, s, a, tiles_m, per, tile0, col0, grp);
     VILA_LAUNCH_CHECK();
     return 0;
 }
-// forward-layout launch that takes the EX kernel when the shape has 1..16 leftover rows (ex = gemm256_ex_rows(a.M) != 0, decided by the caller
-// so that its tile ranges and this launch agree)
+// forward-layout launch that takes the EX kernel when the plan says so (the shape has 1..16 leftover rows)
 template <int MODE, int EPI>
-static int launch256_fwd(const GemmArgs& a, hipStream_t s, bool ex, int splits = 1, int tile0 = 0, int n_tiles = -1, int col0 = 0, int per = 0) {
-    if (ex) return launch256_t<MODE, EPI, false, false, T256_CC_SCHED, 256, true>(a, s, splits, tile0, n_tiles, col0, per);
-    return launch256_t<MODE, EPI, false, false, T256_CC_SCHED>(a, s, splits, tile0, n_tiles, col0, per);
+static int launch256_fwd(const GemmArgs& a, hipStream_t s, const GemmPlan& p, int splits = 1, int tile0 = 0, int n_tiles = -1, int col0 = 0, int per = 0) {
+    if (p.ex) return launch256_t<MODE, EPI, false, false, T256_CC_SCHED, 256, true>(a, s, p.group, splits, tile0, n_tiles, col0, per);
+    return launch256_t<MODE, EPI, false, false, T256_CC_SCHED>(a, s, p.group, splits, tile0, n_tiles, col0, per);
 }

@@ -14,7 +14,6 @@
 //   involution as gemm.hip / gemm256.hip) is applied on the per-lane SOURCE address and on the fragment reads.
 //   K tail: chunks of the last K-tile beyond K are DMA'd from a zero chunk.  M / N tails: row clamping + masked stores.
 // Epilogues: bias, GELU (tanh / erf), residual, bf16 out.
-#include <stdlib.h>
 #include "kernels.h"
 
 #define RG_BM 128
@@ -279,11 +278,6 @@ static int launch_ring_t(const GemmArgs& a, hipStream_t s) {
     return 0;
 }
 
-bool gemm_ring_supported(const GemmArgs& a) {
-    return a.epi != EPI_GATEUP && !a.out_f32 && a.K % 8 == 0 && a.K >= RG_BK && a.N % 4 == 0 && (int64_t)a.M * a.lda < (1ll << 31) &&
-           (int64_t)a.N * a.ldw < (1ll << 31);
-}
-
 template <int STAGES, int NF, int PIPE = 0>
 static int launch_ring_epi(const GemmArgs& a, hipStream_t s) {
     switch (a.epi) {
@@ -294,23 +288,16 @@ static int launch_ring_epi(const GemmArgs& a, hipStream_t s) {
     VILA_FAIL(-1, "gemm_ring: unsupported epilogue %d", a.epi);
 }
 
-// variant: 3 = 128x64 tile, 3 stages (2 blocks / CU); 4 = 128x64, 4 stages (1 block / CU); 8 = 128x128 tile, 2 stages (2 blocks / CU).
-// + 200 = PIPE 2 explicitly, + 300 = the plain fragment schedule explicitly (tests / tools/gemm_bench); otherwise VILA_RING_PIPE decides: "0" = the plain schedule, anything else (or unset) = PIPE 2 — the compiler-scheduled PIPE 1 of round 4 was
-// measured and deleted in round 5, so VILA_RING_PIPE=1 means PIPE 2 today.
-static int ring_pipe_env() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("VILA_RING_PIPE"); v = (e && e[0] == '0') ? 0 : 2; }
-    return v;
-}
-int launch_gemm_ring(const GemmArgs& a, int variant, hipStream_t s) {
-    const int pipe = variant >= 300 ? 0 : variant >= 200 ? 2 : ring_pipe_env();
-    variant %= 100;
+// ring: 3 = 128x64 tile, 3 stages (2 blocks / CU); 4 = 128x64, 4 stages (1 block / CU); 8 = 128x128 tile, 2 stages (2 blocks / CU).
+// pipe: 0 = the plain fragment schedule, 2 = PIPE 2 (gemm_plan.h: forced tiles 12-17 say which explicitly, otherwise VILA_RING_PIPE decides: "0" = plain,
+// anything else (or unset) = PIPE 2 — the compiler-scheduled PIPE 1 of round 4 was measured and deleted in round 5, so VILA_RING_PIPE=1 means PIPE 2 today).
+int launch_gemm_ring(const GemmArgs& a, int ring, int pipe, hipStream_t s) {
     if (pipe) {
-        if (variant == 8) return launch_ring_epi<2, 4, 2>(a, s);
-        if (variant == 4) return launch_ring_epi<4, 2, 2>(a, s);
+        if (ring == 8) return launch_ring_epi<2, 4, 2>(a, s);
+        if (ring == 4) return launch_ring_epi<4, 2, 2>(a, s);
         return launch_ring_epi<3, 2, 2>(a, s);
     }
-    if (variant == 8) return launch_ring_epi<2, 4>(a, s);
-    if (variant == 4) return launch_ring_epi<4, 2>(a, s);
+    if (ring == 8) return launch_ring_epi<2, 4>(a, s);
+    if (ring == 4) return launch_ring_epi<4, 2>(a, s);
     return launch_ring_epi<3, 2>(a, s);
 }

@@ -15,7 +15,6 @@
 //
 // The kernel is the 3-stage 128x64 ring of gemm_ring.hip with (a) its K-tile range [t0, t1) taken from blockIdx.y and (b) an epilogue that
 // stores the raw fp32 accumulators.  Tile / LDS layout, swizzle, counted waits: see gemm_ring.hip.
-#include <stdlib.h>
 #include "kernels.h"
 
 #define RS_BM 128
@@ -182,20 +181,7 @@ __global__ void ring_splitk_reduce_kernel(const float* __restrict__ slab, int sp
     }
 }
 
-// How many K-slices the short-prompt policy would take for this problem (0 = do not slice): fill the 512 resident block slots (two
-// 3-stage blocks per CU), at most 4 slices, at least 8 K-tiles per slice, slabs inside the workspace.
-int gemm_ring_splitk_slices(const GemmArgs& a) {
-    if (a.epi != EPI_NONE || a.out_f32 || a.ws == nullptr || a.a_cm || a.b_cm) return 0;
-    if (a.K % 8 != 0 || a.N % 4 != 0 || (int64_t)a.M * a.lda >= (1ll << 31) || (int64_t)a.N * a.ldw >= (1ll << 31)) return 0;
-    const int64_t tiles = (int64_t)cdiv(a.M, RS_BM) * cdiv(a.N, RS_BN);
-    const int kt = cdiv(a.K, RS_BK);
-    int splits = (int)(512 / tiles);
-    if (splits > 4) splits = 4;
-    while (splits >= 2 && (cdiv(kt, splits) < 8 || (size_t)splits * a.M * a.N * 4 > a.ws_bytes)) --splits;
-    if (splits >= 2) splits = cdiv(kt, cdiv(kt, splits));      // drop empty trailing slices
-    return splits >= 2 ? splits : 0;
-}
-
+// splits >= 2 slices of cdiv(kt, splits) K-tiles (gemm_plan.h GF_RING_SPLITK: the short-prompt policy)
 int launch_gemm_ring_splitk(const GemmArgs& a, int splits, hipStream_t s) {
     const int kt = cdiv(a.K, RS_BK), per = cdiv(kt, splits);
     VILA_REQUIRE(a.epi == EPI_NONE && !a.out_f32 && a.ws != nullptr && splits >= 2 && (splits - 1) * per < kt &&
