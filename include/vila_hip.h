@@ -187,7 +187,11 @@ int vila_llm_decode_step_sample(const VilaLlmWeights* w, const VilaKvCache* cach
 /* Batched greedy decode step (serving: llava_arch.py:823-833 called with a batch, server.py:171-290 serving concurrent requests): ONE pass
  * over the weights advances n <= 16 sequences.  Row i lives in KV-cache slot i (cache->n_slots >= n, filled by vila_llm_prefill with
  * seq_of_tok = slot), consumes token[i] at position pos[i] and leaves its next token in token[i] / out_ids[i][n_out[i]++], pos[i]++.
- * Rows that hit EOS keep stepping (the host ignores what they produce).  head_dim 128, caches up to 2048 positions. */
+ * Rows that hit EOS keep stepping (the host ignores what they produce).  head_dim 128.  Caches up to 2048 positions run with the workspace of
+ * vila_llm_decode_batch_workspace_bytes; caches up to 32768 positions (Qwen2.5's max_position_embeddings) with the workspace of
+ * vila_llm_decode_batch_workspace_bytes_ctx(shape, n, cache->max_ctx), which returns the same size up to 2048 positions.  Beyond 2048 the attention's
+ * blocks walk several 256-key chunks of a row (GQA groups of 1, 2, 4, 7 or 8 query heads); a long cache with the short workspace is refused
+ * before anything is enqueued.  The same holds for the _sample, _w4 and _w4_sample steps and their _ctx sizes. */
 typedef struct {
     int n;               /* sequences */
     int32_t* pos;        /* [n] */
@@ -198,6 +202,7 @@ typedef struct {
     float* logits;       /* [n][vocab] fp32 logits of the last step */
 } VilaDecodeBatch;
 size_t vila_llm_decode_batch_workspace_bytes(const VilaLlmShape* s, int n);
+size_t vila_llm_decode_batch_workspace_bytes_ctx(const VilaLlmShape* s, int n, int max_ctx);
 int vila_llm_decode_step_batch(const VilaLlmWeights* w, const VilaKvCache* cache, const VilaDecodeBatch* st,
                                void* workspace, size_t workspace_bytes, vila_stream_t stream);
 
@@ -222,8 +227,18 @@ int vila_sample_batch_f32(const float* logits, int64_t ld_logits, int n, int voc
  * read before it advances), then token / out_ids / n_out / pos move as in the greedy step.  The launches before the pick are the greedy step's,
  * so the logits are the same bits. */
 size_t vila_llm_decode_batch_sample_workspace_bytes(const VilaLlmShape* s, int n);
+size_t vila_llm_decode_batch_sample_workspace_bytes_ctx(const VilaLlmShape* s, int n, int max_ctx);
 int vila_llm_decode_step_batch_sample(const VilaLlmWeights* w, const VilaKvCache* cache, const VilaDecodeBatch* st,
                                       void* workspace, size_t workspace_bytes, const VilaBatchSampling* sp, vila_stream_t stream);
+
+/* The batched step's attention on its own (operator level): row i of q [n_rows][ldq] (q_heads x 128 bf16) attends keys 0 .. pos[i] of cache slot i;
+ * kcache / vcache are ONE layer's [slots][kv_heads][max_ctx][128] with slots `slot_stride` elements apart; o [n_rows][ldo] bf16.  max_ctx up to
+ * 32768, GQA groups of 1, 2, 4, 7 or 8; the kernel form (one slice per 256-key chunk up to 2048 positions, walking blocks beyond) is chosen as
+ * the step chooses it.  Two launches. */
+size_t vila_attn_decode_batch_workspace_bytes(int n_rows, int q_heads, int max_ctx);
+int vila_attn_decode_batch_bf16(const void* q, int64_t ldq, const void* kcache, const void* vcache, int64_t slot_stride, const int32_t* pos,
+                                void* o, int64_t ldo, int n_rows, int q_heads, int kv_heads, int max_ctx, float scale,
+                                void* workspace, size_t workspace_bytes, vila_stream_t stream);
 
 /* hipGraph helpers: capture whatever is enqueued on `stream` between begin/end, replay it later. */
 int vila_graph_begin(vila_stream_t stream);
@@ -442,13 +457,15 @@ int vila_gemv_w4_batch_bf16(const void* x, int64_t ldx, int n, const void* Wq, c
                             void* y, int N, int K, int mode, vila_stream_t stream);
 /* vila_llm_decode_step_batch with the q|k|v, o, gate/up and down projections of every layer read from `qlayers` [host] (W4A16 batched GEMVs).
  * `w` still supplies embed, norms, the q/k/v biases (one contiguous q|k|v vector) and the bf16 lm_head; its projection pointers are not read.
- * Same contract and limits as vila_llm_decode_step_batch (head_dim 128, max_ctx <= 2048, 1 <= n <= min(16, n_slots), q_heads * head_dim ==
+ * Same contract and limits as vila_llm_decode_step_batch (head_dim 128, max_ctx <= 2048, or <= 32768 with the _ctx workspace, 1 <= n <= min(16, n_slots), q_heads * head_dim ==
  * hidden), plus hidden % 128 == 0 and intermediate % 128 == 0; each is checked before anything is launched (-1). */
 size_t vila_llm_decode_batch_w4_workspace_bytes(const VilaLlmShape* s, int n);
+size_t vila_llm_decode_batch_w4_workspace_bytes_ctx(const VilaLlmShape* s, int n, int max_ctx);
 int vila_llm_decode_step_batch_w4(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers /*[host]*/, const VilaKvCache* cache,
                                   const VilaDecodeBatch* st, void* workspace, size_t workspace_bytes, vila_stream_t stream);
 /* the W4 batched step with the per-row pick of vila_llm_decode_step_batch_sample */
 size_t vila_llm_decode_batch_w4_sample_workspace_bytes(const VilaLlmShape* s, int n);
+size_t vila_llm_decode_batch_w4_sample_workspace_bytes_ctx(const VilaLlmShape* s, int n, int max_ctx);
 int vila_llm_decode_step_batch_w4_sample(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers /*[host]*/, const VilaKvCache* cache,
                                          const VilaDecodeBatch* st, void* workspace, size_t workspace_bytes, const VilaBatchSampling* sp,
                                          vila_stream_t stream);

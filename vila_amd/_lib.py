@@ -119,10 +119,17 @@ PROTOTYPES = {
     "vila_llm_decode_step_sample": (c_int, [C.POINTER(VilaLlmWeights), C.POINTER(VilaKvCache), C.POINTER(VilaDecodeState),
                                             c_void_p, c_size_t, C.POINTER(VilaSampling), c_void_p]),
     "vila_llm_decode_batch_workspace_bytes": (c_size_t, [C.POINTER(VilaLlmShape), c_int]),
+    "vila_llm_decode_batch_workspace_bytes_ctx": (c_size_t, [C.POINTER(VilaLlmShape), c_int, c_int]),
     "vila_llm_decode_step_batch": (c_int, [C.POINTER(VilaLlmWeights), C.POINTER(VilaKvCache), C.POINTER(VilaDecodeBatch), c_void_p, c_size_t, c_void_p]),
+    "vila_attn_decode_batch_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "vila_attn_decode_batch_bf16": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int,
+                                            c_float, c_void_p, c_size_t, c_void_p]),
+    "vila_decode_batch_force_slices": (None, [c_int]),
+    "vila_decode_batch_slices": (c_int, [c_int]),
     "vila_sample_batch_workspace_bytes": (c_size_t, [c_int]),
     "vila_sample_batch_f32": (c_int, [c_void_p, c_int64, c_int, c_int, C.POINTER(VilaBatchSampling), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "vila_llm_decode_batch_sample_workspace_bytes": (c_size_t, [C.POINTER(VilaLlmShape), c_int]),
+    "vila_llm_decode_batch_sample_workspace_bytes_ctx": (c_size_t, [C.POINTER(VilaLlmShape), c_int, c_int]),
     "vila_llm_decode_step_batch_sample": (c_int, [C.POINTER(VilaLlmWeights), C.POINTER(VilaKvCache), C.POINTER(VilaDecodeBatch), c_void_p, c_size_t,
                                                   C.POINTER(VilaBatchSampling), c_void_p]),
     "vila_graph_begin": (c_int, [c_void_p]),
@@ -195,9 +202,11 @@ PROTOTYPES = {
                                                C.POINTER(VilaDecodeState), c_void_p, c_size_t, C.POINTER(VilaSampling), c_void_p]),
     "vila_gemv_w4_batch_bf16": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "vila_llm_decode_batch_w4_workspace_bytes": (c_size_t, [C.POINTER(VilaLlmShape), c_int]),
+    "vila_llm_decode_batch_w4_workspace_bytes_ctx": (c_size_t, [C.POINTER(VilaLlmShape), c_int, c_int]),
     "vila_llm_decode_step_batch_w4": (c_int, [C.POINTER(VilaLlmWeights), C.POINTER(VilaLlmLayerW4), C.POINTER(VilaKvCache),
                                               C.POINTER(VilaDecodeBatch), c_void_p, c_size_t, c_void_p]),
     "vila_llm_decode_batch_w4_sample_workspace_bytes": (c_size_t, [C.POINTER(VilaLlmShape), c_int]),
+    "vila_llm_decode_batch_w4_sample_workspace_bytes_ctx": (c_size_t, [C.POINTER(VilaLlmShape), c_int, c_int]),
     "vila_llm_decode_step_batch_w4_sample": (c_int, [C.POINTER(VilaLlmWeights), C.POINTER(VilaLlmLayerW4), C.POINTER(VilaKvCache),
                                                      C.POINTER(VilaDecodeBatch), c_void_p, c_size_t, C.POINTER(VilaBatchSampling), c_void_p]),
     "vila_gemm_w4_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),

@@ -662,14 +662,18 @@ static int decode_step_impl(const VilaLlmWeights* w, const VilaLlmLayerW4* ql, c
 // A sampled batched step keeps the greedy step's workspace layout and puts the sampler's candidates behind it: with `sp` set, the step's share of
 // *workspace_bytes shrinks to the greedy size and `out` points at the tail.
 struct BatchSamplingWs { const BatchSampling* sp; void* ws; };
-static int batch_sampling_of(const VilaBatchSampling* sp, const VilaLlmShape* sh, int n, void* workspace, size_t* workspace_bytes, BatchSampling* bs,
-                             BatchSamplingWs* out) {
+static int batch_sampling_of(const VilaBatchSampling* sp, const VilaLlmShape* sh, int n, int max_ctx, void* workspace, size_t* workspace_bytes,
+                             BatchSampling* bs, BatchSamplingWs* out) {
     out->sp = nullptr; out->ws = nullptr;
     if (sp == nullptr) return 0;
     VILA_REQUIRE(sp->temperature != nullptr && sp->top_k != nullptr && sp->top_p != nullptr && sp->seed != nullptr,
                  "llm_decode_batch_sample: a per-row parameter array is NULL");
     VILA_REQUIRE(n >= 1 && n <= 16, "llm_decode_batch_sample: 1..16 sequences (got %d)", n);
-    const size_t head = align_up(bdecode_workspace_bytes(sh->hidden, sh->inter, sh->q_heads * sh->head_dim, sh->head_dim, n), 256);
+    VILA_REQUIRE(max_ctx >= 1 && max_ctx <= BDEC_MAX_CTX, "llm_decode_batch_sample: caches up to %d positions (got %d)", BDEC_MAX_CTX, max_ctx);
+    const size_t head = align_up(bdecode_workspace_bytes(sh->hidden, sh->inter, sh->q_heads * sh->head_dim, sh->head_dim, n, max_ctx), 256);
+    VILA_REQUIRE(max_ctx <= BDEC_SHORT_CTX || *workspace_bytes >= head + sample_batch_workspace_bytes(n),
+                 "llm_decode_batch_sample: caches beyond 2048 positions need the workspace of vila_llm_decode_batch*_sample_workspace_bytes_ctx (%d positions)",
+                 max_ctx);
     VILA_REQUIRE(*workspace_bytes >= head + sample_batch_workspace_bytes(n), "llm_decode_batch_sample: workspace too small");
     *bs = BatchSampling{sp->temperature, sp->top_k, sp->top_p, sp->seed};
     out->sp = bs; out->ws = (char*)workspace + head;
@@ -696,10 +700,31 @@ static int decode_step_batch_impl(const VilaLlmWeights* w, const VilaKvCache* ca
     BDecodeArgs m{w->embed, w->norm_w, w->lm_head, sh.hidden, sh.inter, sh.n_layers, sh.q_heads, sh.kv_heads, sh.head_dim, sh.vocab, sh.rms_eps, sh.rope_theta};
     BatchSampling bs{};
     BatchSamplingWs sw{};
-    VILA_TRY(batch_sampling_of(sp, &sh, st->n, workspace, &workspace_bytes, &bs, &sw));
+    VILA_TRY(batch_sampling_of(sp, &sh, st->n, cache->max_ctx, workspace, &workspace_bytes, &bs, &sw));
     return bdecode_step(m, layers.data(), B(cache->k), B(cache->v), cache->max_ctx, cache->n_slots, st->n, st->pos, st->token, st->out_ids, st->n_out,
                         st->max_out, st->logits, workspace, workspace_bytes, s, nullptr, sw.sp, sw.ws);
 }
+// the sizes by capacity: up to 2048 positions what the functions without `_ctx` return, beyond that room for the walking attention's partials
+static size_t decode_batch_ws_ctx(const VilaLlmShape* s, int n, int max_ctx, bool sample) {
+    const size_t b = bdecode_workspace_bytes(s->hidden, s->inter, s->q_heads * s->head_dim, s->head_dim, n, max_ctx);
+    return sample ? align_up(b, 256) + sample_batch_workspace_bytes(n) : b;
+}
+extern "C" size_t vila_llm_decode_batch_workspace_bytes_ctx(const VilaLlmShape* s, int n, int max_ctx) { return decode_batch_ws_ctx(s, n, max_ctx, false); }
+extern "C" size_t vila_llm_decode_batch_sample_workspace_bytes_ctx(const VilaLlmShape* s, int n, int max_ctx) { return decode_batch_ws_ctx(s, n, max_ctx, true); }
+extern "C" size_t vila_llm_decode_batch_w4_workspace_bytes_ctx(const VilaLlmShape* s, int n, int max_ctx) { return decode_batch_ws_ctx(s, n, max_ctx, false); }
+extern "C" size_t vila_llm_decode_batch_w4_sample_workspace_bytes_ctx(const VilaLlmShape* s, int n, int max_ctx) {
+    return decode_batch_ws_ctx(s, n, max_ctx, true);
+}
+// the batched step's attention alone (operator level): the form is chosen as the step chooses it
+extern "C" size_t vila_attn_decode_batch_workspace_bytes(int n_rows, int q_heads, int max_ctx) { return bdecode_attn_workspace_bytes(n_rows, q_heads, max_ctx); }
+extern "C" int vila_attn_decode_batch_bf16(const void* q, int64_t ldq, const void* kcache, const void* vcache, int64_t slot_stride, const int32_t* pos, void* o,
+                                           int64_t ldo, int n_rows, int q_heads, int kv_heads, int max_ctx, float scale, void* workspace,
+                                           size_t workspace_bytes, vila_stream_t stream) {
+    return bdecode_attn(B(q), ldq, B(kcache), B(vcache), slot_stride, pos, (bf16_t*)o, ldo, n_rows, q_heads, kv_heads, max_ctx, scale, workspace,
+                        workspace_bytes, S(stream));
+}
+extern "C" void vila_decode_batch_force_slices(int nsl) { bdecode_force_slices(nsl); }
+extern "C" int vila_decode_batch_slices(int max_ctx) { return bdecode_attn_slices(max_ctx); }
 extern "C" int vila_llm_decode_step_batch(const VilaLlmWeights* w, const VilaKvCache* cache, const VilaDecodeBatch* st,
                                           void* workspace, size_t workspace_bytes, vila_stream_t stream) {
     return decode_step_batch_impl(w, cache, st, workspace, workspace_bytes, nullptr, stream);
@@ -740,7 +765,7 @@ static int decode_step_batch_w4_impl(const VilaLlmWeights* w, const VilaLlmLayer
     BDecodeArgs m{w->embed, w->norm_w, w->lm_head, sh.hidden, sh.inter, sh.n_layers, sh.q_heads, sh.kv_heads, sh.head_dim, sh.vocab, sh.rms_eps, sh.rope_theta};
     BatchSampling bs{};
     BatchSamplingWs sw{};
-    VILA_TRY(batch_sampling_of(sp, &sh, st->n, workspace, &workspace_bytes, &bs, &sw));
+    VILA_TRY(batch_sampling_of(sp, &sh, st->n, cache->max_ctx, workspace, &workspace_bytes, &bs, &sw));
     return bdecode_step(m, layers.data(), B(cache->k), B(cache->v), cache->max_ctx, cache->n_slots, st->n, st->pos, st->token, st->out_ids, st->n_out,
                         st->max_out, st->logits, workspace, workspace_bytes, s, ql.data(), sw.sp, sw.ws);
 }

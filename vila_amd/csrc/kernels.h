@@ -151,7 +151,19 @@ struct BLayer { const void *ln1_w, *wqkv, *bqkv, *wo, *ln2_w, *w_gate, *w_up, *w
 // the int4 projections of a layer (quant.py W4Weights, layout gemv_w4.hip); with them the step runs the four projections as W4A16 batched
 // GEMVs (gemv_w4_batch.hip) and reads no bf16 projection pointer of BLayer (bqkv, the fused q|k|v bias, is still read)
 struct BLayerW4 { const void *qkv_q, *qkv_sz, *o_q, *o_sz, *gateup_q, *gateup_sz, *down_q, *down_sz; };
-size_t bdecode_workspace_bytes(int H, int F, int QS, int hd, int n);
+// attention of the batched step: up to BDEC_SHORT_CTX positions one slice per 256-key chunk of the capacity; beyond, blocks walk chunks s, s + nsl, ...
+// with nsl = min(chunks of the capacity, BDEC_SLICE_CAP).  BDEC_MAX_SLICES bounds what the test hook may force (and sizes the long workspace).
+#define BDEC_SHORT_CTX 2048
+#define BDEC_MAX_CTX 32768        // Qwen2.5's max_position_embeddings
+#define BDEC_SLICE_CAP 8          // measured against 16 and 32 (profiles/long_batch_decode_bench.json): best at n = 8 and 16, within 1 - 4 % at n = 2
+#define BDEC_MAX_SLICES 32
+size_t bdecode_workspace_bytes(int H, int F, int QS, int hd, int n, int max_ctx = BDEC_SHORT_CTX);   // the same bytes for every max_ctx <= 2048
+void bdecode_force_slices(int nsl);
+int bdecode_attn_slices(int max_ctx);   // slices of the walking form at this capacity under the current hook, 0 = the short form
+// the step's attention on its own: q [rows][ldq], o [rows][ldo], one layer's cache [slots][nkv][max_ctx][128], keys 0 .. pos[row] of slot `row`
+size_t bdecode_attn_workspace_bytes(int rows, int nq, int max_ctx);
+int bdecode_attn(const bf16_t* q, int64_t ldq, const bf16_t* kcache, const bf16_t* vcache, int64_t slot_stride, const int32_t* pos, bf16_t* o, int64_t ldo,
+                 int rows, int nq, int nkv, int max_ctx, float scale, void* workspace, size_t workspace_bytes, hipStream_t s);
 int bdecode_step(const BDecodeArgs& m, const BLayer* layers, bf16_t* kcache, bf16_t* vcache, int max_ctx, int n_slots, int n, int32_t* pos, int64_t* token,
                  int64_t* out_ids, int32_t* n_out, int max_out, float* logits, void* workspace, size_t workspace_bytes, hipStream_t s,
                  const BLayerW4* qlayers = nullptr, const BatchSampling* sampling = nullptr, void* sampling_ws = nullptr);

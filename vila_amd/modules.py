@@ -573,7 +573,16 @@ class HipQwen2ForCausalLM(_HipModule):
             ok = forced_ids is None and not return_logits
         return (ok and cache is None and self.can_batch_decode_step() and
                 max_new_tokens >= 1 and (self._w4_batched() or self._qkv_fused()) and 2 <= Bn <= 16 and c.hidden_size % 64 == 0 and
-                c.intermediate_size % 64 == 0 and ((S + max_new_tokens + 255) // 256) * 256 <= 2048)
+                c.intermediate_size % 64 == 0 and ((S + max_new_tokens + 255) // 256) * 256 <= self.BATCH_MAX_CTX and
+                (S + max_new_tokens <= 2048 or self._long_batch_group_ok()))
+
+    # the batched step's caches: up to 2048 positions one attention slice per 256-key chunk, beyond that blocks that walk chunks (up to Qwen2.5's
+    # max_position_embeddings; GQA groups of 1, 2, 4, 7 or 8)
+    BATCH_MAX_CTX = 32768
+
+    def _long_batch_group_ok(self) -> bool:
+        c = self.lcfg
+        return c.num_attention_heads % c.num_key_value_heads == 0 and c.num_attention_heads // c.num_key_value_heads in (1, 2, 4, 7, 8)
 
     def _w4_batched(self) -> bool:
         """The batched step reads the int4 layers (quantize_w4(batch_decode=True))."""
@@ -612,6 +621,7 @@ class HipQwen2ForCausalLM(_HipModule):
             _lib.load().vila_graph_destroy(st.graph)
         dev, lib, w = self.device, _lib.load(), self._struct()
         st = SimpleNamespace(key=key, graph=None, sampling=bool(sampling), sp=None)
+        st.attn_slices = int(lib.vila_decode_batch_slices(int(max_ctx)))     # walking-attention slices the steps of this session launch (0: short form)
         with torch.inference_mode(False):
             st.cache = self.new_cache(max_ctx, n_slots=n)
             st.pos = torch.zeros(n, device=dev, dtype=torch.int32)
@@ -619,15 +629,15 @@ class HipQwen2ForCausalLM(_HipModule):
             st.out_ids = torch.zeros((n, max(max_new_tokens, 1)), device=dev, dtype=torch.int64)
             st.n_out = torch.zeros(n, device=dev, dtype=torch.int32)
             st.logits = torch.zeros((n, self.lcfg.vocab_size), device=dev, dtype=torch.float32)
-            ws_bytes = lib.vila_llm_decode_batch_w4_workspace_bytes if w4 else lib.vila_llm_decode_batch_workspace_bytes
+            ws_bytes = lib.vila_llm_decode_batch_w4_workspace_bytes_ctx if w4 else lib.vila_llm_decode_batch_workspace_bytes_ctx
             if sampling:
-                ws_bytes = lib.vila_llm_decode_batch_w4_sample_workspace_bytes if w4 else lib.vila_llm_decode_batch_sample_workspace_bytes
+                ws_bytes = lib.vila_llm_decode_batch_w4_sample_workspace_bytes_ctx if w4 else lib.vila_llm_decode_batch_sample_workspace_bytes_ctx
                 st.s_temperature = torch.zeros(n, device=dev, dtype=torch.float32)          # 0 = greedy row
                 st.s_top_k = torch.full((n,), 50, device=dev, dtype=torch.int32)
                 st.s_top_p = torch.ones(n, device=dev, dtype=torch.float32)
                 st.s_seed = torch.zeros(n, device=dev, dtype=torch.int64)                   # bit patterns of uint64 seeds
                 st.sp = _lib.VilaBatchSampling(st.s_temperature.data_ptr(), st.s_top_k.data_ptr(), st.s_top_p.data_ptr(), st.s_seed.data_ptr())
-            st.ws = torch.empty((ws_bytes(C.byref(w.shape), n),), device=dev, dtype=torch.uint8)
+            st.ws = torch.empty((ws_bytes(C.byref(w.shape), n, int(max_ctx)),), device=dev, dtype=torch.uint8)    # (<= 2048 positions: the size it always had)
         st.c = _lib.VilaDecodeBatch(n, st.pos.data_ptr(), st.token.data_ptr(), st.out_ids.data_ptr(), st.n_out.data_ptr(), max(max_new_tokens, 1),
                                     st.logits.data_ptr())
         st.stream = torch.cuda.Stream(device=dev)
@@ -685,9 +695,11 @@ class HipQwen2ForCausalLM(_HipModule):
         (`batch_admit(..., sampling=)`); the flag is part of the session key."""
         if not self._w4_batched():
             self._require_bf16("batch_open")
-        if not (1 <= n_slots <= 16 and max_ctx <= 2048 and self.can_batch_decode_step() and (self._w4_batched() or self._qkv_fused())):
+        long_ok = max_ctx <= 2048 or self._long_batch_group_ok()
+        if not (1 <= n_slots <= 16 and 1 <= max_ctx <= self.BATCH_MAX_CTX and long_ok and self.can_batch_decode_step() and
+                (self._w4_batched() or self._qkv_fused())):
             raise ValueError("batch_open: the batched decode step serves 1..16 rows of a head-dim-128 model (bf16, or quantize_w4(batch_decode=True)) "
-                             "with caches <= 2048 positions")
+                             f"with caches <= {self.BATCH_MAX_CTX} positions (beyond 2048: GQA groups of 1, 2, 4, 7 or 8 query heads)")
         st = self._batch_session(max(n_slots, 2), max_ctx, max_new_tokens, sampling)
         st.pos.zero_(); st.n_out.zero_(); st.token.zero_()
         if st.sampling:

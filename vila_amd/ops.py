@@ -259,6 +259,28 @@ def sample_batch(logits: torch.Tensor, temperature: torch.Tensor, top_k: torch.T
     return out
 
 
+def attn_decode_batch(q: torch.Tensor, kcache: torch.Tensor, vcache: torch.Tensor, pos: torch.Tensor, scale: Optional[float] = None) -> torch.Tensor:
+    """The batched decode step's attention on its own: q [n, q_heads, 128] bf16 (rows may be strided), kcache / vcache ONE layer's
+    [slots >= n, kv_heads, max_ctx, 128] bf16 (contiguous), pos [n] i32 — row i attends keys 0 .. pos[i] of slot i.  max_ctx up to 32768, GQA
+    groups of 1, 2, 4, 7 or 8; the kernel form is chosen as the step chooses it (`vila_decode_batch_force_slices`).  -> o [n, q_heads, 128]."""
+    _need(q, name="q"); _need(kcache, name="kcache"); _need(vcache, name="vcache"); _need(pos, dtype=torch.int32, name="pos")
+    if q.dim() != 3 or q.shape[2] != 128 or q.stride(2) != 1 or q.stride(1) != 128:
+        raise ValueError("attn_decode_batch: q must be [n, q_heads, 128] with contiguous heads")
+    n, nq, _ = q.shape
+    if kcache.dim() != 4 or kcache.shape != vcache.shape or kcache.shape[3] != 128 or not kcache.is_contiguous() or not vcache.is_contiguous():
+        raise ValueError("attn_decode_batch: kcache / vcache must be contiguous [slots, kv_heads, max_ctx, 128] of one shape")
+    slots, nkv, max_ctx, _ = kcache.shape
+    if slots < n or pos.numel() != n or not pos.is_contiguous():
+        raise ValueError(f"attn_decode_batch: {n} rows need {n} cache slots and {n} contiguous positions")
+    lib = _lib.load()
+    o = torch.empty((n, nq, 128), device=q.device, dtype=torch.bfloat16)
+    ws = torch.empty((lib.vila_attn_decode_batch_workspace_bytes(n, nq, max_ctx),), device=q.device, dtype=torch.uint8)
+    check(lib.vila_attn_decode_batch_bf16(q.data_ptr(), q.stride(0), kcache.data_ptr(), vcache.data_ptr(), kcache.stride(0), pos.data_ptr(), o.data_ptr(),
+                                          o.stride(0), n, nq, nkv, max_ctx, float(scale if scale is not None else 128 ** -0.5), ws.data_ptr(), ws.numel(),
+                                          _stream()), "attn_decode_batch")
+    return o
+
+
 def embed_tokens(table: torch.Tensor, ids: torch.Tensor) -> torch.Tensor:
     _need(table, name="embed table")
     ids = ids.to(device=table.device, dtype=torch.int64).contiguous()

@@ -516,7 +516,8 @@ class RequestBatcher:
 class HipBatchEngine:
     """The model side of `ContinuousBatcher`: KV slots of ONE open batched-decode session (`HipQwen2ForCausalLM.batch_open`), driven by
     the batcher's worker thread only.  sampling=True opens the session with per-row sampling (`batch_open(sampling=True)`): `admit` then takes
-    a row's (temperature, top_k, top_p, seed) and a `ContinuousBatcher(batch_sampled=True)` puts sampled requests into rows."""
+    a row's (temperature, top_k, top_p, seed) and a `ContinuousBatcher(batch_sampled=True)` puts sampled requests into rows.
+    max_ctx: positions per KV slot, up to 32768 (default 2048); `fits` admits what fits the slot, everything longer runs solo."""
 
     def __init__(self, model, tokenizer, n_slots: int = 8, max_ctx: int = 2048, max_new_tokens: int = 1024, eos_token_id=None,
                  sampling: bool = False):
@@ -858,14 +859,16 @@ def continuous_batching(model) -> bool:
 
 
 def create_app(model, tokenizer, model_name: str = "NVILA-8B", batch_window_s: Optional[float] = None, max_batch: int = 8,
-               stream_timeout_s: Optional[float] = 600.0, batch_sampled: bool = False):
+               stream_timeout_s: Optional[float] = 600.0, batch_sampled: bool = False, max_ctx: int = 2048):
     """FastAPI app with the reference's POST /chat/completions (server.py:171-290).  Import-time optional: needs fastapi + pydantic.
     batch_window_s: when set (any value), requests go through a batcher whose ONE worker thread owns the model: `ContinuousBatcher` (greedy
     requests join / leave the batched decode step between steps; sampled ones run solo on the same thread) where the model has the batched
     step, else `RequestBatcher` (greedy requests that arrive within the window share a batch; the rest run under the batcher's lock).
     batch_sampled=True (with a ContinuousBatcher only): sampled requests — the default request, temperature 0.2 / top_p 0.9 / top_k 50 — join
     the batched step as rows instead of running solo.  The trade: the ids of a sampled request are no longer those of its solo run (the
-    batched step sums in another order); greedy requests are served exactly as before."""
+    batched step sums in another order); greedy requests are served exactly as before.
+    max_ctx (ContinuousBatcher only): positions per KV slot of the batched session, up to 32768.  The default 2048 keeps the KV memory as it was;
+    a larger value lets long prompts (dynamic_s2's 2304 image tokens, video, multi-image chats) take a row instead of running solo."""
     from fastapi import FastAPI
     from fastapi.responses import JSONResponse, StreamingResponse
 
@@ -874,7 +877,14 @@ def create_app(model, tokenizer, model_name: str = "NVILA-8B", batch_window_s: O
     batcher = None
     if batch_window_s is not None:
         if continuous_batching(model):
-            engine = HipBatchEngine(model, tokenizer, n_slots=max_batch, sampling=True) if batch_sampled else HipBatchEngine(model, tokenizer, n_slots=max_batch)
+            # the default call is the one it always was (keywords only when asked for): an engine class substituted for HipBatchEngine with the
+            # narrower constructor (model, tokenizer, n_slots), as tests/test_w4_batch_decode_cpu.py does, keeps working
+            kw = dict(n_slots=max_batch)
+            if int(max_ctx) != 2048:
+                kw["max_ctx"] = int(max_ctx)
+            if batch_sampled:
+                kw["sampling"] = True
+            engine = HipBatchEngine(model, tokenizer, **kw)
             batcher = ContinuousBatcher(engine, max_batch=max_batch, batch_sampled=batch_sampled)
         else:
             batcher = RequestBatcher(model, tokenizer, window_s=batch_window_s)
