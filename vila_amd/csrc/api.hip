@@ -58,6 +58,10 @@ hipStream_t vila_stream_enter(void* s) { return S((vila_stream_t)s); }
 namespace {
 inline const bf16_t* B(const void* p) { return (const bf16_t*)p; }
 inline bf16_t* B(void* p) { return (bf16_t*)p; }
+// q/k/v weights [q_rows | kv_rows | kv_rows, cols] and their biases are views of one fused buffer, in that order
+bool qkv_fused(const void* wq, const void* wk, const void* wv, const void* bq, const void* bk, const void* bv, size_t q_rows, size_t kv_rows, size_t cols) {
+    return B(wk) == B(wq) + q_rows * cols && B(wv) == B(wk) + kv_rows * cols && B(bk) == B(bq) + q_rows && B(bv) == B(bk) + kv_rows;
+}
 
 // the NEXT block's normalisation, offered to a GEMM whose split-K reduce can take it along (kernels.h GemmArgs::norm_*)
 struct NextNorm { const void* w = nullptr; const void* b = nullptr; float eps = 0.f; int rms = 0; bf16_t* out = nullptr; int* done = nullptr; };
@@ -131,9 +135,7 @@ extern "C" int vila_vit_forward(const VilaVitWeights* w, const void* pixels, int
         bf16_t* xo = (l == sh.n_layers_run - 1) ? B(out) : x;   // last layer writes straight into `out`
         if (!ln1_done) VILA_TRY(launch_layernorm(x, B(L.ln1_w), B(L.ln1_b), h, M, D, sh.ln_eps, s));
         ln1_done = 0;
-        const bool fused = (B(L.wk) == B(L.wq) + (size_t)D * D) && (B(L.wv) == B(L.wk) + (size_t)D * D) &&
-                           (B(L.bk) == B(L.bq) + D) && (B(L.bv) == B(L.bk) + D);
-        if (fused) {
+        if (qkv_fused(L.wq, L.wk, L.wv, L.bq, L.bk, L.bv, D, D, D)) {
             VILA_TRY(gemm(h, D, L.wq, D, L.bq, nullptr, 0, qkv, 3 * D, M, 3 * D, D, EPI_NONE, s));
         } else {
             VILA_TRY(gemm(h, D, L.wq, D, L.bq, nullptr, 0, qkv, 3 * D, M, D, D, EPI_NONE, s));
@@ -396,11 +398,9 @@ static int llm_prefill_impl(const VilaLlmWeights* w, const VilaLlmLayerW4* ql, c
             kc = B(cache->k) + l * per_layer; vc = B(cache->v) + l * per_layer; max_ctx = cache->max_ctx;
         }
         int rope_done = 0;
-        const bool fused = !w4 && (B(L.wk) == B(L.wq) + (size_t)QS * H) && (B(L.wv) == B(L.wk) + (size_t)KS * H) &&
-                           (B(L.bk) == B(L.bq) + QS) && (B(L.bv) == B(L.bk) + KS);
         if (w4) {
             VILA_TRY(gemm4(h, Q.qkv_q, Q.qkv_sz, L.bq, nullptr, qkv, QKV, H, 2));                 // q | k | v + bias, natural column order
-        } else if (fused) {
+        } else if (qkv_fused(L.wq, L.wk, L.wv, L.bq, L.bk, L.bv, QS, KS, H)) {
             // one GEMM for q | k | v; where its grid is K-sliced (S = 769: 54 tiles x 4 slices) the reduce adds the bias, rotates q and k and
             // writes K / V into the cache (VILA_PREFILL_QKV_SPLITK=0: ring GEMM + rope_kv_kernel as in rounds 1-5)
             NextRope nr;
@@ -614,9 +614,7 @@ static int decode_step_impl(const VilaLlmWeights* w, const VilaLlmLayerW4* ql, c
             qa.rope_cs = rope_cs; qa.nq = sh.q_heads; qa.nkv = sh.kv_heads; qa.hd = hd; qa.max_ctx = cache->max_ctx;
             VILA_TRY(launch_gemv_w4(qa, s));
         } else {
-            const bool fused = (B(L.wk) == B(L.wq) + (size_t)QS * H) && (B(L.wv) == B(L.wk) + (size_t)KS * H) &&
-                               (B(L.bk) == B(L.bq) + QS) && (B(L.bv) == B(L.bk) + KS);
-            VILA_REQUIRE(fused, "llm_decode: q/k/v projection weights and biases must be views of one fused [q+2kv, hidden] buffer");
+            VILA_REQUIRE(qkv_fused(L.wq, L.wk, L.wv, L.bq, L.bk, L.bv, QS, KS, H), "llm_decode: q/k/v projection weights and biases must be views of one fused [q+2kv, hidden] buffer");
             QkvDecodeArgs qa{};
             qa.x = cur; qa.norm_w = B(L.ln1_w); qa.eps = sh.rms_eps; qa.Wqkv = B(L.wq); qa.bqkv = B(L.bq); qa.q_out = q;
             qa.kcache = kc; qa.vcache = vc; qa.pos_ptr = st->pos; qa.K = H; qa.nq = sh.q_heads; qa.nkv = sh.kv_heads; qa.hd = hd;
@@ -680,40 +678,77 @@ static int batch_sampling_of(const VilaBatchSampling* sp, const VilaLlmShape* sh
     *workspace_bytes = head;
     return 0;
 }
-extern "C" size_t vila_llm_decode_batch_workspace_bytes(const VilaLlmShape* s, int n) {
-    return bdecode_workspace_bytes(s->hidden, s->inter, s->q_heads * s->head_dim, s->head_dim, n);
+// the sizes by capacity: up to 2048 positions what the functions without `_ctx` return, beyond that room for the walking attention's partials.
+// Two sizes, greedy and sampled: the W4 step lays its workspace out as the bf16 step does.
+static size_t decode_batch_ws_ctx(const VilaLlmShape* s, int n, int max_ctx, bool sample) {
+    const size_t b = bdecode_workspace_bytes(s->hidden, s->inter, s->q_heads * s->head_dim, s->head_dim, n, max_ctx);
+    return sample ? align_up(b, 256) + sample_batch_workspace_bytes(n) : b;
 }
-static int decode_step_batch_impl(const VilaLlmWeights* w, const VilaKvCache* cache, const VilaDecodeBatch* st, void* workspace, size_t workspace_bytes,
-                                  const VilaBatchSampling* sp, vila_stream_t stream) {
-    VILA_REQUIRE(w != nullptr && cache != nullptr && st != nullptr && workspace != nullptr, "llm_decode_batch: NULL argument");
+extern "C" size_t vila_llm_decode_batch_workspace_bytes(const VilaLlmShape* s, int n) { return decode_batch_ws_ctx(s, n, BDEC_SHORT_CTX, false); }
+extern "C" size_t vila_llm_decode_batch_sample_workspace_bytes(const VilaLlmShape* s, int n) { return decode_batch_ws_ctx(s, n, BDEC_SHORT_CTX, true); }
+extern "C" size_t vila_llm_decode_batch_w4_workspace_bytes(const VilaLlmShape* s, int n) { return decode_batch_ws_ctx(s, n, BDEC_SHORT_CTX, false); }
+extern "C" size_t vila_llm_decode_batch_w4_sample_workspace_bytes(const VilaLlmShape* s, int n) { return decode_batch_ws_ctx(s, n, BDEC_SHORT_CTX, true); }
+extern "C" size_t vila_llm_decode_batch_workspace_bytes_ctx(const VilaLlmShape* s, int n, int max_ctx) { return decode_batch_ws_ctx(s, n, max_ctx, false); }
+extern "C" size_t vila_llm_decode_batch_sample_workspace_bytes_ctx(const VilaLlmShape* s, int n, int max_ctx) { return decode_batch_ws_ctx(s, n, max_ctx, true); }
+extern "C" size_t vila_llm_decode_batch_w4_workspace_bytes_ctx(const VilaLlmShape* s, int n, int max_ctx) { return decode_batch_ws_ctx(s, n, max_ctx, false); }
+extern "C" size_t vila_llm_decode_batch_w4_sample_workspace_bytes_ctx(const VilaLlmShape* s, int n, int max_ctx) { return decode_batch_ws_ctx(s, n, max_ctx, true); }
+
+// The batched step: qlayers == nullptr runs the bf16 projections; otherwise the four projections of every layer are read from the int4 layers
+// (gemv_w4_batch.hip) and embed, norms, the fused q|k|v biases and the bf16 lm_head come from `w`, whose projection pointers are not read (empty
+// after quantize_w4(release_bf16=True)).  sp != nullptr: a per-row pick (sample.hip's batched sampler) instead of the greedy pair; everything
+// before the pick is the same launches.
+static int decode_step_batch_impl(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers, const VilaKvCache* cache, const VilaDecodeBatch* st,
+                                  void* workspace, size_t workspace_bytes, const VilaBatchSampling* sp, vila_stream_t stream) {
+    const bool w4 = qlayers != nullptr;
+    const char* fn = w4 ? "llm_decode_batch_w4" : "llm_decode_batch";
+    VILA_REQUIRE(w != nullptr && cache != nullptr && st != nullptr && workspace != nullptr, "%s: NULL argument", fn);
     const VilaLlmShape& sh = w->shape;
     hipStream_t s = S(stream);
-    const int hd = sh.head_dim, QS = sh.q_heads * hd, KS = sh.kv_heads * hd, H = sh.hidden;
+    const int QS = sh.q_heads * sh.head_dim, KS = sh.kv_heads * sh.head_dim;
     std::vector<BLayer> layers(sh.n_layers);
+    std::vector<BLayerW4> ql(w4 ? sh.n_layers : 0);
     for (int l = 0; l < sh.n_layers; ++l) {
         const VilaLlmLayer& L = w->layers[l];
-        const bool fused = (B(L.wk) == B(L.wq) + (size_t)QS * H) && (B(L.wv) == B(L.wk) + (size_t)KS * H) &&
-                           (B(L.bk) == B(L.bq) + QS) && (B(L.bv) == B(L.bk) + KS);
-        VILA_REQUIRE(fused, "llm_decode_batch: q/k/v projection weights and biases must be views of one fused [q+2kv, hidden] buffer");
-        layers[l] = BLayer{L.ln1_w, L.wq, L.bq, L.wo, L.ln2_w, L.w_gate, L.w_up, L.w_down};
+        if (w4) {
+            const VilaLlmLayerW4& Q = qlayers[l];
+            VILA_REQUIRE(L.bq != nullptr && B(L.bk) == B(L.bq) + QS && B(L.bv) == B(L.bk) + KS,
+                         "llm_decode_batch_w4: the q/k/v biases must be one contiguous q|k|v vector (layer %d)", l);
+            VILA_REQUIRE(Q.qkv_q && Q.qkv_sz && Q.o_q && Q.o_sz && Q.gateup_q && Q.gateup_sz && Q.down_q && Q.down_sz,
+                         "llm_decode_batch_w4: int4 layer %d has a NULL buffer", l);
+            layers[l] = BLayer{L.ln1_w, nullptr, L.bq, nullptr, L.ln2_w, nullptr, nullptr, nullptr};
+            ql[l] = BLayerW4{Q.qkv_q, Q.qkv_sz, Q.o_q, Q.o_sz, Q.gateup_q, Q.gateup_sz, Q.down_q, Q.down_sz};
+        } else {
+            VILA_REQUIRE(qkv_fused(L.wq, L.wk, L.wv, L.bq, L.bk, L.bv, QS, KS, sh.hidden),
+                         "llm_decode_batch: q/k/v projection weights and biases must be views of one fused [q+2kv, hidden] buffer");
+            layers[l] = BLayer{L.ln1_w, L.wq, L.bq, L.wo, L.ln2_w, L.w_gate, L.w_up, L.w_down};
+        }
     }
     BDecodeArgs m{w->embed, w->norm_w, w->lm_head, sh.hidden, sh.inter, sh.n_layers, sh.q_heads, sh.kv_heads, sh.head_dim, sh.vocab, sh.rms_eps, sh.rope_theta};
     BatchSampling bs{};
     BatchSamplingWs sw{};
     VILA_TRY(batch_sampling_of(sp, &sh, st->n, cache->max_ctx, workspace, &workspace_bytes, &bs, &sw));
     return bdecode_step(m, layers.data(), B(cache->k), B(cache->v), cache->max_ctx, cache->n_slots, st->n, st->pos, st->token, st->out_ids, st->n_out,
-                        st->max_out, st->logits, workspace, workspace_bytes, s, nullptr, sw.sp, sw.ws);
+                        st->max_out, st->logits, workspace, workspace_bytes, s, w4 ? ql.data() : nullptr, sw.sp, sw.ws);
 }
-// the sizes by capacity: up to 2048 positions what the functions without `_ctx` return, beyond that room for the walking attention's partials
-static size_t decode_batch_ws_ctx(const VilaLlmShape* s, int n, int max_ctx, bool sample) {
-    const size_t b = bdecode_workspace_bytes(s->hidden, s->inter, s->q_heads * s->head_dim, s->head_dim, n, max_ctx);
-    return sample ? align_up(b, 256) + sample_batch_workspace_bytes(n) : b;
+extern "C" int vila_llm_decode_step_batch(const VilaLlmWeights* w, const VilaKvCache* cache, const VilaDecodeBatch* st,
+                                          void* workspace, size_t workspace_bytes, vila_stream_t stream) {
+    return decode_step_batch_impl(w, nullptr, cache, st, workspace, workspace_bytes, nullptr, stream);
 }
-extern "C" size_t vila_llm_decode_batch_workspace_bytes_ctx(const VilaLlmShape* s, int n, int max_ctx) { return decode_batch_ws_ctx(s, n, max_ctx, false); }
-extern "C" size_t vila_llm_decode_batch_sample_workspace_bytes_ctx(const VilaLlmShape* s, int n, int max_ctx) { return decode_batch_ws_ctx(s, n, max_ctx, true); }
-extern "C" size_t vila_llm_decode_batch_w4_workspace_bytes_ctx(const VilaLlmShape* s, int n, int max_ctx) { return decode_batch_ws_ctx(s, n, max_ctx, false); }
-extern "C" size_t vila_llm_decode_batch_w4_sample_workspace_bytes_ctx(const VilaLlmShape* s, int n, int max_ctx) {
-    return decode_batch_ws_ctx(s, n, max_ctx, true);
+extern "C" int vila_llm_decode_step_batch_sample(const VilaLlmWeights* w, const VilaKvCache* cache, const VilaDecodeBatch* st,
+                                                 void* workspace, size_t workspace_bytes, const VilaBatchSampling* sp, vila_stream_t stream) {
+    VILA_REQUIRE(sp != nullptr, "llm_decode_batch_sample: sampling parameters are NULL");
+    return decode_step_batch_impl(w, nullptr, cache, st, workspace, workspace_bytes, sp, stream);
+}
+extern "C" int vila_llm_decode_step_batch_w4(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers, const VilaKvCache* cache, const VilaDecodeBatch* st,
+                                             void* workspace, size_t workspace_bytes, vila_stream_t stream) {
+    VILA_REQUIRE(qlayers != nullptr, "llm_decode_batch_w4: NULL argument");
+    return decode_step_batch_impl(w, qlayers, cache, st, workspace, workspace_bytes, nullptr, stream);
+}
+extern "C" int vila_llm_decode_step_batch_w4_sample(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers, const VilaKvCache* cache, const VilaDecodeBatch* st,
+                                                    void* workspace, size_t workspace_bytes, const VilaBatchSampling* sp, vila_stream_t stream) {
+    VILA_REQUIRE(sp != nullptr, "llm_decode_batch_w4_sample: sampling parameters are NULL");
+    VILA_REQUIRE(qlayers != nullptr, "llm_decode_batch_w4: NULL argument");
+    return decode_step_batch_impl(w, qlayers, cache, st, workspace, workspace_bytes, sp, stream);
 }
 // the batched step's attention alone (operator level): the form is chosen as the step chooses it
 extern "C" size_t vila_attn_decode_batch_workspace_bytes(int n_rows, int q_heads, int max_ctx) { return bdecode_attn_workspace_bytes(n_rows, q_heads, max_ctx); }
@@ -725,62 +760,6 @@ extern "C" int vila_attn_decode_batch_bf16(const void* q, int64_t ldq, const voi
 }
 extern "C" void vila_decode_batch_force_slices(int nsl) { bdecode_force_slices(nsl); }
 extern "C" int vila_decode_batch_slices(int max_ctx) { return bdecode_attn_slices(max_ctx); }
-extern "C" int vila_llm_decode_step_batch(const VilaLlmWeights* w, const VilaKvCache* cache, const VilaDecodeBatch* st,
-                                          void* workspace, size_t workspace_bytes, vila_stream_t stream) {
-    return decode_step_batch_impl(w, cache, st, workspace, workspace_bytes, nullptr, stream);
-}
-// the batched step with a per-row pick (sample.hip's batched sampler) instead of the greedy pair; everything before the pick is the same launches
-extern "C" size_t vila_llm_decode_batch_sample_workspace_bytes(const VilaLlmShape* s, int n) {
-    return align_up(vila_llm_decode_batch_workspace_bytes(s, n), 256) + sample_batch_workspace_bytes(n);
-}
-extern "C" int vila_llm_decode_step_batch_sample(const VilaLlmWeights* w, const VilaKvCache* cache, const VilaDecodeBatch* st,
-                                                 void* workspace, size_t workspace_bytes, const VilaBatchSampling* sp, vila_stream_t stream) {
-    VILA_REQUIRE(sp != nullptr, "llm_decode_batch_sample: sampling parameters are NULL");
-    return decode_step_batch_impl(w, cache, st, workspace, workspace_bytes, sp, stream);
-}
-
-// the batched step with the four projections of every layer read from the int4 layers (gemv_w4_batch.hip); embed, norms, the fused q|k|v
-// biases and the bf16 lm_head come from `w`, whose projection pointers are not read (empty after quantize_w4(release_bf16=True))
-extern "C" size_t vila_llm_decode_batch_w4_workspace_bytes(const VilaLlmShape* s, int n) {
-    return bdecode_workspace_bytes(s->hidden, s->inter, s->q_heads * s->head_dim, s->head_dim, n);
-}
-static int decode_step_batch_w4_impl(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers, const VilaKvCache* cache, const VilaDecodeBatch* st,
-                                     void* workspace, size_t workspace_bytes, const VilaBatchSampling* sp, vila_stream_t stream) {
-    VILA_REQUIRE(w != nullptr && qlayers != nullptr && cache != nullptr && st != nullptr && workspace != nullptr, "llm_decode_batch_w4: NULL argument");
-    const VilaLlmShape& sh = w->shape;
-    hipStream_t s = S(stream);
-    const int QS = sh.q_heads * sh.head_dim, KS = sh.kv_heads * sh.head_dim;
-    std::vector<BLayer> layers(sh.n_layers);
-    std::vector<BLayerW4> ql(sh.n_layers);
-    for (int l = 0; l < sh.n_layers; ++l) {
-        const VilaLlmLayer& L = w->layers[l];
-        const VilaLlmLayerW4& Q = qlayers[l];
-        VILA_REQUIRE(L.bq != nullptr && B(L.bk) == B(L.bq) + QS && B(L.bv) == B(L.bk) + KS,
-                     "llm_decode_batch_w4: the q/k/v biases must be one contiguous q|k|v vector (layer %d)", l);
-        VILA_REQUIRE(Q.qkv_q && Q.qkv_sz && Q.o_q && Q.o_sz && Q.gateup_q && Q.gateup_sz && Q.down_q && Q.down_sz,
-                     "llm_decode_batch_w4: int4 layer %d has a NULL buffer", l);
-        layers[l] = BLayer{L.ln1_w, nullptr, L.bq, nullptr, L.ln2_w, nullptr, nullptr, nullptr};
-        ql[l] = BLayerW4{Q.qkv_q, Q.qkv_sz, Q.o_q, Q.o_sz, Q.gateup_q, Q.gateup_sz, Q.down_q, Q.down_sz};
-    }
-    BDecodeArgs m{w->embed, w->norm_w, w->lm_head, sh.hidden, sh.inter, sh.n_layers, sh.q_heads, sh.kv_heads, sh.head_dim, sh.vocab, sh.rms_eps, sh.rope_theta};
-    BatchSampling bs{};
-    BatchSamplingWs sw{};
-    VILA_TRY(batch_sampling_of(sp, &sh, st->n, cache->max_ctx, workspace, &workspace_bytes, &bs, &sw));
-    return bdecode_step(m, layers.data(), B(cache->k), B(cache->v), cache->max_ctx, cache->n_slots, st->n, st->pos, st->token, st->out_ids, st->n_out,
-                        st->max_out, st->logits, workspace, workspace_bytes, s, ql.data(), sw.sp, sw.ws);
-}
-extern "C" int vila_llm_decode_step_batch_w4(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers, const VilaKvCache* cache, const VilaDecodeBatch* st,
-                                             void* workspace, size_t workspace_bytes, vila_stream_t stream) {
-    return decode_step_batch_w4_impl(w, qlayers, cache, st, workspace, workspace_bytes, nullptr, stream);
-}
-extern "C" size_t vila_llm_decode_batch_w4_sample_workspace_bytes(const VilaLlmShape* s, int n) {
-    return align_up(vila_llm_decode_batch_w4_workspace_bytes(s, n), 256) + sample_batch_workspace_bytes(n);
-}
-extern "C" int vila_llm_decode_step_batch_w4_sample(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers, const VilaKvCache* cache, const VilaDecodeBatch* st,
-                                                    void* workspace, size_t workspace_bytes, const VilaBatchSampling* sp, vila_stream_t stream) {
-    VILA_REQUIRE(sp != nullptr, "llm_decode_batch_w4_sample: sampling parameters are NULL");
-    return decode_step_batch_w4_impl(w, qlayers, cache, st, workspace, workspace_bytes, sp, stream);
-}
 
 // the batched sampler on its own (operator level: no state advance)
 extern "C" size_t vila_sample_batch_workspace_bytes(int n) { return sample_batch_workspace_bytes(n); }

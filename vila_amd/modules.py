@@ -55,6 +55,10 @@ def _fuse_groups(names: List[str]) -> Dict[str, Tuple[str, ...]]:
 class _HipModule(nn.Module):
     """Builds parameters from (name, shape, kind) specs, caches the ctypes weight structs, owns a grow-only workspace."""
 
+    _decode = None              # the LLM's batch-1 and batched decode sessions (`_decode_session`, `_batch_session`)
+    _bdecode = None
+    _bf16_released = False      # quantize_w4(release_bf16=True) freed the bf16 projection weights
+
     def _build_params(self, specs, prefix: str, device, dtype, requires_grad=False):
         names = [n for n, _, _ in specs]
         shapes = {n: s for n, s, _ in specs}
@@ -76,21 +80,19 @@ class _HipModule(nn.Module):
         self._cstruct = None
         self._ws = None
 
+    def _drop_session(self, attr: str) -> None:
+        """Destroy the session's captured graph, if it has one, and forget the session."""
+        st = getattr(self, attr)
+        if st is not None and getattr(st, "graph", None) is not None:
+            _lib.load().vila_graph_destroy(st.graph)
+            st.graph = None
+        setattr(self, attr, None)
+
     def _drop_decode_session(self) -> None:
-        st = getattr(self, "_decode", None)
-        if st is not None:
-            if getattr(st, "graph", None) is not None:
-                _lib.load().vila_graph_destroy(st.graph)
-                st.graph = None
-            self._decode = None
+        self._drop_session("_decode")
 
     def _drop_batch_session(self) -> None:
-        bst = getattr(self, "_bdecode", None)
-        if bst is not None:
-            if getattr(bst, "graph", None) is not None:
-                _lib.load().vila_graph_destroy(bst.graph)
-                bst.graph = None
-            self._bdecode = None
+        self._drop_session("_bdecode")
 
     def _invalidate(self) -> None:
         """Parameter storage moved (.to(), refuse(), FlatParams re-pointing, W4 quantisation): every cached object that baked in
@@ -103,7 +105,7 @@ class _HipModule(nn.Module):
 
     def refuse(self) -> None:
         """Re-establish the fused q/k/v storage after an op that re-allocated parameters (.to(), .half(), ...)."""
-        if getattr(self, "_bf16_released", False):
+        if self._bf16_released:
             raise RuntimeError("refuse: the bf16 projection weights were freed by quantize_w4(release_bf16=True); there is no q/k/v buffer to re-fuse")
         for g in self._fused_groups:
             ts = [_get(self, m) for m in g]
@@ -115,7 +117,7 @@ class _HipModule(nn.Module):
         self._invalidate()
 
     def _apply(self, fn, *a, **k):
-        if getattr(self, "_bf16_released", False):
+        if self._bf16_released:
             # .cuda() / .to() / .half() on a model whose bf16 projections were released: the int4 copies stay where they are, so only a
             # conversion that changes nothing is allowed (it leaves the model as it was); any other would split the model across devices / dtypes
             probe = torch.empty(0, device=self.device, dtype=self.dtype)
@@ -132,7 +134,7 @@ class _HipModule(nn.Module):
         return r
 
     def load_weights(self, w: Dict[str, torch.Tensor], prefix: str) -> None:
-        if getattr(self, "_bf16_released", False):
+        if self._bf16_released:
             raise RuntimeError("load_weights: the bf16 projection weights were freed by quantize_w4(release_bf16=True); build a new model")
         with torch.no_grad():
             for n, p in self.named_parameters():
@@ -292,12 +294,67 @@ def _as_i64(u: int) -> int:
     return u - (1 << 64) if u >= (1 << 63) else u
 
 
+def _step_symbols(batch: bool, w4: bool, sampled: bool) -> Tuple[str, str]:
+    """(step, workspace query) of one decode step variant, composed the way the C ABI names them."""
+    tail = ("_w4" if w4 else "") + ("_sample" if sampled else "")
+    if batch:
+        return "vila_llm_decode_step_batch" + tail, "vila_llm_decode_batch" + tail + "_workspace_bytes_ctx"
+    return "vila_llm_decode_step" + tail, "vila_llm_decode_workspace_bytes"
+
+
+def _capture(st, step, restore) -> None:
+    """Capture `step()` on st.stream into st.graph.  The step runs once outside capture first (kernel attributes cannot be set while
+    capturing); `restore()` then puts back the state that warm-up advanced, so the captured step starts where the caller left it."""
+    lib = _lib.load()
+    torch.cuda.current_stream().synchronize()
+    with torch.cuda.stream(st.stream):
+        step()
+        st.stream.synchronize()
+        restore()
+        check(lib.vila_graph_begin(st.stream.cuda_stream), "graph_begin")
+        step()
+        g = C.c_void_p()
+        check(lib.vila_graph_end(st.stream.cuda_stream, C.byref(g)), "graph_end")
+        st.graph = g
+        st.stream.synchronize()
+
+
+def _eos_set(eos_token_id, default=None) -> set:
+    """The ids that end a row: one id or a list of them, `default` (the config's EOS) where none is given."""
+    eos = default if eos_token_id is None else eos_token_id
+    return set(eos) if isinstance(eos, (list, tuple)) else {eos}
+
+
+def _pad_id(pad_token_id, eos_token_id, config_eos) -> int:
+    """HF's pad rule: pad_token_id, else the first EOS given, else the config's EOS."""
+    eos1 = eos_token_id[0] if isinstance(eos_token_id, (list, tuple)) else eos_token_id
+    return int(pad_token_id if pad_token_id is not None else (eos1 if eos1 is not None else config_eos))
+
+
+def _cut_at_eos(row: List[int], eos_set) -> List[int]:
+    """HF stops a row AFTER emitting eos."""
+    return row[:next((i + 1 for i, t in enumerate(row) if t in eos_set), len(row))]
+
+
+def finish_rows(rows: List[List[int]], eos_set, pad: int, device) -> torch.Tensor:
+    """Token lists -> [B, n] int64 like HF: each row cut after its first EOS, right-padded with `pad` to the longest."""
+    rows = [_cut_at_eos(r, eos_set) for r in rows]
+    n = max(len(r) for r in rows)
+    return torch.tensor([r + [int(pad)] * (n - len(r)) for r in rows], dtype=torch.int64, device=device)
+
+
 class CausalLMOutput(SimpleNamespace):
     """Fields of HF CausalLMOutputWithPast that llava_llama.py:134-159 consumes."""
 
 
 class HipQwen2ForCausalLM(_HipModule):
     """HF `Qwen2ForCausalLM` as used at llava_llama.py:134-141 (`forward`) and llava_arch.py:833 (`generate`)."""
+
+    _w4 = None                  # quant.W4Weights once quantize_w4 ran; the two flags say which other paths read it
+    _w4_prefill = False
+    _w4_batch = False
+    _own_cache = None           # generate()'s KV cache, kept across calls
+    _sample_calls = 0
 
     def __init__(self, cfg: VilaConfig, device="cuda", dtype=torch.bfloat16):
         super().__init__()
@@ -306,7 +363,6 @@ class HipQwen2ForCausalLM(_HipModule):
         self._build_params(synthetic.llm_specs(cfg), "llm.", device, dtype)
         self.config = SimpleNamespace(hidden_size=cfg.llm.hidden_size, vocab_size=cfg.llm.vocab_size,
                                       eos_token_id=cfg.llm.eos_token_id, tie_word_embeddings=cfg.llm.tie_word_embeddings)
-        self._decode = None
         # `llm.model.embed_tokens(ids)` is called directly by the reference (llava_arch.py:429, encoders/image/basic.py:27)
         emb = self.model.embed_tokens
         emb.forward = lambda ids, _w=emb: ops.embed_tokens(_w.weight, ids)
@@ -360,7 +416,7 @@ class HipQwen2ForCausalLM(_HipModule):
         dev = embeds.device
         lib = _lib.load()
         w = self._struct()
-        w4 = getattr(self, "_w4", None) if getattr(self, "_w4_prefill", False) else None
+        w4 = self._w4 if self._w4_prefill else None
         if w4 is None:
             self._require_bf16("the bf16 prefill")
         ws_bytes = (lib.vila_llm_prefill_w4_workspace_bytes if w4 is not None else lib.vila_llm_prefill_workspace_bytes)(C.byref(w.shape), T)
@@ -513,7 +569,7 @@ class HipQwen2ForCausalLM(_HipModule):
         decode (quantize_w4(prefill=True)).  Each projection parameter is re-pointed at a zero-element tensor [0, in_features] of its device
         and dtype, so its storage is freed and nothing can read stale memory through it: torch ops see an empty tensor, and every path of
         this package that would use the weights raises a RuntimeError naming release_bf16.  Returns the bytes of bf16 weights dropped."""
-        if getattr(self, "_w4", None) is None or not getattr(self, "_w4_prefill", False):
+        if self._w4 is None or not self._w4_prefill:
             raise RuntimeError("release_bf16 needs quantize_w4(prefill=True) first: the bf16 prefill reads these weights")
         proj = [_get(self, f"model.layers.{i}.{n}.weight") for i in range(self.lcfg.num_hidden_layers) for n in self._W4_PROJ]
         proj_bytes = {}
@@ -536,29 +592,21 @@ class HipQwen2ForCausalLM(_HipModule):
         return super()._load_from_state_dict(*a, **k)
 
     def _require_bf16(self, what: str) -> None:
-        if getattr(self, "_bf16_released", False):
+        if self._bf16_released:
             raise RuntimeError(f"{what}: the bf16 projection weights were freed by quantize_w4(release_bf16=True); only the W4A16 "
                                "prefill and decode can run on this model")
 
+    def _step(self, batch: bool, w4, cache, st, sp) -> None:
+        """One decode step on the current stream.  The variant is looked up at call time (`_step_symbols`): a caller may hold a session
+        across quantize_w4.  w4: the W4Weights whose int4 layers the step reads, or None; sp: the sampling struct, or None for the greedy pick."""
+        name, _ = _step_symbols(batch, w4 is not None, sp is not None)
+        args = [C.byref(self._struct())] + ([w4.ptr] if w4 is not None else []) + [C.byref(cache.c), C.byref(st.c), st.ws.data_ptr(), st.ws.numel()]
+        check(getattr(_lib.load(), name)(*args, *([C.byref(sp)] if sp is not None else []), ops._stream()), name)
+
     def decode_step(self, cache, st) -> None:
-        lib = _lib.load()
-        w4 = getattr(self, "_w4", None)
-        sp = getattr(st, "sampling", None)
-        if w4 is not None:
-            if sp is not None:
-                check(lib.vila_llm_decode_step_w4_sample(C.byref(self._struct()), w4.ptr, C.byref(cache.c), C.byref(st.c), st.ws.data_ptr(),
-                                                         st.ws.numel(), C.byref(sp), ops._stream()), "vila_llm_decode_step_w4_sample")
-                return
-            check(lib.vila_llm_decode_step_w4(C.byref(self._struct()), w4.ptr, C.byref(cache.c), C.byref(st.c), st.ws.data_ptr(),
-                                              st.ws.numel(), ops._stream()), "vila_llm_decode_step_w4")
-            return
-        self._require_bf16("the bf16 decode step")
-        if sp is not None:
-            check(lib.vila_llm_decode_step_sample(C.byref(self._struct()), C.byref(cache.c), C.byref(st.c), st.ws.data_ptr(), st.ws.numel(),
-                                                  C.byref(sp), ops._stream()), "vila_llm_decode_step_sample")
-            return
-        check(lib.vila_llm_decode_step(C.byref(self._struct()), C.byref(cache.c), C.byref(st.c), st.ws.data_ptr(), st.ws.numel(),
-                                       ops._stream()), "vila_llm_decode_step")
+        if self._w4 is None:
+            self._require_bf16("the bf16 decode step")
+        self._step(False, self._w4, cache, st, getattr(st, "sampling", None))
 
     # ---- batched greedy generate: one weight pass per step for up to 16 sequences (vila_llm_decode_step_batch) -----------------------
     def _can_batch_decode(self, inputs_embeds, attention_mask, max_new_tokens, do_sample, forced_ids, return_logits, cache,
@@ -586,12 +634,12 @@ class HipQwen2ForCausalLM(_HipModule):
 
     def _w4_batched(self) -> bool:
         """The batched step reads the int4 layers (quantize_w4(batch_decode=True))."""
-        return getattr(self, "_w4", None) is not None and getattr(self, "_w4_batch", False)
+        return self._w4 is not None and self._w4_batch
 
     def can_batch_decode_step(self) -> bool:
         """Whether this model has a batched decode step (batch_open / continuous batching): a head-dim-128 decoder that is bf16, or
         quantised with quantize_w4(batch_decode=True).  A model quantised without it decodes its rows one at a time."""
-        return self.lcfg.head_dim == 128 and (getattr(self, "_w4", None) is None or self._w4_batched())
+        return self.lcfg.head_dim == 128 and (self._w4 is None or self._w4_batched())
 
     def _qkv_fused(self) -> bool:
         """q/k/v of every layer are views of one buffer (the batched step reads them as ONE [q + 2kv, hidden] matrix); `refuse()` re-establishes
@@ -614,11 +662,9 @@ class HipQwen2ForCausalLM(_HipModule):
         q4 = self._w4.mats[0]["down"].q.data_ptr() if w4 else None
         key = (n, max_ctx, max_new_tokens, bool(sampling), self.model.embed_tokens.weight.data_ptr(),
                _get(self, "model.layers.0.mlp.down_proj.weight").data_ptr(), q4)
-        st = getattr(self, "_bdecode", None)
-        if st is not None and st.key == key:
-            return st
-        if st is not None and st.graph is not None:
-            _lib.load().vila_graph_destroy(st.graph)
+        if self._bdecode is not None and self._bdecode.key == key:
+            return self._bdecode
+        self._drop_session("_bdecode")
         dev, lib, w = self.device, _lib.load(), self._struct()
         st = SimpleNamespace(key=key, graph=None, sampling=bool(sampling), sp=None)
         st.attn_slices = int(lib.vila_decode_batch_slices(int(max_ctx)))     # walking-attention slices the steps of this session launch (0: short form)
@@ -629,9 +675,8 @@ class HipQwen2ForCausalLM(_HipModule):
             st.out_ids = torch.zeros((n, max(max_new_tokens, 1)), device=dev, dtype=torch.int64)
             st.n_out = torch.zeros(n, device=dev, dtype=torch.int32)
             st.logits = torch.zeros((n, self.lcfg.vocab_size), device=dev, dtype=torch.float32)
-            ws_bytes = lib.vila_llm_decode_batch_w4_workspace_bytes_ctx if w4 else lib.vila_llm_decode_batch_workspace_bytes_ctx
+            ws_bytes = getattr(lib, _step_symbols(True, w4, bool(sampling))[1])
             if sampling:
-                ws_bytes = lib.vila_llm_decode_batch_w4_sample_workspace_bytes_ctx if w4 else lib.vila_llm_decode_batch_sample_workspace_bytes_ctx
                 st.s_temperature = torch.zeros(n, device=dev, dtype=torch.float32)          # 0 = greedy row
                 st.s_top_k = torch.full((n,), 50, device=dev, dtype=torch.int32)
                 st.s_top_p = torch.ones(n, device=dev, dtype=torch.float32)
@@ -645,21 +690,7 @@ class HipQwen2ForCausalLM(_HipModule):
         return st
 
     def _batch_step(self, st) -> None:
-        if st.sampling:
-            if self._w4_batched():
-                check(_lib.load().vila_llm_decode_step_batch_w4_sample(C.byref(self._struct()), self._w4.ptr, C.byref(st.cache.c), C.byref(st.c),
-                                                                       st.ws.data_ptr(), st.ws.numel(), C.byref(st.sp), ops._stream()),
-                      "vila_llm_decode_step_batch_w4_sample")
-                return
-            check(_lib.load().vila_llm_decode_step_batch_sample(C.byref(self._struct()), C.byref(st.cache.c), C.byref(st.c), st.ws.data_ptr(),
-                                                                st.ws.numel(), C.byref(st.sp), ops._stream()), "vila_llm_decode_step_batch_sample")
-            return
-        if self._w4_batched():
-            check(_lib.load().vila_llm_decode_step_batch_w4(C.byref(self._struct()), self._w4.ptr, C.byref(st.cache.c), C.byref(st.c), st.ws.data_ptr(),
-                                                            st.ws.numel(), ops._stream()), "vila_llm_decode_step_batch_w4")
-            return
-        check(_lib.load().vila_llm_decode_step_batch(C.byref(self._struct()), C.byref(st.cache.c), C.byref(st.c), st.ws.data_ptr(), st.ws.numel(),
-                                                     ops._stream()), "vila_llm_decode_step_batch")
+        self._step(True, self._w4 if self._w4_batched() else None, st.cache, st, st.sp if st.sampling else None)
 
     # ---- continuous batching (server.py:171-290 serves requests as they arrive): rows join and leave BETWEEN steps ---------
     # `vila_llm_decode_step_batch` takes per-row positions / output counters, so admission is host work: prefill the newcomer alone into its
@@ -701,23 +732,15 @@ class HipQwen2ForCausalLM(_HipModule):
             raise ValueError("batch_open: the batched decode step serves 1..16 rows of a head-dim-128 model (bf16, or quantize_w4(batch_decode=True)) "
                              f"with caches <= {self.BATCH_MAX_CTX} positions (beyond 2048: GQA groups of 1, 2, 4, 7 or 8 query heads)")
         st = self._batch_session(max(n_slots, 2), max_ctx, max_new_tokens, sampling)
-        st.pos.zero_(); st.n_out.zero_(); st.token.zero_()
+        def reset():
+            st.pos.zero_(); st.n_out.zero_(); st.token.zero_()
+        reset()
         if st.sampling:
             st.s_temperature.zero_()                                   # every row starts greedy (idle)
         if st.graph is None:
-            lib = _lib.load()
-            torch.cuda.current_stream().synchronize()
+            _capture(st, lambda: self._batch_step(st), reset)
             with torch.cuda.stream(st.stream):
-                self._batch_step(st)                                   # warm-up outside capture (kernel attributes)
-                st.stream.synchronize()
-                st.pos.zero_(); st.n_out.zero_(); st.token.zero_()
-                check(lib.vila_graph_begin(st.stream.cuda_stream), "graph_begin")
-                self._batch_step(st)
-                g = C.c_void_p()
-                check(lib.vila_graph_end(st.stream.cuda_stream, C.byref(g)), "graph_end")
-                st.graph = g
-                st.stream.synchronize()
-                st.pos.zero_(); st.n_out.zero_(); st.token.zero_()
+                reset()                                                # the session starts idle whatever the capture left
         return st
 
     def batch_admit(self, st, slot: int, embeds: torch.Tensor, sampling=None) -> int:
@@ -805,8 +828,7 @@ class HipQwen2ForCausalLM(_HipModule):
         st.pos.copy_(torch.tensor(lens, dtype=torch.int32))
         st.n_out.zero_()
         st.token.copy_(first)
-        eos = self.lcfg.eos_token_id if eos_token_id is None else eos_token_id
-        eos_set = set(eos) if isinstance(eos, (list, tuple)) else {eos}
+        eos_set = _eos_set(eos_token_id, self.lcfg.eos_token_id)
         n_steps = max_new_tokens - 1
         lib = _lib.load()
         if forced_ids is not None or return_logits:
@@ -824,17 +846,9 @@ class HipQwen2ForCausalLM(_HipModule):
             st.stream.synchronize()
             return torch.stack(ids, 1), torch.stack(step_logits, 0)
         if use_graph and st.graph is None and n_steps > 0:
-            torch.cuda.current_stream().synchronize()
-            with torch.cuda.stream(st.stream):
-                self._batch_step(st)                                   # warm-up outside capture (kernel attributes), then restore the state
-                st.stream.synchronize()
+            def restore():
                 st.pos.copy_(torch.tensor(lens, dtype=torch.int32)); st.n_out.zero_(); st.token.copy_(first)
-                check(lib.vila_graph_begin(st.stream.cuda_stream), "graph_begin")
-                self._batch_step(st)
-                g = C.c_void_p()
-                check(lib.vila_graph_end(st.stream.cuda_stream, C.byref(g)), "graph_end")
-                st.graph = g
-                st.stream.synchronize()
+            _capture(st, lambda: self._batch_step(st), restore)
         first_h = first.tolist()
         done_rows = [t in eos_set for t in first_h]
         done = 0
@@ -852,21 +866,11 @@ class HipQwen2ForCausalLM(_HipModule):
                 done_rows = [first_h[b] in eos_set or any(t in eos_set for t in got[b]) for b in range(Bn)]
         st.stream.synchronize()
         toks = torch.cat([first[:, None], st.out_ids[:, :done]], 1)
-        eos1 = eos[0] if isinstance(eos, (list, tuple)) else eos
-        pad = pad_token_id if pad_token_id is not None else (eos1 if eos1 is not None else self.lcfg.eos_token_id)
-        rows = []
-        for b, row in enumerate(toks.tolist()):
-            cut = next((i + 1 for i, t in enumerate(row) if t in eos_set), len(row))      # HF stops a row AFTER emitting eos
-            rows.append(row[:cut])
-        n = max(len(r) for r in rows)
-        out = torch.full((Bn, n), int(pad), dtype=torch.int64, device=dev)
-        for b, r_ in enumerate(rows):
-            out[b, :len(r_)] = torch.tensor(r_, dtype=torch.int64, device=dev)
-        return out
+        return finish_rows(toks.tolist(), eos_set, _pad_id(pad_token_id, eos_token_id, self.lcfg.eos_token_id), dev)
 
     def _fresh_seed(self) -> int:
         """The seed of a sampled request that names none: torch's initial seed stepped once per request."""
-        self._sample_calls = getattr(self, "_sample_calls", 0) + 1
+        self._sample_calls += 1
         return (torch.initial_seed() + 0x9E3779B97F4A7C15 * self._sample_calls) & 0xFFFFFFFFFFFFFFFF
 
     @torch.no_grad()
@@ -916,28 +920,29 @@ class HipQwen2ForCausalLM(_HipModule):
                 m = None if attention_mask is None else attention_mask[b:b + 1]
                 rows.append(self.generate(inputs_embeds[b:b + 1], m, max_new_tokens, eos_token_id, do_sample, temperature, top_k, top_p,
                                           None if seed is None else seed + b, pad_token_id, None, use_graph, False, None, cache, max_length)[0])
-            eos1 = eos_token_id[0] if isinstance(eos_token_id, (list, tuple)) else eos_token_id
-            pad = pad_token_id if pad_token_id is not None else (eos1 if eos1 is not None else self.lcfg.eos_token_id)
-            n = max(int(r.numel()) for r in rows)
-            out = torch.full((len(rows), n), int(pad), dtype=torch.int64, device=rows[0].device)
-            for b, r in enumerate(rows):
-                out[b, : r.numel()] = r
-            return out
+            return finish_rows([r.tolist() for r in rows], _eos_set(eos_token_id, self.lcfg.eos_token_id),
+                               _pad_id(pad_token_id, eos_token_id, self.lcfg.eos_token_id), rows[0].device)
         sampling = None
         if do_sample:
             if seed is None:
                 seed = self._fresh_seed()
             sampling = (temperature, top_k, top_p, int(seed))
+        return self._generate_solo(inputs_embeds, attention_mask, max_new_tokens, eos_token_id, sampling, use_graph, return_logits, forced_ids, cache,
+                                   streamer)
+
+    def _generate_solo(self, inputs_embeds, attention_mask, max_new_tokens, eos_token_id, sampling, use_graph, return_logits, forced_ids, cache,
+                       streamer):
+        """generate() for one sequence: prefill, then the batch-1 step (one hipGraph replay per token, or step by step under `use_graph=False`,
+        `return_logits` or `forced_ids`).  sampling: None (greedy) or (temperature, top_k, top_p, seed)."""
         ops._need(inputs_embeds, dtype=None, name="inputs_embeds")
         x = inputs_embeds[0]
         if attention_mask is not None:
             x = x[attention_mask[0].bool()]
         S = x.shape[0]
         dev = x.device
-        eos = self.lcfg.eos_token_id if eos_token_id is None else eos_token_id
-        eos_set = set(eos) if isinstance(eos, (list, tuple)) else {eos}
+        eos_set = _eos_set(eos_token_id, self.lcfg.eos_token_id)
         if cache is None:
-            cache = getattr(self, "_own_cache", None)
+            cache = self._own_cache
             if cache is None or cache.max_ctx < S + max_new_tokens:
                 cache = self._own_cache = self.new_cache(((S + max_new_tokens + 255) // 256) * 256)
         if cache.max_ctx < S + max_new_tokens:
@@ -948,8 +953,7 @@ class HipQwen2ForCausalLM(_HipModule):
         st = self._decode_session(cache, max_new_tokens, sampling)
         # the sampler mixes a device counter into its random number: the decode steps use the position of the token they consume
         # (S, S+1, ...); the first token, drawn from the prefill's logits, uses S - 1
-        first = (ops.argmax(r.last_logits[0]) if sampling is None else
-                 ops.sample(r.last_logits[0], temperature, top_k, top_p, sampling[3], counter=last))
+        first = ops.argmax(r.last_logits[0]) if sampling is None else ops.sample(r.last_logits[0], *sampling, counter=last)
         step_logits = [r.last_logits[0].clone()] if return_logits else None
         st.pos.fill_(S)
         st.n_out.zero_()
@@ -958,18 +962,9 @@ class HipQwen2ForCausalLM(_HipModule):
         lib = _lib.load()
         eager = (not use_graph) or return_logits or (forced_ids is not None)
         if not eager and st.graph is None:
-            torch.cuda.current_stream().synchronize()
-            with torch.cuda.stream(st.stream):
-                # warm-up launch outside capture (sets kernel attributes), then restore the state it advanced
-                self.decode_step(cache, st)
-                st.stream.synchronize()
+            def restore():
                 st.pos.fill_(S); st.n_out.zero_(); st.token.copy_(first)
-                check(lib.vila_graph_begin(st.stream.cuda_stream), "graph_begin")
-                self.decode_step(cache, st)
-                g = C.c_void_p()
-                check(lib.vila_graph_end(st.stream.cuda_stream, C.byref(g)), "graph_end")
-                st.graph = g
-                st.stream.synchronize()
+            _capture(st, lambda: self.decode_step(cache, st), restore)
         n_steps = max_new_tokens - 1
         if eager:
             for t in range(n_steps):
@@ -1005,12 +1000,8 @@ class HipQwen2ForCausalLM(_HipModule):
                     stop = any(t in eos_set for t in got)
             st.stream.synchronize()
             out = torch.cat([first, st.out_ids[:done]])
-        toks = out.tolist()
         if forced_ids is None:
-            for i, t in enumerate(toks):                    # HF stops AFTER emitting eos
-                if t in eos_set:
-                    out = out[: i + 1]
-                    break
+            out = out[:len(_cut_at_eos(out.tolist(), eos_set))]
         if streamer is not None:
             if eager:                                       # the step-by-step paths learn of their tokens at the end
                 for t in out.tolist():

@@ -30,6 +30,8 @@ from typing import Any, Dict, Iterator, List, Optional, Sequence, Union
 import numpy as np
 import torch
 
+from .modules import _eos_set
+
 IMAGE_TOKEN = "<image>"
 MEDIA_TOKENS = {"image": "<image>", "video": "<vila/video>"}          # llava/constants.py:32-35
 _DATA_URL = re.compile(r"^data:image/(png|jpe?g);base64,(.*)$", re.S)
@@ -405,7 +407,7 @@ def generate_content(model, tokenizer, prompt: Union[str, Sequence[Any]], max_ne
         gen.update(streamer=streamer)
     out = model.generate(input_ids=ids, media=media, media_config=media_config, **gen)
     toks = out[0].tolist()
-    stop = set(eos) if isinstance(eos, (list, tuple)) else {eos}
+    stop = _eos_set(eos)
     for k, t in enumerate(toks):                       # HF returns the EOS as the last token; decode(skip_special_tokens) drops it
         if t in stop:
             toks = toks[:k]
@@ -429,7 +431,7 @@ def generate_content_batch(model, tokenizer, prompts: Sequence[Union[str, Sequen
         tiles.extend(t)
         blocks.extend(mc.get("image", {}).get("block_sizes", [None] * len(t)))
     eos = _eos_of(tokenizer, eos_token_id)
-    stop = set(eos) if isinstance(eos, (list, tuple)) else {eos}
+    stop = _eos_set(eos)
     pad = pad_token_id if pad_token_id is not None else (getattr(tokenizer, "pad_token_id", None) or 0)
     L = max(int(r.numel()) for r in rows)
     ids = torch.full((len(rows), L), int(pad), dtype=torch.int64)
@@ -524,8 +526,7 @@ class HipBatchEngine:
         self.model, self.tokenizer = model, tokenizer
         self.sampling = bool(sampling)
         self.n_slots, self.max_ctx, self.max_new_tokens = int(n_slots), int(max_ctx), int(max_new_tokens)
-        eos = _eos_of(tokenizer, eos_token_id)
-        self.eos = set(eos) if isinstance(eos, (list, tuple)) else {eos}
+        self.eos = _eos_set(_eos_of(tokenizer, eos_token_id))
         self.st = None
 
     def _session(self):
