@@ -53,7 +53,7 @@ int vila_attn_fwd_form(int n_seq, int max_seqlen, int n_q_heads);
 /* test hook of the attention backward's dQ and dK / dV passes: 0 = VILA_ATTN_BWD from the environment (default: DMA), 1 = the round-1/2 kernels
  * of attn_bwd.hip (VILA_ATTN_BWD=v1), 2 = the DMA-ring kernels of attn_bwd_dma.hip */
 void vila_attn_force_bwd(int impl);
-/* test / measurement hook of the batched decode step's attention (decode_batch.hip): 0 = automatic (up to 2048 cached positions one slice per
+/* test / measurement hook of the batched decode step's attention (attn_decode.hip): 0 = automatic (up to 2048 cached positions one slice per
  * 256-key chunk; beyond, blocks that walk chunks s, s + nsl, ... with nsl = min(chunks of the capacity, 8)), n > 0 = the walking form with
  * min(n, 32, chunks of the capacity) slices at ANY capacity, so that a small cache makes blocks walk many chunks */
 void vila_decode_batch_force_slices(int nsl);

@@ -155,6 +155,28 @@ def test_decode_attention_over_256_key_slices_matches_the_single_block_kernel(mo
     assert torch.equal(idsg, idse)
 
 
+def test_decode_past_2048_cached_positions_matches_the_short_context_kernels():
+    """A batch-1 session whose cache holds more than 2048 positions runs the 64-key split-KV pair (attn_decode.hip: attn_decode_partial +
+    attn_decode_merge) instead of the per-head kernel over 256-key slices.  At 2304 positions — 36 splits, of which a 600-row prompt keeps 10
+    active and 26 idle — it must give the logits of the default capacity (same math, another summation order), eager and through the
+    captured graph."""
+    from vila_amd.vlm import build_model
+    cfg = configs.tiny("mlp_downsample")
+    model = build_model(cfg, seed=5)
+    g = torch.Generator().manual_seed(3)
+    e = (torch.randn(1, 600, cfg.llm.hidden_size, generator=g) * 0.5).to(torch.bfloat16).cuda()
+    n = 6
+    ids0, lg0 = model.llm.generate(inputs_embeds=e, max_new_tokens=n, return_logits=True, use_graph=False, eos_token_id=-1)
+    long_cache = model.llm.new_cache(2304)
+    gen = dict(inputs_embeds=e, max_new_tokens=n, eos_token_id=-1, cache=long_cache)
+    ids1, lg1 = model.llm.generate(return_logits=True, forced_ids=ids0[0].cpu(), use_graph=False, **gen)
+    idsg = model.llm.generate(use_graph=True, **gen)
+    idse = model.llm.generate(use_graph=False, **gen)
+    print(f"split-KV pair at 2304 positions vs default capacity: logits rel={rel_l2(lg1, lg0):.3e}")
+    assert rel_l2(lg1, lg0) < 5e-3, f"split-KV pair vs short-context decode logits rel={rel_l2(lg1, lg0):.3e}"
+    assert torch.equal(idsg, idse)
+
+
 def test_norm_fused_into_the_splitk_reduce_equals_the_separate_launches():
     """Round 4: where a prefill GEMM is K-sliced (LLM down_proj at 512+ rows, tower fc2 at one image) its reduce kernel also writes the NEXT
     block's normalisation (gemm256.hip splitk_reduce_norm_kernel).  LLM: same per-element arithmetic and the same summation order as

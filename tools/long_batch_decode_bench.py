@@ -1,5 +1,5 @@
 """Batched decode past 2048 cached positions, measured in one process on one GPU: the walking attention of the batched step
-(decode_batch.hip bdec_attn_walk_kernel) at NVILA-8B widths with seeded synthetic weights.
+(attn_decode.hip bdec_attn_walk_kernel) at NVILA-8B widths with seeded synthetic weights.
 
   for bf16 and W4, contexts of about 2400 (dynamic_s2's 2304 image tokens + a prompt) and 8192 keys, n = 2 / 8 / 16 rows:
     * ms per batched step and aggregate tokens/s for each slice cap (8 / 16 / 32: vila_decode_batch_force_slices; NSL = min(cap, chunks of

@@ -5,6 +5,7 @@
 #include "../../include/vila_hip.h"
 #include "../../include/vila_hip_tuning.h"
 #include "kernels.h"
+#include "attn_decode.h"
 #include "train.h"
 #include "w4.h"
 
@@ -509,12 +510,12 @@ extern "C" int vila_llm_prefill_w4(const VilaLlmWeights* w, const VilaLlmLayerW4
 // =================================================================================================
 // LLM decode step (batch 1)
 // =================================================================================================
-static inline int dec_splits(int max_ctx) { return cdiv(max_ctx, 64); }
-// kernel launches of one vila_llm_decode_step: prologue + per layer {qkv, attention (1 launch up to 2048 cached positions, else
+static inline int dec_splits(int max_ctx) { return cdiv(max_ctx, DEC_KS); }
+// kernel launches of one vila_llm_decode_step: prologue + per layer {qkv, attention (1 launch up to DEC_SHORT_CTX cached positions, else
 // split-KV + merge), o_proj, gate/up, down} + lm_head (which also reduces each block's logits to one (max, index) pair) + the final pick, which
 // advances the state as well
 extern "C" int vila_llm_decode_launches(const VilaLlmShape* s, int max_ctx) {
-    return 1 + s->n_layers * (max_ctx <= 2048 ? 5 : 6) + 2;      // a sampled step: + 3 (three selection launches and the advance after lm_head)
+    return 1 + s->n_layers * (max_ctx <= DEC_SHORT_CTX ? 5 : 6) + 2;      // a sampled step: + 3 (three selection launches and the advance after lm_head)
 }
 extern "C" size_t vila_llm_decode_workspace_bytes(const VilaLlmShape* s, int max_ctx) {
     const size_t H = s->hidden, F = s->inter, QS = (size_t)s->q_heads * s->head_dim;
@@ -600,7 +601,7 @@ static int decode_step_impl(const VilaLlmWeights* w, const VilaLlmLayerW4* ql, c
     const size_t per_layer = (size_t)cache->n_slots * sh.kv_heads * cache->max_ctx * hd;
 
     // per-head blocks over 256-key slices whose partials meet in the o_proj GEMV's prologue (§4.3; the W4 GEMV's merge holds up to 7 x 16 heads)
-    const bool split256 = decode_attn_mode() >= 1 && cache->max_ctx <= 2048 && hd == 128 && (!w4 || QS <= 7 * 16 * 128);
+    const bool split256 = decode_attn_mode() >= 1 && cache->max_ctx <= DEC_SHORT_CTX && hd == 128 && (!w4 || QS <= 7 * 16 * 128);
     VILA_TRY(launch_decode_prologue(B(w->embed), st->token, x, H, sh.vocab, st->pos, rope_cs, hd, sh.rope_theta, s));
     bf16_t* cur = x; bf16_t* nxt = x2;
     for (int l = 0; l < sh.n_layers; ++l) {

@@ -330,366 +330,6 @@ __global__ __launch_bounds__(64) void bdec_pick2_kernel(const float* __restrict_
     }
 }
 
-// ---- attention of the batch: one block per (kv head, 256-key slice, sequence) -------------------------------------------------------------
-// The batch-1 kernel (gemv.hip attn_decode_head) gives every QUERY head its own block, so the 7 heads of a GQA group each pull the same
-// K/V rows through L2, and a row's whole context is one block's serial loop (19.6 us per layer at 8 x ~800 keys).  Here the K/V chunk a
-// wave loads (16 keys) serves all G query heads of its kv head (scores on the matrix core: S[16 keys][16 heads] = K . Q^T in 4 MFMAs; P.V on
-// the VALU with the probabilities fetched by DPP row broadcasts, reductions by row swaps — the __shfl_xor formulation, 30 ds_bpermute per
-// head, took 69 us), a slice is one chunk per wave (no loop), and the slices are merged by a second small launch.  Merging inside the launch
-// (last-arriving block, agent-scope release/acquire by one lane) measured the same 16-17 us total and needs counters; with EVERY wave
-// fencing it was 59 us (an agent fence is an L2 write-back + invalidate on this multi-XCD part).
-// sum over lane l and lane l ^ 16 (resp. l ^ 32) with gfx950's row swaps (see attn_common.h xor16_max): no LDS crossbar, no lgkmcnt
-__device__ __forceinline__ float bd_xor16_sum(float x) {
-    const unsigned u = __float_as_uint(x);
-    const auto r = __builtin_amdgcn_permlane16_swap(u, u, false, false);
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-__device__ __forceinline__ float bd_xor32_sum(float x) {
-    const unsigned u = __float_as_uint(x);
-    const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-struct BAttnArgs {
-    const bf16_t* q; bf16_t* o;                 // [rows][nq*128]
-    const bf16_t* kcache; const bf16_t* vcache; // this layer's [slots][nkv][max_ctx][128]
-    const int32_t* pos;                         // [rows]: keys 0 .. pos inclusive
-    float* part_o; float* part_ml;              // [rows][nkv][NSL][G][128], [rows][nkv][NSL][G][2]
-    int nq, nkv, max_ctx, nsl; int64_t row_stride, o_row_stride, slot_stride; float scale;   // row_stride: q rows, o_row_stride: o rows
-};
-// the 16 waves' partials (so [16][G][128], sml [16][G][2] in LDS, published by a barrier) -> the slice's partial in the workspace
-template <int G>
-__device__ __forceinline__ void bdec_slice_partial(const BAttnArgs& p, const float* so, const float* sml, int row, int kvh, int slice, int tid) {
-    const int64_t pbase = ((int64_t)(row * p.nkv + kvh) * p.nsl + slice) * G;
-    const int g = tid >> 7, d = tid & 127;
-    if (g < G) {
-        float M = -INFINITY;
-#pragma unroll
-        for (int w = 0; w < 16; ++w) M = fmaxf(M, sml[(w * G + g) * 2]);
-        float L = 0.f, O = 0.f;
-#pragma unroll
-        for (int w = 0; w < 16; ++w) {
-            const float mw = sml[(w * G + g) * 2];
-            const float f = (mw == -INFINITY) ? 0.f : __expf(mw - M);
-            L = fmaf(sml[(w * G + g) * 2 + 1], f, L);
-            O = fmaf(so[(w * G + g) * 128 + d], f, O);
-        }
-        p.part_o[(pbase + g) * 128 + d] = O;
-        if (d == 0) { p.part_ml[(pbase + g) * 2] = M; p.part_ml[(pbase + g) * 2 + 1] = L; }
-    }
-}
-template <int G>
-__global__ __launch_bounds__(1024) void bdec_attn_kernel(BAttnArgs p) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    float* so = (float*)smem;                   // [16 waves][G][128]
-    float* sml = so + 16 * G * 128;             // [16][G][2]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int kvh = blockIdx.x, slice = blockIdx.y, row = blockIdx.z;
-    const int nkeys_all = p.pos[row] + 1;
-    const int active = (nkeys_all + 255) >> 8;
-    if (slice >= active) return;                                 // block-uniform
-    const int key_lo = slice * 256;
-    const int nkeys = nkeys_all < key_lo + 256 ? nkeys_all : key_lo + 256;
-    const bf16_t* kb = p.kcache + (int64_t)row * p.slot_stride + (int64_t)kvh * p.max_ctx * 128;
-    const bf16_t* vb = p.vcache + (int64_t)row * p.slot_stride + (int64_t)kvh * p.max_ctx * 128;
-    const bf16_t* qrow = p.q + (int64_t)row * p.row_stride + kvh * G * 128;
-    const int l15 = lane & 15, lg = lane >> 4;      // scores: MFMA A rows = keys, B rows = query heads; C: key lg*4 + r, head l15
-    const int sg = lane >> 4, dc = lane & 15;       // P.V: 4-key subgroup (= the C layout's row group), d chunk
-    // the wave's 16 keys: everything is issued before anything is used
-    const int k0 = key_lo + wave * 16;
-    u32x4 kc[4], qc[4], vc[4];
-    {
-        const int key = k0 + l15;
-        const bool kok = key < nkeys, qok = l15 < G;
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-            kc[ks] = kok ? *(const u32x4*)(kb + (int64_t)key * 128 + ks * 32 + lg * 8) : (u32x4){0u, 0u, 0u, 0u};
-            qc[ks] = qok ? *(const u32x4*)(qrow + l15 * 128 + ks * 32 + lg * 8) : (u32x4){0u, 0u, 0u, 0u};
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int vk = k0 + sg * 4 + j;
-            vc[j] = (vk < nkeys) ? *(const u32x4*)(vb + (int64_t)vk * 128 + dc * 8) : (u32x4){0u, 0u, 0u, 0u};
-        }
-    }
-    // S[key][head] on the matrix core: 4 MFMAs replace G x (64 FMAs + a 4-lane reduction)
-    f32x4 sc = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks)
-        sc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, kc[ks]), __builtin_bit_cast(bf16x8, qc[ks]), sc, 0, 0, 0);
-    float pr[4], m = -INFINITY;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) { pr[r] = (k0 + lg * 4 + r < nkeys) ? sc[r] * p.scale : -INFINITY; m = fmaxf(m, pr[r]); }
-    m = xor32_max(xor16_max(m));                                 // over the 16 keys of the chunk (lanes l15, l15 + 16, + 32, + 48)
-    float l = 0.f;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) { pr[r] = (m == -INFINITY) ? 0.f : __expf(pr[r] - m); l += pr[r]; }
-    l = bd_xor32_sum(bd_xor16_sum(l));
-    if (lg == 0 && l15 < G) { sml[(wave * G + l15) * 2] = m; sml[(wave * G + l15) * 2 + 1] = l; }
-    // P.V on the VALU: the probability of (key sg*4 + j, head g) sits in lane 16*sg + g, register j — one DPP row broadcast away
-    static_for<0, G>([&](auto gc) {
-        constexpr int g = decltype(gc)::value;
-        float o[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = 0.f;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float pj = __uint_as_float(__builtin_amdgcn_update_dpp(0u, __float_as_uint(pr[j]), 0x150 + g, 0xf, 0xf, false));
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                o[2 * e] = fmaf(pj, lo_bf(vc[j][e]), o[2 * e]);
-                o[2 * e + 1] = fmaf(pj, hi_bf(vc[j][e]), o[2 * e + 1]);
-            }
-        }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = bd_xor32_sum(bd_xor16_sum(o[e]));
-        if (sg == 0) {
-            float* dst = so + (wave * G + g) * 128 + dc * 8;
-            *(f32x4*)dst = (f32x4){o[0], o[1], o[2], o[3]};
-            *(f32x4*)(dst + 4) = (f32x4){o[4], o[5], o[6], o[7]};
-        }
-    });
-    __syncthreads();
-    bdec_slice_partial<G>(p, so, sml, row, kvh, slice, tid);
-}
-// the slices of a (sequence, query head) -> the bf16 attention output; the launch boundary is the publish (no fences)
-__global__ __launch_bounds__(128) void bdec_attn_merge_kernel(BAttnArgs p, int G) {
-    const int h = blockIdx.x, row = blockIdx.y, d = threadIdx.x;
-    const int kvh = h / G, g = h % G;
-    const int chunks = (p.pos[row] + 1 + 255) >> 8;
-    const int active = chunks < p.nsl ? chunks : p.nsl;         // the walking form: a slice owns chunks s, s + nsl, ...; one without a chunk wrote nothing
-    const int64_t b0 = (int64_t)(row * p.nkv + kvh) * p.nsl * G;
-    float M = -INFINITY;
-    for (int sl = 0; sl < active; ++sl) M = fmaxf(M, p.part_ml[(b0 + sl * G + g) * 2]);
-    float L = 0.f, O = 0.f;
-    for (int sl = 0; sl < active; ++sl) {
-        const float f = __expf(p.part_ml[(b0 + sl * G + g) * 2] - M);
-        L = fmaf(p.part_ml[(b0 + sl * G + g) * 2 + 1], f, L);
-        O = fmaf(p.part_o[(b0 + sl * G + g) * 128 + d], f, O);
-    }
-    p.o[(int64_t)row * p.o_row_stride + h * 128 + d] = f2bf(O / L);
-}
-template <int G>
-static int launch_bdec_attn_t(const BAttnArgs& a, int rows, hipStream_t s) {
-    const size_t lds = (size_t)(16 * G * 128 + 16 * G * 2) * 4;
-    static bool attr = false;
-    if (!attr) {
-        VILA_HIP(hipFuncSetAttribute((const void*)bdec_attn_kernel<G>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr = true;
-    }
-    hipLaunchKernelGGL((bdec_attn_kernel<G>), dim3(a.nkv, a.nsl, rows), dim3(1024), lds, s, a);
-    VILA_LAUNCH_CHECK();
-    hipLaunchKernelGGL(bdec_attn_merge_kernel, dim3(a.nq, rows), dim3(128), 0, s, a, G);
-    VILA_LAUNCH_CHECK();
-    return 0;
-}
-// returns 1 when the GQA group size has no instantiation (the caller falls back to the per-head kernel)
-static int launch_bdec_attn(const BAttnArgs& a, int rows, hipStream_t s) {
-    switch (a.nq / a.nkv) {
-        case 1: return launch_bdec_attn_t<1>(a, rows, s);
-        case 2: return launch_bdec_attn_t<2>(a, rows, s);
-        case 4: return launch_bdec_attn_t<4>(a, rows, s);
-        case 7: return launch_bdec_attn_t<7>(a, rows, s);
-        case 8: return launch_bdec_attn_t<8>(a, rows, s);
-        default: return 1;
-    }
-}
-
-// ---- the long-context form: blocks WALK ---------------------------------------------------------------------------------------------
-// bdec_attn_kernel needs one partial slot per 256-key chunk of the CAPACITY: at 32k positions that is 128 slices per (row, kv head), most of
-// them idle for most rows, and a merge over 128 partials.  Here the grid has nsl = min(chunks of the capacity, cap) slices and the block of
-// slice s takes chunks s, s + nsl, s + 2 nsl, ... of the row (interleaved: a short row in a long-capacity session still gets one chunk per
-// block, a long row spreads evenly).  A wave keeps the chunk's 16 keys, as above, and carries the online softmax across chunks in registers:
-// (m, l) of head l15 in every lane, G x 8 fp32 of un-reduced O; a chunk rescales them by exp(m_old - m_new), fetched by the same DPP row
-// broadcast as the probabilities.  The cross-lane sums of O and l are linear, so they run once, behind the walk.
-// Registers: a 1024-thread block leaves a wave 128.  G x 8 accumulators + Q + K and V of two chunks is 176 at G = 8 (the compiler spilled 156),
-// so Q lives in LDS (rows padded for the b128 read), addresses are 32-bit offsets from a uniform base, P.V unpacks one V row at a time, and the
-// next chunk's K and V are requested into the registers this chunk's have just left: K behind the 4 score MFMAs, V behind the P.V.  hipcc keeps
-// K's request where it is written only while registers allow; at G = 7 / 8 it moves it down to V's (pinning it with a sched_barrier made it spill
-// the loaded K, 140 B per lane), and about 10 loop-invariant offsets live in scratch (40 - 56 B per lane; G <= 4: none).  Loads to keys past the
-// row's context are redirected to its last key rather than predicated.  The tail is the short form's: 16-wave merge in LDS, partial [rows][nkv][nsl][G][128] + [..][2], merge launch.
-template <int G>
-__global__ __launch_bounds__(1024) void bdec_attn_walk_kernel(BAttnArgs p) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    float* so = (float*)smem;                   // [16 waves][G][128]
-    float* sml = so + 16 * G * 128;             // [16][G][2]
-    char* sq = (char*)(sml + 16 * G * 2);       // [16 heads][256 + 16 B], rows >= G zero (the pad of one b128 keeps the fragment read conflict-free)
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int kvh = blockIdx.x, slice = blockIdx.y, row = blockIdx.z;
-    const int pos1 = p.pos[row] + 1;
-    const int nkeys = pos1 < p.max_ctx ? pos1 : p.max_ctx;      // never past the slot, whatever the state says
-    const int active = (nkeys + 255) >> 8;
-    if (slice >= active) return;                                 // block-uniform: this slice owns no chunk and writes nothing
-    const bf16_t* kb = p.kcache + (int64_t)row * p.slot_stride + (int64_t)kvh * p.max_ctx * 128;
-    const bf16_t* vb = p.vcache + (int64_t)row * p.slot_stride + (int64_t)kvh * p.max_ctx * 128;
-    const bf16_t* qrow = p.q + (int64_t)row * p.row_stride + kvh * G * 128;
-    const int l15 = lane & 15, lg = lane >> 4;      // scores: MFMA A rows = keys, B rows = query heads; C: key lg*4 + r, head l15
-    const int sg = lane >> 4, dc = lane & 15;       // P.V: 4-key subgroup, d chunk
-    const int kw = wave * 16;
-    // keys past the row's context (the tail of its last chunk, the chunk requested behind the last one) read the row's LAST key instead: every load
-    // is unconditional and finite, the scores of those keys are masked by index, and their probability 0 meets a finite V
-    const int last = nkeys - 1;
-    // (a uniform base + a 32-bit byte offset per lane: a slot's kv head is at most 32768 x 256 B, and an address costs one register, not two)
-    auto load_k = [&](int chunk, u32x4 (&kk)[4]) {
-        int key = chunk * 256 + kw + l15;
-        key = key < last ? key : last;
-        const char* kp = (const char*)kb + (unsigned)(key * 256 + lg * 16);
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) kk[ks] = *(const u32x4*)(kp + ks * 64);
-    };
-    auto load_v = [&](int chunk, u32x4 (&vv)[4]) {
-        const int v0 = chunk * 256 + kw + sg * 4;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int vk = v0 + j < last ? v0 + j : last;
-            vv[j] = *(const u32x4*)((const char*)vb + (unsigned)(vk * 256 + dc * 16));
-        }
-    };
-    u32x4 kc[4], vc[4];
-    load_k(slice, kc);
-    load_v(slice, vc);
-    if (tid < 256) {
-        const int r = tid >> 4, c = tid & 15;
-        const u32x4 v = r < G ? *(const u32x4*)(qrow + r * 128 + c * 8) : (u32x4){0u, 0u, 0u, 0u};
-        *(u32x4*)(sq + r * 272 + c * 16) = v;
-    }
-    __syncthreads();
-    int qoff = l15 * 272 + lg * 16;
-    float m = -INFINITY, l = 0.f, o[G][8];
-#pragma unroll
-    for (int g = 0; g < G; ++g)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[g][e] = 0.f;
-#pragma unroll 1
-    for (int chunk = slice; chunk < active; chunk += p.nsl) {
-        asm volatile("" : "+v"(qoff));                           // keeps the Q fragments in LDS: hoisted out of the loop they cost 16 registers
-        f32x4 sc = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-            const u32x4 qc = *(const u32x4*)(sq + qoff + ks * 64);
-            sc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, kc[ks]), __builtin_bit_cast(bf16x8, qc), sc, 0, 0, 0);
-        }
-        load_k(chunk + p.nsl, kc);
-        const int k0 = chunk * 256 + kw;
-        float pr[4], cm = -INFINITY;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { pr[r] = (k0 + lg * 4 + r < nkeys) ? sc[r] * p.scale : -INFINITY; cm = fmaxf(cm, pr[r]); }
-        cm = xor32_max(xor16_max(cm));                           // over the 16 keys of the chunk
-        const float m_new = fmaxf(m, cm);
-        const bool none = m_new == -INFINITY;                    // no key of this wave yet (only in the row's last chunk)
-        const float alpha = none ? 1.f : __expf(m - m_new);      // m = -inf: 0, and there is nothing to rescale
-        float ls = 0.f;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { pr[r] = none ? 0.f : __expf(pr[r] - m_new); ls += pr[r]; }
-        l = fmaf(l, alpha, ls);                                  // this lane's 4 keys; the other 12 are added behind the walk
-        m = m_new;
-        static_for<0, G>([&](auto gc) {
-            constexpr int g = decltype(gc)::value;
-            const float ag = __uint_as_float(__builtin_amdgcn_update_dpp(0u, __float_as_uint(alpha), 0x150 + g, 0xf, 0xf, false));
-#pragma unroll
-            for (int e = 0; e < 8; ++e) o[g][e] *= ag;
-        });
-        // key-outer, head-inner: one V row is unpacked to 8 floats at a time (head-outer lets the compiler keep all 4 rows unpacked: 32 registers)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            float vf[8];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { vf[2 * e] = lo_bf(vc[j][e]); vf[2 * e + 1] = hi_bf(vc[j][e]); }
-            static_for<0, G>([&](auto gc) {
-                constexpr int g = decltype(gc)::value;
-                const float pj = __uint_as_float(__builtin_amdgcn_update_dpp(0u, __float_as_uint(pr[j]), 0x150 + g, 0xf, 0xf, false));
-#pragma unroll
-                for (int e = 0; e < 8; ++e) o[g][e] = fmaf(pj, vf[e], o[g][e]);
-            });
-        }
-        load_v(chunk + p.nsl, vc);
-    }
-    l = bd_xor32_sum(bd_xor16_sum(l));
-    if (lg == 0 && l15 < G) { sml[(wave * G + l15) * 2] = m; sml[(wave * G + l15) * 2 + 1] = l; }
-    static_for<0, G>([&](auto gc) {
-        constexpr int g = decltype(gc)::value;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[g][e] = bd_xor32_sum(bd_xor16_sum(o[g][e]));
-        if (sg == 0) {
-            float* dst = so + (wave * G + g) * 128 + dc * 8;
-            *(f32x4*)dst = (f32x4){o[g][0], o[g][1], o[g][2], o[g][3]};
-            *(f32x4*)(dst + 4) = (f32x4){o[g][4], o[g][5], o[g][6], o[g][7]};
-        }
-    });
-    __syncthreads();
-    bdec_slice_partial<G>(p, so, sml, row, kvh, slice, tid);
-}
-template <int G>
-static int launch_bdec_attn_walk_t(const BAttnArgs& a, int rows, hipStream_t s) {
-    const size_t lds = (size_t)(16 * G * 128 + 16 * G * 2) * 4 + 16 * 272;
-    static bool attr = false;
-    if (!attr) {
-        VILA_HIP(hipFuncSetAttribute((const void*)bdec_attn_walk_kernel<G>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr = true;
-    }
-    hipLaunchKernelGGL((bdec_attn_walk_kernel<G>), dim3(a.nkv, a.nsl, rows), dim3(1024), lds, s, a);
-    VILA_LAUNCH_CHECK();
-    hipLaunchKernelGGL(bdec_attn_merge_kernel, dim3(a.nq, rows), dim3(128), 0, s, a, G);
-    VILA_LAUNCH_CHECK();
-    return 0;
-}
-static bool bdec_group_ok(int G) { return G == 1 || G == 2 || G == 4 || G == 7 || G == 8; }
-static int launch_bdec_attn_walk(const BAttnArgs& a, int rows, hipStream_t s) {
-    switch (a.nq / a.nkv) {
-        case 1: return launch_bdec_attn_walk_t<1>(a, rows, s);
-        case 2: return launch_bdec_attn_walk_t<2>(a, rows, s);
-        case 4: return launch_bdec_attn_walk_t<4>(a, rows, s);
-        case 7: return launch_bdec_attn_walk_t<7>(a, rows, s);
-        case 8: return launch_bdec_attn_walk_t<8>(a, rows, s);
-        default: VILA_REQUIRE(false, "batched decode attention: the walking form serves GQA groups of 1, 2, 4, 7 or 8 query heads (got %d)", a.nq / a.nkv);
-    }
-    return 0;
-}
-
-// ---- which form, how many slices ----------------------------------------------------------------------------------------------------
-// Up to 2048 positions: the short form, one slice per 256-key chunk of the capacity (<= 8), exactly as before the walking form existed.
-// Beyond: the walking form with min(chunks of the capacity, BDEC_SLICE_CAP) slices.  vila_decode_batch_force_slices (tests, the slice-cap
-// measurement) asks for the walking form with a given slice count at any capacity.
-static int g_bdec_force_slices = 0;
-void bdecode_force_slices(int nsl) { g_bdec_force_slices = nsl < 0 ? 0 : nsl; }
-struct BAttnForm { bool walk; int nsl; };
-static BAttnForm bdec_attn_form(int max_ctx) {
-    const int chunks = cdiv(max_ctx, 256);
-    if (g_bdec_force_slices > 0) {
-        const int f = g_bdec_force_slices < BDEC_MAX_SLICES ? g_bdec_force_slices : BDEC_MAX_SLICES;
-        return BAttnForm{true, f < chunks ? f : chunks};
-    }
-    if (max_ctx <= BDEC_SHORT_CTX) return BAttnForm{false, chunks};
-    return BAttnForm{true, chunks < BDEC_SLICE_CAP ? chunks : BDEC_SLICE_CAP};
-}
-// partial slots the workspace holds per (row, query head): 8 up to 2048 positions (the formula the short form always had), else one per
-// chunk of the capacity up to the most a session may ever launch
-static int bdec_ws_slices(int max_ctx) {
-    const int chunks = cdiv(max_ctx, 256);
-    return max_ctx <= BDEC_SHORT_CTX ? 8 : (chunks < BDEC_MAX_SLICES ? chunks : BDEC_MAX_SLICES);
-}
-int bdecode_attn_slices(int max_ctx) { const BAttnForm f = bdec_attn_form(max_ctx); return f.walk ? f.nsl : 0; }
-size_t bdecode_attn_workspace_bytes(int rows, int nq, int max_ctx) {
-    const size_t sl = (size_t)bdec_ws_slices(max_ctx);
-    return align_up((size_t)rows * nq * sl * 128 * 4, 256) + align_up((size_t)rows * nq * sl * 2 * 4, 256);
-}
-int bdecode_attn(const bf16_t* q, int64_t ldq, const bf16_t* kcache, const bf16_t* vcache, int64_t slot_stride, const int32_t* pos, bf16_t* o, int64_t ldo,
-                 int rows, int nq, int nkv, int max_ctx, float scale, void* workspace, size_t workspace_bytes, hipStream_t s) {
-    VILA_REQUIRE(q && kcache && vcache && pos && o && workspace, "attn_decode_batch: NULL argument");
-    VILA_REQUIRE(rows >= 1 && nkv >= 1 && nq % nkv == 0 && bdec_group_ok(nq / nkv),
-                 "attn_decode_batch: rows >= 1 and a GQA group of 1, 2, 4, 7 or 8 query heads per kv head (got %d rows, %d / %d heads)", rows, nq, nkv);
-    VILA_REQUIRE(max_ctx >= 1 && max_ctx <= BDEC_MAX_CTX, "attn_decode_batch: caches of 1..%d positions (got %d)", BDEC_MAX_CTX, max_ctx);
-    VILA_REQUIRE(ldq % 8 == 0 && ldq >= (int64_t)nq * 128 && ldo >= (int64_t)nq * 128 && (uintptr_t)q % 16 == 0 && (uintptr_t)kcache % 16 == 0 &&
-                 (uintptr_t)vcache % 16 == 0 && slot_stride % 8 == 0 && slot_stride >= (int64_t)nkv * max_ctx * 128,
-                 "attn_decode_batch: head_dim 128 rows, 16-byte aligned, slots of [kv_heads][max_ctx][128]");
-    VILA_REQUIRE(workspace_bytes >= bdecode_attn_workspace_bytes(rows, nq, max_ctx), "attn_decode_batch: workspace too small");
-    const BAttnForm f = bdec_attn_form(max_ctx);
-    BAttnArgs a{};
-    a.q = q; a.o = o; a.kcache = kcache; a.vcache = vcache; a.pos = pos;
-    a.part_o = (float*)workspace; a.part_ml = (float*)((char*)workspace + align_up((size_t)rows * nq * f.nsl * 128 * 4, 256));
-    a.nq = nq; a.nkv = nkv; a.max_ctx = max_ctx; a.nsl = f.nsl; a.row_stride = ldq; a.o_row_stride = ldo; a.slot_stride = slot_stride; a.scale = scale;
-    return f.walk ? launch_bdec_attn_walk(a, rows, s) : launch_bdec_attn(a, rows, s);
-}
-
 // ---- the step ---------------------------------------------------------------------------------------------------------------------
 size_t bdecode_workspace_bytes(int H, int F, int QS, int hd, int n, int max_ctx) {
     size_t b = 0;
@@ -730,9 +370,8 @@ int bdecode_step(const BDecodeArgs& m, const BLayer* layers, bf16_t* kcache, bf1
     bf16_t* ao = (bf16_t*)take((size_t)n * QS * 2);
     bf16_t* act = (bf16_t*)take((size_t)n * F * 2);
     float* rope_cs = (float*)take((size_t)n * hd * 4);
-    const int nsl = form.nsl;
-    float* part_o = (float*)take((size_t)n * m.q_heads * nsl * hd * 4);
-    float* part_ml = (float*)take((size_t)n * m.q_heads * nsl * 2 * 4);
+    float* part_o = (float*)take((size_t)n * m.q_heads * form.nsl * hd * 4);
+    float* part_ml = (float*)take((size_t)n * m.q_heads * form.nsl * 2 * 4);
     float* pick_v = (float*)take((size_t)n * PICK_SLICES * 4);
     int* pick_i = (int*)take((size_t)n * PICK_SLICES * 4);
     VILA_REQUIRE(off <= workspace_bytes, "batched decode: workspace layout");
@@ -760,15 +399,15 @@ int bdecode_step(const BDecodeArgs& m, const BLayer* layers, bf16_t* kcache, bf1
         qa.n = n; qa.N = QS + 2 * KS; qa.K = H; qa.mode = 2; qa.q_out = q; qa.ldq = QS; qa.kcache = kc; qa.vcache = vc; qa.slot_stride = slot_stride;
         qa.pos = pos; qa.rope_cs = rope_cs; qa.nq = m.q_heads; qa.nkv = m.kv_heads; qa.hd = hd; qa.max_ctx = max_ctx;
         VILA_TRY(proj(qa, Q.qkv_q, Q.qkv_sz));
-        AttnDecodeArgs ad{};
-        ad.q = q; ad.kcache = kc; ad.vcache = vc; ad.o = ao; ad.pos_ptr = pos; ad.nq = m.q_heads; ad.nkv = m.kv_heads; ad.hd = hd; ad.max_ctx = max_ctx;
-        ad.n_splits = cdiv(max_ctx, 64); ad.scale = 1.0f / sqrtf((float)hd);
-        BAttnArgs ba{};
-        ba.q = q; ba.o = ao; ba.kcache = kc; ba.vcache = vc; ba.pos = pos; ba.part_o = part_o; ba.part_ml = part_ml;
-        ba.nq = m.q_heads; ba.nkv = m.kv_heads; ba.max_ctx = max_ctx; ba.nsl = nsl; ba.row_stride = QS; ba.o_row_stride = QS; ba.slot_stride = slot_stride; ba.scale = ad.scale;
-        const int rc = form.walk ? launch_bdec_attn_walk(ba, n, s) : (m.q_heads % m.kv_heads == 0) ? launch_bdec_attn(ba, n, s) : 1;
+        const float scale = 1.0f / sqrtf((float)hd);
+        const int rc = bdecode_attn_launch(form, q, QS, kc, vc, slot_stride, pos, ao, QS, n, m.q_heads, m.kv_heads, max_ctx, scale, part_o, part_ml, s);
         if (rc < 0) return rc;
-        if (rc == 1) VILA_TRY(launch_attn_decode_rows(ad, n, QS, QS, slot_stride, s));       // group size without an instantiation: one block per query head
+        if (rc == 1) {                                                                       // group size without an instantiation: one block per query head
+            AttnDecodeArgs ad{};
+            ad.q = q; ad.kcache = kc; ad.vcache = vc; ad.o = ao; ad.pos_ptr = pos; ad.nq = m.q_heads; ad.nkv = m.kv_heads; ad.hd = hd; ad.max_ctx = max_ctx;
+            ad.n_splits = cdiv(max_ctx, 64); ad.scale = scale;
+            VILA_TRY(launch_attn_decode_rows(ad, n, QS, QS, slot_stride, s));
+        }
         BGemmArgs o{};
         o.x = ao; o.ldx = QS; o.W = (const bf16_t*)L.wo; o.residual = cur; o.ldr = H; o.y = nxt; o.ldy = H; o.n = n; o.N = H; o.K = QS; o.mode = 0;
         VILA_TRY(proj(o, Q.o_q, Q.o_sz));

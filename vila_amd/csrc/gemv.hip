@@ -5,16 +5,7 @@
 // (bias, RoPE, KV-cache write, SiLU*up, residual add) are fused so a decoder layer is 6 launches.
 #include "kernels.h"
 #include "gemv_common.h"
-
-#define DEC_KS 64      // keys per split of the decode attention
-#define DEC_MAXG 8     // max query heads per kv head
-
-typedef __attribute__((address_space(1))) unsigned long long gu64;
-__device__ __forceinline__ unsigned long long pack_f2(float a, float b) {
-    return (unsigned long long)__float_as_uint(a) | ((unsigned long long)__float_as_uint(b) << 32);
-}
-__device__ __forceinline__ float lo_f2(unsigned long long v) { return __uint_as_float((uint32_t)v); }
-__device__ __forceinline__ float hi_f2(unsigned long long v) { return __uint_as_float((uint32_t)(v >> 32)); }
+#include "attn_decode.h"
 
 __device__ __forceinline__ u32x4 ldg_nt(const bf16_t* p) { return __builtin_nontemporal_load((const u32x4*)p); }
 
@@ -33,18 +24,7 @@ template <int NT>
 __device__ __forceinline__ void stage_x_attn(const float* __restrict__ part_o, const float* __restrict__ part_ml, int n_active,
                                              int nq, bf16_t* sx, float* wsm /* [n_active*nq] */) {
     const int tid = threadIdx.x;
-    for (int h = tid; h < nq; h += NT) {
-        float M = -INFINITY;
-        for (int s = 0; s < n_active; ++s) M = fmaxf(M, part_ml[((int64_t)s * nq + h) * 2]);
-        float L = 0.f;
-        for (int s = 0; s < n_active; ++s) {
-            const float* ml = part_ml + ((int64_t)s * nq + h) * 2;
-            L += __expf(ml[0] - M) * ml[1];
-        }
-        const float invL = 1.f / L;
-        for (int s = 0; s < n_active; ++s) wsm[s * nq + h] = __expf(part_ml[((int64_t)s * nq + h) * 2] - M) * invL;
-    }
-    __syncthreads();
+    attn_merge_weights<NT>(part_ml, n_active, nq, wsm);
     const int n4 = nq * 32;   // float4 chunks
     for (int i = tid; i < n4; i += NT) {
         const int h = i >> 5;
@@ -391,277 +371,6 @@ int launch_qkv_decode(const QkvDecodeArgs& a, hipStream_t s) {
     if (a.K <= 3584) qkv_launch<7>(per, grid, lds, s, a, ncu);
     else qkv_launch<4>(per, grid, lds, s, a, ncu);
     VILA_LAUNCH_CHECK();
-    return 0;
-}
-
-// ------------------------------------------------------------------------------------------------
-// split-KV decode attention (q_len = 1, GQA, hd = 128): grid (n_splits, nkv); a block handles the G = nq/nkv query
-// heads of one kv head over a 64-key slice of the cache and writes the un-normalised partial O and (m, l).
-// The merge over splits is fused into the o_proj GEMV (gemv_kernel<2>).
-//   scores : thread = (key, quarter of d): 32 FMAs per head, 2 cross-lane adds
-//   P.V    : thread = (4 keys, 8-wide d chunk): 56 accumulators, reduced over the 16 key groups through LDS
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void attn_decode_partial(AttnDecodeArgs p) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    float* sq = (float*)smem;                       // [G][128]  (pre-scaled)
-    float* sc = sq + DEC_MAXG * 128;                // [G][64]
-    float* red = sc + DEC_MAXG * DEC_KS;            // [16][G][128]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int split = blockIdx.x, kvh = blockIdx.y;
-    const int G = p.nq / p.nkv;
-    const int nkeys = *p.pos_ptr + 1;
-    const int k0 = split * DEC_KS;
-    if (k0 >= nkeys) return;
-    const int kn = (nkeys - k0) < DEC_KS ? (nkeys - k0) : DEC_KS;
-    const bf16_t* kb = p.kcache + ((int64_t)kvh * p.max_ctx + k0) * 128;
-    const bf16_t* vb = p.vcache + ((int64_t)kvh * p.max_ctx + k0) * 128;
-
-    const int kq = tid >> 2, qd = tid & 3;          // scores: key, d quarter
-    const int vkg = tid >> 4, vch = tid & 15;       // P.V: key group (4 keys), d chunk
-    u32x4 kv_[4], vv_[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        kv_[j] = (kq < kn) ? *(const u32x4*)(kb + kq * 128 + qd * 32 + j * 8) : (u32x4){0u, 0u, 0u, 0u};
-        const int key = vkg * 4 + j;
-        vv_[j] = (key < kn) ? *(const u32x4*)(vb + key * 128 + vch * 8) : (u32x4){0u, 0u, 0u, 0u};
-    }
-    for (int i = tid; i < G * 128; i += 256) sq[i] = bf2f(p.q[kvh * G * 128 + i]) * p.scale;
-    __syncthreads();
-
-    for (int g = 0; g < G; ++g) {
-        float a = 0.f;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const f32x4 q0 = *(const f32x4*)(sq + g * 128 + qd * 32 + j * 8);
-            const f32x4 q1 = *(const f32x4*)(sq + g * 128 + qd * 32 + j * 8 + 4);
-            a = fmaf(lo_bf(kv_[j][0]), q0[0], a); a = fmaf(hi_bf(kv_[j][0]), q0[1], a);
-            a = fmaf(lo_bf(kv_[j][1]), q0[2], a); a = fmaf(hi_bf(kv_[j][1]), q0[3], a);
-            a = fmaf(lo_bf(kv_[j][2]), q1[0], a); a = fmaf(hi_bf(kv_[j][2]), q1[1], a);
-            a = fmaf(lo_bf(kv_[j][3]), q1[2], a); a = fmaf(hi_bf(kv_[j][3]), q1[3], a);
-        }
-        a += __shfl_xor(a, 1, 64);
-        a += __shfl_xor(a, 2, 64);
-        if (qd == 0) sc[g * DEC_KS + kq] = kq < kn ? a : -INFINITY;
-    }
-    __syncthreads();
-
-    for (int g = wave; g < G; g += 4) {             // softmax statistics: one wave per head, lane = key
-        const float s = sc[g * DEC_KS + lane];
-        const float m = wave_max(s);
-        const float e = __expf(s - m);
-        const float l = wave_sum(e);
-        sc[g * DEC_KS + lane] = e;
-        if (lane == 0) {
-            // (m, l) as ONE 8-byte write-through (sc1) store: the combine below reads it with sc1 loads, no fences needed
-            gu64* ml = (gu64*)(p.part_ml + ((int64_t)split * p.nq + kvh * G + g) * 2);
-            __hip_atomic_store(ml, pack_f2(m, l), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
-    __syncthreads();
-
-    for (int g = 0; g < G; ++g) {
-        float o[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) o[k] = 0.f;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float pr = sc[g * DEC_KS + vkg * 4 + j];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                o[2 * k] = fmaf(pr, lo_bf(vv_[j][k]), o[2 * k]);
-                o[2 * k + 1] = fmaf(pr, hi_bf(vv_[j][k]), o[2 * k + 1]);
-            }
-        }
-        float* r = red + ((vkg * G + g) * 128 + vch * 8);
-        *(f32x4*)r = (f32x4){o[0], o[1], o[2], o[3]};
-        *(f32x4*)(r + 4) = (f32x4){o[4], o[5], o[6], o[7]};
-    }
-    __syncthreads();
-    // partial O as 8-byte write-through (sc1) stores (guide G16 R1: payload sc1 -> every storing wave drains -> flag)
-    for (int i = tid; i < G * 64; i += 256) {
-        float o0 = 0.f, o1 = 0.f;
-#pragma unroll
-        for (int kg = 0; kg < 16; ++kg) { o0 += red[kg * G * 128 + 2 * i]; o1 += red[kg * G * 128 + 2 * i + 1]; }
-        gu64* dst = (gu64*)(p.part_o + ((int64_t)split * p.nq + kvh * G) * 128 + 2 * i);
-        __hip_atomic_store(dst, pack_f2(o0, o1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-}
-
-// merge of the split partials.  Measured alternatives (profiles/r01 notes in DESIGN.md §4.3): combine by the last-arriving
-// block inside the partial kernel (fences: 14.6 us, sc1 stores+loads: 16.3 us) and combine inside the o_proj GEMV prologue
-// (18.0 us for o_proj) are all no faster than this separate 7 us launch, so the simplest form is kept.
-__global__ __launch_bounds__(128) void attn_decode_merge(AttnDecodeArgs p) {
-    const int h = blockIdx.x, d = threadIdx.x;
-    const int nkeys = *p.pos_ptr + 1;
-    const int ns = (nkeys + DEC_KS - 1) / DEC_KS;
-    float M = -INFINITY;
-    for (int s = 0; s < ns; ++s) M = fmaxf(M, p.part_ml[((int64_t)s * p.nq + h) * 2]);
-    float L = 0.f, o = 0.f;
-    for (int s = 0; s < ns; ++s) {
-        const float* ml = p.part_ml + ((int64_t)s * p.nq + h) * 2;
-        const float w = __expf(ml[0] - M);
-        L += w * ml[1];
-        o += w * p.part_o[((int64_t)s * p.nq + h) * 128 + d];
-    }
-    p.o[h * 128 + d] = f2bf(o / L);
-}
-
-// ------------------------------------------------------------------------------------------------
-// single-launch decode attention for short contexts (cache capacity <= 2048): one block of 16 waves per QUERY head walks the
-// whole context (wave w takes 16-key chunks w, w+16, ...), online softmax per wave, cross-wave merge in LDS.  No split-KV
-// partials and no merge launch: 2 launches -> 1 per layer (each launch costs ~3-4 us of floor inside the decode graph); the
-// price is that the G = 7 query heads of a kv head each read that head's K/V (served by L2 / MALL, 2.5 % of a token's bytes).
-//   scores: lane = (key = lane/4, d quarter = lane%4): 32 FMAs + 2 cross-lane adds;  P.V: lane = (4-key subgroup, 8-wide d chunk)
-// ------------------------------------------------------------------------------------------------
-// SPLIT: grid (nq, ceil(max_ctx / 256)); block (h, s) covers keys [256 s, 256 s + 256) — ONE 16-key chunk per wave, no loop — and writes the
-// un-normalised partial (o, m, l) of that slice; the merge over the <= 8 slices happens in the o_proj GEMV's prologue (gemv_kernel<2>).
-template <bool SPLIT>
-__global__ __launch_bounds__(1024) void attn_decode_head(AttnDecodeArgs p) {
-    __shared__ float sq[128];
-    __shared__ float so[16][128];
-    __shared__ float sml[16][2];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int h = blockIdx.x, kvh = h / (p.nq / p.nkv);
-    const int key_lo = SPLIT ? blockIdx.y * 256 : 0;
-    const int row = blockIdx.z;                                  // batched decode: sequence = cache slot (0 for the batch-1 step)
-    p.q += row * p.q_row_stride; p.kcache += row * p.slot_stride; p.vcache += row * p.slot_stride;
-    if (!SPLIT) p.o += row * p.o_row_stride;
-    const int nkeys_all = p.pos_ptr[row] + 1;
-    if (SPLIT && key_lo >= nkeys_all) return;                    // block-uniform: slices beyond the context write nothing (the merge skips them)
-    const int nkeys = SPLIT ? (nkeys_all < key_lo + 256 ? nkeys_all : key_lo + 256) : nkeys_all;
-    const bf16_t* kb = p.kcache + (int64_t)kvh * p.max_ctx * 128;
-    const bf16_t* vb = p.vcache + (int64_t)kvh * p.max_ctx * 128;
-    if (tid < 128) sq[tid] = bf2f(p.q[h * 128 + tid]) * p.scale;
-    __syncthreads();
-    const int kq = lane >> 2, qd = lane & 3;        // scores: key within the chunk, d quarter
-    const int sg = lane >> 4, dc = lane & 15;       // P.V: 4-key subgroup, d chunk
-    float qr[32];
-#pragma unroll
-    for (int i = 0; i < 32; ++i) qr[i] = sq[qd * 32 + i];
-    float m = -INFINITY, l = 0.f, o[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) o[e] = 0.f;
-
-    u32x4 kc[4], vc[4], kn_[4], vn_[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { kn_[j] = (u32x4){0u, 0u, 0u, 0u}; vn_[j] = (u32x4){0u, 0u, 0u, 0u}; }
-    auto load_chunk = [&](int k0, u32x4 (&kk)[4], u32x4 (&vv)[4]) {
-        const int key = k0 + kq;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            kk[j] = (key < nkeys) ? *(const u32x4*)(kb + (int64_t)key * 128 + qd * 32 + j * 8) : (u32x4){0u, 0u, 0u, 0u};
-            const int vk = k0 + sg * 4 + j;
-            vv[j] = (vk < nkeys) ? *(const u32x4*)(vb + (int64_t)vk * 128 + dc * 8) : (u32x4){0u, 0u, 0u, 0u};
-        }
-    };
-    int k0 = key_lo + wave * 16;
-    if (k0 < nkeys) load_chunk(k0, kc, vc);
-    for (; k0 < nkeys; k0 += 256) {
-        const int kn = k0 + 256;
-        if (kn < nkeys) load_chunk(kn, kn_, vn_);            // prefetch the wave's next chunk under this chunk's math
-        float a = 0.f;
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                a = fmaf(lo_bf(kc[j][e]), qr[j * 8 + 2 * e], a);
-                a = fmaf(hi_bf(kc[j][e]), qr[j * 8 + 2 * e + 1], a);
-            }
-        a += __shfl_xor(a, 1, 64);
-        a += __shfl_xor(a, 2, 64);
-        const float s = (k0 + kq < nkeys) ? a : -INFINITY;
-        float cm = s;
-        cm = fmaxf(cm, __shfl_xor(cm, 4, 64)); cm = fmaxf(cm, __shfl_xor(cm, 8, 64));
-        cm = fmaxf(cm, __shfl_xor(cm, 16, 64)); cm = fmaxf(cm, __shfl_xor(cm, 32, 64));
-        const float m_new = fmaxf(m, cm);
-        const float alpha = __expf(m - m_new);
-        const float pr = __expf(s - m_new);
-        float ps = pr;
-        ps += __shfl_xor(ps, 4, 64); ps += __shfl_xor(ps, 8, 64); ps += __shfl_xor(ps, 16, 64); ps += __shfl_xor(ps, 32, 64);
-        l = l * alpha + ps;
-        m = m_new;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] *= alpha;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float pj = __shfl(pr, (sg * 4 + j) * 4, 64);   // probability of key k0 + sg*4 + j (held by lanes 4*key .. 4*key+3)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                o[2 * e] = fmaf(pj, lo_bf(vc[j][e]), o[2 * e]);
-                o[2 * e + 1] = fmaf(pj, hi_bf(vc[j][e]), o[2 * e + 1]);
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { kc[j] = kn_[j]; vc[j] = vn_[j]; }
-    }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { o[e] += __shfl_xor(o[e], 16, 64); o[e] += __shfl_xor(o[e], 32, 64); }
-    if (lane < 16) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) so[wave][dc * 8 + e] = o[e];
-    }
-    if (lane == 0) { sml[wave][0] = m; sml[wave][1] = l; }
-    __syncthreads();
-    if (tid < 128) {
-        float M = -INFINITY;
-#pragma unroll
-        for (int w = 0; w < 16; ++w) M = fmaxf(M, sml[w][0]);
-        float L = 0.f, acc = 0.f;
-#pragma unroll
-        for (int w = 0; w < 16; ++w) {
-            const float wgt = __expf(sml[w][0] - M);
-            L += wgt * sml[w][1];
-            acc += wgt * so[w][tid];
-        }
-        if (SPLIT) {
-            const int64_t slot = (int64_t)blockIdx.y * p.nq + h;
-            p.part_o[slot * 128 + tid] = acc;
-            if (tid == 0) { p.part_ml[slot * 2] = M; p.part_ml[slot * 2 + 1] = L; }
-        } else {
-            p.o[h * 128 + tid] = f2bf(acc / L);
-        }
-    }
-}
-
-
-// batched decode: one block per (query head, sequence) over the sequence's whole context (caches up to 2048 positions)
-int launch_attn_decode_rows(const AttnDecodeArgs& a0, int n_rows, int64_t q_row_stride, int64_t o_row_stride, int64_t slot_stride, hipStream_t s) {
-    AttnDecodeArgs a = a0;
-    VILA_REQUIRE(a.hd == 128 && a.o != nullptr && a.max_ctx <= 2048 && n_rows >= 1, "attn_decode_rows: head_dim 128, caches up to 2048 positions");
-    VILA_REQUIRE(a.nq % a.nkv == 0, "attn_decode_rows: q heads must be a multiple of kv heads");
-    a.q_row_stride = q_row_stride; a.o_row_stride = o_row_stride; a.slot_stride = slot_stride;
-    hipLaunchKernelGGL(attn_decode_head<false>, dim3(a.nq, 1, n_rows), dim3(1024), 0, s, a);
-    VILA_LAUNCH_CHECK();
-    return 0;
-}
-
-int launch_attn_decode(const AttnDecodeArgs& a, hipStream_t s) {
-    VILA_REQUIRE(a.hd == 128, "attn_decode: head_dim must be 128 (got %d)", a.hd);
-    VILA_REQUIRE(a.nq % a.nkv == 0 && a.nq / a.nkv <= DEC_MAXG, "attn_decode: GQA group %d/%d unsupported (max %d)", a.nq, a.nkv, DEC_MAXG);
-    VILA_REQUIRE(a.n_splits * DEC_KS >= a.max_ctx, "attn_decode: n_splits too small for max_ctx");
-    if (a.split256) {                                            // partials per 256-key slice; merged by the o_proj GEMV (mode 2, split_keys 256)
-        VILA_REQUIRE(a.max_ctx <= 2048 && a.n_splits * DEC_KS >= a.max_ctx, "attn_decode: 256-key slices need max_ctx <= 2048");
-        hipLaunchKernelGGL(attn_decode_head<true>, dim3(a.nq, cdiv(a.max_ctx, 256)), dim3(1024), 0, s, a);
-        VILA_LAUNCH_CHECK();
-        return 0;
-    }
-    if (a.o != nullptr && a.max_ctx <= 2048 && !a.force_split) {
-        hipLaunchKernelGGL(attn_decode_head<false>, dim3(a.nq), dim3(1024), 0, s, a);
-        VILA_LAUNCH_CHECK();
-        return 0;
-    }
-    const size_t lds = (size_t)(DEC_MAXG * 128 + DEC_MAXG * DEC_KS + 16 * DEC_MAXG * 128) * 4;
-    static bool attr_set = false;
-    if (!attr_set) {
-        VILA_HIP(hipFuncSetAttribute((const void*)attn_decode_partial, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(attn_decode_partial, dim3(a.n_splits, a.nkv), dim3(256), lds, s, a);
-    VILA_LAUNCH_CHECK();
-    if (a.o != nullptr) {
-        hipLaunchKernelGGL(attn_decode_merge, dim3(a.nq), dim3(128), 0, s, a);
-        VILA_LAUNCH_CHECK();
-    }
     return 0;
 }
 

@@ -18,6 +18,7 @@
 // and the zero point come out per group:   y[n] += scale * (D - (128 + zero) * sum(x))     (group sums precomputed in LDS).
 // One workgroup = one 16-row tile; its W waves split K (contiguous group ranges), partial sums meet in LDS.
 #include "gemv_common.h"
+#include "attn_decode.h"
 #include "w4.h"
 
 #define W4_MAX_WAVES 16
@@ -102,18 +103,7 @@ __device__ __forceinline__ void stage_x_w4(const bf16_t* __restrict__ x, const b
 __device__ __forceinline__ void stage_x_attn_w4(const float* __restrict__ part_o, const float* __restrict__ part_ml, int n_active, int nq,
                                                 bf16_t* sx, float* xg, float* wsm /* [n_active * nq] */) {
     const int tid = threadIdx.x, nt = blockDim.x;
-    for (int h = tid; h < nq; h += nt) {
-        float M = -INFINITY;
-        for (int s = 0; s < n_active; ++s) M = fmaxf(M, part_ml[((int64_t)s * nq + h) * 2]);
-        float L = 0.f;
-        for (int s = 0; s < n_active; ++s) {
-            const float* ml = part_ml + ((int64_t)s * nq + h) * 2;
-            L += __expf(ml[0] - M) * ml[1];
-        }
-        const float invL = 1.f / L;
-        for (int s = 0; s < n_active; ++s) wsm[s * nq + h] = __expf(part_ml[((int64_t)s * nq + h) * 2] - M) * invL;
-    }
-    __syncthreads();
+    attn_merge_weights(part_ml, n_active, nq, wsm);
     const int nch = nq * 16;                                    // chunks of 8; a multiple of 16, so aligned 16-lane groups are in range together
     for (int c = tid; c < nch; c += nt) {
         const int h = c >> 4;

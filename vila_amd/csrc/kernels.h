@@ -101,7 +101,7 @@ struct AttnArgs {
 };
 int launch_attn_fwd(const AttnArgs& a, hipStream_t s);
 
-// ---- decode (gemv.hip) ----
+// ---- decode (gemv.hip; the attention: attn_decode.hip, shared device pieces and constants in attn_decode.h) ----
 struct GemvArgs {
     const bf16_t* x;          // [K] activations (bf16)
     const bf16_t* norm_w;     // optional RMSNorm gain fused in front (null = none)
@@ -135,9 +135,9 @@ struct AttnDecodeArgs {
     float* part_o; float* part_ml;   // workspace: [n_splits][nq][hd], [n_splits][nq][2]
     const int32_t* pos_ptr;          // context length BEFORE this token; keys 0..pos inclusive are attended
     int nq, nkv, hd, max_ctx, n_splits; float scale;
-    int force_split;                 // 1: always use the split-KV + merge pair (default: single-launch per-head kernel when max_ctx <= 2048)
     int split256;                    // 1: per-head blocks over 256-key slices, partials only (merged in the o_proj GEMV prologue)
-    // batched decode (decode_batch.hip): row = blockIdx.z reads q + row * q_row_stride, cache slot row (+ row * slot_stride), pos_ptr[row]
+    // row = blockIdx.z reads q + row * q_row_stride, cache slot row (+ row * slot_stride), pos_ptr[row]; the three strides are meaningful only for
+    // launch_attn_decode_rows (which fills them) and zero otherwise
     int64_t q_row_stride, o_row_stride, slot_stride;
 };
 int launch_attn_decode(const AttnDecodeArgs& a, hipStream_t s);
@@ -158,6 +158,15 @@ struct BLayerW4 { const void *qkv_q, *qkv_sz, *o_q, *o_sz, *gateup_q, *gateup_sz
 #define BDEC_SLICE_CAP 8          // measured against 16 and 32 (profiles/long_batch_decode_bench.json): best at n = 8 and 16, within 1 - 4 % at n = 2
 #define BDEC_MAX_SLICES 32
 size_t bdecode_workspace_bytes(int H, int F, int QS, int hd, int n, int max_ctx = BDEC_SHORT_CTX);   // the same bytes for every max_ctx <= 2048
+// the batched step's attention (attn_decode.hip).  The form at a capacity: the short one with a slice per chunk, or the walking one with nsl slices
+struct BAttnForm { bool walk; int nsl; };
+BAttnForm bdec_attn_form(int max_ctx);
+bool bdec_group_ok(int G);              // GQA group sizes the two forms are instantiated for
+int bdec_ws_slices(int max_ctx);        // partial slots per (row, query head) that a workspace holds at this capacity
+// the launches of one layer on partials laid out for f.nsl slices; returns 1, with nothing launched, when the short form has no instantiation for the
+// GQA group (the caller then runs launch_attn_decode_rows)
+int bdecode_attn_launch(const BAttnForm& f, const bf16_t* q, int64_t ldq, const bf16_t* kcache, const bf16_t* vcache, int64_t slot_stride, const int32_t* pos,
+                        bf16_t* o, int64_t ldo, int rows, int nq, int nkv, int max_ctx, float scale, float* part_o, float* part_ml, hipStream_t s);
 void bdecode_force_slices(int nsl);
 int bdecode_attn_slices(int max_ctx);   // slices of the walking form at this capacity under the current hook, 0 = the short form
 // the step's attention on its own: q [rows][ldq], o [rows][ldo], one layer's cache [slots][nkv][max_ctx][128], keys 0 .. pos[row] of slot `row`
