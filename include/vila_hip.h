@@ -240,6 +240,52 @@ int vila_attn_decode_batch_bf16(const void* q, int64_t ldq, const void* kcache, 
                                 void* o, int64_t ldo, int n_rows, int q_heads, int kv_heads, int max_ctx, float scale,
                                 void* workspace, size_t workspace_bytes, vila_stream_t stream);
 
+/* Greedy speculative decoding with lookup drafts (HF generate(prompt_lookup_num_tokens=k)): one step runs n = k + 1 consecutive positions of ONE
+ * sequence in ONE cache slot and keeps as many tokens as the model itself would have chosen one by one.  Three stages, all on the device, so one
+ * hipGraph replay is one speculative step:
+ *   draft    token[1..n_draft] = a guess at what follows token[0]: HF PromptLookupCandidateGenerator on hist[0 : n_hist] (ngram sizes
+ *            min(max_ngram, n_hist - 1) .. 1, the earliest window equal to the last ngram ids that has a continuation, up to n - 1 ids of it), or in
+ *            candidate mode (cand != NULL and *n_cand >= 0) cand[*n_out + j], j < n - 1, cut at *n_cand: the candidate is a prediction of out_ids,
+ *            aligned by output index;
+ *   forward  row i consumes token[i] at position pos + i of the slot (K/V appended there; rows at or past max_ctx append nothing) and attends keys
+ *            0 .. min(pos + i, max_ctx - 1); the slot's K/V is read once for all rows (vila_attn_decode_verify_bf16).  Rows past 1 + n_draft are
+ *            padding: what they append is overwritten by the next step before anything reads it;
+ *   accept   a[i] = first index of the maximum of logits row i; m = the largest value <= n_draft with a[j] == token[j + 1] for all j < m; a[0..m] are
+ *            appended to out_ids and hist (each up to its capacity), n_out, pos and n_hist move by m + 1 (n_hist stops at hist_cap),
+ *            token[0] = a[m], n_accept = m.
+ * A row's logits do not depend on the other rows or on n, so the ids are exactly those of a session that drafts nothing.  head_dim 128,
+ * q_heads * head_dim == hidden, a GQA group of 1, 2, 4, 7 or 8, max_ctx <= 32768; anything else is refused before a launch.  n is 2..16. */
+typedef struct {
+    int n;               /* rows per step: 1 committed token + up to n - 1 drafts */
+    int slot;            /* KV-cache slot the sequence lives in */
+    int32_t* pos;        /* scalar: tokens in the cache = position of token[0] */
+    int64_t* token;      /* [n]: token[0] in / out; token[1..] the drafts of the last step */
+    int32_t* n_draft;    /* scalar (out): drafts the last step offered, 0 .. n - 1 */
+    int64_t* out_ids;    /* [max_out] */
+    int32_t* n_out;      /* scalar */
+    int max_out;
+    float* logits;       /* [n][vocab] fp32 logits of the last step */
+    int32_t* n_accept;   /* scalar (out): drafts the last step accepted */
+    int64_t* hist;       /* [hist_cap]: the prompt's ids followed by everything generated, token[0] last (NULL with a candidate: no history kept) */
+    int32_t* n_hist;     /* scalar */
+    int hist_cap;
+    int max_ngram;       /* >= 1; HF's max_matching_ngram_size (default 2) */
+    const int64_t* cand; /* nullable: a predicted output */
+    const int32_t* n_cand; /* scalar; < 0: lookup mode although cand is set */
+} VilaDecodeVerify;
+size_t vila_llm_decode_verify_workspace_bytes(const VilaLlmShape* s, int n, int max_ctx);
+int vila_llm_decode_step_verify(const VilaLlmWeights* w, const VilaKvCache* cache, const VilaDecodeVerify* st,
+                                void* workspace, size_t workspace_bytes, vila_stream_t stream);
+/* The draft stage on its own (lookup mode): hist [*n_hist] -> token[1 .. *n_draft], the rest of token[1 .. n - 1] = token[0]. */
+int vila_prompt_lookup_draft(const int64_t* hist, const int32_t* n_hist, int max_ngram, int n, int64_t* token, int32_t* n_draft,
+                             vila_stream_t stream);
+/* The verify step's attention on its own: row i of q [n][ldq] (q_heads x 128 bf16) attends keys 0 .. min(*pos + i, max_ctx - 1) of ONE slot of one
+ * layer, kslot / vslot [kv_heads][max_ctx][128]; o [n][ldo] bf16; n in 1..16.  Two launches; the slice count follows vila_decode_batch_force_slices. */
+size_t vila_attn_decode_verify_workspace_bytes(int n, int q_heads, int max_ctx);
+int vila_attn_decode_verify_bf16(const void* q, int64_t ldq, const void* kslot, const void* vslot, const int32_t* pos, void* o, int64_t ldo,
+                                 int n, int q_heads, int kv_heads, int max_ctx, float scale, void* workspace, size_t workspace_bytes,
+                                 vila_stream_t stream);
+
 /* hipGraph helpers: capture whatever is enqueued on `stream` between begin/end, replay it later. */
 int vila_graph_begin(vila_stream_t stream);
 int vila_graph_end(vila_stream_t stream, void** graph_exec_out);
@@ -469,6 +515,9 @@ size_t vila_llm_decode_batch_w4_sample_workspace_bytes_ctx(const VilaLlmShape* s
 int vila_llm_decode_step_batch_w4_sample(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers /*[host]*/, const VilaKvCache* cache,
                                          const VilaDecodeBatch* st, void* workspace, size_t workspace_bytes, const VilaBatchSampling* sp,
                                          vila_stream_t stream);
+/* vila_llm_decode_step_verify with the four projections of every layer read from `qlayers`; workspace of vila_llm_decode_verify_workspace_bytes */
+int vila_llm_decode_step_verify_w4(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers /*[host]*/, const VilaKvCache* cache,
+                                   const VilaDecodeVerify* st, void* workspace, size_t workspace_bytes, vila_stream_t stream);
 
 /* W4A16 prefill GEMM (vila_amd/csrc/gemm_w4.hip) on the same packed buffers: y[M][N] = x[M][K] . W^T, x bf16 row stride K, y row stride N,
  * any M >= 1.  mode 0: (+bias)(+residual, row stride N; y may alias it); mode 1: W holds 2N interleaved gate/up rows, y = silu(Wg x) * (Wu x),

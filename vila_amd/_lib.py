@@ -63,6 +63,12 @@ class VilaDecodeBatch(C.Structure):
                 ("logits", c_void_p)]
 
 
+class VilaDecodeVerify(C.Structure):
+    _fields_ = [("n", c_int), ("slot", c_int), ("pos", c_void_p), ("token", c_void_p), ("n_draft", c_void_p), ("out_ids", c_void_p), ("n_out", c_void_p),
+                ("max_out", c_int), ("logits", c_void_p), ("n_accept", c_void_p), ("hist", c_void_p), ("n_hist", c_void_p), ("hist_cap", c_int),
+                ("max_ngram", c_int), ("cand", c_void_p), ("n_cand", c_void_p)]
+
+
 class VilaSampling(C.Structure):
     _fields_ = [("temperature", c_float), ("top_k", c_int), ("top_p", c_float), ("seed", C.c_uint64), ("seed_dev", c_void_p)]
 
@@ -124,6 +130,14 @@ PROTOTYPES = {
     "vila_attn_decode_batch_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "vila_attn_decode_batch_bf16": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int,
                                             c_float, c_void_p, c_size_t, c_void_p]),
+    "vila_llm_decode_verify_workspace_bytes": (c_size_t, [C.POINTER(VilaLlmShape), c_int, c_int]),
+    "vila_llm_decode_step_verify": (c_int, [C.POINTER(VilaLlmWeights), C.POINTER(VilaKvCache), C.POINTER(VilaDecodeVerify), c_void_p, c_size_t, c_void_p]),
+    "vila_llm_decode_step_verify_w4": (c_int, [C.POINTER(VilaLlmWeights), C.POINTER(VilaLlmLayerW4), C.POINTER(VilaKvCache), C.POINTER(VilaDecodeVerify),
+                                               c_void_p, c_size_t, c_void_p]),
+    "vila_prompt_lookup_draft": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "vila_attn_decode_verify_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "vila_attn_decode_verify_bf16": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_float, c_void_p,
+                                             c_size_t, c_void_p]),
     "vila_decode_batch_force_slices": (None, [c_int]),
     "vila_decode_batch_slices": (c_int, [c_int]),
     "vila_sample_batch_workspace_bytes": (c_size_t, [c_int]),

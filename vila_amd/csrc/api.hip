@@ -751,6 +751,62 @@ extern "C" int vila_llm_decode_step_batch_w4_sample(const VilaLlmWeights* w, con
     VILA_REQUIRE(qlayers != nullptr, "llm_decode_batch_w4: NULL argument");
     return decode_step_batch_impl(w, qlayers, cache, st, workspace, workspace_bytes, sp, stream);
 }
+// The verify step (greedy speculative decoding, decode_batch.hip bverify_step): the layer tables are the batched step's, the state is one sequence's.
+static int decode_step_verify_impl(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers, const VilaKvCache* cache, const VilaDecodeVerify* st,
+                                   void* workspace, size_t workspace_bytes, vila_stream_t stream) {
+    const bool w4 = qlayers != nullptr;
+    const char* fn = w4 ? "llm_decode_verify_w4" : "llm_decode_verify";
+    VILA_REQUIRE(w != nullptr && cache != nullptr && st != nullptr && workspace != nullptr, "%s: NULL argument", fn);
+    const VilaLlmShape& sh = w->shape;
+    const int QS = sh.q_heads * sh.head_dim, KS = sh.kv_heads * sh.head_dim;
+    std::vector<BLayer> layers(sh.n_layers);
+    std::vector<BLayerW4> ql(w4 ? sh.n_layers : 0);
+    for (int l = 0; l < sh.n_layers; ++l) {
+        const VilaLlmLayer& L = w->layers[l];
+        if (w4) {
+            const VilaLlmLayerW4& Q = qlayers[l];
+            VILA_REQUIRE(L.bq != nullptr && B(L.bk) == B(L.bq) + QS && B(L.bv) == B(L.bk) + KS,
+                         "llm_decode_verify_w4: the q/k/v biases must be one contiguous q|k|v vector (layer %d)", l);
+            VILA_REQUIRE(Q.qkv_q && Q.qkv_sz && Q.o_q && Q.o_sz && Q.gateup_q && Q.gateup_sz && Q.down_q && Q.down_sz,
+                         "llm_decode_verify_w4: int4 layer %d has a NULL buffer", l);
+            layers[l] = BLayer{L.ln1_w, nullptr, L.bq, nullptr, L.ln2_w, nullptr, nullptr, nullptr};
+            ql[l] = BLayerW4{Q.qkv_q, Q.qkv_sz, Q.o_q, Q.o_sz, Q.gateup_q, Q.gateup_sz, Q.down_q, Q.down_sz};
+        } else {
+            VILA_REQUIRE(qkv_fused(L.wq, L.wk, L.wv, L.bq, L.bk, L.bv, QS, KS, sh.hidden),
+                         "llm_decode_verify: q/k/v projection weights and biases must be views of one fused [q+2kv, hidden] buffer");
+            layers[l] = BLayer{L.ln1_w, L.wq, L.bq, L.wo, L.ln2_w, L.w_gate, L.w_up, L.w_down};
+        }
+    }
+    BDecodeArgs m{w->embed, w->norm_w, w->lm_head, sh.hidden, sh.inter, sh.n_layers, sh.q_heads, sh.kv_heads, sh.head_dim, sh.vocab, sh.rms_eps, sh.rope_theta};
+    BVerifyState v{st->n, st->slot, st->pos, st->token, st->n_draft, st->out_ids, st->n_out, st->max_out, st->logits, st->n_accept,
+                   st->hist, st->n_hist, st->hist_cap, st->max_ngram, st->cand, st->n_cand};
+    return bverify_step(m, layers.data(), B(cache->k), B(cache->v), cache->max_ctx, cache->n_slots, v, workspace, workspace_bytes, S(stream),
+                        w4 ? ql.data() : nullptr);
+}
+extern "C" size_t vila_llm_decode_verify_workspace_bytes(const VilaLlmShape* s, int n, int max_ctx) {
+    return bverify_workspace_bytes(s->hidden, s->inter, s->q_heads * s->head_dim, s->head_dim, n, max_ctx);
+}
+extern "C" int vila_llm_decode_step_verify(const VilaLlmWeights* w, const VilaKvCache* cache, const VilaDecodeVerify* st, void* workspace,
+                                           size_t workspace_bytes, vila_stream_t stream) {
+    return decode_step_verify_impl(w, nullptr, cache, st, workspace, workspace_bytes, stream);
+}
+extern "C" int vila_llm_decode_step_verify_w4(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers, const VilaKvCache* cache, const VilaDecodeVerify* st,
+                                              void* workspace, size_t workspace_bytes, vila_stream_t stream) {
+    VILA_REQUIRE(qlayers != nullptr, "llm_decode_verify_w4: NULL argument");
+    return decode_step_verify_impl(w, qlayers, cache, st, workspace, workspace_bytes, stream);
+}
+// the verify step's draft stage and its attention on their own (operator level)
+extern "C" int vila_prompt_lookup_draft(const int64_t* hist, const int32_t* n_hist, int max_ngram, int n, int64_t* token, int32_t* n_draft,
+                                        vila_stream_t stream) {
+    VILA_REQUIRE(hist != nullptr && n_hist != nullptr, "prompt_lookup_draft: NULL argument");
+    return launch_verify_draft(hist, n_hist, max_ngram, nullptr, nullptr, nullptr, n, token, n_draft, nullptr, nullptr, S(stream));
+}
+extern "C" size_t vila_attn_decode_verify_workspace_bytes(int n, int q_heads, int max_ctx) { return bverify_attn_workspace_bytes(n, q_heads, max_ctx); }
+extern "C" int vila_attn_decode_verify_bf16(const void* q, int64_t ldq, const void* kslot, const void* vslot, const int32_t* pos, void* o, int64_t ldo, int n,
+                                            int q_heads, int kv_heads, int max_ctx, float scale, void* workspace, size_t workspace_bytes,
+                                            vila_stream_t stream) {
+    return bverify_attn(B(q), ldq, B(kslot), B(vslot), pos, (bf16_t*)o, ldo, n, q_heads, kv_heads, max_ctx, scale, workspace, workspace_bytes, S(stream));
+}
 // the batched step's attention alone (operator level): the form is chosen as the step chooses it
 extern "C" size_t vila_attn_decode_batch_workspace_bytes(int n_rows, int q_heads, int max_ctx) { return bdecode_attn_workspace_bytes(n_rows, q_heads, max_ctx); }
 extern "C" int vila_attn_decode_batch_bf16(const void* q, int64_t ldq, const void* kcache, const void* vcache, int64_t slot_stride, const int32_t* pos, void* o,

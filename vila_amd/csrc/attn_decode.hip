@@ -630,3 +630,261 @@ int bdecode_attn(const bf16_t* q, int64_t ldq, const bf16_t* kcache, const bf16_
     float* part_ml = (float*)((char*)workspace + align_up((size_t)rows * nq * f.nsl * 128 * 4, 256));
     return bdecode_attn_launch(f, q, ldq, kcache, vcache, slot_stride, pos, o, ldo, rows, nq, nkv, max_ctx, scale, (float*)workspace, part_ml, s);
 }
+
+// ---- the verify step's form: n rows of ONE sequence share the K/V read -----------------------------------------------------------------
+// A speculative step (decode_batch.hip bverify_step) runs n consecutive positions of one sequence in one cache slot: row i holds position pos + i and
+// sees keys 0 .. pos + i.  Through the kernels above (slot_stride 0) every row would pull the same K/V through its own blocks.  Here the columns of
+// the score tile are (row, head) pairs, col = row * G + head, ceil(n G / 16) tiles of 16, and the 16 keys a wave loads serve all of them:
+//   * scores  S[key][col] = K . Q^T, v_mfma_f32_16x16x32_bf16 as above, 4 per column tile; each column masks by its own limit min(pos + row, max_ctx - 1);
+//   * P.V on the matrix core.  The VALU form above keeps 8 fp32 of O per head and lane; with up to 128 columns that is 1024 registers.  The C
+//     layout of the score tile (lane = column, registers = the lane group's 4 keys) IS the B operand of v_mfma_f32_16x16x16_bf16 (k = 4 keys per
+//     lane group), and the V rows a lane loads for the VALU form (4 keys x 8 consecutive d) hold, element e of the 4 keys, its A operand for
+//     the 16 outputs d = 8 l15 + e: O^T[d][col] += V^T[d][key] . P^T[key][col], 8 MFMAs per column tile, no cross-lane movement, no LDS, and the
+//     accumulator's column is the lane's own softmax column (the rescale is lane-local).  P is rounded to bf16 and l sums the rounded values, so a
+//     column's output stays a convex combination of V rows: |o - exact| <= 2^-9 max|V| before the bf16 store;
+//   * a block = 8 waves on one (kv head, slice, group of up to 4 column tiles): 128 accumulator registers per lane of the 256 a wave of a
+//     512-thread block may hold.  Steps of more than 64 columns (n G > 64) run two blocks per (kv head, slice), so their K/V is read twice, the
+//     second time from L2, where the per-row kernels read it n times;
+//   * one form, the walking one: slice s takes the 256-key chunks s, s + nsl, ...; wave w the 16-key pieces w and w + 8 of a chunk; online softmax
+//     per wave across everything it walks, the waves meet in LDS a column tile at a time, partials [row][nkv][nsl][G][128] + [..][2] as above.
+// Invariance: what a column computes depends on its position and head alone.  Every MFMA output element is a sum over k of its own A row and B
+// column; the chunks, pieces and slices are fixed by the capacity; a piece past the column's limit (walked for a later row's sake) is exp(-inf) = 0
+// times finite V added to O, alpha = 1; a slice past it is skipped by the merge as above.  So the row's place in the step, the number of rows and
+// the tile group it lands in change no bit of its output, which is what makes greedy speculation lossless.
+typedef __attribute__((ext_vector_type(4))) short bf16x4s;
+#define BSH_MAX_TILES 4                  // column tiles (of 16) per block
+struct BSharedArgs {
+    const bf16_t* q; bf16_t* o;                 // [n][ldq], [n][ldo]
+    const bf16_t* kslot; const bf16_t* vslot;   // one layer's slot [nkv][max_ctx][128]
+    const int32_t* pos;                         // device scalar: tokens in the cache = position of row 0
+    float* part_o; float* part_ml;              // [n][nkv][nsl][G][128], [n][nkv][nsl][G][2]
+    int n, nq, nkv, max_ctx, nsl; int64_t ldq, ldo; float scale;
+};
+template <int G, int NT>
+__global__ __launch_bounds__(512) void bdec_attn_shared_kernel(BSharedArgs p) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    float* so = (float*)smem;                   // [8 waves][16 cols][128]
+    float* sml = so + 8 * 16 * 128;             // [8][16][2]
+    char* sq = (char*)(sml + 8 * 16 * 2);       // [NT * 16 cols][256 + 16 B]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int kvh = blockIdx.x, slice = blockIdx.y, col0 = blockIdx.z * (NT * 16);
+    const int ncols = p.n * G;
+    const int pos0 = *p.pos;
+    const int hi = pos0 + p.n - 1 < p.max_ctx - 1 ? pos0 + p.n - 1 : p.max_ctx - 1;      // the last key any row of the step sees
+    const int active = (hi >> 8) + 1;
+    if (slice >= active || hi < 0) return;                      // block-uniform: this slice owns no chunk and writes nothing
+    const bf16_t* kb = p.kslot + (int64_t)kvh * p.max_ctx * 128;
+    const bf16_t* vb = p.vslot + (int64_t)kvh * p.max_ctx * 128;
+    const int l15 = lane & 15, lg = lane >> 4;
+    auto load_k = [&](int k0, u32x4 (&kk)[4]) {                  // scores: A row = key l15, k = 32 ks + 8 lg ..
+        int key = k0 + l15;
+        key = key < hi ? key : hi;
+        const char* kp = (const char*)kb + (unsigned)(key * 256 + lg * 16);
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) kk[ks] = *(const u32x4*)(kp + ks * 64);
+    };
+    auto load_v = [&](int k0, u32x4 (&vv)[4]) {                  // P.V: keys 4 lg + j, d = 8 l15 ..
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int vk = k0 + lg * 4 + j < hi ? k0 + lg * 4 + j : hi;
+            vv[j] = *(const u32x4*)((const char*)vb + (unsigned)(vk * 256 + l15 * 16));
+        }
+    };
+    // step t of the wave: chunk slice + (t >> 1) nsl, piece wave + 8 (t & 1)
+    const int nsteps = 2 * ((active - slice + p.nsl - 1) / p.nsl);
+    auto key0 = [&](int t) { return (slice + (t >> 1) * p.nsl) * 256 + (wave + 8 * (t & 1)) * 16; };
+    u32x4 kc[4], vc[4];
+    load_k(key0(0), kc);
+    load_v(key0(0), vc);
+    for (int i = tid; i < NT * 16 * 16; i += 512) {              // Q of the block's columns; columns past the step are zero
+        const int c = i >> 4, ch = i & 15, col = col0 + c;
+        const int row = col / G, g = col - row * G;
+        const u32x4 v = col < ncols ? *(const u32x4*)(p.q + (int64_t)row * p.ldq + (kvh * G + g) * 128 + ch * 8) : (u32x4){0u, 0u, 0u, 0u};
+        *(u32x4*)(sq + c * 272 + ch * 16) = v;
+    }
+    __syncthreads();
+    int lim[NT];                                                 // the last key the lane's column of tile t sees; -1: no such column
+    float m[NT], l[NT];
+    f32x4 acc[NT][8];                                            // O^T: [e][r] = O[col t*16 + l15][d = 8 (4 lg + r) + e]
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        const int col = col0 + t * 16 + l15, row = col / G;
+        lim[t] = col < ncols ? (pos0 + row < p.max_ctx - 1 ? pos0 + row : p.max_ctx - 1) : -1;
+        m[t] = -INFINITY; l[t] = 0.f;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[t][e] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    }
+    int qoff = l15 * 272 + lg * 16;
+#pragma unroll 1
+    for (int st = 0; st < nsteps; ++st) {
+        asm volatile("" : "+v"(qoff));                           // keeps the Q fragments in LDS
+        const int k0 = key0(st);
+        f32x4 sc[NT];
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            sc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks) {
+                const u32x4 qc = *(const u32x4*)(sq + t * 16 * 272 + qoff + ks * 64);
+                sc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, kc[ks]), __builtin_bit_cast(bf16x8, qc), sc[t], 0, 0, 0);
+            }
+        }
+        load_k(key0(st + 1), kc);                                // (past the last step: the clamp makes it a re-read of key `hi`)
+        // V^T fragments: element e of the lane's 4 keys
+        bf16x4s va[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const int d = e >> 1;
+            unsigned lo, hh;
+            if (e & 1) { lo = (vc[0][d] >> 16) | (vc[1][d] & 0xffff0000u); hh = (vc[2][d] >> 16) | (vc[3][d] & 0xffff0000u); }
+            else { lo = (vc[0][d] & 0xffffu) | (vc[1][d] << 16); hh = (vc[2][d] & 0xffffu) | (vc[3][d] << 16); }
+            va[e] = __builtin_bit_cast(bf16x4s, (unsigned long long)lo | ((unsigned long long)hh << 32));
+        }
+        load_v(key0(st + 1), vc);
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            float pr[4], cm = -INFINITY;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) { pr[r] = (k0 + lg * 4 + r <= lim[t]) ? sc[t][r] * p.scale : -INFINITY; cm = fmaxf(cm, pr[r]); }
+            cm = xor32_max(xor16_max(cm));                       // over the 16 keys of the piece
+            const float m_new = fmaxf(m[t], cm);
+            const bool none = m_new == -INFINITY;                // the column has seen no key of this wave yet
+            const float alpha = none ? 1.f : __expf(m[t] - m_new);
+            float ls = 0.f;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) { pr[r] = none ? 0.f : bfround(__expf(pr[r] - m_new)); ls += pr[r]; }
+            l[t] = fmaf(l[t], alpha, ls);                        // this lane group's 4 keys; the other 12 are added behind the walk
+            m[t] = m_new;
+            const unsigned p01 = (__float_as_uint(pr[0]) >> 16) | (__float_as_uint(pr[1]) & 0xffff0000u);
+            const unsigned p23 = (__float_as_uint(pr[2]) >> 16) | (__float_as_uint(pr[3]) & 0xffff0000u);
+            const bf16x4s pb = __builtin_bit_cast(bf16x4s, (unsigned long long)p01 | ((unsigned long long)p23 << 32));
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                acc[t][e] *= alpha;
+                acc[t][e] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(va[e], pb, acc[t][e], 0, 0, 0);
+            }
+        }
+    }
+    // the 8 waves meet in LDS, one column tile at a time; thread = (column, 4 d)
+    const int mc = tid >> 5, md = (tid & 31) * 4;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        const float lt = bd_xor32_sum(bd_xor16_sum(l[t]));
+        if (lg == 0) { sml[(wave * 16 + l15) * 2] = m[t]; sml[(wave * 16 + l15) * 2 + 1] = lt; }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            float* dst = so + (wave * 16 + l15) * 128 + (lg * 4 + r) * 8;
+            *(f32x4*)dst = (f32x4){acc[t][0][r], acc[t][1][r], acc[t][2][r], acc[t][3][r]};
+            *(f32x4*)(dst + 4) = (f32x4){acc[t][4][r], acc[t][5][r], acc[t][6][r], acc[t][7][r]};
+        }
+        __syncthreads();
+        const int col = col0 + t * 16 + mc;
+        if (col < ncols) {
+            const int row = col / G, g = col - row * G;
+            float M = -INFINITY;
+#pragma unroll
+            for (int w = 0; w < 8; ++w) M = fmaxf(M, sml[(w * 16 + mc) * 2]);
+            float L = 0.f;
+            f32x4 O = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int w = 0; w < 8; ++w) {
+                const float mw = sml[(w * 16 + mc) * 2];
+                const float f = (mw == -INFINITY) ? 0.f : __expf(mw - M);
+                L = fmaf(sml[(w * 16 + mc) * 2 + 1], f, L);
+                const f32x4 ow = *(const f32x4*)(so + (w * 16 + mc) * 128 + md);
+                O[0] = fmaf(ow[0], f, O[0]); O[1] = fmaf(ow[1], f, O[1]); O[2] = fmaf(ow[2], f, O[2]); O[3] = fmaf(ow[3], f, O[3]);
+            }
+            const int64_t pb = ((int64_t)(row * p.nkv + kvh) * p.nsl + slice) * G + g;
+            *(f32x4*)(p.part_o + pb * 128 + md) = O;
+            if (md == 0) { p.part_ml[pb * 2] = M; p.part_ml[pb * 2 + 1] = L; }
+        }
+        __syncthreads();
+    }
+}
+// the slices of a (row, query head) -> the bf16 attention output: bdec_attn_merge_kernel with the row's limit taken from the scalar position
+__global__ __launch_bounds__(128) void bdec_attn_shared_merge_kernel(BSharedArgs p, int G) {
+    const int h = blockIdx.x, row = blockIdx.y, d = threadIdx.x;
+    const int kvh = h / G, g = h % G;
+    const int ps = *p.pos + row, last = ps < p.max_ctx - 1 ? ps : p.max_ctx - 1;
+    if (last < 0) return;
+    const int chunks = (last >> 8) + 1;
+    const int active = chunks < p.nsl ? chunks : p.nsl;
+    const int64_t b0 = (int64_t)(row * p.nkv + kvh) * p.nsl * G;
+    float M = -INFINITY;
+    for (int sl = 0; sl < active; ++sl) M = fmaxf(M, p.part_ml[(b0 + sl * G + g) * 2]);
+    float L = 0.f, O = 0.f;
+    for (int sl = 0; sl < active; ++sl) {
+        const float f = __expf(p.part_ml[(b0 + sl * G + g) * 2] - M);
+        L = fmaf(p.part_ml[(b0 + sl * G + g) * 2 + 1], f, L);
+        O = fmaf(p.part_o[(b0 + sl * G + g) * 128 + d], f, O);
+    }
+    p.o[(int64_t)row * p.ldo + h * 128 + d] = f2bf(O / L);
+}
+template <int G, int NT>
+static int launch_bdec_shared_t(const BSharedArgs& a, int groups, hipStream_t s) {
+    const size_t lds = (size_t)(8 * 16 * 128 + 8 * 16 * 2) * 4 + (size_t)NT * 16 * 272;
+    static bool attr = false;
+    if (!attr) {
+        VILA_HIP(hipFuncSetAttribute((const void*)bdec_attn_shared_kernel<G, NT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        attr = true;
+    }
+    hipLaunchKernelGGL((bdec_attn_shared_kernel<G, NT>), dim3(a.nkv, a.nsl, groups), dim3(512), lds, s, a);
+    VILA_LAUNCH_CHECK();
+    hipLaunchKernelGGL(bdec_attn_shared_merge_kernel, dim3(a.nq, a.n), dim3(128), 0, s, a, G);
+    VILA_LAUNCH_CHECK();
+    return 0;
+}
+// tiles = ceil(n G / 16) <= 8: up to 4 in one block, more in two blocks of ceil(tiles / 2)
+template <int G>
+static int launch_bdec_shared_g(const BSharedArgs& a, hipStream_t s) {
+    const int tiles = cdiv(a.n * G, 16), groups = tiles > BSH_MAX_TILES ? 2 : 1, nt = cdiv(tiles, groups);
+    switch (nt) {
+        case 1: return launch_bdec_shared_t<G, 1>(a, groups, s);
+        case 2: return launch_bdec_shared_t<G, 2>(a, groups, s);
+        case 3: return launch_bdec_shared_t<G, 3>(a, groups, s);
+        default: return launch_bdec_shared_t<G, 4>(a, groups, s);
+    }
+}
+// slices of the verify form at a capacity: the walking form's cap, or what vila_decode_batch_force_slices asks for
+int bverify_attn_slices(int max_ctx) {
+    const int chunks = cdiv(max_ctx, 256);
+    if (g_bdec_force_slices > 0) {
+        const int f = g_bdec_force_slices < BDEC_MAX_SLICES ? g_bdec_force_slices : BDEC_MAX_SLICES;
+        return f < chunks ? f : chunks;
+    }
+    return chunks < BDEC_SLICE_CAP ? chunks : BDEC_SLICE_CAP;
+}
+static int bverify_ws_slices(int max_ctx) { const int chunks = cdiv(max_ctx, 256); return chunks < BDEC_MAX_SLICES ? chunks : BDEC_MAX_SLICES; }
+size_t bverify_attn_workspace_bytes(int n, int nq, int max_ctx) {
+    const size_t sl = (size_t)bverify_ws_slices(max_ctx);
+    return align_up((size_t)n * nq * sl * 128 * 4, 256) + align_up((size_t)n * nq * sl * 2 * 4, 256);
+}
+int bverify_attn_launch(const bf16_t* q, int64_t ldq, const bf16_t* kslot, const bf16_t* vslot, const int32_t* pos, bf16_t* o, int64_t ldo, int n, int nq,
+                        int nkv, int max_ctx, float scale, float* part_o, float* part_ml, hipStream_t s) {
+    BSharedArgs a{};
+    a.q = q; a.o = o; a.kslot = kslot; a.vslot = vslot; a.pos = pos; a.part_o = part_o; a.part_ml = part_ml;
+    a.n = n; a.nq = nq; a.nkv = nkv; a.max_ctx = max_ctx; a.nsl = bverify_attn_slices(max_ctx); a.ldq = ldq; a.ldo = ldo; a.scale = scale;
+    switch (nq / nkv) {
+        case 1: return launch_bdec_shared_g<1>(a, s);
+        case 2: return launch_bdec_shared_g<2>(a, s);
+        case 4: return launch_bdec_shared_g<4>(a, s);
+        case 7: return launch_bdec_shared_g<7>(a, s);
+        case 8: return launch_bdec_shared_g<8>(a, s);
+        default: break;
+    }
+    VILA_REQUIRE(false, "attn_decode_verify: GQA groups of 1, 2, 4, 7 or 8 query heads per kv head (got %d)", nq / nkv);
+    return -1;
+}
+int bverify_attn(const bf16_t* q, int64_t ldq, const bf16_t* kslot, const bf16_t* vslot, const int32_t* pos, bf16_t* o, int64_t ldo, int n, int nq, int nkv,
+                 int max_ctx, float scale, void* workspace, size_t workspace_bytes, hipStream_t s) {
+    VILA_REQUIRE(q && kslot && vslot && pos && o && workspace, "attn_decode_verify: NULL argument");
+    VILA_REQUIRE(n >= 1 && n <= 16 && nkv >= 1 && nq % nkv == 0 && bdec_group_ok(nq / nkv),
+                 "attn_decode_verify: 1..16 rows and a GQA group of 1, 2, 4, 7 or 8 query heads per kv head (got %d rows, %d / %d heads)", n, nq, nkv);
+    VILA_REQUIRE(max_ctx >= 1 && max_ctx <= BDEC_MAX_CTX, "attn_decode_verify: caches of 1..%d positions (got %d)", BDEC_MAX_CTX, max_ctx);
+    VILA_REQUIRE(ldq % 8 == 0 && ldq >= (int64_t)nq * 128 && ldo >= (int64_t)nq * 128 && (uintptr_t)q % 16 == 0 && (uintptr_t)kslot % 16 == 0 &&
+                 (uintptr_t)vslot % 16 == 0, "attn_decode_verify: head_dim 128 rows, 16-byte aligned, a slot of [kv_heads][max_ctx][128]");
+    VILA_REQUIRE(workspace_bytes >= bverify_attn_workspace_bytes(n, nq, max_ctx), "attn_decode_verify: workspace too small");
+    const size_t nsl = (size_t)bverify_attn_slices(max_ctx);
+    float* part_ml = (float*)((char*)workspace + align_up((size_t)n * nq * nsl * 128 * 4, 256));
+    return bverify_attn_launch(q, ldq, kslot, vslot, pos, o, ldo, n, nq, nkv, max_ctx, scale, (float*)workspace, part_ml, s);
+}

@@ -330,51 +330,40 @@ __global__ __launch_bounds__(64) void bdec_pick2_kernel(const float* __restrict_
     }
 }
 
-// ---- the step ---------------------------------------------------------------------------------------------------------------------
-size_t bdecode_workspace_bytes(int H, int F, int QS, int hd, int n, int max_ctx) {
-    size_t b = 0;
-    b += 3 * align_up((size_t)n * H * 2, 256) + 2 * align_up((size_t)n * QS * 2, 256) + align_up((size_t)n * F * 2, 256);
-    b += align_up((size_t)n * hd * 4, 256);
-    b += align_up((size_t)n * (QS / hd) * bdec_ws_slices(max_ctx) * (hd + 2) * 4, 256) + 256 + 2 * align_up((size_t)n * 32 * 4, 256);   // attention slice partials, argmax partials
-    return b + 4096;
-}
-
-int bdecode_step(const BDecodeArgs& m, const BLayer* layers, bf16_t* kcache, bf16_t* vcache, int max_ctx, int n_slots, int n, int32_t* pos, int64_t* token,
-                 int64_t* out_ids, int32_t* n_out, int max_out, float* logits, void* workspace, size_t workspace_bytes, hipStream_t s,
-                 const BLayerW4* qlayers, const BatchSampling* sampling, void* sampling_ws) {
-    const int H = m.hidden, F = m.inter, hd = m.head_dim, QS = m.q_heads * hd, KS = m.kv_heads * hd;
-    VILA_REQUIRE(n >= 1 && n <= 16 && n <= n_slots, "batched decode: %d sequences need 1..16 KV-cache slots (cache has %d)", n, n_slots);
-    VILA_REQUIRE(QS == H, "batched decode: q_heads*head_dim (%d) must equal hidden (%d)", QS, H);
-    VILA_REQUIRE(hd == 128 && max_ctx >= 1 && max_ctx <= BDEC_MAX_CTX, "batched decode: head_dim 128 and caches up to %d positions (got %d, %d)", BDEC_MAX_CTX, hd,
-                 max_ctx);
-    const BAttnForm form = bdec_attn_form(max_ctx);
-    VILA_REQUIRE(!form.walk || (m.q_heads % m.kv_heads == 0 && bdec_group_ok(m.q_heads / m.kv_heads)),
-                 "batched decode: caches beyond 2048 positions need a GQA group of 1, 2, 4, 7 or 8 query heads per kv head (got %d / %d)", m.q_heads, m.kv_heads);
-    VILA_REQUIRE(max_ctx <= BDEC_SHORT_CTX || workspace_bytes >= bdecode_workspace_bytes(H, F, QS, hd, n, max_ctx),
-                 "batched decode: caches beyond 2048 positions need the workspace of vila_llm_decode_batch*_workspace_bytes_ctx (%d positions)", max_ctx);
-    VILA_REQUIRE(qlayers == nullptr || (H % 128 == 0 && F % 128 == 0),
-                 "batched W4 decode: hidden (%d) and intermediate (%d) must be multiples of the 128-wide quantisation group", H, F);
-    VILA_REQUIRE(workspace_bytes >= bdecode_workspace_bytes(H, F, QS, hd, n, max_ctx), "batched decode: workspace too small");
-    VILA_REQUIRE(sampling == nullptr || sampling_ws != nullptr, "batched decode: the sampled pick needs its workspace");
+// ---- what the batched step and the verify step share: the workspace layout and the forward of n rows ------------------------------------
+struct BStepBufs {
+    bf16_t *x, *x2, *xn, *q, *ao, *act; float* rope_cs; float *part_o, *part_ml; float* pick_v; int* pick_i;
+    int32_t* pos_rows;                                       // the verify step's per-row positions
+};
+static bool bdec_carve(void* workspace, size_t workspace_bytes, int n, int H, int F, int QS, int hd, int nq, int nsl, bool pos_rows, BStepBufs* b) {
     char* wp = (char*)workspace; size_t off = 0;
     auto take = [&](size_t bytes) { off = align_up(off, 256); void* r = wp + off; off += bytes; return r; };
-    bf16_t* x = (bf16_t*)take((size_t)n * H * 2);
-    bf16_t* x2 = (bf16_t*)take((size_t)n * H * 2);
-    bf16_t* xn = (bf16_t*)take((size_t)n * H * 2);           // the normalised activations in front of qkv / gate-up / lm_head
+    b->x = (bf16_t*)take((size_t)n * H * 2);
+    b->x2 = (bf16_t*)take((size_t)n * H * 2);
+    b->xn = (bf16_t*)take((size_t)n * H * 2);                // the normalised activations in front of qkv / gate-up / lm_head
+    b->q = (bf16_t*)take((size_t)n * QS * 2);
+    b->ao = (bf16_t*)take((size_t)n * QS * 2);
+    b->act = (bf16_t*)take((size_t)n * F * 2);
+    b->rope_cs = (float*)take((size_t)n * hd * 4);
+    b->part_o = (float*)take((size_t)n * nq * nsl * hd * 4);
+    b->part_ml = (float*)take((size_t)n * nq * nsl * 2 * 4);
+    b->pick_v = (float*)take((size_t)n * PICK_SLICES * 4);
+    b->pick_i = (int*)take((size_t)n * PICK_SLICES * 4);
+    b->pos_rows = pos_rows ? (int32_t*)take((size_t)n * 4) : nullptr;
+    return off <= workspace_bytes;
+}
+// embed + rope table, the layers, lm_head -> logits [n][vocab].  Row i appends its K/V at position pos[i] of kcache/vcache + i * slot_stride (+ the
+// layer); attn(q, kc, vc, ao) enqueues the layer's attention on that layer's cache.
+template <class Attn>
+static int bdec_forward(const BDecodeArgs& m, const BLayer* layers, const BLayerW4* qlayers, bf16_t* kcache, bf16_t* vcache, int64_t per_layer, int64_t slot_stride,
+                        int max_ctx, int n, const int32_t* pos, const int64_t* token, float* logits, const BStepBufs& b, hipStream_t s, Attn&& attn) {
+    const int H = m.hidden, F = m.inter, hd = m.head_dim, QS = m.q_heads * hd, KS = m.kv_heads * hd;
+    bf16_t* x = b.x; bf16_t* x2 = b.x2; bf16_t* xn = b.xn; bf16_t* q = b.q; bf16_t* ao = b.ao; bf16_t* act = b.act; float* rope_cs = b.rope_cs;
     auto normed = [&](BGemmArgs& g, const bf16_t* src, const void* w) -> int {
         VILA_TRY(launch_rmsnorm(src, (const bf16_t*)w, xn, n, H, m.rms_eps, s));
         g.x = xn;
         return 0;
     };
-    bf16_t* q = (bf16_t*)take((size_t)n * QS * 2);
-    bf16_t* ao = (bf16_t*)take((size_t)n * QS * 2);
-    bf16_t* act = (bf16_t*)take((size_t)n * F * 2);
-    float* rope_cs = (float*)take((size_t)n * hd * 4);
-    float* part_o = (float*)take((size_t)n * m.q_heads * form.nsl * hd * 4);
-    float* part_ml = (float*)take((size_t)n * m.q_heads * form.nsl * 2 * 4);
-    float* pick_v = (float*)take((size_t)n * PICK_SLICES * 4);
-    int* pick_i = (int*)take((size_t)n * PICK_SLICES * 4);
-    VILA_REQUIRE(off <= workspace_bytes, "batched decode: workspace layout");
     // the four projections: bf16 skinny GEMMs, or with int4 layers the W4A16 batched GEMV on the same operands and epilogue
     auto proj = [&](const BGemmArgs& g, const void* wq, const void* wsz) -> int {
         if (qlayers == nullptr) return launch_bgemm(g, s);
@@ -387,7 +376,6 @@ int bdecode_step(const BDecodeArgs& m, const BLayer* layers, bf16_t* kcache, bf1
     };
     hipLaunchKernelGGL(bdec_prologue_kernel, dim3(cdiv(H / 8, 256), n), dim3(256), 0, s, (const bf16_t*)m.embed, token, x, H, (int64_t)m.vocab, pos, rope_cs, hd, m.rope_theta);
     VILA_LAUNCH_CHECK();
-    const int64_t per_layer = (int64_t)n_slots * m.kv_heads * max_ctx * hd, slot_stride = (int64_t)m.kv_heads * max_ctx * hd;
     bf16_t* cur = x; bf16_t* nxt = x2;
     for (int l = 0; l < m.n_layers; ++l) {
         const BLayer& L = layers[l];
@@ -399,15 +387,7 @@ int bdecode_step(const BDecodeArgs& m, const BLayer* layers, bf16_t* kcache, bf1
         qa.n = n; qa.N = QS + 2 * KS; qa.K = H; qa.mode = 2; qa.q_out = q; qa.ldq = QS; qa.kcache = kc; qa.vcache = vc; qa.slot_stride = slot_stride;
         qa.pos = pos; qa.rope_cs = rope_cs; qa.nq = m.q_heads; qa.nkv = m.kv_heads; qa.hd = hd; qa.max_ctx = max_ctx;
         VILA_TRY(proj(qa, Q.qkv_q, Q.qkv_sz));
-        const float scale = 1.0f / sqrtf((float)hd);
-        const int rc = bdecode_attn_launch(form, q, QS, kc, vc, slot_stride, pos, ao, QS, n, m.q_heads, m.kv_heads, max_ctx, scale, part_o, part_ml, s);
-        if (rc < 0) return rc;
-        if (rc == 1) {                                                                       // group size without an instantiation: one block per query head
-            AttnDecodeArgs ad{};
-            ad.q = q; ad.kcache = kc; ad.vcache = vc; ad.o = ao; ad.pos_ptr = pos; ad.nq = m.q_heads; ad.nkv = m.kv_heads; ad.hd = hd; ad.max_ctx = max_ctx;
-            ad.n_splits = cdiv(max_ctx, 64); ad.scale = scale;
-            VILA_TRY(launch_attn_decode_rows(ad, n, QS, QS, slot_stride, s));
-        }
+        VILA_TRY(attn(q, kc, vc, ao));
         BGemmArgs o{};
         o.x = ao; o.ldx = QS; o.W = (const bf16_t*)L.wo; o.residual = cur; o.ldr = H; o.y = nxt; o.ldy = H; o.n = n; o.N = H; o.K = QS; o.mode = 0;
         VILA_TRY(proj(o, Q.o_q, Q.o_sz));
@@ -425,12 +405,187 @@ int bdecode_step(const BDecodeArgs& m, const BLayer* layers, bf16_t* kcache, bf1
     lm.ldx = H; lm.W = (const bf16_t*)m.lm_head; lm.y_f32 = logits; lm.ldf = m.vocab;
     lm.n = n; lm.N = m.vocab; lm.K = H; lm.mode = 0;
     VILA_TRY(launch_bgemm(lm, s));
+    return 0;
+}
+
+// ---- the step ---------------------------------------------------------------------------------------------------------------------
+size_t bdecode_workspace_bytes(int H, int F, int QS, int hd, int n, int max_ctx) {
+    size_t b = 0;
+    b += 3 * align_up((size_t)n * H * 2, 256) + 2 * align_up((size_t)n * QS * 2, 256) + align_up((size_t)n * F * 2, 256);
+    b += align_up((size_t)n * hd * 4, 256);
+    b += align_up((size_t)n * (QS / hd) * bdec_ws_slices(max_ctx) * (hd + 2) * 4, 256) + 256 + 2 * align_up((size_t)n * 32 * 4, 256);   // attention slice partials, argmax partials
+    return b + 4096;
+}
+
+int bdecode_step(const BDecodeArgs& m, const BLayer* layers, bf16_t* kcache, bf16_t* vcache, int max_ctx, int n_slots, int n, int32_t* pos, int64_t* token,
+                 int64_t* out_ids, int32_t* n_out, int max_out, float* logits, void* workspace, size_t workspace_bytes, hipStream_t s,
+                 const BLayerW4* qlayers, const BatchSampling* sampling, void* sampling_ws) {
+    const int H = m.hidden, F = m.inter, hd = m.head_dim, QS = m.q_heads * hd;
+    VILA_REQUIRE(n >= 1 && n <= 16 && n <= n_slots, "batched decode: %d sequences need 1..16 KV-cache slots (cache has %d)", n, n_slots);
+    VILA_REQUIRE(QS == H, "batched decode: q_heads*head_dim (%d) must equal hidden (%d)", QS, H);
+    VILA_REQUIRE(hd == 128 && max_ctx >= 1 && max_ctx <= BDEC_MAX_CTX, "batched decode: head_dim 128 and caches up to %d positions (got %d, %d)", BDEC_MAX_CTX, hd,
+                 max_ctx);
+    const BAttnForm form = bdec_attn_form(max_ctx);
+    VILA_REQUIRE(!form.walk || (m.q_heads % m.kv_heads == 0 && bdec_group_ok(m.q_heads / m.kv_heads)),
+                 "batched decode: caches beyond 2048 positions need a GQA group of 1, 2, 4, 7 or 8 query heads per kv head (got %d / %d)", m.q_heads, m.kv_heads);
+    VILA_REQUIRE(max_ctx <= BDEC_SHORT_CTX || workspace_bytes >= bdecode_workspace_bytes(H, F, QS, hd, n, max_ctx),
+                 "batched decode: caches beyond 2048 positions need the workspace of vila_llm_decode_batch*_workspace_bytes_ctx (%d positions)", max_ctx);
+    VILA_REQUIRE(qlayers == nullptr || (H % 128 == 0 && F % 128 == 0),
+                 "batched W4 decode: hidden (%d) and intermediate (%d) must be multiples of the 128-wide quantisation group", H, F);
+    VILA_REQUIRE(workspace_bytes >= bdecode_workspace_bytes(H, F, QS, hd, n, max_ctx), "batched decode: workspace too small");
+    VILA_REQUIRE(sampling == nullptr || sampling_ws != nullptr, "batched decode: the sampled pick needs its workspace");
+    BStepBufs b{};
+    VILA_REQUIRE(bdec_carve(workspace, workspace_bytes, n, H, F, QS, hd, m.q_heads, form.nsl, false, &b), "batched decode: workspace layout");
+    const int64_t per_layer = (int64_t)n_slots * m.kv_heads * max_ctx * hd, slot_stride = (int64_t)m.kv_heads * max_ctx * hd;
+    const float scale = 1.0f / sqrtf((float)hd);
+    auto attn = [&](const bf16_t* q, bf16_t* kc, bf16_t* vc, bf16_t* ao) -> int {
+        const int rc = bdecode_attn_launch(form, q, QS, kc, vc, slot_stride, pos, ao, QS, n, m.q_heads, m.kv_heads, max_ctx, scale, b.part_o, b.part_ml, s);
+        if (rc < 0) return rc;
+        if (rc == 1) {                                                                       // group size without an instantiation: one block per query head
+            AttnDecodeArgs ad{};
+            ad.q = q; ad.kcache = kc; ad.vcache = vc; ad.o = ao; ad.pos_ptr = pos; ad.nq = m.q_heads; ad.nkv = m.kv_heads; ad.hd = hd; ad.max_ctx = max_ctx;
+            ad.n_splits = cdiv(max_ctx, 64); ad.scale = scale;
+            VILA_TRY(launch_attn_decode_rows(ad, n, QS, QS, slot_stride, s));
+        }
+        return 0;
+    };
+    VILA_TRY(bdec_forward(m, layers, qlayers, kcache, vcache, per_layer, slot_stride, max_ctx, n, pos, token, logits, b, s, attn));
+    float* pick_v = b.pick_v; int* pick_i = b.pick_i;
     // the pick: per-row sampling (sample.hip; greedy rows included, position = the draw's counter, read before it advances) or the greedy pair
     if (sampling != nullptr)
         return launch_sample_batch(logits, m.vocab, n, m.vocab, *sampling, pos, token, sampling_ws, nullptr, pos, out_ids, n_out, max_out, s);
     hipLaunchKernelGGL(bdec_pick1_kernel, dim3(PICK_SLICES, n), dim3(256), 0, s, logits, m.vocab, pick_v, pick_i);
     VILA_LAUNCH_CHECK();
     hipLaunchKernelGGL(bdec_pick2_kernel, dim3(n), dim3(64), 0, s, pick_v, pick_i, token, pos, out_ids, n_out, max_out);
+    VILA_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- the verify step: greedy speculative decoding with lookup drafts -------------------------------------------------------------------
+// One sequence, one slot.  token[0] is the last chosen token (not yet in the cache), token[1..n_draft] are guesses at what follows it.  The n rows run
+// as consecutive positions pos .. pos + n - 1 of the slot (slot_stride 0: row i's K/V lands at position pos + i), so row i's logits are the model's
+// answer to "what follows token[0..i]", and the guesses are accepted as far as the answers reproduce them.  Every accepted token is the greedy
+// token of its position, computed by the same arithmetic whatever the drafts were (attn_decode.hip, the shared form's invariance), so the ids are
+// those of drafting nothing.  Rows beyond 1 + n_draft are padding: they compute (the graph is fixed) and write K/V past the accepted length,
+// which a later step overwrites before any column may see it.
+// The draft: HF PromptLookupCandidateGenerator on hist[0 : n_hist] (the ids so far, token[0] last) — for ngram = min(max_ngram, n_hist - 1) .. 1 the
+// EARLIEST window equal to the last ngram ids that has something behind it, and up to n - 1 ids from there; or, in candidate mode (cand != NULL and
+// *n_cand >= 0), cand[n_out + j]: the candidate's guess for the very output index the row decides, so a rejection re-aligns by itself.
+// Also writes the rows' positions for the forward.  One block.
+__global__ __launch_bounds__(1024) void bver_draft_kernel(const int64_t* __restrict__ hist, const int32_t* __restrict__ n_hist_p, int max_ngram,
+                                                          const int64_t* __restrict__ cand, const int32_t* __restrict__ n_cand_p,
+                                                          const int32_t* __restrict__ n_out_p, int n, int64_t* __restrict__ token, int32_t* __restrict__ n_draft,
+                                                          const int32_t* __restrict__ pos, int32_t* __restrict__ pos_rows) {
+    __shared__ int best;
+    const int tid = threadIdx.x;
+    if (pos_rows != nullptr && tid < n) pos_rows[tid] = *pos + tid;
+    const int64_t pad = token[0];
+    int nd = 0, src = 0;
+    const int64_t* from = hist;
+    const int nc = (cand != nullptr && n_cand_p != nullptr) ? *n_cand_p : -1;
+    if (nc >= 0) {
+        const int o = n_out_p != nullptr ? *n_out_p : 0;
+        nd = nc - o < n - 1 ? nc - o : n - 1;
+        nd = nd < 0 ? 0 : nd;
+        src = o; from = cand;
+    } else {
+        const int nh = *n_hist_p;
+        for (int ng = (max_ngram < nh - 1 ? max_ngram : nh - 1); ng >= 1 && nd == 0; --ng) {
+            __syncthreads();
+            if (tid == 0) best = 0x7fffffff;
+            __syncthreads();
+            // windows s .. s + ng - 1 with s + ng < nh: the tail itself (s = nh - ng) has nothing behind it
+            for (int s0 = tid; s0 + ng < nh; s0 += 1024) {
+                bool eq = true;
+                for (int j = 0; j < ng && eq; ++j) eq = hist[s0 + j] == hist[nh - ng + j];
+                if (eq) { atomicMin(&best, s0); break; }         // a thread's windows ascend: its first match is its earliest
+            }
+            __syncthreads();
+            if (best != 0x7fffffff) { src = best + ng; nd = nh - src < n - 1 ? nh - src : n - 1; }
+        }
+    }
+    // (token[0] was read by every thread before the barrier-free stores below can matter: they touch token[1..] only)
+    if (tid >= 1 && tid < n) token[tid] = tid <= nd ? from[src + tid - 1] : pad;
+    if (tid == 0) *n_draft = nd;
+}
+int launch_verify_draft(const int64_t* hist, const int32_t* n_hist, int max_ngram, const int64_t* cand, const int32_t* n_cand, const int32_t* n_out, int n,
+                        int64_t* token, int32_t* n_draft, const int32_t* pos, int32_t* pos_rows, hipStream_t s) {
+    VILA_REQUIRE(n >= 1 && n <= 16 && token != nullptr && n_draft != nullptr && (cand != nullptr || (hist != nullptr && n_hist != nullptr)) && max_ngram >= 1 &&
+                 (pos_rows == nullptr || pos != nullptr), "verify draft: 1..16 rows, a history or a candidate, max_ngram >= 1");
+    hipLaunchKernelGGL(bver_draft_kernel, dim3(1), dim3(1024), 0, s, hist, n_hist, max_ngram, cand, n_cand, n_out, n, token, n_draft, pos, pos_rows);
+    VILA_LAUNCH_CHECK();
+    return 0;
+}
+// The accept: wave i finishes row i's greedy pick a[i] (bdec_pick1_kernel's partials); m = the longest prefix of drafts with a[j] == token[j + 1];
+// a[0..m] go to out_ids and hist, the state moves m + 1 tokens and a[m] is the next token[0].  One block of n waves.
+__global__ __launch_bounds__(1024) void bver_accept_kernel(const float* __restrict__ pv, const int* __restrict__ pi, int n, int64_t* __restrict__ token,
+                                                           const int32_t* __restrict__ n_draft, int32_t* __restrict__ pos, int64_t* __restrict__ out_ids,
+                                                           int32_t* __restrict__ n_out, int max_out, int64_t* __restrict__ hist, int32_t* __restrict__ n_hist,
+                                                           int hist_cap, int32_t* __restrict__ n_accept) {
+    __shared__ int a[16];
+    const int row = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    float best = lane < PICK_SLICES ? pv[row * PICK_SLICES + lane] : -INFINITY;
+    int bi = lane < PICK_SLICES ? pi[row * PICK_SLICES + lane] : 0x7fffffff;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float v2 = __shfl_xor(best, o, 64); const int i2 = __shfl_xor(bi, o, 64);
+        if (v2 > best || (v2 == best && i2 < bi)) { best = v2; bi = i2; }
+    }
+    if (lane == 0) a[row] = bi;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int nd = *n_draft;
+        nd = nd < 0 ? 0 : (nd > n - 1 ? n - 1 : nd);
+        int m = 0;
+        while (m < nd && (int64_t)a[m] == token[m + 1]) ++m;
+        const int no = *n_out, nh = hist != nullptr ? *n_hist : 0;
+        for (int j = 0; j <= m; ++j) {
+            if (no + j < max_out) out_ids[no + j] = (int64_t)a[j];
+            if (hist != nullptr && nh + j < hist_cap) hist[nh + j] = (int64_t)a[j];
+        }
+        *n_out = no + m + 1;
+        if (hist != nullptr) *n_hist = nh + m + 1 < hist_cap ? nh + m + 1 : hist_cap;      // (a full history stops growing: later drafts are poorer, never wrong)
+        *pos = *pos + m + 1;
+        token[0] = (int64_t)a[m];
+        *n_accept = m;
+    }
+}
+size_t bverify_workspace_bytes(int H, int F, int QS, int hd, int n, int max_ctx) {
+    size_t b = 0;
+    b += 3 * align_up((size_t)n * H * 2, 256) + 2 * align_up((size_t)n * QS * 2, 256) + align_up((size_t)n * F * 2, 256);
+    b += align_up((size_t)n * hd * 4, 256);
+    b += bverify_attn_workspace_bytes(n, QS / hd, max_ctx) + 2 * align_up((size_t)n * PICK_SLICES * 4, 256) + align_up((size_t)n * 4, 256);
+    return b + 4096;
+}
+int bverify_step(const BDecodeArgs& m, const BLayer* layers, bf16_t* kcache, bf16_t* vcache, int max_ctx, int n_slots, const BVerifyState& st, void* workspace,
+                 size_t workspace_bytes, hipStream_t s, const BLayerW4* qlayers) {
+    const int H = m.hidden, F = m.inter, hd = m.head_dim, QS = m.q_heads * hd, n = st.n;
+    VILA_REQUIRE(n >= 2 && n <= 16, "verify step: 2..16 rows per step (1 committed token + up to 15 drafts), got %d", n);
+    VILA_REQUIRE(st.slot >= 0 && st.slot < n_slots, "verify step: slot %d of a cache with %d", st.slot, n_slots);
+    VILA_REQUIRE(hd == 128 && QS == H && m.q_heads % m.kv_heads == 0 && bdec_group_ok(m.q_heads / m.kv_heads) && max_ctx >= 1 && max_ctx <= BDEC_MAX_CTX,
+                 "verify step: head_dim 128 (got %d), q_heads*head_dim == hidden (%d, %d), a GQA group of 1, 2, 4, 7 or 8 query heads per kv head (got %d / %d) "
+                 "and caches up to %d positions (got %d)", hd, QS, H, m.q_heads, m.kv_heads, BDEC_MAX_CTX, max_ctx);
+    VILA_REQUIRE(qlayers == nullptr || (H % 128 == 0 && F % 128 == 0),
+                 "verify step (W4): hidden (%d) and intermediate (%d) must be multiples of the 128-wide quantisation group", H, F);
+    VILA_REQUIRE(st.pos && st.token && st.n_draft && st.out_ids && st.n_out && st.logits && st.n_accept && st.max_out >= 1, "verify step: a NULL state member");
+    VILA_REQUIRE(st.cand != nullptr || (st.hist != nullptr && st.n_hist != nullptr && st.hist_cap >= 1), "verify step: neither a history nor a candidate");
+    VILA_REQUIRE(st.max_ngram >= 1, "verify step: max_ngram >= 1 (got %d)", st.max_ngram);
+    VILA_REQUIRE(workspace_bytes >= bverify_workspace_bytes(H, F, QS, hd, n, max_ctx), "verify step: workspace too small");
+    const int nsl = bverify_attn_slices(max_ctx);
+    BStepBufs b{};
+    VILA_REQUIRE(bdec_carve(workspace, workspace_bytes, n, H, F, QS, hd, m.q_heads, nsl, true, &b), "verify step: workspace layout");
+    VILA_TRY(launch_verify_draft(st.hist, st.n_hist, st.max_ngram, st.cand, st.n_cand, st.n_out, n, st.token, st.n_draft, st.pos, b.pos_rows, s));
+    const int64_t slot_elems = (int64_t)m.kv_heads * max_ctx * hd, per_layer = (int64_t)n_slots * slot_elems;
+    const float scale = 1.0f / sqrtf((float)hd);
+    auto attn = [&](const bf16_t* q, bf16_t* kc, bf16_t* vc, bf16_t* ao) -> int {
+        return bverify_attn_launch(q, QS, kc, vc, st.pos, ao, QS, n, m.q_heads, m.kv_heads, max_ctx, scale, b.part_o, b.part_ml, s);
+    };
+    VILA_TRY(bdec_forward(m, layers, qlayers, kcache + st.slot * slot_elems, vcache + st.slot * slot_elems, per_layer, 0, max_ctx, n, b.pos_rows, st.token,
+                          st.logits, b, s, attn));
+    hipLaunchKernelGGL(bdec_pick1_kernel, dim3(PICK_SLICES, n), dim3(256), 0, s, st.logits, m.vocab, b.pick_v, b.pick_i);
+    VILA_LAUNCH_CHECK();
+    hipLaunchKernelGGL(bver_accept_kernel, dim3(1), dim3(64 * n), 0, s, b.pick_v, b.pick_i, n, st.token, st.n_draft, st.pos, st.out_ids, st.n_out, st.max_out,
+                       st.hist, st.n_hist, st.hist_cap, st.n_accept);
     VILA_LAUNCH_CHECK();
     return 0;
 }

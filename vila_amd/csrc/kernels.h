@@ -176,6 +176,26 @@ int bdecode_attn(const bf16_t* q, int64_t ldq, const bf16_t* kcache, const bf16_
 int bdecode_step(const BDecodeArgs& m, const BLayer* layers, bf16_t* kcache, bf16_t* vcache, int max_ctx, int n_slots, int n, int32_t* pos, int64_t* token,
                  int64_t* out_ids, int32_t* n_out, int max_out, float* logits, void* workspace, size_t workspace_bytes, hipStream_t s,
                  const BLayerW4* qlayers = nullptr, const BatchSampling* sampling = nullptr, void* sampling_ws = nullptr);
+// the verify step (greedy speculative decoding): n rows = n consecutive positions of ONE sequence in ONE slot.  Its attention (attn_decode.hip
+// bdec_attn_shared_kernel) reads the slot's K/V once for all rows; `pos` is the device scalar of the state, row i sees keys 0 .. min(pos + i, max_ctx - 1)
+int bverify_attn_slices(int max_ctx);
+size_t bverify_attn_workspace_bytes(int n, int nq, int max_ctx);
+int bverify_attn_launch(const bf16_t* q, int64_t ldq, const bf16_t* kslot, const bf16_t* vslot, const int32_t* pos, bf16_t* o, int64_t ldo, int n, int nq,
+                        int nkv, int max_ctx, float scale, float* part_o, float* part_ml, hipStream_t s);
+int bverify_attn(const bf16_t* q, int64_t ldq, const bf16_t* kslot, const bf16_t* vslot, const int32_t* pos, bf16_t* o, int64_t ldo, int n, int nq, int nkv,
+                 int max_ctx, float scale, void* workspace, size_t workspace_bytes, hipStream_t s);
+// the device state of a verify session (include/vila_hip.h VilaDecodeVerify) and the step: draft -> forward of n rows -> accept
+struct BVerifyState {
+    int n, slot;
+    int32_t* pos; int64_t* token; int32_t* n_draft; int64_t* out_ids; int32_t* n_out; int max_out; float* logits; int32_t* n_accept;
+    int64_t* hist; int32_t* n_hist; int hist_cap, max_ngram;
+    const int64_t* cand; const int32_t* n_cand;
+};
+size_t bverify_workspace_bytes(int H, int F, int QS, int hd, int n, int max_ctx);
+int bverify_step(const BDecodeArgs& m, const BLayer* layers, bf16_t* kcache, bf16_t* vcache, int max_ctx, int n_slots, const BVerifyState& st, void* workspace,
+                 size_t workspace_bytes, hipStream_t s, const BLayerW4* qlayers = nullptr);
+int launch_verify_draft(const int64_t* hist, const int32_t* n_hist, int max_ngram, const int64_t* cand, const int32_t* n_cand, const int32_t* n_out, int n,
+                        int64_t* token, int32_t* n_draft, const int32_t* pos, int32_t* pos_rows, hipStream_t s);
 int launch_decode_prologue(const bf16_t* table, const int64_t* tok, bf16_t* out, int H, int64_t vocab, const int32_t* pos, float* rope_cs,
                            int hd, float theta, hipStream_t s);
 int launch_decode_advance(int32_t* pos, const int64_t* tok, int64_t* out_ids, int32_t* n_out, int max_out, hipStream_t s);

@@ -260,3 +260,18 @@ def expand2square(pil_img, background_color):
     result = Image.new(pil_img.mode, (side, side), background_color)
     result.paste(pil_img, (0, (width - height) // 2) if width > height else ((height - width) // 2, 0))
     return result
+
+
+def prompt_lookup_draft(ids, k: int, max_ngram: int = 2) -> List[int]:
+    """Draft tokens by n-gram lookup in the ids seen so far, as HF `PromptLookupCandidateGenerator.get_candidates` picks them
+    (`generate(prompt_lookup_num_tokens=k, max_matching_ngram_size=max_ngram)`): for ngram sizes min(max_ngram, len(ids) - 1) down to 1, the
+    EARLIEST window of `ids` equal to its last `ngram` ids whose continuation is not empty; up to k ids that follow it, cut at the end of `ids`.
+    [] when nothing matches.  The host reference of the verify step's draft kernel."""
+    ids = [int(t) for t in (ids.tolist() if hasattr(ids, "tolist") else ids)]
+    n = len(ids)
+    for ngram in range(min(int(max_ngram), n - 1), 0, -1):
+        tail = ids[n - ngram:]
+        for s in range(n - ngram):                      # s + ngram < n: the tail itself has nothing behind it
+            if ids[s:s + ngram] == tail:
+                return ids[s + ngram:min(s + ngram + int(k), n)]
+    return []

@@ -57,6 +57,7 @@ class _HipModule(nn.Module):
 
     _decode = None              # the LLM's batch-1 and batched decode sessions (`_decode_session`, `_batch_session`)
     _bdecode = None
+    _vdecode = None             # the LLM's verify session (`_verify_session`: greedy speculative decoding)
     _bf16_released = False      # quantize_w4(release_bf16=True) freed the bf16 projection weights
 
     def _build_params(self, specs, prefix: str, device, dtype, requires_grad=False):
@@ -102,6 +103,7 @@ class _HipModule(nn.Module):
         self._cstruct = None
         self._drop_decode_session()
         self._drop_batch_session()
+        self._drop_session("_vdecode")
 
     def refuse(self) -> None:
         """Re-establish the fused q/k/v storage after an op that re-allocated parameters (.to(), .half(), ...)."""
@@ -878,7 +880,9 @@ class HipQwen2ForCausalLM(_HipModule):
                  eos_token_id=None, do_sample: Optional[bool] = None, temperature: Optional[float] = None, top_k: Optional[int] = None,
                  top_p: Optional[float] = None, seed: Optional[int] = None, pad_token_id: Optional[int] = None, generation_config=None,
                  use_graph: bool = True, return_logits: bool = False, forced_ids: Optional[torch.Tensor] = None, cache=None,
-                 max_length: Optional[int] = None, streamer=None, batch_sample: Optional[bool] = None, **kw):
+                 max_length: Optional[int] = None, streamer=None, batch_sample: Optional[bool] = None,
+                 prompt_lookup_num_tokens: Optional[int] = None, max_matching_ngram_size: Optional[int] = None,
+                 prompt_ids: Optional[torch.Tensor] = None, draft_ids: Optional[torch.Tensor] = None, **kw):
         """`llm.generate(inputs_embeds=, attention_mask=, **generation_kwargs)` as called at llava_arch.py:833 (HF semantics: returns ONLY the
         new tokens, [B, n_new]).  Greedy search or sampling (do_sample: temperature / top_k / top_p, HF order, on the device); explicit
         keyword arguments override `generation_config` (HF GenerationConfig-like: do_sample, temperature, top_k, top_p, max_new_tokens,
@@ -889,6 +893,12 @@ class HipQwen2ForCausalLM(_HipModule):
         runs the batched step with its per-row sampler — one weight pass per step for all rows, row b seeded `seed + b` as the row-by-row loop
         seeds it.  The batched step sums in another order than the solo step, so the ids are no longer those of the rows' solo runs.
         forced_ids = teacher forcing for margin-aware parity tests.
+        prompt_lookup_num_tokens=k (HF's name, also read from generation_config; 1..15; default None = off): greedy speculative decoding.  One
+        graph replay runs the last token and up to k drafted ones as k + 1 positions of the sequence (`vila_llm_decode_step_verify`) and keeps the
+        longest run the model itself would have chosen, so the ids are those of the same session drafting nothing.  Drafts come from an n-gram
+        lookup (sizes max_matching_ngram_size, default 2, down to 1) in `prompt_ids` (LongTensor, optional) followed by what has been generated;
+        draft_ids (LongTensor: a predicted output, token for token) replaces the lookup, with k = 7 unless given.  Batch 1 and greedy only;
+        forced_ids and return_logits are not served in this mode.
         streamer = HF's `generate(streamer=...)` contract (what server.py:243 streams from): `put(LongTensor[1])` once per new token — the EOS
         included, nothing for a prompt given as embeddings — as the host learns of them (every 16 graph replays), then `end()`; batch size 1."""
         if streamer is not None and inputs_embeds.shape[0] > 1:
@@ -901,6 +911,21 @@ class HipQwen2ForCausalLM(_HipModule):
         eos_token_id = pick(eos_token_id, "eos_token_id", None)
         pad_token_id = pick(pad_token_id, "pad_token_id", None)
         batch_sample = bool(pick(batch_sample, "batch_sample", False))
+        k_spec = pick(prompt_lookup_num_tokens, "prompt_lookup_num_tokens", None)
+        if k_spec is not None or draft_ids is not None:
+            k_spec = 7 if k_spec is None else int(k_spec)
+            if do_sample:
+                raise ValueError("prompt_lookup_num_tokens / draft_ids: speculative decoding here is greedy; do_sample=True is not supported with it")
+            if inputs_embeds.shape[0] != 1:
+                raise ValueError("prompt_lookup_num_tokens / draft_ids: speculative decoding serves batch size 1 (as HF's assisted generation does)")
+            if not 1 <= k_spec <= 15:
+                raise ValueError(f"prompt_lookup_num_tokens has to be in 1..15 (a step runs k + 1 <= 16 rows), but is {k_spec}")
+            max_ngram = int(pick(max_matching_ngram_size, "max_matching_ngram_size", 2))
+            if max_ngram < 1:
+                raise ValueError(f"max_matching_ngram_size has to be a positive integer, but is {max_ngram}")
+            if forced_ids is not None or return_logits:
+                raise ValueError("prompt_lookup_num_tokens / draft_ids: forced_ids and return_logits are not supported in this mode")
+            return self._generate_verify(inputs_embeds, attention_mask, max_new_tokens, eos_token_id, k_spec, max_ngram, prompt_ids, draft_ids, cache, streamer)
         if do_sample and temperature <= 0:
             raise ValueError(f"`temperature` (={temperature}) has to be a strictly positive float, otherwise your next token scores will be invalid.")
         if do_sample and top_k < 0:
@@ -1009,3 +1034,131 @@ class HipQwen2ForCausalLM(_HipModule):
             streamer.end()
         out = out[None]
         return (out, torch.stack(step_logits)) if return_logits else out
+
+    # ---- greedy speculative decoding: lookup drafts, k + 1 rows of one sequence per step (vila_llm_decode_step_verify) --------------------
+    spec_trace = None           # diagnostics / tests: set to a list and _generate_verify syncs after every replay and appends its n_accept
+
+    def _verify_refusal(self) -> Optional[str]:
+        """Why this model has no verify step, or None.  The restrictions are the batched step's."""
+        c = self.lcfg
+        if c.head_dim != 128 or c.num_attention_heads * c.head_dim != c.hidden_size or not self._long_batch_group_ok():
+            return ("the verify step needs head_dim 128, q_heads * head_dim == hidden and a GQA group of 1, 2, 4, 7 or 8 query heads per kv head "
+                    f"(got head_dim {c.head_dim}, {c.num_attention_heads} / {c.num_key_value_heads} heads, hidden {c.hidden_size})")
+        if self._w4 is not None and not self._w4_batched():
+            return "a quantised model needs quantize_w4(batch_decode=True) for the verify step (it runs the W4A16 batched GEMVs)"
+        if self._w4 is None and not self._qkv_fused():
+            return "the verify step reads q/k/v as one fused [q + 2kv, hidden] buffer (refuse() re-establishes it)"
+        return None
+
+    def _verify_session(self, cache, n: int, max_out: int, max_ngram: int):
+        """Device-resident state of a verify session (+ its captured hipGraph), keyed like `_decode_session`."""
+        w4 = self._w4_batched()
+        q4 = self._w4.mats[0]["down"].q.data_ptr() if w4 else None
+        key = (cache.k.data_ptr(), cache.max_ctx, n, max_out, max_ngram, self.model.embed_tokens.weight.data_ptr(),
+               _get(self, "model.layers.0.mlp.down_proj.weight").data_ptr(), q4)
+        if self._vdecode is not None and self._vdecode.key == key:
+            return self._vdecode
+        self._drop_session("_vdecode")
+        dev, lib, w = self.device, _lib.load(), self._struct()
+        st = SimpleNamespace(key=key, cache=cache, graph=None, n=n, max_out=max_out, w4=w4)
+        i32 = lambda m: torch.zeros(m, device=dev, dtype=torch.int32)
+        with torch.inference_mode(False):
+            st.pos, st.n_draft, st.n_out, st.n_accept, st.n_hist, st.n_cand = i32(1), i32(1), i32(1), i32(1), i32(1), i32(1)
+            st.token = torch.zeros(n, device=dev, dtype=torch.int64)
+            st.out_ids = torch.zeros(max_out, device=dev, dtype=torch.int64)
+            st.cand = torch.zeros(max_out, device=dev, dtype=torch.int64)
+            st.hist = torch.zeros(cache.max_ctx + max_out + 1, device=dev, dtype=torch.int64)
+            st.logits = torch.zeros((n, self.lcfg.vocab_size), device=dev, dtype=torch.float32)
+            st.ws = torch.empty((lib.vila_llm_decode_verify_workspace_bytes(C.byref(w.shape), n, cache.max_ctx),), device=dev, dtype=torch.uint8)
+        st.c = _lib.VilaDecodeVerify(n, 0, st.pos.data_ptr(), st.token.data_ptr(), st.n_draft.data_ptr(), st.out_ids.data_ptr(), st.n_out.data_ptr(), max_out,
+                                     st.logits.data_ptr(), st.n_accept.data_ptr(), st.hist.data_ptr(), st.n_hist.data_ptr(), st.hist.numel(), max_ngram,
+                                     st.cand.data_ptr(), st.n_cand.data_ptr())
+        st.stream = torch.cuda.Stream(device=dev)
+        self._vdecode = st
+        return st
+
+    def verify_step(self, cache, st) -> None:
+        """One verify step on the current stream: draft, forward of st.n rows, accept."""
+        lib = _lib.load()
+        if st.w4:
+            check(lib.vila_llm_decode_step_verify_w4(C.byref(self._struct()), self._w4.ptr, C.byref(cache.c), C.byref(st.c), st.ws.data_ptr(), st.ws.numel(),
+                                                     ops._stream()), "vila_llm_decode_step_verify_w4")
+        else:
+            self._require_bf16("the bf16 verify step")
+            check(lib.vila_llm_decode_step_verify(C.byref(self._struct()), C.byref(cache.c), C.byref(st.c), st.ws.data_ptr(), st.ws.numel(), ops._stream()),
+                  "vila_llm_decode_step_verify")
+
+    def _generate_verify(self, inputs_embeds, attention_mask, max_new_tokens, eos_token_id, k, max_ngram, prompt_ids, draft_ids, cache, streamer):
+        """generate() for one greedy sequence with the verify step: prefill as `_generate_solo`, first token from the prefill, then graph replays
+        that each append 1 .. k + 1 tokens.  The host cuts at EOS and at max_new_tokens (a step may overshoot by up to k)."""
+        why = self._verify_refusal()
+        if why is not None:
+            raise ValueError("prompt_lookup_num_tokens / draft_ids: " + why)
+        ops._need(inputs_embeds, dtype=None, name="inputs_embeds")
+        x = inputs_embeds[0]
+        if attention_mask is not None:
+            x = x[attention_mask[0].bool()]
+        S, dev, n = x.shape[0], x.device, k + 1
+        eos_set = _eos_set(eos_token_id, self.lcfg.eos_token_id)
+        if cache is None:
+            cache = self._own_cache
+            if cache is None or cache.max_ctx < S + max_new_tokens:
+                cache = self._own_cache = self.new_cache(((S + max_new_tokens + 255) // 256) * 256)
+        if cache.max_ctx < S + max_new_tokens:
+            raise ValueError(f"KV cache too small: {cache.max_ctx} < {S} + {max_new_tokens}")
+        if cache.max_ctx > self.BATCH_MAX_CTX:
+            raise ValueError(f"prompt_lookup_num_tokens / draft_ids: the verify step serves caches up to {self.BATCH_MAX_CTX} positions (got {cache.max_ctx})")
+        pos = torch.arange(S, device=dev, dtype=torch.int32)
+        last = torch.full((1,), S - 1, device=dev, dtype=torch.int32)
+        r = self.prefill_packed(x.to(self.dtype), pos, None, S, cache=cache, last_rows=last)
+        first = ops.argmax(r.last_logits[0])
+        need = max_new_tokens - 1                                   # tokens wanted from the steps
+        st = self._verify_session(cache, n, max(max_new_tokens, 1) + k, max_ngram)
+        # the history the lookup starts from: the prompt's ids (its tail, if longer than the room) and the first token
+        room = st.hist.numel() - st.max_out - 1
+        pids = torch.zeros(0, dtype=torch.int64, device=dev) if prompt_ids is None else prompt_ids.reshape(-1).to(device=dev, dtype=torch.int64)[-room:]
+        n0 = pids.numel() + 1
+        st.hist[:n0 - 1].copy_(pids)
+        st.hist[n0 - 1:n0].copy_(first)
+        if draft_ids is not None:                                   # a predicted output: its token t is the draft for output token t (t = 0 is `first`)
+            cand = draft_ids.reshape(-1).to(device=dev, dtype=torch.int64)[1:st.max_out + 1]
+            st.cand[:cand.numel()].copy_(cand)
+            st.n_cand.fill_(cand.numel())
+        else:
+            st.n_cand.fill_(-1)
+
+        def restore():
+            st.pos.fill_(S); st.n_out.zero_(); st.n_hist.fill_(n0); st.token[:1].copy_(first)
+        restore()
+        if st.graph is None:
+            _capture(st, lambda: self.verify_step(cache, st), restore)
+        lib = _lib.load()
+        torch.cuda.current_stream().synchronize()
+        first_id = first.item()
+        stop = first_id in eos_set
+        if streamer is not None:
+            streamer.put(torch.tensor([first_id], dtype=torch.int64))
+        got: List[int] = []
+        trace = self.spec_trace
+        with torch.cuda.stream(st.stream):
+            while len(got) < need and not stop:
+                # every replay appends at least one token: never more replays than tokens still wanted, at most 16 between two looks at the ids
+                chunk = 1 if trace is not None else max(1, min(16, (need - len(got) + n - 1) // n))
+                for _ in range(chunk):
+                    check(lib.vila_graph_launch(st.graph, st.stream.cuda_stream), "graph_launch")
+                n_out = min(int(st.n_out.item()), need, st.max_out)  # (the sync)
+                if trace is not None:
+                    trace.append(int(st.n_accept.item()))
+                new = st.out_ids[len(got):n_out].tolist()
+                for t in new:
+                    got.append(t)
+                    if streamer is not None:
+                        streamer.put(torch.tensor([t], dtype=torch.int64))
+                    if t in eos_set:
+                        stop = True
+                        break
+        st.stream.synchronize()
+        out = torch.tensor(_cut_at_eos([first_id] + got, eos_set)[:max(max_new_tokens, 1)], dtype=torch.int64, device=dev)
+        if streamer is not None:
+            streamer.end()
+        return out[None]

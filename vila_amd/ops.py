@@ -281,6 +281,43 @@ def attn_decode_batch(q: torch.Tensor, kcache: torch.Tensor, vcache: torch.Tenso
     return o
 
 
+def attn_decode_verify(q: torch.Tensor, kslot: torch.Tensor, vslot: torch.Tensor, pos: torch.Tensor, scale: Optional[float] = None) -> torch.Tensor:
+    """The verify step's attention on its own: q [n, q_heads, 128] bf16 (rows may be strided), n in 1..16 consecutive positions of ONE sequence;
+    kslot / vslot one layer's slot [kv_heads, max_ctx, 128] bf16 (contiguous); pos a device int32 scalar — row i attends keys
+    0 .. min(pos + i, max_ctx - 1), and the slot's K/V is read once for all rows.  GQA groups of 1, 2, 4, 7 or 8; the slice count follows
+    `vila_decode_batch_force_slices`.  -> o [n, q_heads, 128]."""
+    _need(q, name="q"); _need(kslot, name="kslot"); _need(vslot, name="vslot"); _need(pos, dtype=torch.int32, name="pos")
+    if q.dim() != 3 or q.shape[2] != 128 or q.stride(2) != 1 or q.stride(1) != 128:
+        raise ValueError("attn_decode_verify: q must be [n, q_heads, 128] with contiguous heads")
+    n, nq, _ = q.shape
+    if kslot.dim() != 3 or kslot.shape != vslot.shape or kslot.shape[2] != 128 or not kslot.is_contiguous() or not vslot.is_contiguous():
+        raise ValueError("attn_decode_verify: kslot / vslot must be contiguous [kv_heads, max_ctx, 128] of one shape")
+    nkv, max_ctx, _ = kslot.shape
+    if pos.numel() != 1:
+        raise ValueError("attn_decode_verify: pos is one device scalar, the position of row 0")
+    lib = _lib.load()
+    o = torch.empty((n, nq, 128), device=q.device, dtype=torch.bfloat16)
+    ws = torch.empty((lib.vila_attn_decode_verify_workspace_bytes(n, nq, max_ctx),), device=q.device, dtype=torch.uint8)
+    check(lib.vila_attn_decode_verify_bf16(q.data_ptr(), q.stride(0), kslot.data_ptr(), vslot.data_ptr(), pos.data_ptr(), o.data_ptr(), o.stride(0), n, nq, nkv,
+                                           max_ctx, float(scale if scale is not None else 128 ** -0.5), ws.data_ptr(), ws.numel(), _stream()),
+          "attn_decode_verify")
+    return o
+
+
+def prompt_lookup_draft(hist: torch.Tensor, n_hist: int, k: int, max_ngram: int = 2) -> list:
+    """The verify step's draft stage on its own: hist int64 on the device, the first n_hist ids are the history -> up to k draft ids (a list),
+    what `host.prompt_lookup_draft(hist[:n_hist], k, max_ngram)` returns."""
+    _need(hist, dtype=torch.int64, name="hist")
+    if not 1 <= k <= 15 or not 1 <= n_hist <= hist.numel() or max_ngram < 1:
+        raise ValueError("prompt_lookup_draft: k in 1..15, 1 <= n_hist <= len(hist), max_ngram >= 1")
+    nh = torch.full((1,), int(n_hist), device=hist.device, dtype=torch.int32)
+    token = torch.full((k + 1,), -1, device=hist.device, dtype=torch.int64)
+    nd = torch.zeros(1, device=hist.device, dtype=torch.int32)
+    check(_lib.load().vila_prompt_lookup_draft(hist.data_ptr(), nh.data_ptr(), int(max_ngram), k + 1, token.data_ptr(), nd.data_ptr(), _stream()),
+          "prompt_lookup_draft")
+    return token[1:1 + int(nd.item())].tolist()
+
+
 def embed_tokens(table: torch.Tensor, ids: torch.Tensor) -> torch.Tensor:
     _need(table, name="embed table")
     ids = ids.to(device=table.device, dtype=torch.int64).contiguous()

@@ -390,9 +390,11 @@ def _eos_of(tokenizer, eos_token_id=None):
 
 def generate_content(model, tokenizer, prompt: Union[str, Sequence[Any]], max_new_tokens: int = 128, system: Optional[str] = None,
                      eos_token_id=None, device: Optional[str] = None, temperature: float = 0.0, top_p: float = 1.0, top_k: int = 50,
-                     seed: Optional[int] = None, streamer=None) -> str:
+                     seed: Optional[int] = None, streamer=None, prompt_lookup_num_tokens: Optional[int] = None) -> str:
     """Text + images in, decoded reply out — the contract of `LlavaLlamaModel.generate_content` for image / text prompts.
     temperature > 0 samples (server.py:185-187: do_sample = temperature > 0, with the request's top_p and HF's default top_k = 50).
+    prompt_lookup_num_tokens=k (greedy requests only, ignored for a sampled one): speculative decoding with k lookup drafts per step
+    (`llm.generate(prompt_lookup_num_tokens=)`); the reply is the greedy reply.
     streamer: a `TextStream` (or any HF streamer) that receives the new tokens while they are generated (`llm.generate(streamer=...)`)."""
     cfg = model.cfg
     dev = device or str(model.device)
@@ -403,6 +405,8 @@ def generate_content(model, tokenizer, prompt: Union[str, Sequence[Any]], max_ne
     gen = dict(max_new_tokens=max_new_tokens, eos_token_id=eos)
     if temperature and temperature > 0:
         gen.update(do_sample=True, temperature=float(temperature), top_p=float(top_p), top_k=int(top_k), seed=seed)
+    elif prompt_lookup_num_tokens is not None:
+        gen.update(prompt_lookup_num_tokens=int(prompt_lookup_num_tokens))
     if streamer is not None:
         gen.update(streamer=streamer)
     out = model.generate(input_ids=ids, media=media, media_config=media_config, **gen)
@@ -860,7 +864,8 @@ def continuous_batching(model) -> bool:
 
 
 def create_app(model, tokenizer, model_name: str = "NVILA-8B", batch_window_s: Optional[float] = None, max_batch: int = 8,
-               stream_timeout_s: Optional[float] = 600.0, batch_sampled: bool = False, max_ctx: int = 2048):
+               stream_timeout_s: Optional[float] = 600.0, batch_sampled: bool = False, max_ctx: int = 2048,
+               prompt_lookup_num_tokens: Optional[int] = None):
     """FastAPI app with the reference's POST /chat/completions (server.py:171-290).  Import-time optional: needs fastapi + pydantic.
     batch_window_s: when set (any value), requests go through a batcher whose ONE worker thread owns the model: `ContinuousBatcher` (greedy
     requests join / leave the batched decode step between steps; sampled ones run solo on the same thread) where the model has the batched
@@ -869,7 +874,9 @@ def create_app(model, tokenizer, model_name: str = "NVILA-8B", batch_window_s: O
     the batched step as rows instead of running solo.  The trade: the ids of a sampled request are no longer those of its solo run (the
     batched step sums in another order); greedy requests are served exactly as before.
     max_ctx (ContinuousBatcher only): positions per KV slot of the batched session, up to 32768.  The default 2048 keeps the KV memory as it was;
-    a larger value lets long prompts (dynamic_s2's 2304 image tokens, video, multi-image chats) take a row instead of running solo."""
+    a larger value lets long prompts (dynamic_s2's 2304 image tokens, video, multi-image chats) take a row instead of running solo.
+    prompt_lookup_num_tokens=k: greedy requests that this app runs solo (not through a batcher) decode speculatively with k lookup drafts per
+    step; their replies are the greedy replies.  None (default): every request takes the path it always took."""
     from fastapi import FastAPI
     from fastapi.responses import JSONResponse, StreamingResponse
 
@@ -923,7 +930,8 @@ def create_app(model, tokenizer, model_name: str = "NVILA-8B", batch_window_s: O
         """A request the batcher does not take: under the model lock — never beside the worker thread's batch, never beside another solo
         request."""
         with model_lock, torch.inference_mode():
-            return generate_content(model, tokenizer, parts, max_new_tokens=n, system=system, temperature=temperature, top_p=top_p, streamer=streamer)
+            kw = {} if prompt_lookup_num_tokens is None else dict(prompt_lookup_num_tokens=prompt_lookup_num_tokens)
+            return generate_content(model, tokenizer, parts, max_new_tokens=n, system=system, temperature=temperature, top_p=top_p, streamer=streamer, **kw)
 
     async def chat_completions(request):
         import asyncio

@@ -304,6 +304,11 @@ class HipLlavaLlamaModel(nn.Module):
         inputs_embeds, _, attention_mask = self._embed(input_ids, media, media_config, None, attention_mask)
         if getattr(attention_mask, "_vila_all_true", False):
             attention_mask = None                      # nothing is padded: the LLM need not compact rows (a device round trip) before the prefill
+        gc = generation_kwargs.get("generation_config")
+        if (generation_kwargs.get("prompt_lookup_num_tokens", getattr(gc, "prompt_lookup_num_tokens", None)) is not None
+                and generation_kwargs.get("prompt_ids") is None and input_ids is not None and input_ids.shape[0] == 1):
+            # lookup drafts start from the prompt's ids; media placeholders stay in as ids that no generated token equals
+            generation_kwargs["prompt_ids"] = input_ids[0] if attention_mask is None else input_ids[0][attention_mask[0].bool()]
         return self.llm.generate(inputs_embeds=inputs_embeds, attention_mask=attention_mask, **generation_kwargs)
 
 
