@@ -1,12 +1,14 @@
-"""Host logic of the decode drivers in vila_amd/modules.py: the step table, the row finisher, the pad rule and the order of a graph capture."""
+"""Host logic of the decode drivers in vila_amd/modules.py: the step table, the row finisher, the pad rule, the order of a graph capture, the
+choice of a one-sequence generate()'s KV cache and the replay loop."""
 import contextlib
 import itertools
 from types import SimpleNamespace
 
+import pytest
 import torch
 
 from vila_amd import _lib, modules
-from vila_amd.modules import _capture, _eos_set, _pad_id, _step_symbols, finish_rows
+from vila_amd.modules import HipQwen2ForCausalLM, _capture, _eos_set, _pad_id, _replay, _step_symbols, finish_rows
 
 
 def test_step_table_names_exist_in_the_abi():
@@ -27,6 +29,59 @@ def test_step_table_names_exist_in_the_abi():
             assert ws == "vila_llm_decode_workspace_bytes"
         steps.add(step)
     assert len(steps) == 8
+    for w4 in (False, True):
+        step, ws = _step_symbols(True, w4, False, verify=True)
+        assert step == "vila_llm_decode_step_verify" + ("_w4" if w4 else "") and ws == "vila_llm_decode_verify_workspace_bytes"
+        assert step in _lib.PROTOTYPES and ws in _lib.PROTOTYPES
+        assert len(_lib.PROTOTYPES[step][1]) == 6 + int(w4), step
+        assert _step_symbols(False, w4, False, verify=True) == (step, ws)          # one sequence's rows: `batch` is not read
+        with pytest.raises(ValueError, match="verify step is greedy"):
+            _step_symbols(True, w4, True, verify=True)
+        steps.add(step)
+    assert len(steps) == 10
+
+
+def test_cache_for_keeps_grows_and_refuses():
+    made = []
+    llm = SimpleNamespace(_own_cache=None)
+    llm.new_cache = lambda max_ctx: made.append(max_ctx) or SimpleNamespace(max_ctx=max_ctx)
+    cache_for = lambda *a: HipQwen2ForCausalLM._cache_for(llm, *a)
+    c = cache_for(20, 6, None)
+    assert made == [256] and c.max_ctx == 256 and llm._own_cache is c
+    assert cache_for(100, 156, None) is c and made == [256]          # fits exactly: reused
+    c2 = cache_for(250, 10, None)
+    assert made == [256, 512] and c2.max_ctx == 512 and llm._own_cache is c2
+    assert cache_for(20, 6, None) is c2 and made == [256, 512]       # a larger cache is kept, never shrunk
+    mine = SimpleNamespace(max_ctx=24)
+    with pytest.raises(ValueError, match=r"KV cache too small: 24 < 20 \+ 6"):
+        cache_for(20, 6, mine)
+    assert cache_for(20, 4, mine) is mine and llm._own_cache is c2 and made == [256, 512]
+
+
+def test_replay_launches_k_times_and_raises_through_check(monkeypatch):
+    calls = []
+
+    class Lib:
+        rc = 0
+
+        def vila_graph_launch(self, graph, stream):
+            calls.append((graph, stream))
+            return self.rc
+
+        def vila_last_error(self):
+            return b"launch refused"
+
+    lib = Lib()
+    monkeypatch.setattr(modules._lib, "load", lambda *a, **k: lib)
+    st = SimpleNamespace(graph="the graph", stream=SimpleNamespace(cuda_stream=1234))
+    _replay(st, 3)
+    assert calls == [("the graph", 1234)] * 3
+    _replay(st, 0)
+    assert len(calls) == 3
+    lib.rc = 1
+    with pytest.raises(_lib.VilaHipError, match="graph_launch: launch refused"):
+        _replay(st, 3)
+    assert len(calls) == 4, "the first failure ends the loop"
 
 
 def test_finish_rows_cuts_after_the_first_eos_and_right_pads():

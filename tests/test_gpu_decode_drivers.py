@@ -70,3 +70,21 @@ def test_batch_graph_equals_eager(w4, sampled):
     assert llm._bdecode.graph is not None
     assert eager.shape == (len(lens), N_NEW)
     assert torch.equal(graph, eager), (graph.tolist(), eager.tolist())
+
+
+@pytest.mark.parametrize("w4", [False, True])
+def test_verify_graph_is_captured_once_and_replays_the_same_ids(w4):
+    llm = _llm(w4)
+    e, _ = _prompts(llm, [20], 13)
+    ids = torch.randint(0, 900, (1, 20), generator=torch.Generator().manual_seed(13))        # the ids `_prompts` embedded
+    kw = dict(inputs_embeds=e, max_new_tokens=N_NEW, eos_token_id=-1, prompt_lookup_num_tokens=3)
+    llm._drop_session("_vdecode")
+    first = llm.generate(prompt_ids=ids, **kw)                       # captures: the warm-up step advances the state, `restore` puts it back
+    st, graph = llm._vdecode, llm._vdecode.graph
+    assert graph is not None and first.shape == (1, N_NEW)
+    second = llm.generate(prompt_ids=ids, **kw)
+    assert torch.equal(second, first), (second.tolist(), first.tolist())
+    assert llm._vdecode is st and st.graph is graph
+    third = llm.generate(prompt_ids=ids, draft_ids=first, **kw)      # candidate mode: n_cand is a device scalar, so the same graph serves it
+    assert torch.equal(third, first), (third.tolist(), first.tolist())
+    assert llm._vdecode is st and st.graph is graph

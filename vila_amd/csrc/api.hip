@@ -694,42 +694,49 @@ extern "C" size_t vila_llm_decode_batch_sample_workspace_bytes_ctx(const VilaLlm
 extern "C" size_t vila_llm_decode_batch_w4_workspace_bytes_ctx(const VilaLlmShape* s, int n, int max_ctx) { return decode_batch_ws_ctx(s, n, max_ctx, false); }
 extern "C" size_t vila_llm_decode_batch_w4_sample_workspace_bytes_ctx(const VilaLlmShape* s, int n, int max_ctx) { return decode_batch_ws_ctx(s, n, max_ctx, true); }
 
+// What the batched step and the verify step read of the model: the layer tables (ql stays empty without int4 layers) and the model arguments, with the
+// fused q/k/v (bf16) or contiguous-bias and int4-buffer (W4) requirements per layer.  fn names the entry point in the messages.
+struct BTables { std::vector<BLayer> layers; std::vector<BLayerW4> ql; BDecodeArgs m; };
+static int blayer_tables(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers, const char* fn, BTables* t) {
+    const bool w4 = qlayers != nullptr;
+    const VilaLlmShape& sh = w->shape;
+    const int QS = sh.q_heads * sh.head_dim, KS = sh.kv_heads * sh.head_dim;
+    t->layers.resize(sh.n_layers);
+    t->ql.resize(w4 ? sh.n_layers : 0);
+    for (int l = 0; l < sh.n_layers; ++l) {
+        const VilaLlmLayer& L = w->layers[l];
+        if (w4) {
+            const VilaLlmLayerW4& Q = qlayers[l];
+            VILA_REQUIRE(L.bq != nullptr && B(L.bk) == B(L.bq) + QS && B(L.bv) == B(L.bk) + KS,
+                         "%s: the q/k/v biases must be one contiguous q|k|v vector (layer %d)", fn, l);
+            VILA_REQUIRE(Q.qkv_q && Q.qkv_sz && Q.o_q && Q.o_sz && Q.gateup_q && Q.gateup_sz && Q.down_q && Q.down_sz,
+                         "%s: int4 layer %d has a NULL buffer", fn, l);
+            t->layers[l] = BLayer{L.ln1_w, nullptr, L.bq, nullptr, L.ln2_w, nullptr, nullptr, nullptr};
+            t->ql[l] = BLayerW4{Q.qkv_q, Q.qkv_sz, Q.o_q, Q.o_sz, Q.gateup_q, Q.gateup_sz, Q.down_q, Q.down_sz};
+        } else {
+            VILA_REQUIRE(qkv_fused(L.wq, L.wk, L.wv, L.bq, L.bk, L.bv, QS, KS, sh.hidden),
+                         "%s: q/k/v projection weights and biases must be views of one fused [q+2kv, hidden] buffer", fn);
+            t->layers[l] = BLayer{L.ln1_w, L.wq, L.bq, L.wo, L.ln2_w, L.w_gate, L.w_up, L.w_down};
+        }
+    }
+    t->m = BDecodeArgs{w->embed, w->norm_w, w->lm_head, sh.hidden, sh.inter, sh.n_layers, sh.q_heads, sh.kv_heads, sh.head_dim, sh.vocab, sh.rms_eps, sh.rope_theta};
+    return 0;
+}
 // The batched step: qlayers == nullptr runs the bf16 projections; otherwise the four projections of every layer are read from the int4 layers
 // (gemv_w4_batch.hip) and embed, norms, the fused q|k|v biases and the bf16 lm_head come from `w`, whose projection pointers are not read (empty
 // after quantize_w4(release_bf16=True)).  sp != nullptr: a per-row pick (sample.hip's batched sampler) instead of the greedy pair; everything
 // before the pick is the same launches.
 static int decode_step_batch_impl(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers, const VilaKvCache* cache, const VilaDecodeBatch* st,
                                   void* workspace, size_t workspace_bytes, const VilaBatchSampling* sp, vila_stream_t stream) {
-    const bool w4 = qlayers != nullptr;
-    const char* fn = w4 ? "llm_decode_batch_w4" : "llm_decode_batch";
+    const char* fn = qlayers != nullptr ? "llm_decode_batch_w4" : "llm_decode_batch";
     VILA_REQUIRE(w != nullptr && cache != nullptr && st != nullptr && workspace != nullptr, "%s: NULL argument", fn);
-    const VilaLlmShape& sh = w->shape;
-    hipStream_t s = S(stream);
-    const int QS = sh.q_heads * sh.head_dim, KS = sh.kv_heads * sh.head_dim;
-    std::vector<BLayer> layers(sh.n_layers);
-    std::vector<BLayerW4> ql(w4 ? sh.n_layers : 0);
-    for (int l = 0; l < sh.n_layers; ++l) {
-        const VilaLlmLayer& L = w->layers[l];
-        if (w4) {
-            const VilaLlmLayerW4& Q = qlayers[l];
-            VILA_REQUIRE(L.bq != nullptr && B(L.bk) == B(L.bq) + QS && B(L.bv) == B(L.bk) + KS,
-                         "llm_decode_batch_w4: the q/k/v biases must be one contiguous q|k|v vector (layer %d)", l);
-            VILA_REQUIRE(Q.qkv_q && Q.qkv_sz && Q.o_q && Q.o_sz && Q.gateup_q && Q.gateup_sz && Q.down_q && Q.down_sz,
-                         "llm_decode_batch_w4: int4 layer %d has a NULL buffer", l);
-            layers[l] = BLayer{L.ln1_w, nullptr, L.bq, nullptr, L.ln2_w, nullptr, nullptr, nullptr};
-            ql[l] = BLayerW4{Q.qkv_q, Q.qkv_sz, Q.o_q, Q.o_sz, Q.gateup_q, Q.gateup_sz, Q.down_q, Q.down_sz};
-        } else {
-            VILA_REQUIRE(qkv_fused(L.wq, L.wk, L.wv, L.bq, L.bk, L.bv, QS, KS, sh.hidden),
-                         "llm_decode_batch: q/k/v projection weights and biases must be views of one fused [q+2kv, hidden] buffer");
-            layers[l] = BLayer{L.ln1_w, L.wq, L.bq, L.wo, L.ln2_w, L.w_gate, L.w_up, L.w_down};
-        }
-    }
-    BDecodeArgs m{w->embed, w->norm_w, w->lm_head, sh.hidden, sh.inter, sh.n_layers, sh.q_heads, sh.kv_heads, sh.head_dim, sh.vocab, sh.rms_eps, sh.rope_theta};
+    BTables t{};
+    VILA_TRY(blayer_tables(w, qlayers, fn, &t));
     BatchSampling bs{};
     BatchSamplingWs sw{};
-    VILA_TRY(batch_sampling_of(sp, &sh, st->n, cache->max_ctx, workspace, &workspace_bytes, &bs, &sw));
-    return bdecode_step(m, layers.data(), B(cache->k), B(cache->v), cache->max_ctx, cache->n_slots, st->n, st->pos, st->token, st->out_ids, st->n_out,
-                        st->max_out, st->logits, workspace, workspace_bytes, s, w4 ? ql.data() : nullptr, sw.sp, sw.ws);
+    VILA_TRY(batch_sampling_of(sp, &w->shape, st->n, cache->max_ctx, workspace, &workspace_bytes, &bs, &sw));
+    return bdecode_step(t.m, t.layers.data(), B(cache->k), B(cache->v), cache->max_ctx, cache->n_slots, st->n, st->pos, st->token, st->out_ids, st->n_out,
+                        st->max_out, st->logits, workspace, workspace_bytes, S(stream), qlayers != nullptr ? t.ql.data() : nullptr, sw.sp, sw.ws);
 }
 extern "C" int vila_llm_decode_step_batch(const VilaLlmWeights* w, const VilaKvCache* cache, const VilaDecodeBatch* st,
                                           void* workspace, size_t workspace_bytes, vila_stream_t stream) {
@@ -754,34 +761,14 @@ extern "C" int vila_llm_decode_step_batch_w4_sample(const VilaLlmWeights* w, con
 // The verify step (greedy speculative decoding, decode_batch.hip bverify_step): the layer tables are the batched step's, the state is one sequence's.
 static int decode_step_verify_impl(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers, const VilaKvCache* cache, const VilaDecodeVerify* st,
                                    void* workspace, size_t workspace_bytes, vila_stream_t stream) {
-    const bool w4 = qlayers != nullptr;
-    const char* fn = w4 ? "llm_decode_verify_w4" : "llm_decode_verify";
+    const char* fn = qlayers != nullptr ? "llm_decode_verify_w4" : "llm_decode_verify";
     VILA_REQUIRE(w != nullptr && cache != nullptr && st != nullptr && workspace != nullptr, "%s: NULL argument", fn);
-    const VilaLlmShape& sh = w->shape;
-    const int QS = sh.q_heads * sh.head_dim, KS = sh.kv_heads * sh.head_dim;
-    std::vector<BLayer> layers(sh.n_layers);
-    std::vector<BLayerW4> ql(w4 ? sh.n_layers : 0);
-    for (int l = 0; l < sh.n_layers; ++l) {
-        const VilaLlmLayer& L = w->layers[l];
-        if (w4) {
-            const VilaLlmLayerW4& Q = qlayers[l];
-            VILA_REQUIRE(L.bq != nullptr && B(L.bk) == B(L.bq) + QS && B(L.bv) == B(L.bk) + KS,
-                         "llm_decode_verify_w4: the q/k/v biases must be one contiguous q|k|v vector (layer %d)", l);
-            VILA_REQUIRE(Q.qkv_q && Q.qkv_sz && Q.o_q && Q.o_sz && Q.gateup_q && Q.gateup_sz && Q.down_q && Q.down_sz,
-                         "llm_decode_verify_w4: int4 layer %d has a NULL buffer", l);
-            layers[l] = BLayer{L.ln1_w, nullptr, L.bq, nullptr, L.ln2_w, nullptr, nullptr, nullptr};
-            ql[l] = BLayerW4{Q.qkv_q, Q.qkv_sz, Q.o_q, Q.o_sz, Q.gateup_q, Q.gateup_sz, Q.down_q, Q.down_sz};
-        } else {
-            VILA_REQUIRE(qkv_fused(L.wq, L.wk, L.wv, L.bq, L.bk, L.bv, QS, KS, sh.hidden),
-                         "llm_decode_verify: q/k/v projection weights and biases must be views of one fused [q+2kv, hidden] buffer");
-            layers[l] = BLayer{L.ln1_w, L.wq, L.bq, L.wo, L.ln2_w, L.w_gate, L.w_up, L.w_down};
-        }
-    }
-    BDecodeArgs m{w->embed, w->norm_w, w->lm_head, sh.hidden, sh.inter, sh.n_layers, sh.q_heads, sh.kv_heads, sh.head_dim, sh.vocab, sh.rms_eps, sh.rope_theta};
+    BTables t{};
+    VILA_TRY(blayer_tables(w, qlayers, fn, &t));
     BVerifyState v{st->n, st->slot, st->pos, st->token, st->n_draft, st->out_ids, st->n_out, st->max_out, st->logits, st->n_accept,
                    st->hist, st->n_hist, st->hist_cap, st->max_ngram, st->cand, st->n_cand};
-    return bverify_step(m, layers.data(), B(cache->k), B(cache->v), cache->max_ctx, cache->n_slots, v, workspace, workspace_bytes, S(stream),
-                        w4 ? ql.data() : nullptr);
+    return bverify_step(t.m, t.layers.data(), B(cache->k), B(cache->v), cache->max_ctx, cache->n_slots, v, workspace, workspace_bytes, S(stream),
+                        qlayers != nullptr ? t.ql.data() : nullptr);
 }
 extern "C" size_t vila_llm_decode_verify_workspace_bytes(const VilaLlmShape* s, int n, int max_ctx) {
     return bverify_workspace_bytes(s->hidden, s->inter, s->q_heads * s->head_dim, s->head_dim, n, max_ctx);

@@ -335,6 +335,10 @@ struct BStepBufs {
     bf16_t *x, *x2, *xn, *q, *ao, *act; float* rope_cs; float *part_o, *part_ml; float* pick_v; int* pick_i;
     int32_t* pos_rows;                                       // the verify step's per-row positions
 };
+// The size functions below bound this layout: bdec_step_common_bytes counts every take() but the attention partials and pos_rows at its aligned size,
+// and each step adds its own term for those.  The partials are two separately aligned arrays (part_o, part_ml) where the batched step's term is one
+// aligned sum plus 256: align(a) + align(b) <= align(a + b) + 256, since rounding two parts up can overshoot rounding their sum by less than one
+// more unit.  The verify step's term is bverify_attn_workspace_bytes, the two aligned arrays themselves.  The 4096 on top is slack.
 static bool bdec_carve(void* workspace, size_t workspace_bytes, int n, int H, int F, int QS, int hd, int nq, int nsl, bool pos_rows, BStepBufs* b) {
     char* wp = (char*)workspace; size_t off = 0;
     auto take = [&](size_t bytes) { off = align_up(off, 256); void* r = wp + off; off += bytes; return r; };
@@ -409,12 +413,13 @@ static int bdec_forward(const BDecodeArgs& m, const BLayer* layers, const BLayer
 }
 
 // ---- the step ---------------------------------------------------------------------------------------------------------------------
+// what both steps carve whatever their attention: the six activation buffers, the RoPE table, the two pick-partials arrays, and the slack
+static size_t bdec_step_common_bytes(int H, int F, int QS, int hd, int n) {
+    return 3 * align_up((size_t)n * H * 2, 256) + 2 * align_up((size_t)n * QS * 2, 256) + align_up((size_t)n * F * 2, 256) +
+           align_up((size_t)n * hd * 4, 256) + 2 * align_up((size_t)n * PICK_SLICES * 4, 256) + 4096;
+}
 size_t bdecode_workspace_bytes(int H, int F, int QS, int hd, int n, int max_ctx) {
-    size_t b = 0;
-    b += 3 * align_up((size_t)n * H * 2, 256) + 2 * align_up((size_t)n * QS * 2, 256) + align_up((size_t)n * F * 2, 256);
-    b += align_up((size_t)n * hd * 4, 256);
-    b += align_up((size_t)n * (QS / hd) * bdec_ws_slices(max_ctx) * (hd + 2) * 4, 256) + 256 + 2 * align_up((size_t)n * 32 * 4, 256);   // attention slice partials, argmax partials
-    return b + 4096;
+    return bdec_step_common_bytes(H, F, QS, hd, n) + align_up((size_t)n * (QS / hd) * bdec_ws_slices(max_ctx) * (hd + 2) * 4, 256) + 256;   // + attention slice partials
 }
 
 int bdecode_step(const BDecodeArgs& m, const BLayer* layers, bf16_t* kcache, bf16_t* vcache, int max_ctx, int n_slots, int n, int32_t* pos, int64_t* token,
@@ -551,11 +556,7 @@ __global__ __launch_bounds__(1024) void bver_accept_kernel(const float* __restri
     }
 }
 size_t bverify_workspace_bytes(int H, int F, int QS, int hd, int n, int max_ctx) {
-    size_t b = 0;
-    b += 3 * align_up((size_t)n * H * 2, 256) + 2 * align_up((size_t)n * QS * 2, 256) + align_up((size_t)n * F * 2, 256);
-    b += align_up((size_t)n * hd * 4, 256);
-    b += bverify_attn_workspace_bytes(n, QS / hd, max_ctx) + 2 * align_up((size_t)n * PICK_SLICES * 4, 256) + align_up((size_t)n * 4, 256);
-    return b + 4096;
+    return bdec_step_common_bytes(H, F, QS, hd, n) + bverify_attn_workspace_bytes(n, QS / hd, max_ctx) + align_up((size_t)n * 4, 256);   // + partials, pos_rows
 }
 int bverify_step(const BDecodeArgs& m, const BLayer* layers, bf16_t* kcache, bf16_t* vcache, int max_ctx, int n_slots, const BVerifyState& st, void* workspace,
                  size_t workspace_bytes, hipStream_t s, const BLayerW4* qlayers) {

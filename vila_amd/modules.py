@@ -296,9 +296,13 @@ def _as_i64(u: int) -> int:
     return u - (1 << 64) if u >= (1 << 63) else u
 
 
-def _step_symbols(batch: bool, w4: bool, sampled: bool) -> Tuple[str, str]:
-    """(step, workspace query) of one decode step variant, composed the way the C ABI names them."""
+def _step_symbols(batch: bool, w4: bool, sampled: bool, verify: bool = False) -> Tuple[str, str]:
+    """(step, workspace query) of one decode step variant, composed the way the C ABI names them.  verify: the greedy verify step, whatever `batch`."""
+    if verify and sampled:
+        raise ValueError("the verify step is greedy: it has no sampled variant")
     tail = ("_w4" if w4 else "") + ("_sample" if sampled else "")
+    if verify:
+        return "vila_llm_decode_step_verify" + tail, "vila_llm_decode_verify_workspace_bytes"
     if batch:
         return "vila_llm_decode_step_batch" + tail, "vila_llm_decode_batch" + tail + "_workspace_bytes_ctx"
     return "vila_llm_decode_step" + tail, "vila_llm_decode_workspace_bytes"
@@ -319,6 +323,19 @@ def _capture(st, step, restore) -> None:
         check(lib.vila_graph_end(st.stream.cuda_stream, C.byref(g)), "graph_end")
         st.graph = g
         st.stream.synchronize()
+
+
+def _replay(st, k: int) -> None:
+    """k launches of st.graph on st.stream.  The caller has made st.stream current and does its own syncs."""
+    lib = _lib.load()
+    for _ in range(int(k)):
+        check(lib.vila_graph_launch(st.graph, st.stream.cuda_stream), "graph_launch")
+
+
+def _stream_put(streamer, t: int) -> None:
+    """One new token to an HF streamer (`put(LongTensor[1])`), if there is one."""
+    if streamer is not None:
+        streamer.put(torch.tensor([t], dtype=torch.int64))
 
 
 def _eos_set(eos_token_id, default=None) -> set:
@@ -500,14 +517,18 @@ class HipQwen2ForCausalLM(_HipModule):
         return CausalLMOutput(loss=loss, logits=logits, past_key_values=None)
 
     # ---- greedy generate ---------------------------------------------------------------------------------------
+    def _weights_key(self) -> tuple:
+        """The weight storage a captured graph bakes in: embedding, layer 0's down_proj, the batched int4 down buffer (a re-quantise moves it) or None."""
+        q4 = self._w4.mats[0]["down"].q.data_ptr() if self._w4_batched() else None
+        return self.model.embed_tokens.weight.data_ptr(), _get(self, "model.layers.0.mlp.down_proj.weight").data_ptr(), q4
+
     def _decode_session(self, cache, max_new_tokens: int, sampling=None):
         """Device-resident decode state + workspace (+ captured hipGraph) reused across generate() calls.
         sampling: None (greedy) or (temperature, top_k, top_p, seed) — baked into the captured graph, hence part of the key."""
         # the seed is NOT part of the key: it lives in a device scalar the sampler reads (VilaSampling.seed_dev), so every sampled request
         # with the same (temperature, top_k, top_p) replays the same captured graph (ADVICE round 2: a fresh seed per call used to drop
         # the graph, the workspace and the weight struct on every sampled request)
-        key = (cache.k.data_ptr(), max_new_tokens, self.model.embed_tokens.weight.data_ptr(),
-               _get(self, "model.layers.0.mlp.down_proj.weight").data_ptr(), None if sampling is None else tuple(sampling[:3]))
+        key = (cache.k.data_ptr(), max_new_tokens, *self._weights_key()[:2], None if sampling is None else tuple(sampling[:3]))   # (no int4 pointer: as ever)
         if self._decode is not None and self._decode.key == key:
             if sampling is not None:
                 self._decode.seed.fill_(_as_i64(sampling[3]))
@@ -598,10 +619,10 @@ class HipQwen2ForCausalLM(_HipModule):
             raise RuntimeError(f"{what}: the bf16 projection weights were freed by quantize_w4(release_bf16=True); only the W4A16 "
                                "prefill and decode can run on this model")
 
-    def _step(self, batch: bool, w4, cache, st, sp) -> None:
+    def _step(self, batch: bool, w4, cache, st, sp, verify: bool = False) -> None:
         """One decode step on the current stream.  The variant is looked up at call time (`_step_symbols`): a caller may hold a session
         across quantize_w4.  w4: the W4Weights whose int4 layers the step reads, or None; sp: the sampling struct, or None for the greedy pick."""
-        name, _ = _step_symbols(batch, w4 is not None, sp is not None)
+        name, _ = _step_symbols(batch, w4 is not None, sp is not None, verify)
         args = [C.byref(self._struct())] + ([w4.ptr] if w4 is not None else []) + [C.byref(cache.c), C.byref(st.c), st.ws.data_ptr(), st.ws.numel()]
         check(getattr(_lib.load(), name)(*args, *([C.byref(sp)] if sp is not None else []), ops._stream()), name)
 
@@ -660,10 +681,7 @@ class HipQwen2ForCausalLM(_HipModule):
         w4 = self._w4_batched()
         if not w4:
             self._require_bf16("the batched decode")
-        # a W4 session's graph bakes the int4 buffers' pointers: a re-quantise must not replay it
-        q4 = self._w4.mats[0]["down"].q.data_ptr() if w4 else None
-        key = (n, max_ctx, max_new_tokens, bool(sampling), self.model.embed_tokens.weight.data_ptr(),
-               _get(self, "model.layers.0.mlp.down_proj.weight").data_ptr(), q4)
+        key = (n, max_ctx, max_new_tokens, bool(sampling), *self._weights_key())
         if self._bdecode is not None and self._bdecode.key == key:
             return self._bdecode
         self._drop_session("_bdecode")
@@ -775,11 +793,9 @@ class HipQwen2ForCausalLM(_HipModule):
         return tok
 
     def batch_run(self, st, k: int) -> None:
-        lib = _lib.load()
         torch.cuda.current_stream().synchronize()
         with torch.cuda.stream(st.stream):
-            for _ in range(int(k)):
-                check(lib.vila_graph_launch(st.graph, st.stream.cuda_stream), "graph_launch")
+            _replay(st, k)
         st.stream.synchronize()
 
     def batch_release(self, st, slots) -> None:
@@ -832,7 +848,6 @@ class HipQwen2ForCausalLM(_HipModule):
         st.token.copy_(first)
         eos_set = _eos_set(eos_token_id, self.lcfg.eos_token_id)
         n_steps = max_new_tokens - 1
-        lib = _lib.load()
         if forced_ids is not None or return_logits:
             step_logits, ids = [r.last_logits[:Bn].float().clone()], [first]
             if forced_ids is not None:
@@ -858,10 +873,10 @@ class HipQwen2ForCausalLM(_HipModule):
         with torch.cuda.stream(st.stream):
             while done < n_steps and not all(done_rows):
                 chunk = min(16, n_steps - done)
-                for _ in range(chunk):
-                    if use_graph:
-                        check(lib.vila_graph_launch(st.graph, st.stream.cuda_stream), "graph_launch")
-                    else:
+                if use_graph:
+                    _replay(st, chunk)
+                else:
+                    for _ in range(chunk):
                         self._batch_step(st)
                 done += chunk
                 got = st.out_ids[:, :done].tolist()                 # one sync per 16 steps
@@ -955,26 +970,38 @@ class HipQwen2ForCausalLM(_HipModule):
         return self._generate_solo(inputs_embeds, attention_mask, max_new_tokens, eos_token_id, sampling, use_graph, return_logits, forced_ids, cache,
                                    streamer)
 
-    def _generate_solo(self, inputs_embeds, attention_mask, max_new_tokens, eos_token_id, sampling, use_graph, return_logits, forced_ids, cache,
-                       streamer):
-        """generate() for one sequence: prefill, then the batch-1 step (one hipGraph replay per token, or step by step under `use_graph=False`,
-        `return_logits` or `forced_ids`).  sampling: None (greedy) or (temperature, top_k, top_p, seed)."""
-        ops._need(inputs_embeds, dtype=None, name="inputs_embeds")
-        x = inputs_embeds[0]
-        if attention_mask is not None:
-            x = x[attention_mask[0].bool()]
-        S = x.shape[0]
-        dev = x.device
-        eos_set = _eos_set(eos_token_id, self.lcfg.eos_token_id)
+    def _cache_for(self, S: int, max_new_tokens: int, cache):
+        """A one-sequence generate()'s KV cache: the caller's, or `_own_cache`, re-made at the next multiple of 256 when missing or too small."""
         if cache is None:
             cache = self._own_cache
             if cache is None or cache.max_ctx < S + max_new_tokens:
                 cache = self._own_cache = self.new_cache(((S + max_new_tokens + 255) // 256) * 256)
         if cache.max_ctx < S + max_new_tokens:
             raise ValueError(f"KV cache too small: {cache.max_ctx} < {S} + {max_new_tokens}")
+        return cache
+
+    def _prefill_one(self, inputs_embeds, attention_mask, max_new_tokens, cache, admit=None):
+        """The opening of a one-sequence generate(): the row cut by its mask, its cache, the prefill.  admit(cache) may refuse the cache before
+        any kernel runs.  Returns (S, cache, the prefill's result, the last row's index as a device int32[1])."""
+        ops._need(inputs_embeds, dtype=None, name="inputs_embeds")
+        x = inputs_embeds[0]
+        if attention_mask is not None:
+            x = x[attention_mask[0].bool()]
+        S, dev = x.shape[0], x.device
+        cache = self._cache_for(S, max_new_tokens, cache)
+        if admit is not None:
+            admit(cache)
         pos = torch.arange(S, device=dev, dtype=torch.int32)
         last = torch.full((1,), S - 1, device=dev, dtype=torch.int32)          # (a fill kernel, not a host copy)
-        r = self.prefill_packed(x.to(self.dtype), pos, None, S, cache=cache, last_rows=last)
+        return S, cache, self.prefill_packed(x.to(self.dtype), pos, None, S, cache=cache, last_rows=last), last
+
+    def _generate_solo(self, inputs_embeds, attention_mask, max_new_tokens, eos_token_id, sampling, use_graph, return_logits, forced_ids, cache,
+                       streamer):
+        """generate() for one sequence: prefill, then the batch-1 step (one hipGraph replay per token, or step by step under `use_graph=False`,
+        `return_logits` or `forced_ids`).  sampling: None (greedy) or (temperature, top_k, top_p, seed)."""
+        S, cache, r, last = self._prefill_one(inputs_embeds, attention_mask, max_new_tokens, cache)
+        dev = inputs_embeds.device
+        eos_set = _eos_set(eos_token_id, self.lcfg.eos_token_id)
         st = self._decode_session(cache, max_new_tokens, sampling)
         # the sampler mixes a device counter into its random number: the decode steps use the position of the token they consume
         # (S, S+1, ...); the first token, drawn from the prefill's logits, uses S - 1
@@ -984,7 +1011,6 @@ class HipQwen2ForCausalLM(_HipModule):
         st.n_out.zero_()
         st.token.copy_(first if forced_ids is None else forced_ids[:1].to(dev))
         ids = [first]
-        lib = _lib.load()
         eager = (not use_graph) or return_logits or (forced_ids is not None)
         if not eager and st.graph is None:
             def restore():
@@ -1008,17 +1034,15 @@ class HipQwen2ForCausalLM(_HipModule):
             done = 0
             first_id = first.item()
             stop = first_id in eos_set
-            if streamer is not None:
-                streamer.put(torch.tensor([first_id], dtype=torch.int64))
+            _stream_put(streamer, first_id)
             with torch.cuda.stream(st.stream):
                 while done < n_steps and not stop:
                     chunk = min(16, n_steps - done)
-                    for _ in range(chunk):
-                        check(lib.vila_graph_launch(st.graph, st.stream.cuda_stream), "graph_launch")
+                    _replay(st, chunk)
                     got = st.out_ids[:done + chunk].tolist()       # one sync per 16 tokens
                     if streamer is not None:
                         for t in got[done:]:
-                            streamer.put(torch.tensor([t], dtype=torch.int64))
+                            _stream_put(streamer, t)
                             if t in eos_set:
                                 break
                     done += chunk
@@ -1030,7 +1054,7 @@ class HipQwen2ForCausalLM(_HipModule):
         if streamer is not None:
             if eager:                                       # the step-by-step paths learn of their tokens at the end
                 for t in out.tolist():
-                    streamer.put(torch.tensor([t], dtype=torch.int64))
+                    _stream_put(streamer, t)
             streamer.end()
         out = out[None]
         return (out, torch.stack(step_logits)) if return_logits else out
@@ -1053,9 +1077,7 @@ class HipQwen2ForCausalLM(_HipModule):
     def _verify_session(self, cache, n: int, max_out: int, max_ngram: int):
         """Device-resident state of a verify session (+ its captured hipGraph), keyed like `_decode_session`."""
         w4 = self._w4_batched()
-        q4 = self._w4.mats[0]["down"].q.data_ptr() if w4 else None
-        key = (cache.k.data_ptr(), cache.max_ctx, n, max_out, max_ngram, self.model.embed_tokens.weight.data_ptr(),
-               _get(self, "model.layers.0.mlp.down_proj.weight").data_ptr(), q4)
+        key = (cache.k.data_ptr(), cache.max_ctx, n, max_out, max_ngram, *self._weights_key())
         if self._vdecode is not None and self._vdecode.key == key:
             return self._vdecode
         self._drop_session("_vdecode")
@@ -1069,7 +1091,8 @@ class HipQwen2ForCausalLM(_HipModule):
             st.cand = torch.zeros(max_out, device=dev, dtype=torch.int64)
             st.hist = torch.zeros(cache.max_ctx + max_out + 1, device=dev, dtype=torch.int64)
             st.logits = torch.zeros((n, self.lcfg.vocab_size), device=dev, dtype=torch.float32)
-            st.ws = torch.empty((lib.vila_llm_decode_verify_workspace_bytes(C.byref(w.shape), n, cache.max_ctx),), device=dev, dtype=torch.uint8)
+            ws_bytes = getattr(lib, _step_symbols(True, w4, False, verify=True)[1])
+            st.ws = torch.empty((ws_bytes(C.byref(w.shape), n, cache.max_ctx),), device=dev, dtype=torch.uint8)
         st.c = _lib.VilaDecodeVerify(n, 0, st.pos.data_ptr(), st.token.data_ptr(), st.n_draft.data_ptr(), st.out_ids.data_ptr(), st.n_out.data_ptr(), max_out,
                                      st.logits.data_ptr(), st.n_accept.data_ptr(), st.hist.data_ptr(), st.n_hist.data_ptr(), st.hist.numel(), max_ngram,
                                      st.cand.data_ptr(), st.n_cand.data_ptr())
@@ -1079,14 +1102,9 @@ class HipQwen2ForCausalLM(_HipModule):
 
     def verify_step(self, cache, st) -> None:
         """One verify step on the current stream: draft, forward of st.n rows, accept."""
-        lib = _lib.load()
-        if st.w4:
-            check(lib.vila_llm_decode_step_verify_w4(C.byref(self._struct()), self._w4.ptr, C.byref(cache.c), C.byref(st.c), st.ws.data_ptr(), st.ws.numel(),
-                                                     ops._stream()), "vila_llm_decode_step_verify_w4")
-        else:
+        if not st.w4:
             self._require_bf16("the bf16 verify step")
-            check(lib.vila_llm_decode_step_verify(C.byref(self._struct()), C.byref(cache.c), C.byref(st.c), st.ws.data_ptr(), st.ws.numel(), ops._stream()),
-                  "vila_llm_decode_step_verify")
+        self._step(True, self._w4 if st.w4 else None, cache, st, None, verify=True)
 
     def _generate_verify(self, inputs_embeds, attention_mask, max_new_tokens, eos_token_id, k, max_ngram, prompt_ids, draft_ids, cache, streamer):
         """generate() for one greedy sequence with the verify step: prefill as `_generate_solo`, first token from the prefill, then graph replays
@@ -1094,23 +1112,12 @@ class HipQwen2ForCausalLM(_HipModule):
         why = self._verify_refusal()
         if why is not None:
             raise ValueError("prompt_lookup_num_tokens / draft_ids: " + why)
-        ops._need(inputs_embeds, dtype=None, name="inputs_embeds")
-        x = inputs_embeds[0]
-        if attention_mask is not None:
-            x = x[attention_mask[0].bool()]
-        S, dev, n = x.shape[0], x.device, k + 1
+        def admit(c):
+            if c.max_ctx > self.BATCH_MAX_CTX:
+                raise ValueError(f"prompt_lookup_num_tokens / draft_ids: the verify step serves caches up to {self.BATCH_MAX_CTX} positions (got {c.max_ctx})")
+        S, cache, r, _ = self._prefill_one(inputs_embeds, attention_mask, max_new_tokens, cache, admit)
+        dev, n = inputs_embeds.device, k + 1
         eos_set = _eos_set(eos_token_id, self.lcfg.eos_token_id)
-        if cache is None:
-            cache = self._own_cache
-            if cache is None or cache.max_ctx < S + max_new_tokens:
-                cache = self._own_cache = self.new_cache(((S + max_new_tokens + 255) // 256) * 256)
-        if cache.max_ctx < S + max_new_tokens:
-            raise ValueError(f"KV cache too small: {cache.max_ctx} < {S} + {max_new_tokens}")
-        if cache.max_ctx > self.BATCH_MAX_CTX:
-            raise ValueError(f"prompt_lookup_num_tokens / draft_ids: the verify step serves caches up to {self.BATCH_MAX_CTX} positions (got {cache.max_ctx})")
-        pos = torch.arange(S, device=dev, dtype=torch.int32)
-        last = torch.full((1,), S - 1, device=dev, dtype=torch.int32)
-        r = self.prefill_packed(x.to(self.dtype), pos, None, S, cache=cache, last_rows=last)
         first = ops.argmax(r.last_logits[0])
         need = max_new_tokens - 1                                   # tokens wanted from the steps
         st = self._verify_session(cache, n, max(max_new_tokens, 1) + k, max_ngram)
@@ -1132,28 +1139,24 @@ class HipQwen2ForCausalLM(_HipModule):
         restore()
         if st.graph is None:
             _capture(st, lambda: self.verify_step(cache, st), restore)
-        lib = _lib.load()
         torch.cuda.current_stream().synchronize()
         first_id = first.item()
         stop = first_id in eos_set
-        if streamer is not None:
-            streamer.put(torch.tensor([first_id], dtype=torch.int64))
+        _stream_put(streamer, first_id)
         got: List[int] = []
         trace = self.spec_trace
         with torch.cuda.stream(st.stream):
             while len(got) < need and not stop:
                 # every replay appends at least one token: never more replays than tokens still wanted, at most 16 between two looks at the ids
                 chunk = 1 if trace is not None else max(1, min(16, (need - len(got) + n - 1) // n))
-                for _ in range(chunk):
-                    check(lib.vila_graph_launch(st.graph, st.stream.cuda_stream), "graph_launch")
+                _replay(st, chunk)
                 n_out = min(int(st.n_out.item()), need, st.max_out)  # (the sync)
                 if trace is not None:
                     trace.append(int(st.n_accept.item()))
                 new = st.out_ids[len(got):n_out].tolist()
                 for t in new:
                     got.append(t)
-                    if streamer is not None:
-                        streamer.put(torch.tensor([t], dtype=torch.int64))
+                    _stream_put(streamer, t)
                     if t in eos_set:
                         stop = True
                         break
