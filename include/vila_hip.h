@@ -286,6 +286,25 @@ int vila_attn_decode_verify_bf16(const void* q, int64_t ldq, const void* kslot, 
                                  int n, int q_heads, int kv_heads, int max_ctx, float scale, void* workspace, size_t workspace_bytes,
                                  vila_stream_t stream);
 
+/* The batch-1 step's attention on its own (operator level): q [q_heads][128] bf16 attends keys 0 .. *pos of ONE slot of one layer, kslot / vslot
+ * [kv_heads][max_ctx][128]; GQA groups of 1..8.  *pos must be below max_ctx: these kernels read *pos + 1 keys unguarded (the step's drivers refuse a
+ * full cache before any launch).  The three forms of vila_llm_decode_step, launched as the step launches them:
+ *   HEAD       one block per query head over the whole context, o [q_heads][128] bf16; max_ctx <= 2048;
+ *   SLICES256  per-head blocks over 256-key slices whose partials are merged in the prologue of the o_proj GEMV (the step's default up to 2048
+ *              positions).  The attention output exists only inside that GEMV, so the form is served by vila_attn_decode_oproj_bf16 / _w4:
+ *              y[N] = W[N][q_heads * 128] . o (+ residual[N]), with W bf16 or int4 groups of 128 (the layout of vila_gemv_w4_bf16; q_heads <= 112);
+ *   SPLIT64    64-key split-KV partials and a merge launch, o [q_heads][128] bf16; 2048 < max_ctx <= 32768. */
+enum { VILA_ATTN_DECODE_HEAD = 0, VILA_ATTN_DECODE_SLICES256 = 1, VILA_ATTN_DECODE_SPLIT64 = 2 };
+size_t vila_attn_decode_workspace_bytes(int q_heads, int max_ctx);
+int vila_attn_decode_bf16(const void* q, const void* kslot, const void* vslot, const int32_t* pos, void* o, int q_heads, int kv_heads, int max_ctx,
+                          float scale, int form, void* workspace, size_t workspace_bytes, vila_stream_t stream);
+int vila_attn_decode_oproj_bf16(const void* q, const void* kslot, const void* vslot, const int32_t* pos, const void* W, const void* residual, void* y,
+                                int N, int q_heads, int kv_heads, int max_ctx, float scale, void* workspace, size_t workspace_bytes,
+                                vila_stream_t stream);
+int vila_attn_decode_oproj_w4(const void* q, const void* kslot, const void* vslot, const int32_t* pos, const void* Wq, const void* Wsz,
+                              const void* residual, void* y, int N, int q_heads, int kv_heads, int max_ctx, float scale, void* workspace,
+                              size_t workspace_bytes, vila_stream_t stream);
+
 /* hipGraph helpers: capture whatever is enqueued on `stream` between begin/end, replay it later. */
 int vila_graph_begin(vila_stream_t stream);
 int vila_graph_end(vila_stream_t stream, void** graph_exec_out);

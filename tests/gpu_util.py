@@ -105,3 +105,56 @@ def attn_ref_grads(q, k, v, do, causal, cu=None, scale=None):
         og.backward(do[:, hs].float())
         o[:, hs], dq[:, hs], dk[:, g], dv[:, g] = og.detach(), qf.grad, kf.grad, vf.grad
     return o, dq, dk, dv
+
+
+# ---- planted-key inputs for the decode attentions (tests/test_decode_probe_cpu.py, tests/test_gpu_decode_keys.py) -------------------------
+# With i.i.d. random Q/K/V one key of L carries about 1/L of a head's softmax weight, so a key lost or admitted at a chunk, slice or capacity
+# boundary moves the output by less than the tests' bound once L is a few hundred.  A PLANTED key is alpha * q of one target query head per kv
+# head: its score alpha |q|^2 / sqrt(128) is about 22 at alpha = 2 against N(0, 1) for the random keys, so it takes essentially all of that
+# head's weight and the head returns that key's (random) V row.  Lose the key or admit one too many and the target heads move by O(|V|).
+def probe_targets(kv: int, G: int):
+    """The target query head of every kv head: another member of the group for each (kv head h -> head h * G + h % G)."""
+    return [h * G + h % G for h in range(kv)]
+
+
+def plant_keys(k_slot: torch.Tensor, q_row: torch.Tensor, keys, alpha=2.0) -> None:
+    """In place: k_slot [kv, C, 128] bf16 gets, for every kv head h, rows `keys` = bf16(alpha * q_row[target head of h]) (q_row [nq, 128] bf16);
+    alpha a number or one per key.  The V rows stay as they are."""
+    kv, G = k_slot.shape[0], q_row.shape[0] // k_slot.shape[0]
+    keys = list(keys)
+    alphas = [float(alpha)] * len(keys) if not hasattr(alpha, "__len__") else [float(a) for a in alpha]
+    for h, t in enumerate(probe_targets(kv, G)):
+        for key, a in zip(keys, alphas):
+            k_slot[h, key] = (a * q_row[t].float()).to(torch.bfloat16)
+
+
+def staircase_alphas(q_row: torch.Tensor, kv: int, n_keys: int, step: float = 9.0, alpha0: float = 2.0):
+    """alpha of planted key j = alpha0 + j * c with c chosen so that the score alpha |q|^2 / sqrt(128) of EVERY kv head's target rises by at least
+    `step` per key (c from the smallest |q_t|^2): key j then outweighs all earlier ones by e^step."""
+    G = q_row.shape[0] // kv
+    n2 = min(float(q_row[t].float().pow(2).sum()) for t in probe_targets(kv, G))
+    c = step * 128 ** 0.5 / n2
+    return [alpha0 + j * c for j in range(n_keys)]
+
+
+def decode_attn_ref(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, visible: torch.Tensor, scale=None) -> torch.Tensor:
+    """fp32 softmax over exactly the visible keys: q [n, nq, 128], k / v [n or 1, kv, C, 128] (row i reads slot i, or all rows the one slot),
+    visible [n, C] bool -> o [n, nq, 128] fp32.  One kv head at a time, nothing expanded."""
+    n, nq, D = q.shape
+    kv = k.shape[1]
+    G = nq // kv
+    scale = D ** -0.5 if scale is None else scale
+    out = torch.empty((n, nq, D), dtype=torch.float32, device=q.device)
+    hide = ~visible[:, None, :]
+    assert k.shape[0] in (1, n) and k.shape == v.shape and visible.shape == (n, k.shape[2])
+    for h in range(kv):
+        kh, vh = k[:, h].float().expand(n, -1, -1), v[:, h].float().expand(n, -1, -1)      # (a view: one slot serves every row)
+        s = torch.einsum("ngd,ncd->ngc", q[:, h * G:(h + 1) * G].float(), kh) * scale
+        p = torch.softmax(s.masked_fill(hide, float("-inf")), -1)
+        out[:, h * G:(h + 1) * G] = torch.einsum("ngc,ncd->ngd", p, vh)
+    return out
+
+
+def visible_upto(lens, C: int, device="cpu") -> torch.Tensor:
+    """[n, C] bool: row i sees keys 0 .. lens[i] - 1."""
+    return torch.arange(C, device=device)[None, :] < torch.as_tensor(list(lens), device=device)[:, None]

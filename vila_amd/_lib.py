@@ -138,6 +138,12 @@ PROTOTYPES = {
     "vila_attn_decode_verify_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "vila_attn_decode_verify_bf16": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_float, c_void_p,
                                              c_size_t, c_void_p]),
+    "vila_attn_decode_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "vila_attn_decode_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p, c_size_t, c_void_p]),
+    "vila_attn_decode_oproj_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float,
+                                            c_void_p, c_size_t, c_void_p]),
+    "vila_attn_decode_oproj_w4": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                          c_float, c_void_p, c_size_t, c_void_p]),
     "vila_decode_batch_force_slices": (None, [c_int]),
     "vila_decode_batch_slices": (c_int, [c_int]),
     "vila_sample_batch_workspace_bytes": (c_size_t, [c_int]),

@@ -802,6 +802,70 @@ extern "C" int vila_attn_decode_batch_bf16(const void* q, int64_t ldq, const voi
     return bdecode_attn(B(q), ldq, B(kcache), B(vcache), slot_stride, pos, (bf16_t*)o, ldo, n_rows, q_heads, kv_heads, max_ctx, scale, workspace,
                         workspace_bytes, S(stream));
 }
+// the batch-1 step's attention on its own (operator level): AttnDecodeArgs filled the way decode_step_impl fills them, on a workspace that holds the
+// step's partials ([splits of 64 keys][q_heads][128] + [..][2]).  `o_proj`: the 256-key slices, whose merge exists only in the o_proj GEMV's prologue
+static_assert(VILA_ATTN_DECODE_HEAD == 0 && VILA_ATTN_DECODE_SLICES256 == 1 && VILA_ATTN_DECODE_SPLIT64 == 2, "attention forms of the batch-1 step");
+extern "C" size_t vila_attn_decode_workspace_bytes(int q_heads, int max_ctx) {
+    const size_t ns = dec_splits(max_ctx);
+    return align_up(ns * q_heads * 128 * 4, 256) + align_up(ns * q_heads * 2 * 4, 256);
+}
+static int attn_decode_op(const void* q, const void* kslot, const void* vslot, const int32_t* pos, void* o, int q_heads, int kv_heads, int max_ctx, float scale,
+                          int form, void* workspace, size_t workspace_bytes, float** part_o, float** part_ml, hipStream_t s) {
+    VILA_REQUIRE(q && kslot && vslot && pos && workspace, "attn_decode: NULL argument");
+    VILA_REQUIRE(q_heads >= 1 && kv_heads >= 1 && q_heads % kv_heads == 0 && q_heads / kv_heads <= DEC_MAXG,
+                 "attn_decode: a GQA group of 1..%d query heads per kv head (got %d / %d heads)", DEC_MAXG, q_heads, kv_heads);
+    VILA_REQUIRE((uintptr_t)q % 16 == 0 && (uintptr_t)kslot % 16 == 0 && (uintptr_t)vslot % 16 == 0 && (uintptr_t)workspace % 16 == 0,
+                 "attn_decode: head_dim 128 rows, 16-byte aligned, a slot of [kv_heads][max_ctx][128]");
+    if (form == VILA_ATTN_DECODE_SPLIT64)
+        VILA_REQUIRE(max_ctx > DEC_SHORT_CTX && max_ctx <= BDEC_MAX_CTX, "attn_decode: the 64-key split serves caches of %d..%d positions (got %d)",
+                     DEC_SHORT_CTX + 1, BDEC_MAX_CTX, max_ctx);
+    else
+        VILA_REQUIRE(max_ctx >= 1 && max_ctx <= DEC_SHORT_CTX, "attn_decode: the per-head forms serve caches of 1..%d positions (got %d)", DEC_SHORT_CTX, max_ctx);
+    VILA_REQUIRE(workspace_bytes >= vila_attn_decode_workspace_bytes(q_heads, max_ctx), "attn_decode: workspace too small");
+    const int ns = dec_splits(max_ctx);
+    *part_o = (float*)workspace;
+    *part_ml = (float*)((char*)workspace + align_up((size_t)ns * q_heads * 128 * 4, 256));
+    AttnDecodeArgs ad{};
+    ad.q = B(q); ad.kcache = B(kslot); ad.vcache = B(vslot); ad.o = (bf16_t*)o; ad.part_o = *part_o; ad.part_ml = *part_ml; ad.pos_ptr = pos;
+    ad.nq = q_heads; ad.nkv = kv_heads; ad.hd = 128; ad.max_ctx = max_ctx; ad.n_splits = ns; ad.scale = scale;
+    ad.split256 = form == VILA_ATTN_DECODE_SLICES256 ? 1 : 0;
+    return launch_attn_decode(ad, s);
+}
+extern "C" int vila_attn_decode_bf16(const void* q, const void* kslot, const void* vslot, const int32_t* pos, void* o, int q_heads, int kv_heads, int max_ctx,
+                                     float scale, int form, void* workspace, size_t workspace_bytes, vila_stream_t stream) {
+    VILA_REQUIRE(form == VILA_ATTN_DECODE_HEAD || form == VILA_ATTN_DECODE_SPLIT64,
+                 "attn_decode: form %d has no attention output of its own (the 256-key slices meet in vila_attn_decode_oproj_bf16 / _w4)", form);
+    VILA_REQUIRE(o != nullptr, "attn_decode: NULL argument");
+    float *part_o, *part_ml;
+    return attn_decode_op(q, kslot, vslot, pos, o, q_heads, kv_heads, max_ctx, scale, form, workspace, workspace_bytes, &part_o, &part_ml, S(stream));
+}
+static int attn_decode_oproj(const void* q, const void* kslot, const void* vslot, const int32_t* pos, const void* W, const void* Wq, const void* Wsz,
+                             const void* residual, void* y, int N, int q_heads, int kv_heads, int max_ctx, float scale, void* workspace, size_t workspace_bytes,
+                             vila_stream_t stream) {
+    VILA_REQUIRE(y != nullptr && N >= 1 && (W != nullptr || (Wq != nullptr && Wsz != nullptr)), "attn_decode_oproj: NULL argument");
+    const bool w4 = W == nullptr;
+    VILA_REQUIRE(!w4 || q_heads <= 7 * 16, "attn_decode_oproj: the W4 merge holds up to %d heads (got %d)", 7 * 16, q_heads);
+    hipStream_t s = S(stream);
+    float *part_o, *part_ml;
+    VILA_TRY(attn_decode_op(q, kslot, vslot, pos, nullptr, q_heads, kv_heads, max_ctx, scale, VILA_ATTN_DECODE_SLICES256, workspace, workspace_bytes, &part_o,
+                            &part_ml, s));
+    GemvArgs g{};
+    g.x = B(workspace); g.W = B(W); g.residual = B(residual); g.y = B(y); g.N = N; g.K = q_heads * 128;       // x: never read in this mode
+    g.mode = 2; g.part_o = part_o; g.part_ml = part_ml; g.pos_ptr = pos; g.n_splits = cdiv(max_ctx, 256); g.split_keys = 256;
+    return proj_gemv(g, w4, Wq, Wsz, s);
+}
+extern "C" int vila_attn_decode_oproj_bf16(const void* q, const void* kslot, const void* vslot, const int32_t* pos, const void* W, const void* residual, void* y,
+                                           int N, int q_heads, int kv_heads, int max_ctx, float scale, void* workspace, size_t workspace_bytes,
+                                           vila_stream_t stream) {
+    VILA_REQUIRE(W != nullptr, "attn_decode_oproj: NULL argument");
+    return attn_decode_oproj(q, kslot, vslot, pos, W, nullptr, nullptr, residual, y, N, q_heads, kv_heads, max_ctx, scale, workspace, workspace_bytes, stream);
+}
+extern "C" int vila_attn_decode_oproj_w4(const void* q, const void* kslot, const void* vslot, const int32_t* pos, const void* Wq, const void* Wsz,
+                                         const void* residual, void* y, int N, int q_heads, int kv_heads, int max_ctx, float scale, void* workspace,
+                                         size_t workspace_bytes, vila_stream_t stream) {
+    VILA_REQUIRE(Wq != nullptr && Wsz != nullptr, "attn_decode_oproj_w4: NULL argument");
+    return attn_decode_oproj(q, kslot, vslot, pos, nullptr, Wq, Wsz, residual, y, N, q_heads, kv_heads, max_ctx, scale, workspace, workspace_bytes, stream);
+}
 extern "C" void vila_decode_batch_force_slices(int nsl) { bdecode_force_slices(nsl); }
 extern "C" int vila_decode_batch_slices(int max_ctx) { return bdecode_attn_slices(max_ctx); }
 

@@ -304,6 +304,65 @@ def attn_decode_verify(q: torch.Tensor, kslot: torch.Tensor, vslot: torch.Tensor
     return o
 
 
+ATTN_DECODE_FORMS = {"head": 0, "slices256": 1, "split64": 2}
+
+
+def attn_decode(q: torch.Tensor, kslot: torch.Tensor, vslot: torch.Tensor, pos: torch.Tensor, form: str = "head", scale: Optional[float] = None,
+                w=None, residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The batch-1 decode step's attention on its own: q [q_heads, 128] bf16, kslot / vslot one layer's slot [kv_heads, max_ctx, 128] bf16
+    (contiguous), pos a device int32 scalar below max_ctx — keys 0 .. pos are attended.  GQA groups of 1..8.  form: "head" (one block per query
+    head, max_ctx <= 2048) or "split64" (64-key split-KV + merge launch, max_ctx > 2048) -> o [q_heads, 128]; "slices256" (the step's default up
+    to 2048 positions: 256-key slices merged in the o_proj GEMV's prologue) needs the o_proj weight `w`, bf16 [N, q_heads * 128] or a
+    vila_amd.quant.W4Matrix -> y [N] = w . o (+ residual [N]).  The kernels read pos + 1 keys unguarded, so a position at or past the capacity is
+    refused here (one host read of pos)."""
+    _need(q, name="q"); _need(kslot, name="kslot"); _need(vslot, name="vslot"); _need(pos, dtype=torch.int32, name="pos")
+    if form not in ATTN_DECODE_FORMS:
+        raise ValueError(f"attn_decode: form must be one of {sorted(ATTN_DECODE_FORMS)}, got {form!r}")
+    if q.dim() != 2 or q.shape[1] != 128 or not q.is_contiguous():
+        raise ValueError("attn_decode: q must be contiguous [q_heads, 128]")
+    nq = q.shape[0]
+    if kslot.dim() != 3 or kslot.shape != vslot.shape or kslot.shape[2] != 128 or not kslot.is_contiguous() or not vslot.is_contiguous():
+        raise ValueError("attn_decode: kslot / vslot must be contiguous [kv_heads, max_ctx, 128] of one shape")
+    nkv, max_ctx, _ = kslot.shape
+    if pos.numel() != 1:
+        raise ValueError("attn_decode: pos is one device scalar")
+    p = int(pos)
+    if not 0 <= p < max_ctx:
+        raise ValueError(f"attn_decode: position {p} outside the cache of {max_ctx} positions")
+    if (form == "slices256") != (w is not None):
+        raise ValueError("attn_decode: the o_proj weight goes with form 'slices256', and only with it")
+    lib = _lib.load()
+    sc = float(scale if scale is not None else 128 ** -0.5)
+    ws = torch.empty((lib.vila_attn_decode_workspace_bytes(nq, max_ctx),), device=q.device, dtype=torch.uint8)
+    if w is None:
+        o = torch.empty((nq, 128), device=q.device, dtype=torch.bfloat16)
+        check(lib.vila_attn_decode_bf16(q.data_ptr(), kslot.data_ptr(), vslot.data_ptr(), pos.data_ptr(), o.data_ptr(), nq, nkv, max_ctx, sc,
+                                        ATTN_DECODE_FORMS[form], ws.data_ptr(), ws.numel(), _stream()), "attn_decode")
+        return o
+    if residual is not None:
+        _need(residual, name="residual")
+    if isinstance(w, torch.Tensor):
+        _need(w, name="w")
+        if w.dim() != 2 or w.shape[1] != nq * 128 or not w.is_contiguous():
+            raise ValueError(f"attn_decode: w must be contiguous [N, {nq * 128}]")
+        N = w.shape[0]
+        if residual is not None and residual.numel() != N:
+            raise ValueError(f"attn_decode: residual must have {N} entries")
+        y = torch.empty((N,), device=q.device, dtype=torch.bfloat16)
+        check(lib.vila_attn_decode_oproj_bf16(q.data_ptr(), kslot.data_ptr(), vslot.data_ptr(), pos.data_ptr(), w.data_ptr(), _p(residual), y.data_ptr(), N,
+                                              nq, nkv, max_ctx, sc, ws.data_ptr(), ws.numel(), _stream()), "attn_decode_oproj")
+        return y
+    _need(w.q, dtype=torch.int32, name="w.q"); _need(w.sz, dtype=torch.int32, name="w.sz")
+    if w.K != nq * 128 or w.mode != 0:
+        raise ValueError(f"attn_decode: the W4 matrix must be a plain one with K = {nq * 128} (got K = {w.K}, mode {w.mode})")
+    if residual is not None and residual.numel() != w.N:
+        raise ValueError(f"attn_decode: residual must have {w.N} entries")
+    y = torch.empty((w.N,), device=q.device, dtype=torch.bfloat16)
+    check(lib.vila_attn_decode_oproj_w4(q.data_ptr(), kslot.data_ptr(), vslot.data_ptr(), pos.data_ptr(), w.q.data_ptr(), w.sz.data_ptr(), _p(residual),
+                                        y.data_ptr(), w.N, nq, nkv, max_ctx, sc, ws.data_ptr(), ws.numel(), _stream()), "attn_decode_oproj_w4")
+    return y
+
+
 def prompt_lookup_draft(hist: torch.Tensor, n_hist: int, k: int, max_ngram: int = 2) -> list:
     """The verify step's draft stage on its own: hist int64 on the device, the first n_hist ids are the history -> up to k draft ids (a list),
     what `host.prompt_lookup_draft(hist[:n_hist], k, max_ngram)` returns."""
