@@ -145,25 +145,33 @@ __global__ __launch_bounds__(1024) void attn_decode_head(AttnDecodeArgs p) {
     const int row = blockIdx.z;                                  // batched decode: sequence = cache slot (0 for the batch-1 step)
     p.q += row * p.q_row_stride; p.kcache += row * p.slot_stride; p.vcache += row * p.slot_stride;
     if (!SPLIT) p.o += row * p.o_row_stride;
-    const int nkeys_all = p.pos_ptr[row] + 1;
-    if (SPLIT && key_lo >= nkeys_all) return;                    // block-uniform: slices beyond the context write nothing (the merge skips them)
-    const int nkeys = SPLIT ? (nkeys_all < key_lo + 256 ? nkeys_all : key_lo + 256) : nkeys_all;
     const bf16_t* kb = p.kcache + (int64_t)kvh * p.max_ctx * 128;
     const bf16_t* vb = p.vcache + (int64_t)kvh * p.max_ctx * 128;
-    if (tid < 128) sq[tid] = bf2f(p.q[h * 128 + tid]) * p.scale;
-    __syncthreads();
     const int kq = lane >> 2, qd = lane & 3;        // scores: key within the chunk, d quarter
     const int sg = lane >> 4, dc = lane & 15;       // P.V: 4-key subgroup, d chunk
-    float qr[32];
-#pragma unroll
-    for (int i = 0; i < 32; ++i) qr[i] = sq[qd * 32 + i];
-    float m = -INFINITY, l = 0.f, o[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) o[e] = 0.f;
-
     u32x4 kc[4], vc[4], kn_[4], vn_[4];
+    // The order of the prologue: q, the position and the wave's first K/V chunk are requested together; none needs another and
+    // none is predicated (straight-line code: the wait in front of the LDS write of q is a count that leaves K/V in flight).  The chunk's loads
+    // know only the CAPACITY yet: a key at or past max_ctx is clamped to the cache's last row (a cache of 300 positions is never read at row
+    // 300).  Once the position is here, the rows at or past nkeys, which may hold anything, are replaced by the zero vectors that a load
+    // predicated on nkeys produces.
+    int k0 = key_lo + wave * 16;
+    const int nkeys_all = p.pos_ptr[row] + 1;
+    const bf16_t qv = p.q[h * 128 + (tid & 127)];
+    __builtin_amdgcn_sched_barrier(0);                           // the small loads stay in front of K/V ...
+    {
+        const int cap = p.max_ctx - 1;
+        const int key = k0 + kq < cap ? k0 + kq : cap;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) { kn_[j] = (u32x4){0u, 0u, 0u, 0u}; vn_[j] = (u32x4){0u, 0u, 0u, 0u}; }
+        for (int j = 0; j < 4; ++j) {
+            kc[j] = *(const u32x4*)(kb + (int64_t)key * 128 + qd * 32 + j * 8);
+            const int vk = k0 + sg * 4 + j < cap ? k0 + sg * 4 + j : cap;
+            vc[j] = *(const u32x4*)(vb + (int64_t)vk * 128 + dc * 8);
+        }
+    }
+    __builtin_amdgcn_sched_barrier(0);                           // ... and in front of the return below, which waits for the position
+    if (SPLIT && key_lo >= nkeys_all) return;                    // block-uniform: slices beyond the context write nothing (the merge skips them)
+    const int nkeys = SPLIT ? (nkeys_all < key_lo + 256 ? nkeys_all : key_lo + 256) : nkeys_all;
     auto load_chunk = [&](int k0, u32x4 (&kk)[4], u32x4 (&vv)[4]) {
         const int key = k0 + kq;
 #pragma unroll
@@ -173,11 +181,24 @@ __global__ __launch_bounds__(1024) void attn_decode_head(AttnDecodeArgs p) {
             vv[j] = (vk < nkeys) ? *(const u32x4*)(vb + (int64_t)vk * 128 + dc * 8) : (u32x4){0u, 0u, 0u, 0u};
         }
     };
-    int k0 = key_lo + wave * 16;
-    if (k0 < nkeys) load_chunk(k0, kc, vc);
+    if (tid < 128) sq[tid] = bf2f(qv) * p.scale;
+    sync_lds();                                                  // LDS only: a __syncthreads() would drain the K/V loads (gemv_common.h)
+    float qr[32];
+#pragma unroll
+    for (int i = 0; i < 32; ++i) qr[i] = sq[qd * 32 + i];
+    float m = -INFINITY, l = 0.f, o[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o[e] = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        if (k0 + kq >= nkeys) kc[j] = (u32x4){0u, 0u, 0u, 0u};
+        if (k0 + sg * 4 + j >= nkeys) vc[j] = (u32x4){0u, 0u, 0u, 0u};
+        kn_[j] = (u32x4){0u, 0u, 0u, 0u}; vn_[j] = (u32x4){0u, 0u, 0u, 0u};
+    }
     for (; k0 < nkeys; k0 += 256) {
         const int kn = k0 + 256;
-        if (kn < nkeys) load_chunk(kn, kn_, vn_);            // prefetch the wave's next chunk under this chunk's math
+        // prefetch the wave's next chunk under this chunk's math (a 256-key slice is one chunk per wave: nothing follows)
+        if (!SPLIT && kn < nkeys) load_chunk(kn, kn_, vn_);
         float a = 0.f;
 #pragma unroll
         for (int j = 0; j < 4; ++j)

@@ -2,7 +2,7 @@
 // the roofline is HBM (14.14 GB / token for NVILA-8B bf16), not MFMA.  Design rules (cdna guide, "GEMV / M<=16"):
 // weights go straight HBM -> VGPR with 16-B non-temporal loads, deep unroll, late wait; the activation vector is
 // staged once per block in LDS (with the preceding RMSNorm fused in, HF rounding order kept); all epilogues
-// (bias, RoPE, KV-cache write, SiLU*up, residual add) are fused so a decoder layer is 6 launches.
+// (bias, RoPE, KV-cache write, SiLU*up, residual add) are fused so a decoder layer is 5 launches.
 #include "kernels.h"
 #include "gemv_common.h"
 #include "attn_decode.h"
@@ -18,15 +18,82 @@ __device__ __forceinline__ float dot8(const u32x4 w, const u32x4 x, float acc) {
     return acc;
 }
 
+// A bf16 epilogue operand that was requested ahead of the dot product, converted where it is used.  The empty asm keeps the compiler from moving
+// the conversion up to the load, where it would wait for the load — and, loads retiring in order, for every weight requested in front of it.
+__device__ __forceinline__ float bf2f_late(bf16_t raw) {
+    unsigned r = raw;
+    asm volatile("" : "+v"(r));
+    return __uint_as_float(r << 16);
+}
+
 // stage x = merged split-KV attention output (flash-decoding combine fused into the o_proj GEMV):
 //   o[h][d] = sum_s exp(m_s - M) part_o[s][h][d] / sum_s exp(m_s - M) l_s ,  rounded to bf16 like the reference's attn output
+// In two halves like stage_x (gemv_common.h).  The issue half requests, for every slice of the CAPACITY (n_splits <= MERGE_MAXS; the workspace is
+// sized for it), the (m, l) pair of this thread's head and this thread's first MERGE_PI chunks of part_o, without waiting for the position.  The
+// finish half drops the slices at or past n_active by SELECTION (they hold stale bytes, so never by a zero weight) and merges exactly as
+// attn_merge_weights (attn_decode.h) and the slice-ordered fmaf sum always did: M by fmaxf over s = 0 .. n_active - 1 in order, L and the weights
+// by the same expressions, one thread per head; the weighted sum by fmaf in slice order, one thread per chunk.
+#define MERGE_MAXS 8                     // slices of the capacity (256-key slices of caches up to 2048 positions)
+#define MERGE_PI 2                       // float4 chunks per thread requested up front (28 heads, NT = 512: all of them)
+struct AttnMergeLoads { float m[MERGE_MAXS], l[MERGE_MAXS]; f32x4 po[MERGE_PI][MERGE_MAXS]; };
 template <int NT>
-__device__ __forceinline__ void stage_x_attn(const float* __restrict__ part_o, const float* __restrict__ part_ml, int n_active,
-                                             int nq, bf16_t* sx, float* wsm /* [n_active*nq] */) {
+__device__ __forceinline__ void stage_x_attn_issue(const float* __restrict__ part_o, const float* __restrict__ part_ml, int n_splits, int nq,
+                                                   AttnMergeLoads& ld) {
+    const int tid = threadIdx.x, n4 = nq * 32;   // float4 chunks
+    // No load is predicated per lane (an index past the end is clamped to the last slot and its value never used): straight-line code, so the
+    // finish waits with a count.  Slices 4 .. 7 sit behind ONE block-uniform branch, so that a cache of up to 1024 positions requests 4.
+    auto issue = [&](int s0) {
+#pragma unroll
+        for (int s = s0; s < s0 + MERGE_MAXS / 2; ++s) {
+            const int sc = s < n_splits ? s : n_splits - 1;
+            const float* ml = part_ml + ((int64_t)sc * nq + (tid < nq ? tid : nq - 1)) * 2;
+            ld.m[s] = ml[0]; ld.l[s] = ml[1];
+#pragma unroll
+            for (int it = 0; it < MERGE_PI; ++it) {
+                const int i = tid + NT * it < n4 ? tid + NT * it : n4 - 1;
+                ld.po[it][s] = *(const f32x4*)(part_o + ((int64_t)sc * nq) * 128 + i * 4);
+            }
+        }
+    };
+    issue(0);
+    if (n_splits > MERGE_MAXS / 2) issue(MERGE_MAXS / 2);
+}
+template <int NT>
+__device__ __forceinline__ void stage_x_attn_finish(const float* __restrict__ part_o, const float* __restrict__ part_ml, int n_active, int nq,
+                                                    bf16_t* sx, float* wsm /* [n_splits * nq] */, const AttnMergeLoads& ld) {
     const int tid = threadIdx.x;
-    attn_merge_weights<NT>(part_ml, n_active, nq, wsm);
-    const int n4 = nq * 32;   // float4 chunks
-    for (int i = tid; i < n4; i += NT) {
+    if (tid < nq) {
+        float M = -INFINITY;
+#pragma unroll
+        for (int s = 0; s < MERGE_MAXS; ++s) if (s < n_active) M = fmaxf(M, ld.m[s]);
+        float L = 0.f;
+#pragma unroll
+        for (int s = 0; s < MERGE_MAXS; ++s) if (s < n_active) L += __expf(ld.m[s] - M) * ld.l[s];
+        const float invL = 1.f / L;
+#pragma unroll
+        for (int s = 0; s < MERGE_MAXS; ++s) if (s < n_active) wsm[s * nq + tid] = __expf(ld.m[s] - M) * invL;
+    }
+    sync_lds();
+    const int n4 = nq * 32;
+#pragma unroll
+    for (int it = 0; it < MERGE_PI; ++it) {
+        const int i = tid + NT * it;
+        if (i < n4) {
+            const int h = i >> 5;
+            f32x4 o = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int s = 0; s < MERGE_MAXS; ++s) {
+                if (s < n_active) {
+                    const f32x4 pv = ld.po[it][s];
+                    const float w = wsm[s * nq + h];
+                    o[0] = fmaf(w, pv[0], o[0]); o[1] = fmaf(w, pv[1], o[1]); o[2] = fmaf(w, pv[2], o[2]); o[3] = fmaf(w, pv[3], o[3]);
+                }
+            }
+            u32x2 r; r[0] = pack2bf(o[0], o[1]); r[1] = pack2bf(o[2], o[3]);
+            *(u32x2*)(sx + i * 4) = r;
+        }
+    }
+    for (int i = tid + NT * MERGE_PI; i < n4; i += NT) {          // more heads than the up-front chunks cover (small grids: NT = 256)
         const int h = i >> 5;
         f32x4 o = (f32x4){0.f, 0.f, 0.f, 0.f};
         for (int s = 0; s < n_active; ++s) {
@@ -37,7 +104,7 @@ __device__ __forceinline__ void stage_x_attn(const float* __restrict__ part_o, c
         u32x2 r; r[0] = pack2bf(o[0], o[1]); r[1] = pack2bf(o[2], o[3]);
         *(u32x2*)(sx + i * 4) = r;
     }
-    __syncthreads();
+    sync_lds();
 }
 
 // ---- weight streaming -----------------------------------------------------------------------------
@@ -51,6 +118,28 @@ __device__ __forceinline__ void load_batch(const bf16_t* const (&wrow)[R], int c
 #pragma unroll
         for (int r = 0; r < R; ++r) b.v[u][r] = (c < nch) ? ldg_nt(wrow[r] + c * 8) : (u32x4){0u, 0u, 0u, 0u};
     }
+}
+// A wave's FIRST batch, requested between the two halves of the staging.  Nothing here is predicated or branched over, so that the code from
+// the staging's loads to its waits is straight-line and those waits COUNT this batch instead of draining it (behind a join with a path that
+// requested fewer loads the compiler's wait falls back to the smaller count): a chunk past the row is clamped to the row's last chunk, and a
+// wave without a row group (`has` false; its rows are group 0's) requests the first 16 bytes of those rows in every lane and request — one
+// cache line each, so that it stays on the same path at next to no traffic.  first_batch_mask then puts the zeros of load_batch in place of
+// the clamped chunks.
+template <int R, int U>
+__device__ __forceinline__ void load_first_batch(const bf16_t* const (&wrow)[R], int lane, int nch, bool has, Batch<R, U>& b) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const int c = u * 64 + lane < nch ? u * 64 + lane : nch - 1;
+#pragma unroll
+        for (int r = 0; r < R; ++r) b.v[u][r] = ldg_nt(wrow[r] + (has ? c : 0) * 8);
+    }
+}
+template <int R, int U>
+__device__ __forceinline__ void first_batch_mask(int lane, int nch, Batch<R, U>& b) {
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+#pragma unroll
+        for (int r = 0; r < R; ++r) b.v[u][r] = (u * 64 + lane < nch) ? b.v[u][r] : (u32x4){0u, 0u, 0u, 0u};
 }
 template <int R, int U>
 __device__ __forceinline__ void fma_batch(const Batch<R, U>& b, const bf16_t* sx, int c0, int lane, int nch, float (&acc)[R]) {
@@ -77,8 +166,13 @@ __device__ __forceinline__ void wave_rows_dot(const bf16_t* const (&wrow)[R], co
 
 // ------------------------------------------------------------------------------------------------
 // generic GEMV: y = W x (+bias) (+residual)   |   gate/up: y = silu(Wg x) * (Wu x)   |   x from attention partials
-// The first weight batch of every wave is issued BEFORE the activation is staged, so the HBM latency of the first
-// loads overlaps the norm / merge prologue.
+// Order of the prologue.  A wave's vector loads retire in order.  INPUTS_FIRST: the wave requests (1) every small load the
+// staging needs, (2) its first weight batch, and then (3) waits for (1) alone — a counted vmcnt that leaves the weights outstanding — and
+// forms the merge, writes LDS and takes the block syncs while the weights are in flight.  That is the merge mode (o_proj) and every plain GEMV
+// over rows longer than hidden (U = 4).  Of the latter only down_proj, which has no norm, was measured; with a norm the staging's loads still
+// sit behind `tid < 256` and the one- or two-pass choice, so some of its waits may fall back to a smaller count (correct either way).  The
+// GEMVs over K = hidden (lm_head, gate/up, and the QKV kernel below) measured no gain and keep the weights in front: their staging then waits
+// until the batch has landed.  Figures: DESIGN.md §4.3, CHANGELOG.
 // ------------------------------------------------------------------------------------------------
 // U = 16-B loads in flight per row and lane: 7 covers a whole K = 3584 row in ONE round trip (the short K=hidden GEMVs are
 // latency-bound), 4 is enough for the long rows (K = 18944) where many iterations pipeline anyway.
@@ -92,6 +186,7 @@ __global__ __launch_bounds__(NT) void gemv_kernel(GemvArgs p, int n_groups, int 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int nch = p.K >> 3;
     constexpr int R = (MODE == 1) ? 4 : 2;
+    constexpr bool INPUTS_FIRST = MODE == 2 || (MODE == 0 && U < 7);
     // ncu > 0: the CU-balanced map (gemv_common.h CuMap; block = CU); ncu == 0: small grids, the plain grid-stride walk
     constexpr int WPB = NT / 64;
     const CuMap cm(n_groups, ncu > 0 ? ncu : 8, ncu > 0 ? skew : 0);
@@ -114,7 +209,7 @@ __global__ __launch_bounds__(NT) void gemv_kernel(GemvArgs p, int n_groups, int 
     };
     // Epilogue: after the wave reduction every lane holds the sums; lanes 0 and 1 each produce and store one of the wave's two adjacent
     // outputs (rows n, n + 1).
-    float e_bias = 0.f, e_res = 0.f;
+    bf16_t e_bias = 0, e_res = 0;                    // as loaded (bf2f_late)
     float best = -INFINITY; int bi = 0x7fffffff;     // p.amax_v: the largest fp32 output of this lane's rows so far (lanes 0 and 1)
     auto finish = [&](int gg, float (&acc)[R]) {
         const int n = gg * 2;
@@ -125,10 +220,10 @@ __global__ __launch_bounds__(NT) void gemv_kernel(GemvArgs p, int n_groups, int 
             o = f2bf(bfround(silu_f(gv)) * uv);
         } else {
             float v = lane == 0 ? acc[0] : acc[1];
-            v += e_bias;
+            v += bf2f_late(e_bias);
             if (lane < 2 && n + lane < p.N && p.y_f32 != nullptr) p.y_f32[n + lane] = v;
             if (p.amax_v != nullptr && lane < 2 && n + lane < p.N) amax_merge(best, bi, v, n + lane);
-            if (p.residual != nullptr) v = bfround(v) + e_res;
+            if (p.residual != nullptr) v = bfround(v) + bf2f_late(e_res);
             o = f2bf(v);
         }
         if (p.y != nullptr && lane < 2 && n + lane < p.N) p.y[n + lane] = o;
@@ -138,10 +233,10 @@ __global__ __launch_bounds__(NT) void gemv_kernel(GemvArgs p, int n_groups, int 
     auto epi_fetch = [&](int gg) {
         if constexpr (MODE != 1) {
             const int nn = gg * 2 + lane;
-            e_bias = 0.f; e_res = 0.f;
+            e_bias = 0; e_res = 0;
             if (lane < 2 && nn < p.N) {
-                if (p.bias != nullptr) e_bias = bf2f(p.bias[nn]);
-                if (p.residual != nullptr && p.y != nullptr) e_res = bf2f(p.residual[nn]);
+                if (p.bias != nullptr) e_bias = p.bias[nn];
+                if (p.residual != nullptr && p.y != nullptr) e_res = p.residual[nn];
             }
         }
     };
@@ -149,19 +244,35 @@ __global__ __launch_bounds__(NT) void gemv_kernel(GemvArgs p, int n_groups, int 
     const bf16_t* rows[R];
     Batch<R, U> b0;
     const bool has = g < n_groups;
-    // issue the first weight batch before staging x only for short rows (K <= 4096: the staging latency is comparable to the
-    // stream); for K = 18944 the x staging is long and queuing the weight loads in front of it measured 13 % slower
-    const bool early = has && p.K <= 4096;
-    if (early) { rows_of(g, rows); load_batch<R, U>(rows, 0, lane, nch, b0); }
-    if (has) epi_fetch(g);
-    if constexpr (MODE == 2) {
-        const int ks = p.split_keys > 0 ? p.split_keys : DEC_KS;
-        const int n_active = (*p.pos_ptr + ks) / ks;             // ceil((pos+1)/ks)
-        stage_x_attn<NT>(p.part_o, p.part_ml, n_active, p.K >> 7, sx, scratch);
+    if constexpr (INPUTS_FIRST) {
+        rows_of(has ? g : 0, rows);
+        if constexpr (MODE == 2) {
+            const int ks = p.split_keys > 0 ? p.split_keys : DEC_KS;
+            AttnMergeLoads ld;
+            stage_x_attn_issue<NT>(p.part_o, p.part_ml, p.n_splits, p.K >> 7, ld);
+            __builtin_amdgcn_sched_barrier(0);                   // the staging's loads stay in front of the weights
+            load_first_batch<R, U>(rows, lane, nch, has, b0);
+            if (has) epi_fetch(g);
+            const int n_active = (*p.pos_ptr + ks) / ks;         // ceil((pos+1)/ks)
+            stage_x_attn_finish<NT>(p.part_o, p.part_ml, n_active < p.n_splits ? n_active : p.n_splits, p.K >> 7, sx, scratch, ld);
+        } else {
+            STAGE_X_REGS(NT, st);
+            stage_x_issue<NT>(p.x, p.norm_w, p.K, STAGE_X_ARGS(st));
+            __builtin_amdgcn_sched_barrier(0);
+            load_first_batch<R, U>(rows, lane, nch, has, b0);
+            if (has) epi_fetch(g);                               // behind the weights: in front, the staging's loads waited for it at a join
+            stage_x_finish<NT, true>(p.x, p.norm_w, p.eps, p.K, sx, scratch, STAGE_X_ARGS(st));
+        }
+        if (has) first_batch_mask<R, U>(lane, nch, b0);
     } else {
-        stage_x<NT>(p.x, p.norm_w, p.eps, p.K, sx, scratch);
+        // the first weight batch in front of the staging, for short rows only (K <= 4096: the staging latency is comparable to the stream)
+        if (has && p.K <= 4096) { rows_of(g, rows); load_batch<R, U>(rows, 0, lane, nch, b0); }
+        if (has) epi_fetch(g);
+        STAGE_X_REGS(NT, st);
+        stage_x_issue<NT>(p.x, p.norm_w, p.K, STAGE_X_ARGS(st));
+        stage_x_finish<NT, false>(p.x, p.norm_w, p.eps, p.K, sx, scratch, STAGE_X_ARGS(st));   // __syncthreads(): exactly the waits these kernels had
     }
-    if (early) {
+    if (has && (INPUTS_FIRST || p.K <= 4096)) {
         float acc[R];
 #pragma unroll
         for (int r = 0; r < R; ++r) acc[r] = 0.f;
@@ -230,7 +341,10 @@ int gemv_grid_blocks(int N) {
 
 template <int MODE, int U>
 static void gemv_launch(int per, int grid, size_t lds, hipStream_t s, const GemvArgs& a, int n_groups, int ncu, int skew) {
-    switch (per) {
+    if constexpr (MODE == 2) {   // 8 waves per CU at most (launch_gemv asks balanced_grid for per <= 2): the wider blocks are not built
+        if (per == 1) hipLaunchKernelGGL((gemv_kernel<2, U, 256>), dim3(grid), dim3(256), lds, s, a, n_groups, ncu, skew);
+        else hipLaunchKernelGGL((gemv_kernel<2, U, 512>), dim3(grid), dim3(512), lds, s, a, n_groups, ncu, skew);
+    } else switch (per) {
         case 1: hipLaunchKernelGGL((gemv_kernel<MODE, U, 256>), dim3(grid), dim3(256), lds, s, a, n_groups, ncu, skew); break;
         case 2: hipLaunchKernelGGL((gemv_kernel<MODE, U, 512>), dim3(grid), dim3(512), lds, s, a, n_groups, ncu, skew); break;
         case 3: hipLaunchKernelGGL((gemv_kernel<MODE, U, 768>), dim3(grid), dim3(768), lds, s, a, n_groups, ncu, skew); break;
@@ -254,6 +368,8 @@ int launch_gemv(const GemvArgs& a, hipStream_t s) {
         gemv_launch<1, 4>(per, grid, lds, s, a, n_groups, ncu, 1);
     } else if (a.mode == 2) {
         VILA_REQUIRE(a.part_o != nullptr && a.part_ml != nullptr && a.pos_ptr != nullptr && a.K % 128 == 0, "gemv: attention-merge mode needs partials");
+        VILA_REQUIRE(a.n_splits >= 1 && a.n_splits <= MERGE_MAXS, "gemv: the merge prologue holds 1..%d slices (got %d)", MERGE_MAXS, a.n_splits);
+        VILA_REQUIRE(a.K / 128 <= 256, "gemv: the merge prologue forms one head's weights per thread of its smallest block: up to 256 heads (got %d)", a.K / 128);
         lds += (size_t)a.n_splits * (a.K / 128) * 4;
         if (short_k) gemv_launch<2, 7>(per, grid, lds, s, a, n_groups, ncu, 0);
         else gemv_launch<2, 4>(per, grid, lds, s, a, n_groups, ncu, 0);
@@ -301,13 +417,14 @@ __global__ __launch_bounds__(NT) void qkv_decode_kernel(QkvDecodeArgs p, int ncu
     };
     // epilogue operands (position, the pair's biases, its RoPE row) are requested before the dot product, not after the reduction
     int e_pos = 0;
-    float e_b0 = 0.f, e_b1 = 0.f, e_c = 1.f, e_s = 0.f;
+    bf16_t e_b0 = 0, e_b1 = 0;                       // as loaded (bf2f_late)
+    float e_c = 1.f, e_s = 0.f;
     auto epi_fetch = [&](int gg) {
         if (lane >= 2) return;
         const int head = gg / gph, gi = gg % gph;
         e_pos = *p.pos_ptr;
-        e_b0 = p.bqkv != nullptr ? bf2f(p.bqkv[rows_i[0]]) : 0.f;
-        e_b1 = p.bqkv != nullptr ? bf2f(p.bqkv[rows_i[1]]) : 0.f;
+        e_b0 = p.bqkv != nullptr ? p.bqkv[rows_i[0]] : (bf16_t)0;
+        e_b1 = p.bqkv != nullptr ? p.bqkv[rows_i[1]] : (bf16_t)0;
         if (head < p.nq + p.nkv) { e_c = p.rope_cs[gi]; e_s = p.rope_cs[half + gi]; }
     };
     auto finish = [&](int gg, float (&acc)[2]) {
@@ -315,8 +432,8 @@ __global__ __launch_bounds__(NT) void qkv_decode_kernel(QkvDecodeArgs p, int ncu
         const int head = gg / gph;
         const bool is_v = head >= p.nq + p.nkv;
         const int pos = e_pos;
-        const float lo = bfround(acc[0] + e_b0);
-        const float hi = bfround(acc[1] + e_b1);
+        const float lo = bfround(acc[0] + bf2f_late(e_b0));
+        const float hi = bfround(acc[1] + bf2f_late(e_b1));
         float out = lane ? hi : lo;
         if (!is_v) {
             const float c = e_c, sn = e_s;
@@ -334,8 +451,10 @@ __global__ __launch_bounds__(NT) void qkv_decode_kernel(QkvDecodeArgs p, int ncu
 
     Batch<2, U> b0;
     const bool has = g < n_groups;
-    if (has) { rows_of(g); load_batch<2, U>(rows, 0, lane, nch, b0); epi_fetch(g); }
-    stage_x<NT>(p.x, p.norm_w, p.eps, p.K, sx, scratch);
+    if (has) { rows_of(g); load_batch<2, U>(rows, 0, lane, nch, b0); epi_fetch(g); }   // weights in front (gemv_kernel: no gain from the inputs first)
+    STAGE_X_REGS(NT, st);
+    stage_x_issue<NT>(p.x, p.norm_w, p.K, STAGE_X_ARGS(st));
+    stage_x_finish<NT, true>(p.x, p.norm_w, p.eps, p.K, sx, scratch, STAGE_X_ARGS(st));   // LDS-only syncs: measured faster here (CHANGELOG)
     if (has) {
         float acc[2] = {0.f, 0.f};
         fma_batch<2, U>(b0, sx, 0, lane, nch, acc);

@@ -50,43 +50,96 @@ __device__ __forceinline__ void wave_amax(float& v, int& i) {
 // ---- activation staging -------------------------------------------------------------------------
 // stage x (optionally RMS-normalised with gain, HF rounding order) as bf16 into LDS, once per block of NT threads (NT = 256 x the blocks a CU
 // used to hold: one copy per CU instead of one per 256 threads).
+// Two halves, so that the caller can put its first weight batch between them (the ordering rule of the batch-1 decode kernels, DESIGN.md §4.3:
+// vector loads retire in order per wave, so everything the prologue needs is requested first, the weights behind it, and the prologue waits with
+// a counted vmcnt for its own loads alone while the weights are in flight):
+//   stage_x_issue  requests into registers, none depending on another and none predicated (a chunk index past the row is clamped to the row's last
+//                  chunk and its value dropped in the finish: straight-line code, so the waits count loads instead of draining them): x and the gain of this thread's chunks and, in the four summing waves,
+//                  their chunks of the sum of squares; without a norm, the thread's first PC chunks of x;
+//   stage_x_finish does the rest: sum of squares, sync, scaling, LDS writes, sync.
 // The sum of squares is formed by the FIRST FOUR waves alone, each thread over the chunks tid + 256 i in that order, then wave_sum, then
-// scratch[0] + ... + scratch[3]: the summation order of the 256-thread form, so the result does not depend on NT.  The other waves fetch their
-// share of x and of the gain meanwhile and join in the scaling and the LDS writes, which are element-wise.
-// Single pass for K <= 8192 (x kept in registers between the sum of squares and the scaling).
-template <int NT = 256>
-__device__ __forceinline__ void stage_x(const bf16_t* x, const bf16_t* __restrict__ norm_w, float eps, int K,
-                                        bf16_t* sx, float* scratch) {
+// scratch[0] + ... + scratch[3]: the summation order of the 256-thread form, so the result does not depend on NT.  The other waves join in the
+// scaling and the LDS writes, which are element-wise.
+// Single pass for K <= 8192 (x kept in registers between the sum of squares and the scaling); beyond, the first four chunks of the sum of squares
+// are requested up front and the rest of both passes follows in the finish.
+// The block sync of the staging: it publishes LDS and nothing else.  __syncthreads() is a workgroup fence over every address space, and on gfx950
+// the release half of that fence is s_waitcnt vmcnt(0): it would drain the weight batch that the ordering rule keeps in flight across the staging.
+__device__ __forceinline__ void sync_lds() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+}
+template <bool LDS_SYNC>
+__device__ __forceinline__ void stage_sync() {
+    if constexpr (LDS_SYNC) sync_lds(); else __syncthreads();
+}
+template <int NT>
+struct StageX {
     static_assert(NT % 256 == 0 && NT >= 256 && NT <= 1024, "stage_x: 4..16 waves");
-    const int tid = threadIdx.x, nch = K >> 3;
+    static constexpr int MAXC = 4;                          // chunks per thread of the four summing waves
+    static constexpr int SC = (256 * MAXC + NT - 1) / NT;   // chunks per thread in the scaling of the single-pass form
+    static constexpr int PC = MAXC + 1;                     // no norm: chunks per thread requested up front (K = 18944, NT = 512: all of x),
+                                                            // held in v[0 .. MAXC - 1] and t
+};
+// the registers between the two halves (separate arrays: as members of one struct some of them stayed in scratch)
+#define STAGE_X_REGS(NT, name) u32x4 name##_v[StageX<NT>::MAXC], name##_xs[StageX<NT>::SC], name##_gs[StageX<NT>::SC], name##_t
+#define STAGE_X_ARGS(name) name##_v, name##_xs, name##_gs, name##_t
+template <int NT>
+__device__ __forceinline__ void stage_x_issue(const bf16_t* x, const bf16_t* __restrict__ norm_w, int K, u32x4 (&v)[StageX<NT>::MAXC],
+                                              u32x4 (&xs)[StageX<NT>::SC], u32x4 (&gs)[StageX<NT>::SC], u32x4& t) {
+    using S = StageX<NT>;
+    const int tid = threadIdx.x, nch = K >> 3, last = nch - 1;
     if (norm_w == nullptr) {
-        // 4 independent 16-B loads in flight per thread and pass (K = 18944: 3 passes of 256 threads instead of 10 dependent round trips)
-        for (int c0 = tid; c0 < nch; c0 += NT * 4) {
-            u32x4 t[4];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) { const int c = c0 + NT * i; t[i] = (c < nch) ? *(const u32x4*)(x + c * 8) : (u32x4){0u, 0u, 0u, 0u}; }
-#pragma unroll
-            for (int i = 0; i < 4; ++i) { const int c = c0 + NT * i; if (c < nch) *(u32x4*)(sx + c * 8) = t[i]; }
-        }
-        __syncthreads();
+        for (int i = 0; i < S::PC; ++i) { const int c = tid + NT * i; (i < S::MAXC ? v[i] : t) = *(const u32x4*)(x + (c < nch ? c : last) * 8); }
         return;
     }
-    constexpr int MAXC = 4;                 // chunks per thread of the four summing waves
-    constexpr int SC = (256 * MAXC + NT - 1) / NT;   // chunks per thread in the scaling of the single-pass form
-    const bool small = nch <= 256 * MAXC;
-    u32x4 v[MAXC], xs[SC], gs[SC];
-    float s = 0.f;
+    const bool small = nch <= 256 * S::MAXC;
     if (tid < 256) {
-        if (small) {
 #pragma unroll
-            for (int i = 0; i < MAXC; ++i) {
-                const int c = tid + 256 * i;
-                v[i] = (c < nch) ? *(const u32x4*)(x + c * 8) : (u32x4){0u, 0u, 0u, 0u};
+        for (int i = 0; i < S::MAXC; ++i) { const int c = tid + 256 * i; v[i] = *(const u32x4*)(x + (c < nch ? c : last) * 8); }
+    }
+    if (small) {                           // every wave's share of x and of the gain
 #pragma unroll
-                for (int k = 0; k < 4; ++k) { const float a = lo_bf(v[i][k]), b = hi_bf(v[i][k]); s += a * a + b * b; }
-            }
-        } else {
-            for (int c = tid; c < nch; c += 256) {
+        for (int i = 0; i < S::SC; ++i) {
+            const int c = tid + NT * i < nch ? tid + NT * i : last;
+            if constexpr (NT != 256) xs[i] = *(const u32x4*)(x + c * 8);
+            gs[i] = *(const u32x4*)(norm_w + c * 8);
+        }
+    }
+}
+// LDS_SYNC: the block syncs are sync_lds() (callers with loads in flight that the staging must not drain); otherwise __syncthreads()
+template <int NT, bool LDS_SYNC>
+__device__ __forceinline__ void stage_x_finish(const bf16_t* x, const bf16_t* __restrict__ norm_w, float eps, int K, bf16_t* sx, float* scratch,
+                                               u32x4 (&v)[StageX<NT>::MAXC], u32x4 (&xs)[StageX<NT>::SC], u32x4 (&gs)[StageX<NT>::SC],
+                                               u32x4& t) {
+    using S = StageX<NT>;
+    const int tid = threadIdx.x, nch = K >> 3;
+    if (norm_w == nullptr) {
+#pragma unroll
+        for (int i = 0; i < S::PC; ++i) { const int c = tid + NT * i; if (c < nch) *(u32x4*)(sx + c * 8) = i < S::MAXC ? v[i] : t; }
+        // longer rows: 4 independent 16-B loads in flight per thread and pass
+        for (int c0 = tid + NT * S::PC; c0 < nch; c0 += NT * 4) {
+            u32x4 r[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) { const int c = c0 + NT * i; r[i] = (c < nch) ? *(const u32x4*)(x + c * 8) : (u32x4){0u, 0u, 0u, 0u}; }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) { const int c = c0 + NT * i; if (c < nch) *(u32x4*)(sx + c * 8) = r[i]; }
+        }
+        stage_sync<LDS_SYNC>();
+        return;
+    }
+    const bool small = nch <= 256 * S::MAXC;
+    if (tid < 256) {
+        float s = 0.f;
+#pragma unroll
+        for (int i = 0; i < S::MAXC; ++i) {
+            const u32x4 vi = (tid + 256 * i < nch) ? v[i] : (u32x4){0u, 0u, 0u, 0u};
+#pragma unroll
+            for (int k = 0; k < 4; ++k) { const float a = lo_bf(vi[k]), b = hi_bf(vi[k]); s += a * a + b * b; }
+        }
+        if (!small) {
+            for (int c = tid + 256 * S::MAXC; c < nch; c += 256) {
                 const u32x4 t = *(const u32x4*)(x + c * 8);
 #pragma unroll
                 for (int k = 0; k < 4; ++k) { const float a = lo_bf(t[k]), b = hi_bf(t[k]); s += a * a + b * b; }
@@ -97,23 +150,15 @@ __device__ __forceinline__ void stage_x(const bf16_t* x, const bf16_t* __restric
     }
     if constexpr (NT == 256) {
 #pragma unroll
-        for (int i = 0; i < SC; ++i) xs[i] = v[i];
-    } else if (small) {                    // every wave's share of x and of the gain, requested before the wait
-#pragma unroll
-        for (int i = 0; i < SC; ++i) {
-            const int c = tid + NT * i;
-            xs[i] = (c < nch) ? *(const u32x4*)(x + c * 8) : (u32x4){0u, 0u, 0u, 0u};
-            gs[i] = (c < nch) ? *(const u32x4*)(norm_w + c * 8) : (u32x4){0u, 0u, 0u, 0u};
-        }
+        for (int i = 0; i < S::SC; ++i) xs[i] = v[i];
     }
-    __syncthreads();
+    stage_sync<LDS_SYNC>();
     const float rstd = rsqrtf((scratch[0] + scratch[1] + scratch[2] + scratch[3]) / K + eps);
     if (small) {
 #pragma unroll
-        for (int i = 0; i < SC; ++i) {
+        for (int i = 0; i < S::SC; ++i) {
             const int c = tid + NT * i;
             if (c < nch) {
-                if constexpr (NT == 256) gs[i] = *(const u32x4*)(norm_w + c * 8);
                 u32x4 o;
 #pragma unroll
                 for (int k = 0; k < 4; ++k)
@@ -132,5 +177,5 @@ __device__ __forceinline__ void stage_x(const bf16_t* x, const bf16_t* __restric
             *(u32x4*)(sx + c * 8) = o;
         }
     }
-    __syncthreads();
+    stage_sync<LDS_SYNC>();
 }
