@@ -286,6 +286,13 @@ int vila_attn_decode_verify_bf16(const void* q, int64_t ldq, const void* kslot, 
                                  int n, int q_heads, int kv_heads, int max_ctx, float scale, void* workspace, size_t workspace_bytes,
                                  vila_stream_t stream);
 
+/* Causal attention with a key prefix, the append prefill's attention on its own: row i of q [T][ldq] (q_heads x 128 bf16) sits at position past + i
+ * and attends keys 0 .. past + i of ONE slot of one layer, kslot / vslot [kv_heads][max_ctx][128], whose rows past .. past + T - 1 hold the K / V of
+ * these same tokens; o [T][ldo] bf16.  past >= 0, T >= 1, past + T <= max_ctx <= 32768, q_heads % kv_heads == 0.  Rows of the slot at or beyond
+ * past + T are never read.  One launch; the block form follows vila_attn_force_append (vila_hip_tuning.h). */
+int vila_attn_append_bf16(const void* q, int64_t ldq, const void* kslot, const void* vslot, int past, int T, void* o, int64_t ldo,
+                          int q_heads, int kv_heads, int max_ctx, float scale, vila_stream_t stream);
+
 /* The batch-1 step's attention on its own (operator level): q [q_heads][128] bf16 attends keys 0 .. *pos of ONE slot of one layer, kslot / vslot
  * [kv_heads][max_ctx][128]; GQA groups of 1..8.  *pos must be below max_ctx: these kernels read *pos + 1 keys unguarded (the step's drivers refuse a
  * full cache before any launch).  The three forms of vila_llm_decode_step, launched as the step launches them:
@@ -557,6 +564,21 @@ int vila_llm_prefill_w4(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers /
                         const int32_t* cu_seqlens, int n_seq, int total_tokens, int max_seqlen, const int32_t* seq_of_tok, const VilaKvCache* cache,
                         const int32_t* last_rows, int n_last, float* last_logits, float* all_logits, void* final_hidden,
                         void* layer_hidden, void* workspace, size_t workspace_bytes, vila_stream_t stream);
+
+/* Prefill onto a live KV cache: T tokens of ONE sequence appended to `slot` of `cache`, which holds `past` positions.  The tokens take positions
+ * past .. past + T - 1, their K / V are written there (no other row of the cache is touched), and every row attends the slot's keys 0 .. its own
+ * position.  `past` is a host integer (a prefill is never graph-captured).  Outputs as vila_llm_prefill: last_rows / last_logits, final_hidden
+ * [T, hidden], layer_hidden [(n_layers+1), T, hidden], rows counted inside these T tokens.  head_dim 128 and q_heads * 128 == hidden;
+ * past + T <= cache->max_ctx; 0 <= slot < cache->n_slots; anything else is refused before a launch.  The _w4 form reads the five decoder
+ * projections from the int4 layers like vila_llm_prefill_w4. */
+size_t vila_llm_prefill_append_workspace_bytes(const VilaLlmShape* s, int T);
+size_t vila_llm_prefill_append_w4_workspace_bytes(const VilaLlmShape* s, int T);
+int vila_llm_prefill_append(const VilaLlmWeights* w, const void* embeds, int T, int past, int slot, const VilaKvCache* cache,
+                            const int32_t* last_rows, int n_last, float* last_logits, void* final_hidden, void* layer_hidden,
+                            void* workspace, size_t workspace_bytes, vila_stream_t stream);
+int vila_llm_prefill_append_w4(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers /*[host]*/, const void* embeds, int T, int past, int slot,
+                               const VilaKvCache* cache, const int32_t* last_rows, int n_last, float* last_logits, void* final_hidden,
+                               void* layer_hidden, void* workspace, size_t workspace_bytes, vila_stream_t stream);
 
 #ifdef __cplusplus
 }

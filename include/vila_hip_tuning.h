@@ -50,6 +50,11 @@ void vila_prefill_force_fusions(int qkv_rope, int oproj_norm);
 void vila_attn_force_fwd(int form);
 /* the form (1..5 as above) the automatic policy launches for this grid on the current device; host only, launches nothing */
 int vila_attn_fwd_form(int n_seq, int max_seqlen, int n_q_heads);
+/* test hook of the append prefill's attention (vila_attn_append_bf16, vila_llm_prefill_append): 0 = automatic (the forward's policy for one sequence
+ * of T rows), 1..4 = forms A..D as above whatever the grid (the round-2 kernel has no key-prefix mode) */
+void vila_attn_force_append(int form);
+/* the form (1..4) the automatic policy launches for an append of T rows on the current device; host only, launches nothing */
+int vila_attn_append_form(int T, int n_q_heads);
 /* test hook of the attention backward's dQ and dK / dV passes: 0 = VILA_ATTN_BWD from the environment (default: DMA), 1 = the round-1/2 kernels
  * of attn_bwd.hip (VILA_ATTN_BWD=v1), 2 = the DMA-ring kernels of attn_bwd_dma.hip */
 void vila_attn_force_bwd(int impl);

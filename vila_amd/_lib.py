@@ -138,6 +138,15 @@ PROTOTYPES = {
     "vila_attn_decode_verify_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "vila_attn_decode_verify_bf16": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_float, c_void_p,
                                              c_size_t, c_void_p]),
+    "vila_attn_append_bf16": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_int, c_int, c_int, c_float, c_void_p]),
+    "vila_attn_force_append": (None, [c_int]),
+    "vila_attn_append_form": (c_int, [c_int, c_int]),
+    "vila_llm_prefill_append_workspace_bytes": (c_size_t, [C.POINTER(VilaLlmShape), c_int]),
+    "vila_llm_prefill_append_w4_workspace_bytes": (c_size_t, [C.POINTER(VilaLlmShape), c_int]),
+    "vila_llm_prefill_append": (c_int, [C.POINTER(VilaLlmWeights), c_void_p, c_int, c_int, c_int, C.POINTER(VilaKvCache), c_void_p, c_int, c_void_p,
+                                        c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "vila_llm_prefill_append_w4": (c_int, [C.POINTER(VilaLlmWeights), C.POINTER(VilaLlmLayerW4), c_void_p, c_int, c_int, c_int, C.POINTER(VilaKvCache),
+                                           c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "vila_attn_decode_workspace_bytes": (c_size_t, [c_int, c_int]),
     "vila_attn_decode_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p, c_size_t, c_void_p]),
     "vila_attn_decode_oproj_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float,

@@ -341,18 +341,29 @@ static int proj_gemv(const GemvArgs& g, bool w4, const void* wq, const void* wsz
 // in their split-K reduce and say so through rope_done / ln2_done / ln1_done.  ql != nullptr (vila_llm_prefill_w4): the five decoder
 // projections read from the int4 layers (gemm_w4.hip), so a quantised model runs from its int4 weights alone; those GEMMs take no follow-up,
 // so the standalone rmsnorm / rope_kv kernels run instead.
+// ap != nullptr (vila_llm_prefill_append / _w4): the T tokens are ONE sequence continuing slot ap->slot of the cache at position ap->past.  The
+// positions and the slot of every token are then made here (two int32 arrays at the end of the workspace) and the attention reads its keys and
+// values from the slot (launch_attn_append) instead of the q/k/v buffer; everything else is the loop below as it stands.
+struct PrefillAppend { int past, slot; };
+static size_t prefill_append_extra(int T) { return 2 * align_up((size_t)T * 4, 256) + 512; }
+extern "C" size_t vila_llm_prefill_append_workspace_bytes(const VilaLlmShape* s, int T) {
+    return vila_llm_prefill_workspace_bytes(s, T) + prefill_append_extra(T);
+}
+extern "C" size_t vila_llm_prefill_append_w4_workspace_bytes(const VilaLlmShape* s, int T) {
+    return vila_llm_prefill_w4_workspace_bytes(s, T) + prefill_append_extra(T);
+}
 static int llm_prefill_impl(const VilaLlmWeights* w, const VilaLlmLayerW4* ql, const void* embeds, const int32_t* positions,
                             const int32_t* cu_seqlens, int n_seq, int T, int max_seqlen, const int32_t* seq_of_tok, const VilaKvCache* cache,
                             const int32_t* last_rows, int n_last, float* last_logits, float* all_logits, void* final_hidden,
-                            void* layer_hidden, void* workspace, size_t workspace_bytes, vila_stream_t stream) {
+                            void* layer_hidden, void* workspace, size_t workspace_bytes, vila_stream_t stream, const PrefillAppend* ap = nullptr) {
     const VilaLlmShape& sh = w->shape;
     hipStream_t s = S(stream);
     const bool w4 = ql != nullptr;
-    const char* fn = w4 ? "llm_prefill_w4" : "llm_prefill";
+    const char* fn = ap ? (w4 ? "llm_prefill_append_w4" : "llm_prefill_append") : (w4 ? "llm_prefill_w4" : "llm_prefill");
     VILA_REQUIRE(T > 0 && n_seq > 0, "%s: empty input", fn);
     VILA_REQUIRE(sh.q_heads % sh.kv_heads == 0, "llm: q heads must be a multiple of kv heads");
     VILA_REQUIRE(cu_seqlens != nullptr || n_seq == 1, "%s: n_seq > 1 needs cu_seqlens", fn);
-    VILA_REQUIRE(workspace_bytes >= (w4 ? vila_llm_prefill_w4_workspace_bytes(&sh, T) : vila_llm_prefill_workspace_bytes(&sh, T)),
+    VILA_REQUIRE(workspace_bytes >= (w4 ? vila_llm_prefill_w4_workspace_bytes(&sh, T) : vila_llm_prefill_workspace_bytes(&sh, T)) + (ap ? prefill_append_extra(T) : 0),
                  "%s: workspace too small", fn);
     const int H = sh.hidden, F = sh.inter, hd = sh.head_dim, QS = sh.q_heads * hd, KS = sh.kv_heads * hd, QKV = QS + 2 * KS;
     VILA_REQUIRE(QS == H, "llm: q_heads*head_dim (%d) must equal hidden (%d) for the in-place attention buffer", QS, H);
@@ -368,6 +379,13 @@ static int llm_prefill_impl(const VilaLlmWeights* w, const VilaLlmLayerW4* ql, c
     float* skws = w4 ? nullptr : a.take<float>(skws_bytes / 4);
     const size_t gws_bytes = w4 ? prefill_w4_gemm_ws(sh, T) : 0;     // the W4A16 GEMMs' slabs
     char* gws = w4 ? a.take<char>(gws_bytes) : nullptr;
+    if (ap != nullptr) {
+        int32_t* apos = a.take<int32_t>((size_t)T);
+        int32_t* aseq = a.take<int32_t>((size_t)T);
+        VILA_REQUIRE(a.ok(), "%s: workspace arena overflow", fn);
+        VILA_TRY(launch_append_index(apos, aseq, ap->past, ap->slot, T, s));
+        positions = apos; seq_of_tok = aseq;
+    }
     VILA_REQUIRE(a.ok(), "%s: workspace arena overflow", fn);
     if (cache != nullptr) VILA_REQUIRE(max_seqlen <= cache->max_ctx, "%s: sequence (%d) longer than the KV cache (%d)", fn, max_seqlen, cache->max_ctx);
 
@@ -421,7 +439,12 @@ static int llm_prefill_impl(const VilaLlmWeights* w, const VilaLlmLayerW4* ql, c
         at.cu_seqlens = cu_seqlens; at.n_seq = n_seq; at.total_tokens = T; at.max_seqlen = (cu_seqlens ? max_seqlen : T);
         at.n_q_heads = sh.q_heads; at.n_kv_heads = sh.kv_heads; at.head_dim = hd; at.causal = 1;
         at.scale = 1.0f / sqrtf((float)hd); at.lse = nullptr;
-        VILA_TRY(launch_attn_fwd(at, s));
+        if (ap != nullptr) {
+            const size_t slot_off = (size_t)ap->slot * sh.kv_heads * max_ctx * hd;
+            VILA_TRY(launch_attn_append(qkv, QKV, kc + slot_off, vc + slot_off, ap->past, T, h, QS, sh.q_heads, sh.kv_heads, max_ctx, at.scale, s));
+        } else {
+            VILA_TRY(launch_attn_fwd(at, s));
+        }
         if (l == sh.n_layers - 1 && prune_last) {
             // Generation prefill: after the last layer's K / V are in the cache only the rows whose logits are asked for feed anything.
             // Their o_proj, post-attention norm and MLP run as three decode GEMVs per row (weights stream once at HBM rate) instead of
@@ -505,6 +528,36 @@ extern "C" int vila_llm_prefill_w4(const VilaLlmWeights* w, const VilaLlmLayerW4
     VILA_REQUIRE(ql != nullptr, "llm_prefill_w4: the int4 layers are NULL");
     return llm_prefill_impl(w, ql, embeds, positions, cu_seqlens, n_seq, T, max_seqlen, seq_of_tok, cache, last_rows, n_last, last_logits,
                             all_logits, final_hidden, layer_hidden, workspace, workspace_bytes, stream);
+}
+
+// The append prefill: T tokens of ONE sequence continue slot `slot` of the cache, which holds `past` positions.
+static int llm_prefill_append(const VilaLlmWeights* w, const VilaLlmLayerW4* ql, const void* embeds, int T, int past, int slot, const VilaKvCache* cache,
+                              const int32_t* last_rows, int n_last, float* last_logits, void* final_hidden, void* layer_hidden, void* workspace,
+                              size_t workspace_bytes, vila_stream_t stream) {
+    const char* fn = ql ? "llm_prefill_append_w4" : "llm_prefill_append";
+    VILA_REQUIRE(w != nullptr && embeds != nullptr && cache != nullptr && cache->k != nullptr && cache->v != nullptr, "%s: weights, embeds and cache must be given", fn);
+    const VilaLlmShape& sh = w->shape;
+    VILA_REQUIRE(T >= 1 && past >= 0, "%s: T (%d) must be >= 1 and past (%d) >= 0", fn, T, past);
+    VILA_REQUIRE((int64_t)past + T <= cache->max_ctx, "%s: past + T (%d + %d) exceeds the KV cache (%d positions)", fn, past, T, cache->max_ctx);
+    VILA_REQUIRE(slot >= 0 && slot < cache->n_slots, "%s: slot %d outside the cache's %d slots", fn, slot, cache->n_slots);
+    VILA_REQUIRE(sh.head_dim == 128, "%s: head_dim 128 only (got %d)", fn, sh.head_dim);
+    VILA_REQUIRE(sh.q_heads * sh.head_dim == sh.hidden, "%s: q_heads*head_dim (%d) must equal hidden (%d)", fn, sh.q_heads * sh.head_dim, sh.hidden);
+    const PrefillAppend ap{past, slot};
+    return llm_prefill_impl(w, ql, embeds, nullptr, nullptr, 1, T, T, nullptr, cache, last_rows, n_last, last_logits, nullptr, final_hidden, layer_hidden,
+                            workspace, workspace_bytes, stream, &ap);
+}
+extern "C" int vila_llm_prefill_append(const VilaLlmWeights* w, const void* embeds, int T, int past, int slot, const VilaKvCache* cache,
+                                       const int32_t* last_rows, int n_last, float* last_logits, void* final_hidden, void* layer_hidden,
+                                       void* workspace, size_t workspace_bytes, vila_stream_t stream) {
+    return llm_prefill_append(w, nullptr, embeds, T, past, slot, cache, last_rows, n_last, last_logits, final_hidden, layer_hidden, workspace,
+                              workspace_bytes, stream);
+}
+extern "C" int vila_llm_prefill_append_w4(const VilaLlmWeights* w, const VilaLlmLayerW4* ql, const void* embeds, int T, int past, int slot,
+                                          const VilaKvCache* cache, const int32_t* last_rows, int n_last, float* last_logits, void* final_hidden,
+                                          void* layer_hidden, void* workspace, size_t workspace_bytes, vila_stream_t stream) {
+    VILA_REQUIRE(ql != nullptr, "llm_prefill_append_w4: the int4 layers are NULL");
+    return llm_prefill_append(w, ql, embeds, T, past, slot, cache, last_rows, n_last, last_logits, final_hidden, layer_hidden, workspace,
+                              workspace_bytes, stream);
 }
 
 // =================================================================================================
@@ -789,6 +842,12 @@ extern "C" int vila_prompt_lookup_draft(const int64_t* hist, const int32_t* n_hi
     return launch_verify_draft(hist, n_hist, max_ngram, nullptr, nullptr, nullptr, n, token, n_draft, nullptr, nullptr, S(stream));
 }
 extern "C" size_t vila_attn_decode_verify_workspace_bytes(int n, int q_heads, int max_ctx) { return bverify_attn_workspace_bytes(n, q_heads, max_ctx); }
+// the append prefill's attention on its own (attn.hip launch_attn_append)
+extern "C" int vila_attn_append_bf16(const void* q, int64_t ldq, const void* kslot, const void* vslot, int past, int T, void* o, int64_t ldo, int q_heads,
+                                     int kv_heads, int max_ctx, float scale, vila_stream_t stream) {
+    VILA_REQUIRE(q != nullptr && kslot != nullptr && vslot != nullptr && o != nullptr, "attn_append: NULL pointer");
+    return launch_attn_append(B(q), ldq, B(kslot), B(vslot), past, T, B(o), ldo, q_heads, kv_heads, max_ctx, scale, S(stream));
+}
 extern "C" int vila_attn_decode_verify_bf16(const void* q, int64_t ldq, const void* kslot, const void* vslot, const int32_t* pos, void* o, int64_t ldo, int n,
                                             int q_heads, int kv_heads, int max_ctx, float scale, void* workspace, size_t workspace_bytes,
                                             vila_stream_t stream) {

@@ -300,9 +300,17 @@ template <int N, int cnt> __device__ __forceinline__ void pv_retire(u32x2 (&v)[4
 // CU walking <= 13 (16) dependent tiles, and with 16 rows per wave (QF = 1, taken to keep 196 blocks) each of the 8 waves reads the whole
 // 32-KB K / V stage per tile: 256 KB of LDS reads = 2048 cycles per tile for 512 cycles of MFMA.  32 rows per wave halve the LDS bytes per
 // row, the key split keeps the block at 128 rows: the same grid, half the dependent steps.
-template <int HD, int QF, bool CAUSAL, int KS = 1>
-__global__ __launch_bounds__(512, 2) void attn_fwd_kernel(AttnArgs p, int nqb) {
+//
+// PFX (append prefill, launch_attn_append): the T queries sit at positions past .. past + T - 1 of ONE sequence whose keys 0 .. past + T - 1 lie
+// in a cache slot (p.k / p.v = the slot, token stride 128, head stride max_ctx * 128).  Row i sees keys 0 .. past + i.  Tiles stay aligned to
+// key 0, so a row walks the tiles the one-shot prefill gives the row at the same position; a block's last tile is the one of its last row's
+// own key, the mask is key <= past + row, and no tile request reaches past key past + T - 1 (the slot's rows beyond hold anything).  The
+// prefix rides in a struct of its own behind AttnArgs, so the kernel arguments of the other instantiations are what they were.
+struct AttnAppendArgs : AttnArgs { int past; };
+template <int HD, int QF, bool CAUSAL, int KS = 1, bool PFX = false>
+__global__ __launch_bounds__(512, 2) void attn_fwd_kernel(std::conditional_t<PFX, AttnAppendArgs, AttnArgs> p, int nqb) {
     using C = AttnDma<HD>;
+    static_assert(!PFX || (CAUSAL && HD == 128), "the key prefix: causal, head dim 128");
     constexpr int KK = C::KK, DN = C::DN, CH = C::CH, CHP = C::CHP, ROWB = C::ROWB, KT = C::KT, NST = C::NST, P = C::P, PW = C::PW;
     static_assert(KS == 1 || KS == 2, "key split: 1 or 2");
     constexpr int WQ = 8 / KS;                     // query groups (waves per key group)
@@ -329,6 +337,10 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_kernel(AttnArgs p, int nqb) {
 
     int kv_end = seqlen;
     if (CAUSAL) { const int lim = qb0 + BQ; kv_end = lim < seqlen ? lim : seqlen; }
+    // (the statements of the prefix mode stand beside the ones they replace, under `if constexpr`: folded into shared expressions with a zero
+    // prefix they reordered the other instantiations' instructions)
+    int past = 0, kvlen = seqlen;                            // keys in front of query row 0; keys of the sequence
+    if constexpr (PFX) { past = p.past; kvlen = past + seqlen; kv_end += past; }
     const int ntiles = (kv_end + KT - 1) / KT;
     const bf16_t* kbase = p.k + (int64_t)tok0 * p.k_tok_stride + kvh * p.k_head_stride;
     const bf16_t* vbase = p.v + (int64_t)tok0 * p.v_tok_stride + kvh * p.v_head_stride;
@@ -355,6 +367,8 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_kernel(AttnArgs p, int nqb) {
 #pragma unroll
         for (int i = 0; i < P; ++i) {
             int key = key0 + drow[i];
+            if constexpr (PFX) key = key < kvlen ? key : kvlen - 1;   // never a row at or beyond past + T of the slot
+            else
             key = key < seqlen ? key : seqlen - 1;            // rows past the sequence: any valid row (masked in the softmax)
             char* dst = smem + st * C::STAGE + (wave * PW + i * 64) * 16;
             if (dact[i]) __builtin_amdgcn_global_load_lds((gbl_void_t*)(dsrc[i] + (int64_t)key * dstr[i]), (lds_void_t*)dst, 16, 0, 0);
@@ -442,7 +456,11 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_kernel(AttnArgs p, int nqb) {
         asm volatile("" ::: "memory");
         const int t = st * KS + ksp;
         const int key0 = t * KT;
-        const bool active = wave_has_rows && t < ntiles && !(CAUSAL && key0 > qw_last);   // else nothing of this tile is visible to this wave's rows
+        bool active_;
+        if constexpr (PFX) active_ = wave_has_rows && t < ntiles && key0 <= past + qw_last;
+        else
+        active_ = wave_has_rows && t < ntiles && !(CAUSAL && key0 > qw_last);   // else nothing of this tile is visible to this wave's rows
+        const bool active = active_;
         const char* cK = smem + ((t < ntiles ? t : 0) % NST) * C::STAGE;
         v_lds = lds_addr(cK + C::IMG);
 
@@ -489,6 +507,20 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_kernel(AttnArgs p, int nqb) {
         if (!active) continue;
 
         // ---- mask (sequence end / causal diagonal) ----
+        if constexpr (PFX) {
+            // keys at or beyond past + T lie behind every row's own key, so the causal test covers the sequence end as well
+            if (key0 + KT - 1 > past + qw0) {
+#pragma unroll
+                for (int f = 0; f < QF; ++f) {
+                    const int qpos = past + qw0 + f * 16 + l15;
+#pragma unroll
+                    for (int jn = 0; jn < 4; ++jn)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r)
+                            if (key0 + jn * 16 + lg * 4 + r > qpos) sacc[jn][f][r] = NEG_BIG;
+                }
+            }
+        } else {
         const bool need_mask = (key0 + KT > seqlen) || (CAUSAL && (key0 + KT - 1 > qw0));
         if (need_mask) {
 #pragma unroll
@@ -503,6 +535,7 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_kernel(AttnArgs p, int nqb) {
                         if (!ok) sacc[jn][f][r] = NEG_BIG;
                     }
             }
+        }
         }
 
         if constexpr (!TIGHT) pv_issue(std::integral_constant<int, 0>{});       // the first V^T group travels while the softmax runs
@@ -520,7 +553,14 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_kernel(AttnArgs p, int nqb) {
             mx = xor32_max(mx);
             const float m_new = fmaxf(m_run[f], mx);
             const float alpha = __builtin_amdgcn_exp2f((m_run[f] - m_new) * c);   // raw v_exp_f32: arguments are <= 0
-            const float mc = m_new * c;
+            float mc_;
+            // (prefix mode: a row that has met only masked keys so far — the odd-tile key group of a row below position 64 — gets weights
+            // exp2(NEG_BIG * c - 0) = 0 at any scale; NEG_BIG * c - round(NEG_BIG * c) is the product's rounding residue, +-1e21, whose sign
+            // depends on the caller's scale)
+            if constexpr (PFX) mc_ = (m_new > NEG_BIG ? m_new : 0.f) * c;
+            else
+            mc_ = m_new * c;
+            const float mc = mc_;
             m_run[f] = m_new;
             float ps = 0.f;
             float pv[4][4];
@@ -654,8 +694,8 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_kernel(AttnArgs p, int nqb) {
     }
 }
 
-template <int HD, bool CAUSAL, int QF, int KS = 1>
-static int launch_attn_q(const AttnArgs& a, hipStream_t s) {
+template <int HD, bool CAUSAL, int QF, int KS = 1, bool PFX = false>
+static int launch_attn_q(const std::conditional_t<PFX, AttnAppendArgs, AttnArgs>& a, hipStream_t s) {
     using C = AttnDma<HD>;
     constexpr int WQ = 8 / KS;
     const size_t ring = (size_t)C::NST * C::STAGE;
@@ -663,13 +703,13 @@ static int launch_attn_q(const AttnArgs& a, hipStream_t s) {
     const size_t lds = ring > ost ? ring : ost;
     static bool attr_set = false;
     if (!attr_set) {
-        VILA_HIP(hipFuncSetAttribute((const void*)attn_fwd_kernel<HD, QF, CAUSAL, KS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        VILA_HIP(hipFuncSetAttribute((const void*)attn_fwd_kernel<HD, QF, CAUSAL, KS, PFX>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         attr_set = true;
     }
     const int nqb = cdiv(a.max_seqlen, WQ * QF * 16);
     const int64_t blocks = (int64_t)nqb * a.n_q_heads * a.n_seq;
     VILA_REQUIRE(blocks < (1ll << 31), "attn: grid too large");
-    hipLaunchKernelGGL((attn_fwd_kernel<HD, QF, CAUSAL, KS>), dim3((unsigned)blocks), dim3(512), lds, s, a, nqb);
+    hipLaunchKernelGGL((attn_fwd_kernel<HD, QF, CAUSAL, KS, PFX>), dim3((unsigned)blocks), dim3(512), lds, s, a, nqb);
     VILA_LAUNCH_CHECK();
     return 0;
 }
@@ -744,4 +784,55 @@ int launch_attn_fwd(const AttnArgs& a, hipStream_t s) {
     if (a.head_dim == 72) return a.causal ? launch_attn_t<72, true>(a, form, s) : launch_attn_t<72, false>(a, form, s);
     if (a.head_dim == 64) return a.causal ? launch_attn_t<64, true>(a, form, s) : launch_attn_t<64, false>(a, form, s);
     VILA_FAIL(-1, "attn: unsupported head_dim %d (supported: 64, 72, 128)", a.head_dim);
+}
+
+// ---- append prefill: causal attention whose keys start `past` positions before its queries (attn_fwd_kernel<128, QF, true, KS, true>) ----
+// The forms are A..D of the forward (the round-2 kernel has no prefix mode: where VILA_ATTN_FWD=v1 would select it the policy is asked as if it
+// were unset).  vila_attn_force_append (vila_hip_tuning.h): 0 = automatic = attn_auto_form(1, T, q_heads), 1..4 = that form whatever the grid.
+static int g_attn_force_append = ATTN_FORM_AUTO;
+extern "C" void vila_attn_force_append(int form) { g_attn_force_append = form; }
+static int attn_append_auto_form(int T, int n_q_heads) {
+    const int f = attn_auto_form(1, T, n_q_heads);
+    if (f != ATTN_FORM_V1) return f;
+    if ((int64_t)cdiv(T, 256) * n_q_heads >= 512) return ATTN_FORM_A;
+    return (int64_t)cdiv(T, 64) * n_q_heads <= attn_cu_count() ? ATTN_FORM_B : ATTN_FORM_C;
+}
+extern "C" int vila_attn_append_form(int T, int n_q_heads) { return attn_append_auto_form(T, n_q_heads); }
+
+int launch_attn_append(const bf16_t* q, int64_t ldq, const bf16_t* kslot, const bf16_t* vslot, int past, int T, bf16_t* o, int64_t ldo, int q_heads,
+                       int kv_heads, int max_ctx, float scale, hipStream_t s) {
+    VILA_REQUIRE(T >= 1 && past >= 0, "attn_append: T (%d) must be >= 1 and past (%d) >= 0", T, past);
+    VILA_REQUIRE(max_ctx >= 1 && max_ctx <= BDEC_MAX_CTX, "attn_append: caches of 1..%d positions (got %d)", BDEC_MAX_CTX, max_ctx);
+    VILA_REQUIRE((int64_t)past + T <= max_ctx, "attn_append: past + T (%d + %d) exceeds the slot's %d positions", past, T, max_ctx);
+    VILA_REQUIRE(q_heads >= 1 && kv_heads >= 1 && q_heads % kv_heads == 0, "attn_append: q heads (%d) must be a multiple of kv heads (%d)", q_heads, kv_heads);
+    VILA_REQUIRE(ldq >= (int64_t)q_heads * 128 && ldo >= (int64_t)q_heads * 128 && ldq % 8 == 0 && ldo % 8 == 0,
+                 "attn_append: row strides (q %lld, o %lld) must hold %d heads of 128 and keep 16-B alignment", (long long)ldq, (long long)ldo, q_heads);
+    VILA_REQUIRE((uintptr_t)q % 16 == 0 && (uintptr_t)kslot % 16 == 0 && (uintptr_t)vslot % 16 == 0 && (uintptr_t)o % 16 == 0, "attn_append: pointer alignment");
+    VILA_REQUIRE(g_attn_force_append >= ATTN_FORM_AUTO && g_attn_force_append <= ATTN_FORM_D, "attn_append: forced form %d (0 = automatic, 1..4)",
+                 g_attn_force_append);
+    AttnAppendArgs a{};
+    a.q = q; a.k = kslot; a.v = vslot; a.o = o;
+    a.q_tok_stride = ldq; a.o_tok_stride = ldo; a.k_tok_stride = a.v_tok_stride = 128;
+    a.q_head_stride = a.o_head_stride = 128; a.k_head_stride = a.v_head_stride = max_ctx * 128;
+    a.cu_seqlens = nullptr; a.n_seq = 1; a.total_tokens = T; a.max_seqlen = T;
+    a.n_q_heads = q_heads; a.n_kv_heads = kv_heads; a.head_dim = 128; a.causal = 1; a.scale = scale; a.lse = nullptr;
+    a.past = past;
+    const int form = g_attn_force_append != ATTN_FORM_AUTO ? g_attn_force_append : attn_append_auto_form(T, q_heads);
+    switch (form) {
+        case ATTN_FORM_A: return launch_attn_q<128, true, 2, 1, true>(a, s);
+        case ATTN_FORM_B: return launch_attn_q<128, true, 1, 2, true>(a, s);
+        case ATTN_FORM_C: return launch_attn_q<128, true, 2, 2, true>(a, s);
+        default: return launch_attn_q<128, true, 1, 1, true>(a, s);
+    }
+}
+
+// positions past .. past + T - 1 and the slot of every token, for the RoPE table and the K / V scatter of an append prefill
+__global__ void append_index_kernel(int32_t* __restrict__ pos, int32_t* __restrict__ seq_of_tok, int past, int slot, int T) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < T) { pos[i] = past + i; seq_of_tok[i] = slot; }
+}
+int launch_append_index(int32_t* pos, int32_t* seq_of_tok, int past, int slot, int T, hipStream_t s) {
+    hipLaunchKernelGGL(append_index_kernel, dim3(cdiv(T, 256)), dim3(256), 0, s, pos, seq_of_tok, past, slot, T);
+    VILA_LAUNCH_CHECK();
+    return 0;
 }

@@ -100,6 +100,12 @@ struct AttnArgs {
     float* lse;                  // optional [n_q_heads][total_tokens] fp32 (natural-log LSE) for backward
 };
 int launch_attn_fwd(const AttnArgs& a, hipStream_t s);
+// causal attention with a key prefix (append prefill): q [T][ldq] at positions past .. past + T - 1, keys / values = ONE cache slot of one layer
+// [kv_heads][max_ctx][128]; row i attends keys 0 .. past + i and nothing at or beyond past + T is read; o [T][ldo]
+int launch_attn_append(const bf16_t* q, int64_t ldq, const bf16_t* kslot, const bf16_t* vslot, int past, int T, bf16_t* o, int64_t ldo, int q_heads,
+                       int kv_heads, int max_ctx, float scale, hipStream_t s);
+// pos[i] = past + i, seq_of_tok[i] = slot for i < T
+int launch_append_index(int32_t* pos, int32_t* seq_of_tok, int past, int slot, int T, hipStream_t s);
 
 // ---- decode (gemv.hip; the attention: attn_decode.hip, shared device pieces and constants in attn_decode.h) ----
 struct GemvArgs {

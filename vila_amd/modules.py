@@ -455,6 +455,44 @@ class HipQwen2ForCausalLM(_HipModule):
             check(lib.vila_llm_prefill(C.byref(w), *args), "vila_llm_prefill")
         return SimpleNamespace(last_logits=last_logits, all_logits=all_logits, final_hidden=final_hidden, layer_hidden=layer_hidden)
 
+    # ---- prefill onto a live cache ----------------------------------------------------------------------------
+    @torch.no_grad()
+    def prefill_append(self, embeds: torch.Tensor, cache, past: int, slot: int = 0, last_rows: Optional[torch.Tensor] = None,
+                       want_final_hidden: bool = False, want_layer_hidden: bool = False):
+        """embeds [T,H] bf16: T tokens of ONE sequence appended to `slot` of `cache`, which holds `past` positions.  They take positions
+        past .. past + T - 1, their K/V are written there and every row attends the slot's keys 0 .. its own position.  last_rows counts rows
+        inside these T tokens.  Returns the namespace of `prefill_packed` (all_logits is None).  The W4 route is taken as there."""
+        ops._need(embeds, name="inputs_embeds")
+        c = self.lcfg
+        if embeds.dim() != 2 or embeds.shape[1] != c.hidden_size:
+            raise ValueError(f"prefill_append: embeds must be [T, {c.hidden_size}] (got {tuple(embeds.shape)})")
+        T, past, slot = embeds.shape[0], int(past), int(slot)
+        if cache is None:
+            raise ValueError("prefill_append: a KV cache that holds the sequence's first `past` positions is required")
+        if T < 1 or past < 0 or past + T > cache.max_ctx:
+            raise ValueError(f"prefill_append: past ({past}) + T ({T}) must fit the KV cache ({cache.max_ctx} positions), T >= 1, past >= 0")
+        if not 0 <= slot < cache.n_slots:
+            raise ValueError(f"prefill_append: slot {slot} outside the cache's {cache.n_slots} slots")
+        dev = embeds.device
+        lib = _lib.load()
+        w = self._struct()
+        w4 = self._w4 if self._w4_prefill else None
+        if w4 is None:
+            self._require_bf16("the bf16 prefill")
+        ws_bytes = (lib.vila_llm_prefill_append_w4_workspace_bytes if w4 is not None else lib.vila_llm_prefill_append_workspace_bytes)(C.byref(w.shape), T)
+        ws = self._workspace(ws_bytes, dev)
+        n_last = 0 if last_rows is None else last_rows.numel()
+        last_logits = torch.empty((n_last, c.vocab_size), device=dev, dtype=torch.float32) if n_last else None
+        final_hidden = torch.empty((T, c.hidden_size), device=dev, dtype=self.dtype) if want_final_hidden else None
+        layer_hidden = torch.empty((c.num_hidden_layers + 1, T, c.hidden_size), device=dev, dtype=self.dtype) if want_layer_hidden else None
+        args = (embeds.contiguous().data_ptr(), T, past, slot, C.byref(cache.c), ops._p(last_rows), n_last, ops._p(last_logits), ops._p(final_hidden),
+                ops._p(layer_hidden), ws.data_ptr(), ws.numel(), ops._stream())
+        if w4 is not None:
+            check(lib.vila_llm_prefill_append_w4(C.byref(w), w4.ptr, *args), "vila_llm_prefill_append_w4")
+        else:
+            check(lib.vila_llm_prefill_append(C.byref(w), *args), "vila_llm_prefill_append")
+        return SimpleNamespace(last_logits=last_logits, all_logits=None, final_hidden=final_hidden, layer_hidden=layer_hidden)
+
     # ---- HF-style forward (inference logits / loss; no autograd here: training goes through vila_amd.train) ----
     @torch.no_grad()
     def forward(self, input_ids=None, inputs_embeds: Optional[torch.Tensor] = None, attention_mask: Optional[torch.Tensor] = None,
@@ -897,7 +935,8 @@ class HipQwen2ForCausalLM(_HipModule):
                  use_graph: bool = True, return_logits: bool = False, forced_ids: Optional[torch.Tensor] = None, cache=None,
                  max_length: Optional[int] = None, streamer=None, batch_sample: Optional[bool] = None,
                  prompt_lookup_num_tokens: Optional[int] = None, max_matching_ngram_size: Optional[int] = None,
-                 prompt_ids: Optional[torch.Tensor] = None, draft_ids: Optional[torch.Tensor] = None, **kw):
+                 prompt_ids: Optional[torch.Tensor] = None, draft_ids: Optional[torch.Tensor] = None, past_len: Optional[int] = None,
+                 prefill_chunk: Optional[int] = None, **kw):
         """`llm.generate(inputs_embeds=, attention_mask=, **generation_kwargs)` as called at llava_arch.py:833 (HF semantics: returns ONLY the
         new tokens, [B, n_new]).  Greedy search or sampling (do_sample: temperature / top_k / top_p, HF order, on the device); explicit
         keyword arguments override `generation_config` (HF GenerationConfig-like: do_sample, temperature, top_k, top_p, max_new_tokens,
@@ -915,7 +954,13 @@ class HipQwen2ForCausalLM(_HipModule):
         draft_ids (LongTensor: a predicted output, token for token) replaces the lookup, with k = 7 unless given.  Batch 1 and greedy only;
         forced_ids and return_logits are not served in this mode.
         streamer = HF's `generate(streamer=...)` contract (what server.py:243 streams from): `put(LongTensor[1])` once per new token — the EOS
-        included, nothing for a prompt given as embeddings — as the host learns of them (every 16 graph replays), then `end()`; batch size 1."""
+        included, nothing for a prompt given as embeddings — as the host learns of them (every 16 graph replays), then `end()`; batch size 1.
+        past_len=P with cache=c (both required together; batch size 1): slot 0 of `c` already holds the K/V of the sequence's first P positions
+        (a previous generate on it), inputs_embeds holds only the NEW tokens, which are appended at P (`prefill_append`), and decoding goes on
+        from P + S.  After n returned tokens the cache holds P + S + n - 1 valid positions: the last token was never fed.
+        prefill_chunk=C (batch size 1): a prompt longer than C is fed as the usual prefill of its first C tokens and `prefill_append` calls of
+        at most C, logits only from the last, so the prefill workspace is that of C tokens.  Both default to None: the one-shot path."""
+        self._check_append_args(inputs_embeds, cache, past_len, prefill_chunk)
         if streamer is not None and inputs_embeds.shape[0] > 1:
             raise ValueError("TextStreamer only supports batch size 1")          # transformers/generation/streamers.py, TextStreamer.put
         gc = generation_config
@@ -940,7 +985,8 @@ class HipQwen2ForCausalLM(_HipModule):
                 raise ValueError(f"max_matching_ngram_size has to be a positive integer, but is {max_ngram}")
             if forced_ids is not None or return_logits:
                 raise ValueError("prompt_lookup_num_tokens / draft_ids: forced_ids and return_logits are not supported in this mode")
-            return self._generate_verify(inputs_embeds, attention_mask, max_new_tokens, eos_token_id, k_spec, max_ngram, prompt_ids, draft_ids, cache, streamer)
+            return self._generate_verify(inputs_embeds, attention_mask, max_new_tokens, eos_token_id, k_spec, max_ngram, prompt_ids, draft_ids, cache, streamer,
+                                         past_len, prefill_chunk)
         if do_sample and temperature <= 0:
             raise ValueError(f"`temperature` (={temperature}) has to be a strictly positive float, otherwise your next token scores will be invalid.")
         if do_sample and top_k < 0:
@@ -968,7 +1014,23 @@ class HipQwen2ForCausalLM(_HipModule):
                 seed = self._fresh_seed()
             sampling = (temperature, top_k, top_p, int(seed))
         return self._generate_solo(inputs_embeds, attention_mask, max_new_tokens, eos_token_id, sampling, use_graph, return_logits, forced_ids, cache,
-                                   streamer)
+                                   streamer, past_len, prefill_chunk)
+
+    @staticmethod
+    def _check_append_args(inputs_embeds, cache, past_len, prefill_chunk) -> None:
+        """generate()'s past_len / prefill_chunk, refused before anything runs."""
+        if past_len is not None:
+            if cache is None:
+                raise ValueError("past_len: the caller's `cache` (whose slot 0 holds the first past_len positions) is required with it")
+            if inputs_embeds.shape[0] != 1:
+                raise ValueError(f"past_len: continuing a cache serves batch size 1 (got {inputs_embeds.shape[0]})")
+            if int(past_len) < 0:
+                raise ValueError(f"past_len has to be a non-negative integer, but is {past_len}")
+        if prefill_chunk is not None:
+            if int(prefill_chunk) < 1:
+                raise ValueError(f"prefill_chunk has to be a positive integer, but is {prefill_chunk}")
+            if inputs_embeds.shape[0] != 1:
+                raise ValueError(f"prefill_chunk: a chunked prefill serves batch size 1 (got {inputs_embeds.shape[0]})")
 
     def _cache_for(self, S: int, max_new_tokens: int, cache):
         """A one-sequence generate()'s KV cache: the caller's, or `_own_cache`, re-made at the next multiple of 256 when missing or too small."""
@@ -980,26 +1042,42 @@ class HipQwen2ForCausalLM(_HipModule):
             raise ValueError(f"KV cache too small: {cache.max_ctx} < {S} + {max_new_tokens}")
         return cache
 
-    def _prefill_one(self, inputs_embeds, attention_mask, max_new_tokens, cache, admit=None):
+    def _prefill_one(self, inputs_embeds, attention_mask, max_new_tokens, cache, admit=None, past_len=None, prefill_chunk=None):
         """The opening of a one-sequence generate(): the row cut by its mask, its cache, the prefill.  admit(cache) may refuse the cache before
-        any kernel runs.  Returns (S, cache, the prefill's result, the last row's index as a device int32[1])."""
+        any kernel runs.  Returns (S, cache, the prefill's result, the last row's index as a device int32[1]).  With past_len or a prompt longer
+        than prefill_chunk the prompt reaches the cache through `prefill_append`; S is then the number of positions the cache holds afterwards
+        and the index that of the last position, as for a one-shot prefill of the whole sequence."""
         ops._need(inputs_embeds, dtype=None, name="inputs_embeds")
         x = inputs_embeds[0]
         if attention_mask is not None:
             x = x[attention_mask[0].bool()]
         S, dev = x.shape[0], x.device
-        cache = self._cache_for(S, max_new_tokens, cache)
+        P = 0 if past_len is None else int(past_len)
+        cache = self._cache_for(P + S, max_new_tokens, cache)
         if admit is not None:
             admit(cache)
+        if past_len is not None or (prefill_chunk is not None and S > int(prefill_chunk)):
+            x = x.to(self.dtype)
+            step = S if prefill_chunk is None else int(prefill_chunk)
+            off, r = 0, None
+            if past_len is None:                                    # an empty cache: the first chunk is the prefill as it always was
+                self.prefill_packed(x[:step], torch.arange(step, device=dev, dtype=torch.int32), None, step, cache=cache)
+                off = step
+            while off < S:
+                n = min(step, S - off)
+                rows = torch.full((1,), n - 1, device=dev, dtype=torch.int32) if off + n == S else None
+                r = self.prefill_append(x[off:off + n], cache, P + off, 0, last_rows=rows)
+                off += n
+            return P + S, cache, r, torch.full((1,), P + S - 1, device=dev, dtype=torch.int32)
         pos = torch.arange(S, device=dev, dtype=torch.int32)
         last = torch.full((1,), S - 1, device=dev, dtype=torch.int32)          # (a fill kernel, not a host copy)
         return S, cache, self.prefill_packed(x.to(self.dtype), pos, None, S, cache=cache, last_rows=last), last
 
     def _generate_solo(self, inputs_embeds, attention_mask, max_new_tokens, eos_token_id, sampling, use_graph, return_logits, forced_ids, cache,
-                       streamer):
+                       streamer, past_len=None, prefill_chunk=None):
         """generate() for one sequence: prefill, then the batch-1 step (one hipGraph replay per token, or step by step under `use_graph=False`,
         `return_logits` or `forced_ids`).  sampling: None (greedy) or (temperature, top_k, top_p, seed)."""
-        S, cache, r, last = self._prefill_one(inputs_embeds, attention_mask, max_new_tokens, cache)
+        S, cache, r, last = self._prefill_one(inputs_embeds, attention_mask, max_new_tokens, cache, None, past_len, prefill_chunk)
         dev = inputs_embeds.device
         eos_set = _eos_set(eos_token_id, self.lcfg.eos_token_id)
         st = self._decode_session(cache, max_new_tokens, sampling)
@@ -1106,7 +1184,8 @@ class HipQwen2ForCausalLM(_HipModule):
             self._require_bf16("the bf16 verify step")
         self._step(True, self._w4 if st.w4 else None, cache, st, None, verify=True)
 
-    def _generate_verify(self, inputs_embeds, attention_mask, max_new_tokens, eos_token_id, k, max_ngram, prompt_ids, draft_ids, cache, streamer):
+    def _generate_verify(self, inputs_embeds, attention_mask, max_new_tokens, eos_token_id, k, max_ngram, prompt_ids, draft_ids, cache, streamer,
+                         past_len=None, prefill_chunk=None):
         """generate() for one greedy sequence with the verify step: prefill as `_generate_solo`, first token from the prefill, then graph replays
         that each append 1 .. k + 1 tokens.  The host cuts at EOS and at max_new_tokens (a step may overshoot by up to k)."""
         why = self._verify_refusal()
@@ -1115,7 +1194,7 @@ class HipQwen2ForCausalLM(_HipModule):
         def admit(c):
             if c.max_ctx > self.BATCH_MAX_CTX:
                 raise ValueError(f"prompt_lookup_num_tokens / draft_ids: the verify step serves caches up to {self.BATCH_MAX_CTX} positions (got {c.max_ctx})")
-        S, cache, r, _ = self._prefill_one(inputs_embeds, attention_mask, max_new_tokens, cache, admit)
+        S, cache, r, _ = self._prefill_one(inputs_embeds, attention_mask, max_new_tokens, cache, admit, past_len, prefill_chunk)
         dev, n = inputs_embeds.device, k + 1
         eos_set = _eos_set(eos_token_id, self.lcfg.eos_token_id)
         first = ops.argmax(r.last_logits[0])

@@ -281,6 +281,32 @@ def attn_decode_batch(q: torch.Tensor, kcache: torch.Tensor, vcache: torch.Tenso
     return o
 
 
+def attn_append(q: torch.Tensor, kslot: torch.Tensor, vslot: torch.Tensor, past: int, scale: Optional[float] = None,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Causal attention with a key prefix (the append prefill's attention on its own): q [T, q_heads, 128] bf16 (rows may be strided) at positions
+    past .. past + T - 1 of ONE sequence; kslot / vslot one layer's slot [kv_heads, max_ctx, 128] bf16 (contiguous) holding the keys / values of
+    positions 0 .. past + T - 1.  Row i attends keys 0 .. past + i; rows of the slot at or beyond past + T are never read.  The block form follows
+    `vila_attn_force_append`.  -> o [T, q_heads, 128] (`out`, if given, is written and returned)."""
+    _need(q, name="q"); _need(kslot, name="kslot"); _need(vslot, name="vslot")
+    if q.dim() != 3 or q.shape[2] != 128 or q.stride(2) != 1 or q.stride(1) != 128:
+        raise ValueError("attn_append: q must be [T, q_heads, 128] with contiguous heads")
+    T, nq, _ = q.shape
+    if kslot.dim() != 3 or kslot.shape != vslot.shape or kslot.shape[2] != 128 or not kslot.is_contiguous() or not vslot.is_contiguous():
+        raise ValueError("attn_append: kslot / vslot must be contiguous [kv_heads, max_ctx, 128] of one shape")
+    nkv, max_ctx, _ = kslot.shape
+    past = int(past)
+    if past < 0 or T < 1 or past + T > max_ctx:
+        raise ValueError(f"attn_append: past ({past}) >= 0, T ({T}) >= 1 and past + T <= max_ctx ({max_ctx}) are required")
+    o = torch.empty((T, nq, 128), device=q.device, dtype=torch.bfloat16) if out is None else out
+    if out is not None:
+        _need(out, name="out")
+        if out.shape != (T, nq, 128) or out.stride(2) != 1 or out.stride(1) != 128:
+            raise ValueError("attn_append: out must be [T, q_heads, 128] with contiguous heads")
+    check(_lib.load().vila_attn_append_bf16(q.data_ptr(), q.stride(0), kslot.data_ptr(), vslot.data_ptr(), past, T, o.data_ptr(), o.stride(0), nq, nkv,
+                                            max_ctx, float(scale if scale is not None else 128 ** -0.5), _stream()), "attn_append")
+    return o
+
+
 def attn_decode_verify(q: torch.Tensor, kslot: torch.Tensor, vslot: torch.Tensor, pos: torch.Tensor, scale: Optional[float] = None) -> torch.Tensor:
     """The verify step's attention on its own: q [n, q_heads, 128] bf16 (rows may be strided), n in 1..16 consecutive positions of ONE sequence;
     kslot / vslot one layer's slot [kv_heads, max_ctx, 128] bf16 (contiguous); pos a device int32 scalar — row i attends keys

@@ -419,6 +419,82 @@ def generate_content(model, tokenizer, prompt: Union[str, Sequence[Any]], max_ne
     return tokenizer.decode(toks, skip_special_tokens=True).strip()
 
 
+class ChatOverflow(ValueError):
+    """A turn that does not fit the session's KV cache.  The session is unchanged and stays usable (ask something shorter, or `reset()`)."""
+
+
+class ChatSession:
+    """A conversation that keeps its KV cache: every `ask` prefills only the NEW tokens onto the cache (`llm.generate(cache=, past_len=)`), so a
+    follow-up question re-encodes no earlier image and re-prefills no earlier turn.
+
+    The session owns one cache of `max_ctx` positions and three pieces of state:
+      ids       the conversation's token ids so far, media as their placeholder ids (what a one-shot `generate` of the whole conversation is fed);
+      cached    the number of leading POSITIONS of the cache whose K/V are valid (an image placeholder is many positions);
+      the last emitted token, which has NOT been fed yet: after `generate` returns n tokens on top of P cached positions and S new ones the cache
+      holds P + S + n - 1 — rows beyond that may hold steps the device ran past the EOS, or rejected drafts, and count for nothing.
+    So the next turn's new tokens open with that last token, then the end-of-turn marker if the reply was cut by max_new_tokens rather than by it,
+    the separator and the new user turn in the Qwen2 chat form (`chat_text`, the template every NVILA recipe runs).  Media of a later turn are
+    encoded and spliced for the new part only.  gen_defaults / `ask(**gen)`: keyword arguments of `llm.generate` (do_sample, temperature, top_k,
+    top_p, seed, prompt_lookup_num_tokens, streamer, ...)."""
+
+    TURN_END = "<|im_end|>"
+
+    def __init__(self, model, tokenizer, max_ctx: int = 4096, system: Optional[str] = None, eos_token_id=None, **gen_defaults):
+        self.model, self.tokenizer, self.max_ctx, self.system = model, tokenizer, int(max_ctx), system
+        self.eos = _eos_of(tokenizer, eos_token_id)
+        self.gen_defaults = dict(gen_defaults)
+        self.cache = None
+        self.reset()
+
+    def reset(self) -> None:
+        """Back to an empty conversation (the cache's memory is kept and overwritten)."""
+        self.ids: List[int] = []
+        self.cached = 0
+        self._last: Optional[int] = None          # the last emitted token (in `ids`, not in the cache)
+        self._closed = True                       # the last reply ended with a stop token of its own
+
+    def _new_ids(self, text: str) -> List[int]:
+        """The ids this turn adds in front of the reply: the first turn's prompt, or end-of-turn (if missing) + separator + the user turn."""
+        image_id = self.model.cfg.image_token_id
+        if self._last is None:
+            return encode_with_images(self.tokenizer, prompt_text(self.tokenizer, text, self.system), image_id).tolist()
+        return encode_with_images(self.tokenizer, ("" if self._closed else self.TURN_END) + "\n" + chat_text(text), image_id).tolist()
+
+    def ask(self, prompt: Union[str, Sequence[Any]], max_new_tokens: int = 128, **gen) -> str:
+        if max_new_tokens < 1:
+            raise ValueError(f"max_new_tokens has to be a positive integer, but is {max_new_tokens}")
+        model, dev = self.model, str(self.model.device)
+        text, tiles, media_config = prepare_prompt(prompt, model.cfg)
+        new = self._new_ids(text)
+        fed = ([] if self._last is None else [self._last]) + new              # what is prefilled: the token never fed comes first
+        media = {"image": [t.to(device=dev, dtype=torch.bfloat16) for t in tiles]}
+        with torch.inference_mode():
+            embeds, _, _ = model._embed(torch.tensor([fed], dtype=torch.int64, device=dev), media, media_config, None, None)
+        P, S = self.cached, int(embeds.shape[1])
+        if P + S + max_new_tokens > self.max_ctx:
+            raise ChatOverflow(f"the turn does not fit the session's cache: {P} cached + {S} new + {max_new_tokens} to generate > max_ctx {self.max_ctx} "
+                               "(the session is unchanged; reset() starts a new conversation)")
+        if self.cache is None:
+            self.cache = model.llm.new_cache(self.max_ctx)
+        kw = {**self.gen_defaults, **gen}
+        kw.setdefault("eos_token_id", self.eos)
+        if kw.get("prompt_lookup_num_tokens") is not None and kw.get("prompt_ids") is None:
+            kw["prompt_ids"] = torch.tensor(self.ids + new, dtype=torch.int64, device=dev)
+        if P:
+            kw["past_len"] = P
+        out = model.llm.generate(inputs_embeds=embeds, max_new_tokens=max_new_tokens, cache=self.cache, **kw)
+        toks = [int(t) for t in out[0].tolist()]
+        stop = _eos_set(kw["eos_token_id"], model.cfg.llm.eos_token_id)
+        # the state moves only now: a turn that raised left it as it was
+        self.ids.extend(new)
+        self.ids.extend(toks)
+        self.cached = P + S + len(toks) - 1
+        self._last = toks[-1]
+        self._closed = toks[-1] in stop
+        reply = toks[:-1] if self._closed else toks
+        return self.tokenizer.decode(reply, skip_special_tokens=True).strip()
+
+
 def generate_content_batch(model, tokenizer, prompts: Sequence[Union[str, Sequence[Any]]], max_new_tokens: int = 128, system: Optional[str] = None,
                            eos_token_id=None, pad_token_id: Optional[int] = None, device: Optional[str] = None) -> List[str]:
     """Several greedy requests as ONE padded batch (server.py:171-290 serves concurrent requests; here they share every pass over the
