@@ -20,6 +20,10 @@ LIB = os.path.join(LIBDIR, "libvila_hip.so")
 SOURCES = ["api.hip", "gemm.hip", "attn.hip", "elementwise.hip", "gemv.hip", "attn_decode.hip", "train.hip", "attn_bwd.hip", "gemm256.hip", "s2.hip", "gemv_w4.hip", "gemm_ring.hip", "video.hip", "gemm256_cm.hip", "gemm_i8.hip", "sample.hip", "sft.hip", "attn_bwd_dma.hip", "decode_batch.hip", "gemm_ring_splitk.hip", "gemm_w4.hip", "gemv_w4_batch.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
          "-ffp-contract=off"]  # fp-contract off: keep the HF rounding order (bf16(q*cos)+bf16(rot*sin)) explicit
+# Per-source flags on top of FLAGS.  Kernarg preload: the leading (flat) kernel arguments of the batch-1 decode kernels arrive in SGPRs at wave
+# start, so their first weight request waits for no scalar load.  Only these two files: no other translation unit changes.
+_PRELOAD = ["-mllvm", "-amdgpu-kernarg-preload-count=14"]
+EXTRA_FLAGS = {"gemv.hip": _PRELOAD, "attn_decode.hip": _PRELOAD}
 
 
 def hipcc() -> str:
@@ -59,7 +63,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
         path = os.path.join(CSRC, src)
         if not force and os.path.exists(obj) and os.path.getmtime(obj) > max(os.path.getmtime(path), hdr_t):
             return obj
-        cmd = [cc, *FLAGS, "-c", path, "-o", obj]
+        cmd = [cc, *FLAGS, *EXTRA_FLAGS.get(src, []), "-c", path, "-o", obj]
         if verbose:
             cmd.insert(1, "-Rpass-analysis=kernel-resource-usage")
         r = subprocess.run(cmd, capture_output=True, text=True)

@@ -6,6 +6,7 @@
 //     both serving a whole GQA group from one K/V read, and bdec_attn_merge_kernel.
 #include "attn_decode.h"
 #include "gemv_common.h"
+#include "gemv_plan.h"
 #include "attn_common.h"
 
 typedef __attribute__((address_space(1))) unsigned long long gu64;
@@ -134,19 +135,24 @@ __global__ __launch_bounds__(128) void attn_decode_merge(AttnDecodeArgs p) {
 // ------------------------------------------------------------------------------------------------
 // SPLIT: grid (nq, ceil(max_ctx / 256)); block (h, s) covers keys [256 s, 256 s + 256) — ONE 16-key chunk per wave, no loop — and writes the
 // un-normalised partial (o, m, l) of that slice; the merge over the <= 8 slices happens in the o_proj GEMV's prologue (gemv_kernel<2>).
+// Arguments ("the head of a kernel"): what the first requests need — q, the caches, the position, the row strides of the batched
+// form, the capacity and the kv head of a query head as a multiplication (kvh_magic: gemv_plan.h udiv_magic of the GQA group, 0 for a group of
+// one) — flat in front, 14 dwords that the wave finds in SGPRs at its start (kernarg preload; vila_amd/build.py); the rest in AttnHeadTail,
+// fetched behind the first K/V chunk.
+struct AttnHeadTail { bf16_t* o; float* part_o; float* part_ml; int64_t o_row_stride; int nq; float scale; };
 template <bool SPLIT>
-__global__ __launch_bounds__(1024) void attn_decode_head(AttnDecodeArgs p) {
+__global__ __launch_bounds__(1024) void attn_decode_head(const bf16_t* q, const bf16_t* kcache, const bf16_t* vcache, const int32_t* pos_ptr,
+                                                         int64_t q_row_stride, int64_t slot_stride, int max_ctx, unsigned kvh_magic, AttnHeadTail t) {
     __shared__ float sq[128];
     __shared__ float so[16][128];
     __shared__ float sml[16][2];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int h = blockIdx.x, kvh = h / (p.nq / p.nkv);
+    const int h = blockIdx.x, kvh = kvh_magic ? (int)udiv_by_magic((unsigned)h, kvh_magic) : h;
     const int key_lo = SPLIT ? blockIdx.y * 256 : 0;
     const int row = blockIdx.z;                                  // batched decode: sequence = cache slot (0 for the batch-1 step)
-    p.q += row * p.q_row_stride; p.kcache += row * p.slot_stride; p.vcache += row * p.slot_stride;
-    if (!SPLIT) p.o += row * p.o_row_stride;
-    const bf16_t* kb = p.kcache + (int64_t)kvh * p.max_ctx * 128;
-    const bf16_t* vb = p.vcache + (int64_t)kvh * p.max_ctx * 128;
+    q += row * q_row_stride; kcache += row * slot_stride; vcache += row * slot_stride;
+    const bf16_t* kb = kcache + (int64_t)kvh * max_ctx * 128;
+    const bf16_t* vb = vcache + (int64_t)kvh * max_ctx * 128;
     const int kq = lane >> 2, qd = lane & 3;        // scores: key within the chunk, d quarter
     const int sg = lane >> 4, dc = lane & 15;       // P.V: 4-key subgroup, d chunk
     u32x4 kc[4], vc[4], kn_[4], vn_[4];
@@ -156,11 +162,11 @@ __global__ __launch_bounds__(1024) void attn_decode_head(AttnDecodeArgs p) {
     // 300).  Once the position is here, the rows at or past nkeys, which may hold anything, are replaced by the zero vectors that a load
     // predicated on nkeys produces.
     int k0 = key_lo + wave * 16;
-    const int nkeys_all = p.pos_ptr[row] + 1;
-    const bf16_t qv = p.q[h * 128 + (tid & 127)];
+    const int nkeys_all = pos_ptr[row] + 1;
+    const bf16_t qv = q[h * 128 + (tid & 127)];
     __builtin_amdgcn_sched_barrier(0);                           // the small loads stay in front of K/V ...
     {
-        const int cap = p.max_ctx - 1;
+        const int cap = max_ctx - 1;
         const int key = k0 + kq < cap ? k0 + kq : cap;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -170,6 +176,8 @@ __global__ __launch_bounds__(1024) void attn_decode_head(AttnDecodeArgs p) {
         }
     }
     __builtin_amdgcn_sched_barrier(0);                           // ... and in front of the return below, which waits for the position
+    asm volatile("" :: "s"(t.o), "s"(t.part_o), "s"(t.part_ml), "s"(t.o_row_stride), "s"(t.nq), "s"(t.scale));   // the tail's scalar loads: here
+    __builtin_amdgcn_sched_barrier(0);
     if (SPLIT && key_lo >= nkeys_all) return;                    // block-uniform: slices beyond the context write nothing (the merge skips them)
     const int nkeys = SPLIT ? (nkeys_all < key_lo + 256 ? nkeys_all : key_lo + 256) : nkeys_all;
     auto load_chunk = [&](int k0, u32x4 (&kk)[4], u32x4 (&vv)[4]) {
@@ -181,7 +189,7 @@ __global__ __launch_bounds__(1024) void attn_decode_head(AttnDecodeArgs p) {
             vv[j] = (vk < nkeys) ? *(const u32x4*)(vb + (int64_t)vk * 128 + dc * 8) : (u32x4){0u, 0u, 0u, 0u};
         }
     };
-    if (tid < 128) sq[tid] = bf2f(qv) * p.scale;
+    if (tid < 128) sq[tid] = bf2f(qv) * t.scale;
     sync_lds();                                                  // LDS only: a __syncthreads() would drain the K/V loads (gemv_common.h)
     float qr[32];
 #pragma unroll
@@ -254,13 +262,22 @@ __global__ __launch_bounds__(1024) void attn_decode_head(AttnDecodeArgs p) {
             acc += wgt * so[w][tid];
         }
         if (SPLIT) {
-            const int64_t slot = (int64_t)blockIdx.y * p.nq + h;
-            p.part_o[slot * 128 + tid] = acc;
-            if (tid == 0) { p.part_ml[slot * 2] = M; p.part_ml[slot * 2 + 1] = L; }
+            const int64_t slot = (int64_t)blockIdx.y * t.nq + h;
+            t.part_o[slot * 128 + tid] = acc;
+            if (tid == 0) { t.part_ml[slot * 2] = M; t.part_ml[slot * 2 + 1] = L; }
         } else {
-            p.o[h * 128 + tid] = f2bf(acc / L);
+            (t.o + row * t.o_row_stride)[h * 128 + tid] = f2bf(acc / L);
         }
     }
+}
+
+// the kernel's arguments from AttnDecodeArgs (nq a multiple of nkv: checked by the callers)
+template <bool SPLIT>
+static void launch_head(const AttnDecodeArgs& a, dim3 grid, hipStream_t s) {
+    const int G = a.nq / a.nkv;
+    const AttnHeadTail t{a.o, a.part_o, a.part_ml, a.o_row_stride, a.nq, a.scale};
+    hipLaunchKernelGGL(attn_decode_head<SPLIT>, grid, dim3(1024), 0, s, a.q, a.kcache, a.vcache, a.pos_ptr, a.q_row_stride, a.slot_stride, a.max_ctx,
+                       G > 1 ? udiv_magic((unsigned)G) : 0u, t);
 }
 
 // batched decode: one block per (query head, sequence) over the sequence's whole context (caches up to DEC_SHORT_CTX positions)
@@ -269,7 +286,7 @@ int launch_attn_decode_rows(const AttnDecodeArgs& a0, int n_rows, int64_t q_row_
     VILA_REQUIRE(a.hd == 128 && a.o != nullptr && a.max_ctx <= DEC_SHORT_CTX && n_rows >= 1, "attn_decode_rows: head_dim 128, caches up to 2048 positions");
     VILA_REQUIRE(a.nq % a.nkv == 0, "attn_decode_rows: q heads must be a multiple of kv heads");
     a.q_row_stride = q_row_stride; a.o_row_stride = o_row_stride; a.slot_stride = slot_stride;
-    hipLaunchKernelGGL(attn_decode_head<false>, dim3(a.nq, 1, n_rows), dim3(1024), 0, s, a);
+    launch_head<false>(a, dim3(a.nq, 1, n_rows), s);
     VILA_LAUNCH_CHECK();
     return 0;
 }
@@ -280,12 +297,12 @@ int launch_attn_decode(const AttnDecodeArgs& a, hipStream_t s) {
     VILA_REQUIRE(a.n_splits * DEC_KS >= a.max_ctx, "attn_decode: n_splits too small for max_ctx");
     if (a.split256) {                                            // partials per 256-key slice; merged by the o_proj GEMV (mode 2, split_keys 256)
         VILA_REQUIRE(a.max_ctx <= DEC_SHORT_CTX && a.n_splits * DEC_KS >= a.max_ctx, "attn_decode: 256-key slices need max_ctx <= 2048");
-        hipLaunchKernelGGL(attn_decode_head<true>, dim3(a.nq, cdiv(a.max_ctx, 256)), dim3(1024), 0, s, a);
+        launch_head<true>(a, dim3(a.nq, cdiv(a.max_ctx, 256)), s);
         VILA_LAUNCH_CHECK();
         return 0;
     }
     if (a.o != nullptr && a.max_ctx <= DEC_SHORT_CTX) {
-        hipLaunchKernelGGL(attn_decode_head<false>, dim3(a.nq), dim3(1024), 0, s, a);
+        launch_head<false>(a, dim3(a.nq), s);
         VILA_LAUNCH_CHECK();
         return 0;
     }

@@ -3,8 +3,12 @@
 // weights go straight HBM -> VGPR with 16-B non-temporal loads, deep unroll, late wait; the activation vector is
 // staged once per block in LDS (with the preceding RMSNorm fused in, HF rounding order kept); all epilogues
 // (bias, RoPE, KV-cache write, SiLU*up, residual add) are fused so a decoder layer is 5 launches.
+// The head of a kernel: what its first memory requests need arrives as flat leading arguments, preloaded into SGPRs at wave start (this file and
+// attn_decode.hip are built with the kernarg preload count set, vila_amd/build.py); the CU map is planned on the host (gemv_plan.h); the rest of
+// the arguments is a by-value struct fetched behind the first requests.  See gemv_kernel below and DESIGN.md §4.3.
 #include "kernels.h"
 #include "gemv_common.h"
+#include "gemv_plan.h"
 #include "attn_decode.h"
 
 __device__ __forceinline__ u32x4 ldg_nt(const bf16_t* p) { return __builtin_nontemporal_load((const u32x4*)p); }
@@ -178,39 +182,65 @@ __device__ __forceinline__ void wave_rows_dot(const bf16_t* const (&wrow)[R], co
 // latency-bound), 4 is enough for the long rows (K = 18944) where many iterations pipeline anyway.
 // NT = threads per block.  On the CU map ONE block of 256 x (blocks per CU of the balanced grid) threads runs per CU, so the activation is
 // loaded, normalised and written to LDS once per CU; its NT / 64 waves deal the CU's row groups (j = wave, stride NT / 64).
-template <int MODE, int U, int NT>   // MODE 0 plain, 1 gate/up, 2 plain with x = merged attention partials
-__global__ __launch_bounds__(NT) void gemv_kernel(GemvArgs p, int n_groups, int ncu, int skew) {
+// Kernel arguments ("the head of a kernel").  What the FIRST memory requests need comes first and flat — four pointers and six
+// ints, 14 dwords — so that the wave starts with them in SGPRs (kernarg preload; gemv.hip is built with the preload count set, vila_amd/build.py)
+// and requests its first weight batch without a scalar load, a wait or a division in front: the weights, then per mode
+//   0: a1 = x, a2 = norm_w          1: a1 = x, a2 = W2, a3 = norm_w          2: a1 = part_o, a2 = part_ml, a3 = pos_ptr,
+// K, N, n_splits (mode 2) and the CU map as launch_gemv planned it (gemv_plan.h GemvPlan; ncu_xr == 0: small grids, cf = the walk's stride).
+// The head reads neither blockDim nor gridDim (hidden arguments: a scalar load each).  Everything else is GemvTail, a by-value struct behind
+// them, fetched right after the first requests (tail_here).
+struct GemvTail {
+    const bf16_t* bias; const bf16_t* residual; bf16_t* y; float* y_f32; float* amax_v; int* amax_i;
+    float eps; int split_keys;
+};
+// The tail's scalar loads belong HERE: behind the requests already made and in front of everything that follows (left alone the compiler sinks
+// them to their first uses, behind the staging's barrier, where each is one more round trip in line).
+__device__ __forceinline__ void tail_here(const GemvTail& t) {
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("" :: "s"(t.bias), "s"(t.residual), "s"(t.y), "s"(t.y_f32), "s"(t.amax_v), "s"(t.amax_i), "s"(t.eps), "s"(t.split_keys));
+    __builtin_amdgcn_sched_barrier(0);
+}
+// Which instantiations take the flat head: decided per kernel from two kernel-trace profiles per build (CHANGELOG).  lm_head (<0,7,...>: one
+// launch of 172 us per token) measured inside its spread and keeps the head it had: GemvArgs by value, the map derived on the device (CuMap).
+constexpr bool gemv_flat_head(int MODE, int U) { return !(MODE == 0 && U == 7); }
+
+// The body both heads share.  Map: GemvPlan (host-planned) or CuMap (device-derived) — the same count() / gid().  FLAT: pin the tail's loads.
+template <int MODE, int U, int NT, bool FLAT, class Map>   // MODE 0 plain, 1 gate/up, 2 plain with x = merged attention partials
+__device__ __forceinline__ void gemv_body(const bf16_t* W, const void* a1, const void* a2, const void* a3, int K, int N, int n_splits, const Map& cm,
+                                          int ncu, int stride, const GemvTail& t) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     bf16_t* sx = (bf16_t*)smem;
-    float* scratch = (float*)(smem + ((p.K * 2 + 15) & ~15));
+    float* scratch = (float*)(smem + ((K * 2 + 15) & ~15));
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int nch = p.K >> 3;
+    const int nch = K >> 3;
+    const int n_groups = (N + 1) >> 1;
     constexpr int R = (MODE == 1) ? 4 : 2;
     constexpr bool INPUTS_FIRST = MODE == 2 || (MODE == 0 && U < 7);
-    // ncu > 0: the CU-balanced map (gemv_common.h CuMap; block = CU); ncu == 0: small grids, the plain grid-stride walk
+    const bf16_t* const W2 = (const bf16_t*)a2;                                                   // mode 1
+    const bf16_t* const x = (const bf16_t*)a1;                                                    // modes 0, 1
+    const bf16_t* const norm_w = (const bf16_t*)(MODE == 1 ? a3 : a2);                            // modes 0, 1
+    // ncu > 0: the CU-balanced map (block = CU); ncu == 0: small grids, the plain grid-stride walk (stride = blocks x WPB)
     constexpr int WPB = NT / 64;
-    const CuMap cm(n_groups, ncu > 0 ? ncu : 8, ncu > 0 ? skew : 0);
     const int cu = ncu > 0 ? (int)blockIdx.x : 0;
     const int cnt = ncu > 0 ? cm.count(cu) : 0;
     int j = wave;                                                             // the block's WPB waves deal the CU's groups
-    const int stride = gridDim.x * WPB;
     int g = ncu > 0 ? (j < cnt ? cm.gid(cu, j) : n_groups) : blockIdx.x * WPB + wave;
     auto next_group = [&]() { if (ncu > 0) { j += WPB; g = j < cnt ? cm.gid(cu, j) : n_groups; } else g += stride; };
 
     auto rows_of = [&](int gg, const bf16_t* (&rows)[R]) {
         const int n = gg * 2;
-        const int n1 = (n + 1 < p.N) ? n + 1 : n;
+        const int n1 = (n + 1 < N) ? n + 1 : n;
         if constexpr (MODE == 1) {
-            rows[0] = p.W + (int64_t)n * p.K; rows[1] = p.W2 + (int64_t)n * p.K;
-            rows[2] = p.W + (int64_t)n1 * p.K; rows[3] = p.W2 + (int64_t)n1 * p.K;
+            rows[0] = W + (int64_t)n * K; rows[1] = W2 + (int64_t)n * K;
+            rows[2] = W + (int64_t)n1 * K; rows[3] = W2 + (int64_t)n1 * K;
         } else {
-            rows[0] = p.W + (int64_t)n * p.K; rows[1] = p.W + (int64_t)n1 * p.K;
+            rows[0] = W + (int64_t)n * K; rows[1] = W + (int64_t)n1 * K;
         }
     };
     // Epilogue: after the wave reduction every lane holds the sums; lanes 0 and 1 each produce and store one of the wave's two adjacent
     // outputs (rows n, n + 1).
     bf16_t e_bias = 0, e_res = 0;                    // as loaded (bf2f_late)
-    float best = -INFINITY; int bi = 0x7fffffff;     // p.amax_v: the largest fp32 output of this lane's rows so far (lanes 0 and 1)
+    float best = -INFINITY; int bi = 0x7fffffff;     // t.amax_v: the largest fp32 output of this lane's rows so far (lanes 0 and 1)
     auto finish = [&](int gg, float (&acc)[R]) {
         const int n = gg * 2;
         bf16_t o = 0;
@@ -221,12 +251,12 @@ __global__ __launch_bounds__(NT) void gemv_kernel(GemvArgs p, int n_groups, int 
         } else {
             float v = lane == 0 ? acc[0] : acc[1];
             v += bf2f_late(e_bias);
-            if (lane < 2 && n + lane < p.N && p.y_f32 != nullptr) p.y_f32[n + lane] = v;
-            if (p.amax_v != nullptr && lane < 2 && n + lane < p.N) amax_merge(best, bi, v, n + lane);
-            if (p.residual != nullptr) v = bfround(v) + bf2f_late(e_res);
+            if (lane < 2 && n + lane < N && t.y_f32 != nullptr) t.y_f32[n + lane] = v;
+            if (t.amax_v != nullptr && lane < 2 && n + lane < N) amax_merge(best, bi, v, n + lane);
+            if (t.residual != nullptr) v = bfround(v) + bf2f_late(e_res);
             o = f2bf(v);
         }
-        if (p.y != nullptr && lane < 2 && n + lane < p.N) p.y[n + lane] = o;
+        if (t.y != nullptr && lane < 2 && n + lane < N) t.y[n + lane] = o;
     };
     // the epilogue's operands are requested BEFORE the dot product: fetched after the reduction they add a dependent memory round
     // trip (~1 us) to the tail of every wave, i.e. to the kernel
@@ -234,9 +264,9 @@ __global__ __launch_bounds__(NT) void gemv_kernel(GemvArgs p, int n_groups, int 
         if constexpr (MODE != 1) {
             const int nn = gg * 2 + lane;
             e_bias = 0; e_res = 0;
-            if (lane < 2 && nn < p.N) {
-                if (p.bias != nullptr) e_bias = p.bias[nn];
-                if (p.residual != nullptr && p.y != nullptr) e_res = p.residual[nn];
+            if (lane < 2 && nn < N) {
+                if (t.bias != nullptr) e_bias = t.bias[nn];
+                if (t.residual != nullptr && t.y != nullptr) e_res = t.residual[nn];
             }
         }
     };
@@ -247,37 +277,42 @@ __global__ __launch_bounds__(NT) void gemv_kernel(GemvArgs p, int n_groups, int 
     if constexpr (INPUTS_FIRST) {
         rows_of(has ? g : 0, rows);
         if constexpr (MODE == 2) {
-            const int ks = p.split_keys > 0 ? p.split_keys : DEC_KS;
+            const int pos = *(const int32_t*)a3;               // its pointer is here at wave start: requested in front of the tail's wait, not behind it
+            __builtin_amdgcn_sched_barrier(0);
             AttnMergeLoads ld;
-            stage_x_attn_issue<NT>(p.part_o, p.part_ml, p.n_splits, p.K >> 7, ld);
+            stage_x_attn_issue<NT>((const float*)a1, (const float*)a2, n_splits, K >> 7, ld);
             __builtin_amdgcn_sched_barrier(0);                   // the staging's loads stay in front of the weights
             load_first_batch<R, U>(rows, lane, nch, has, b0);
+            if constexpr (FLAT) tail_here(t);
             if (has) epi_fetch(g);
-            const int n_active = (*p.pos_ptr + ks) / ks;         // ceil((pos+1)/ks)
-            stage_x_attn_finish<NT>(p.part_o, p.part_ml, n_active < p.n_splits ? n_active : p.n_splits, p.K >> 7, sx, scratch, ld);
+            const int ks = t.split_keys > 0 ? t.split_keys : DEC_KS;
+            const int n_active = (pos + ks) / ks;                // ceil((pos+1)/ks)
+            stage_x_attn_finish<NT>((const float*)a1, (const float*)a2, n_active < n_splits ? n_active : n_splits, K >> 7, sx, scratch, ld);
         } else {
             STAGE_X_REGS(NT, st);
-            stage_x_issue<NT>(p.x, p.norm_w, p.K, STAGE_X_ARGS(st));
+            stage_x_issue<NT>(x, norm_w, K, STAGE_X_ARGS(st));
             __builtin_amdgcn_sched_barrier(0);
             load_first_batch<R, U>(rows, lane, nch, has, b0);
+            if constexpr (FLAT) tail_here(t);
             if (has) epi_fetch(g);                               // behind the weights: in front, the staging's loads waited for it at a join
-            stage_x_finish<NT, true>(p.x, p.norm_w, p.eps, p.K, sx, scratch, STAGE_X_ARGS(st));
+            stage_x_finish<NT, true>(x, norm_w, t.eps, K, sx, scratch, STAGE_X_ARGS(st));
         }
         if (has) first_batch_mask<R, U>(lane, nch, b0);
     } else {
         // the first weight batch in front of the staging, for short rows only (K <= 4096: the staging latency is comparable to the stream)
-        if (has && p.K <= 4096) { rows_of(g, rows); load_batch<R, U>(rows, 0, lane, nch, b0); }
+        if (has && K <= 4096) { rows_of(g, rows); load_batch<R, U>(rows, 0, lane, nch, b0); }
+        if constexpr (FLAT) tail_here(t);
         if (has) epi_fetch(g);
         STAGE_X_REGS(NT, st);
-        stage_x_issue<NT>(p.x, p.norm_w, p.K, STAGE_X_ARGS(st));
-        stage_x_finish<NT, false>(p.x, p.norm_w, p.eps, p.K, sx, scratch, STAGE_X_ARGS(st));   // __syncthreads(): exactly the waits these kernels had
+        stage_x_issue<NT>(x, norm_w, K, STAGE_X_ARGS(st));
+        stage_x_finish<NT, false>(x, norm_w, t.eps, K, sx, scratch, STAGE_X_ARGS(st));   // __syncthreads(): exactly the waits these kernels had
     }
-    if (has && (INPUTS_FIRST || p.K <= 4096)) {
+    if (has && (INPUTS_FIRST || K <= 4096)) {
         float acc[R];
 #pragma unroll
         for (int r = 0; r < R; ++r) acc[r] = 0.f;
         fma_batch<R, U>(b0, sx, 0, lane, nch, acc);
-        wave_rows_dot<R, U>(rows, sx, p.K, lane, acc, 64 * U);
+        wave_rows_dot<R, U>(rows, sx, K, lane, acc, 64 * U);
         finish(g, acc);
         next_group();
     }
@@ -287,12 +322,12 @@ __global__ __launch_bounds__(NT) void gemv_kernel(GemvArgs p, int n_groups, int 
         float acc[R];
 #pragma unroll
         for (int r = 0; r < R; ++r) acc[r] = 0.f;
-        wave_rows_dot<R, U>(rows, sx, p.K, lane, acc, 0);
+        wave_rows_dot<R, U>(rows, sx, K, lane, acc, 0);
         finish(g, acc);
     }
     // the greedy pick's first stage (lm_head of the batch-1 step): this block's rows reduced to one (max, index) pair with argmax's tie rule
     if constexpr (MODE == 0) {
-        if (p.amax_v != nullptr) {
+        if (t.amax_v != nullptr) {
             __shared__ float sv[WPB];
             __shared__ int si[WPB];
             wave_amax(best, bi);
@@ -300,10 +335,25 @@ __global__ __launch_bounds__(NT) void gemv_kernel(GemvArgs p, int n_groups, int 
             __syncthreads();
             if (threadIdx.x == 0) {
                 for (int w = 1; w < WPB; ++w) amax_merge(best, bi, sv[w], si[w]);
-                p.amax_v[blockIdx.x] = best; p.amax_i[blockIdx.x] = bi;
+                t.amax_v[blockIdx.x] = best; t.amax_i[blockIdx.x] = bi;
             }
         }
     }
+}
+
+template <int MODE, int U, int NT>
+__global__ __launch_bounds__(NT) void gemv_kernel(const bf16_t* W, const void* a1, const void* a2, const void* a3, int K, int N, int n_splits, int ncu_xr,
+                                                  int cf, int xq, GemvTail t) {
+    const GemvPlan cm{ncu_xr, cf, xq};
+    gemv_body<MODE, U, NT, true>(W, a1, a2, a3, K, N, n_splits, cm, cm.ncu(), cf, t);
+}
+template <int MODE, int U, int NT>
+__global__ __launch_bounds__(NT) void gemv_kernel_args(GemvArgs p, int n_groups, int ncu, int skew) {
+    const CuMap cm(n_groups, ncu > 0 ? ncu : 8, ncu > 0 ? skew : 0);
+    const GemvTail t{p.bias, p.residual, p.y, p.y_f32, p.amax_v, p.amax_i, p.eps, p.split_keys};
+    gemv_body<MODE, U, NT, false>(p.W, MODE == 2 ? (const void*)p.part_o : (const void*)p.x,
+                                  MODE == 2 ? (const void*)p.part_ml : MODE == 1 ? (const void*)p.W2 : (const void*)p.norm_w,
+                                  MODE == 2 ? (const void*)p.pos_ptr : MODE == 1 ? (const void*)p.norm_w : nullptr, p.K, p.N, p.n_splits, cm, ncu, (int)gridDim.x * (NT / 64), t);
 }
 
 // Grid sizing for the HBM-bound GEMVs: one block per CU (the dispatcher deals blocks round-robin, so 448 blocks of 256 threads would leave
@@ -339,17 +389,31 @@ int gemv_grid_blocks(int N) {
     return balanced_grid(cdiv(N, 2), &ncu, &per);
 }
 
+// The kernel's arguments from GemvArgs: the flat head (per mode, see gemv_kernel), the map planned here once per launch, the tail.
 template <int MODE, int U>
 static void gemv_launch(int per, int grid, size_t lds, hipStream_t s, const GemvArgs& a, int n_groups, int ncu, int skew) {
+    const void* a1 = MODE == 2 ? (const void*)a.part_o : (const void*)a.x;
+    const void* a2 = MODE == 2 ? (const void*)a.part_ml : MODE == 1 ? (const void*)a.W2 : (const void*)a.norm_w;
+    const void* a3 = MODE == 2 ? (const void*)a.pos_ptr : MODE == 1 ? (const void*)a.norm_w : nullptr;
+    GemvPlan pl{0, grid * 4, 0};                                  // small grids: 256-thread blocks walk with stride blocks x 4 waves
+    if (ncu > 0) pl = gemv_plan(n_groups, ncu, skew);
+    const GemvTail t{a.bias, a.residual, a.y, a.y_f32, a.amax_v, a.amax_i, a.eps, a.split_keys};
+#define GEMV_GO(NT)                                                                                                                                  \
+    do {                                                                                                                                             \
+        if constexpr (gemv_flat_head(MODE, U))                                                                                                       \
+            hipLaunchKernelGGL((gemv_kernel<MODE, U, NT>), dim3(grid), dim3(NT), lds, s, a.W, a1, a2, a3, a.K, a.N, a.n_splits, pl.ncu_xr, pl.cf, pl.xq, t); \
+        else                                                                                                                                         \
+            hipLaunchKernelGGL((gemv_kernel_args<MODE, U, NT>), dim3(grid), dim3(NT), lds, s, a, n_groups, ncu, skew);                               \
+    } while (0)
     if constexpr (MODE == 2) {   // 8 waves per CU at most (launch_gemv asks balanced_grid for per <= 2): the wider blocks are not built
-        if (per == 1) hipLaunchKernelGGL((gemv_kernel<2, U, 256>), dim3(grid), dim3(256), lds, s, a, n_groups, ncu, skew);
-        else hipLaunchKernelGGL((gemv_kernel<2, U, 512>), dim3(grid), dim3(512), lds, s, a, n_groups, ncu, skew);
+        if (per == 1) GEMV_GO(256); else GEMV_GO(512);
     } else switch (per) {
-        case 1: hipLaunchKernelGGL((gemv_kernel<MODE, U, 256>), dim3(grid), dim3(256), lds, s, a, n_groups, ncu, skew); break;
-        case 2: hipLaunchKernelGGL((gemv_kernel<MODE, U, 512>), dim3(grid), dim3(512), lds, s, a, n_groups, ncu, skew); break;
-        case 3: hipLaunchKernelGGL((gemv_kernel<MODE, U, 768>), dim3(grid), dim3(768), lds, s, a, n_groups, ncu, skew); break;
-        default: hipLaunchKernelGGL((gemv_kernel<MODE, U, 1024>), dim3(grid), dim3(1024), lds, s, a, n_groups, ncu, skew); break;
+        case 1: GEMV_GO(256); break;
+        case 2: GEMV_GO(512); break;
+        case 3: GEMV_GO(768); break;
+        default: GEMV_GO(1024); break;
     }
+#undef GEMV_GO
 }
 
 int launch_gemv(const GemvArgs& a, hipStream_t s) {
@@ -360,6 +424,7 @@ int launch_gemv(const GemvArgs& a, hipStream_t s) {
     int ncu = 0, per = 1;
     // mode 2: 8 waves per CU at most (the merge prologue; measured best)
     const int grid = balanced_grid(n_groups, &ncu, &per, a.mode == 2 ? 2 : GEMV_BPC);
+    VILA_REQUIRE(ncu <= GEMV_PLAN_MAX_CUS, "gemv: the CU map holds up to %d CUs (got %d)", GEMV_PLAN_MAX_CUS, ncu);
     size_t lds = ((size_t)a.K * 2 + 15) / 16 * 16 + 16;
     const bool short_k = a.K <= 3584;
     if (a.mode == 1) {
@@ -387,33 +452,46 @@ int launch_gemv(const GemvArgs& a, hipStream_t s) {
 // Group = 2 rows per wave: q/k heads -> the rotate-half pair {d, d+hd/2} of one head, v heads -> 2 consecutive rows.  cos/sin of the token's position come from the per-token table written by
 // decode_prologue_kernel (already rounded to bf16 like HF's cast of cos/sin to the activation dtype).
 // ------------------------------------------------------------------------------------------------
+// Arguments as in gemv_kernel: the weights, x, the gain, K, the head geometry and the CU map flat in front (14 dwords, preloaded); the rest in
+// QkvTail, fetched behind the first weight batch.  A row group splits into (head, pair) by a multiplication (gph_magic: gemv_plan.h udiv_magic).
+struct QkvTail {
+    const bf16_t* bqkv; bf16_t* q_out; bf16_t* kcache; bf16_t* vcache; const int32_t* pos_ptr; const float* rope_cs;
+    float eps; int max_ctx;
+};
+__device__ __forceinline__ void tail_here(const QkvTail& t) {
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("" :: "s"(t.bqkv), "s"(t.q_out), "s"(t.kcache), "s"(t.vcache), "s"(t.pos_ptr), "s"(t.rope_cs), "s"(t.eps), "s"(t.max_ctx));
+    __builtin_amdgcn_sched_barrier(0);
+}
 template <int U, int NT>
-__global__ __launch_bounds__(NT) void qkv_decode_kernel(QkvDecodeArgs p, int ncu) {
+__global__ __launch_bounds__(NT) void qkv_decode_kernel(const bf16_t* Wqkv, const bf16_t* x, const bf16_t* norm_w, int K, int hd, int nq, int nkv,
+                                                        unsigned gph_magic, int ncu_xr, int cf, int xq, QkvTail t) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     bf16_t* sx = (bf16_t*)smem;
-    float* scratch = (float*)(smem + ((p.K * 2 + 15) & ~15));
+    float* scratch = (float*)(smem + ((K * 2 + 15) & ~15));
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int hd = p.hd, half = hd >> 1;
+    const int half = hd >> 1;
     const int gph = half;                                      // groups (row pairs) per head
-    const int n_groups = (p.nq + 2 * p.nkv) * gph;
-    const int nch = p.K >> 3;
+    const int n_groups = (nq + 2 * nkv) * gph;
+    const int nch = K >> 3;
     constexpr int WPB = NT / 64;
-    const CuMap cm(n_groups, ncu > 0 ? ncu : 8, 0);
+    const GemvPlan cm{ncu_xr, cf, xq};
+    const int ncu = cm.ncu();
     const int cu = ncu > 0 ? (int)blockIdx.x : 0;
     const int cnt = ncu > 0 ? cm.count(cu) : 0;
     int j = wave;
-    const int stride = gridDim.x * WPB;
+    const int stride = cf;                                     // small grids: blocks x WPB
     int g = ncu > 0 ? (j < cnt ? cm.gid(cu, j) : n_groups) : blockIdx.x * WPB + wave;
     auto next_group = [&]() { if (ncu > 0) { j += WPB; g = j < cnt ? cm.gid(cu, j) : n_groups; } else g += stride; };
 
     int rows_i[2];
     const bf16_t* rows[2];
     auto rows_of = [&](int gg) {
-        const int head = gg / gph, gi = gg % gph;
-        if (head >= p.nq + p.nkv) { rows_i[0] = head * hd + gi * 2; rows_i[1] = rows_i[0] + 1; }   // v: two consecutive rows
+        const int head = (int)udiv_by_magic((unsigned)gg, gph_magic), gi = gg - head * gph;
+        if (head >= nq + nkv) { rows_i[0] = head * hd + gi * 2; rows_i[1] = rows_i[0] + 1; }   // v: two consecutive rows
         else { rows_i[0] = head * hd + gi; rows_i[1] = rows_i[0] + half; }                        // q/k: the rotate-half pair (d, d + hd/2)
-        rows[0] = p.Wqkv + (int64_t)rows_i[0] * p.K;
-        rows[1] = p.Wqkv + (int64_t)rows_i[1] * p.K;
+        rows[0] = Wqkv + (int64_t)rows_i[0] * K;
+        rows[1] = Wqkv + (int64_t)rows_i[1] * K;
     };
     // epilogue operands (position, the pair's biases, its RoPE row) are requested before the dot product, not after the reduction
     int e_pos = 0;
@@ -421,16 +499,16 @@ __global__ __launch_bounds__(NT) void qkv_decode_kernel(QkvDecodeArgs p, int ncu
     float e_c = 1.f, e_s = 0.f;
     auto epi_fetch = [&](int gg) {
         if (lane >= 2) return;
-        const int head = gg / gph, gi = gg % gph;
-        e_pos = *p.pos_ptr;
-        e_b0 = p.bqkv != nullptr ? p.bqkv[rows_i[0]] : (bf16_t)0;
-        e_b1 = p.bqkv != nullptr ? p.bqkv[rows_i[1]] : (bf16_t)0;
-        if (head < p.nq + p.nkv) { e_c = p.rope_cs[gi]; e_s = p.rope_cs[half + gi]; }
+        const int head = (int)udiv_by_magic((unsigned)gg, gph_magic), gi = gg - head * gph;
+        e_pos = *t.pos_ptr;
+        e_b0 = t.bqkv != nullptr ? t.bqkv[rows_i[0]] : (bf16_t)0;
+        e_b1 = t.bqkv != nullptr ? t.bqkv[rows_i[1]] : (bf16_t)0;
+        if (head < nq + nkv) { e_c = t.rope_cs[gi]; e_s = t.rope_cs[half + gi]; }
     };
     auto finish = [&](int gg, float (&acc)[2]) {
         if (lane >= 2) return;
-        const int head = gg / gph;
-        const bool is_v = head >= p.nq + p.nkv;
+        const int head = (int)udiv_by_magic((unsigned)gg, gph_magic);
+        const bool is_v = head >= nq + nkv;
         const int pos = e_pos;
         const float lo = bfround(acc[0] + bf2f_late(e_b0));
         const float hi = bfround(acc[1] + bf2f_late(e_b1));
@@ -440,25 +518,27 @@ __global__ __launch_bounds__(NT) void qkv_decode_kernel(QkvDecodeArgs p, int ncu
             out = lane ? bfround(bfround(hi * c) + bfround(lo * sn)) : bfround(bfround(lo * c) + bfround(-hi * sn));
         }
         const int row = rows_i[lane];
-        if (head < p.nq) {
-            p.q_out[row] = f2bf(out);
-        } else if (pos < p.max_ctx) {
-            const int kvh = is_v ? head - p.nq - p.nkv : head - p.nq;
-            bf16_t* dst = (is_v ? p.vcache : p.kcache) + ((int64_t)kvh * p.max_ctx + pos) * hd;
+        if (head < nq) {
+            t.q_out[row] = f2bf(out);
+        } else if (pos < t.max_ctx) {
+            const int kvh = is_v ? head - nq - nkv : head - nq;
+            bf16_t* dst = (is_v ? t.vcache : t.kcache) + ((int64_t)kvh * t.max_ctx + pos) * hd;
             dst[row - head * hd] = f2bf(out);
         }
     };
 
     Batch<2, U> b0;
     const bool has = g < n_groups;
-    if (has) { rows_of(g); load_batch<2, U>(rows, 0, lane, nch, b0); epi_fetch(g); }   // weights in front (gemv_kernel: no gain from the inputs first)
+    if (has) { rows_of(g); load_batch<2, U>(rows, 0, lane, nch, b0); }
+    tail_here(t);
+    if (has) epi_fetch(g);   // weights in front (gemv_kernel: no gain from the inputs first)
     STAGE_X_REGS(NT, st);
-    stage_x_issue<NT>(p.x, p.norm_w, p.K, STAGE_X_ARGS(st));
-    stage_x_finish<NT, true>(p.x, p.norm_w, p.eps, p.K, sx, scratch, STAGE_X_ARGS(st));   // LDS-only syncs: measured faster here (CHANGELOG)
+    stage_x_issue<NT>(x, norm_w, K, STAGE_X_ARGS(st));
+    stage_x_finish<NT, true>(x, norm_w, t.eps, K, sx, scratch, STAGE_X_ARGS(st));   // LDS-only syncs: measured faster here (CHANGELOG)
     if (has) {
         float acc[2] = {0.f, 0.f};
         fma_batch<2, U>(b0, sx, 0, lane, nch, acc);
-        wave_rows_dot<2, U>(rows, sx, p.K, lane, acc, 64 * U);
+        wave_rows_dot<2, U>(rows, sx, K, lane, acc, 64 * U);
         finish(g, acc);
         next_group();
     }
@@ -466,29 +546,37 @@ __global__ __launch_bounds__(NT) void qkv_decode_kernel(QkvDecodeArgs p, int ncu
         rows_of(g);
         epi_fetch(g);
         float acc[2] = {0.f, 0.f};
-        wave_rows_dot<2, U>(rows, sx, p.K, lane, acc, 0);
+        wave_rows_dot<2, U>(rows, sx, K, lane, acc, 0);
         finish(g, acc);
     }
 }
 
 template <int U>
-static void qkv_launch(int per, int grid, size_t lds, hipStream_t s, const QkvDecodeArgs& a, int ncu) {
+static void qkv_launch(int per, int grid, size_t lds, hipStream_t s, const QkvDecodeArgs& a, int n_groups, int ncu) {
+    GemvPlan pl{0, grid * 4, 0};                                  // small grids: 256-thread blocks walk with stride blocks x 4 waves
+    if (ncu > 0) pl = gemv_plan(n_groups, ncu, 0);
+    const unsigned magic = udiv_magic((unsigned)(a.hd / 2));
+    const QkvTail t{a.bqkv, a.q_out, a.kcache, a.vcache, a.pos_ptr, a.rope_cs, a.eps, a.max_ctx};
+#define QKV_GO(NT) hipLaunchKernelGGL((qkv_decode_kernel<U, NT>), dim3(grid), dim3(NT), lds, s, a.Wqkv, a.x, a.norm_w, a.K, a.hd, a.nq, a.nkv, magic, pl.ncu_xr, pl.cf, pl.xq, t)
     switch (per) {
-        case 1: hipLaunchKernelGGL((qkv_decode_kernel<U, 256>), dim3(grid), dim3(256), lds, s, a, ncu); break;
-        case 2: hipLaunchKernelGGL((qkv_decode_kernel<U, 512>), dim3(grid), dim3(512), lds, s, a, ncu); break;
-        case 3: hipLaunchKernelGGL((qkv_decode_kernel<U, 768>), dim3(grid), dim3(768), lds, s, a, ncu); break;
-        default: hipLaunchKernelGGL((qkv_decode_kernel<U, 1024>), dim3(grid), dim3(1024), lds, s, a, ncu); break;
+        case 1: QKV_GO(256); break;
+        case 2: QKV_GO(512); break;
+        case 3: QKV_GO(768); break;
+        default: QKV_GO(1024); break;
     }
+#undef QKV_GO
 }
 int launch_qkv_decode(const QkvDecodeArgs& a, hipStream_t s) {
-    VILA_REQUIRE(a.K % 8 == 0 && a.hd % 4 == 0 && a.rope_cs != nullptr, "qkv_decode: K=%d hd=%d", a.K, a.hd);
+    VILA_REQUIRE(a.K % 8 == 0 && a.hd % 4 == 0 && a.hd > 0 && a.rope_cs != nullptr, "qkv_decode: K=%d hd=%d", a.K, a.hd);
     const int n_groups = (a.nq + 2 * a.nkv) * (a.hd / 2);
+    VILA_REQUIRE(n_groups > 0 && (uint64_t)n_groups * (uint64_t)(a.hd / 2) < (1ull << 32), "qkv_decode: %d row groups of %d per head", n_groups, a.hd / 2);
     const size_t lds = ((size_t)a.K * 2 + 15) / 16 * 16 + 16;
     // one rotate-half pair per wave; K <= 3584: the whole row pair (14 x 16 B per lane) is in flight in ONE round trip
     int ncu = 0, per = 1;
     const int grid = balanced_grid(n_groups, &ncu, &per);
-    if (a.K <= 3584) qkv_launch<7>(per, grid, lds, s, a, ncu);
-    else qkv_launch<4>(per, grid, lds, s, a, ncu);
+    VILA_REQUIRE(ncu <= GEMV_PLAN_MAX_CUS, "qkv_decode: the CU map holds up to %d CUs (got %d)", GEMV_PLAN_MAX_CUS, ncu);
+    if (a.K <= 3584) qkv_launch<7>(per, grid, lds, s, a, n_groups, ncu);
+    else qkv_launch<4>(per, grid, lds, s, a, n_groups, ncu);
     VILA_LAUNCH_CHECK();
     return 0;
 }
