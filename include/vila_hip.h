@@ -276,6 +276,21 @@ typedef struct {
 size_t vila_llm_decode_verify_workspace_bytes(const VilaLlmShape* s, int n, int max_ctx);
 int vila_llm_decode_step_verify(const VilaLlmWeights* w, const VilaKvCache* cache, const VilaDecodeVerify* st,
                                 void* workspace, size_t workspace_bytes, vila_stream_t stream);
+/* The verify step for a SAMPLED request.  Draft and forward are the greedy step's launches (the logits are the same bits); only a[i] changes:
+ *   draw     a[i] = the token vila_sample_f32 returns for logits row i with the request's temperature / top_k / top_p / seed and the counter
+ *            pos + i — the position of the token row i consumes, which is the counter the solo sampled step uses at that position.  The draw is
+ *            the batched sampler's (vila_sample_batch_f32), bit for bit.
+ *   accept   the rule above with these a[i]: a draft is kept exactly when the draw hits it.
+ * The draw behind a position is a pure function of (logits bits, parameters, seed, counter), and a row's logits do not depend on the step it runs
+ * in, so the ids are exactly those of the same sampled session drafting nothing.  (HF's assisted sampling accepts a point-mass draft x with
+ * probability p(x); "the draw hits x" has that same probability, coupled to the request's fixed random stream.)
+ * `sp` describes ONE sequence: its four members are device arrays of ONE entry, and every row reads entry 0.  The host rewrites the four scalars
+ * per request; the captured graph stays.  temperature <= 0 makes every row a greedy row (largest logit, ties to the lower index: the greedy
+ * step's a[i]).  On the device top_k is clamped to 1..64 and top_p to (0, 1]; checking them is the host's business.
+ * Workspace: vila_llm_decode_verify_sample_workspace_bytes (the greedy step's plus the sampler's candidates and the n draws). */
+size_t vila_llm_decode_verify_sample_workspace_bytes(const VilaLlmShape* s, int n, int max_ctx);
+int vila_llm_decode_step_verify_sample(const VilaLlmWeights* w, const VilaKvCache* cache, const VilaDecodeVerify* st,
+                                       void* workspace, size_t workspace_bytes, const VilaBatchSampling* sp, vila_stream_t stream);
 /* The draft stage on its own (lookup mode): hist [*n_hist] -> token[1 .. *n_draft], the rest of token[1 .. n - 1] = token[0]. */
 int vila_prompt_lookup_draft(const int64_t* hist, const int32_t* n_hist, int max_ngram, int n, int64_t* token, int32_t* n_draft,
                              vila_stream_t stream);
@@ -544,6 +559,10 @@ int vila_llm_decode_step_batch_w4_sample(const VilaLlmWeights* w, const VilaLlmL
 /* vila_llm_decode_step_verify with the four projections of every layer read from `qlayers`; workspace of vila_llm_decode_verify_workspace_bytes */
 int vila_llm_decode_step_verify_w4(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers /*[host]*/, const VilaKvCache* cache,
                                    const VilaDecodeVerify* st, void* workspace, size_t workspace_bytes, vila_stream_t stream);
+/* vila_llm_decode_step_verify_sample likewise; workspace of vila_llm_decode_verify_sample_workspace_bytes, `sp` of ONE entry per array */
+int vila_llm_decode_step_verify_w4_sample(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers /*[host]*/, const VilaKvCache* cache,
+                                          const VilaDecodeVerify* st, void* workspace, size_t workspace_bytes, const VilaBatchSampling* sp,
+                                          vila_stream_t stream);
 
 /* W4A16 prefill GEMM (vila_amd/csrc/gemm_w4.hip) on the same packed buffers: y[M][N] = x[M][K] . W^T, x bf16 row stride K, y row stride N,
  * any M >= 1.  mode 0: (+bias)(+residual, row stride N; y may alias it); mode 1: W holds 2N interleaved gate/up rows, y = silu(Wg x) * (Wu x),

@@ -1,5 +1,5 @@
-"""Greedy speculative decoding, measured in one process on one GPU: the verify step (vila_llm_decode_step_verify, attn_decode.hip
-bdec_attn_shared_kernel) at NVILA-8B widths with seeded synthetic weights.
+"""Speculative decoding, greedy and sampled, measured in one process on one GPU: the verify step (vila_llm_decode_step_verify and its `_sample`
+form, attn_decode.hip bdec_attn_shared_kernel) at NVILA-8B widths with seeded synthetic weights.
 
   for bf16 and W4, 769 and 8192 cached keys, n = 4 / 8 / 16 rows per step:
     * ms per verify step (one hipGraph replay: draft + forward of n rows + accept),
@@ -8,6 +8,10 @@ bdec_attn_shared_kernel) at NVILA-8B widths with seeded synthetic weights.
     * tokens/s in candidate mode at 0 % acceptance (a candidate that is wrong everywhere: 1 token per step) and at 100 % (the candidate is the
       model's own output, recorded by a run that drafts nothing: n tokens per step).  These are the two ends; synthetic weights have no meaningful
       acceptance rate of their own.
+    * the sampled arm at temperature 0.2 / top_k 50 / top_p 0.9 (the server's default request): ms per sampled verify step beside the greedy one —
+      both sessions alive at once, their timing rounds alternating — the solo SAMPLED step, and the break-even against it.  sample_delta_us is
+      sampled minus greedy verify step: what the three sampler launches and the accept cost over the greedy pick and accept.  The batched sampler's
+      cost for the same three launches in the batched step is c - a = 50-72 us in profiles/batch_sample_bench.json, printed beside it.
 
     python tools/spec_decode_bench.py [--steps 10] [--iters 3] [--layers 28] [--out profiles/spec_decode_bench.json]
 
@@ -19,6 +23,7 @@ import json
 import os
 import statistics
 import sys
+from types import SimpleNamespace
 
 import torch
 
@@ -68,11 +73,16 @@ def batched_ms(llm, n, keys, steps, iters):
     return statistics.median(ts[1:])
 
 
-def solo_ms(llm, keys, steps, iters):
+SAMPLING = (0.2, 50, 0.9, 1)                         # temperature / top_k / top_p of the server's default request, a fixed seed
+BATCH_SAMPLER_US = (50, 72)                          # c - a of profiles/batch_sample_bench.json: the same three launches in the batched step
+
+
+def solo_ms(llm, keys, steps, iters, sampled=False):
     room = steps + 2
     g = torch.Generator(device="cuda").manual_seed(keys)
     e = torch.randn((1, keys, llm.lcfg.hidden_size), device="cuda", generator=g, dtype=torch.float32).mul_(0.02).to(torch.bfloat16)
-    llm.generate(inputs_embeds=e, max_new_tokens=room, eos_token_id=-1)                       # session + captured graph
+    kw = dict(do_sample=True, temperature=SAMPLING[0], top_k=SAMPLING[1], top_p=SAMPLING[2], seed=SAMPLING[3]) if sampled else {}
+    llm.generate(inputs_embeds=e, max_new_tokens=room, eos_token_id=-1, **kw)                 # session + captured graph
     torch.cuda.synchronize()
     st = llm._decode
     assert st is not None and st.graph is not None
@@ -86,34 +96,45 @@ def solo_ms(llm, keys, steps, iters):
 
 
 def verify_ms(llm, n, keys, steps, iters):
-    """-> (ms per step at 0 % acceptance, at 100 %, tokens per step seen at 0 %, at 100 %)"""
+    """-> {"greedy" | "sampled": (ms per step at 0 % acceptance, at 100 %, tokens per step seen at 0 %, at 100 %)}.  Both sessions live on one cache
+    (every step writes the K/V rows it reads at or past `keys` before it reads them) and their timing rounds alternate."""
     room = n * steps + n
     cache = llm.new_cache(((keys + room + 255) // 256) * 256)
     noise(cache, keys + n)
     llm._drop_session("_vdecode")
-    st = llm._verify_session(cache, n, room, 2)
+    arms = {}
+    for name in ("greedy", "sampled"):
+        st = llm._verify_session(cache, n, room, 2, sampled=name == "sampled")
+        llm._vdecode = None                              # keep this session alive beside the next one; dropped by hand below
+        if st.sampled:
+            llm._verify_set_sampling(st, SAMPLING)
 
-    def reset(n_cand):
-        st.pos.fill_(keys); st.n_out.zero_(); st.n_hist.fill_(1); st.token.fill_(17); st.n_cand.fill_(n_cand)
-    reset(0)
-    _capture(st, lambda: llm.verify_step(cache, st), lambda: reset(0))
-    # the model's own output from this state: n * steps replays that draft nothing
-    reset(0)
-    torch.cuda.synchronize()
-    replay(st.graph, st.stream, n * steps)
-    own = st.out_ids[:n * steps].clone()
-    out = []
-    for cand, n_cand in ((own + 1, n * steps), (own, n * steps)):     # wrong everywhere / right everywhere
-        st.cand[:n * steps].copy_(cand)
-        ts = []
+        def reset(n_cand, st=st):
+            st.pos.fill_(keys); st.n_out.zero_(); st.n_hist.fill_(1); st.token.fill_(17); st.n_cand.fill_(n_cand)
+        reset(0)
+        _capture(st, lambda st=st: llm.verify_step(cache, st), lambda reset=reset: reset(0))
+        # the model's own output from this state: n * steps replays that draft nothing
+        reset(0)
+        torch.cuda.synchronize()
+        replay(st.graph, st.stream, n * steps)
+        own = st.out_ids[:n * steps].clone()
+        arms[name] = SimpleNamespace(st=st, reset=reset, own=own, ts={0: [], 1: []}, toks={})
+    for which in (0, 1):                                 # candidate wrong everywhere / right everywhere
+        for a in arms.values():
+            a.st.cand[:n * steps].copy_(a.own if which else a.own + 1)
         for it in range(iters + 1):
-            reset(n_cand)
-            torch.cuda.synchronize()
-            ts.append(replay(st.graph, st.stream, steps) / steps)
-        out.append((statistics.median(ts[1:]), int(st.n_out.item()) / steps))
-    assert torch.equal(st.out_ids[:n * steps], own), "speculation changed the ids"
-    llm._drop_session("_vdecode")
-    return out[0][0], out[1][0], out[0][1], out[1][1]
+            for a in arms.values():                      # the arms alternate inside every round
+                a.reset(n * steps)
+                torch.cuda.synchronize()
+                a.ts[which].append(replay(a.st.graph, a.st.stream, steps) / steps)
+                a.toks[which] = int(a.st.n_out.item()) / steps
+    out = {}
+    for name, a in arms.items():
+        assert torch.equal(a.st.out_ids[:n * steps], a.own), f"speculation changed the {name} ids"
+        out[name] = (statistics.median(a.ts[0][1:]), statistics.median(a.ts[1][1:]), a.toks[0], a.toks[1])
+        llm._vdecode = a.st
+        llm._drop_session("_vdecode")
+    return out
 
 
 def main():
@@ -135,18 +156,30 @@ def main():
             llm.quantize_w4(keep_logical=False, batch_decode=True)
         for keys in KEYS:
             solo = solo_ms(llm, keys, a.steps, a.iters)
+            solo_s = solo_ms(llm, keys, a.steps, a.iters, sampled=True)
             for n in NS:
                 bat = batched_ms(llm, n, keys, a.steps, a.iters)
-                v0, v100, t0, t100 = verify_ms(llm, n, keys, a.steps, a.iters)
+                arms = verify_ms(llm, n, keys, a.steps, a.iters)
+                v0, v100, t0, t100 = arms["greedy"]
+                s0, s100, u0, u100 = arms["sampled"]
                 r = {"dtype": dtype, "keys": keys, "n": n, "solo_ms": round(solo, 4), "batched_ms": round(bat, 4), "verify_ms": round(v0, 4),
                      "verify_ms_all_accepted": round(v100, 4), "verify_over_batched": round(v0 / bat, 3), "break_even_accepted_per_step": round(v0 / solo - 1, 3),
                      "solo_tok_s": round(1e3 / solo, 1), "tok_s_0pct": round(t0 * 1e3 / v0, 1), "tok_s_100pct": round(t100 * 1e3 / v100, 1),
-                     "tokens_per_step_0pct": t0, "tokens_per_step_100pct": t100}
+                     "tokens_per_step_0pct": t0, "tokens_per_step_100pct": t100,
+                     "solo_sampled_ms": round(solo_s, 4), "verify_sampled_ms": round(s0, 4), "verify_sampled_ms_all_accepted": round(s100, 4),
+                     "sample_delta_us": round((s0 - v0) * 1e3, 1), "batch_sampler_c_minus_a_us": list(BATCH_SAMPLER_US),
+                     "break_even_accepted_per_step_sampled": round(s0 / solo_s - 1, 3), "solo_sampled_tok_s": round(1e3 / solo_s, 1),
+                     "sampled_tok_s_0pct": round(u0 * 1e3 / s0, 1), "sampled_tok_s_100pct": round(u100 * 1e3 / s100, 1),
+                     "sampled_tokens_per_step_0pct": u0, "sampled_tokens_per_step_100pct": u100}
                 rows.append(r)
                 print(json.dumps(r), flush=True)
     res = {"config": {"model": cfg.name, "layers": a.layers, "steps_per_timing": a.steps, "timings": a.iters,
                       "method": "HIP events around back-to-back graph replays, warm, median",
-                      "break_even_accepted_per_step": "verify_ms / solo_ms - 1", "verify_over_batched": "verify_ms / batched_ms at equal n and keys"},
+                      "break_even_accepted_per_step": "verify_ms / solo_ms - 1", "verify_over_batched": "verify_ms / batched_ms at equal n and keys",
+                      "sampling": {"temperature": SAMPLING[0], "top_k": SAMPLING[1], "top_p": SAMPLING[2]},
+                      "sample_delta_us": "verify_sampled_ms - verify_ms (0 % acceptance), greedy and sampled rounds alternating in one process",
+                      "break_even_accepted_per_step_sampled": "verify_sampled_ms / solo_sampled_ms - 1",
+                      "batch_sampler_c_minus_a_us": "range of c - a in profiles/batch_sample_bench.json: the sampler's three launches in the batched step"},
            "rows": rows}
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:

@@ -134,6 +134,11 @@ PROTOTYPES = {
     "vila_llm_decode_step_verify": (c_int, [C.POINTER(VilaLlmWeights), C.POINTER(VilaKvCache), C.POINTER(VilaDecodeVerify), c_void_p, c_size_t, c_void_p]),
     "vila_llm_decode_step_verify_w4": (c_int, [C.POINTER(VilaLlmWeights), C.POINTER(VilaLlmLayerW4), C.POINTER(VilaKvCache), C.POINTER(VilaDecodeVerify),
                                                c_void_p, c_size_t, c_void_p]),
+    "vila_llm_decode_verify_sample_workspace_bytes": (c_size_t, [C.POINTER(VilaLlmShape), c_int, c_int]),
+    "vila_llm_decode_step_verify_sample": (c_int, [C.POINTER(VilaLlmWeights), C.POINTER(VilaKvCache), C.POINTER(VilaDecodeVerify), c_void_p, c_size_t,
+                                                   C.POINTER(VilaBatchSampling), c_void_p]),
+    "vila_llm_decode_step_verify_w4_sample": (c_int, [C.POINTER(VilaLlmWeights), C.POINTER(VilaLlmLayerW4), C.POINTER(VilaKvCache),
+                                                      C.POINTER(VilaDecodeVerify), c_void_p, c_size_t, C.POINTER(VilaBatchSampling), c_void_p]),
     "vila_prompt_lookup_draft": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "vila_attn_decode_verify_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "vila_attn_decode_verify_bf16": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_float, c_void_p,

@@ -811,29 +811,48 @@ extern "C" int vila_llm_decode_step_batch_w4_sample(const VilaLlmWeights* w, con
     VILA_REQUIRE(qlayers != nullptr, "llm_decode_batch_w4: NULL argument");
     return decode_step_batch_impl(w, qlayers, cache, st, workspace, workspace_bytes, sp, stream);
 }
-// The verify step (greedy speculative decoding, decode_batch.hip bverify_step): the layer tables are the batched step's, the state is one sequence's.
+// The verify step (speculative decoding, decode_batch.hip bverify_step): the layer tables are the batched step's, the state is one sequence's.
+// sp != nullptr: the sampled form, whose four parameter arrays hold ONE entry each.
 static int decode_step_verify_impl(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers, const VilaKvCache* cache, const VilaDecodeVerify* st,
-                                   void* workspace, size_t workspace_bytes, vila_stream_t stream) {
+                                   void* workspace, size_t workspace_bytes, const VilaBatchSampling* sp, vila_stream_t stream) {
     const char* fn = qlayers != nullptr ? "llm_decode_verify_w4" : "llm_decode_verify";
     VILA_REQUIRE(w != nullptr && cache != nullptr && st != nullptr && workspace != nullptr, "%s: NULL argument", fn);
+    VILA_REQUIRE(sp == nullptr || (sp->temperature != nullptr && sp->top_k != nullptr && sp->top_p != nullptr && sp->seed != nullptr),
+                 "%s_sample: a sampling parameter array is NULL", fn);
+    const BatchSampling bs = sp != nullptr ? BatchSampling{sp->temperature, sp->top_k, sp->top_p, sp->seed} : BatchSampling{};
     BTables t{};
     VILA_TRY(blayer_tables(w, qlayers, fn, &t));
     BVerifyState v{st->n, st->slot, st->pos, st->token, st->n_draft, st->out_ids, st->n_out, st->max_out, st->logits, st->n_accept,
                    st->hist, st->n_hist, st->hist_cap, st->max_ngram, st->cand, st->n_cand};
     return bverify_step(t.m, t.layers.data(), B(cache->k), B(cache->v), cache->max_ctx, cache->n_slots, v, workspace, workspace_bytes, S(stream),
-                        qlayers != nullptr ? t.ql.data() : nullptr);
+                        qlayers != nullptr ? t.ql.data() : nullptr, sp != nullptr ? &bs : nullptr);
 }
 extern "C" size_t vila_llm_decode_verify_workspace_bytes(const VilaLlmShape* s, int n, int max_ctx) {
     return bverify_workspace_bytes(s->hidden, s->inter, s->q_heads * s->head_dim, s->head_dim, n, max_ctx);
 }
+extern "C" size_t vila_llm_decode_verify_sample_workspace_bytes(const VilaLlmShape* s, int n, int max_ctx) {
+    return bverify_sample_workspace_bytes(s->hidden, s->inter, s->q_heads * s->head_dim, s->head_dim, n, max_ctx);
+}
+extern "C" int vila_llm_decode_step_verify_sample(const VilaLlmWeights* w, const VilaKvCache* cache, const VilaDecodeVerify* st, void* workspace,
+                                                  size_t workspace_bytes, const VilaBatchSampling* sp, vila_stream_t stream) {
+    VILA_REQUIRE(sp != nullptr, "llm_decode_verify_sample: sampling parameters are NULL");
+    return decode_step_verify_impl(w, nullptr, cache, st, workspace, workspace_bytes, sp, stream);
+}
+extern "C" int vila_llm_decode_step_verify_w4_sample(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers, const VilaKvCache* cache,
+                                                     const VilaDecodeVerify* st, void* workspace, size_t workspace_bytes, const VilaBatchSampling* sp,
+                                                     vila_stream_t stream) {
+    VILA_REQUIRE(sp != nullptr, "llm_decode_verify_w4_sample: sampling parameters are NULL");
+    VILA_REQUIRE(qlayers != nullptr, "llm_decode_verify_w4: NULL argument");
+    return decode_step_verify_impl(w, qlayers, cache, st, workspace, workspace_bytes, sp, stream);
+}
 extern "C" int vila_llm_decode_step_verify(const VilaLlmWeights* w, const VilaKvCache* cache, const VilaDecodeVerify* st, void* workspace,
                                            size_t workspace_bytes, vila_stream_t stream) {
-    return decode_step_verify_impl(w, nullptr, cache, st, workspace, workspace_bytes, stream);
+    return decode_step_verify_impl(w, nullptr, cache, st, workspace, workspace_bytes, nullptr, stream);
 }
 extern "C" int vila_llm_decode_step_verify_w4(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers, const VilaKvCache* cache, const VilaDecodeVerify* st,
                                               void* workspace, size_t workspace_bytes, vila_stream_t stream) {
     VILA_REQUIRE(qlayers != nullptr, "llm_decode_verify_w4: NULL argument");
-    return decode_step_verify_impl(w, qlayers, cache, st, workspace, workspace_bytes, stream);
+    return decode_step_verify_impl(w, qlayers, cache, st, workspace, workspace_bytes, nullptr, stream);
 }
 // the verify step's draft stage and its attention on their own (operator level)
 extern "C" int vila_prompt_lookup_draft(const int64_t* hist, const int32_t* n_hist, int max_ngram, int n, int64_t* token, int32_t* n_draft,
@@ -934,7 +953,7 @@ extern "C" int vila_sample_batch_f32(const float* logits, int64_t ld_logits, int
                                      void* workspace, float* dist_out, vila_stream_t stream) {
     VILA_REQUIRE(sp != nullptr && logits != nullptr && out != nullptr && workspace != nullptr, "sample_batch: NULL argument");
     const BatchSampling bs{sp->temperature, sp->top_k, sp->top_p, sp->seed};
-    return launch_sample_batch(logits, ld_logits, n, vocab, bs, counter, out, workspace, dist_out, nullptr, nullptr, nullptr, 0, S(stream));
+    return launch_sample_batch(logits, ld_logits, n, vocab, bs, 1, counter, out, workspace, dist_out, nullptr, nullptr, nullptr, 0, S(stream));
 }
 
 // =================================================================================================

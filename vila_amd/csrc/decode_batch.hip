@@ -334,12 +334,14 @@ __global__ __launch_bounds__(64) void bdec_pick2_kernel(const float* __restrict_
 struct BStepBufs {
     bf16_t *x, *x2, *xn, *q, *ao, *act; float* rope_cs; float *part_o, *part_ml; float* pick_v; int* pick_i;
     int32_t* pos_rows;                                       // the verify step's per-row positions
+    void* smp_ws; int64_t* draws;                            // the sampled verify step's sampler candidates and its n draws
 };
 // The size functions below bound this layout: bdec_step_common_bytes counts every take() but the attention partials and pos_rows at its aligned size,
 // and each step adds its own term for those.  The partials are two separately aligned arrays (part_o, part_ml) where the batched step's term is one
 // aligned sum plus 256: align(a) + align(b) <= align(a + b) + 256, since rounding two parts up can overshoot rounding their sum by less than one
 // more unit.  The verify step's term is bverify_attn_workspace_bytes, the two aligned arrays themselves.  The 4096 on top is slack.
-static bool bdec_carve(void* workspace, size_t workspace_bytes, int n, int H, int F, int QS, int hd, int nq, int nsl, bool pos_rows, BStepBufs* b) {
+// draws: the sampled verify step's two arrays behind everything else, each counted at its aligned size by bverify_sample_workspace_bytes.
+static bool bdec_carve(void* workspace, size_t workspace_bytes, int n, int H, int F, int QS, int hd, int nq, int nsl, bool pos_rows, bool draws, BStepBufs* b) {
     char* wp = (char*)workspace; size_t off = 0;
     auto take = [&](size_t bytes) { off = align_up(off, 256); void* r = wp + off; off += bytes; return r; };
     b->x = (bf16_t*)take((size_t)n * H * 2);
@@ -354,6 +356,8 @@ static bool bdec_carve(void* workspace, size_t workspace_bytes, int n, int H, in
     b->pick_v = (float*)take((size_t)n * PICK_SLICES * 4);
     b->pick_i = (int*)take((size_t)n * PICK_SLICES * 4);
     b->pos_rows = pos_rows ? (int32_t*)take((size_t)n * 4) : nullptr;
+    b->smp_ws = draws ? take(sample_batch_workspace_bytes(n)) : nullptr;
+    b->draws = draws ? (int64_t*)take((size_t)n * 8) : nullptr;
     return off <= workspace_bytes;
 }
 // embed + rope table, the layers, lm_head -> logits [n][vocab].  Row i appends its K/V at position pos[i] of kcache/vcache + i * slot_stride (+ the
@@ -440,7 +444,7 @@ int bdecode_step(const BDecodeArgs& m, const BLayer* layers, bf16_t* kcache, bf1
     VILA_REQUIRE(workspace_bytes >= bdecode_workspace_bytes(H, F, QS, hd, n, max_ctx), "batched decode: workspace too small");
     VILA_REQUIRE(sampling == nullptr || sampling_ws != nullptr, "batched decode: the sampled pick needs its workspace");
     BStepBufs b{};
-    VILA_REQUIRE(bdec_carve(workspace, workspace_bytes, n, H, F, QS, hd, m.q_heads, form.nsl, false, &b), "batched decode: workspace layout");
+    VILA_REQUIRE(bdec_carve(workspace, workspace_bytes, n, H, F, QS, hd, m.q_heads, form.nsl, false, false, &b), "batched decode: workspace layout");
     const int64_t per_layer = (int64_t)n_slots * m.kv_heads * max_ctx * hd, slot_stride = (int64_t)m.kv_heads * max_ctx * hd;
     const float scale = 1.0f / sqrtf((float)hd);
     auto attn = [&](const bf16_t* q, bf16_t* kc, bf16_t* vc, bf16_t* ao) -> int {
@@ -458,7 +462,7 @@ int bdecode_step(const BDecodeArgs& m, const BLayer* layers, bf16_t* kcache, bf1
     float* pick_v = b.pick_v; int* pick_i = b.pick_i;
     // the pick: per-row sampling (sample.hip; greedy rows included, position = the draw's counter, read before it advances) or the greedy pair
     if (sampling != nullptr)
-        return launch_sample_batch(logits, m.vocab, n, m.vocab, *sampling, pos, token, sampling_ws, nullptr, pos, out_ids, n_out, max_out, s);
+        return launch_sample_batch(logits, m.vocab, n, m.vocab, *sampling, 1, pos, token, sampling_ws, nullptr, pos, out_ids, n_out, max_out, s);
     hipLaunchKernelGGL(bdec_pick1_kernel, dim3(PICK_SLICES, n), dim3(256), 0, s, logits, m.vocab, pick_v, pick_i);
     VILA_LAUNCH_CHECK();
     hipLaunchKernelGGL(bdec_pick2_kernel, dim3(n), dim3(64), 0, s, pick_v, pick_i, token, pos, out_ids, n_out, max_out);
@@ -466,13 +470,16 @@ int bdecode_step(const BDecodeArgs& m, const BLayer* layers, bf16_t* kcache, bf1
     return 0;
 }
 
-// ---- the verify step: greedy speculative decoding with lookup drafts -------------------------------------------------------------------
+// ---- the verify step: speculative decoding with lookup drafts, greedy or sampled ------------------------------------------------------------
 // One sequence, one slot.  token[0] is the last chosen token (not yet in the cache), token[1..n_draft] are guesses at what follows it.  The n rows run
 // as consecutive positions pos .. pos + n - 1 of the slot (slot_stride 0: row i's K/V lands at position pos + i), so row i's logits are the model's
 // answer to "what follows token[0..i]", and the guesses are accepted as far as the answers reproduce them.  Every accepted token is the greedy
 // token of its position, computed by the same arithmetic whatever the drafts were (attn_decode.hip, the shared form's invariance), so the ids are
 // those of drafting nothing.  Rows beyond 1 + n_draft are padding: they compute (the graph is fixed) and write K/V past the accepted length,
 // which a later step overwrites before any column may see it.
+// The sampled form changes only where a[i] comes from: row i DRAWS it with the batched sampler (sample.hip) from the request's parameters and seed
+// and the counter pos + i.  The solo sampled step draws the token behind position p with counter p from the same logits bits, so a[i] is again the
+// token the session would have chosen one by one, and "the draft equals the draw" keeps the ids those of drafting nothing.
 // The draft: HF PromptLookupCandidateGenerator on hist[0 : n_hist] (the ids so far, token[0] last) — for ngram = min(max_ngram, n_hist - 1) .. 1 the
 // EARLIEST window equal to the last ngram ids that has something behind it, and up to n - 1 ids from there; or, in candidate mode (cand != NULL and
 // *n_cand >= 0), cand[n_out + j]: the candidate's guess for the very output index the row decides, so a rejection re-aligns by itself.
@@ -521,8 +528,27 @@ int launch_verify_draft(const int64_t* hist, const int32_t* n_hist, int max_ngra
     VILA_LAUNCH_CHECK();
     return 0;
 }
-// The accept: wave i finishes row i's greedy pick a[i] (bdec_pick1_kernel's partials); m = the longest prefix of drafts with a[j] == token[j + 1];
-// a[0..m] go to out_ids and hist, the state moves m + 1 tokens and a[m] is the next token[0].  One block of n waves.
+// The accept rule, by ONE thread, on the rows' choices a[0..n-1] (greedy picks or draws): m = the longest prefix of drafts with a[j] == token[j + 1];
+// a[0..m] go to out_ids and hist, the state moves m + 1 tokens and a[m] is the next token[0].
+__device__ __forceinline__ void bver_accept(const int* a, int n, int64_t* __restrict__ token, const int32_t* __restrict__ n_draft, int32_t* __restrict__ pos,
+                                            int64_t* __restrict__ out_ids, int32_t* __restrict__ n_out, int max_out, int64_t* __restrict__ hist,
+                                            int32_t* __restrict__ n_hist, int hist_cap, int32_t* __restrict__ n_accept) {
+    int nd = *n_draft;
+    nd = nd < 0 ? 0 : (nd > n - 1 ? n - 1 : nd);
+    int m = 0;
+    while (m < nd && (int64_t)a[m] == token[m + 1]) ++m;
+    const int no = *n_out, nh = hist != nullptr ? *n_hist : 0;
+    for (int j = 0; j <= m; ++j) {
+        if (no + j < max_out) out_ids[no + j] = (int64_t)a[j];
+        if (hist != nullptr && nh + j < hist_cap) hist[nh + j] = (int64_t)a[j];
+    }
+    *n_out = no + m + 1;
+    if (hist != nullptr) *n_hist = nh + m + 1 < hist_cap ? nh + m + 1 : hist_cap;      // (a full history stops growing: later drafts are poorer, never wrong)
+    *pos = *pos + m + 1;
+    token[0] = (int64_t)a[m];
+    *n_accept = m;
+}
+// The greedy accept: wave i finishes row i's greedy pick a[i] (bdec_pick1_kernel's partials), then the rule.  One block of n waves.
 __global__ __launch_bounds__(1024) void bver_accept_kernel(const float* __restrict__ pv, const int* __restrict__ pi, int n, int64_t* __restrict__ token,
                                                            const int32_t* __restrict__ n_draft, int32_t* __restrict__ pos, int64_t* __restrict__ out_ids,
                                                            int32_t* __restrict__ n_out, int max_out, int64_t* __restrict__ hist, int32_t* __restrict__ n_hist,
@@ -538,28 +564,27 @@ __global__ __launch_bounds__(1024) void bver_accept_kernel(const float* __restri
     }
     if (lane == 0) a[row] = bi;
     __syncthreads();
-    if (threadIdx.x == 0) {
-        int nd = *n_draft;
-        nd = nd < 0 ? 0 : (nd > n - 1 ? n - 1 : nd);
-        int m = 0;
-        while (m < nd && (int64_t)a[m] == token[m + 1]) ++m;
-        const int no = *n_out, nh = hist != nullptr ? *n_hist : 0;
-        for (int j = 0; j <= m; ++j) {
-            if (no + j < max_out) out_ids[no + j] = (int64_t)a[j];
-            if (hist != nullptr && nh + j < hist_cap) hist[nh + j] = (int64_t)a[j];
-        }
-        *n_out = no + m + 1;
-        if (hist != nullptr) *n_hist = nh + m + 1 < hist_cap ? nh + m + 1 : hist_cap;      // (a full history stops growing: later drafts are poorer, never wrong)
-        *pos = *pos + m + 1;
-        token[0] = (int64_t)a[m];
-        *n_accept = m;
-    }
+    if (threadIdx.x == 0) bver_accept(a, n, token, n_draft, pos, out_ids, n_out, max_out, hist, n_hist, hist_cap, n_accept);
+}
+// The sampled accept: a[i] = draws[i], what the batched sampler drew for row i (one wave; n <= 16), then the same rule.
+__global__ __launch_bounds__(64) void bver_accept_draws_kernel(const int64_t* __restrict__ draws, int n, int64_t* __restrict__ token,
+                                                               const int32_t* __restrict__ n_draft, int32_t* __restrict__ pos, int64_t* __restrict__ out_ids,
+                                                               int32_t* __restrict__ n_out, int max_out, int64_t* __restrict__ hist,
+                                                               int32_t* __restrict__ n_hist, int hist_cap, int32_t* __restrict__ n_accept) {
+    __shared__ int a[16];
+    if (threadIdx.x < n && threadIdx.x < 16) a[threadIdx.x] = (int)draws[threadIdx.x];
+    __syncthreads();
+    if (threadIdx.x == 0) bver_accept(a, n, token, n_draft, pos, out_ids, n_out, max_out, hist, n_hist, hist_cap, n_accept);
 }
 size_t bverify_workspace_bytes(int H, int F, int QS, int hd, int n, int max_ctx) {
     return bdec_step_common_bytes(H, F, QS, hd, n) + bverify_attn_workspace_bytes(n, QS / hd, max_ctx) + align_up((size_t)n * 4, 256);   // + partials, pos_rows
 }
+// the sampled step's workspace: the greedy step's, the batched sampler's candidates for n rows, the n draws
+size_t bverify_sample_workspace_bytes(int H, int F, int QS, int hd, int n, int max_ctx) {
+    return align_up(bverify_workspace_bytes(H, F, QS, hd, n, max_ctx), 256) + align_up(sample_batch_workspace_bytes(n), 256) + align_up((size_t)(n > 0 ? n : 0) * 8, 256);
+}
 int bverify_step(const BDecodeArgs& m, const BLayer* layers, bf16_t* kcache, bf16_t* vcache, int max_ctx, int n_slots, const BVerifyState& st, void* workspace,
-                 size_t workspace_bytes, hipStream_t s, const BLayerW4* qlayers) {
+                 size_t workspace_bytes, hipStream_t s, const BLayerW4* qlayers, const BatchSampling* sampling) {
     const int H = m.hidden, F = m.inter, hd = m.head_dim, QS = m.q_heads * hd, n = st.n;
     VILA_REQUIRE(n >= 2 && n <= 16, "verify step: 2..16 rows per step (1 committed token + up to 15 drafts), got %d", n);
     VILA_REQUIRE(st.slot >= 0 && st.slot < n_slots, "verify step: slot %d of a cache with %d", st.slot, n_slots);
@@ -571,10 +596,12 @@ int bverify_step(const BDecodeArgs& m, const BLayer* layers, bf16_t* kcache, bf1
     VILA_REQUIRE(st.pos && st.token && st.n_draft && st.out_ids && st.n_out && st.logits && st.n_accept && st.max_out >= 1, "verify step: a NULL state member");
     VILA_REQUIRE(st.cand != nullptr || (st.hist != nullptr && st.n_hist != nullptr && st.hist_cap >= 1), "verify step: neither a history nor a candidate");
     VILA_REQUIRE(st.max_ngram >= 1, "verify step: max_ngram >= 1 (got %d)", st.max_ngram);
-    VILA_REQUIRE(workspace_bytes >= bverify_workspace_bytes(H, F, QS, hd, n, max_ctx), "verify step: workspace too small");
+    VILA_REQUIRE(workspace_bytes >= (sampling != nullptr ? bverify_sample_workspace_bytes(H, F, QS, hd, n, max_ctx) : bverify_workspace_bytes(H, F, QS, hd, n, max_ctx)),
+                 "verify step: workspace too small");
+    VILA_REQUIRE(sampling == nullptr || (sampling->temperature && sampling->top_k && sampling->top_p && sampling->seed), "verify step: a NULL sampling array");
     const int nsl = bverify_attn_slices(max_ctx);
     BStepBufs b{};
-    VILA_REQUIRE(bdec_carve(workspace, workspace_bytes, n, H, F, QS, hd, m.q_heads, nsl, true, &b), "verify step: workspace layout");
+    VILA_REQUIRE(bdec_carve(workspace, workspace_bytes, n, H, F, QS, hd, m.q_heads, nsl, true, sampling != nullptr, &b), "verify step: workspace layout");
     VILA_TRY(launch_verify_draft(st.hist, st.n_hist, st.max_ngram, st.cand, st.n_cand, st.n_out, n, st.token, st.n_draft, st.pos, b.pos_rows, s));
     const int64_t slot_elems = (int64_t)m.kv_heads * max_ctx * hd, per_layer = (int64_t)n_slots * slot_elems;
     const float scale = 1.0f / sqrtf((float)hd);
@@ -583,6 +610,15 @@ int bverify_step(const BDecodeArgs& m, const BLayer* layers, bf16_t* kcache, bf1
     };
     VILA_TRY(bdec_forward(m, layers, qlayers, kcache + st.slot * slot_elems, vcache + st.slot * slot_elems, per_layer, 0, max_ctx, n, b.pos_rows, st.token,
                           st.logits, b, s, attn));
+    if (sampling != nullptr) {
+        // row i draws a[i] with counter pos_rows[i] = pos + i (written by the draft kernel; pos moves only in the accept below) from entry 0 of the
+        // one-entry parameter arrays (stride 0), into the workspace; no state advance in the sampler
+        VILA_TRY(launch_sample_batch(st.logits, m.vocab, n, m.vocab, *sampling, 0, b.pos_rows, b.draws, b.smp_ws, nullptr, nullptr, nullptr, nullptr, 0, s));
+        hipLaunchKernelGGL(bver_accept_draws_kernel, dim3(1), dim3(64), 0, s, (const int64_t*)b.draws, n, st.token, st.n_draft, st.pos, st.out_ids, st.n_out,
+                           st.max_out, st.hist, st.n_hist, st.hist_cap, st.n_accept);
+        VILA_LAUNCH_CHECK();
+        return 0;
+    }
     hipLaunchKernelGGL(bdec_pick1_kernel, dim3(PICK_SLICES, n), dim3(256), 0, s, st.logits, m.vocab, b.pick_v, b.pick_i);
     VILA_LAUNCH_CHECK();
     hipLaunchKernelGGL(bver_accept_kernel, dim3(1), dim3(64 * n), 0, s, b.pick_v, b.pick_i, n, st.token, st.n_draft, st.pos, st.out_ids, st.n_out, st.max_out,

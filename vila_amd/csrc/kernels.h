@@ -68,8 +68,8 @@ int launch_sample(const float* logits, int n, float temperature, int top_k, floa
 // (out_ids[row][n_out[row]++] = token, pos[row] = counter[row] + 1)
 struct BatchSampling { const float* temperature; const int32_t* top_k; const float* top_p; const uint64_t* seed; };
 size_t sample_batch_workspace_bytes(int n);
-int launch_sample_batch(const float* logits, int64_t ld_logits, int n, int vocab, const BatchSampling& sp, const int32_t* counter, int64_t* out, void* workspace,
-                        float* dist_out, int32_t* adv_pos, int64_t* adv_out_ids, int32_t* adv_n_out, int max_out, hipStream_t s);
+int launch_sample_batch(const float* logits, int64_t ld_logits, int n, int vocab, const BatchSampling& sp, int sp_stride, const int32_t* counter, int64_t* out,
+                        void* workspace, float* dist_out, int32_t* adv_pos, int64_t* adv_out_ids, int32_t* adv_n_out, int max_out, hipStream_t s);
 // dynamic_s2 merge (s2.hip): tower output -> projector input, desc = device [n_blocks][6] {tile_base, bh, bw, i, j, single}
 int launch_s2_merge(const bf16_t* feats, bf16_t* out, const int32_t* desc, int n_blocks, int g, int C, int n_scales, const int* splits,
                     hipStream_t s);
@@ -197,9 +197,12 @@ struct BVerifyState {
     int64_t* hist; int32_t* n_hist; int hist_cap, max_ngram;
     const int64_t* cand; const int32_t* n_cand;
 };
+// sampling != nullptr: the sampled verify step — row i's a[i] is drawn by the batched sampler with counter pos + i from ONE-entry parameter arrays
+// (every row reads entry 0); the workspace is then bverify_sample_workspace_bytes
 size_t bverify_workspace_bytes(int H, int F, int QS, int hd, int n, int max_ctx);
+size_t bverify_sample_workspace_bytes(int H, int F, int QS, int hd, int n, int max_ctx);
 int bverify_step(const BDecodeArgs& m, const BLayer* layers, bf16_t* kcache, bf16_t* vcache, int max_ctx, int n_slots, const BVerifyState& st, void* workspace,
-                 size_t workspace_bytes, hipStream_t s, const BLayerW4* qlayers = nullptr);
+                 size_t workspace_bytes, hipStream_t s, const BLayerW4* qlayers = nullptr, const BatchSampling* sampling = nullptr);
 int launch_verify_draft(const int64_t* hist, const int32_t* n_hist, int max_ngram, const int64_t* cand, const int32_t* n_cand, const int32_t* n_out, int n,
                         int64_t* token, int32_t* n_draft, const int32_t* pos, int32_t* pos_rows, hipStream_t s);
 int launch_decode_prologue(const bf16_t* table, const int64_t* tok, bf16_t* out, int H, int64_t vocab, const int32_t* pos, float* rope_cs,

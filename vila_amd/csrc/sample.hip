@@ -67,10 +67,11 @@ __device__ void smp_max1024(uint64_t* keys) {
 
 // stage 1 / 2: candidates in, SMP_CAND best per block out.  in_keys == nullptr: read raw logits [n] (index = position);
 // otherwise read (key) candidates produced by the previous stage.  Rows of a batch lie on blockIdx.y (in_stride / out_stride elements apart);
-// row_temperature (nullable, [rows], device): a row whose temperature is not positive is a greedy row and keeps its largest key only.
+// row_temperature (nullable, device): row `row` reads entry row * param_stride (1: an entry per row; 0: every row reads entry 0 of a one-entry
+// array); a row whose temperature is not positive is a greedy row and keeps its largest key only.
 __global__ __launch_bounds__(256) void smp_select_kernel(const float* __restrict__ logits, const uint64_t* __restrict__ in_keys, int n, int per_block,
                                                          uint64_t* __restrict__ out_keys, int64_t in_stride, int64_t out_stride,
-                                                         const float* __restrict__ row_temperature) {
+                                                         const float* __restrict__ row_temperature, int param_stride) {
     __shared__ uint64_t keys[1024];
     const int row = blockIdx.y;
     const float* lr = logits != nullptr ? logits + row * in_stride : nullptr;
@@ -82,7 +83,7 @@ __global__ __launch_bounds__(256) void smp_select_kernel(const float* __restrict
         if (i < per_block && g < n) k = (kr != nullptr) ? kr[g] : smp_key(lr[g], g);
         keys[i] = k;
     }
-    if (row_temperature != nullptr && !(row_temperature[row] > 0.f)) smp_max1024(keys);       // block-uniform
+    if (row_temperature != nullptr && !(row_temperature[row * param_stride] > 0.f)) smp_max1024(keys);       // block-uniform
     else smp_sort1024(keys);
     if (threadIdx.x < SMP_CAND) out_keys[row * out_stride + blockIdx.x * SMP_CAND + threadIdx.x] = keys[threadIdx.x];
 }
@@ -147,13 +148,16 @@ __global__ __launch_bounds__(256) void smp_final_kernel(const uint64_t* __restri
 // of rows: temperature <= 0 = greedy row (the largest key: highest value, ties to the lower index).  top_k / top_p are clamped to 1..64 / (0, 1]
 // (the host validates; a bad device value must not index out of range).  adv_pos != nullptr: the state advance of the batched decode step
 // (bdec_pick2_kernel's), with `counter` read BEFORE the position moves (counter and adv_pos are the same array there: no __restrict__).
+// param_stride: 1 = row `row` reads entry `row` of the four parameter arrays (the batched step: one request per row); 0 = every row reads entry 0
+// (the sampled verify step: n rows of ONE request, arrays of one entry).  counter / out / prob_out / adv_* stay per row either way.
 __global__ __launch_bounds__(256) void smp_batch_final_kernel(const uint64_t* __restrict__ in_keys, int n_in, int64_t in_stride, const float* __restrict__ temperature,
                                                               const int32_t* __restrict__ top_k, const float* __restrict__ top_p, const uint64_t* __restrict__ seed,
                                                               const int32_t* counter, int64_t* __restrict__ out, float* __restrict__ prob_out,
-                                                              int32_t* adv_pos, int64_t* __restrict__ adv_out_ids, int32_t* __restrict__ adv_n_out, int max_out) {
+                                                              int32_t* adv_pos, int64_t* __restrict__ adv_out_ids, int32_t* __restrict__ adv_n_out, int max_out,
+                                                              int param_stride) {
     __shared__ uint64_t keys[1024];
-    const int row = blockIdx.x;
-    const float t = temperature[row];
+    const int row = blockIdx.x, prow = row * param_stride;
+    const float t = temperature[prow];
     const bool sampled = t > 0.f;                                   // block-uniform
     for (int i = threadIdx.x; i < 1024; i += 256) keys[i] = i < n_in ? in_keys[row * in_stride + i] : 0;
     if (sampled) smp_sort1024(keys); else smp_max1024(keys);
@@ -163,10 +167,10 @@ __global__ __launch_bounds__(256) void smp_batch_final_kernel(const uint64_t* __
     float* pr = prob_out != nullptr ? prob_out + (int64_t)row * 2 * SMP_CAND : nullptr;
     int tok;
     if (sampled) {
-        int k = top_k[row];
+        int k = top_k[prow];
         k = k < 1 ? 1 : (k > SMP_CAND ? SMP_CAND : k);
-        const float p = fminf(fmaxf(top_p[row], 1.17549435e-38f), 1.0f);
-        tok = smp_draw_wave(keys, lane, 1.0f / t, k, p, seed[row], ctr, pr);
+        const float p = fminf(fmaxf(top_p[prow], 1.17549435e-38f), 1.0f);
+        tok = smp_draw_wave(keys, lane, 1.0f / t, k, p, seed[prow], ctr, pr);
     } else {
         tok = smp_idx(keys[0]);
         if (pr != nullptr) { pr[lane] = lane == 0 ? 1.f : 0.f; ((int*)(pr + 64))[lane] = lane == 0 ? tok : -1; }
@@ -339,9 +343,9 @@ int launch_sample(const float* logits, int n, float temperature, int top_k, floa
     VILA_REQUIRE(per1 <= 1024, "sample: vocabulary of %d exceeds %d x 1024 entries", n, SMP_S1_BLOCKS);
     uint64_t* c1 = (uint64_t*)workspace;
     uint64_t* c2 = c1 + SMP_S1_BLOCKS * SMP_CAND;
-    hipLaunchKernelGGL(smp_select_kernel, dim3(SMP_S1_BLOCKS), dim3(256), 0, s, logits, (const uint64_t*)nullptr, n, per1, c1, (int64_t)0, (int64_t)0, (const float*)nullptr);
+    hipLaunchKernelGGL(smp_select_kernel, dim3(SMP_S1_BLOCKS), dim3(256), 0, s, logits, (const uint64_t*)nullptr, n, per1, c1, (int64_t)0, (int64_t)0, (const float*)nullptr, 0);
     VILA_LAUNCH_CHECK();
-    hipLaunchKernelGGL(smp_select_kernel, dim3(SMP_S2_BLOCKS), dim3(256), 0, s, (const float*)nullptr, (const uint64_t*)c1, SMP_S1_BLOCKS * SMP_CAND, 1024, c2, (int64_t)0, (int64_t)0, (const float*)nullptr);
+    hipLaunchKernelGGL(smp_select_kernel, dim3(SMP_S2_BLOCKS), dim3(256), 0, s, (const float*)nullptr, (const uint64_t*)c1, SMP_S1_BLOCKS * SMP_CAND, 1024, c2, (int64_t)0, (int64_t)0, (const float*)nullptr, 0);
     VILA_LAUNCH_CHECK();
     hipLaunchKernelGGL(smp_final_kernel, dim3(1), dim3(256), 0, s, (const uint64_t*)c2, SMP_S2_BLOCKS * SMP_CAND, 1.0f / temperature, top_k, top_p, seed, seed_dev, counter, out, prob_out);
     VILA_LAUNCH_CHECK();
@@ -352,27 +356,29 @@ int launch_sample(const float* logits, int n, float temperature, int top_k, floa
 // Rows lie on blockIdx.y.  Stage 1 cuts a row into cdiv(vocab, 1024) slices of (almost) 1024 logits — full sorts, where the solo path's fixed
 // 256 slices sort 594 logits and 430 pads each — stage 2 sorts 1024 candidates per block, stage 3 is one block per row.  The top-64 set under the
 // strict key order does not depend on the cut, and stage 3 draws with the solo sampler's own arithmetic (smp_draw_wave).
+// sp_stride: 1 = sp's arrays hold n entries, one per row; 0 = they hold ONE entry that every row reads (n rows of one request).
 static inline int smpb_s1(int vocab) { return cdiv(vocab, 1024); }
 static inline int smpb_s2(int vocab) { return cdiv(smpb_s1(vocab) * SMP_CAND, 1024); }
 size_t sample_batch_workspace_bytes(int n) { return (size_t)(n > 0 ? n : 0) * (SMP_S1_BLOCKS + SMP_S2_BLOCKS) * SMP_CAND * sizeof(uint64_t) + 256; }
 
-int launch_sample_batch(const float* logits, int64_t ld_logits, int n, int vocab, const BatchSampling& sp, const int32_t* counter, int64_t* out, void* workspace,
-                        float* dist_out, int32_t* adv_pos, int64_t* adv_out_ids, int32_t* adv_n_out, int max_out, hipStream_t s) {
+int launch_sample_batch(const float* logits, int64_t ld_logits, int n, int vocab, const BatchSampling& sp, int sp_stride, const int32_t* counter, int64_t* out,
+                        void* workspace, float* dist_out, int32_t* adv_pos, int64_t* adv_out_ids, int32_t* adv_n_out, int max_out, hipStream_t s) {
     VILA_REQUIRE(n >= 1 && n <= 16, "sample_batch: 1..16 rows (got %d)", n);
     VILA_REQUIRE(vocab > 0 && ld_logits >= vocab, "sample_batch: row stride %lld is below the vocabulary %d", (long long)ld_logits, vocab);
     VILA_REQUIRE(smpb_s1(vocab) <= SMP_S1_BLOCKS, "sample_batch: vocabulary of %d exceeds %d x 1024 entries", vocab, SMP_S1_BLOCKS);
     VILA_REQUIRE(sp.temperature != nullptr && sp.top_k != nullptr && sp.top_p != nullptr && sp.seed != nullptr, "sample_batch: a per-row parameter array is NULL");
+    VILA_REQUIRE(sp_stride == 0 || sp_stride == 1, "sample_batch: the parameter arrays hold one entry per row (stride 1) or one in all (0), got %d", sp_stride);
     VILA_REQUIRE(adv_pos == nullptr || (adv_out_ids != nullptr && adv_n_out != nullptr && max_out >= 1), "sample_batch: the state advance needs out_ids and n_out");
     const int s1 = smpb_s1(vocab), s2 = smpb_s2(vocab), per1 = cdiv(vocab, s1);
     uint64_t* c1 = (uint64_t*)workspace;
     uint64_t* c2 = c1 + (size_t)n * SMP_S1_BLOCKS * SMP_CAND;
-    hipLaunchKernelGGL(smp_select_kernel, dim3(s1, n), dim3(256), 0, s, logits, (const uint64_t*)nullptr, vocab, per1, c1, ld_logits, (int64_t)s1 * SMP_CAND, sp.temperature);
+    hipLaunchKernelGGL(smp_select_kernel, dim3(s1, n), dim3(256), 0, s, logits, (const uint64_t*)nullptr, vocab, per1, c1, ld_logits, (int64_t)s1 * SMP_CAND, sp.temperature, sp_stride);
     VILA_LAUNCH_CHECK();
     hipLaunchKernelGGL(smp_select_kernel, dim3(s2, n), dim3(256), 0, s, (const float*)nullptr, (const uint64_t*)c1, s1 * SMP_CAND, 1024, c2, (int64_t)s1 * SMP_CAND,
-                       (int64_t)s2 * SMP_CAND, sp.temperature);
+                       (int64_t)s2 * SMP_CAND, sp.temperature, sp_stride);
     VILA_LAUNCH_CHECK();
     hipLaunchKernelGGL(smp_batch_final_kernel, dim3(n), dim3(256), 0, s, (const uint64_t*)c2, s2 * SMP_CAND, (int64_t)s2 * SMP_CAND, sp.temperature, sp.top_k, sp.top_p, sp.seed,
-                       counter, out, dist_out, adv_pos, adv_out_ids, adv_n_out, max_out);
+                       counter, out, dist_out, adv_pos, adv_out_ids, adv_n_out, max_out, sp_stride);
     VILA_LAUNCH_CHECK();
     return 0;
 }

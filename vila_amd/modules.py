@@ -296,8 +296,13 @@ def _as_i64(u: int) -> int:
     return u - (1 << 64) if u >= (1 << 63) else u
 
 
-def _step_symbols(batch: bool, w4: bool, sampled: bool, verify: bool = False) -> Tuple[str, str]:
-    """(step, workspace query) of one decode step variant, composed the way the C ABI names them.  verify: the greedy verify step, whatever `batch`."""
+def _step_symbols(batch: bool, w4: bool, sampled: bool, verify: bool = False, verify_sample: bool = False) -> Tuple[str, str]:
+    """(step, workspace query) of one decode step variant, composed the way the C ABI names them.  verify: the greedy verify step, whatever `batch`.
+    verify_sample: the sampled verify step, whatever `batch`, `sampled` and `verify` — a spelling of its own, since `verify` with `sampled` stays the
+    refusal it always was (that pair names the greedy step asked to sample)."""
+    if verify_sample:
+        tail = ("_w4" if w4 else "") + "_sample"
+        return "vila_llm_decode_step_verify" + tail, "vila_llm_decode_verify_sample_workspace_bytes"
     if verify and sampled:
         raise ValueError("the verify step is greedy: it has no sampled variant")
     tail = ("_w4" if w4 else "") + ("_sample" if sampled else "")
@@ -657,10 +662,10 @@ class HipQwen2ForCausalLM(_HipModule):
             raise RuntimeError(f"{what}: the bf16 projection weights were freed by quantize_w4(release_bf16=True); only the W4A16 "
                                "prefill and decode can run on this model")
 
-    def _step(self, batch: bool, w4, cache, st, sp, verify: bool = False) -> None:
+    def _step(self, batch: bool, w4, cache, st, sp, verify: bool = False, verify_sample: bool = False) -> None:
         """One decode step on the current stream.  The variant is looked up at call time (`_step_symbols`): a caller may hold a session
         across quantize_w4.  w4: the W4Weights whose int4 layers the step reads, or None; sp: the sampling struct, or None for the greedy pick."""
-        name, _ = _step_symbols(batch, w4 is not None, sp is not None, verify)
+        name, _ = _step_symbols(batch, w4 is not None, sp is not None, verify, verify_sample)
         args = [C.byref(self._struct())] + ([w4.ptr] if w4 is not None else []) + [C.byref(cache.c), C.byref(st.c), st.ws.data_ptr(), st.ws.numel()]
         check(getattr(_lib.load(), name)(*args, *([C.byref(sp)] if sp is not None else []), ops._stream()), name)
 
@@ -936,7 +941,7 @@ class HipQwen2ForCausalLM(_HipModule):
                  max_length: Optional[int] = None, streamer=None, batch_sample: Optional[bool] = None,
                  prompt_lookup_num_tokens: Optional[int] = None, max_matching_ngram_size: Optional[int] = None,
                  prompt_ids: Optional[torch.Tensor] = None, draft_ids: Optional[torch.Tensor] = None, past_len: Optional[int] = None,
-                 prefill_chunk: Optional[int] = None, **kw):
+                 prefill_chunk: Optional[int] = None, spec_sample: Optional[bool] = None, **kw):
         """`llm.generate(inputs_embeds=, attention_mask=, **generation_kwargs)` as called at llava_arch.py:833 (HF semantics: returns ONLY the
         new tokens, [B, n_new]).  Greedy search or sampling (do_sample: temperature / top_k / top_p, HF order, on the device); explicit
         keyword arguments override `generation_config` (HF GenerationConfig-like: do_sample, temperature, top_k, top_p, max_new_tokens,
@@ -953,6 +958,12 @@ class HipQwen2ForCausalLM(_HipModule):
         lookup (sizes max_matching_ngram_size, default 2, down to 1) in `prompt_ids` (LongTensor, optional) followed by what has been generated;
         draft_ids (LongTensor: a predicted output, token for token) replaces the lookup, with k = 7 unless given.  Batch 1 and greedy only;
         forced_ids and return_logits are not served in this mode.
+        spec_sample (opt-in, also read from generation_config; default False): with do_sample=True, speculative decoding for a SAMPLED request
+        (`vila_llm_decode_step_verify_sample`).  The sampler is counter-based: the token behind position p is a pure function of (logits bits,
+        temperature, top_k, top_p, seed, p).  Row i of a step draws with counter pos + i, and a draft is accepted exactly when it equals that
+        draw, so the ids are bit for bit those of the same sampled session drafting nothing — no statistical argument involved.  (Not HF's
+        assisted-sampling rule: there a point-mass draft x is accepted with probability p(x); "the draw hits x" has the same probability,
+        coupled to the request's fixed random stream.)  top_k in 1..64; without spec_sample a sampled request is refused in this mode as ever.
         streamer = HF's `generate(streamer=...)` contract (what server.py:243 streams from): `put(LongTensor[1])` once per new token — the EOS
         included, nothing for a prompt given as embeddings — as the host learns of them (every 16 graph replays), then `end()`; batch size 1.
         past_len=P with cache=c (both required together; batch size 1): slot 0 of `c` already holds the K/V of the sequence's first P positions
@@ -974,8 +985,10 @@ class HipQwen2ForCausalLM(_HipModule):
         k_spec = pick(prompt_lookup_num_tokens, "prompt_lookup_num_tokens", None)
         if k_spec is not None or draft_ids is not None:
             k_spec = 7 if k_spec is None else int(k_spec)
-            if do_sample:
-                raise ValueError("prompt_lookup_num_tokens / draft_ids: speculative decoding here is greedy; do_sample=True is not supported with it")
+            spec_sample = bool(pick(spec_sample, "spec_sample", False))
+            if do_sample and not spec_sample:
+                raise ValueError("prompt_lookup_num_tokens / draft_ids: speculative decoding here is greedy; do_sample=True is not supported with it "
+                                 "(spec_sample=True opts a sampled request in)")
             if inputs_embeds.shape[0] != 1:
                 raise ValueError("prompt_lookup_num_tokens / draft_ids: speculative decoding serves batch size 1 (as HF's assisted generation does)")
             if not 1 <= k_spec <= 15:
@@ -985,8 +998,17 @@ class HipQwen2ForCausalLM(_HipModule):
                 raise ValueError(f"max_matching_ngram_size has to be a positive integer, but is {max_ngram}")
             if forced_ids is not None or return_logits:
                 raise ValueError("prompt_lookup_num_tokens / draft_ids: forced_ids and return_logits are not supported in this mode")
+            sampling = None
+            if do_sample:
+                if temperature <= 0:
+                    raise ValueError(f"`temperature` (={temperature}) has to be a strictly positive float, otherwise your next token scores will be invalid.")
+                if not 1 <= top_k <= 64:
+                    raise ValueError(f"spec_sample: the sampled verify step serves top_k in 1..64 (got top_k = {top_k})")
+                if not 0.0 < top_p <= 1.0:
+                    raise ValueError(f"`top_p` has to be a float > 0 and <= 1, but is {top_p}")
+                sampling = (temperature, top_k, top_p, int(self._fresh_seed() if seed is None else seed))
             return self._generate_verify(inputs_embeds, attention_mask, max_new_tokens, eos_token_id, k_spec, max_ngram, prompt_ids, draft_ids, cache, streamer,
-                                         past_len, prefill_chunk)
+                                         past_len, prefill_chunk, sampling)
         if do_sample and temperature <= 0:
             raise ValueError(f"`temperature` (={temperature}) has to be a strictly positive float, otherwise your next token scores will be invalid.")
         if do_sample and top_k < 0:
@@ -1137,7 +1159,7 @@ class HipQwen2ForCausalLM(_HipModule):
         out = out[None]
         return (out, torch.stack(step_logits)) if return_logits else out
 
-    # ---- greedy speculative decoding: lookup drafts, k + 1 rows of one sequence per step (vila_llm_decode_step_verify) --------------------
+    # ---- speculative decoding: lookup drafts, k + 1 rows of one sequence per step (vila_llm_decode_step_verify[_sample]) -------------------
     spec_trace = None           # diagnostics / tests: set to a list and _generate_verify syncs after every replay and appends its n_accept
 
     def _verify_refusal(self) -> Optional[str]:
@@ -1152,15 +1174,17 @@ class HipQwen2ForCausalLM(_HipModule):
             return "the verify step reads q/k/v as one fused [q + 2kv, hidden] buffer (refuse() re-establishes it)"
         return None
 
-    def _verify_session(self, cache, n: int, max_out: int, max_ngram: int):
-        """Device-resident state of a verify session (+ its captured hipGraph), keyed like `_decode_session`."""
+    def _verify_session(self, cache, n: int, max_out: int, max_ngram: int, sampled: bool = False):
+        """Device-resident state of a verify session (+ its captured hipGraph), keyed like `_decode_session`.  sampled: the session steps through
+        the `_sample` entry points (another graph, hence part of the key) and owns the request's four sampling parameters as ONE-entry device
+        tensors that `_verify_set_sampling` rewrites per request: neither the parameters nor the seed are baked into the graph."""
         w4 = self._w4_batched()
-        key = (cache.k.data_ptr(), cache.max_ctx, n, max_out, max_ngram, *self._weights_key())
+        key = (cache.k.data_ptr(), cache.max_ctx, n, max_out, max_ngram, bool(sampled), *self._weights_key())
         if self._vdecode is not None and self._vdecode.key == key:
             return self._vdecode
         self._drop_session("_vdecode")
         dev, lib, w = self.device, _lib.load(), self._struct()
-        st = SimpleNamespace(key=key, cache=cache, graph=None, n=n, max_out=max_out, w4=w4)
+        st = SimpleNamespace(key=key, cache=cache, graph=None, n=n, max_out=max_out, w4=w4, sampled=bool(sampled), sp=None)
         i32 = lambda m: torch.zeros(m, device=dev, dtype=torch.int32)
         with torch.inference_mode(False):
             st.pos, st.n_draft, st.n_out, st.n_accept, st.n_hist, st.n_cand = i32(1), i32(1), i32(1), i32(1), i32(1), i32(1)
@@ -1169,8 +1193,14 @@ class HipQwen2ForCausalLM(_HipModule):
             st.cand = torch.zeros(max_out, device=dev, dtype=torch.int64)
             st.hist = torch.zeros(cache.max_ctx + max_out + 1, device=dev, dtype=torch.int64)
             st.logits = torch.zeros((n, self.lcfg.vocab_size), device=dev, dtype=torch.float32)
-            ws_bytes = getattr(lib, _step_symbols(True, w4, False, verify=True)[1])
+            ws_bytes = getattr(lib, _step_symbols(True, w4, False, verify=not sampled, verify_sample=bool(sampled))[1])
             st.ws = torch.empty((ws_bytes(C.byref(w.shape), n, cache.max_ctx),), device=dev, dtype=torch.uint8)
+            if sampled:                                             # ONE entry each: every row of a step reads entry 0
+                st.s_temperature = torch.zeros(1, device=dev, dtype=torch.float32)
+                st.s_top_k = torch.full((1,), 50, device=dev, dtype=torch.int32)
+                st.s_top_p = torch.ones(1, device=dev, dtype=torch.float32)
+                st.s_seed = torch.zeros(1, device=dev, dtype=torch.int64)                   # bit pattern of a uint64 seed
+                st.sp = _lib.VilaBatchSampling(st.s_temperature.data_ptr(), st.s_top_k.data_ptr(), st.s_top_p.data_ptr(), st.s_seed.data_ptr())
         st.c = _lib.VilaDecodeVerify(n, 0, st.pos.data_ptr(), st.token.data_ptr(), st.n_draft.data_ptr(), st.out_ids.data_ptr(), st.n_out.data_ptr(), max_out,
                                      st.logits.data_ptr(), st.n_accept.data_ptr(), st.hist.data_ptr(), st.n_hist.data_ptr(), st.hist.numel(), max_ngram,
                                      st.cand.data_ptr(), st.n_cand.data_ptr())
@@ -1178,28 +1208,41 @@ class HipQwen2ForCausalLM(_HipModule):
         self._vdecode = st
         return st
 
+    @staticmethod
+    def _verify_set_sampling(st, sampling) -> None:
+        """Write a request's (temperature, top_k, top_p, seed) into a sampled verify session's one-entry device tensors: the next replay reads them."""
+        t, k, p, seed = sampling
+        st.s_temperature.fill_(float(t))
+        st.s_top_k.fill_(int(k))
+        st.s_top_p.fill_(float(p))
+        st.s_seed.fill_(_as_i64(seed))
+
     def verify_step(self, cache, st) -> None:
-        """One verify step on the current stream: draft, forward of st.n rows, accept."""
+        """One verify step on the current stream: draft, forward of st.n rows, pick or draw, accept."""
         if not st.w4:
             self._require_bf16("the bf16 verify step")
-        self._step(True, self._w4 if st.w4 else None, cache, st, None, verify=True)
+        self._step(True, self._w4 if st.w4 else None, cache, st, st.sp if st.sampled else None, verify=not st.sampled, verify_sample=st.sampled)
 
     def _generate_verify(self, inputs_embeds, attention_mask, max_new_tokens, eos_token_id, k, max_ngram, prompt_ids, draft_ids, cache, streamer,
-                         past_len=None, prefill_chunk=None):
-        """generate() for one greedy sequence with the verify step: prefill as `_generate_solo`, first token from the prefill, then graph replays
-        that each append 1 .. k + 1 tokens.  The host cuts at EOS and at max_new_tokens (a step may overshoot by up to k)."""
+                         past_len=None, prefill_chunk=None, sampling=None):
+        """generate() for one sequence with the verify step: prefill as `_generate_solo`, first token from the prefill, then graph replays
+        that each append 1 .. k + 1 tokens.  The host cuts at EOS and at max_new_tokens (a step may overshoot by up to k).
+        sampling: None (greedy) or (temperature, top_k in 1..64, top_p, seed): the first token is drawn from the prefill's last row with counter
+        S - 1, as `_generate_solo` draws it, and the steps draw with the positions of the tokens they consume (S, S + 1, ...)."""
         why = self._verify_refusal()
         if why is not None:
             raise ValueError("prompt_lookup_num_tokens / draft_ids: " + why)
         def admit(c):
             if c.max_ctx > self.BATCH_MAX_CTX:
                 raise ValueError(f"prompt_lookup_num_tokens / draft_ids: the verify step serves caches up to {self.BATCH_MAX_CTX} positions (got {c.max_ctx})")
-        S, cache, r, _ = self._prefill_one(inputs_embeds, attention_mask, max_new_tokens, cache, admit, past_len, prefill_chunk)
+        S, cache, r, last = self._prefill_one(inputs_embeds, attention_mask, max_new_tokens, cache, admit, past_len, prefill_chunk)
         dev, n = inputs_embeds.device, k + 1
         eos_set = _eos_set(eos_token_id, self.lcfg.eos_token_id)
-        first = ops.argmax(r.last_logits[0])
+        first = ops.argmax(r.last_logits[0]) if sampling is None else ops.sample(r.last_logits[0], *sampling, counter=last)
         need = max_new_tokens - 1                                   # tokens wanted from the steps
-        st = self._verify_session(cache, n, max(max_new_tokens, 1) + k, max_ngram)
+        st = self._verify_session(cache, n, max(max_new_tokens, 1) + k, max_ngram, sampling is not None)
+        if sampling is not None:
+            self._verify_set_sampling(st, sampling)
         # the history the lookup starts from: the prompt's ids (its tail, if longer than the room) and the first token
         room = st.hist.numel() - st.max_out - 1
         pids = torch.zeros(0, dtype=torch.int64, device=dev) if prompt_ids is None else prompt_ids.reshape(-1).to(device=dev, dtype=torch.int64)[-room:]

@@ -390,11 +390,13 @@ def _eos_of(tokenizer, eos_token_id=None):
 
 def generate_content(model, tokenizer, prompt: Union[str, Sequence[Any]], max_new_tokens: int = 128, system: Optional[str] = None,
                      eos_token_id=None, device: Optional[str] = None, temperature: float = 0.0, top_p: float = 1.0, top_k: int = 50,
-                     seed: Optional[int] = None, streamer=None, prompt_lookup_num_tokens: Optional[int] = None) -> str:
+                     seed: Optional[int] = None, streamer=None, prompt_lookup_num_tokens: Optional[int] = None, spec_sample: bool = False) -> str:
     """Text + images in, decoded reply out — the contract of `LlavaLlamaModel.generate_content` for image / text prompts.
     temperature > 0 samples (server.py:185-187: do_sample = temperature > 0, with the request's top_p and HF's default top_k = 50).
-    prompt_lookup_num_tokens=k (greedy requests only, ignored for a sampled one): speculative decoding with k lookup drafts per step
-    (`llm.generate(prompt_lookup_num_tokens=)`); the reply is the greedy reply.
+    prompt_lookup_num_tokens=k: speculative decoding with k lookup drafts per step (`llm.generate(prompt_lookup_num_tokens=)`); the reply is
+    the greedy reply.  A sampled request ignores it unless spec_sample=True (default False), which passes both on
+    (`llm.generate(do_sample=True, prompt_lookup_num_tokens=k, spec_sample=True)`, top_k in 1..64): the reply is then the one the same sampled
+    request gives without drafts, a draft being accepted exactly when the request's own draw hits it.
     streamer: a `TextStream` (or any HF streamer) that receives the new tokens while they are generated (`llm.generate(streamer=...)`)."""
     cfg = model.cfg
     dev = device or str(model.device)
@@ -405,6 +407,8 @@ def generate_content(model, tokenizer, prompt: Union[str, Sequence[Any]], max_ne
     gen = dict(max_new_tokens=max_new_tokens, eos_token_id=eos)
     if temperature and temperature > 0:
         gen.update(do_sample=True, temperature=float(temperature), top_p=float(top_p), top_k=int(top_k), seed=seed)
+        if spec_sample and prompt_lookup_num_tokens is not None:
+            gen.update(prompt_lookup_num_tokens=int(prompt_lookup_num_tokens), spec_sample=True)
     elif prompt_lookup_num_tokens is not None:
         gen.update(prompt_lookup_num_tokens=int(prompt_lookup_num_tokens))
     if streamer is not None:
@@ -435,7 +439,7 @@ class ChatSession:
     So the next turn's new tokens open with that last token, then the end-of-turn marker if the reply was cut by max_new_tokens rather than by it,
     the separator and the new user turn in the Qwen2 chat form (`chat_text`, the template every NVILA recipe runs).  Media of a later turn are
     encoded and spliced for the new part only.  gen_defaults / `ask(**gen)`: keyword arguments of `llm.generate` (do_sample, temperature, top_k,
-    top_p, seed, prompt_lookup_num_tokens, streamer, ...)."""
+    top_p, seed, prompt_lookup_num_tokens, spec_sample, streamer, ...)."""
 
     TURN_END = "<|im_end|>"
 
@@ -941,7 +945,7 @@ def continuous_batching(model) -> bool:
 
 def create_app(model, tokenizer, model_name: str = "NVILA-8B", batch_window_s: Optional[float] = None, max_batch: int = 8,
                stream_timeout_s: Optional[float] = 600.0, batch_sampled: bool = False, max_ctx: int = 2048,
-               prompt_lookup_num_tokens: Optional[int] = None):
+               prompt_lookup_num_tokens: Optional[int] = None, spec_sample: bool = False):
     """FastAPI app with the reference's POST /chat/completions (server.py:171-290).  Import-time optional: needs fastapi + pydantic.
     batch_window_s: when set (any value), requests go through a batcher whose ONE worker thread owns the model: `ContinuousBatcher` (greedy
     requests join / leave the batched decode step between steps; sampled ones run solo on the same thread) where the model has the batched
@@ -952,7 +956,10 @@ def create_app(model, tokenizer, model_name: str = "NVILA-8B", batch_window_s: O
     max_ctx (ContinuousBatcher only): positions per KV slot of the batched session, up to 32768.  The default 2048 keeps the KV memory as it was;
     a larger value lets long prompts (dynamic_s2's 2304 image tokens, video, multi-image chats) take a row instead of running solo.
     prompt_lookup_num_tokens=k: greedy requests that this app runs solo (not through a batcher) decode speculatively with k lookup drafts per
-    step; their replies are the greedy replies.  None (default): every request takes the path it always took."""
+    step; their replies are the greedy replies.  None (default): every request takes the path it always took.
+    spec_sample=True (with prompt_lookup_num_tokens): sampled requests that run solo — the default request — speculate as well when their top_k
+    lies in 1..64 (the sampled verify step's range); their replies are those of the same sampled request without drafts.  Other sampled
+    requests, and every sampled request without the flag, stay non-speculative."""
     from fastapi import FastAPI
     from fastapi.responses import JSONResponse, StreamingResponse
 
@@ -1007,6 +1014,9 @@ def create_app(model, tokenizer, model_name: str = "NVILA-8B", batch_window_s: O
         request."""
         with model_lock, torch.inference_mode():
             kw = {} if prompt_lookup_num_tokens is None else dict(prompt_lookup_num_tokens=prompt_lookup_num_tokens)
+            top_k = 50                                  # the endpoint carries no top_k: a solo request samples with generate_content's default
+            if spec_sample and kw and temperature and temperature > 0 and 1 <= top_k <= 64:
+                kw.update(spec_sample=True, top_k=top_k)
             return generate_content(model, tokenizer, parts, max_new_tokens=n, system=system, temperature=temperature, top_p=top_p, streamer=streamer, **kw)
 
     async def chat_completions(request):
