@@ -240,6 +240,40 @@ int vila_attn_decode_batch_bf16(const void* q, int64_t ldq, const void* kcache, 
                                 void* o, int64_t ldo, int n_rows, int q_heads, int kv_heads, int max_ctx, float scale,
                                 void* workspace, size_t workspace_bytes, vila_stream_t stream);
 
+/* Batched decode over a shared prompt prefix: several rows of a batch (ten questions about one video, n samples of one prompt) begin with the same
+ * S positions, and the step reads their K/V once for all rows.  The cache has one slot more than the batch has rows, the PREFIX SLOT; its keys
+ * 0 .. S - 1 are the common start.  S (`shared_len`, a device scalar, a multiple of 256 — the kernels round it down to one inside the slot) and the
+ * per-row flags `uses` are read on the device, so one captured hipGraph serves any S and any mix of rows.
+ *   uses[i] != 0  row i attends keys 0 .. S - 1 of the prefix slot and keys S .. pos[i] of its own slot i (pos[i] >= S is the host's duty).  Positions
+ *                 stay absolute: RoPE uses pos[i] and the step's K/V lands at position pos[i] of slot i, as in the plain step.  Rows 0 .. S - 1 of
+ *                 slot i are never read.
+ *   uses[i] == 0  an ordinary row: keys 0 .. pos[i] of slot i, with the bits of vila_attn_decode_batch_bf16 in its walking form at the same slice count.
+ * S = 0 or all flags 0 is an ordinary session.  Rows of the prefix slot at or beyond S are never read by a step (the host may stage a prefill there).
+ * A sharing row's output does not depend on n, its row index or the other rows.  GQA groups of 1, 2, 4, 7 or 8, n <= 16, caches up to 32768. */
+typedef struct {
+    int prefix_slot;            /* slot of the cache that holds the prefix: n <= prefix_slot < cache->n_slots */
+    const int32_t* shared_len;  /* device scalar S */
+    const int32_t* uses;        /* device [n] */
+} VilaDecodePrefix;
+/* The attention alone (operator level): vila_attn_decode_batch_bf16's arguments, plus the cache's slot count, the prefix slot, the two device arrays
+ * and shared_len_host = S where the host knows it (refused unless a multiple of 256 within max_ctx) or -1.  Three launches; the private phase is always
+ * the walking form, and both slice counts follow vila_decode_batch_force_slices. */
+size_t vila_attn_decode_batch_prefix_workspace_bytes(int n_rows, int q_heads, int max_ctx);
+int vila_attn_decode_batch_prefix_bf16(const void* q, int64_t ldq, const void* kcache, const void* vcache, int64_t slot_stride, int n_slots,
+                                       int prefix_slot, const int32_t* shared_len, int shared_len_host, const int32_t* uses, const int32_t* pos,
+                                       void* o, int64_t ldo, int n_rows, int q_heads, int kv_heads, int max_ctx, float scale,
+                                       void* workspace, size_t workspace_bytes, vila_stream_t stream);
+/* The batched steps on such a session: vila_llm_decode_step_batch{,_sample} with the descriptor.  cache->n_slots counts the prefix slot
+ * (1 <= n <= min(16, n_slots - 1)); the workspace is the prefix step's, and a plain step's workspace is refused before anything is enqueued.
+ * The W4 pair is declared with the W4 steps below. */
+size_t vila_llm_decode_batch_prefix_workspace_bytes(const VilaLlmShape* s, int n, int max_ctx);
+size_t vila_llm_decode_batch_prefix_sample_workspace_bytes(const VilaLlmShape* s, int n, int max_ctx);
+int vila_llm_decode_step_batch_prefix(const VilaLlmWeights* w, const VilaKvCache* cache, const VilaDecodeBatch* st, const VilaDecodePrefix* prefix,
+                                      void* workspace, size_t workspace_bytes, vila_stream_t stream);
+int vila_llm_decode_step_batch_prefix_sample(const VilaLlmWeights* w, const VilaKvCache* cache, const VilaDecodeBatch* st,
+                                             const VilaDecodePrefix* prefix, void* workspace, size_t workspace_bytes,
+                                             const VilaBatchSampling* sp, vila_stream_t stream);
+
 /* Greedy speculative decoding with lookup drafts (HF generate(prompt_lookup_num_tokens=k)): one step runs n = k + 1 consecutive positions of ONE
  * sequence in ONE cache slot and keeps as many tokens as the model itself would have chosen one by one.  Three stages, all on the device, so one
  * hipGraph replay is one speculative step:
@@ -556,6 +590,15 @@ size_t vila_llm_decode_batch_w4_sample_workspace_bytes_ctx(const VilaLlmShape* s
 int vila_llm_decode_step_batch_w4_sample(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers /*[host]*/, const VilaKvCache* cache,
                                          const VilaDecodeBatch* st, void* workspace, size_t workspace_bytes, const VilaBatchSampling* sp,
                                          vila_stream_t stream);
+/* the W4 steps of a session with a shared prompt prefix (VilaDecodePrefix) */
+size_t vila_llm_decode_batch_prefix_w4_workspace_bytes(const VilaLlmShape* s, int n, int max_ctx);
+size_t vila_llm_decode_batch_prefix_w4_sample_workspace_bytes(const VilaLlmShape* s, int n, int max_ctx);
+int vila_llm_decode_step_batch_prefix_w4(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers /*[host]*/, const VilaKvCache* cache,
+                                         const VilaDecodeBatch* st, const VilaDecodePrefix* prefix, void* workspace, size_t workspace_bytes,
+                                         vila_stream_t stream);
+int vila_llm_decode_step_batch_prefix_w4_sample(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers /*[host]*/, const VilaKvCache* cache,
+                                                const VilaDecodeBatch* st, const VilaDecodePrefix* prefix, void* workspace, size_t workspace_bytes,
+                                                const VilaBatchSampling* sp, vila_stream_t stream);
 /* vila_llm_decode_step_verify with the four projections of every layer read from `qlayers`; workspace of vila_llm_decode_verify_workspace_bytes */
 int vila_llm_decode_step_verify_w4(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers /*[host]*/, const VilaKvCache* cache,
                                    const VilaDecodeVerify* st, void* workspace, size_t workspace_bytes, vila_stream_t stream);

@@ -63,6 +63,10 @@ class VilaDecodeBatch(C.Structure):
                 ("logits", c_void_p)]
 
 
+class VilaDecodePrefix(C.Structure):
+    _fields_ = [("prefix_slot", c_int), ("shared_len", c_void_p), ("uses", c_void_p)]
+
+
 class VilaDecodeVerify(C.Structure):
     _fields_ = [("n", c_int), ("slot", c_int), ("pos", c_void_p), ("token", c_void_p), ("n_draft", c_void_p), ("out_ids", c_void_p), ("n_out", c_void_p),
                 ("max_out", c_int), ("logits", c_void_p), ("n_accept", c_void_p), ("hist", c_void_p), ("n_hist", c_void_p), ("hist_cap", c_int),
@@ -130,6 +134,22 @@ PROTOTYPES = {
     "vila_attn_decode_batch_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "vila_attn_decode_batch_bf16": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int,
                                             c_float, c_void_p, c_size_t, c_void_p]),
+    "vila_attn_decode_batch_prefix_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "vila_attn_decode_batch_prefix_bf16": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                                   c_int64, c_int, c_int, c_int, c_int, c_float, c_void_p, c_size_t, c_void_p]),
+    "vila_llm_decode_batch_prefix_workspace_bytes": (c_size_t, [C.POINTER(VilaLlmShape), c_int, c_int]),
+    "vila_llm_decode_batch_prefix_sample_workspace_bytes": (c_size_t, [C.POINTER(VilaLlmShape), c_int, c_int]),
+    "vila_llm_decode_batch_prefix_w4_workspace_bytes": (c_size_t, [C.POINTER(VilaLlmShape), c_int, c_int]),
+    "vila_llm_decode_batch_prefix_w4_sample_workspace_bytes": (c_size_t, [C.POINTER(VilaLlmShape), c_int, c_int]),
+    "vila_llm_decode_step_batch_prefix": (c_int, [C.POINTER(VilaLlmWeights), C.POINTER(VilaKvCache), C.POINTER(VilaDecodeBatch), C.POINTER(VilaDecodePrefix),
+                                                  c_void_p, c_size_t, c_void_p]),
+    "vila_llm_decode_step_batch_prefix_sample": (c_int, [C.POINTER(VilaLlmWeights), C.POINTER(VilaKvCache), C.POINTER(VilaDecodeBatch),
+                                                         C.POINTER(VilaDecodePrefix), c_void_p, c_size_t, C.POINTER(VilaBatchSampling), c_void_p]),
+    "vila_llm_decode_step_batch_prefix_w4": (c_int, [C.POINTER(VilaLlmWeights), C.POINTER(VilaLlmLayerW4), C.POINTER(VilaKvCache), C.POINTER(VilaDecodeBatch),
+                                                     C.POINTER(VilaDecodePrefix), c_void_p, c_size_t, c_void_p]),
+    "vila_llm_decode_step_batch_prefix_w4_sample": (c_int, [C.POINTER(VilaLlmWeights), C.POINTER(VilaLlmLayerW4), C.POINTER(VilaKvCache),
+                                                            C.POINTER(VilaDecodeBatch), C.POINTER(VilaDecodePrefix), c_void_p, c_size_t,
+                                                            C.POINTER(VilaBatchSampling), c_void_p]),
     "vila_llm_decode_verify_workspace_bytes": (c_size_t, [C.POINTER(VilaLlmShape), c_int, c_int]),
     "vila_llm_decode_step_verify": (c_int, [C.POINTER(VilaLlmWeights), C.POINTER(VilaKvCache), C.POINTER(VilaDecodeVerify), c_void_p, c_size_t, c_void_p]),
     "vila_llm_decode_step_verify_w4": (c_int, [C.POINTER(VilaLlmWeights), C.POINTER(VilaLlmLayerW4), C.POINTER(VilaKvCache), C.POINTER(VilaDecodeVerify),

@@ -715,14 +715,17 @@ static int decode_step_impl(const VilaLlmWeights* w, const VilaLlmLayerW4* ql, c
 // *workspace_bytes shrinks to the greedy size and `out` points at the tail.
 struct BatchSamplingWs { const BatchSampling* sp; void* ws; };
 static int batch_sampling_of(const VilaBatchSampling* sp, const VilaLlmShape* sh, int n, int max_ctx, void* workspace, size_t* workspace_bytes,
-                             BatchSampling* bs, BatchSamplingWs* out) {
+                             BatchSampling* bs, BatchSamplingWs* out, bool prefix = false) {
     out->sp = nullptr; out->ws = nullptr;
     if (sp == nullptr) return 0;
     VILA_REQUIRE(sp->temperature != nullptr && sp->top_k != nullptr && sp->top_p != nullptr && sp->seed != nullptr,
                  "llm_decode_batch_sample: a per-row parameter array is NULL");
     VILA_REQUIRE(n >= 1 && n <= 16, "llm_decode_batch_sample: 1..16 sequences (got %d)", n);
     VILA_REQUIRE(max_ctx >= 1 && max_ctx <= BDEC_MAX_CTX, "llm_decode_batch_sample: caches up to %d positions (got %d)", BDEC_MAX_CTX, max_ctx);
-    const size_t head = align_up(bdecode_workspace_bytes(sh->hidden, sh->inter, sh->q_heads * sh->head_dim, sh->head_dim, n, max_ctx), 256);
+    const size_t head = align_up(prefix ? bdecode_prefix_workspace_bytes(sh->hidden, sh->inter, sh->q_heads * sh->head_dim, sh->head_dim, n, max_ctx)
+                                        : bdecode_workspace_bytes(sh->hidden, sh->inter, sh->q_heads * sh->head_dim, sh->head_dim, n, max_ctx), 256);
+    VILA_REQUIRE(!prefix || *workspace_bytes >= head + sample_batch_workspace_bytes(n),
+                 "llm_decode_batch_prefix_sample: the step needs the workspace of vila_llm_decode_batch_prefix*_sample_workspace_bytes (%d positions)", max_ctx);
     VILA_REQUIRE(max_ctx <= BDEC_SHORT_CTX || *workspace_bytes >= head + sample_batch_workspace_bytes(n),
                  "llm_decode_batch_sample: caches beyond 2048 positions need the workspace of vila_llm_decode_batch*_sample_workspace_bytes_ctx (%d positions)",
                  max_ctx);
@@ -779,17 +782,53 @@ static int blayer_tables(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers,
 // (gemv_w4_batch.hip) and embed, norms, the fused q|k|v biases and the bf16 lm_head come from `w`, whose projection pointers are not read (empty
 // after quantize_w4(release_bf16=True)).  sp != nullptr: a per-row pick (sample.hip's batched sampler) instead of the greedy pair; everything
 // before the pick is the same launches.
+// px != nullptr: the step of a session with a shared prompt prefix (attn_decode.hip): cache->n_slots counts the prefix slot, and the workspace is the
+// prefix step's, which a plain one never reaches.
 static int decode_step_batch_impl(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers, const VilaKvCache* cache, const VilaDecodeBatch* st,
-                                  void* workspace, size_t workspace_bytes, const VilaBatchSampling* sp, vila_stream_t stream) {
+                                  void* workspace, size_t workspace_bytes, const VilaBatchSampling* sp, vila_stream_t stream,
+                                  const VilaDecodePrefix* px = nullptr) {
     const char* fn = qlayers != nullptr ? "llm_decode_batch_w4" : "llm_decode_batch";
     VILA_REQUIRE(w != nullptr && cache != nullptr && st != nullptr && workspace != nullptr, "%s: NULL argument", fn);
     BTables t{};
     VILA_TRY(blayer_tables(w, qlayers, fn, &t));
     BatchSampling bs{};
     BatchSamplingWs sw{};
-    VILA_TRY(batch_sampling_of(sp, &w->shape, st->n, cache->max_ctx, workspace, &workspace_bytes, &bs, &sw));
+    VILA_TRY(batch_sampling_of(sp, &w->shape, st->n, cache->max_ctx, workspace, &workspace_bytes, &bs, &sw, px != nullptr));
+    const BPrefix bp = px != nullptr ? BPrefix{px->prefix_slot, px->shared_len, px->uses} : BPrefix{};
     return bdecode_step(t.m, t.layers.data(), B(cache->k), B(cache->v), cache->max_ctx, cache->n_slots, st->n, st->pos, st->token, st->out_ids, st->n_out,
-                        st->max_out, st->logits, workspace, workspace_bytes, S(stream), qlayers != nullptr ? t.ql.data() : nullptr, sw.sp, sw.ws);
+                        st->max_out, st->logits, workspace, workspace_bytes, S(stream), qlayers != nullptr ? t.ql.data() : nullptr, sw.sp, sw.ws,
+                        px != nullptr ? &bp : nullptr);
+}
+// the four steps of a prefix session and their workspace sizes (two sizes, greedy and sampled, as above)
+static size_t decode_batch_prefix_ws(const VilaLlmShape* s, int n, int max_ctx, bool sample) {
+    const size_t b = bdecode_prefix_workspace_bytes(s->hidden, s->inter, s->q_heads * s->head_dim, s->head_dim, n, max_ctx);
+    return sample ? align_up(b, 256) + sample_batch_workspace_bytes(n) : b;
+}
+extern "C" size_t vila_llm_decode_batch_prefix_workspace_bytes(const VilaLlmShape* s, int n, int max_ctx) { return decode_batch_prefix_ws(s, n, max_ctx, false); }
+extern "C" size_t vila_llm_decode_batch_prefix_sample_workspace_bytes(const VilaLlmShape* s, int n, int max_ctx) { return decode_batch_prefix_ws(s, n, max_ctx, true); }
+extern "C" size_t vila_llm_decode_batch_prefix_w4_workspace_bytes(const VilaLlmShape* s, int n, int max_ctx) { return decode_batch_prefix_ws(s, n, max_ctx, false); }
+extern "C" size_t vila_llm_decode_batch_prefix_w4_sample_workspace_bytes(const VilaLlmShape* s, int n, int max_ctx) { return decode_batch_prefix_ws(s, n, max_ctx, true); }
+extern "C" int vila_llm_decode_step_batch_prefix(const VilaLlmWeights* w, const VilaKvCache* cache, const VilaDecodeBatch* st, const VilaDecodePrefix* prefix,
+                                                 void* workspace, size_t workspace_bytes, vila_stream_t stream) {
+    VILA_REQUIRE(prefix != nullptr, "llm_decode_batch_prefix: the prefix descriptor is NULL");
+    return decode_step_batch_impl(w, nullptr, cache, st, workspace, workspace_bytes, nullptr, stream, prefix);
+}
+extern "C" int vila_llm_decode_step_batch_prefix_sample(const VilaLlmWeights* w, const VilaKvCache* cache, const VilaDecodeBatch* st,
+                                                        const VilaDecodePrefix* prefix, void* workspace, size_t workspace_bytes, const VilaBatchSampling* sp,
+                                                        vila_stream_t stream) {
+    VILA_REQUIRE(prefix != nullptr && sp != nullptr, "llm_decode_batch_prefix_sample: the prefix descriptor or the sampling parameters are NULL");
+    return decode_step_batch_impl(w, nullptr, cache, st, workspace, workspace_bytes, sp, stream, prefix);
+}
+extern "C" int vila_llm_decode_step_batch_prefix_w4(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers, const VilaKvCache* cache, const VilaDecodeBatch* st,
+                                                    const VilaDecodePrefix* prefix, void* workspace, size_t workspace_bytes, vila_stream_t stream) {
+    VILA_REQUIRE(prefix != nullptr && qlayers != nullptr, "llm_decode_batch_prefix_w4: NULL argument");
+    return decode_step_batch_impl(w, qlayers, cache, st, workspace, workspace_bytes, nullptr, stream, prefix);
+}
+extern "C" int vila_llm_decode_step_batch_prefix_w4_sample(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers, const VilaKvCache* cache,
+                                                           const VilaDecodeBatch* st, const VilaDecodePrefix* prefix, void* workspace, size_t workspace_bytes,
+                                                           const VilaBatchSampling* sp, vila_stream_t stream) {
+    VILA_REQUIRE(prefix != nullptr && qlayers != nullptr && sp != nullptr, "llm_decode_batch_prefix_w4_sample: NULL argument");
+    return decode_step_batch_impl(w, qlayers, cache, st, workspace, workspace_bytes, sp, stream, prefix);
 }
 extern "C" int vila_llm_decode_step_batch(const VilaLlmWeights* w, const VilaKvCache* cache, const VilaDecodeBatch* st,
                                           void* workspace, size_t workspace_bytes, vila_stream_t stream) {
@@ -943,6 +982,15 @@ extern "C" int vila_attn_decode_oproj_w4(const void* q, const void* kslot, const
                                          size_t workspace_bytes, vila_stream_t stream) {
     VILA_REQUIRE(Wq != nullptr && Wsz != nullptr, "attn_decode_oproj_w4: NULL argument");
     return attn_decode_oproj(q, kslot, vslot, pos, nullptr, Wq, Wsz, residual, y, N, q_heads, kv_heads, max_ctx, scale, workspace, workspace_bytes, stream);
+}
+// the prefix session's attention alone (operator level): shared_len_host = S where the host knows it, -1 where only the device does
+extern "C" size_t vila_attn_decode_batch_prefix_workspace_bytes(int n_rows, int q_heads, int max_ctx) { return bprefix_attn_workspace_bytes(n_rows, q_heads, max_ctx); }
+extern "C" int vila_attn_decode_batch_prefix_bf16(const void* q, int64_t ldq, const void* kcache, const void* vcache, int64_t slot_stride, int n_slots,
+                                                  int prefix_slot, const int32_t* shared_len, int shared_len_host, const int32_t* uses, const int32_t* pos,
+                                                  void* o, int64_t ldo, int n_rows, int q_heads, int kv_heads, int max_ctx, float scale, void* workspace,
+                                                  size_t workspace_bytes, vila_stream_t stream) {
+    return bprefix_attn(B(q), ldq, B(kcache), B(vcache), slot_stride, n_slots, prefix_slot, shared_len, shared_len_host, uses, pos, (bf16_t*)o, ldo, n_rows,
+                        q_heads, kv_heads, max_ctx, scale, workspace, workspace_bytes, S(stream));
 }
 extern "C" void vila_decode_batch_force_slices(int nsl) { bdecode_force_slices(nsl); }
 extern "C" int vila_decode_batch_slices(int max_ctx) { return bdecode_attn_slices(max_ctx); }

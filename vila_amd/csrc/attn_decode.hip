@@ -346,7 +346,15 @@ struct BAttnArgs {
     const int32_t* pos;                         // [rows]: keys 0 .. pos inclusive
     float* part_o; float* part_ml;              // [rows][nkv][NSL][G][128], [rows][nkv][NSL][G][2]
     int nq, nkv, max_ctx, nsl; int64_t row_stride, o_row_stride, slot_stride; float scale;   // row_stride: q rows, o_row_stride: o rows
+    // a prefix session (bdec_attn_walk_kernel<G, true>, bdec_attn_prefix_merge_kernel; unread by every other kernel): the shared length, the rows' flags,
+    // the prefix phase's partials [rows][nkv][psl][G][128] + [..][2]
+    const int32_t* shared_len; const int32_t* uses; const float* pfx_o; const float* pfx_ml; int psl;
 };
+// the shared length a prefix session's kernels work with: whole chunks inside the slot, whatever the scalar says
+__device__ __forceinline__ int bdec_shared_keys(const int32_t* shared_len, int max_ctx) {
+    const int S = *shared_len;
+    return (S < 0 ? 0 : (S < max_ctx ? S : max_ctx)) & ~255;
+}
 // the 16 waves' partials (so [16][G][128], sml [16][G][2] in LDS, published by a barrier) -> the slice's partial in the workspace
 template <int G>
 __device__ __forceinline__ void bdec_slice_partial(const BAttnArgs& p, const float* so, const float* sml, int row, int kvh, int slice, int tid) {
@@ -473,7 +481,11 @@ __global__ __launch_bounds__(128) void bdec_attn_merge_kernel(BAttnArgs p, int G
 // K's request where it is written only while registers allow; at G = 7 / 8 it moves it down to V's (pinning it with a sched_barrier made it spill
 // the loaded K, 140 B per lane), and about 10 loop-invariant offsets live in scratch (40 - 56 B per lane; G <= 4: none).  Loads to keys past the
 // row's context are redirected to its last key rather than predicated.  The tail is the short form's: 16-wave merge in LDS, partial [rows][nkv][nsl][G][128] + [..][2], merge launch.
-template <int G>
+// PREFIX (a session with a shared prompt prefix, see bdec_attn_shared_kernel<G, NT, true> below): the private phase.  A row with uses[row] != 0 starts
+// behind the shared chunks, c0 = S >> 8, and slice s walks chunks c0 + s, c0 + s + nsl, ... of its own slot; rows 0 .. S - 1 of that slot are never
+// read (the redirect of a load past the context goes to the row's LAST key, which is at or behind S).  A row with uses[row] == 0 has c0 = 0 and runs
+// the arithmetic of the plain form, operation for operation.
+template <int G, bool PREFIX = false>
 __global__ __launch_bounds__(1024) void bdec_attn_walk_kernel(BAttnArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* so = (float*)smem;                   // [16 waves][G][128]
@@ -484,7 +496,9 @@ __global__ __launch_bounds__(1024) void bdec_attn_walk_kernel(BAttnArgs p) {
     const int pos1 = p.pos[row] + 1;
     const int nkeys = pos1 < p.max_ctx ? pos1 : p.max_ctx;      // never past the slot, whatever the state says
     const int active = (nkeys + 255) >> 8;
-    if (slice >= active) return;                                 // block-uniform: this slice owns no chunk and writes nothing
+    int first = slice;                                           // the slice's first chunk
+    if constexpr (PREFIX) first += p.uses[row] != 0 ? bdec_shared_keys(p.shared_len, p.max_ctx) >> 8 : 0;
+    if (first >= active) return;                                 // block-uniform: this slice owns no chunk and writes nothing
     const bf16_t* kb = p.kcache + (int64_t)row * p.slot_stride + (int64_t)kvh * p.max_ctx * 128;
     const bf16_t* vb = p.vcache + (int64_t)row * p.slot_stride + (int64_t)kvh * p.max_ctx * 128;
     const bf16_t* qrow = p.q + (int64_t)row * p.row_stride + kvh * G * 128;
@@ -511,8 +525,8 @@ __global__ __launch_bounds__(1024) void bdec_attn_walk_kernel(BAttnArgs p) {
         }
     };
     u32x4 kc[4], vc[4];
-    load_k(slice, kc);
-    load_v(slice, vc);
+    load_k(first, kc);
+    load_v(first, vc);
     if (tid < 256) {
         const int r = tid >> 4, c = tid & 15;
         const u32x4 v = r < G ? *(const u32x4*)(qrow + r * 128 + c * 8) : (u32x4){0u, 0u, 0u, 0u};
@@ -526,7 +540,7 @@ __global__ __launch_bounds__(1024) void bdec_attn_walk_kernel(BAttnArgs p) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) o[g][e] = 0.f;
 #pragma unroll 1
-    for (int chunk = slice; chunk < active; chunk += p.nsl) {
+    for (int chunk = first; chunk < active; chunk += p.nsl) {
         asm volatile("" : "+v"(qoff));                           // keeps the Q fragments in LDS: hoisted out of the loop they cost 16 registers
         f32x4 sc = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -694,11 +708,14 @@ typedef __attribute__((ext_vector_type(4))) short bf16x4s;
 struct BSharedArgs {
     const bf16_t* q; bf16_t* o;                 // [n][ldq], [n][ldo]
     const bf16_t* kslot; const bf16_t* vslot;   // one layer's slot [nkv][max_ctx][128]
-    const int32_t* pos;                         // device scalar: tokens in the cache = position of row 0
+    const int32_t* pos;                         // device scalar: tokens in the cache = position of row 0 (PREFIX: the shared length S)
     float* part_o; float* part_ml;              // [n][nkv][nsl][G][128], [n][nkv][nsl][G][2]
     int n, nq, nkv, max_ctx, nsl; int64_t ldq, ldo; float scale;
 };
-template <int G, int NT>
+// PREFIX: the prefix phase of a session whose rows share a prompt prefix (bdecode_prefix_attn below).  The n rows are rows of DIFFERENT sequences; the slot
+// is the session's prefix slot, and every column's limit is S - 1: uniform, whole chunks only (S is read on the device and rounded down to a multiple
+// of 256 inside the slot; S = 0: every block returns).  Nothing else changes, so the invariance above holds with "position" read as S.
+template <int G, int NT, bool PREFIX = false>
 __global__ __launch_bounds__(512) void bdec_attn_shared_kernel(BSharedArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* so = (float*)smem;                   // [8 waves][16 cols][128]
@@ -707,8 +724,8 @@ __global__ __launch_bounds__(512) void bdec_attn_shared_kernel(BSharedArgs p) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int kvh = blockIdx.x, slice = blockIdx.y, col0 = blockIdx.z * (NT * 16);
     const int ncols = p.n * G;
-    const int pos0 = *p.pos;
-    const int hi = pos0 + p.n - 1 < p.max_ctx - 1 ? pos0 + p.n - 1 : p.max_ctx - 1;      // the last key any row of the step sees
+    const int pos0 = PREFIX ? bdec_shared_keys(p.pos, p.max_ctx) - 1 : *p.pos;
+    const int hi = PREFIX ? pos0 : (pos0 + p.n - 1 < p.max_ctx - 1 ? pos0 + p.n - 1 : p.max_ctx - 1);      // the last key any row of the step sees
     const int active = (hi >> 8) + 1;
     if (slice >= active || hi < 0) return;                      // block-uniform: this slice owns no chunk and writes nothing
     const bf16_t* kb = p.kslot + (int64_t)kvh * p.max_ctx * 128;
@@ -747,7 +764,7 @@ __global__ __launch_bounds__(512) void bdec_attn_shared_kernel(BSharedArgs p) {
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
         const int col = col0 + t * 16 + l15, row = col / G;
-        lim[t] = col < ncols ? (pos0 + row < p.max_ctx - 1 ? pos0 + row : p.max_ctx - 1) : -1;
+        lim[t] = col < ncols ? (PREFIX ? hi : (pos0 + row < p.max_ctx - 1 ? pos0 + row : p.max_ctx - 1)) : -1;
         m[t] = -INFINITY; l[t] = 0.f;
 #pragma unroll
         for (int e = 0; e < 8; ++e) acc[t][e] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -858,29 +875,31 @@ __global__ __launch_bounds__(128) void bdec_attn_shared_merge_kernel(BSharedArgs
     }
     p.o[(int64_t)row * p.ldo + h * 128 + d] = f2bf(O / L);
 }
-template <int G, int NT>
+// (PREFIX: the slice launch alone; the prefix session's merge runs behind its private phase)
+template <int G, int NT, bool PREFIX>
 static int launch_bdec_shared_t(const BSharedArgs& a, int groups, hipStream_t s) {
     const size_t lds = (size_t)(8 * 16 * 128 + 8 * 16 * 2) * 4 + (size_t)NT * 16 * 272;
     static bool attr = false;
     if (!attr) {
-        VILA_HIP(hipFuncSetAttribute((const void*)bdec_attn_shared_kernel<G, NT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        VILA_HIP(hipFuncSetAttribute((const void*)bdec_attn_shared_kernel<G, NT, PREFIX>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         attr = true;
     }
-    hipLaunchKernelGGL((bdec_attn_shared_kernel<G, NT>), dim3(a.nkv, a.nsl, groups), dim3(512), lds, s, a);
+    hipLaunchKernelGGL((bdec_attn_shared_kernel<G, NT, PREFIX>), dim3(a.nkv, a.nsl, groups), dim3(512), lds, s, a);
     VILA_LAUNCH_CHECK();
+    if (PREFIX) return 0;
     hipLaunchKernelGGL(bdec_attn_shared_merge_kernel, dim3(a.nq, a.n), dim3(128), 0, s, a, G);
     VILA_LAUNCH_CHECK();
     return 0;
 }
 // tiles = ceil(n G / 16) <= 8: up to 4 in one block, more in two blocks of ceil(tiles / 2)
-template <int G>
+template <int G, bool PREFIX = false>
 static int launch_bdec_shared_g(const BSharedArgs& a, hipStream_t s) {
     const int tiles = cdiv(a.n * G, 16), groups = tiles > BSH_MAX_TILES ? 2 : 1, nt = cdiv(tiles, groups);
     switch (nt) {
-        case 1: return launch_bdec_shared_t<G, 1>(a, groups, s);
-        case 2: return launch_bdec_shared_t<G, 2>(a, groups, s);
-        case 3: return launch_bdec_shared_t<G, 3>(a, groups, s);
-        default: return launch_bdec_shared_t<G, 4>(a, groups, s);
+        case 1: return launch_bdec_shared_t<G, 1, PREFIX>(a, groups, s);
+        case 2: return launch_bdec_shared_t<G, 2, PREFIX>(a, groups, s);
+        case 3: return launch_bdec_shared_t<G, 3, PREFIX>(a, groups, s);
+        default: return launch_bdec_shared_t<G, 4, PREFIX>(a, groups, s);
     }
 }
 // slices of the verify form at a capacity: the walking form's cap, or what vila_decode_batch_force_slices asks for
@@ -925,4 +944,119 @@ int bverify_attn(const bf16_t* q, int64_t ldq, const bf16_t* kslot, const bf16_t
     const size_t nsl = (size_t)bverify_attn_slices(max_ctx);
     float* part_ml = (float*)((char*)workspace + align_up((size_t)n * nq * nsl * 128 * 4, 256));
     return bverify_attn_launch(q, ldq, kslot, vslot, pos, o, ldo, n, nq, nkv, max_ctx, scale, (float*)workspace, part_ml, s);
+}
+
+// ---- a session whose rows share a prompt prefix: one K/V read of the prefix for all rows --------------------------------------------------------
+// The session's cache has one slot more than it has rows, the PREFIX SLOT, whose keys 0 .. S - 1 (S a multiple of 256, a device scalar) are the
+// common start of every row with uses[row] != 0.  Such a row attends keys 0 .. S - 1 of the prefix slot and keys S .. pos[row] of its own slot
+// (pos[row] >= S is the host's duty); positions stay absolute.  A row with uses[row] == 0 is an ordinary row: keys 0 .. pos[row] of its own slot.
+// Three launches:
+//   prefix   bdec_attn_shared_kernel<G, NT, true>: columns (row, head) of ALL n rows against the prefix slot, every limit S - 1; partials
+//            [n][nkv][psl][G][128] + [..][2], psl = bverify_attn_slices(capacity).  Slices at or past S >> 8 return; S = 0: all of them.  The columns of
+//            ordinary rows are computed and never read.
+//   private  bdec_attn_walk_kernel<G, true>: row i from chunk c0 = uses[i] ? S >> 8 : 0; partials [n][nkv][nsl][G][128] + [..][2], nsl =
+//            bdec_attn_form(capacity).nsl.  Always the walking form (the force hook shows it valid at every capacity).
+//   merge    bdec_attn_prefix_merge_kernel: for a sharing row the min(S >> 8, psl) prefix slices, then the min(chunks - c0, nsl) private slices that own
+//            a chunk; for an ordinary row the private slices alone.  It reads exactly the partials the two launches above wrote.
+// Invariances:
+//   (a) a sharing row's output bits do not depend on n, on its row index or on the other rows' flags and positions.  Prefix phase: the shared form's
+//       argument — a column's bits depend on its limit (S - 1 for all) and its head, not on the tile group or the column count.  Private phase: a block
+//       serves one (row, kv head, slice) and reads that row's q, flag, position and slot alone.  psl and nsl are fixed by the capacity (and the force
+//       hook), and the merge walks a row's own partials in a fixed order.
+//   (b) an ordinary row gives the bits of vila_attn_decode_batch_bf16 in walking form at the same slice count: c0 = 0 makes the private phase that
+//       kernel's arithmetic, and with no prefix slice the merge below is bdec_attn_merge_kernel's loop, operation for operation.
+__global__ __launch_bounds__(128) void bdec_attn_prefix_merge_kernel(BAttnArgs p, int G) {
+    const int h = blockIdx.x, row = blockIdx.y, d = threadIdx.x;
+    const int kvh = h / G, g = h % G;
+    const int pos1 = p.pos[row] + 1;
+    const int nkeys = pos1 < p.max_ctx ? pos1 : p.max_ctx;
+    const int c0 = p.uses[row] != 0 ? bdec_shared_keys(p.shared_len, p.max_ctx) >> 8 : 0;
+    const int pact = c0 < p.psl ? c0 : p.psl;                     // prefix slices that own a chunk (none for an ordinary row)
+    const int own = ((nkeys + 255) >> 8) - c0;
+    const int active = own < p.nsl ? (own < 0 ? 0 : own) : p.nsl; // private slices that own a chunk
+    const int64_t a0 = (int64_t)(row * p.nkv + kvh) * p.psl * G;
+    const int64_t b0 = (int64_t)(row * p.nkv + kvh) * p.nsl * G;
+    float M = -INFINITY;
+    for (int sl = 0; sl < pact; ++sl) M = fmaxf(M, p.pfx_ml[(a0 + sl * G + g) * 2]);
+    for (int sl = 0; sl < active; ++sl) M = fmaxf(M, p.part_ml[(b0 + sl * G + g) * 2]);
+    float L = 0.f, O = 0.f;
+    for (int sl = 0; sl < pact; ++sl) {
+        const float f = __expf(p.pfx_ml[(a0 + sl * G + g) * 2] - M);
+        L = fmaf(p.pfx_ml[(a0 + sl * G + g) * 2 + 1], f, L);
+        O = fmaf(p.pfx_o[(a0 + sl * G + g) * 128 + d], f, O);
+    }
+    for (int sl = 0; sl < active; ++sl) {
+        const float f = __expf(p.part_ml[(b0 + sl * G + g) * 2] - M);
+        L = fmaf(p.part_ml[(b0 + sl * G + g) * 2 + 1], f, L);
+        O = fmaf(p.part_o[(b0 + sl * G + g) * 128 + d], f, O);
+    }
+    p.o[(int64_t)row * p.o_row_stride + h * 128 + d] = f2bf(O / L);
+}
+template <int G>
+static int launch_bdec_prefix_g(const BSharedArgs& sh, const BAttnArgs& a, int rows, hipStream_t s) {
+    VILA_TRY((launch_bdec_shared_g<G, true>(sh, s)));
+    const size_t lds = (size_t)(16 * G * 128 + 16 * G * 2) * 4 + 16 * 272;
+    static bool attr = false;
+    if (!attr) {
+        VILA_HIP(hipFuncSetAttribute((const void*)bdec_attn_walk_kernel<G, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        attr = true;
+    }
+    hipLaunchKernelGGL((bdec_attn_walk_kernel<G, true>), dim3(a.nkv, a.nsl, rows), dim3(1024), lds, s, a);
+    VILA_LAUNCH_CHECK();
+    hipLaunchKernelGGL(bdec_attn_prefix_merge_kernel, dim3(a.nq, rows), dim3(128), 0, s, a, G);
+    VILA_LAUNCH_CHECK();
+    return 0;
+}
+// the two partial sets, each two separately aligned arrays: the private phase's at the batched step's slot count, the prefix phase's at the verify form's
+size_t bprefix_attn_workspace_bytes(int rows, int nq, int max_ctx) {
+    return bdecode_attn_workspace_bytes(rows, nq, max_ctx) + bverify_attn_workspace_bytes(rows, nq, max_ctx);
+}
+// the launches alone, on partials the caller has laid out for bdec_attn_form(max_ctx).nsl private and bverify_attn_slices(max_ctx) prefix slices
+int bprefix_attn_launch(const bf16_t* q, int64_t ldq, const bf16_t* kcache, const bf16_t* vcache, int64_t slot_stride, int prefix_slot, const int32_t* shared_len,
+                        const int32_t* uses, const int32_t* pos, bf16_t* o, int64_t ldo, int rows, int nq, int nkv, int max_ctx, float scale, float* part_o,
+                        float* part_ml, float* pfx_o, float* pfx_ml, hipStream_t s) {
+    BSharedArgs sh{};
+    sh.q = q; sh.o = o; sh.kslot = kcache + (int64_t)prefix_slot * slot_stride; sh.vslot = vcache + (int64_t)prefix_slot * slot_stride; sh.pos = shared_len;
+    sh.part_o = pfx_o; sh.part_ml = pfx_ml; sh.n = rows; sh.nq = nq; sh.nkv = nkv; sh.max_ctx = max_ctx; sh.nsl = bverify_attn_slices(max_ctx);
+    sh.ldq = ldq; sh.ldo = ldo; sh.scale = scale;
+    BAttnArgs a{};
+    a.q = q; a.o = o; a.kcache = kcache; a.vcache = vcache; a.pos = pos; a.part_o = part_o; a.part_ml = part_ml;
+    a.nq = nq; a.nkv = nkv; a.max_ctx = max_ctx; a.nsl = bdec_attn_form(max_ctx).nsl; a.row_stride = ldq; a.o_row_stride = ldo; a.slot_stride = slot_stride;
+    a.scale = scale; a.shared_len = shared_len; a.uses = uses; a.pfx_o = pfx_o; a.pfx_ml = pfx_ml; a.psl = sh.nsl;
+    switch (nq / nkv) {
+        case 1: return launch_bdec_prefix_g<1>(sh, a, rows, s);
+        case 2: return launch_bdec_prefix_g<2>(sh, a, rows, s);
+        case 4: return launch_bdec_prefix_g<4>(sh, a, rows, s);
+        case 7: return launch_bdec_prefix_g<7>(sh, a, rows, s);
+        case 8: return launch_bdec_prefix_g<8>(sh, a, rows, s);
+        default: break;
+    }
+    VILA_REQUIRE(false, "attn_decode_batch_prefix: GQA groups of 1, 2, 4, 7 or 8 query heads per kv head (got %d)", nq / nkv);
+    return -1;
+}
+// shared_len_host: S where the host knows it (refused unless a multiple of 256 inside the slot), -1 where it does not
+int bprefix_attn(const bf16_t* q, int64_t ldq, const bf16_t* kcache, const bf16_t* vcache, int64_t slot_stride, int n_slots, int prefix_slot,
+                 const int32_t* shared_len, int shared_len_host, const int32_t* uses, const int32_t* pos, bf16_t* o, int64_t ldo, int rows, int nq, int nkv,
+                 int max_ctx, float scale, void* workspace, size_t workspace_bytes, hipStream_t s) {
+    VILA_REQUIRE(q && kcache && vcache && shared_len && uses && pos && o && workspace, "attn_decode_batch_prefix: NULL argument");
+    VILA_REQUIRE(rows >= 1 && rows <= 16 && nkv >= 1 && nq % nkv == 0 && bdec_group_ok(nq / nkv),
+                 "attn_decode_batch_prefix: 1..16 rows and a GQA group of 1, 2, 4, 7 or 8 query heads per kv head (got %d rows, %d / %d heads)", rows, nq, nkv);
+    VILA_REQUIRE(max_ctx >= 1 && max_ctx <= BDEC_MAX_CTX, "attn_decode_batch_prefix: caches of 1..%d positions (got %d)", BDEC_MAX_CTX, max_ctx);
+    VILA_REQUIRE(n_slots > rows && prefix_slot >= rows && prefix_slot < n_slots,
+                 "attn_decode_batch_prefix: the prefix slot (%d) is a slot of the cache (%d slots) behind the %d rows' own", prefix_slot, n_slots, rows);
+    VILA_REQUIRE(shared_len_host == -1 || (shared_len_host >= 0 && shared_len_host <= max_ctx && shared_len_host % 256 == 0),
+                 "attn_decode_batch_prefix: the shared length is a multiple of 256 within the slot (got %d of %d)", shared_len_host, max_ctx);
+    VILA_REQUIRE(ldq % 8 == 0 && ldq >= (int64_t)nq * 128 && ldo >= (int64_t)nq * 128 && (uintptr_t)q % 16 == 0 && (uintptr_t)kcache % 16 == 0 &&
+                 (uintptr_t)vcache % 16 == 0 && slot_stride % 8 == 0 && slot_stride >= (int64_t)nkv * max_ctx * 128,
+                 "attn_decode_batch_prefix: head_dim 128 rows, 16-byte aligned, slots of [kv_heads][max_ctx][128]");
+    VILA_REQUIRE(workspace_bytes >= bprefix_attn_workspace_bytes(rows, nq, max_ctx), "attn_decode_batch_prefix: workspace too small");
+    const size_t nsl = (size_t)bdec_attn_form(max_ctx).nsl, psl = (size_t)bverify_attn_slices(max_ctx);
+    char* w = (char*)workspace;
+    float* part_o = (float*)w;
+    float* part_ml = (float*)(w + align_up((size_t)rows * nq * nsl * 128 * 4, 256));
+    w += bdecode_attn_workspace_bytes(rows, nq, max_ctx);
+    float* pfx_o = (float*)w;
+    float* pfx_ml = (float*)(w + align_up((size_t)rows * nq * psl * 128 * 4, 256));
+    return bprefix_attn_launch(q, ldq, kcache, vcache, slot_stride, prefix_slot, shared_len, uses, pos, o, ldo, rows, nq, nkv, max_ctx, scale, part_o, part_ml,
+                               pfx_o, pfx_ml, s);
 }

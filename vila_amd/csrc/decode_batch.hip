@@ -335,13 +335,16 @@ struct BStepBufs {
     bf16_t *x, *x2, *xn, *q, *ao, *act; float* rope_cs; float *part_o, *part_ml; float* pick_v; int* pick_i;
     int32_t* pos_rows;                                       // the verify step's per-row positions
     void* smp_ws; int64_t* draws;                            // the sampled verify step's sampler candidates and its n draws
+    float *pfx_o, *pfx_ml;                                   // the prefix step's prefix-phase partials
 };
 // The size functions below bound this layout: bdec_step_common_bytes counts every take() but the attention partials and pos_rows at its aligned size,
 // and each step adds its own term for those.  The partials are two separately aligned arrays (part_o, part_ml) where the batched step's term is one
 // aligned sum plus 256: align(a) + align(b) <= align(a + b) + 256, since rounding two parts up can overshoot rounding their sum by less than one
 // more unit.  The verify step's term is bverify_attn_workspace_bytes, the two aligned arrays themselves.  The 4096 on top is slack.
 // draws: the sampled verify step's two arrays behind everything else, each counted at its aligned size by bverify_sample_workspace_bytes.
-static bool bdec_carve(void* workspace, size_t workspace_bytes, int n, int H, int F, int QS, int hd, int nq, int nsl, bool pos_rows, bool draws, BStepBufs* b) {
+// psl > 0: the prefix step's second set of partials behind everything else, bverify_attn_workspace_bytes in bdecode_prefix_workspace_bytes.
+static bool bdec_carve(void* workspace, size_t workspace_bytes, int n, int H, int F, int QS, int hd, int nq, int nsl, bool pos_rows, bool draws, BStepBufs* b,
+                       int psl = 0) {
     char* wp = (char*)workspace; size_t off = 0;
     auto take = [&](size_t bytes) { off = align_up(off, 256); void* r = wp + off; off += bytes; return r; };
     b->x = (bf16_t*)take((size_t)n * H * 2);
@@ -358,6 +361,8 @@ static bool bdec_carve(void* workspace, size_t workspace_bytes, int n, int H, in
     b->pos_rows = pos_rows ? (int32_t*)take((size_t)n * 4) : nullptr;
     b->smp_ws = draws ? take(sample_batch_workspace_bytes(n)) : nullptr;
     b->draws = draws ? (int64_t*)take((size_t)n * 8) : nullptr;
+    b->pfx_o = psl > 0 ? (float*)take((size_t)n * nq * psl * hd * 4) : nullptr;
+    b->pfx_ml = psl > 0 ? (float*)take((size_t)n * nq * psl * 2 * 4) : nullptr;
     return off <= workspace_bytes;
 }
 // embed + rope table, the layers, lm_head -> logits [n][vocab].  Row i appends its K/V at position pos[i] of kcache/vcache + i * slot_stride (+ the
@@ -425,11 +430,24 @@ static size_t bdec_step_common_bytes(int H, int F, int QS, int hd, int n) {
 size_t bdecode_workspace_bytes(int H, int F, int QS, int hd, int n, int max_ctx) {
     return bdec_step_common_bytes(H, F, QS, hd, n) + align_up((size_t)n * (QS / hd) * bdec_ws_slices(max_ctx) * (hd + 2) * 4, 256) + 256;   // + attention slice partials
 }
+// the prefix step: the plain step's layout and, behind it, the prefix phase's partials (two aligned arrays; + 256 for the take() in front of them)
+size_t bdecode_prefix_workspace_bytes(int H, int F, int QS, int hd, int n, int max_ctx) {
+    return align_up(bdecode_workspace_bytes(H, F, QS, hd, n, max_ctx), 256) + bverify_attn_workspace_bytes(n, QS / hd, max_ctx) + 256;
+}
 
 int bdecode_step(const BDecodeArgs& m, const BLayer* layers, bf16_t* kcache, bf16_t* vcache, int max_ctx, int n_slots, int n, int32_t* pos, int64_t* token,
                  int64_t* out_ids, int32_t* n_out, int max_out, float* logits, void* workspace, size_t workspace_bytes, hipStream_t s,
-                 const BLayerW4* qlayers, const BatchSampling* sampling, void* sampling_ws) {
+                 const BLayerW4* qlayers, const BatchSampling* sampling, void* sampling_ws, const BPrefix* prefix) {
     const int H = m.hidden, F = m.inter, hd = m.head_dim, QS = m.q_heads * hd;
+    if (prefix != nullptr) {
+        VILA_REQUIRE(prefix->shared_len != nullptr && prefix->uses != nullptr, "batched decode (shared prefix): NULL argument");
+        VILA_REQUIRE(n >= 1 && n < n_slots && prefix->prefix_slot >= n && prefix->prefix_slot < n_slots,
+                     "batched decode (shared prefix): the prefix slot (%d) is a slot of the cache (%d slots) behind the %d rows' own", prefix->prefix_slot, n_slots, n);
+        VILA_REQUIRE(hd == 128 && m.q_heads % m.kv_heads == 0 && bdec_group_ok(m.q_heads / m.kv_heads),
+                     "batched decode (shared prefix): head_dim 128 and a GQA group of 1, 2, 4, 7 or 8 query heads per kv head (got %d / %d)", m.q_heads, m.kv_heads);
+        VILA_REQUIRE(max_ctx >= 1 && max_ctx <= BDEC_MAX_CTX && workspace_bytes >= bdecode_prefix_workspace_bytes(H, F, QS, hd, n, max_ctx),
+                     "batched decode (shared prefix): the step needs the workspace of vila_llm_decode_batch_prefix*_workspace_bytes (%d positions)", max_ctx);
+    }
     VILA_REQUIRE(n >= 1 && n <= 16 && n <= n_slots, "batched decode: %d sequences need 1..16 KV-cache slots (cache has %d)", n, n_slots);
     VILA_REQUIRE(QS == H, "batched decode: q_heads*head_dim (%d) must equal hidden (%d)", QS, H);
     VILA_REQUIRE(hd == 128 && max_ctx >= 1 && max_ctx <= BDEC_MAX_CTX, "batched decode: head_dim 128 and caches up to %d positions (got %d, %d)", BDEC_MAX_CTX, hd,
@@ -444,10 +462,14 @@ int bdecode_step(const BDecodeArgs& m, const BLayer* layers, bf16_t* kcache, bf1
     VILA_REQUIRE(workspace_bytes >= bdecode_workspace_bytes(H, F, QS, hd, n, max_ctx), "batched decode: workspace too small");
     VILA_REQUIRE(sampling == nullptr || sampling_ws != nullptr, "batched decode: the sampled pick needs its workspace");
     BStepBufs b{};
-    VILA_REQUIRE(bdec_carve(workspace, workspace_bytes, n, H, F, QS, hd, m.q_heads, form.nsl, false, false, &b), "batched decode: workspace layout");
+    VILA_REQUIRE(bdec_carve(workspace, workspace_bytes, n, H, F, QS, hd, m.q_heads, form.nsl, false, false, &b, prefix != nullptr ? bverify_attn_slices(max_ctx) : 0),
+                 "batched decode: workspace layout");
     const int64_t per_layer = (int64_t)n_slots * m.kv_heads * max_ctx * hd, slot_stride = (int64_t)m.kv_heads * max_ctx * hd;
     const float scale = 1.0f / sqrtf((float)hd);
     auto attn = [&](const bf16_t* q, bf16_t* kc, bf16_t* vc, bf16_t* ao) -> int {
+        if (prefix != nullptr)
+            return bprefix_attn_launch(q, QS, kc, vc, slot_stride, prefix->prefix_slot, prefix->shared_len, prefix->uses, pos, ao, QS, n, m.q_heads, m.kv_heads,
+                                       max_ctx, scale, b.part_o, b.part_ml, b.pfx_o, b.pfx_ml, s);
         const int rc = bdecode_attn_launch(form, q, QS, kc, vc, slot_stride, pos, ao, QS, n, m.q_heads, m.kv_heads, max_ctx, scale, b.part_o, b.part_ml, s);
         if (rc < 0) return rc;
         if (rc == 1) {                                                                       // group size without an instantiation: one block per query head

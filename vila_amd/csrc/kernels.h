@@ -179,9 +179,21 @@ int bdecode_attn_slices(int max_ctx);   // slices of the walking form at this ca
 size_t bdecode_attn_workspace_bytes(int rows, int nq, int max_ctx);
 int bdecode_attn(const bf16_t* q, int64_t ldq, const bf16_t* kcache, const bf16_t* vcache, int64_t slot_stride, const int32_t* pos, bf16_t* o, int64_t ldo,
                  int rows, int nq, int nkv, int max_ctx, float scale, void* workspace, size_t workspace_bytes, hipStream_t s);
+// a session whose rows share a prompt prefix (attn_decode.hip, behind the verify form): slot `prefix_slot` of the cache holds keys 0 .. *shared_len - 1 (a
+// multiple of 256) of every row with uses[row] != 0, which reads its own slot from there on; other rows are ordinary.  Three launches per layer.
+struct BPrefix { int prefix_slot; const int32_t* shared_len; const int32_t* uses; };
+size_t bprefix_attn_workspace_bytes(int rows, int nq, int max_ctx);
+int bprefix_attn_launch(const bf16_t* q, int64_t ldq, const bf16_t* kcache, const bf16_t* vcache, int64_t slot_stride, int prefix_slot, const int32_t* shared_len,
+                        const int32_t* uses, const int32_t* pos, bf16_t* o, int64_t ldo, int rows, int nq, int nkv, int max_ctx, float scale, float* part_o,
+                        float* part_ml, float* pfx_o, float* pfx_ml, hipStream_t s);
+int bprefix_attn(const bf16_t* q, int64_t ldq, const bf16_t* kcache, const bf16_t* vcache, int64_t slot_stride, int n_slots, int prefix_slot,
+                 const int32_t* shared_len, int shared_len_host, const int32_t* uses, const int32_t* pos, bf16_t* o, int64_t ldo, int rows, int nq, int nkv,
+                 int max_ctx, float scale, void* workspace, size_t workspace_bytes, hipStream_t s);
+// prefix != nullptr: the step of such a session (n_slots counts the prefix slot; the workspace is bdecode_prefix_workspace_bytes)
+size_t bdecode_prefix_workspace_bytes(int H, int F, int QS, int hd, int n, int max_ctx);
 int bdecode_step(const BDecodeArgs& m, const BLayer* layers, bf16_t* kcache, bf16_t* vcache, int max_ctx, int n_slots, int n, int32_t* pos, int64_t* token,
                  int64_t* out_ids, int32_t* n_out, int max_out, float* logits, void* workspace, size_t workspace_bytes, hipStream_t s,
-                 const BLayerW4* qlayers = nullptr, const BatchSampling* sampling = nullptr, void* sampling_ws = nullptr);
+                 const BLayerW4* qlayers = nullptr, const BatchSampling* sampling = nullptr, void* sampling_ws = nullptr, const BPrefix* prefix = nullptr);
 // the verify step (greedy speculative decoding): n rows = n consecutive positions of ONE sequence in ONE slot.  Its attention (attn_decode.hip
 // bdec_attn_shared_kernel) reads the slot's K/V once for all rows; `pos` is the device scalar of the state, row i sees keys 0 .. min(pos + i, max_ctx - 1)
 int bverify_attn_slices(int max_ctx);

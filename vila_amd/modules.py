@@ -296,10 +296,16 @@ def _as_i64(u: int) -> int:
     return u - (1 << 64) if u >= (1 << 63) else u
 
 
-def _step_symbols(batch: bool, w4: bool, sampled: bool, verify: bool = False, verify_sample: bool = False) -> Tuple[str, str]:
+def _step_symbols(batch: bool, w4: bool, sampled: bool, verify: bool = False, verify_sample: bool = False, prefix: bool = False) -> Tuple[str, str]:
     """(step, workspace query) of one decode step variant, composed the way the C ABI names them.  verify: the greedy verify step, whatever `batch`.
     verify_sample: the sampled verify step, whatever `batch`, `sampled` and `verify` — a spelling of its own, since `verify` with `sampled` stays the
-    refusal it always was (that pair names the greedy step asked to sample)."""
+    refusal it always was (that pair names the greedy step asked to sample).  prefix: the batched step of a session with a shared prompt prefix
+    (its workspace query takes the capacity and has no `_ctx` twin)."""
+    if prefix:
+        if not batch or verify or verify_sample:
+            raise ValueError("the shared-prefix step is a batched step")
+        tail = ("_w4" if w4 else "") + ("_sample" if sampled else "")
+        return "vila_llm_decode_step_batch_prefix" + tail, "vila_llm_decode_batch_prefix" + tail + "_workspace_bytes"
     if verify_sample:
         tail = ("_w4" if w4 else "") + "_sample"
         return "vila_llm_decode_step_verify" + tail, "vila_llm_decode_verify_sample_workspace_bytes"
@@ -665,8 +671,10 @@ class HipQwen2ForCausalLM(_HipModule):
     def _step(self, batch: bool, w4, cache, st, sp, verify: bool = False, verify_sample: bool = False) -> None:
         """One decode step on the current stream.  The variant is looked up at call time (`_step_symbols`): a caller may hold a session
         across quantize_w4.  w4: the W4Weights whose int4 layers the step reads, or None; sp: the sampling struct, or None for the greedy pick."""
-        name, _ = _step_symbols(batch, w4 is not None, sp is not None, verify, verify_sample)
-        args = [C.byref(self._struct())] + ([w4.ptr] if w4 is not None else []) + [C.byref(cache.c), C.byref(st.c), st.ws.data_ptr(), st.ws.numel()]
+        px = getattr(st, "px", None)                                    # a session with a shared prompt prefix: its descriptor follows the state
+        name, _ = _step_symbols(batch, w4 is not None, sp is not None, verify, verify_sample, prefix=px is not None)
+        args = ([C.byref(self._struct())] + ([w4.ptr] if w4 is not None else []) + [C.byref(cache.c), C.byref(st.c)] +
+                ([C.byref(px)] if px is not None else []) + [st.ws.data_ptr(), st.ws.numel()])
         check(getattr(_lib.load(), name)(*args, *([C.byref(sp)] if sp is not None else []), ops._stream()), name)
 
     def decode_step(self, cache, st) -> None:
@@ -718,27 +726,35 @@ class HipQwen2ForCausalLM(_HipModule):
                 return False
         return True
 
-    def _batch_session(self, n: int, max_ctx: int, max_new_tokens: int, sampling: bool = False):
+    def _batch_session(self, n: int, max_ctx: int, max_new_tokens: int, sampling: bool = False, shared_prefix: bool = False):
         """sampling=True: the session owns per-row sampling parameters on the device (temperature / top_k / top_p / seed, every row greedy
-        until `_batch_set_sampling` says otherwise) and steps through the `_sample` entry points: one captured graph for any mix of rows."""
+        until `_batch_set_sampling` says otherwise) and steps through the `_sample` entry points: one captured graph for any mix of rows.
+        shared_prefix=True: the cache has one slot more, the prefix slot (index n), and the session owns the shared length and the rows' flags on
+        the device; it steps through the `_prefix` entry points."""
         w4 = self._w4_batched()
         if not w4:
             self._require_bf16("the batched decode")
-        key = (n, max_ctx, max_new_tokens, bool(sampling), *self._weights_key())
+        key = (n, max_ctx, max_new_tokens, bool(sampling), *self._weights_key()) + ((True,) if shared_prefix else ())
         if self._bdecode is not None and self._bdecode.key == key:
             return self._bdecode
         self._drop_session("_bdecode")
         dev, lib, w = self.device, _lib.load(), self._struct()
-        st = SimpleNamespace(key=key, graph=None, sampling=bool(sampling), sp=None)
+        st = SimpleNamespace(key=key, graph=None, sampling=bool(sampling), sp=None, px=None, shared_prefix=bool(shared_prefix))
         st.attn_slices = int(lib.vila_decode_batch_slices(int(max_ctx)))     # walking-attention slices the steps of this session launch (0: short form)
         with torch.inference_mode(False):
-            st.cache = self.new_cache(max_ctx, n_slots=n)
+            st.cache = self.new_cache(max_ctx, n_slots=n + 1 if shared_prefix else n)
+            if shared_prefix:
+                st.prefix_slot = n
+                st.shared_len = torch.zeros(1, device=dev, dtype=torch.int32)
+                st.uses = torch.zeros(n, device=dev, dtype=torch.int32)
+                st.px = _lib.VilaDecodePrefix(n, st.shared_len.data_ptr(), st.uses.data_ptr())
+                self._prefix_reset(st)
             st.pos = torch.zeros(n, device=dev, dtype=torch.int32)
             st.token = torch.zeros(n, device=dev, dtype=torch.int64)
             st.out_ids = torch.zeros((n, max(max_new_tokens, 1)), device=dev, dtype=torch.int64)
             st.n_out = torch.zeros(n, device=dev, dtype=torch.int32)
             st.logits = torch.zeros((n, self.lcfg.vocab_size), device=dev, dtype=torch.float32)
-            ws_bytes = getattr(lib, _step_symbols(True, w4, bool(sampling))[1])
+            ws_bytes = getattr(lib, _step_symbols(True, w4, bool(sampling), prefix=bool(shared_prefix))[1])
             if sampling:
                 st.s_temperature = torch.zeros(n, device=dev, dtype=torch.float32)          # 0 = greedy row
                 st.s_top_k = torch.full((n,), 50, device=dev, dtype=torch.int32)
@@ -783,21 +799,26 @@ class HipQwen2ForCausalLM(_HipModule):
         st.s_top_p[slot:slot + 1].fill_(float(p))
         st.s_seed[slot:slot + 1].fill_(_as_i64(seed))
 
-    def batch_open(self, n_slots: int, max_ctx: int = 2048, max_new_tokens: int = 1024, sampling: bool = False):
+    def batch_open(self, n_slots: int, max_ctx: int = 2048, max_new_tokens: int = 1024, sampling: bool = False, shared_prefix: bool = False):
         """Open (or re-use) the batched-decode session of `n_slots` rows with its captured step.  sampling=False: the greedy step.  sampling=True:
         the step picks per row from device-resident parameters, so the ONE captured graph serves any mix of greedy and sampled rows
-        (`batch_admit(..., sampling=)`); the flag is part of the session key."""
+        (`batch_admit(..., sampling=)`); the flag is part of the session key.
+        shared_prefix=True (part of the key as well): the session may hold one shared prompt prefix in an extra cache slot (`batch_set_prefix`), and
+        rows admitted with `batch_admit(..., share=True)` read its K/V instead of a copy of their own: the step's attention reads the prefix once for
+        all of them.  The ONE captured graph serves any shared length and any mix of sharing and ordinary rows.  GQA groups of 1, 2, 4, 7 or 8."""
         if not self._w4_batched():
             self._require_bf16("batch_open")
-        long_ok = max_ctx <= 2048 or self._long_batch_group_ok()
+        long_ok = (max_ctx <= 2048 and not shared_prefix) or self._long_batch_group_ok()
         if not (1 <= n_slots <= 16 and 1 <= max_ctx <= self.BATCH_MAX_CTX and long_ok and self.can_batch_decode_step() and
                 (self._w4_batched() or self._qkv_fused())):
             raise ValueError("batch_open: the batched decode step serves 1..16 rows of a head-dim-128 model (bf16, or quantize_w4(batch_decode=True)) "
                              f"with caches <= {self.BATCH_MAX_CTX} positions (beyond 2048: GQA groups of 1, 2, 4, 7 or 8 query heads)")
-        st = self._batch_session(max(n_slots, 2), max_ctx, max_new_tokens, sampling)
+        st = self._batch_session(max(n_slots, 2), max_ctx, max_new_tokens, sampling, shared_prefix)
         def reset():
             st.pos.zero_(); st.n_out.zero_(); st.token.zero_()
         reset()
+        if st.shared_prefix:
+            self._prefix_reset(st)                                     # no prefix, every row ordinary
         if st.sampling:
             st.s_temperature.zero_()                                   # every row starts greedy (idle)
         if st.graph is None:
@@ -806,30 +827,110 @@ class HipQwen2ForCausalLM(_HipModule):
                 reset()                                                # the session starts idle whatever the capture left
         return st
 
-    def batch_admit(self, st, slot: int, embeds: torch.Tensor, sampling=None) -> int:
-        """Prefill ONE sequence [S, H] into KV slot `slot` of the open batch and make the row live: position S, first token = argmax of the
+    @staticmethod
+    def _prefix_reset(st) -> None:
+        """A shared-prefix session without a prefix: S = 0, no flag set, nothing staged."""
+        st.shared_len.zero_(); st.uses.zero_()
+        st.S, st.sharers = 0, set()
+        st.staged_len, st.staged_tail, st.staged_logits = None, None, None
+
+    def batch_set_prefix(self, st, embeds: torch.Tensor, prefix_len: Optional[int] = None) -> int:
+        """Make embeds [C, H] the shared prefix of a session opened with batch_open(shared_prefix=True): it is prefilled into the prefix slot and its
+        first S = C // 256 * 256 positions (whole attention chunks) become the keys every sharing row reads.  Returns S.  Refused while a live row
+        shares the current prefix (`batch_release` frees them).  Rows S .. C - 1 of the prefix slot are staging: a request whose whole prompt is
+        `embeds` is then admitted without another prefill (`batch_admit(..., share=True)`).
+        prefix_len (default C): embeds is a first request's whole prompt of which only the first prefix_len rows are common to the requests that
+        will share; S = prefix_len // 256 * 256."""
+        if not getattr(st, "shared_prefix", False):
+            raise ValueError("batch_set_prefix: the session was opened without batch_open(shared_prefix=True)")
+        if st.sharers:
+            raise ValueError(f"batch_set_prefix: rows {sorted(st.sharers)} still share the current prefix; release them first")
+        ops._need(embeds, dtype=None, name="embeds")
+        Cn = int(embeds.shape[0])
+        if embeds.dim() != 2 or Cn < 1 or Cn + 1 > st.cache.max_ctx:
+            raise ValueError(f"batch_set_prefix: embeds must be [C, H] with 1 <= C < {st.cache.max_ctx} (got {tuple(embeds.shape)})")
+        shared = Cn if prefix_len is None else int(prefix_len)
+        if not 0 <= shared <= Cn:
+            raise ValueError(f"batch_set_prefix: prefix_len ({shared}) outside the {Cn} rows given")
+        dev = embeds.device
+        st.stream.synchronize()
+        self._prefix_reset(st)                                         # a prefill that fails leaves the session without a prefix, not with half of one
+        x = embeds.to(self.dtype)
+        last = torch.full((1,), Cn - 1, device=dev, dtype=torch.int32)
+        r = self.prefill_packed(x, torch.arange(Cn, device=dev, dtype=torch.int32), torch.tensor([0, Cn], device=dev, dtype=torch.int32), Cn, cache=st.cache,
+                                seq_of_tok=torch.full((Cn,), st.prefix_slot, device=dev, dtype=torch.int32), last_rows=last)
+        S = shared // 256 * 256
+        st.shared_len.fill_(S)
+        st.S = S
+        st.staged_len, st.staged_tail, st.staged_logits = Cn, x[S:].clone(), r.last_logits[0].clone()
+        torch.cuda.current_stream().synchronize()
+        return S
+
+    def _admit_sharing(self, st, slot: int, embeds: torch.Tensor, first_row: int):
+        """The tail S .. P - 1 of a sharing row: prefilled behind the prefix in the prefix slot's staging rows (unless the rows staged there are this
+        very tail) and copied to the row's own slot, every layer.  Returns the logits of the prompt's last row."""
+        S, P = st.S, first_row + int(embeds.shape[0])
+        tail = embeds.to(self.dtype)[S - first_row:]
+        staged = st.staged_len == P and (P == S or torch.equal(st.staged_tail, tail))
+        if not staged:
+            if P == S:
+                raise ValueError(f"batch_admit(share=True): a prompt that ends with the prefix (P = S = {S}) is served only right after the "
+                                 "batch_set_prefix of that same prompt, which kept the logits of its last row")
+            last = torch.full((1,), P - S - 1, device=tail.device, dtype=torch.int32)
+            r = self.prefill_append(tail, st.cache, S, st.prefix_slot, last_rows=last)
+            st.staged_len, st.staged_tail, st.staged_logits = P, tail.clone(), r.last_logits[0].clone()
+        if P > S:
+            for c in (st.cache.k, st.cache.v):
+                c[:, slot, :, S:P].copy_(c[:, st.prefix_slot, :, S:P])
+        return st.staged_logits
+
+    def batch_admit(self, st, slot: int, embeds: torch.Tensor, sampling=None, share: bool = False, first_row: int = 0) -> int:
+        """Prefill ONE sequence [P, H] into KV slot `slot` of the open batch and make the row live: position P, first token = argmax of the
         prefill's last row (returned), output counter 0.  sampling = (temperature, top_k in 1..64, top_p, seed), sampling sessions only: the
-        row samples — its parameters go to the device arrays, its first token is drawn from the prefill's last row with counter S - 1 (as the
-        solo generate draws it), the steps draw with the position of the token they consume.  None = greedy row."""
+        row samples — its parameters go to the device arrays, its first token is drawn from the prefill's last row with counter P - 1 (as the
+        solo generate draws it), the steps draw with the position of the token they consume.  None = greedy row.
+        share=True (sessions opened with shared_prefix=True, after `batch_set_prefix`): embeds is the WHOLE prompt [P, H], whose first S positions
+        (S = the session's shared length) are the session's prefix (the caller's word: they are not compared) and P >= S.  Only the tail S .. P - 1 is prefilled, onto the prefix, and
+        copied to the row's own slot; the row's flag is set, so its steps read keys 0 .. S - 1 from the prefix slot.
+        first_row (share=True only, 0 <= first_row <= S): embeds holds the prompt's rows first_row .. P - 1 only — rows below S are never read, so a
+        caller that has no embeddings of the prefix (a server that skipped the tower) passes the rest."""
         if sampling is not None:
             if not st.sampling:
                 raise ValueError("batch_admit: a sampled row needs a session opened with batch_open(sampling=True)")
             sampling = self._check_batch_sampling(sampling, "batch_admit")
-        S = int(embeds.shape[0])
-        if S + 1 > st.cache.max_ctx:
-            raise ValueError(f"KV cache too small: {st.cache.max_ctx} < {S} + 1")
+        first_row = int(first_row)
+        if first_row != 0 and not (share and 0 <= first_row <= getattr(st, "S", 0)):
+            raise ValueError(f"batch_admit: first_row ({first_row}) is for share=True and lies in 0 .. the shared length")
+        P = first_row + int(embeds.shape[0])
+        if P + 1 > st.cache.max_ctx:
+            raise ValueError(f"KV cache too small: {st.cache.max_ctx} < {P} + 1")
+        if share:
+            if not getattr(st, "shared_prefix", False):
+                raise ValueError("batch_admit: share=True needs a session opened with batch_open(shared_prefix=True)")
+            if st.S <= 0:
+                raise ValueError("batch_admit: share=True needs a prefix of at least 256 positions (batch_set_prefix)")
+            if P < st.S:
+                raise ValueError(f"batch_admit: the prompt ({P} positions) is shorter than the shared prefix ({st.S})")
         dev = embeds.device
         st.stream.synchronize()                                        # no step is reading the cache while the newcomer's rows are written
-        pos = torch.arange(S, device=dev, dtype=torch.int32)
-        seq = torch.full((S,), int(slot), device=dev, dtype=torch.int32)
-        cu = torch.tensor([0, S], device=dev, dtype=torch.int32)
-        last = torch.full((1,), S - 1, device=dev, dtype=torch.int32)
-        r = self.prefill_packed(embeds.to(self.dtype), pos, cu, S, cache=st.cache, seq_of_tok=seq, last_rows=last)
-        first = (ops.argmax(r.last_logits[0]) if sampling is None else
-                 ops.sample(r.last_logits[0], sampling[0], sampling[1], sampling[2], sampling[3], counter=last))
+        if not share and getattr(st, "shared_prefix", False):          # (behind the synchronise: no step in flight sees the flag change)
+            st.uses[slot:slot + 1].zero_()
+            st.sharers.discard(int(slot))
+        last = torch.full((1,), P - 1, device=dev, dtype=torch.int32)
+        if share:
+            logits = self._admit_sharing(st, int(slot), embeds, first_row)
+            st.uses[slot:slot + 1].fill_(1)
+            st.sharers.add(int(slot))
+        else:
+            pos = torch.arange(P, device=dev, dtype=torch.int32)
+            seq = torch.full((P,), int(slot), device=dev, dtype=torch.int32)
+            cu = torch.tensor([0, P], device=dev, dtype=torch.int32)
+            logits = self.prefill_packed(embeds.to(self.dtype), pos, cu, P, cache=st.cache, seq_of_tok=seq, last_rows=last).last_logits[0]
+        first = (ops.argmax(logits) if sampling is None else
+                 ops.sample(logits, sampling[0], sampling[1], sampling[2], sampling[3], counter=last))
         if st.sampling:
             self._batch_set_sampling(st, slot, sampling)
-        st.pos[slot:slot + 1].fill_(S)
+        st.pos[slot:slot + 1].fill_(P)
         st.n_out[slot:slot + 1].zero_()
         st.token[slot:slot + 1].copy_(first)
         tok = int(first.item())                                        # (also orders the prefill before the next replay on st.stream)
@@ -850,6 +951,59 @@ class HipQwen2ForCausalLM(_HipModule):
             st.n_out.index_fill_(0, idx, 0)
             if st.sampling:
                 st.s_temperature.index_fill_(0, idx, 0.0)              # an idle row is a greedy row
+            if getattr(st, "shared_prefix", False):
+                st.uses.index_fill_(0, idx, 0)                         # ... and an ordinary one
+                st.sharers.difference_update(int(s) for s in slots)
+
+    def _generate_shared(self, inputs_embeds, n: int, max_new_tokens, eos_token_id, pad_token_id, use_graph: bool, return_logits: bool, sampling):
+        """generate(num_return_sequences=n): ONE prefill of the prompt into the prefix slot of a shared-prefix sampling session, n sharing rows that
+        differ in their seeds.  Returns [n, n_new] like `_generate_batch`; return_logits: (ids [n, n_new], logits [n_new, n, V] fp32), eager steps.
+        A prompt below 256 positions has no whole chunk to share: nothing goes into the prefix slot and the n rows are ordinary rows of the same
+        session, each prefilled on its own (return_logits is refused for it by the caller)."""
+        x = inputs_embeds[0]
+        P, dev = int(x.shape[0]), x.device
+        max_ctx = ((P + max_new_tokens + 255) // 256) * 256
+        st = self.batch_open(n, max_ctx, max_new_tokens, sampling=True, shared_prefix=True)
+        self.batch_release(st, range(st.pos.numel()))
+        if P < 256:
+            first_h = [self.batch_admit(st, j, x, sampling=sampling[j]) for j in range(n)]
+        else:
+            self.batch_set_prefix(st, x)
+            first_h = [self.batch_admit(st, j, x, sampling=sampling[j], share=True) for j in range(n)]
+        first = torch.tensor(first_h, device=dev, dtype=torch.int64)
+        eos_set = _eos_set(eos_token_id, self.lcfg.eos_token_id)
+        n_steps = max_new_tokens - 1
+        try:
+            if return_logits:
+                # the first token's logits are the prompt's last row for every sequence
+                step_logits, ids = [st.staged_logits.float()[None].expand(n, -1).clone()], [first]
+                torch.cuda.current_stream().synchronize()
+                with torch.cuda.stream(st.stream):
+                    for _ in range(n_steps):
+                        self._batch_step(st)
+                        step_logits.append(st.logits[:n].float().clone())
+                        ids.append(st.token[:n].clone())
+                st.stream.synchronize()
+                return torch.stack(ids, 1), torch.stack(step_logits, 0)
+            done_rows = [t in eos_set for t in first_h]
+            done = 0
+            torch.cuda.current_stream().synchronize()
+            with torch.cuda.stream(st.stream):
+                while done < n_steps and not all(done_rows):
+                    chunk = min(16, n_steps - done)
+                    if use_graph:
+                        _replay(st, chunk)
+                    else:
+                        for _ in range(chunk):
+                            self._batch_step(st)
+                    done += chunk
+                    got = st.out_ids[:n, :done].tolist()
+                    done_rows = [first_h[b] in eos_set or any(t in eos_set for t in got[b]) for b in range(n)]
+            st.stream.synchronize()
+            toks = torch.cat([first[:, None], st.out_ids[:n, :done]], 1)
+            return finish_rows(toks.tolist(), eos_set, _pad_id(pad_token_id, eos_token_id, self.lcfg.eos_token_id), dev)
+        finally:
+            self.batch_release(st, range(st.pos.numel()))
 
     def _generate_batch(self, inputs_embeds, attention_mask, max_new_tokens, eos_token_id, pad_token_id, use_graph: bool = True,
                         forced_ids: Optional[torch.Tensor] = None, return_logits: bool = False, sampling=None):
@@ -941,7 +1095,7 @@ class HipQwen2ForCausalLM(_HipModule):
                  max_length: Optional[int] = None, streamer=None, batch_sample: Optional[bool] = None,
                  prompt_lookup_num_tokens: Optional[int] = None, max_matching_ngram_size: Optional[int] = None,
                  prompt_ids: Optional[torch.Tensor] = None, draft_ids: Optional[torch.Tensor] = None, past_len: Optional[int] = None,
-                 prefill_chunk: Optional[int] = None, spec_sample: Optional[bool] = None, **kw):
+                 prefill_chunk: Optional[int] = None, spec_sample: Optional[bool] = None, num_return_sequences: Optional[int] = None, **kw):
         """`llm.generate(inputs_embeds=, attention_mask=, **generation_kwargs)` as called at llava_arch.py:833 (HF semantics: returns ONLY the
         new tokens, [B, n_new]).  Greedy search or sampling (do_sample: temperature / top_k / top_p, HF order, on the device); explicit
         keyword arguments override `generation_config` (HF GenerationConfig-like: do_sample, temperature, top_k, top_p, max_new_tokens,
@@ -951,6 +1105,10 @@ class HipQwen2ForCausalLM(_HipModule):
         batch_sample (opt-in, also read from generation_config; default False): a padded batch of 2..16 rows with do_sample and top_k in 1..64
         runs the batched step with its per-row sampler — one weight pass per step for all rows, row b seeded `seed + b` as the row-by-row loop
         seeds it.  The batched step sums in another order than the solo step, so the ids are no longer those of the rows' solo runs.
+        num_return_sequences=n (HF's name; with do_sample=True and batch_sample=True, n in 2..16, top_k in 1..64, inputs_embeds [1, P, H]): n
+        samples of ONE prompt, returned as [n, n_new].  The prompt is prefilled once (from 256 positions on; a shorter one shares nothing and is
+        prefilled per row); its first P // 256 * 256 positions are the shared prefix of n sharing rows of a batch session (`batch_open(shared_prefix=True)`), whose steps read that K/V once for all rows.  Row j draws with seed
+        `seed + j`, the seeds a padded batch of n copies would get.  Anything else (greedy, n > 16, a padded batch) raises a ValueError.
         forced_ids = teacher forcing for margin-aware parity tests.
         prompt_lookup_num_tokens=k (HF's name, also read from generation_config; 1..15; default None = off): greedy speculative decoding.  One
         graph replay runs the last token and up to k drafted ones as k + 1 positions of the sequence (`vila_llm_decode_step_verify`) and keeps the
@@ -972,6 +1130,10 @@ class HipQwen2ForCausalLM(_HipModule):
         prefill_chunk=C (batch size 1): a prompt longer than C is fed as the usual prefill of its first C tokens and `prefill_append` calls of
         at most C, logits only from the last, so the prefill workspace is that of C tokens.  Both default to None: the one-shot path."""
         self._check_append_args(inputs_embeds, cache, past_len, prefill_chunk)
+        if num_return_sequences is not None and int(num_return_sequences) != 1:
+            return self._generate_return_sequences(inputs_embeds, attention_mask, int(num_return_sequences), max_new_tokens, eos_token_id, do_sample,
+                                                   temperature, top_k, top_p, seed, pad_token_id, generation_config, use_graph, return_logits,
+                                                   forced_ids, cache, streamer, batch_sample, prompt_lookup_num_tokens, draft_ids, past_len, prefill_chunk)
         if streamer is not None and inputs_embeds.shape[0] > 1:
             raise ValueError("TextStreamer only supports batch size 1")          # transformers/generation/streamers.py, TextStreamer.put
         gc = generation_config
@@ -1037,6 +1199,39 @@ class HipQwen2ForCausalLM(_HipModule):
             sampling = (temperature, top_k, top_p, int(seed))
         return self._generate_solo(inputs_embeds, attention_mask, max_new_tokens, eos_token_id, sampling, use_graph, return_logits, forced_ids, cache,
                                    streamer, past_len, prefill_chunk)
+
+    def _generate_return_sequences(self, inputs_embeds, attention_mask, n, max_new_tokens, eos_token_id, do_sample, temperature, top_k, top_p, seed,
+                                   pad_token_id, gc, use_graph, return_logits, forced_ids, cache, streamer, batch_sample, k_spec, draft_ids, past_len,
+                                   prefill_chunk):
+        """generate(num_return_sequences=n): what is served, refused with a ValueError that says so otherwise."""
+        pick = lambda v, name, default: v if v is not None else (getattr(gc, name, None) if gc is not None and getattr(gc, name, None) is not None else default)
+        what = "num_return_sequences: n samples of ONE prompt over its shared K/V"
+        if not bool(pick(do_sample, "do_sample", False)):
+            raise ValueError(f"{what} needs do_sample=True (greedy search returns n copies of one sequence; it is not served)")
+        if not bool(pick(batch_sample, "batch_sample", False)):
+            raise ValueError(f"{what} runs the batched sampler: pass batch_sample=True")
+        if not 2 <= n <= 16:
+            raise ValueError(f"{what} serves n in 2..16 (got {n})")
+        if inputs_embeds.dim() != 3 or inputs_embeds.shape[0] != 1 or (attention_mask is not None and not bool(attention_mask.bool().all())):
+            raise ValueError(f"{what} takes inputs_embeds [1, P, H] without padding (a padded batch is not served)")
+        if (forced_ids is not None or cache is not None or streamer is not None or k_spec is not None or draft_ids is not None or past_len is not None or
+                prefill_chunk is not None):
+            raise ValueError(f"{what} does not combine with forced_ids, cache, streamer, speculative decoding, past_len or prefill_chunk")
+        temperature, top_k, top_p = float(pick(temperature, "temperature", 1.0)), int(pick(top_k, "top_k", 50)), float(pick(top_p, "top_p", 1.0))
+        max_new_tokens = int(pick(max_new_tokens, "max_new_tokens", 32))
+        if max_new_tokens < 1 or not self.can_batch_decode_step() or not self._long_batch_group_ok() or not (self._w4_batched() or self._qkv_fused()):
+            raise ValueError(f"{what} needs max_new_tokens >= 1 and a model the batched step serves (head_dim 128, GQA group 1, 2, 4, 7 or 8)")
+        if inputs_embeds.shape[1] + max_new_tokens > self.BATCH_MAX_CTX:
+            raise ValueError(f"{what}: prompt and output must fit {self.BATCH_MAX_CTX} positions")
+        if return_logits and inputs_embeds.shape[1] < 256:
+            raise ValueError(f"{what}: return_logits needs a prompt of at least 256 positions (a shorter one shares nothing and its rows are admitted "
+                             "one by one)")
+        if seed is None:
+            seed = self._fresh_seed()
+        rows = [self._check_batch_sampling((temperature, top_k, top_p, (int(seed) + j) & 0xFFFFFFFFFFFFFFFF), "generate(num_return_sequences=)")
+                for j in range(n)]
+        return self._generate_shared(inputs_embeds, n, max_new_tokens, pick(eos_token_id, "eos_token_id", None), pick(pad_token_id, "pad_token_id", None),
+                                     use_graph, return_logits, rows)
 
     @staticmethod
     def _check_append_args(inputs_embeds, cache, past_len, prefill_chunk) -> None:

@@ -281,6 +281,34 @@ def attn_decode_batch(q: torch.Tensor, kcache: torch.Tensor, vcache: torch.Tenso
     return o
 
 
+def attn_decode_batch_prefix(q: torch.Tensor, kcache: torch.Tensor, vcache: torch.Tensor, pos: torch.Tensor, shared_len: torch.Tensor, uses: torch.Tensor,
+                             prefix_slot: Optional[int] = None, shared_len_host: Optional[int] = None, scale: Optional[float] = None) -> torch.Tensor:
+    """The attention of a batch session with a shared prompt prefix, on its own: `attn_decode_batch`'s operands with one slot more in the cache, the
+    prefix slot (default: the last).  shared_len: device int32 scalar S, a multiple of 256; uses [n] i32.  Row i with uses[i] != 0 attends keys
+    0 .. S - 1 of the prefix slot and keys S .. pos[i] of slot i (pos[i] >= S); a row with uses[i] == 0 attends keys 0 .. pos[i] of slot i, with the
+    bits of `attn_decode_batch` in walking form.  shared_len_host: S where the host knows it (checked), else left to the device.  n <= 16.
+    -> o [n, q_heads, 128]."""
+    _need(q, name="q"); _need(kcache, name="kcache"); _need(vcache, name="vcache"); _need(pos, dtype=torch.int32, name="pos")
+    _need(shared_len, dtype=torch.int32, name="shared_len"); _need(uses, dtype=torch.int32, name="uses")
+    if q.dim() != 3 or q.shape[2] != 128 or q.stride(2) != 1 or q.stride(1) != 128:
+        raise ValueError("attn_decode_batch_prefix: q must be [n, q_heads, 128] with contiguous heads")
+    n, nq, _ = q.shape
+    if kcache.dim() != 4 or kcache.shape != vcache.shape or kcache.shape[3] != 128 or not kcache.is_contiguous() or not vcache.is_contiguous():
+        raise ValueError("attn_decode_batch_prefix: kcache / vcache must be contiguous [slots, kv_heads, max_ctx, 128] of one shape")
+    slots, nkv, max_ctx, _ = kcache.shape
+    if pos.numel() != n or not pos.is_contiguous() or uses.numel() != n or not uses.is_contiguous() or shared_len.numel() != 1:
+        raise ValueError(f"attn_decode_batch_prefix: {n} rows need {n} contiguous positions and flags and one shared length")
+    lib = _lib.load()
+    o = torch.empty((n, nq, 128), device=q.device, dtype=torch.bfloat16)
+    ws = torch.empty((lib.vila_attn_decode_batch_prefix_workspace_bytes(n, nq, max_ctx),), device=q.device, dtype=torch.uint8)
+    check(lib.vila_attn_decode_batch_prefix_bf16(q.data_ptr(), q.stride(0), kcache.data_ptr(), vcache.data_ptr(), kcache.stride(0), slots,
+                                                 slots - 1 if prefix_slot is None else int(prefix_slot), shared_len.data_ptr(),
+                                                 -1 if shared_len_host is None else int(shared_len_host), uses.data_ptr(), pos.data_ptr(), o.data_ptr(),
+                                                 o.stride(0), n, nq, nkv, max_ctx, float(scale if scale is not None else 128 ** -0.5), ws.data_ptr(),
+                                                 ws.numel(), _stream()), "attn_decode_batch_prefix")
+    return o
+
+
 def attn_append(q: torch.Tensor, kslot: torch.Tensor, vslot: torch.Tensor, past: int, scale: Optional[float] = None,
                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Causal attention with a key prefix (the append prefill's attention on its own): q [T, q_heads, 128] bf16 (rows may be strided) at positions

@@ -603,12 +603,25 @@ class HipBatchEngine:
     """The model side of `ContinuousBatcher`: KV slots of ONE open batched-decode session (`HipQwen2ForCausalLM.batch_open`), driven by
     the batcher's worker thread only.  sampling=True opens the session with per-row sampling (`batch_open(sampling=True)`): `admit` then takes
     a row's (temperature, top_k, top_p, seed) and a `ContinuousBatcher(batch_sampled=True)` puts sampled requests into rows.
-    max_ctx: positions per KV slot, up to 32768 (default 2048); `fits` admits what fits the slot, everything longer runs solo."""
+    max_ctx: positions per KV slot, up to 32768 (default 2048); `fits` admits what fits the slot, everything longer runs solo.
+    share_prefix=True opens the session with a prefix slot (`batch_open(shared_prefix=True)`): requests over the same media — a request's prefix is
+    its prompt up to and including its last media placeholder — can then share the K/V of that prefix (`prepare`, `pinned_key`, `pin`, `embed_tail`,
+    `admit(..., share=True)`), which a `ContinuousBatcher(share_prefix=True)` drives.  min_shared_len (default 2048): a prefix whose shared length would
+    be shorter is not pinned and its request takes an ordinary row — the prefix step's three attention launches cost more than they save on a short
+    prefix (a one-tile image, about 256 keys: 1.07 - 1.19x the ordinary step; `DESIGN.md` 4.3b).  A prefix that may be pinned must also fit a slot
+    with something behind it, so share_prefix needs max_ctx > min_shared_len: the default 2048 / 2048 pair could never share and is refused."""
 
     def __init__(self, model, tokenizer, n_slots: int = 8, max_ctx: int = 2048, max_new_tokens: int = 1024, eos_token_id=None,
-                 sampling: bool = False):
+                 sampling: bool = False, share_prefix: bool = False, min_shared_len: int = 2048):
         self.model, self.tokenizer = model, tokenizer
         self.sampling = bool(sampling)
+        self.share_prefix = bool(share_prefix)
+        self.min_shared_len = int(min_shared_len)
+        if self.share_prefix and int(max_ctx) <= max(self.min_shared_len, 256):
+            raise ValueError(f"HipBatchEngine(share_prefix=True): a prefix is pinned from min_shared_len = {max(self.min_shared_len, 256)} shared positions on and "
+                             f"has to fit a slot with its tail and reply behind it; max_ctx = {int(max_ctx)} leaves nothing to share (raise max_ctx, e.g. "
+                             "4096 for a dynamic_s2 document, or lower min_shared_len)")
+        self._pinned = None                                 # the session's prefix: its key, S, and its embedding rows S .. prefix rows - 1
         self.n_slots, self.max_ctx, self.max_new_tokens = int(n_slots), int(max_ctx), int(max_new_tokens)
         self.eos = _eos_set(_eos_of(tokenizer, eos_token_id))
         self.st = None
@@ -616,9 +629,66 @@ class HipBatchEngine:
     def _session(self):
         llm = self.model.llm
         if self.st is None or getattr(llm, "_bdecode", None) is not self.st:       # first use, or the weights moved and the session was dropped
-            self.st = llm.batch_open(self.n_slots, self.max_ctx, self.max_new_tokens, sampling=True) if self.sampling else \
-                llm.batch_open(self.n_slots, self.max_ctx, self.max_new_tokens)
+            kw = dict(sampling=True) if self.sampling else {}
+            if self.share_prefix:
+                kw["shared_prefix"] = True
+                self._pinned = None                                                 # a new session holds no prefix
+            self.st = llm.batch_open(self.n_slots, self.max_ctx, self.max_new_tokens, **kw)
         return self.st
+
+    @property
+    def shares_prefix(self) -> bool:
+        """Whether requests over the same media can share their prefix's K/V in this engine's batch."""
+        return self.share_prefix
+
+    def prepare(self, prompt, system):
+        """The host side of a request, done ONCE per request and handed on to `embed`, `pin` and `embed_tail`: media loaded and tiled, the prompt's
+        token ids, and the key of its prefix — the ids up to and including its last media placeholder plus a digest of the media bytes; None for a
+        request without media.  No tower, no projector."""
+        import hashlib
+        cfg = self.model.cfg
+        text, tiles, media_config = prepare_prompt(prompt, cfg)
+        ids = encode_with_images(self.tokenizer, prompt_text(self.tokenizer, text, system), cfg.image_token_id)
+        at = (ids == cfg.image_token_id).nonzero()
+        key, n_tail = None, 0
+        if at.numel() and tiles:
+            h = hashlib.sha1()
+            for t in tiles:
+                t = t.detach().cpu().contiguous()
+                h.update(str((tuple(t.shape), str(t.dtype))).encode())
+                h.update(t.view(torch.uint8).numpy().tobytes())
+            key, n_tail = (tuple(ids[:int(at[-1]) + 1].tolist()), h.hexdigest()), int(ids.numel()) - int(at[-1]) - 1
+        return SimpleNamespace(ids=ids, tiles=tiles, media_config=media_config, key=key, n_tail=n_tail)
+
+    @property
+    def pinned_key(self):
+        """The key of the prefix this engine's session holds, or None: none was pinned, or the session that held it is gone (the weights moved, the
+        llm opened another batch session)."""
+        if self.st is None or getattr(self.model.llm, "_bdecode", None) is not self.st:
+            self._pinned = None
+        return None if self._pinned is None else self._pinned.key
+
+    def pin(self, e, prep) -> bool:
+        """Make the prefix of the request (e = `embed` of it, prep = `prepare` of it) the session's shared prefix: the whole prompt is prefilled into the
+        prefix slot once, and its rows up to the last whole 256-position chunk of the prefix become the shared keys.  True: `admit(e, share=True)`
+        then takes the request without another prefill.  Only while no live row shares the current prefix, and only for a request that `fits`.
+        False, with the session's prefix left as it was: the shared length would be below min_shared_len, or the prompt does not fit a slot."""
+        rows = int(e.shape[0]) - prep.n_tail                                       # embedding rows up to the end of the last media item
+        if prep.key is None or rows // 256 * 256 < max(self.min_shared_len, 256) or int(e.shape[0]) + 1 > self.max_ctx:
+            return False
+        st = self._session()
+        self._pinned = None
+        S = self.model.llm.batch_set_prefix(st, e, prefix_len=rows)
+        self._pinned = SimpleNamespace(key=prep.key, S=S, rest=e[S:rows].clone())
+        return True
+
+    def embed_tail(self, prep):
+        """A request whose key is `pinned_key` -> (its embeddings from row S on, S): the pinned prefix's rows behind the last whole chunk, then the
+        text behind the last media placeholder, embedded the way `ChatSession.ask` embeds a new turn.  No tower, no projector."""
+        pin = self._pinned
+        tail = prep.ids[prep.ids.numel() - prep.n_tail:].to(pin.rest.device)
+        e = self.model.llm.embed_tokens(tail[None])[0].to(pin.rest.dtype) if tail.numel() else pin.rest[:0]
+        return torch.cat([pin.rest, e], 0), pin.S
 
     @property
     def batches_sampled(self) -> bool:
@@ -632,20 +702,25 @@ class HipBatchEngine:
     def fits(self, n_prompt_tokens: int, max_new_tokens: int) -> bool:
         return max_new_tokens <= self.max_new_tokens and n_prompt_tokens + max_new_tokens <= self.max_ctx
 
-    def embed(self, prompt, system):
-        """Prompt -> spliced embeddings [S, H] on the device (tower + projector + splice run here, on the worker thread)."""
+    def embed(self, prompt, system, prep=None):
+        """Prompt -> spliced embeddings [S, H] on the device (tower + projector + splice run here, on the worker thread).  prep: what `prepare`
+        returned for this request, so that its media is not loaded and tiled again."""
         cfg = self.model.cfg
         dev = str(self.model.device)
-        text, tiles, media_config = prepare_prompt(prompt, cfg)
-        ids = encode_with_images(self.tokenizer, prompt_text(self.tokenizer, text, system), cfg.image_token_id)[None].to(dev)
+        if prep is None:
+            text, tiles, media_config = prepare_prompt(prompt, cfg)
+            ids = encode_with_images(self.tokenizer, prompt_text(self.tokenizer, text, system), cfg.image_token_id)
+        else:
+            ids, tiles, media_config = prep.ids, prep.tiles, prep.media_config
         media = {"image": [t.to(device=dev, dtype=torch.bfloat16) for t in tiles]}
-        e, _, _ = self.model._embed(ids, media, media_config)
+        e, _, _ = self.model._embed(ids[None].to(dev), media, media_config)
         return e[0]
 
-    def admit(self, slot: int, embeds, sampling=None) -> int:
-        if sampling is None:
-            return self.model.llm.batch_admit(self._session(), slot, embeds)
-        return self.model.llm.batch_admit(self._session(), slot, embeds, sampling=sampling)
+    def admit(self, slot: int, embeds, sampling=None, share: bool = False, first_row: int = 0) -> int:
+        kw = {} if sampling is None else dict(sampling=sampling)
+        if share:
+            kw.update(share=True, first_row=first_row)
+        return self.model.llm.batch_admit(self._session(), slot, embeds, **kw)
 
     def run(self, k: int) -> None:
         self.model.llm.batch_run(self._session(), k)
@@ -678,13 +753,20 @@ class ContinuousBatcher:
     temperature > 0 and top_k (default 50) in 1..64 takes a free row like a greedy one — the reference's default request (0.2 / 0.9) then
     batches instead of stalling the line.  The trade: the batched step sums in another order than the solo step, so the ids of a sampled
     request are no longer those of its solo run (same distribution, same seed -> same reply within the batched path).  A request without a
-    seed gets one derived as `generate` derives it.  top_k = 0 or > 64 stays solo."""
+    seed gets one derived as `generate` derives it.  top_k = 0 or > 64 stays solo.
+    share_prefix=True (opt-in; needs an engine whose `shares_prefix` is true, i.e. `HipBatchEngine(share_prefix=True)`): requests over the same
+    media share the K/V of their common prefix.  When no live row shares the current prefix, a request with media that fits a slot PINS its own
+    (`engine.pin`: one tower / projector / prefill run); later requests with the same key (`engine.prepare(...).key == engine.pinned_key`) are
+    admitted as sharing rows, for which only the text behind the media is embedded and prefilled.  A request without media, with a prefix the engine finds too short to pay, or with another key
+    while sharers live, takes an ordinary row and does not wait; the pin moves once the sharers have retired.  `events` records ("pin", slot) and ("share", slot)."""
 
-    def __init__(self, engine, max_batch: int = 8, chunk: int = 8, batch_sampled: bool = False):
+    def __init__(self, engine, max_batch: int = 8, chunk: int = 8, batch_sampled: bool = False, share_prefix: bool = False):
         import queue
         import threading
         self.engine = engine
         self.batch_sampled = bool(batch_sampled) and bool(getattr(engine, "batches_sampled", False))
+        self.share_prefix = bool(share_prefix) and bool(getattr(engine, "shares_prefix", False))
+        self._pin_rows = set()                           # the live rows that share the engine's current prefix (`engine.pinned_key`)
         self._seedless = 0
         self.max_batch = int(max(1, min(16, max_batch, getattr(engine, "n_slots", max_batch))))
         self.chunk = int(max(1, chunk))
@@ -782,6 +864,27 @@ class ContinuousBatcher:
         if row.req.stream is not None:
             row.req.stream.end()
 
+    def _embed_for(self, req, slot):
+        """A request's embeddings for `slot` and how to admit them: (embeds, prompt positions, admit keywords).  Without share_prefix: the whole
+        prompt, an ordinary row.  With it the request is prepared once (media, ids, key) and is: a sharing row when its key is the one the engine
+        holds; the pin itself when no live row shares the current prefix, the request fits a slot and the engine finds the prefix worth pinning;
+        an ordinary row otherwise.  What does not fit is decided before anything is pinned: the caller then sends it solo, as ever."""
+        eng = self.engine
+        if not self.share_prefix:
+            e = eng.embed(req.prompt, req.system)
+            return e, int(e.shape[0]), {}
+        prep = eng.prepare(req.prompt, req.system)
+        if prep.key is not None and prep.key == eng.pinned_key:
+            e, first_row = eng.embed_tail(prep)
+            self.events.append(("share", slot))
+            return e, first_row + int(e.shape[0]), dict(share=True, first_row=first_row)
+        e = eng.embed(req.prompt, req.system, prep)
+        n = int(e.shape[0])
+        if prep.key is not None and not self._pin_rows and req.max_new >= 1 and eng.fits(n, req.max_new) and eng.pin(e, prep):
+            self.events.append(("pin", slot))
+            return e, n, dict(share=True)
+        return e, n, {}
+
     def _loop(self):
         """The worker: `_loop_body` under a guard — if the worker dies, everything it held and everything still queued fails with the
         cause instead of hanging (the futures / streams of a dead worker would never resolve)."""
@@ -838,14 +941,16 @@ class ContinuousBatcher:
                     try:
                         if not self._batchable(req) or req.gen.get("_solo"):
                             break
-                        e = eng.embed(req.prompt, req.system)
-                        if not eng.fits(int(e.shape[0]), req.max_new) or req.max_new < 1:
+                        e, n_prompt, how = self._embed_for(req, free[0])
+                        if not eng.fits(n_prompt, req.max_new) or req.max_new < 1:
                             req.gen = dict(req.gen, _solo=True)
                             break
                         pending.popleft()
                         slot = free.pop(0)
                         sampling = self._row_sampling(req)
-                        first = eng.admit(slot, e) if sampling is None else eng.admit(slot, e, sampling)
+                        first = eng.admit(slot, e, **how) if sampling is None else eng.admit(slot, e, sampling, **how)
+                        if how:
+                            self._pin_rows.add(slot)
                         row = SimpleNamespace(req=req, toks=[first], read=0, sent=0, closed=False)
                         self.events.append(("admit", slot, steps, len(rows)))
                         self._emit(row, [first])
@@ -853,6 +958,7 @@ class ContinuousBatcher:
                             self._finish(row, row.toks)
                             eng.release([slot])
                             free.append(slot)
+                            self._pin_rows.discard(slot)
                             self.events.append(("retire", slot, steps))
                             slot = None
                         else:
@@ -863,6 +969,7 @@ class ContinuousBatcher:
                             pending.popleft()
                         if slot is not None:
                             rows.pop(slot, None)
+                            self._pin_rows.discard(slot)
                             try:
                                 eng.release([slot])
                             except Exception:
@@ -896,6 +1003,7 @@ class ContinuousBatcher:
                         self._fail(r.req, ex)
                     free.extend(rows)
                     rows.clear()
+                    self._pin_rows.clear()
                     continue
                 steps += k
                 self.events.append(("run", k, len(rows)))
@@ -914,6 +1022,7 @@ class ContinuousBatcher:
                         done.append(slot)
                 for slot in done:
                     del rows[slot]
+                    self._pin_rows.discard(slot)
                     self.events.append(("retire", slot, steps))
                 idle = done + free                                     # idle rows took part in the steps too: re-wind them
                 eng.release(idle)
@@ -945,7 +1054,7 @@ def continuous_batching(model) -> bool:
 
 def create_app(model, tokenizer, model_name: str = "NVILA-8B", batch_window_s: Optional[float] = None, max_batch: int = 8,
                stream_timeout_s: Optional[float] = 600.0, batch_sampled: bool = False, max_ctx: int = 2048,
-               prompt_lookup_num_tokens: Optional[int] = None, spec_sample: bool = False):
+               prompt_lookup_num_tokens: Optional[int] = None, spec_sample: bool = False, share_prefix: bool = False):
     """FastAPI app with the reference's POST /chat/completions (server.py:171-290).  Import-time optional: needs fastapi + pydantic.
     batch_window_s: when set (any value), requests go through a batcher whose ONE worker thread owns the model: `ContinuousBatcher` (greedy
     requests join / leave the batched decode step between steps; sampled ones run solo on the same thread) where the model has the batched
@@ -959,7 +1068,11 @@ def create_app(model, tokenizer, model_name: str = "NVILA-8B", batch_window_s: O
     step; their replies are the greedy replies.  None (default): every request takes the path it always took.
     spec_sample=True (with prompt_lookup_num_tokens): sampled requests that run solo — the default request — speculate as well when their top_k
     lies in 1..64 (the sampled verify step's range); their replies are those of the same sampled request without drafts.  Other sampled
-    requests, and every sampled request without the flag, stay non-speculative."""
+    requests, and every sampled request without the flag, stay non-speculative.
+    share_prefix=True (ContinuousBatcher only; default off): requests over the same media — several questions about one video or document —
+    share the K/V of their common prefix in the batched session (`ContinuousBatcher(share_prefix=True)`): the media is encoded and prefilled once,
+    and every step reads its keys once for all of them.  Needs max_ctx above the engine's min_shared_len (2048): with the default max_ctx no
+    prefix worth sharing fits a slot, and the pairing is refused with a ValueError (`create_app(..., share_prefix=True, max_ctx=4096)` or more)."""
     from fastapi import FastAPI
     from fastapi.responses import JSONResponse, StreamingResponse
 
@@ -975,8 +1088,10 @@ def create_app(model, tokenizer, model_name: str = "NVILA-8B", batch_window_s: O
                 kw["max_ctx"] = int(max_ctx)
             if batch_sampled:
                 kw["sampling"] = True
+            if share_prefix:
+                kw["share_prefix"] = True
             engine = HipBatchEngine(model, tokenizer, **kw)
-            batcher = ContinuousBatcher(engine, max_batch=max_batch, batch_sampled=batch_sampled)
+            batcher = ContinuousBatcher(engine, max_batch=max_batch, batch_sampled=batch_sampled, **(dict(share_prefix=True) if share_prefix else {}))
         else:
             batcher = RequestBatcher(model, tokenizer, window_s=batch_window_s)
     app.state.batcher = batcher
