@@ -158,3 +158,106 @@ def decode_attn_ref(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, visible: 
 def visible_upto(lens, C: int, device="cpu") -> torch.Tensor:
     """[n, C] bool: row i sees keys 0 .. lens[i] - 1."""
     return torch.arange(C, device=device)[None, :] < torch.as_tensor(list(lens), device=device)[:, None]
+
+
+# ---- element-wise GEMM checks and framed buffers (tests/test_gemm_bound_cpu.py proves them, tests/test_gpu_gemm_elements.py uses them) ----------
+# A whole-matrix rel-L2 below 4e-3 leaves a factor 2.4 over the floor of a correct kernel (one bf16 rounding, 1.66e-3), spread over every
+# element: a fault confined to one row, column or tile corner fits inside it.  The bound below is per element and derived, not measured.
+BF16_U = 2.0 ** -8          # unit roundoff of bf16 under round-to-nearest
+FP32_U = 2.0 ** -24         # unit roundoff of fp32
+FRAME_PATTERN = {2: 0x7FA5, 4: 0x7FC0A5A5, 1: 0x5A}       # per element size: a NaN with a payload (bf16, fp32) / a byte
+
+
+def gemm_elem_bound(ref64: torch.Tensor, absprod64: torch.Tensor, K: int, roundings: int = 1, extra_fp32_ops: int = 2) -> torch.Tensor:
+    """Per-element bound on |out - ref| for out = bf16-rounded fp32 sum of K products (+ bias + residual):
+        roundings * 2^-8 * |ref|  +  (1 + 2^-8) * (K + extra_fp32_ops) * 2^-24 * absprod
+    `ref64`: the fp64 result on the same inputs; `absprod64`: |A| @ |W|^T + |bias| + |residual| in fp64, the magnitudes the kernel sums.  The
+    second term is the textbook bound on an fp32 sum of K products in ANY order (split-K, sliced rings and the hybrid tail only reorder), the
+    factor (1 + 2^-8) carries it through the final rounding.  roundings = 0: fp32 output; 2: the projection is rounded before the residual add."""
+    return roundings * BF16_U * ref64.abs() + (1.0 + BF16_U) * (K + extra_fp32_ops) * FP32_U * absprod64
+
+
+def assert_elementwise(out: torch.Tensor, ref64: torch.Tensor, bound: torch.Tensor, what: str = "") -> float:
+    """Every element finite and |out - ref64| <= bound.  A failure states the count, the worst err / bound and the (row, col) of the worst few
+    offenders, so that it names the tile.  -> the worst err / bound."""
+    o = out.detach().double()
+    assert o.shape == ref64.shape == bound.shape, (tuple(o.shape), tuple(ref64.shape), tuple(bound.shape))
+    bad = ~torch.isfinite(o)
+    n_bad = int(bad.sum())
+    if n_bad:
+        at = [tuple(int(i) for i in rc) for rc in bad.nonzero()[:8].tolist()]
+        raise AssertionError(f"{what}: {n_bad} non-finite elements of {o.numel()}, first at (row, col) {at}")
+    err = (o - ref64).abs()
+    ratio = torch.where(bound > 0, err / bound.clamp_min(1e-300), torch.where(err > 0, torch.full_like(err, float("inf")), torch.zeros_like(err)))
+    worst = float(ratio.max()) if ratio.numel() else 0.0
+    over = ratio > 1.0
+    n_over = int(over.sum())
+    if n_over:
+        top = ratio.flatten().topk(min(8, n_over))
+        ncol = o.shape[-1]
+        at = [(int(i) // ncol, int(i) % ncol, round(float(v), 2)) for v, i in zip(top.values.tolist(), top.indices.tolist())]
+        raise AssertionError(f"{what}: {n_over} of {o.numel()} elements over the bound, worst err / bound {worst:.3g}; (row, col, ratio) of the worst: {at}")
+    return worst
+
+
+def _int_view(t: torch.Tensor) -> torch.Tensor:
+    return t.view({1: torch.uint8, 2: torch.int16, 4: torch.int32}[t.element_size()])
+
+
+def _pattern_of(t: torch.Tensor) -> int:
+    p = FRAME_PATTERN[t.element_size()]
+    return p - (1 << 32) if p >= (1 << 31) else p
+
+
+def _frame_check(buf: torch.Tensor, r0: int, rows: int, cols: int, what: str):
+    def check():
+        iv = _int_view(buf).clone()
+        iv[r0:r0 + rows, :cols] = _pattern_of(buf)
+        hit = iv != _pattern_of(buf)
+        n = int(hit.sum())
+        if n:
+            at = [(int(r) - r0, int(c)) for r, c in hit.nonzero()[:8].tolist()]
+            raise AssertionError(f"{what}: {n} elements outside the [{rows}, {cols}] view were written; first at (row, col) relative to the view {at}")
+    return check
+
+
+def framed_out(M: int, N: int, ld_pad: int, guard_rows: int, dtype=torch.bfloat16, device="cuda", fill: torch.Tensor = None):
+    """-> (view, check): the view is rows [g, g + M), columns [0, N) of a [(M + 2 g), N + ld_pad] buffer pre-filled with a fixed non-zero bit
+    pattern (a NaN with a payload); check() asserts that every element outside the view still holds it bit for bit.  `fill` [M, N]: the view's
+    initial values (the residual stream of an in-place GEMM).  The caller keeps ld = N + ld_pad and g * ld 16-byte aligned."""
+    g, ld = guard_rows, N + ld_pad
+    buf = torch.empty((M + 2 * g, ld), dtype=dtype, device=device)
+    _int_view(buf).fill_(_pattern_of(buf))
+    view = buf[g:g + M, :N]
+    if fill is not None:
+        view.copy_(fill)
+    assert (ld * buf.element_size()) % 8 == 0 and view.data_ptr() % 16 == 0, (M, N, ld_pad, guard_rows)
+    return view, _frame_check(buf, g, M, N, f"output frame [{M}, {N}] ld {ld}")
+
+
+def framed_operand(t: torch.Tensor, ld_pad: int = 0, guard_rows: int = 0, pad=float("nan")) -> torch.Tensor:
+    """The same values as a view of a larger buffer whose padding columns and guard rows hold `pad` (NaN; 127 for int8): a read outside the operand
+    that reaches the result shows there.  1-D (bias, scales): `pad` on both sides, the view at an offset that is a multiple of 8 elements."""
+    if t.dim() == 1:
+        off = 8 * max(1, guard_rows)
+        buf = torch.full((t.numel() + 2 * off,), pad, dtype=t.dtype, device=t.device)
+        view = buf[off:off + t.numel()]
+    else:
+        R, C = t.shape
+        buf = torch.full((R + 2 * guard_rows, C + ld_pad), pad, dtype=t.dtype, device=t.device)
+        view = buf[guard_rows:guard_rows + R, :C]
+    view.copy_(t)
+    return view
+
+
+def framed_ws(n_bytes: int, device="cuda", guard_bytes: int = 4096):
+    """-> (ws, check): a uint8 workspace of exactly n_bytes with a patterned guard in front of it and behind it; check() asserts both guards intact."""
+    buf = torch.full((n_bytes + 2 * guard_bytes,), FRAME_PATTERN[1], dtype=torch.uint8, device=device)
+    ws = buf[guard_bytes:guard_bytes + n_bytes]
+
+    def check():
+        for name, part, base in (("before", buf[:guard_bytes], -guard_bytes), ("past", buf[guard_bytes + n_bytes:], n_bytes)):
+            hit = part != FRAME_PATTERN[1]
+            if bool(hit.any()):
+                raise AssertionError(f"workspace of {n_bytes} bytes: {int(hit.sum())} bytes written {name} it, first at byte offset {base + int(hit.nonzero()[0])}")
+    return ws, check

@@ -119,6 +119,15 @@ def test_gemm_strided_views_and_inplace_residual(ops):
     ref = x.float() + a.float() @ w.float().t()
     ops.gemm(a, w, residual=x, out=x)     # x += a w^T in place (how the residual stream is updated)
     assert rel_l2(x, ref) < 4e-3
+    # a strided output and a strided residual as well (ldc = N + 8, ldr = N + 4): separate buffers, then in place on the strided view;
+    # the columns behind the views must stay as they were
+    big_x, big_o = randn_bf16(M, N + 4, seed=7), randn_bf16(M, N + 8, seed=8)
+    xs, os_, pad_x, pad_o = big_x[:, :N], big_o[:, :N], big_x[:, N:].clone(), big_o[:, N:].clone()
+    ref = xs.float() + a.float() @ w.float().t()
+    ops.gemm(a, w, residual=xs, out=os_)
+    assert rel_l2(os_, ref) < 4e-3 and torch.equal(big_o[:, N:], pad_o) and torch.equal(big_x[:, N:], pad_x)
+    ops.gemm(a, w, residual=xs, out=xs)
+    assert rel_l2(xs, ref) < 4e-3 and torch.equal(big_x[:, N:], pad_x)
 
 
 @pytest.mark.parametrize("epi,fn", [(1, lambda t: torch.nn.functional.gelu(t, approximate="tanh")),
