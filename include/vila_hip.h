@@ -400,6 +400,9 @@ int vila_attn_fwd_bf16(const void* q, const void* k, const void* v, void* o, int
 int vila_gemv_bf16(const void* x, const void* norm_w, float eps, const void* W, const void* W2, const void* bias,
                    const void* residual, void* y_bf16, float* y_f32, int N, int K, int mode, vila_stream_t stream);
 int vila_argmax_f32(const float* logits, int n, int64_t* out, void* workspace /* >= 4 KiB */, vila_stream_t stream);
+/* Probe of the decode GEMVs' wave reduction: one wave per 64 inputs; lane l of wave w writes to out_xor[64 w + l] the sum the LDS-free xor
+ * butterfly (row swaps + DPP) gives it and to out_shfl[64 w + l] the sum of the shuffle butterfly it replaces.  The two must agree bit for bit. */
+int vila_wave_sum_probe(const float* in, float* out_xor, float* out_shfl, int n_waves, vila_stream_t stream);
 
 
 /* ------------------------------------------------------------------------------------------------------------

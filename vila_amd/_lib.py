@@ -220,6 +220,7 @@ PROTOTYPES = {
     "vila_gemv_bf16": (c_int, [c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                c_int, c_int, c_int, c_void_p]),
     "vila_argmax_f32": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "vila_wave_sum_probe": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     # ---- SFT step operators ----
     "vila_transpose_bf16": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_int64, c_void_p]),
     "vila_act_fwd_bf16": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p]),

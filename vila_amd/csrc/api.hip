@@ -1087,6 +1087,9 @@ extern "C" int vila_argmax_f32(const float* logits, int n, int64_t* out, void* w
     int* ti = (int*)((char*)workspace + 2048);
     return launch_argmax(logits, n, out, tv, ti, S(stream));
 }
+extern "C" int vila_wave_sum_probe(const float* in, float* out_xor, float* out_shfl, int n_waves, vila_stream_t stream) {
+    return launch_wave_sum_probe(in, out_xor, out_shfl, n_waves, S(stream));
+}
 
 // =================================================================================================
 // Training operator exports (backward kernels + optimizer); orchestrated by vila_amd/train.py

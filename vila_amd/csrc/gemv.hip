@@ -155,18 +155,100 @@ __device__ __forceinline__ void fma_batch(const Batch<R, U>& b, const bf16_t* sx
         for (int r = 0; r < R; ++r) acc[r] = dot8(b.v[u][r], xv, acc[r]);
     }
 }
-// dot products of R rows with x (LDS) for chunks [c_start, nch); accumulates into acc, then reduces across the wave
+// ---- the tail of a kernel: counted waits inside a batch, a reduction without LDS --------------------------------------
+// A wave's loads retire in order, so chunk 0 of a batch can be consumed while chunks 1 .. U - 1 are in flight — if the code from the batch's
+// loads to its waits is straight-line (behind a predicated load's join the compiler's wait falls back to a drain) and the dot product takes
+// the chunks in the order they were requested.  Mid-kernel the other waves of the SIMD hide the difference; on a wave's last group, which is
+// the kernel's tail, and where a wave has one group only (o_proj, down), nothing does.
+// A FULL batch (c0 + 64 U <= nch) is requested unpredicated; a partial one clamps every chunk index to the row's last chunk (no new address
+// is read) and puts load_batch's zeros in place of the clamped chunks where they are consumed.
+// The weights are global memory, and said to be: a flat load counts on both counters and its wait is a drain.  Chunk u's R requests stay in
+// front of chunk u + 1's (the scheduler would otherwise go row by row, and the first chunk would wait for half the batch).
+__device__ __forceinline__ u32x4 ldg_nt_global(const bf16_t* p) {
+    return __builtin_nontemporal_load((const __attribute__((address_space(1))) u32x4*)p);
+}
 template <int R, int U>
+__device__ __forceinline__ void load_batch_full(const bf16_t* const (&wrow)[R], int c0, int lane, Batch<R, U>& b) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) b.v[u][r] = ldg_nt_global(wrow[r] + (c0 + u * 64 + lane) * 8);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+template <int R, int U>
+__device__ __forceinline__ void load_batch_clamped(const bf16_t* const (&wrow)[R], int c0, int lane, int nch, Batch<R, U>& b) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const int c = c0 + u * 64 + lane < nch ? c0 + u * 64 + lane : nch - 1;
+#pragma unroll
+        for (int r = 0; r < R; ++r) b.v[u][r] = ldg_nt_global(wrow[r] + c * 8);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+// Chunk by chunk in request order, the scheduler held to it, so that the wait in front of chunk u leaves the R (U - 1 - u) later loads
+// outstanding.  The LDS read of x for chunk u + 1 goes out in front of chunk u's wait (one chunk of arithmetic covers an LDS trip; all U reads
+// up front would hold 4 U registers and cost a wave per SIMD).  Per acc[r] the fmaf chain is fma_batch's: u-major, then k.
+template <int R, int U, bool FULL>
+__device__ __forceinline__ void fma_batch_counted(const Batch<R, U>& b, const bf16_t* sx, int c0, int lane, int nch, float (&acc)[R]) {
+    auto read_x = [&](int u) {
+        const int c = c0 + u * 64 + lane;
+        return *(const u32x4*)(sx + (FULL || c < nch ? c : nch - 1) * 8);
+    };
+    u32x4 xc = read_x(0);
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        u32x4 xn = xc;
+        if (u + 1 < U) xn = read_x(u + 1);
+        __builtin_amdgcn_sched_barrier(0);
+        const bool in = FULL || c0 + u * 64 + lane < nch;
+        const u32x4 x = in ? xc : (u32x4){0u, 0u, 0u, 0u};
+#pragma unroll
+        for (int r = 0; r < R; ++r) acc[r] = dot8(in ? b.v[u][r] : (u32x4){0u, 0u, 0u, 0u}, x, acc[r]);
+#pragma unroll
+        for (int r = 0; r < R; ++r) asm volatile("" : "+v"(acc[r]));   // chunk u + 1 starts from chunk u's sums: no arithmetic of it moves up (bf2f_late's pin)
+        xc = xn;
+    }
+    __builtin_amdgcn_sched_barrier(0);
+}
+// a batch already requested (full or clamped, by one wave-uniform choice behind its loads: neither arm requests anything from memory)
+template <int R, int U>
+__device__ __forceinline__ void fma_batch_any(const Batch<R, U>& b, const bf16_t* sx, int c0, int lane, int nch, float (&acc)[R]) {
+    if (c0 + 64 * U <= nch) fma_batch_counted<R, U, true>(b, sx, c0, lane, nch, acc);
+    else fma_batch_counted<R, U, false>(b, sx, c0, lane, nch, acc);
+}
+// dot products of R rows with x (LDS) for chunks [c_start, nch); accumulates into acc, then reduces across the wave.
+// CW: counted waits inside a batch (above); XS: wave_sum_xor.  Both keep every bit; which kernels take them is decided per instantiation.
+template <int R, int U, bool CW, bool XS>
 __device__ __forceinline__ void wave_rows_dot(const bf16_t* const (&wrow)[R], const bf16_t* sx, int K, int lane, float (&acc)[R], int c_start) {
     const int nch = K >> 3;
-    for (int c0 = c_start; c0 < nch; c0 += 64 * U) {
-        Batch<R, U> b;
-        load_batch<R, U>(wrow, c0, lane, nch, b);
-        fma_batch<R, U>(b, sx, c0, lane, nch, acc);
+    if constexpr (CW) {
+        int c0 = c_start;
+        for (; c0 + 64 * U <= nch; c0 += 64 * U) {
+            Batch<R, U> b;
+            load_batch_full<R, U>(wrow, c0, lane, b);
+            fma_batch_counted<R, U, true>(b, sx, c0, lane, nch, acc);
+        }
+        if (c0 < nch) {
+            Batch<R, U> b;
+            load_batch_clamped<R, U>(wrow, c0, lane, nch, b);
+            fma_batch_counted<R, U, false>(b, sx, c0, lane, nch, acc);
+        }
+    } else {
+        for (int c0 = c_start; c0 < nch; c0 += 64 * U) {
+            Batch<R, U> b;
+            load_batch<R, U>(wrow, c0, lane, nch, b);
+            fma_batch<R, U>(b, sx, c0, lane, nch, acc);
+        }
     }
 #pragma unroll
-    for (int r = 0; r < R; ++r) acc[r] = wave_sum(acc[r]);
+    for (int r = 0; r < R; ++r) acc[r] = XS ? wave_sum_xor(acc[r]) : wave_sum(acc[r]);
 }
+// Which instantiations take the two parts: decided per kernel from two kernel-trace profiles per build (CHANGELOG), like gemv_flat_head below.
+constexpr bool gemv_tail_dpp(int MODE, int U) { return !(MODE == 0 && U == 7); }
+constexpr bool gemv_counted_waits(int MODE, int U) { return !(MODE == 0 && U == 7); }
+constexpr bool qkv_tail_dpp(int U) { return true; }
+constexpr bool qkv_counted_waits(int U) { return true; }
 
 // ------------------------------------------------------------------------------------------------
 // generic GEMV: y = W x (+bias) (+residual)   |   gate/up: y = silu(Wg x) * (Wu x)   |   x from attention partials
@@ -216,6 +298,7 @@ __device__ __forceinline__ void gemv_body(const bf16_t* W, const void* a1, const
     const int n_groups = (N + 1) >> 1;
     constexpr int R = (MODE == 1) ? 4 : 2;
     constexpr bool INPUTS_FIRST = MODE == 2 || (MODE == 0 && U < 7);
+    constexpr bool CW = gemv_counted_waits(MODE, U), XS = gemv_tail_dpp(MODE, U);
     const bf16_t* const W2 = (const bf16_t*)a2;                                                   // mode 1
     const bf16_t* const x = (const bf16_t*)a1;                                                    // modes 0, 1
     const bf16_t* const norm_w = (const bf16_t*)(MODE == 1 ? a3 : a2);                            // modes 0, 1
@@ -228,6 +311,7 @@ __device__ __forceinline__ void gemv_body(const bf16_t* W, const void* a1, const
     auto next_group = [&]() { if (ncu > 0) { j += WPB; g = j < cnt ? cm.gid(cu, j) : n_groups; } else g += stride; };
 
     auto rows_of = [&](int gg, const bf16_t* (&rows)[R]) {
+        if constexpr (CW) gg = __builtin_amdgcn_readfirstlane(gg);   // a group belongs to a wave, and said so its row bases are scalars: fewer address registers
         const int n = gg * 2;
         const int n1 = (n + 1 < N) ? n + 1 : n;
         if constexpr (MODE == 1) {
@@ -295,9 +379,9 @@ __device__ __forceinline__ void gemv_body(const bf16_t* W, const void* a1, const
             load_first_batch<R, U>(rows, lane, nch, has, b0);
             if constexpr (FLAT) tail_here(t);
             if (has) epi_fetch(g);                               // behind the weights: in front, the staging's loads waited for it at a join
-            stage_x_finish<NT, true>(x, norm_w, t.eps, K, sx, scratch, STAGE_X_ARGS(st));
+            stage_x_finish<NT, true, XS>(x, norm_w, t.eps, K, sx, scratch, STAGE_X_ARGS(st));
         }
-        if (has) first_batch_mask<R, U>(lane, nch, b0);
+        if constexpr (!CW) { if (has) first_batch_mask<R, U>(lane, nch, b0); }   // CW: masked where consumed (fma_batch_counted)
     } else {
         // the first weight batch in front of the staging, for short rows only (K <= 4096: the staging latency is comparable to the stream)
         if (has && K <= 4096) { rows_of(g, rows); load_batch<R, U>(rows, 0, lane, nch, b0); }
@@ -305,14 +389,14 @@ __device__ __forceinline__ void gemv_body(const bf16_t* W, const void* a1, const
         if (has) epi_fetch(g);
         STAGE_X_REGS(NT, st);
         stage_x_issue<NT>(x, norm_w, K, STAGE_X_ARGS(st));
-        stage_x_finish<NT, false>(x, norm_w, t.eps, K, sx, scratch, STAGE_X_ARGS(st));   // __syncthreads(): exactly the waits these kernels had
+        stage_x_finish<NT, false, XS>(x, norm_w, t.eps, K, sx, scratch, STAGE_X_ARGS(st));   // __syncthreads(): exactly the waits these kernels had
     }
     if (has && (INPUTS_FIRST || K <= 4096)) {
         float acc[R];
 #pragma unroll
         for (int r = 0; r < R; ++r) acc[r] = 0.f;
-        fma_batch<R, U>(b0, sx, 0, lane, nch, acc);
-        wave_rows_dot<R, U>(rows, sx, K, lane, acc, 64 * U);
+        if constexpr (CW) fma_batch_any<R, U>(b0, sx, 0, lane, nch, acc); else fma_batch<R, U>(b0, sx, 0, lane, nch, acc);
+        wave_rows_dot<R, U, CW, XS>(rows, sx, K, lane, acc, 64 * U);
         finish(g, acc);
         next_group();
     }
@@ -322,7 +406,7 @@ __device__ __forceinline__ void gemv_body(const bf16_t* W, const void* a1, const
         float acc[R];
 #pragma unroll
         for (int r = 0; r < R; ++r) acc[r] = 0.f;
-        wave_rows_dot<R, U>(rows, sx, K, lane, acc, 0);
+        wave_rows_dot<R, U, CW, XS>(rows, sx, K, lane, acc, 0);
         finish(g, acc);
     }
     // the greedy pick's first stage (lm_head of the batch-1 step): this block's rows reduced to one (max, index) pair with argmax's tie rule
@@ -475,6 +559,7 @@ __global__ __launch_bounds__(NT) void qkv_decode_kernel(const bf16_t* Wqkv, cons
     const int n_groups = (nq + 2 * nkv) * gph;
     const int nch = K >> 3;
     constexpr int WPB = NT / 64;
+    constexpr bool CW = qkv_counted_waits(U), XS = qkv_tail_dpp(U);
     const GemvPlan cm{ncu_xr, cf, xq};
     const int ncu = cm.ncu();
     const int cu = ncu > 0 ? (int)blockIdx.x : 0;
@@ -487,6 +572,7 @@ __global__ __launch_bounds__(NT) void qkv_decode_kernel(const bf16_t* Wqkv, cons
     int rows_i[2];
     const bf16_t* rows[2];
     auto rows_of = [&](int gg) {
+        if constexpr (CW) gg = __builtin_amdgcn_readfirstlane(gg);   // as in gemv_body
         const int head = (int)udiv_by_magic((unsigned)gg, gph_magic), gi = gg - head * gph;
         if (head >= nq + nkv) { rows_i[0] = head * hd + gi * 2; rows_i[1] = rows_i[0] + 1; }   // v: two consecutive rows
         else { rows_i[0] = head * hd + gi; rows_i[1] = rows_i[0] + half; }                        // q/k: the rotate-half pair (d, d + hd/2)
@@ -534,11 +620,11 @@ __global__ __launch_bounds__(NT) void qkv_decode_kernel(const bf16_t* Wqkv, cons
     if (has) epi_fetch(g);   // weights in front (gemv_kernel: no gain from the inputs first)
     STAGE_X_REGS(NT, st);
     stage_x_issue<NT>(x, norm_w, K, STAGE_X_ARGS(st));
-    stage_x_finish<NT, true>(x, norm_w, t.eps, K, sx, scratch, STAGE_X_ARGS(st));   // LDS-only syncs: measured faster here (CHANGELOG)
+    stage_x_finish<NT, true, XS>(x, norm_w, t.eps, K, sx, scratch, STAGE_X_ARGS(st));   // LDS-only syncs: measured faster here (CHANGELOG)
     if (has) {
         float acc[2] = {0.f, 0.f};
-        fma_batch<2, U>(b0, sx, 0, lane, nch, acc);
-        wave_rows_dot<2, U>(rows, sx, K, lane, acc, 64 * U);
+        if constexpr (CW) fma_batch_any<2, U>(b0, sx, 0, lane, nch, acc); else fma_batch<2, U>(b0, sx, 0, lane, nch, acc);
+        wave_rows_dot<2, U, CW, XS>(rows, sx, K, lane, acc, 64 * U);
         finish(g, acc);
         next_group();
     }
@@ -546,7 +632,7 @@ __global__ __launch_bounds__(NT) void qkv_decode_kernel(const bf16_t* Wqkv, cons
         rows_of(g);
         epi_fetch(g);
         float acc[2] = {0.f, 0.f};
-        wave_rows_dot<2, U>(rows, sx, K, lane, acc, 0);
+        wave_rows_dot<2, U, CW, XS>(rows, sx, K, lane, acc, 0);
         finish(g, acc);
     }
 }
@@ -577,6 +663,21 @@ int launch_qkv_decode(const QkvDecodeArgs& a, hipStream_t s) {
     VILA_REQUIRE(ncu <= GEMV_PLAN_MAX_CUS, "qkv_decode: the CU map holds up to %d CUs (got %d)", GEMV_PLAN_MAX_CUS, ncu);
     if (a.K <= 3584) qkv_launch<7>(per, grid, lds, s, a, n_groups, ncu);
     else qkv_launch<4>(per, grid, lds, s, a, n_groups, ncu);
+    VILA_LAUNCH_CHECK();
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// probe of the two wave reductions (tests/test_gpu_decode_tail.py): one wave per 64 inputs, every lane writes what each butterfly leaves it
+__global__ __launch_bounds__(64) void wave_sum_probe_kernel(const float* __restrict__ in, float* __restrict__ out_xor, float* __restrict__ out_shfl) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    const float v = in[i];
+    out_xor[i] = wave_sum_xor(v);
+    out_shfl[i] = wave_sum(v);
+}
+int launch_wave_sum_probe(const float* in, float* out_xor, float* out_shfl, int n_waves, hipStream_t s) {
+    VILA_REQUIRE(n_waves > 0 && in != nullptr && out_xor != nullptr && out_shfl != nullptr, "wave_sum_probe: %d waves", n_waves);
+    hipLaunchKernelGGL(wave_sum_probe_kernel, dim3(n_waves), dim3(64), 0, s, in, out_xor, out_shfl);
     VILA_LAUNCH_CHECK();
     return 0;
 }

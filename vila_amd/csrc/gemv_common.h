@@ -47,6 +47,31 @@ __device__ __forceinline__ void wave_amax(float& v, int& i) {
     }
 }
 
+// ---- wave reduction without LDS -------------------------------------------------------------------
+// The xor butterfly of wave_sum (common.h: v += v[lane ^ o] for o = 32, 16, 8, 4, 2, 1, the same partner at every step, so the same bits) on
+// the VALU alone.  __shfl_xor is ds_bpermute_b32: six dependent trips over the LDS crossbar, each behind an lgkmcnt wait, at the tail of every
+// row group.  Here: lane ^ 32 and ^ 16 by gfx950's row swaps (attn_common.h xor32_max), ^ 8 by a DPP rotation of the 16-lane row, ^ 4 by two
+// bank-masked rotations (a DPP lane reads lane (i - n) mod 16 under row_ror:n: the lanes with bit 2 set — banks 1 and 3 — find i ^ 4 = i - 4
+// under row_ror:4, the others i + 4 under row_ror:12), ^ 2 and ^ 1 by quad permutations.  IEEE addition is commutative, so which of the two
+// swapped values is "this lane's" does not matter (NaN payloads aside).
+template <int CTRL, int BANKS = 0xf>
+__device__ __forceinline__ float dpp_mov(float old, float x) {
+    return __uint_as_float(__builtin_amdgcn_update_dpp(__float_as_uint(old), __float_as_uint(x), CTRL, 0xf, BANKS, false));
+}
+__device__ __forceinline__ float wave_sum_xor(float v) {
+    unsigned u = __float_as_uint(v);
+    auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
+    v = __uint_as_float(r[0]) + __uint_as_float(r[1]);
+    u = __float_as_uint(v);
+    r = __builtin_amdgcn_permlane16_swap(u, u, false, false);
+    v = __uint_as_float(r[0]) + __uint_as_float(r[1]);
+    v += dpp_mov<0x128>(v, v);                                   // row_ror:8
+    v += dpp_mov<0x12c, 0x5>(dpp_mov<0x124, 0xa>(v, v), v);      // row_ror:4 on banks 1, 3; row_ror:12 on banks 0, 2
+    v += dpp_mov<0x4e>(v, v);                                    // quad_perm:[2,3,0,1]
+    v += dpp_mov<0xb1>(v, v);                                    // quad_perm:[1,0,3,2]
+    return v;
+}
+
 // ---- activation staging -------------------------------------------------------------------------
 // stage x (optionally RMS-normalised with gain, HF rounding order) as bf16 into LDS, once per block of NT threads (NT = 256 x the blocks a CU
 // used to hold: one copy per CU instead of one per 256 threads).
@@ -57,7 +82,7 @@ __device__ __forceinline__ void wave_amax(float& v, int& i) {
 //                  chunk and its value dropped in the finish: straight-line code, so the waits count loads instead of draining them): x and the gain of this thread's chunks and, in the four summing waves,
 //                  their chunks of the sum of squares; without a norm, the thread's first PC chunks of x;
 //   stage_x_finish does the rest: sum of squares, sync, scaling, LDS writes, sync.
-// The sum of squares is formed by the FIRST FOUR waves alone, each thread over the chunks tid + 256 i in that order, then wave_sum, then
+// The sum of squares is formed by the FIRST FOUR waves alone, each thread over the chunks tid + 256 i in that order, then wave_sum (or wave_sum_xor: the same bits), then
 // scratch[0] + ... + scratch[3]: the summation order of the 256-thread form, so the result does not depend on NT.  The other waves join in the
 // scaling and the LDS writes, which are element-wise.
 // Single pass for K <= 8192 (x kept in registers between the sum of squares and the scaling); beyond, the first four chunks of the sum of squares
@@ -109,7 +134,8 @@ __device__ __forceinline__ void stage_x_issue(const bf16_t* x, const bf16_t* __r
     }
 }
 // LDS_SYNC: the block syncs are sync_lds() (callers with loads in flight that the staging must not drain); otherwise __syncthreads()
-template <int NT, bool LDS_SYNC>
+// XOR_SUM: the sum of squares is reduced by wave_sum_xor (the same bits as wave_sum, no LDS trip in front of the first barrier)
+template <int NT, bool LDS_SYNC, bool XOR_SUM = false>
 __device__ __forceinline__ void stage_x_finish(const bf16_t* x, const bf16_t* __restrict__ norm_w, float eps, int K, bf16_t* sx, float* scratch,
                                                u32x4 (&v)[StageX<NT>::MAXC], u32x4 (&xs)[StageX<NT>::SC], u32x4 (&gs)[StageX<NT>::SC],
                                                u32x4& t) {
@@ -145,7 +171,7 @@ __device__ __forceinline__ void stage_x_finish(const bf16_t* x, const bf16_t* __
                 for (int k = 0; k < 4; ++k) { const float a = lo_bf(t[k]), b = hi_bf(t[k]); s += a * a + b * b; }
             }
         }
-        s = wave_sum(s);
+        s = XOR_SUM ? wave_sum_xor(s) : wave_sum(s);
         if ((tid & 63) == 0) scratch[tid >> 6] = s;
     }
     if constexpr (NT == 256) {

@@ -55,6 +55,8 @@ int launch_rope_kv(bf16_t* qkv, const float* cs, const float* sn, const int32_t*
 int launch_embed_gather(const bf16_t* table, const int64_t* ids, bf16_t* out, int n, int H, int64_t vocab, hipStream_t s);
 int launch_copy_rows(const bf16_t* src, bf16_t* dst, const int32_t* src_row, const int32_t* dst_row, int n, int H, hipStream_t s);
 int launch_argmax(const float* logits, int V, int64_t* out, float* tmpv, int* tmpi, hipStream_t s);
+// probe of wave_sum_xor (gemv_common.h) against wave_sum: one wave per 64 inputs, every lane writes both sums
+int launch_wave_sum_probe(const float* in, float* out_xor, float* out_shfl, int n_waves, hipStream_t s);
 // final pick of the batch-1 greedy step: merges the n (max, index) pairs left by the lm_head GEMV (GemvArgs::amax_v), writes *token and advances
 // the state like launch_decode_advance
 int launch_argmax_pick_advance(const float* tv, const int* ti, int n, int64_t* token, int32_t* pos, int64_t* out_ids, int32_t* n_out, int max_out,

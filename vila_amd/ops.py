@@ -210,6 +210,17 @@ def argmax(logits: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def wave_sum_probe(x: torch.Tensor):
+    """Both wave reductions of the decode GEMVs over every 64 consecutive fp32 inputs: (LDS-free xor butterfly, shuffle butterfly), each
+    the size of x, every lane's own result."""
+    _need(x, dtype=torch.float32, name="x")
+    if x.numel() == 0 or x.numel() % 64:
+        raise ValueError(f"wave_sum_probe: {x.numel()} inputs are not whole waves of 64")
+    a, b = torch.empty_like(x), torch.empty_like(x)
+    check(_lib.load().vila_wave_sum_probe(x.data_ptr(), a.data_ptr(), b.data_ptr(), x.numel() // 64, _stream()), "wave_sum_probe")
+    return a, b
+
+
 def sample(logits: torch.Tensor, temperature: float = 1.0, top_k: int = 50, top_p: float = 1.0, seed: int = 0,
            counter: Optional[torch.Tensor] = None, return_dist: bool = False):
     """HF sampling on the device (GenerationMixin.sample): logits / temperature -> TopK (any k >= 1; 0 = no top-k filter, as HF treats it) ->
