@@ -645,6 +645,41 @@ int vila_llm_prefill_append_w4(const VilaLlmWeights* w, const VilaLlmLayerW4* ql
                                const VilaKvCache* cache, const int32_t* last_rows, int n_last, float* last_logits, void* final_hidden,
                                void* layer_hidden, void* workspace, size_t workspace_bytes, vila_stream_t stream);
 
+/* Repetition, presence and frequency penalties in front of the token choice (vila_amd/csrc/penalty.hip): the first element of HF's processor chain,
+ * ahead of temperature -> top-k -> top-p.  Row r keeps counts[r][vocab] (uint16, rows ld_counts apart): how often its request has GENERATED each id.
+ * The table is zero when a request starts (the host's duty), saturates at 65535 and never counts the prompt.  One launch, per row r and index i:
+ *   bump        counts[r][token[r]] += 1 for the token the step consumes (token NULL or an id outside 0 .. vocab - 1: nothing), before the count is used
+ *   repetition  c > 0: y = x < 0 ? x * rep : x / rep               (HF RepetitionPenaltyLogitsProcessor)
+ *   frequency   y = y - freq * (float)c                            (OpenAI's definition, vLLM's order)
+ *   presence    c > 0: y = y - pres
+ * each ONE correctly rounded fp32 operation, so y is bit for bit the same expression in torch on the CPU and rep = 1, pres = freq = 0 return x's bits.
+ * All members are DEVICE arrays read at run time (the three parameters hold one entry per row): one captured hipGraph serves any values. */
+typedef struct {
+    const float* repetition;    /* [n]; > 0 (the host checks) */
+    const float* presence;      /* [n] */
+    const float* frequency;     /* [n] */
+    uint16_t* counts;           /* [n][ld_counts] */
+    int64_t ld_counts;          /* >= vocab */
+} VilaPenalties;
+/* The operator: logits [n][ld] fp32 -> out [n][ld_out] fp32 (nothing at or beyond vocab is read or written); pick_v / pick_i (both or neither)
+ * [n][vila_logits_penalize_slices()]: per slice of a processed row its maximum and the first index that holds it. */
+int vila_logits_penalize_slices(void);
+int vila_logits_penalize_f32(const float* logits, int64_t ld, int n, int vocab, const VilaPenalties* pen, const int64_t* token /*nullable: no bump*/,
+                             float* out, int64_t ld_out, float* pick_v, int* pick_i /*nullable*/, vila_stream_t stream);
+/* The decode steps with that launch between the logits and the pick: st->logits stays the raw model logits, the pick (greedy: first index of the
+ * maximum; sampled: the sampler of the plain step, unchanged) runs on the processed row, and token[] is counted before it is replaced.  One entry
+ * per driver: qlayers NULL = bf16, else the W4 step; sp NULL = greedy; prefix NULL = a plain batch session.  The launches in front of the pick are
+ * the plain steps', so the logits are the same bits.  Workspaces: the sizes below (they differ from the plain steps').  The verify steps have no
+ * penalised form. */
+size_t vila_llm_decode_penalized_workspace_bytes(const VilaLlmShape* s, int max_ctx);
+int vila_llm_decode_step_penalized(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers /*[host], nullable*/, const VilaKvCache* cache,
+                                   const VilaDecodeState* st, void* workspace, size_t workspace_bytes, const VilaSampling* sp /*nullable*/,
+                                   const VilaPenalties* pen, vila_stream_t stream);
+size_t vila_llm_decode_batch_penalized_workspace_bytes(const VilaLlmShape* s, int n, int max_ctx, int prefix);
+int vila_llm_decode_step_batch_penalized(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers /*[host], nullable*/, const VilaKvCache* cache,
+                                         const VilaDecodeBatch* st, const VilaDecodePrefix* prefix /*nullable*/, void* workspace, size_t workspace_bytes,
+                                         const VilaBatchSampling* sp /*nullable*/, const VilaPenalties* pen, vila_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,123 @@
+"""What repetition / presence / frequency penalties cost a decode step, one process on one GPU:
+
+  NVILA-8B widths (seeded synthetic weights, 1 x 448^2 image + 512-token prompt per row: 769 keys), bf16, ms per step of
+    solo greedy, solo sampled (temperature 0.2 / top_k 50 / top_p 0.9), and the greedy batched step at n = 2, 8 and 16 rows, each
+      a. without penalties           (the plain session: vila_llm_decode_step / _sample / _batch, the code path of a build without the feature),
+      b. with neutral penalties      (the penalised session at 1 / 0 / 0: vila_llm_decode_step[_batch]_penalized — what the extra launch costs),
+      c. with 1.1 / 0 / 0            (the same launches; the values are read from device arrays).
+
+    python tools/penalty_bench.py [--steps 50] [--iters 5] [--layers 28] [--out profiles/penalty_bench.json]
+
+Timing: each step is one hipGraph replay (the graph generate() captured); a figure is the median over `--iters` timings of `--steps` back-to-back
+replays, divided by `--steps`, after one warm-up round; the spread is max - min of those timings.  The baseline of every delta is case a of the
+same run."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+from vila_amd import _lib, configs, synthetic  # noqa: E402
+from vila_amd._lib import check  # noqa: E402
+
+NS = (2, 8, 16)
+SERVER_DEFAULT = (0.2, 50, 0.9)
+CASES = (("none", None), ("neutral", (1.0, 0.0, 0.0)), ("rep_1.1", (1.1, 0.0, 0.0)))
+
+
+def model_and_inputs(layers, prompt_tokens, n_max):
+    from vila_amd.vlm import build_model
+    cfg = configs.nvila_8b()
+    cfg.llm.num_hidden_layers = layers
+    model = build_model(cfg, seed=0)
+    pixels = synthetic.make_pixels(cfg, n_max, 0, device="cuda", dtype=torch.bfloat16)
+    ids = torch.stack([synthetic.make_prompt(cfg, prompt_tokens, 1, i) for i in range(n_max)], 0).cuda()
+    e, _, m = model._embed(ids, {"image": [pixels[i] for i in range(n_max)]})
+    return cfg, model, e, m
+
+
+def time_replays(graph, stream, steps, iters):
+    lib = _lib.load()
+    ts = []
+    with torch.cuda.stream(stream):
+        for it in range(iters + 1):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record(stream)
+            for _ in range(steps):
+                check(lib.vila_graph_launch(graph, stream.cuda_stream), "graph_launch")
+            b.record(stream)
+            b.synchronize()
+            if it:                                              # the first round warms up
+                ts.append(a.elapsed_time(b) / steps)
+    return statistics.median(ts), (max(ts) - min(ts))
+
+
+def solo_ms(llm, e, m, steps, iters, sampled, pen):
+    max_new = (iters + 1) * steps + 2
+    n = int(m[0].sum())
+    sampling = SERVER_DEFAULT + (1000,) if sampled else None
+    kw = {} if pen is None else dict(penalties=pen)
+    llm._generate_solo(e[:1, :n], None, max_new, -1, sampling, True, False, None, None, None, **kw)      # session + captured graph
+    torch.cuda.synchronize()
+    st = llm._decode
+    assert st is not None and st.graph is not None and (st.sampling is not None) == sampled and (st.pen is not None) == (pen is not None)
+    st.pos.fill_(n); st.n_out.zero_()
+    return time_replays(st.graph, st.stream, steps, iters)
+
+
+def batched_ms(llm, e, m, n, steps, iters, pen):
+    max_new = (iters + 1) * steps + 2
+    kw = {} if pen is None else dict(penalties=pen)
+    out = llm._generate_batch(e[:n], m[:n], max_new, -1, None, use_graph=True, **kw)                     # session + captured graph
+    torch.cuda.synchronize()
+    st = llm._bdecode
+    assert st is not None and st.graph is not None and out.shape == (n, max_new) and (st.pen is not None) == (pen is not None)
+    S = [int(v) for v in m[:n].sum(1).tolist()]
+    st.pos.copy_(torch.tensor(S, dtype=torch.int32)); st.n_out.zero_()
+    return time_replays(st.graph, st.stream, steps, iters)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--iters", type=int, default=5)
+    ap.add_argument("--layers", type=int, default=28)
+    ap.add_argument("--prompt-tokens", type=int, default=512)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "penalty_bench.json"))
+    a = ap.parse_args()
+
+    cfg, model, e, m = model_and_inputs(a.layers, a.prompt_tokens, max(NS))
+    llm = model.llm
+    S = int(m[0].sum())
+    configs_ = [("solo_greedy", lambda pen: solo_ms(llm, e, m, a.steps, a.iters, False, pen)),
+                ("solo_sampled", lambda pen: solo_ms(llm, e, m, a.steps, a.iters, True, pen))]
+    configs_ += [(f"batch_{n}", (lambda pen, n=n: batched_ms(llm, e, m, n, a.steps, a.iters, pen))) for n in NS]
+    rows = []
+    for name, run in configs_:
+        r = {"config": name}
+        for case, pen in CASES:
+            ms, spread = run(pen)
+            r[f"{case}_ms"] = round(ms, 4)
+            r[f"{case}_spread_us"] = round(spread * 1e3, 1)
+        r["neutral_minus_none_us"] = round((r["neutral_ms"] - r["none_ms"]) * 1e3, 1)
+        r["rep_1.1_minus_none_us"] = round((r["rep_1.1_ms"] - r["none_ms"]) * 1e3, 1)
+        rows.append(r)
+        print(json.dumps(r), flush=True)
+    res = {"config": {"model": cfg.name, "layers": a.layers, "dtype": "bf16", "vocab": cfg.llm.vocab_size,
+                      "context": f"1 x 448^2 image + {a.prompt_tokens}-token prompt per row (S={S})", "steps_per_timing": a.steps, "timings": a.iters,
+                      "method": "graph replays, median of timings after one warm-up round; spread = max - min of the timings",
+                      "solo_sampled": "temperature 0.2, top_k 50, top_p 0.9", "baseline": "none_ms of the same run (the unpenalised session)"},
+           "rows": rows}
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()

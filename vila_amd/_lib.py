@@ -81,6 +81,10 @@ class VilaBatchSampling(C.Structure):
     _fields_ = [("temperature", c_void_p), ("top_k", c_void_p), ("top_p", c_void_p), ("seed", c_void_p)]
 
 
+class VilaPenalties(C.Structure):
+    _fields_ = [("repetition", c_void_p), ("presence", c_void_p), ("frequency", c_void_p), ("counts", c_void_p), ("ld_counts", c_int64)]
+
+
 class VilaDecodeState(C.Structure):
     _fields_ = [("pos", c_void_p), ("token", c_void_p), ("out_ids", c_void_p), ("n_out", c_void_p),
                 ("max_out", c_int), ("logits", c_void_p)]
@@ -281,6 +285,16 @@ PROTOTYPES = {
                                  GRAD_READY_CB, c_void_p, c_void_p]),
     "vila_s2_merge_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, C.POINTER(C.c_int32), c_void_p]),
     "vila_s2_merge_bwd_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, C.POINTER(C.c_int32), c_void_p]),
+    # ---- repetition / presence / frequency penalties ----
+    "vila_logits_penalize_slices": (c_int, []),
+    "vila_logits_penalize_f32": (c_int, [c_void_p, c_int64, c_int, c_int, C.POINTER(VilaPenalties), c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "vila_llm_decode_penalized_workspace_bytes": (c_size_t, [C.POINTER(VilaLlmShape), c_int]),
+    "vila_llm_decode_step_penalized": (c_int, [C.POINTER(VilaLlmWeights), C.POINTER(VilaLlmLayerW4), C.POINTER(VilaKvCache), C.POINTER(VilaDecodeState),
+                                               c_void_p, c_size_t, C.POINTER(VilaSampling), C.POINTER(VilaPenalties), c_void_p]),
+    "vila_llm_decode_batch_penalized_workspace_bytes": (c_size_t, [C.POINTER(VilaLlmShape), c_int, c_int, c_int]),
+    "vila_llm_decode_step_batch_penalized": (c_int, [C.POINTER(VilaLlmWeights), C.POINTER(VilaLlmLayerW4), C.POINTER(VilaKvCache), C.POINTER(VilaDecodeBatch),
+                                                     C.POINTER(VilaDecodePrefix), c_void_p, c_size_t, C.POINTER(VilaBatchSampling), C.POINTER(VilaPenalties),
+                                                     c_void_p]),
 }
 
 _lib: Optional[C.CDLL] = None

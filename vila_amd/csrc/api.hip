@@ -592,7 +592,7 @@ static int decode_attn_mode() {
     return g_decode_attn;
 }
 static int decode_step_impl(const VilaLlmWeights* w, const VilaLlmLayerW4* ql, const VilaKvCache* cache, const VilaDecodeState* st,
-                            void* workspace, size_t workspace_bytes, const VilaSampling* sp, vila_stream_t stream);
+                            void* workspace, size_t workspace_bytes, const VilaSampling* sp, vila_stream_t stream, const VilaPenalties* pen = nullptr);
 extern "C" int vila_llm_decode_step(const VilaLlmWeights* w, const VilaKvCache* cache, const VilaDecodeState* st,
                                     void* workspace, size_t workspace_bytes, vila_stream_t stream) {
     return decode_step_impl(w, nullptr, cache, st, workspace, workspace_bytes, nullptr, stream);
@@ -616,6 +616,29 @@ extern "C" int vila_llm_decode_step_w4_sample(const VilaLlmWeights* w, const Vil
     VILA_REQUIRE(ql != nullptr, "llm_decode_w4: the int4 layers are NULL");
     return decode_step_impl(w, ql, cache, st, workspace, workspace_bytes, sp, stream);
 }
+// The penalised batch-1 step (penalty.hip): ql and sp nullable — bf16 / W4, greedy / sampled in one entry.
+static int penalties_ok(const VilaPenalties* pen, int vocab, const char* fn) {
+    VILA_REQUIRE(pen != nullptr && pen->repetition != nullptr && pen->presence != nullptr && pen->frequency != nullptr && pen->counts != nullptr,
+                 "%s: the penalties or one of their arrays are NULL", fn);
+    VILA_REQUIRE(pen->ld_counts >= vocab, "%s: the count rows (%lld apart) are shorter than the vocabulary %d", fn, (long long)pen->ld_counts, vocab);
+    return 0;
+}
+extern "C" size_t vila_llm_decode_penalized_workspace_bytes(const VilaLlmShape* s, int max_ctx) {
+    return align_up(vila_llm_decode_workspace_bytes(s, max_ctx), 256) + align_up((size_t)s->vocab * 4, 256) + 2 * align_up((size_t)PEN_SOLO_SLICES * 4, 256) + 256;
+}
+extern "C" int vila_llm_decode_step_penalized(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers, const VilaKvCache* cache, const VilaDecodeState* st,
+                                              void* workspace, size_t workspace_bytes, const VilaSampling* sp, const VilaPenalties* pen, vila_stream_t stream) {
+    VILA_REQUIRE(w != nullptr, "llm_decode_penalized: the weights are NULL");
+    VILA_TRY(penalties_ok(pen, w->shape.vocab, "llm_decode_penalized"));
+    return decode_step_impl(w, qlayers, cache, st, workspace, workspace_bytes, sp, stream, pen);
+}
+extern "C" int vila_logits_penalize_slices(void) { return PEN_PICK_SLICES; }
+extern "C" int vila_logits_penalize_f32(const float* logits, int64_t ld, int n, int vocab, const VilaPenalties* pen, const int64_t* token, float* out,
+                                        int64_t ld_out, float* pick_v, int* pick_i, vila_stream_t stream) {
+    VILA_REQUIRE(pen != nullptr, "logits_penalize: the penalties are NULL");
+    const Penalties P{pen->repetition, pen->presence, pen->frequency, pen->counts, pen->ld_counts};
+    return launch_penalize(logits, ld, n, vocab, P, token, out, ld_out, PEN_PICK_SLICES, pick_v, pick_i, S(stream));
+}
 extern "C" size_t vila_sample_workspace_bytes(void) { return sample_workspace_bytes(); }
 extern "C" int vila_sample_f32(const float* logits, int n, const VilaSampling* sp, const int32_t* counter, int64_t* out, void* workspace,
                                float* dist_out, vila_stream_t stream) {
@@ -628,13 +651,14 @@ extern "C" int vila_llm_decode_chain_error(void*, vila_stream_t) { return 0; }
 // The batch-1 step: ql == nullptr runs the bf16 projections, otherwise the int4 layers' W4A16 GEMVs (the lm_head stays bf16 either way, as
 // AWQ / TinyChat keep it fp16).  Only the four projection launches of a layer differ between the two.
 static int decode_step_impl(const VilaLlmWeights* w, const VilaLlmLayerW4* ql, const VilaKvCache* cache, const VilaDecodeState* st,
-                            void* workspace, size_t workspace_bytes, const VilaSampling* sp, vila_stream_t stream) {
+                            void* workspace, size_t workspace_bytes, const VilaSampling* sp, vila_stream_t stream, const VilaPenalties* pen) {
     const VilaLlmShape& sh = w->shape;
     hipStream_t s = S(stream);
     const bool w4 = ql != nullptr;
     const char* fn = w4 ? "llm_decode_w4" : "llm_decode";
     VILA_REQUIRE(cache != nullptr && st != nullptr, "%s: cache/state is NULL", fn);
-    VILA_REQUIRE(workspace_bytes >= vila_llm_decode_workspace_bytes(&sh, cache->max_ctx), "%s: workspace too small", fn);
+    VILA_REQUIRE(workspace_bytes >= (pen != nullptr ? vila_llm_decode_penalized_workspace_bytes(&sh, cache->max_ctx) : vila_llm_decode_workspace_bytes(&sh, cache->max_ctx)),
+                 "%s: workspace too small", fn);
     const int H = sh.hidden, F = sh.inter, hd = sh.head_dim, QS = sh.q_heads * hd, KS = sh.kv_heads * hd;
     const int ns = dec_splits(cache->max_ctx);
     Arena a(workspace, workspace_bytes);
@@ -650,6 +674,10 @@ static int decode_step_impl(const VilaLlmWeights* w, const VilaLlmLayerW4* ql, c
     float* rope_cs = a.take<float>(hd);
     bf16_t* ao = a.take<bf16_t>(QS);
     void* smp_ws = a.take<char>(sample_workspace_bytes());
+    // the penalised step (behind the plain step's layout): the processed logits and the pairs of its greedy pick
+    float* pen_y = pen != nullptr ? a.take<float>(sh.vocab) : nullptr;
+    float* pen_v = pen != nullptr ? a.take<float>(PEN_SOLO_SLICES) : nullptr;
+    int* pen_i = pen != nullptr ? a.take<int>(PEN_SOLO_SLICES) : nullptr;
     VILA_REQUIRE(a.ok(), "%s: workspace arena overflow", fn);
     const size_t per_layer = (size_t)cache->n_slots * sh.kv_heads * cache->max_ctx * hd;
 
@@ -697,11 +725,22 @@ static int decode_step_impl(const VilaLlmWeights* w, const VilaLlmLayerW4* ql, c
     lm.x = x; lm.norm_w = B(w->norm_w); lm.eps = sh.rms_eps; lm.W = B(w->lm_head); lm.y_f32 = st->logits; lm.N = sh.vocab; lm.K = H; lm.mode = 0;
     // greedy: every lm_head block also reduces its rows to one (max, index) pair, and one small launch merges the pairs, writes the token and
     // advances the state; sampled: the sampler reads the logits, then the advance
-    if (sp == nullptr) { lm.amax_v = tv; lm.amax_i = ti; }
+    // penalised: lm_head without its fused pick, then one launch that bumps the count of the consumed token (st->token still holds it), writes the
+    // processed row to pen_y and leaves its greedy pairs; the pick reads pen_y, st->logits stays raw
+    if (sp == nullptr && pen == nullptr) { lm.amax_v = tv; lm.amax_i = ti; }
     VILA_TRY(launch_gemv(lm, s));
+    const float* pick_src = st->logits;
+    if (pen != nullptr) {
+        const Penalties P{pen->repetition, pen->presence, pen->frequency, pen->counts, pen->ld_counts};
+        VILA_TRY(launch_penalize(st->logits, sh.vocab, 1, sh.vocab, P, st->token, pen_y, sh.vocab, PEN_SOLO_SLICES, sp != nullptr ? nullptr : pen_v,
+                                 sp != nullptr ? nullptr : pen_i, s));
+        pick_src = pen_y;
+    }
     if (sp != nullptr) {
-        VILA_TRY(launch_sample(st->logits, sh.vocab, sp->temperature, sp->top_k, sp->top_p, sp->seed, sp->seed_dev, st->pos, st->token, smp_ws, nullptr, s));
+        VILA_TRY(launch_sample(pick_src, sh.vocab, sp->temperature, sp->top_k, sp->top_p, sp->seed, sp->seed_dev, st->pos, st->token, smp_ws, nullptr, s));
         VILA_TRY(launch_decode_advance(st->pos, st->token, st->out_ids, st->n_out, st->max_out, s));
+    } else if (pen != nullptr) {
+        VILA_TRY(launch_argmax_pick_advance(pen_v, pen_i, PEN_SOLO_SLICES, st->token, st->pos, st->out_ids, st->n_out, st->max_out, s));
     } else {
         VILA_TRY(launch_argmax_pick_advance(tv, ti, n_pick, st->token, st->pos, st->out_ids, st->n_out, st->max_out, s));
     }
@@ -786,7 +825,7 @@ static int blayer_tables(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers,
 // prefix step's, which a plain one never reaches.
 static int decode_step_batch_impl(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers, const VilaKvCache* cache, const VilaDecodeBatch* st,
                                   void* workspace, size_t workspace_bytes, const VilaBatchSampling* sp, vila_stream_t stream,
-                                  const VilaDecodePrefix* px = nullptr) {
+                                  const VilaDecodePrefix* px = nullptr, const Penalties* pen = nullptr, float* pen_out = nullptr) {
     const char* fn = qlayers != nullptr ? "llm_decode_batch_w4" : "llm_decode_batch";
     VILA_REQUIRE(w != nullptr && cache != nullptr && st != nullptr && workspace != nullptr, "%s: NULL argument", fn);
     BTables t{};
@@ -797,7 +836,7 @@ static int decode_step_batch_impl(const VilaLlmWeights* w, const VilaLlmLayerW4*
     const BPrefix bp = px != nullptr ? BPrefix{px->prefix_slot, px->shared_len, px->uses} : BPrefix{};
     return bdecode_step(t.m, t.layers.data(), B(cache->k), B(cache->v), cache->max_ctx, cache->n_slots, st->n, st->pos, st->token, st->out_ids, st->n_out,
                         st->max_out, st->logits, workspace, workspace_bytes, S(stream), qlayers != nullptr ? t.ql.data() : nullptr, sw.sp, sw.ws,
-                        px != nullptr ? &bp : nullptr);
+                        px != nullptr ? &bp : nullptr, pen, pen_out);
 }
 // the four steps of a prefix session and their workspace sizes (two sizes, greedy and sampled, as above)
 static size_t decode_batch_prefix_ws(const VilaLlmShape* s, int n, int max_ctx, bool sample) {
@@ -849,6 +888,28 @@ extern "C" int vila_llm_decode_step_batch_w4_sample(const VilaLlmWeights* w, con
     VILA_REQUIRE(sp != nullptr, "llm_decode_batch_w4_sample: sampling parameters are NULL");
     VILA_REQUIRE(qlayers != nullptr, "llm_decode_batch_w4: NULL argument");
     return decode_step_batch_impl(w, qlayers, cache, st, workspace, workspace_bytes, sp, stream);
+}
+// The penalised batched step (penalty.hip): qlayers, prefix and sp nullable — bf16 / W4, plain / shared prefix, greedy / sampled in one entry.  One
+// workspace size for all of them: the sampled step's (plain or prefix), and behind it the processed rows [n][vocab].
+static size_t decode_batch_penalized_head(const VilaLlmShape* s, int n, int max_ctx, bool prefix) {
+    return align_up(prefix ? decode_batch_prefix_ws(s, n, max_ctx, true) : decode_batch_ws_ctx(s, n, max_ctx, true), 256);
+}
+extern "C" size_t vila_llm_decode_batch_penalized_workspace_bytes(const VilaLlmShape* s, int n, int max_ctx, int prefix) {
+    return decode_batch_penalized_head(s, n, max_ctx, prefix != 0) + align_up((size_t)(n > 0 ? n : 0) * s->vocab * 4, 256) + 256;
+}
+extern "C" int vila_llm_decode_step_batch_penalized(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers, const VilaKvCache* cache, const VilaDecodeBatch* st,
+                                                    const VilaDecodePrefix* prefix, void* workspace, size_t workspace_bytes, const VilaBatchSampling* sp,
+                                                    const VilaPenalties* pen, vila_stream_t stream) {
+    const char* fn = "llm_decode_batch_penalized";
+    VILA_REQUIRE(w != nullptr && cache != nullptr && st != nullptr && workspace != nullptr, "%s: NULL argument", fn);
+    VILA_TRY(penalties_ok(pen, w->shape.vocab, fn));
+    VILA_REQUIRE(st->n >= 1 && st->n <= 16, "%s: 1..16 sequences (got %d)", fn, st->n);
+    VILA_REQUIRE(cache->max_ctx >= 1 && cache->max_ctx <= BDEC_MAX_CTX, "%s: caches up to %d positions (got %d)", fn, BDEC_MAX_CTX, cache->max_ctx);
+    VILA_REQUIRE(workspace_bytes >= vila_llm_decode_batch_penalized_workspace_bytes(&w->shape, st->n, cache->max_ctx, prefix != nullptr),
+                 "%s: the step needs the workspace of vila_llm_decode_batch_penalized_workspace_bytes", fn);
+    const size_t head = decode_batch_penalized_head(&w->shape, st->n, cache->max_ctx, prefix != nullptr);
+    const Penalties P{pen->repetition, pen->presence, pen->frequency, pen->counts, pen->ld_counts};
+    return decode_step_batch_impl(w, qlayers, cache, st, workspace, head, sp, stream, prefix, &P, (float*)((char*)workspace + head));
 }
 // The verify step (speculative decoding, decode_batch.hip bverify_step): the layer tables are the batched step's, the state is one sequence's.
 // sp != nullptr: the sampled form, whose four parameter arrays hold ONE entry each.

@@ -437,8 +437,10 @@ size_t bdecode_prefix_workspace_bytes(int H, int F, int QS, int hd, int n, int m
 
 int bdecode_step(const BDecodeArgs& m, const BLayer* layers, bf16_t* kcache, bf16_t* vcache, int max_ctx, int n_slots, int n, int32_t* pos, int64_t* token,
                  int64_t* out_ids, int32_t* n_out, int max_out, float* logits, void* workspace, size_t workspace_bytes, hipStream_t s,
-                 const BLayerW4* qlayers, const BatchSampling* sampling, void* sampling_ws, const BPrefix* prefix) {
+                 const BLayerW4* qlayers, const BatchSampling* sampling, void* sampling_ws, const BPrefix* prefix, const Penalties* pen, float* pen_out) {
+    static_assert(PEN_PICK_SLICES == PICK_SLICES, "the penalty launch writes the pairs bdec_pick2_kernel merges");
     const int H = m.hidden, F = m.inter, hd = m.head_dim, QS = m.q_heads * hd;
+    VILA_REQUIRE(pen == nullptr || pen_out != nullptr, "batched decode: the penalised pick needs its scratch rows");
     if (prefix != nullptr) {
         VILA_REQUIRE(prefix->shared_len != nullptr && prefix->uses != nullptr, "batched decode (shared prefix): NULL argument");
         VILA_REQUIRE(n >= 1 && n < n_slots && prefix->prefix_slot >= n && prefix->prefix_slot < n_slots,
@@ -483,10 +485,20 @@ int bdecode_step(const BDecodeArgs& m, const BLayer* layers, bf16_t* kcache, bf1
     VILA_TRY(bdec_forward(m, layers, qlayers, kcache, vcache, per_layer, slot_stride, max_ctx, n, pos, token, logits, b, s, attn));
     float* pick_v = b.pick_v; int* pick_i = b.pick_i;
     // the pick: per-row sampling (sample.hip; greedy rows included, position = the draw's counter, read before it advances) or the greedy pair
+    // penalised: one launch bumps each row's count of the token it consumed (token[] still holds it), writes the processed rows to pen_out and, for the
+    // greedy pick, the pairs bdec_pick1_kernel would have written; the sampler reads pen_out in place of the logits, which stay raw
+    const float* pick_src = logits;
+    if (pen != nullptr) {
+        VILA_TRY(launch_penalize(logits, m.vocab, n, m.vocab, *pen, token, pen_out, m.vocab, PICK_SLICES, sampling != nullptr ? nullptr : pick_v,
+                                 sampling != nullptr ? nullptr : pick_i, s));
+        pick_src = pen_out;
+    }
     if (sampling != nullptr)
-        return launch_sample_batch(logits, m.vocab, n, m.vocab, *sampling, 1, pos, token, sampling_ws, nullptr, pos, out_ids, n_out, max_out, s);
-    hipLaunchKernelGGL(bdec_pick1_kernel, dim3(PICK_SLICES, n), dim3(256), 0, s, logits, m.vocab, pick_v, pick_i);
-    VILA_LAUNCH_CHECK();
+        return launch_sample_batch(pick_src, m.vocab, n, m.vocab, *sampling, 1, pos, token, sampling_ws, nullptr, pos, out_ids, n_out, max_out, s);
+    if (pen == nullptr) {
+        hipLaunchKernelGGL(bdec_pick1_kernel, dim3(PICK_SLICES, n), dim3(256), 0, s, logits, m.vocab, pick_v, pick_i);
+        VILA_LAUNCH_CHECK();
+    }
     hipLaunchKernelGGL(bdec_pick2_kernel, dim3(n), dim3(64), 0, s, pick_v, pick_i, token, pos, out_ids, n_out, max_out);
     VILA_LAUNCH_CHECK();
     return 0;

@@ -72,6 +72,14 @@ struct BatchSampling { const float* temperature; const int32_t* top_k; const flo
 size_t sample_batch_workspace_bytes(int n);
 int launch_sample_batch(const float* logits, int64_t ld_logits, int n, int vocab, const BatchSampling& sp, int sp_stride, const int32_t* counter, int64_t* out,
                         void* workspace, float* dist_out, int32_t* adv_pos, int64_t* adv_out_ids, int32_t* adv_n_out, int max_out, hipStream_t s);
+// repetition / presence / frequency penalties in front of the pick (penalty.hip): logits [n][ld] -> out [n][ld_out], counts[row][token[row]] bumped first
+// (token nullable: no bump), every parameter a device array [n]; pick_v / pick_i (nullable) [n][n_slices]: the (max, first index) pair of each slice of
+// the processed row — with PEN_PICK_SLICES slices the pairs bdec_pick2_kernel merges
+struct Penalties { const float* repetition; const float* presence; const float* frequency; uint16_t* counts; int64_t ld_counts; };
+constexpr int PEN_PICK_SLICES = 32;      // = decode_batch.hip's PICK_SLICES
+constexpr int PEN_SOLO_SLICES = 256;     // the batch-1 step: one block per CU, merged by launch_argmax_pick_advance
+int launch_penalize(const float* logits, int64_t ld, int n, int vocab, const Penalties& p, const int64_t* token, float* out, int64_t ld_out, int n_slices,
+                    float* pick_v, int* pick_i, hipStream_t s);
 // dynamic_s2 merge (s2.hip): tower output -> projector input, desc = device [n_blocks][6] {tile_base, bh, bw, i, j, single}
 int launch_s2_merge(const bf16_t* feats, bf16_t* out, const int32_t* desc, int n_blocks, int g, int C, int n_scales, const int* splits,
                     hipStream_t s);
@@ -195,7 +203,8 @@ int bprefix_attn(const bf16_t* q, int64_t ldq, const bf16_t* kcache, const bf16_
 size_t bdecode_prefix_workspace_bytes(int H, int F, int QS, int hd, int n, int max_ctx);
 int bdecode_step(const BDecodeArgs& m, const BLayer* layers, bf16_t* kcache, bf16_t* vcache, int max_ctx, int n_slots, int n, int32_t* pos, int64_t* token,
                  int64_t* out_ids, int32_t* n_out, int max_out, float* logits, void* workspace, size_t workspace_bytes, hipStream_t s,
-                 const BLayerW4* qlayers = nullptr, const BatchSampling* sampling = nullptr, void* sampling_ws = nullptr, const BPrefix* prefix = nullptr);
+                 const BLayerW4* qlayers = nullptr, const BatchSampling* sampling = nullptr, void* sampling_ws = nullptr, const BPrefix* prefix = nullptr,
+                 const Penalties* pen = nullptr, float* pen_out = nullptr);   // pen: the pick runs on the penalised rows, written to pen_out [n][vocab]
 // the verify step (greedy speculative decoding): n rows = n consecutive positions of ONE sequence in ONE slot.  Its attention (attn_decode.hip
 // bdec_attn_shared_kernel) reads the slot's K/V once for all rows; `pos` is the device scalar of the state, row i sees keys 0 .. min(pos + i, max_ctx - 1)
 int bverify_attn_slices(int max_ctx);

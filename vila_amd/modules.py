@@ -12,6 +12,8 @@ Each keeps the reference's parameter names/shapes so the 
 from __future__ import annotations
 
 import ctypes as C
+import math
+import numbers
 from types import SimpleNamespace
 from typing import Dict, List, Optional, Tuple
 
@@ -296,11 +298,21 @@ def _as_i64(u: int) -> int:
     return u - (1 << 64) if u >= (1 << 63) else u
 
 
-def _step_symbols(batch: bool, w4: bool, sampled: bool, verify: bool = False, verify_sample: bool = False, prefix: bool = False) -> Tuple[str, str]:
+def _step_symbols(batch: bool, w4: bool, sampled: bool, verify: bool = False, verify_sample: bool = False, prefix: bool = False,
+                  penalized: bool = False) -> Tuple[str, str]:
     """(step, workspace query) of one decode step variant, composed the way the C ABI names them.  verify: the greedy verify step, whatever `batch`.
     verify_sample: the sampled verify step, whatever `batch`, `sampled` and `verify` — a spelling of its own, since `verify` with `sampled` stays the
     refusal it always was (that pair names the greedy step asked to sample).  prefix: the batched step of a session with a shared prompt prefix
-    (its workspace query takes the capacity and has no `_ctx` twin)."""
+    (its workspace query takes the capacity and has no `_ctx` twin).  penalized: the step with repetition / presence / frequency penalties in front
+    of its pick — ONE entry per driver, which takes the int4 layers, the sampling parameters and (batched) the prefix descriptor as nullable arguments,
+    so w4 / sampled / prefix do not change the names."""
+    if penalized:
+        if verify or verify_sample:
+            raise ValueError("the verify steps have no penalised form")
+        if prefix and not batch:
+            raise ValueError("the shared-prefix step is a batched step")
+        return (("vila_llm_decode_step_batch_penalized", "vila_llm_decode_batch_penalized_workspace_bytes") if batch else
+                ("vila_llm_decode_step_penalized", "vila_llm_decode_penalized_workspace_bytes"))
     if prefix:
         if not batch or verify or verify_sample:
             raise ValueError("the shared-prefix step is a batched step")
@@ -571,13 +583,49 @@ class HipQwen2ForCausalLM(_HipModule):
         q4 = self._w4.mats[0]["down"].q.data_ptr() if self._w4_batched() else None
         return self.model.embed_tokens.weight.data_ptr(), _get(self, "model.layers.0.mlp.down_proj.weight").data_ptr(), q4
 
-    def _decode_session(self, cache, max_new_tokens: int, sampling=None):
+    @staticmethod
+    def _check_penalties(repetition_penalty, presence_penalty, frequency_penalty):
+        """generate()'s three penalties -> None where all are neutral (1, 0, 0 or None: today's path) or (rep, pres, freq) floats.  rep must be > 0
+        (HF RepetitionPenaltyLogitsProcessor's error); pres and freq may be any finite float, negative ones reward repeats."""
+        rep = 1.0 if repetition_penalty is None else repetition_penalty
+        if not isinstance(rep, numbers.Real) or isinstance(rep, bool) or not rep > 0:
+            raise ValueError(f"`penalty` has to be a strictly positive float, but is {rep}")
+        pres = 0.0 if presence_penalty is None else float(presence_penalty)
+        freq = 0.0 if frequency_penalty is None else float(frequency_penalty)
+        for name, v in (("repetition_penalty", float(rep)), ("presence_penalty", pres), ("frequency_penalty", freq)):
+            if not math.isfinite(v):
+                raise ValueError(f"`{name}` has to be a finite float, but is {v}")
+        return None if (float(rep), pres, freq) == (1.0, 0.0, 0.0) else (float(rep), pres, freq)
+
+    @staticmethod
+    def _penalty_state(st, n: int, vocab: int, dev) -> None:
+        """What a session with the `penalties` flag owns: the count table (uint16 bits, one row per sequence) and the three parameter arrays, neutral.
+        The values live here, on the device, never in the session key: one captured graph serves any of them."""
+        st.counts = torch.zeros((n, vocab), device=dev, dtype=torch.int16)
+        st.p_rep = torch.ones(n, device=dev, dtype=torch.float32)
+        st.p_pres = torch.zeros(n, device=dev, dtype=torch.float32)
+        st.p_freq = torch.zeros(n, device=dev, dtype=torch.float32)
+        st.pen = _lib.VilaPenalties(st.p_rep.data_ptr(), st.p_pres.data_ptr(), st.p_freq.data_ptr(), st.counts.data_ptr(), vocab)
+
+    @staticmethod
+    def _set_penalties(st, slot: int, penalties) -> None:
+        """A request starts in row `slot` of a penalised session: its (rep, pres, freq) — None = neutral — go to the device arrays and its counts to zero."""
+        rep, pres, freq = (1.0, 0.0, 0.0) if penalties is None else penalties
+        st.p_rep[slot:slot + 1].fill_(float(rep))
+        st.p_pres[slot:slot + 1].fill_(float(pres))
+        st.p_freq[slot:slot + 1].fill_(float(freq))
+        st.counts[slot].zero_()
+
+    def _decode_session(self, cache, max_new_tokens: int, sampling=None, penalties: bool = False):
         """Device-resident decode state + workspace (+ captured hipGraph) reused across generate() calls.
-        sampling: None (greedy) or (temperature, top_k, top_p, seed) — baked into the captured graph, hence part of the key."""
+        sampling: None (greedy) or (temperature, top_k, top_p, seed) — baked into the captured graph, hence part of the key.
+        penalties=True (part of the key; a session without the flag keeps the key it always had): the session steps through
+        `vila_llm_decode_step_penalized` and owns the count table and the parameter arrays (`_penalty_state`)."""
         # the seed is NOT part of the key: it lives in a device scalar the sampler reads (VilaSampling.seed_dev), so every sampled request
         # with the same (temperature, top_k, top_p) replays the same captured graph (ADVICE round 2: a fresh seed per call used to drop
         # the graph, the workspace and the weight struct on every sampled request)
         key = (cache.k.data_ptr(), max_new_tokens, *self._weights_key()[:2], None if sampling is None else tuple(sampling[:3]))   # (no int4 pointer: as ever)
+        key += (True,) if penalties else ()
         if self._decode is not None and self._decode.key == key:
             if sampling is not None:
                 self._decode.seed.fill_(_as_i64(sampling[3]))
@@ -592,6 +640,7 @@ class HipQwen2ForCausalLM(_HipModule):
         w = self._struct()
         st = SimpleNamespace(key=key, cache=cache)
         st.sampling = None
+        st.pen = None
         # the session outlives the call that creates it: built outside inference mode even when the first generate() runs under
         # torch.inference_mode() (llava_arch.py:823), or a later no_grad caller could not update `pos` / `token` in place
         with torch.inference_mode(False):
@@ -600,8 +649,11 @@ class HipQwen2ForCausalLM(_HipModule):
             st.out_ids = torch.zeros(max(max_new_tokens, 1), device=dev, dtype=torch.int64)
             st.n_out = torch.zeros(1, device=dev, dtype=torch.int32)
             st.logits = torch.zeros(self.lcfg.vocab_size, device=dev, dtype=torch.float32)
-            st.ws = torch.empty((lib.vila_llm_decode_workspace_bytes(C.byref(w.shape), cache.max_ctx),), device=dev, dtype=torch.uint8)
+            ws_bytes = getattr(lib, _step_symbols(False, False, False, penalized=bool(penalties))[1])
+            st.ws = torch.empty((ws_bytes(C.byref(w.shape), cache.max_ctx),), device=dev, dtype=torch.uint8)
             st.seed = torch.zeros(1, device=dev, dtype=torch.int64)          # the sampler's seed (bit pattern of a uint64)
+            if penalties:
+                self._penalty_state(st, 1, self.lcfg.vocab_size, dev)
         if sampling is not None:
             st.seed.fill_(_as_i64(sampling[3]))
             st.sampling = _lib.VilaSampling(float(sampling[0]), int(sampling[1]), float(sampling[2]), int(sampling[3]) & 0xFFFFFFFFFFFFFFFF,
@@ -672,6 +724,14 @@ class HipQwen2ForCausalLM(_HipModule):
         """One decode step on the current stream.  The variant is looked up at call time (`_step_symbols`): a caller may hold a session
         across quantize_w4.  w4: the W4Weights whose int4 layers the step reads, or None; sp: the sampling struct, or None for the greedy pick."""
         px = getattr(st, "px", None)                                    # a session with a shared prompt prefix: its descriptor follows the state
+        pen = getattr(st, "pen", None)                                  # a session with the penalties flag: the one entry of its driver, NULLs for what is off
+        if pen is not None:
+            name, _ = _step_symbols(batch, w4 is not None, sp is not None, verify, verify_sample, prefix=px is not None, penalized=True)
+            ref = lambda s: None if s is None else C.byref(s)
+            args = ([C.byref(self._struct()), w4.ptr if w4 is not None else None, C.byref(cache.c), C.byref(st.c)] + ([ref(px)] if batch else []) +
+                    [st.ws.data_ptr(), st.ws.numel(), ref(sp), C.byref(pen), ops._stream()])
+            check(getattr(_lib.load(), name)(*args), name)
+            return
         name, _ = _step_symbols(batch, w4 is not None, sp is not None, verify, verify_sample, prefix=px is not None)
         args = ([C.byref(self._struct())] + ([w4.ptr] if w4 is not None else []) + [C.byref(cache.c), C.byref(st.c)] +
                 ([C.byref(px)] if px is not None else []) + [st.ws.data_ptr(), st.ws.numel()])
@@ -726,20 +786,23 @@ class HipQwen2ForCausalLM(_HipModule):
                 return False
         return True
 
-    def _batch_session(self, n: int, max_ctx: int, max_new_tokens: int, sampling: bool = False, shared_prefix: bool = False):
+    def _batch_session(self, n: int, max_ctx: int, max_new_tokens: int, sampling: bool = False, shared_prefix: bool = False, penalties: bool = False):
         """sampling=True: the session owns per-row sampling parameters on the device (temperature / top_k / top_p / seed, every row greedy
         until `_batch_set_sampling` says otherwise) and steps through the `_sample` entry points: one captured graph for any mix of rows.
         shared_prefix=True: the cache has one slot more, the prefix slot (index n), and the session owns the shared length and the rows' flags on
-        the device; it steps through the `_prefix` entry points."""
+        the device; it steps through the `_prefix` entry points.
+        penalties=True (in the key only when set, so every other session keeps its key): the session steps through
+        `vila_llm_decode_step_batch_penalized` and owns a count row and (rep, pres, freq) per row (`_penalty_state`), every row neutral until
+        `_set_penalties` says otherwise."""
         w4 = self._w4_batched()
         if not w4:
             self._require_bf16("the batched decode")
-        key = (n, max_ctx, max_new_tokens, bool(sampling), *self._weights_key()) + ((True,) if shared_prefix else ())
+        key = (n, max_ctx, max_new_tokens, bool(sampling), *self._weights_key()) + ((True,) if shared_prefix else ()) + (("penalties",) if penalties else ())
         if self._bdecode is not None and self._bdecode.key == key:
             return self._bdecode
         self._drop_session("_bdecode")
         dev, lib, w = self.device, _lib.load(), self._struct()
-        st = SimpleNamespace(key=key, graph=None, sampling=bool(sampling), sp=None, px=None, shared_prefix=bool(shared_prefix))
+        st = SimpleNamespace(key=key, graph=None, sampling=bool(sampling), sp=None, px=None, shared_prefix=bool(shared_prefix), pen=None)
         st.attn_slices = int(lib.vila_decode_batch_slices(int(max_ctx)))     # walking-attention slices the steps of this session launch (0: short form)
         with torch.inference_mode(False):
             st.cache = self.new_cache(max_ctx, n_slots=n + 1 if shared_prefix else n)
@@ -754,14 +817,17 @@ class HipQwen2ForCausalLM(_HipModule):
             st.out_ids = torch.zeros((n, max(max_new_tokens, 1)), device=dev, dtype=torch.int64)
             st.n_out = torch.zeros(n, device=dev, dtype=torch.int32)
             st.logits = torch.zeros((n, self.lcfg.vocab_size), device=dev, dtype=torch.float32)
-            ws_bytes = getattr(lib, _step_symbols(True, w4, bool(sampling), prefix=bool(shared_prefix))[1])
+            ws_bytes = getattr(lib, _step_symbols(True, w4, bool(sampling), prefix=bool(shared_prefix), penalized=bool(penalties))[1])
+            if penalties:
+                self._penalty_state(st, n, self.lcfg.vocab_size, dev)
             if sampling:
                 st.s_temperature = torch.zeros(n, device=dev, dtype=torch.float32)          # 0 = greedy row
                 st.s_top_k = torch.full((n,), 50, device=dev, dtype=torch.int32)
                 st.s_top_p = torch.ones(n, device=dev, dtype=torch.float32)
                 st.s_seed = torch.zeros(n, device=dev, dtype=torch.int64)                   # bit patterns of uint64 seeds
                 st.sp = _lib.VilaBatchSampling(st.s_temperature.data_ptr(), st.s_top_k.data_ptr(), st.s_top_p.data_ptr(), st.s_seed.data_ptr())
-            st.ws = torch.empty((ws_bytes(C.byref(w.shape), n, int(max_ctx)),), device=dev, dtype=torch.uint8)    # (<= 2048 positions: the size it always had)
+            ws_args = (int(bool(shared_prefix)),) if penalties else ()
+            st.ws = torch.empty((ws_bytes(C.byref(w.shape), n, int(max_ctx), *ws_args),), device=dev, dtype=torch.uint8)    # (<= 2048 positions: the size it always had)
         st.c = _lib.VilaDecodeBatch(n, st.pos.data_ptr(), st.token.data_ptr(), st.out_ids.data_ptr(), st.n_out.data_ptr(), max(max_new_tokens, 1),
                                     st.logits.data_ptr())
         st.stream = torch.cuda.Stream(device=dev)
@@ -799,13 +865,16 @@ class HipQwen2ForCausalLM(_HipModule):
         st.s_top_p[slot:slot + 1].fill_(float(p))
         st.s_seed[slot:slot + 1].fill_(_as_i64(seed))
 
-    def batch_open(self, n_slots: int, max_ctx: int = 2048, max_new_tokens: int = 1024, sampling: bool = False, shared_prefix: bool = False):
+    def batch_open(self, n_slots: int, max_ctx: int = 2048, max_new_tokens: int = 1024, sampling: bool = False, shared_prefix: bool = False,
+                   penalties: bool = False):
         """Open (or re-use) the batched-decode session of `n_slots` rows with its captured step.  sampling=False: the greedy step.  sampling=True:
         the step picks per row from device-resident parameters, so the ONE captured graph serves any mix of greedy and sampled rows
         (`batch_admit(..., sampling=)`); the flag is part of the session key.
         shared_prefix=True (part of the key as well): the session may hold one shared prompt prefix in an extra cache slot (`batch_set_prefix`), and
         rows admitted with `batch_admit(..., share=True)` read its K/V instead of a copy of their own: the step's attention reads the prefix once for
-        all of them.  The ONE captured graph serves any shared length and any mix of sharing and ordinary rows.  GQA groups of 1, 2, 4, 7 or 8."""
+        all of them.  The ONE captured graph serves any shared length and any mix of sharing and ordinary rows.  GQA groups of 1, 2, 4, 7 or 8.
+        penalties=True (part of the key as well): rows may carry repetition / presence / frequency penalties (`batch_admit(..., penalties=)`); the
+        values and every row's token counts live on the device, so the ONE captured graph serves any mix of penalised and plain rows."""
         if not self._w4_batched():
             self._require_bf16("batch_open")
         long_ok = (max_ctx <= 2048 and not shared_prefix) or self._long_batch_group_ok()
@@ -813,10 +882,14 @@ class HipQwen2ForCausalLM(_HipModule):
                 (self._w4_batched() or self._qkv_fused())):
             raise ValueError("batch_open: the batched decode step serves 1..16 rows of a head-dim-128 model (bf16, or quantize_w4(batch_decode=True)) "
                              f"with caches <= {self.BATCH_MAX_CTX} positions (beyond 2048: GQA groups of 1, 2, 4, 7 or 8 query heads)")
-        st = self._batch_session(max(n_slots, 2), max_ctx, max_new_tokens, sampling, shared_prefix)
+        st = self._batch_session(max(n_slots, 2), max_ctx, max_new_tokens, sampling, shared_prefix, penalties)
         def reset():
             st.pos.zero_(); st.n_out.zero_(); st.token.zero_()
+            if getattr(st, "pen", None) is not None:
+                st.counts.zero_()                                      # (the warm-up step outside capture bumps one count per row)
         reset()
+        if getattr(st, "pen", None) is not None:
+            st.p_rep.fill_(1.0); st.p_pres.zero_(); st.p_freq.zero_()  # every row starts neutral
         if st.shared_prefix:
             self._prefix_reset(st)                                     # no prefix, every row ordinary
         if st.sampling:
@@ -884,7 +957,7 @@ class HipQwen2ForCausalLM(_HipModule):
                 c[:, slot, :, S:P].copy_(c[:, st.prefix_slot, :, S:P])
         return st.staged_logits
 
-    def batch_admit(self, st, slot: int, embeds: torch.Tensor, sampling=None, share: bool = False, first_row: int = 0) -> int:
+    def batch_admit(self, st, slot: int, embeds: torch.Tensor, sampling=None, share: bool = False, first_row: int = 0, penalties=None) -> int:
         """Prefill ONE sequence [P, H] into KV slot `slot` of the open batch and make the row live: position P, first token = argmax of the
         prefill's last row (returned), output counter 0.  sampling = (temperature, top_k in 1..64, top_p, seed), sampling sessions only: the
         row samples — its parameters go to the device arrays, its first token is drawn from the prefill's last row with counter P - 1 (as the
@@ -893,7 +966,14 @@ class HipQwen2ForCausalLM(_HipModule):
         (S = the session's shared length) are the session's prefix (the caller's word: they are not compared) and P >= S.  Only the tail S .. P - 1 is prefilled, onto the prefix, and
         copied to the row's own slot; the row's flag is set, so its steps read keys 0 .. S - 1 from the prefix slot.
         first_row (share=True only, 0 <= first_row <= S): embeds holds the prompt's rows first_row .. P - 1 only — rows below S are never read, so a
-        caller that has no embeddings of the prefix (a server that skipped the tower) passes the rest."""
+        caller that has no embeddings of the prefix (a server that skipped the tower) passes the rest.
+        penalties = (repetition, presence, frequency), sessions opened with penalties=True only: the row's picks run on the penalised logits.  The
+        row's counts start from zero whatever the slot held before; the first token, chosen from the prefill, is never penalised (nothing has been
+        generated yet).  None = a neutral row."""
+        if penalties is not None:
+            penalties = self._check_penalties(*penalties)
+            if penalties is not None and getattr(st, "pen", None) is None:
+                raise ValueError("batch_admit: a penalised row needs a session opened with batch_open(penalties=True)")
         if sampling is not None:
             if not st.sampling:
                 raise ValueError("batch_admit: a sampled row needs a session opened with batch_open(sampling=True)")
@@ -930,6 +1010,8 @@ class HipQwen2ForCausalLM(_HipModule):
                  ops.sample(logits, sampling[0], sampling[1], sampling[2], sampling[3], counter=last))
         if st.sampling:
             self._batch_set_sampling(st, slot, sampling)
+        if getattr(st, "pen", None) is not None:
+            self._set_penalties(st, slot, penalties)
         st.pos[slot:slot + 1].fill_(P)
         st.n_out[slot:slot + 1].zero_()
         st.token[slot:slot + 1].copy_(first)
@@ -955,21 +1037,24 @@ class HipQwen2ForCausalLM(_HipModule):
                 st.uses.index_fill_(0, idx, 0)                         # ... and an ordinary one
                 st.sharers.difference_update(int(s) for s in slots)
 
-    def _generate_shared(self, inputs_embeds, n: int, max_new_tokens, eos_token_id, pad_token_id, use_graph: bool, return_logits: bool, sampling):
+    def _generate_shared(self, inputs_embeds, n: int, max_new_tokens, eos_token_id, pad_token_id, use_graph: bool, return_logits: bool, sampling,
+                         penalties=None):
         """generate(num_return_sequences=n): ONE prefill of the prompt into the prefix slot of a shared-prefix sampling session, n sharing rows that
         differ in their seeds.  Returns [n, n_new] like `_generate_batch`; return_logits: (ids [n, n_new], logits [n_new, n, V] fp32), eager steps.
         A prompt below 256 positions has no whole chunk to share: nothing goes into the prefix slot and the n rows are ordinary rows of the same
-        session, each prefilled on its own (return_logits is refused for it by the caller)."""
+        session, each prefilled on its own (return_logits is refused for it by the caller).
+        penalties: None, or the request's (rep, pres, freq): the session is opened with the penalties flag and every row carries them, with counts of
+        its own."""
         x = inputs_embeds[0]
         P, dev = int(x.shape[0]), x.device
         max_ctx = ((P + max_new_tokens + 255) // 256) * 256
-        st = self.batch_open(n, max_ctx, max_new_tokens, sampling=True, shared_prefix=True)
+        st = self.batch_open(n, max_ctx, max_new_tokens, sampling=True, shared_prefix=True, penalties=penalties is not None)
         self.batch_release(st, range(st.pos.numel()))
         if P < 256:
-            first_h = [self.batch_admit(st, j, x, sampling=sampling[j]) for j in range(n)]
+            first_h = [self.batch_admit(st, j, x, sampling=sampling[j], penalties=penalties) for j in range(n)]
         else:
             self.batch_set_prefix(st, x)
-            first_h = [self.batch_admit(st, j, x, sampling=sampling[j], share=True) for j in range(n)]
+            first_h = [self.batch_admit(st, j, x, sampling=sampling[j], share=True, penalties=penalties) for j in range(n)]
         first = torch.tensor(first_h, device=dev, dtype=torch.int64)
         eos_set = _eos_set(eos_token_id, self.lcfg.eos_token_id)
         n_steps = max_new_tokens - 1
@@ -1006,14 +1091,17 @@ class HipQwen2ForCausalLM(_HipModule):
             self.batch_release(st, range(st.pos.numel()))
 
     def _generate_batch(self, inputs_embeds, attention_mask, max_new_tokens, eos_token_id, pad_token_id, use_graph: bool = True,
-                        forced_ids: Optional[torch.Tensor] = None, return_logits: bool = False, sampling=None):
+                        forced_ids: Optional[torch.Tensor] = None, return_logits: bool = False, sampling=None, penalties=None):
         """The padded batch as ONE packed prefill (every row into its own KV-cache slot) + batched decode steps: the weights are streamed
         once per step for all rows.  Returns [B, n_new] right-padded with pad_token_id behind each row's EOS, like HF.
         forced_ids [B, n_new] / return_logits: teacher forcing for the parity tests (eager launches; the ids fed after step t are
         forced_ids[:, t]); returns (argmax ids [B, n_new], logits [n_new, B, V] fp32).
         sampling: None (greedy session) or one entry per row, (temperature, top_k in 1..64, top_p, seed) or None for a greedy row: the batch
         runs in a sampling session (`_batch_session(sampling=True)`), row b draws its first token with counter len_b - 1 and every step with
-        the position of the token it consumes; under teacher forcing the returned ids are the ones each step CHOSE."""
+        the position of the token it consumes; under teacher forcing the returned ids are the ones each step CHOSE.
+        penalties: None, or (rep, pres, freq) for every row (or one such entry / None per row): the batch runs in a session with the penalties flag,
+        whose steps count the tokens they consume and pick from the penalised logits; the returned logits stay raw, the returned ids are the ones
+        each step chose."""
         ops._need(inputs_embeds, dtype=None, name="inputs_embeds")
         if sampling is not None:
             sampling = [None if sp is None else self._check_batch_sampling(sp, "generate(batch_sample=True)") for sp in sampling]
@@ -1030,7 +1118,11 @@ class HipQwen2ForCausalLM(_HipModule):
         seq = torch.cat([torch.full((n,), b, dtype=torch.int32) for b, n in enumerate(lens)]).to(dev)
         last = torch.tensor([c - 1 for c in cu_h[1:]], device=dev, dtype=torch.int32)
         max_ctx = ((max(lens) + max_new_tokens + 255) // 256) * 256
-        st = self._batch_session(Bn, max_ctx, max_new_tokens, sampling is not None)
+        st = self._batch_session(Bn, max_ctx, max_new_tokens, sampling is not None, penalties=penalties is not None)
+        if penalties is not None:
+            rows_pen = list(penalties) if isinstance(penalties, list) else [penalties] * Bn
+            for b in range(Bn):
+                self._set_penalties(st, b, rows_pen[b])
         r = self.prefill_packed(packed, pos, cu, max(lens), cache=st.cache, seq_of_tok=seq, last_rows=last)
         if sampling is None:
             first = torch.cat([ops.argmax(r.last_logits[b]) for b in range(Bn)])
@@ -1054,7 +1146,7 @@ class HipQwen2ForCausalLM(_HipModule):
                 for t in range(n_steps):
                     self._batch_step(st)
                     step_logits.append(st.logits[:Bn].float().clone())
-                    ids.append(torch.cat([ops.argmax(st.logits[b]) for b in range(Bn)]) if sampling is None else st.token[:Bn].clone())
+                    ids.append(torch.cat([ops.argmax(st.logits[b]) for b in range(Bn)]) if sampling is None and getattr(st, "pen", None) is None else st.token[:Bn].clone())
                     if forced_ids is not None and t + 1 < forced_ids.shape[1]:
                         st.token.copy_(forced_ids[:, t + 1].to(dev))
             st.stream.synchronize()
@@ -1062,6 +1154,8 @@ class HipQwen2ForCausalLM(_HipModule):
         if use_graph and st.graph is None and n_steps > 0:
             def restore():
                 st.pos.copy_(torch.tensor(lens, dtype=torch.int32)); st.n_out.zero_(); st.token.copy_(first)
+                if getattr(st, "pen", None) is not None:
+                    st.counts.zero_()                              # the warm-up step outside capture bumped one count per row
             _capture(st, lambda: self._batch_step(st), restore)
         first_h = first.tolist()
         done_rows = [t in eos_set for t in first_h]
@@ -1095,7 +1189,8 @@ class HipQwen2ForCausalLM(_HipModule):
                  max_length: Optional[int] = None, streamer=None, batch_sample: Optional[bool] = None,
                  prompt_lookup_num_tokens: Optional[int] = None, max_matching_ngram_size: Optional[int] = None,
                  prompt_ids: Optional[torch.Tensor] = None, draft_ids: Optional[torch.Tensor] = None, past_len: Optional[int] = None,
-                 prefill_chunk: Optional[int] = None, spec_sample: Optional[bool] = None, num_return_sequences: Optional[int] = None, **kw):
+                 prefill_chunk: Optional[int] = None, spec_sample: Optional[bool] = None, num_return_sequences: Optional[int] = None,
+                 repetition_penalty: Optional[float] = None, presence_penalty: Optional[float] = None, frequency_penalty: Optional[float] = None, **kw):
         """`llm.generate(inputs_embeds=, attention_mask=, **generation_kwargs)` as called at llava_arch.py:833 (HF semantics: returns ONLY the
         new tokens, [B, n_new]).  Greedy search or sampling (do_sample: temperature / top_k / top_p, HF order, on the device); explicit
         keyword arguments override `generation_config` (HF GenerationConfig-like: do_sample, temperature, top_k, top_p, max_new_tokens,
@@ -1128,16 +1223,29 @@ class HipQwen2ForCausalLM(_HipModule):
         (a previous generate on it), inputs_embeds holds only the NEW tokens, which are appended at P (`prefill_append`), and decoding goes on
         from P + S.  After n returned tokens the cache holds P + S + n - 1 valid positions: the last token was never fed.
         prefill_chunk=C (batch size 1): a prompt longer than C is fed as the usual prefill of its first C tokens and `prefill_append` calls of
-        at most C, logits only from the last, so the prefill workspace is that of C tokens.  Both default to None: the one-shot path."""
+        at most C, logits only from the last, so the prefill workspace is that of C tokens.  Both default to None: the one-shot path.
+        repetition_penalty (HF's name and rule, also read from generation_config; > 0), presence_penalty, frequency_penalty (OpenAI's definitions,
+        also read from generation_config; any finite float, negative ones reward repeats): applied on the device in front of the pick, greedy or
+        sampled, solo or batched, bf16 or W4 (`vila_llm_decode_step[_batch]_penalized`).  They count the tokens this request has GENERATED: the
+        prompt, given as embeddings, is not counted (HF's input_ids is empty then), so the first token is never penalised.  return_logits stays
+        the raw model logits.  Neutral values (1, 0, 0 or None) take the unpenalised path, sessions and graphs untouched; the values never enter a
+        session key, so one captured graph serves every penalised request.  Not served with prompt_lookup_num_tokens / draft_ids / spec_sample."""
         self._check_append_args(inputs_embeds, cache, past_len, prefill_chunk)
+        gc = generation_config
+        pick = lambda v, name, default: v if v is not None else (getattr(gc, name, None) if gc is not None and getattr(gc, name, None) is not None else default)
+        penalties = self._check_penalties(pick(repetition_penalty, "repetition_penalty", None), pick(presence_penalty, "presence_penalty", None),
+                                          pick(frequency_penalty, "frequency_penalty", None))
+        if penalties is not None and (pick(prompt_lookup_num_tokens, "prompt_lookup_num_tokens", None) is not None or draft_ids is not None or
+                                      bool(pick(spec_sample, "spec_sample", False))):
+            raise ValueError("repetition_penalty / presence_penalty / frequency_penalty are not served with speculative decoding "
+                             "(prompt_lookup_num_tokens, draft_ids, spec_sample): the verify step has no penalised form")
         if num_return_sequences is not None and int(num_return_sequences) != 1:
             return self._generate_return_sequences(inputs_embeds, attention_mask, int(num_return_sequences), max_new_tokens, eos_token_id, do_sample,
                                                    temperature, top_k, top_p, seed, pad_token_id, generation_config, use_graph, return_logits,
-                                                   forced_ids, cache, streamer, batch_sample, prompt_lookup_num_tokens, draft_ids, past_len, prefill_chunk)
+                                                   forced_ids, cache, streamer, batch_sample, prompt_lookup_num_tokens, draft_ids, past_len, prefill_chunk,
+                                                   penalties)
         if streamer is not None and inputs_embeds.shape[0] > 1:
             raise ValueError("TextStreamer only supports batch size 1")          # transformers/generation/streamers.py, TextStreamer.put
-        gc = generation_config
-        pick = lambda v, name, default: v if v is not None else (getattr(gc, name, None) if gc is not None and getattr(gc, name, None) is not None else default)
         do_sample = bool(pick(do_sample, "do_sample", False))
         temperature, top_k, top_p = float(pick(temperature, "temperature", 1.0)), int(pick(top_k, "top_k", 50)), float(pick(top_p, "top_p", 1.0))
         max_new_tokens = int(pick(max_new_tokens, "max_new_tokens", 32))
@@ -1175,21 +1283,28 @@ class HipQwen2ForCausalLM(_HipModule):
             raise ValueError(f"`temperature` (={temperature}) has to be a strictly positive float, otherwise your next token scores will be invalid.")
         if do_sample and top_k < 0:
             raise ValueError(f"`top_k` has to be a non-negative integer, but is {top_k}")       # (0 = no top-k filter, like HF)
-        if inputs_embeds.shape[0] > 1 and self._can_batch_decode(inputs_embeds, attention_mask, max_new_tokens, do_sample, forced_ids, return_logits, cache,
+        # (a penalised greedy batch is teacher-forced and returns its logits through the batched step as well: its ids are the step's own picks)
+        pen_kw = {} if penalties is None else dict(penalties=penalties)
+        if inputs_embeds.shape[0] > 1 and self._can_batch_decode(inputs_embeds, attention_mask, max_new_tokens, do_sample,
+                                                                 forced_ids if penalties is None else None, return_logits and penalties is None, cache,
                                                                  batch_sample, top_k):
             if not do_sample:
-                return self._generate_batch(inputs_embeds, attention_mask, max_new_tokens, eos_token_id, pad_token_id, use_graph)
+                if penalties is None:
+                    return self._generate_batch(inputs_embeds, attention_mask, max_new_tokens, eos_token_id, pad_token_id, use_graph)
+                return self._generate_batch(inputs_embeds, attention_mask, max_new_tokens, eos_token_id, pad_token_id, use_graph, forced_ids,
+                                            return_logits, **pen_kw)
             if seed is None:
                 seed = self._fresh_seed()
             rows = [(temperature, top_k, top_p, (int(seed) + b) & 0xFFFFFFFFFFFFFFFF) for b in range(inputs_embeds.shape[0])]
             return self._generate_batch(inputs_embeds, attention_mask, max_new_tokens, eos_token_id, pad_token_id, use_graph, forced_ids,
-                                        return_logits, sampling=rows)
+                                        return_logits, sampling=rows, **pen_kw)
         if inputs_embeds.shape[0] > 1:
             rows = []
+            row_pen = {} if penalties is None else dict(repetition_penalty=penalties[0], presence_penalty=penalties[1], frequency_penalty=penalties[2])
             for b in range(inputs_embeds.shape[0]):
                 m = None if attention_mask is None else attention_mask[b:b + 1]
                 rows.append(self.generate(inputs_embeds[b:b + 1], m, max_new_tokens, eos_token_id, do_sample, temperature, top_k, top_p,
-                                          None if seed is None else seed + b, pad_token_id, None, use_graph, False, None, cache, max_length)[0])
+                                          None if seed is None else seed + b, pad_token_id, None, use_graph, False, None, cache, max_length, **row_pen)[0])
             return finish_rows([r.tolist() for r in rows], _eos_set(eos_token_id, self.lcfg.eos_token_id),
                                _pad_id(pad_token_id, eos_token_id, self.lcfg.eos_token_id), rows[0].device)
         sampling = None
@@ -1198,11 +1313,11 @@ class HipQwen2ForCausalLM(_HipModule):
                 seed = self._fresh_seed()
             sampling = (temperature, top_k, top_p, int(seed))
         return self._generate_solo(inputs_embeds, attention_mask, max_new_tokens, eos_token_id, sampling, use_graph, return_logits, forced_ids, cache,
-                                   streamer, past_len, prefill_chunk)
+                                   streamer, past_len, prefill_chunk, **pen_kw)
 
     def _generate_return_sequences(self, inputs_embeds, attention_mask, n, max_new_tokens, eos_token_id, do_sample, temperature, top_k, top_p, seed,
                                    pad_token_id, gc, use_graph, return_logits, forced_ids, cache, streamer, batch_sample, k_spec, draft_ids, past_len,
-                                   prefill_chunk):
+                                   prefill_chunk, penalties=None):
         """generate(num_return_sequences=n): what is served, refused with a ValueError that says so otherwise."""
         pick = lambda v, name, default: v if v is not None else (getattr(gc, name, None) if gc is not None and getattr(gc, name, None) is not None else default)
         what = "num_return_sequences: n samples of ONE prompt over its shared K/V"
@@ -1231,7 +1346,7 @@ class HipQwen2ForCausalLM(_HipModule):
         rows = [self._check_batch_sampling((temperature, top_k, top_p, (int(seed) + j) & 0xFFFFFFFFFFFFFFFF), "generate(num_return_sequences=)")
                 for j in range(n)]
         return self._generate_shared(inputs_embeds, n, max_new_tokens, pick(eos_token_id, "eos_token_id", None), pick(pad_token_id, "pad_token_id", None),
-                                     use_graph, return_logits, rows)
+                                     use_graph, return_logits, rows, **({} if penalties is None else dict(penalties=penalties)))
 
     @staticmethod
     def _check_append_args(inputs_embeds, cache, past_len, prefill_chunk) -> None:
@@ -1291,13 +1406,17 @@ class HipQwen2ForCausalLM(_HipModule):
         return S, cache, self.prefill_packed(x.to(self.dtype), pos, None, S, cache=cache, last_rows=last), last
 
     def _generate_solo(self, inputs_embeds, attention_mask, max_new_tokens, eos_token_id, sampling, use_graph, return_logits, forced_ids, cache,
-                       streamer, past_len=None, prefill_chunk=None):
+                       streamer, past_len=None, prefill_chunk=None, penalties=None):
         """generate() for one sequence: prefill, then the batch-1 step (one hipGraph replay per token, or step by step under `use_graph=False`,
-        `return_logits` or `forced_ids`).  sampling: None (greedy) or (temperature, top_k, top_p, seed)."""
+        `return_logits` or `forced_ids`).  sampling: None (greedy) or (temperature, top_k, top_p, seed).
+        penalties: None, or (rep, pres, freq): the session carries the penalties flag, its counts start from zero here (a request starts), and the
+        ids returned with return_logits are the ones each step chose from the penalised logits."""
         S, cache, r, last = self._prefill_one(inputs_embeds, attention_mask, max_new_tokens, cache, None, past_len, prefill_chunk)
         dev = inputs_embeds.device
         eos_set = _eos_set(eos_token_id, self.lcfg.eos_token_id)
-        st = self._decode_session(cache, max_new_tokens, sampling)
+        st = self._decode_session(cache, max_new_tokens, sampling, **({} if penalties is None else dict(penalties=True)))
+        if penalties is not None:
+            self._set_penalties(st, 0, penalties)
         # the sampler mixes a device counter into its random number: the decode steps use the position of the token they consume
         # (S, S+1, ...); the first token, drawn from the prefill's logits, uses S - 1
         first = ops.argmax(r.last_logits[0]) if sampling is None else ops.sample(r.last_logits[0], *sampling, counter=last)
@@ -1310,6 +1429,8 @@ class HipQwen2ForCausalLM(_HipModule):
         if not eager and st.graph is None:
             def restore():
                 st.pos.fill_(S); st.n_out.zero_(); st.token.copy_(first)
+                if penalties is not None:
+                    st.counts.zero_()                              # the warm-up step outside capture bumped the first token's count
             _capture(st, lambda: self.decode_step(cache, st), restore)
         n_steps = max_new_tokens - 1
         if eager:
@@ -1317,7 +1438,7 @@ class HipQwen2ForCausalLM(_HipModule):
                 self.decode_step(cache, st)
                 if return_logits:
                     step_logits.append(st.logits.clone())
-                    ids.append(ops.argmax(st.logits) if sampling is None else st.token.clone())
+                    ids.append(ops.argmax(st.logits) if sampling is None and penalties is None else st.token.clone())
                 if forced_ids is not None and t + 1 < forced_ids.numel():
                     st.token.copy_(forced_ids[t + 1:t + 2].to(dev))
             if not return_logits:

@@ -270,6 +270,39 @@ def sample_batch(logits: torch.Tensor, temperature: torch.Tensor, top_k: torch.T
     return out
 
 
+def penalize(logits: torch.Tensor, counts: torch.Tensor, repetition: torch.Tensor, presence: torch.Tensor, frequency: torch.Tensor,
+             token: Optional[torch.Tensor] = None, return_pick: bool = False):
+    """Repetition / presence / frequency penalties on logits [n, V] fp32 (rows may be strided): the launch the penalised decode steps run between the
+    logits and the pick.  counts [n, >= V] int16 or uint16 (the bits of uint16 counters; rows may be strided) = how often each row's request has
+    generated each id; token [n] i64 (optional): counts[r, token[r]] is bumped first (saturating at 65535; an id outside 0 .. V - 1 bumps nothing).
+    repetition / presence / frequency: DEVICE tensors [n] f32.  Where c = counts[r, i] > 0: y = x * rep if x < 0 else x / rep; then
+    y -= frequency * c; then y -= presence where c > 0 — each one rounded fp32 operation, bit for bit the torch expression on the CPU.
+    -> y [n, V] f32 (and, on request, the greedy pick's first stage: (values [n, S], indices [n, S] i32), the maximum of each of the S slices of a
+    processed row and the first index that holds it)."""
+    _need(logits, dtype=torch.float32, name="logits")
+    if logits.dim() != 2 or logits.stride(1) != 1:
+        raise ValueError("penalize: logits must be [n, vocab] with contiguous rows")
+    n, V = logits.shape
+    _need(counts, dtype=None, name="counts")
+    if counts.dtype not in (torch.int16, torch.uint16) or counts.dim() != 2 or counts.shape[0] != n or counts.shape[1] < V or counts.stride(1) != 1:
+        raise ValueError(f"penalize: counts must be [{n}, >= {V}] int16 / uint16 with contiguous rows")
+    for name, t, dt in (("repetition", repetition, torch.float32), ("presence", presence, torch.float32), ("frequency", frequency, torch.float32)) + \
+            ((("token", token, torch.int64),) if token is not None else ()):
+        _need(t, dtype=dt, name=name)
+        if t.numel() != n or not t.is_contiguous():
+            raise ValueError(f"penalize: {name} must be a contiguous tensor of {n} entries")
+    import ctypes as C
+    lib = _lib.load()
+    out = torch.empty((n, V), device=logits.device, dtype=torch.float32)
+    S = int(lib.vila_logits_penalize_slices())
+    pv = torch.empty((n, S), device=logits.device, dtype=torch.float32) if return_pick else None
+    pi = torch.empty((n, S), device=logits.device, dtype=torch.int32) if return_pick else None
+    pen = _lib.VilaPenalties(repetition.data_ptr(), presence.data_ptr(), frequency.data_ptr(), counts.data_ptr(), counts.stride(0))
+    check(lib.vila_logits_penalize_f32(logits.data_ptr(), logits.stride(0), n, V, C.byref(pen), _p(token), out.data_ptr(), out.stride(0), _p(pv), _p(pi),
+                                       _stream()), "penalize")
+    return (out, pv, pi) if return_pick else out
+
+
 def attn_decode_batch(q: torch.Tensor, kcache: torch.Tensor, vcache: torch.Tensor, pos: torch.Tensor, scale: Optional[float] = None) -> torch.Tensor:
     """The batched decode step's attention on its own: q [n, q_heads, 128] bf16 (rows may be strided), kcache / vcache ONE layer's
     [slots >= n, kv_heads, max_ctx, 128] bf16 (contiguous), pos [n] i32 — row i attends keys 0 .. pos[i] of slot i.  max_ctx up to 32768, GQA

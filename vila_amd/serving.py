@@ -388,16 +388,32 @@ def _eos_of(tokenizer, eos_token_id=None):
     return getattr(tokenizer, "eos_token_id", None)
 
 
+PENALTY_NEUTRAL = dict(repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0)
+
+
+def _penalties_of(gen) -> Dict[str, float]:
+    """The non-neutral penalties among a request's keywords, as keywords of `llm.generate`: {} for a request that asks for none (None or the neutral
+    1 / 0 / 0), which is then served exactly as a request without the fields."""
+    return {k: float(gen[k]) for k, v in PENALTY_NEUTRAL.items() if gen.get(k) is not None and float(gen[k]) != v}
+
+
 def generate_content(model, tokenizer, prompt: Union[str, Sequence[Any]], max_new_tokens: int = 128, system: Optional[str] = None,
                      eos_token_id=None, device: Optional[str] = None, temperature: float = 0.0, top_p: float = 1.0, top_k: int = 50,
-                     seed: Optional[int] = None, streamer=None, prompt_lookup_num_tokens: Optional[int] = None, spec_sample: bool = False) -> str:
+                     seed: Optional[int] = None, streamer=None, prompt_lookup_num_tokens: Optional[int] = None, spec_sample: bool = False,
+                     repetition_penalty: Optional[float] = None, presence_penalty: Optional[float] = None,
+                     frequency_penalty: Optional[float] = None) -> str:
     """Text + images in, decoded reply out — the contract of `LlavaLlamaModel.generate_content` for image / text prompts.
     temperature > 0 samples (server.py:185-187: do_sample = temperature > 0, with the request's top_p and HF's default top_k = 50).
     prompt_lookup_num_tokens=k: speculative decoding with k lookup drafts per step (`llm.generate(prompt_lookup_num_tokens=)`); the reply is
     the greedy reply.  A sampled request ignores it unless spec_sample=True (default False), which passes both on
     (`llm.generate(do_sample=True, prompt_lookup_num_tokens=k, spec_sample=True)`, top_k in 1..64): the reply is then the one the same sampled
     request gives without drafts, a draft being accepted exactly when the request's own draw hits it.
-    streamer: a `TextStream` (or any HF streamer) that receives the new tokens while they are generated (`llm.generate(streamer=...)`)."""
+    streamer: a `TextStream` (or any HF streamer) that receives the new tokens while they are generated (`llm.generate(streamer=...)`).
+    repetition_penalty / presence_penalty / frequency_penalty: passed on to `llm.generate` when they are not neutral (1 / 0 / 0 or None); a
+    penalised request is not speculated (prompt_lookup_num_tokens is dropped for it: the verify step has no penalised form)."""
+    pen = _penalties_of(dict(repetition_penalty=repetition_penalty, presence_penalty=presence_penalty, frequency_penalty=frequency_penalty))
+    if pen:
+        prompt_lookup_num_tokens = None
     cfg = model.cfg
     dev = device or str(model.device)
     text, tiles, media_config = prepare_prompt(prompt, cfg)
@@ -413,6 +429,7 @@ def generate_content(model, tokenizer, prompt: Union[str, Sequence[Any]], max_ne
         gen.update(prompt_lookup_num_tokens=int(prompt_lookup_num_tokens))
     if streamer is not None:
         gen.update(streamer=streamer)
+    gen.update(pen)
     out = model.generate(input_ids=ids, media=media, media_config=media_config, **gen)
     toks = out[0].tolist()
     stop = _eos_set(eos)
@@ -439,7 +456,8 @@ class ChatSession:
     So the next turn's new tokens open with that last token, then the end-of-turn marker if the reply was cut by max_new_tokens rather than by it,
     the separator and the new user turn in the Qwen2 chat form (`chat_text`, the template every NVILA recipe runs).  Media of a later turn are
     encoded and spliced for the new part only.  gen_defaults / `ask(**gen)`: keyword arguments of `llm.generate` (do_sample, temperature, top_k,
-    top_p, seed, prompt_lookup_num_tokens, spec_sample, streamer, ...)."""
+    top_p, seed, prompt_lookup_num_tokens, spec_sample, streamer, repetition_penalty, presence_penalty, frequency_penalty, ...).  The penalties
+    count what the CURRENT turn has generated: every `ask` is a request of its own, earlier turns are prompt."""
 
     TURN_END = "<|im_end|>"
 
@@ -609,12 +627,15 @@ class HipBatchEngine:
     `admit(..., share=True)`), which a `ContinuousBatcher(share_prefix=True)` drives.  min_shared_len (default 2048): a prefix whose shared length would
     be shorter is not pinned and its request takes an ordinary row — the prefix step's three attention launches cost more than they save on a short
     prefix (a one-tile image, about 256 keys: 1.07 - 1.19x the ordinary step; `DESIGN.md` 4.3b).  A prefix that may be pinned must also fit a slot
-    with something behind it, so share_prefix needs max_ctx > min_shared_len: the default 2048 / 2048 pair could never share and is refused."""
+    with something behind it, so share_prefix needs max_ctx > min_shared_len: the default 2048 / 2048 pair could never share and is refused.
+    penalties=True opens the session with per-row repetition / presence / frequency penalties (`batch_open(penalties=True)`): `admit` then takes a
+    row's (rep, pres, freq) and a `ContinuousBatcher(penalties=True)` puts penalised requests into rows."""
 
     def __init__(self, model, tokenizer, n_slots: int = 8, max_ctx: int = 2048, max_new_tokens: int = 1024, eos_token_id=None,
-                 sampling: bool = False, share_prefix: bool = False, min_shared_len: int = 2048):
+                 sampling: bool = False, share_prefix: bool = False, min_shared_len: int = 2048, penalties: bool = False):
         self.model, self.tokenizer = model, tokenizer
         self.sampling = bool(sampling)
+        self.penalties = bool(penalties)                    # batch_open(penalties=True): `admit` takes a row's (rep, pres, freq)
         self.share_prefix = bool(share_prefix)
         self.min_shared_len = int(min_shared_len)
         if self.share_prefix and int(max_ctx) <= max(self.min_shared_len, 256):
@@ -633,6 +654,8 @@ class HipBatchEngine:
             if self.share_prefix:
                 kw["shared_prefix"] = True
                 self._pinned = None                                                 # a new session holds no prefix
+            if self.penalties:
+                kw["penalties"] = True
             self.st = llm.batch_open(self.n_slots, self.max_ctx, self.max_new_tokens, **kw)
         return self.st
 
@@ -695,6 +718,11 @@ class HipBatchEngine:
         """Whether a sampled request (top_k in 1..64) can take a row of this engine's batch."""
         return self.sampling
 
+    @property
+    def batches_penalties(self) -> bool:
+        """Whether a request with repetition / presence / frequency penalties can take a row of this engine's batch."""
+        return self.penalties
+
     def fresh_seed(self) -> int:
         """The seed of a sampled request that names none, derived as `generate` derives it."""
         return self.model.llm._fresh_seed()
@@ -716,10 +744,12 @@ class HipBatchEngine:
         e, _, _ = self.model._embed(ids[None].to(dev), media, media_config)
         return e[0]
 
-    def admit(self, slot: int, embeds, sampling=None, share: bool = False, first_row: int = 0) -> int:
+    def admit(self, slot: int, embeds, sampling=None, share: bool = False, first_row: int = 0, penalties=None) -> int:
         kw = {} if sampling is None else dict(sampling=sampling)
         if share:
             kw.update(share=True, first_row=first_row)
+        if penalties is not None:
+            kw.update(penalties=penalties)
         return self.model.llm.batch_admit(self._session(), slot, embeds, **kw)
 
     def run(self, k: int) -> None:
@@ -758,13 +788,17 @@ class ContinuousBatcher:
     media share the K/V of their common prefix.  When no live row shares the current prefix, a request with media that fits a slot PINS its own
     (`engine.pin`: one tower / projector / prefill run); later requests with the same key (`engine.prepare(...).key == engine.pinned_key`) are
     admitted as sharing rows, for which only the text behind the media is embedded and prefilled.  A request without media, with a prefix the engine finds too short to pay, or with another key
-    while sharers live, takes an ordinary row and does not wait; the pin moves once the sharers have retired.  `events` records ("pin", slot) and ("share", slot)."""
+    while sharers live, takes an ordinary row and does not wait; the pin moves once the sharers have retired.  `events` records ("pin", slot) and ("share", slot).
+    penalties=True (opt-in; needs an engine whose `batches_penalties` is true, i.e. `HipBatchEngine(penalties=True)`): a request with a non-neutral
+    repetition_penalty / presence_penalty / frequency_penalty that is otherwise batchable takes a row, whose counts start from zero.  Without the
+    flag such a request runs solo, the way a sampled one does without batch_sampled.  A request with neutral values is served exactly as before."""
 
-    def __init__(self, engine, max_batch: int = 8, chunk: int = 8, batch_sampled: bool = False, share_prefix: bool = False):
+    def __init__(self, engine, max_batch: int = 8, chunk: int = 8, batch_sampled: bool = False, share_prefix: bool = False, penalties: bool = False):
         import queue
         import threading
         self.engine = engine
         self.batch_sampled = bool(batch_sampled) and bool(getattr(engine, "batches_sampled", False))
+        self.penalties = bool(penalties) and bool(getattr(engine, "batches_penalties", False))
         self.share_prefix = bool(share_prefix) and bool(getattr(engine, "shares_prefix", False))
         self._pin_rows = set()                           # the live rows that share the engine's current prefix (`engine.pinned_key`)
         self._seedless = 0
@@ -827,7 +861,15 @@ class ContinuousBatcher:
             req.gen = dict(g, seed=seed)
         return (float(g["temperature"]), top_k, 1.0 if g.get("top_p") is None else float(g["top_p"]), int(seed))
 
+    @staticmethod
+    def _row_penalties(req):
+        """(rep, pres, freq) of a request that asks for a non-neutral penalty, else None."""
+        pen = _penalties_of(req.gen)
+        return tuple(pen.get(k, v) for k, v in PENALTY_NEUTRAL.items()) if pen else None
+
     def _batchable(self, req) -> bool:
+        if not self.penalties and self._row_penalties(req) is not None:
+            return False                                                # a penalised request without the flag runs solo
         return self._greedy(req) or self._row_sampling(req) is not None
 
     @staticmethod
@@ -948,7 +990,12 @@ class ContinuousBatcher:
                         pending.popleft()
                         slot = free.pop(0)
                         sampling = self._row_sampling(req)
+                        pen = self._row_penalties(req)
+                        if pen is not None:                            # (keyword only when asked for: a neutral request makes the call it always made)
+                            how = dict(how, penalties=pen)
                         first = eng.admit(slot, e, **how) if sampling is None else eng.admit(slot, e, sampling, **how)
+                        if pen is not None:
+                            how = {k: v for k, v in how.items() if k != "penalties"}
                         if how:
                             self._pin_rows.add(slot)
                         row = SimpleNamespace(req=req, toks=[first], read=0, sent=0, closed=False)
@@ -1040,7 +1087,8 @@ def _request_models():
         ChatMessage = pydantic.create_model("ChatMessage", role=(str, ...), content=(Union[str, List[Dict[str, Any]]], ...))
         ChatCompletionRequest = pydantic.create_model(
             "ChatCompletionRequest", model=(str, ...), messages=(List[ChatMessage], ...), max_tokens=(Optional[int], 512),
-            temperature=(Optional[float], 0.2), top_p=(Optional[float], 0.9), stream=(Optional[bool], False))      # server.py:101-102
+            temperature=(Optional[float], 0.2), top_p=(Optional[float], 0.9), stream=(Optional[bool], False),      # server.py:101-102
+            repetition_penalty=(Optional[float], 1.0), presence_penalty=(Optional[float], 0.0), frequency_penalty=(Optional[float], 0.0))
         _MODELS = (ChatMessage, ChatCompletionRequest)
     return _MODELS
 
@@ -1054,7 +1102,7 @@ def continuous_batching(model) -> bool:
 
 def create_app(model, tokenizer, model_name: str = "NVILA-8B", batch_window_s: Optional[float] = None, max_batch: int = 8,
                stream_timeout_s: Optional[float] = 600.0, batch_sampled: bool = False, max_ctx: int = 2048,
-               prompt_lookup_num_tokens: Optional[int] = None, spec_sample: bool = False, share_prefix: bool = False):
+               prompt_lookup_num_tokens: Optional[int] = None, spec_sample: bool = False, share_prefix: bool = False, penalties: bool = False):
     """FastAPI app with the reference's POST /chat/completions (server.py:171-290).  Import-time optional: needs fastapi + pydantic.
     batch_window_s: when set (any value), requests go through a batcher whose ONE worker thread owns the model: `ContinuousBatcher` (greedy
     requests join / leave the batched decode step between steps; sampled ones run solo on the same thread) where the model has the batched
@@ -1072,7 +1120,11 @@ def create_app(model, tokenizer, model_name: str = "NVILA-8B", batch_window_s: O
     share_prefix=True (ContinuousBatcher only; default off): requests over the same media — several questions about one video or document —
     share the K/V of their common prefix in the batched session (`ContinuousBatcher(share_prefix=True)`): the media is encoded and prefilled once,
     and every step reads its keys once for all of them.  Needs max_ctx above the engine's min_shared_len (2048): with the default max_ctx no
-    prefix worth sharing fits a slot, and the pairing is refused with a ValueError (`create_app(..., share_prefix=True, max_ctx=4096)` or more)."""
+    prefix worth sharing fits a slot, and the pairing is refused with a ValueError (`create_app(..., share_prefix=True, max_ctx=4096)` or more).
+    The request's repetition_penalty (HF's rule, default 1.0), presence_penalty and frequency_penalty (OpenAI's, default 0.0) reach `llm.generate`;
+    a request that leaves them neutral is served exactly as before.  penalties=True (ContinuousBatcher only; default off): the batched session is
+    opened with per-row penalties, so a penalised request takes a row; without it such a request runs solo, as a sampled one does without
+    batch_sampled."""
     from fastapi import FastAPI
     from fastapi.responses import JSONResponse, StreamingResponse
 
@@ -1090,8 +1142,11 @@ def create_app(model, tokenizer, model_name: str = "NVILA-8B", batch_window_s: O
                 kw["sampling"] = True
             if share_prefix:
                 kw["share_prefix"] = True
+            if penalties:
+                kw["penalties"] = True
             engine = HipBatchEngine(model, tokenizer, **kw)
-            batcher = ContinuousBatcher(engine, max_batch=max_batch, batch_sampled=batch_sampled, **(dict(share_prefix=True) if share_prefix else {}))
+            batcher = ContinuousBatcher(engine, max_batch=max_batch, batch_sampled=batch_sampled, **(dict(share_prefix=True) if share_prefix else {}),
+                                        **(dict(penalties=True) if penalties else {}))
         else:
             batcher = RequestBatcher(model, tokenizer, window_s=batch_window_s)
     app.state.batcher = batcher
@@ -1124,11 +1179,12 @@ def create_app(model, tokenizer, model_name: str = "NVILA-8B", batch_window_s: O
     model_lock = batcher.model_lock if isinstance(batcher, RequestBatcher) else threading.Lock()
     app.state.model_lock = model_lock
 
-    def _solo(parts, n, system, temperature, top_p, streamer=None):
+    def _solo(parts, n, system, temperature, top_p, streamer=None, **pen):
         """A request the batcher does not take: under the model lock — never beside the worker thread's batch, never beside another solo
         request."""
         with model_lock, torch.inference_mode():
             kw = {} if prompt_lookup_num_tokens is None else dict(prompt_lookup_num_tokens=prompt_lookup_num_tokens)
+            kw.update(pen)                              # (non-neutral penalties only; generate_content then drops the speculation)
             top_k = 50                                  # the endpoint carries no top_k: a solo request samples with generate_content's default
             if spec_sample and kw and temperature and temperature > 0 and 1 <= top_k <= 64:
                 kw.update(spec_sample=True, top_k=top_k)
@@ -1143,17 +1199,20 @@ def create_app(model, tokenizer, model_name: str = "NVILA-8B", batch_window_s: O
             temperature = request.temperature if request.temperature is not None else 0.2
             top_p = request.top_p if request.top_p is not None else 0.9
             n = request.max_tokens or 512
+            # non-neutral penalties only: a request that leaves them at 1 / 0 / 0 makes the calls it always made
+            pen = _penalties_of(dict(repetition_penalty=request.repetition_penalty, presence_penalty=request.presence_penalty,
+                                     frequency_penalty=request.frequency_penalty))
             loop = asyncio.get_running_loop()
             if request.stream:
                 # server.py:241-270: the reply leaves as it is generated.  The tokens reach a `TextStream` from whoever runs the request (the
                 # continuous batcher's worker after every chunk of steps, else a thread of its own: the reference's Thread + TextIteratorStreamer)
                 stream = TextStream(tokenizer, timeout=stream_timeout_s)
                 if isinstance(batcher, ContinuousBatcher):
-                    batcher.submit(parts, n, system, stream=stream, temperature=temperature, top_p=top_p)
+                    batcher.submit(parts, n, system, stream=stream, temperature=temperature, top_p=top_p, **pen)
                 else:
                     def run():
                         try:
-                            stream.finish(_solo(parts, n, system, temperature, top_p, streamer=stream))
+                            stream.finish(_solo(parts, n, system, temperature, top_p, streamer=stream, **pen))
                         except Exception as ex:                       # the consumer raises it
                             stream.fail(ex)
                     threading.Thread(target=run, daemon=True).start()
@@ -1161,11 +1220,11 @@ def create_app(model, tokenizer, model_name: str = "NVILA-8B", batch_window_s: O
                 pieces = stream if first is None else itertools.chain([first], stream)
                 return StreamingResponse(sse_chunks(pieces, request.model), media_type="text/event-stream")
             if isinstance(batcher, ContinuousBatcher):
-                text = await loop.run_in_executor(None, batcher.submit(parts, n, system, temperature=temperature, top_p=top_p).result)
-            elif batcher is not None and not temperature:
+                text = await loop.run_in_executor(None, batcher.submit(parts, n, system, temperature=temperature, top_p=top_p, **pen).result)
+            elif batcher is not None and not temperature and not pen:
                 text = await loop.run_in_executor(None, batcher.submit(parts, n, system).result)
             else:
-                text = _solo(parts, n, system, temperature, top_p)
+                text = _solo(parts, n, system, temperature, top_p, **pen)
             return {"id": uuid.uuid4().hex, "object": "chat.completion", "created": time.time(), "model": request.model,
                     "choices": [{"message": {"role": "assistant", "content": [{"type": "text", "text": text}]}}]}
         except Exception as e:                                       # server.py:292-297: errors come back as a 500 JSON body
