@@ -579,6 +579,21 @@ int vila_llm_decode_step_w4_sample(const VilaLlmWeights* w, const VilaLlmLayerW4
  * rows >= n and columns >= N of y are not written.  n outside 1..16, K % 128 != 0 or another mode -> -1. */
 int vila_gemv_w4_batch_bf16(const void* x, int64_t ldx, int n, const void* Wq, const void* Wsz, const void* bias, const void* residual,
                             void* y, int N, int K, int mode, vila_stream_t stream);
+/* The bf16 skinny GEMM of the batched decode, verify and shared-prefix steps (vila_amd/csrc/decode_batch.hip, bgemm_dma_kernel) on the caller's
+ * buffers, as those steps launch it.  x: 1 <= n <= 16 rows of K bf16 (row stride ldx, a multiple of 8 elements; x and W 16-byte aligned); W, W2:
+ * [N][K] bf16 with row stride K; K a positive multiple of 64, any N > 0.
+ * vila_gemm_batch_bf16: W2 == NULL: y[m][N] = x[m] . W^T (+bias); the fp32 sum goes to y_f32 (row stride ldf) and/or, rounded to bf16, to y (row
+ *   stride ldy), where `residual` (row stride ldr; may be y itself) is added to the rounded value and the sum rounded again.  At least one output.
+ *   W2 != NULL (gate/up): y = bf16(silu(bf16(x . W^T))) * bf16(x . W2^T); bias, residual and y_f32 must be NULL.
+ * vila_qkv_batch_bf16: Wqkv holds (q_heads + 2 kv_heads) * head_dim rows, q | k | v; head_dim % 32 == 0.  Row m gets bias, then rotate-half RoPE on
+ *   its q and k heads with rope_cs[m][0 : head_dim/2] = cos, [head_dim/2 : head_dim] = sin (fp32); q goes to q_out[m] (row stride ldq), K and V
+ *   to row pos[m] of kcache / vcache + m * slot_stride, each [kv_heads][max_ctx][head_dim]; a row with pos[m] >= max_ctx writes q and no K/V.
+ * Deterministic; rows >= n, columns >= N and every other cache row are not written.  Every refusal (-1) comes before anything is launched. */
+int vila_gemm_batch_bf16(const void* x, int64_t ldx, int n, const void* W, const void* W2, const void* bias, const void* residual, int64_t ldr,
+                         void* y, int64_t ldy, float* y_f32, int64_t ldf, int N, int K, vila_stream_t stream);
+int vila_qkv_batch_bf16(const void* x, int64_t ldx, int n, const void* Wqkv, const void* bias, void* q_out, int64_t ldq, void* kcache, void* vcache,
+                        int64_t slot_stride, const int32_t* pos, const float* rope_cs, int q_heads, int kv_heads, int head_dim, int max_ctx, int K,
+                        vila_stream_t stream);
 /* vila_llm_decode_step_batch with the q|k|v, o, gate/up and down projections of every layer read from `qlayers` [host] (W4A16 batched GEMVs).
  * `w` still supplies embed, norms, the q/k/v biases (one contiguous q|k|v vector) and the bf16 lm_head; its projection pointers are not read.
  * Same contract and limits as vila_llm_decode_step_batch (head_dim 128, max_ctx <= 2048, or <= 32768 with the _ctx workspace, 1 <= n <= min(16, n_slots), q_heads * head_dim ==

@@ -261,3 +261,139 @@ def framed_ws(n_bytes: int, device="cuda", guard_bytes: int = 4096):
             if bool(hit.any()):
                 raise AssertionError(f"workspace of {n_bytes} bytes: {int(hit.sum())} bytes written {name} it, first at byte offset {base + int(hit.nonzero()[0])}")
     return ws, check
+
+
+# ---- the batched decode's skinny GEMM (vila_amd/csrc/decode_batch.hip bgemm_dma_kernel): per-element bounds of its three epilogues and frames with
+# 16 rows of which n are used (tests/test_batch_gemm_bound_cpu.py proves them, tests/test_gpu_batch_gemm_elements.py uses them) -------------------
+BGEMM_EXTRA_OPS = 10        # fp32 additions behind the K products: the 8 wave partials (decode_batch.hip:232-235), the bias and the residual
+
+
+def bgemm_acc_bound(absprod64: torch.Tensor, K: int) -> torch.Tensor:
+    """A(.): gemm_elem_bound's accumulation term alone, (1 + 2^-8) (K + 10) 2^-24 absprod, for an fp32 sum of K products in any order (eight waves'
+    k-blocks round-robin, then the eight partials), bias and residual."""
+    return gemm_elem_bound(absprod64, absprod64, K, roundings=0, extra_fp32_ops=BGEMM_EXTRA_OPS)
+
+
+def bgemm_plain_bound(core64, core_abs64, K: int, bias64=None, res64=None, out_f32: bool = False):
+    """Mode 0 (decode_batch.hip:100-104) -> (ref, bound).  fp32 output: v = sum + bias as summed, A only (the residual is not part of it).  bf16
+    output without residual: one rounding, 2^-8 |ref| + A.  With residual: bfround(v) + residual, rounded again (line 103): 2^-8 |core + bias| for
+    the first rounding at ITS magnitude, 2^-8 |ref| for the second, + A; not 2 * 2^-8 |ref|, which fails a correct kernel where the residual
+    cancels the projection."""
+    proj = core64 if bias64 is None else core64 + bias64
+    absprod = core_abs64 if bias64 is None else core_abs64 + bias64.abs()
+    if out_f32 or res64 is None:
+        return proj, (0.0 if out_f32 else BF16_U) * proj.abs() + bgemm_acc_bound(absprod, K)
+    ref = proj + res64
+    return ref, BF16_U * proj.abs() + BF16_U * ref.abs() + bgemm_acc_bound(absprod + res64.abs(), K)
+
+
+def silu_f_rel_err(x_abs: torch.Tensor) -> torch.Tensor:
+    """Relative error of common.h silu_f(x) = x / (1.f + __expf(-x)) in fp32.  __expf(-x) is v_exp_f32(-x * log2 e): the product's rounding moves
+    the exponent by at most |x| log2(e) 2^-24, that is the result by |x| 2^-24 of itself, and v_exp_f32 is good to 1 ulp = 2 * 2^-24; the sum
+    1 + E passes E's error on times E / (1 + E) <= 1 and rounds once (2^-24); the division is good to 2.5 ulp = 5 * 2^-24 in its fast form
+    (correctly rounded otherwise).  Together (|x| + 8) 2^-24."""
+    return (x_abs + 8.0) * FP32_U
+
+
+def bgemm_gateup_bound(g64, g_abs64, u64, u_abs64, K: int):
+    """Mode 1 (decode_batch.hip:57-58): y = bf(bf(silu_f(bf(g))) * bf(u)), four roundings -> (ref, bound).  d_g = A_g + 2^-8 |g| bounds the rounded
+    gate, d_u likewise; s = bf(silu_f(bf(g))) is off silu(g) by d_s = 1.1 d_g + 2^-8 |silu(g)| + silu_f's own error (1.1 >= max |silu'| = 1.0998;
+    silu_f_rel_err at the rounded gate, of magnitude at most |silu(g)| + 1.1 d_g); the product of the two rounded factors is off by
+    d_s (|u| + d_u) + |silu(g)| d_u, and the last rounding adds 2^-8 |ref|.  Terms of second order in 2^-8 beyond those written (2^-8 of a
+    first-order term each, below 0.4 % of the bound) are left out, as the project's other bounds leave them out."""
+    d_g = bgemm_acc_bound(g_abs64, K) + BF16_U * g64.abs()
+    d_u = bgemm_acc_bound(u_abs64, K) + BF16_U * u64.abs()
+    s = g64 / (1.0 + torch.exp(-g64))
+    d_s = 1.1 * d_g + BF16_U * s.abs() + silu_f_rel_err(g64.abs() + d_g) * (s.abs() + 1.1 * d_g)
+    ref = s * u64
+    return ref, d_s * (u64.abs() + d_u) + s.abs() * d_u + BF16_U * ref.abs()
+
+
+def bgemm_qkv_bound(core64, core_abs64, K: int, bias64, cs64, q_heads: int, kv_heads: int, head_dim: int):
+    """Mode 2 (decode_batch.hip:72-77) -> (ref, bound), both [n, (q + 2 kv) * head_dim] in q | k | v column order.  cs64 [n, head_dim]: the table
+    the kernel reads (cos | sin).  Every element is first lo = bf(sum + bias): d = A + 2^-8 |a + bias| (V heads stop here).  Q and K heads:
+    lo' = bf(bf(lo c) + bf(-hi s)), hi' = bf(bf(hi c) + bf(lo s)).  First order F = |c| d_lo + |s| d_hi + 2^-8 (|a c| + |b s|) + 2^-8 |ref| (a, b:
+    the biased sums of the element and of its partner; symmetric for hi').  Second order: the two product roundings and the last one act on values
+    that already carry the earlier errors, each at most F, so 2 * 2^-8 F more; the fp32 add of the two rounded products rounds once, and the
+    conversion reads that sum: below 4 * 2^-24 (|a c| + |b s|).  bound = (1 + 2^-7) F + 2^-22 (|a c| + |b s|)."""
+    n = core64.shape[0]
+    half = head_dim // 2
+    proj = core64 if bias64 is None else core64 + bias64
+    absprod = core_abs64 if bias64 is None else core_abs64 + bias64.abs()
+    d = bgemm_acc_bound(absprod, K) + BF16_U * proj.abs()
+    ref, bound = proj.clone(), d.clone()
+    rope = (q_heads + kv_heads) * head_dim
+    p4, d4 = proj[:, :rope].reshape(n, -1, 2, half), d[:, :rope].reshape(n, -1, 2, half)
+    lo, hi, d_lo, d_hi = p4[:, :, 0], p4[:, :, 1], d4[:, :, 0], d4[:, :, 1]
+    c, s = cs64[:, None, :half], cs64[:, None, half:]
+    r_lo, r_hi = lo * c - hi * s, hi * c + lo * s
+    m_lo, m_hi = (lo * c).abs() + (hi * s).abs(), (hi * c).abs() + (lo * s).abs()
+    f_lo = c.abs() * d_lo + s.abs() * d_hi + BF16_U * m_lo + BF16_U * r_lo.abs()
+    f_hi = c.abs() * d_hi + s.abs() * d_lo + BF16_U * m_hi + BF16_U * r_hi.abs()
+    ref[:, :rope] = torch.stack((r_lo, r_hi), 2).reshape(n, rope)
+    bound[:, :rope] = torch.stack(((1 + 2 * BF16_U) * f_lo + 4 * FP32_U * m_lo, (1 + 2 * BF16_U) * f_hi + 4 * FP32_U * m_hi), 2).reshape(n, rope)
+    return ref, bound
+
+
+def rope_table(positions, head_dim: int, theta: float = 1e6, device="cpu") -> torch.Tensor:
+    """[n, head_dim] fp32, cos | sin of position * theta^(-2 d / head_dim), each rounded to bf16: the table bdec_prologue_kernel writes."""
+    p = torch.as_tensor(list(positions), dtype=torch.float64, device=device)[:, None]
+    inv = theta ** (-torch.arange(head_dim // 2, dtype=torch.float64, device=device) * 2.0 / head_dim)
+    ang = p * inv[None, :]
+    return torch.cat((torch.cos(ang), torch.sin(ang)), 1).to(torch.bfloat16).float().contiguous()
+
+
+def framed_out_rows(n: int, N: int, ld_pad: int, guard_rows: int, rows: int = 16, dtype=torch.bfloat16, device="cuda", fill: torch.Tensor = None):
+    """-> (view, check): framed_out for an output of `rows` rows of which only the first n may be written.  The view has all `rows` rows; check()
+    asserts that everything outside its first n rows and N columns (rows n .. rows - 1, the ld padding, the guard rows) still holds the pattern.
+    `fill` [n, N]: the initial values of the rows in use (an in-place residual)."""
+    g, ld = guard_rows, N + ld_pad
+    buf = torch.empty((rows + 2 * g, ld), dtype=dtype, device=device)
+    _int_view(buf).fill_(_pattern_of(buf))
+    view = buf[g:g + rows, :N]
+    if fill is not None:
+        view[:n].copy_(fill)
+    return view, _frame_check(buf, g, n, N, f"output frame [{n} of {rows}, {N}] ld {ld}")
+
+
+def framed_cache(kv_heads: int, max_ctx: int, head_dim: int, slots: int = 16, guard_slots: int = 1, device="cuda"):
+    """-> (cache, check): a bf16 KV cache [slots][kv][max_ctx][head_dim] holding the frame pattern, between guard slots.  check(pos, n) asserts
+    that the only elements that differ from the pattern lie in (slot m, every kv head, row pos[m]) of the rows m < n with pos[m] < max_ctx."""
+    buf = torch.empty((slots + 2 * guard_slots, kv_heads, max_ctx, head_dim), dtype=torch.bfloat16, device=device)
+    _int_view(buf).fill_(_pattern_of(buf))
+    cache = buf[guard_slots:guard_slots + slots]
+
+    def check(pos, n):
+        allowed = torch.zeros(buf.shape[:3], dtype=torch.bool, device=buf.device)
+        for m, p in enumerate(list(pos)[:n]):
+            if 0 <= int(p) < max_ctx:
+                allowed[guard_slots + m, :, int(p)] = True
+        hit = (_int_view(buf) != _pattern_of(buf)) & ~allowed[..., None]
+        k = int(hit.sum())
+        if k:
+            at = [(s - guard_slots, h, r, c) for s, h, r, c in hit.nonzero()[:8].tolist()]
+            raise AssertionError(f"KV cache: {k} elements outside the rows' own (slot, position) were written; first at (slot, kv head, position, column) {at}")
+    return cache, check
+
+
+def cache_rows(cache: torch.Tensor, pos, n: int):
+    """-> (rows [k, kv * head_dim], index): the cache rows (slot m, every kv head, pos[m]) of the k rows m < n with pos[m] < max_ctx, heads side
+    by side as the q|k|v reference has them, and the list of those m."""
+    idx = [m for m in range(n) if 0 <= int(pos[m]) < cache.shape[2]]
+    if not idx:
+        return cache.new_zeros((0, cache.shape[1] * cache.shape[3])), idx
+    return torch.stack([cache[m, :, int(pos[m])].reshape(-1) for m in idx]), idx
+
+
+def assert_qkv_outputs(q, kcache, vcache, frame_checks, pos, n: int, ref64, bound, q_heads: int, kv_heads: int, head_dim: int, what: str = "") -> float:
+    """The checks of one q|k|v call: q [>= n, q * head_dim] and the rows' own cache rows element by element against ref / bound (an unwritten cache
+    row still holds the pattern, a NaN, and fails as non-finite), then every frame (q's, and check(pos, n) of both caches).  -> worst err / bound."""
+    QS, KS = q_heads * head_dim, kv_heads * head_dim
+    worst = assert_elementwise(q[:n], ref64[:, :QS], bound[:, :QS], f"{what} q")
+    for name, cache, c0 in (("K", kcache, QS), ("V", vcache, QS + KS)):
+        rows, live = cache_rows(cache, pos, n)
+        if live:
+            worst = max(worst, assert_elementwise(rows, ref64[live, c0:c0 + KS], bound[live, c0:c0 + KS], f"{what} {name} rows of {live}"))
+    check_q, check_k, check_v = frame_checks
+    check_q(); check_k(pos, n); check_v(pos, n)
+    return worst

@@ -14,6 +14,7 @@
 //   * attention: one block per (kv head, 256-key slice, sequence) serving the whole GQA group from one K/V read (bdec_attn_kernel).
 // History (round 3, batch 8, NVILA-8B, ms per step on one MI355X): register kernel with operand-shaped loads 5.17 -> software-pipelined
 // 5.14 -> row-contiguous loads re-dealt by ds_bpermute 6.30 (rejected) -> LDS-DMA rings 3.74 -> GQA-sliced attention 3.59.
+#include "../../include/vila_hip.h"
 #include "kernels.h"
 #include "gemv_common.h"
 #include "attn_common.h"
@@ -659,4 +660,37 @@ int bverify_step(const BDecodeArgs& m, const BLayer* layers, bf16_t* kcache, bf1
                        st.hist, st.n_hist, st.hist_cap, st.n_accept);
     VILA_LAUNCH_CHECK();
     return 0;
+}
+
+// ---- operator entries of the skinny GEMM (include/vila_hip.h; tests/test_gpu_batch_gemm_elements.py) -----------------------------------
+// The step's own launcher on caller-owned buffers: a BGemmArgs filled from the arguments, launch_bgemm unchanged.  What the step guarantees
+// by construction (row strides that hold a row, gate/up without bias or residual, heads that exist) is refused here before anything is launched.
+extern "C" int vila_gemm_batch_bf16(const void* x, int64_t ldx, int n, const void* W, const void* W2, const void* bias, const void* residual, int64_t ldr,
+                                    void* y, int64_t ldy, float* y_f32, int64_t ldf, int N, int K, vila_stream_t stream) {
+    VILA_REQUIRE(x != nullptr && W != nullptr, "vila_gemm_batch_bf16: NULL operand");
+    VILA_REQUIRE(y != nullptr || y_f32 != nullptr, "vila_gemm_batch_bf16: NULL output (y, y_f32 or both)");
+    VILA_REQUIRE(N > 0 && K > 0 && ldx >= K && (y == nullptr || ldy >= N) && (y_f32 == nullptr || ldf >= N) && (residual == nullptr || ldr >= N),
+                 "vila_gemm_batch_bf16: a row stride shorter than its row (N=%d, K=%d)", N, K);
+    VILA_REQUIRE(W2 == nullptr || (bias == nullptr && residual == nullptr && y_f32 == nullptr),
+                 "vila_gemm_batch_bf16: gate/up takes no bias, residual or fp32 output");
+    VILA_REQUIRE(residual == nullptr || y != nullptr, "vila_gemm_batch_bf16: the residual is added to the bf16 output only");
+    BGemmArgs g{};
+    g.x = (const bf16_t*)x; g.ldx = ldx; g.W = (const bf16_t*)W; g.W2 = (const bf16_t*)W2; g.bias = (const bf16_t*)bias;
+    g.residual = (const bf16_t*)residual; g.ldr = ldr; g.y = (bf16_t*)y; g.ldy = ldy; g.y_f32 = y_f32; g.ldf = ldf;
+    g.n = n; g.N = N; g.K = K; g.mode = W2 != nullptr ? 1 : 0;
+    return launch_bgemm(g, vila_stream_enter((void*)stream));
+}
+extern "C" int vila_qkv_batch_bf16(const void* x, int64_t ldx, int n, const void* Wqkv, const void* bias, void* q_out, int64_t ldq, void* kcache, void* vcache,
+                                   int64_t slot_stride, const int32_t* pos, const float* rope_cs, int q_heads, int kv_heads, int head_dim, int max_ctx, int K,
+                                   vila_stream_t stream) {
+    VILA_REQUIRE(x != nullptr && Wqkv != nullptr && q_out != nullptr && kcache != nullptr && vcache != nullptr && pos != nullptr && rope_cs != nullptr,
+                 "vila_qkv_batch_bf16: NULL pointer");
+    VILA_REQUIRE(q_heads > 0 && kv_heads > 0 && head_dim > 0 && max_ctx > 0 && K > 0 && ldx >= K && ldq >= (int64_t)q_heads * head_dim && slot_stride >= 0,
+                 "vila_qkv_batch_bf16: q_heads=%d, kv_heads=%d, head_dim=%d, max_ctx=%d, or a row stride shorter than its row", q_heads, kv_heads, head_dim, max_ctx);
+    BGemmArgs g{};
+    g.x = (const bf16_t*)x; g.ldx = ldx; g.W = (const bf16_t*)Wqkv; g.bias = (const bf16_t*)bias;
+    g.n = n; g.N = (q_heads + 2 * kv_heads) * head_dim; g.K = K; g.mode = 2;
+    g.q_out = (bf16_t*)q_out; g.ldq = ldq; g.kcache = (bf16_t*)kcache; g.vcache = (bf16_t*)vcache; g.slot_stride = slot_stride;
+    g.pos = pos; g.rope_cs = rope_cs; g.nq = q_heads; g.nkv = kv_heads; g.hd = head_dim; g.max_ctx = max_ctx;
+    return launch_bgemm(g, vila_stream_enter((void*)stream));
 }

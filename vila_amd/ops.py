@@ -170,6 +170,51 @@ def gemv_w4_batch(x: torch.Tensor, mat, bias: Optional[torch.Tensor] = None, res
     return out
 
 
+def gemm_batch(x: torch.Tensor, w: torch.Tensor, w2: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None,
+               residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, out_f32: Optional[torch.Tensor] = None,
+               n: Optional[int] = None) -> Optional[torch.Tensor]:
+    """The batched decode step's skinny GEMM (vila_gemm_batch_bf16): x [n, K] bf16 (1 <= n <= 16, any row stride that is a multiple of 8),
+    w [N, K] contiguous -> out [>= n, N] bf16 = x . w^T (+bias)(+residual; may be `out`) and/or out_f32 [>= n, N] fp32 (the sum before any rounding);
+    with w2: out = silu(x w^T) * (x w2^T).  Without `out` and `out_f32` a bf16 result is allocated.  Rows of the outputs beyond n are not written.
+    `n` overrides x's row count (the refusals of the entry point are reachable with it)."""
+    _need(x, name="x"); _need(w, name="w")
+    assert x.dim() == 2 and w.dim() == 2 and x.stride(1) == 1 and w.is_contiguous() and (w2 is None or (w2.is_contiguous() and w2.shape == w.shape))
+    if x.shape[1] != w.shape[1]:
+        raise ValueError(f"gemm_batch: x has {x.shape[1]} columns, the matrix {w.shape[1]}")
+    n = x.shape[0] if n is None else n
+    N, K = w.shape
+    if out is None and out_f32 is None:
+        out = torch.empty((n, N), device=x.device, dtype=torch.bfloat16)
+    for t, dt, name in ((out, torch.bfloat16, "out"), (out_f32, torch.float32, "out_f32"), (residual, torch.bfloat16, "residual")):
+        if t is not None:
+            _need(t, dtype=dt, name=name); assert t.dim() == 2 and t.stride(1) == 1 and t.shape[1] == N and t.shape[0] >= min(n, 16)
+    ld = lambda t: 0 if t is None else t.stride(0)
+    check(_lib.load().vila_gemm_batch_bf16(x.data_ptr(), x.stride(0), n, w.data_ptr(), _p(w2), _p(bias), _p(residual), ld(residual), _p(out), ld(out),
+                                           _p(out_f32), ld(out_f32), N, K, _stream()), "gemm_batch")
+    return out if out is not None else out_f32
+
+
+def qkv_batch(x: torch.Tensor, wqkv: torch.Tensor, bias: Optional[torch.Tensor], q_out: torch.Tensor, kcache: torch.Tensor, vcache: torch.Tensor,
+              pos: torch.Tensor, rope_cs: torch.Tensor, q_heads: int, kv_heads: int, head_dim: int, n: Optional[int] = None) -> torch.Tensor:
+    """The batched decode step's q|k|v projection (vila_qkv_batch_bf16): x [n, K] bf16, wqkv [(q + 2 kv) * head_dim, K] contiguous; row m gets the
+    bias, RoPE from rope_cs [n, head_dim] fp32 (cos | sin of its position), q into q_out [>= n, q * head_dim] and K / V into row pos[m] (int32) of
+    kcache / vcache [slots >= n, kv, max_ctx, head_dim] slot m; rows with pos[m] >= max_ctx write no K/V."""
+    _need(x, name="x"); _need(wqkv, name="wqkv"); _need(q_out, name="q_out"); _need(kcache, name="kcache"); _need(vcache, name="vcache")
+    _need(pos, dtype=torch.int32, name="pos"); _need(rope_cs, dtype=torch.float32, name="rope_cs")
+    assert x.dim() == 2 and x.stride(1) == 1 and wqkv.is_contiguous() and q_out.dim() == 2 and q_out.stride(1) == 1
+    if x.shape[1] != wqkv.shape[1]:
+        raise ValueError(f"qkv_batch: x has {x.shape[1]} columns, the matrix {wqkv.shape[1]}")
+    n = x.shape[0] if n is None else n
+    assert wqkv.shape[0] == (q_heads + 2 * kv_heads) * head_dim and q_out.shape[1] == q_heads * head_dim and q_out.shape[0] >= min(n, 16)
+    assert kcache.dim() == 4 and kcache.shape == vcache.shape and kcache.shape[1:] == (kv_heads, kcache.shape[2], head_dim) and kcache.shape[0] >= min(n, 16)
+    assert kcache[0].is_contiguous() and vcache[0].is_contiguous() and kcache.stride(0) == vcache.stride(0)
+    assert pos.numel() >= min(n, 16) and rope_cs.is_contiguous() and rope_cs.numel() >= min(n, 16) * head_dim
+    check(_lib.load().vila_qkv_batch_bf16(x.data_ptr(), x.stride(0), n, wqkv.data_ptr(), _p(bias), q_out.data_ptr(), q_out.stride(0), kcache.data_ptr(),
+                                          vcache.data_ptr(), kcache.stride(0), pos.data_ptr(), rope_cs.data_ptr(), q_heads, kv_heads, head_dim,
+                                          kcache.shape[2], x.shape[1], _stream()), "qkv_batch")
+    return q_out
+
+
 def gemm_w4(x: torch.Tensor, mat, bias: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
             out: Optional[torch.Tensor] = None, heads: Optional[tuple] = None) -> torch.Tensor:
     """W4A16 GEMM (prefill shapes) on a vila_amd.quant.W4Matrix: x [M, K] bf16 -> [M, N] bf16 = x . W^T (+bias)(+residual); gate/up
