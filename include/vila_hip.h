@@ -695,6 +695,37 @@ int vila_llm_decode_step_batch_penalized(const VilaLlmWeights* w, const VilaLlmL
                                          const VilaDecodeBatch* st, const VilaDecodePrefix* prefix /*nullable*/, void* workspace, size_t workspace_bytes,
                                          const VilaBatchSampling* sp /*nullable*/, const VilaPenalties* pen, vila_stream_t stream);
 
+/* Log-probabilities of the chosen token and of its top alternatives (vila_amd/csrc/logprob.hip): the `logprobs` / `top_logprobs` of an OpenAI-style
+ * endpoint, HF's `compute_transition_scores`.  For a row x[0 .. vocab - 1] of RAW fp32 logits, all in fp32:
+ *   M = max x,  lse = M + log(sum_i exp(x_i - M)),  logprob(t) = x_t - lse          (an -inf entry contributes 0 to the sum)
+ * RAW: the numbers describe the model's own distribution.  Temperature, top-k, top-p and penalties do not enter, also where the session's pick is
+ * sampled or penalised (st->logits stays raw under every step entry).
+ * The alternatives are the top_n (0 .. VILA_LOGPROBS_MAX_TOP) largest raw logits in descending order, ties towards the LOWER index, selected by
+ * comparing the floats only: the ids are exact.  Places from top_n on, and places that a vocabulary below 20 cannot fill, hold id -1 and logprob
+ * -inf.  The chosen token's logprob is always reported; a token outside 0 .. vocab - 1 gives NaN for it and disturbs nothing else.
+ * Two launches whatever n; every reduction runs in a fixed order without floating-point atomics, so the bits are the same on every run, and a row's
+ * bits depend neither on n nor on which row it is.  Nothing at or beyond vocab within a row is read.
+ * Records: row r writes record rec[r] + rec_bias (rec NULL: rec_bias); an index outside 0 .. max_rec - 1 writes NOTHING.  token, rec and the logits
+ * are device arrays read at run time: one captured hipGraph serves every request.
+ * Behind a decode step: launch it AFTER the step entry on the same stream, with logits = st->logits, token = st->token, rec = st->n_out and
+ * rec_bias = -1.  It then records the token that step chose, and record k of a row lines up with out_ids[k] (an idle row that has stepped past
+ * max_out writes nothing, as out_ids is guarded). */
+#define VILA_LOGPROBS_MAX_TOP 20
+typedef struct {
+    float*   token_logprob;   /* [n][max_rec] */
+    float*   top_logprob;     /* [n][max_rec][VILA_LOGPROBS_MAX_TOP]; NULL together with top_id: no alternatives (top_n must be 0) */
+    int32_t* top_id;          /* same shape */
+    int      max_rec;         /* >= 1 */
+} VilaLogprobOut;
+size_t vila_logprobs_workspace_bytes(int n);
+/* the number of logits in one slice of a row of `vocab` entries (stage 1 reduces a row slice by slice; a multiple of 4) */
+int vila_logprobs_slice_width(int vocab);
+/* n >= 1 rows (not limited to 16), ld >= vocab; workspace: vila_logprobs_workspace_bytes(n) bytes, 8-byte aligned.  Bad arguments are refused before
+ * any launch. */
+int vila_logprobs_f32(const float* logits, int64_t ld, int n, int vocab, const int64_t* token /*[n] device*/, int top_n /*0..20*/,
+                      const int32_t* rec /*[n] device, nullable: record 0*/, int rec_bias, const VilaLogprobOut* out,
+                      void* workspace, vila_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

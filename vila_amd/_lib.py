@@ -85,6 +85,10 @@ class VilaPenalties(C.Structure):
     _fields_ = [("repetition", c_void_p), ("presence", c_void_p), ("frequency", c_void_p), ("counts", c_void_p), ("ld_counts", c_int64)]
 
 
+class VilaLogprobOut(C.Structure):
+    _fields_ = [("token_logprob", c_void_p), ("top_logprob", c_void_p), ("top_id", c_void_p), ("max_rec", c_int)]
+
+
 class VilaDecodeState(C.Structure):
     _fields_ = [("pos", c_void_p), ("token", c_void_p), ("out_ids", c_void_p), ("n_out", c_void_p),
                 ("max_out", c_int), ("logits", c_void_p)]
@@ -299,6 +303,10 @@ PROTOTYPES = {
     "vila_llm_decode_step_batch_penalized": (c_int, [C.POINTER(VilaLlmWeights), C.POINTER(VilaLlmLayerW4), C.POINTER(VilaKvCache), C.POINTER(VilaDecodeBatch),
                                                      C.POINTER(VilaDecodePrefix), c_void_p, c_size_t, C.POINTER(VilaBatchSampling), C.POINTER(VilaPenalties),
                                                      c_void_p]),
+    # ---- log-probabilities of the chosen token and its top alternatives ----
+    "vila_logprobs_workspace_bytes": (c_size_t, [c_int]),
+    "vila_logprobs_slice_width": (c_int, [c_int]),
+    "vila_logprobs_f32": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_int, c_void_p, c_int, C.POINTER(VilaLogprobOut), c_void_p, c_void_p]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -639,6 +639,16 @@ extern "C" int vila_logits_penalize_f32(const float* logits, int64_t ld, int n, 
     const Penalties P{pen->repetition, pen->presence, pen->frequency, pen->counts, pen->ld_counts};
     return launch_penalize(logits, ld, n, vocab, P, token, out, ld_out, PEN_PICK_SLICES, pick_v, pick_i, S(stream));
 }
+// log-probabilities of the chosen token and its top alternatives (logprob.hip)
+extern "C" size_t vila_logprobs_workspace_bytes(int n) { return logprob_workspace_bytes(n); }
+extern "C" int vila_logprobs_slice_width(int vocab) { return vocab >= 1 ? logprob_slice_width(vocab) : 0; }
+extern "C" int vila_logprobs_f32(const float* logits, int64_t ld, int n, int vocab, const int64_t* token, int top_n, const int32_t* rec, int rec_bias,
+                                 const VilaLogprobOut* out, void* workspace, vila_stream_t stream) {
+    static_assert(VILA_LOGPROBS_MAX_TOP == LP_TOP, "the header's record width is the kernel's");
+    VILA_REQUIRE(out != nullptr, "logprobs: the output descriptor is NULL");
+    VILA_REQUIRE((uintptr_t)workspace % 8 == 0, "logprobs: the workspace must be 8-byte aligned");
+    return launch_logprobs(logits, ld, n, vocab, token, top_n, rec, rec_bias, out->token_logprob, out->top_logprob, out->top_id, out->max_rec, workspace, S(stream));
+}
 extern "C" size_t vila_sample_workspace_bytes(void) { return sample_workspace_bytes(); }
 extern "C" int vila_sample_f32(const float* logits, int n, const VilaSampling* sp, const int32_t* counter, int64_t* out, void* workspace,
                                float* dist_out, vila_stream_t stream) {

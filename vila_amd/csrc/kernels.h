@@ -72,6 +72,21 @@ struct BatchSampling { const float* temperature; const int32_t* top_k; const flo
 size_t sample_batch_workspace_bytes(int n);
 int launch_sample_batch(const float* logits, int64_t ld_logits, int n, int vocab, const BatchSampling& sp, int sp_stride, const int32_t* counter, int64_t* out,
                         void* workspace, float* dist_out, int32_t* adv_pos, int64_t* adv_out_ids, int32_t* adv_n_out, int max_out, hipStream_t s);
+// ---- the (value, index) keys of sample.hip, shared with logprob.hip (device code; moved here unchanged) ----
+#if defined(__HIPCC__)
+// order-preserving key: larger float -> larger key; ties broken towards the LOWER index (index stored inverted in the low bits)
+__device__ __forceinline__ uint64_t smp_key(float v, int idx) {
+    uint32_t u = __float_as_uint(v);
+    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    return ((uint64_t)u << 32) | (uint32_t)(0x7fffffff - idx);
+}
+__device__ __forceinline__ float smp_val(uint64_t k) {
+    uint32_t u = (uint32_t)(k >> 32);
+    u = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
+    return __uint_as_float(u);
+}
+__device__ __forceinline__ int smp_idx(uint64_t k) { return 0x7fffffff - (int)(uint32_t)(k & 0xffffffffu); }
+#endif
 // repetition / presence / frequency penalties in front of the pick (penalty.hip): logits [n][ld] -> out [n][ld_out], counts[row][token[row]] bumped first
 // (token nullable: no bump), every parameter a device array [n]; pick_v / pick_i (nullable) [n][n_slices]: the (max, first index) pair of each slice of
 // the processed row — with PEN_PICK_SLICES slices the pairs bdec_pick2_kernel merges
@@ -80,6 +95,13 @@ constexpr int PEN_PICK_SLICES = 32;      // = decode_batch.hip's PICK_SLICES
 constexpr int PEN_SOLO_SLICES = 256;     // the batch-1 step: one block per CU, merged by launch_argmax_pick_advance
 int launch_penalize(const float* logits, int64_t ld, int n, int vocab, const Penalties& p, const int64_t* token, float* out, int64_t ld_out, int n_slices,
                     float* pick_v, int* pick_i, hipStream_t s);
+// log-probabilities of the chosen token and of the LP_TOP most likely ones from raw logits [n][ld] (logprob.hip): row r writes record rec[r] + rec_bias
+// (rec nullable) of token_lp [n][max_rec] and top_lp / top_id [n][max_rec][LP_TOP] (both or neither); an index outside 0 .. max_rec - 1 writes nothing
+constexpr int LP_TOP = 20;
+size_t logprob_workspace_bytes(int n);
+int logprob_slice_width(int vocab);
+int launch_logprobs(const float* logits, int64_t ld, int n, int vocab, const int64_t* token, int top_n, const int32_t* rec, int rec_bias, float* token_lp,
+                    float* top_lp, int32_t* top_id, int max_rec, void* workspace, hipStream_t s);
 // dynamic_s2 merge (s2.hip): tower output -> projector input, desc = device [n_blocks][6] {tile_base, bh, bw, i, j, single}
 int launch_s2_merge(const bf16_t* feats, bf16_t* out, const int32_t* desc, int n_blocks, int g, int C, int n_scales, const int* splits,
                     hipStream_t s);

@@ -20,18 +20,7 @@
 #define SMP_S1_BLOCKS 256
 #define SMP_S2_BLOCKS 16
 
-// order-preserving key: larger float -> larger key; ties broken towards the LOWER index (index stored inverted in the low bits)
-__device__ __forceinline__ uint64_t smp_key(float v, int idx) {
-    uint32_t u = __float_as_uint(v);
-    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    return ((uint64_t)u << 32) | (uint32_t)(0x7fffffff - idx);
-}
-__device__ __forceinline__ float smp_val(uint64_t k) {
-    uint32_t u = (uint32_t)(k >> 32);
-    u = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
-    return __uint_as_float(u);
-}
-__device__ __forceinline__ int smp_idx(uint64_t k) { return 0x7fffffff - (int)(uint32_t)(k & 0xffffffffu); }
+// smp_key / smp_val / smp_idx live in kernels.h: logprob.hip orders its alternatives with the same keys
 
 // descending bitonic sort of 1024 keys in LDS by 256 threads
 __device__ void smp_sort1024(uint64_t* keys) {

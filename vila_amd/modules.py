@@ -15,7 +15,7 @@ import ctypes as C
 import math
 import numbers
 from types import SimpleNamespace
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import torch
 import torch.nn as nn
@@ -385,6 +385,14 @@ def finish_rows(rows: List[List[int]], eos_set, pad: int, device) -> torch.Tenso
     return torch.tensor([r + [int(pad)] * (n - len(r)) for r in rows], dtype=torch.int64, device=device)
 
 
+class Logprobs(NamedTuple):
+    """What `generate(logprobs=k)` returns beside the ids [B, n_new] (and `batch_logprobs` / `score` for one row): RAW log-probabilities, i.e. of the
+    model's own distribution, independent of temperature, top-k, top-p and penalties.  Pad positions behind a row's EOS hold 0.0 / -inf / -1."""
+    token_logprobs: torch.Tensor        # [B, n_new] fp32: the logprob of the token at that position
+    top_logprobs: torch.Tensor          # [B, n_new, k] fp32: the k most likely tokens' logprobs, descending, ties towards the lower id
+    top_ids: torch.Tensor               # [B, n_new, k] int64: their ids
+
+
 class CausalLMOutput(SimpleNamespace):
     """Fields of HF CausalLMOutputWithPast that llava_llama.py:134-159 consumes."""
 
@@ -616,16 +624,97 @@ class HipQwen2ForCausalLM(_HipModule):
         st.p_freq[slot:slot + 1].fill_(float(freq))
         st.counts[slot].zero_()
 
-    def _decode_session(self, cache, max_new_tokens: int, sampling=None, penalties: bool = False):
+    @staticmethod
+    def _logprob_state(st, n: int, max_rec: int, dev) -> None:
+        """What a session with the `logprobs` flag owns: one record per row and step — the chosen token's logprob and all 20 alternatives, whatever a
+        request asks for (the host slices) — the workspace of the launch, and per row the record of the FIRST token, which the host path chooses from
+        the prefill's last row (`lp_first[row]`, three tensors, or None)."""
+        st.lp_tok = torch.zeros((n, max_rec), device=dev, dtype=torch.float32)
+        st.lp_top = torch.full((n, max_rec, ops.LOGPROBS_MAX_TOP), float("-inf"), device=dev, dtype=torch.float32)
+        st.lp_id = torch.full((n, max_rec, ops.LOGPROBS_MAX_TOP), -1, device=dev, dtype=torch.int32)
+        st.lp_ws = torch.empty((_lib.load().vila_logprobs_workspace_bytes(n),), device=dev, dtype=torch.uint8)
+        st.lp_first = [None] * n
+        st.lp = _lib.VilaLogprobOut(st.lp_tok.data_ptr(), st.lp_top.data_ptr(), st.lp_id.data_ptr(), max_rec)
+
+    @staticmethod
+    def _first_logprobs(st, row: int, logits: torch.Tensor, first: torch.Tensor) -> None:
+        """The record of a request's first token: one eager `ops.logprobs` on the prefill's last row (raw logits [V]), kept with the session's row."""
+        t, p, i = ops.logprobs(logits.reshape(1, -1).float(), first.reshape(1), ops.LOGPROBS_MAX_TOP)
+        st.lp_first[row] = (t.clone(), p.clone(), i.clone())
+
+    @staticmethod
+    def _row_logprobs(st, row: int, n_steps: int):
+        """(token_logprob [1 + n], top_logprob [1 + n, 20], top_id [1 + n, 20] i32) of a session's row: the first token's record, then those of its
+        first n_steps steps (record k belongs to out_ids[row, k])."""
+        t0, p0, i0 = st.lp_first[row]
+        n = max(0, min(int(n_steps), st.lp_tok.shape[1]))
+        return torch.cat([t0, st.lp_tok[row, :n]]), torch.cat([p0, st.lp_top[row, :n]]), torch.cat([i0, st.lp_id[row, :n]])
+
+    @staticmethod
+    def _pack_logprobs(rows, lens, n_cols: int, k: int, dev) -> "Logprobs":
+        """Per-row records -> the value `generate(logprobs=k)` returns beside ids [B, n_cols]: row b keeps its first lens[b] records (the tokens up to
+        and including its EOS), the pad positions behind them hold 0.0 / -inf / -1."""
+        B = len(rows)
+        tok = torch.zeros((B, n_cols), device=dev, dtype=torch.float32)
+        top = torch.full((B, n_cols, k), float("-inf"), device=dev, dtype=torch.float32)
+        ids = torch.full((B, n_cols, k), -1, device=dev, dtype=torch.int64)
+        for b, (t, p, i) in enumerate(rows):
+            m = min(int(lens[b]), n_cols, int(t.shape[0]))
+            tok[b, :m] = t[:m]
+            top[b, :m] = p[:m, :k]
+            ids[b, :m] = i[:m, :k].long()
+        return Logprobs(tok, top, ids)
+
+    def batch_logprobs(self, st, slot: int) -> "Logprobs":
+        """The records of row `slot` of a session opened with batch_open(logprobs=True): the first token's (chosen at `batch_admit`), then one per
+        step the row has taken since, token for token the row's own ids ([first] + out_ids[slot, :n_out]).  All 20 alternatives; RAW logprobs (the
+        model's distribution, whatever the row's sampling or penalties).  A slot that served another request before shows only the current one's."""
+        if getattr(st, "lp", None) is None:
+            raise ValueError("batch_logprobs: the session was opened without batch_open(logprobs=True)")
+        if st.lp_first[int(slot)] is None:
+            raise ValueError(f"batch_logprobs: no request was admitted into row {int(slot)}")
+        st.stream.synchronize()
+        t, p, i = self._row_logprobs(st, int(slot), int(st.n_out[int(slot)].item()))
+        return Logprobs(t, p, i.long())
+
+    SCORE_MAX_TARGETS = 512
+
+    @torch.no_grad()
+    def score(self, inputs_embeds: torch.Tensor, target_ids: torch.Tensor, top_n: int = 0) -> "Logprobs":
+        """Per-token log-likelihoods of a GIVEN continuation (HF: `log_softmax(logits).gather(...)` over a forward pass): inputs_embeds [S, H] is the
+        whole sequence, target_ids [T] are the ids at its last T positions (whose embeddings are the last T rows of inputs_embeds).  ONE
+        `prefill_packed` with last_rows = S - T - 1 .. S - 2 (the rows that predict the targets; a logits buffer of T x V fp32), then ONE
+        `ops.logprobs` over those T rows against target_ids.  1 <= T <= 512 and T < S.  bf16, or W4 where quantize_w4(prefill=True).
+        -> `Logprobs`(token_logprobs [T], top_logprobs [T, top_n], top_ids [T, top_n] int64): RAW logprobs, the top_n most likely ids per position."""
+        ops._need(inputs_embeds, dtype=None, name="inputs_embeds")
+        if inputs_embeds.dim() != 2 or inputs_embeds.shape[1] != self.lcfg.hidden_size:
+            raise ValueError(f"score: inputs_embeds must be [S, {self.lcfg.hidden_size}] (got {tuple(inputs_embeds.shape)})")
+        S, T = int(inputs_embeds.shape[0]), int(target_ids.numel())
+        if not 1 <= T <= self.SCORE_MAX_TARGETS:
+            raise ValueError(f"score: 1..{self.SCORE_MAX_TARGETS} target ids (got {T}): the logits buffer is T x vocabulary fp32")
+        if not T < S:
+            raise ValueError(f"score: the {T} targets are the LAST positions of the sequence, behind at least one position of context (got S = {S})")
+        if isinstance(top_n, bool) or not isinstance(top_n, numbers.Integral) or not 0 <= int(top_n) <= ops.LOGPROBS_MAX_TOP:
+            raise ValueError(f"score: top_n has to be an integer in 0..{ops.LOGPROBS_MAX_TOP}, but is {top_n!r}")
+        dev = inputs_embeds.device
+        rows = torch.arange(S - T - 1, S - 1, device=dev, dtype=torch.int32)
+        r = self.prefill_packed(inputs_embeds.to(self.dtype), torch.arange(S, device=dev, dtype=torch.int32), None, S, last_rows=rows)
+        t, p, i = ops.logprobs(r.last_logits, target_ids.reshape(-1).to(device=dev, dtype=torch.int64).contiguous(), int(top_n))
+        return Logprobs(t, p, i.long())
+
+    def _decode_session(self, cache, max_new_tokens: int, sampling=None, penalties: bool = False, logprobs: bool = False):
         """Device-resident decode state + workspace (+ captured hipGraph) reused across generate() calls.
         sampling: None (greedy) or (temperature, top_k, top_p, seed) — baked into the captured graph, hence part of the key.
         penalties=True (part of the key; a session without the flag keeps the key it always had): the session steps through
-        `vila_llm_decode_step_penalized` and owns the count table and the parameter arrays (`_penalty_state`)."""
+        `vila_llm_decode_step_penalized` and owns the count table and the parameter arrays (`_penalty_state`).
+        logprobs=True (part of the key only when set, likewise): `vila_logprobs_f32` runs behind every step, inside the captured graph, and the
+        session owns the records (`_logprob_state`); no launch of the step itself changes."""
         # the seed is NOT part of the key: it lives in a device scalar the sampler reads (VilaSampling.seed_dev), so every sampled request
         # with the same (temperature, top_k, top_p) replays the same captured graph (ADVICE round 2: a fresh seed per call used to drop
         # the graph, the workspace and the weight struct on every sampled request)
         key = (cache.k.data_ptr(), max_new_tokens, *self._weights_key()[:2], None if sampling is None else tuple(sampling[:3]))   # (no int4 pointer: as ever)
         key += (True,) if penalties else ()
+        key += ("logprobs",) if logprobs else ()
         if self._decode is not None and self._decode.key == key:
             if sampling is not None:
                 self._decode.seed.fill_(_as_i64(sampling[3]))
@@ -641,6 +730,7 @@ class HipQwen2ForCausalLM(_HipModule):
         st = SimpleNamespace(key=key, cache=cache)
         st.sampling = None
         st.pen = None
+        st.lp = None
         # the session outlives the call that creates it: built outside inference mode even when the first generate() runs under
         # torch.inference_mode() (llava_arch.py:823), or a later no_grad caller could not update `pos` / `token` in place
         with torch.inference_mode(False):
@@ -654,6 +744,8 @@ class HipQwen2ForCausalLM(_HipModule):
             st.seed = torch.zeros(1, device=dev, dtype=torch.int64)          # the sampler's seed (bit pattern of a uint64)
             if penalties:
                 self._penalty_state(st, 1, self.lcfg.vocab_size, dev)
+            if logprobs:
+                self._logprob_state(st, 1, max(max_new_tokens, 1), dev)
         if sampling is not None:
             st.seed.fill_(_as_i64(sampling[3]))
             st.sampling = _lib.VilaSampling(float(sampling[0]), int(sampling[1]), float(sampling[2]), int(sampling[3]) & 0xFFFFFFFFFFFFFFFF,
@@ -731,11 +823,17 @@ class HipQwen2ForCausalLM(_HipModule):
             args = ([C.byref(self._struct()), w4.ptr if w4 is not None else None, C.byref(cache.c), C.byref(st.c)] + ([ref(px)] if batch else []) +
                     [st.ws.data_ptr(), st.ws.numel(), ref(sp), C.byref(pen), ops._stream()])
             check(getattr(_lib.load(), name)(*args), name)
-            return
-        name, _ = _step_symbols(batch, w4 is not None, sp is not None, verify, verify_sample, prefix=px is not None)
-        args = ([C.byref(self._struct())] + ([w4.ptr] if w4 is not None else []) + [C.byref(cache.c), C.byref(st.c)] +
-                ([C.byref(px)] if px is not None else []) + [st.ws.data_ptr(), st.ws.numel()])
-        check(getattr(_lib.load(), name)(*args, *([C.byref(sp)] if sp is not None else []), ops._stream()), name)
+        else:
+            name, _ = _step_symbols(batch, w4 is not None, sp is not None, verify, verify_sample, prefix=px is not None)
+            args = ([C.byref(self._struct())] + ([w4.ptr] if w4 is not None else []) + [C.byref(cache.c), C.byref(st.c)] +
+                    ([C.byref(px)] if px is not None else []) + [st.ws.data_ptr(), st.ws.numel()])
+            check(getattr(_lib.load(), name)(*args, *([C.byref(sp)] if sp is not None else []), ops._stream()), name)
+        lp = getattr(st, "lp", None)                                    # a session with the logprobs flag: the record of the token this step chose
+        if lp is not None:
+            # behind the step, on its stream (inside the captured graph): token = the step's pick, n_out - 1 = its place in out_ids
+            V = self.lcfg.vocab_size
+            check(_lib.load().vila_logprobs_f32(st.logits.data_ptr(), V, st.pos.numel(), V, st.token.data_ptr(), ops.LOGPROBS_MAX_TOP, st.n_out.data_ptr(), -1,
+                                                C.byref(lp), st.lp_ws.data_ptr(), ops._stream()), "vila_logprobs_f32")
 
     def decode_step(self, cache, st) -> None:
         if self._w4 is None:
@@ -786,23 +884,27 @@ class HipQwen2ForCausalLM(_HipModule):
                 return False
         return True
 
-    def _batch_session(self, n: int, max_ctx: int, max_new_tokens: int, sampling: bool = False, shared_prefix: bool = False, penalties: bool = False):
+    def _batch_session(self, n: int, max_ctx: int, max_new_tokens: int, sampling: bool = False, shared_prefix: bool = False, penalties: bool = False,
+                       logprobs: bool = False):
         """sampling=True: the session owns per-row sampling parameters on the device (temperature / top_k / top_p / seed, every row greedy
         until `_batch_set_sampling` says otherwise) and steps through the `_sample` entry points: one captured graph for any mix of rows.
         shared_prefix=True: the cache has one slot more, the prefix slot (index n), and the session owns the shared length and the rows' flags on
         the device; it steps through the `_prefix` entry points.
         penalties=True (in the key only when set, so every other session keeps its key): the session steps through
         `vila_llm_decode_step_batch_penalized` and owns a count row and (rep, pres, freq) per row (`_penalty_state`), every row neutral until
-        `_set_penalties` says otherwise."""
+        `_set_penalties` says otherwise.
+        logprobs=True (in the key only when set, likewise): `vila_logprobs_f32` runs behind every step and the session owns a record per row and step
+        (`_logprob_state`)."""
         w4 = self._w4_batched()
         if not w4:
             self._require_bf16("the batched decode")
         key = (n, max_ctx, max_new_tokens, bool(sampling), *self._weights_key()) + ((True,) if shared_prefix else ()) + (("penalties",) if penalties else ())
+        key += ("logprobs",) if logprobs else ()
         if self._bdecode is not None and self._bdecode.key == key:
             return self._bdecode
         self._drop_session("_bdecode")
         dev, lib, w = self.device, _lib.load(), self._struct()
-        st = SimpleNamespace(key=key, graph=None, sampling=bool(sampling), sp=None, px=None, shared_prefix=bool(shared_prefix), pen=None)
+        st = SimpleNamespace(key=key, graph=None, sampling=bool(sampling), sp=None, px=None, shared_prefix=bool(shared_prefix), pen=None, lp=None)
         st.attn_slices = int(lib.vila_decode_batch_slices(int(max_ctx)))     # walking-attention slices the steps of this session launch (0: short form)
         with torch.inference_mode(False):
             st.cache = self.new_cache(max_ctx, n_slots=n + 1 if shared_prefix else n)
@@ -820,6 +922,8 @@ class HipQwen2ForCausalLM(_HipModule):
             ws_bytes = getattr(lib, _step_symbols(True, w4, bool(sampling), prefix=bool(shared_prefix), penalized=bool(penalties))[1])
             if penalties:
                 self._penalty_state(st, n, self.lcfg.vocab_size, dev)
+            if logprobs:
+                self._logprob_state(st, n, max(max_new_tokens, 1), dev)
             if sampling:
                 st.s_temperature = torch.zeros(n, device=dev, dtype=torch.float32)          # 0 = greedy row
                 st.s_top_k = torch.full((n,), 50, device=dev, dtype=torch.int32)
@@ -866,7 +970,7 @@ class HipQwen2ForCausalLM(_HipModule):
         st.s_seed[slot:slot + 1].fill_(_as_i64(seed))
 
     def batch_open(self, n_slots: int, max_ctx: int = 2048, max_new_tokens: int = 1024, sampling: bool = False, shared_prefix: bool = False,
-                   penalties: bool = False):
+                   penalties: bool = False, logprobs: bool = False):
         """Open (or re-use) the batched-decode session of `n_slots` rows with its captured step.  sampling=False: the greedy step.  sampling=True:
         the step picks per row from device-resident parameters, so the ONE captured graph serves any mix of greedy and sampled rows
         (`batch_admit(..., sampling=)`); the flag is part of the session key.
@@ -874,7 +978,10 @@ class HipQwen2ForCausalLM(_HipModule):
         rows admitted with `batch_admit(..., share=True)` read its K/V instead of a copy of their own: the step's attention reads the prefix once for
         all of them.  The ONE captured graph serves any shared length and any mix of sharing and ordinary rows.  GQA groups of 1, 2, 4, 7 or 8.
         penalties=True (part of the key as well): rows may carry repetition / presence / frequency penalties (`batch_admit(..., penalties=)`); the
-        values and every row's token counts live on the device, so the ONE captured graph serves any mix of penalised and plain rows."""
+        values and every row's token counts live on the device, so the ONE captured graph serves any mix of penalised and plain rows.
+        logprobs=True (part of the key as well): every step also records, per row, the RAW log-probability of the token it chose and of the 20 most
+        likely ones (`vila_logprobs_f32` behind the step, in the same graph; `batch_logprobs(st, slot)` reads a row's records).  Raw: the model's
+        own distribution, independent of the row's temperature, top-k, top-p and penalties."""
         if not self._w4_batched():
             self._require_bf16("batch_open")
         long_ok = (max_ctx <= 2048 and not shared_prefix) or self._long_batch_group_ok()
@@ -882,7 +989,7 @@ class HipQwen2ForCausalLM(_HipModule):
                 (self._w4_batched() or self._qkv_fused())):
             raise ValueError("batch_open: the batched decode step serves 1..16 rows of a head-dim-128 model (bf16, or quantize_w4(batch_decode=True)) "
                              f"with caches <= {self.BATCH_MAX_CTX} positions (beyond 2048: GQA groups of 1, 2, 4, 7 or 8 query heads)")
-        st = self._batch_session(max(n_slots, 2), max_ctx, max_new_tokens, sampling, shared_prefix, penalties)
+        st = self._batch_session(max(n_slots, 2), max_ctx, max_new_tokens, sampling, shared_prefix, penalties, logprobs)
         def reset():
             st.pos.zero_(); st.n_out.zero_(); st.token.zero_()
             if getattr(st, "pen", None) is not None:
@@ -1012,6 +1119,8 @@ class HipQwen2ForCausalLM(_HipModule):
             self._batch_set_sampling(st, slot, sampling)
         if getattr(st, "pen", None) is not None:
             self._set_penalties(st, slot, penalties)
+        if getattr(st, "lp", None) is not None:
+            self._first_logprobs(st, int(slot), logits, first)         # the row's records are its own from here: n_out restarts at 0 below
         st.pos[slot:slot + 1].fill_(P)
         st.n_out[slot:slot + 1].zero_()
         st.token[slot:slot + 1].copy_(first)
@@ -1038,17 +1147,19 @@ class HipQwen2ForCausalLM(_HipModule):
                 st.sharers.difference_update(int(s) for s in slots)
 
     def _generate_shared(self, inputs_embeds, n: int, max_new_tokens, eos_token_id, pad_token_id, use_graph: bool, return_logits: bool, sampling,
-                         penalties=None):
+                         penalties=None, logprobs=None):
         """generate(num_return_sequences=n): ONE prefill of the prompt into the prefix slot of a shared-prefix sampling session, n sharing rows that
         differ in their seeds.  Returns [n, n_new] like `_generate_batch`; return_logits: (ids [n, n_new], logits [n_new, n, V] fp32), eager steps.
         A prompt below 256 positions has no whole chunk to share: nothing goes into the prefix slot and the n rows are ordinary rows of the same
         session, each prefilled on its own (return_logits is refused for it by the caller).
         penalties: None, or the request's (rep, pres, freq): the session is opened with the penalties flag and every row carries them, with counts of
-        its own."""
+        its own.
+        logprobs: None, or k: the session is opened with the logprobs flag and the call returns (ids, `Logprobs`) with k alternatives per token."""
         x = inputs_embeds[0]
         P, dev = int(x.shape[0]), x.device
         max_ctx = ((P + max_new_tokens + 255) // 256) * 256
-        st = self.batch_open(n, max_ctx, max_new_tokens, sampling=True, shared_prefix=True, penalties=penalties is not None)
+        st = self.batch_open(n, max_ctx, max_new_tokens, sampling=True, shared_prefix=True, penalties=penalties is not None,
+                             **({} if logprobs is None else dict(logprobs=True)))
         self.batch_release(st, range(st.pos.numel()))
         if P < 256:
             first_h = [self.batch_admit(st, j, x, sampling=sampling[j], penalties=penalties) for j in range(n)]
@@ -1086,12 +1197,16 @@ class HipQwen2ForCausalLM(_HipModule):
                     done_rows = [first_h[b] in eos_set or any(t in eos_set for t in got[b]) for b in range(n)]
             st.stream.synchronize()
             toks = torch.cat([first[:, None], st.out_ids[:n, :done]], 1)
-            return finish_rows(toks.tolist(), eos_set, _pad_id(pad_token_id, eos_token_id, self.lcfg.eos_token_id), dev)
+            out = finish_rows(toks.tolist(), eos_set, _pad_id(pad_token_id, eos_token_id, self.lcfg.eos_token_id), dev)
+            if logprobs is not None:
+                lens = [len(_cut_at_eos(r, eos_set)) for r in toks.tolist()]
+                return out, self._pack_logprobs([self._row_logprobs(st, b, done) for b in range(n)], lens, out.shape[1], logprobs, dev)
+            return out
         finally:
             self.batch_release(st, range(st.pos.numel()))
 
     def _generate_batch(self, inputs_embeds, attention_mask, max_new_tokens, eos_token_id, pad_token_id, use_graph: bool = True,
-                        forced_ids: Optional[torch.Tensor] = None, return_logits: bool = False, sampling=None, penalties=None):
+                        forced_ids: Optional[torch.Tensor] = None, return_logits: bool = False, sampling=None, penalties=None, logprobs=None):
         """The padded batch as ONE packed prefill (every row into its own KV-cache slot) + batched decode steps: the weights are streamed
         once per step for all rows.  Returns [B, n_new] right-padded with pad_token_id behind each row's EOS, like HF.
         forced_ids [B, n_new] / return_logits: teacher forcing for the parity tests (eager launches; the ids fed after step t are
@@ -1101,7 +1216,9 @@ class HipQwen2ForCausalLM(_HipModule):
         the position of the token it consumes; under teacher forcing the returned ids are the ones each step CHOSE.
         penalties: None, or (rep, pres, freq) for every row (or one such entry / None per row): the batch runs in a session with the penalties flag,
         whose steps count the tokens they consume and pick from the penalised logits; the returned logits stay raw, the returned ids are the ones
-        each step chose."""
+        each step chose.
+        logprobs: None, or k: the batch runs in a session with the logprobs flag and the call returns (ids, `Logprobs`) with k alternatives per
+        token (not with forced_ids / return_logits)."""
         ops._need(inputs_embeds, dtype=None, name="inputs_embeds")
         if sampling is not None:
             sampling = [None if sp is None else self._check_batch_sampling(sp, "generate(batch_sample=True)") for sp in sampling]
@@ -1118,7 +1235,8 @@ class HipQwen2ForCausalLM(_HipModule):
         seq = torch.cat([torch.full((n,), b, dtype=torch.int32) for b, n in enumerate(lens)]).to(dev)
         last = torch.tensor([c - 1 for c in cu_h[1:]], device=dev, dtype=torch.int32)
         max_ctx = ((max(lens) + max_new_tokens + 255) // 256) * 256
-        st = self._batch_session(Bn, max_ctx, max_new_tokens, sampling is not None, penalties=penalties is not None)
+        st = self._batch_session(Bn, max_ctx, max_new_tokens, sampling is not None, penalties=penalties is not None,
+                                 **({} if logprobs is None else dict(logprobs=True)))
         if penalties is not None:
             rows_pen = list(penalties) if isinstance(penalties, list) else [penalties] * Bn
             for b in range(Bn):
@@ -1135,6 +1253,9 @@ class HipQwen2ForCausalLM(_HipModule):
         st.pos.copy_(torch.tensor(lens, dtype=torch.int32))
         st.n_out.zero_()
         st.token.copy_(first)
+        if logprobs is not None:
+            for b in range(Bn):
+                self._first_logprobs(st, b, r.last_logits[b], first[b:b + 1])
         eos_set = _eos_set(eos_token_id, self.lcfg.eos_token_id)
         n_steps = max_new_tokens - 1
         if forced_ids is not None or return_logits:
@@ -1174,7 +1295,11 @@ class HipQwen2ForCausalLM(_HipModule):
                 done_rows = [first_h[b] in eos_set or any(t in eos_set for t in got[b]) for b in range(Bn)]
         st.stream.synchronize()
         toks = torch.cat([first[:, None], st.out_ids[:, :done]], 1)
-        return finish_rows(toks.tolist(), eos_set, _pad_id(pad_token_id, eos_token_id, self.lcfg.eos_token_id), dev)
+        out = finish_rows(toks.tolist(), eos_set, _pad_id(pad_token_id, eos_token_id, self.lcfg.eos_token_id), dev)
+        if logprobs is not None:
+            cut = [len(_cut_at_eos(row, eos_set)) for row in toks.tolist()]
+            return out, self._pack_logprobs([self._row_logprobs(st, b, done) for b in range(Bn)], cut, out.shape[1], logprobs, dev)
+        return out
 
     def _fresh_seed(self) -> int:
         """The seed of a sampled request that names none: torch's initial seed stepped once per request."""
@@ -1190,7 +1315,8 @@ class HipQwen2ForCausalLM(_HipModule):
                  prompt_lookup_num_tokens: Optional[int] = None, max_matching_ngram_size: Optional[int] = None,
                  prompt_ids: Optional[torch.Tensor] = None, draft_ids: Optional[torch.Tensor] = None, past_len: Optional[int] = None,
                  prefill_chunk: Optional[int] = None, spec_sample: Optional[bool] = None, num_return_sequences: Optional[int] = None,
-                 repetition_penalty: Optional[float] = None, presence_penalty: Optional[float] = None, frequency_penalty: Optional[float] = None, **kw):
+                 repetition_penalty: Optional[float] = None, presence_penalty: Optional[float] = None, frequency_penalty: Optional[float] = None,
+                 logprobs: Optional[int] = None, **kw):
         """`llm.generate(inputs_embeds=, attention_mask=, **generation_kwargs)` as called at llava_arch.py:833 (HF semantics: returns ONLY the
         new tokens, [B, n_new]).  Greedy search or sampling (do_sample: temperature / top_k / top_p, HF order, on the device); explicit
         keyword arguments override `generation_config` (HF GenerationConfig-like: do_sample, temperature, top_k, top_p, max_new_tokens,
@@ -1229,8 +1355,26 @@ class HipQwen2ForCausalLM(_HipModule):
         sampled, solo or batched, bf16 or W4 (`vila_llm_decode_step[_batch]_penalized`).  They count the tokens this request has GENERATED: the
         prompt, given as embeddings, is not counted (HF's input_ids is empty then), so the first token is never penalised.  return_logits stays
         the raw model logits.  Neutral values (1, 0, 0 or None) take the unpenalised path, sessions and graphs untouched; the values never enter a
-        session key, so one captured graph serves every penalised request.  Not served with prompt_lookup_num_tokens / draft_ids / spec_sample."""
+        session key, so one captured graph serves every penalised request.  Not served with prompt_lookup_num_tokens / draft_ids / spec_sample.
+        logprobs=k (None = off, today's call and return value; 0..20): returns (ids, lp) with lp a `Logprobs`: token_logprobs [B, n_new] fp32 — the
+        log-probability of every returned token —, top_logprobs [B, n_new, k] fp32 and top_ids [B, n_new, k] int64 — the k most likely tokens at
+        that position, descending, ties towards the lower id.  They are RAW: log_softmax of the model's logits in fp32, independent of temperature,
+        top-k, top-p and penalties (vLLM's default; `return_logits` is raw as well), computed on the device behind every step, inside the captured
+        graph (`vila_logprobs_f32`).  The positions behind a row's EOS (the pads of `ids`) hold 0.0 / -inf / -1.  The session carries a `logprobs`
+        flag in its key and always records 20 alternatives, so one graph serves any k.  Served on every path above except speculative decoding
+        (prompt_lookup_num_tokens / draft_ids: the verify steps have no logprob form) and not together with return_logits or forced_ids."""
         self._check_append_args(inputs_embeds, cache, past_len, prefill_chunk)
+        if logprobs is not None:
+            if isinstance(logprobs, bool) or not isinstance(logprobs, numbers.Integral) or not 0 <= int(logprobs) <= ops.LOGPROBS_MAX_TOP:
+                raise ValueError(f"`logprobs` has to be None or an integer in 0..{ops.LOGPROBS_MAX_TOP} (the number of top alternatives), but is {logprobs!r}")
+            if return_logits or forced_ids is not None:
+                raise ValueError("logprobs is not served together with return_logits / forced_ids: ask for one of them")
+            gc_ = generation_config
+            if (prompt_lookup_num_tokens is not None or draft_ids is not None or
+                    (gc_ is not None and getattr(gc_, "prompt_lookup_num_tokens", None) is not None)):
+                raise ValueError("logprobs is not served with speculative decoding (prompt_lookup_num_tokens / draft_ids): the verify steps have no "
+                                 "logprob form")
+            logprobs = int(logprobs)
         gc = generation_config
         pick = lambda v, name, default: v if v is not None else (getattr(gc, name, None) if gc is not None and getattr(gc, name, None) is not None else default)
         penalties = self._check_penalties(pick(repetition_penalty, "repetition_penalty", None), pick(presence_penalty, "presence_penalty", None),
@@ -1243,7 +1387,7 @@ class HipQwen2ForCausalLM(_HipModule):
             return self._generate_return_sequences(inputs_embeds, attention_mask, int(num_return_sequences), max_new_tokens, eos_token_id, do_sample,
                                                    temperature, top_k, top_p, seed, pad_token_id, generation_config, use_graph, return_logits,
                                                    forced_ids, cache, streamer, batch_sample, prompt_lookup_num_tokens, draft_ids, past_len, prefill_chunk,
-                                                   penalties)
+                                                   penalties, **({} if logprobs is None else dict(logprobs=logprobs)))
         if streamer is not None and inputs_embeds.shape[0] > 1:
             raise ValueError("TextStreamer only supports batch size 1")          # transformers/generation/streamers.py, TextStreamer.put
         do_sample = bool(pick(do_sample, "do_sample", False))
@@ -1285,11 +1429,13 @@ class HipQwen2ForCausalLM(_HipModule):
             raise ValueError(f"`top_k` has to be a non-negative integer, but is {top_k}")       # (0 = no top-k filter, like HF)
         # (a penalised greedy batch is teacher-forced and returns its logits through the batched step as well: its ids are the step's own picks)
         pen_kw = {} if penalties is None else dict(penalties=penalties)
+        if logprobs is not None:                                       # (keyword only when asked: a call without it makes the calls it always made)
+            pen_kw = dict(pen_kw, logprobs=logprobs)
         if inputs_embeds.shape[0] > 1 and self._can_batch_decode(inputs_embeds, attention_mask, max_new_tokens, do_sample,
                                                                  forced_ids if penalties is None else None, return_logits and penalties is None, cache,
                                                                  batch_sample, top_k):
             if not do_sample:
-                if penalties is None:
+                if penalties is None and logprobs is None:
                     return self._generate_batch(inputs_embeds, attention_mask, max_new_tokens, eos_token_id, pad_token_id, use_graph)
                 return self._generate_batch(inputs_embeds, attention_mask, max_new_tokens, eos_token_id, pad_token_id, use_graph, forced_ids,
                                             return_logits, **pen_kw)
@@ -1301,12 +1447,22 @@ class HipQwen2ForCausalLM(_HipModule):
         if inputs_embeds.shape[0] > 1:
             rows = []
             row_pen = {} if penalties is None else dict(repetition_penalty=penalties[0], presence_penalty=penalties[1], frequency_penalty=penalties[2])
+            if logprobs is not None:
+                row_pen = dict(row_pen, logprobs=logprobs)
+            recs = []
             for b in range(inputs_embeds.shape[0]):
                 m = None if attention_mask is None else attention_mask[b:b + 1]
-                rows.append(self.generate(inputs_embeds[b:b + 1], m, max_new_tokens, eos_token_id, do_sample, temperature, top_k, top_p,
-                                          None if seed is None else seed + b, pad_token_id, None, use_graph, False, None, cache, max_length, **row_pen)[0])
-            return finish_rows([r.tolist() for r in rows], _eos_set(eos_token_id, self.lcfg.eos_token_id),
-                               _pad_id(pad_token_id, eos_token_id, self.lcfg.eos_token_id), rows[0].device)
+                got = self.generate(inputs_embeds[b:b + 1], m, max_new_tokens, eos_token_id, do_sample, temperature, top_k, top_p,
+                                    None if seed is None else seed + b, pad_token_id, None, use_graph, False, None, cache, max_length, **row_pen)
+                if logprobs is not None:
+                    got, lp = got
+                    recs.append((lp.token_logprobs[0], lp.top_logprobs[0], lp.top_ids[0]))
+                rows.append(got[0])
+            out = finish_rows([r.tolist() for r in rows], _eos_set(eos_token_id, self.lcfg.eos_token_id),
+                              _pad_id(pad_token_id, eos_token_id, self.lcfg.eos_token_id), rows[0].device)
+            if logprobs is not None:                                   # (a solo row is cut at its EOS already: its records are its tokens)
+                return out, self._pack_logprobs(recs, [r.numel() for r in rows], out.shape[1], logprobs, out.device)
+            return out
         sampling = None
         if do_sample:
             if seed is None:
@@ -1317,7 +1473,7 @@ class HipQwen2ForCausalLM(_HipModule):
 
     def _generate_return_sequences(self, inputs_embeds, attention_mask, n, max_new_tokens, eos_token_id, do_sample, temperature, top_k, top_p, seed,
                                    pad_token_id, gc, use_graph, return_logits, forced_ids, cache, streamer, batch_sample, k_spec, draft_ids, past_len,
-                                   prefill_chunk, penalties=None):
+                                   prefill_chunk, penalties=None, logprobs=None):
         """generate(num_return_sequences=n): what is served, refused with a ValueError that says so otherwise."""
         pick = lambda v, name, default: v if v is not None else (getattr(gc, name, None) if gc is not None and getattr(gc, name, None) is not None else default)
         what = "num_return_sequences: n samples of ONE prompt over its shared K/V"
@@ -1346,7 +1502,8 @@ class HipQwen2ForCausalLM(_HipModule):
         rows = [self._check_batch_sampling((temperature, top_k, top_p, (int(seed) + j) & 0xFFFFFFFFFFFFFFFF), "generate(num_return_sequences=)")
                 for j in range(n)]
         return self._generate_shared(inputs_embeds, n, max_new_tokens, pick(eos_token_id, "eos_token_id", None), pick(pad_token_id, "pad_token_id", None),
-                                     use_graph, return_logits, rows, **({} if penalties is None else dict(penalties=penalties)))
+                                     use_graph, return_logits, rows, **({} if penalties is None else dict(penalties=penalties)),
+                                     **({} if logprobs is None else dict(logprobs=logprobs)))
 
     @staticmethod
     def _check_append_args(inputs_embeds, cache, past_len, prefill_chunk) -> None:
@@ -1406,21 +1563,25 @@ class HipQwen2ForCausalLM(_HipModule):
         return S, cache, self.prefill_packed(x.to(self.dtype), pos, None, S, cache=cache, last_rows=last), last
 
     def _generate_solo(self, inputs_embeds, attention_mask, max_new_tokens, eos_token_id, sampling, use_graph, return_logits, forced_ids, cache,
-                       streamer, past_len=None, prefill_chunk=None, penalties=None):
+                       streamer, past_len=None, prefill_chunk=None, penalties=None, logprobs=None):
         """generate() for one sequence: prefill, then the batch-1 step (one hipGraph replay per token, or step by step under `use_graph=False`,
         `return_logits` or `forced_ids`).  sampling: None (greedy) or (temperature, top_k, top_p, seed).
         penalties: None, or (rep, pres, freq): the session carries the penalties flag, its counts start from zero here (a request starts), and the
-        ids returned with return_logits are the ones each step chose from the penalised logits."""
+        ids returned with return_logits are the ones each step chose from the penalised logits.
+        logprobs: None, or k: the session carries the logprobs flag and the call returns (ids, `Logprobs`) with k alternatives per token."""
         S, cache, r, last = self._prefill_one(inputs_embeds, attention_mask, max_new_tokens, cache, None, past_len, prefill_chunk)
         dev = inputs_embeds.device
         eos_set = _eos_set(eos_token_id, self.lcfg.eos_token_id)
-        st = self._decode_session(cache, max_new_tokens, sampling, **({} if penalties is None else dict(penalties=True)))
+        st = self._decode_session(cache, max_new_tokens, sampling, **({} if penalties is None else dict(penalties=True)),
+                                  **({} if logprobs is None else dict(logprobs=True)))
         if penalties is not None:
             self._set_penalties(st, 0, penalties)
         # the sampler mixes a device counter into its random number: the decode steps use the position of the token they consume
         # (S, S+1, ...); the first token, drawn from the prefill's logits, uses S - 1
         first = ops.argmax(r.last_logits[0]) if sampling is None else ops.sample(r.last_logits[0], *sampling, counter=last)
         step_logits = [r.last_logits[0].clone()] if return_logits else None
+        if logprobs is not None:
+            self._first_logprobs(st, 0, r.last_logits[0], first)
         st.pos.fill_(S)
         st.n_out.zero_()
         st.token.copy_(first if forced_ids is None else forced_ids[:1].to(dev))
@@ -1473,6 +1634,9 @@ class HipQwen2ForCausalLM(_HipModule):
                     _stream_put(streamer, t)
             streamer.end()
         out = out[None]
+        if logprobs is not None:                                   # (cut at the EOS like `out`: record t belongs to out[0, t])
+            m = out.shape[1]
+            return out, self._pack_logprobs([self._row_logprobs(st, 0, m - 1)], [m], m, logprobs, dev)
         return (out, torch.stack(step_logits)) if return_logits else out
 
     # ---- speculative decoding: lookup drafts, k + 1 rows of one sequence per step (vila_llm_decode_step_verify[_sample]) -------------------

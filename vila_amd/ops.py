@@ -348,6 +348,39 @@ def penalize(logits: torch.Tensor, counts: torch.Tensor, repetition: torch.Tenso
     return (out, pv, pi) if return_pick else out
 
 
+LOGPROBS_MAX_TOP = 20
+
+
+def logprobs(logits: torch.Tensor, token: torch.Tensor, top_n: int = 0):
+    """Log-probabilities from RAW logits [n, V] fp32 (rows may be strided; n is not limited to 16): for every row the logprob of token[r] (i64,
+    device) and the top_n (0..20) most likely ids with theirs, descending, ties towards the lower index.  logprob(t) = x_t - logsumexp(x), all fp32, in
+    a fixed order (the same bits on every run, whatever n).  A token outside 0 .. V - 1 gives NaN; places beyond V hold id -1 / -inf.  The eager form
+    of the launch a session opened with logprobs=True runs behind its step.
+    -> (token_logprob [n] f32, top_logprob [n, top_n] f32, top_id [n, top_n] i32)."""
+    _need(logits, dtype=torch.float32, name="logits")
+    if logits.dim() != 2 or logits.stride(1) != 1:
+        raise ValueError("logprobs: logits must be [n, vocab] with contiguous rows")
+    n, V = logits.shape
+    _need(token, dtype=torch.int64, name="token")
+    if token.numel() != n or not token.is_contiguous():
+        raise ValueError(f"logprobs: token must be a contiguous tensor of {n} entries")
+    if isinstance(top_n, bool) or not isinstance(top_n, int) or not 0 <= top_n <= LOGPROBS_MAX_TOP:
+        raise ValueError(f"logprobs: top_n must be an integer in 0..{LOGPROBS_MAX_TOP} (got {top_n!r})")
+    import ctypes as C
+    lib = _lib.load()
+    dev = logits.device
+    tok_lp = torch.empty((n, 1), device=dev, dtype=torch.float32)
+    top_lp = torch.empty((n, 1, LOGPROBS_MAX_TOP), device=dev, dtype=torch.float32) if top_n else None
+    top_id = torch.empty((n, 1, LOGPROBS_MAX_TOP), device=dev, dtype=torch.int32) if top_n else None
+    ws = torch.empty((lib.vila_logprobs_workspace_bytes(n),), device=dev, dtype=torch.uint8)
+    out = _lib.VilaLogprobOut(tok_lp.data_ptr(), _p(top_lp), _p(top_id), 1)
+    check(lib.vila_logprobs_f32(logits.data_ptr(), logits.stride(0), n, V, token.data_ptr(), top_n, None, 0, C.byref(out), ws.data_ptr(), _stream()),
+          "logprobs")
+    if not top_n:
+        return tok_lp[:, 0], torch.empty((n, 0), device=dev, dtype=torch.float32), torch.empty((n, 0), device=dev, dtype=torch.int32)
+    return tok_lp[:, 0], top_lp[:, 0, :top_n], top_id[:, 0, :top_n]
+
+
 def attn_decode_batch(q: torch.Tensor, kcache: torch.Tensor, vcache: torch.Tensor, pos: torch.Tensor, scale: Optional[float] = None) -> torch.Tensor:
     """The batched decode step's attention on its own: q [n, q_heads, 128] bf16 (rows may be strided), kcache / vcache ONE layer's
     [slots >= n, kv_heads, max_ctx, 128] bf16 (contiguous), pos [n] i32 — row i attends keys 0 .. pos[i] of slot i.  max_ctx up to 32768, GQA

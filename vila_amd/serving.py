@@ -397,11 +397,56 @@ def _penalties_of(gen) -> Dict[str, float]:
     return {k: float(gen[k]) for k, v in PENALTY_NEUTRAL.items() if gen.get(k) is not None and float(gen[k]) != v}
 
 
+LOGPROBS_MAX_TOP = 20
+
+
+class ReplyWithLogprobs(str):
+    """A reply that carries its per-token log-probabilities: the text, as every caller that treats the result as text expects it, with `.logprobs`,
+    the entries in OpenAI layout (`logprob_entries`)."""
+
+    def __new__(cls, text: str, logprobs: List[Dict[str, Any]]):
+        self = super().__new__(cls, text)
+        self.logprobs = logprobs
+        return self
+
+
+def _logprobs_of(logprobs, top_logprobs) -> Optional[int]:
+    """A request's `logprobs` / `top_logprobs` -> None for a request that asks for none (served exactly as a request without the fields), else the
+    number of alternatives per token (0..20, OpenAI's limit).  top_logprobs without logprobs is an error, as it is there."""
+    if not logprobs:
+        if top_logprobs is not None:
+            raise ValueError("`top_logprobs` needs `logprobs`: true")
+        return None
+    k = 0 if top_logprobs is None else top_logprobs
+    if isinstance(k, bool) or not isinstance(k, int) or not 0 <= k <= LOGPROBS_MAX_TOP:
+        raise ValueError(f"`top_logprobs` has to be an integer in 0..{LOGPROBS_MAX_TOP}, but is {top_logprobs!r}")
+    return k
+
+
+def logprob_entries(tokenizer, toks: Sequence[int], token_logprobs, top_logprobs, top_ids, k: int) -> List[Dict[str, Any]]:
+    """The `logprobs.content` list of an OpenAI chat completion for the reply tokens `toks`: per token {"token", "logprob", "bytes",
+    "top_logprobs": [{"token", "logprob", "bytes"}, ... k of them]}, token = tokenizer.decode([id]), bytes = its UTF-8 bytes.  The three records
+    hold at least len(toks) positions (lists or tensors: [n], [n, >= k], [n, >= k]); what lies behind is ignored, so the entries are cut exactly
+    where the caller cut the tokens."""
+    as_list = lambda v: v.tolist() if hasattr(v, "tolist") else list(v)
+    tl, pl, pi = as_list(token_logprobs), as_list(top_logprobs), as_list(top_ids)
+
+    def one(t, lp):
+        piece = tokenizer.decode([int(t)])
+        return {"token": piece, "logprob": float(lp), "bytes": list(piece.encode("utf-8"))}
+    out = []
+    for j, t in enumerate(toks):
+        entry = one(t, tl[j])
+        entry["top_logprobs"] = [one(i, l) for i, l in zip(pi[j][:k], pl[j][:k]) if int(i) >= 0] if k else []
+        out.append(entry)
+    return out
+
+
 def generate_content(model, tokenizer, prompt: Union[str, Sequence[Any]], max_new_tokens: int = 128, system: Optional[str] = None,
                      eos_token_id=None, device: Optional[str] = None, temperature: float = 0.0, top_p: float = 1.0, top_k: int = 50,
                      seed: Optional[int] = None, streamer=None, prompt_lookup_num_tokens: Optional[int] = None, spec_sample: bool = False,
                      repetition_penalty: Optional[float] = None, presence_penalty: Optional[float] = None,
-                     frequency_penalty: Optional[float] = None) -> str:
+                     frequency_penalty: Optional[float] = None, logprobs: Optional[bool] = None, top_logprobs: Optional[int] = None) -> str:
     """Text + images in, decoded reply out — the contract of `LlavaLlamaModel.generate_content` for image / text prompts.
     temperature > 0 samples (server.py:185-187: do_sample = temperature > 0, with the request's top_p and HF's default top_k = 50).
     prompt_lookup_num_tokens=k: speculative decoding with k lookup drafts per step (`llm.generate(prompt_lookup_num_tokens=)`); the reply is
@@ -410,9 +455,14 @@ def generate_content(model, tokenizer, prompt: Union[str, Sequence[Any]], max_ne
     request gives without drafts, a draft being accepted exactly when the request's own draw hits it.
     streamer: a `TextStream` (or any HF streamer) that receives the new tokens while they are generated (`llm.generate(streamer=...)`).
     repetition_penalty / presence_penalty / frequency_penalty: passed on to `llm.generate` when they are not neutral (1 / 0 / 0 or None); a
-    penalised request is not speculated (prompt_lookup_num_tokens is dropped for it: the verify step has no penalised form)."""
+    penalised request is not speculated (prompt_lookup_num_tokens is dropped for it: the verify step has no penalised form).
+    logprobs=True (with top_logprobs = 0..20 alternatives per token): the reply comes back as a `ReplyWithLogprobs` — the same text, with
+    `.logprobs`, one OpenAI-layout entry per reply token (`logprob_entries`), cut exactly where the text's tokens are cut: the EOS and what follows
+    are dropped.  The numbers are RAW: the model's own distribution, independent of temperature, top_p and penalties (`llm.generate(logprobs=)`).
+    Such a request is not speculated either (the verify step has no logprob form)."""
     pen = _penalties_of(dict(repetition_penalty=repetition_penalty, presence_penalty=presence_penalty, frequency_penalty=frequency_penalty))
-    if pen:
+    n_top = _logprobs_of(logprobs, top_logprobs)
+    if pen or n_top is not None:
         prompt_lookup_num_tokens = None
     cfg = model.cfg
     dev = device or str(model.device)
@@ -430,14 +480,21 @@ def generate_content(model, tokenizer, prompt: Union[str, Sequence[Any]], max_ne
     if streamer is not None:
         gen.update(streamer=streamer)
     gen.update(pen)
-    out = model.generate(input_ids=ids, media=media, media_config=media_config, **gen)
+    lp = None
+    if n_top is not None:                              # (keyword only when asked: a request without the fields makes the call it always made)
+        out, lp = model.generate(input_ids=ids, media=media, media_config=media_config, logprobs=n_top, **gen)
+    else:
+        out = model.generate(input_ids=ids, media=media, media_config=media_config, **gen)
     toks = out[0].tolist()
     stop = _eos_set(eos)
     for k, t in enumerate(toks):                       # HF returns the EOS as the last token; decode(skip_special_tokens) drops it
         if t in stop:
             toks = toks[:k]
             break
-    return tokenizer.decode(toks, skip_special_tokens=True).strip()
+    text = tokenizer.decode(toks, skip_special_tokens=True).strip()
+    if lp is not None:
+        return ReplyWithLogprobs(text, logprob_entries(tokenizer, toks, lp.token_logprobs[0], lp.top_logprobs[0], lp.top_ids[0], n_top))
+    return text
 
 
 class ChatOverflow(ValueError):
@@ -629,12 +686,16 @@ class HipBatchEngine:
     prefix (a one-tile image, about 256 keys: 1.07 - 1.19x the ordinary step; `DESIGN.md` 4.3b).  A prefix that may be pinned must also fit a slot
     with something behind it, so share_prefix needs max_ctx > min_shared_len: the default 2048 / 2048 pair could never share and is refused.
     penalties=True opens the session with per-row repetition / presence / frequency penalties (`batch_open(penalties=True)`): `admit` then takes a
-    row's (rep, pres, freq) and a `ContinuousBatcher(penalties=True)` puts penalised requests into rows."""
+    row's (rep, pres, freq) and a `ContinuousBatcher(penalties=True)` puts penalised requests into rows.
+    logprobs=True opens the session with per-row logprob records (`batch_open(logprobs=True)`): every step records the raw log-probability of each
+    row's token and of its 20 most likely alternatives, `read_logprobs` turns a row's records into OpenAI-layout entries, and a
+    `ContinuousBatcher(logprobs=True)` puts requests that ask for logprobs into rows."""
 
     def __init__(self, model, tokenizer, n_slots: int = 8, max_ctx: int = 2048, max_new_tokens: int = 1024, eos_token_id=None,
-                 sampling: bool = False, share_prefix: bool = False, min_shared_len: int = 2048, penalties: bool = False):
+                 sampling: bool = False, share_prefix: bool = False, min_shared_len: int = 2048, penalties: bool = False, logprobs: bool = False):
         self.model, self.tokenizer = model, tokenizer
         self.sampling = bool(sampling)
+        self.logprobs = bool(logprobs)                      # batch_open(logprobs=True): every row's steps leave records for `read_logprobs`
         self.penalties = bool(penalties)                    # batch_open(penalties=True): `admit` takes a row's (rep, pres, freq)
         self.share_prefix = bool(share_prefix)
         self.min_shared_len = int(min_shared_len)
@@ -656,6 +717,8 @@ class HipBatchEngine:
                 self._pinned = None                                                 # a new session holds no prefix
             if self.penalties:
                 kw["penalties"] = True
+            if self.logprobs:
+                kw["logprobs"] = True
             self.st = llm.batch_open(self.n_slots, self.max_ctx, self.max_new_tokens, **kw)
         return self.st
 
@@ -722,6 +785,17 @@ class HipBatchEngine:
     def batches_penalties(self) -> bool:
         """Whether a request with repetition / presence / frequency penalties can take a row of this engine's batch."""
         return self.penalties
+
+    @property
+    def batches_logprobs(self) -> bool:
+        """Whether a request that asks for logprobs can take a row of this engine's batch."""
+        return self.logprobs
+
+    def read_logprobs(self, slot: int, toks: Sequence[int], top_logprobs: int) -> List[Dict[str, Any]]:
+        """The OpenAI-layout entries (`logprob_entries`) of the reply tokens `toks` of the request in row `slot`: its first token's record and those
+        of its steps (`llm.batch_logprobs`), cut where `toks` is cut.  Before the row is released."""
+        lp = self.model.llm.batch_logprobs(self._session(), slot)
+        return logprob_entries(self.tokenizer, toks, lp.token_logprobs, lp.top_logprobs, lp.top_ids, int(top_logprobs))
 
     def fresh_seed(self) -> int:
         """The seed of a sampled request that names none, derived as `generate` derives it."""
@@ -791,14 +865,20 @@ class ContinuousBatcher:
     while sharers live, takes an ordinary row and does not wait; the pin moves once the sharers have retired.  `events` records ("pin", slot) and ("share", slot).
     penalties=True (opt-in; needs an engine whose `batches_penalties` is true, i.e. `HipBatchEngine(penalties=True)`): a request with a non-neutral
     repetition_penalty / presence_penalty / frequency_penalty that is otherwise batchable takes a row, whose counts start from zero.  Without the
-    flag such a request runs solo, the way a sampled one does without batch_sampled.  A request with neutral values is served exactly as before."""
+    flag such a request runs solo, the way a sampled one does without batch_sampled.  A request with neutral values is served exactly as before.
+    logprobs=True (opt-in; needs an engine whose `batches_logprobs` is true, i.e. `HipBatchEngine(logprobs=True)`): a request submitted with
+    logprobs=True (and top_logprobs=k) that is otherwise batchable takes a row, and its future resolves to a `ReplyWithLogprobs` whose entries come
+    from the row's records (`engine.read_logprobs`).  Without the flag such a request runs solo (`engine.solo` gets the two keywords), exactly as
+    `penalties=` does it.  A request that does not ask is served exactly as before."""
 
-    def __init__(self, engine, max_batch: int = 8, chunk: int = 8, batch_sampled: bool = False, share_prefix: bool = False, penalties: bool = False):
+    def __init__(self, engine, max_batch: int = 8, chunk: int = 8, batch_sampled: bool = False, share_prefix: bool = False, penalties: bool = False,
+                 logprobs: bool = False):
         import queue
         import threading
         self.engine = engine
         self.batch_sampled = bool(batch_sampled) and bool(getattr(engine, "batches_sampled", False))
         self.penalties = bool(penalties) and bool(getattr(engine, "batches_penalties", False))
+        self.logprobs = bool(logprobs) and bool(getattr(engine, "batches_logprobs", False))
         self.share_prefix = bool(share_prefix) and bool(getattr(engine, "shares_prefix", False))
         self._pin_rows = set()                           # the live rows that share the engine's current prefix (`engine.pinned_key`)
         self._seedless = 0
@@ -821,6 +901,11 @@ class ContinuousBatcher:
         from concurrent.futures import Future
         f: Future = Future()
         req = SimpleNamespace(prompt=prompt, max_new=int(max_new_tokens), system=system, gen=gen, fut=f, stream=stream)
+        try:
+            _logprobs_of(gen.get("logprobs"), gen.get("top_logprobs"))     # a bad pair fails the request here, not after its row has run
+        except ValueError as ex:
+            self._fail(req, ex)
+            return f
         if self.dead is not None:
             self._fail(req, self.dead)
             return f
@@ -867,9 +952,16 @@ class ContinuousBatcher:
         pen = _penalties_of(req.gen)
         return tuple(pen.get(k, v) for k, v in PENALTY_NEUTRAL.items()) if pen else None
 
+    @staticmethod
+    def _row_logprobs(req) -> Optional[int]:
+        """The number of alternatives per token of a request that asks for logprobs, else None."""
+        return _logprobs_of(req.gen.get("logprobs"), req.gen.get("top_logprobs"))
+
     def _batchable(self, req) -> bool:
         if not self.penalties and self._row_penalties(req) is not None:
             return False                                                # a penalised request without the flag runs solo
+        if not self.logprobs and req.gen.get("logprobs"):
+            return False                                                # ... and so does one that asks for logprobs
         return self._greedy(req) or self._row_sampling(req) is not None
 
     @staticmethod
@@ -896,13 +988,16 @@ class ContinuousBatcher:
                 row.closed = True
                 break
 
-    def _finish(self, row, toks):
+    def _finish(self, row, toks, slot=None):
         eng = self.engine
         for k, t in enumerate(toks):                       # HF stops AFTER emitting eos; decode(skip_special_tokens) drops it
             if t in eng.eos:
                 toks = toks[:k]
                 break
-        row.req.fut.set_result(eng.decode(toks))
+        text = eng.decode(toks)
+        if row.req.gen.get("logprobs"):                    # (the row is still live: its records are read before it is released)
+            text = ReplyWithLogprobs(text, eng.read_logprobs(slot, toks, self._row_logprobs(row.req)))
+        row.req.fut.set_result(text)
         if row.req.stream is not None:
             row.req.stream.end()
 
@@ -1002,7 +1097,7 @@ class ContinuousBatcher:
                         self.events.append(("admit", slot, steps, len(rows)))
                         self._emit(row, [first])
                         if first in eng.eos or req.max_new <= 1:
-                            self._finish(row, row.toks)
+                            self._finish(row, row.toks, slot)
                             eng.release([slot])
                             free.append(slot)
                             self._pin_rows.discard(slot)
@@ -1062,7 +1157,7 @@ class ContinuousBatcher:
                         row.read = n_out[slot]
                         self._emit(row, new)
                         if any(t in eng.eos for t in row.toks) or len(row.toks) >= row.req.max_new:
-                            self._finish(row, row.toks[:row.req.max_new])
+                            self._finish(row, row.toks[:row.req.max_new], slot)
                             done.append(slot)
                     except Exception as ex:
                         self._fail(row.req, ex)
@@ -1088,7 +1183,8 @@ def _request_models():
         ChatCompletionRequest = pydantic.create_model(
             "ChatCompletionRequest", model=(str, ...), messages=(List[ChatMessage], ...), max_tokens=(Optional[int], 512),
             temperature=(Optional[float], 0.2), top_p=(Optional[float], 0.9), stream=(Optional[bool], False),      # server.py:101-102
-            repetition_penalty=(Optional[float], 1.0), presence_penalty=(Optional[float], 0.0), frequency_penalty=(Optional[float], 0.0))
+            repetition_penalty=(Optional[float], 1.0), presence_penalty=(Optional[float], 0.0), frequency_penalty=(Optional[float], 0.0),
+            logprobs=(Optional[bool], False), top_logprobs=(Optional[int], None))                                  # OpenAI's fields; top_logprobs 0..20
         _MODELS = (ChatMessage, ChatCompletionRequest)
     return _MODELS
 
@@ -1102,7 +1198,8 @@ def continuous_batching(model) -> bool:
 
 def create_app(model, tokenizer, model_name: str = "NVILA-8B", batch_window_s: Optional[float] = None, max_batch: int = 8,
                stream_timeout_s: Optional[float] = 600.0, batch_sampled: bool = False, max_ctx: int = 2048,
-               prompt_lookup_num_tokens: Optional[int] = None, spec_sample: bool = False, share_prefix: bool = False, penalties: bool = False):
+               prompt_lookup_num_tokens: Optional[int] = None, spec_sample: bool = False, share_prefix: bool = False, penalties: bool = False,
+               logprobs: bool = False):
     """FastAPI app with the reference's POST /chat/completions (server.py:171-290).  Import-time optional: needs fastapi + pydantic.
     batch_window_s: when set (any value), requests go through a batcher whose ONE worker thread owns the model: `ContinuousBatcher` (greedy
     requests join / leave the batched decode step between steps; sampled ones run solo on the same thread) where the model has the batched
@@ -1124,7 +1221,12 @@ def create_app(model, tokenizer, model_name: str = "NVILA-8B", batch_window_s: O
     The request's repetition_penalty (HF's rule, default 1.0), presence_penalty and frequency_penalty (OpenAI's, default 0.0) reach `llm.generate`;
     a request that leaves them neutral is served exactly as before.  penalties=True (ContinuousBatcher only; default off): the batched session is
     opened with per-row penalties, so a penalised request takes a row; without it such a request runs solo, as a sampled one does without
-    batch_sampled."""
+    batch_sampled.
+    The request's `logprobs`: true (with `top_logprobs`: 0..20) adds "logprobs": {"content": [...]} to the response's choice, one OpenAI-layout
+    entry per reply token (RAW log-probabilities: the model's own distribution, whatever the request's temperature, top_p and penalties); a request
+    without the fields gets today's response byte for byte and makes today's calls.  top_logprobs without logprobs, and logprobs together with
+    stream (entries on SSE pieces are not served), come back as the usual 500 body.  logprobs=True (ContinuousBatcher only; default off): the
+    batched session records logprobs per row, so such a request takes a row; without it such a request runs solo, as `penalties=` does it."""
     from fastapi import FastAPI
     from fastapi.responses import JSONResponse, StreamingResponse
 
@@ -1144,9 +1246,11 @@ def create_app(model, tokenizer, model_name: str = "NVILA-8B", batch_window_s: O
                 kw["share_prefix"] = True
             if penalties:
                 kw["penalties"] = True
+            if logprobs:
+                kw["logprobs"] = True
             engine = HipBatchEngine(model, tokenizer, **kw)
             batcher = ContinuousBatcher(engine, max_batch=max_batch, batch_sampled=batch_sampled, **(dict(share_prefix=True) if share_prefix else {}),
-                                        **(dict(penalties=True) if penalties else {}))
+                                        **(dict(penalties=True) if penalties else {}), **(dict(logprobs=True) if logprobs else {}))
         else:
             batcher = RequestBatcher(model, tokenizer, window_s=batch_window_s)
     app.state.batcher = batcher
@@ -1202,6 +1306,12 @@ def create_app(model, tokenizer, model_name: str = "NVILA-8B", batch_window_s: O
             # non-neutral penalties only: a request that leaves them at 1 / 0 / 0 makes the calls it always made
             pen = _penalties_of(dict(repetition_penalty=request.repetition_penalty, presence_penalty=request.presence_penalty,
                                      frequency_penalty=request.frequency_penalty))
+            # logprobs likewise: the two keywords travel with the penalties only for a request that asks
+            n_top = _logprobs_of(getattr(request, "logprobs", None), getattr(request, "top_logprobs", None))
+            if n_top is not None:
+                if request.stream:
+                    raise ValueError("`logprobs` is not served together with `stream`: true (entries on streamed pieces are not supported)")
+                pen = dict(pen, logprobs=True, top_logprobs=n_top)
             loop = asyncio.get_running_loop()
             if request.stream:
                 # server.py:241-270: the reply leaves as it is generated.  The tokens reach a `TextStream` from whoever runs the request (the
@@ -1225,8 +1335,10 @@ def create_app(model, tokenizer, model_name: str = "NVILA-8B", batch_window_s: O
                 text = await loop.run_in_executor(None, batcher.submit(parts, n, system).result)
             else:
                 text = _solo(parts, n, system, temperature, top_p, **pen)
-            return {"id": uuid.uuid4().hex, "object": "chat.completion", "created": time.time(), "model": request.model,
-                    "choices": [{"message": {"role": "assistant", "content": [{"type": "text", "text": text}]}}]}
+            choice: Dict[str, Any] = {"message": {"role": "assistant", "content": [{"type": "text", "text": str(text)}]}}
+            if n_top is not None:
+                choice["logprobs"] = {"content": list(getattr(text, "logprobs", None) or [])}
+            return {"id": uuid.uuid4().hex, "object": "chat.completion", "created": time.time(), "model": request.model, "choices": [choice]}
         except Exception as e:                                       # server.py:292-297: errors come back as a 500 JSON body
             return JSONResponse(status_code=500, content={"error": str(e)})
 
