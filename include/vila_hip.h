@@ -695,6 +695,43 @@ int vila_llm_decode_step_batch_penalized(const VilaLlmWeights* w, const VilaLlmL
                                          const VilaDecodeBatch* st, const VilaDecodePrefix* prefix /*nullable*/, void* workspace, size_t workspace_bytes,
                                          const VilaBatchSampling* sp /*nullable*/, const VilaPenalties* pen, vila_stream_t stream);
 
+/* Structured output: a token-level automaton per row in front of the token choice (vila_amd/csrc/constrain.hip), behind the penalties and ahead of
+ * temperature -> top-k -> top-p (where HF runs a caller's logits_processor).  Row r carries a deterministic automaton over token CLASSES, compiled on
+ * the host (vila_amd/constrain.py).  Per row r of one step:
+ *   advance  s = state[r] >= 0 and the consumed token t = token[r] in 0 .. vocab - 1: s2 = next[r][s * C + cls[r][t]], C = n_classes[r]; s2 >= 0
+ *            replaces the state, otherwise it stays.  token NULL or an id out of range: no advance (the first token is masked from the start state).
+ *   mask     y[i] = next[r][state * C + cls[r][i]] >= 0 ? x[i] : -inf for every i < vocab; a row with state -1 copies x bit for bit.
+ * Nothing at or beyond vocab is read or written; out may alias logits.  All members are DEVICE arrays read at run time: one captured hipGraph serves
+ * any automata.  The kernel cannot validate their contents (the host binds them); it keeps its own reads inside a row's table and treats a class
+ * >= C as not allowed. */
+#define VILA_CONSTRAIN_MAX_CLASSES 4096
+typedef struct {
+    int32_t*        state;      /* [n] device; -1 = the row is unconstrained; else the row's current state */
+    const uint16_t* cls;        /* [n][ld_cls] class of every token id under the row's automaton, ld_cls >= vocab */
+    int64_t         ld_cls;
+    const int16_t*  next;       /* [n][ld_next]: the row's table, row-major [n_states][n_classes[r]]; < 0 = not allowed in that state */
+    int64_t         ld_next;
+    const int32_t*  n_classes;  /* [n]; 1 .. VILA_CONSTRAIN_MAX_CLASSES */
+} VilaConstraints;
+/* The operator: logits [n][ld] fp32 -> out [n][ld_out] fp32; pick_v / pick_i (both or neither) [n][vila_logits_constrain_slices()]: per slice of a
+ * processed row its maximum and the first index that holds it (an all -inf row merges to index 0).  n in 1..65535. */
+int vila_logits_constrain_slices(void);
+int vila_logits_constrain_max_classes(void);
+int vila_logits_constrain_f32(const float* logits, int64_t ld, int n, int vocab, const VilaConstraints* con, const int64_t* token /*nullable: no advance*/,
+                              float* out, int64_t ld_out, float* pick_v, int* pick_i /*nullable*/, vila_stream_t stream);
+/* The decode steps with raw logits -> penalties (if pen) -> constrain -> pick.  st->logits stays raw; the launches in front of the pick are the plain
+ * steps', so the logits are the same bits.  qlayers, sp, prefix and pen are nullable, as in the penalised entries, whose workspace sizes these share.
+ * The verify steps have no constrained form. */
+size_t vila_llm_decode_constrained_workspace_bytes(const VilaLlmShape* s, int max_ctx);
+int vila_llm_decode_step_constrained(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers /*[host], nullable*/, const VilaKvCache* cache,
+                                     const VilaDecodeState* st, void* workspace, size_t workspace_bytes, const VilaSampling* sp /*nullable*/,
+                                     const VilaPenalties* pen /*nullable*/, const VilaConstraints* con, vila_stream_t stream);
+size_t vila_llm_decode_batch_constrained_workspace_bytes(const VilaLlmShape* s, int n, int max_ctx, int prefix);
+int vila_llm_decode_step_batch_constrained(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers /*[host], nullable*/, const VilaKvCache* cache,
+                                           const VilaDecodeBatch* st, const VilaDecodePrefix* prefix /*nullable*/, void* workspace, size_t workspace_bytes,
+                                           const VilaBatchSampling* sp /*nullable*/, const VilaPenalties* pen /*nullable*/, const VilaConstraints* con,
+                                           vila_stream_t stream);
+
 /* Log-probabilities of the chosen token and of its top alternatives (vila_amd/csrc/logprob.hip): the `logprobs` / `top_logprobs` of an OpenAI-style
  * endpoint, HF's `compute_transition_scores`.  For a row x[0 .. vocab - 1] of RAW fp32 logits, all in fp32:
  *   M = max x,  lse = M + log(sum_i exp(x_i - M)),  logprob(t) = x_t - lse          (an -inf entry contributes 0 to the sum)

@@ -85,6 +85,10 @@ class VilaPenalties(C.Structure):
     _fields_ = [("repetition", c_void_p), ("presence", c_void_p), ("frequency", c_void_p), ("counts", c_void_p), ("ld_counts", c_int64)]
 
 
+class VilaConstraints(C.Structure):
+    _fields_ = [("state", c_void_p), ("cls", c_void_p), ("ld_cls", c_int64), ("next", c_void_p), ("ld_next", c_int64), ("n_classes", c_void_p)]
+
+
 class VilaLogprobOut(C.Structure):
     _fields_ = [("token_logprob", c_void_p), ("top_logprob", c_void_p), ("top_id", c_void_p), ("max_rec", c_int)]
 
@@ -307,6 +311,17 @@ PROTOTYPES = {
     "vila_logprobs_workspace_bytes": (c_size_t, [c_int]),
     "vila_logprobs_slice_width": (c_int, [c_int]),
     "vila_logprobs_f32": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_int, c_void_p, c_int, C.POINTER(VilaLogprobOut), c_void_p, c_void_p]),
+    # ---- structured output: token-automaton constrained decoding ----
+    "vila_logits_constrain_slices": (c_int, []),
+    "vila_logits_constrain_max_classes": (c_int, []),
+    "vila_logits_constrain_f32": (c_int, [c_void_p, c_int64, c_int, c_int, C.POINTER(VilaConstraints), c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "vila_llm_decode_constrained_workspace_bytes": (c_size_t, [C.POINTER(VilaLlmShape), c_int]),
+    "vila_llm_decode_step_constrained": (c_int, [C.POINTER(VilaLlmWeights), C.POINTER(VilaLlmLayerW4), C.POINTER(VilaKvCache), C.POINTER(VilaDecodeState),
+                                                 c_void_p, c_size_t, C.POINTER(VilaSampling), C.POINTER(VilaPenalties), C.POINTER(VilaConstraints), c_void_p]),
+    "vila_llm_decode_batch_constrained_workspace_bytes": (c_size_t, [C.POINTER(VilaLlmShape), c_int, c_int, c_int]),
+    "vila_llm_decode_step_batch_constrained": (c_int, [C.POINTER(VilaLlmWeights), C.POINTER(VilaLlmLayerW4), C.POINTER(VilaKvCache), C.POINTER(VilaDecodeBatch),
+                                                       C.POINTER(VilaDecodePrefix), c_void_p, c_size_t, C.POINTER(VilaBatchSampling), C.POINTER(VilaPenalties),
+                                                       C.POINTER(VilaConstraints), c_void_p]),
 }
 
 _lib: Optional[C.CDLL] = None

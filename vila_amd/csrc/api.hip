@@ -592,7 +592,8 @@ static int decode_attn_mode() {
     return g_decode_attn;
 }
 static int decode_step_impl(const VilaLlmWeights* w, const VilaLlmLayerW4* ql, const VilaKvCache* cache, const VilaDecodeState* st,
-                            void* workspace, size_t workspace_bytes, const VilaSampling* sp, vila_stream_t stream, const VilaPenalties* pen = nullptr);
+                            void* workspace, size_t workspace_bytes, const VilaSampling* sp, vila_stream_t stream, const VilaPenalties* pen = nullptr,
+                            const VilaConstraints* con = nullptr);
 extern "C" int vila_llm_decode_step(const VilaLlmWeights* w, const VilaKvCache* cache, const VilaDecodeState* st,
                                     void* workspace, size_t workspace_bytes, vila_stream_t stream) {
     return decode_step_impl(w, nullptr, cache, st, workspace, workspace_bytes, nullptr, stream);
@@ -639,6 +640,33 @@ extern "C" int vila_logits_penalize_f32(const float* logits, int64_t ld, int n, 
     const Penalties P{pen->repetition, pen->presence, pen->frequency, pen->counts, pen->ld_counts};
     return launch_penalize(logits, ld, n, vocab, P, token, out, ld_out, PEN_PICK_SLICES, pick_v, pick_i, S(stream));
 }
+// Structured output (constrain.hip): the operator, and the batch-1 step with it between the (optional) penalties and the pick.
+static int constraints_ok(const VilaConstraints* con, int vocab, const char* fn) {
+    VILA_REQUIRE(con != nullptr && con->state != nullptr && con->cls != nullptr && con->next != nullptr && con->n_classes != nullptr,
+                 "%s: the constraints or one of their arrays are NULL", fn);
+    VILA_REQUIRE(con->ld_cls >= vocab, "%s: the class rows (%lld apart) are shorter than the vocabulary %d", fn, (long long)con->ld_cls, vocab);
+    VILA_REQUIRE(con->ld_next >= 1, "%s: the table rows are %lld entries apart", fn, (long long)con->ld_next);
+    return 0;
+}
+extern "C" int vila_logits_constrain_slices(void) { return PEN_PICK_SLICES; }
+extern "C" int vila_logits_constrain_max_classes(void) { return CON_MAX_CLASSES; }
+extern "C" int vila_logits_constrain_f32(const float* logits, int64_t ld, int n, int vocab, const VilaConstraints* con, const int64_t* token, float* out,
+                                         int64_t ld_out, float* pick_v, int* pick_i, vila_stream_t stream) {
+    VILA_REQUIRE(logits != nullptr && out != nullptr, "logits_constrain: NULL argument");
+    VILA_REQUIRE(n >= 1 && n <= 65535 && vocab >= 1, "logits_constrain: 1..65535 rows of a non-empty vocabulary (got %d x %d)", n, vocab);
+    VILA_TRY(constraints_ok(con, vocab, "logits_constrain"));
+    const Constraints Cn{con->state, con->cls, con->ld_cls, con->next, con->ld_next, con->n_classes};
+    return launch_constrain(logits, ld, n, vocab, Cn, token, out, ld_out, PEN_PICK_SLICES, pick_v, pick_i, S(stream));
+}
+extern "C" size_t vila_llm_decode_constrained_workspace_bytes(const VilaLlmShape* s, int max_ctx) { return vila_llm_decode_penalized_workspace_bytes(s, max_ctx); }
+extern "C" int vila_llm_decode_step_constrained(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers, const VilaKvCache* cache, const VilaDecodeState* st,
+                                                void* workspace, size_t workspace_bytes, const VilaSampling* sp, const VilaPenalties* pen,
+                                                const VilaConstraints* con, vila_stream_t stream) {
+    VILA_REQUIRE(w != nullptr, "llm_decode_constrained: the weights are NULL");
+    if (pen != nullptr) VILA_TRY(penalties_ok(pen, w->shape.vocab, "llm_decode_constrained"));
+    VILA_TRY(constraints_ok(con, w->shape.vocab, "llm_decode_constrained"));
+    return decode_step_impl(w, qlayers, cache, st, workspace, workspace_bytes, sp, stream, pen, con);
+}
 // log-probabilities of the chosen token and its top alternatives (logprob.hip)
 extern "C" size_t vila_logprobs_workspace_bytes(int n) { return logprob_workspace_bytes(n); }
 extern "C" int vila_logprobs_slice_width(int vocab) { return vocab >= 1 ? logprob_slice_width(vocab) : 0; }
@@ -661,13 +689,15 @@ extern "C" int vila_llm_decode_chain_error(void*, vila_stream_t) { return 0; }
 // The batch-1 step: ql == nullptr runs the bf16 projections, otherwise the int4 layers' W4A16 GEMVs (the lm_head stays bf16 either way, as
 // AWQ / TinyChat keep it fp16).  Only the four projection launches of a layer differ between the two.
 static int decode_step_impl(const VilaLlmWeights* w, const VilaLlmLayerW4* ql, const VilaKvCache* cache, const VilaDecodeState* st,
-                            void* workspace, size_t workspace_bytes, const VilaSampling* sp, vila_stream_t stream, const VilaPenalties* pen) {
+                            void* workspace, size_t workspace_bytes, const VilaSampling* sp, vila_stream_t stream, const VilaPenalties* pen,
+                            const VilaConstraints* con) {
     const VilaLlmShape& sh = w->shape;
     hipStream_t s = S(stream);
     const bool w4 = ql != nullptr;
     const char* fn = w4 ? "llm_decode_w4" : "llm_decode";
     VILA_REQUIRE(cache != nullptr && st != nullptr, "%s: cache/state is NULL", fn);
-    VILA_REQUIRE(workspace_bytes >= (pen != nullptr ? vila_llm_decode_penalized_workspace_bytes(&sh, cache->max_ctx) : vila_llm_decode_workspace_bytes(&sh, cache->max_ctx)),
+    const bool scratch = pen != nullptr || con != nullptr;         // (the constrained step's workspace is the penalised step's)
+    VILA_REQUIRE(workspace_bytes >= (scratch ? vila_llm_decode_penalized_workspace_bytes(&sh, cache->max_ctx) : vila_llm_decode_workspace_bytes(&sh, cache->max_ctx)),
                  "%s: workspace too small", fn);
     const int H = sh.hidden, F = sh.inter, hd = sh.head_dim, QS = sh.q_heads * hd, KS = sh.kv_heads * hd;
     const int ns = dec_splits(cache->max_ctx);
@@ -685,9 +715,9 @@ static int decode_step_impl(const VilaLlmWeights* w, const VilaLlmLayerW4* ql, c
     bf16_t* ao = a.take<bf16_t>(QS);
     void* smp_ws = a.take<char>(sample_workspace_bytes());
     // the penalised step (behind the plain step's layout): the processed logits and the pairs of its greedy pick
-    float* pen_y = pen != nullptr ? a.take<float>(sh.vocab) : nullptr;
-    float* pen_v = pen != nullptr ? a.take<float>(PEN_SOLO_SLICES) : nullptr;
-    int* pen_i = pen != nullptr ? a.take<int>(PEN_SOLO_SLICES) : nullptr;
+    float* pen_y = scratch ? a.take<float>(sh.vocab) : nullptr;
+    float* pen_v = scratch ? a.take<float>(PEN_SOLO_SLICES) : nullptr;
+    int* pen_i = scratch ? a.take<int>(PEN_SOLO_SLICES) : nullptr;
     VILA_REQUIRE(a.ok(), "%s: workspace arena overflow", fn);
     const size_t per_layer = (size_t)cache->n_slots * sh.kv_heads * cache->max_ctx * hd;
 
@@ -737,7 +767,8 @@ static int decode_step_impl(const VilaLlmWeights* w, const VilaLlmLayerW4* ql, c
     // advances the state; sampled: the sampler reads the logits, then the advance
     // penalised: lm_head without its fused pick, then one launch that bumps the count of the consumed token (st->token still holds it), writes the
     // processed row to pen_y and leaves its greedy pairs; the pick reads pen_y, st->logits stays raw
-    if (sp == nullptr && pen == nullptr) { lm.amax_v = tv; lm.amax_i = ti; }
+    // constrained: behind the penalties (in place on pen_y then), the automaton advances by the consumed token and masks the row (constrain.hip)
+    if (sp == nullptr && !scratch) { lm.amax_v = tv; lm.amax_i = ti; }
     VILA_TRY(launch_gemv(lm, s));
     const float* pick_src = st->logits;
     if (pen != nullptr) {
@@ -746,10 +777,16 @@ static int decode_step_impl(const VilaLlmWeights* w, const VilaLlmLayerW4* ql, c
                                  sp != nullptr ? nullptr : pen_i, s));
         pick_src = pen_y;
     }
+    if (con != nullptr) {
+        const Constraints Cn{con->state, con->cls, con->ld_cls, con->next, con->ld_next, con->n_classes};
+        VILA_TRY(launch_constrain(pick_src, sh.vocab, 1, sh.vocab, Cn, st->token, pen_y, sh.vocab, PEN_SOLO_SLICES, sp != nullptr ? nullptr : pen_v,
+                                  sp != nullptr ? nullptr : pen_i, s));
+        pick_src = pen_y;
+    }
     if (sp != nullptr) {
         VILA_TRY(launch_sample(pick_src, sh.vocab, sp->temperature, sp->top_k, sp->top_p, sp->seed, sp->seed_dev, st->pos, st->token, smp_ws, nullptr, s));
         VILA_TRY(launch_decode_advance(st->pos, st->token, st->out_ids, st->n_out, st->max_out, s));
-    } else if (pen != nullptr) {
+    } else if (scratch) {
         VILA_TRY(launch_argmax_pick_advance(pen_v, pen_i, PEN_SOLO_SLICES, st->token, st->pos, st->out_ids, st->n_out, st->max_out, s));
     } else {
         VILA_TRY(launch_argmax_pick_advance(tv, ti, n_pick, st->token, st->pos, st->out_ids, st->n_out, st->max_out, s));
@@ -835,7 +872,8 @@ static int blayer_tables(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers,
 // prefix step's, which a plain one never reaches.
 static int decode_step_batch_impl(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers, const VilaKvCache* cache, const VilaDecodeBatch* st,
                                   void* workspace, size_t workspace_bytes, const VilaBatchSampling* sp, vila_stream_t stream,
-                                  const VilaDecodePrefix* px = nullptr, const Penalties* pen = nullptr, float* pen_out = nullptr) {
+                                  const VilaDecodePrefix* px = nullptr, const Penalties* pen = nullptr, float* pen_out = nullptr,
+                                  const Constraints* con = nullptr) {
     const char* fn = qlayers != nullptr ? "llm_decode_batch_w4" : "llm_decode_batch";
     VILA_REQUIRE(w != nullptr && cache != nullptr && st != nullptr && workspace != nullptr, "%s: NULL argument", fn);
     BTables t{};
@@ -846,7 +884,7 @@ static int decode_step_batch_impl(const VilaLlmWeights* w, const VilaLlmLayerW4*
     const BPrefix bp = px != nullptr ? BPrefix{px->prefix_slot, px->shared_len, px->uses} : BPrefix{};
     return bdecode_step(t.m, t.layers.data(), B(cache->k), B(cache->v), cache->max_ctx, cache->n_slots, st->n, st->pos, st->token, st->out_ids, st->n_out,
                         st->max_out, st->logits, workspace, workspace_bytes, S(stream), qlayers != nullptr ? t.ql.data() : nullptr, sw.sp, sw.ws,
-                        px != nullptr ? &bp : nullptr, pen, pen_out);
+                        px != nullptr ? &bp : nullptr, pen, pen_out, con);
 }
 // the four steps of a prefix session and their workspace sizes (two sizes, greedy and sampled, as above)
 static size_t decode_batch_prefix_ws(const VilaLlmShape* s, int n, int max_ctx, bool sample) {
@@ -920,6 +958,26 @@ extern "C" int vila_llm_decode_step_batch_penalized(const VilaLlmWeights* w, con
     const size_t head = decode_batch_penalized_head(&w->shape, st->n, cache->max_ctx, prefix != nullptr);
     const Penalties P{pen->repetition, pen->presence, pen->frequency, pen->counts, pen->ld_counts};
     return decode_step_batch_impl(w, qlayers, cache, st, workspace, head, sp, stream, prefix, &P, (float*)((char*)workspace + head));
+}
+// The constrained batched step (constrain.hip): as the penalised one, with pen nullable too; its workspace is the penalised step's.
+extern "C" size_t vila_llm_decode_batch_constrained_workspace_bytes(const VilaLlmShape* s, int n, int max_ctx, int prefix) {
+    return vila_llm_decode_batch_penalized_workspace_bytes(s, n, max_ctx, prefix);
+}
+extern "C" int vila_llm_decode_step_batch_constrained(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers, const VilaKvCache* cache, const VilaDecodeBatch* st,
+                                                      const VilaDecodePrefix* prefix, void* workspace, size_t workspace_bytes, const VilaBatchSampling* sp,
+                                                      const VilaPenalties* pen, const VilaConstraints* con, vila_stream_t stream) {
+    const char* fn = "llm_decode_batch_constrained";
+    VILA_REQUIRE(w != nullptr && cache != nullptr && st != nullptr && workspace != nullptr, "%s: NULL argument", fn);
+    if (pen != nullptr) VILA_TRY(penalties_ok(pen, w->shape.vocab, fn));
+    VILA_TRY(constraints_ok(con, w->shape.vocab, fn));
+    VILA_REQUIRE(st->n >= 1 && st->n <= 16, "%s: 1..16 sequences (got %d)", fn, st->n);
+    VILA_REQUIRE(cache->max_ctx >= 1 && cache->max_ctx <= BDEC_MAX_CTX, "%s: caches up to %d positions (got %d)", fn, BDEC_MAX_CTX, cache->max_ctx);
+    VILA_REQUIRE(workspace_bytes >= vila_llm_decode_batch_constrained_workspace_bytes(&w->shape, st->n, cache->max_ctx, prefix != nullptr),
+                 "%s: the step needs the workspace of vila_llm_decode_batch_constrained_workspace_bytes", fn);
+    const size_t head = decode_batch_penalized_head(&w->shape, st->n, cache->max_ctx, prefix != nullptr);
+    const Penalties P = pen != nullptr ? Penalties{pen->repetition, pen->presence, pen->frequency, pen->counts, pen->ld_counts} : Penalties{};
+    const Constraints Cn{con->state, con->cls, con->ld_cls, con->next, con->ld_next, con->n_classes};
+    return decode_step_batch_impl(w, qlayers, cache, st, workspace, head, sp, stream, prefix, pen != nullptr ? &P : nullptr, (float*)((char*)workspace + head), &Cn);
 }
 // The verify step (speculative decoding, decode_batch.hip bverify_step): the layer tables are the batched step's, the state is one sequence's.
 // sp != nullptr: the sampled form, whose four parameter arrays hold ONE entry each.

@@ -438,10 +438,11 @@ size_t bdecode_prefix_workspace_bytes(int H, int F, int QS, int hd, int n, int m
 
 int bdecode_step(const BDecodeArgs& m, const BLayer* layers, bf16_t* kcache, bf16_t* vcache, int max_ctx, int n_slots, int n, int32_t* pos, int64_t* token,
                  int64_t* out_ids, int32_t* n_out, int max_out, float* logits, void* workspace, size_t workspace_bytes, hipStream_t s,
-                 const BLayerW4* qlayers, const BatchSampling* sampling, void* sampling_ws, const BPrefix* prefix, const Penalties* pen, float* pen_out) {
+                 const BLayerW4* qlayers, const BatchSampling* sampling, void* sampling_ws, const BPrefix* prefix, const Penalties* pen, float* pen_out,
+                 const Constraints* con) {
     static_assert(PEN_PICK_SLICES == PICK_SLICES, "the penalty launch writes the pairs bdec_pick2_kernel merges");
     const int H = m.hidden, F = m.inter, hd = m.head_dim, QS = m.q_heads * hd;
-    VILA_REQUIRE(pen == nullptr || pen_out != nullptr, "batched decode: the penalised pick needs its scratch rows");
+    VILA_REQUIRE((pen == nullptr && con == nullptr) || pen_out != nullptr, "batched decode: the penalised / constrained pick needs its scratch rows");
     if (prefix != nullptr) {
         VILA_REQUIRE(prefix->shared_len != nullptr && prefix->uses != nullptr, "batched decode (shared prefix): NULL argument");
         VILA_REQUIRE(n >= 1 && n < n_slots && prefix->prefix_slot >= n && prefix->prefix_slot < n_slots,
@@ -494,9 +495,16 @@ int bdecode_step(const BDecodeArgs& m, const BLayer* layers, bf16_t* kcache, bf1
                                  sampling != nullptr ? nullptr : pick_i, s));
         pick_src = pen_out;
     }
+    // constrained: behind the penalties (in place on pen_out then), the rows' automata advance by the consumed token and mask the row; the pairs of
+    // the greedy pick are this launch's, which replace the penalty launch's
+    if (con != nullptr) {
+        VILA_TRY(launch_constrain(pick_src, m.vocab, n, m.vocab, *con, token, pen_out, m.vocab, PICK_SLICES, sampling != nullptr ? nullptr : pick_v,
+                                  sampling != nullptr ? nullptr : pick_i, s));
+        pick_src = pen_out;
+    }
     if (sampling != nullptr)
         return launch_sample_batch(pick_src, m.vocab, n, m.vocab, *sampling, 1, pos, token, sampling_ws, nullptr, pos, out_ids, n_out, max_out, s);
-    if (pen == nullptr) {
+    if (pen == nullptr && con == nullptr) {
         hipLaunchKernelGGL(bdec_pick1_kernel, dim3(PICK_SLICES, n), dim3(256), 0, s, logits, m.vocab, pick_v, pick_i);
         VILA_LAUNCH_CHECK();
     }

@@ -95,6 +95,12 @@ constexpr int PEN_PICK_SLICES = 32;      // = decode_batch.hip's PICK_SLICES
 constexpr int PEN_SOLO_SLICES = 256;     // the batch-1 step: one block per CU, merged by launch_argmax_pick_advance
 int launch_penalize(const float* logits, int64_t ld, int n, int vocab, const Penalties& p, const int64_t* token, float* out, int64_t ld_out, int n_slices,
                     float* pick_v, int* pick_i, hipStream_t s);
+// structured output (constrain.hip): a token-class automaton per row behind the penalties and in front of the pick.  state[r] < 0 = unconstrained row;
+// token (nullable: no advance) = the token the step consumes; out may alias logits; pick_v / pick_i as launch_penalize's.  Two launches (one without token).
+constexpr int CON_MAX_CLASSES = 4096;    // = VILA_CONSTRAIN_MAX_CLASSES: one state's table row in LDS
+struct Constraints { int32_t* state; const uint16_t* cls; int64_t ld_cls; const int16_t* next; int64_t ld_next; const int32_t* n_classes; };
+int launch_constrain(const float* logits, int64_t ld, int n, int vocab, const Constraints& c, const int64_t* token, float* out, int64_t ld_out, int n_slices,
+                     float* pick_v, int* pick_i, hipStream_t s);
 // log-probabilities of the chosen token and of the LP_TOP most likely ones from raw logits [n][ld] (logprob.hip): row r writes record rec[r] + rec_bias
 // (rec nullable) of token_lp [n][max_rec] and top_lp / top_id [n][max_rec][LP_TOP] (both or neither); an index outside 0 .. max_rec - 1 writes nothing
 constexpr int LP_TOP = 20;
@@ -226,7 +232,8 @@ size_t bdecode_prefix_workspace_bytes(int H, int F, int QS, int hd, int n, int m
 int bdecode_step(const BDecodeArgs& m, const BLayer* layers, bf16_t* kcache, bf16_t* vcache, int max_ctx, int n_slots, int n, int32_t* pos, int64_t* token,
                  int64_t* out_ids, int32_t* n_out, int max_out, float* logits, void* workspace, size_t workspace_bytes, hipStream_t s,
                  const BLayerW4* qlayers = nullptr, const BatchSampling* sampling = nullptr, void* sampling_ws = nullptr, const BPrefix* prefix = nullptr,
-                 const Penalties* pen = nullptr, float* pen_out = nullptr);   // pen: the pick runs on the penalised rows, written to pen_out [n][vocab]
+                 const Penalties* pen = nullptr, float* pen_out = nullptr,    // pen: the pick runs on the penalised rows, written to pen_out [n][vocab]
+                 const Constraints* con = nullptr);                           // con: ... masked by the rows' automata (behind the penalties), in pen_out as well
 // the verify step (greedy speculative decoding): n rows = n consecutive positions of ONE sequence in ONE slot.  Its attention (attn_decode.hip
 // bdec_attn_shared_kernel) reads the slot's K/V once for all rows; `pos` is the device scalar of the state, row i sees keys 0 .. min(pos + i, max_ctx - 1)
 int bverify_attn_slices(int max_ctx);

@@ -89,7 +89,9 @@ __device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
 __device__ __forceinline__ int smp_draw_wave(const uint64_t* keys, int lane, float inv_temperature, int top_k, float top_p, uint64_t seed, uint32_t counter,
                                              float* __restrict__ prob_out) {
     const uint64_t k = keys[lane];
-    const bool real = k != 0 && lane < top_k;                      // TopK: the k most likely survive
+    // TopK: the k most likely survive.  A -inf candidate (a masked token: constrain.hip; fewer finite entries than top_k) is no candidate: its mass is
+    // zero, but the lane sums of `cum` below are rounded per lane, so it could still win the draw.  Rows without -inf keep their bits.
+    const bool real = k != 0 && lane < top_k && smp_val(k) != -INFINITY;
     const float z = smp_val(k) * inv_temperature, zmax = smp_val(keys[0]) * inv_temperature;
     const float e = real ? __expf(z - zmax) : 0.f;
     const float total = wave_sum(e);
@@ -306,7 +308,7 @@ __global__ __launch_bounds__(SMPL_T) void smp_large_kernel(const float* __restri
         float acc = base; int pick = -1, last = -1;
         for (int i = i0; i < i1; ++i) {
             const float v = logits[i];
-            if (smp_key(v, i) >= T) { last = i; acc += __expf(v * inv_temperature - zmax); if (pick < 0 && u < acc) pick = i; }
+            if (smp_key(v, i) >= T) { if (v != -INFINITY) last = i; acc += __expf(v * inv_temperature - zmax); if (pick < 0 && u < acc) pick = i; }   // (a -inf entry, a masked token, is never the fallback)
         }
         atomicMax(&sh_i, pick >= 0 ? pick : last);               // (at most one chunk contains u; rounding at a chunk edge: the later one wins)
     }

@@ -299,13 +299,21 @@ def _as_i64(u: int) -> int:
 
 
 def _step_symbols(batch: bool, w4: bool, sampled: bool, verify: bool = False, verify_sample: bool = False, prefix: bool = False,
-                  penalized: bool = False) -> Tuple[str, str]:
+                  penalized: bool = False, constrained: bool = False) -> Tuple[str, str]:
     """(step, workspace query) of one decode step variant, composed the way the C ABI names them.  verify: the greedy verify step, whatever `batch`.
     verify_sample: the sampled verify step, whatever `batch`, `sampled` and `verify` — a spelling of its own, since `verify` with `sampled` stays the
     refusal it always was (that pair names the greedy step asked to sample).  prefix: the batched step of a session with a shared prompt prefix
     (its workspace query takes the capacity and has no `_ctx` twin).  penalized: the step with repetition / presence / frequency penalties in front
     of its pick — ONE entry per driver, which takes the int4 layers, the sampling parameters and (batched) the prefix descriptor as nullable arguments,
-    so w4 / sampled / prefix do not change the names."""
+    so w4 / sampled / prefix do not change the names.  constrained: the step with a token automaton per row between the penalties and the pick —
+    ONE entry per driver as well, which takes the penalties as a nullable argument too, so `penalized` does not change the names either."""
+    if constrained:
+        if verify or verify_sample:
+            raise ValueError("the verify steps have no constrained form")
+        if prefix and not batch:
+            raise ValueError("the shared-prefix step is a batched step")
+        return (("vila_llm_decode_step_batch_constrained", "vila_llm_decode_batch_constrained_workspace_bytes") if batch else
+                ("vila_llm_decode_step_constrained", "vila_llm_decode_constrained_workspace_bytes"))
     if penalized:
         if verify or verify_sample:
             raise ValueError("the verify steps have no penalised form")
@@ -624,6 +632,71 @@ class HipQwen2ForCausalLM(_HipModule):
         st.p_freq[slot:slot + 1].fill_(float(freq))
         st.counts[slot].zero_()
 
+    CONSTRAIN_MAX_STATES, CONSTRAIN_MAX_CLASSES = 512, 4096          # the table a session of generate(constraint=) holds per row (batch_open: arguments)
+
+    @staticmethod
+    def _constraint_caps(max_states, max_classes) -> Tuple[int, int]:
+        ms, mc = int(max_states), int(max_classes)
+        cap = int(_lib.load().vila_logits_constrain_max_classes())
+        if not 1 <= ms <= 32767 or not 1 <= mc <= cap:
+            raise ValueError(f"constraints: max_states has to be in 1..32767 and max_classes in 1..{cap} (got {ms}, {mc})")
+        return ms, mc
+
+    @staticmethod
+    def _constraint_state(st, n: int, vocab: int, caps: Tuple[int, int], dev) -> None:
+        """What a session with the `constraints` flag owns: per row the automaton's state (-1 = unconstrained), the class of every token id, the table
+        (max_states x max_classes int16 entries; a row's automaton lies in it row-major with its OWN class count) and the class count.  The automata
+        live here, on the device, never in the session key: one captured graph serves any of them."""
+        ld = (vocab + 3) // 4 * 4                                    # (class rows 8-byte aligned: the launch moves 4 classes per access)
+        st.con_state = torch.full((n,), -1, device=dev, dtype=torch.int32)
+        st.con_cls = torch.zeros((n, ld), device=dev, dtype=torch.int16)
+        st.con_next = torch.full((n, caps[0] * caps[1]), -1, device=dev, dtype=torch.int16)
+        st.con_nc = torch.ones(n, device=dev, dtype=torch.int32)
+        st.con_caps, st.con_auto = caps, [None] * n
+        st.con = _lib.VilaConstraints(st.con_state.data_ptr(), st.con_cls.data_ptr(), ld, st.con_next.data_ptr(), caps[0] * caps[1], st.con_nc.data_ptr())
+
+    def _check_constraint(self, constraint, what: str):
+        from .constrain import Automaton
+        if not isinstance(constraint, Automaton):
+            raise ValueError(f"{what}: constraint has to be a vila_amd.constrain.Automaton (compile_automaton / ConstraintCompiler), got {type(constraint).__name__}")
+        if constraint.vocab != self.lcfg.vocab_size:
+            raise ValueError(f"{what}: the automaton was compiled for a vocabulary of {constraint.vocab}, the model has {self.lcfg.vocab_size} "
+                             "(token_bytes_from_tokenizer(tokenizer, vocab_size=...) pads the tokenizer's)")
+        return constraint
+
+    def _set_constraint(self, st, slot: int, constraint) -> None:
+        """A request starts in row `slot` of a constrained session: None = an unconstrained row (state -1); else the automaton's classes and table go
+        to the row (unless the row holds that very automaton already) and its state to the start.  The host binds the device contents here: the
+        table must fit the row, and every state and class in it lies inside the table by construction (`compile_automaton`)."""
+        if constraint is None:
+            st.con_state[slot:slot + 1].fill_(-1)
+            return
+        a = self._check_constraint(constraint, "constraint")
+        S, Cn = a.n_states, a.n_classes
+        if Cn > st.con_caps[1] or S * Cn > st.con_caps[0] * st.con_caps[1]:
+            raise ValueError(f"constraint: the automaton's table ({S} states x {Cn} classes = {S * Cn} entries) does not fit the session's "
+                             f"{st.con_caps[0] * st.con_caps[1]} table entries per row (max_states x max_classes) with at most {st.con_caps[1]} classes: "
+                             "open it with larger max_states / max_classes")
+        if not (0 <= a.start < S and int(a.next.max()) < S and int(a.cls.max()) < Cn):
+            raise ValueError("constraint: the automaton's table points outside itself")
+        if st.con_auto[slot] is not a:
+            dev = st.con_state.device
+            st.con_auto[slot] = None
+            st.con_cls[slot, :a.vocab].copy_(torch.from_numpy(a.cls.view("int16")).to(dev))
+            st.con_next[slot, :S * Cn].copy_(torch.from_numpy(a.next.reshape(-1)).to(dev))
+            st.con_nc[slot:slot + 1].fill_(Cn)
+            st.con_auto[slot] = a
+        st.con_state[slot:slot + 1].fill_(a.start)
+
+    @staticmethod
+    def _first_constrained(st, slot: int, logits: torch.Tensor) -> torch.Tensor:
+        """The logits a constrained row's FIRST token is chosen from: one eager operator call on the prefill's last row (raw logits [V]) with no
+        token, so the row is masked from its start state, which the first step then advances by that token.  An unconstrained row: `logits`."""
+        if st.con_auto[slot] is None or int(st.con_state[slot].item()) < 0:
+            return logits
+        x = logits.reshape(1, -1).float().contiguous()
+        return ops.logits_constrain(x, st.con_state[slot:slot + 1], st.con_cls[slot:slot + 1], st.con_next[slot:slot + 1], st.con_nc[slot:slot + 1])[0]
+
     @staticmethod
     def _logprob_state(st, n: int, max_rec: int, dev) -> None:
         """What a session with the `logprobs` flag owns: one record per row and step — the chosen token's logprob and all 20 alternatives, whatever a
@@ -702,19 +775,22 @@ class HipQwen2ForCausalLM(_HipModule):
         t, p, i = ops.logprobs(r.last_logits, target_ids.reshape(-1).to(device=dev, dtype=torch.int64).contiguous(), int(top_n))
         return Logprobs(t, p, i.long())
 
-    def _decode_session(self, cache, max_new_tokens: int, sampling=None, penalties: bool = False, logprobs: bool = False):
+    def _decode_session(self, cache, max_new_tokens: int, sampling=None, penalties: bool = False, logprobs: bool = False, constraints=None):
         """Device-resident decode state + workspace (+ captured hipGraph) reused across generate() calls.
         sampling: None (greedy) or (temperature, top_k, top_p, seed) — baked into the captured graph, hence part of the key.
         penalties=True (part of the key; a session without the flag keeps the key it always had): the session steps through
         `vila_llm_decode_step_penalized` and owns the count table and the parameter arrays (`_penalty_state`).
         logprobs=True (part of the key only when set, likewise): `vila_logprobs_f32` runs behind every step, inside the captured graph, and the
-        session owns the records (`_logprob_state`); no launch of the step itself changes."""
+        session owns the records (`_logprob_state`); no launch of the step itself changes.
+        constraints=(max_states, max_classes) (part of the key only when set, likewise): the session steps through `vila_llm_decode_step_constrained`
+        (with its penalties, where it has them, as that entry's nullable argument) and owns the automaton's arrays (`_constraint_state`)."""
         # the seed is NOT part of the key: it lives in a device scalar the sampler reads (VilaSampling.seed_dev), so every sampled request
         # with the same (temperature, top_k, top_p) replays the same captured graph (ADVICE round 2: a fresh seed per call used to drop
         # the graph, the workspace and the weight struct on every sampled request)
         key = (cache.k.data_ptr(), max_new_tokens, *self._weights_key()[:2], None if sampling is None else tuple(sampling[:3]))   # (no int4 pointer: as ever)
         key += (True,) if penalties else ()
         key += ("logprobs",) if logprobs else ()
+        key += ("constraints", *constraints) if constraints else ()
         if self._decode is not None and self._decode.key == key:
             if sampling is not None:
                 self._decode.seed.fill_(_as_i64(sampling[3]))
@@ -731,6 +807,7 @@ class HipQwen2ForCausalLM(_HipModule):
         st.sampling = None
         st.pen = None
         st.lp = None
+        st.con = None
         # the session outlives the call that creates it: built outside inference mode even when the first generate() runs under
         # torch.inference_mode() (llava_arch.py:823), or a later no_grad caller could not update `pos` / `token` in place
         with torch.inference_mode(False):
@@ -739,8 +816,10 @@ class HipQwen2ForCausalLM(_HipModule):
             st.out_ids = torch.zeros(max(max_new_tokens, 1), device=dev, dtype=torch.int64)
             st.n_out = torch.zeros(1, device=dev, dtype=torch.int32)
             st.logits = torch.zeros(self.lcfg.vocab_size, device=dev, dtype=torch.float32)
-            ws_bytes = getattr(lib, _step_symbols(False, False, False, penalized=bool(penalties))[1])
+            ws_bytes = getattr(lib, _step_symbols(False, False, False, penalized=bool(penalties), constrained=bool(constraints))[1])
             st.ws = torch.empty((ws_bytes(C.byref(w.shape), cache.max_ctx),), device=dev, dtype=torch.uint8)
+            if constraints:
+                self._constraint_state(st, 1, self.lcfg.vocab_size, constraints, dev)
             st.seed = torch.zeros(1, device=dev, dtype=torch.int64)          # the sampler's seed (bit pattern of a uint64)
             if penalties:
                 self._penalty_state(st, 1, self.lcfg.vocab_size, dev)
@@ -817,9 +896,15 @@ class HipQwen2ForCausalLM(_HipModule):
         across quantize_w4.  w4: the W4Weights whose int4 layers the step reads, or None; sp: the sampling struct, or None for the greedy pick."""
         px = getattr(st, "px", None)                                    # a session with a shared prompt prefix: its descriptor follows the state
         pen = getattr(st, "pen", None)                                  # a session with the penalties flag: the one entry of its driver, NULLs for what is off
-        if pen is not None:
+        con = getattr(st, "con", None)                                  # a session with the constraints flag: likewise, the penalties nullable too
+        ref = lambda s: None if s is None else C.byref(s)
+        if con is not None:
+            name, _ = _step_symbols(batch, w4 is not None, sp is not None, verify, verify_sample, prefix=px is not None, constrained=True)
+            args = ([C.byref(self._struct()), w4.ptr if w4 is not None else None, C.byref(cache.c), C.byref(st.c)] + ([ref(px)] if batch else []) +
+                    [st.ws.data_ptr(), st.ws.numel(), ref(sp), ref(pen), C.byref(con), ops._stream()])
+            check(getattr(_lib.load(), name)(*args), name)
+        elif pen is not None:
             name, _ = _step_symbols(batch, w4 is not None, sp is not None, verify, verify_sample, prefix=px is not None, penalized=True)
-            ref = lambda s: None if s is None else C.byref(s)
             args = ([C.byref(self._struct()), w4.ptr if w4 is not None else None, C.byref(cache.c), C.byref(st.c)] + ([ref(px)] if batch else []) +
                     [st.ws.data_ptr(), st.ws.numel(), ref(sp), C.byref(pen), ops._stream()])
             check(getattr(_lib.load(), name)(*args), name)
@@ -885,7 +970,7 @@ class HipQwen2ForCausalLM(_HipModule):
         return True
 
     def _batch_session(self, n: int, max_ctx: int, max_new_tokens: int, sampling: bool = False, shared_prefix: bool = False, penalties: bool = False,
-                       logprobs: bool = False):
+                       logprobs: bool = False, constraints=None):
         """sampling=True: the session owns per-row sampling parameters on the device (temperature / top_k / top_p / seed, every row greedy
         until `_batch_set_sampling` says otherwise) and steps through the `_sample` entry points: one captured graph for any mix of rows.
         shared_prefix=True: the cache has one slot more, the prefix slot (index n), and the session owns the shared length and the rows' flags on
@@ -894,17 +979,21 @@ class HipQwen2ForCausalLM(_HipModule):
         `vila_llm_decode_step_batch_penalized` and owns a count row and (rep, pres, freq) per row (`_penalty_state`), every row neutral until
         `_set_penalties` says otherwise.
         logprobs=True (in the key only when set, likewise): `vila_logprobs_f32` runs behind every step and the session owns a record per row and step
-        (`_logprob_state`)."""
+        (`_logprob_state`).
+        constraints=(max_states, max_classes) (in the key only when set, likewise): the session steps through
+        `vila_llm_decode_step_batch_constrained` and owns an automaton per row (`_constraint_state`), every row unconstrained until
+        `_set_constraint` says otherwise."""
         w4 = self._w4_batched()
         if not w4:
             self._require_bf16("the batched decode")
         key = (n, max_ctx, max_new_tokens, bool(sampling), *self._weights_key()) + ((True,) if shared_prefix else ()) + (("penalties",) if penalties else ())
         key += ("logprobs",) if logprobs else ()
+        key += ("constraints", *constraints) if constraints else ()
         if self._bdecode is not None and self._bdecode.key == key:
             return self._bdecode
         self._drop_session("_bdecode")
         dev, lib, w = self.device, _lib.load(), self._struct()
-        st = SimpleNamespace(key=key, graph=None, sampling=bool(sampling), sp=None, px=None, shared_prefix=bool(shared_prefix), pen=None, lp=None)
+        st = SimpleNamespace(key=key, graph=None, sampling=bool(sampling), sp=None, px=None, shared_prefix=bool(shared_prefix), pen=None, lp=None, con=None)
         st.attn_slices = int(lib.vila_decode_batch_slices(int(max_ctx)))     # walking-attention slices the steps of this session launch (0: short form)
         with torch.inference_mode(False):
             st.cache = self.new_cache(max_ctx, n_slots=n + 1 if shared_prefix else n)
@@ -919,7 +1008,10 @@ class HipQwen2ForCausalLM(_HipModule):
             st.out_ids = torch.zeros((n, max(max_new_tokens, 1)), device=dev, dtype=torch.int64)
             st.n_out = torch.zeros(n, device=dev, dtype=torch.int32)
             st.logits = torch.zeros((n, self.lcfg.vocab_size), device=dev, dtype=torch.float32)
-            ws_bytes = getattr(lib, _step_symbols(True, w4, bool(sampling), prefix=bool(shared_prefix), penalized=bool(penalties))[1])
+            ws_bytes = getattr(lib, _step_symbols(True, w4, bool(sampling), prefix=bool(shared_prefix), penalized=bool(penalties),
+                                                  constrained=bool(constraints))[1])
+            if constraints:
+                self._constraint_state(st, n, self.lcfg.vocab_size, constraints, dev)
             if penalties:
                 self._penalty_state(st, n, self.lcfg.vocab_size, dev)
             if logprobs:
@@ -930,7 +1022,7 @@ class HipQwen2ForCausalLM(_HipModule):
                 st.s_top_p = torch.ones(n, device=dev, dtype=torch.float32)
                 st.s_seed = torch.zeros(n, device=dev, dtype=torch.int64)                   # bit patterns of uint64 seeds
                 st.sp = _lib.VilaBatchSampling(st.s_temperature.data_ptr(), st.s_top_k.data_ptr(), st.s_top_p.data_ptr(), st.s_seed.data_ptr())
-            ws_args = (int(bool(shared_prefix)),) if penalties else ()
+            ws_args = (int(bool(shared_prefix)),) if penalties or constraints else ()
             st.ws = torch.empty((ws_bytes(C.byref(w.shape), n, int(max_ctx), *ws_args),), device=dev, dtype=torch.uint8)    # (<= 2048 positions: the size it always had)
         st.c = _lib.VilaDecodeBatch(n, st.pos.data_ptr(), st.token.data_ptr(), st.out_ids.data_ptr(), st.n_out.data_ptr(), max(max_new_tokens, 1),
                                     st.logits.data_ptr())
@@ -970,7 +1062,7 @@ class HipQwen2ForCausalLM(_HipModule):
         st.s_seed[slot:slot + 1].fill_(_as_i64(seed))
 
     def batch_open(self, n_slots: int, max_ctx: int = 2048, max_new_tokens: int = 1024, sampling: bool = False, shared_prefix: bool = False,
-                   penalties: bool = False, logprobs: bool = False):
+                   penalties: bool = False, logprobs: bool = False, constraints: bool = False, max_states: int = 512, max_classes: int = 4096):
         """Open (or re-use) the batched-decode session of `n_slots` rows with its captured step.  sampling=False: the greedy step.  sampling=True:
         the step picks per row from device-resident parameters, so the ONE captured graph serves any mix of greedy and sampled rows
         (`batch_admit(..., sampling=)`); the flag is part of the session key.
@@ -981,15 +1073,25 @@ class HipQwen2ForCausalLM(_HipModule):
         values and every row's token counts live on the device, so the ONE captured graph serves any mix of penalised and plain rows.
         logprobs=True (part of the key as well): every step also records, per row, the RAW log-probability of the token it chose and of the 20 most
         likely ones (`vila_logprobs_f32` behind the step, in the same graph; `batch_logprobs(st, slot)` reads a row's records).  Raw: the model's
-        own distribution, independent of the row's temperature, top-k, top-p and penalties."""
+        own distribution, independent of the row's temperature, top-k, top-p and penalties.
+        constraints=True (part of the key as well, with max_states and max_classes): rows may carry a token automaton (`batch_admit(..., constraint=)`,
+        `vila_amd.constrain`) that holds their reply to a choice list, a regular expression or a JSON schema.  The automata live on the device — per
+        row the class of every token id and a table of max_states x max_classes int16 ENTRIES — so the ONE captured graph serves any mix of
+        constrained and plain rows and any change of automaton.  The two arguments size the table, they do not bound states on their own: an
+        automaton lies in it row-major with its OWN class count, so it fits when states x classes <= max_states x max_classes and classes <=
+        max_classes (an automaton with few classes may have more than max_states states)."""
         if not self._w4_batched():
             self._require_bf16("batch_open")
+        con_caps = self._constraint_caps(max_states, max_classes) if constraints else None
         long_ok = (max_ctx <= 2048 and not shared_prefix) or self._long_batch_group_ok()
         if not (1 <= n_slots <= 16 and 1 <= max_ctx <= self.BATCH_MAX_CTX and long_ok and self.can_batch_decode_step() and
                 (self._w4_batched() or self._qkv_fused())):
             raise ValueError("batch_open: the batched decode step serves 1..16 rows of a head-dim-128 model (bf16, or quantize_w4(batch_decode=True)) "
                              f"with caches <= {self.BATCH_MAX_CTX} positions (beyond 2048: GQA groups of 1, 2, 4, 7 or 8 query heads)")
-        st = self._batch_session(max(n_slots, 2), max_ctx, max_new_tokens, sampling, shared_prefix, penalties, logprobs)
+        st = self._batch_session(max(n_slots, 2), max_ctx, max_new_tokens, sampling, shared_prefix, penalties, logprobs,
+                                 **({} if con_caps is None else dict(constraints=con_caps)))
+        if getattr(st, "con", None) is not None:
+            st.con_state.fill_(-1)                                     # every row starts unconstrained (an idle row never advances)
         def reset():
             st.pos.zero_(); st.n_out.zero_(); st.token.zero_()
             if getattr(st, "pen", None) is not None:
@@ -1064,7 +1166,8 @@ class HipQwen2ForCausalLM(_HipModule):
                 c[:, slot, :, S:P].copy_(c[:, st.prefix_slot, :, S:P])
         return st.staged_logits
 
-    def batch_admit(self, st, slot: int, embeds: torch.Tensor, sampling=None, share: bool = False, first_row: int = 0, penalties=None) -> int:
+    def batch_admit(self, st, slot: int, embeds: torch.Tensor, sampling=None, share: bool = False, first_row: int = 0, penalties=None,
+                    constraint=None) -> int:
         """Prefill ONE sequence [P, H] into KV slot `slot` of the open batch and make the row live: position P, first token = argmax of the
         prefill's last row (returned), output counter 0.  sampling = (temperature, top_k in 1..64, top_p, seed), sampling sessions only: the
         row samples — its parameters go to the device arrays, its first token is drawn from the prefill's last row with counter P - 1 (as the
@@ -1076,7 +1179,14 @@ class HipQwen2ForCausalLM(_HipModule):
         caller that has no embeddings of the prefix (a server that skipped the tower) passes the rest.
         penalties = (repetition, presence, frequency), sessions opened with penalties=True only: the row's picks run on the penalised logits.  The
         row's counts start from zero whatever the slot held before; the first token, chosen from the prefill, is never penalised (nothing has been
-        generated yet).  None = a neutral row."""
+        generated yet).  None = a neutral row.
+        constraint = a `vila_amd.constrain.Automaton`, sessions opened with constraints=True only: its classes and table go to the row, the first
+        token is chosen from the prefill's last row masked from the start state (one eager operator call), and every step advances the state by the
+        token it consumes and masks its pick.  None = an unconstrained row (state -1)."""
+        if constraint is not None:
+            if getattr(st, "con", None) is None:
+                raise ValueError("batch_admit: a constrained row needs a session opened with batch_open(constraints=True)")
+            self._check_constraint(constraint, "batch_admit")
         if penalties is not None:
             penalties = self._check_penalties(*penalties)
             if penalties is not None and getattr(st, "pen", None) is None:
@@ -1113,8 +1223,12 @@ class HipQwen2ForCausalLM(_HipModule):
             seq = torch.full((P,), int(slot), device=dev, dtype=torch.int32)
             cu = torch.tensor([0, P], device=dev, dtype=torch.int32)
             logits = self.prefill_packed(embeds.to(self.dtype), pos, cu, P, cache=st.cache, seq_of_tok=seq, last_rows=last).last_logits[0]
-        first = (ops.argmax(logits) if sampling is None else
-                 ops.sample(logits, sampling[0], sampling[1], sampling[2], sampling[3], counter=last))
+        pick_from = logits
+        if getattr(st, "con", None) is not None:
+            self._set_constraint(st, int(slot), constraint)
+            pick_from = self._first_constrained(st, int(slot), logits)
+        first = (ops.argmax(pick_from) if sampling is None else
+                 ops.sample(pick_from, sampling[0], sampling[1], sampling[2], sampling[3], counter=last))
         if st.sampling:
             self._batch_set_sampling(st, slot, sampling)
         if getattr(st, "pen", None) is not None:
@@ -1140,6 +1254,8 @@ class HipQwen2ForCausalLM(_HipModule):
             idx = torch.tensor(slots, device=st.pos.device, dtype=torch.int64)
             st.pos.index_fill_(0, idx, 0)
             st.n_out.index_fill_(0, idx, 0)
+            if getattr(st, "con", None) is not None:
+                st.con_state.index_fill_(0, idx, -1)                   # an idle row is an unconstrained row
             if st.sampling:
                 st.s_temperature.index_fill_(0, idx, 0.0)              # an idle row is a greedy row
             if getattr(st, "shared_prefix", False):
@@ -1147,7 +1263,7 @@ class HipQwen2ForCausalLM(_HipModule):
                 st.sharers.difference_update(int(s) for s in slots)
 
     def _generate_shared(self, inputs_embeds, n: int, max_new_tokens, eos_token_id, pad_token_id, use_graph: bool, return_logits: bool, sampling,
-                         penalties=None, logprobs=None):
+                         penalties=None, logprobs=None, constraint=None):
         """generate(num_return_sequences=n): ONE prefill of the prompt into the prefix slot of a shared-prefix sampling session, n sharing rows that
         differ in their seeds.  Returns [n, n_new] like `_generate_batch`; return_logits: (ids [n, n_new], logits [n_new, n, V] fp32), eager steps.
         A prompt below 256 positions has no whole chunk to share: nothing goes into the prefix slot and the n rows are ordinary rows of the same
@@ -1158,14 +1274,16 @@ class HipQwen2ForCausalLM(_HipModule):
         x = inputs_embeds[0]
         P, dev = int(x.shape[0]), x.device
         max_ctx = ((P + max_new_tokens + 255) // 256) * 256
+        con_kw = {} if constraint is None else dict(constraints=True, max_states=self.CONSTRAIN_MAX_STATES, max_classes=self.CONSTRAIN_MAX_CLASSES)
+        row_kw = {} if constraint is None else dict(constraint=constraint)      # (every row carries the request's automaton, with a state of its own)
         st = self.batch_open(n, max_ctx, max_new_tokens, sampling=True, shared_prefix=True, penalties=penalties is not None,
-                             **({} if logprobs is None else dict(logprobs=True)))
+                             **({} if logprobs is None else dict(logprobs=True)), **con_kw)
         self.batch_release(st, range(st.pos.numel()))
         if P < 256:
-            first_h = [self.batch_admit(st, j, x, sampling=sampling[j], penalties=penalties) for j in range(n)]
+            first_h = [self.batch_admit(st, j, x, sampling=sampling[j], penalties=penalties, **row_kw) for j in range(n)]
         else:
             self.batch_set_prefix(st, x)
-            first_h = [self.batch_admit(st, j, x, sampling=sampling[j], share=True, penalties=penalties) for j in range(n)]
+            first_h = [self.batch_admit(st, j, x, sampling=sampling[j], share=True, penalties=penalties, **row_kw) for j in range(n)]
         first = torch.tensor(first_h, device=dev, dtype=torch.int64)
         eos_set = _eos_set(eos_token_id, self.lcfg.eos_token_id)
         n_steps = max_new_tokens - 1
@@ -1206,7 +1324,8 @@ class HipQwen2ForCausalLM(_HipModule):
             self.batch_release(st, range(st.pos.numel()))
 
     def _generate_batch(self, inputs_embeds, attention_mask, max_new_tokens, eos_token_id, pad_token_id, use_graph: bool = True,
-                        forced_ids: Optional[torch.Tensor] = None, return_logits: bool = False, sampling=None, penalties=None, logprobs=None):
+                        forced_ids: Optional[torch.Tensor] = None, return_logits: bool = False, sampling=None, penalties=None, logprobs=None,
+                        constraint=None):
         """The padded batch as ONE packed prefill (every row into its own KV-cache slot) + batched decode steps: the weights are streamed
         once per step for all rows.  Returns [B, n_new] right-padded with pad_token_id behind each row's EOS, like HF.
         forced_ids [B, n_new] / return_logits: teacher forcing for the parity tests (eager launches; the ids fed after step t are
@@ -1218,7 +1337,10 @@ class HipQwen2ForCausalLM(_HipModule):
         whose steps count the tokens they consume and pick from the penalised logits; the returned logits stay raw, the returned ids are the ones
         each step chose.
         logprobs: None, or k: the batch runs in a session with the logprobs flag and the call returns (ids, `Logprobs`) with k alternatives per
-        token (not with forced_ids / return_logits)."""
+        token (not with forced_ids / return_logits).
+        constraint: None, or an `Automaton` for every row (or a list with one / None per row): the batch runs in a session with the constraints flag;
+        the first tokens are chosen from the prefill's rows masked from the start states, the returned logits stay raw, the returned ids are the
+        ones each step chose."""
         ops._need(inputs_embeds, dtype=None, name="inputs_embeds")
         if sampling is not None:
             sampling = [None if sp is None else self._check_batch_sampling(sp, "generate(batch_sample=True)") for sp in sampling]
@@ -1236,18 +1358,25 @@ class HipQwen2ForCausalLM(_HipModule):
         last = torch.tensor([c - 1 for c in cu_h[1:]], device=dev, dtype=torch.int32)
         max_ctx = ((max(lens) + max_new_tokens + 255) // 256) * 256
         st = self._batch_session(Bn, max_ctx, max_new_tokens, sampling is not None, penalties=penalties is not None,
-                                 **({} if logprobs is None else dict(logprobs=True)))
+                                 **({} if logprobs is None else dict(logprobs=True)),
+                                 **({} if constraint is None else dict(constraints=self._constraint_caps(self.CONSTRAIN_MAX_STATES, self.CONSTRAIN_MAX_CLASSES))))
         if penalties is not None:
             rows_pen = list(penalties) if isinstance(penalties, list) else [penalties] * Bn
             for b in range(Bn):
                 self._set_penalties(st, b, rows_pen[b])
         r = self.prefill_packed(packed, pos, cu, max(lens), cache=st.cache, seq_of_tok=seq, last_rows=last)
+        pick_from = r.last_logits
+        if constraint is not None:
+            rows_con = list(constraint) if isinstance(constraint, (list, tuple)) else [constraint] * Bn
+            for b in range(Bn):
+                self._set_constraint(st, b, rows_con[b])
+            pick_from = [self._first_constrained(st, b, r.last_logits[b]) for b in range(Bn)]
         if sampling is None:
-            first = torch.cat([ops.argmax(r.last_logits[b]) for b in range(Bn)])
+            first = torch.cat([ops.argmax(pick_from[b]) for b in range(Bn)])
         else:
             ctr = torch.tensor([n - 1 for n in lens], device=dev, dtype=torch.int32)
-            first = torch.cat([ops.argmax(r.last_logits[b]) if sp is None else
-                               ops.sample(r.last_logits[b], sp[0], sp[1], sp[2], sp[3], counter=ctr[b:b + 1]) for b, sp in enumerate(sampling)])
+            first = torch.cat([ops.argmax(pick_from[b]) if sp is None else
+                               ops.sample(pick_from[b], sp[0], sp[1], sp[2], sp[3], counter=ctr[b:b + 1]) for b, sp in enumerate(sampling)])
             for b, sp in enumerate(sampling):
                 self._batch_set_sampling(st, b, sp)
         st.pos.copy_(torch.tensor(lens, dtype=torch.int32))
@@ -1267,7 +1396,7 @@ class HipQwen2ForCausalLM(_HipModule):
                 for t in range(n_steps):
                     self._batch_step(st)
                     step_logits.append(st.logits[:Bn].float().clone())
-                    ids.append(torch.cat([ops.argmax(st.logits[b]) for b in range(Bn)]) if sampling is None and getattr(st, "pen", None) is None else st.token[:Bn].clone())
+                    ids.append(torch.cat([ops.argmax(st.logits[b]) for b in range(Bn)]) if sampling is None and getattr(st, "pen", None) is None and getattr(st, "con", None) is None else st.token[:Bn].clone())
                     if forced_ids is not None and t + 1 < forced_ids.shape[1]:
                         st.token.copy_(forced_ids[:, t + 1].to(dev))
             st.stream.synchronize()
@@ -1277,6 +1406,9 @@ class HipQwen2ForCausalLM(_HipModule):
                 st.pos.copy_(torch.tensor(lens, dtype=torch.int32)); st.n_out.zero_(); st.token.copy_(first)
                 if getattr(st, "pen", None) is not None:
                     st.counts.zero_()                              # the warm-up step outside capture bumped one count per row
+                if constraint is not None:                         # ... and advanced every automaton by its first token
+                    for b in range(Bn):
+                        self._set_constraint(st, b, rows_con[b])
             _capture(st, lambda: self._batch_step(st), restore)
         first_h = first.tolist()
         done_rows = [t in eos_set for t in first_h]
@@ -1316,7 +1448,7 @@ class HipQwen2ForCausalLM(_HipModule):
                  prompt_ids: Optional[torch.Tensor] = None, draft_ids: Optional[torch.Tensor] = None, past_len: Optional[int] = None,
                  prefill_chunk: Optional[int] = None, spec_sample: Optional[bool] = None, num_return_sequences: Optional[int] = None,
                  repetition_penalty: Optional[float] = None, presence_penalty: Optional[float] = None, frequency_penalty: Optional[float] = None,
-                 logprobs: Optional[int] = None, **kw):
+                 logprobs: Optional[int] = None, constraint=None, **kw):
         """`llm.generate(inputs_embeds=, attention_mask=, **generation_kwargs)` as called at llava_arch.py:833 (HF semantics: returns ONLY the
         new tokens, [B, n_new]).  Greedy search or sampling (do_sample: temperature / top_k / top_p, HF order, on the device); explicit
         keyword arguments override `generation_config` (HF GenerationConfig-like: do_sample, temperature, top_k, top_p, max_new_tokens,
@@ -1362,8 +1494,26 @@ class HipQwen2ForCausalLM(_HipModule):
         top-k, top-p and penalties (vLLM's default; `return_logits` is raw as well), computed on the device behind every step, inside the captured
         graph (`vila_logprobs_f32`).  The positions behind a row's EOS (the pads of `ids`) hold 0.0 / -inf / -1.  The session carries a `logprobs`
         flag in its key and always records 20 alternatives, so one graph serves any k.  Served on every path above except speculative decoding
-        (prompt_lookup_num_tokens / draft_ids: the verify steps have no logprob form) and not together with return_logits or forced_ids."""
+        (prompt_lookup_num_tokens / draft_ids: the verify steps have no logprob form) and not together with return_logits or forced_ids.
+        constraint = a `vila_amd.constrain.Automaton` (None = off, today's call): structured output.  The reply is held to the automaton's language —
+        a choice list, a regular expression or a JSON schema compiled over this model's vocabulary (`ConstraintCompiler`).  On the device, between
+        the penalties and temperature / top-k / top-p (where HF runs a caller's logits_processor): every step advances the automaton by the token
+        it consumes and masks the disallowed ids to -inf before the pick (`vila_llm_decode_step[_batch]_constrained`), so a constrained step still
+        replays from one graph; the automaton lives in device arrays, never in a session key.  Greedy or sampled, solo or batched (every row carries
+        the automaton, with a state of its own), bf16 or W4, with batch_sample, num_return_sequences, penalties, logprobs (which stay RAW), cache= /
+        past_len= / prefill_chunk.  return_logits stays raw, and its ids are the ones each step chose.  EOS is allowed exactly where the text is a
+        member of the language; max_new_tokens can still cut the reply before that.  Not served with prompt_lookup_num_tokens / draft_ids /
+        spec_sample (the verify steps have no constrained form) and not with forced_ids (a forced token may leave the language)."""
         self._check_append_args(inputs_embeds, cache, past_len, prefill_chunk)
+        if constraint is not None:
+            self._check_constraint(constraint, "generate")
+            gc_ = generation_config
+            if (prompt_lookup_num_tokens is not None or draft_ids is not None or spec_sample or
+                    (gc_ is not None and (getattr(gc_, "prompt_lookup_num_tokens", None) is not None or getattr(gc_, "spec_sample", None)))):
+                raise ValueError("constraint is not served with speculative decoding (prompt_lookup_num_tokens, draft_ids, spec_sample): the verify "
+                                 "steps have no constrained form")
+            if forced_ids is not None:
+                raise ValueError("constraint is not served with forced_ids: a forced token may leave the language")
         if logprobs is not None:
             if isinstance(logprobs, bool) or not isinstance(logprobs, numbers.Integral) or not 0 <= int(logprobs) <= ops.LOGPROBS_MAX_TOP:
                 raise ValueError(f"`logprobs` has to be None or an integer in 0..{ops.LOGPROBS_MAX_TOP} (the number of top alternatives), but is {logprobs!r}")
@@ -1387,7 +1537,8 @@ class HipQwen2ForCausalLM(_HipModule):
             return self._generate_return_sequences(inputs_embeds, attention_mask, int(num_return_sequences), max_new_tokens, eos_token_id, do_sample,
                                                    temperature, top_k, top_p, seed, pad_token_id, generation_config, use_graph, return_logits,
                                                    forced_ids, cache, streamer, batch_sample, prompt_lookup_num_tokens, draft_ids, past_len, prefill_chunk,
-                                                   penalties, **({} if logprobs is None else dict(logprobs=logprobs)))
+                                                   penalties, **({} if logprobs is None else dict(logprobs=logprobs)),
+                                                   **({} if constraint is None else dict(constraint=constraint)))
         if streamer is not None and inputs_embeds.shape[0] > 1:
             raise ValueError("TextStreamer only supports batch size 1")          # transformers/generation/streamers.py, TextStreamer.put
         do_sample = bool(pick(do_sample, "do_sample", False))
@@ -1431,11 +1582,14 @@ class HipQwen2ForCausalLM(_HipModule):
         pen_kw = {} if penalties is None else dict(penalties=penalties)
         if logprobs is not None:                                       # (keyword only when asked: a call without it makes the calls it always made)
             pen_kw = dict(pen_kw, logprobs=logprobs)
+        if constraint is not None:                                     # (likewise)
+            pen_kw = dict(pen_kw, constraint=constraint)
+        processed = penalties is not None or constraint is not None    # (a constrained greedy batch returns its logits through the batched step too)
         if inputs_embeds.shape[0] > 1 and self._can_batch_decode(inputs_embeds, attention_mask, max_new_tokens, do_sample,
-                                                                 forced_ids if penalties is None else None, return_logits and penalties is None, cache,
+                                                                 forced_ids if not processed else None, return_logits and not processed, cache,
                                                                  batch_sample, top_k):
             if not do_sample:
-                if penalties is None and logprobs is None:
+                if not processed and logprobs is None:
                     return self._generate_batch(inputs_embeds, attention_mask, max_new_tokens, eos_token_id, pad_token_id, use_graph)
                 return self._generate_batch(inputs_embeds, attention_mask, max_new_tokens, eos_token_id, pad_token_id, use_graph, forced_ids,
                                             return_logits, **pen_kw)
@@ -1449,6 +1603,8 @@ class HipQwen2ForCausalLM(_HipModule):
             row_pen = {} if penalties is None else dict(repetition_penalty=penalties[0], presence_penalty=penalties[1], frequency_penalty=penalties[2])
             if logprobs is not None:
                 row_pen = dict(row_pen, logprobs=logprobs)
+            if constraint is not None:
+                row_pen = dict(row_pen, constraint=constraint)
             recs = []
             for b in range(inputs_embeds.shape[0]):
                 m = None if attention_mask is None else attention_mask[b:b + 1]
@@ -1473,7 +1629,7 @@ class HipQwen2ForCausalLM(_HipModule):
 
     def _generate_return_sequences(self, inputs_embeds, attention_mask, n, max_new_tokens, eos_token_id, do_sample, temperature, top_k, top_p, seed,
                                    pad_token_id, gc, use_graph, return_logits, forced_ids, cache, streamer, batch_sample, k_spec, draft_ids, past_len,
-                                   prefill_chunk, penalties=None, logprobs=None):
+                                   prefill_chunk, penalties=None, logprobs=None, constraint=None):
         """generate(num_return_sequences=n): what is served, refused with a ValueError that says so otherwise."""
         pick = lambda v, name, default: v if v is not None else (getattr(gc, name, None) if gc is not None and getattr(gc, name, None) is not None else default)
         what = "num_return_sequences: n samples of ONE prompt over its shared K/V"
@@ -1503,7 +1659,8 @@ class HipQwen2ForCausalLM(_HipModule):
                 for j in range(n)]
         return self._generate_shared(inputs_embeds, n, max_new_tokens, pick(eos_token_id, "eos_token_id", None), pick(pad_token_id, "pad_token_id", None),
                                      use_graph, return_logits, rows, **({} if penalties is None else dict(penalties=penalties)),
-                                     **({} if logprobs is None else dict(logprobs=logprobs)))
+                                     **({} if logprobs is None else dict(logprobs=logprobs)),
+                                     **({} if constraint is None else dict(constraint=constraint)))
 
     @staticmethod
     def _check_append_args(inputs_embeds, cache, past_len, prefill_chunk) -> None:
@@ -1563,22 +1720,29 @@ class HipQwen2ForCausalLM(_HipModule):
         return S, cache, self.prefill_packed(x.to(self.dtype), pos, None, S, cache=cache, last_rows=last), last
 
     def _generate_solo(self, inputs_embeds, attention_mask, max_new_tokens, eos_token_id, sampling, use_graph, return_logits, forced_ids, cache,
-                       streamer, past_len=None, prefill_chunk=None, penalties=None, logprobs=None):
+                       streamer, past_len=None, prefill_chunk=None, penalties=None, logprobs=None, constraint=None):
         """generate() for one sequence: prefill, then the batch-1 step (one hipGraph replay per token, or step by step under `use_graph=False`,
         `return_logits` or `forced_ids`).  sampling: None (greedy) or (temperature, top_k, top_p, seed).
         penalties: None, or (rep, pres, freq): the session carries the penalties flag, its counts start from zero here (a request starts), and the
         ids returned with return_logits are the ones each step chose from the penalised logits.
-        logprobs: None, or k: the session carries the logprobs flag and the call returns (ids, `Logprobs`) with k alternatives per token."""
+        logprobs: None, or k: the session carries the logprobs flag and the call returns (ids, `Logprobs`) with k alternatives per token.
+        constraint: None, or an `Automaton`: the session carries the constraints flag, the automaton starts from its start state here, the first
+        token is chosen from the prefill's row masked from that state, and the ids returned with return_logits are the ones each step chose."""
         S, cache, r, last = self._prefill_one(inputs_embeds, attention_mask, max_new_tokens, cache, None, past_len, prefill_chunk)
         dev = inputs_embeds.device
         eos_set = _eos_set(eos_token_id, self.lcfg.eos_token_id)
         st = self._decode_session(cache, max_new_tokens, sampling, **({} if penalties is None else dict(penalties=True)),
-                                  **({} if logprobs is None else dict(logprobs=True)))
+                                  **({} if logprobs is None else dict(logprobs=True)),
+                                  **({} if constraint is None else dict(constraints=self._constraint_caps(self.CONSTRAIN_MAX_STATES, self.CONSTRAIN_MAX_CLASSES))))
         if penalties is not None:
             self._set_penalties(st, 0, penalties)
+        pick_from = r.last_logits[0]
+        if constraint is not None:
+            self._set_constraint(st, 0, constraint)
+            pick_from = self._first_constrained(st, 0, pick_from)
         # the sampler mixes a device counter into its random number: the decode steps use the position of the token they consume
         # (S, S+1, ...); the first token, drawn from the prefill's logits, uses S - 1
-        first = ops.argmax(r.last_logits[0]) if sampling is None else ops.sample(r.last_logits[0], *sampling, counter=last)
+        first = ops.argmax(pick_from) if sampling is None else ops.sample(pick_from, *sampling, counter=last)
         step_logits = [r.last_logits[0].clone()] if return_logits else None
         if logprobs is not None:
             self._first_logprobs(st, 0, r.last_logits[0], first)
@@ -1592,6 +1756,8 @@ class HipQwen2ForCausalLM(_HipModule):
                 st.pos.fill_(S); st.n_out.zero_(); st.token.copy_(first)
                 if penalties is not None:
                     st.counts.zero_()                              # the warm-up step outside capture bumped the first token's count
+                if constraint is not None:
+                    self._set_constraint(st, 0, constraint)        # ... and advanced the automaton by it
             _capture(st, lambda: self.decode_step(cache, st), restore)
         n_steps = max_new_tokens - 1
         if eager:
@@ -1599,7 +1765,7 @@ class HipQwen2ForCausalLM(_HipModule):
                 self.decode_step(cache, st)
                 if return_logits:
                     step_logits.append(st.logits.clone())
-                    ids.append(ops.argmax(st.logits) if sampling is None and penalties is None else st.token.clone())
+                    ids.append(ops.argmax(st.logits) if sampling is None and penalties is None and constraint is None else st.token.clone())
                 if forced_ids is not None and t + 1 < forced_ids.numel():
                     st.token.copy_(forced_ids[t + 1:t + 2].to(dev))
             if not return_logits:

@@ -351,6 +351,48 @@ def penalize(logits: torch.Tensor, counts: torch.Tensor, repetition: torch.Tenso
 LOGPROBS_MAX_TOP = 20
 
 
+def logits_constrain(logits: torch.Tensor, state: torch.Tensor, cls: torch.Tensor, next: torch.Tensor, n_classes: torch.Tensor,
+                     token: Optional[torch.Tensor] = None, return_pick: bool = False, out: Optional[torch.Tensor] = None):
+    """Structured output on logits [n, V] fp32 (rows may be strided): the launches the constrained decode steps run between the (penalised) logits and
+    the pick.  Row r carries an automaton over token classes (`vila_amd.constrain`): state [n] i32 (device, UPDATED IN PLACE; -1 = the row is
+    unconstrained), cls [n, >= V] int16 / uint16 (the bits of uint16 classes; rows may be strided), next [n, ld] int16 (the row's table, row-major
+    [states][n_classes[r]], an entry < 0 = not allowed), n_classes [n] i32.  token [n] i64 (optional): the token each row consumes — where it lies
+    in 0 .. V - 1 and next[r][s * C + cls[r][t]] >= 0 that entry becomes the row's state first; otherwise the state stays.
+    y[r, i] = x[r, i] where next[r][state * C + cls[r][i]] >= 0, else -inf; an unconstrained row returns x's bits.  out: the tensor to write (it may
+    be `logits` itself).  The caller binds the device contents: states and classes must lie inside the table.
+    -> y [n, V] f32 (and, on request, the greedy pick's first stage as `penalize` returns it; an all -inf row merges to index 0)."""
+    _need(logits, dtype=torch.float32, name="logits")
+    if logits.dim() != 2 or logits.stride(1) != 1:
+        raise ValueError("logits_constrain: logits must be [n, vocab] with contiguous rows")
+    n, V = logits.shape
+    for name, t, dts in (("cls", cls, (torch.int16, torch.uint16)), ("next", next, (torch.int16,))):
+        _need(t, dtype=None, name=name)
+        if t.dtype not in dts or t.dim() != 2 or t.shape[0] != n or t.stride(1) != 1 or t.shape[1] < 1:
+            raise ValueError(f"logits_constrain: {name} must be [{n}, *] {' / '.join(str(d) for d in dts)} with contiguous rows")
+    if cls.shape[1] < V:
+        raise ValueError(f"logits_constrain: cls must hold at least {V} entries per row")
+    for name, t, dt in (("state", state, torch.int32), ("n_classes", n_classes, torch.int32)) + ((("token", token, torch.int64),) if token is not None else ()):
+        _need(t, dtype=dt, name=name)
+        if t.numel() != n or not t.is_contiguous():
+            raise ValueError(f"logits_constrain: {name} must be a contiguous tensor of {n} entries")
+    if out is None:
+        out = torch.empty((n, V), device=logits.device, dtype=torch.float32)
+    else:
+        _need(out, dtype=torch.float32, name="out")
+        if out.dim() != 2 or out.shape != logits.shape or out.stride(1) != 1:
+            raise ValueError("logits_constrain: out must be [n, vocab] fp32 with contiguous rows")
+    import ctypes as C
+    lib = _lib.load()
+    S = int(lib.vila_logits_constrain_slices())
+    pv = torch.empty((n, S), device=logits.device, dtype=torch.float32) if return_pick else None
+    pi = torch.empty((n, S), device=logits.device, dtype=torch.int32) if return_pick else None
+    con = _lib.VilaConstraints(state.data_ptr(), cls.data_ptr(), cls.stride(0) if n > 1 else cls.shape[1], next.data_ptr(),
+                               next.stride(0) if n > 1 else next.shape[1], n_classes.data_ptr())
+    check(lib.vila_logits_constrain_f32(logits.data_ptr(), logits.stride(0) if n > 1 else max(logits.stride(0), V), n, V, C.byref(con), _p(token),
+                                        out.data_ptr(), out.stride(0) if n > 1 else max(out.stride(0), V), _p(pv), _p(pi), _stream()), "logits_constrain")
+    return (out, pv, pi) if return_pick else out
+
+
 def logprobs(logits: torch.Tensor, token: torch.Tensor, top_n: int = 0):
     """Log-probabilities from RAW logits [n, V] fp32 (rows may be strided; n is not limited to 16): for every row the logprob of token[r] (i64,
     device) and the top_n (0..20) most likely ids with theirs, descending, ties towards the lower index.  logprob(t) = x_t - logsumexp(x), all fp32, in

@@ -8,7 +8,9 @@ Mirrors the parts of the reference a client sees:
     (`TextStream` = `transformers.TextIteratorStreamer`'s release rule, fed by `llm.generate(streamer=...)` or by the continuous batcher)
   * `process_image` / `process_images` (llava/mm_utils.py:442-541): every `image_aspect_ratio` mode — resize, pad, dynamic (the NVILA-Lite
     tiler), dynamic_s2 (the NVILA tiler)
-What stays in the reference: conversation templates beyond the Qwen2 chat form, video FILE decoding (OpenCV), structured output (xgrammar).
+What stays in the reference: conversation templates beyond the Qwen2 chat form, video FILE decoding (OpenCV).  Structured output (the reference's
+`response_format`, compiled there with xgrammar) is served by `generate_content(response_format= / guided_choice= / guided_regex=)` and the endpoint's request fields of the same names through a token
+automaton on the device (`vila_amd/constrain.py`); free-form `json_object` is not.
 The tokenizer is whatever the checkpoint ships (`transformers.AutoTokenizer`), handed in by the caller; images are pre-processed the way
 `SiglipImageProcessor` does for NVILA (resize to the tower's resolution, bicubic, rescale 1/255, normalise mean = std = 0.5).
 """
@@ -24,6 +26,7 @@ import re
 import threading
 import time
 import uuid
+from collections import OrderedDict
 from types import SimpleNamespace
 from typing import Any, Dict, Iterator, List, Optional, Sequence, Union
 
@@ -442,11 +445,73 @@ def logprob_entries(tokenizer, toks: Sequence[int], token_logprobs, top_logprobs
     return out
 
 
+_COMPILERS: "OrderedDict[Any, Any]" = OrderedDict()
+_COMPILERS_KEPT = 4              # tokenizers whose compiler (a byte table of the vocabulary and an LRU of automata) is kept; the oldest goes
+STRUCTURED_FIELDS = ("response_format", "guided_choice", "guided_regex")
+
+
+def constraint_compiler(tokenizer, vocab_size: int, eos_token_id=None, max_table: Optional[int] = None, max_classes: Optional[int] = None):
+    """The `ConstraintCompiler` of a tokenizer (byte-level BPE: `token_bytes_from_tokenizer`), kept per (tokenizer, vocabulary, EOS set, caps) with
+    its LRU of compiled automata, as xgrammar's GrammarCompiler keeps its cache.  At most `_COMPILERS_KEPT` are kept, least recently used first out.
+    max_table / max_classes: the caps of the session that will hold the automata (default: `generate`'s)."""
+    from .constrain import MAX_CLASSES, ConstraintCompiler, token_bytes_from_tokenizer
+    eos = tuple(sorted(int(e) for e in _eos_set(_eos_of(tokenizer, eos_token_id)) if 0 <= int(e) < int(vocab_size)))
+    key = (id(tokenizer), int(vocab_size), eos, max_table, max_classes)
+    got = _COMPILERS.get(key)
+    if got is None or got[0] is not tokenizer:           # (the tokenizer is held with its entry, so its id cannot be another object's)
+        got = (tokenizer, ConstraintCompiler(token_bytes_from_tokenizer(tokenizer, vocab_size), eos, max_table=max_table,
+                                             max_classes=MAX_CLASSES if max_classes is None else int(max_classes)))
+    _COMPILERS[key] = got
+    _COMPILERS.move_to_end(key)
+    while len(_COMPILERS) > _COMPILERS_KEPT:
+        _COMPILERS.popitem(last=False)
+    return got[1]
+
+
+def structured_of(gen) -> Dict[str, Any]:
+    """The structured-output fields a request carries, as keywords of `generate_content`: {} for a request that asks for none (absent, None, or a
+    `response_format` of type "text"), which is then served exactly as a request without the fields.  More than one is an error."""
+    from .constrain import response_format_spec
+    asks = {k: gen[k] for k in STRUCTURED_FIELDS if gen.get(k) is not None}
+    if "response_format" in asks and response_format_spec(asks["response_format"]) is None:
+        del asks["response_format"]
+    if len(asks) > 1:
+        raise ValueError(f"structured output: give one of response_format / guided_choice / guided_regex (got {sorted(asks)})")
+    return asks
+
+
+def check_structured_request(gen, stream: bool) -> Dict[str, Any]:
+    """`structured_of(gen)`, refused together with `stream`: a constrained reply is not streamed."""
+    asks = structured_of(gen)
+    if asks and stream:
+        raise ValueError("structured output (response_format / guided_choice / guided_regex) is not served together with `stream`: true")
+    return asks
+
+
+def constraint_of(gen, compiler):
+    """The automaton a request asks for, or None: `response_format` (the reference's ResponseFormat shape: `type` plus `json_schema.schema`; laid
+    out with indent=2, as the reference asks xgrammar), `guided_choice` (a list of strings) or `guided_regex` (a pattern) — one of them.  A
+    compile error (an unsupported schema, `json_object`, a constraint the vocabulary cannot spell) is a ValueError."""
+    from .constrain import response_format_spec
+    spec = response_format_spec(gen.get("response_format"))
+    asked = [k for k, v in (("response_format", spec), ("guided_choice", gen.get("guided_choice")), ("guided_regex", gen.get("guided_regex"))) if v is not None]
+    if len(asked) > 1:
+        raise ValueError(f"structured output: give one of response_format / guided_choice / guided_regex (got {asked})")
+    if not asked:
+        return None
+    if spec is not None:
+        return compiler.json_schema(spec[1], indent=2)
+    if gen.get("guided_choice") is not None:
+        return compiler.choice(list(gen["guided_choice"]))
+    return compiler.regex(gen["guided_regex"])
+
+
 def generate_content(model, tokenizer, prompt: Union[str, Sequence[Any]], max_new_tokens: int = 128, system: Optional[str] = None,
                      eos_token_id=None, device: Optional[str] = None, temperature: float = 0.0, top_p: float = 1.0, top_k: int = 50,
                      seed: Optional[int] = None, streamer=None, prompt_lookup_num_tokens: Optional[int] = None, spec_sample: bool = False,
                      repetition_penalty: Optional[float] = None, presence_penalty: Optional[float] = None,
-                     frequency_penalty: Optional[float] = None, logprobs: Optional[bool] = None, top_logprobs: Optional[int] = None) -> str:
+                     frequency_penalty: Optional[float] = None, logprobs: Optional[bool] = None, top_logprobs: Optional[int] = None,
+                     response_format=None, guided_choice: Optional[Sequence[str]] = None, guided_regex: Optional[str] = None) -> str:
     """Text + images in, decoded reply out — the contract of `LlavaLlamaModel.generate_content` for image / text prompts.
     temperature > 0 samples (server.py:185-187: do_sample = temperature > 0, with the request's top_p and HF's default top_k = 50).
     prompt_lookup_num_tokens=k: speculative decoding with k lookup drafts per step (`llm.generate(prompt_lookup_num_tokens=)`); the reply is
@@ -459,7 +524,19 @@ def generate_content(model, tokenizer, prompt: Union[str, Sequence[Any]], max_ne
     logprobs=True (with top_logprobs = 0..20 alternatives per token): the reply comes back as a `ReplyWithLogprobs` — the same text, with
     `.logprobs`, one OpenAI-layout entry per reply token (`logprob_entries`), cut exactly where the text's tokens are cut: the EOS and what follows
     are dropped.  The numbers are RAW: the model's own distribution, independent of temperature, top_p and penalties (`llm.generate(logprobs=)`).
-    Such a request is not speculated either (the verify step has no logprob form)."""
+    Such a request is not speculated either (the verify step has no logprob form).
+    response_format (the reference's `ResponseFormat`: {"type": "json_schema", "json_schema": {"schema": ...}}, an object or a dict), guided_choice
+    (a list of strings) or guided_regex (a pattern): structured output — the reply is held to the schema (in the layout of
+    `json.dumps(obj, indent=2)`), to one of the strings, or to the pattern, by a token automaton on the device (`llm.generate(constraint=)`,
+    `vila_amd/constrain.py` has the served subsets; `{"type": "json_object"}` is not served).  max_new_tokens can still cut the reply before it is
+    complete.  Such a request is not speculated and not streamed."""
+    asks = check_structured_request(dict(response_format=response_format, guided_choice=guided_choice, guided_regex=guided_regex), streamer is not None)
+    constraint = None
+    if asks:
+        from .modules import HipQwen2ForCausalLM as _Llm
+        constraint = constraint_of(asks, constraint_compiler(tokenizer, model.cfg.llm.vocab_size, eos_token_id,
+                                                             max_table=_Llm.CONSTRAIN_MAX_STATES * _Llm.CONSTRAIN_MAX_CLASSES))
+        prompt_lookup_num_tokens = None
     pen = _penalties_of(dict(repetition_penalty=repetition_penalty, presence_penalty=presence_penalty, frequency_penalty=frequency_penalty))
     n_top = _logprobs_of(logprobs, top_logprobs)
     if pen or n_top is not None:
@@ -480,6 +557,8 @@ def generate_content(model, tokenizer, prompt: Union[str, Sequence[Any]], max_ne
     if streamer is not None:
         gen.update(streamer=streamer)
     gen.update(pen)
+    if constraint is not None:                         # (keyword only when asked, likewise)
+        gen.update(constraint=constraint)
     lp = None
     if n_top is not None:                              # (keyword only when asked: a request without the fields makes the call it always made)
         out, lp = model.generate(input_ids=ids, media=media, media_config=media_config, logprobs=n_top, **gen)
@@ -689,12 +768,20 @@ class HipBatchEngine:
     row's (rep, pres, freq) and a `ContinuousBatcher(penalties=True)` puts penalised requests into rows.
     logprobs=True opens the session with per-row logprob records (`batch_open(logprobs=True)`): every step records the raw log-probability of each
     row's token and of its 20 most likely alternatives, `read_logprobs` turns a row's records into OpenAI-layout entries, and a
-    `ContinuousBatcher(logprobs=True)` puts requests that ask for logprobs into rows."""
+    `ContinuousBatcher(logprobs=True)` puts requests that ask for logprobs into rows.
+    constraints=True opens the session with a token automaton per row (`batch_open(constraints=True, max_states=, max_classes=)`: a table of
+    max_states x max_classes entries per row): `compile_constraint` turns a request's `response_format` / `guided_choice` / `guided_regex` into an
+    automaton (cached per vocabulary), `admit` takes it, and a `ContinuousBatcher(constraints=True)` puts such requests into rows.  compiler: the
+    `ConstraintCompiler` to use in place of the one derived from a byte-level BPE tokenizer."""
 
     def __init__(self, model, tokenizer, n_slots: int = 8, max_ctx: int = 2048, max_new_tokens: int = 1024, eos_token_id=None,
-                 sampling: bool = False, share_prefix: bool = False, min_shared_len: int = 2048, penalties: bool = False, logprobs: bool = False):
+                 sampling: bool = False, share_prefix: bool = False, min_shared_len: int = 2048, penalties: bool = False, logprobs: bool = False,
+                 constraints: bool = False, max_states: int = 512, max_classes: int = 4096, compiler=None):
         self.model, self.tokenizer = model, tokenizer
         self.sampling = bool(sampling)
+        self.constraints = bool(constraints)                # batch_open(constraints=True, max_states=, max_classes=): `admit` takes a row's automaton
+        self.max_states, self.max_classes = int(max_states), int(max_classes)
+        self.compiler = compiler                            # a `ConstraintCompiler` (for a tokenizer that is not byte-level BPE); default: the tokenizer's
         self.logprobs = bool(logprobs)                      # batch_open(logprobs=True): every row's steps leave records for `read_logprobs`
         self.penalties = bool(penalties)                    # batch_open(penalties=True): `admit` takes a row's (rep, pres, freq)
         self.share_prefix = bool(share_prefix)
@@ -719,6 +806,8 @@ class HipBatchEngine:
                 kw["penalties"] = True
             if self.logprobs:
                 kw["logprobs"] = True
+            if self.constraints:
+                kw.update(constraints=True, max_states=self.max_states, max_classes=self.max_classes)
             self.st = llm.batch_open(self.n_slots, self.max_ctx, self.max_new_tokens, **kw)
         return self.st
 
@@ -791,6 +880,20 @@ class HipBatchEngine:
         """Whether a request that asks for logprobs can take a row of this engine's batch."""
         return self.logprobs
 
+    @property
+    def batches_constraints(self) -> bool:
+        """Whether a request with `response_format` / `guided_choice` / `guided_regex` can take a row of this engine's batch."""
+        return self.constraints
+
+    def compile_constraint(self, asks):
+        """The automaton of a request's structured-output fields (`structured_of`), compiled for this engine's vocabulary within its rows' table; a
+        ValueError where the schema or pattern is not served, the vocabulary cannot spell it, or it does not fit."""
+        comp = self.compiler
+        if comp is None:
+            comp = constraint_compiler(self.tokenizer, self.model.cfg.llm.vocab_size, sorted(self.eos), max_table=self.max_states * self.max_classes,
+                                       max_classes=self.max_classes)
+        return constraint_of(asks, comp)
+
     def read_logprobs(self, slot: int, toks: Sequence[int], top_logprobs: int) -> List[Dict[str, Any]]:
         """The OpenAI-layout entries (`logprob_entries`) of the reply tokens `toks` of the request in row `slot`: its first token's record and those
         of its steps (`llm.batch_logprobs`), cut where `toks` is cut.  Before the row is released."""
@@ -818,8 +921,10 @@ class HipBatchEngine:
         e, _, _ = self.model._embed(ids[None].to(dev), media, media_config)
         return e[0]
 
-    def admit(self, slot: int, embeds, sampling=None, share: bool = False, first_row: int = 0, penalties=None) -> int:
+    def admit(self, slot: int, embeds, sampling=None, share: bool = False, first_row: int = 0, penalties=None, constraint=None) -> int:
         kw = {} if sampling is None else dict(sampling=sampling)
+        if constraint is not None:
+            kw.update(constraint=constraint)
         if share:
             kw.update(share=True, first_row=first_row)
         if penalties is not None:
@@ -869,16 +974,21 @@ class ContinuousBatcher:
     logprobs=True (opt-in; needs an engine whose `batches_logprobs` is true, i.e. `HipBatchEngine(logprobs=True)`): a request submitted with
     logprobs=True (and top_logprobs=k) that is otherwise batchable takes a row, and its future resolves to a `ReplyWithLogprobs` whose entries come
     from the row's records (`engine.read_logprobs`).  Without the flag such a request runs solo (`engine.solo` gets the two keywords), exactly as
-    `penalties=` does it.  A request that does not ask is served exactly as before."""
+    `penalties=` does it.  A request that does not ask is served exactly as before.
+    constraints=True (opt-in; needs an engine whose `batches_constraints` is true, i.e. `HipBatchEngine(constraints=True)`): a request submitted
+    with `response_format`, `guided_choice` or `guided_regex` that is otherwise batchable takes a row: its automaton is compiled on the worker thread
+    (`engine.compile_constraint`; a compile error fails that request alone) and handed to `engine.admit`.  Without the flag such a request runs solo
+    (`engine.solo` gets the field).  With a `stream` it is refused.  A request that does not ask is served exactly as before."""
 
     def __init__(self, engine, max_batch: int = 8, chunk: int = 8, batch_sampled: bool = False, share_prefix: bool = False, penalties: bool = False,
-                 logprobs: bool = False):
+                 logprobs: bool = False, constraints: bool = False):
         import queue
         import threading
         self.engine = engine
         self.batch_sampled = bool(batch_sampled) and bool(getattr(engine, "batches_sampled", False))
         self.penalties = bool(penalties) and bool(getattr(engine, "batches_penalties", False))
         self.logprobs = bool(logprobs) and bool(getattr(engine, "batches_logprobs", False))
+        self.constraints = bool(constraints) and bool(getattr(engine, "batches_constraints", False))
         self.share_prefix = bool(share_prefix) and bool(getattr(engine, "shares_prefix", False))
         self._pin_rows = set()                           # the live rows that share the engine's current prefix (`engine.pinned_key`)
         self._seedless = 0
@@ -903,6 +1013,7 @@ class ContinuousBatcher:
         req = SimpleNamespace(prompt=prompt, max_new=int(max_new_tokens), system=system, gen=gen, fut=f, stream=stream)
         try:
             _logprobs_of(gen.get("logprobs"), gen.get("top_logprobs"))     # a bad pair fails the request here, not after its row has run
+            check_structured_request(gen, stream is not None)              # ... and so do two structured-output fields, or one with a stream
         except ValueError as ex:
             self._fail(req, ex)
             return f
@@ -957,7 +1068,14 @@ class ContinuousBatcher:
         """The number of alternatives per token of a request that asks for logprobs, else None."""
         return _logprobs_of(req.gen.get("logprobs"), req.gen.get("top_logprobs"))
 
+    def _row_constraint(self, req):
+        """The automaton of a request that asks for structured output (compiled by the engine, on the worker thread), else None."""
+        asks = structured_of(req.gen)
+        return self.engine.compile_constraint(asks) if asks else None
+
     def _batchable(self, req) -> bool:
+        if not self.constraints and structured_of(req.gen):
+            return False                                                # a constrained request without the flag runs solo
         if not self.penalties and self._row_penalties(req) is not None:
             return False                                                # a penalised request without the flag runs solo
         if not self.logprobs and req.gen.get("logprobs"):
@@ -1088,9 +1206,12 @@ class ContinuousBatcher:
                         pen = self._row_penalties(req)
                         if pen is not None:                            # (keyword only when asked for: a neutral request makes the call it always made)
                             how = dict(how, penalties=pen)
+                        con = self._row_constraint(req)
+                        if con is not None:                            # (likewise)
+                            how = dict(how, constraint=con)
                         first = eng.admit(slot, e, **how) if sampling is None else eng.admit(slot, e, sampling, **how)
-                        if pen is not None:
-                            how = {k: v for k, v in how.items() if k != "penalties"}
+                        if pen is not None or con is not None:
+                            how = {k: v for k, v in how.items() if k not in ("penalties", "constraint")}
                         if how:
                             self._pin_rows.add(slot)
                         row = SimpleNamespace(req=req, toks=[first], read=0, sent=0, closed=False)
@@ -1184,7 +1305,9 @@ def _request_models():
             "ChatCompletionRequest", model=(str, ...), messages=(List[ChatMessage], ...), max_tokens=(Optional[int], 512),
             temperature=(Optional[float], 0.2), top_p=(Optional[float], 0.9), stream=(Optional[bool], False),      # server.py:101-102
             repetition_penalty=(Optional[float], 1.0), presence_penalty=(Optional[float], 0.0), frequency_penalty=(Optional[float], 0.0),
-            logprobs=(Optional[bool], False), top_logprobs=(Optional[int], None))                                  # OpenAI's fields; top_logprobs 0..20
+            logprobs=(Optional[bool], False), top_logprobs=(Optional[int], None),                                  # OpenAI's fields; top_logprobs 0..20
+            # structured output: the reference's ResponseFormat ({"type": "json_schema", "json_schema": {"schema": ...}}), vLLM's guided fields
+            response_format=(Optional[Dict[str, Any]], None), guided_choice=(Optional[List[str]], None), guided_regex=(Optional[str], None))
         _MODELS = (ChatMessage, ChatCompletionRequest)
     return _MODELS
 
@@ -1199,7 +1322,7 @@ def continuous_batching(model) -> bool:
 def create_app(model, tokenizer, model_name: str = "NVILA-8B", batch_window_s: Optional[float] = None, max_batch: int = 8,
                stream_timeout_s: Optional[float] = 600.0, batch_sampled: bool = False, max_ctx: int = 2048,
                prompt_lookup_num_tokens: Optional[int] = None, spec_sample: bool = False, share_prefix: bool = False, penalties: bool = False,
-               logprobs: bool = False):
+               logprobs: bool = False, constraints: bool = False):
     """FastAPI app with the reference's POST /chat/completions (server.py:171-290).  Import-time optional: needs fastapi + pydantic.
     batch_window_s: when set (any value), requests go through a batcher whose ONE worker thread owns the model: `ContinuousBatcher` (greedy
     requests join / leave the batched decode step between steps; sampled ones run solo on the same thread) where the model has the batched
@@ -1226,7 +1349,13 @@ def create_app(model, tokenizer, model_name: str = "NVILA-8B", batch_window_s: O
     entry per reply token (RAW log-probabilities: the model's own distribution, whatever the request's temperature, top_p and penalties); a request
     without the fields gets today's response byte for byte and makes today's calls.  top_logprobs without logprobs, and logprobs together with
     stream (entries on SSE pieces are not served), come back as the usual 500 body.  logprobs=True (ContinuousBatcher only; default off): the
-    batched session records logprobs per row, so such a request takes a row; without it such a request runs solo, as `penalties=` does it."""
+    batched session records logprobs per row, so such a request takes a row; without it such a request runs solo, as `penalties=` does it.
+    The request's `response_format` (the reference's ResponseFormat: {"type": "json_schema", "json_schema": {"schema": ...}}), `guided_choice` (a
+    list of strings) or `guided_regex` (a pattern) holds the reply to the schema (laid out as `json.dumps(obj, indent=2)`), to one of the strings or
+    to the pattern (`generate_content` has the served subsets; `max_tokens` can still cut the reply).  A request without the fields is served exactly
+    as before.  A compile error (`json_object`, an unsupported keyword, a pattern the vocabulary cannot spell), two of the fields at once, and any of
+    them together with `stream` come back as the usual 500 body.  constraints=True (ContinuousBatcher only; default off): the batched session holds
+    an automaton per row, so such a request takes a row; without it such a request runs solo, as `penalties=` does it."""
     from fastapi import FastAPI
     from fastapi.responses import JSONResponse, StreamingResponse
 
@@ -1248,9 +1377,12 @@ def create_app(model, tokenizer, model_name: str = "NVILA-8B", batch_window_s: O
                 kw["penalties"] = True
             if logprobs:
                 kw["logprobs"] = True
+            if constraints:
+                kw["constraints"] = True
             engine = HipBatchEngine(model, tokenizer, **kw)
             batcher = ContinuousBatcher(engine, max_batch=max_batch, batch_sampled=batch_sampled, **(dict(share_prefix=True) if share_prefix else {}),
-                                        **(dict(penalties=True) if penalties else {}), **(dict(logprobs=True) if logprobs else {}))
+                                        **(dict(penalties=True) if penalties else {}), **(dict(logprobs=True) if logprobs else {}),
+                                        **(dict(constraints=True) if constraints else {}))
         else:
             batcher = RequestBatcher(model, tokenizer, window_s=batch_window_s)
     app.state.batcher = batcher
@@ -1312,6 +1444,8 @@ def create_app(model, tokenizer, model_name: str = "NVILA-8B", batch_window_s: O
                 if request.stream:
                     raise ValueError("`logprobs` is not served together with `stream`: true (entries on streamed pieces are not supported)")
                 pen = dict(pen, logprobs=True, top_logprobs=n_top)
+            # structured output likewise; refused with stream before anything runs
+            pen = dict(pen, **check_structured_request({k: getattr(request, k, None) for k in STRUCTURED_FIELDS}, bool(request.stream)))
             loop = asyncio.get_running_loop()
             if request.stream:
                 # server.py:241-270: the reply leaves as it is generated.  The tokens reach a `TextStream` from whoever runs the request (the
