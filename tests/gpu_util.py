@@ -397,3 +397,356 @@ def assert_qkv_outputs(q, kcache, vcache, frame_checks, pos, n: int, ref64, boun
     check_q, check_k, check_v = frame_checks
     check_q(); check_k(pos, n); check_v(pos, n)
     return worst
+
+
+# ---- the SFT operators of vila_amd/csrc/train.hip and the norms of elementwise.hip: per-element references and bounds -------------------------
+# (tests/test_train_bound_cpu.py proves them, tests/test_gpu_train_elements.py uses them).  Every bound has the shape
+#     roundings * 2^-8 * |ref|  +  (1 + 2^-8) * 2^-24 * sum_k c_k |term_k|  +  floor
+# c_k: the number of fp32 roundings term k passes through (reduction depth + single operations), term_k: what the kernel adds for that element.
+# The functions return (ref64, bound64, acc64): acc64 is the middle part alone, which the CPU file compares with the rounding part.
+FTZ = 2.0 ** -126           # v_exp_f32 / v_rcp_f32 flush results below the smallest normal fp32; multiplied by what the result is scaled with
+
+
+def f32(x: float) -> float:
+    """The value a C float argument or literal takes."""
+    return float(torch.tensor(float(x), dtype=torch.float32))
+
+
+def _cdiv(a: int, b: int) -> int:
+    return (a + b - 1) // b
+
+
+def train_bound(ref64, acc64, roundings: int = 1, floor=FTZ):
+    return roundings * BF16_U * ref64.abs() + (1.0 + BF16_U) * FP32_U * acc64 + floor
+
+
+def bf16_round64(v64: torch.Tensor) -> torch.Tensor:
+    return v64.to(torch.bfloat16).double()
+
+
+def bf16_near_tie(v64: torch.Tensor, err64: torch.Tensor):
+    """-> (near, ulp): whether v lies within err of a bf16 rounding tie (an odd multiple of half the spacing at |v|), and that spacing.  Only such
+    an element may come out one inner ulp away when its fp32 value is rounded to bf16 before the next operation."""
+    _, e = torch.frexp(v64.abs().clamp_min(FTZ))
+    ulp = torch.ldexp(torch.ones_like(v64), e - 8)
+    q = v64.abs() / ulp
+    return ((q - q.floor()) - 0.5).abs() * ulp <= err64, ulp
+
+
+def framed_flat(n: int, dtype=torch.bfloat16, device="cuda", guard: int = 64, fill: torch.Tensor = None):
+    """-> (view, check): n contiguous elements between two guards of `guard` elements holding the frame pattern (the view too, unless `fill`);
+    check() asserts both guards intact.  The view is 16-byte aligned when guard * element size is."""
+    buf = torch.empty((n + 2 * guard,), dtype=dtype, device=device)
+    _int_view(buf).fill_(_pattern_of(buf))
+    view = buf[guard:guard + n]
+    if fill is not None:
+        view.copy_(fill.reshape(-1))
+
+    def check():
+        iv = _int_view(buf)
+        for name, part, base in (("before", iv[:guard], -guard), ("past", iv[guard + n:], n)):
+            hit = part != _pattern_of(buf)
+            if bool(hit.any()):
+                raise AssertionError(f"buffer of {n} elements: {int(hit.sum())} elements written {name} it, first at offset {base + int(hit.nonzero()[0])}")
+    return view, check
+
+
+# -- LayerNorm / RMSNorm forward (elementwise.hip) ---------------------------------------------------------------------------------------------
+NORM_FWD_OPS = 8            # behind the reductions: / cols, + eps, rsqrtf (2 roundings), x - mean, * rstd, * w, + b  (elementwise.hip:39-41, 55, 72)
+
+
+def norm_fwd_depth(cols: int) -> int:
+    """Longest chain of fp32 additions of a row sum.  cols <= 1536: norm_wave_kernel<_, 3> (elementwise.hip:266, 278), a lane adds its
+    ceil(nch / 64) chunks as 4 pairs each (lines 120-125: one add for the pair, one into s; chunks past the row add exact zeros), then 6 shuffle
+    levels (lines 113-117).  Wider: norm_kernel / norm_block_lat_kernel, 256 lanes (lines 24-35, 200-206), 6 shuffle levels and the three adds
+    of the four wave sums (common.h:40-45)."""
+    nch = cols // 8
+    lanes, levels = (64, 6) if cols <= 1536 else (256, 9)
+    return 4 * _cdiv(nch, lanes) + 1 + levels
+
+
+def norm_stats64(x64: torch.Tensor, rms: bool, eps: float):
+    """-> mean [R, 1] (0 for RMSNorm), rstd [R, 1], xhat [R, C] in fp64; eps as the C float."""
+    mean = torch.zeros_like(x64[:, :1]) if rms else x64.mean(-1, keepdim=True)
+    rstd = ((x64 - mean).square().mean(-1, keepdim=True) + f32(eps)).rsqrt()
+    return mean, rstd, (x64 - mean) * rstd
+
+
+def layernorm_fwd_bound(x64, w64, b64, eps: float):
+    """y = bf16((x - mean) rstd w + b), one rounding (elementwise.hip:72-75, 158-161, 239-242).  mag = |w| (rstd (|x| + mean|x|) + |xhat|) + |b|:
+    the mean is off by depth 2^-24 mean|x| and x - mean rounds at |x| + |mean|, both scaled by rstd |w|; rstd is off by (depth / 2 + 4) 2^-24 of
+    itself, which scales |w xhat|; b is added last.  Every term passes at most depth + NORM_FWD_OPS roundings.  The effect of the mean's error on
+    the two-pass variance is (dmean / std)^2 < 2^-24 while mean|x| / std < 2^12 / depth (40 at the widest row; the inputs stay below 31)."""
+    mean, rstd, xhat = norm_stats64(x64, False, eps)
+    ref = xhat * w64 + (0.0 if b64 is None else b64)
+    mag = w64.abs() * (rstd * (x64.abs() + x64.abs().mean(-1, keepdim=True)) + xhat.abs()) + (0.0 if b64 is None else b64.abs())
+    acc = (norm_fwd_depth(x64.shape[-1]) + NORM_FWD_OPS) * mag
+    return ref, train_bound(ref, acc), acc
+
+
+def rmsnorm_fwd_bound(x64, w64, eps: float):
+    """y = bf16(w * bf16(x rstd)), HF's two roundings (elementwise.hip:69-70, 155-156, 236-237) -> (ref, bound, acc, near).  The reference rounds
+    in that order.  The product of two bf16 values is exact in fp32, so an element whose inner value x rstd is NOT within the fp32 error
+    (depth + NORM_FWD_OPS) 2^-24 |x rstd| of a rounding tie must meet 2^-8 |ref| alone; a near-tie element may take one inner ulp, |w| ulp, more."""
+    _, rstd, inner = norm_stats64(x64, True, eps)
+    near, ulp = bf16_near_tie(inner, (norm_fwd_depth(x64.shape[-1]) + NORM_FWD_OPS) * FP32_U * inner.abs())
+    ref = w64 * bf16_round64(inner)
+    acc = torch.where(near, w64.abs() * ulp / FP32_U, torch.zeros_like(ref))
+    return ref, train_bound(ref, acc), acc, near
+
+
+# -- LayerNorm / RMSNorm backward (train.hip:301-524) ----------------------------------------------------------------------------------------------
+NORM_BWD_OPS = 12           # single operations behind the reductions of dx: * inv_cols (x 2, inv_cols itself rounded), + eps, rsqrtf (2), x - mean,
+                            # * rstd, xhat * mb, g - ma, - (xhat mb), * rstd and the product g xhat inside sb  (train.hip:423-458)
+
+
+def norm_bwd_route(rows: int, cols: int, rms: bool, aligned: bool = True) -> dict:
+    """The kernel launch_norm_bwd takes (train.hip:498-519) and its depths.  Wave kernel (RMS cols <= 4096, LayerNorm cols <= 1536, 16-byte
+    aligned pointers, cols % 8 == 0): a lane adds 4 pairs per chunk over ceil(nch / 64) chunks (lines 419-423, 439-447), 6 shuffle levels; a
+    wave adds its NB_ROWS = 3 rows into dwacc (lines 459-460), the four waves meet as (a + b) + (c + d) (line 480): blocks of 12 rows.  Generic
+    kernel: a thread adds ceil(cols / 256) elements (lines 334, 348-352), 6 shuffle levels and 3 adds (block_sum4, lines 306-313); a block adds
+    its 8 rows (line 364).  Then colpart_reduce_kernel (lines 240-253): ceil(parts / 4) partials in order, two tree levels, the old value."""
+    wave = aligned and cols % 8 == 0 and ((rms and cols <= 4096) or (not rms and cols <= 1536))
+    parts = _cdiv(rows, 12 if wave else 8)
+    stat = 4 * _cdiv(cols // 8, 64) + 1 + 6 if wave else _cdiv(cols, 256) + 6 + 3
+    return {"wave": wave, "parts": parts, "stat_depth": stat, "dw_depth": (3 + 2 if wave else 8) + _cdiv(parts, 4) + 2 + 1}
+
+
+def norm_bwd_bounds(x64, w64, dy64, eps: float, rms: bool, route: dict, dw_old64=None, db_old64=None):
+    """-> {"dx" / "dw" / "db": (ref, bound, acc)}.  dx = rstd (g - mean(g) - xhat mean(g xhat)), g = dy w (exact in fp32).
+    X = rstd (|x| + mean|x|) + |xhat| is what xhat's own error scales with (the forward's argument; RMSNorm: |xhat|, there is no mean).
+    dx: mag = rstd (|g| + mean|g| + |xhat| mean|g xhat|) plus the carried error of xhat, rstd (|mb| X + |xhat| mean(|g| X)); a term passes at most
+    1.5 reductions (rstd carries half the relative error of its sum, the square root's; mean(g) or mb a whole one) and NORM_BWD_OPS single operations.
+    dw = sum_r dy xhat (+ old): dw_depth roundings on sum_r |dy xhat| (+ |old|), and xhat's error (stat_depth + NORM_FWD_OPS) on sum_r |dy| X.
+    db = sum_r dy (+ old): dw_depth roundings on sum_r |dy| (+ |old|)."""
+    mean, rstd, xhat = norm_stats64(x64, rms, eps)
+    g = dy64 * w64
+    ma = torch.zeros_like(mean) if rms else g.mean(-1, keepdim=True)
+    mb = (g * xhat).mean(-1, keepdim=True)
+    X = xhat.abs() if rms else rstd * (x64.abs() + x64.abs().mean(-1, keepdim=True)) + xhat.abs()
+    dx = rstd * (g - ma - xhat * mb)
+    mag = rstd * (g.abs() + (0.0 if rms else g.abs().mean(-1, keepdim=True)) + xhat.abs() * (g * xhat).abs().mean(-1, keepdim=True)
+                  + mb.abs() * X + xhat.abs() * (g.abs() * X).mean(-1, keepdim=True))
+    acc_dx = (1.5 * route["stat_depth"] + NORM_BWD_OPS) * mag
+    out = {"dx": (dx, train_bound(dx, acc_dx), acc_dx)}
+    dw = (dy64 * xhat).sum(0) + (0.0 if dw_old64 is None else dw_old64)
+    acc_dw = route["dw_depth"] * ((dy64 * xhat).abs().sum(0) + (0.0 if dw_old64 is None else dw_old64.abs())) \
+        + (route["stat_depth"] + NORM_FWD_OPS) * (dy64.abs() * X).sum(0)
+    out["dw"] = (dw, train_bound(dw, acc_dw), acc_dw)
+    if not rms:
+        db = dy64.sum(0) + (0.0 if db_old64 is None else db_old64)
+        acc_db = route["dw_depth"] * (dy64.abs().sum(0) + (0.0 if db_old64 is None else db_old64.abs()))
+        out["db"] = (db, train_bound(db, acc_db), acc_db)
+    return out
+
+
+# -- cross entropy (train.hip:531-573) -----------------------------------------------------------------------------------------------------------
+CE_IGNORE = -100
+
+
+def ce_bounds(z64: torch.Tensor, labels: torch.Tensor, scale: float, loss0: float = 0.0):
+    """z64 [n, V]: the fp32 logits as fp64 -> (dref, dbound, dacc, loss_ref, loss_bound).  dz = bf16((softmax(z) - onehot) scale), rows with an
+    ignored label exactly 0 (their bound is 0).  p = e / sum: e = __expf(z - m) is off by (|z - m| + 3) 2^-24 of itself (the subtraction's
+    rounding and the product with log2 e move the exponent by |z - m| 2^-24 each way at most, v_exp_f32 is good to 2 * 2^-24; line 546), the sum
+    by the p-weighted mean of that plus its depth ceil(V / 256) + 6 + 3 (lines 546-547), then 1 / sum, * inv, - 1, * scale (lines 548-553): 4
+    more.  The one-hot term enters through the rounding of p - 1 and of the scaling: 2 * 2^-24 |p - onehot|.
+    loss = loss0 + sum_r (m + log(sum) - z[label]) scale in fp32 (lines 555, 558-564): each row's three terms pass 4 operations (logf at 2
+    roundings) and log(sum) carries the sum's relative error as an absolute one; the ordered sum has depth ceil(n / 256) + 6 + 3 + 1."""
+    n, V = z64.shape
+    s = f32(scale)
+    valid = labels != CE_IGNORE
+    lab = labels.clamp_min(0)
+    m = z64.max(-1, keepdim=True).values
+    d = (z64 - m).abs()
+    e = torch.exp(z64 - m)
+    tot = e.sum(-1, keepdim=True)
+    p = e / tot
+    onehot = torch.zeros_like(p).scatter_(1, lab[:, None], 1.0)
+    sum_rel = (p * (d + 3.0)).sum(-1, keepdim=True) + (_cdiv(V, 256) + 9)
+    vm = valid[:, None].to(z64.dtype)
+    dref = (p - onehot) * s * vm
+    dacc = abs(s) * (p * (d + 3.0 + sum_rel + 4.0) + 2.0 * (p - onehot).abs()) * vm
+    dbound = train_bound(dref, dacc, floor=2 * FTZ) * vm
+    zl = z64.gather(1, lab[:, None])
+    rows = (m + tot.log() - zl) * s * vm
+    loss_ref = f32(loss0) + float(rows.sum())
+    mag = abs(f32(loss0)) + float(((m.abs() + tot.log().abs() + zl.abs()) * abs(s) * vm).sum())
+    loss_bound = FP32_U * ((_cdiv(n, 256) + 10 + 4) * mag + float((sum_rel * abs(s) * vm).sum()))
+    return dref, dbound, dacc, loss_ref, loss_bound
+
+
+# -- GELU (tanh and erf forms), SwiGLU and their backwards (train.hip:57-149, common.h:53-61) ------------------------------------------------------
+GELU_K0, GELU_K1 = f32(0.7978845608028654), f32(0.044715)
+ERF_C, PDF_C = f32(0.7071067811865476), f32(0.3989422804014327)
+ERF_ULPS = 8.0              # erff is taken as good to 4 ulp = 8 * 2^-24 of its value (the device library's polynomial forms are within a few
+                            # ulp); the figure matters only where 1 + erf cancels, below z = -3.5, and is an assumption, not a count
+SAT = 20.0                  # 2 e^-20 = 4.2e-9 < 2^-25 = 3.0e-8, with room for E's own error: above it 1.f + __expf(-u) is 1.f exactly and
+                            # v_rcp_f32(1.f) = 1.f (a power of two); below -SAT 2 s - 1 rounds to -1.f exactly (half the spacing there is 2^-25)
+
+
+def _sigmoid_err(u64):
+    """s = 1 / (1 + E), E = __expf(-u) -> (s, relative fp32 error of s in units of 2^-24 for a correctly rounded or 1-ulp reciprocal).  E is off by
+    (|u| + 2) 2^-24 of itself (silu_f_rel_err's argument), which reaches s times E / (1 + E) = 1 - s; the sum and the reciprocal / division add 6."""
+    s = 1.0 / (1.0 + torch.exp(-u64))
+    return s, (u64.abs() + 2.0) * (1.0 - s) + 6.0
+
+
+def _gelu_tanh_u(x64):
+    """u2 = 2 k0 (x + k1 x^3) (common.h:57, train.hip:59) and the relative error of its fp32 value in 2^-24: 5 operations, no cancellation."""
+    return 2.0 * GELU_K0 * (x64 + GELU_K1 * x64 * x64 * x64), 5.0
+
+
+def gelu_tanh_fwd_bound(x64):
+    """y = bf16(x * rcp(1 + __expf(-u2))) (common.h:53-59).  u2's relative error 5 * 2^-24 is an absolute one of the exponent, 5 |u2| 2^-24, so E is
+    off by (6 |u2| + 2) 2^-24 of itself; then as _sigmoid_err, and the product with x."""
+    u2, ur = _gelu_tanh_u(x64)
+    s = 1.0 / (1.0 + torch.exp(-u2))
+    ref = x64 * s
+    acc = (((ur + 1.0) * u2.abs() + 2.0) * (1.0 - s) + 7.0) * ref.abs()
+    return ref, train_bound(ref, acc, floor=FTZ * (1.0 + x64.abs())), acc
+
+
+def _one_plus_erf(a64):
+    """1 + erf(a) without cancellation in fp64."""
+    return torch.where(a64 < 0, torch.special.erfc(-a64), 1.0 + torch.erf(a64))
+
+
+def gelu_erf_fwd_bound(x64):
+    """y = bf16(0.5 x (1 + erff(x c))) (common.h:60).  erff's value is off by ERF_ULPS 2^-24 |erf| and, through its argument's rounding, by
+    erf'(a) |a| 2^-24 <= 0.49 * 2^-24; the sum rounds once: 10.5 * 2^-24 (1 + |erf|) at most, an ABSOLUTE error where 1 + erf cancels (x < -4);
+    two products follow.  mag = 0.5 |x| (1 + |erf|), 13 roundings."""
+    a = x64 * ERF_C
+    ref = 0.5 * x64 * _one_plus_erf(a)
+    acc = 13.0 * 0.5 * x64.abs() * (1.0 + torch.erf(a).abs())
+    return ref, train_bound(ref, acc), acc
+
+
+def gelu_tanh_bwd_bound(x64, dy64):
+    """dz = bf16(dy (A + B)), A = 0.5 (1 + t), B = 0.5 x (1 - t^2) k0 (1 + 3 k1 x^2), t = 2 s - 1, s = rcp(1 + __expf(-u2)) (train.hip:57-61).
+    dt = 2 s r_s + 2^-24 |t|; d(1 - t^2) = 2 |t| dt + 2^-24 (t^2 + |1 - t^2|); the other factors of B pass 7 roundings; A, the sum and the product
+    with dy 2 each.  Where |u2| >= SAT the fp32 t is exactly +-1 (SAT's comment; 2 s < 2^-25 rounds 2 s - 1 to -1), so 1 - t * t and, at -1, A are
+    exactly 0: the error there is the true value of what vanished, not a rounding scaled by C ~ x^3.  The sweep stops at |z| = 2^16; from |z| ~ 5e19 on the factor
+    1 + 3 k1 x^2 overflows against 1 - t^2 = 0 (0 * inf): outside the contract (train.hip's comment at dgelu_tanh)."""
+    u2, ur = _gelu_tanh_u(x64)
+    s = 1.0 / (1.0 + torch.exp(-u2))
+    r_s = ((ur + 1.0) * u2.abs() + 2.0) * (1.0 - s) + 6.0
+    t = 2.0 * s - 1.0
+    one_m_t2 = 4.0 * s * (1.0 - s)
+    C = (0.5 * x64 * GELU_K0 * (1.0 + 3.0 * GELU_K1 * x64 * x64)).abs()
+    A, B = s, C * one_m_t2 * torch.sign(x64)
+    ref = dy64 * (A + B)
+    sat = u2.abs() >= SAT
+    dt = 2.0 * s * r_s + t.abs()                                        # in units of 2^-24
+    d_q = torch.where(sat, one_m_t2 / FP32_U, 2.0 * t.abs() * dt + t * t + one_m_t2)
+    d_A = torch.where(sat & (u2 < 0), A / FP32_U, 0.5 * dt + 2.0 * A)
+    acc = dy64.abs() * (d_A + C * d_q + 8.0 * B.abs() + 2.0 * (A + B).abs())
+    return ref, train_bound(ref, acc, floor=FTZ * (1.0 + x64.abs()) * dy64.abs()), acc
+
+
+def gelu_erf_bwd_bound(x64, dy64):
+    """dz = bf16(dy (0.5 (1 + erff(x c)) + x pdf_c __expf(-0.5 x^2))) (train.hip:62-64).  mag = |dy| (0.5 (1 + |erf|) + |x| pdf(x)).  The first
+    term passes 13 roundings (gelu_erf_fwd_bound's 10.5, the sum, the product with dy); the exponent -0.5 x^2 log2 e rounds twice, x^2 * 2^-24 of
+    the exponential, v_exp_f32 2, the products, the sum and dy 4: x^2 + 6."""
+    a = x64 * ERF_C
+    A = 0.5 * _one_plus_erf(a)
+    B = x64 * PDF_C * torch.exp(-0.5 * x64 * x64)
+    ref = dy64 * (A + B)
+    acc = dy64.abs() * (13.0 * 0.5 * (1.0 + torch.erf(a).abs()) + (x64 * x64 + 6.0) * B.abs())
+    return ref, train_bound(ref, acc, floor=FTZ * (1.0 + x64.abs()) * dy64.abs()), acc
+
+
+def silu_mul_fwd_bound(g64, u64):
+    """a = bf16(bf16(silu_f(g)) * u), HF's two roundings (train.hip:118) -> (ref, bound, acc, near).  As rmsnorm_fwd_bound: the reference rounds the
+    inner value first, the product is exact in fp32, and only an element whose silu(g) lies within silu_f_rel_err(|g|) |silu(g)| of a rounding
+    tie may take one inner ulp, |u| ulp, more.  (A flushed denormal intermediate moves the inner value by at most 2^-126, and only where it is
+    itself below 2^-118, where an inner ulp is below 2^-126: the floor FTZ (1 + |g|) (1 + |u|) carries both.)"""
+    inner = g64 / (1.0 + torch.exp(-g64))
+    near, ulp = bf16_near_tie(inner, silu_f_rel_err(g64.abs()) * inner.abs())
+    ref = bf16_round64(inner) * u64
+    acc = torch.where(near, u64.abs() * ulp / FP32_U, torch.zeros_like(ref))
+    return ref, train_bound(ref, acc, floor=FTZ * (1.0 + g64.abs()) * (1.0 + u64.abs())), acc, near
+
+
+def silu_mul_bwd_bound(g64, u64, da64):
+    """dg = bf16(da u dsilu(g)), du = bf16(da silu_f(g)) (train.hip:122-137) -> ((dg ref, bound, acc), (du ref, bound, acc)).
+    dsilu = s (1 + x (1 - s)), s = 1.f / (1.f + __expf(-x)): ds = s r_s; d(1 - s) = ds + 2^-24 (1 - s); d(x (1 - s)) = |x| d(1 - s) + 2^-24 |x (1 - s)|;
+    the sum and the last product round once each.  Where x >= SAT the fp32 s is exactly 1 (SAT's comment) and 1 - s exactly 0: there
+    ds = d(1 - s) = 1 - s, the true value of what vanished.  da * u is exact in fp32; its product with dsilu rounds once.
+    du: silu_f_rel_err and the product."""
+    x = g64
+    s, r_s = _sigmoid_err(x)
+    sat = x >= SAT
+    ds = torch.where(sat, (1.0 - s) / FP32_U, s * r_s)                   # units of 2^-24
+    d1s = torch.where(sat, (1.0 - s) / FP32_U, ds + (1.0 - s))
+    inner = 1.0 + x * (1.0 - s)
+    d_inner = x.abs() * d1s + (x * (1.0 - s)).abs() + inner.abs()
+    dsilu = s * inner
+    d_dsilu = ds * inner.abs() + s * d_inner + dsilu.abs()
+    dg = da64 * u64 * dsilu
+    acc_g = (da64 * u64).abs() * (d_dsilu + dsilu.abs())
+    floor = FTZ * (1.0 + x.abs())
+    silu = x * s
+    du = da64 * silu
+    acc_u = (silu_f_rel_err(x.abs()) / FP32_U + 1.0) * du.abs()
+    return (dg, train_bound(dg, acc_g, floor=floor * (1.0 + x.abs()) * (da64 * u64).abs() + FTZ), acc_g), \
+           (du, train_bound(du, acc_u, floor=floor * da64.abs() + FTZ), acc_u)
+
+
+# -- AdamW (train.hip:678-800) ---------------------------------------------------------------------------------------------------------------------
+def adamw_bounds(p64, m64, v64, g64, lr, b1, b2, eps, wd, step: int, grad_scale: float):
+    """fp64 AdamW on the C float arguments, the bias corrections formed in fp64 -> {"master" / "m" / "v": (ref, bound)} (fp32 outputs: no bf16
+    rounding; param is bf16(master) and compared bit for bit by the caller).  adamw_one (train.hip:678-684):
+      g = bf16 grad * grad_scale: 1 rounding.  m' = b1 m + (1 - b1) g: 4 on |b1 m| + |(1 - b1) g| (1.f - b1 is exact for b1 in [0.5, 1)).
+      v' = b2 v + (1 - b2) g^2: 5 (g enters twice).  p1 = p (1 - lr wd): 3 on |p|.
+      bc = 1 - powf(b, step) on the host (train.hip:719): powf within 1 ulp = 2 * 2^-24 of b^step, the subtraction rounds once: (2 b^step / bc + 1) 2^-24
+      of bc, a large relative error at step 1 and 2 of b2 = 0.999 that the bound has to carry.
+      den = sqrtf(v' / bc2) + eps: sqrt halves the relative error of its argument (dv / v' + bc2's + the division), sqrtf and the sum round once each.
+      upd = lr (m' / bc1) / den: m's absolute error scaled by lr / (bc1 den), and |upd| times (bc1's + den's relative error + 4).
+      p' = p1 - upd rounds at |p'|."""
+    lr, b1, b2, eps, wd, gs = (f32(a) for a in (lr, b1, b2, eps, wd, grad_scale))
+    g = g64 * gs
+    m1a, m1b = b1 * m64, (1.0 - b1) * g
+    v1a, v1b = b2 * v64, (1.0 - b2) * g * g
+    m1, v1 = m1a + m1b, v1a + v1b
+    dm = 4.0 * (m1a.abs() + m1b.abs())                                  # units of 2^-24
+    dv = 5.0 * (v1a.abs() + v1b.abs())
+    bc1, bc2 = 1.0 - b1 ** step, 1.0 - b2 ** step
+    r_bc1, r_bc2 = 2.0 * b1 ** step / bc1 + 1.0, 2.0 * b2 ** step / bc2 + 1.0
+    root = (v1 / bc2).sqrt()
+    den = root + eps
+    d_den = root * (0.5 * (dv / v1.clamp_min(1e-300) + r_bc2 + 1.0) + 1.0) + den
+    upd = lr * (m1 / bc1) / den
+    d_upd = lr / (bc1 * den) * dm + upd.abs() * (r_bc1 + d_den / den + 4.0)
+    p1 = p64 * (1.0 - lr * wd)
+    pn = p1 - upd
+    d_p = 3.0 * p64.abs() + d_upd + pn.abs()
+    return {"master": (pn, train_bound(pn, d_p, roundings=0, floor=FTZ)), "m": (m1, train_bound(m1, dm, roundings=0, floor=FTZ)),
+            "v": (v1, train_bound(v1, dv, roundings=0, floor=FTZ))}
+
+
+# -- scatter_add_rows and depth_to_space: exact references ---------------------------------------------------------------------------------------
+def scatter_add_rows_ref(src: torch.Tensor, dst: torch.Tensor, ids: torch.Tensor) -> torch.Tensor:
+    """The documented order (train.hip:576-611): for every id its first occurrence, the later occurrences added in ascending order in fp32, then
+    old + sum rounded once.  -> the new table (dst is not modified)."""
+    out = dst.clone()
+    order = {}
+    for i, r in enumerate(ids.tolist()):
+        order.setdefault(int(r), []).append(i)
+    for r, occ in order.items():
+        a = src[occ[0]].float()
+        for j in occ[1:]:
+            a = a + src[j].float()
+        out[r] = (dst[r].float() + a).to(torch.bfloat16)
+    return out
+
+
+def depth_to_space_index_map(B: int, g: int, k: int) -> torch.Tensor:
+    """[B, g * g] int64: for every source cell (b, sy, sx) the flat index into dy viewed as [B * gd * gd * k * k] cells of C channels, obtained
+    by sending the cell numbers 1 .. through oracle.vila_oracle.downsample_block (0 marks its zero padding)."""
+    from oracle.vila_oracle import downsample_block
+    idx = torch.arange(1, B * g * g + 1, dtype=torch.float64).reshape(B, g * g, 1)
+    y = downsample_block(idx, k).reshape(-1).long()                      # [B * gd * gd * k * k]: the source cell (+1) each dy cell came from
+    pos = torch.full((B * g * g + 1,), -1, dtype=torch.int64)
+    pos[y] = torch.arange(y.numel())
+    assert bool((pos[1:] >= 0).all())
+    return pos[1:].reshape(B, g * g)

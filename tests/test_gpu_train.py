@@ -1,6 +1,8 @@
 """GPU parity tests of the SFT step: backward operators against PyTorch fp32 autograd of the same
 op, and the whole forward+backward (ViT + projector + packed LLM + loss) against autograd through the CPU oracle.
-Tolerances: operator gradients rel-L2 <= 1.5e-2 (bf16 in/out); model gradients cosine >= 0.999 (SURVEY 8c's stated bound,
+Tolerances: operator gradients rel-L2 <= 1.5e-2 (bf16 in/out) here, one number per tensor at one or a few shapes; the per-element bounds of
+the norms, cross entropy, scatter_add_rows, depth_to_space, the activations and AdamW at every dispatch edge, in framed buffers, are in
+tests/test_gpu_train_elements.py (proved on the CPU in tests/test_train_bound_cpu.py); model gradients cosine >= 0.999 (SURVEY 8c's stated bound,
 `gpu_util.GRAD_COS_MIN`; per-tensor exceptions are listed in GRAD_COS_EXCEPTIONS with the measured value and the reason) and
 rel-L2 <= 6e-2 per tensor (bf16 GPU vs fp32 CPU through ~10 layers), loss |delta| <= 1e-2 relative."""
 import pytest

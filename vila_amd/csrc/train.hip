@@ -51,6 +51,9 @@ int launch_transpose(const bf16_t* in, bf16_t* out, int R, int C, int64_t ldi, i
 #define EW_GRID(total) ((int)(((total) + 255) / 256 < 8192 ? ((total) + 255) / 256 : 8192))
 #define EW_LOOP(total) for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < (total); i += (int64_t)gridDim.x * blockDim.x)
 
+// Contract: finite z; checked element by element for every bf16 z with |z| <= 2^16 (tests/test_gpu_train_elements.py), where t is exactly +-1
+// from |u| ~ 20 on and the second term exactly 0.  From |z| ~ 5e19 on 3 k1 x^2 overflows against 1 - t^2 = 0 and 0 * inf gives NaN: outside
+// the contract (no activation of a bf16 model is of that size).
 __device__ __forceinline__ float dgelu_tanh(float x) {
     const float k0 = 0.7978845608028654f, k1 = 0.044715f;
     const float t = 2.f * __builtin_amdgcn_rcpf(1.f + __expf(-2.f * k0 * (x + k1 * x * x * x))) - 1.f;      // tanh(u) = 2 sigmoid(2u) - 1 (common.h gelu_tanh_f)
