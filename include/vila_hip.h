@@ -732,6 +732,32 @@ int vila_llm_decode_step_batch_constrained(const VilaLlmWeights* w, const VilaLl
                                            const VilaBatchSampling* sp /*nullable*/, const VilaPenalties* pen /*nullable*/, const VilaConstraints* con,
                                            vila_stream_t stream);
 
+/* Any top_k for the rows of the batched sampler (opt-in; vila_amd/csrc/sample.hip): the entries above serve top_k in 1..64 and clamp anything else;
+ * the entries below also serve top_k = 0 (no top-k filter, HF's meaning: pure top-p sampling) and top_k > 64, per row and from the same device
+ * arrays, so ONE captured hipGraph serves any mix of greedy rows, rows of 1..64 and such rows.  One launch more, of one 1024-thread block per row,
+ * draws every row with temperature > 0 and (top_k == 0 or top_k > 64) by the exact selection of vila_sample_f32 — the predicate by which that
+ * function picks its own path — and every other block of it returns at once.  The contract of VilaBatchSampling extends to them: a sampled row's
+ * token is bit for bit what vila_sample_f32 returns for the same logits row, parameters, seed and counter, for every top_k >= 0.  A negative
+ * top_k is still clamped to 1 and top_p to (0, 1].
+ * vila_sample_batch_any_f32: vila_sample_batch_f32 with that launch (four launches whatever n; the workspace of vila_sample_batch_workspace_bytes).
+ * dist_out (nullable) [n][128] as there; a row drawn by the exact path gets zeros and -1 ids.  dense_out (nullable) [n][ld_dense], ld_dense >= vocab:
+ * such a row's distribution over the vocabulary (what vila_sample_f32 returns in dist_out for it); the other rows' entries are not written. */
+int vila_sample_batch_any_f32(const float* logits, int64_t ld_logits, int n, int vocab, const VilaBatchSampling* sp, const int32_t* counter,
+                              int64_t* out, void* workspace, float* dist_out /*nullable*/, float* dense_out /*nullable*/, int64_t ld_dense,
+                              vila_stream_t stream);
+/* The sampled batched step with that pick.  One entry: qlayers NULL = bf16, else the W4 step; prefix NULL = a plain batch session; pen / con NULL =
+ * no penalties / no automata in front of the pick; sp is required.  One workspace size serves every combination.  The launches in front of the pick
+ * are the plain steps', so st->logits stays raw and keeps the same bits. */
+size_t vila_llm_decode_batch_any_k_workspace_bytes(const VilaLlmShape* s, int n, int max_ctx, int prefix);
+int vila_llm_decode_step_batch_any_k(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers /*[host], nullable*/, const VilaKvCache* cache,
+                                     const VilaDecodeBatch* st, const VilaDecodePrefix* prefix /*nullable*/, void* workspace, size_t workspace_bytes,
+                                     const VilaBatchSampling* sp, const VilaPenalties* pen /*nullable*/, const VilaConstraints* con /*nullable*/,
+                                     vila_stream_t stream);
+/* The sampled verify step with that pick: `sp` of ONE entry per array, read by every row; workspace of vila_llm_decode_verify_sample_workspace_bytes. */
+int vila_llm_decode_step_verify_any_k(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers /*[host], nullable*/, const VilaKvCache* cache,
+                                      const VilaDecodeVerify* st, void* workspace, size_t workspace_bytes, const VilaBatchSampling* sp,
+                                      vila_stream_t stream);
+
 /* Log-probabilities of the chosen token and of its top alternatives (vila_amd/csrc/logprob.hip): the `logprobs` / `top_logprobs` of an OpenAI-style
  * endpoint, HF's `compute_transition_scores`.  For a row x[0 .. vocab - 1] of RAW fp32 logits, all in fp32:
  *   M = max x,  lse = M + log(sum_i exp(x_i - M)),  logprob(t) = x_t - lse          (an -inf entry contributes 0 to the sum)

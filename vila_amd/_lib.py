@@ -322,6 +322,15 @@ PROTOTYPES = {
     "vila_llm_decode_step_batch_constrained": (c_int, [C.POINTER(VilaLlmWeights), C.POINTER(VilaLlmLayerW4), C.POINTER(VilaKvCache), C.POINTER(VilaDecodeBatch),
                                                        C.POINTER(VilaDecodePrefix), c_void_p, c_size_t, C.POINTER(VilaBatchSampling), C.POINTER(VilaPenalties),
                                                        C.POINTER(VilaConstraints), c_void_p]),
+    # ---- any top_k for the rows of the batched sampler ----
+    "vila_sample_batch_any_f32": (c_int, [c_void_p, c_int64, c_int, c_int, C.POINTER(VilaBatchSampling), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                          c_int64, c_void_p]),
+    "vila_llm_decode_batch_any_k_workspace_bytes": (c_size_t, [C.POINTER(VilaLlmShape), c_int, c_int, c_int]),
+    "vila_llm_decode_step_batch_any_k": (c_int, [C.POINTER(VilaLlmWeights), C.POINTER(VilaLlmLayerW4), C.POINTER(VilaKvCache), C.POINTER(VilaDecodeBatch),
+                                                 C.POINTER(VilaDecodePrefix), c_void_p, c_size_t, C.POINTER(VilaBatchSampling), C.POINTER(VilaPenalties),
+                                                 C.POINTER(VilaConstraints), c_void_p]),
+    "vila_llm_decode_step_verify_any_k": (c_int, [C.POINTER(VilaLlmWeights), C.POINTER(VilaLlmLayerW4), C.POINTER(VilaKvCache), C.POINTER(VilaDecodeVerify),
+                                                  c_void_p, c_size_t, C.POINTER(VilaBatchSampling), c_void_p]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -873,7 +873,7 @@ static int blayer_tables(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers,
 static int decode_step_batch_impl(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers, const VilaKvCache* cache, const VilaDecodeBatch* st,
                                   void* workspace, size_t workspace_bytes, const VilaBatchSampling* sp, vila_stream_t stream,
                                   const VilaDecodePrefix* px = nullptr, const Penalties* pen = nullptr, float* pen_out = nullptr,
-                                  const Constraints* con = nullptr) {
+                                  const Constraints* con = nullptr, bool any_k = false) {
     const char* fn = qlayers != nullptr ? "llm_decode_batch_w4" : "llm_decode_batch";
     VILA_REQUIRE(w != nullptr && cache != nullptr && st != nullptr && workspace != nullptr, "%s: NULL argument", fn);
     BTables t{};
@@ -884,7 +884,7 @@ static int decode_step_batch_impl(const VilaLlmWeights* w, const VilaLlmLayerW4*
     const BPrefix bp = px != nullptr ? BPrefix{px->prefix_slot, px->shared_len, px->uses} : BPrefix{};
     return bdecode_step(t.m, t.layers.data(), B(cache->k), B(cache->v), cache->max_ctx, cache->n_slots, st->n, st->pos, st->token, st->out_ids, st->n_out,
                         st->max_out, st->logits, workspace, workspace_bytes, S(stream), qlayers != nullptr ? t.ql.data() : nullptr, sw.sp, sw.ws,
-                        px != nullptr ? &bp : nullptr, pen, pen_out, con);
+                        px != nullptr ? &bp : nullptr, pen, pen_out, con, any_k);
 }
 // the four steps of a prefix session and their workspace sizes (two sizes, greedy and sampled, as above)
 static size_t decode_batch_prefix_ws(const VilaLlmShape* s, int n, int max_ctx, bool sample) {
@@ -979,10 +979,34 @@ extern "C" int vila_llm_decode_step_batch_constrained(const VilaLlmWeights* w, c
     const Constraints Cn{con->state, con->cls, con->ld_cls, con->next, con->ld_next, con->n_classes};
     return decode_step_batch_impl(w, qlayers, cache, st, workspace, head, sp, stream, prefix, pen != nullptr ? &P : nullptr, (float*)((char*)workspace + head), &Cn);
 }
+// The sampled batched step that serves every top_k >= 0 (sample.hip, launch_sample_batch(any_k)): qlayers, prefix, pen and con nullable — bf16 / W4,
+// plain / shared prefix, with or without penalties and automata in one entry; sp is required (the option is the sampled pick's).  One workspace size
+// for all of them, the constrained step's: without pen and con the rows behind the head stay unused.  Everything in front of the pick is the launches
+// of the step without the option, so st->logits holds the same bits.
+extern "C" size_t vila_llm_decode_batch_any_k_workspace_bytes(const VilaLlmShape* s, int n, int max_ctx, int prefix) {
+    return vila_llm_decode_batch_penalized_workspace_bytes(s, n, max_ctx, prefix);
+}
+extern "C" int vila_llm_decode_step_batch_any_k(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers, const VilaKvCache* cache, const VilaDecodeBatch* st,
+                                                const VilaDecodePrefix* prefix, void* workspace, size_t workspace_bytes, const VilaBatchSampling* sp,
+                                                const VilaPenalties* pen, const VilaConstraints* con, vila_stream_t stream) {
+    const char* fn = "llm_decode_batch_any_k";
+    VILA_REQUIRE(w != nullptr && cache != nullptr && st != nullptr && workspace != nullptr && sp != nullptr, "%s: NULL argument", fn);
+    if (pen != nullptr) VILA_TRY(penalties_ok(pen, w->shape.vocab, fn));
+    if (con != nullptr) VILA_TRY(constraints_ok(con, w->shape.vocab, fn));
+    VILA_REQUIRE(st->n >= 1 && st->n <= 16, "%s: 1..16 sequences (got %d)", fn, st->n);
+    VILA_REQUIRE(cache->max_ctx >= 1 && cache->max_ctx <= BDEC_MAX_CTX, "%s: caches up to %d positions (got %d)", fn, BDEC_MAX_CTX, cache->max_ctx);
+    VILA_REQUIRE(workspace_bytes >= vila_llm_decode_batch_any_k_workspace_bytes(&w->shape, st->n, cache->max_ctx, prefix != nullptr),
+                 "%s: the step needs the workspace of vila_llm_decode_batch_any_k_workspace_bytes", fn);
+    const size_t head = decode_batch_penalized_head(&w->shape, st->n, cache->max_ctx, prefix != nullptr);
+    const Penalties P = pen != nullptr ? Penalties{pen->repetition, pen->presence, pen->frequency, pen->counts, pen->ld_counts} : Penalties{};
+    const Constraints Cn = con != nullptr ? Constraints{con->state, con->cls, con->ld_cls, con->next, con->ld_next, con->n_classes} : Constraints{};
+    return decode_step_batch_impl(w, qlayers, cache, st, workspace, head, sp, stream, prefix, pen != nullptr ? &P : nullptr, (float*)((char*)workspace + head),
+                                  con != nullptr ? &Cn : nullptr, true);
+}
 // The verify step (speculative decoding, decode_batch.hip bverify_step): the layer tables are the batched step's, the state is one sequence's.
 // sp != nullptr: the sampled form, whose four parameter arrays hold ONE entry each.
 static int decode_step_verify_impl(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers, const VilaKvCache* cache, const VilaDecodeVerify* st,
-                                   void* workspace, size_t workspace_bytes, const VilaBatchSampling* sp, vila_stream_t stream) {
+                                   void* workspace, size_t workspace_bytes, const VilaBatchSampling* sp, vila_stream_t stream, bool any_k = false) {
     const char* fn = qlayers != nullptr ? "llm_decode_verify_w4" : "llm_decode_verify";
     VILA_REQUIRE(w != nullptr && cache != nullptr && st != nullptr && workspace != nullptr, "%s: NULL argument", fn);
     VILA_REQUIRE(sp == nullptr || (sp->temperature != nullptr && sp->top_k != nullptr && sp->top_p != nullptr && sp->seed != nullptr),
@@ -993,7 +1017,7 @@ static int decode_step_verify_impl(const VilaLlmWeights* w, const VilaLlmLayerW4
     BVerifyState v{st->n, st->slot, st->pos, st->token, st->n_draft, st->out_ids, st->n_out, st->max_out, st->logits, st->n_accept,
                    st->hist, st->n_hist, st->hist_cap, st->max_ngram, st->cand, st->n_cand};
     return bverify_step(t.m, t.layers.data(), B(cache->k), B(cache->v), cache->max_ctx, cache->n_slots, v, workspace, workspace_bytes, S(stream),
-                        qlayers != nullptr ? t.ql.data() : nullptr, sp != nullptr ? &bs : nullptr);
+                        qlayers != nullptr ? t.ql.data() : nullptr, sp != nullptr ? &bs : nullptr, any_k);
 }
 extern "C" size_t vila_llm_decode_verify_workspace_bytes(const VilaLlmShape* s, int n, int max_ctx) {
     return bverify_workspace_bytes(s->hidden, s->inter, s->q_heads * s->head_dim, s->head_dim, n, max_ctx);
@@ -1012,6 +1036,12 @@ extern "C" int vila_llm_decode_step_verify_w4_sample(const VilaLlmWeights* w, co
     VILA_REQUIRE(sp != nullptr, "llm_decode_verify_w4_sample: sampling parameters are NULL");
     VILA_REQUIRE(qlayers != nullptr, "llm_decode_verify_w4: NULL argument");
     return decode_step_verify_impl(w, qlayers, cache, st, workspace, workspace_bytes, sp, stream);
+}
+// the sampled verify step whose draws serve every top_k >= 0 (qlayers nullable: bf16 / W4 in one entry); the workspace is the sampled step's
+extern "C" int vila_llm_decode_step_verify_any_k(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers, const VilaKvCache* cache, const VilaDecodeVerify* st,
+                                                 void* workspace, size_t workspace_bytes, const VilaBatchSampling* sp, vila_stream_t stream) {
+    VILA_REQUIRE(sp != nullptr, "llm_decode_verify_any_k: sampling parameters are NULL");
+    return decode_step_verify_impl(w, qlayers, cache, st, workspace, workspace_bytes, sp, stream, true);
 }
 extern "C" int vila_llm_decode_step_verify(const VilaLlmWeights* w, const VilaKvCache* cache, const VilaDecodeVerify* st, void* workspace,
                                            size_t workspace_bytes, vila_stream_t stream) {
@@ -1131,6 +1161,15 @@ extern "C" int vila_sample_batch_f32(const float* logits, int64_t ld_logits, int
     VILA_REQUIRE(sp != nullptr && logits != nullptr && out != nullptr && workspace != nullptr, "sample_batch: NULL argument");
     const BatchSampling bs{sp->temperature, sp->top_k, sp->top_p, sp->seed};
     return launch_sample_batch(logits, ld_logits, n, vocab, bs, 1, counter, out, workspace, dist_out, nullptr, nullptr, nullptr, 0, S(stream));
+}
+
+// ... and with the rows of top_k = 0 or > 64 drawn by the exact path (four launches whatever n; the same workspace).  dense_out (nullable)
+// [n][ld_dense]: such a row's distribution over the vocabulary; the other rows' entries are not written
+extern "C" int vila_sample_batch_any_f32(const float* logits, int64_t ld_logits, int n, int vocab, const VilaBatchSampling* sp, const int32_t* counter, int64_t* out,
+                                         void* workspace, float* dist_out, float* dense_out, int64_t ld_dense, vila_stream_t stream) {
+    VILA_REQUIRE(sp != nullptr && logits != nullptr && out != nullptr && workspace != nullptr, "sample_batch_any: NULL argument");
+    const BatchSampling bs{sp->temperature, sp->top_k, sp->top_p, sp->seed};
+    return launch_sample_batch(logits, ld_logits, n, vocab, bs, 1, counter, out, workspace, dist_out, nullptr, nullptr, nullptr, 0, S(stream), true, dense_out, ld_dense);
 }
 
 // =================================================================================================

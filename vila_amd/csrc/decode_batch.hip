@@ -439,7 +439,7 @@ size_t bdecode_prefix_workspace_bytes(int H, int F, int QS, int hd, int n, int m
 int bdecode_step(const BDecodeArgs& m, const BLayer* layers, bf16_t* kcache, bf16_t* vcache, int max_ctx, int n_slots, int n, int32_t* pos, int64_t* token,
                  int64_t* out_ids, int32_t* n_out, int max_out, float* logits, void* workspace, size_t workspace_bytes, hipStream_t s,
                  const BLayerW4* qlayers, const BatchSampling* sampling, void* sampling_ws, const BPrefix* prefix, const Penalties* pen, float* pen_out,
-                 const Constraints* con) {
+                 const Constraints* con, bool any_k) {
     static_assert(PEN_PICK_SLICES == PICK_SLICES, "the penalty launch writes the pairs bdec_pick2_kernel merges");
     const int H = m.hidden, F = m.inter, hd = m.head_dim, QS = m.q_heads * hd;
     VILA_REQUIRE((pen == nullptr && con == nullptr) || pen_out != nullptr, "batched decode: the penalised / constrained pick needs its scratch rows");
@@ -465,6 +465,7 @@ int bdecode_step(const BDecodeArgs& m, const BLayer* layers, bf16_t* kcache, bf1
                  "batched W4 decode: hidden (%d) and intermediate (%d) must be multiples of the 128-wide quantisation group", H, F);
     VILA_REQUIRE(workspace_bytes >= bdecode_workspace_bytes(H, F, QS, hd, n, max_ctx), "batched decode: workspace too small");
     VILA_REQUIRE(sampling == nullptr || sampling_ws != nullptr, "batched decode: the sampled pick needs its workspace");
+    VILA_REQUIRE(!any_k || sampling != nullptr, "batched decode: any top_k is an option of the sampled pick");
     BStepBufs b{};
     VILA_REQUIRE(bdec_carve(workspace, workspace_bytes, n, H, F, QS, hd, m.q_heads, form.nsl, false, false, &b, prefix != nullptr ? bverify_attn_slices(max_ctx) : 0),
                  "batched decode: workspace layout");
@@ -503,7 +504,7 @@ int bdecode_step(const BDecodeArgs& m, const BLayer* layers, bf16_t* kcache, bf1
         pick_src = pen_out;
     }
     if (sampling != nullptr)
-        return launch_sample_batch(pick_src, m.vocab, n, m.vocab, *sampling, 1, pos, token, sampling_ws, nullptr, pos, out_ids, n_out, max_out, s);
+        return launch_sample_batch(pick_src, m.vocab, n, m.vocab, *sampling, 1, pos, token, sampling_ws, nullptr, pos, out_ids, n_out, max_out, s, any_k);
     if (pen == nullptr && con == nullptr) {
         hipLaunchKernelGGL(bdec_pick1_kernel, dim3(PICK_SLICES, n), dim3(256), 0, s, logits, m.vocab, pick_v, pick_i);
         VILA_LAUNCH_CHECK();
@@ -627,7 +628,7 @@ size_t bverify_sample_workspace_bytes(int H, int F, int QS, int hd, int n, int m
     return align_up(bverify_workspace_bytes(H, F, QS, hd, n, max_ctx), 256) + align_up(sample_batch_workspace_bytes(n), 256) + align_up((size_t)(n > 0 ? n : 0) * 8, 256);
 }
 int bverify_step(const BDecodeArgs& m, const BLayer* layers, bf16_t* kcache, bf16_t* vcache, int max_ctx, int n_slots, const BVerifyState& st, void* workspace,
-                 size_t workspace_bytes, hipStream_t s, const BLayerW4* qlayers, const BatchSampling* sampling) {
+                 size_t workspace_bytes, hipStream_t s, const BLayerW4* qlayers, const BatchSampling* sampling, bool any_k) {
     const int H = m.hidden, F = m.inter, hd = m.head_dim, QS = m.q_heads * hd, n = st.n;
     VILA_REQUIRE(n >= 2 && n <= 16, "verify step: 2..16 rows per step (1 committed token + up to 15 drafts), got %d", n);
     VILA_REQUIRE(st.slot >= 0 && st.slot < n_slots, "verify step: slot %d of a cache with %d", st.slot, n_slots);
@@ -642,6 +643,7 @@ int bverify_step(const BDecodeArgs& m, const BLayer* layers, bf16_t* kcache, bf1
     VILA_REQUIRE(workspace_bytes >= (sampling != nullptr ? bverify_sample_workspace_bytes(H, F, QS, hd, n, max_ctx) : bverify_workspace_bytes(H, F, QS, hd, n, max_ctx)),
                  "verify step: workspace too small");
     VILA_REQUIRE(sampling == nullptr || (sampling->temperature && sampling->top_k && sampling->top_p && sampling->seed), "verify step: a NULL sampling array");
+    VILA_REQUIRE(!any_k || sampling != nullptr, "verify step: any top_k is an option of the sampled step");
     const int nsl = bverify_attn_slices(max_ctx);
     BStepBufs b{};
     VILA_REQUIRE(bdec_carve(workspace, workspace_bytes, n, H, F, QS, hd, m.q_heads, nsl, true, sampling != nullptr, &b), "verify step: workspace layout");
@@ -656,7 +658,7 @@ int bverify_step(const BDecodeArgs& m, const BLayer* layers, bf16_t* kcache, bf1
     if (sampling != nullptr) {
         // row i draws a[i] with counter pos_rows[i] = pos + i (written by the draft kernel; pos moves only in the accept below) from entry 0 of the
         // one-entry parameter arrays (stride 0), into the workspace; no state advance in the sampler
-        VILA_TRY(launch_sample_batch(st.logits, m.vocab, n, m.vocab, *sampling, 0, b.pos_rows, b.draws, b.smp_ws, nullptr, nullptr, nullptr, nullptr, 0, s));
+        VILA_TRY(launch_sample_batch(st.logits, m.vocab, n, m.vocab, *sampling, 0, b.pos_rows, b.draws, b.smp_ws, nullptr, nullptr, nullptr, nullptr, 0, s, any_k));
         hipLaunchKernelGGL(bver_accept_draws_kernel, dim3(1), dim3(64), 0, s, (const int64_t*)b.draws, n, st.token, st.n_draft, st.pos, st.out_ids, st.n_out,
                            st.max_out, st.hist, st.n_hist, st.hist_cap, st.n_accept);
         VILA_LAUNCH_CHECK();

@@ -68,10 +68,13 @@ int launch_sample(const float* logits, int n, float temperature, int top_k, floa
 // the batched sampler: one choice per row of logits [n][vocab] (n <= 16, top_k 1..64), every per-row parameter a device array [n]; temperature <= 0 =
 // greedy row.  out[row] = the token; dist_out (nullable) [n][128]; adv_pos != nullptr: also the batched decode step's state advance
 // (out_ids[row][n_out[row]++] = token, pos[row] = counter[row] + 1)
+// any_k (opt-in): one launch more draws the rows with top_k = 0 or > 64 by the solo sampler's exact path, in the same workspace; dense_out
+// (nullable, any_k only) [n][ld_dense]: such a row's distribution over the vocabulary
 struct BatchSampling { const float* temperature; const int32_t* top_k; const float* top_p; const uint64_t* seed; };
 size_t sample_batch_workspace_bytes(int n);
 int launch_sample_batch(const float* logits, int64_t ld_logits, int n, int vocab, const BatchSampling& sp, int sp_stride, const int32_t* counter, int64_t* out,
-                        void* workspace, float* dist_out, int32_t* adv_pos, int64_t* adv_out_ids, int32_t* adv_n_out, int max_out, hipStream_t s);
+                        void* workspace, float* dist_out, int32_t* adv_pos, int64_t* adv_out_ids, int32_t* adv_n_out, int max_out, hipStream_t s,
+                        bool any_k = false, float* dense_out = nullptr, int64_t ld_dense = 0);
 // ---- the (value, index) keys of sample.hip, shared with logprob.hip (device code; moved here unchanged) ----
 #if defined(__HIPCC__)
 // order-preserving key: larger float -> larger key; ties broken towards the LOWER index (index stored inverted in the low bits)
@@ -233,7 +236,8 @@ int bdecode_step(const BDecodeArgs& m, const BLayer* layers, bf16_t* kcache, bf1
                  int64_t* out_ids, int32_t* n_out, int max_out, float* logits, void* workspace, size_t workspace_bytes, hipStream_t s,
                  const BLayerW4* qlayers = nullptr, const BatchSampling* sampling = nullptr, void* sampling_ws = nullptr, const BPrefix* prefix = nullptr,
                  const Penalties* pen = nullptr, float* pen_out = nullptr,    // pen: the pick runs on the penalised rows, written to pen_out [n][vocab]
-                 const Constraints* con = nullptr);                           // con: ... masked by the rows' automata (behind the penalties), in pen_out as well
+                 const Constraints* con = nullptr,                            // con: ... masked by the rows' automata (behind the penalties), in pen_out as well
+                 bool any_k = false);                                         // any_k: the sampled pick serves every top_k >= 0 (launch_sample_batch)
 // the verify step (greedy speculative decoding): n rows = n consecutive positions of ONE sequence in ONE slot.  Its attention (attn_decode.hip
 // bdec_attn_shared_kernel) reads the slot's K/V once for all rows; `pos` is the device scalar of the state, row i sees keys 0 .. min(pos + i, max_ctx - 1)
 int bverify_attn_slices(int max_ctx);
@@ -254,7 +258,8 @@ struct BVerifyState {
 size_t bverify_workspace_bytes(int H, int F, int QS, int hd, int n, int max_ctx);
 size_t bverify_sample_workspace_bytes(int H, int F, int QS, int hd, int n, int max_ctx);
 int bverify_step(const BDecodeArgs& m, const BLayer* layers, bf16_t* kcache, bf16_t* vcache, int max_ctx, int n_slots, const BVerifyState& st, void* workspace,
-                 size_t workspace_bytes, hipStream_t s, const BLayerW4* qlayers = nullptr, const BatchSampling* sampling = nullptr);
+                 size_t workspace_bytes, hipStream_t s, const BLayerW4* qlayers = nullptr, const BatchSampling* sampling = nullptr,
+                 bool any_k = false);                                         // any_k: the rows' draws serve every top_k >= 0
 int launch_verify_draft(const int64_t* hist, const int32_t* n_hist, int max_ngram, const int64_t* cand, const int32_t* n_cand, const int32_t* n_out, int n,
                         int64_t* token, int32_t* n_draft, const int32_t* pos, int32_t* pos_rows, hipStream_t s);
 int launch_decode_prologue(const bf16_t* table, const int64_t* tok, bf16_t* out, int H, int64_t vocab, const int32_t* pos, float* rope_cs,

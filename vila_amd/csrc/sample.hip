@@ -13,7 +13,8 @@
 // largest, a mass-weighted radix descent for the nucleus threshold, a draw by prefix sums in index order.  The draw cannot match
 // torch.multinomial's generator bit for bit — parity for this op is distributional (tests/test_gpu_sampling.py).
 // The batched sampler at the end of the file makes the same choice for up to 16 rows at once (rows on blockIdx.y, per-row parameters in device
-// arrays, greedy rows beside sampled ones): the pick of a batched decode step whose ONE captured graph serves any mix of requests.
+// arrays, greedy rows beside sampled ones): the pick of a batched decode step whose ONE captured graph serves any mix of requests.  It serves
+// top_k in 1..64 and clamps anything else; with any_k (opt-in) rows with top_k = 0 or > 64 are drawn by smp_batch_large_kernel, one block per row.
 #include "kernels.h"
 
 #define SMP_CAND 64
@@ -57,10 +58,16 @@ __device__ void smp_max1024(uint64_t* keys) {
 // stage 1 / 2: candidates in, SMP_CAND best per block out.  in_keys == nullptr: read raw logits [n] (index = position);
 // otherwise read (key) candidates produced by the previous stage.  Rows of a batch lie on blockIdx.y (in_stride / out_stride elements apart);
 // row_temperature (nullable, device): row `row` reads entry row * param_stride (1: an entry per row; 0: every row reads entry 0 of a one-entry
-// array); a row whose temperature is not positive is a greedy row and keeps its largest key only.
+// array); a row whose temperature is not positive is a greedy row and keeps its largest key only.  row_top_k (nullable, device, read like
+// row_temperature; the any-top_k sampler only): a LARGE row (smp_row_large) is drawn by smp_batch_large_kernel from the logits themselves, so its
+// candidates are never read and it takes the greedy row's cheap route too.  nullptr: no row is large here.
+__device__ __forceinline__ bool smp_row_large(float temperature, int top_k) {       // launch_sample's own route to smp_large_kernel
+    return temperature > 0.f && (top_k == 0 || top_k > SMP_CAND);
+}
 __global__ __launch_bounds__(256) void smp_select_kernel(const float* __restrict__ logits, const uint64_t* __restrict__ in_keys, int n, int per_block,
                                                          uint64_t* __restrict__ out_keys, int64_t in_stride, int64_t out_stride,
-                                                         const float* __restrict__ row_temperature, int param_stride) {
+                                                         const float* __restrict__ row_temperature, int param_stride,
+                                                         const int32_t* __restrict__ row_top_k) {
     __shared__ uint64_t keys[1024];
     const int row = blockIdx.y;
     const float* lr = logits != nullptr ? logits + row * in_stride : nullptr;
@@ -72,7 +79,12 @@ __global__ __launch_bounds__(256) void smp_select_kernel(const float* __restrict
         if (i < per_block && g < n) k = (kr != nullptr) ? kr[g] : smp_key(lr[g], g);
         keys[i] = k;
     }
-    if (row_temperature != nullptr && !(row_temperature[row * param_stride] > 0.f)) smp_max1024(keys);       // block-uniform
+    bool cheap = false;                                             // block-uniform
+    if (row_temperature != nullptr) {
+        const float t = row_temperature[row * param_stride];
+        cheap = !(t > 0.f) || (row_top_k != nullptr && smp_row_large(t, row_top_k[row * param_stride]));
+    }
+    if (cheap) smp_max1024(keys);
     else smp_sort1024(keys);
     if (threadIdx.x < SMP_CAND) out_keys[row * out_stride + blockIdx.x * SMP_CAND + threadIdx.x] = keys[threadIdx.x];
 }
@@ -141,23 +153,32 @@ __global__ __launch_bounds__(256) void smp_final_kernel(const uint64_t* __restri
 // (bdec_pick2_kernel's), with `counter` read BEFORE the position moves (counter and adv_pos are the same array there: no __restrict__).
 // param_stride: 1 = row `row` reads entry `row` of the four parameter arrays (the batched step: one request per row); 0 = every row reads entry 0
 // (the sampled verify step: n rows of ONE request, arrays of one entry).  counter / out / prob_out / adv_* stay per row either way.
+// large_tok (nullable; the any-top_k sampler only): a LARGE row (smp_row_large) was drawn by smp_batch_large_kernel, which ran BEFORE this launch;
+// the row skips sort and draw, takes large_tok[row], and is written and advanced here like every other row (prob_out: zeros and -1 ids, the row's
+// distribution is the dense one of that kernel).  nullptr: no row is large, and top_k is clamped as ever.
 __global__ __launch_bounds__(256) void smp_batch_final_kernel(const uint64_t* __restrict__ in_keys, int n_in, int64_t in_stride, const float* __restrict__ temperature,
                                                               const int32_t* __restrict__ top_k, const float* __restrict__ top_p, const uint64_t* __restrict__ seed,
                                                               const int32_t* counter, int64_t* __restrict__ out, float* __restrict__ prob_out,
                                                               int32_t* adv_pos, int64_t* __restrict__ adv_out_ids, int32_t* __restrict__ adv_n_out, int max_out,
-                                                              int param_stride) {
+                                                              int param_stride, const int64_t* __restrict__ large_tok) {
     __shared__ uint64_t keys[1024];
     const int row = blockIdx.x, prow = row * param_stride;
     const float t = temperature[prow];
     const bool sampled = t > 0.f;                                   // block-uniform
-    for (int i = threadIdx.x; i < 1024; i += 256) keys[i] = i < n_in ? in_keys[row * in_stride + i] : 0;
-    if (sampled) smp_sort1024(keys); else smp_max1024(keys);
+    const bool large = large_tok != nullptr && smp_row_large(t, top_k[prow]);       // block-uniform
+    if (!large) {
+        for (int i = threadIdx.x; i < 1024; i += 256) keys[i] = i < n_in ? in_keys[row * in_stride + i] : 0;
+        if (sampled) smp_sort1024(keys); else smp_max1024(keys);
+    }
     if (threadIdx.x >= 64) return;
     const int lane = threadIdx.x;
     const uint32_t ctr = counter != nullptr ? (uint32_t)counter[row] : 0u;
     float* pr = prob_out != nullptr ? prob_out + (int64_t)row * 2 * SMP_CAND : nullptr;
     int tok;
-    if (sampled) {
+    if (large) {
+        tok = (int)large_tok[row];
+        if (pr != nullptr) { pr[lane] = 0.f; ((int*)(pr + 64))[lane] = -1; }
+    } else if (sampled) {
         int k = top_k[prow];
         k = k < 1 ? 1 : (k > SMP_CAND ? SMP_CAND : k);
         const float p = fminf(fmaxf(top_p[prow], 1.17549435e-38f), 1.0f);
@@ -196,9 +217,10 @@ __device__ __forceinline__ float smpl_block_sum(float v, float* red) {      // f
     for (int i = 0; i < SMPL_T / 64; ++i) t += red[i];
     return t;
 }
-__global__ __launch_bounds__(SMPL_T) void smp_large_kernel(const float* __restrict__ logits, int n, float inv_temperature, int top_k, float top_p,
-                                                           uint64_t seed_imm, const uint64_t* __restrict__ seed_dev, const int32_t* __restrict__ counter,
-                                                           int64_t* __restrict__ out, float* __restrict__ prob_out) {
+// One block of SMPL_T threads draws ONE row: the body of the solo kernel and of the batched one below, so that both make the same choice bit for
+// bit (the same per-thread strides, fixed-order reductions, fixed-point histograms and index-order draw whatever the launch).
+__device__ __forceinline__ void smp_large_row(const float* __restrict__ logits, int n, float inv_temperature, int top_k, float top_p, uint64_t seed,
+                                              uint32_t counter, int64_t* __restrict__ out, float* __restrict__ prob_out) {
     __shared__ uint32_t hist[256];
     __shared__ unsigned long long histq[SMPL_T / 64][256];     // nucleus masses in 2^-40 fixed point: INTEGER atomics commute, so a bin's sum
                                                                // has the same bits whatever order the lanes of a wave arrive in
@@ -300,8 +322,7 @@ __global__ __launch_bounds__(SMPL_T) void smp_large_kernel(const float* __restri
     }
     __syncthreads();
     const float kept_total = sh_f;
-    const uint64_t seed = seed_dev != nullptr ? *seed_dev : seed_imm;
-    const uint64_t r = splitmix64(seed ^ splitmix64((uint64_t)(uint32_t)(counter != nullptr ? *counter : 0)));
+    const uint64_t r = splitmix64(seed ^ splitmix64((uint64_t)counter));
     const float u = (float)(r >> 40) * (1.0f / 16777216.0f) * kept_total;
     const float base = scan[tid];
     if (mine > 0.f && u >= base && (u < base + mine || tid == SMPL_T - 1)) {
@@ -316,6 +337,30 @@ __global__ __launch_bounds__(SMPL_T) void smp_large_kernel(const float* __restri
     if (tid == 0) *out = (int64_t)(sh_i >= 0 ? sh_i : smp_idx(kmax));      // u beyond the last partial by rounding: the most likely token
     if (prob_out != nullptr)
         for (int i = tid; i < n; i += SMPL_T) { const float v = logits[i]; prob_out[i] = smp_key(v, i) >= T ? __expf(v * inv_temperature - zmax) / kept_total : 0.f; }
+}
+__global__ __launch_bounds__(SMPL_T) void smp_large_kernel(const float* __restrict__ logits, int n, float inv_temperature, int top_k, float top_p,
+                                                           uint64_t seed_imm, const uint64_t* __restrict__ seed_dev, const int32_t* __restrict__ counter,
+                                                           int64_t* __restrict__ out, float* __restrict__ prob_out) {
+    smp_large_row(logits, n, inv_temperature, top_k, top_p, seed_dev != nullptr ? *seed_dev : seed_imm, (uint32_t)(counter != nullptr ? *counter : 0), out,
+                  prob_out);
+}
+// The batched form: one block per row of logits [rows][ld_logits], the row's parameters read from the device arrays as smp_batch_final_kernel reads
+// them (param_stride 1 or 0), the counter from counter[row].  Only a LARGE row (smp_row_large: launch_sample's route to the kernel above, so the
+// bits are the solo path's) is drawn; every other block returns at once (the branch is block-uniform).  The token goes to large_tok[row], which
+// smp_batch_final_kernel reads: the row's `out` and its state advance stay in that kernel, which therefore runs AFTER this one — counter and the
+// advanced position are the same array in the decode step, and it must be read here before it moves.  top_p is clamped to (0, 1] as the final
+// kernel clamps it (an identity on what the host admits).  dense_out (nullable): the row's distribution [vocab] at dense_out + row * ld_dense.
+__global__ __launch_bounds__(SMPL_T) void smp_batch_large_kernel(const float* __restrict__ logits, int64_t ld_logits, int vocab, const float* __restrict__ temperature,
+                                                                 const int32_t* __restrict__ top_k, const float* __restrict__ top_p,
+                                                                 const uint64_t* __restrict__ seed, const int32_t* __restrict__ counter,
+                                                                 int64_t* __restrict__ large_tok, float* __restrict__ dense_out, int64_t ld_dense, int param_stride) {
+    const int row = blockIdx.x, prow = row * param_stride;
+    const float t = temperature[prow];
+    const int k = top_k[prow];
+    if (!smp_row_large(t, k)) return;                              // block-uniform
+    const float p = fminf(fmaxf(top_p[prow], 1.17549435e-38f), 1.0f);
+    smp_large_row(logits + (int64_t)row * ld_logits, vocab, 1.0f / t, k, p, seed[prow], counter != nullptr ? (uint32_t)counter[row] : 0u, large_tok + row,
+                  dense_out != nullptr ? dense_out + (int64_t)row * ld_dense : nullptr);
 }
 
 size_t sample_workspace_bytes() { return (size_t)(SMP_S1_BLOCKS + SMP_S2_BLOCKS) * SMP_CAND * sizeof(uint64_t) + 256; }
@@ -334,9 +379,9 @@ int launch_sample(const float* logits, int n, float temperature, int top_k, floa
     VILA_REQUIRE(per1 <= 1024, "sample: vocabulary of %d exceeds %d x 1024 entries", n, SMP_S1_BLOCKS);
     uint64_t* c1 = (uint64_t*)workspace;
     uint64_t* c2 = c1 + SMP_S1_BLOCKS * SMP_CAND;
-    hipLaunchKernelGGL(smp_select_kernel, dim3(SMP_S1_BLOCKS), dim3(256), 0, s, logits, (const uint64_t*)nullptr, n, per1, c1, (int64_t)0, (int64_t)0, (const float*)nullptr, 0);
+    hipLaunchKernelGGL(smp_select_kernel, dim3(SMP_S1_BLOCKS), dim3(256), 0, s, logits, (const uint64_t*)nullptr, n, per1, c1, (int64_t)0, (int64_t)0, (const float*)nullptr, 0, (const int32_t*)nullptr);
     VILA_LAUNCH_CHECK();
-    hipLaunchKernelGGL(smp_select_kernel, dim3(SMP_S2_BLOCKS), dim3(256), 0, s, (const float*)nullptr, (const uint64_t*)c1, SMP_S1_BLOCKS * SMP_CAND, 1024, c2, (int64_t)0, (int64_t)0, (const float*)nullptr, 0);
+    hipLaunchKernelGGL(smp_select_kernel, dim3(SMP_S2_BLOCKS), dim3(256), 0, s, (const float*)nullptr, (const uint64_t*)c1, SMP_S1_BLOCKS * SMP_CAND, 1024, c2, (int64_t)0, (int64_t)0, (const float*)nullptr, 0, (const int32_t*)nullptr);
     VILA_LAUNCH_CHECK();
     hipLaunchKernelGGL(smp_final_kernel, dim3(1), dim3(256), 0, s, (const uint64_t*)c2, SMP_S2_BLOCKS * SMP_CAND, 1.0f / temperature, top_k, top_p, seed, seed_dev, counter, out, prob_out);
     VILA_LAUNCH_CHECK();
@@ -348,28 +393,43 @@ int launch_sample(const float* logits, int n, float temperature, int top_k, floa
 // 256 slices sort 594 logits and 430 pads each — stage 2 sorts 1024 candidates per block, stage 3 is one block per row.  The top-64 set under the
 // strict key order does not depend on the cut, and stage 3 draws with the solo sampler's own arithmetic (smp_draw_wave).
 // sp_stride: 1 = sp's arrays hold n entries, one per row; 0 = they hold ONE entry that every row reads (n rows of one request).
+// any_k (opt-in; false = the three launches above, kernel for kernel, every pointer this option added NULL): a fourth launch, smp_batch_large_kernel, draws the
+// rows with top_k = 0 or > 64 by the solo sampler's exact path, and the final kernel takes their tokens instead of clamping top_k to 1..64.
 static inline int smpb_s1(int vocab) { return cdiv(vocab, 1024); }
 static inline int smpb_s2(int vocab) { return cdiv(smpb_s1(vocab) * SMP_CAND, 1024); }
 size_t sample_batch_workspace_bytes(int n) { return (size_t)(n > 0 ? n : 0) * (SMP_S1_BLOCKS + SMP_S2_BLOCKS) * SMP_CAND * sizeof(uint64_t) + 256; }
 
 int launch_sample_batch(const float* logits, int64_t ld_logits, int n, int vocab, const BatchSampling& sp, int sp_stride, const int32_t* counter, int64_t* out,
-                        void* workspace, float* dist_out, int32_t* adv_pos, int64_t* adv_out_ids, int32_t* adv_n_out, int max_out, hipStream_t s) {
+                        void* workspace, float* dist_out, int32_t* adv_pos, int64_t* adv_out_ids, int32_t* adv_n_out, int max_out, hipStream_t s, bool any_k,
+                        float* dense_out, int64_t ld_dense) {
     VILA_REQUIRE(n >= 1 && n <= 16, "sample_batch: 1..16 rows (got %d)", n);
     VILA_REQUIRE(vocab > 0 && ld_logits >= vocab, "sample_batch: row stride %lld is below the vocabulary %d", (long long)ld_logits, vocab);
     VILA_REQUIRE(smpb_s1(vocab) <= SMP_S1_BLOCKS, "sample_batch: vocabulary of %d exceeds %d x 1024 entries", vocab, SMP_S1_BLOCKS);
     VILA_REQUIRE(sp.temperature != nullptr && sp.top_k != nullptr && sp.top_p != nullptr && sp.seed != nullptr, "sample_batch: a per-row parameter array is NULL");
     VILA_REQUIRE(sp_stride == 0 || sp_stride == 1, "sample_batch: the parameter arrays hold one entry per row (stride 1) or one in all (0), got %d", sp_stride);
     VILA_REQUIRE(adv_pos == nullptr || (adv_out_ids != nullptr && adv_n_out != nullptr && max_out >= 1), "sample_batch: the state advance needs out_ids and n_out");
+    VILA_REQUIRE(dense_out == nullptr || (any_k && ld_dense >= vocab), "sample_batch: the dense distribution is the any-top_k sampler's, rows of at least the vocabulary");
     const int s1 = smpb_s1(vocab), s2 = smpb_s2(vocab), per1 = cdiv(vocab, s1);
     uint64_t* c1 = (uint64_t*)workspace;
     uint64_t* c2 = c1 + (size_t)n * SMP_S1_BLOCKS * SMP_CAND;
-    hipLaunchKernelGGL(smp_select_kernel, dim3(s1, n), dim3(256), 0, s, logits, (const uint64_t*)nullptr, vocab, per1, c1, ld_logits, (int64_t)s1 * SMP_CAND, sp.temperature, sp_stride);
+    // any_k: the large rows' tokens, 16 int64 in the 256 trailing bytes of sample_batch_workspace_bytes(n) — c1 ends where c2 begins, c2's n rows of
+    // at most SMP_S2_BLOCKS * SMP_CAND keys end at n * (SMP_S1_BLOCKS + SMP_S2_BLOCKS) * SMP_CAND keys, and nothing else lies behind them
+    static_assert(16 * sizeof(int64_t) <= 256, "the large rows' tokens fit the workspace's trailing bytes");
+    int64_t* large_tok = any_k ? (int64_t*)(c1 + (size_t)n * (SMP_S1_BLOCKS + SMP_S2_BLOCKS) * SMP_CAND) : nullptr;
+    const int32_t* sel_k = any_k ? sp.top_k : nullptr;
+    hipLaunchKernelGGL(smp_select_kernel, dim3(s1, n), dim3(256), 0, s, logits, (const uint64_t*)nullptr, vocab, per1, c1, ld_logits, (int64_t)s1 * SMP_CAND, sp.temperature, sp_stride,
+                       sel_k);
     VILA_LAUNCH_CHECK();
     hipLaunchKernelGGL(smp_select_kernel, dim3(s2, n), dim3(256), 0, s, (const float*)nullptr, (const uint64_t*)c1, s1 * SMP_CAND, 1024, c2, (int64_t)s1 * SMP_CAND,
-                       (int64_t)s2 * SMP_CAND, sp.temperature, sp_stride);
+                       (int64_t)s2 * SMP_CAND, sp.temperature, sp_stride, sel_k);
     VILA_LAUNCH_CHECK();
+    if (any_k) {                                                    // before the final kernel: it reads `counter`, which that kernel advances
+        hipLaunchKernelGGL(smp_batch_large_kernel, dim3(n), dim3(SMPL_T), 0, s, logits, ld_logits, vocab, sp.temperature, sp.top_k, sp.top_p, sp.seed, counter, large_tok,
+                           dense_out, ld_dense, sp_stride);
+        VILA_LAUNCH_CHECK();
+    }
     hipLaunchKernelGGL(smp_batch_final_kernel, dim3(n), dim3(256), 0, s, (const uint64_t*)c2, s2 * SMP_CAND, (int64_t)s2 * SMP_CAND, sp.temperature, sp.top_k, sp.top_p, sp.seed,
-                       counter, out, dist_out, adv_pos, adv_out_ids, adv_n_out, max_out, sp_stride);
+                       counter, out, dist_out, adv_pos, adv_out_ids, adv_n_out, max_out, sp_stride, (const int64_t*)large_tok);
     VILA_LAUNCH_CHECK();
     return 0;
 }

@@ -299,14 +299,25 @@ def _as_i64(u: int) -> int:
 
 
 def _step_symbols(batch: bool, w4: bool, sampled: bool, verify: bool = False, verify_sample: bool = False, prefix: bool = False,
-                  penalized: bool = False, constrained: bool = False) -> Tuple[str, str]:
+                  penalized: bool = False, constrained: bool = False, any_k: bool = False) -> Tuple[str, str]:
     """(step, workspace query) of one decode step variant, composed the way the C ABI names them.  verify: the greedy verify step, whatever `batch`.
     verify_sample: the sampled verify step, whatever `batch`, `sampled` and `verify` — a spelling of its own, since `verify` with `sampled` stays the
     refusal it always was (that pair names the greedy step asked to sample).  prefix: the batched step of a session with a shared prompt prefix
     (its workspace query takes the capacity and has no `_ctx` twin).  penalized: the step with repetition / presence / frequency penalties in front
     of its pick — ONE entry per driver, which takes the int4 layers, the sampling parameters and (batched) the prefix descriptor as nullable arguments,
     so w4 / sampled / prefix do not change the names.  constrained: the step with a token automaton per row between the penalties and the pick —
-    ONE entry per driver as well, which takes the penalties as a nullable argument too, so `penalized` does not change the names either."""
+    ONE entry per driver as well, which takes the penalties as a nullable argument too, so `penalized` does not change the names either.
+    any_k: the sampled pick that serves every top_k >= 0 — ONE entry for the batched step (int4 layers, prefix, penalties and automata nullable, so
+    none of them changes the names) and one for the sampled verify step (int4 layers nullable).  It is an option of a sampled pick: the greedy
+    steps and the solo step (whose sampler serves any top_k already) have no such form."""
+    if any_k:
+        if verify_sample:
+            if penalized or constrained or prefix:
+                raise ValueError("the verify steps have no penalised, constrained or shared-prefix form")
+            return "vila_llm_decode_step_verify_any_k", "vila_llm_decode_verify_sample_workspace_bytes"
+        if verify or not batch or not sampled:
+            raise ValueError("any top_k is an option of the sampled batched step and of the sampled verify step")
+        return "vila_llm_decode_step_batch_any_k", "vila_llm_decode_batch_any_k_workspace_bytes"
     if constrained:
         if verify or verify_sample:
             raise ValueError("the verify steps have no constrained form")
@@ -898,7 +909,12 @@ class HipQwen2ForCausalLM(_HipModule):
         pen = getattr(st, "pen", None)                                  # a session with the penalties flag: the one entry of its driver, NULLs for what is off
         con = getattr(st, "con", None)                                  # a session with the constraints flag: likewise, the penalties nullable too
         ref = lambda s: None if s is None else C.byref(s)
-        if con is not None:
+        if getattr(st, "any_k", False):                                 # a session with the any_top_k flag: the one entry of its driver, NULLs for what is off
+            name, _ = _step_symbols(batch, w4 is not None, sp is not None, verify, verify_sample, prefix=px is not None, any_k=True)
+            args = ([C.byref(self._struct()), w4.ptr if w4 is not None else None, C.byref(cache.c), C.byref(st.c)] + ([] if verify_sample else [ref(px)]) +
+                    [st.ws.data_ptr(), st.ws.numel(), C.byref(sp)] + ([] if verify_sample else [ref(pen), ref(con)]) + [ops._stream()])
+            check(getattr(_lib.load(), name)(*args), name)
+        elif con is not None:
             name, _ = _step_symbols(batch, w4 is not None, sp is not None, verify, verify_sample, prefix=px is not None, constrained=True)
             args = ([C.byref(self._struct()), w4.ptr if w4 is not None else None, C.byref(cache.c), C.byref(st.c)] + ([ref(px)] if batch else []) +
                     [st.ws.data_ptr(), st.ws.numel(), ref(sp), ref(pen), C.byref(con), ops._stream()])
@@ -927,13 +943,13 @@ class HipQwen2ForCausalLM(_HipModule):
 
     # ---- batched greedy generate: one weight pass per step for up to 16 sequences (vila_llm_decode_step_batch) -----------------------
     def _can_batch_decode(self, inputs_embeds, attention_mask, max_new_tokens, do_sample, forced_ids, return_logits, cache,
-                          batch_sample: bool = False, top_k: int = 50) -> bool:
+                          batch_sample: bool = False, top_k: int = 50, any_top_k: bool = False) -> bool:
         """The greedy batched step serves a padded batch; with batch_sample (opt-in) the same holds for a sampled batch whose top_k the
-        batched sampler serves (1..64), teacher forcing included."""
+        batched sampler serves (1..64; with any_top_k every top_k >= 0), teacher forcing included."""
         c = self.lcfg
         Bn, S = inputs_embeds.shape[0], inputs_embeds.shape[1]
         if do_sample:
-            ok = batch_sample and 1 <= top_k <= 64
+            ok = batch_sample and (1 <= top_k <= 64 or (any_top_k and top_k >= 0))
         else:
             ok = forced_ids is None and not return_logits
         return (ok and cache is None and self.can_batch_decode_step() and
@@ -970,7 +986,7 @@ class HipQwen2ForCausalLM(_HipModule):
         return True
 
     def _batch_session(self, n: int, max_ctx: int, max_new_tokens: int, sampling: bool = False, shared_prefix: bool = False, penalties: bool = False,
-                       logprobs: bool = False, constraints=None):
+                       logprobs: bool = False, constraints=None, any_top_k: bool = False):
         """sampling=True: the session owns per-row sampling parameters on the device (temperature / top_k / top_p / seed, every row greedy
         until `_batch_set_sampling` says otherwise) and steps through the `_sample` entry points: one captured graph for any mix of rows.
         shared_prefix=True: the cache has one slot more, the prefix slot (index n), and the session owns the shared length and the rows' flags on
@@ -982,18 +998,25 @@ class HipQwen2ForCausalLM(_HipModule):
         (`_logprob_state`).
         constraints=(max_states, max_classes) (in the key only when set, likewise): the session steps through
         `vila_llm_decode_step_batch_constrained` and owns an automaton per row (`_constraint_state`), every row unconstrained until
-        `_set_constraint` says otherwise."""
+        `_set_constraint` says otherwise.
+        any_top_k=True (sampling sessions; in the key only when set, likewise): the session steps through `vila_llm_decode_step_batch_any_k`, whose
+        pick serves a row with any top_k >= 0 (0 = no top-k filter) from the same device arrays."""
+        if any_top_k and not sampling:
+            raise ValueError("any_top_k is an option of a sampling session (sampling=True)")
         w4 = self._w4_batched()
         if not w4:
             self._require_bf16("the batched decode")
         key = (n, max_ctx, max_new_tokens, bool(sampling), *self._weights_key()) + ((True,) if shared_prefix else ()) + (("penalties",) if penalties else ())
         key += ("logprobs",) if logprobs else ()
         key += ("constraints", *constraints) if constraints else ()
+        key += ("any_top_k",) if any_top_k else ()
         if self._bdecode is not None and self._bdecode.key == key:
             return self._bdecode
         self._drop_session("_bdecode")
         dev, lib, w = self.device, _lib.load(), self._struct()
         st = SimpleNamespace(key=key, graph=None, sampling=bool(sampling), sp=None, px=None, shared_prefix=bool(shared_prefix), pen=None, lp=None, con=None)
+        if any_top_k:
+            st.any_k = True
         st.attn_slices = int(lib.vila_decode_batch_slices(int(max_ctx)))     # walking-attention slices the steps of this session launch (0: short form)
         with torch.inference_mode(False):
             st.cache = self.new_cache(max_ctx, n_slots=n + 1 if shared_prefix else n)
@@ -1009,7 +1032,7 @@ class HipQwen2ForCausalLM(_HipModule):
             st.n_out = torch.zeros(n, device=dev, dtype=torch.int32)
             st.logits = torch.zeros((n, self.lcfg.vocab_size), device=dev, dtype=torch.float32)
             ws_bytes = getattr(lib, _step_symbols(True, w4, bool(sampling), prefix=bool(shared_prefix), penalized=bool(penalties),
-                                                  constrained=bool(constraints))[1])
+                                                  constrained=bool(constraints), **(dict(any_k=True) if any_top_k else {}))[1])
             if constraints:
                 self._constraint_state(st, n, self.lcfg.vocab_size, constraints, dev)
             if penalties:
@@ -1022,7 +1045,7 @@ class HipQwen2ForCausalLM(_HipModule):
                 st.s_top_p = torch.ones(n, device=dev, dtype=torch.float32)
                 st.s_seed = torch.zeros(n, device=dev, dtype=torch.int64)                   # bit patterns of uint64 seeds
                 st.sp = _lib.VilaBatchSampling(st.s_temperature.data_ptr(), st.s_top_k.data_ptr(), st.s_top_p.data_ptr(), st.s_seed.data_ptr())
-            ws_args = (int(bool(shared_prefix)),) if penalties or constraints else ()
+            ws_args = (int(bool(shared_prefix)),) if penalties or constraints or any_top_k else ()
             st.ws = torch.empty((ws_bytes(C.byref(w.shape), n, int(max_ctx), *ws_args),), device=dev, dtype=torch.uint8)    # (<= 2048 positions: the size it always had)
         st.c = _lib.VilaDecodeBatch(n, st.pos.data_ptr(), st.token.data_ptr(), st.out_ids.data_ptr(), st.n_out.data_ptr(), max(max_new_tokens, 1),
                                     st.logits.data_ptr())
@@ -1038,15 +1061,15 @@ class HipQwen2ForCausalLM(_HipModule):
     # KV slot, set the row's position and first token, replay the same captured graph.  A free row idles at positions 0..15 of its own slot
     # (re-wound after every chunk), which costs nothing extra: the step streams the weights once whatever the number of live rows.
     @staticmethod
-    def _check_batch_sampling(sampling, what: str):
+    def _check_batch_sampling(sampling, what: str, any_top_k: bool = False):
         """(temperature, top_k, top_p, seed) of ONE row of a sampling batch session, validated where the values are known (the kernel only
-        clamps).  The batched sampler serves top_k in 1..64."""
+        clamps).  The batched sampler serves top_k in 1..64; that of a session with the any_top_k flag every top_k >= 0 (0 = no top-k filter)."""
         temperature, top_k, top_p, seed = float(sampling[0]), int(sampling[1]), float(sampling[2]), int(sampling[3])
         if temperature <= 0:
             raise ValueError(f"`temperature` (={temperature}) has to be a strictly positive float, otherwise your next token scores will be invalid.")
         if top_k < 0:
             raise ValueError(f"`top_k` has to be a non-negative integer, but is {top_k}")
-        if not 1 <= top_k <= 64:
+        if not 1 <= top_k <= 64 and not any_top_k:
             raise ValueError(f"{what}: the batched sampler serves top_k in 1..64 (got {top_k}); such a request runs solo")
         if not 0.0 < top_p <= 1.0:
             raise ValueError(f"`top_p` has to be a float > 0 and <= 1, but is {top_p}")
@@ -1062,7 +1085,8 @@ class HipQwen2ForCausalLM(_HipModule):
         st.s_seed[slot:slot + 1].fill_(_as_i64(seed))
 
     def batch_open(self, n_slots: int, max_ctx: int = 2048, max_new_tokens: int = 1024, sampling: bool = False, shared_prefix: bool = False,
-                   penalties: bool = False, logprobs: bool = False, constraints: bool = False, max_states: int = 512, max_classes: int = 4096):
+                   penalties: bool = False, logprobs: bool = False, constraints: bool = False, max_states: int = 512, max_classes: int = 4096,
+                   any_top_k: bool = False):
         """Open (or re-use) the batched-decode session of `n_slots` rows with its captured step.  sampling=False: the greedy step.  sampling=True:
         the step picks per row from device-resident parameters, so the ONE captured graph serves any mix of greedy and sampled rows
         (`batch_admit(..., sampling=)`); the flag is part of the session key.
@@ -1079,7 +1103,13 @@ class HipQwen2ForCausalLM(_HipModule):
         row the class of every token id and a table of max_states x max_classes int16 ENTRIES — so the ONE captured graph serves any mix of
         constrained and plain rows and any change of automaton.  The two arguments size the table, they do not bound states on their own: an
         automaton lies in it row-major with its OWN class count, so it fits when states x classes <= max_states x max_classes and classes <=
-        max_classes (an automaton with few classes may have more than max_states states)."""
+        max_classes (an automaton with few classes may have more than max_states states).
+        any_top_k=True (with sampling=True; part of the key as well): a sampled row may carry ANY top_k >= 0 — 0 = no top-k filter, HF's meaning,
+        i.e. pure top-p sampling, and k > 64 — where the session without the flag serves 1..64.  Such a row is drawn on the device by the solo
+        sampler's exact path (one launch more per step, one block per row) and gets bit for bit the token `ops.sample` returns for its logits,
+        parameters, seed and counter; the ONE captured graph serves any mix of greedy rows, rows of 1..64 and such rows."""
+        if any_top_k and not sampling:
+            raise ValueError("batch_open: any_top_k=True is an option of a sampling session (sampling=True)")
         if not self._w4_batched():
             self._require_bf16("batch_open")
         con_caps = self._constraint_caps(max_states, max_classes) if constraints else None
@@ -1089,7 +1119,7 @@ class HipQwen2ForCausalLM(_HipModule):
             raise ValueError("batch_open: the batched decode step serves 1..16 rows of a head-dim-128 model (bf16, or quantize_w4(batch_decode=True)) "
                              f"with caches <= {self.BATCH_MAX_CTX} positions (beyond 2048: GQA groups of 1, 2, 4, 7 or 8 query heads)")
         st = self._batch_session(max(n_slots, 2), max_ctx, max_new_tokens, sampling, shared_prefix, penalties, logprobs,
-                                 **({} if con_caps is None else dict(constraints=con_caps)))
+                                 **({} if con_caps is None else dict(constraints=con_caps)), **(dict(any_top_k=True) if any_top_k else {}))
         if getattr(st, "con", None) is not None:
             st.con_state.fill_(-1)                                     # every row starts unconstrained (an idle row never advances)
         def reset():
@@ -1169,7 +1199,8 @@ class HipQwen2ForCausalLM(_HipModule):
     def batch_admit(self, st, slot: int, embeds: torch.Tensor, sampling=None, share: bool = False, first_row: int = 0, penalties=None,
                     constraint=None) -> int:
         """Prefill ONE sequence [P, H] into KV slot `slot` of the open batch and make the row live: position P, first token = argmax of the
-        prefill's last row (returned), output counter 0.  sampling = (temperature, top_k in 1..64, top_p, seed), sampling sessions only: the
+        prefill's last row (returned), output counter 0.  sampling = (temperature, top_k in 1..64 — any top_k >= 0 in a session opened with
+        any_top_k=True —, top_p, seed), sampling sessions only: the
         row samples — its parameters go to the device arrays, its first token is drawn from the prefill's last row with counter P - 1 (as the
         solo generate draws it), the steps draw with the position of the token they consume.  None = greedy row.
         share=True (sessions opened with shared_prefix=True, after `batch_set_prefix`): embeds is the WHOLE prompt [P, H], whose first S positions
@@ -1194,7 +1225,7 @@ class HipQwen2ForCausalLM(_HipModule):
         if sampling is not None:
             if not st.sampling:
                 raise ValueError("batch_admit: a sampled row needs a session opened with batch_open(sampling=True)")
-            sampling = self._check_batch_sampling(sampling, "batch_admit")
+            sampling = self._check_batch_sampling(sampling, "batch_admit", **(dict(any_top_k=True) if getattr(st, "any_k", False) else {}))
         first_row = int(first_row)
         if first_row != 0 and not (share and 0 <= first_row <= getattr(st, "S", 0)):
             raise ValueError(f"batch_admit: first_row ({first_row}) is for share=True and lies in 0 .. the shared length")
@@ -1263,21 +1294,22 @@ class HipQwen2ForCausalLM(_HipModule):
                 st.sharers.difference_update(int(s) for s in slots)
 
     def _generate_shared(self, inputs_embeds, n: int, max_new_tokens, eos_token_id, pad_token_id, use_graph: bool, return_logits: bool, sampling,
-                         penalties=None, logprobs=None, constraint=None):
+                         penalties=None, logprobs=None, constraint=None, any_top_k: bool = False):
         """generate(num_return_sequences=n): ONE prefill of the prompt into the prefix slot of a shared-prefix sampling session, n sharing rows that
         differ in their seeds.  Returns [n, n_new] like `_generate_batch`; return_logits: (ids [n, n_new], logits [n_new, n, V] fp32), eager steps.
         A prompt below 256 positions has no whole chunk to share: nothing goes into the prefix slot and the n rows are ordinary rows of the same
         session, each prefilled on its own (return_logits is refused for it by the caller).
         penalties: None, or the request's (rep, pres, freq): the session is opened with the penalties flag and every row carries them, with counts of
         its own.
-        logprobs: None, or k: the session is opened with the logprobs flag and the call returns (ids, `Logprobs`) with k alternatives per token."""
+        logprobs: None, or k: the session is opened with the logprobs flag and the call returns (ids, `Logprobs`) with k alternatives per token.
+        any_top_k: the session is opened with the any_top_k flag, so the rows' top_k may be 0 or above 64."""
         x = inputs_embeds[0]
         P, dev = int(x.shape[0]), x.device
         max_ctx = ((P + max_new_tokens + 255) // 256) * 256
         con_kw = {} if constraint is None else dict(constraints=True, max_states=self.CONSTRAIN_MAX_STATES, max_classes=self.CONSTRAIN_MAX_CLASSES)
         row_kw = {} if constraint is None else dict(constraint=constraint)      # (every row carries the request's automaton, with a state of its own)
         st = self.batch_open(n, max_ctx, max_new_tokens, sampling=True, shared_prefix=True, penalties=penalties is not None,
-                             **({} if logprobs is None else dict(logprobs=True)), **con_kw)
+                             **({} if logprobs is None else dict(logprobs=True)), **con_kw, **(dict(any_top_k=True) if any_top_k else {}))
         self.batch_release(st, range(st.pos.numel()))
         if P < 256:
             first_h = [self.batch_admit(st, j, x, sampling=sampling[j], penalties=penalties, **row_kw) for j in range(n)]
@@ -1325,7 +1357,7 @@ class HipQwen2ForCausalLM(_HipModule):
 
     def _generate_batch(self, inputs_embeds, attention_mask, max_new_tokens, eos_token_id, pad_token_id, use_graph: bool = True,
                         forced_ids: Optional[torch.Tensor] = None, return_logits: bool = False, sampling=None, penalties=None, logprobs=None,
-                        constraint=None):
+                        constraint=None, any_top_k: bool = False):
         """The padded batch as ONE packed prefill (every row into its own KV-cache slot) + batched decode steps: the weights are streamed
         once per step for all rows.  Returns [B, n_new] right-padded with pad_token_id behind each row's EOS, like HF.
         forced_ids [B, n_new] / return_logits: teacher forcing for the parity tests (eager launches; the ids fed after step t are
@@ -1340,10 +1372,12 @@ class HipQwen2ForCausalLM(_HipModule):
         token (not with forced_ids / return_logits).
         constraint: None, or an `Automaton` for every row (or a list with one / None per row): the batch runs in a session with the constraints flag;
         the first tokens are chosen from the prefill's rows masked from the start states, the returned logits stay raw, the returned ids are the
-        ones each step chose."""
+        ones each step chose.
+        any_top_k (with sampling): the session carries the any_top_k flag, so a row's top_k may be 0 (no top-k filter) or above 64."""
         ops._need(inputs_embeds, dtype=None, name="inputs_embeds")
+        any_kw = dict(any_top_k=True) if any_top_k and sampling is not None else {}
         if sampling is not None:
-            sampling = [None if sp is None else self._check_batch_sampling(sp, "generate(batch_sample=True)") for sp in sampling]
+            sampling = [None if sp is None else self._check_batch_sampling(sp, "generate(batch_sample=True)", **any_kw) for sp in sampling]
         Bn, S, H = inputs_embeds.shape
         dev = inputs_embeds.device
         mask = attention_mask.bool() if attention_mask is not None else torch.ones((Bn, S), dtype=torch.bool, device=dev)
@@ -1359,7 +1393,8 @@ class HipQwen2ForCausalLM(_HipModule):
         max_ctx = ((max(lens) + max_new_tokens + 255) // 256) * 256
         st = self._batch_session(Bn, max_ctx, max_new_tokens, sampling is not None, penalties=penalties is not None,
                                  **({} if logprobs is None else dict(logprobs=True)),
-                                 **({} if constraint is None else dict(constraints=self._constraint_caps(self.CONSTRAIN_MAX_STATES, self.CONSTRAIN_MAX_CLASSES))))
+                                 **({} if constraint is None else dict(constraints=self._constraint_caps(self.CONSTRAIN_MAX_STATES, self.CONSTRAIN_MAX_CLASSES))),
+                                 **any_kw)
         if penalties is not None:
             rows_pen = list(penalties) if isinstance(penalties, list) else [penalties] * Bn
             for b in range(Bn):
@@ -1448,7 +1483,7 @@ class HipQwen2ForCausalLM(_HipModule):
                  prompt_ids: Optional[torch.Tensor] = None, draft_ids: Optional[torch.Tensor] = None, past_len: Optional[int] = None,
                  prefill_chunk: Optional[int] = None, spec_sample: Optional[bool] = None, num_return_sequences: Optional[int] = None,
                  repetition_penalty: Optional[float] = None, presence_penalty: Optional[float] = None, frequency_penalty: Optional[float] = None,
-                 logprobs: Optional[int] = None, constraint=None, **kw):
+                 logprobs: Optional[int] = None, constraint=None, any_top_k: Optional[bool] = None, **kw):
         """`llm.generate(inputs_embeds=, attention_mask=, **generation_kwargs)` as called at llava_arch.py:833 (HF semantics: returns ONLY the
         new tokens, [B, n_new]).  Greedy search or sampling (do_sample: temperature / top_k / top_p, HF order, on the device); explicit
         keyword arguments override `generation_config` (HF GenerationConfig-like: do_sample, temperature, top_k, top_p, max_new_tokens,
@@ -1503,7 +1538,12 @@ class HipQwen2ForCausalLM(_HipModule):
         the automaton, with a state of its own), bf16 or W4, with batch_sample, num_return_sequences, penalties, logprobs (which stay RAW), cache= /
         past_len= / prefill_chunk.  return_logits stays raw, and its ids are the ones each step chose.  EOS is allowed exactly where the text is a
         member of the language; max_new_tokens can still cut the reply before that.  Not served with prompt_lookup_num_tokens / draft_ids /
-        spec_sample (the verify steps have no constrained form) and not with forced_ids (a forced token may leave the language)."""
+        spec_sample (the verify steps have no constrained form) and not with forced_ids (a forced token may leave the language).
+        any_top_k (opt-in, also read from generation_config; default False): with it, batch_sample, num_return_sequences and spec_sample serve EVERY
+        top_k >= 0 — 0 = no top-k filter (pure temperature / top-p sampling, HF's meaning) and k > 64 — where they serve 1..64 without it (a padded
+        batch then runs row by row, the other two raise).  Such rows are drawn on the device by the solo sampler's exact selection, one block per
+        row and one launch more per step (`vila_llm_decode_step_batch_any_k`, `vila_llm_decode_step_verify_any_k`): a row's token is bit for bit
+        what `ops.sample` returns for the same logits, parameters, seed and counter.  The flag enters the session key, the values do not."""
         self._check_append_args(inputs_embeds, cache, past_len, prefill_chunk)
         if constraint is not None:
             self._check_constraint(constraint, "generate")
@@ -1538,7 +1578,8 @@ class HipQwen2ForCausalLM(_HipModule):
                                                    temperature, top_k, top_p, seed, pad_token_id, generation_config, use_graph, return_logits,
                                                    forced_ids, cache, streamer, batch_sample, prompt_lookup_num_tokens, draft_ids, past_len, prefill_chunk,
                                                    penalties, **({} if logprobs is None else dict(logprobs=logprobs)),
-                                                   **({} if constraint is None else dict(constraint=constraint)))
+                                                   **({} if constraint is None else dict(constraint=constraint)),
+                                                   **({} if any_top_k is None else dict(any_top_k=any_top_k)))
         if streamer is not None and inputs_embeds.shape[0] > 1:
             raise ValueError("TextStreamer only supports batch size 1")          # transformers/generation/streamers.py, TextStreamer.put
         do_sample = bool(pick(do_sample, "do_sample", False))
@@ -1547,6 +1588,7 @@ class HipQwen2ForCausalLM(_HipModule):
         eos_token_id = pick(eos_token_id, "eos_token_id", None)
         pad_token_id = pick(pad_token_id, "pad_token_id", None)
         batch_sample = bool(pick(batch_sample, "batch_sample", False))
+        any_top_k = bool(pick(any_top_k, "any_top_k", False))
         k_spec = pick(prompt_lookup_num_tokens, "prompt_lookup_num_tokens", None)
         if k_spec is not None or draft_ids is not None:
             k_spec = 7 if k_spec is None else int(k_spec)
@@ -1567,13 +1609,15 @@ class HipQwen2ForCausalLM(_HipModule):
             if do_sample:
                 if temperature <= 0:
                     raise ValueError(f"`temperature` (={temperature}) has to be a strictly positive float, otherwise your next token scores will be invalid.")
-                if not 1 <= top_k <= 64:
+                if any_top_k and top_k < 0:
+                    raise ValueError(f"`top_k` has to be a non-negative integer, but is {top_k}")
+                if not 1 <= top_k <= 64 and not any_top_k:
                     raise ValueError(f"spec_sample: the sampled verify step serves top_k in 1..64 (got top_k = {top_k})")
                 if not 0.0 < top_p <= 1.0:
                     raise ValueError(f"`top_p` has to be a float > 0 and <= 1, but is {top_p}")
                 sampling = (temperature, top_k, top_p, int(self._fresh_seed() if seed is None else seed))
             return self._generate_verify(inputs_embeds, attention_mask, max_new_tokens, eos_token_id, k_spec, max_ngram, prompt_ids, draft_ids, cache, streamer,
-                                         past_len, prefill_chunk, sampling)
+                                         past_len, prefill_chunk, sampling, **(dict(any_top_k=True) if any_top_k and sampling is not None else {}))
         if do_sample and temperature <= 0:
             raise ValueError(f"`temperature` (={temperature}) has to be a strictly positive float, otherwise your next token scores will be invalid.")
         if do_sample and top_k < 0:
@@ -1587,7 +1631,7 @@ class HipQwen2ForCausalLM(_HipModule):
         processed = penalties is not None or constraint is not None    # (a constrained greedy batch returns its logits through the batched step too)
         if inputs_embeds.shape[0] > 1 and self._can_batch_decode(inputs_embeds, attention_mask, max_new_tokens, do_sample,
                                                                  forced_ids if not processed else None, return_logits and not processed, cache,
-                                                                 batch_sample, top_k):
+                                                                 batch_sample, top_k, **(dict(any_top_k=True) if any_top_k else {})):
             if not do_sample:
                 if not processed and logprobs is None:
                     return self._generate_batch(inputs_embeds, attention_mask, max_new_tokens, eos_token_id, pad_token_id, use_graph)
@@ -1597,7 +1641,7 @@ class HipQwen2ForCausalLM(_HipModule):
                 seed = self._fresh_seed()
             rows = [(temperature, top_k, top_p, (int(seed) + b) & 0xFFFFFFFFFFFFFFFF) for b in range(inputs_embeds.shape[0])]
             return self._generate_batch(inputs_embeds, attention_mask, max_new_tokens, eos_token_id, pad_token_id, use_graph, forced_ids,
-                                        return_logits, sampling=rows, **pen_kw)
+                                        return_logits, sampling=rows, **pen_kw, **(dict(any_top_k=True) if any_top_k else {}))
         if inputs_embeds.shape[0] > 1:
             rows = []
             row_pen = {} if penalties is None else dict(repetition_penalty=penalties[0], presence_penalty=penalties[1], frequency_penalty=penalties[2])
@@ -1629,7 +1673,7 @@ class HipQwen2ForCausalLM(_HipModule):
 
     def _generate_return_sequences(self, inputs_embeds, attention_mask, n, max_new_tokens, eos_token_id, do_sample, temperature, top_k, top_p, seed,
                                    pad_token_id, gc, use_graph, return_logits, forced_ids, cache, streamer, batch_sample, k_spec, draft_ids, past_len,
-                                   prefill_chunk, penalties=None, logprobs=None, constraint=None):
+                                   prefill_chunk, penalties=None, logprobs=None, constraint=None, any_top_k=None):
         """generate(num_return_sequences=n): what is served, refused with a ValueError that says so otherwise."""
         pick = lambda v, name, default: v if v is not None else (getattr(gc, name, None) if gc is not None and getattr(gc, name, None) is not None else default)
         what = "num_return_sequences: n samples of ONE prompt over its shared K/V"
@@ -1655,12 +1699,13 @@ class HipQwen2ForCausalLM(_HipModule):
                              "one by one)")
         if seed is None:
             seed = self._fresh_seed()
-        rows = [self._check_batch_sampling((temperature, top_k, top_p, (int(seed) + j) & 0xFFFFFFFFFFFFFFFF), "generate(num_return_sequences=)")
+        any_kw = dict(any_top_k=True) if bool(pick(any_top_k, "any_top_k", False)) else {}
+        rows = [self._check_batch_sampling((temperature, top_k, top_p, (int(seed) + j) & 0xFFFFFFFFFFFFFFFF), "generate(num_return_sequences=)", **any_kw)
                 for j in range(n)]
         return self._generate_shared(inputs_embeds, n, max_new_tokens, pick(eos_token_id, "eos_token_id", None), pick(pad_token_id, "pad_token_id", None),
                                      use_graph, return_logits, rows, **({} if penalties is None else dict(penalties=penalties)),
                                      **({} if logprobs is None else dict(logprobs=logprobs)),
-                                     **({} if constraint is None else dict(constraint=constraint)))
+                                     **({} if constraint is None else dict(constraint=constraint)), **any_kw)
 
     @staticmethod
     def _check_append_args(inputs_embeds, cache, past_len, prefill_chunk) -> None:
@@ -1820,17 +1865,21 @@ class HipQwen2ForCausalLM(_HipModule):
             return "the verify step reads q/k/v as one fused [q + 2kv, hidden] buffer (refuse() re-establishes it)"
         return None
 
-    def _verify_session(self, cache, n: int, max_out: int, max_ngram: int, sampled: bool = False):
+    def _verify_session(self, cache, n: int, max_out: int, max_ngram: int, sampled: bool = False, any_top_k: bool = False):
         """Device-resident state of a verify session (+ its captured hipGraph), keyed like `_decode_session`.  sampled: the session steps through
         the `_sample` entry points (another graph, hence part of the key) and owns the request's four sampling parameters as ONE-entry device
-        tensors that `_verify_set_sampling` rewrites per request: neither the parameters nor the seed are baked into the graph."""
+        tensors that `_verify_set_sampling` rewrites per request: neither the parameters nor the seed are baked into the graph.
+        any_top_k (sampled sessions; in the key only when set): the session steps through `vila_llm_decode_step_verify_any_k`, whose draws serve
+        every top_k >= 0."""
         w4 = self._w4_batched()
-        key = (cache.k.data_ptr(), cache.max_ctx, n, max_out, max_ngram, bool(sampled), *self._weights_key())
+        key = (cache.k.data_ptr(), cache.max_ctx, n, max_out, max_ngram, bool(sampled), *self._weights_key()) + (("any_top_k",) if any_top_k and sampled else ())
         if self._vdecode is not None and self._vdecode.key == key:
             return self._vdecode
         self._drop_session("_vdecode")
         dev, lib, w = self.device, _lib.load(), self._struct()
         st = SimpleNamespace(key=key, cache=cache, graph=None, n=n, max_out=max_out, w4=w4, sampled=bool(sampled), sp=None)
+        if any_top_k and sampled:
+            st.any_k = True
         i32 = lambda m: torch.zeros(m, device=dev, dtype=torch.int32)
         with torch.inference_mode(False):
             st.pos, st.n_draft, st.n_out, st.n_accept, st.n_hist, st.n_cand = i32(1), i32(1), i32(1), i32(1), i32(1), i32(1)
@@ -1870,11 +1919,12 @@ class HipQwen2ForCausalLM(_HipModule):
         self._step(True, self._w4 if st.w4 else None, cache, st, st.sp if st.sampled else None, verify=not st.sampled, verify_sample=st.sampled)
 
     def _generate_verify(self, inputs_embeds, attention_mask, max_new_tokens, eos_token_id, k, max_ngram, prompt_ids, draft_ids, cache, streamer,
-                         past_len=None, prefill_chunk=None, sampling=None):
+                         past_len=None, prefill_chunk=None, sampling=None, any_top_k: bool = False):
         """generate() for one sequence with the verify step: prefill as `_generate_solo`, first token from the prefill, then graph replays
         that each append 1 .. k + 1 tokens.  The host cuts at EOS and at max_new_tokens (a step may overshoot by up to k).
         sampling: None (greedy) or (temperature, top_k in 1..64, top_p, seed): the first token is drawn from the prefill's last row with counter
-        S - 1, as `_generate_solo` draws it, and the steps draw with the positions of the tokens they consume (S, S + 1, ...)."""
+        S - 1, as `_generate_solo` draws it, and the steps draw with the positions of the tokens they consume (S, S + 1, ...).
+        any_top_k (with sampling): the session carries the any_top_k flag, so top_k may be 0 (no top-k filter) or above 64."""
         why = self._verify_refusal()
         if why is not None:
             raise ValueError("prompt_lookup_num_tokens / draft_ids: " + why)
@@ -1886,7 +1936,8 @@ class HipQwen2ForCausalLM(_HipModule):
         eos_set = _eos_set(eos_token_id, self.lcfg.eos_token_id)
         first = ops.argmax(r.last_logits[0]) if sampling is None else ops.sample(r.last_logits[0], *sampling, counter=last)
         need = max_new_tokens - 1                                   # tokens wanted from the steps
-        st = self._verify_session(cache, n, max(max_new_tokens, 1) + k, max_ngram, sampling is not None)
+        st = self._verify_session(cache, n, max(max_new_tokens, 1) + k, max_ngram, sampling is not None,
+                                  **(dict(any_top_k=True) if any_top_k and sampling is not None else {}))
         if sampling is not None:
             self._verify_set_sampling(st, sampling)
         # the history the lookup starts from: the prompt's ids (its tail, if longer than the room) and the first token

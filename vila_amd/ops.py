@@ -288,14 +288,19 @@ def sample(logits: torch.Tensor, temperature: float = 1.0, top_k: int = 50, top_
 
 
 def sample_batch(logits: torch.Tensor, temperature: torch.Tensor, top_k: torch.Tensor, top_p: torch.Tensor, seed: torch.Tensor,
-                 counter: Optional[torch.Tensor] = None, return_dist: bool = False):
+                 counter: Optional[torch.Tensor] = None, return_dist: bool = False, any_top_k: bool = False, return_dense: bool = False):
     """`sample` for up to 16 rows at once (the pick of the batched decode step): logits [n, V] fp32 (rows may be strided), every parameter a
     DEVICE tensor [n] — temperature f32 (<= 0: greedy row = argmax, ties to the lower index), top_k i32 in 1..64, top_p f32 in (0, 1], seed i64
     (the bit pattern of a uint64), counter i32 (optional).  A sampled row gets bit for bit the token `sample` returns for that row.
-    -> token ids [n] i64 (and, on request, (probabilities [n, 64], token ids [n, 64] i32))."""
+    any_top_k (opt-in; default False = the call and the clamp of top_k to 1..64 as ever): `vila_sample_batch_any_f32` — a row with top_k = 0 (no
+    top-k filter) or top_k > 64 is drawn by `sample`'s exact path for such a k, one launch more; its entries of the 64-slot distribution are zeros
+    and -1 ids.  return_dense (with any_top_k): also the dense distributions [n, V] fp32, of which only such rows are written (the others stay 0).
+    -> token ids [n] i64 (and, on request, (probabilities [n, 64], token ids [n, 64] i32), then the dense distributions)."""
     _need(logits, dtype=torch.float32, name="logits")
     if logits.dim() != 2 or logits.stride(1) != 1:
         raise ValueError("sample_batch: logits must be [n, vocab] with contiguous rows")
+    if return_dense and not any_top_k:
+        raise ValueError("sample_batch: return_dense is the dense distribution of the rows any_top_k=True draws")
     n, V = logits.shape
     for name, t, dt in (("temperature", temperature, torch.float32), ("top_k", top_k, torch.int32), ("top_p", top_p, torch.float32),
                         ("seed", seed, torch.int64)) + ((("counter", counter, torch.int32),) if counter is not None else ()):
@@ -308,11 +313,20 @@ def sample_batch(logits: torch.Tensor, temperature: torch.Tensor, top_k: torch.T
     ws = torch.empty((lib.vila_sample_batch_workspace_bytes(n),), device=logits.device, dtype=torch.uint8)
     dist = torch.zeros((n, 128), device=logits.device, dtype=torch.float32) if return_dist else None
     sp = _lib.VilaBatchSampling(temperature.data_ptr(), top_k.data_ptr(), top_p.data_ptr(), seed.data_ptr())
-    check(lib.vila_sample_batch_f32(logits.data_ptr(), logits.stride(0), n, V, C.byref(sp), _p(counter), out.data_ptr(), ws.data_ptr(), _p(dist),
-                                    _stream()), "sample_batch")
+    dense = None
+    if any_top_k:
+        dense = torch.zeros((n, V), device=logits.device, dtype=torch.float32) if return_dense else None
+        check(lib.vila_sample_batch_any_f32(logits.data_ptr(), logits.stride(0), n, V, C.byref(sp), _p(counter), out.data_ptr(), ws.data_ptr(), _p(dist),
+                                            _p(dense), V, _stream()), "sample_batch_any")
+    else:
+        check(lib.vila_sample_batch_f32(logits.data_ptr(), logits.stride(0), n, V, C.byref(sp), _p(counter), out.data_ptr(), ws.data_ptr(), _p(dist),
+                                        _stream()), "sample_batch")
+    res = (out,)
     if return_dist:
-        return out, dist[:, :64].clone(), dist[:, 64:].contiguous().view(torch.int32)
-    return out
+        res += (dist[:, :64].clone(), dist[:, 64:].contiguous().view(torch.int32))
+    if return_dense:
+        res += (dense,)
+    return res if len(res) > 1 else out
 
 
 def penalize(logits: torch.Tensor, counts: torch.Tensor, repetition: torch.Tensor, presence: torch.Tensor, frequency: torch.Tensor,

@@ -511,13 +511,15 @@ def generate_content(model, tokenizer, prompt: Union[str, Sequence[Any]], max_ne
                      seed: Optional[int] = None, streamer=None, prompt_lookup_num_tokens: Optional[int] = None, spec_sample: bool = False,
                      repetition_penalty: Optional[float] = None, presence_penalty: Optional[float] = None,
                      frequency_penalty: Optional[float] = None, logprobs: Optional[bool] = None, top_logprobs: Optional[int] = None,
-                     response_format=None, guided_choice: Optional[Sequence[str]] = None, guided_regex: Optional[str] = None) -> str:
+                     response_format=None, guided_choice: Optional[Sequence[str]] = None, guided_regex: Optional[str] = None,
+                     any_top_k: bool = False) -> str:
     """Text + images in, decoded reply out — the contract of `LlavaLlamaModel.generate_content` for image / text prompts.
     temperature > 0 samples (server.py:185-187: do_sample = temperature > 0, with the request's top_p and HF's default top_k = 50).
     prompt_lookup_num_tokens=k: speculative decoding with k lookup drafts per step (`llm.generate(prompt_lookup_num_tokens=)`); the reply is
     the greedy reply.  A sampled request ignores it unless spec_sample=True (default False), which passes both on
     (`llm.generate(do_sample=True, prompt_lookup_num_tokens=k, spec_sample=True)`, top_k in 1..64): the reply is then the one the same sampled
-    request gives without drafts, a draft being accepted exactly when the request's own draw hits it.
+    request gives without drafts, a draft being accepted exactly when the request's own draw hits it.  any_top_k=True (default False) passes
+    `any_top_k=True` on with them, and the speculating request may carry any top_k >= 0 (0 = no top-k filter).
     streamer: a `TextStream` (or any HF streamer) that receives the new tokens while they are generated (`llm.generate(streamer=...)`).
     repetition_penalty / presence_penalty / frequency_penalty: passed on to `llm.generate` when they are not neutral (1 / 0 / 0 or None); a
     penalised request is not speculated (prompt_lookup_num_tokens is dropped for it: the verify step has no penalised form).
@@ -552,6 +554,8 @@ def generate_content(model, tokenizer, prompt: Union[str, Sequence[Any]], max_ne
         gen.update(do_sample=True, temperature=float(temperature), top_p=float(top_p), top_k=int(top_k), seed=seed)
         if spec_sample and prompt_lookup_num_tokens is not None:
             gen.update(prompt_lookup_num_tokens=int(prompt_lookup_num_tokens), spec_sample=True)
+            if any_top_k:                              # (keyword only when asked: a call without it makes the call it always made)
+                gen.update(any_top_k=True)
     elif prompt_lookup_num_tokens is not None:
         gen.update(prompt_lookup_num_tokens=int(prompt_lookup_num_tokens))
     if streamer is not None:
@@ -772,13 +776,16 @@ class HipBatchEngine:
     constraints=True opens the session with a token automaton per row (`batch_open(constraints=True, max_states=, max_classes=)`: a table of
     max_states x max_classes entries per row): `compile_constraint` turns a request's `response_format` / `guided_choice` / `guided_regex` into an
     automaton (cached per vocabulary), `admit` takes it, and a `ContinuousBatcher(constraints=True)` puts such requests into rows.  compiler: the
-    `ConstraintCompiler` to use in place of the one derived from a byte-level BPE tokenizer."""
+    `ConstraintCompiler` to use in place of the one derived from a byte-level BPE tokenizer.
+    any_top_k=True (with sampling=True) opens the session with `batch_open(any_top_k=True)`: a sampled row may then carry any top_k >= 0 (0 = no
+    top-k filter, i.e. pure top-p sampling; k > 64), and a `ContinuousBatcher(batch_sampled=True, any_top_k=True)` puts such requests into rows."""
 
     def __init__(self, model, tokenizer, n_slots: int = 8, max_ctx: int = 2048, max_new_tokens: int = 1024, eos_token_id=None,
                  sampling: bool = False, share_prefix: bool = False, min_shared_len: int = 2048, penalties: bool = False, logprobs: bool = False,
-                 constraints: bool = False, max_states: int = 512, max_classes: int = 4096, compiler=None):
+                 constraints: bool = False, max_states: int = 512, max_classes: int = 4096, compiler=None, any_top_k: bool = False):
         self.model, self.tokenizer = model, tokenizer
         self.sampling = bool(sampling)
+        self.any_top_k = bool(any_top_k) and self.sampling  # batch_open(any_top_k=True): a sampled row's top_k may be 0 or above 64
         self.constraints = bool(constraints)                # batch_open(constraints=True, max_states=, max_classes=): `admit` takes a row's automaton
         self.max_states, self.max_classes = int(max_states), int(max_classes)
         self.compiler = compiler                            # a `ConstraintCompiler` (for a tokenizer that is not byte-level BPE); default: the tokenizer's
@@ -799,6 +806,8 @@ class HipBatchEngine:
         llm = self.model.llm
         if self.st is None or getattr(llm, "_bdecode", None) is not self.st:       # first use, or the weights moved and the session was dropped
             kw = dict(sampling=True) if self.sampling else {}
+            if self.any_top_k:
+                kw["any_top_k"] = True
             if self.share_prefix:
                 kw["shared_prefix"] = True
                 self._pinned = None                                                 # a new session holds no prefix
@@ -869,6 +878,11 @@ class HipBatchEngine:
     def batches_sampled(self) -> bool:
         """Whether a sampled request (top_k in 1..64) can take a row of this engine's batch."""
         return self.sampling
+
+    @property
+    def batches_any_top_k(self) -> bool:
+        """Whether a sampled request with top_k = 0 (no top-k filter) or top_k > 64 can take a row of this engine's batch."""
+        return self.any_top_k
 
     @property
     def batches_penalties(self) -> bool:
@@ -962,7 +976,11 @@ class ContinuousBatcher:
     temperature > 0 and top_k (default 50) in 1..64 takes a free row like a greedy one — the reference's default request (0.2 / 0.9) then
     batches instead of stalling the line.  The trade: the batched step sums in another order than the solo step, so the ids of a sampled
     request are no longer those of its solo run (same distribution, same seed -> same reply within the batched path).  A request without a
-    seed gets one derived as `generate` derives it.  top_k = 0 or > 64 stays solo.
+    seed gets one derived as `generate` derives it.  top_k = 0 or > 64 stays solo, unless:
+    any_top_k=True (opt-in, with batch_sampled; needs an engine whose `batches_any_top_k` is true, i.e. `HipBatchEngine(sampling=True,
+    any_top_k=True)`): a sampled request with ANY top_k >= 0 takes a row — top_k = 0, no top-k filter, is how an OpenAI-style client samples
+    (temperature + top_p), and without the flag one such request at the head of the line waits for the live rows to drain and blocks later
+    admissions.  Its row is drawn on the device by the solo sampler's exact path.
     share_prefix=True (opt-in; needs an engine whose `shares_prefix` is true, i.e. `HipBatchEngine(share_prefix=True)`): requests over the same
     media share the K/V of their common prefix.  When no live row shares the current prefix, a request with media that fits a slot PINS its own
     (`engine.pin`: one tower / projector / prefill run); later requests with the same key (`engine.prepare(...).key == engine.pinned_key`) are
@@ -981,11 +999,12 @@ class ContinuousBatcher:
     (`engine.solo` gets the field).  With a `stream` it is refused.  A request that does not ask is served exactly as before."""
 
     def __init__(self, engine, max_batch: int = 8, chunk: int = 8, batch_sampled: bool = False, share_prefix: bool = False, penalties: bool = False,
-                 logprobs: bool = False, constraints: bool = False):
+                 logprobs: bool = False, constraints: bool = False, any_top_k: bool = False):
         import queue
         import threading
         self.engine = engine
         self.batch_sampled = bool(batch_sampled) and bool(getattr(engine, "batches_sampled", False))
+        self.any_top_k = bool(any_top_k) and self.batch_sampled and bool(getattr(engine, "batches_any_top_k", False))
         self.penalties = bool(penalties) and bool(getattr(engine, "batches_penalties", False))
         self.logprobs = bool(logprobs) and bool(getattr(engine, "batches_logprobs", False))
         self.constraints = bool(constraints) and bool(getattr(engine, "batches_constraints", False))
@@ -1004,7 +1023,7 @@ class ContinuousBatcher:
 
     def submit(self, prompt, max_new_tokens: int = 128, system: Optional[str] = None, stream: Optional["TextStream"] = None, **gen):
         """-> Future of the decoded reply.  gen: temperature / top_p / top_k / seed — a request with temperature > 0 is a solo one, unless the
-        batcher was built with batch_sampled=True and the request's top_k lies in 1..64 (then it takes a row).
+        batcher was built with batch_sampled=True and the request's top_k lies in 1..64 (with any_top_k=True: is >= 0); then it takes a row.
         stream: a `TextStream` that receives the request's tokens while the row is still decoding — its first token at admission, then
         the new ones after every chunk of steps (server.py:241-270 streams a reply as it is generated); `end()` when the row retires,
         `fail()` with the exception the future gets."""
@@ -1044,7 +1063,7 @@ class ContinuousBatcher:
             return None
         g = req.gen
         top_k = 50 if g.get("top_k") is None else int(g["top_k"])
-        if not 1 <= top_k <= 64:
+        if not (1 <= top_k <= 64 or (self.any_top_k and top_k >= 0)):
             return None
         seed = g.get("seed")
         if seed is None:                                               # once per request: kept in `gen`, so a retry of the admission re-uses it
@@ -1306,6 +1325,7 @@ def _request_models():
             temperature=(Optional[float], 0.2), top_p=(Optional[float], 0.9), stream=(Optional[bool], False),      # server.py:101-102
             repetition_penalty=(Optional[float], 1.0), presence_penalty=(Optional[float], 0.0), frequency_penalty=(Optional[float], 0.0),
             logprobs=(Optional[bool], False), top_logprobs=(Optional[int], None),                                  # OpenAI's fields; top_logprobs 0..20
+            top_k=(Optional[int], None),                         # HF's / vLLM's field: absent = 50; 0 (HF) or -1 (vLLM) = no top-k filter
             # structured output: the reference's ResponseFormat ({"type": "json_schema", "json_schema": {"schema": ...}}), vLLM's guided fields
             response_format=(Optional[Dict[str, Any]], None), guided_choice=(Optional[List[str]], None), guided_regex=(Optional[str], None))
         _MODELS = (ChatMessage, ChatCompletionRequest)
@@ -1322,7 +1342,7 @@ def continuous_batching(model) -> bool:
 def create_app(model, tokenizer, model_name: str = "NVILA-8B", batch_window_s: Optional[float] = None, max_batch: int = 8,
                stream_timeout_s: Optional[float] = 600.0, batch_sampled: bool = False, max_ctx: int = 2048,
                prompt_lookup_num_tokens: Optional[int] = None, spec_sample: bool = False, share_prefix: bool = False, penalties: bool = False,
-               logprobs: bool = False, constraints: bool = False):
+               logprobs: bool = False, constraints: bool = False, any_top_k: bool = False):
     """FastAPI app with the reference's POST /chat/completions (server.py:171-290).  Import-time optional: needs fastapi + pydantic.
     batch_window_s: when set (any value), requests go through a batcher whose ONE worker thread owns the model: `ContinuousBatcher` (greedy
     requests join / leave the batched decode step between steps; sampled ones run solo on the same thread) where the model has the batched
@@ -1355,7 +1375,12 @@ def create_app(model, tokenizer, model_name: str = "NVILA-8B", batch_window_s: O
     to the pattern (`generate_content` has the served subsets; `max_tokens` can still cut the reply).  A request without the fields is served exactly
     as before.  A compile error (`json_object`, an unsupported keyword, a pattern the vocabulary cannot spell), two of the fields at once, and any of
     them together with `stream` come back as the usual 500 body.  constraints=True (ContinuousBatcher only; default off): the batched session holds
-    an automaton per row, so such a request takes a row; without it such a request runs solo, as `penalties=` does it."""
+    an automaton per row, so such a request takes a row; without it such a request runs solo, as `penalties=` does it.
+    The request's `top_k` (optional): absent = 50, today's calls and bits; 0, or vLLM's -1, = no top-k filter (pure temperature / top-p sampling,
+    what an OpenAI-style client means); any other negative value comes back as the usual 500 body.  A greedy request ignores it.
+    any_top_k=True (default off; with batch_sampled, ContinuousBatcher only): the batched session's sampler serves every top_k >= 0, so a sampled
+    request with top_k = 0 or > 64 takes a row; without it such a request runs solo, as a penalised one does without `penalties=`.  With
+    spec_sample (and prompt_lookup_num_tokens) it lets solo sampled requests with such a top_k speculate as well."""
     from fastapi import FastAPI
     from fastapi.responses import JSONResponse, StreamingResponse
 
@@ -1379,10 +1404,13 @@ def create_app(model, tokenizer, model_name: str = "NVILA-8B", batch_window_s: O
                 kw["logprobs"] = True
             if constraints:
                 kw["constraints"] = True
+            if any_top_k and batch_sampled:
+                kw["any_top_k"] = True
             engine = HipBatchEngine(model, tokenizer, **kw)
             batcher = ContinuousBatcher(engine, max_batch=max_batch, batch_sampled=batch_sampled, **(dict(share_prefix=True) if share_prefix else {}),
                                         **(dict(penalties=True) if penalties else {}), **(dict(logprobs=True) if logprobs else {}),
-                                        **(dict(constraints=True) if constraints else {}))
+                                        **(dict(constraints=True) if constraints else {}),
+                                        **(dict(any_top_k=True) if any_top_k and batch_sampled else {}))
         else:
             batcher = RequestBatcher(model, tokenizer, window_s=batch_window_s)
     app.state.batcher = batcher
@@ -1421,9 +1449,11 @@ def create_app(model, tokenizer, model_name: str = "NVILA-8B", batch_window_s: O
         with model_lock, torch.inference_mode():
             kw = {} if prompt_lookup_num_tokens is None else dict(prompt_lookup_num_tokens=prompt_lookup_num_tokens)
             kw.update(pen)                              # (non-neutral penalties only; generate_content then drops the speculation)
-            top_k = 50                                  # the endpoint carries no top_k: a solo request samples with generate_content's default
-            if spec_sample and kw and temperature and temperature > 0 and 1 <= top_k <= 64:
+            top_k = kw.get("top_k", 50)                 # a request without the field samples with generate_content's default
+            if spec_sample and kw and temperature and temperature > 0 and (1 <= top_k <= 64 or (any_top_k and top_k >= 0)):
                 kw.update(spec_sample=True, top_k=top_k)
+                if any_top_k and not 1 <= top_k <= 64:
+                    kw.update(any_top_k=True)
             return generate_content(model, tokenizer, parts, max_new_tokens=n, system=system, temperature=temperature, top_p=top_p, streamer=streamer, **kw)
 
     async def chat_completions(request):
@@ -1446,6 +1476,14 @@ def create_app(model, tokenizer, model_name: str = "NVILA-8B", batch_window_s: O
                 pen = dict(pen, logprobs=True, top_logprobs=n_top)
             # structured output likewise; refused with stream before anything runs
             pen = dict(pen, **check_structured_request({k: getattr(request, k, None) for k in STRUCTURED_FIELDS}, bool(request.stream)))
+            # top_k likewise: it travels only for a sampled request that names one (-1, vLLM's "no filter", is HF's 0)
+            top_k = getattr(request, "top_k", None)
+            if top_k is not None:
+                top_k = 0 if int(top_k) == -1 else int(top_k)
+                if top_k < 0:
+                    raise ValueError(f"`top_k` has to be a non-negative integer (0 or -1: no top-k filter), but is {request.top_k}")
+                if temperature and temperature > 0:
+                    pen = dict(pen, top_k=top_k)
             loop = asyncio.get_running_loop()
             if request.stream:
                 # server.py:241-270: the reply leaves as it is generated.  The tokens reach a `TextStream` from whoever runs the request (the
