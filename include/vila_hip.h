@@ -594,6 +594,20 @@ int vila_gemm_batch_bf16(const void* x, int64_t ldx, int n, const void* W, const
 int vila_qkv_batch_bf16(const void* x, int64_t ldx, int n, const void* Wqkv, const void* bias, void* q_out, int64_t ldq, void* kcache, void* vcache,
                         int64_t slot_stride, const int32_t* pos, const float* rope_cs, int q_heads, int kv_heads, int head_dim, int max_ctx, int K,
                         vila_stream_t stream);
+/* The fused q|k|v projections of the W4A16 decode steps on the caller's buffers, as those steps launch them (tests/test_gpu_w4_elements.py).
+ * Wq / Wsz: the packed (q_heads + 2 kv_heads) * head_dim rows of a layer's fused q|k|v matrix, q and k heads RoPE-interleaved (above);
+ * head_dim % 16 == 0, K % 128 == 0; bias [N] in natural q | k | v order or NULL; rope_cs fp32, cos | sin.
+ * vila_qkv_w4_bf16 (gemv_w4.hip mode 3, the solo step's): x [K] with an optional fused RMSNorm (norm_w NULL: none); RoPE from rope_cs[head_dim];
+ *   q goes to q_out [q_heads * head_dim], K and V to row *pos (device int32) of kcache / vcache [kv_heads][max_ctx][head_dim]; *pos >= max_ctx
+ *   writes q and no K/V.
+ * vila_qkv_w4_batch_bf16 (gemv_w4_batch.hip mode 2): the arguments of vila_qkv_batch_bf16 with Wq / Wsz in place of Wqkv, same contract.
+ * Deterministic; nothing else is written.  Every refusal (-1) comes before anything is launched. */
+int vila_qkv_w4_bf16(const void* x, const void* norm_w, float eps, const void* Wq, const void* Wsz, const void* bias, void* q_out,
+                     void* kcache, void* vcache, const int32_t* pos, const float* rope_cs, int q_heads, int kv_heads, int head_dim,
+                     int max_ctx, int K, vila_stream_t stream);
+int vila_qkv_w4_batch_bf16(const void* x, int64_t ldx, int n, const void* Wq, const void* Wsz, const void* bias, void* q_out, int64_t ldq,
+                           void* kcache, void* vcache, int64_t slot_stride, const int32_t* pos, const float* rope_cs, int q_heads, int kv_heads,
+                           int head_dim, int max_ctx, int K, vila_stream_t stream);
 /* vila_llm_decode_step_batch with the q|k|v, o, gate/up and down projections of every layer read from `qlayers` [host] (W4A16 batched GEMVs).
  * `w` still supplies embed, norms, the q/k/v biases (one contiguous q|k|v vector) and the bf16 lm_head; its projection pointers are not read.
  * Same contract and limits as vila_llm_decode_step_batch (head_dim 128, max_ctx <= 2048, or <= 32768 with the _ctx workspace, 1 <= n <= min(16, n_slots), q_heads * head_dim ==

@@ -750,3 +750,191 @@ def depth_to_space_index_map(B: int, g: int, k: int) -> torch.Tensor:
     pos[y] = torch.arange(y.numel())
     assert bool((pos[1:] >= 0).all())
     return pos[1:].reshape(B, g * g)
+
+
+# ---- the W4A16 kernels (vila_amd/csrc/gemv_w4.hip, gemv_w4_batch.hip, gemm_w4.hip): exact cases, exact references and a per-element bound ------
+# (tests/test_w4_bound_cpu.py proves them, tests/test_gpu_w4_elements.py uses them).  The kernels never dequantise: per 128-wide group they sum
+# x (128 + q) on the matrix cores, remove (128 + zero) sum(x) in fp32 and add scale * that to a running total with one fmaf.  With integer
+# activations and power-of-two scales every one of those values is an integer multiple of 2^kmin below 2^24 of them: each operation is exact, the
+# fp32 value before the epilogue equals the fp64 product whatever the order of groups, waves, tiles or K-slices, and a plain output is the bf16
+# rounding of that product BIT FOR BIT.  Ordinary inputs get a bound derived from what the kernels add (w4_generic_acc).
+def exact_w4(shape, seed, log2_scale=(-7, -6, -5), device="cpu"):
+    """Weights exactly representable as (q - zero) * 2^k with every group spanning q = 0..15.  device "cuda": drawn there (other numbers, the same
+    construction), for matrices of 10^8 weights."""
+    N, K = shape
+    g = torch.Generator(device=device).manual_seed(seed)
+    q = torch.randint(0, 16, (N, K // 128, 128), generator=g, device=device)
+    q[..., 0], q[..., 1] = 0, 15
+    zero = torch.randint(4, 12, (N, K // 128, 1), generator=g, device=device)
+    k = torch.tensor(log2_scale, device=device)[torch.randint(0, len(log2_scale), (N, K // 128, 1), generator=g, device=device)]
+    return ((q - zero).float() * torch.exp2(k.float())).view(N, K)
+
+
+W4_EXACT_QZ = 11            # max |q - zero| of exact_w4: q in 0..15, zero in 4..11
+W4_EXACT_ADDEND = 64        # bias and residual of an exact case: integers up to this, times 2^kmin (the residual times res_mult as well)
+
+
+def w4_exact_case(N: int, K: int, seed: int, log2_scales=(-7, -6, -5), x_max: int = 4, rows: int = 16, gateup: bool = False, heads=None,
+                  normed: bool = False, x_pow: int = 1, device="cpu") -> dict:
+    """One problem of the exact regime -> dict:
+      w [N, K] fp32 (gateup: w = gate, w_up = up), exact_w4 weights; mat: their W4Matrix on `device` (heads = (q, kv, head_dim): packed with
+      quant.rope_interleave_rows, N = (q + 2 kv) head_dim), quantise -> dequantise asserted to be the identity;
+      x [rows, K] bf16: integers in [-x_max, x_max]; x_eff: what the kernel multiplies (x itself);
+      bias [N], res [rows, N] bf16: integers up to 64 times 2^kmin (the residual also times res_mult, the power of two next below sqrt(K / 128), so
+      that it stays of the size of the projection's own bf16 spacing at every K and the order of the two roundings of the residual epilogue shows);
+      core [rows, N] fp64 = x_eff . w^T (core_up with gateup), exact: every term is an integer multiple of 2^kmin.
+    normed (the fused RMSNorm of stage_x_w4, gemv_w4.hip:63-71): every |x_k| = 2^x_pow with random signs, norm_w integers in [-x_max, x_max]
+    (zeros included), eps = 1e-6.  Then sum x^2 = K 4^x_pow and its mean 4^x_pow are exact in fp32 in any order, rstd = rsqrtf(4^x_pow + 1e-6) is
+    2^-x_pow (1 - 5e-7 / 4^x_pow) up to a few ulp, x rstd = +-(1 - 5e-7 ..): 2^-9 away from the nearest bf16 rounding tie, so bfround(x rstd) is +-1
+    whatever the last ulp of rsqrtf or of the division, and the staged value bfround(norm_w * +-1) = +-norm_w.  x_eff holds those (x_pow >= 0: with
+    |x| << 1e-3 the eps would dominate).
+    Asserted here: the worst partial sum G 128 x_max 11 2^(kmax - kmin) plus bias and residual stays below 2^24 in units of 2^kmin, so every
+    intermediate (a group's sum of x (128 + q) < 128 x_max 143 < 2^17, (128 + zero) sum x <= 139 * 128 x_max, their integer difference, the fmaf
+    with a power-of-two scale, the wave and slab partials, bias, bfround(v) + residual) is exact in fp32."""
+    from vila_amd.quant import W4Matrix, rope_interleave_rows
+    kmin, kmax = min(log2_scales), max(log2_scales)
+    G, u = K // 128, 2.0 ** min(log2_scales)
+    if heads is not None:
+        nq, nkv, hd = heads
+        assert N == (nq + 2 * nkv) * hd and not gateup
+    g = torch.Generator().manual_seed(seed + 12345)
+    res_mult = 1
+    while 4 * res_mult * res_mult <= G:
+        res_mult *= 2
+    worst = G * 128 * x_max * W4_EXACT_QZ * 2 ** (kmax - kmin) + W4_EXACT_ADDEND * (1 + res_mult)
+    assert worst < 2 ** 24 and x_pow >= 0, (N, K, log2_scales, x_max, worst)
+    c = {"N": N, "K": K, "u": u, "gateup": gateup, "heads": heads, "eps": 1e-6}
+    wdev = device if N * K >= 1 << 24 else "cpu"             # (matrices of 10^7 weights and more are drawn where they are used)
+    c["w"] = exact_w4((N, K), seed, log2_scales, wdev)
+    if gateup:
+        c["w_up"] = exact_w4((N, K), seed + 1, log2_scales, wdev)
+    if normed:
+        c["x"] = ((torch.randint(0, 2, (rows, K), generator=g) * 2 - 1).float() * 2.0 ** x_pow).to(torch.bfloat16)
+        c["norm_w"] = torch.randint(-x_max, x_max + 1, (K,), generator=g).to(torch.bfloat16)
+        c["x_eff"] = (torch.sign(c["x"].float()) * c["norm_w"].float()).to(torch.bfloat16)
+    else:
+        c["x"] = torch.randint(-x_max, x_max + 1, (rows, K), generator=g).to(torch.bfloat16)
+        c["norm_w"], c["x_eff"] = None, c["x"]
+    c["bias"] = (torch.randint(-W4_EXACT_ADDEND, W4_EXACT_ADDEND + 1, (N,), generator=g).float() * u).to(torch.bfloat16)
+    c["res"] = (torch.randint(-W4_EXACT_ADDEND, W4_EXACT_ADDEND + 1, (rows, N), generator=g).float() * (u * res_mult)).to(torch.bfloat16)
+    assert float(c["bias"].float().abs().max()) <= W4_EXACT_ADDEND * u and float(c["res"].float().abs().max()) <= W4_EXACT_ADDEND * u * res_mult
+    dev = torch.device(device)
+    for k in ("w", "w_up", "x", "x_eff", "norm_w", "bias", "res"):
+        if c.get(k) is not None:
+            c[k] = c[k].to(dev)
+    perm = rope_interleave_rows(nq + nkv, nq + 2 * nkv, hd, device=dev) if heads is not None else None
+    c["mat"] = W4Matrix.pack(c["w"], c.get("w_up"), row_perm=perm)
+    d = c["mat"].dequantized()
+    for got, want in zip(d if gateup else (d,), (c["w"], c.get("w_up"))):
+        assert torch.equal(got, want), f"quantise -> dequantise of the exact weights ({N}, {K}) is not the identity"
+    xe = c["x_eff"].double()
+    c["core"] = xe @ c["w"].double().t()
+    if gateup:
+        c["core_up"] = xe @ c["w_up"].double().t()
+    assert float(c["core"].abs().max()) / u + W4_EXACT_ADDEND * (1 + res_mult) < 2 ** 24
+    return c
+
+
+def w4_exact_plain_ref(core64: torch.Tensor, bias64=None, res64=None) -> torch.Tensor:
+    """The bf16 result of a plain epilogue in the exact regime, to be compared as bits.  v = sum + bias is exact; without a residual the output is
+    its bf16 rounding; with one the kernels round twice, f2bf(bfround(v) + r) (gemv_w4.hip:233-235, gemv_w4_batch.hip:118-120, gemm_w4.hip:67-69),
+    and bfround(v) + r is exact in fp32 too (both are multiples of 2^kmin below 2^24 of them)."""
+    v = core64 if bias64 is None else core64 + bias64
+    if res64 is None:
+        return v.to(torch.bfloat16)
+    return (bf16_round64(v) + res64).to(torch.bfloat16)
+
+
+def assert_bits_equal(out: torch.Tensor, ref: torch.Tensor, what: str = "") -> None:
+    """out and ref, bf16 [rows, cols], identical bit for bit; a failure states the count and the (row, col, got, expected) of the first few."""
+    assert out.shape == ref.shape and out.dtype == ref.dtype == torch.bfloat16, (tuple(out.shape), tuple(ref.shape), out.dtype, ref.dtype)
+    o, r = out.contiguous().view(torch.int16), ref.to(out.device).contiguous().view(torch.int16)
+    bad = o != r
+    k = int(bad.sum())
+    if k:
+        o2, r2 = out.reshape(-1, out.shape[-1]), ref.to(out.device).reshape(-1, out.shape[-1])
+        at = [(int(i), int(j), float(o2[i, j]), float(r2[i, j])) for i, j in bad.reshape(o2.shape).nonzero()[:8].tolist()]
+        raise AssertionError(f"{what}: {k} of {out.numel()} elements differ from the exact result; first (row, col, got, expected) {at}")
+
+
+def w4_unpack(logical):
+    """quant.py's logical arrays -> (q [N, K], zero [N, G], scale [N, G]) in fp64: the integers and the bf16 scales the kernels read."""
+    wq, wsz = logical
+    N, K8 = wq.shape
+    q = torch.empty((N, K8, 8), dtype=torch.float64, device=wq.device)
+    for p in range(4):
+        q[..., 2 * p] = ((wq >> (4 * p)) & 0xF).double()
+        q[..., 2 * p + 1] = ((wq >> (4 * (p + 4))) & 0xF).double()
+    scale = (wsz & 0xFFFF).to(torch.int16).view(torch.bfloat16).double()
+    zero = ((wsz >> 16) & 0xFFFF).to(torch.int16).view(torch.bfloat16).double() - 128.0
+    return q.view(N, K8 * 8), zero, scale
+
+
+W4_SUM_OPS = 129            # roundings one product of a group passes at most: 128 additions of an fp32 sum in any order (the four MFMAs of a group
+                            # add 32 products each to an accumulator, two chains, gemv_w4.hip:208-218, gemv_w4_batch.hip:76-86, gemm_w4.hip:143-155)
+                            # and the addition of the two chains (gemv_w4.hip:219).  The group sum of x passes at most 128 too (an MFMA against ones in
+                            # gemv_w4_batch.hip:78; three tree levels and four shuffles, 7, in gemv_w4.hip:77-84 and gemm_w4.hip:103-106) and the
+                            # product with 128 + zero one more (gemv_w4.hip:219, gemv_w4_batch.hip:92, gemm_w4.hip:165)
+W4_CHAIN_EXTRA = 20         # roundings behind a group's difference D - zp S besides the G fmaf of the chain: the subtraction itself, the <= 16 wave
+                            # partials (gemv_w4.hip:229, gemv_w4_batch.hip:110-114) or <= 8 slabs (gemm_w4.hip:201), the bias, and the fp32 addition of
+                            # the residual
+
+
+W4_NORM_DEPTH = 60          # fp32 roundings behind x rstd in stage_x_w4 (gemv_w4.hip:44-71): a thread adds at most 4 chunks of 8 squares, 6 shuffle levels,
+                            # the <= 16 wave sums, / K, + eps, rsqrtf (2), the product; half of the sum's relative error reaches rstd, the bound takes all
+
+
+def w4_staged_norm(x64: torch.Tensor, norm_w64: torch.Tensor, eps: float):
+    """The activation stage_x_w4 leaves in LDS with a fused RMSNorm, bfround(w * bfround(x rstd)) (gemv_w4.hip:70-71) -> (x_eff bf16, slack fp64).
+    As rmsnorm_fwd_bound: an element whose x rstd lies within the fp32 error of a bf16 rounding tie may come out one inner ulp away, which moves
+    the staged value by at most |w| ulp and then by one bf16 spacing of the product; slack holds that (0 elsewhere), for w4_generic_acc."""
+    _, _, inner = norm_stats64(x64, True, eps)
+    near, ulp = bf16_near_tie(inner, W4_NORM_DEPTH * FP32_U * inner.abs())
+    staged = norm_w64 * bf16_round64(inner)
+    slack = torch.where(near, norm_w64.abs() * ulp + 2 * BF16_U * staged.abs(), torch.zeros_like(staged))
+    return staged.to(torch.bfloat16), slack
+
+
+def w4_generic_acc(x64: torch.Tensor, q64: torch.Tensor, zero64: torch.Tensor, scale64: torch.Tensor, x_slack64: torch.Tensor = None):
+    """-> (core [n, N], acc [n, N]) in fp64 for x64 [n, K] and unpacked weights [N, K] / [N, G]: core = x . ((q - zero) scale)^T, the product with
+    the dequantised weights, and acc, the first-order bound on the fp32 error of the kernels' sum before the epilogue,
+        2^-24 [ 129 sum_g s_g (sum_k |x_k| (128 + q_k) + zp_g sum_k |x_k|)  +  (G + 20) sum_g s_g sum_k |x_k| |q_k - z_g| ],   zp = 128 + zero.
+    Per group: D = the fp32 sum of 128 exact products x (128 + q) (bf16 x bf16 is exact in fp32) in any order, off by 129 * 2^-24 of the sum of
+    their magnitudes; P = zp S with S the group sum of x, off by (128 + 1) 2^-24 zp sum |x|; the subtraction D - P rounds once, at the size of the
+    true difference sum x (q - z) (first order), which sum |x| |q - z| bounds; so does every later operation the difference passes, each scaled by
+    s: the fmaf of its own and of the later groups of the chain (<= G), the partials, the bias, the residual (W4_CHAIN_EXTRA).  The first term is
+    the price of never dequantising: it is of the size of K 2^-24 * 129 * 135 |x| s, where a dequantising kernel would pay K 2^-24 |x| |w|.
+    x_slack64 [n, K] (w4_staged_norm): by how much a staged activation may differ from x64; acc gains x_slack . |w|^T."""
+    N, K = q64.shape
+    G = K // 128
+    n = x64.shape[0]
+    xa = x64.abs()
+    sk = scale64.repeat_interleave(128, 1)
+    zk = zero64.repeat_interleave(128, 1)
+    core = x64 @ ((q64 - zk) * sk).t()
+    t1 = xa @ ((128.0 + q64) * sk).t()
+    t2 = xa.view(n, G, 128).sum(-1) @ ((128.0 + zero64) * scale64).t()
+    t3 = xa @ ((q64 - zk).abs() * sk).t()
+    acc = FP32_U * (W4_SUM_OPS * (t1 + t2) + (G + W4_CHAIN_EXTRA) * t3)
+    if x_slack64 is not None:
+        acc = acc + x_slack64 @ ((q64 - zk).abs() * sk).t()
+    return core, acc
+
+
+def w4_absprod(acc64: torch.Tensor, K: int) -> torch.Tensor:
+    """The `absprod` argument with which bgemm_acc_bound(., K) gives (1 + 2^-8) acc: the W4 kernels' epilogues round as bgemm_epilogue does
+    (gemv_w4_batch.hip's header), so bgemm_plain_bound / bgemm_gateup_bound / bgemm_qkv_bound supply the rounding terms and this the accumulation
+    term.  acc = 0 (the exact regime): the epilogue's own roundings and silu_f's error alone."""
+    return acc64 / ((K + BGEMM_EXTRA_OPS) * FP32_U)
+
+
+def w4_generic_bound(kind: str, K: int, core64, acc64, core_up64=None, acc_up64=None, bias64=None, res64=None, cs64=None, heads=None):
+    """-> (ref, bound) per element for ordinary inputs.  kind "plain" (modes 0 and 4, and the prefill's q|k|v form, which adds the bias and stores in
+    natural order without RoPE), "gateup", "qkv" (bias + RoPE; ref in natural q | k | v column order).  The bgemm bounds add |bias| and |residual|
+    to absprod, (K + 10) 2^-24 of them: more than the one rounding each really costs, and below 1e-5 of either."""
+    if kind == "plain":
+        return bgemm_plain_bound(core64, w4_absprod(acc64, K), K, bias64, res64)
+    if kind == "gateup":
+        return bgemm_gateup_bound(core64, w4_absprod(acc64, K), core_up64, w4_absprod(acc_up64, K), K)
+    assert kind == "qkv"
+    return bgemm_qkv_bound(core64, w4_absprod(acc64, K), K, bias64, cs64, *heads)

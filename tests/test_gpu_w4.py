@@ -12,21 +12,10 @@ import pytest
 import torch
 
 from oracle import vila_oracle as O
-from tests.gpu_util import max_abs, rel_l2
+from tests.gpu_util import exact_w4 as _exact_w4, max_abs, rel_l2
 from vila_amd import configs, synthetic
 
 pytestmark = pytest.mark.gpu
-
-
-def _exact_w4(shape, seed, log2_scale=(-7, -6, -5)):
-    """Weights exactly representable as (q - zero) * 2^k with every group spanning q = 0..15."""
-    N, K = shape
-    g = torch.Generator().manual_seed(seed)
-    q = torch.randint(0, 16, (N, K // 128, 128), generator=g)
-    q[..., 0], q[..., 1] = 0, 15
-    zero = torch.randint(4, 12, (N, K // 128, 1), generator=g)
-    k = torch.tensor(log2_scale)[torch.randint(0, len(log2_scale), (N, K // 128, 1), generator=g)]
-    return ((q - zero).float() * torch.exp2(k.float())).view(N, K)
 
 
 def test_quantizer_roundtrip_and_packing():

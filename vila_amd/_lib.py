@@ -272,6 +272,10 @@ PROTOTYPES = {
                                      c_int, c_int, c_void_p]),
     "vila_qkv_batch_bf16": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
                                     c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "vila_qkv_w4_bf16": (c_int, [c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "vila_qkv_w4_batch_bf16": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p,
+                                       c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "vila_llm_decode_batch_w4_workspace_bytes": (c_size_t, [C.POINTER(VilaLlmShape), c_int]),
     "vila_llm_decode_batch_w4_workspace_bytes_ctx": (c_size_t, [C.POINTER(VilaLlmShape), c_int, c_int]),
     "vila_llm_decode_step_batch_w4": (c_int, [C.POINTER(VilaLlmWeights), C.POINTER(VilaLlmLayerW4), C.POINTER(VilaKvCache),

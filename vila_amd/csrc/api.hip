@@ -1391,6 +1391,37 @@ extern "C" int vila_gemv_w4_batch_bf16(const void* x, int64_t ldx, int n, const 
     g.y = B(y); g.ldy = N; g.n = n; g.N = N; g.K = K; g.mode = mode;
     return launch_gemv_w4_batch(g, S(stream));
 }
+
+// ---- operator entries of the two fused q|k|v W4 kernels (include/vila_hip.h; tests/test_gpu_w4_elements.py) ------------------------------
+// The decode steps' own launchers on caller-owned buffers: the argument structs filled as vila_llm_decode_step_w4 (mode 3) and the batched step
+// (mode 2) fill them, launch_gemv_w4 / launch_gemv_w4_batch unchanged.  What the steps guarantee by construction is refused here first.
+extern "C" int vila_qkv_w4_bf16(const void* x, const void* norm_w, float eps, const void* Wq, const void* Wsz, const void* bias, void* q_out,
+                                void* kcache, void* vcache, const int32_t* pos, const float* rope_cs, int q_heads, int kv_heads, int head_dim,
+                                int max_ctx, int K, vila_stream_t stream) {
+    VILA_REQUIRE(x != nullptr && Wq != nullptr && Wsz != nullptr && q_out != nullptr && kcache != nullptr && vcache != nullptr && pos != nullptr &&
+                 rope_cs != nullptr, "vila_qkv_w4_bf16: NULL pointer");
+    VILA_REQUIRE(q_heads > 0 && kv_heads > 0 && head_dim > 0 && head_dim % 16 == 0 && max_ctx > 0 && K > 0,
+                 "vila_qkv_w4_bf16: q_heads=%d, kv_heads=%d, head_dim=%d (a multiple of 16), max_ctx=%d, K=%d", q_heads, kv_heads, head_dim, max_ctx, K);
+    GemvW4Args g{};
+    g.x = B(x); g.norm_w = B(norm_w); g.eps = eps; g.Wq = (const uint32_t*)Wq; g.Wsz = (const uint32_t*)Wsz; g.bias = B(bias);
+    g.K = K; g.N = (q_heads + 2 * kv_heads) * head_dim; g.mode = 3; g.q_out = B(q_out); g.kcache = B(kcache); g.vcache = B(vcache); g.pos_ptr = pos;
+    g.rope_cs = rope_cs; g.nq = q_heads; g.nkv = kv_heads; g.hd = head_dim; g.max_ctx = max_ctx;
+    return launch_gemv_w4(g, S(stream));
+}
+extern "C" int vila_qkv_w4_batch_bf16(const void* x, int64_t ldx, int n, const void* Wq, const void* Wsz, const void* bias, void* q_out, int64_t ldq,
+                                      void* kcache, void* vcache, int64_t slot_stride, const int32_t* pos, const float* rope_cs, int q_heads, int kv_heads,
+                                      int head_dim, int max_ctx, int K, vila_stream_t stream) {
+    VILA_REQUIRE(x != nullptr && Wq != nullptr && Wsz != nullptr && q_out != nullptr && kcache != nullptr && vcache != nullptr && pos != nullptr &&
+                 rope_cs != nullptr, "vila_qkv_w4_batch_bf16: NULL pointer");
+    VILA_REQUIRE(q_heads > 0 && kv_heads > 0 && head_dim > 0 && max_ctx > 0 && K > 0 && ldx >= K && ldq >= (int64_t)q_heads * head_dim && slot_stride >= 0,
+                 "vila_qkv_w4_batch_bf16: q_heads=%d, kv_heads=%d, head_dim=%d, max_ctx=%d, or a row stride shorter than its row", q_heads, kv_heads, head_dim, max_ctx);
+    GemvW4BatchArgs g{};
+    g.x = B(x); g.ldx = ldx; g.Wq = (const uint32_t*)Wq; g.Wsz = (const uint32_t*)Wsz; g.bias = B(bias);
+    g.n = n; g.N = (q_heads + 2 * kv_heads) * head_dim; g.K = K; g.mode = 2;
+    g.q_out = B(q_out); g.ldq = ldq; g.kcache = B(kcache); g.vcache = B(vcache); g.slot_stride = slot_stride;
+    g.pos = pos; g.rope_cs = rope_cs; g.nq = q_heads; g.nkv = kv_heads; g.hd = head_dim; g.max_ctx = max_ctx;
+    return launch_gemv_w4_batch(g, S(stream));
+}
 extern "C" size_t vila_gemm_w4_workspace_bytes(int M, int N, int K, int mode) { return gemm_w4_workspace_bytes(M, N, K, mode); }
 extern "C" int vila_gemm_w4_bf16(const void* x, const void* Wq, const void* Wsz, const void* bias, const void* residual, void* y,
                                  int M, int N, int K, int mode, void* workspace, size_t workspace_bytes, vila_stream_t stream) {

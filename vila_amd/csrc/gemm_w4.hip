@@ -1,5 +1,5 @@
 // W4A16 GEMM for prefill shapes (SURVEY.md §8f row 3 / BASELINE configs[4]):  Y[M, N] = X[M, K] . W4^T, any M >= 1.
-//
+// Tests: every element in tests/test_gpu_w4_elements.py (bit for bit on exact inputs, a derived bound otherwise; tests/test_w4_bound_cpu.py proves both).
 // W4 is the SAME tile-major buffer the decode GEMVs read (gemv_w4.hip header, vila_amd/quant.py tile_w4): one packed copy serves both.
 // That layout already is the B operand of v_mfma_f32_16x16x32_bf16: lane 16g + n of a 16-row tile holds k = 32g .. 32g+31 of row n
 // for one 128-wide group, and word w of the lane, unpacked with ((word >> 4p) & 0x000F000F) | 0x43004300 into the exact bf16 pairs

@@ -1,7 +1,7 @@
 // W4A16 decode GEMVs (SURVEY.md §8f row 3 / BASELINE configs[4]: "AWQ int4 dequant-GEMV").  The reference names TinyChat
 // (mit-han-lab/llm-awq, external, un-pinned, zero call sites in-tree: README.md:87) as its W4A16 backend; there is no reference
 // code for it, so the format below is ours and parity is against a CPU dequantise-then-fp32 oracle of the SAME quantised weights.
-//
+// Tests: every element in tests/test_gpu_w4_elements.py (bit for bit on exact inputs, a derived bound otherwise; tests/test_w4_bound_cpu.py proves both).
 // Quantisation: AWQ-style asymmetric uint4, groups of 128 along K:  w = (q - zero) * scale.
 // HBM layout (vila_amd/quant.py: tile_w4) is TILE-MAJOR so that one wave instruction reads 1 KB contiguous:
 //   Wq  [N/16 tiles][K/128 groups][64 lanes][4] u32      lane = 16*g + n: row n of the tile, 32-wide K slice g of the group;
@@ -306,7 +306,17 @@ int launch_gemv_w4(const GemvW4Args& a, hipStream_t s) {
         lds += (size_t)a.n_splits * G * 4;                     // the merge weights [n_splits][heads]
     }
     VILA_REQUIRE(lds <= 160 * 1024, "gemv_w4: K=%d does not fit the 160 KB LDS", a.K);
-#define W4_LAUNCH(MODE, UB_, PIPE_) hipLaunchKernelGGL((gemv_w4_kernel<MODE, UB_, PIPE_>), dim3(grid), dim3(W * 64), lds, s, a, n_tiles)
+    // above the 64 KB a kernel gets by default (K >= 31232) the instantiation's dynamic-LDS limit is raised first, once, as gemv_w4_batch does;
+    // launches below it are what they were
+    const bool big_lds = lds > 64 * 1024;
+#define W4_LAUNCH(MODE, UB_, PIPE_) do { \
+        static bool attr = false; \
+        if (big_lds && !attr) { \
+            VILA_HIP(hipFuncSetAttribute((const void*)gemv_w4_kernel<MODE, UB_, PIPE_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
+            attr = true; \
+        } \
+        hipLaunchKernelGGL((gemv_w4_kernel<MODE, UB_, PIPE_>), dim3(grid), dim3(W * 64), lds, s, a, n_tiles); \
+    } while (0)
     if (a.mode == 1) { if (pipe) W4_LAUNCH(1, 7, true); else W4_LAUNCH(1, 7, false); }
     else if (a.mode == 3) W4_LAUNCH(3, 7, false);
     else if (a.mode == 4) { if (pipe) W4_LAUNCH(4, 7, true); else W4_LAUNCH(4, 7, false); }

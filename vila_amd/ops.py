@@ -142,32 +142,85 @@ def gemv(x: torch.Tensor, w: torch.Tensor, norm_w: Optional[torch.Tensor] = None
 
 
 def gemv_w4(x: torch.Tensor, mat, norm_w: Optional[torch.Tensor] = None, eps: float = 0.0, bias: Optional[torch.Tensor] = None,
-            residual: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """W4A16 GEMV on a vila_amd.quant.W4Matrix (tile-major int4, group 128); gate/up matrices give silu(Wg x) * (Wu x)."""
+            residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """W4A16 GEMV on a vila_amd.quant.W4Matrix (tile-major int4, group 128); gate/up matrices give silu(Wg x) * (Wu x).  `out` [N] bf16
+    contiguous: written in place of a fresh result."""
     _need(x, name="x"); _need(mat.q, dtype=torch.int32, name="mat.q"); _need(mat.sz, dtype=torch.int32, name="mat.sz")
-    y = torch.empty((mat.N,), device=x.device, dtype=torch.bfloat16)
+    if x.numel() != mat.K:
+        raise ValueError(f"gemv_w4: x has {x.numel()} elements, the matrix K = {mat.K}")
+    y = torch.empty((mat.N,), device=x.device, dtype=torch.bfloat16) if out is None else out
+    _need(y, name="out"); assert y.shape == (mat.N,) and y.is_contiguous()
     check(_lib.load().vila_gemv_w4_bf16(x.data_ptr(), _p(norm_w), eps, mat.q.data_ptr(), mat.sz.data_ptr(), _p(bias), _p(residual),
                                         y.data_ptr(), mat.N, mat.K, mat.mode, _stream()), "gemv_w4")
     return y
 
 
+def qkv_w4(x: torch.Tensor, mat, bias: Optional[torch.Tensor], q_out: torch.Tensor, kcache: torch.Tensor, vcache: torch.Tensor, pos: torch.Tensor,
+           rope_cs: torch.Tensor, q_heads: int, kv_heads: int, head_dim: int, norm_w: Optional[torch.Tensor] = None, eps: float = 0.0) -> torch.Tensor:
+    """The solo W4A16 decode step's fused q|k|v projection (vila_qkv_w4_bf16, gemv_w4.hip mode 3): x [K] bf16 (optionally RMS-normalised with norm_w,
+    eps), mat a plain W4Matrix of the (q + 2 kv) * head_dim fused rows packed with quant.rope_interleave_rows; bias [N] in natural order; RoPE from
+    rope_cs [head_dim] fp32 (cos | sin); q into q_out [q * head_dim], K / V into row pos[0] (device int32) of kcache / vcache [kv, max_ctx, head_dim];
+    pos[0] >= max_ctx writes q and no K/V."""
+    _need(x, name="x"); _need(mat.q, dtype=torch.int32, name="mat.q"); _need(mat.sz, dtype=torch.int32, name="mat.sz")
+    _need(q_out, name="q_out"); _need(kcache, name="kcache"); _need(vcache, name="vcache")
+    _need(pos, dtype=torch.int32, name="pos"); _need(rope_cs, dtype=torch.float32, name="rope_cs")
+    if x.numel() != mat.K:
+        raise ValueError(f"qkv_w4: x has {x.numel()} elements, the matrix K = {mat.K}")
+    if mat.mode != 0 or mat.N != (q_heads + 2 * kv_heads) * head_dim:
+        raise ValueError(f"qkv_w4: heads ({q_heads}, {kv_heads}, {head_dim}) describe {(q_heads + 2 * kv_heads) * head_dim} q|k|v rows, the matrix has "
+                         f"{mat.N} (mode {mat.mode})")
+    assert x.is_contiguous() and q_out.is_contiguous() and q_out.numel() >= q_heads * head_dim
+    assert kcache.dim() == 3 and kcache.shape == vcache.shape and kcache.shape[0] == kv_heads and kcache.shape[2] == head_dim
+    assert kcache.is_contiguous() and vcache.is_contiguous() and pos.numel() >= 1 and rope_cs.is_contiguous() and rope_cs.numel() >= head_dim
+    check(_lib.load().vila_qkv_w4_bf16(x.data_ptr(), _p(norm_w), eps, mat.q.data_ptr(), mat.sz.data_ptr(), _p(bias), q_out.data_ptr(), kcache.data_ptr(),
+                                       vcache.data_ptr(), pos.data_ptr(), rope_cs.data_ptr(), q_heads, kv_heads, head_dim, kcache.shape[1], mat.K,
+                                       _stream()), "qkv_w4")
+    return q_out
+
+
 def gemv_w4_batch(x: torch.Tensor, mat, bias: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
-                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """W4A16 batched decode GEMV on a vila_amd.quant.W4Matrix: x [n, K] bf16 (1 <= n <= 16 rows) -> [n, N] bf16 = x . W^T (+bias)(+residual
-    [n, N]); gate/up matrices give silu(x Wg^T) * (x Wu^T) and take no bias or residual.  Rows of `out` beyond n are not written."""
+                  out: Optional[torch.Tensor] = None, n: Optional[int] = None) -> torch.Tensor:
+    """W4A16 batched decode GEMV on a vila_amd.quant.W4Matrix: x [n, K] bf16 (1 <= n <= 16 rows, any row stride that is a multiple of 8) ->
+    [n, N] bf16 = x . W^T (+bias)(+residual [>= n, N]); gate/up matrices give silu(x Wg^T) * (x Wu^T) and take no bias or residual.  `out` and
+    `residual` have row stride N (the entry point fixes it) and may be views of larger buffers (guard rows around them, more rows than n; the
+    residual may be `out`).  Rows of `out` beyond n are not written.  `n` overrides x's row count (the refusals are reachable with it)."""
     _need(x, name="x"); _need(mat.q, dtype=torch.int32, name="mat.q"); _need(mat.sz, dtype=torch.int32, name="mat.sz")
     assert x.dim() == 2 and x.stride(1) == 1
     if x.shape[1] != mat.K:
         raise ValueError(f"gemv_w4_batch: x has {x.shape[1]} columns, the matrix {mat.K}")
-    n = x.shape[0]
+    n = x.shape[0] if n is None else n
     if out is None:
         out = torch.empty((n, mat.N), device=x.device, dtype=torch.bfloat16)
-    assert out.is_contiguous() and out.shape[1] == mat.N and out.shape[0] >= n
-    if residual is not None:
-        _need(residual, name="residual"); assert residual.shape == (n, mat.N) and residual.is_contiguous()
+    for t, name in ((out, "out"), (residual, "residual")):
+        if t is not None:
+            _need(t, name=name); assert t.dim() == 2 and t.is_contiguous() and t.shape[1] == mat.N and t.shape[0] >= min(n, 16)
     check(_lib.load().vila_gemv_w4_batch_bf16(x.data_ptr(), x.stride(0), n, mat.q.data_ptr(), mat.sz.data_ptr(), _p(bias), _p(residual),
                                               out.data_ptr(), mat.N, mat.K, mat.mode, _stream()), "gemv_w4_batch")
     return out
+
+
+def qkv_w4_batch(x: torch.Tensor, mat, bias: Optional[torch.Tensor], q_out: torch.Tensor, kcache: torch.Tensor, vcache: torch.Tensor,
+                 pos: torch.Tensor, rope_cs: torch.Tensor, q_heads: int, kv_heads: int, head_dim: int, n: Optional[int] = None) -> torch.Tensor:
+    """The batched W4A16 decode step's q|k|v projection (vila_qkv_w4_batch_bf16, gemv_w4_batch.hip mode 2): qkv_batch's arguments with a plain
+    W4Matrix of the fused rows, packed with quant.rope_interleave_rows, in place of wqkv; same contract."""
+    _need(x, name="x"); _need(mat.q, dtype=torch.int32, name="mat.q"); _need(mat.sz, dtype=torch.int32, name="mat.sz")
+    _need(q_out, name="q_out"); _need(kcache, name="kcache"); _need(vcache, name="vcache")
+    _need(pos, dtype=torch.int32, name="pos"); _need(rope_cs, dtype=torch.float32, name="rope_cs")
+    assert x.dim() == 2 and x.stride(1) == 1 and q_out.dim() == 2 and q_out.stride(1) == 1
+    if x.shape[1] != mat.K:
+        raise ValueError(f"qkv_w4_batch: x has {x.shape[1]} columns, the matrix {mat.K}")
+    if mat.mode != 0 or mat.N != (q_heads + 2 * kv_heads) * head_dim:
+        raise ValueError(f"qkv_w4_batch: heads ({q_heads}, {kv_heads}, {head_dim}) describe {(q_heads + 2 * kv_heads) * head_dim} q|k|v rows, the matrix "
+                         f"has {mat.N} (mode {mat.mode})")
+    n = x.shape[0] if n is None else n
+    assert q_out.shape[1] == q_heads * head_dim and q_out.shape[0] >= min(n, 16)
+    assert kcache.dim() == 4 and kcache.shape == vcache.shape and kcache.shape[1:] == (kv_heads, kcache.shape[2], head_dim) and kcache.shape[0] >= min(n, 16)
+    assert kcache[0].is_contiguous() and vcache[0].is_contiguous() and kcache.stride(0) == vcache.stride(0)
+    assert pos.numel() >= min(n, 16) and rope_cs.is_contiguous() and rope_cs.numel() >= min(n, 16) * head_dim
+    check(_lib.load().vila_qkv_w4_batch_bf16(x.data_ptr(), x.stride(0), n, mat.q.data_ptr(), mat.sz.data_ptr(), _p(bias), q_out.data_ptr(),
+                                             q_out.stride(0), kcache.data_ptr(), vcache.data_ptr(), kcache.stride(0), pos.data_ptr(), rope_cs.data_ptr(),
+                                             q_heads, kv_heads, head_dim, kcache.shape[2], mat.K, _stream()), "qkv_w4_batch")
+    return q_out
 
 
 def gemm_batch(x: torch.Tensor, w: torch.Tensor, w2: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None,
@@ -216,10 +269,11 @@ def qkv_batch(x: torch.Tensor, wqkv: torch.Tensor, bias: Optional[torch.Tensor],
 
 
 def gemm_w4(x: torch.Tensor, mat, bias: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
-            out: Optional[torch.Tensor] = None, heads: Optional[tuple] = None) -> torch.Tensor:
+            out: Optional[torch.Tensor] = None, heads: Optional[tuple] = None, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
     """W4A16 GEMM (prefill shapes) on a vila_amd.quant.W4Matrix: x [M, K] bf16 -> [M, N] bf16 = x . W^T (+bias)(+residual); gate/up
     matrices give silu(x Wg^T) * (x Wu^T).  heads = (q_heads, kv_heads, head_dim) marks the fused q|k|v matrix of a W4 layer (rows of the
-    q and k heads RoPE-interleaved): the result comes back in natural q | k | v column order with the bias added."""
+    q and k heads RoPE-interleaved): the result comes back in natural q | k | v column order with the bias added.  `ws`: a caller's uint8 workspace
+    of at least vila_gemm_w4_workspace_bytes (one is allocated otherwise)."""
     _need(x, name="x"); _need(mat.q, dtype=torch.int32, name="mat.q"); _need(mat.sz, dtype=torch.int32, name="mat.sz")
     assert x.dim() == 2 and x.is_contiguous()
     if x.shape[1] != mat.K:
@@ -232,7 +286,11 @@ def gemm_w4(x: torch.Tensor, mat, bias: Optional[torch.Tensor] = None, residual:
     if residual is not None:
         _need(residual, name="residual"); assert residual.shape == (M, mat.N) and residual.is_contiguous()
     nb = lib.vila_gemm_w4_workspace_bytes(M, mat.N, mat.K, mode)
-    ws = torch.empty((max(nb, 1),), device=x.device, dtype=torch.uint8)
+    if ws is None:
+        ws = torch.empty((max(nb, 1),), device=x.device, dtype=torch.uint8)
+    else:
+        _need(ws, dtype=torch.uint8, name="ws"); assert ws.is_contiguous()
+        nb = ws.numel()
     if heads is not None:
         nq, nkv, hd = (int(v) for v in heads)
         if (nq + 2 * nkv) * hd != mat.N or mat.mode != 0:
