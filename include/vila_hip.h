@@ -698,8 +698,8 @@ int vila_logits_penalize_f32(const float* logits, int64_t ld, int n, int vocab, 
 /* The decode steps with that launch between the logits and the pick: st->logits stays the raw model logits, the pick (greedy: first index of the
  * maximum; sampled: the sampler of the plain step, unchanged) runs on the processed row, and token[] is counted before it is replaced.  One entry
  * per driver: qlayers NULL = bf16, else the W4 step; sp NULL = greedy; prefix NULL = a plain batch session.  The launches in front of the pick are
- * the plain steps', so the logits are the same bits.  Workspaces: the sizes below (they differ from the plain steps').  The verify steps have no
- * penalised form. */
+ * the plain steps', so the logits are the same bits.  Workspaces: the sizes below (they differ from the plain steps').  The verify steps' penalised
+ * form is vila_llm_decode_step_verify_processed (below). */
 size_t vila_llm_decode_penalized_workspace_bytes(const VilaLlmShape* s, int max_ctx);
 int vila_llm_decode_step_penalized(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers /*[host], nullable*/, const VilaKvCache* cache,
                                    const VilaDecodeState* st, void* workspace, size_t workspace_bytes, const VilaSampling* sp /*nullable*/,
@@ -735,7 +735,7 @@ int vila_logits_constrain_f32(const float* logits, int64_t ld, int n, int vocab,
                               float* out, int64_t ld_out, float* pick_v, int* pick_i /*nullable*/, vila_stream_t stream);
 /* The decode steps with raw logits -> penalties (if pen) -> constrain -> pick.  st->logits stays raw; the launches in front of the pick are the plain
  * steps', so the logits are the same bits.  qlayers, sp, prefix and pen are nullable, as in the penalised entries, whose workspace sizes these share.
- * The verify steps have no constrained form. */
+ * The verify steps' constrained form is vila_llm_decode_step_verify_processed (below). */
 size_t vila_llm_decode_constrained_workspace_bytes(const VilaLlmShape* s, int max_ctx);
 int vila_llm_decode_step_constrained(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers /*[host], nullable*/, const VilaKvCache* cache,
                                      const VilaDecodeState* st, void* workspace, size_t workspace_bytes, const VilaSampling* sp /*nullable*/,
@@ -786,7 +786,8 @@ int vila_llm_decode_step_verify_any_k(const VilaLlmWeights* w, const VilaLlmLaye
  * are device arrays read at run time: one captured hipGraph serves every request.
  * Behind a decode step: launch it AFTER the step entry on the same stream, with logits = st->logits, token = st->token, rec = st->n_out and
  * rec_bias = -1.  It then records the token that step chose, and record k of a row lines up with out_ids[k] (an idle row that has stepped past
- * max_out writes nothing, as out_ids is guarded). */
+ * max_out writes nothing, as out_ids is guarded).  A verify step emits up to n tokens of ONE sequence: its records are written by
+ * vila_llm_decode_step_verify_processed (below), through the one-sequence mode vila_logprobs_seq_f32. */
 #define VILA_LOGPROBS_MAX_TOP 20
 typedef struct {
     float*   token_logprob;   /* [n][max_rec] */
@@ -802,6 +803,51 @@ int vila_logprobs_slice_width(int vocab);
 int vila_logprobs_f32(const float* logits, int64_t ld, int n, int vocab, const int64_t* token /*[n] device*/, int top_n /*0..20*/,
                       const int32_t* rec /*[n] device, nullable: record 0*/, int rec_bias, const VilaLogprobOut* out,
                       void* workspace, vila_stream_t stream);
+
+
+/* Speculative decoding for penalised, constrained and logprob requests: the verify step with the processing chain in front of its pick,
+ *   raw logits -> penalties -> automaton mask -> pick (greedy) or draw (sampled, top_k 1..64 or, with any_k, every top_k >= 0) -> accept -> commit,
+ * and the records of the tokens it emits.  A step runs n = k + 1 rows of ONE sequence; row i consumes token[i] at position pos + i, so it is processed
+ * as the session drafting nothing processes the step that consumes token[i], after consuming token[0 .. i]:
+ *   penalties  row i sees c_i(v) = min(65535, counts[v] + #{j <= i : token[j] == v}) (ids outside 0 .. vocab - 1 count nothing): the saturating sum,
+ *              which equals the sequential saturating bumps.  y = the expression of VilaPenalties with c_i(v), one rounding per operation; neutral
+ *              values return x's bits.  `pen` describes ONE sequence: one count row and ONE-entry parameter arrays read by every row (as `sp` is).  The
+ *              launch does NOT write the table.
+ *   automaton  s_0 = adv(state, token[0]), s_i = adv(s_{i-1}, token[i]) with adv the advance rule of VilaConstraints (a transition < 0, an id out of
+ *              range or a class >= C leaves the state; -1 stays -1 and copies the row); row i is masked from s_i with the ONE cls / next table.  The launch
+ *              does NOT write `state`.  A draft the automaton forbids holds -inf in the row in front of it and is rejected like any wrong draft.
+ *   pick / draw, accept   the plain verify steps' launches, reading the processed rows; st->logits stays RAW; the draw of row i keeps counter pos + i.
+ *   commit     behind the accept, with m = *n_accept, by one thread: counts[t] gets one saturating bump for each of the m + 1 tokens the step consumed
+ *              (token[0 .. m] as they were before the accept replaced token[0]), in order, and state = s_m.  Nothing of the rows behind m reaches the
+ *              table or the state.
+ *   records    RAW (VilaLogprobOut of ONE sequence, n = 1 in its shapes): row i <= m emitted out_ids[old + i], old = *n_out - (m + 1) behind the accept,
+ *              and writes record old + i; rows behind m and indices at or beyond max_rec (or max_out) write nothing.  Record k lines up with out_ids[k],
+ *              with the bits vila_logprobs_f32 gives that row alone.  top_logprob / top_id non-NULL: all 20 alternatives.
+ * A row's logits do not depend on the step it runs in, so the ids, the table, the state and the records are those of the same session drafting nothing.
+ * qlayers NULL = bf16, else W4; sp NULL = greedy; any_k != 0 needs sp; pen, con and lp NULL = that stage is off, and with all three NULL the launches
+ * are the plain verify step's.  One workspace size serves every combination.  Bad arguments are refused before any launch. */
+size_t vila_llm_decode_verify_processed_workspace_bytes(const VilaLlmShape* s, int n, int max_ctx);
+int vila_llm_decode_step_verify_processed(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers /*[host], nullable*/, const VilaKvCache* cache,
+                                          const VilaDecodeVerify* st, void* workspace, size_t workspace_bytes, const VilaBatchSampling* sp /*nullable*/,
+                                          int any_k, const VilaPenalties* pen /*nullable*/, const VilaConstraints* con /*nullable*/,
+                                          const VilaLogprobOut* lp /*nullable*/, vila_stream_t stream);
+/* Its launches on their own.  n in 1..16 rows of ONE sequence, token [n] device.
+ * penalise-verify: logits [n][ld] -> out [n][ld_out] with pen's ONE count row (read only) and entry 0 of its parameter arrays; pick_v / pick_i (both or
+ *   neither) [n][vila_logits_penalize_slices()].
+ * constrain-verify: the chain s_0 .. s_{n-1} of con's ONE automaton along token[] -> states_out [n] (con->state is read only), then logits -> out masked
+ *   per row; pairs as above.  out may alias logits.
+ * commit: consumed [n] (the tokens a step consumed), states [n] (the chain), *n_accept = m (clamped to 0 .. n - 1): counts bumped for consumed[0 .. m] where
+ *   pen is given, con->state = states[m] where con is given (one of the two at least).
+ * one-sequence records: vila_logprobs_f32 with every row writing output row 0: row r writes record rec[r] (required; outside 0 .. max_rec - 1: nothing) of
+ *   token_logprob [max_rec], top_logprob / top_id [max_rec][20]. */
+int vila_logits_penalize_verify_f32(const float* logits, int64_t ld, int n, int vocab, const VilaPenalties* pen, const int64_t* token, float* out,
+                                    int64_t ld_out, float* pick_v, int* pick_i /*nullable*/, vila_stream_t stream);
+int vila_logits_constrain_verify_f32(const float* logits, int64_t ld, int n, int vocab, const VilaConstraints* con, const int64_t* token,
+                                     int32_t* states_out, float* out, int64_t ld_out, float* pick_v, int* pick_i /*nullable*/, vila_stream_t stream);
+int vila_verify_commit(const VilaPenalties* pen /*nullable*/, const VilaConstraints* con /*nullable*/, int vocab, const int64_t* consumed,
+                       const int32_t* states, const int32_t* n_accept, int n, vila_stream_t stream);
+int vila_logprobs_seq_f32(const float* logits, int64_t ld, int n, int vocab, const int64_t* token /*[n] device*/, int top_n /*0..20*/,
+                          const int32_t* rec /*[n] device*/, const VilaLogprobOut* out, void* workspace, vila_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -335,6 +335,17 @@ PROTOTYPES = {
                                                  C.POINTER(VilaConstraints), c_void_p]),
     "vila_llm_decode_step_verify_any_k": (c_int, [C.POINTER(VilaLlmWeights), C.POINTER(VilaLlmLayerW4), C.POINTER(VilaKvCache), C.POINTER(VilaDecodeVerify),
                                                   c_void_p, c_size_t, C.POINTER(VilaBatchSampling), c_void_p]),
+    # ---- the verify step with penalties / an automaton in front of its pick and logprob records behind its accept ----
+    "vila_llm_decode_verify_processed_workspace_bytes": (c_size_t, [C.POINTER(VilaLlmShape), c_int, c_int]),
+    "vila_llm_decode_step_verify_processed": (c_int, [C.POINTER(VilaLlmWeights), C.POINTER(VilaLlmLayerW4), C.POINTER(VilaKvCache), C.POINTER(VilaDecodeVerify),
+                                                      c_void_p, c_size_t, C.POINTER(VilaBatchSampling), c_int, C.POINTER(VilaPenalties),
+                                                      C.POINTER(VilaConstraints), C.POINTER(VilaLogprobOut), c_void_p]),
+    "vila_logits_penalize_verify_f32": (c_int, [c_void_p, c_int64, c_int, c_int, C.POINTER(VilaPenalties), c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
+                                                c_void_p]),
+    "vila_logits_constrain_verify_f32": (c_int, [c_void_p, c_int64, c_int, c_int, C.POINTER(VilaConstraints), c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
+                                                 c_void_p, c_void_p]),
+    "vila_verify_commit": (c_int, [C.POINTER(VilaPenalties), C.POINTER(VilaConstraints), c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "vila_logprobs_seq_f32": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_int, c_void_p, C.POINTER(VilaLogprobOut), c_void_p, c_void_p]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -1006,7 +1006,8 @@ extern "C" int vila_llm_decode_step_batch_any_k(const VilaLlmWeights* w, const V
 // The verify step (speculative decoding, decode_batch.hip bverify_step): the layer tables are the batched step's, the state is one sequence's.
 // sp != nullptr: the sampled form, whose four parameter arrays hold ONE entry each.
 static int decode_step_verify_impl(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers, const VilaKvCache* cache, const VilaDecodeVerify* st,
-                                   void* workspace, size_t workspace_bytes, const VilaBatchSampling* sp, vila_stream_t stream, bool any_k = false) {
+                                   void* workspace, size_t workspace_bytes, const VilaBatchSampling* sp, vila_stream_t stream, bool any_k = false,
+                                   const BVerifyProc* proc = nullptr) {
     const char* fn = qlayers != nullptr ? "llm_decode_verify_w4" : "llm_decode_verify";
     VILA_REQUIRE(w != nullptr && cache != nullptr && st != nullptr && workspace != nullptr, "%s: NULL argument", fn);
     VILA_REQUIRE(sp == nullptr || (sp->temperature != nullptr && sp->top_k != nullptr && sp->top_p != nullptr && sp->seed != nullptr),
@@ -1017,7 +1018,7 @@ static int decode_step_verify_impl(const VilaLlmWeights* w, const VilaLlmLayerW4
     BVerifyState v{st->n, st->slot, st->pos, st->token, st->n_draft, st->out_ids, st->n_out, st->max_out, st->logits, st->n_accept,
                    st->hist, st->n_hist, st->hist_cap, st->max_ngram, st->cand, st->n_cand};
     return bverify_step(t.m, t.layers.data(), B(cache->k), B(cache->v), cache->max_ctx, cache->n_slots, v, workspace, workspace_bytes, S(stream),
-                        qlayers != nullptr ? t.ql.data() : nullptr, sp != nullptr ? &bs : nullptr, any_k);
+                        qlayers != nullptr ? t.ql.data() : nullptr, sp != nullptr ? &bs : nullptr, any_k, proc);
 }
 extern "C" size_t vila_llm_decode_verify_workspace_bytes(const VilaLlmShape* s, int n, int max_ctx) {
     return bverify_workspace_bytes(s->hidden, s->inter, s->q_heads * s->head_dim, s->head_dim, n, max_ctx);
@@ -1042,6 +1043,64 @@ extern "C" int vila_llm_decode_step_verify_any_k(const VilaLlmWeights* w, const 
                                                  void* workspace, size_t workspace_bytes, const VilaBatchSampling* sp, vila_stream_t stream) {
     VILA_REQUIRE(sp != nullptr, "llm_decode_verify_any_k: sampling parameters are NULL");
     return decode_step_verify_impl(w, qlayers, cache, st, workspace, workspace_bytes, sp, stream, true);
+}
+// The processed verify step (decode_batch.hip bverify_step with a BVerifyProc): qlayers, sp, pen, con and lp nullable — bf16 / W4, greedy / sampled (any_k:
+// every top_k >= 0), with penalties, an automaton and records in any mix, in one entry with one workspace size.  Everything is refused here, before a launch.
+extern "C" size_t vila_llm_decode_verify_processed_workspace_bytes(const VilaLlmShape* s, int n, int max_ctx) {
+    return bverify_processed_workspace_bytes(s->hidden, s->inter, s->q_heads * s->head_dim, s->head_dim, n, max_ctx, s->vocab);
+}
+extern "C" int vila_llm_decode_step_verify_processed(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers, const VilaKvCache* cache, const VilaDecodeVerify* st,
+                                                     void* workspace, size_t workspace_bytes, const VilaBatchSampling* sp, int any_k, const VilaPenalties* pen,
+                                                     const VilaConstraints* con, const VilaLogprobOut* lp, vila_stream_t stream) {
+    const char* fn = "llm_decode_verify_processed";
+    VILA_REQUIRE(w != nullptr && cache != nullptr && st != nullptr && workspace != nullptr, "%s: NULL argument", fn);
+    VILA_REQUIRE(!any_k || sp != nullptr, "%s: any top_k is an option of the sampled step", fn);
+    if (pen != nullptr) VILA_TRY(penalties_ok(pen, w->shape.vocab, fn));
+    if (con != nullptr) VILA_TRY(constraints_ok(con, w->shape.vocab, fn));
+    VILA_REQUIRE(lp == nullptr || (lp->token_logprob != nullptr && (lp->top_logprob == nullptr) == (lp->top_id == nullptr) && lp->max_rec >= 1),
+                 "%s: the records need token_logprob, both top_logprob and top_id or neither, and max_rec >= 1", fn);
+    VILA_REQUIRE(st->n >= 2 && st->n <= 16, "%s: 2..16 rows per step (got %d)", fn, st->n);
+    VILA_REQUIRE(cache->max_ctx >= 1 && cache->max_ctx <= BDEC_MAX_CTX, "%s: caches up to %d positions (got %d)", fn, BDEC_MAX_CTX, cache->max_ctx);
+    VILA_REQUIRE(workspace_bytes >= vila_llm_decode_verify_processed_workspace_bytes(&w->shape, st->n, cache->max_ctx),
+                 "%s: the step needs the workspace of vila_llm_decode_verify_processed_workspace_bytes", fn);
+    const Penalties P = pen != nullptr ? Penalties{pen->repetition, pen->presence, pen->frequency, pen->counts, pen->ld_counts} : Penalties{};
+    const Constraints Cn = con != nullptr ? Constraints{con->state, con->cls, con->ld_cls, con->next, con->ld_next, con->n_classes} : Constraints{};
+    const BVerifyProc pr{pen != nullptr ? &P : nullptr, con != nullptr ? &Cn : nullptr, lp != nullptr ? lp->token_logprob : nullptr,
+                         lp != nullptr ? lp->top_logprob : nullptr, lp != nullptr ? lp->top_id : nullptr, lp != nullptr ? lp->max_rec : 0};
+    return decode_step_verify_impl(w, qlayers, cache, st, workspace, workspace_bytes, sp, stream, any_k != 0, &pr);
+}
+// its launches on their own (operator level): the penalty and mask launches of n rows of ONE sequence, the commit behind an accept, one-sequence records
+extern "C" int vila_logits_penalize_verify_f32(const float* logits, int64_t ld, int n, int vocab, const VilaPenalties* pen, const int64_t* token, float* out,
+                                               int64_t ld_out, float* pick_v, int* pick_i, vila_stream_t stream) {
+    VILA_REQUIRE(pen != nullptr, "logits_penalize_verify: the penalties are NULL");
+    const Penalties P{pen->repetition, pen->presence, pen->frequency, pen->counts, pen->ld_counts};
+    return launch_penalize_verify(logits, ld, n, vocab, P, token, out, ld_out, PEN_PICK_SLICES, pick_v, pick_i, S(stream));
+}
+extern "C" int vila_logits_constrain_verify_f32(const float* logits, int64_t ld, int n, int vocab, const VilaConstraints* con, const int64_t* token,
+                                                int32_t* states_out, float* out, int64_t ld_out, float* pick_v, int* pick_i, vila_stream_t stream) {
+    VILA_REQUIRE(logits != nullptr && out != nullptr && token != nullptr && states_out != nullptr, "logits_constrain_verify: NULL argument");
+    VILA_REQUIRE(n >= 1 && n <= PEN_VERIFY_MAX_ROWS && vocab >= 1, "logits_constrain_verify: 1..%d rows of a non-empty vocabulary (got %d x %d)",
+                 PEN_VERIFY_MAX_ROWS, n, vocab);
+    VILA_TRY(constraints_ok(con, vocab, "logits_constrain_verify"));
+    VILA_REQUIRE(ld >= vocab && ld_out >= vocab && (pick_v == nullptr) == (pick_i == nullptr), "logits_constrain_verify: a row stride below the vocabulary %d, or "
+                 "one of the two pair arrays", vocab);
+    const Constraints Cn{con->state, con->cls, con->ld_cls, con->next, con->ld_next, con->n_classes};
+    VILA_TRY(launch_verify_chain(&Cn, token, n, vocab, states_out, nullptr, S(stream)));
+    return launch_constrain_rows(logits, ld, n, vocab, Cn, states_out, out, ld_out, PEN_PICK_SLICES, pick_v, pick_i, S(stream));
+}
+extern "C" int vila_verify_commit(const VilaPenalties* pen, const VilaConstraints* con, int vocab, const int64_t* consumed, const int32_t* states,
+                                  const int32_t* n_accept, int n, vila_stream_t stream) {
+    VILA_REQUIRE(pen != nullptr || con != nullptr, "verify_commit: neither penalties nor an automaton");
+    VILA_REQUIRE(vocab >= 1, "verify_commit: an empty vocabulary");
+    if (pen != nullptr) VILA_TRY(penalties_ok(pen, vocab, "verify_commit"));
+    if (con != nullptr) VILA_REQUIRE(con->state != nullptr, "verify_commit: the automaton's state is NULL");
+    return launch_verify_commit(pen != nullptr ? pen->counts : nullptr, vocab, con != nullptr ? con->state : nullptr, consumed, states, n_accept, n, S(stream));
+}
+extern "C" int vila_logprobs_seq_f32(const float* logits, int64_t ld, int n, int vocab, const int64_t* token, int top_n, const int32_t* rec,
+                                     const VilaLogprobOut* out, void* workspace, vila_stream_t stream) {
+    VILA_REQUIRE(out != nullptr && rec != nullptr, "logprobs (one sequence): the output descriptor or the record indices are NULL");
+    VILA_REQUIRE((uintptr_t)workspace % 8 == 0, "logprobs: the workspace must be 8-byte aligned");
+    return launch_logprobs(logits, ld, n, vocab, token, top_n, rec, 0, out->token_logprob, out->top_logprob, out->top_id, out->max_rec, workspace, S(stream), true);
 }
 extern "C" int vila_llm_decode_step_verify(const VilaLlmWeights* w, const VilaKvCache* cache, const VilaDecodeVerify* st, void* workspace,
                                            size_t workspace_bytes, vila_stream_t stream) {

@@ -40,7 +40,7 @@ template <bool VEC>
 __global__ __launch_bounds__(256) void constrain_mask_kernel(const float* logits, int64_t ld, int V, const int32_t* __restrict__ state,
                                                              const uint16_t* __restrict__ cls, int64_t ld_cls, const int16_t* __restrict__ next,
                                                              int64_t ld_next, const int32_t* __restrict__ n_classes, float* out, int64_t ld_out,
-                                                             int n_slices, float* __restrict__ pv, int* __restrict__ pi) {
+                                                             int n_slices, float* __restrict__ pv, int* __restrict__ pi, int one_auto) {
     __shared__ int16_t trow[CON_MAX_CLASSES];
     __shared__ float sv[4];
     __shared__ int si[4];
@@ -48,17 +48,18 @@ __global__ __launch_bounds__(256) void constrain_mask_kernel(const float* logits
     const int per = (((V + n_slices - 1) / n_slices) + 3) & ~3;
     const int lo = sl * per < V ? sl * per : V, hi = lo + per < V ? lo + per : V;
     const int s = state[row];                                       // block-uniform
+    const int arow = one_auto ? 0 : row;                            // the verify form: every row is a state of automaton 0 (constrain_chain_kernel)
     const bool free_row = s < 0;
     int C = 0;
     if (!free_row) {
-        C = n_classes[row];
+        C = n_classes[arow];
         if (C < 1 || C > CON_MAX_CLASSES || ((int64_t)s + 1) * C > ld_next) C = 0;          // nothing allowed: no read outside the row's table
-        const int16_t* tr = next + (int64_t)row * ld_next + (int64_t)s * C;
+        const int16_t* tr = next + (int64_t)arow * ld_next + (int64_t)s * C;
         for (int c = tid; c < C; c += 256) trow[c] = tr[c];
         __syncthreads();
     }
     const float* lr = logits + (int64_t)row * ld;
-    const uint16_t* cr = cls + (int64_t)row * ld_cls;
+    const uint16_t* cr = cls + (int64_t)arow * ld_cls;
     float* yr = out + (int64_t)row * ld_out;
     float best = -INFINITY; int bi = 0x7fffffff;
     auto ok = [&](uint32_t c) { return free_row || ((int)c < C && trow[c] >= 0); };
@@ -118,10 +119,70 @@ int launch_constrain(const float* logits, int64_t ld, int n, int vocab, const Co
     const bool vec = (uintptr_t)logits % 16 == 0 && ld % 4 == 0 && (uintptr_t)out % 16 == 0 && ld_out % 4 == 0 && (uintptr_t)c.cls % 8 == 0 && c.ld_cls % 4 == 0;
     if (vec)
         hipLaunchKernelGGL(constrain_mask_kernel<true>, dim3(n_slices, n), dim3(256), 0, s, logits, ld, vocab, (const int32_t*)c.state, c.cls, c.ld_cls, c.next,
-                           c.ld_next, c.n_classes, out, ld_out, n_slices, pick_v, pick_i);
+                           c.ld_next, c.n_classes, out, ld_out, n_slices, pick_v, pick_i, 0);
     else
         hipLaunchKernelGGL(constrain_mask_kernel<false>, dim3(n_slices, n), dim3(256), 0, s, logits, ld, vocab, (const int32_t*)c.state, c.cls, c.ld_cls, c.next,
-                           c.ld_next, c.n_classes, out, ld_out, n_slices, pick_v, pick_i);
+                           c.ld_next, c.n_classes, out, ld_out, n_slices, pick_v, pick_i, 0);
+    VILA_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- the verify form (speculative decoding, decode_batch.hip bverify_step) --------------------------------------------------------------------
+// n rows of ONE sequence under ONE automaton: row i consumes token[i] behind token[0 .. i - 1], so it is masked from s_i with s_0 = adv(state, token[0]),
+// s_i = adv(s_{i-1}, token[i]) — adv being constrain_advance_kernel's rule word for word.  The chain is at most 16 dependent lookups by ONE thread; it
+// lands in states_out and leaves `state` alone: what the step accepts is committed behind the accept (penalty.hip verify_commit_kernel).  The other
+// lanes of the wave keep the consumed tokens (consumed[i] = token[i], nullable), which the accept is about to overwrite.  state NULL: the copy only.
+// The mask kernel then runs with the per-row states of the chain and automaton 0's classes and table for every row (one_auto).
+__global__ __launch_bounds__(64) void constrain_chain_kernel(const int32_t* __restrict__ state, const uint16_t* __restrict__ cls, const int16_t* __restrict__ next,
+                                                             int64_t ld_next, const int32_t* __restrict__ n_classes, const int64_t* __restrict__ token, int n, int V,
+                                                             int32_t* __restrict__ states_out, int64_t* __restrict__ consumed) {
+    const int tid = threadIdx.x;
+    if (consumed != nullptr && tid < n) consumed[tid] = token[tid];
+    if (tid != 0 || state == nullptr) return;
+    int s = state[0];
+    const int C = n_classes[0];
+    for (int i = 0; i < n; ++i) {
+        const int64_t t = token[i];
+        if (s >= 0 && t >= 0 && t < (int64_t)V && C >= 1 && C <= CON_MAX_CLASSES && ((int64_t)s + 1) * C <= ld_next) {
+            const int c = cls[t];
+            if (c < C) {
+                const int s2 = next[(int64_t)s * C + c];
+                if (s2 >= 0) s = s2;
+            }
+        }
+        states_out[i] = s;
+    }
+}
+int launch_verify_chain(const Constraints* c, const int64_t* token, int n, int vocab, int32_t* states_out, int64_t* consumed, hipStream_t s) {
+    VILA_REQUIRE(token != nullptr && n >= 1 && n <= 64 && vocab >= 1, "constrain_verify: 1..64 rows of one sequence and their tokens (got %d)", n);
+    VILA_REQUIRE(c != nullptr || consumed != nullptr, "constrain_verify: neither an automaton nor a place for the consumed tokens");
+    VILA_REQUIRE(c == nullptr || (c->state != nullptr && c->cls != nullptr && c->next != nullptr && c->n_classes != nullptr && states_out != nullptr &&
+                                  c->ld_cls >= vocab && c->ld_next >= 1), "constrain_verify: NULL argument or a class row below the vocabulary");
+    if (c != nullptr)
+        hipLaunchKernelGGL(constrain_chain_kernel, dim3(1), dim3(64), 0, s, (const int32_t*)c->state, c->cls, c->next, c->ld_next, c->n_classes, token, n, vocab,
+                           states_out, consumed);
+    else
+        hipLaunchKernelGGL(constrain_chain_kernel, dim3(1), dim3(64), 0, s, (const int32_t*)nullptr, (const uint16_t*)nullptr, (const int16_t*)nullptr, (int64_t)0,
+                           (const int32_t*)nullptr, token, n, vocab, (int32_t*)nullptr, consumed);
+    VILA_LAUNCH_CHECK();
+    return 0;
+}
+int launch_constrain_rows(const float* logits, int64_t ld, int n, int vocab, const Constraints& c, const int32_t* states, float* out, int64_t ld_out, int n_slices,
+                          float* pick_v, int* pick_i, hipStream_t s) {
+    VILA_REQUIRE(logits != nullptr && out != nullptr && states != nullptr && c.cls != nullptr && c.next != nullptr && c.n_classes != nullptr,
+                 "constrain_verify: NULL argument");
+    VILA_REQUIRE(n >= 1 && n <= 64 && vocab >= 1, "constrain_verify: 1..64 rows of a non-empty vocabulary (got %d x %d)", n, vocab);
+    VILA_REQUIRE(ld >= vocab && ld_out >= vocab && c.ld_cls >= vocab, "constrain_verify: a row stride (%lld, %lld, %lld) is below the vocabulary %d",
+                 (long long)ld, (long long)ld_out, (long long)c.ld_cls, vocab);
+    VILA_REQUIRE(c.ld_next >= 1, "constrain_verify: the table holds %lld entries", (long long)c.ld_next);
+    VILA_REQUIRE((pick_v == nullptr) == (pick_i == nullptr) && n_slices >= 1 && n_slices <= 65535, "constrain_verify: the pairs need both arrays and 1..65535 slices");
+    const bool vec = (uintptr_t)logits % 16 == 0 && ld % 4 == 0 && (uintptr_t)out % 16 == 0 && ld_out % 4 == 0 && (uintptr_t)c.cls % 8 == 0;
+    if (vec)
+        hipLaunchKernelGGL(constrain_mask_kernel<true>, dim3(n_slices, n), dim3(256), 0, s, logits, ld, vocab, states, c.cls, c.ld_cls, c.next, c.ld_next, c.n_classes,
+                           out, ld_out, n_slices, pick_v, pick_i, 1);
+    else
+        hipLaunchKernelGGL(constrain_mask_kernel<false>, dim3(n_slices, n), dim3(256), 0, s, logits, ld, vocab, states, c.cls, c.ld_cls, c.next, c.ld_next, c.n_classes,
+                           out, ld_out, n_slices, pick_v, pick_i, 1);
     VILA_LAUNCH_CHECK();
     return 0;
 }

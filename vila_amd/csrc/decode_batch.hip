@@ -627,9 +627,49 @@ size_t bverify_workspace_bytes(int H, int F, int QS, int hd, int n, int max_ctx)
 size_t bverify_sample_workspace_bytes(int H, int F, int QS, int hd, int n, int max_ctx) {
     return align_up(bverify_workspace_bytes(H, F, QS, hd, n, max_ctx), 256) + align_up(sample_batch_workspace_bytes(n), 256) + align_up((size_t)(n > 0 ? n : 0) * 8, 256);
 }
+// The processed verify step: raw logits -> penalties -> automaton mask -> pick / draw -> accept -> commit (-> records).  Row i is processed as the
+// session drafting nothing would process it at the step that consumes token[i]: penalised with the counts behind token[0 .. i] (penalty.hip
+// penalize_verify_kernel) and masked from the automaton's state behind them (constrain.hip constrain_chain_kernel), both WITHOUT touching the count
+// table or the state; the unchanged pick / sampler / accept read the processed rows, and st.logits stays raw.  Behind the accept one thread commits
+// what the step really consumed — token[0 .. m] as they were before the accept overwrote token[0], kept in the workspace — so nothing of a rejected
+// draft or a padding row reaches the table or the state.  The records are RAW, one per emitted token, into the ONE sequence's arrays.
+// Its workspace: the sampled step's (whatever `sampling`), and behind it the processed rows [n][vocab], the consumed tokens, the chain's states, the
+// rows' emitted tokens and record indices, and the logprob launch's workspace.
+struct BProcBufs { float* rows; int64_t* consumed; int32_t* states; int64_t* tok_rows; int32_t* rec_rows; void* lp_ws; };
+static size_t bverify_proc_head(int H, int F, int QS, int hd, int n, int max_ctx) { return align_up(bverify_sample_workspace_bytes(H, F, QS, hd, n, max_ctx), 256); }
+size_t bverify_processed_workspace_bytes(int H, int F, int QS, int hd, int n, int max_ctx, int vocab) {
+    const size_t r = (size_t)(n > 0 ? n : 0);
+    return bverify_proc_head(H, F, QS, hd, n, max_ctx) + align_up(r * (size_t)(vocab > 0 ? vocab : 0) * 4, 256) + 2 * align_up(r * 8, 256) + 2 * align_up(r * 4, 256) +
+           align_up(logprob_workspace_bytes(n), 256) + 256;
+}
+static bool bverify_proc_carve(void* workspace, size_t workspace_bytes, size_t head, int n, int vocab, BProcBufs* b) {
+    char* wp = (char*)workspace; size_t off = head;
+    auto take = [&](size_t bytes) { off = align_up(off, 256); void* r = wp + off; off += bytes; return r; };
+    b->rows = (float*)take((size_t)n * vocab * 4);
+    b->consumed = (int64_t*)take((size_t)n * 8);
+    b->states = (int32_t*)take((size_t)n * 4);
+    b->tok_rows = (int64_t*)take((size_t)n * 8);
+    b->rec_rows = (int32_t*)take((size_t)n * 4);
+    b->lp_ws = take(logprob_workspace_bytes(n));
+    return off <= workspace_bytes;
+}
 int bverify_step(const BDecodeArgs& m, const BLayer* layers, bf16_t* kcache, bf16_t* vcache, int max_ctx, int n_slots, const BVerifyState& st, void* workspace,
-                 size_t workspace_bytes, hipStream_t s, const BLayerW4* qlayers, const BatchSampling* sampling, bool any_k) {
+                 size_t workspace_bytes, hipStream_t s, const BLayerW4* qlayers, const BatchSampling* sampling, bool any_k, const BVerifyProc* proc) {
     const int H = m.hidden, F = m.inter, hd = m.head_dim, QS = m.q_heads * hd, n = st.n;
+    const Penalties* pen = proc != nullptr ? proc->pen : nullptr;
+    const Constraints* con = proc != nullptr ? proc->con : nullptr;
+    const bool lp = proc != nullptr && proc->lp_tok != nullptr;
+    BProcBufs pb{};
+    if (pen != nullptr || con != nullptr || lp) {
+        // everything the plain step checks below holds for the head; the rest is carved here, before any launch
+        VILA_REQUIRE(n >= 2 && n <= 16 && m.vocab >= 1, "verify step (processed): 2..16 rows per step, got %d", n);
+        VILA_REQUIRE(workspace_bytes >= bverify_processed_workspace_bytes(H, F, QS, hd, n, max_ctx, m.vocab), "verify step (processed): workspace too small");
+        VILA_REQUIRE(!lp || ((proc->lp_top == nullptr) == (proc->lp_id == nullptr) && proc->lp_max_rec >= 1), "verify step (processed): the records need both "
+                     "top_logprob and top_id, or neither, and max_rec >= 1");
+        const size_t head = bverify_proc_head(H, F, QS, hd, n, max_ctx);
+        VILA_REQUIRE(bverify_proc_carve(workspace, workspace_bytes, head, n, m.vocab, &pb), "verify step (processed): workspace layout");
+        workspace_bytes = head;
+    }
     VILA_REQUIRE(n >= 2 && n <= 16, "verify step: 2..16 rows per step (1 committed token + up to 15 drafts), got %d", n);
     VILA_REQUIRE(st.slot >= 0 && st.slot < n_slots, "verify step: slot %d of a cache with %d", st.slot, n_slots);
     VILA_REQUIRE(hd == 128 && QS == H && m.q_heads % m.kv_heads == 0 && bdec_group_ok(m.q_heads / m.kv_heads) && max_ctx >= 1 && max_ctx <= BDEC_MAX_CTX,
@@ -655,20 +695,46 @@ int bverify_step(const BDecodeArgs& m, const BLayer* layers, bf16_t* kcache, bf1
     };
     VILA_TRY(bdec_forward(m, layers, qlayers, kcache + st.slot * slot_elems, vcache + st.slot * slot_elems, per_layer, 0, max_ctx, n, b.pos_rows, st.token,
                           st.logits, b, s, attn));
+    // the processing chain in front of the pick / draw (none of it without pen and con: the launch list is then the plain step's).  The greedy pairs
+    // are those of the last processing launch, which bver_accept_kernel merges as it merges bdec_pick1_kernel's
+    const float* pick_src = st.logits;
+    const bool greedy = sampling == nullptr;
+    if (pen != nullptr || con != nullptr)
+        VILA_TRY(launch_verify_chain(con, st.token, n, m.vocab, pb.states, pb.consumed, s));     // the chain's states, and token[] before the accept overwrites it
+    if (pen != nullptr) {
+        VILA_TRY(launch_penalize_verify(pick_src, m.vocab, n, m.vocab, *pen, st.token, pb.rows, m.vocab, PICK_SLICES, greedy && con == nullptr ? b.pick_v : nullptr,
+                                        greedy && con == nullptr ? b.pick_i : nullptr, s));
+        pick_src = pb.rows;
+    }
+    if (con != nullptr) {
+        VILA_TRY(launch_constrain_rows(pick_src, m.vocab, n, m.vocab, *con, pb.states, pb.rows, m.vocab, PICK_SLICES, greedy ? b.pick_v : nullptr,
+                                       greedy ? b.pick_i : nullptr, s));
+        pick_src = pb.rows;
+    }
     if (sampling != nullptr) {
         // row i draws a[i] with counter pos_rows[i] = pos + i (written by the draft kernel; pos moves only in the accept below) from entry 0 of the
         // one-entry parameter arrays (stride 0), into the workspace; no state advance in the sampler
-        VILA_TRY(launch_sample_batch(st.logits, m.vocab, n, m.vocab, *sampling, 0, b.pos_rows, b.draws, b.smp_ws, nullptr, nullptr, nullptr, nullptr, 0, s, any_k));
+        VILA_TRY(launch_sample_batch(pick_src, m.vocab, n, m.vocab, *sampling, 0, b.pos_rows, b.draws, b.smp_ws, nullptr, nullptr, nullptr, nullptr, 0, s, any_k));
         hipLaunchKernelGGL(bver_accept_draws_kernel, dim3(1), dim3(64), 0, s, (const int64_t*)b.draws, n, st.token, st.n_draft, st.pos, st.out_ids, st.n_out,
                            st.max_out, st.hist, st.n_hist, st.hist_cap, st.n_accept);
         VILA_LAUNCH_CHECK();
-        return 0;
+    } else {
+        if (pick_src == st.logits) {
+            hipLaunchKernelGGL(bdec_pick1_kernel, dim3(PICK_SLICES, n), dim3(256), 0, s, st.logits, m.vocab, b.pick_v, b.pick_i);
+            VILA_LAUNCH_CHECK();
+        }
+        hipLaunchKernelGGL(bver_accept_kernel, dim3(1), dim3(64 * n), 0, s, b.pick_v, b.pick_i, n, st.token, st.n_draft, st.pos, st.out_ids, st.n_out, st.max_out,
+                           st.hist, st.n_hist, st.hist_cap, st.n_accept);
+        VILA_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(bdec_pick1_kernel, dim3(PICK_SLICES, n), dim3(256), 0, s, st.logits, m.vocab, b.pick_v, b.pick_i);
-    VILA_LAUNCH_CHECK();
-    hipLaunchKernelGGL(bver_accept_kernel, dim3(1), dim3(64 * n), 0, s, b.pick_v, b.pick_i, n, st.token, st.n_draft, st.pos, st.out_ids, st.n_out, st.max_out,
-                       st.hist, st.n_hist, st.hist_cap, st.n_accept);
-    VILA_LAUNCH_CHECK();
+    // behind the accept: the commit of what the step consumed, and the records of what it emitted
+    if (pen != nullptr || con != nullptr)
+        VILA_TRY(launch_verify_commit(pen != nullptr ? pen->counts : nullptr, m.vocab, con != nullptr ? con->state : nullptr, pb.consumed, pb.states, st.n_accept, n, s));
+    if (lp) {
+        VILA_TRY(launch_logprobs_verify_index(st.out_ids, st.n_out, st.n_accept, n, st.max_out, pb.tok_rows, pb.rec_rows, s));
+        VILA_TRY(launch_logprobs(st.logits, m.vocab, n, m.vocab, pb.tok_rows, proc->lp_top != nullptr ? LP_TOP : 0, pb.rec_rows, 0, proc->lp_tok, proc->lp_top,
+                                 proc->lp_id, proc->lp_max_rec, pb.lp_ws, s, true));
+    }
     return 0;
 }
 

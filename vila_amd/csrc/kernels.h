@@ -98,19 +98,36 @@ constexpr int PEN_PICK_SLICES = 32;      // = decode_batch.hip's PICK_SLICES
 constexpr int PEN_SOLO_SLICES = 256;     // the batch-1 step: one block per CU, merged by launch_argmax_pick_advance
 int launch_penalize(const float* logits, int64_t ld, int n, int vocab, const Penalties& p, const int64_t* token, float* out, int64_t ld_out, int n_slices,
                     float* pick_v, int* pick_i, hipStream_t s);
+// the verify form: n <= PEN_VERIFY_MAX_ROWS rows of ONE sequence, row i penalised with counts[0][v] + #{j <= i : token[j] == v} (saturating) and entry 0
+// of the parameter arrays; the table is only read.  launch_verify_commit, behind the accept, by one thread: counts[consumed[j]] bumped for j = 0 .. *n_accept
+// and *state = states[*n_accept] (counts / state nullable, not both)
+constexpr int PEN_VERIFY_MAX_ROWS = 16;
+int launch_penalize_verify(const float* logits, int64_t ld, int n, int vocab, const Penalties& p, const int64_t* token, float* out, int64_t ld_out, int n_slices,
+                           float* pick_v, int* pick_i, hipStream_t s);
+int launch_verify_commit(uint16_t* counts, int vocab, int32_t* state, const int64_t* consumed, const int32_t* states, const int32_t* n_accept, int n,
+                         hipStream_t s);
 // structured output (constrain.hip): a token-class automaton per row behind the penalties and in front of the pick.  state[r] < 0 = unconstrained row;
 // token (nullable: no advance) = the token the step consumes; out may alias logits; pick_v / pick_i as launch_penalize's.  Two launches (one without token).
 constexpr int CON_MAX_CLASSES = 4096;    // = VILA_CONSTRAIN_MAX_CLASSES: one state's table row in LDS
 struct Constraints { int32_t* state; const uint16_t* cls; int64_t ld_cls; const int16_t* next; int64_t ld_next; const int32_t* n_classes; };
 int launch_constrain(const float* logits, int64_t ld, int n, int vocab, const Constraints& c, const int64_t* token, float* out, int64_t ld_out, int n_slices,
                      float* pick_v, int* pick_i, hipStream_t s);
+// the verify form: launch_verify_chain walks automaton 0 along token[0 .. n - 1] of ONE sequence into states_out (c->state is only read; c NULL: no
+// chain) and keeps the tokens in consumed (nullable); launch_constrain_rows masks row i from states[i] with automaton 0's classes and table
+int launch_verify_chain(const Constraints* c, const int64_t* token, int n, int vocab, int32_t* states_out, int64_t* consumed, hipStream_t s);
+int launch_constrain_rows(const float* logits, int64_t ld, int n, int vocab, const Constraints& c, const int32_t* states, float* out, int64_t ld_out, int n_slices,
+                          float* pick_v, int* pick_i, hipStream_t s);
 // log-probabilities of the chosen token and of the LP_TOP most likely ones from raw logits [n][ld] (logprob.hip): row r writes record rec[r] + rec_bias
 // (rec nullable) of token_lp [n][max_rec] and top_lp / top_id [n][max_rec][LP_TOP] (both or neither); an index outside 0 .. max_rec - 1 writes nothing
 constexpr int LP_TOP = 20;
 size_t logprob_workspace_bytes(int n);
 int logprob_slice_width(int vocab);
 int launch_logprobs(const float* logits, int64_t ld, int n, int vocab, const int64_t* token, int top_n, const int32_t* rec, int rec_bias, float* token_lp,
-                    float* top_lp, int32_t* top_id, int max_rec, void* workspace, hipStream_t s);
+                    float* top_lp, int32_t* top_id, int max_rec, void* workspace, hipStream_t s,
+                    bool one_seq = false);                                    // one_seq: every row writes output row 0 (the steps of ONE sequence)
+// behind a verify step's accept: tok_rows[i] / rec_rows[i] = the token row i emitted and its record, -1 / -1 for the rows behind *n_accept
+int launch_logprobs_verify_index(const int64_t* out_ids, const int32_t* n_out, const int32_t* n_accept, int n, int max_out, int64_t* tok_rows, int32_t* rec_rows,
+                                 hipStream_t s);
 // dynamic_s2 merge (s2.hip): tower output -> projector input, desc = device [n_blocks][6] {tile_base, bh, bw, i, j, single}
 int launch_s2_merge(const bf16_t* feats, bf16_t* out, const int32_t* desc, int n_blocks, int g, int C, int n_scales, const int* splits,
                     hipStream_t s);
@@ -257,9 +274,17 @@ struct BVerifyState {
 // (every row reads entry 0); the workspace is then bverify_sample_workspace_bytes
 size_t bverify_workspace_bytes(int H, int F, int QS, int hd, int n, int max_ctx);
 size_t bverify_sample_workspace_bytes(int H, int F, int QS, int hd, int n, int max_ctx);
+// the processing chain of a verify step (all nullable): penalties and an automaton of ONE sequence in front of the pick / draw, committed behind the
+// accept, and the records of the accepted rows.  With one of them the workspace is bverify_processed_workspace_bytes, whatever `sampling`.
+struct BVerifyProc {
+    const Penalties* pen; const Constraints* con;
+    float* lp_tok; float* lp_top; int32_t* lp_id; int lp_max_rec;             // lp_tok NULL: no records; lp_top / lp_id both or neither
+};
+size_t bverify_processed_workspace_bytes(int H, int F, int QS, int hd, int n, int max_ctx, int vocab);
 int bverify_step(const BDecodeArgs& m, const BLayer* layers, bf16_t* kcache, bf16_t* vcache, int max_ctx, int n_slots, const BVerifyState& st, void* workspace,
                  size_t workspace_bytes, hipStream_t s, const BLayerW4* qlayers = nullptr, const BatchSampling* sampling = nullptr,
-                 bool any_k = false);                                         // any_k: the rows' draws serve every top_k >= 0
+                 bool any_k = false,                                          // any_k: the rows' draws serve every top_k >= 0
+                 const BVerifyProc* proc = nullptr);
 int launch_verify_draft(const int64_t* hist, const int32_t* n_hist, int max_ngram, const int64_t* cand, const int32_t* n_cand, const int32_t* n_out, int n,
                         int64_t* token, int32_t* n_draft, const int32_t* pos, int32_t* pos_rows, hipStream_t s);
 int launch_decode_prologue(const bf16_t* table, const int64_t* tok, bf16_t* out, int H, int64_t vocab, const int32_t* pos, float* rope_cs,

@@ -22,6 +22,7 @@
 // Records: row r writes record rec[r] + rec_bias (rec NULL: rec_bias) of token_logprob [n][max_rec] and top_logprob / top_id [n][max_rec][20]; an
 // index outside 0 .. max_rec - 1 writes NOTHING (an idle row of a batch steps past its buffers).  Places from top_n on, and places a vocabulary
 // below 20 cannot fill, hold id -1 / -inf.  A token outside 0 .. V - 1 gives NaN for the chosen logprob and disturbs nothing else.
+// one_seq (the verify step): the rows are steps of ONE sequence, so every row writes output row 0 — record rec[r] of token_logprob [max_rec] etc.
 // Nothing at or beyond `vocab` within a row is read; nothing outside the records and the workspace is written.
 #include "kernels.h"
 
@@ -139,7 +140,7 @@ __global__ __launch_bounds__(256) void lp_slice_kernel(const float* __restrict__
 __global__ __launch_bounds__(256) void lp_final_kernel(const float* __restrict__ logits, int64_t ld, int V, int n_slices, const uint64_t* __restrict__ wkeys,
                                                        const float* __restrict__ wms, const int64_t* __restrict__ token, int top_n,
                                                        const int32_t* __restrict__ rec, int rec_bias, float* __restrict__ token_lp, float* __restrict__ top_lp,
-                                                       int32_t* __restrict__ top_id, int max_rec) {
+                                                       int32_t* __restrict__ top_id, int max_rec, int one_seq) {
     __shared__ LpSel sel;
     __shared__ float ms[2 * LP_MAX_SLICES];
     const int row = blockIdx.x, tid = threadIdx.x;
@@ -163,7 +164,7 @@ __global__ __launch_bounds__(256) void lp_final_kernel(const float* __restrict__
     float L = 0.f;
     for (int s = 0; s < n_slices; ++s) { const float m = ms[2 * s]; if (m > -INFINITY) L += ms[2 * s + 1] * expf(m - M); }
     const float lse = M + logf(L);
-    const int64_t o = (int64_t)row * max_rec + r;
+    const int64_t o = (one_seq ? (int64_t)0 : (int64_t)row * max_rec) + r;      // one_seq: every row is a step of ONE sequence and writes output row 0
     if (tid == 0) token_lp[o] = xt - lse;
     if (top_lp != nullptr) {
         const uint64_t best = sel.top[tid];
@@ -174,7 +175,7 @@ __global__ __launch_bounds__(256) void lp_final_kernel(const float* __restrict__
 }
 
 int launch_logprobs(const float* logits, int64_t ld, int n, int vocab, const int64_t* token, int top_n, const int32_t* rec, int rec_bias, float* token_lp,
-                    float* top_lp, int32_t* top_id, int max_rec, void* workspace, hipStream_t s) {
+                    float* top_lp, int32_t* top_id, int max_rec, void* workspace, hipStream_t s, bool one_seq) {
     static_assert(LP_TOP == 20 && LP_MAX_SLICES * LP_TOP <= 4 * 256, "stage 2 holds the candidates of a row as four keys per thread");
     VILA_REQUIRE(logits != nullptr && token != nullptr && token_lp != nullptr && workspace != nullptr, "logprobs: NULL argument");
     VILA_REQUIRE(n >= 1 && n <= 65535 && vocab >= 1, "logprobs: 1..65535 rows of a non-empty vocabulary (got %d x %d)", n, vocab);
@@ -189,7 +190,30 @@ int launch_logprobs(const float* logits, int64_t ld, int n, int vocab, const int
     hipLaunchKernelGGL(lp_slice_kernel, dim3(ns, n), dim3(256), 0, s, logits, ld, vocab, per, wkeys, wms);
     VILA_LAUNCH_CHECK();
     hipLaunchKernelGGL(lp_final_kernel, dim3(n), dim3(256), 0, s, logits, ld, vocab, ns, (const uint64_t*)wkeys, (const float*)wms, token, top_n, rec, rec_bias,
-                       token_lp, top_lp, top_id, max_rec);
+                       token_lp, top_lp, top_id, max_rec, one_seq ? 1 : 0);
+    VILA_LAUNCH_CHECK();
+    return 0;
+}
+
+// The records of a verify step (decode_batch.hip bverify_step), behind its accept: with m = *n_accept and old = *n_out - (m + 1), row i <= m emitted
+// out_ids[old + i], which goes into record old + i of the ONE sequence's arrays; a row behind m (a rejected draft, padding) gets record -1 and writes
+// nothing, and so does an id the guarded out_ids never held.  One wave writes tok_rows[i] / rec_rows[i] for launch_logprobs(one_seq).
+__global__ __launch_bounds__(64) void lp_verify_index_kernel(const int64_t* __restrict__ out_ids, const int32_t* __restrict__ n_out, const int32_t* __restrict__ n_accept,
+                                                             int n, int max_out, int64_t* __restrict__ tok_rows, int32_t* __restrict__ rec_rows) {
+    const int i = threadIdx.x;
+    if (i >= n) return;
+    int m = *n_accept;
+    m = m < 0 ? 0 : (m > n - 1 ? n - 1 : m);
+    const int64_t k = (int64_t)*n_out - (m + 1) + i;
+    const bool live = i <= m && k >= 0 && k < (int64_t)max_out;
+    tok_rows[i] = live ? out_ids[k] : (int64_t)-1;
+    rec_rows[i] = live ? (int32_t)k : -1;
+}
+int launch_logprobs_verify_index(const int64_t* out_ids, const int32_t* n_out, const int32_t* n_accept, int n, int max_out, int64_t* tok_rows, int32_t* rec_rows,
+                                 hipStream_t s) {
+    VILA_REQUIRE(out_ids != nullptr && n_out != nullptr && n_accept != nullptr && tok_rows != nullptr && rec_rows != nullptr && n >= 1 && n <= 64 && max_out >= 1,
+                 "logprobs (verify index): NULL argument, or not 1..64 rows");
+    hipLaunchKernelGGL(lp_verify_index_kernel, dim3(1), dim3(64), 0, s, out_ids, n_out, n_accept, n, max_out, tok_rows, rec_rows);
     VILA_LAUNCH_CHECK();
     return 0;
 }

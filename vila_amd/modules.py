@@ -299,7 +299,7 @@ def _as_i64(u: int) -> int:
 
 
 def _step_symbols(batch: bool, w4: bool, sampled: bool, verify: bool = False, verify_sample: bool = False, prefix: bool = False,
-                  penalized: bool = False, constrained: bool = False, any_k: bool = False) -> Tuple[str, str]:
+                  penalized: bool = False, constrained: bool = False, any_k: bool = False, processed: bool = False) -> Tuple[str, str]:
     """(step, workspace query) of one decode step variant, composed the way the C ABI names them.  verify: the greedy verify step, whatever `batch`.
     verify_sample: the sampled verify step, whatever `batch`, `sampled` and `verify` — a spelling of its own, since `verify` with `sampled` stays the
     refusal it always was (that pair names the greedy step asked to sample).  prefix: the batched step of a session with a shared prompt prefix
@@ -309,7 +309,14 @@ def _step_symbols(batch: bool, w4: bool, sampled: bool, verify: bool = False, ve
     ONE entry per driver as well, which takes the penalties as a nullable argument too, so `penalized` does not change the names either.
     any_k: the sampled pick that serves every top_k >= 0 — ONE entry for the batched step (int4 layers, prefix, penalties and automata nullable, so
     none of them changes the names) and one for the sampled verify step (int4 layers nullable).  It is an option of a sampled pick: the greedy
-    steps and the solo step (whose sampler serves any top_k already) have no such form."""
+    steps and the solo step (whose sampler serves any top_k already) have no such form.
+    processed: the verify step with penalties / an automaton in front of its pick and logprob records behind its accept — ONE entry for the verify steps
+    (int4 layers, sampling parameters, the any_k option, penalties, automaton and records all arguments of it, so none of them changes the names).  A
+    spelling of its own: `verify` / `verify_sample` with `penalized` or `constrained` stay the refusals they always were."""
+    if processed:
+        if not (verify or verify_sample) or prefix:
+            raise ValueError("the processed step is a verify step")
+        return "vila_llm_decode_step_verify_processed", "vila_llm_decode_verify_processed_workspace_bytes"
     if any_k:
         if verify_sample:
             if penalized or constrained or prefix:
@@ -909,6 +916,12 @@ class HipQwen2ForCausalLM(_HipModule):
         pen = getattr(st, "pen", None)                                  # a session with the penalties flag: the one entry of its driver, NULLs for what is off
         con = getattr(st, "con", None)                                  # a session with the constraints flag: likewise, the penalties nullable too
         ref = lambda s: None if s is None else C.byref(s)
+        if getattr(st, "processed", False):                             # a verify session with the processed flag: one entry, NULLs for what is off
+            name, _ = _step_symbols(batch, w4 is not None, sp is not None, verify, verify_sample, processed=True)
+            check(getattr(_lib.load(), name)(C.byref(self._struct()), w4.ptr if w4 is not None else None, C.byref(cache.c), C.byref(st.c), st.ws.data_ptr(),
+                                             st.ws.numel(), ref(sp), 1 if getattr(st, "any_k", False) else 0, ref(pen), ref(con), ref(getattr(st, "lp", None)),
+                                             ops._stream()), name)
+            return                                                      # (its records are written inside the entry, behind the accept)
         if getattr(st, "any_k", False):                                 # a session with the any_top_k flag: the one entry of its driver, NULLs for what is off
             name, _ = _step_symbols(batch, w4 is not None, sp is not None, verify, verify_sample, prefix=px is not None, any_k=True)
             args = ([C.byref(self._struct()), w4.ptr if w4 is not None else None, C.byref(cache.c), C.byref(st.c)] + ([] if verify_sample else [ref(px)]) +
@@ -1483,7 +1496,7 @@ class HipQwen2ForCausalLM(_HipModule):
                  prompt_ids: Optional[torch.Tensor] = None, draft_ids: Optional[torch.Tensor] = None, past_len: Optional[int] = None,
                  prefill_chunk: Optional[int] = None, spec_sample: Optional[bool] = None, num_return_sequences: Optional[int] = None,
                  repetition_penalty: Optional[float] = None, presence_penalty: Optional[float] = None, frequency_penalty: Optional[float] = None,
-                 logprobs: Optional[int] = None, constraint=None, any_top_k: Optional[bool] = None, **kw):
+                 logprobs: Optional[int] = None, constraint=None, any_top_k: Optional[bool] = None, spec_processed: Optional[bool] = None, **kw):
         """`llm.generate(inputs_embeds=, attention_mask=, **generation_kwargs)` as called at llava_arch.py:833 (HF semantics: returns ONLY the
         new tokens, [B, n_new]).  Greedy search or sampling (do_sample: temperature / top_k / top_p, HF order, on the device); explicit
         keyword arguments override `generation_config` (HF GenerationConfig-like: do_sample, temperature, top_k, top_p, max_new_tokens,
@@ -1522,14 +1535,15 @@ class HipQwen2ForCausalLM(_HipModule):
         sampled, solo or batched, bf16 or W4 (`vila_llm_decode_step[_batch]_penalized`).  They count the tokens this request has GENERATED: the
         prompt, given as embeddings, is not counted (HF's input_ids is empty then), so the first token is never penalised.  return_logits stays
         the raw model logits.  Neutral values (1, 0, 0 or None) take the unpenalised path, sessions and graphs untouched; the values never enter a
-        session key, so one captured graph serves every penalised request.  Not served with prompt_lookup_num_tokens / draft_ids / spec_sample.
+        session key, so one captured graph serves every penalised request.  With prompt_lookup_num_tokens / draft_ids / spec_sample only under
+        spec_processed=True (below).
         logprobs=k (None = off, today's call and return value; 0..20): returns (ids, lp) with lp a `Logprobs`: token_logprobs [B, n_new] fp32 — the
         log-probability of every returned token —, top_logprobs [B, n_new, k] fp32 and top_ids [B, n_new, k] int64 — the k most likely tokens at
         that position, descending, ties towards the lower id.  They are RAW: log_softmax of the model's logits in fp32, independent of temperature,
         top-k, top-p and penalties (vLLM's default; `return_logits` is raw as well), computed on the device behind every step, inside the captured
         graph (`vila_logprobs_f32`).  The positions behind a row's EOS (the pads of `ids`) hold 0.0 / -inf / -1.  The session carries a `logprobs`
         flag in its key and always records 20 alternatives, so one graph serves any k.  Served on every path above except speculative decoding
-        (prompt_lookup_num_tokens / draft_ids: the verify steps have no logprob form) and not together with return_logits or forced_ids.
+        (prompt_lookup_num_tokens / draft_ids: only under spec_processed=True, below) and not together with return_logits or forced_ids.
         constraint = a `vila_amd.constrain.Automaton` (None = off, today's call): structured output.  The reply is held to the automaton's language —
         a choice list, a regular expression or a JSON schema compiled over this model's vocabulary (`ConstraintCompiler`).  On the device, between
         the penalties and temperature / top-k / top-p (where HF runs a caller's logits_processor): every step advances the automaton by the token
@@ -1538,17 +1552,27 @@ class HipQwen2ForCausalLM(_HipModule):
         the automaton, with a state of its own), bf16 or W4, with batch_sample, num_return_sequences, penalties, logprobs (which stay RAW), cache= /
         past_len= / prefill_chunk.  return_logits stays raw, and its ids are the ones each step chose.  EOS is allowed exactly where the text is a
         member of the language; max_new_tokens can still cut the reply before that.  Not served with prompt_lookup_num_tokens / draft_ids /
-        spec_sample (the verify steps have no constrained form) and not with forced_ids (a forced token may leave the language).
+        spec_sample unless spec_processed=True (below), and not with forced_ids (a forced token may leave the language).
         any_top_k (opt-in, also read from generation_config; default False): with it, batch_sample, num_return_sequences and spec_sample serve EVERY
         top_k >= 0 — 0 = no top-k filter (pure temperature / top-p sampling, HF's meaning) and k > 64 — where they serve 1..64 without it (a padded
         batch then runs row by row, the other two raise).  Such rows are drawn on the device by the solo sampler's exact selection, one block per
         row and one launch more per step (`vila_llm_decode_step_batch_any_k`, `vila_llm_decode_step_verify_any_k`): a row's token is bit for bit
-        what `ops.sample` returns for the same logits, parameters, seed and counter.  The flag enters the session key, the values do not."""
+        what `ops.sample` returns for the same logits, parameters, seed and counter.  The flag enters the session key, the values do not.
+        spec_processed (opt-in, also read from generation_config; default False): with it, speculative decoding (prompt_lookup_num_tokens / draft_ids,
+        with spec_sample and any_top_k where the request samples) also serves repetition_penalty / presence_penalty / frequency_penalty, constraint=
+        and logprobs=k, in any mix, where each of them raises without it.  The verify step then runs the processing chain in front of its pick on
+        the device (`vila_llm_decode_step_verify_processed`): row i of a step is penalised with the counts behind the tokens the step has consumed
+        up to it and masked from the automaton's state behind them, the table and the state are committed behind the accept for the accepted
+        rows only, and every emitted token gets its RAW record.  The ids (and the records) are bit for bit those of the same session drafting
+        nothing.  With logprobs the call returns (ids, `Logprobs`), as the solo path does.  Batch 1; bf16 or W4; the flags enter the session key,
+        the values and the automaton do not."""
         self._check_append_args(inputs_embeds, cache, past_len, prefill_chunk)
+        spec_processed = bool(spec_processed if spec_processed is not None else
+                              (getattr(generation_config, "spec_processed", None) if generation_config is not None else False) or False)
         if constraint is not None:
             self._check_constraint(constraint, "generate")
             gc_ = generation_config
-            if (prompt_lookup_num_tokens is not None or draft_ids is not None or spec_sample or
+            if not spec_processed and (prompt_lookup_num_tokens is not None or draft_ids is not None or spec_sample or
                     (gc_ is not None and (getattr(gc_, "prompt_lookup_num_tokens", None) is not None or getattr(gc_, "spec_sample", None)))):
                 raise ValueError("constraint is not served with speculative decoding (prompt_lookup_num_tokens, draft_ids, spec_sample): the verify "
                                  "steps have no constrained form")
@@ -1560,8 +1584,8 @@ class HipQwen2ForCausalLM(_HipModule):
             if return_logits or forced_ids is not None:
                 raise ValueError("logprobs is not served together with return_logits / forced_ids: ask for one of them")
             gc_ = generation_config
-            if (prompt_lookup_num_tokens is not None or draft_ids is not None or
-                    (gc_ is not None and getattr(gc_, "prompt_lookup_num_tokens", None) is not None)):
+            if not spec_processed and (prompt_lookup_num_tokens is not None or draft_ids is not None or
+                                       (gc_ is not None and getattr(gc_, "prompt_lookup_num_tokens", None) is not None)):
                 raise ValueError("logprobs is not served with speculative decoding (prompt_lookup_num_tokens / draft_ids): the verify steps have no "
                                  "logprob form")
             logprobs = int(logprobs)
@@ -1569,8 +1593,8 @@ class HipQwen2ForCausalLM(_HipModule):
         pick = lambda v, name, default: v if v is not None else (getattr(gc, name, None) if gc is not None and getattr(gc, name, None) is not None else default)
         penalties = self._check_penalties(pick(repetition_penalty, "repetition_penalty", None), pick(presence_penalty, "presence_penalty", None),
                                           pick(frequency_penalty, "frequency_penalty", None))
-        if penalties is not None and (pick(prompt_lookup_num_tokens, "prompt_lookup_num_tokens", None) is not None or draft_ids is not None or
-                                      bool(pick(spec_sample, "spec_sample", False))):
+        if penalties is not None and not spec_processed and (pick(prompt_lookup_num_tokens, "prompt_lookup_num_tokens", None) is not None or
+                                                             draft_ids is not None or bool(pick(spec_sample, "spec_sample", False))):
             raise ValueError("repetition_penalty / presence_penalty / frequency_penalty are not served with speculative decoding "
                              "(prompt_lookup_num_tokens, draft_ids, spec_sample): the verify step has no penalised form")
         if num_return_sequences is not None and int(num_return_sequences) != 1:
@@ -1616,8 +1640,12 @@ class HipQwen2ForCausalLM(_HipModule):
                 if not 0.0 < top_p <= 1.0:
                     raise ValueError(f"`top_p` has to be a float > 0 and <= 1, but is {top_p}")
                 sampling = (temperature, top_k, top_p, int(self._fresh_seed() if seed is None else seed))
+            proc_kw = {}                                              # (keywords only when asked: a call without them makes the calls it always made)
+            if spec_processed:
+                proc_kw = dict(**({} if penalties is None else dict(penalties=penalties)), **({} if logprobs is None else dict(logprobs=logprobs)),
+                               **({} if constraint is None else dict(constraint=constraint)))
             return self._generate_verify(inputs_embeds, attention_mask, max_new_tokens, eos_token_id, k_spec, max_ngram, prompt_ids, draft_ids, cache, streamer,
-                                         past_len, prefill_chunk, sampling, **(dict(any_top_k=True) if any_top_k and sampling is not None else {}))
+                                         past_len, prefill_chunk, sampling, **(dict(any_top_k=True) if any_top_k and sampling is not None else {}), **proc_kw)
         if do_sample and temperature <= 0:
             raise ValueError(f"`temperature` (={temperature}) has to be a strictly positive float, otherwise your next token scores will be invalid.")
         if do_sample and top_k < 0:
@@ -1852,6 +1880,8 @@ class HipQwen2ForCausalLM(_HipModule):
 
     # ---- speculative decoding: lookup drafts, k + 1 rows of one sequence per step (vila_llm_decode_step_verify[_sample]) -------------------
     spec_trace = None           # diagnostics / tests: set to a list and _generate_verify syncs after every replay and appends its n_accept
+    spec_probe = None           # ... and, with spec_trace set, a callable invoked with the session after every such replay (one replay, synced): it may
+                                # read st.logits, st.token, st.n_out, st.n_accept of that replay
 
     def _verify_refusal(self) -> Optional[str]:
         """Why this model has no verify step, or None.  The restrictions are the batched step's."""
@@ -1865,14 +1895,23 @@ class HipQwen2ForCausalLM(_HipModule):
             return "the verify step reads q/k/v as one fused [q + 2kv, hidden] buffer (refuse() re-establishes it)"
         return None
 
-    def _verify_session(self, cache, n: int, max_out: int, max_ngram: int, sampled: bool = False, any_top_k: bool = False):
+    def _verify_session(self, cache, n: int, max_out: int, max_ngram: int, sampled: bool = False, any_top_k: bool = False, penalties: bool = False,
+                        constraints=None, logprobs: bool = False):
         """Device-resident state of a verify session (+ its captured hipGraph), keyed like `_decode_session`.  sampled: the session steps through
         the `_sample` entry points (another graph, hence part of the key) and owns the request's four sampling parameters as ONE-entry device
         tensors that `_verify_set_sampling` rewrites per request: neither the parameters nor the seed are baked into the graph.
         any_top_k (sampled sessions; in the key only when set): the session steps through `vila_llm_decode_step_verify_any_k`, whose draws serve
-        every top_k >= 0."""
+        every top_k >= 0.
+        penalties / constraints=(max_states, max_classes) / logprobs (each in the key only when set): the session steps through
+        `vila_llm_decode_step_verify_processed` and owns ONE count row with the three one-entry parameter tensors (`_penalty_state`), the bound
+        automaton arrays (`_constraint_state`) and the record arrays (`_logprob_state`), all at n = 1: the step's rows are ONE sequence.  The
+        values and the automaton are rewritten per request; the graph stays."""
         w4 = self._w4_batched()
         key = (cache.k.data_ptr(), cache.max_ctx, n, max_out, max_ngram, bool(sampled), *self._weights_key()) + (("any_top_k",) if any_top_k and sampled else ())
+        processed = bool(penalties) or bool(constraints) or bool(logprobs)
+        key += ("penalties",) if penalties else ()
+        key += ("constraints", *constraints) if constraints else ()
+        key += ("logprobs",) if logprobs else ()
         if self._vdecode is not None and self._vdecode.key == key:
             return self._vdecode
         self._drop_session("_vdecode")
@@ -1888,8 +1927,16 @@ class HipQwen2ForCausalLM(_HipModule):
             st.cand = torch.zeros(max_out, device=dev, dtype=torch.int64)
             st.hist = torch.zeros(cache.max_ctx + max_out + 1, device=dev, dtype=torch.int64)
             st.logits = torch.zeros((n, self.lcfg.vocab_size), device=dev, dtype=torch.float32)
-            ws_bytes = getattr(lib, _step_symbols(True, w4, False, verify=not sampled, verify_sample=bool(sampled))[1])
+            ws_bytes = getattr(lib, _step_symbols(True, w4, False, verify=not sampled, verify_sample=bool(sampled), **(dict(processed=True) if processed else {}))[1])
             st.ws = torch.empty((ws_bytes(C.byref(w.shape), n, cache.max_ctx),), device=dev, dtype=torch.uint8)
+            if processed:
+                st.processed = True
+                if penalties:
+                    self._penalty_state(st, 1, self.lcfg.vocab_size, dev)
+                if constraints:
+                    self._constraint_state(st, 1, self.lcfg.vocab_size, constraints, dev)
+                if logprobs:
+                    self._logprob_state(st, 1, max_out, dev)
             if sampled:                                             # ONE entry each: every row of a step reads entry 0
                 st.s_temperature = torch.zeros(1, device=dev, dtype=torch.float32)
                 st.s_top_k = torch.full((1,), 50, device=dev, dtype=torch.int32)
@@ -1919,12 +1966,15 @@ class HipQwen2ForCausalLM(_HipModule):
         self._step(True, self._w4 if st.w4 else None, cache, st, st.sp if st.sampled else None, verify=not st.sampled, verify_sample=st.sampled)
 
     def _generate_verify(self, inputs_embeds, attention_mask, max_new_tokens, eos_token_id, k, max_ngram, prompt_ids, draft_ids, cache, streamer,
-                         past_len=None, prefill_chunk=None, sampling=None, any_top_k: bool = False):
+                         past_len=None, prefill_chunk=None, sampling=None, any_top_k: bool = False, penalties=None, logprobs=None, constraint=None):
         """generate() for one sequence with the verify step: prefill as `_generate_solo`, first token from the prefill, then graph replays
         that each append 1 .. k + 1 tokens.  The host cuts at EOS and at max_new_tokens (a step may overshoot by up to k).
         sampling: None (greedy) or (temperature, top_k in 1..64, top_p, seed): the first token is drawn from the prefill's last row with counter
         S - 1, as `_generate_solo` draws it, and the steps draw with the positions of the tokens they consume (S, S + 1, ...).
-        any_top_k (with sampling): the session carries the any_top_k flag, so top_k may be 0 (no top-k filter) or above 64."""
+        any_top_k (with sampling): the session carries the any_top_k flag, so top_k may be 0 (no top-k filter) or above 64.
+        penalties / logprobs / constraint (generate(spec_processed=True)): as `_generate_solo` takes them.  The session carries the matching flags and
+        steps through the processed verify step; the first token is picked / drawn and recorded eagerly from the prefill's last row — penalties see
+        an empty table, the mask runs from the start state with no advance — and with logprobs the call returns (ids, `Logprobs`)."""
         why = self._verify_refusal()
         if why is not None:
             raise ValueError("prompt_lookup_num_tokens / draft_ids: " + why)
@@ -1934,12 +1984,23 @@ class HipQwen2ForCausalLM(_HipModule):
         S, cache, r, last = self._prefill_one(inputs_embeds, attention_mask, max_new_tokens, cache, admit, past_len, prefill_chunk)
         dev, n = inputs_embeds.device, k + 1
         eos_set = _eos_set(eos_token_id, self.lcfg.eos_token_id)
-        first = ops.argmax(r.last_logits[0]) if sampling is None else ops.sample(r.last_logits[0], *sampling, counter=last)
         need = max_new_tokens - 1                                   # tokens wanted from the steps
         st = self._verify_session(cache, n, max(max_new_tokens, 1) + k, max_ngram, sampling is not None,
-                                  **(dict(any_top_k=True) if any_top_k and sampling is not None else {}))
+                                  **(dict(any_top_k=True) if any_top_k and sampling is not None else {}),
+                                  **({} if penalties is None else dict(penalties=True)),
+                                  **({} if constraint is None else dict(constraints=self._constraint_caps(self.CONSTRAIN_MAX_STATES, self.CONSTRAIN_MAX_CLASSES))),
+                                  **({} if logprobs is None else dict(logprobs=True)))
         if sampling is not None:
             self._verify_set_sampling(st, sampling)
+        if penalties is not None:
+            self._set_penalties(st, 0, penalties)
+        pick_from = r.last_logits[0]
+        if constraint is not None:
+            self._set_constraint(st, 0, constraint)
+            pick_from = self._first_constrained(st, 0, pick_from)
+        first = ops.argmax(pick_from) if sampling is None else ops.sample(pick_from, *sampling, counter=last)
+        if logprobs is not None:
+            self._first_logprobs(st, 0, r.last_logits[0], first)
         # the history the lookup starts from: the prompt's ids (its tail, if longer than the room) and the first token
         room = st.hist.numel() - st.max_out - 1
         pids = torch.zeros(0, dtype=torch.int64, device=dev) if prompt_ids is None else prompt_ids.reshape(-1).to(device=dev, dtype=torch.int64)[-room:]
@@ -1955,6 +2016,12 @@ class HipQwen2ForCausalLM(_HipModule):
 
         def restore():
             st.pos.fill_(S); st.n_out.zero_(); st.n_hist.fill_(n0); st.token[:1].copy_(first)
+            if penalties is not None:
+                st.counts.zero_()                                   # the warm-up step outside capture committed what it consumed
+            if constraint is not None:
+                self._set_constraint(st, 0, constraint)             # ... moved the automaton
+            if logprobs is not None:                                # ... and wrote the records of what it emitted
+                st.lp_tok.zero_(); st.lp_top.fill_(float("-inf")); st.lp_id.fill_(-1)
         restore()
         if st.graph is None:
             _capture(st, lambda: self.verify_step(cache, st), restore)
@@ -1972,6 +2039,8 @@ class HipQwen2ForCausalLM(_HipModule):
                 n_out = min(int(st.n_out.item()), need, st.max_out)  # (the sync)
                 if trace is not None:
                     trace.append(int(st.n_accept.item()))
+                    if self.spec_probe is not None:
+                        self.spec_probe(st)
                 new = st.out_ids[len(got):n_out].tolist()
                 for t in new:
                     got.append(t)
@@ -1983,4 +2052,7 @@ class HipQwen2ForCausalLM(_HipModule):
         out = torch.tensor(_cut_at_eos([first_id] + got, eos_set)[:max(max_new_tokens, 1)], dtype=torch.int64, device=dev)
         if streamer is not None:
             streamer.end()
+        if logprobs is not None:                                    # (cut like `out`: record t - 1 of the session belongs to out[0, t])
+            m = out.numel()
+            return out[None], self._pack_logprobs([self._row_logprobs(st, 0, m - 1)], [m], m, logprobs, dev)
         return out[None]

@@ -495,6 +495,107 @@ def logprobs(logits: torch.Tensor, token: torch.Tensor, top_n: int = 0):
     return tok_lp[:, 0], top_lp[:, 0, :top_n], top_id[:, 0, :top_n]
 
 
+def _verify_rows(what: str, logits: torch.Tensor, token: torch.Tensor, out: Optional[torch.Tensor]):
+    """The shared argument checks of the verify-form operators -> (n, V, out, pv, pi)."""
+    _need(logits, dtype=torch.float32, name="logits")
+    if logits.dim() != 2 or logits.stride(1) != 1:
+        raise ValueError(f"{what}: logits must be [n, vocab] with contiguous rows")
+    n, V = logits.shape
+    _need(token, dtype=torch.int64, name="token")
+    if token.numel() != n or not token.is_contiguous():
+        raise ValueError(f"{what}: token must be a contiguous tensor of {n} entries")
+    if out is None:
+        out = torch.empty((n, V), device=logits.device, dtype=torch.float32)
+    else:
+        _need(out, dtype=torch.float32, name="out")
+        if out.dim() != 2 or out.shape != logits.shape or out.stride(1) != 1:
+            raise ValueError(f"{what}: out must be [n, vocab] fp32 with contiguous rows")
+    S = int(_lib.load().vila_logits_penalize_slices())
+    return n, V, out, torch.empty((n, S), device=logits.device, dtype=torch.float32), torch.empty((n, S), device=logits.device, dtype=torch.int32)
+
+
+def penalize_verify(logits: torch.Tensor, counts: torch.Tensor, repetition: torch.Tensor, presence: torch.Tensor, frequency: torch.Tensor,
+                    token: torch.Tensor, out: Optional[torch.Tensor] = None):
+    """The penalty launch of the processed verify step: logits [n, V] fp32 are n <= 16 rows of ONE sequence, row i consuming token[i] behind
+    token[0 .. i - 1].  counts [>= V] int16 / uint16 (ONE row, only read); repetition / presence / frequency: device tensors of ONE entry.  Row i is
+    penalised with min(65535, counts[v] + #{j <= i : token[j] == v}), by `penalize`'s expression.
+    -> (y [n, V], pair values [n, S], pair indices [n, S] i32)."""
+    n, V, out, pv, pi = _verify_rows("penalize_verify", logits, token, out)
+    _need(counts, dtype=None, name="counts")
+    if counts.dtype not in (torch.int16, torch.uint16) or counts.dim() != 1 or counts.numel() < V or not counts.is_contiguous():
+        raise ValueError(f"penalize_verify: counts must be ONE contiguous row of >= {V} int16 / uint16 entries")
+    for name, t in (("repetition", repetition), ("presence", presence), ("frequency", frequency)):
+        _need(t, dtype=torch.float32, name=name)
+        if t.numel() != 1:
+            raise ValueError(f"penalize_verify: {name} must hold ONE entry")
+    import ctypes as C
+    pen = _lib.VilaPenalties(repetition.data_ptr(), presence.data_ptr(), frequency.data_ptr(), counts.data_ptr(), counts.numel())
+    check(_lib.load().vila_logits_penalize_verify_f32(logits.data_ptr(), max(logits.stride(0), V), n, V, C.byref(pen), token.data_ptr(), out.data_ptr(),
+                                                      max(out.stride(0), V), pv.data_ptr(), pi.data_ptr(), _stream()), "penalize_verify")
+    return out, pv, pi
+
+
+def constrain_verify(logits: torch.Tensor, state: torch.Tensor, cls: torch.Tensor, next: torch.Tensor, n_classes: torch.Tensor, token: torch.Tensor,
+                     out: Optional[torch.Tensor] = None):
+    """The automaton launches of the processed verify step: logits [n, V] fp32 are n <= 16 rows of ONE sequence under ONE automaton — state [1] i32
+    (only read), cls [>= V] int16 / uint16, next [ld] int16, n_classes [1] i32.  s_0 = adv(state, token[0]), s_i = adv(s_{i-1}, token[i]) by
+    `logits_constrain`'s advance rule; row i is masked from s_i.  out may be `logits` itself.
+    -> (y [n, V], states [n] i32, pair values [n, S], pair indices [n, S] i32)."""
+    n, V, out, pv, pi = _verify_rows("constrain_verify", logits, token, out)
+    for name, t, dts, m in (("cls", cls, (torch.int16, torch.uint16), V), ("next", next, (torch.int16,), 1)):
+        _need(t, dtype=None, name=name)
+        if t.dtype not in dts or t.dim() != 1 or t.numel() < m or not t.is_contiguous():
+            raise ValueError(f"constrain_verify: {name} must be ONE contiguous row of >= {m} entries")
+    for name, t in (("state", state), ("n_classes", n_classes)):
+        _need(t, dtype=torch.int32, name=name)
+        if t.numel() != 1:
+            raise ValueError(f"constrain_verify: {name} must hold ONE entry")
+    import ctypes as C
+    states = torch.empty(n, device=logits.device, dtype=torch.int32)
+    con = _lib.VilaConstraints(state.data_ptr(), cls.data_ptr(), cls.numel(), next.data_ptr(), next.numel(), n_classes.data_ptr())
+    check(_lib.load().vila_logits_constrain_verify_f32(logits.data_ptr(), max(logits.stride(0), V), n, V, C.byref(con), token.data_ptr(), states.data_ptr(),
+                                                       out.data_ptr(), max(out.stride(0), V), pv.data_ptr(), pi.data_ptr(), _stream()), "constrain_verify")
+    return out, states, pv, pi
+
+
+def verify_commit(vocab: int, consumed: torch.Tensor, n_accept: torch.Tensor, counts: Optional[torch.Tensor] = None,
+                  state: Optional[torch.Tensor] = None, states: Optional[torch.Tensor] = None) -> None:
+    """The commit behind a verify step's accept, in place: with m = n_accept[0] (i32, device; clamped to 0 .. n - 1), counts [>= vocab] (ONE row) gets
+    one saturating bump for each of consumed[0 .. m] (i64 [n]; ids outside the vocabulary bump nothing) and state [1] i32 becomes states[m]."""
+    _need(consumed, dtype=torch.int64, name="consumed")
+    _need(n_accept, dtype=torch.int32, name="n_accept")
+    n = consumed.numel()
+    if counts is not None and (counts.dtype not in (torch.int16, torch.uint16) or counts.dim() != 1 or counts.numel() < vocab or not counts.is_contiguous()):
+        raise ValueError(f"verify_commit: counts must be ONE contiguous row of >= {vocab} int16 / uint16 entries")
+    if (state is None) != (states is None) or (states is not None and (states.dtype != torch.int32 or states.numel() != n or state.dtype != torch.int32)):
+        raise ValueError(f"verify_commit: state [1] i32 comes with states [{n}] i32")
+    import ctypes as C
+    pen = None if counts is None else _lib.VilaPenalties(counts.data_ptr(), counts.data_ptr(), counts.data_ptr(), counts.data_ptr(), counts.numel())
+    con = None if state is None else _lib.VilaConstraints(state.data_ptr(), None, 0, None, 0, None)
+    check(_lib.load().vila_verify_commit(None if pen is None else C.byref(pen), None if con is None else C.byref(con), int(vocab), consumed.data_ptr(),
+                                         _p(states), n_accept.data_ptr(), n, _stream()), "verify_commit")
+
+
+def logprobs_seq(logits: torch.Tensor, token: torch.Tensor, rec: torch.Tensor, token_lp: torch.Tensor, top_lp: torch.Tensor, top_id: torch.Tensor) -> None:
+    """`logprobs` for the rows of ONE sequence, in place: row r of logits [n, V] writes record rec[r] (i32, device; outside 0 .. max_rec - 1: nothing) of
+    token_lp [max_rec] f32, top_lp [max_rec, 20] f32 and top_id [max_rec, 20] i32 — what the processed verify step runs behind its accept."""
+    _need(logits, dtype=torch.float32, name="logits")
+    n, V = logits.shape
+    _need(token, dtype=torch.int64, name="token")
+    _need(rec, dtype=torch.int32, name="rec")
+    max_rec = token_lp.numel()
+    if token.numel() != n or rec.numel() != n or tuple(top_lp.shape) != (max_rec, LOGPROBS_MAX_TOP) or tuple(top_id.shape) != (max_rec, LOGPROBS_MAX_TOP) or \
+            token_lp.dtype != torch.float32 or top_lp.dtype != torch.float32 or top_id.dtype != torch.int32 or \
+            not (token_lp.is_contiguous() and top_lp.is_contiguous() and top_id.is_contiguous()):
+        raise ValueError(f"logprobs_seq: token / rec hold {n} entries, token_lp [max_rec] f32, top_lp / top_id [max_rec, {LOGPROBS_MAX_TOP}] f32 / i32, contiguous")
+    import ctypes as C
+    lib = _lib.load()
+    ws = torch.empty((lib.vila_logprobs_workspace_bytes(n),), device=logits.device, dtype=torch.uint8)
+    out = _lib.VilaLogprobOut(token_lp.data_ptr(), top_lp.data_ptr(), top_id.data_ptr(), max_rec)
+    check(lib.vila_logprobs_seq_f32(logits.data_ptr(), logits.stride(0), n, V, token.data_ptr(), LOGPROBS_MAX_TOP, rec.data_ptr(), C.byref(out), ws.data_ptr(),
+                                    _stream()), "logprobs_seq")
+
+
 def attn_decode_batch(q: torch.Tensor, kcache: torch.Tensor, vcache: torch.Tensor, pos: torch.Tensor, scale: Optional[float] = None) -> torch.Tensor:
     """The batched decode step's attention on its own: q [n, q_heads, 128] bf16 (rows may be strided), kcache / vcache ONE layer's
     [slots >= n, kv_heads, max_ctx, 128] bf16 (contiguous), pos [n] i32 — row i attends keys 0 .. pos[i] of slot i.  max_ctx up to 32768, GQA

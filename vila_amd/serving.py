@@ -512,7 +512,7 @@ def generate_content(model, tokenizer, prompt: Union[str, Sequence[Any]], max_ne
                      repetition_penalty: Optional[float] = None, presence_penalty: Optional[float] = None,
                      frequency_penalty: Optional[float] = None, logprobs: Optional[bool] = None, top_logprobs: Optional[int] = None,
                      response_format=None, guided_choice: Optional[Sequence[str]] = None, guided_regex: Optional[str] = None,
-                     any_top_k: bool = False) -> str:
+                     any_top_k: bool = False, spec_processed: bool = False) -> str:
     """Text + images in, decoded reply out — the contract of `LlavaLlamaModel.generate_content` for image / text prompts.
     temperature > 0 samples (server.py:185-187: do_sample = temperature > 0, with the request's top_p and HF's default top_k = 50).
     prompt_lookup_num_tokens=k: speculative decoding with k lookup drafts per step (`llm.generate(prompt_lookup_num_tokens=)`); the reply is
@@ -522,26 +522,29 @@ def generate_content(model, tokenizer, prompt: Union[str, Sequence[Any]], max_ne
     `any_top_k=True` on with them, and the speculating request may carry any top_k >= 0 (0 = no top-k filter).
     streamer: a `TextStream` (or any HF streamer) that receives the new tokens while they are generated (`llm.generate(streamer=...)`).
     repetition_penalty / presence_penalty / frequency_penalty: passed on to `llm.generate` when they are not neutral (1 / 0 / 0 or None); a
-    penalised request is not speculated (prompt_lookup_num_tokens is dropped for it: the verify step has no penalised form).
+    penalised request is not speculated (prompt_lookup_num_tokens is dropped for it) unless spec_processed=True, below.
     logprobs=True (with top_logprobs = 0..20 alternatives per token): the reply comes back as a `ReplyWithLogprobs` — the same text, with
     `.logprobs`, one OpenAI-layout entry per reply token (`logprob_entries`), cut exactly where the text's tokens are cut: the EOS and what follows
     are dropped.  The numbers are RAW: the model's own distribution, independent of temperature, top_p and penalties (`llm.generate(logprobs=)`).
-    Such a request is not speculated either (the verify step has no logprob form).
+    Such a request is not speculated either, unless spec_processed=True.
     response_format (the reference's `ResponseFormat`: {"type": "json_schema", "json_schema": {"schema": ...}}, an object or a dict), guided_choice
     (a list of strings) or guided_regex (a pattern): structured output — the reply is held to the schema (in the layout of
     `json.dumps(obj, indent=2)`), to one of the strings, or to the pattern, by a token automaton on the device (`llm.generate(constraint=)`,
     `vila_amd/constrain.py` has the served subsets; `{"type": "json_object"}` is not served).  max_new_tokens can still cut the reply before it is
-    complete.  Such a request is not speculated and not streamed."""
+    complete.  Such a request is not streamed, and not speculated unless spec_processed=True.
+    spec_processed=True (default False): a penalised, logprob or structured request KEEPS prompt_lookup_num_tokens instead of dropping it, and
+    `spec_processed=True` travels to `llm.generate` with it (the processed verify step); the reply is the one the same request gives without drafts."""
     asks = check_structured_request(dict(response_format=response_format, guided_choice=guided_choice, guided_regex=guided_regex), streamer is not None)
     constraint = None
     if asks:
         from .modules import HipQwen2ForCausalLM as _Llm
         constraint = constraint_of(asks, constraint_compiler(tokenizer, model.cfg.llm.vocab_size, eos_token_id,
                                                              max_table=_Llm.CONSTRAIN_MAX_STATES * _Llm.CONSTRAIN_MAX_CLASSES))
-        prompt_lookup_num_tokens = None
+        if not spec_processed:
+            prompt_lookup_num_tokens = None
     pen = _penalties_of(dict(repetition_penalty=repetition_penalty, presence_penalty=presence_penalty, frequency_penalty=frequency_penalty))
     n_top = _logprobs_of(logprobs, top_logprobs)
-    if pen or n_top is not None:
+    if (pen or n_top is not None) and not spec_processed:
         prompt_lookup_num_tokens = None
     cfg = model.cfg
     dev = device or str(model.device)
@@ -558,6 +561,8 @@ def generate_content(model, tokenizer, prompt: Union[str, Sequence[Any]], max_ne
                 gen.update(any_top_k=True)
     elif prompt_lookup_num_tokens is not None:
         gen.update(prompt_lookup_num_tokens=int(prompt_lookup_num_tokens))
+    if spec_processed and "prompt_lookup_num_tokens" in gen and (pen or n_top is not None or constraint is not None):
+        gen.update(spec_processed=True)                # (keyword only for a request that needs it: every other call is the one it always was)
     if streamer is not None:
         gen.update(streamer=streamer)
     gen.update(pen)
@@ -596,7 +601,7 @@ class ChatSession:
     So the next turn's new tokens open with that last token, then the end-of-turn marker if the reply was cut by max_new_tokens rather than by it,
     the separator and the new user turn in the Qwen2 chat form (`chat_text`, the template every NVILA recipe runs).  Media of a later turn are
     encoded and spliced for the new part only.  gen_defaults / `ask(**gen)`: keyword arguments of `llm.generate` (do_sample, temperature, top_k,
-    top_p, seed, prompt_lookup_num_tokens, spec_sample, streamer, repetition_penalty, presence_penalty, frequency_penalty, ...).  The penalties
+    top_p, seed, prompt_lookup_num_tokens, spec_sample, spec_processed, streamer, repetition_penalty, presence_penalty, frequency_penalty, ...).  The penalties
     count what the CURRENT turn has generated: every `ask` is a request of its own, earlier turns are prompt."""
 
     TURN_END = "<|im_end|>"
@@ -1342,7 +1347,7 @@ def continuous_batching(model) -> bool:
 def create_app(model, tokenizer, model_name: str = "NVILA-8B", batch_window_s: Optional[float] = None, max_batch: int = 8,
                stream_timeout_s: Optional[float] = 600.0, batch_sampled: bool = False, max_ctx: int = 2048,
                prompt_lookup_num_tokens: Optional[int] = None, spec_sample: bool = False, share_prefix: bool = False, penalties: bool = False,
-               logprobs: bool = False, constraints: bool = False, any_top_k: bool = False):
+               logprobs: bool = False, constraints: bool = False, any_top_k: bool = False, spec_processed: bool = False):
     """FastAPI app with the reference's POST /chat/completions (server.py:171-290).  Import-time optional: needs fastapi + pydantic.
     batch_window_s: when set (any value), requests go through a batcher whose ONE worker thread owns the model: `ContinuousBatcher` (greedy
     requests join / leave the batched decode step between steps; sampled ones run solo on the same thread) where the model has the batched
@@ -1380,7 +1385,9 @@ def create_app(model, tokenizer, model_name: str = "NVILA-8B", batch_window_s: O
     what an OpenAI-style client means); any other negative value comes back as the usual 500 body.  A greedy request ignores it.
     any_top_k=True (default off; with batch_sampled, ContinuousBatcher only): the batched session's sampler serves every top_k >= 0, so a sampled
     request with top_k = 0 or > 64 takes a row; without it such a request runs solo, as a penalised one does without `penalties=`.  With
-    spec_sample (and prompt_lookup_num_tokens) it lets solo sampled requests with such a top_k speculate as well."""
+    spec_sample (and prompt_lookup_num_tokens) it lets solo sampled requests with such a top_k speculate as well.
+    spec_processed=True (default off; with prompt_lookup_num_tokens): penalised, logprob and structured requests that this app runs solo speculate
+    as well (`generate_content(spec_processed=True)`) instead of dropping the drafts; their replies are those of the same requests without drafts."""
     from fastapi import FastAPI
     from fastapi.responses import JSONResponse, StreamingResponse
 
@@ -1454,6 +1461,8 @@ def create_app(model, tokenizer, model_name: str = "NVILA-8B", batch_window_s: O
                 kw.update(spec_sample=True, top_k=top_k)
                 if any_top_k and not 1 <= top_k <= 64:
                     kw.update(any_top_k=True)
+            if spec_processed and prompt_lookup_num_tokens is not None:
+                kw.update(spec_processed=True)
             return generate_content(model, tokenizer, parts, max_new_tokens=n, system=system, temperature=temperature, top_p=top_p, streamer=streamer, **kw)
 
     async def chat_completions(request):
