@@ -465,6 +465,29 @@ int vila_sumsq_bf16(const void* x, int64_t n, float* out, float* scratch, vila_s
 
 
 /* ------------------------------------------------------------------------------------------------------------
+ * LoRA fine-tuning (reference llava/train/train.py:149-171, 648-706): the three skinny products of a rank-r adapter.  All operands bf16,
+ * fp32 accumulation, `scale` applied to the fp32 accumulator before anything else is added, one rounding to bf16.  R, the skinny width,
+ * is a multiple of 16 from 16 to 192 (q|k|v stacked at r = 64).  Every leading dimension is a multiple of 8 elements and every base
+ * pointer 16-byte aligned; a call that breaks this returns -1 and launches nothing.  Same bits on every run: split sums are combined in
+ * a fixed order from fp32 partials in `workspace` (vila_lora_*_workspace_bytes; nothing outside it is written), never with atomics.
+ * ------------------------------------------------------------------------------------------------------------ */
+size_t vila_lora_down_workspace_bytes(int M, int K, int R);
+size_t vila_lora_up_workspace_bytes(int M, int N, int R);
+size_t vila_lora_wgrad_workspace_bytes(int M, int R, int C);
+/* T[M, R] = scale * X[M, K] . A[R, K]^T; X and A rows contiguous along K (K % 8 == 0); T may be a column slice of a wider buffer */
+int vila_lora_down_bf16(const void* X, int64_t ldx, const void* A, int64_t lda, void* T, int64_t ldt, int M, int K, int R, float scale,
+                        void* workspace, size_t workspace_bytes, vila_stream_t stream);
+/* Y[M, N] = Res[M, N] (nullable) + scale * T[M, R] . Bt[R, N]; Bt rows contiguous along N (N % 8 == 0); Y and Res may be column slices;
+ * Res aliases nothing, Y is write-only */
+int vila_lora_up_bf16(const void* T, int64_t ldt, const void* Bt, int64_t ldb, const void* Res, int64_t ldres, void* Y, int64_t ldy, int M,
+                      int N, int R, float scale, void* workspace, size_t workspace_bytes, vila_stream_t stream);
+/* G[R, C] = scale * L[M, R]^T . X[M, C] (accumulate: + G); the contraction runs over the M rows and both operands are read as they lie
+ * (C % 8 == 0, any M >= 1) */
+int vila_lora_wgrad_bf16(const void* L, int64_t ldl, const void* X, int64_t ldx, void* G, int64_t ldg, int M, int R, int C, float scale,
+                         int accumulate, void* workspace, size_t workspace_bytes, vila_stream_t stream);
+
+
+/* ------------------------------------------------------------------------------------------------------------
  * The whole SFT forward + backward as ONE call — replaces what autograd does under the reference's
  * patched `Trainer.training_step` (llava/train/transformer_normalize_monkey_patch.py:183-249): LlavaLlamaModel.forward
  * (llava_llama.py:94-159) on a packed batch, loss = sum CE * loss_scale (loss_scale = 1 / GLOBAL num_items, :261-268), gradients of

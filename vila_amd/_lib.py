@@ -346,6 +346,15 @@ PROTOTYPES = {
                                                  c_void_p, c_void_p]),
     "vila_verify_commit": (c_int, [C.POINTER(VilaPenalties), C.POINTER(VilaConstraints), c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "vila_logprobs_seq_f32": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_int, c_void_p, C.POINTER(VilaLogprobOut), c_void_p, c_void_p]),
+    # ---- LoRA: the three skinny products of a rank-r adapter ----
+    "vila_lora_down_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "vila_lora_up_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "vila_lora_wgrad_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "vila_lora_down_bf16": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_float, c_void_p, c_size_t, c_void_p]),
+    "vila_lora_up_bf16": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_float, c_void_p,
+                                  c_size_t, c_void_p]),
+    "vila_lora_wgrad_bf16": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_float, c_int, c_void_p, c_size_t,
+                                     c_void_p]),
 }
 
 _lib: Optional[C.CDLL] = None

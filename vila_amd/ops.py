@@ -1034,3 +1034,60 @@ def s2_merge_bwd(dy: torch.Tensor, tile_desc: torch.Tensor, n_scales: int, split
     check(_L().vila_s2_merge_bwd_bf16(dy.contiguous().data_ptr(), dx.data_ptr(), tile_desc.contiguous().data_ptr(), tile_desc.shape[0], g, Cc,
                                       n_scales, sp, _stream()), "s2_merge_bwd")
     return dx
+
+
+# ---- LoRA: the three skinny products of a rank-r adapter (vila_amd/csrc/lora.hip) -------------------------------------------------------------
+def _lora_ws(n_bytes: int, device) -> Optional[torch.Tensor]:
+    return torch.empty((n_bytes,), device=device, dtype=torch.uint8) if n_bytes else None
+
+
+def lora_down(x: torch.Tensor, a: torch.Tensor, scale: float = 1.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[M, R] = scale * x[M, K] @ a[R, K]^T.  `out` may be a column slice of a wider buffer (the q|k|v stack of the backward)."""
+    _need(x, name="x"); _need(a, name="a")
+    assert x.dim() == 2 and a.dim() == 2 and x.stride(1) == 1 and a.stride(1) == 1
+    if x.shape[1] != a.shape[1]:
+        raise ValueError(f"lora_down: contraction widths differ ({x.shape[1]} vs {a.shape[1]})")
+    M, K = x.shape
+    R = a.shape[0]
+    if out is None:
+        out = torch.empty((M, R), device=x.device, dtype=torch.bfloat16)
+    assert out.shape == (M, R) and out.stride(1) == 1 and out.dtype == torch.bfloat16
+    n = int(_L().vila_lora_down_workspace_bytes(M, K, R))
+    ws = _lora_ws(n, x.device)
+    check(_L().vila_lora_down_bf16(x.data_ptr(), x.stride(0), a.data_ptr(), a.stride(0), out.data_ptr(), out.stride(0), M, K, R, float(scale), _p(ws), n,
+                                   _stream()), "lora_down")
+    return out
+
+
+def lora_up(t: torch.Tensor, bt: torch.Tensor, scale: float = 1.0, res: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[M, N] = res + scale * t[M, R] @ bt[R, N].  `t`, `res` and `out` may be column slices; `out` is write-only and `res` aliases nothing."""
+    _need(t, name="t"); _need(bt, name="bt")
+    assert t.dim() == 2 and bt.dim() == 2 and t.stride(1) == 1 and bt.stride(1) == 1
+    if t.shape[1] != bt.shape[0]:
+        raise ValueError(f"lora_up: contraction widths differ ({t.shape[1]} vs {bt.shape[0]})")
+    M, R = t.shape
+    N = bt.shape[1]
+    if out is None:
+        out = torch.empty((M, N), device=t.device, dtype=torch.bfloat16)
+    assert out.shape == (M, N) and out.stride(1) == 1 and out.dtype == torch.bfloat16
+    if res is not None:
+        _need(res, name="res"); assert res.shape == (M, N) and res.stride(1) == 1
+    check(_L().vila_lora_up_bf16(t.data_ptr(), t.stride(0), bt.data_ptr(), bt.stride(0), _p(res), res.stride(0) if res is not None else 0, out.data_ptr(),
+                                 out.stride(0), M, N, R, float(scale), None, 0, _stream()), "lora_up")
+    return out
+
+
+def lora_wgrad(l: torch.Tensor, x: torch.Tensor, out: torch.Tensor, scale: float = 1.0, accumulate: bool = False) -> torch.Tensor:
+    """out[R, C] (+)= scale * l[M, R]^T @ x[M, C]: the contraction runs over the rows, both operands are read as they lie."""
+    _need(l, name="l"); _need(x, name="x"); _need(out, name="out")
+    assert l.dim() == 2 and x.dim() == 2 and l.stride(1) == 1 and x.stride(1) == 1 and out.stride(1) == 1
+    if l.shape[0] != x.shape[0]:
+        raise ValueError(f"lora_wgrad: row counts differ ({l.shape[0]} vs {x.shape[0]})")
+    M, R = l.shape
+    C = x.shape[1]
+    assert out.shape == (R, C)
+    n = int(_L().vila_lora_wgrad_workspace_bytes(M, R, C))
+    ws = _lora_ws(n, x.device)
+    check(_L().vila_lora_wgrad_bf16(l.data_ptr(), l.stride(0), x.data_ptr(), x.stride(0), out.data_ptr(), out.stride(0), M, R, C, float(scale),
+                                    int(accumulate), _p(ws), n, _stream()), "lora_wgrad")
+    return out

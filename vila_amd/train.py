@@ -36,7 +36,7 @@ from .modules import _get
 class FlatParams:
     """Re-points every parameter of (llm, vision_tower, mm_projector) into one flat bf16 buffer; same layout for grads."""
 
-    def __init__(self, model, with_optimizer_state: bool = True):
+    def __init__(self, model, with_optimizer_state: bool = True, with_grads: bool = True):
         if getattr(model.llm, "_bf16_released", False):
             raise RuntimeError("FlatParams: the LLM's bf16 projection weights were freed by quantize_w4(release_bf16=True); "
                                "an SFT step cannot be built on the int4 copies")
@@ -66,7 +66,8 @@ class FlatParams:
             off += (p.numel() + 7) // 8 * 8          # keep every tensor 16-B aligned
         self.numel = off
         self.params = torch.zeros(off, device=dev, dtype=torch.bfloat16)
-        self.grads = torch.zeros(off, device=dev, dtype=torch.bfloat16)
+        # with_grads=False: a frozen base under adapters (vila_amd/lora.py), whose gradients are neither computed nor stored
+        self.grads = torch.zeros(off, device=dev, dtype=torch.bfloat16) if with_grads else None
         with torch.no_grad():
             for n, p in entries:
                 o, k, shape = self.index[n]
@@ -318,7 +319,7 @@ class SFTTrainer:
                  max_grad_norm: Optional[float] = None, optimizer_state: bool = True, group=None, decay_groups: bool = True):
         self.model = model
         self.cfg = model.cfg
-        self.flat = FlatParams(model, with_optimizer_state=optimizer_state)
+        self.flat = self._make_flat(model, optimizer_state)
         self.reducer = GradReducer(self.flat, group)
         self.lr, self.betas, self.eps, self.wd = lr, betas, eps, weight_decay
         self.max_grad_norm = max_grad_norm
@@ -343,6 +344,10 @@ class SFTTrainer:
         # None: a plain step; "hold": not the last micro-batch (no exchange, no update); "add": the last one (bucket += held sum, then as usual)
         self._acc: Optional[torch.Tensor] = None
         self._acc_mode: Optional[str] = None
+
+    def _make_flat(self, model, optimizer_state: bool) -> FlatParams:
+        """The flat parameter / gradient / optimizer storage of this trainer (vila_amd/lora.py keeps the trainable elements only)."""
+        return FlatParams(model, with_optimizer_state=optimizer_state)
 
     def _ready(self, prefix: str) -> None:
         """Gradients under `prefix` are final once the compute stream and the wgrad stream reach this point: hand the bucket to the
@@ -914,7 +919,7 @@ class SFTTrainer:
                 logits = ops.gemm(hv[r0:r1], head, out_f32=True)                         # [<= LOGIT_CHUNK, V] fp32
                 ops.ce_loss(logits, tgt_valid[r0:r1], loss, 1.0 / max(n_items, 1), out=dlog[r0:r1])
             del logits
-            dhv = linear_bwd(hv, head, dlog, G(head_name), cm=True, ws=self.ws)
+            dhv = self._head_bwd(hv, head, dlog, head_name)
             ops.copy_rows(dhv, dhn, None, rows32, n_valid)
         if not c.tie_word_embeddings:
             self._ready("llm.lm_head.")
@@ -922,18 +927,7 @@ class SFTTrainer:
         self._ready("llm.model.norm.")
         dx0 = self._llm_bwd(dx, saved)
         # ---- embedding rows (text + "\n") and media rows ----
-        ge = G("llm.model.embed_tokens.weight")
-        dtxt = torch.empty((int(txt_dst.numel()), H), device=dev, dtype=torch.bfloat16)
-        ops.copy_rows(dx0, dtxt, txt_dst, None, int(txt_dst.numel()))
-        # the token ids are uploaded a second time on purpose: the pageable copy holds the host back until the decoder's backward has drained.
-        # With the projector / tower backward enqueued further ahead instead, the step measured 180.9-181.2 against 179.3-180.5 ms on one
-        # box, five alternating runs each (the chip is power-bound: DESIGN §4.4)
-        ops.scatter_add_rows(dtxt, ge, p.txt_src.to(dev))
-        if n_img and n_nl:
-            dnl = torch.empty((n_nl, H), device=dev, dtype=torch.bfloat16)
-            ops.copy_rows(dx0, dnl, nl_dst, None, n_nl)
-            ops.scatter_add_rows(dnl, ge, nl_src)
-        self._ready("llm.model.embed_tokens.")
+        self._embed_bwd(dx0, p, txt_dst, nl_src if n_img else None, nl_dst if n_img else None, n_nl if n_img else 0)
         if n_img and not getattr(self, "skip_proj_bwd", False):
             full = n_feat == n_buf
             dmedia = (torch.empty if full else torch.zeros)((n_buf, H), device=dev, dtype=torch.bfloat16)   # truncated / pooled-only rows: zero
@@ -949,6 +943,26 @@ class SFTTrainer:
         self._announce_absent_media(n_img)
         self._finish_backward()
         return loss[0]
+
+    def _head_bwd(self, hv: torch.Tensor, head: torch.Tensor, dlog: torch.Tensor, head_name: str) -> torch.Tensor:
+        """lm_head backward: the head's weight gradient and d(hidden) of the rows that have a target (a frozen head overrides it: vila_amd/lora.py)."""
+        return linear_bwd(hv, head, dlog, self.flat.grad(head_name), cm=True, ws=self.ws)
+
+    def _embed_bwd(self, dx0: torch.Tensor, p, txt_dst: torch.Tensor, nl_src, nl_dst, n_nl: int) -> None:
+        """Gradient of the embedding rows: the text tokens and the media blocks' token rows ("\n")."""
+        dev, H = dx0.device, dx0.shape[1]
+        ge = self.flat.grad("llm.model.embed_tokens.weight")
+        dtxt = torch.empty((int(txt_dst.numel()), H), device=dev, dtype=torch.bfloat16)
+        ops.copy_rows(dx0, dtxt, txt_dst, None, int(txt_dst.numel()))
+        # the token ids are uploaded a second time on purpose: the pageable copy holds the host back until the decoder's backward has drained.
+        # With the projector / tower backward enqueued further ahead instead, the step measured 180.9-181.2 against 179.3-180.5 ms on one
+        # box, five alternating runs each (the chip is power-bound: DESIGN §4.4)
+        ops.scatter_add_rows(dtxt, ge, p.txt_src.to(dev))
+        if n_nl:
+            dnl = torch.empty((n_nl, H), device=dev, dtype=torch.bfloat16)
+            ops.copy_rows(dx0, dnl, nl_dst, None, n_nl)
+            ops.scatter_add_rows(dnl, ge, nl_src)
+        self._ready("llm.model.embed_tokens.")
 
     def media_bucket_order(self) -> List[str]:
         """The buckets the projector / tower backward announces, in its order (`_proj_bwd`, `_vit_bwd`; BUCKET_PROJECTOR / BUCKET_VIT_* of the
