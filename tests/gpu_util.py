@@ -938,3 +938,230 @@ def w4_generic_bound(kind: str, K: int, core64, acc64, core_up64=None, acc_up64=
         return bgemm_gateup_bound(core64, w4_absprod(acc64, K), core_up64, w4_absprod(acc_up64, K), K)
     assert kind == "qkv"
     return bgemm_qkv_bound(core64, w4_absprod(acc64, K), K, bias64, cs64, *heads)
+
+
+# ---- the prefill / SFT attention (vila_amd/csrc/attn.hip, attn_bwd.hip, attn_bwd_dma.hip): per-element references and bounds ------------------------
+# (tests/test_attn_bound_cpu.py proves them, tests/test_gpu_attn_elements.py uses them).  Everything is computed in fp64 per sequence and kv head,
+# as attn_ref does; the bounds have train_bound's shape with one more rounding term, 2^-8 of the magnitudes that pass a bf16 operand (P or t).
+# Notation: x = s * scale the scaled score of a (row, key) pair (scale as the C float), M the row's maximum of x over its visible keys, p the exact
+# softmax weights, u = 2^-24.  All "units of u" below are counts of fp32 roundings read from the cited lines.
+ATTN_KT = 64                # keys per K / V tile (attn.hip:26, attn_common.h AttnDma::KT); also the key block of both dK / dV kernels
+ATTN_EXP_OPS = 3            # one rescale of a running sum: v_exp_f32 (1 ulp = 2 u) and the product with it (attn.hip:555, 575, 580; 651-658)
+ATTN_DELTA_DEPTH = 12       # attn_bwd.hip:30-32: a lane adds its 8 products (exact: bf16 x bf16) one after the other, then 4 shuffle levels
+
+
+def _attn_blocks(T: int, Hkv: int, cu):
+    bounds = [0, T] if cu is None else [int(b) for b in cu.tolist()]
+    for a, b in zip(bounds[:-1], bounds[1:]):
+        if b > a:
+            for g in range(Hkv):
+                yield a, b, g
+
+
+def attn_visible(Lq: int, Lk: int, causal: bool, past: int = 0, device="cpu") -> torch.Tensor:
+    """[Lq, Lk] bool: row i sees key j iff j <= past + i (causal), every key otherwise."""
+    if not causal:
+        return torch.ones((Lq, Lk), dtype=torch.bool, device=device)
+    return torch.arange(Lk, device=device)[None, :] <= past + torch.arange(Lq, device=device)[:, None]
+
+
+def _attn_scores(q, k, a, b, g, G, s, causal, past):
+    """One (sequence, kv head) block -> q64 [G, L, D], k64 [Lk, D], vis [L, Lk], x [G, L, Lk] (masked: -inf), A = scale |q| . |k|."""
+    ka, kb = (0, k.shape[0]) if past else (a, b)
+    q64 = q[a:b, g * G:(g + 1) * G].double().transpose(0, 1)
+    k64 = k[ka:kb, g].double()
+    vis = attn_visible(b - a, kb - ka, causal, past, q.device)
+    x = torch.einsum("hqd,kd->hqk", q64, k64) * s
+    A = torch.einsum("hqd,kd->hqk", q64.abs(), k64.abs()) * abs(s)
+    return q64, k64, vis, x.masked_fill(~vis, float("-inf")), A
+
+
+def attn_fwd_bounds(q, k, v, causal: bool, cu=None, scale=None, past: int = 0) -> dict:
+    """q [T, Hq, D], k / v [Tk, Hkv, D] bf16 (Tk = T; with `past`, ONE sequence whose Tk = past + T keys start `past` positions before its
+    queries: the append prefill) -> {"o": (ref, bound, acc) [T, Hq, D], "lse": (ref, bound, acc) [Hq, T], "rnd_o": the rounding part of o's bound}.
+
+    What the kernels do (attn.hip:543-591 and 663-681, the DMA-ring kernel of forms A - D; 160-245 the round-2 kernel, form v1; the same arithmetic):
+    the score is an fp32 MFMA sum of D exact products; per 64-key tile e = v_exp_f32(fma(s, c, -m c)) with c = scale * log2 e and m the running
+    maximum (line 571), l = l alpha + sum e of the UNROUNDED e (573-575), O = O alpha + V^T bf16(e) (580, 585-588, 620); the key-split forms merge
+    two (m, l, O) with a_i = v_exp_f32((m_i - m) c) (650-658); o = bf16(O * (1 / l)) (668, 675), lse = m scale + logf(l) (681).
+
+    The weight a key ends with is e times every later rescale.  In the exponent the chain telescopes to (s - m_final) c, so m's own error drops
+    out of o and of lse, and what remains, as a relative error of the weight in units of u, is
+        r = (D + 2) A                the score: an fp32 sum of D products in any order, scaled (gemm_elem_bound's term)
+          + 5 |x - M|                c's two roundings act on (s - m) c, the fma rounds once at |s c - m c| <= that, and the rescales' exponents
+                                     (m_old - m_new) c round twice each and add up to at most (M - x) (m only grows)
+          + max |x|                  m c is rounded before the fma (line 562): |m c| u with |m| <= the largest |x| of the row
+          + 3 (tiles + 2)            ATTN_EXP_OPS per rescale: one per tile, the merge, and e itself (ce_bounds' "+ 3")
+    l: the weights' own errors, p-weighted (rbar), and an fp32 sum of the row's visible keys in any order plus one product per tile and the merge.
+    O: bf16(e) is off by 2^-8 e (the rounding term 2^-8 sum p |v|); the fp32 part is r per key, the depth of the PV sum (visible keys), a product per
+    tile and the merge; then 1 / l (rbar, l's depth, 5 for a fast reciprocal as silu_f_rel_err counts it) and the product: together
+        acc_o = sum_k p_k r_k |v_kd| + sum_k p_k |v_kd| (rbar + 2 (visible + tiles) + 11).
+    lse = m scale + logf(l): rbar and l's depth as an absolute error, |M| for the product m scale, logf at 2 ulp of |log l|, the sum at |lse|.
+    Floor: v_exp_f32 and the bf16 conversion flush below 2^-126, per key at most FTZ |v|."""
+    T, Hq, D = q.shape
+    Hkv = k.shape[1]
+    G = Hq // Hkv
+    s = f32(D ** -0.5 if scale is None else scale)
+    dev = q.device
+    z = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=dev)
+    ref, rnd, acc, floor = z(T, Hq, D), z(T, Hq, D), z(T, Hq, D), z(T, Hq, D)
+    lref, lacc = z(Hq, T), z(Hq, T)
+    assert not (past and cu is not None)
+    for a, b, g in _attn_blocks(T, Hkv, cu):
+        hs = slice(g * G, (g + 1) * G)
+        _, _, vis, x, A = _attn_scores(q, k, a, b, g, G, s, causal, past)
+        v64 = v[(slice(None) if past else slice(a, b)), g].double()
+        M = x.max(-1, keepdim=True).values
+        e = torch.exp(x - M)
+        l = e.sum(-1, keepdim=True)
+        p = e / l
+        nvis = vis.sum(-1).double()                                     # [L]
+        tiles = torch.ceil(nvis / ATTN_KT)
+        r = (D + 2) * A + 5.0 * torch.where(vis, M - x, torch.zeros_like(x)) + torch.where(vis, x.abs(), torch.zeros_like(x)).max(-1, keepdim=True).values \
+            + ATTN_EXP_OPS * (tiles[None, :, None] + 2.0)
+        rbar = (p * r).sum(-1)                                          # [G, L]
+        depth = nvis + tiles
+        av = v64.abs()
+        S1 = torch.einsum("hqk,kd->hqd", p, av)
+        ref[a:b, hs] = torch.einsum("hqk,kd->hqd", p, v64).transpose(0, 1)
+        rnd[a:b, hs] = S1.transpose(0, 1)
+        acc[a:b, hs] = (torch.einsum("hqk,kd->hqd", p * r, av) + S1 * (rbar + 2.0 * depth[None, :] + 11.0)[..., None]).transpose(0, 1)
+        floor[a:b, hs] = FTZ * (1.0 + av.sum(0))
+        lse = (M + l.log())[..., 0]
+        lref[hs, a:b] = lse
+        lacc[hs, a:b] = rbar + depth[None, :] + 3.0 + M[..., 0].abs() + 4.0 * l.log()[..., 0].abs() + lse.abs() + 2.0
+    rnd_o = BF16_U * ref.abs() + BF16_U * rnd
+    bound = BF16_U * ref.abs() + (1.0 + BF16_U) * (BF16_U * rnd + FP32_U * acc) + floor
+    return {"o": (ref, bound, acc), "lse": (lref, train_bound(lref, lacc, roundings=0), lacc), "rnd_o": rnd_o}
+
+
+def attn_bwd_bounds(q, k, v, do, o, lse, causal: bool, cu=None, scale=None, o_err=None, lse_err=None) -> dict:
+    """The backward operator on ITS inputs: o [T, Hq, D] and lse [Hq, T] are what it consumes (ops.attn_bwd) -> {"delta" / "dq" / "dk" / "dv":
+    (ref, bound, acc), "rnd_dq" / "rnd_dk" / "rnd_dv": the rounding parts}.  References in fp64:
+        P = exp(x - lse),  delta = sum_d o do,  dP = do . V^T,  t = P (dP - delta) scale,  dv = P^T do,  dq = t K,  dk = t^T Q
+    (dk and dv summed over the query rows and the G heads of the group).  The kernels (attn_bwd_dma.hip:174-191, 398-402, 446-448; attn_bwd.hip:19-34,
+    159-179, 366-379 and the pack2bf stores) round P to bf16 before dV, t to bf16 before dQ and dK, and every output once.
+    delta (attn_bwd.hip:30-33): ATTN_DELTA_DEPTH u sum_d |o do|, an fp32 output.
+    P = v_exp_f32(fma(s, c, -lse log2 e)): relative error in units of u
+        rP = (D + 1) A + 3 |x| + 2 |lse| + |x - lse| + 2
+    (the score; c's two roundings and, without fma contraction in attn_bwd.hip:169, the product's; lse * LOG2E: the constant and the product; the
+    subtraction; the exponential).  dP is an fp32 sum of D products, (D + 1) u B with B = |do| . |v|^T; dP - delta rounds once and carries delta's
+    error; two products follow.  So t is off, before its bf16 rounding, by the CARRIED error
+        dt = |t| (rP + 3) + P scale ((D + 1) B + ATTN_DELTA_DEPTH sum_d |o do|)      (units of u)
+    whose second part does not shrink where dP - delta cancels: with P near 1 (large logits) t vanishes and dt does not.
+        dv: 2^-8 |ref| + (1 + 2^-8) [2^-8 sum P |do| + u (sum P rP |do| + (n + 2) sum P |do|)]
+        dq: 2^-8 |ref| + (1 + 2^-8) [2^-8 sum_k |t| |K| + u (sum_k dt |K| + (visible + 1) sum_k |t| |K|)]
+        dk: as dq over the n = G * (rows that see the key) terms, + 2 for the two halves that meet in LDS (attn_bwd.hip:413-418, attn_bwd_dma.hip:433-438).
+    o_err / lse_err (end to end: o and lse come from the project's forward, the reference uses the exact ones): the forward's own bounds, carried
+    through delta (sum_d o_err |do|) and P (lse_err, relative)."""
+    T, Hq, D = q.shape
+    Hkv = k.shape[1]
+    G = Hq // Hkv
+    s = f32(D ** -0.5 if scale is None else scale)
+    dev = q.device
+    z = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=dev)
+    out = {n: [z(T, h, D) for _ in range(4)] for n, h in (("dq", Hq), ("dk", Hkv), ("dv", Hkv))}       # ref, rnd, acc, floor
+    dref, dacc = z(Hq, T), z(Hq, T)
+    for a, b, g in _attn_blocks(T, Hkv, cu):
+        hs = slice(g * G, (g + 1) * G)
+        q64, k64, vis, x, A = _attn_scores(q, k, a, b, g, G, s, causal, 0)
+        v64 = v[a:b, g].double()
+        do64 = do[a:b, hs].double().transpose(0, 1)
+        o64 = o[a:b, hs].double().transpose(0, 1)
+        lse64 = lse[hs, a:b].double()[..., None]
+        P = torch.exp(x - lse64)                                        # masked: exp(-inf) = 0
+        x0 = torch.where(vis, x, torch.zeros_like(x))
+        delta = (o64 * do64).sum(-1)
+        Dd = ATTN_DELTA_DEPTH * (o64 * do64).abs().sum(-1)
+        dref[hs, a:b], dacc[hs, a:b] = delta, Dd
+        if o_err is not None:
+            Dd = Dd + (o_err[a:b, hs].double().transpose(0, 1) * do64.abs()).sum(-1) / FP32_U
+        diff = torch.einsum("hqd,kd->hqk", do64, v64) - delta[..., None]
+        B = torch.einsum("hqd,kd->hqk", do64.abs(), v64.abs())
+        t = P * diff * s
+        rP = (D + 1) * A + 3.0 * x0.abs() + 2.0 * lse64.abs() + torch.where(vis, (x0 - lse64).abs(), torch.zeros_like(x0)) + 2.0
+        if lse_err is not None:
+            rP = rP + lse_err[hs, a:b].double()[..., None] / FP32_U
+        dt = t.abs() * (rP + 3.0) + P * abs(s) * ((D + 1) * B + Dd[..., None])
+        nvis = vis.sum(-1).double()
+        nq = G * vis.sum(0).double()
+        dmax = 1.0 + abs(s) * float(diff.abs().max())
+        ka, qa, da = k64.abs(), q64.abs(), do64.abs()
+        ref_, rnd_, acc_, fl_ = out["dq"]
+        Tq = torch.einsum("hqk,kd->hqd", t.abs(), ka)
+        ref_[a:b, hs] = torch.einsum("hqk,kd->hqd", t, k64).transpose(0, 1)
+        rnd_[a:b, hs] = Tq.transpose(0, 1)
+        acc_[a:b, hs] = (torch.einsum("hqk,kd->hqd", dt, ka) + (nvis + 1.0)[None, :, None] * Tq).transpose(0, 1)
+        fl_[a:b, hs] = FTZ * dmax * (1.0 + ka.sum(0))
+        ref_, rnd_, acc_, fl_ = out["dk"]
+        Tk = torch.einsum("hqk,hqd->kd", t.abs(), qa)
+        ref_[a:b, g] = torch.einsum("hqk,hqd->kd", t, q64)
+        rnd_[a:b, g] = Tk
+        acc_[a:b, g] = torch.einsum("hqk,hqd->kd", dt, qa) + (nq + 2.0)[:, None] * Tk
+        fl_[a:b, g] = FTZ * dmax * (1.0 + qa.sum((0, 1)))
+        ref_, rnd_, acc_, fl_ = out["dv"]
+        Tv = torch.einsum("hqk,hqd->kd", P, da)
+        ref_[a:b, g] = torch.einsum("hqk,hqd->kd", P, do64)
+        rnd_[a:b, g] = Tv
+        acc_[a:b, g] = torch.einsum("hqk,hqd->kd", P * rP, da) + (nq + 2.0)[:, None] * Tv
+        fl_[a:b, g] = FTZ * (1.0 + da.sum((0, 1)))
+    res = {"delta": (dref, train_bound(dref, dacc, roundings=0), dacc)}
+    for n, (ref_, rnd_, acc_, fl_) in out.items():
+        res[n] = (ref_, BF16_U * ref_.abs() + (1.0 + BF16_U) * (BF16_U * rnd_ + FP32_U * acc_) + fl_, acc_)
+        res["rnd_" + n] = BF16_U * ref_.abs() + BF16_U * rnd_
+    return res
+
+
+def plant_pairs(q: torch.Tensor, k: torch.Tensor, pairs, causal: bool, cu=None, scale=None, weight: float = 0.5, past: int = 0) -> torch.Tensor:
+    """Planted pairs for prefill shapes, in place: for every (row, key) of `pairs` (token indices of q and of k; the rows distinct, the keys distinct,
+    each pair inside one sequence and visible) and every kv head h, k[key, h] = bf16(alpha q[row, target head of h]) (probe_targets) with alpha
+    such that, by the fp64 softmax over the row's visible keys, the planted key carries `weight` of the target head's row: alpha |q|^2 scale =
+    log(weight / (1 - weight) * sum of the other keys' exp(x)).  At about 1/2 the pair carries O(|v|) in o, O(|do|) in dv and, unlike a weight of
+    about 1, where t = P (dP - delta) vanishes, O(1) in dq and dk.  Two passes: the second sees every other planted key in place.
+    -> the weights reached [pairs, Hkv] fp64, which the caller asserts to lie in 0.3 .. 0.7."""
+    T, Hq, D = q.shape
+    Hkv = k.shape[1]
+    G = Hq // Hkv
+    s = f32(D ** -0.5 if scale is None else scale)
+    bounds = [0, T] if cu is None else [int(b) for b in cu.tolist()]
+    pairs = [(int(r), int(c)) for r, c in pairs]
+    assert len({r for r, _ in pairs}) == len(pairs) == len({c for _, c in pairs})
+
+    def span(r, c):
+        if past:
+            assert c <= past + r, (r, c)
+            return 0, (past + r + 1 if causal else k.shape[0]), c
+        a, b = next((a, b) for a, b in zip(bounds[:-1], bounds[1:]) if a <= r < b)
+        assert a <= c < b and (not causal or c <= r), (r, c)
+        return a, (r + 1 if causal else b), c
+
+    def scores(r, c, h):
+        lo, hi, _ = span(r, c)
+        return torch.mv(k[lo:hi, h].double(), q[r, probe_targets(Hkv, G)[h]].double()) * s, c - lo
+
+    got = torch.zeros((len(pairs), Hkv), dtype=torch.float64)
+    for step in range(3):
+        for i, (r, c) in enumerate(pairs):
+            for h, tgt in enumerate(probe_targets(Hkv, G)):
+                x, j = scores(r, c, h)
+                if step == 2:
+                    got[i, h] = float(torch.softmax(x, 0)[j])
+                    continue
+                rest = torch.cat((x[:j], x[j + 1:]))
+                assert rest.numel() > 0, f"row {r} sees no key but its own: its weight is 1 whatever alpha"
+                want = float(torch.logsumexp(rest, 0)) + float(torch.log(torch.tensor(weight / (1.0 - weight), dtype=torch.float64)))
+                n2 = float(q[r, tgt].double().pow(2).sum()) * s
+                k[c, h] = (want / n2 * q[r, tgt].float()).to(torch.bfloat16)
+    return got
+
+
+def framed_thd(T: int, H: int, D: int, ld_pad: int = 8, guard_rows: int = 3, dtype=torch.bfloat16, device="cuda"):
+    """-> (view [T, H, D], check): framed_out's [T, H * D] view with the heads split off (strides ld, D, 1)."""
+    view, check = framed_out(T, H * D, ld_pad, guard_rows, dtype=dtype, device=device)
+    return view.unflatten(1, (H, D)), check
+
+
+def framed_thd_operand(t: torch.Tensor, ld_pad: int = 8, guard_rows: int = 3) -> torch.Tensor:
+    """t [T, H, D] -> the same values as a [T, H, D] view of framed_operand's NaN-padded buffer."""
+    T, H, D = t.shape
+    return framed_operand(t.reshape(T, H * D), ld_pad, guard_rows).unflatten(1, (H, D))
