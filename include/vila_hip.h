@@ -872,6 +872,67 @@ int vila_verify_commit(const VilaPenalties* pen /*nullable*/, const VilaConstrai
 int vila_logprobs_seq_f32(const float* logits, int64_t ld, int n, int vocab, const int64_t* token /*[n] device*/, int top_n /*0..20*/,
                           const int32_t* rec /*[n] device*/, const VilaLogprobOut* out, void* workspace, vila_stream_t stream);
 
+/* LoRA adapters served unmerged: a per-row adapter in the batched step (vila_amd/csrc/lora_decode.hip, decode_batch.hip).
+ * A bank holds `capacity` (1 .. 32) slots of rank r (16, 32, 48 or 64; an adapter of lower rank is zero-padded) in buffers whose addresses never
+ * change.  row_adapter [n] int32 (device) names each row's slot, or -1 for none (a value outside 0 .. capacity - 1 counts as -1); it is read at run
+ * time, so ONE captured hipGraph serves every mix of rows and every load or unload.  Per layer and per stack of projections that share an input
+ * (q|k|v: Rs = 3 r rows, N = (q + 2 kv) * head_dim columns; o: r, hidden; gate|up: 2 r, 2 * inter; down: r, hidden):
+ *   A  [capacity][Rs][K] bf16          the members' lora_A stacked, rows contiguous along K
+ *   B  [capacity][r / 8][N][8] bf16    lora_B of the members side by side over the stack's columns, chunk-major: element (c, col, e) = B[col][8 c + e]
+ * and scale [capacity] fp32 = alpha / r_adapter.  A projection not targeted has zero B; zero rows and columns contribute exact zeros.
+ * shrink: T[i][0 : Rs) = scale[a] * (x_i . A_a^T), a = row_adapter[i]; x [n <= 16][K] bf16 (ldx % 8 == 0, 16-byte aligned), K % 64 == 0, Rs % 16 == 0; T fp32.
+ * expand: D[i][col] = sum_j T[i][seg(col) + j] * B_a[col][j], j = 0 .. r - 1 in that order (fmaf); seg = 0 for col < c1, r for col < c2, else 2 r
+ *   (one member: c1 = c2 = N; two: c2 = N); fp32 out.
+ * Both: a slot that no row names is not read; a row without an adapter gets +0.0; row i's T and D depend on x_i (T_i) and its slot only, bit for bit,
+ * whatever n and the other rows; fixed summation order, no atomics; nothing outside [n][Rs] / [n][N] is written.  Refusals (-1) come before any launch. */
+int vila_lora_shrink_bf16(const void* x, int64_t ldx, int n, const void* A, int64_t slot_stride /*elements*/, const float* scale,
+                          const int32_t* row_adapter, int capacity, float* T, int64_t ldt, int Rs, int K, vila_stream_t stream);
+int vila_lora_expand_f32(const float* T, int64_t ldt, int n, const void* B, int64_t slot_stride /*elements*/, const int32_t* row_adapter, int capacity,
+                         float* D, int64_t ldd, int N, int r, int c1, int c2, vila_stream_t stream);
+/* vila_gemm_batch_bf16 (W2 == NULL) / its gate/up form / vila_qkv_batch_bf16 with an fp32 addend [n][N] (gate/up: [n][2 N], gate | up; row stride lda)
+ * added to the fp32 sum in front of the bias and the first rounding: so in front of silu (gate/up) and of RoPE and the cache append (q|k|v).  A row
+ * with row_adapter[m] < 0 skips the add (it is NOT + 0.0: a sum of -0.0 keeps its sign) and has the bits of the entries without addend; row_adapter
+ * NULL: every row adds.  addend NULL launches the very kernels of those entries. */
+int vila_gemm_batch_lora_bf16(const void* x, int64_t ldx, int n, const void* W, const void* bias, const void* residual, int64_t ldr, void* y, int64_t ldy,
+                              float* y_f32, int64_t ldf, int N, int K, const float* addend, int64_t lda, const int32_t* row_adapter, vila_stream_t stream);
+int vila_gateup_batch_lora_bf16(const void* x, int64_t ldx, int n, const void* Wgate, const void* Wup, void* y, int64_t ldy, int N, int K,
+                                const float* addend, int64_t lda, const int32_t* row_adapter, vila_stream_t stream);
+int vila_qkv_batch_lora_bf16(const void* x, int64_t ldx, int n, const void* Wqkv, const void* bias, void* q_out, int64_t ldq, void* kcache, void* vcache,
+                             int64_t slot_stride, const int32_t* pos, const float* rope_cs, int q_heads, int kv_heads, int head_dim, int max_ctx, int K,
+                             const float* addend, int64_t lda, const int32_t* row_adapter, vila_stream_t stream);
+typedef struct {
+    const void *a_qkv, *b_qkv, *a_o, *b_o, *a_gateup, *b_gateup, *a_down, *b_down;   /* slot 0 of each buffer (layouts above) */
+} VilaLoraBankLayer;
+typedef struct {
+    const VilaLoraBankLayer* layers;   /* [n_layers] host */
+    const float*   scale;              /* [capacity] device */
+    const int32_t* row_adapter;        /* [n] device */
+    int32_t        capacity, r;
+} VilaLoraBank;
+/* The batched step with per-row adapters: in front of each of a layer's four projections, shrink and expand on the projection's own input (eight
+ * small launches per layer), the result added in the GEMM's epilogue: a row computes round(acc + D + bias) with T and D in fp32.  lm_head is never
+ * adapted.  ONE entry: sp, pen and con NULL = greedy / no penalties / no automata, any_k != 0 needs sp; logprobs run behind it as behind every step.
+ * qlayers and prefix must be NULL: the step has no int4 and no shared-prefix form (-1), nor have the verify and solo steps an adapter form.  A row
+ * with -1 keeps the bits of vila_llm_decode_step_batch. */
+size_t vila_llm_decode_batch_lora_workspace_bytes(const VilaLlmShape* s, int n, int max_ctx, int r);
+int vila_llm_decode_step_batch_lora(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers /*must be NULL*/, const VilaKvCache* cache,
+                                    const VilaDecodeBatch* st, const VilaDecodePrefix* prefix /*must be NULL*/, const VilaLoraBank* bank, void* workspace,
+                                    size_t workspace_bytes, const VilaBatchSampling* sp /*nullable*/, const VilaPenalties* pen /*nullable*/,
+                                    const VilaConstraints* con /*nullable*/, int any_k, vila_stream_t stream);
+/* The prefill with every packed sequence under ONE adapter, in the trainer's orientation (vila_amd/lora.py): per layer and stack the stacked
+ * A [Rs][K] and the members' Bt side by side, [r][N] over the stack's N output columns (a projection that is not adapted: zero columns), rank r
+ * (16, 32, 48 or 64), scale alpha / r_adapter.  Per projection lora_down on the stack's input, lora_up into the base GEMM's residual (t and u rounded
+ * to bf16, the trainer's forward dataflow), RoPE and the norms as launches of their own, gate and up as two GEMMs and silu_mul; no last-row pruning.
+ * The other arguments are vila_llm_prefill's. */
+typedef struct {
+    const void *a_qkv, *bt_qkv, *a_o, *bt_o, *a_gateup, *bt_gateup, *a_down, *bt_down;
+} VilaLoraLayer;
+size_t vila_llm_prefill_lora_workspace_bytes(const VilaLlmShape* s, int T, int r);
+int vila_llm_prefill_lora(const VilaLlmWeights* w, const VilaLoraLayer* lora /*[n_layers] host*/, int r, float scale, const void* embeds,
+                          const int32_t* positions, const int32_t* cu_seqlens, int n_seq, int T, int max_seqlen, const int32_t* seq_of_tok,
+                          const VilaKvCache* cache, const int32_t* last_rows, int n_last, float* last_logits, float* all_logits, void* final_hidden,
+                          void* workspace, size_t workspace_bytes, vila_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

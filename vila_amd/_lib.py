@@ -93,6 +93,18 @@ class VilaLogprobOut(C.Structure):
     _fields_ = [("token_logprob", c_void_p), ("top_logprob", c_void_p), ("top_id", c_void_p), ("max_rec", c_int)]
 
 
+class VilaLoraBankLayer(C.Structure):
+    _fields_ = [(n, c_void_p) for n in ("a_qkv", "b_qkv", "a_o", "b_o", "a_gateup", "b_gateup", "a_down", "b_down")]
+
+
+class VilaLoraBank(C.Structure):
+    _fields_ = [("layers", C.POINTER(VilaLoraBankLayer)), ("scale", c_void_p), ("row_adapter", c_void_p), ("capacity", C.c_int32), ("r", C.c_int32)]
+
+
+class VilaLoraLayer(C.Structure):
+    _fields_ = [(n, c_void_p) for n in ("a_qkv", "bt_qkv", "a_o", "bt_o", "a_gateup", "bt_gateup", "a_down", "bt_down")]
+
+
 class VilaDecodeState(C.Structure):
     _fields_ = [("pos", c_void_p), ("token", c_void_p), ("out_ids", c_void_p), ("n_out", c_void_p),
                 ("max_out", c_int), ("logits", c_void_p)]
@@ -355,6 +367,21 @@ PROTOTYPES = {
                                   c_size_t, c_void_p]),
     "vila_lora_wgrad_bf16": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_float, c_int, c_void_p, c_size_t,
                                      c_void_p]),
+    "vila_lora_shrink_bf16": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_int, c_void_p]),
+    "vila_lora_expand_f32": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p]),
+    "vila_gemm_batch_lora_bf16": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int,
+                                          c_void_p, c_int64, c_void_p, c_void_p]),
+    "vila_gateup_batch_lora_bf16": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_int64, c_void_p,
+                                            c_void_p]),
+    "vila_qkv_batch_lora_bf16": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
+                                         c_int, c_int, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p]),
+    "vila_llm_decode_batch_lora_workspace_bytes": (c_size_t, [C.POINTER(VilaLlmShape), c_int, c_int, c_int]),
+    "vila_llm_decode_step_batch_lora": (c_int, [C.POINTER(VilaLlmWeights), C.POINTER(VilaLlmLayerW4), C.POINTER(VilaKvCache), C.POINTER(VilaDecodeBatch),
+                                                C.POINTER(VilaDecodePrefix), C.POINTER(VilaLoraBank), c_void_p, c_size_t, C.POINTER(VilaBatchSampling),
+                                                C.POINTER(VilaPenalties), C.POINTER(VilaConstraints), c_int, c_void_p]),
+    "vila_llm_prefill_lora_workspace_bytes": (c_size_t, [C.POINTER(VilaLlmShape), c_int, c_int]),
+    "vila_llm_prefill_lora": (c_int, [C.POINTER(VilaLlmWeights), C.POINTER(VilaLoraLayer), c_int, c_float, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                      c_void_p, C.POINTER(VilaKvCache), c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
 _lib: Optional[C.CDLL] = None

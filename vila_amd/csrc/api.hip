@@ -530,6 +530,112 @@ extern "C" int vila_llm_prefill_w4(const VilaLlmWeights* w, const VilaLlmLayerW4
                             all_logits, final_hidden, layer_hidden, workspace, workspace_bytes, stream);
 }
 
+// The prefill under ONE LoRA adapter (a request admitted under an adapter of the serving bank): llm_prefill_impl's sibling from launches that exist.  Per
+// projection the trainer's forward dataflow (vila_amd/lora.py): t = lora_down(stack input, A), u = lora_up(t slice, Bt, scale, res = the linear's
+// residual), y = gemm(input, W, bias, residual = u).  The GEMMs take no follow-up along, so RoPE + cache scatter and the norms are their own launches;
+// gate and up are two GEMMs and silu_mul; every row runs every layer.
+extern "C" size_t vila_llm_prefill_lora_workspace_bytes(const VilaLlmShape* s, int T, int r) {
+    const size_t F = s->inter, QKV = (size_t)(s->q_heads + 2 * s->kv_heads) * s->head_dim, wide = QKV > F ? QKV : F;
+    const size_t down = vila_lora_down_workspace_bytes(T, (int)(F > (size_t)s->hidden ? F : (size_t)s->hidden), 3 * r);
+    return vila_llm_prefill_workspace_bytes(s, T) + align_up((size_t)T * 3 * r * 2, 256) + align_up((size_t)T * wide * 2, 256) + align_up((size_t)T * F * 2, 256) +
+           align_up(down, 256) + 1024;
+}
+extern "C" int vila_llm_prefill_lora(const VilaLlmWeights* w, const VilaLoraLayer* lora, int r, float scale, const void* embeds, const int32_t* positions,
+                                     const int32_t* cu_seqlens, int n_seq, int T, int max_seqlen, const int32_t* seq_of_tok, const VilaKvCache* cache,
+                                     const int32_t* last_rows, int n_last, float* last_logits, float* all_logits, void* final_hidden, void* workspace,
+                                     size_t workspace_bytes, vila_stream_t stream) {
+    const char* fn = "llm_prefill_lora";
+    VILA_REQUIRE(w != nullptr && lora != nullptr && embeds != nullptr && positions != nullptr && workspace != nullptr, "%s: NULL argument", fn);
+    const VilaLlmShape& sh = w->shape;
+    hipStream_t s = S(stream);
+    VILA_REQUIRE(T > 0 && n_seq > 0, "%s: empty input", fn);
+    VILA_REQUIRE(r == 16 || r == 32 || r == 48 || r == 64, "%s: rank 16, 32, 48 or 64 (got %d)", fn, r);
+    VILA_REQUIRE(sh.q_heads % sh.kv_heads == 0, "llm: q heads must be a multiple of kv heads");
+    VILA_REQUIRE(cu_seqlens != nullptr || n_seq == 1, "%s: n_seq > 1 needs cu_seqlens", fn);
+    VILA_REQUIRE(workspace_bytes >= vila_llm_prefill_lora_workspace_bytes(&sh, T, r), "%s: workspace too small", fn);
+    const int H = sh.hidden, F = sh.inter, hd = sh.head_dim, QS = sh.q_heads * hd, KS = sh.kv_heads * hd, QKV = QS + 2 * KS;
+    VILA_REQUIRE(QS == H, "llm: q_heads*head_dim (%d) must equal hidden (%d) for the in-place attention buffer", QS, H);
+    VILA_REQUIRE(H % 8 == 0 && F % 8 == 0 && KS % 8 == 0, "%s: hidden, intermediate and kv widths must be multiples of 8", fn);
+    Arena a(workspace, workspace_bytes);
+    bf16_t* x = a.take<bf16_t>((size_t)T * H);
+    bf16_t* h = a.take<bf16_t>((size_t)T * H);
+    bf16_t* qkv = a.take<bf16_t>((size_t)T * QKV);
+    bf16_t* act = a.take<bf16_t>((size_t)T * F);
+    float* cs = a.take<float>((size_t)T * hd / 2);
+    float* sn = a.take<float>((size_t)T * hd / 2);
+    bf16_t* lastbuf = a.take<bf16_t>((size_t)(T > 8 ? T : 8) * H);
+    const size_t skws_bytes = (size_t)8 * T * H * 4;
+    float* skws = a.take<float>(skws_bytes / 4);
+    bf16_t* t = a.take<bf16_t>((size_t)T * 3 * r);                     // x . A^T of the current stack
+    bf16_t* u = a.take<bf16_t>((size_t)T * (QKV > F ? QKV : F));         // scale * t . Bt (+ the residual): the base GEMM's residual
+    bf16_t* gate = a.take<bf16_t>((size_t)T * F);
+    const size_t dws_bytes = vila_lora_down_workspace_bytes(T, F > H ? F : H, 3 * r);
+    char* dws = a.take<char>(dws_bytes);
+    VILA_REQUIRE(a.ok(), "%s: workspace arena overflow", fn);
+    if (cache != nullptr) VILA_REQUIRE(max_seqlen <= cache->max_ctx, "%s: sequence (%d) longer than the KV cache (%d)", fn, max_seqlen, cache->max_ctx);
+    auto down = [&](const bf16_t* in, int K, const void* A, int Rs) {
+        return vila_lora_down_bf16(in, K, A, K, t, 3 * r, T, K, Rs, 1.0f, dws, dws_bytes, stream);
+    };
+    // member j of the stack: columns [c0, c0 + N) of the stack's Ntot; res (nullable, row stride H) is the linear's residual
+    auto up = [&](int j, const void* Bt, int Ntot, int c0, int N, const bf16_t* res, bf16_t* out, int ldo) {
+        return vila_lora_up_bf16(t + j * r, 3 * r, B(Bt) + c0, Ntot, res, H, out, ldo, T, N, r, scale, nullptr, 0, stream);
+    };
+
+    VILA_HIP(hipMemcpyAsync(x, embeds, (size_t)T * H * 2, hipMemcpyDeviceToDevice, s));
+    VILA_TRY(launch_rope_table(positions, cs, sn, T, hd, sh.rope_theta, s));
+    for (int l = 0; l < sh.n_layers; ++l) {
+        const VilaLlmLayer& L = w->layers[l];
+        const VilaLoraLayer& A = lora[l];
+        VILA_REQUIRE(A.a_qkv && A.bt_qkv && A.a_o && A.bt_o && A.a_gateup && A.bt_gateup && A.a_down && A.bt_down, "%s: adapter layer %d has a NULL buffer", fn, l);
+        VILA_REQUIRE(qkv_fused(L.wq, L.wk, L.wv, L.bq, L.bk, L.bv, QS, KS, H), "%s: q/k/v projection weights and biases must be views of one fused buffer", fn);
+        VILA_TRY(launch_rmsnorm(x, B(L.ln1_w), h, T, H, sh.rms_eps, s));
+        bf16_t* kc = nullptr; bf16_t* vc = nullptr; int max_ctx = 0;
+        if (cache != nullptr) {
+            const size_t per_layer = (size_t)cache->n_slots * sh.kv_heads * cache->max_ctx * hd;
+            kc = B(cache->k) + l * per_layer; vc = B(cache->v) + l * per_layer; max_ctx = cache->max_ctx;
+        }
+        VILA_TRY(down(h, H, A.a_qkv, 3 * r));
+        VILA_TRY(up(0, A.bt_qkv, QKV, 0, QS, nullptr, u, QKV));
+        VILA_TRY(up(1, A.bt_qkv, QKV, QS, KS, nullptr, u + QS, QKV));
+        VILA_TRY(up(2, A.bt_qkv, QKV, QS + KS, KS, nullptr, u + QS + KS, QKV));
+        VILA_TRY(gemm(h, H, L.wq, H, L.bq, u, QKV, qkv, QKV, T, QKV, H, EPI_NONE, s));
+        VILA_TRY(launch_rope_kv(qkv, cs, sn, positions, seq_of_tok, kc, vc, T, sh.q_heads, sh.kv_heads, hd, max_ctx, s));
+        AttnArgs at{};
+        at.q = qkv; at.k = qkv + QS; at.v = qkv + QS + KS; at.o = h;
+        at.q_tok_stride = at.k_tok_stride = at.v_tok_stride = QKV; at.o_tok_stride = QS;
+        at.q_head_stride = at.k_head_stride = at.v_head_stride = at.o_head_stride = hd;
+        at.cu_seqlens = cu_seqlens; at.n_seq = n_seq; at.total_tokens = T; at.max_seqlen = (cu_seqlens ? max_seqlen : T);
+        at.n_q_heads = sh.q_heads; at.n_kv_heads = sh.kv_heads; at.head_dim = hd; at.causal = 1;
+        at.scale = 1.0f / sqrtf((float)hd); at.lse = nullptr;
+        VILA_TRY(launch_attn_fwd(at, s));
+        VILA_TRY(down(h, QS, A.a_o, r));                                                          // x += o_proj(attn): u = x + s t Bt, x = gemm + u
+        VILA_TRY(up(0, A.bt_o, H, 0, H, x, u, H));
+        VILA_TRY(gemm(h, QS, L.wo, QS, nullptr, u, H, x, H, T, H, QS, EPI_NONE, s, nullptr, 0, skws, skws_bytes));
+        VILA_TRY(launch_rmsnorm(x, B(L.ln2_w), h, T, H, sh.rms_eps, s));
+        VILA_TRY(down(h, H, A.a_gateup, 2 * r));
+        VILA_TRY(up(0, A.bt_gateup, 2 * F, 0, F, nullptr, u, F));
+        VILA_TRY(gemm(h, H, L.w_gate, H, nullptr, u, F, gate, F, T, F, H, EPI_NONE, s, nullptr, 0, skws, skws_bytes));
+        VILA_TRY(up(1, A.bt_gateup, 2 * F, F, F, nullptr, u, F));
+        VILA_TRY(gemm(h, H, L.w_up, H, nullptr, u, F, u, F, T, F, H, EPI_NONE, s, nullptr, 0, skws, skws_bytes));
+        VILA_TRY(launch_silu_mul_fwd(gate, u, act, (int64_t)T * F, s));
+        VILA_TRY(down(act, F, A.a_down, r));
+        VILA_TRY(up(0, A.bt_down, H, 0, H, x, u, H));
+        VILA_TRY(gemm(act, F, L.w_down, F, nullptr, u, H, x, H, T, H, F, EPI_NONE, s, nullptr, 0, skws, skws_bytes));
+    }
+    if (final_hidden != nullptr || all_logits != nullptr) {
+        bf16_t* fh = final_hidden ? B(final_hidden) : h;
+        VILA_TRY(launch_rmsnorm(x, B(w->norm_w), fh, T, H, sh.rms_eps, s));
+        if (all_logits) VILA_TRY(gemm(fh, H, w->lm_head, H, nullptr, nullptr, 0, all_logits, sh.vocab, T, sh.vocab, H, EPI_NONE, s, nullptr, 1));
+    }
+    if (n_last > 0 && last_logits != nullptr) {
+        VILA_REQUIRE(last_rows != nullptr, "%s: last_rows is NULL", fn);
+        VILA_TRY(launch_copy_rows(x, lastbuf, last_rows, nullptr, n_last, H, s));
+        VILA_TRY(launch_rmsnorm(lastbuf, B(w->norm_w), lastbuf, n_last, H, sh.rms_eps, s));
+        VILA_TRY(gemm(lastbuf, H, w->lm_head, H, nullptr, nullptr, 0, last_logits, sh.vocab, n_last, sh.vocab, H, EPI_NONE, s, nullptr, 1));
+    }
+    return 0;
+}
+
 // The append prefill: T tokens of ONE sequence continue slot `slot` of the cache, which holds `past` positions.
 static int llm_prefill_append(const VilaLlmWeights* w, const VilaLlmLayerW4* ql, const void* embeds, int T, int past, int slot, const VilaKvCache* cache,
                               const int32_t* last_rows, int n_last, float* last_logits, void* final_hidden, void* layer_hidden, void* workspace,
@@ -873,7 +979,7 @@ static int blayer_tables(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers,
 static int decode_step_batch_impl(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers, const VilaKvCache* cache, const VilaDecodeBatch* st,
                                   void* workspace, size_t workspace_bytes, const VilaBatchSampling* sp, vila_stream_t stream,
                                   const VilaDecodePrefix* px = nullptr, const Penalties* pen = nullptr, float* pen_out = nullptr,
-                                  const Constraints* con = nullptr, bool any_k = false) {
+                                  const Constraints* con = nullptr, bool any_k = false, const BLora* lora = nullptr) {
     const char* fn = qlayers != nullptr ? "llm_decode_batch_w4" : "llm_decode_batch";
     VILA_REQUIRE(w != nullptr && cache != nullptr && st != nullptr && workspace != nullptr, "%s: NULL argument", fn);
     BTables t{};
@@ -884,7 +990,7 @@ static int decode_step_batch_impl(const VilaLlmWeights* w, const VilaLlmLayerW4*
     const BPrefix bp = px != nullptr ? BPrefix{px->prefix_slot, px->shared_len, px->uses} : BPrefix{};
     return bdecode_step(t.m, t.layers.data(), B(cache->k), B(cache->v), cache->max_ctx, cache->n_slots, st->n, st->pos, st->token, st->out_ids, st->n_out,
                         st->max_out, st->logits, workspace, workspace_bytes, S(stream), qlayers != nullptr ? t.ql.data() : nullptr, sw.sp, sw.ws,
-                        px != nullptr ? &bp : nullptr, pen, pen_out, con, any_k);
+                        px != nullptr ? &bp : nullptr, pen, pen_out, con, any_k, lora);
 }
 // the four steps of a prefix session and their workspace sizes (two sizes, greedy and sampled, as above)
 static size_t decode_batch_prefix_ws(const VilaLlmShape* s, int n, int max_ctx, bool sample) {
@@ -1002,6 +1108,50 @@ extern "C" int vila_llm_decode_step_batch_any_k(const VilaLlmWeights* w, const V
     const Constraints Cn = con != nullptr ? Constraints{con->state, con->cls, con->ld_cls, con->next, con->ld_next, con->n_classes} : Constraints{};
     return decode_step_batch_impl(w, qlayers, cache, st, workspace, head, sp, stream, prefix, pen != nullptr ? &P : nullptr, (float*)((char*)workspace + head),
                                   con != nullptr ? &Cn : nullptr, true);
+}
+// The batched step with per-row LoRA adapters (lora_decode.hip): sp, pen and con nullable, any_k an option of sp — greedy / sampled, with or without
+// penalties and automata in one entry.  One workspace size: the penalised step's (processed rows behind the head, unused without pen and con), and behind
+// it the adapters' fp32 scratch T [n][3 r] and D [n][max(q + 2 kv, 2 inter)].  No int4 and no shared-prefix form.
+static size_t decode_batch_lora_head(const VilaLlmShape* s, int n, int max_ctx) {
+    return align_up(vila_llm_decode_batch_penalized_workspace_bytes(s, n, max_ctx, 0), 256);
+}
+extern "C" size_t vila_llm_decode_batch_lora_workspace_bytes(const VilaLlmShape* s, int n, int max_ctx, int r) {
+    const size_t rows = n > 0 ? n : 0, QKV = (size_t)(s->q_heads + 2 * s->kv_heads) * s->head_dim, wide = QKV > 2 * (size_t)s->inter ? QKV : 2 * (size_t)s->inter;
+    return decode_batch_lora_head(s, n, max_ctx) + align_up(rows * 3 * (r > 0 ? r : 0) * 4, 256) + align_up(rows * wide * 4, 256);
+}
+extern "C" int vila_llm_decode_step_batch_lora(const VilaLlmWeights* w, const VilaLlmLayerW4* qlayers, const VilaKvCache* cache, const VilaDecodeBatch* st,
+                                               const VilaDecodePrefix* prefix, const VilaLoraBank* bank, void* workspace, size_t workspace_bytes,
+                                               const VilaBatchSampling* sp, const VilaPenalties* pen, const VilaConstraints* con, int any_k,
+                                               vila_stream_t stream) {
+    const char* fn = "llm_decode_batch_lora";
+    VILA_REQUIRE(w != nullptr && cache != nullptr && st != nullptr && workspace != nullptr && bank != nullptr, "%s: NULL argument", fn);
+    VILA_REQUIRE(qlayers == nullptr, "%s: the step with per-row adapters has no int4 form (the adapters add to bf16 projections)", fn);
+    VILA_REQUIRE(prefix == nullptr, "%s: the step with per-row adapters has no shared-prefix form", fn);
+    VILA_REQUIRE(!any_k || sp != nullptr, "%s: any top_k is an option of the sampled pick", fn);
+    VILA_REQUIRE(bank->layers != nullptr && bank->scale != nullptr && bank->row_adapter != nullptr, "%s: the bank has a NULL pointer", fn);
+    VILA_REQUIRE((bank->r == 16 || bank->r == 32 || bank->r == 48 || bank->r == 64) && bank->capacity >= 1 && bank->capacity <= LORA_MAX_SLOTS,
+                 "%s: a bank of rank 16, 32, 48 or 64 with 1..%d slots (got r %d, %d slots)", fn, LORA_MAX_SLOTS, bank->r, bank->capacity);
+    if (pen != nullptr) VILA_TRY(penalties_ok(pen, w->shape.vocab, fn));
+    if (con != nullptr) VILA_TRY(constraints_ok(con, w->shape.vocab, fn));
+    VILA_REQUIRE(st->n >= 1 && st->n <= 16, "%s: 1..16 sequences (got %d)", fn, st->n);
+    VILA_REQUIRE(cache->max_ctx >= 1 && cache->max_ctx <= BDEC_MAX_CTX, "%s: caches up to %d positions (got %d)", fn, BDEC_MAX_CTX, cache->max_ctx);
+    VILA_REQUIRE(workspace_bytes >= vila_llm_decode_batch_lora_workspace_bytes(&w->shape, st->n, cache->max_ctx, bank->r),
+                 "%s: the step needs the workspace of vila_llm_decode_batch_lora_workspace_bytes", fn);
+    const VilaLlmShape& sh = w->shape;
+    std::vector<BLoraLayer> layers(sh.n_layers);
+    for (int l = 0; l < sh.n_layers; ++l) {
+        const VilaLoraBankLayer& L = bank->layers[l];
+        VILA_REQUIRE(L.a_qkv && L.b_qkv && L.a_o && L.b_o && L.a_gateup && L.b_gateup && L.a_down && L.b_down, "%s: bank layer %d has a NULL buffer", fn, l);
+        layers[l] = BLoraLayer{L.a_qkv, L.b_qkv, L.a_o, L.b_o, L.a_gateup, L.b_gateup, L.a_down, L.b_down};
+    }
+    const size_t head = decode_batch_penalized_head(&sh, st->n, cache->max_ctx, false), tail = decode_batch_lora_head(&sh, st->n, cache->max_ctx);
+    float* T = (float*)((char*)workspace + tail);
+    float* D = (float*)((char*)workspace + tail + align_up((size_t)st->n * 3 * bank->r * 4, 256));
+    const BLora lora{layers.data(), bank->scale, bank->row_adapter, bank->capacity, bank->r, T, D};
+    const Penalties P = pen != nullptr ? Penalties{pen->repetition, pen->presence, pen->frequency, pen->counts, pen->ld_counts} : Penalties{};
+    const Constraints Cn = con != nullptr ? Constraints{con->state, con->cls, con->ld_cls, con->next, con->ld_next, con->n_classes} : Constraints{};
+    return decode_step_batch_impl(w, nullptr, cache, st, workspace, head, sp, stream, nullptr, pen != nullptr ? &P : nullptr, (float*)((char*)workspace + head),
+                                  con != nullptr ? &Cn : nullptr, any_k != 0, &lora);
 }
 // The verify step (speculative decoding, decode_batch.hip bverify_step): the layer tables are the batched step's, the state is one sequence's.
 // sp != nullptr: the sampled form, whose four parameter arrays hold ONE entry each.

@@ -23,7 +23,9 @@
 #include <cstring>
 
 
-struct BGemmArgs {
+// BGemmCore: what the kernels of a step without adapters take (their kernarg layout is part of their machine code).  BGemmArgs adds the fp32 addend
+// of a step with per-row LoRA adapters (lora_decode.hip); a launch with addend == NULL runs the BGemmCore kernel.
+struct BGemmCore {
     const bf16_t* x; int64_t ldx;            // [n][K] activations
     const bf16_t* W; const bf16_t* W2;       // [N][K]; W2: up_proj rows (mode 1)
     const bf16_t* bias;                      // [N] optional
@@ -39,11 +41,16 @@ struct BGemmArgs {
     const float* rope_cs;                    // [n][hd]: cos | sin of each row's position
     int nq, nkv, hd, max_ctx;
 };
+struct BGemmArgs : BGemmCore {
+    const float* addend; int64_t lda;        // [n][N] fp32 (mode 1: [n][2 N], gate | up) added to the fp32 sum in front of the bias and the first rounding
+    const int32_t* row_adapter;              // [n] optional: a row with row_adapter[m] < 0 skips the add (NOT + 0.0: a sum of -0.0 keeps its sign)
+};
 
 // The finishing step of one work item, run by one wave on the block-reduced sums (C layout of v_mfma_f32_16x16x32: sequence m = lg*4 + r,
 // output feature n = r0 + l15).  Rounding mirrors gemv.hip / HF: every tensor rounded to bf16.
-template <int MODE, int NT>
-__device__ __forceinline__ void bgemm_epilogue(const BGemmArgs& p, int item, const int (&r0)[NT], const f32x4 (&sum)[NT], int lane) {
+// ADD (P = BGemmArgs): row m's addend joins the fp32 sum first, so in front of the bias, of silu (mode 1) and of RoPE and the cache append (mode 2).
+template <int MODE, int NT, bool ADD, class P>
+__device__ __forceinline__ void bgemm_epilogue(const P& p, int item, const int (&r0)[NT], const f32x4 (&sum)[NT], int lane) {
     const int l15 = lane & 15, lg = lane >> 4;
     const int half = p.hd >> 1, gph = half >> 4;
     (void)half; (void)gph; (void)item;
@@ -55,7 +62,11 @@ __device__ __forceinline__ void bgemm_epilogue(const BGemmArgs& p, int item, con
             for (int r = 0; r < 4; ++r) {
                 const int m = lg * 4 + r;
                 if (m < p.n) {
-                    const float gv = bfround(sum[0][r]), uv = bfround(sum[1][r]);            // HF: every tensor rounded to bf16
+                    float gs = sum[0][r], us = sum[1][r];
+                    if constexpr (ADD) {
+                        if (p.row_adapter == nullptr || p.row_adapter[m] >= 0) { gs += p.addend[(int64_t)m * p.lda + n]; us += p.addend[(int64_t)m * p.lda + p.N + n]; }
+                    }
+                    const float gv = bfround(gs), uv = bfround(us);                          // HF: every tensor rounded to bf16
                     p.y[(int64_t)m * p.ldy + n] = f2bf(bfround(silu_f(gv)) * uv);
                 }
             }
@@ -70,7 +81,11 @@ __device__ __forceinline__ void bgemm_epilogue(const BGemmArgs& p, int item, con
         for (int r = 0; r < 4; ++r) {
             const int m = lg * 4 + r;
             if (m >= p.n) continue;
-            const float lo = bfround(sum[0][r] + ba), hi = bfround(sum[1][r] + bb);
+            float sa = sum[0][r], sb = sum[1][r];
+            if constexpr (ADD) {
+                if (p.row_adapter == nullptr || p.row_adapter[m] >= 0) { sa += p.addend[(int64_t)m * p.lda + na]; sb += p.addend[(int64_t)m * p.lda + nb]; }
+            }
+            const float lo = bfround(sa + ba), hi = bfround(sb + bb);
             float oa = lo, ob = hi;
             if (!is_v) {
                 const float c = p.rope_cs[m * p.hd + gi], sn = p.rope_cs[m * p.hd + half + gi];
@@ -98,7 +113,11 @@ __device__ __forceinline__ void bgemm_epilogue(const BGemmArgs& p, int item, con
             for (int r = 0; r < 4; ++r) {
                 const int m = lg * 4 + r;
                 if (m >= p.n) continue;
-                float v = sum[0][r] + bv;
+                float v = sum[0][r];
+                if constexpr (ADD) {
+                    if (p.row_adapter == nullptr || p.row_adapter[m] >= 0) v += p.addend[(int64_t)m * p.lda + n];
+                }
+                v += bv;
                 if (p.y_f32 != nullptr) p.y_f32[(int64_t)m * p.ldf + n] = v;
                 if (p.y != nullptr) {
                     if (p.residual != nullptr) v = bfround(v) + bf2f(p.residual[(int64_t)m * p.ldr + n]);
@@ -125,8 +144,8 @@ __device__ __forceinline__ void bgemm_epilogue(const BGemmArgs& p, int item, con
 // between its ds_read and its MFMA, rstd per block in a prologue).  The fragment is re-normalised for every work item and wave, and with
 // software rounding that is ~240 VALU ops per k-block: gate/up 46.8 -> 67 us, lm_head 180 -> 414 us; with v_cvt_pk_bf16_f32 the step is
 // 3.64 ms against 3.60 with the two 5-us norm launches per layer — not worth a second code path.
-template <int MODE, int XR>
-__global__ __launch_bounds__(512) void bgemm_dma_kernel(BGemmArgs p, int n_items) {
+template <int MODE, int XR, bool ADD = false>
+__global__ __launch_bounds__(512) void bgemm_dma_kernel(std::conditional_t<ADD, BGemmArgs, BGemmCore> p, int n_items) {
     constexpr int NT = (MODE == 1 || MODE == 2) ? 2 : 1;
     constexpr int XI = XR / 8;                               // DMA instructions per activation slice
     constexpr int DPS = NT * 2 + XI;                         // DMA instructions per slot
@@ -235,41 +254,48 @@ __global__ __launch_bounds__(512) void bgemm_dma_kernel(BGemmArgs p, int n_items
                     sum[t][0] += a[0]; sum[t][1] += a[1]; sum[t][2] += a[2]; sum[t][3] += a[3];
                 }
             }
-            bgemm_epilogue<MODE, NT>(p, item, r0, sum, lane);
+            bgemm_epilogue<MODE, NT, ADD>(p, item, r0, sum, lane);
         }
     }
 }
-template <int MODE, int XR>
-static int launch_bgemm_dma_t(const BGemmArgs& a, int n_items, hipStream_t s) {
+template <int MODE, int XR, bool ADD = false>
+static int launch_bgemm_dma_t(const std::conditional_t<ADD, BGemmArgs, BGemmCore>& a, int n_items, hipStream_t s) {
     constexpr int NT = (MODE == 1 || MODE == 2) ? 2 : 1;
     const size_t lds = (size_t)8 * 16384 + (size_t)2 * 8 * NT * 256 * 4;
     static bool attr = false;
     if (!attr) {
-        VILA_HIP(hipFuncSetAttribute((const void*)bgemm_dma_kernel<MODE, XR>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        VILA_HIP(hipFuncSetAttribute((const void*)bgemm_dma_kernel<MODE, XR, ADD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         attr = true;
     }
     const int grid = n_items < 256 ? n_items : 256;
-    hipLaunchKernelGGL((bgemm_dma_kernel<MODE, XR>), dim3(grid), dim3(512), lds, s, a, n_items);
+    hipLaunchKernelGGL((bgemm_dma_kernel<MODE, XR, ADD>), dim3(grid), dim3(512), lds, s, a, n_items);
     VILA_LAUNCH_CHECK();
     return 0;
 }
 
-static int launch_bgemm(const BGemmArgs& a, hipStream_t s) {
-    VILA_REQUIRE(a.n >= 1 && a.n <= 16, "batched decode: 1..16 sequences (got %d)", a.n);
-    VILA_REQUIRE(a.K % 64 == 0 && a.K > 0 && a.N > 0, "batched decode GEMM: K (%d) must be a positive multiple of 64", a.K);
-    VILA_REQUIRE((uintptr_t)a.W % 16 == 0 && (uintptr_t)a.x % 16 == 0 && a.ldx % 8 == 0, "batched decode GEMM: operand alignment");
+// ADD: the kernels with the addend in the epilogue (a step with adapters); otherwise the BGemmCore kernels every other step launches
+template <bool ADD>
+static int launch_bgemm_t(const BGemmArgs& a, hipStream_t s) {
     const bool x8 = a.n <= 8;
     if (a.mode == 1) {
         VILA_REQUIRE(a.W2 != nullptr && a.y != nullptr, "batched decode GEMM: gate/up needs W2 and a bf16 output");
-        return x8 ? launch_bgemm_dma_t<1, 8>(a, cdiv(a.N, 16), s) : launch_bgemm_dma_t<1, 16>(a, cdiv(a.N, 16), s);
+        return x8 ? launch_bgemm_dma_t<1, 8, ADD>(a, cdiv(a.N, 16), s) : launch_bgemm_dma_t<1, 16, ADD>(a, cdiv(a.N, 16), s);
     }
     if (a.mode == 2) {
         VILA_REQUIRE(a.hd % 32 == 0 && a.N == (a.nq + 2 * a.nkv) * a.hd && a.q_out && a.kcache && a.vcache && a.pos && a.rope_cs,
                      "batched decode GEMM: qkv mode needs head_dim %% 32 == 0 and its outputs");
         const int items = (a.nq + 2 * a.nkv) * (a.hd / 32);
-        return x8 ? launch_bgemm_dma_t<2, 8>(a, items, s) : launch_bgemm_dma_t<2, 16>(a, items, s);
+        return x8 ? launch_bgemm_dma_t<2, 8, ADD>(a, items, s) : launch_bgemm_dma_t<2, 16, ADD>(a, items, s);
     }
-    return x8 ? launch_bgemm_dma_t<0, 8>(a, cdiv(a.N, 16), s) : launch_bgemm_dma_t<0, 16>(a, cdiv(a.N, 16), s);
+    return x8 ? launch_bgemm_dma_t<0, 8, ADD>(a, cdiv(a.N, 16), s) : launch_bgemm_dma_t<0, 16, ADD>(a, cdiv(a.N, 16), s);
+}
+static int launch_bgemm(const BGemmArgs& a, hipStream_t s) {
+    VILA_REQUIRE(a.n >= 1 && a.n <= 16, "batched decode: 1..16 sequences (got %d)", a.n);
+    VILA_REQUIRE(a.K % 64 == 0 && a.K > 0 && a.N > 0, "batched decode GEMM: K (%d) must be a positive multiple of 64", a.K);
+    VILA_REQUIRE((uintptr_t)a.W % 16 == 0 && (uintptr_t)a.x % 16 == 0 && a.ldx % 8 == 0, "batched decode GEMM: operand alignment");
+    if (a.addend == nullptr) return launch_bgemm_t<false>(a, s);
+    VILA_REQUIRE(a.lda >= (a.mode == 1 ? 2 : 1) * (int64_t)a.N, "batched decode GEMM: the addend's row stride (%lld) is shorter than its row", (long long)a.lda);
+    return launch_bgemm_t<true>(a, s);
 }
 
 // ---- per-row prologue / pick / advance -------------------------------------------------------------------------------------------
@@ -370,7 +396,8 @@ static bool bdec_carve(void* workspace, size_t workspace_bytes, int n, int H, in
 // layer); attn(q, kc, vc, ao) enqueues the layer's attention on that layer's cache.
 template <class Attn>
 static int bdec_forward(const BDecodeArgs& m, const BLayer* layers, const BLayerW4* qlayers, bf16_t* kcache, bf16_t* vcache, int64_t per_layer, int64_t slot_stride,
-                        int max_ctx, int n, const int32_t* pos, const int64_t* token, float* logits, const BStepBufs& b, hipStream_t s, Attn&& attn) {
+                        int max_ctx, int n, const int32_t* pos, const int64_t* token, float* logits, const BStepBufs& b, hipStream_t s, Attn&& attn,
+                        const BLora* lora = nullptr) {
     const int H = m.hidden, F = m.inter, hd = m.head_dim, QS = m.q_heads * hd, KS = m.kv_heads * hd;
     bf16_t* x = b.x; bf16_t* x2 = b.x2; bf16_t* xn = b.xn; bf16_t* q = b.q; bf16_t* ao = b.ao; bf16_t* act = b.act; float* rope_cs = b.rope_cs;
     auto normed = [&](BGemmArgs& g, const bf16_t* src, const void* w) -> int {
@@ -388,30 +415,45 @@ static int bdec_forward(const BDecodeArgs& m, const BLayer* layers, const BLayer
         a.nq = g.nq; a.nkv = g.nkv; a.hd = g.hd; a.max_ctx = g.max_ctx;
         return launch_gemv_w4_batch(a, s);
     };
+    // lora != nullptr (bf16 layers only): in front of a projection, shrink and expand of the rows' adapters on the projection's own input (lora_decode.hip)
+    // into lora->D [n][Ntot], which the GEMM's epilogue adds to its fp32 sum; columns [0, c1) | [c1, c2) | [c2, Ntot) are the members of the stack
+    auto adapt = [&](BGemmArgs& g, const void* A, const void* Bp, int Ntot, int c1, int c2) -> int {
+        if (lora == nullptr) return 0;
+        const int r = lora->r, Rs = (1 + (c1 < Ntot) + (c2 < Ntot)) * r;
+        VILA_TRY(launch_lora_shrink(g.x, g.ldx, n, (const bf16_t*)A, (int64_t)Rs * g.K, lora->scale, lora->row_adapter, lora->capacity, lora->T, Rs, Rs, g.K, s));
+        VILA_TRY(launch_lora_expand(lora->T, Rs, n, (const bf16_t*)Bp, (int64_t)r * Ntot, lora->row_adapter, lora->capacity, lora->D, Ntot, Ntot, r, c1, c2, s));
+        g.addend = lora->D; g.lda = Ntot; g.row_adapter = lora->row_adapter;
+        return 0;
+    };
     hipLaunchKernelGGL(bdec_prologue_kernel, dim3(cdiv(H / 8, 256), n), dim3(256), 0, s, (const bf16_t*)m.embed, token, x, H, (int64_t)m.vocab, pos, rope_cs, hd, m.rope_theta);
     VILA_LAUNCH_CHECK();
     bf16_t* cur = x; bf16_t* nxt = x2;
     for (int l = 0; l < m.n_layers; ++l) {
         const BLayer& L = layers[l];
         const BLayerW4 Q = qlayers != nullptr ? qlayers[l] : BLayerW4{};
+        const BLoraLayer A = lora != nullptr ? lora->layers[l] : BLoraLayer{};
         bf16_t* kc = kcache + l * per_layer; bf16_t* vc = vcache + l * per_layer;
         BGemmArgs qa{};
         VILA_TRY(normed(qa, cur, L.ln1_w));
         qa.ldx = H; qa.W = (const bf16_t*)L.wqkv; qa.bias = (const bf16_t*)L.bqkv;
         qa.n = n; qa.N = QS + 2 * KS; qa.K = H; qa.mode = 2; qa.q_out = q; qa.ldq = QS; qa.kcache = kc; qa.vcache = vc; qa.slot_stride = slot_stride;
         qa.pos = pos; qa.rope_cs = rope_cs; qa.nq = m.q_heads; qa.nkv = m.kv_heads; qa.hd = hd; qa.max_ctx = max_ctx;
+        VILA_TRY(adapt(qa, A.a_qkv, A.b_qkv, QS + 2 * KS, QS, QS + KS));
         VILA_TRY(proj(qa, Q.qkv_q, Q.qkv_sz));
         VILA_TRY(attn(q, kc, vc, ao));
         BGemmArgs o{};
         o.x = ao; o.ldx = QS; o.W = (const bf16_t*)L.wo; o.residual = cur; o.ldr = H; o.y = nxt; o.ldy = H; o.n = n; o.N = H; o.K = QS; o.mode = 0;
+        VILA_TRY(adapt(o, A.a_o, A.b_o, H, H, H));
         VILA_TRY(proj(o, Q.o_q, Q.o_sz));
         BGemmArgs gu{};
         VILA_TRY(normed(gu, nxt, L.ln2_w));
         gu.ldx = H; gu.W = (const bf16_t*)L.w_gate; gu.W2 = (const bf16_t*)L.w_up;
         gu.y = act; gu.ldy = F; gu.n = n; gu.N = F; gu.K = H; gu.mode = 1;
+        VILA_TRY(adapt(gu, A.a_gateup, A.b_gateup, 2 * F, F, 2 * F));
         VILA_TRY(proj(gu, Q.gateup_q, Q.gateup_sz));
         BGemmArgs dn{};
         dn.x = act; dn.ldx = F; dn.W = (const bf16_t*)L.w_down; dn.residual = nxt; dn.ldr = H; dn.y = cur; dn.ldy = H; dn.n = n; dn.N = H; dn.K = F; dn.mode = 0;
+        VILA_TRY(adapt(dn, A.a_down, A.b_down, H, H, H));
         VILA_TRY(proj(dn, Q.down_q, Q.down_sz));
     }
     BGemmArgs lm{};
@@ -439,7 +481,7 @@ size_t bdecode_prefix_workspace_bytes(int H, int F, int QS, int hd, int n, int m
 int bdecode_step(const BDecodeArgs& m, const BLayer* layers, bf16_t* kcache, bf16_t* vcache, int max_ctx, int n_slots, int n, int32_t* pos, int64_t* token,
                  int64_t* out_ids, int32_t* n_out, int max_out, float* logits, void* workspace, size_t workspace_bytes, hipStream_t s,
                  const BLayerW4* qlayers, const BatchSampling* sampling, void* sampling_ws, const BPrefix* prefix, const Penalties* pen, float* pen_out,
-                 const Constraints* con, bool any_k) {
+                 const Constraints* con, bool any_k, const BLora* lora) {
     static_assert(PEN_PICK_SLICES == PICK_SLICES, "the penalty launch writes the pairs bdec_pick2_kernel merges");
     const int H = m.hidden, F = m.inter, hd = m.head_dim, QS = m.q_heads * hd;
     VILA_REQUIRE((pen == nullptr && con == nullptr) || pen_out != nullptr, "batched decode: the penalised / constrained pick needs its scratch rows");
@@ -465,6 +507,13 @@ int bdecode_step(const BDecodeArgs& m, const BLayer* layers, bf16_t* kcache, bf1
                  "batched W4 decode: hidden (%d) and intermediate (%d) must be multiples of the 128-wide quantisation group", H, F);
     VILA_REQUIRE(workspace_bytes >= bdecode_workspace_bytes(H, F, QS, hd, n, max_ctx), "batched decode: workspace too small");
     VILA_REQUIRE(sampling == nullptr || sampling_ws != nullptr, "batched decode: the sampled pick needs its workspace");
+    if (lora != nullptr) {
+        VILA_REQUIRE(qlayers == nullptr && prefix == nullptr, "batched decode (adapters): the step with per-row adapters has no int4 and no shared-prefix form");
+        VILA_REQUIRE(lora->layers != nullptr && lora->scale != nullptr && lora->row_adapter != nullptr && lora->T != nullptr && lora->D != nullptr,
+                     "batched decode (adapters): NULL argument");
+        VILA_REQUIRE((lora->r == 16 || lora->r == 32 || lora->r == 48 || lora->r == 64) && lora->capacity >= 1 && lora->capacity <= LORA_MAX_SLOTS && F % 64 == 0,
+                     "batched decode (adapters): rank 16, 32, 48 or 64, 1..%d slots, intermediate %% 64 == 0 (got r %d, %d slots)", LORA_MAX_SLOTS, lora->r, lora->capacity);
+    }
     VILA_REQUIRE(!any_k || sampling != nullptr, "batched decode: any top_k is an option of the sampled pick");
     BStepBufs b{};
     VILA_REQUIRE(bdec_carve(workspace, workspace_bytes, n, H, F, QS, hd, m.q_heads, form.nsl, false, false, &b, prefix != nullptr ? bverify_attn_slices(max_ctx) : 0),
@@ -485,7 +534,7 @@ int bdecode_step(const BDecodeArgs& m, const BLayer* layers, bf16_t* kcache, bf1
         }
         return 0;
     };
-    VILA_TRY(bdec_forward(m, layers, qlayers, kcache, vcache, per_layer, slot_stride, max_ctx, n, pos, token, logits, b, s, attn));
+    VILA_TRY(bdec_forward(m, layers, qlayers, kcache, vcache, per_layer, slot_stride, max_ctx, n, pos, token, logits, b, s, attn, lora));
     float* pick_v = b.pick_v; int* pick_i = b.pick_i;
     // the pick: per-row sampling (sample.hip; greedy rows included, position = the draw's counter, read before it advances) or the greedy pair
     // penalised: one launch bumps each row's count of the token it consumed (token[] still holds it), writes the processed rows to pen_out and, for the
@@ -768,5 +817,47 @@ extern "C" int vila_qkv_batch_bf16(const void* x, int64_t ldx, int n, const void
     g.n = n; g.N = (q_heads + 2 * kv_heads) * head_dim; g.K = K; g.mode = 2;
     g.q_out = (bf16_t*)q_out; g.ldq = ldq; g.kcache = (bf16_t*)kcache; g.vcache = (bf16_t*)vcache; g.slot_stride = slot_stride;
     g.pos = pos; g.rope_cs = rope_cs; g.nq = q_heads; g.nkv = kv_heads; g.hd = head_dim; g.max_ctx = max_ctx;
+    return launch_bgemm(g, vila_stream_enter((void*)stream));
+}
+
+// The same launches with the fp32 addend of a step with per-row adapters (lora_decode.hip): addend [n][N] (gate/up: [n][2 N], gate | up; row stride
+// lda) joins the fp32 sum in front of the bias; a row with row_adapter[m] < 0 skips the add (row_adapter NULL: every row adds).  addend == NULL
+// launches the kernels of the entries above.
+extern "C" int vila_gemm_batch_lora_bf16(const void* x, int64_t ldx, int n, const void* W, const void* bias, const void* residual, int64_t ldr, void* y, int64_t ldy,
+                                         float* y_f32, int64_t ldf, int N, int K, const float* addend, int64_t lda, const int32_t* row_adapter,
+                                         vila_stream_t stream) {
+    VILA_REQUIRE(x != nullptr && W != nullptr, "vila_gemm_batch_lora_bf16: NULL operand");
+    VILA_REQUIRE(y != nullptr || y_f32 != nullptr, "vila_gemm_batch_lora_bf16: NULL output (y, y_f32 or both)");
+    VILA_REQUIRE(N > 0 && K > 0 && ldx >= K && (y == nullptr || ldy >= N) && (y_f32 == nullptr || ldf >= N) && (residual == nullptr || ldr >= N),
+                 "vila_gemm_batch_lora_bf16: a row stride shorter than its row (N=%d, K=%d)", N, K);
+    VILA_REQUIRE(residual == nullptr || y != nullptr, "vila_gemm_batch_lora_bf16: the residual is added to the bf16 output only");
+    BGemmArgs g{};
+    g.x = (const bf16_t*)x; g.ldx = ldx; g.W = (const bf16_t*)W; g.bias = (const bf16_t*)bias;
+    g.residual = (const bf16_t*)residual; g.ldr = ldr; g.y = (bf16_t*)y; g.ldy = ldy; g.y_f32 = y_f32; g.ldf = ldf;
+    g.n = n; g.N = N; g.K = K; g.mode = 0; g.addend = addend; g.lda = lda; g.row_adapter = row_adapter;
+    return launch_bgemm(g, vila_stream_enter((void*)stream));
+}
+extern "C" int vila_gateup_batch_lora_bf16(const void* x, int64_t ldx, int n, const void* Wgate, const void* Wup, void* y, int64_t ldy, int N, int K,
+                                           const float* addend, int64_t lda, const int32_t* row_adapter, vila_stream_t stream) {
+    VILA_REQUIRE(x != nullptr && Wgate != nullptr && Wup != nullptr && y != nullptr, "vila_gateup_batch_lora_bf16: NULL pointer");
+    VILA_REQUIRE(N > 0 && K > 0 && ldx >= K && ldy >= N, "vila_gateup_batch_lora_bf16: a row stride shorter than its row (N=%d, K=%d)", N, K);
+    BGemmArgs g{};
+    g.x = (const bf16_t*)x; g.ldx = ldx; g.W = (const bf16_t*)Wgate; g.W2 = (const bf16_t*)Wup; g.y = (bf16_t*)y; g.ldy = ldy;
+    g.n = n; g.N = N; g.K = K; g.mode = 1; g.addend = addend; g.lda = lda; g.row_adapter = row_adapter;
+    return launch_bgemm(g, vila_stream_enter((void*)stream));
+}
+extern "C" int vila_qkv_batch_lora_bf16(const void* x, int64_t ldx, int n, const void* Wqkv, const void* bias, void* q_out, int64_t ldq, void* kcache, void* vcache,
+                                        int64_t slot_stride, const int32_t* pos, const float* rope_cs, int q_heads, int kv_heads, int head_dim, int max_ctx, int K,
+                                        const float* addend, int64_t lda, const int32_t* row_adapter, vila_stream_t stream) {
+    VILA_REQUIRE(x != nullptr && Wqkv != nullptr && q_out != nullptr && kcache != nullptr && vcache != nullptr && pos != nullptr && rope_cs != nullptr,
+                 "vila_qkv_batch_lora_bf16: NULL pointer");
+    VILA_REQUIRE(q_heads > 0 && kv_heads > 0 && head_dim > 0 && max_ctx > 0 && K > 0 && ldx >= K && ldq >= (int64_t)q_heads * head_dim && slot_stride >= 0,
+                 "vila_qkv_batch_lora_bf16: q_heads=%d, kv_heads=%d, head_dim=%d, max_ctx=%d, or a row stride shorter than its row", q_heads, kv_heads, head_dim, max_ctx);
+    BGemmArgs g{};
+    g.x = (const bf16_t*)x; g.ldx = ldx; g.W = (const bf16_t*)Wqkv; g.bias = (const bf16_t*)bias;
+    g.n = n; g.N = (q_heads + 2 * kv_heads) * head_dim; g.K = K; g.mode = 2;
+    g.q_out = (bf16_t*)q_out; g.ldq = ldq; g.kcache = (bf16_t*)kcache; g.vcache = (bf16_t*)vcache; g.slot_stride = slot_stride;
+    g.pos = pos; g.rope_cs = rope_cs; g.nq = q_heads; g.nkv = kv_heads; g.hd = head_dim; g.max_ctx = max_ctx;
+    g.addend = addend; g.lda = lda; g.row_adapter = row_adapter;
     return launch_bgemm(g, vila_stream_enter((void*)stream));
 }

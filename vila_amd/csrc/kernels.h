@@ -247,6 +247,16 @@ int bprefix_attn_launch(const bf16_t* q, int64_t ldq, const bf16_t* kcache, cons
 int bprefix_attn(const bf16_t* q, int64_t ldq, const bf16_t* kcache, const bf16_t* vcache, int64_t slot_stride, int n_slots, int prefix_slot,
                  const int32_t* shared_len, int shared_len_host, const int32_t* uses, const int32_t* pos, bf16_t* o, int64_t ldo, int rows, int nq, int nkv,
                  int max_ctx, float scale, void* workspace, size_t workspace_bytes, hipStream_t s);
+// per-row LoRA adapters in the batched step (lora_decode.hip): row i runs under slot row_adapter[i] of a bank of `capacity` adapters of rank r, or under
+// none (-1).  Per layer and stack, A [capacity][Rs][K] bf16 (Rs = 3 r: q|k|v, 2 r: gate|up, r: o, down) and B packed [capacity][r / 8][N][8] bf16 over the
+// stack's N output columns; scale [capacity] fp32.  T [16][3 r] and D [16][max(q + 2 kv, 2 inter)] fp32 are the step's scratch.
+#define LORA_MAX_SLOTS 32
+struct BLoraLayer { const void *a_qkv, *b_qkv, *a_o, *b_o, *a_gateup, *b_gateup, *a_down, *b_down; };
+struct BLora { const BLoraLayer* layers; const float* scale; const int32_t* row_adapter; int capacity, r; float* T; float* D; };
+int launch_lora_shrink(const bf16_t* x, int64_t ldx, int n, const bf16_t* A, int64_t slot_stride, const float* scale, const int32_t* row_adapter, int capacity,
+                       float* T, int64_t ldt, int Rs, int K, hipStream_t s);
+int launch_lora_expand(const float* T, int64_t ldt, int n, const bf16_t* B, int64_t slot_stride, const int32_t* row_adapter, int capacity, float* D, int64_t ldd,
+                       int N, int r, int c1, int c2, hipStream_t s);
 // prefix != nullptr: the step of such a session (n_slots counts the prefix slot; the workspace is bdecode_prefix_workspace_bytes)
 size_t bdecode_prefix_workspace_bytes(int H, int F, int QS, int hd, int n, int max_ctx);
 int bdecode_step(const BDecodeArgs& m, const BLayer* layers, bf16_t* kcache, bf16_t* vcache, int max_ctx, int n_slots, int n, int32_t* pos, int64_t* token,
@@ -254,7 +264,8 @@ int bdecode_step(const BDecodeArgs& m, const BLayer* layers, bf16_t* kcache, bf1
                  const BLayerW4* qlayers = nullptr, const BatchSampling* sampling = nullptr, void* sampling_ws = nullptr, const BPrefix* prefix = nullptr,
                  const Penalties* pen = nullptr, float* pen_out = nullptr,    // pen: the pick runs on the penalised rows, written to pen_out [n][vocab]
                  const Constraints* con = nullptr,                            // con: ... masked by the rows' automata (behind the penalties), in pen_out as well
-                 bool any_k = false);                                         // any_k: the sampled pick serves every top_k >= 0 (launch_sample_batch)
+                 bool any_k = false,                                          // any_k: the sampled pick serves every top_k >= 0 (launch_sample_batch)
+                 const BLora* lora = nullptr);                                // lora: every row under its own adapter of the bank (bf16 layers, no prefix)
 // the verify step (greedy speculative decoding): n rows = n consecutive positions of ONE sequence in ONE slot.  Its attention (attn_decode.hip
 // bdec_attn_shared_kernel) reads the slot's K/V once for all rows; `pos` is the device scalar of the state, row i sees keys 0 .. min(pos + i, max_ctx - 1)
 int bverify_attn_slices(int max_ctx);

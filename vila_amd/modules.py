@@ -299,7 +299,7 @@ def _as_i64(u: int) -> int:
 
 
 def _step_symbols(batch: bool, w4: bool, sampled: bool, verify: bool = False, verify_sample: bool = False, prefix: bool = False,
-                  penalized: bool = False, constrained: bool = False, any_k: bool = False, processed: bool = False) -> Tuple[str, str]:
+                  penalized: bool = False, constrained: bool = False, any_k: bool = False, processed: bool = False, lora: bool = False) -> Tuple[str, str]:
     """(step, workspace query) of one decode step variant, composed the way the C ABI names them.  verify: the greedy verify step, whatever `batch`.
     verify_sample: the sampled verify step, whatever `batch`, `sampled` and `verify` — a spelling of its own, since `verify` with `sampled` stays the
     refusal it always was (that pair names the greedy step asked to sample).  prefix: the batched step of a session with a shared prompt prefix
@@ -312,7 +312,20 @@ def _step_symbols(batch: bool, w4: bool, sampled: bool, verify: bool = False, ve
     steps and the solo step (whose sampler serves any top_k already) have no such form.
     processed: the verify step with penalties / an automaton in front of its pick and logprob records behind its accept — ONE entry for the verify steps
     (int4 layers, sampling parameters, the any_k option, penalties, automaton and records all arguments of it, so none of them changes the names).  A
-    spelling of its own: `verify` / `verify_sample` with `penalized` or `constrained` stay the refusals they always were."""
+    spelling of its own: `verify` / `verify_sample` with `penalized` or `constrained` stay the refusals they always were.
+    lora: the batched step with a per-row LoRA adapter (`vila_amd.lora_serving.AdapterBank`) — ONE entry, which takes the sampling parameters, the any_k
+    option, penalties and automata as nullable arguments, so none of them changes the names.  The adapters add to bf16 projections of rows with caches
+    of their own: int4 layers, a shared prefix, the verify steps and the solo step have no such form."""
+    if lora:
+        if w4:
+            raise ValueError("the step with per-row adapters has no int4 form: the adapters add to bf16 projections")
+        if prefix:
+            raise ValueError("the step with per-row adapters has no shared-prefix form")
+        if verify or verify_sample or processed:
+            raise ValueError("the verify steps have no adapter form")
+        if not batch:
+            raise ValueError("the step with per-row adapters is a batched step: the solo step has no adapter form")
+        return "vila_llm_decode_step_batch_lora", "vila_llm_decode_batch_lora_workspace_bytes"
     if processed:
         if not (verify or verify_sample) or prefix:
             raise ValueError("the processed step is a verify step")
@@ -484,9 +497,15 @@ class HipQwen2ForCausalLM(_HipModule):
     @torch.no_grad()
     def prefill_packed(self, embeds: torch.Tensor, positions: torch.Tensor, cu_seqlens: Optional[torch.Tensor], max_seqlen: int,
                        cache=None, seq_of_tok: Optional[torch.Tensor] = None, last_rows: Optional[torch.Tensor] = None,
-                       want_all_logits: bool = False, want_final_hidden: bool = False, want_layer_hidden: bool = False):
-        """embeds [T,H] bf16 packed stream.  Returns a namespace with last_logits / all_logits / final_hidden / layer_hidden."""
+                       want_all_logits: bool = False, want_final_hidden: bool = False, want_layer_hidden: bool = False, adapter: Optional[str] = None,
+                       adapters=None):
+        """embeds [T,H] bf16 packed stream.  Returns a namespace with last_logits / all_logits / final_hidden / layer_hidden.
+        adapter=name with adapters=bank (`vila_amd.lora_serving.AdapterBank`): every packed sequence runs under that adapter of the bank, unmerged
+        (`vila_llm_prefill_lora`: the trainer's forward dataflow, t and u rounded to bf16); bf16 models, no layer_hidden."""
         ops._need(embeds, name="inputs_embeds")
+        if adapter is not None:
+            return self._prefill_packed_lora(embeds, positions, cu_seqlens, max_seqlen, cache, seq_of_tok, last_rows, want_all_logits, want_final_hidden,
+                                             want_layer_hidden, adapter, adapters)
         c = self.lcfg
         T = embeds.shape[0]
         dev = embeds.device
@@ -512,13 +531,38 @@ class HipQwen2ForCausalLM(_HipModule):
             check(lib.vila_llm_prefill(C.byref(w), *args), "vila_llm_prefill")
         return SimpleNamespace(last_logits=last_logits, all_logits=all_logits, final_hidden=final_hidden, layer_hidden=layer_hidden)
 
+    def _prefill_packed_lora(self, embeds, positions, cu_seqlens, max_seqlen, cache, seq_of_tok, last_rows, want_all_logits, want_final_hidden,
+                             want_layer_hidden, adapter, adapters):
+        if adapters is None:
+            raise ValueError("prefill_packed(adapter=): pass the bank that holds the adapter as adapters=")
+        if self._w4 is not None or want_layer_hidden:
+            raise ValueError("prefill_packed(adapter=): the prefill under an adapter serves bf16 models and returns no layer_hidden")
+        self._require_bf16("the prefill under an adapter")
+        c, T, dev, lib, w = self.lcfg, embeds.shape[0], embeds.device, _lib.load(), self._struct()
+        layers, r, scale = adapters.c_prefill(adapter)
+        ws = self._workspace(lib.vila_llm_prefill_lora_workspace_bytes(C.byref(w.shape), T, r), dev)
+        n_seq = 1 if cu_seqlens is None else cu_seqlens.numel() - 1
+        n_last = 0 if last_rows is None else last_rows.numel()
+        last_logits = torch.empty((n_last, c.vocab_size), device=dev, dtype=torch.float32) if n_last else None
+        all_logits = torch.empty((T, c.vocab_size), device=dev, dtype=torch.float32) if want_all_logits else None
+        final_hidden = torch.empty((T, c.hidden_size), device=dev, dtype=self.dtype) if want_final_hidden else None
+        check(lib.vila_llm_prefill_lora(C.byref(w), layers, r, scale, embeds.contiguous().data_ptr(), positions.data_ptr(), ops._p(cu_seqlens), n_seq, T,
+                                        int(max_seqlen), ops._p(seq_of_tok), C.byref(cache.c) if cache is not None else None, ops._p(last_rows), n_last,
+                                        ops._p(last_logits), ops._p(all_logits), ops._p(final_hidden), ws.data_ptr(), ws.numel(), ops._stream()),
+              "vila_llm_prefill_lora")
+        return SimpleNamespace(last_logits=last_logits, all_logits=all_logits, final_hidden=final_hidden, layer_hidden=None)
+
     # ---- prefill onto a live cache ----------------------------------------------------------------------------
     @torch.no_grad()
     def prefill_append(self, embeds: torch.Tensor, cache, past: int, slot: int = 0, last_rows: Optional[torch.Tensor] = None,
-                       want_final_hidden: bool = False, want_layer_hidden: bool = False):
+                       want_final_hidden: bool = False, want_layer_hidden: bool = False, adapter: Optional[str] = None):
         """embeds [T,H] bf16: T tokens of ONE sequence appended to `slot` of `cache`, which holds `past` positions.  They take positions
         past .. past + T - 1, their K/V are written there and every row attends the slot's keys 0 .. its own position.  last_rows counts rows
-        inside these T tokens.  Returns the namespace of `prefill_packed` (all_logits is None).  The W4 route is taken as there."""
+        inside these T tokens.  Returns the namespace of `prefill_packed` (all_logits is None).  The W4 route is taken as there.
+        adapter: must be None — the append prefill has no form under an unmerged adapter (prefill_packed(adapter=) has)."""
+        if adapter is not None:
+            raise ValueError("prefill_append: the append prefill (follow-up turns, prefill_chunk, ChatSession) does not run under an unmerged adapter; "
+                             "prefill the whole prompt with prefill_packed(adapter=) / batch_admit(adapter=)")
         ops._need(embeds, name="inputs_embeds")
         c = self.lcfg
         if embeds.dim() != 2 or embeds.shape[1] != c.hidden_size:
@@ -916,13 +960,17 @@ class HipQwen2ForCausalLM(_HipModule):
         pen = getattr(st, "pen", None)                                  # a session with the penalties flag: the one entry of its driver, NULLs for what is off
         con = getattr(st, "con", None)                                  # a session with the constraints flag: likewise, the penalties nullable too
         ref = lambda s: None if s is None else C.byref(s)
-        if getattr(st, "processed", False):                             # a verify session with the processed flag: one entry, NULLs for what is off
+        if getattr(st, "lora", None) is not None:                       # a session with an adapter bank: the one entry, NULLs for what is off
+            name, _ = _step_symbols(batch, w4 is not None, sp is not None, verify, verify_sample, prefix=px is not None, lora=True)
+            check(getattr(_lib.load(), name)(C.byref(self._struct()), None, C.byref(cache.c), C.byref(st.c), None, C.byref(st.lora), st.ws.data_ptr(), st.ws.numel(),
+                                             ref(sp), ref(pen), ref(con), 1 if getattr(st, "any_k", False) else 0, ops._stream()), name)
+        elif getattr(st, "processed", False):                           # a verify session with the processed flag: one entry, NULLs for what is off
             name, _ = _step_symbols(batch, w4 is not None, sp is not None, verify, verify_sample, processed=True)
             check(getattr(_lib.load(), name)(C.byref(self._struct()), w4.ptr if w4 is not None else None, C.byref(cache.c), C.byref(st.c), st.ws.data_ptr(),
                                              st.ws.numel(), ref(sp), 1 if getattr(st, "any_k", False) else 0, ref(pen), ref(con), ref(getattr(st, "lp", None)),
                                              ops._stream()), name)
             return                                                      # (its records are written inside the entry, behind the accept)
-        if getattr(st, "any_k", False):                                 # a session with the any_top_k flag: the one entry of its driver, NULLs for what is off
+        elif getattr(st, "any_k", False):                               # a session with the any_top_k flag: the one entry of its driver, NULLs for what is off
             name, _ = _step_symbols(batch, w4 is not None, sp is not None, verify, verify_sample, prefix=px is not None, any_k=True)
             args = ([C.byref(self._struct()), w4.ptr if w4 is not None else None, C.byref(cache.c), C.byref(st.c)] + ([] if verify_sample else [ref(px)]) +
                     [st.ws.data_ptr(), st.ws.numel(), C.byref(sp)] + ([] if verify_sample else [ref(pen), ref(con)]) + [ops._stream()])
@@ -999,7 +1047,7 @@ class HipQwen2ForCausalLM(_HipModule):
         return True
 
     def _batch_session(self, n: int, max_ctx: int, max_new_tokens: int, sampling: bool = False, shared_prefix: bool = False, penalties: bool = False,
-                       logprobs: bool = False, constraints=None, any_top_k: bool = False):
+                       logprobs: bool = False, constraints=None, any_top_k: bool = False, adapters=None):
         """sampling=True: the session owns per-row sampling parameters on the device (temperature / top_k / top_p / seed, every row greedy
         until `_batch_set_sampling` says otherwise) and steps through the `_sample` entry points: one captured graph for any mix of rows.
         shared_prefix=True: the cache has one slot more, the prefix slot (index n), and the session owns the shared length and the rows' flags on
@@ -1013,16 +1061,22 @@ class HipQwen2ForCausalLM(_HipModule):
         `vila_llm_decode_step_batch_constrained` and owns an automaton per row (`_constraint_state`), every row unconstrained until
         `_set_constraint` says otherwise.
         any_top_k=True (sampling sessions; in the key only when set, likewise): the session steps through `vila_llm_decode_step_batch_any_k`, whose
-        pick serves a row with any top_k >= 0 (0 = no top-k filter) from the same device arrays."""
+        pick serves a row with any top_k >= 0 (0 = no top-k filter) from the same device arrays.
+        adapters=bank (an `AdapterBank`; in the key only when set, likewise): the session steps through `vila_llm_decode_step_batch_lora` and owns
+        `row_adapter` [n] int32 on the device, every row -1 (the base model) until `batch_admit(adapter=)` / `_set_row_adapter` says otherwise.  bf16
+        models, no shared prefix."""
         if any_top_k and not sampling:
             raise ValueError("any_top_k is an option of a sampling session (sampling=True)")
         w4 = self._w4_batched()
+        if adapters is not None:
+            _step_symbols(True, self._w4 is not None, bool(sampling), prefix=bool(shared_prefix), lora=True)      # (its refusals: int4 layers, a shared prefix)
         if not w4:
             self._require_bf16("the batched decode")
         key = (n, max_ctx, max_new_tokens, bool(sampling), *self._weights_key()) + ((True,) if shared_prefix else ()) + (("penalties",) if penalties else ())
         key += ("logprobs",) if logprobs else ()
         key += ("constraints", *constraints) if constraints else ()
         key += ("any_top_k",) if any_top_k else ()
+        key += ("adapters", id(adapters), adapters.capacity, adapters.r) if adapters is not None else ()
         if self._bdecode is not None and self._bdecode.key == key:
             return self._bdecode
         self._drop_session("_bdecode")
@@ -1030,6 +1084,7 @@ class HipQwen2ForCausalLM(_HipModule):
         st = SimpleNamespace(key=key, graph=None, sampling=bool(sampling), sp=None, px=None, shared_prefix=bool(shared_prefix), pen=None, lp=None, con=None)
         if any_top_k:
             st.any_k = True
+        st.lora, st.adapters = None, adapters
         st.attn_slices = int(lib.vila_decode_batch_slices(int(max_ctx)))     # walking-attention slices the steps of this session launch (0: short form)
         with torch.inference_mode(False):
             st.cache = self.new_cache(max_ctx, n_slots=n + 1 if shared_prefix else n)
@@ -1045,7 +1100,12 @@ class HipQwen2ForCausalLM(_HipModule):
             st.n_out = torch.zeros(n, device=dev, dtype=torch.int32)
             st.logits = torch.zeros((n, self.lcfg.vocab_size), device=dev, dtype=torch.float32)
             ws_bytes = getattr(lib, _step_symbols(True, w4, bool(sampling), prefix=bool(shared_prefix), penalized=bool(penalties),
-                                                  constrained=bool(constraints), **(dict(any_k=True) if any_top_k else {}))[1])
+                                                  constrained=bool(constraints), **(dict(any_k=True) if any_top_k else {}),
+                                                  **(dict(lora=True) if adapters is not None else {}))[1])
+            if adapters is not None:
+                st.row_adapter = torch.full((n,), -1, device=dev, dtype=torch.int32)
+                st.row_names = [None] * n                              # the adapter each live row was admitted under (the bank counts them)
+                st.lora = adapters.c_bank(st.row_adapter)
             if constraints:
                 self._constraint_state(st, n, self.lcfg.vocab_size, constraints, dev)
             if penalties:
@@ -1059,6 +1119,8 @@ class HipQwen2ForCausalLM(_HipModule):
                 st.s_seed = torch.zeros(n, device=dev, dtype=torch.int64)                   # bit patterns of uint64 seeds
                 st.sp = _lib.VilaBatchSampling(st.s_temperature.data_ptr(), st.s_top_k.data_ptr(), st.s_top_p.data_ptr(), st.s_seed.data_ptr())
             ws_args = (int(bool(shared_prefix)),) if penalties or constraints or any_top_k else ()
+            if adapters is not None:
+                ws_args = (adapters.r,)
             st.ws = torch.empty((ws_bytes(C.byref(w.shape), n, int(max_ctx), *ws_args),), device=dev, dtype=torch.uint8)    # (<= 2048 positions: the size it always had)
         st.c = _lib.VilaDecodeBatch(n, st.pos.data_ptr(), st.token.data_ptr(), st.out_ids.data_ptr(), st.n_out.data_ptr(), max(max_new_tokens, 1),
                                     st.logits.data_ptr())
@@ -1097,9 +1159,23 @@ class HipQwen2ForCausalLM(_HipModule):
         st.s_top_p[slot:slot + 1].fill_(float(p))
         st.s_seed[slot:slot + 1].fill_(_as_i64(seed))
 
+    @staticmethod
+    def _set_row_adapter(st, slot: int, name) -> int:
+        """Row `slot` of a session with a bank runs under adapter `name` from its next step on (None: the base model, -1); the bank counts the
+        live rows of every slot, so that `unload` can refuse.  -> the bank slot."""
+        bank, old = st.adapters, st.row_names[slot]
+        new = bank.slot_of(name)
+        if old is not None and old in bank:
+            bank.in_use[bank.slot_of(old)] -= 1
+        if name is not None:
+            bank.in_use[new] += 1
+        st.row_names[slot] = name
+        st.row_adapter[slot:slot + 1].fill_(new)
+        return new
+
     def batch_open(self, n_slots: int, max_ctx: int = 2048, max_new_tokens: int = 1024, sampling: bool = False, shared_prefix: bool = False,
                    penalties: bool = False, logprobs: bool = False, constraints: bool = False, max_states: int = 512, max_classes: int = 4096,
-                   any_top_k: bool = False):
+                   any_top_k: bool = False, adapters=None):
         """Open (or re-use) the batched-decode session of `n_slots` rows with its captured step.  sampling=False: the greedy step.  sampling=True:
         the step picks per row from device-resident parameters, so the ONE captured graph serves any mix of greedy and sampled rows
         (`batch_admit(..., sampling=)`); the flag is part of the session key.
@@ -1120,9 +1196,16 @@ class HipQwen2ForCausalLM(_HipModule):
         any_top_k=True (with sampling=True; part of the key as well): a sampled row may carry ANY top_k >= 0 — 0 = no top-k filter, HF's meaning,
         i.e. pure top-p sampling, and k > 64 — where the session without the flag serves 1..64.  Such a row is drawn on the device by the solo
         sampler's exact path (one launch more per step, one block per row) and gets bit for bit the token `ops.sample` returns for its logits,
-        parameters, seed and counter; the ONE captured graph serves any mix of greedy rows, rows of 1..64 and such rows."""
+        parameters, seed and counter; the ONE captured graph serves any mix of greedy rows, rows of 1..64 and such rows.
+        adapters=bank (a `vila_amd.lora_serving.AdapterBank`; part of the key as well, only when set): every row may run under its own LoRA adapter
+        of the bank, unmerged (`batch_admit(..., adapter=name)`; None = the base model).  The rows' slots live in a device array and the bank's
+        buffers never move, so the ONE captured graph serves any mix of adapters and survives `bank.load` / `bank.unload`.  bf16 models; not with
+        shared_prefix.  A row without an adapter keeps the bits of the session without the flag."""
         if any_top_k and not sampling:
             raise ValueError("batch_open: any_top_k=True is an option of a sampling session (sampling=True)")
+        if adapters is not None and (self._w4 is not None or shared_prefix):
+            raise ValueError("batch_open: adapters= serves bf16 models without a shared prefix (the adapters add to bf16 projections of rows with "
+                             "caches of their own)")
         if not self._w4_batched():
             self._require_bf16("batch_open")
         con_caps = self._constraint_caps(max_states, max_classes) if constraints else None
@@ -1132,9 +1215,13 @@ class HipQwen2ForCausalLM(_HipModule):
             raise ValueError("batch_open: the batched decode step serves 1..16 rows of a head-dim-128 model (bf16, or quantize_w4(batch_decode=True)) "
                              f"with caches <= {self.BATCH_MAX_CTX} positions (beyond 2048: GQA groups of 1, 2, 4, 7 or 8 query heads)")
         st = self._batch_session(max(n_slots, 2), max_ctx, max_new_tokens, sampling, shared_prefix, penalties, logprobs,
-                                 **({} if con_caps is None else dict(constraints=con_caps)), **(dict(any_top_k=True) if any_top_k else {}))
+                                 **({} if con_caps is None else dict(constraints=con_caps)), **(dict(any_top_k=True) if any_top_k else {}),
+                                 **({} if adapters is None else dict(adapters=adapters)))
         if getattr(st, "con", None) is not None:
             st.con_state.fill_(-1)                                     # every row starts unconstrained (an idle row never advances)
+        if getattr(st, "lora", None) is not None:
+            for slot in range(len(st.row_names)):
+                self._set_row_adapter(st, slot, None)                  # every row starts on the base model
         def reset():
             st.pos.zero_(); st.n_out.zero_(); st.token.zero_()
             if getattr(st, "pen", None) is not None:
@@ -1210,7 +1297,7 @@ class HipQwen2ForCausalLM(_HipModule):
         return st.staged_logits
 
     def batch_admit(self, st, slot: int, embeds: torch.Tensor, sampling=None, share: bool = False, first_row: int = 0, penalties=None,
-                    constraint=None) -> int:
+                    constraint=None, adapter: Optional[str] = None) -> int:
         """Prefill ONE sequence [P, H] into KV slot `slot` of the open batch and make the row live: position P, first token = argmax of the
         prefill's last row (returned), output counter 0.  sampling = (temperature, top_k in 1..64 — any top_k >= 0 in a session opened with
         any_top_k=True —, top_p, seed), sampling sessions only: the
@@ -1226,7 +1313,14 @@ class HipQwen2ForCausalLM(_HipModule):
         generated yet).  None = a neutral row.
         constraint = a `vila_amd.constrain.Automaton`, sessions opened with constraints=True only: its classes and table go to the row, the first
         token is chosen from the prefill's last row masked from the start state (one eager operator call), and every step advances the state by the
-        token it consumes and masks its pick.  None = an unconstrained row (state -1)."""
+        token it consumes and masks its pick.  None = an unconstrained row (state -1).
+        adapter = the name of an adapter loaded into the session's bank, sessions opened with adapters= only: the prompt is prefilled under the
+        adapter (`prefill_packed(adapter=)`) and the row's entry of `row_adapter` is set, so its steps add the adapter's deltas.  None = the base
+        model (-1)."""
+        if adapter is not None:
+            if getattr(st, "lora", None) is None:
+                raise ValueError("batch_admit: a row under an adapter needs a session opened with batch_open(adapters=bank)")
+            st.adapters.slot_of(adapter)                               # (raises for a name that is not loaded)
         if constraint is not None:
             if getattr(st, "con", None) is None:
                 raise ValueError("batch_admit: a constrained row needs a session opened with batch_open(constraints=True)")
@@ -1266,7 +1360,10 @@ class HipQwen2ForCausalLM(_HipModule):
             pos = torch.arange(P, device=dev, dtype=torch.int32)
             seq = torch.full((P,), int(slot), device=dev, dtype=torch.int32)
             cu = torch.tensor([0, P], device=dev, dtype=torch.int32)
-            logits = self.prefill_packed(embeds.to(self.dtype), pos, cu, P, cache=st.cache, seq_of_tok=seq, last_rows=last).last_logits[0]
+            lora_kw = {} if adapter is None else dict(adapter=adapter, adapters=st.adapters)
+            logits = self.prefill_packed(embeds.to(self.dtype), pos, cu, P, cache=st.cache, seq_of_tok=seq, last_rows=last, **lora_kw).last_logits[0]
+        if getattr(st, "lora", None) is not None:
+            self._set_row_adapter(st, int(slot), adapter)
         pick_from = logits
         if getattr(st, "con", None) is not None:
             self._set_constraint(st, int(slot), constraint)
@@ -1298,6 +1395,9 @@ class HipQwen2ForCausalLM(_HipModule):
             idx = torch.tensor(slots, device=st.pos.device, dtype=torch.int64)
             st.pos.index_fill_(0, idx, 0)
             st.n_out.index_fill_(0, idx, 0)
+            if getattr(st, "lora", None) is not None:
+                for s_ in slots:
+                    self._set_row_adapter(st, int(s_), None)           # an idle row runs on the base model
             if getattr(st, "con", None) is not None:
                 st.con_state.index_fill_(0, idx, -1)                   # an idle row is an unconstrained row
             if st.sampling:
@@ -1370,7 +1470,7 @@ class HipQwen2ForCausalLM(_HipModule):
 
     def _generate_batch(self, inputs_embeds, attention_mask, max_new_tokens, eos_token_id, pad_token_id, use_graph: bool = True,
                         forced_ids: Optional[torch.Tensor] = None, return_logits: bool = False, sampling=None, penalties=None, logprobs=None,
-                        constraint=None, any_top_k: bool = False):
+                        constraint=None, any_top_k: bool = False, adapter=None, adapters=None):
         """The padded batch as ONE packed prefill (every row into its own KV-cache slot) + batched decode steps: the weights are streamed
         once per step for all rows.  Returns [B, n_new] right-padded with pad_token_id behind each row's EOS, like HF.
         forced_ids [B, n_new] / return_logits: teacher forcing for the parity tests (eager launches; the ids fed after step t are
@@ -1386,7 +1486,9 @@ class HipQwen2ForCausalLM(_HipModule):
         constraint: None, or an `Automaton` for every row (or a list with one / None per row): the batch runs in a session with the constraints flag;
         the first tokens are chosen from the prefill's rows masked from the start states, the returned logits stay raw, the returned ids are the
         ones each step chose.
-        any_top_k (with sampling): the session carries the any_top_k flag, so a row's top_k may be 0 (no top-k filter) or above 64."""
+        any_top_k (with sampling): the session carries the any_top_k flag, so a row's top_k may be 0 (no top-k filter) or above 64.
+        adapters=bank with adapter = one name / None per row: the batch (1..16 rows; one row runs in a session of two) runs in a session with the
+        bank, every row under its own adapter, unmerged.  The prefill is one packed call per adapter, over the rows that share it."""
         ops._need(inputs_embeds, dtype=None, name="inputs_embeds")
         any_kw = dict(any_top_k=True) if any_top_k and sampling is not None else {}
         if sampling is not None:
@@ -1404,6 +1506,9 @@ class HipQwen2ForCausalLM(_HipModule):
         seq = torch.cat([torch.full((n,), b, dtype=torch.int32) for b, n in enumerate(lens)]).to(dev)
         last = torch.tensor([c - 1 for c in cu_h[1:]], device=dev, dtype=torch.int32)
         max_ctx = ((max(lens) + max_new_tokens + 255) // 256) * 256
+        if adapters is not None:
+            return self._generate_batch_adapters(packed, lens, cu_h, max_ctx, max_new_tokens, eos_token_id, pad_token_id, use_graph, forced_ids, return_logits,
+                                                 sampling, penalties, logprobs, constraint, any_kw, list(adapter), adapters)
         st = self._batch_session(Bn, max_ctx, max_new_tokens, sampling is not None, penalties=penalties is not None,
                                  **({} if logprobs is None else dict(logprobs=True)),
                                  **({} if constraint is None else dict(constraints=self._constraint_caps(self.CONSTRAIN_MAX_STATES, self.CONSTRAIN_MAX_CLASSES))),
@@ -1481,6 +1586,97 @@ class HipQwen2ForCausalLM(_HipModule):
             return out, self._pack_logprobs([self._row_logprobs(st, b, done) for b in range(Bn)], cut, out.shape[1], logprobs, dev)
         return out
 
+    def _generate_batch_adapters(self, packed, lens, cu_h, max_ctx, max_new_tokens, eos_token_id, pad_token_id, use_graph, forced_ids, return_logits,
+                                 sampling, penalties, logprobs, constraint, any_kw, names, bank):
+        """`_generate_batch` in a session with an adapter bank: row b runs under names[b] (None: the base model).  The rows are those of a
+        continuous-batching session: prefilled per adapter group into their slots, made live, stepped by the session's ONE graph, released."""
+        Bn, dev = len(lens), packed.device
+        st = self.batch_open(Bn, max_ctx, max_new_tokens, sampling=sampling is not None, penalties=penalties is not None,
+                             **({} if logprobs is None else dict(logprobs=True)),
+                             **({} if constraint is None else dict(constraints=True, max_states=self.CONSTRAIN_MAX_STATES, max_classes=self.CONSTRAIN_MAX_CLASSES)),
+                             **any_kw, adapters=bank)
+        self.batch_release(st, range(st.pos.numel()))
+        try:
+            st.stream.synchronize()
+            last_logits = torch.empty((Bn, self.lcfg.vocab_size), device=dev, dtype=torch.float32)
+            for name in dict.fromkeys(names):                          # one packed prefill per adapter, over the rows that share it
+                rows = [b for b in range(Bn) if names[b] == name]
+                x = torch.cat([packed[cu_h[b]:cu_h[b + 1]] for b in rows])
+                cu = torch.tensor([0] + list(torch.tensor([lens[b] for b in rows]).cumsum(0).tolist()), device=dev, dtype=torch.int32)
+                pos = torch.cat([torch.arange(lens[b], dtype=torch.int32) for b in rows]).to(dev)
+                seq = torch.cat([torch.full((lens[b],), b, dtype=torch.int32) for b in rows]).to(dev)
+                last = (cu[1:] - 1).contiguous()
+                r = self.prefill_packed(x, pos, cu, max(lens[b] for b in rows), cache=st.cache, seq_of_tok=seq, last_rows=last,
+                                        **({} if name is None else dict(adapter=name, adapters=bank)))
+                last_logits[rows] = r.last_logits
+            rows_pen = (list(penalties) if isinstance(penalties, list) else [penalties] * Bn) if penalties is not None else None
+            rows_con = (list(constraint) if isinstance(constraint, (list, tuple)) else [constraint] * Bn) if constraint is not None else None
+            ctr = torch.tensor([n - 1 for n in lens], device=dev, dtype=torch.int32)
+
+            def arm():
+                """Rows 0 .. Bn - 1 live at their prompts' ends with their first tokens; also what the capture's warm-up step is undone with."""
+                firsts = []
+                for b in range(Bn):
+                    self._set_row_adapter(st, b, names[b])
+                    pick_from = last_logits[b]
+                    if rows_con is not None:
+                        self._set_constraint(st, b, rows_con[b])
+                        pick_from = self._first_constrained(st, b, last_logits[b])
+                    sp = None if sampling is None else sampling[b]
+                    firsts.append(ops.argmax(pick_from) if sp is None else ops.sample(pick_from, sp[0], sp[1], sp[2], sp[3], counter=ctr[b:b + 1]))
+                    if sampling is not None:
+                        self._batch_set_sampling(st, b, sp)
+                    if rows_pen is not None:
+                        self._set_penalties(st, b, rows_pen[b])
+                first = torch.cat(firsts)
+                st.pos[:Bn].copy_(torch.tensor(lens, dtype=torch.int32)); st.n_out.zero_(); st.token[:Bn].copy_(first)
+                return first
+            first = arm()
+            if logprobs is not None:
+                for b in range(Bn):
+                    self._first_logprobs(st, b, last_logits[b], first[b:b + 1])
+            eos_set = _eos_set(eos_token_id, self.lcfg.eos_token_id)
+            n_steps = max_new_tokens - 1
+            if forced_ids is not None or return_logits:
+                step_logits, ids = [last_logits.clone()], [first]
+                if forced_ids is not None:
+                    st.token[:Bn].copy_(forced_ids[:, 0].to(dev))
+                plain = sampling is None and rows_pen is None and rows_con is None
+                torch.cuda.current_stream().synchronize()
+                with torch.cuda.stream(st.stream):
+                    for t in range(n_steps):
+                        self._batch_step(st)
+                        step_logits.append(st.logits[:Bn].float().clone())
+                        ids.append(torch.cat([ops.argmax(st.logits[b]) for b in range(Bn)]) if plain else st.token[:Bn].clone())
+                        if forced_ids is not None and t + 1 < forced_ids.shape[1]:
+                            st.token[:Bn].copy_(forced_ids[:, t + 1].to(dev))
+                st.stream.synchronize()
+                return torch.stack(ids, 1), torch.stack(step_logits, 0)
+            first_h = first.tolist()
+            done_rows = [t in eos_set for t in first_h]
+            done = 0
+            torch.cuda.current_stream().synchronize()
+            with torch.cuda.stream(st.stream):
+                while done < n_steps and not all(done_rows):
+                    chunk = min(16, n_steps - done)
+                    if use_graph:
+                        _replay(st, chunk)
+                    else:
+                        for _ in range(chunk):
+                            self._batch_step(st)
+                    done += chunk
+                    got = st.out_ids[:Bn, :done].tolist()
+                    done_rows = [first_h[b] in eos_set or any(t in eos_set for t in got[b]) for b in range(Bn)]
+            st.stream.synchronize()
+            toks = torch.cat([first[:, None], st.out_ids[:Bn, :done]], 1)
+            out = finish_rows(toks.tolist(), eos_set, _pad_id(pad_token_id, eos_token_id, self.lcfg.eos_token_id), dev)
+            if logprobs is not None:
+                cut = [len(_cut_at_eos(row, eos_set)) for row in toks.tolist()]
+                return out, self._pack_logprobs([self._row_logprobs(st, b, done) for b in range(Bn)], cut, out.shape[1], logprobs, dev)
+            return out
+        finally:
+            self.batch_release(st, range(st.pos.numel()))
+
     def _fresh_seed(self) -> int:
         """The seed of a sampled request that names none: torch's initial seed stepped once per request."""
         self._sample_calls += 1
@@ -1496,7 +1692,8 @@ class HipQwen2ForCausalLM(_HipModule):
                  prompt_ids: Optional[torch.Tensor] = None, draft_ids: Optional[torch.Tensor] = None, past_len: Optional[int] = None,
                  prefill_chunk: Optional[int] = None, spec_sample: Optional[bool] = None, num_return_sequences: Optional[int] = None,
                  repetition_penalty: Optional[float] = None, presence_penalty: Optional[float] = None, frequency_penalty: Optional[float] = None,
-                 logprobs: Optional[int] = None, constraint=None, any_top_k: Optional[bool] = None, spec_processed: Optional[bool] = None, **kw):
+                 logprobs: Optional[int] = None, constraint=None, any_top_k: Optional[bool] = None, spec_processed: Optional[bool] = None,
+                 adapter=None, adapters=None, **kw):
         """`llm.generate(inputs_embeds=, attention_mask=, **generation_kwargs)` as called at llava_arch.py:833 (HF semantics: returns ONLY the
         new tokens, [B, n_new]).  Greedy search or sampling (do_sample: temperature / top_k / top_p, HF order, on the device); explicit
         keyword arguments override `generation_config` (HF GenerationConfig-like: do_sample, temperature, top_k, top_p, max_new_tokens,
@@ -1565,7 +1762,22 @@ class HipQwen2ForCausalLM(_HipModule):
         up to it and masked from the automaton's state behind them, the table and the state are committed behind the accept for the accepted
         rows only, and every emitted token gets its RAW record.  The ids (and the records) are bit for bit those of the same session drafting
         nothing.  With logprobs the call returns (ids, `Logprobs`), as the solo path does.  Batch 1; bf16 or W4; the flags enter the session key,
-        the values and the automaton do not."""
+        the values and the automaton do not.
+        adapters=bank (a `vila_amd.lora_serving.AdapterBank`; None = off, today's call) with adapter = the name of a loaded adapter, or one name /
+        None per row: the 1..16 rows run under their adapters UNMERGED, through a batched session with the bank (`batch_open(adapters=)`; one row is
+        a session of one live row) — the base weights stay as they are and rows of different adapters share every weight pass.  Prefill is one packed
+        call per adapter; a row with None is the base model.  Served where the batched step is (bf16, head_dim 128, no cache=; sampling needs
+        batch_sample=True with top_k in 1..64, or any_top_k), with penalties, logprobs, constraint, forced_ids and return_logits; anything else
+        raises a ValueError.  Speculative decoding, past_len, prefill_chunk and num_return_sequences have no adapter form."""
+        if adapter is not None or adapters is not None:
+            if adapters is None:
+                raise ValueError("generate(adapter=): pass the AdapterBank that holds the adapter as adapters=")
+            gc_ = generation_config
+            if (past_len is not None or prefill_chunk is not None or prompt_lookup_num_tokens is not None or draft_ids is not None or spec_sample or
+                    (num_return_sequences is not None and int(num_return_sequences) != 1) or streamer is not None or
+                    (gc_ is not None and getattr(gc_, "prompt_lookup_num_tokens", None) is not None)):
+                raise ValueError("generate(adapters=): speculative decoding, past_len, prefill_chunk, num_return_sequences and streamer have no form under "
+                                 "an unmerged adapter")
         self._check_append_args(inputs_embeds, cache, past_len, prefill_chunk)
         spec_processed = bool(spec_processed if spec_processed is not None else
                               (getattr(generation_config, "spec_processed", None) if generation_config is not None else False) or False)
@@ -1657,6 +1869,26 @@ class HipQwen2ForCausalLM(_HipModule):
         if constraint is not None:                                     # (likewise)
             pen_kw = dict(pen_kw, constraint=constraint)
         processed = penalties is not None or constraint is not None    # (a constrained greedy batch returns its logits through the batched step too)
+        if adapters is not None:
+            Bn = inputs_embeds.shape[0]
+            names = list(adapter) if isinstance(adapter, (list, tuple)) else [adapter] * Bn
+            if len(names) != Bn:
+                raise ValueError(f"generate(adapter=): {len(names)} adapter names for {Bn} rows")
+            for nm in names:
+                adapters.slot_of(nm)                                   # (raises for a name that is not loaded)
+            # what `_can_batch_decode` asks of a batch, on 1..16 rows (it asks for 2..16: one row joins a session of two)
+            probe = inputs_embeds if Bn > 1 else inputs_embeds.expand(2, -1, -1)
+            if self._w4 is not None or not self._can_batch_decode(probe, attention_mask, max_new_tokens, do_sample, None, False, cache, batch_sample, top_k,
+                                                                 **(dict(any_top_k=True) if any_top_k else {})):
+                raise ValueError("generate(adapters=): rows under unmerged adapters run through the batched step — 1..16 rows of a bf16 head-dim-128 "
+                                 "model, no cache=, and for do_sample batch_sample=True with top_k in 1..64 (any top_k with any_top_k=True)")
+            rows = None
+            if do_sample:
+                if seed is None:
+                    seed = self._fresh_seed()
+                rows = [(temperature, top_k, top_p, (int(seed) + b) & 0xFFFFFFFFFFFFFFFF) for b in range(Bn)]
+            return self._generate_batch(inputs_embeds, attention_mask, max_new_tokens, eos_token_id, pad_token_id, use_graph, forced_ids, return_logits,
+                                        sampling=rows, **pen_kw, **(dict(any_top_k=True) if any_top_k else {}), adapter=names, adapters=adapters)
         if inputs_embeds.shape[0] > 1 and self._can_batch_decode(inputs_embeds, attention_mask, max_new_tokens, do_sample,
                                                                  forced_ids if not processed else None, return_logits and not processed, cache,
                                                                  batch_sample, top_k, **(dict(any_top_k=True) if any_top_k else {})):

@@ -268,6 +268,103 @@ def qkv_batch(x: torch.Tensor, wqkv: torch.Tensor, bias: Optional[torch.Tensor],
     return q_out
 
 
+def _addend_args(addend, row_adapter, n: int, width: int, what: str):
+    """(addend pointer, row stride, row_adapter pointer) of an entry that takes the adapters' fp32 addend [>= n, width] and the rows' slots [>= n] int32."""
+    if addend is None:
+        return None, 0, _p(row_adapter)
+    _need(addend, dtype=torch.float32, name="addend")
+    assert addend.dim() == 2 and addend.stride(1) == 1 and addend.shape[1] == width and addend.shape[0] >= min(n, 16), what
+    if row_adapter is not None:
+        _need(row_adapter, dtype=torch.int32, name="row_adapter"); assert row_adapter.numel() >= min(n, 16)
+    return addend.data_ptr(), addend.stride(0), _p(row_adapter)
+
+
+def gemm_batch_lora(x: torch.Tensor, w: torch.Tensor, addend: Optional[torch.Tensor], row_adapter: Optional[torch.Tensor],
+                    w2: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
+                    out: Optional[torch.Tensor] = None, out_f32: Optional[torch.Tensor] = None, n: Optional[int] = None) -> Optional[torch.Tensor]:
+    """gemm_batch with the fp32 addend of a step with per-row adapters (vila_gemm_batch_lora_bf16; with w2 vila_gateup_batch_lora_bf16): addend
+    [>= n, N] (gate/up: [>= n, 2 N], gate | up) joins the fp32 sum in front of the bias and the first rounding; a row with row_adapter[m] < 0 skips
+    the add.  addend None launches gemm_batch's kernels."""
+    _need(x, name="x"); _need(w, name="w")
+    assert x.dim() == 2 and w.dim() == 2 and x.stride(1) == 1 and w.is_contiguous() and (w2 is None or (w2.is_contiguous() and w2.shape == w.shape))
+    if x.shape[1] != w.shape[1]:
+        raise ValueError(f"gemm_batch_lora: x has {x.shape[1]} columns, the matrix {w.shape[1]}")
+    n = x.shape[0] if n is None else n
+    N, K = w.shape
+    if out is None and out_f32 is None:
+        out = torch.empty((n, N), device=x.device, dtype=torch.bfloat16)
+    for t, dt, name in ((out, torch.bfloat16, "out"), (out_f32, torch.float32, "out_f32"), (residual, torch.bfloat16, "residual")):
+        if t is not None:
+            _need(t, dtype=dt, name=name); assert t.dim() == 2 and t.stride(1) == 1 and t.shape[1] == N and t.shape[0] >= min(n, 16)
+    ld = lambda t: 0 if t is None else t.stride(0)
+    ap, lda, rp = _addend_args(addend, row_adapter, n, 2 * N if w2 is not None else N, "gemm_batch_lora")
+    if w2 is not None:
+        assert bias is None and residual is None and out_f32 is None, "gate/up takes no bias, residual or fp32 output"
+        check(_lib.load().vila_gateup_batch_lora_bf16(x.data_ptr(), x.stride(0), n, w.data_ptr(), w2.data_ptr(), out.data_ptr(), ld(out), N, K, ap, lda, rp,
+                                                      _stream()), "gemm_batch_lora")
+    else:
+        check(_lib.load().vila_gemm_batch_lora_bf16(x.data_ptr(), x.stride(0), n, w.data_ptr(), _p(bias), _p(residual), ld(residual), _p(out), ld(out),
+                                                    _p(out_f32), ld(out_f32), N, K, ap, lda, rp, _stream()), "gemm_batch_lora")
+    return out if out is not None else out_f32
+
+
+def qkv_batch_lora(x: torch.Tensor, wqkv: torch.Tensor, bias: Optional[torch.Tensor], q_out: torch.Tensor, kcache: torch.Tensor, vcache: torch.Tensor,
+                   pos: torch.Tensor, rope_cs: torch.Tensor, q_heads: int, kv_heads: int, head_dim: int, addend: Optional[torch.Tensor],
+                   row_adapter: Optional[torch.Tensor], n: Optional[int] = None) -> torch.Tensor:
+    """qkv_batch with the adapters' fp32 addend [>= n, (q + 2 kv) * head_dim] in front of the bias, RoPE and the cache append (vila_qkv_batch_lora_bf16)."""
+    _need(x, name="x"); _need(wqkv, name="wqkv"); _need(q_out, name="q_out"); _need(kcache, name="kcache"); _need(vcache, name="vcache")
+    _need(pos, dtype=torch.int32, name="pos"); _need(rope_cs, dtype=torch.float32, name="rope_cs")
+    assert x.dim() == 2 and x.stride(1) == 1 and wqkv.is_contiguous() and q_out.dim() == 2 and q_out.stride(1) == 1
+    if x.shape[1] != wqkv.shape[1]:
+        raise ValueError(f"qkv_batch_lora: x has {x.shape[1]} columns, the matrix {wqkv.shape[1]}")
+    n = x.shape[0] if n is None else n
+    assert wqkv.shape[0] == (q_heads + 2 * kv_heads) * head_dim and q_out.shape[1] == q_heads * head_dim and q_out.shape[0] >= min(n, 16)
+    assert kcache.dim() == 4 and kcache.shape == vcache.shape and kcache.shape[1:] == (kv_heads, kcache.shape[2], head_dim) and kcache.shape[0] >= min(n, 16)
+    assert kcache[0].is_contiguous() and vcache[0].is_contiguous() and kcache.stride(0) == vcache.stride(0)
+    assert pos.numel() >= min(n, 16) and rope_cs.is_contiguous() and rope_cs.numel() >= min(n, 16) * head_dim
+    ap, lda, rp = _addend_args(addend, row_adapter, n, wqkv.shape[0], "qkv_batch_lora")
+    check(_lib.load().vila_qkv_batch_lora_bf16(x.data_ptr(), x.stride(0), n, wqkv.data_ptr(), _p(bias), q_out.data_ptr(), q_out.stride(0), kcache.data_ptr(),
+                                               vcache.data_ptr(), kcache.stride(0), pos.data_ptr(), rope_cs.data_ptr(), q_heads, kv_heads, head_dim,
+                                               kcache.shape[2], x.shape[1], ap, lda, rp, _stream()), "qkv_batch_lora")
+    return q_out
+
+
+def lora_shrink(x: torch.Tensor, a_bank: torch.Tensor, scale: torch.Tensor, row_adapter: torch.Tensor, out: torch.Tensor,
+                n: Optional[int] = None) -> torch.Tensor:
+    """The shrink of the step with per-row adapters (vila_lora_shrink_bf16): x [n, K] bf16, a_bank [capacity, Rs, K] bf16 (slots may be strided),
+    scale [capacity] fp32, row_adapter [n] int32 -> out [>= n, Rs] fp32 = scale[a] * x_i . A_a^T with a = row_adapter[i]; +0.0 for a row without."""
+    _need(x, name="x"); _need(a_bank, name="a_bank"); _need(scale, dtype=torch.float32, name="scale"); _need(row_adapter, dtype=torch.int32, name="row_adapter")
+    _need(out, dtype=torch.float32, name="out")
+    assert x.dim() == 2 and x.stride(1) == 1 and a_bank.dim() == 3 and a_bank[0].is_contiguous() and out.dim() == 2 and out.stride(1) == 1
+    cap, Rs, K = a_bank.shape
+    if x.shape[1] != K:
+        raise ValueError(f"lora_shrink: x has {x.shape[1]} columns, the bank's A {K}")
+    n = x.shape[0] if n is None else n
+    assert out.shape[1] == Rs and out.shape[0] >= min(n, 16) and scale.numel() >= cap and row_adapter.numel() >= min(n, 16)
+    check(_lib.load().vila_lora_shrink_bf16(x.data_ptr(), x.stride(0), n, a_bank.data_ptr(), a_bank.stride(0), scale.data_ptr(), row_adapter.data_ptr(), cap,
+                                            out.data_ptr(), out.stride(0), Rs, K, _stream()), "lora_shrink")
+    return out
+
+
+def lora_expand(t: torch.Tensor, b_bank: torch.Tensor, row_adapter: torch.Tensor, out: torch.Tensor, c1: Optional[int] = None, c2: Optional[int] = None,
+                n: Optional[int] = None) -> torch.Tensor:
+    """The expand of the step with per-row adapters (vila_lora_expand_f32): t [n, segments * r] fp32, b_bank [capacity, r / 8, N, 8] bf16 (lora_B of
+    the stack's members side by side, chunk-major), row_adapter [n] int32 -> out [>= n, N] fp32.  Columns [0, c1) read t[:, 0:r], [c1, c2) t[:, r:2r],
+    [c2, N) t[:, 2r:3r]; c1 = c2 = N (the default): one member."""
+    _need(t, dtype=torch.float32, name="t"); _need(b_bank, name="b_bank"); _need(row_adapter, dtype=torch.int32, name="row_adapter")
+    _need(out, dtype=torch.float32, name="out")
+    assert t.dim() == 2 and t.stride(1) == 1 and b_bank.dim() == 4 and b_bank.shape[3] == 8 and b_bank[0].is_contiguous() and out.dim() == 2 and out.stride(1) == 1
+    cap, chunks, N, _ = b_bank.shape
+    c1 = N if c1 is None else int(c1)
+    c2 = N if c2 is None else int(c2)
+    n = t.shape[0] if n is None else n
+    assert out.shape[1] == N and out.shape[0] >= min(n, 16) and row_adapter.numel() >= min(n, 16)
+    assert t.shape[1] == (1 + (c1 < N) + (c2 < N)) * chunks * 8, "t holds one r-wide slice per member of the stack"
+    check(_lib.load().vila_lora_expand_f32(t.data_ptr(), t.stride(0), n, b_bank.data_ptr(), b_bank.stride(0), row_adapter.data_ptr(), cap, out.data_ptr(),
+                                           out.stride(0), N, chunks * 8, c1, c2, _stream()), "lora_expand")
+    return out
+
+
 def gemm_w4(x: torch.Tensor, mat, bias: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
             out: Optional[torch.Tensor] = None, heads: Optional[tuple] = None, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
     """W4A16 GEMM (prefill shapes) on a vila_amd.quant.W4Matrix: x [M, K] bf16 -> [M, N] bf16 = x . W^T (+bias)(+residual); gate/up

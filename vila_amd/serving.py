@@ -783,12 +783,18 @@ class HipBatchEngine:
     automaton (cached per vocabulary), `admit` takes it, and a `ContinuousBatcher(constraints=True)` puts such requests into rows.  compiler: the
     `ConstraintCompiler` to use in place of the one derived from a byte-level BPE tokenizer.
     any_top_k=True (with sampling=True) opens the session with `batch_open(any_top_k=True)`: a sampled row may then carry any top_k >= 0 (0 = no
-    top-k filter, i.e. pure top-p sampling; k > 64), and a `ContinuousBatcher(batch_sampled=True, any_top_k=True)` puts such requests into rows."""
+    top-k filter, i.e. pure top-p sampling; k > 64), and a `ContinuousBatcher(batch_sampled=True, any_top_k=True)` puts such requests into rows.
+    adapters=bank (a `vila_amd.lora_serving.AdapterBank`) opens the session with `batch_open(adapters=bank)`: `admit(..., adapter=name)` prefills the
+    request under that LoRA adapter, unmerged, and its row steps under it; `embed(..., adapter=name)` encodes the media through the adapter's tuned
+    projector where it has one.  A `ContinuousBatcher(adapters=True)` routes requests by their `model` field.  Not with share_prefix."""
 
     def __init__(self, model, tokenizer, n_slots: int = 8, max_ctx: int = 2048, max_new_tokens: int = 1024, eos_token_id=None,
                  sampling: bool = False, share_prefix: bool = False, min_shared_len: int = 2048, penalties: bool = False, logprobs: bool = False,
-                 constraints: bool = False, max_states: int = 512, max_classes: int = 4096, compiler=None, any_top_k: bool = False):
+                 constraints: bool = False, max_states: int = 512, max_classes: int = 4096, compiler=None, any_top_k: bool = False, adapters=None):
         self.model, self.tokenizer = model, tokenizer
+        self.adapters = adapters                            # batch_open(adapters=bank): `admit` takes the name of a row's adapter
+        if adapters is not None and share_prefix:
+            raise ValueError("HipBatchEngine: adapters= is not served together with share_prefix (the step with adapters has no shared-prefix form)")
         self.sampling = bool(sampling)
         self.any_top_k = bool(any_top_k) and self.sampling  # batch_open(any_top_k=True): a sampled row's top_k may be 0 or above 64
         self.constraints = bool(constraints)                # batch_open(constraints=True, max_states=, max_classes=): `admit` takes a row's automaton
@@ -822,6 +828,8 @@ class HipBatchEngine:
                 kw["logprobs"] = True
             if self.constraints:
                 kw.update(constraints=True, max_states=self.max_states, max_classes=self.max_classes)
+            if self.adapters is not None:
+                kw["adapters"] = self.adapters
             self.st = llm.batch_open(self.n_slots, self.max_ctx, self.max_new_tokens, **kw)
         return self.st
 
@@ -904,6 +912,15 @@ class HipBatchEngine:
         """Whether a request with `response_format` / `guided_choice` / `guided_regex` can take a row of this engine's batch."""
         return self.constraints
 
+    @property
+    def batches_adapters(self) -> bool:
+        """Whether a request under a LoRA adapter of the engine's bank can take a row of this engine's batch."""
+        return self.adapters is not None
+
+    def has_adapter(self, name) -> bool:
+        """Whether `name` is an adapter loaded into the engine's bank."""
+        return self.adapters is not None and name in self.adapters
+
     def compile_constraint(self, asks):
         """The automaton of a request's structured-output fields (`structured_of`), compiled for this engine's vocabulary within its rows' table; a
         ValueError where the schema or pattern is not served, the vocabulary cannot spell it, or it does not fit."""
@@ -926,9 +943,10 @@ class HipBatchEngine:
     def fits(self, n_prompt_tokens: int, max_new_tokens: int) -> bool:
         return max_new_tokens <= self.max_new_tokens and n_prompt_tokens + max_new_tokens <= self.max_ctx
 
-    def embed(self, prompt, system, prep=None):
+    def embed(self, prompt, system, prep=None, adapter=None):
         """Prompt -> spliced embeddings [S, H] on the device (tower + projector + splice run here, on the worker thread).  prep: what `prepare`
-        returned for this request, so that its media is not loaded and tiled again."""
+        returned for this request, so that its media is not loaded and tiled again.  adapter: the request's adapter, whose tuned projector (if it
+        keeps one) encodes the media."""
         cfg = self.model.cfg
         dev = str(self.model.device)
         if prep is None:
@@ -937,11 +955,13 @@ class HipBatchEngine:
         else:
             ids, tiles, media_config = prep.ids, prep.tiles, prep.media_config
         media = {"image": [t.to(device=dev, dtype=torch.bfloat16) for t in tiles]}
-        e, _, _ = self.model._embed(ids[None].to(dev), media, media_config)
+        e, _, _ = self.model._embed(ids[None].to(dev), media, media_config, **({} if adapter is None else dict(adapter=adapter, adapters=self.adapters)))
         return e[0]
 
-    def admit(self, slot: int, embeds, sampling=None, share: bool = False, first_row: int = 0, penalties=None, constraint=None) -> int:
+    def admit(self, slot: int, embeds, sampling=None, share: bool = False, first_row: int = 0, penalties=None, constraint=None, adapter=None) -> int:
         kw = {} if sampling is None else dict(sampling=sampling)
+        if adapter is not None:
+            kw.update(adapter=adapter)
         if constraint is not None:
             kw.update(constraint=constraint)
         if share:
@@ -1001,13 +1021,20 @@ class ContinuousBatcher:
     constraints=True (opt-in; needs an engine whose `batches_constraints` is true, i.e. `HipBatchEngine(constraints=True)`): a request submitted
     with `response_format`, `guided_choice` or `guided_regex` that is otherwise batchable takes a row: its automaton is compiled on the worker thread
     (`engine.compile_constraint`; a compile error fails that request alone) and handed to `engine.admit`.  Without the flag such a request runs solo
-    (`engine.solo` gets the field).  With a `stream` it is refused.  A request that does not ask is served exactly as before."""
+    (`engine.solo` gets the field).  With a `stream` it is refused.  A request that does not ask is served exactly as before.
+    adapters=True (opt-in; needs an engine whose `batches_adapters` is true, i.e. `HipBatchEngine(adapters=bank)`): a request submitted with
+    model=name, name an adapter loaded into the engine's bank (`engine.has_adapter`), takes a row under that adapter, unmerged — vLLM's convention
+    for its `model` field; requests under different adapters and base requests share every step.  Any other `model` value, and every `model` value
+    without the flag, is dropped: the request is the base model's, served exactly as before.  A request under an adapter never runs solo (a solo
+    run would need a second session, which evicts the batcher's): one the session cannot take as a row — it samples without batch_sampled, asks
+    for penalties, logprobs or structured output without that flag, or does not fit a slot — fails with a ValueError that names what is missing."""
 
     def __init__(self, engine, max_batch: int = 8, chunk: int = 8, batch_sampled: bool = False, share_prefix: bool = False, penalties: bool = False,
-                 logprobs: bool = False, constraints: bool = False, any_top_k: bool = False):
+                 logprobs: bool = False, constraints: bool = False, any_top_k: bool = False, adapters: bool = False):
         import queue
         import threading
         self.engine = engine
+        self.adapters = bool(adapters) and bool(getattr(engine, "batches_adapters", False))
         self.batch_sampled = bool(batch_sampled) and bool(getattr(engine, "batches_sampled", False))
         self.any_top_k = bool(any_top_k) and self.batch_sampled and bool(getattr(engine, "batches_any_top_k", False))
         self.penalties = bool(penalties) and bool(getattr(engine, "batches_penalties", False))
@@ -1034,6 +1061,10 @@ class ContinuousBatcher:
         `fail()` with the exception the future gets."""
         from concurrent.futures import Future
         f: Future = Future()
+        if "model" in gen:                                                 # (only a loaded adapter's name routes; anything else is the base model)
+            name = gen.pop("model")
+            if self.adapters and name is not None and self.engine.has_adapter(name):
+                gen["adapter"] = name
         req = SimpleNamespace(prompt=prompt, max_new=int(max_new_tokens), system=system, gen=gen, fut=f, stream=stream)
         try:
             _logprobs_of(gen.get("logprobs"), gen.get("top_logprobs"))     # a bad pair fails the request here, not after its row has run
@@ -1106,6 +1137,23 @@ class ContinuousBatcher:
             return False                                                # ... and so does one that asks for logprobs
         return self._greedy(req) or self._row_sampling(req) is not None
 
+    def _adapter_refusal(self, req) -> Optional[str]:
+        """Why a request under an adapter cannot take a row of this batcher's session (it never runs solo), or None."""
+        what = None
+        if structured_of(req.gen) and not self.constraints:
+            what = "structured output needs create_app(constraints=True) / ContinuousBatcher(constraints=True)"
+        elif self._row_penalties(req) is not None and not self.penalties:
+            what = "penalties need create_app(penalties=True) / ContinuousBatcher(penalties=True)"
+        elif req.gen.get("logprobs") and not self.logprobs:
+            what = "logprobs need create_app(logprobs=True) / ContinuousBatcher(logprobs=True)"
+        elif not self._greedy(req) and not self.batch_sampled:
+            what = "a sampled request (temperature > 0) needs create_app(batch_sampled=True) / ContinuousBatcher(batch_sampled=True)"
+        elif not self._greedy(req) and self._row_sampling(req) is None:
+            what = "top_k = 0 or > 64 needs create_app(any_top_k=True) / ContinuousBatcher(any_top_k=True)"
+        if what is None:
+            return None
+        return f"a request under the adapter '{req.gen['adapter']}' is served as a row of the batched session only, and {what}"
+
     @staticmethod
     def _fail(req, ex) -> None:
         if getattr(req, "_failed", False):               # (a dying worker's drain and `submit`'s re-check may both reach a request)
@@ -1149,6 +1197,9 @@ class ContinuousBatcher:
         holds; the pin itself when no live row shares the current prefix, the request fits a slot and the engine finds the prefix worth pinning;
         an ordinary row otherwise.  What does not fit is decided before anything is pinned: the caller then sends it solo, as ever."""
         eng = self.engine
+        if req.gen.get("adapter") is not None:                         # (an engine with adapters shares no prefix)
+            e = eng.embed(req.prompt, req.system, adapter=req.gen["adapter"])
+            return e, int(e.shape[0]), dict(adapter=req.gen["adapter"])
         if not self.share_prefix:
             e = eng.embed(req.prompt, req.system)
             return e, int(e.shape[0]), {}
@@ -1218,10 +1269,16 @@ class ContinuousBatcher:
                     req = pending[0]
                     slot = None                                        # the KV slot this admission took, if it got that far
                     try:
+                        under = req.gen.get("adapter")                 # a request under an adapter takes a row or fails: it never runs solo
+                        if under is not None and self._adapter_refusal(req) is not None:
+                            raise ValueError(self._adapter_refusal(req))
                         if not self._batchable(req) or req.gen.get("_solo"):
                             break
                         e, n_prompt, how = self._embed_for(req, free[0])
                         if not eng.fits(n_prompt, req.max_new) or req.max_new < 1:
+                            if under is not None:
+                                raise ValueError(f"a request under the adapter '{under}' is served as a row of the batched session only, and its "
+                                                 f"{n_prompt} prompt positions + {req.max_new} new tokens do not fit a slot (create_app(max_ctx=))")
                             req.gen = dict(req.gen, _solo=True)
                             break
                         pending.popleft()
@@ -1234,8 +1291,8 @@ class ContinuousBatcher:
                         if con is not None:                            # (likewise)
                             how = dict(how, constraint=con)
                         first = eng.admit(slot, e, **how) if sampling is None else eng.admit(slot, e, sampling, **how)
-                        if pen is not None or con is not None:
-                            how = {k: v for k, v in how.items() if k not in ("penalties", "constraint")}
+                        if pen is not None or con is not None or under is not None:
+                            how = {k: v for k, v in how.items() if k not in ("penalties", "constraint", "adapter")}
                         if how:
                             self._pin_rows.add(slot)
                         row = SimpleNamespace(req=req, toks=[first], read=0, sent=0, closed=False)
@@ -1347,7 +1404,8 @@ def continuous_batching(model) -> bool:
 def create_app(model, tokenizer, model_name: str = "NVILA-8B", batch_window_s: Optional[float] = None, max_batch: int = 8,
                stream_timeout_s: Optional[float] = 600.0, batch_sampled: bool = False, max_ctx: int = 2048,
                prompt_lookup_num_tokens: Optional[int] = None, spec_sample: bool = False, share_prefix: bool = False, penalties: bool = False,
-               logprobs: bool = False, constraints: bool = False, any_top_k: bool = False, spec_processed: bool = False):
+               logprobs: bool = False, constraints: bool = False, any_top_k: bool = False, spec_processed: bool = False, adapters=None,
+               max_adapters: int = 4):
     """FastAPI app with the reference's POST /chat/completions (server.py:171-290).  Import-time optional: needs fastapi + pydantic.
     batch_window_s: when set (any value), requests go through a batcher whose ONE worker thread owns the model: `ContinuousBatcher` (greedy
     requests join / leave the batched decode step between steps; sampled ones run solo on the same thread) where the model has the batched
@@ -1387,7 +1445,25 @@ def create_app(model, tokenizer, model_name: str = "NVILA-8B", batch_window_s: O
     request with top_k = 0 or > 64 takes a row; without it such a request runs solo, as a penalised one does without `penalties=`.  With
     spec_sample (and prompt_lookup_num_tokens) it lets solo sampled requests with such a top_k speculate as well.
     spec_processed=True (default off; with prompt_lookup_num_tokens): penalised, logprob and structured requests that this app runs solo speculate
-    as well (`generate_content(spec_processed=True)`) instead of dropping the drafts; their replies are those of the same requests without drafts."""
+    as well (`generate_content(spec_processed=True)`) instead of dropping the drafts; their replies are those of the same requests without drafts.
+    adapters={"name": folder, ...} (default None; needs batch_window_s and a model with the batched step, i.e. the ContinuousBatcher; bf16, not with
+    share_prefix): the LoRA adapters of the folders (written by `save_adapter`) are loaded into an `AdapterBank` of max_adapters slots beside the
+    untouched base model, and a request whose `model` field names one of them takes a row of the batched session under it, unmerged — vLLM's
+    convention; requests under different adapters and base requests share every weight pass.  Any other `model` value is served byte for byte as
+    before.  An adapter request that the session cannot take as a row (e.g. a sampled one without batch_sampled) comes back as the usual 500 body
+    naming the missing flag; it does not run solo, because a second session would evict the batcher's."""
+    bank = None
+    if adapters:
+        if batch_window_s is None or not continuous_batching(model):
+            raise ValueError("create_app(adapters=): adapters are served as rows of the batched session; pass batch_window_s and a model that has the "
+                             "batched decode step (bf16, head_dim 128)")
+        from .lora_serving import AdapterBank
+        ranks = [int(json.load(open(os.path.join(str(f), "adapter_config.json")))["r"]) for f in adapters.values()]
+        bank = AdapterBank(model, capacity=max(int(max_adapters), 1), r=max(ranks))
+        for name, folder in adapters.items():
+            if name == model_name:
+                raise ValueError(f"create_app(adapters=): '{name}' is the base model's name")
+            bank.load(name, folder)
     from fastapi import FastAPI
     from fastapi.responses import JSONResponse, StreamingResponse
 
@@ -1413,14 +1489,18 @@ def create_app(model, tokenizer, model_name: str = "NVILA-8B", batch_window_s: O
                 kw["constraints"] = True
             if any_top_k and batch_sampled:
                 kw["any_top_k"] = True
+            if bank is not None:
+                kw["adapters"] = bank
             engine = HipBatchEngine(model, tokenizer, **kw)
             batcher = ContinuousBatcher(engine, max_batch=max_batch, batch_sampled=batch_sampled, **(dict(share_prefix=True) if share_prefix else {}),
                                         **(dict(penalties=True) if penalties else {}), **(dict(logprobs=True) if logprobs else {}),
                                         **(dict(constraints=True) if constraints else {}),
-                                        **(dict(any_top_k=True) if any_top_k and batch_sampled else {}))
+                                        **(dict(any_top_k=True) if any_top_k and batch_sampled else {}),
+                                        **(dict(adapters=True) if bank is not None else {}))
         else:
             batcher = RequestBatcher(model, tokenizer, window_s=batch_window_s)
     app.state.batcher = batcher
+    app.state.adapters = bank
 
     def _prompt_of(messages):
         parts: List[Any] = []
@@ -1468,7 +1548,8 @@ def create_app(model, tokenizer, model_name: str = "NVILA-8B", batch_window_s: O
     async def chat_completions(request):
         import asyncio
         try:
-            if request.model != model_name:
+            under = request.model if bank is not None and request.model in bank else None     # vLLM's convention: `model` names a loaded adapter
+            if under is None and request.model != model_name:
                 raise ValueError(f"The endpoint is configured to use the model {model_name}, but the request model is {request.model}")
             parts, system = _prompt_of(request.messages)
             temperature = request.temperature if request.temperature is not None else 0.2
@@ -1493,6 +1574,8 @@ def create_app(model, tokenizer, model_name: str = "NVILA-8B", batch_window_s: O
                     raise ValueError(f"`top_k` has to be a non-negative integer (0 or -1: no top-k filter), but is {request.top_k}")
                 if temperature and temperature > 0:
                     pen = dict(pen, top_k=top_k)
+            if under is not None:                                     # (the key travels only for a request under an adapter)
+                pen = dict(pen, model=under)
             loop = asyncio.get_running_loop()
             if request.stream:
                 # server.py:241-270: the reply leaves as it is generated.  The tokens reach a `TextStream` from whoever runs the request (the

@@ -159,7 +159,8 @@ class HipLlavaLlamaModel(nn.Module):
         return self.vision_tower
 
     def get_mm_projector(self):
-        return self.mm_projector
+        # (inside `_embed(adapter=)`: the tuned projector kept with that adapter of the serving bank)
+        return self.__dict__.get("_adapter_projector") or self.mm_projector
 
     def load_weights(self, w: Dict[str, torch.Tensor]) -> None:
         self.llm.load_weights(w, "llm.")
@@ -193,7 +194,17 @@ class HipLlavaLlamaModel(nn.Module):
 
     # llava_arch.py:412-490 + 528-555
     def _embed(self, input_ids: torch.Tensor, media: Dict[str, List[torch.Tensor]], media_config: Optional[Dict[str, Dict[str, Any]]] = None,
-               labels: Optional[torch.Tensor] = None, attention_mask: Optional[torch.Tensor] = None, max_length: Optional[int] = None):
+               labels: Optional[torch.Tensor] = None, attention_mask: Optional[torch.Tensor] = None, max_length: Optional[int] = None,
+               adapter: Optional[str] = None, adapters=None):
+        """adapter=name with adapters=bank (`vila_amd.lora_serving.AdapterBank`): the media are encoded through the tuned projector the bank keeps
+        with that adapter, if it has one (an adapter trained with tune_mm_projector=True); the base model's otherwise."""
+        tuned = adapters.projector(adapter) if adapters is not None and adapter is not None else None
+        if tuned is not None:
+            self.__dict__["_adapter_projector"] = tuned
+            try:
+                return self._embed(input_ids, media, media_config, labels, attention_mask, max_length)
+            finally:
+                self.__dict__.pop("_adapter_projector", None)
         dev = self.device
         media_config = media_config or {}
         # The integer work of the splice runs on the HOST while the tower runs on the GPU: ids / mask / labels are brought over
@@ -301,7 +312,16 @@ class HipLlavaLlamaModel(nn.Module):
     def generate(self, input_ids: Optional[torch.Tensor] = None, media: Optional[Dict[str, List[torch.Tensor]]] = None,
                  media_config: Optional[Dict[str, Dict[str, Any]]] = None, attention_mask: Optional[torch.Tensor] = None,
                  **generation_kwargs):
-        inputs_embeds, _, attention_mask = self._embed(input_ids, media, media_config, None, attention_mask)
+        bank, names = generation_kwargs.get("adapters"), generation_kwargs.get("adapter")
+        embed_kw = {}
+        if bank is not None and names is not None:
+            # rows under adapters (llm.generate(adapter=, adapters=)): one projector encodes the whole call's media
+            rows = list(names) if isinstance(names, (list, tuple)) else [names]
+            if len({id(bank.projector(n)) for n in rows}) > 1:
+                raise ValueError("generate(adapter=[...]): the rows' adapters keep different tuned projectors; embed such requests one by one "
+                                 "(_embed(adapter=, adapters=)) and pass inputs_embeds to llm.generate")
+            embed_kw = dict(adapter=rows[0], adapters=bank)
+        inputs_embeds, _, attention_mask = self._embed(input_ids, media, media_config, None, attention_mask, **embed_kw)
         if getattr(attention_mask, "_vila_all_true", False):
             attention_mask = None                      # nothing is padded: the LLM need not compact rows (a device round trip) before the prefill
         gc = generation_kwargs.get("generation_config")
